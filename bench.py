@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — headline benchmark of the k-NN correspondence + ICP hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
         N = 1: runs in this process.  N > 1 without a launcher (WORLD_SIZE unset): starts its own ranks —
         `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py <same flags>` as a
         CHILD process before anything touches the GPU, and exits with the child's code (rank 0's JSON line goes to stdout).
@@ -11,6 +11,15 @@ A *step* is one point-to-point ICP iteration on the BASELINE.json configs[1]/[2]
 points against the 120 000-point target (exhaustive / brute force) + Kabsch accumulation + (N > 1: one RCCL all-reduce of
 56 + 2N f64) + 3x3 SVD + in-place transform.  W untimed iterations, then exactly K iterations timed between
 barrier + torch.cuda.synchronize() on both sides; max over ranks.
+
+A plain run (no --full) does only what the headline needs: set-up, the W + K steps, the outputs (--dump-outputs) and ONE short line with
+metric, value, unit, higher_is_better, dtype, ms_per_step (= the wall time of the K timed steps / K) and the workload's config.  Everything
+below `value` — roofline, kernels, one_shot, exact_grid, weak, predicted_scaling, cpu_baseline and the c4 / c5 blocks — is measured only
+with --full (--no-extras / --no-c4 / --no-c5 / --no-predict / --no-cpu-baseline trim that run).
+--dump-outputs DIR: after the timed steps, what the timed call returned, one DIR/<name>.npy per array (float32 / float64; inputs are
+                   seeded, so two builds can be compared output for output).  c2 / c5: pose (the 4x4 f32 pose after the last step) and the
+                   call's deterministic stats (iters_run, converged, empty_pairs, last_pairs, last_loss); c4: the plane counts, the radius
+                   neighbour count per query and a fixed, seeded sample of the (index, distance) entries of the radius rows.
 
 value            = correspondences of the whole job per second (M corr/s) on ONE 120 000 x 120 000 pair; with N > 1 ranks the
                    120 000 sources are SHARDED N ways (contiguous blocks, target replicated): "scaling": "strong" — the reading of
@@ -22,8 +31,8 @@ roofline         = the dominant kernel (nn1_btrack_kernel, f16 form): matrix flo
 kernels          = the same for the exact-only kernel (9-op convention of SURVEY.md 8d) and the two HBM streaming kernels.
 one_shot         = the cold configs[1] search (no previous correspondences), fresh target and indexed target.
 c4 / c5          = BASELINE configs[3] (plane count + radius-NN on the 120k scan) and configs[4] (10 M x 10 M pair, exact grid,
-                   sources sharded) measured in the same invocation (--no-c4 / --no-c5 skip them; --workload c4|c5 makes one the
-                   headline instead).
+                   sources sharded) measured in the same --full invocation (--no-c4 / --no-c5 skip them; --workload c4|c5 makes one
+                   the headline instead).
 cpu_baseline     = the reference's own nanoflann 1-NN (oracle/_ref, kind "reference") or, if that binary is absent, the oracle's
                    scalar brute force (kind "port"), timed on this box's host cores (rank 0, N = 1 only).
 Inputs are resident in HBM before the timed region starts; data = synthetic (no dataset ships, no network).
@@ -151,6 +160,30 @@ def load_pmc(name, sha):
         return None
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def icp_outputs(np, T, st):
+    """what a caller of icp_point2point receives: the pose and the stats that do not depend on timing"""
+    out = {"pose": np.ascontiguousarray(T, np.float32)}
+    for k in ("iters_run", "converged", "empty_pairs", "last_pairs"):
+        out[k] = np.array([st[k]], np.float64)
+    out["last_loss"] = np.array([st["last_loss"]], np.float32)
+    return out
+
+
+def dump_outputs(np, path, arrays):
+    """--dump-outputs: one <path>/<name>.npy per array, float32 / float64 only, at most DUMP_LIMIT_BYTES in all"""
+    total = 0
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        total += a.nbytes
+    assert total <= DUMP_LIMIT_BYTES, f"outputs of {total} B exceed {DUMP_LIMIT_BYTES} B"
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 # ------------------------------------------------------------------------------------------------------------ main
 def main():
     ap = argparse.ArgumentParser()
@@ -171,7 +204,12 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-c4", action="store_true", help="skip the configs[3] block of the default line")
     ap.add_argument("--no-c5", action="store_true", help="skip the configs[4] block of the default line")
-    ap.add_argument("--no-extras", action="store_true", help="only the timed loop and its roofline (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: roofline, kernels, one-shot and grid searches, weak and predicted "
+                         "scaling, CPU baseline, the c4 / c5 blocks (off: the timed steps and the short line only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed call returned as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: only the timed loop and its roofline (profiling runs)")
     ap.add_argument("--c5-points", type=int, default=10_000_000)
     ap.add_argument("--tiles-per-slice", type=int, default=0)
     ap.add_argument("--variant", type=int, default=0, help="nn1 kernel variant (0 = library default; 1 FTRACK, 2 exact TRACK, 4 ETRACK, 6 BTRACK, 7 HTRACK)")
@@ -414,10 +452,13 @@ def main():
         ctx.tune("nn_method", 0)
         main_method = 1 if args.nn == "brute" else 2
         # the K timed steps run WITHOUT event pairs (a pair around every search costs ~10 us of stream time per step — 15 % of a 70 us iteration);
-        # the same K steps are then repeated with the pairs for the kernel's duration (roofline): same pose bits, `ms_per_step_with_event_pairs` beside it
+        # the same K steps are then repeated with the pairs for the kernel's duration (roofline, --full): same pose bits, `ms_per_step_with_event_pairs` beside it
         T, st, dt = timed_icp(cs, ct, main_method, src, prof=0)
-        Tp, stp, dt_pairs = timed_icp(cs, ct, main_method, src, prof=1)
-        assert np.array_equal(T.view(np.uint32), Tp.view(np.uint32)) and stp["iters_run"] == st["iters_run"]
+        if args.dump_outputs and rank == 0:
+            dump_outputs(np, args.dump_outputs, icp_outputs(np, T, st))
+        if args.full:
+            Tp, stp, dt_pairs = timed_icp(cs, ct, main_method, src, prof=1)
+            assert np.array_equal(T.view(np.uint32), Tp.view(np.uint32)) and stp["iters_run"] == st["iters_run"]
         nn_name = "nn1_brute" if args.nn == "brute" else "nn1_grid"
         nn_launches, nn_ms = ctx.prof_get(nn_name)
         family = ctx.mfma_check()["last_nn1_kernel"]        # which kernel family the library's dispatcher took for the timed searches
@@ -425,7 +466,7 @@ def main():
         n_q, n_t = src.shape[1], tgt.shape[1]
         pairs = float(n_q) * float(n_t)
         default_kernels = not args.variant
-        extras = not args.no_extras
+        extras = args.full and not args.no_extras
         bd = kernel_breakdown(cs, ct, main_method, min(args.steps, 10)) if extras else {}
 
         # ---- the shader clock the chip holds under the headline kernel's own load: s_memtime / s_memrealtime stamps of a diagnostics
@@ -449,7 +490,7 @@ def main():
         # ---- STRACK3 (the sign filter over three levels of bounding spheres): how many matrix instructions a search at the final pose executes — the last
         # search of a 9-iteration loop from that pose (the loop sorts its working cloud along the target's order, as the timed loop does), diagnostics launch
         s2_counts = None
-        if args.nn == "brute" and family == "strack3":
+        if args.full and args.nn == "brute" and family == "strack3":
             ctx.tune("nn_method", 1); ctx.tune("prof", 0)
             ctx.tune("grid_stats", 1)
             ctx.icp_point2point(cs, ct, init_T=T, max_corr=1.0, max_iter=9, eps=0.0)
@@ -554,10 +595,17 @@ def main():
         # what the 1 / 2 / 4 / 8 reading of the metric should show: every rank's shard timed on this one GPU (world == 1 only: no collective inside)
         pred_c2 = predicted_scaling(full_src, ct, main_method, args.steps, T) if (extras and world == 1 and not args.no_predict) else None
         # (grid_roofline runs ICP loops — collectives under world > 1 — so EVERY rank calls it, not only the one that prints)
-        groof_c2 = grid_roofline(ctx, pcr, np, cs, ct, T, n_q, n_t, kern_s, sha) if args.nn == "grid" else None
+        groof_c2 = grid_roofline(ctx, pcr, np, cs, ct, T, n_q, n_t, kern_s, sha) if (args.full and args.nn == "grid") else None
         if rank == 0:
             gt_err = float(np.linalg.norm(T.astype(np.float64) - synth.gt_pose()))
             if args.nn == "brute":
+                workload = (f"point-to-point ICP iteration = exhaustive 1-NN correspondence of ONE {n} x {n_t} pair + Kabsch + transform; BASELINE.json "
+                            "configs[1]/[2] ('LDS-tiled brute force': the default kernel stages the target's matrix-core operands through LDS, one "
+                            "256-target super-tile per workgroup and barrier)")
+            else:
+                workload = f"point-to-point ICP iteration on ONE {n_t} x {n} pair = exact grid 1-NN + Kabsch + transform"
+            roofline = groof_c2
+            if args.full and args.nn == "brute":
                 two = three = family == "strack3"
                 sign = family in ("strack", "strack3")
                 f16 = family in ("strack3", "strack", "htrack")
@@ -681,12 +729,6 @@ def main():
                     "hbm_literal": {"bound": "hbm", "achieved": compulsory_bytes / kern_s / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                                     "frac": compulsory_bytes / kern_s / 1e9 / HBM_PEAK_GBS,
                                     "note": "compulsory bytes (32 B/point); brute force is VALU-bound, see DESIGN.md"}}
-                workload = (f"point-to-point ICP iteration = exhaustive 1-NN correspondence of ONE {n} x {n_t} pair + Kabsch + transform; BASELINE.json "
-                            "configs[1]/[2] ('LDS-tiled brute force': the default kernel stages the target's matrix-core operands through LDS, one "
-                            "256-target super-tile per workgroup and barrier)")
-            else:
-                roofline, workload = groof_c2, \
-                    f"point-to-point ICP iteration on ONE {n_t} x {n} pair = exact grid 1-NN + Kabsch + transform"
             out = {
                 "metric": METRIC, "value": n * args.steps / dt / 1e6, "unit": "M corr/s", "icp_iter_per_s": args.steps / dt,
                 "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt * 1e3 / args.steps, "higher_is_better": True,
@@ -696,18 +738,19 @@ def main():
                            "collective": collective,
                            "pose_err_vs_gt_fro": gt_err, "kept_pairs_last_iter": int(st["last_pairs"]), "lib_sha16": sha,
                            "first_timed_iteration": "seeded by the warm-up run's correspondences (as every iteration after the first of an ICP is)",
-                           "timing": "the K timed steps carry no HIP-event pairs; an identical repetition with a pair around every search gives the kernel durations (roofline)",
+                           "timing": "the K timed steps carry no HIP-event pairs; an identical repetition with a pair around every search gives the kernel durations (roofline, --full)",
                            "M_corr_per_s_three_readings": ({"warm_icp_iteration (= value)": n * args.steps / dt / 1e6,
                                                             "one_shot_indexed_target (kernel, cold)": one_shot["indexed_target"]["M_corr_per_s"],
                                                             "one_shot_fresh_target (wall, index build included)": one_shot["fresh_target"]["M_corr_per_s"]}
                                                            if (one_shot and world == 1) else None),
                            "pose_bits": "".join(f"{int(v):08x}" for v in np.ascontiguousarray(T, np.float32).view(np.uint32).ravel())},
-                "roofline": roofline,
-                "kernels": dict(({"nn1_exact_track": exact_line} if exact_line else {}), **stream_kernels(bd, n_q, int(st["last_pairs"]) * n_q // max(n, 1))),
             }
-            # the fixed tail of an iteration (sums + solve + move + the bench's own event pairs): what caps strong scaling on a small pair
-            out["tail_us_per_iteration"] = (dt * 1e3 / args.steps - kern_s * 1e3) * 1e3
-            out["ms_per_step_with_event_pairs"] = dt_pairs * 1e3 / args.steps        # (the repetition the kernel durations of `roofline` come from)
+            if args.full:
+                out["roofline"] = roofline
+                out["kernels"] = dict(({"nn1_exact_track": exact_line} if exact_line else {}), **stream_kernels(bd, n_q, int(st["last_pairs"]) * n_q // max(n, 1)))
+                # the fixed tail of an iteration (sums + solve + move + the bench's own event pairs): what caps strong scaling on a small pair
+                out["tail_us_per_iteration"] = (dt * 1e3 / args.steps - kern_s * 1e3) * 1e3
+                out["ms_per_step_with_event_pairs"] = dt_pairs * 1e3 / args.steps        # (the repetition the kernel durations of `roofline` come from)
             if pred_c2 is not None:
                 out["predicted_scaling"] = pred_c2
             if one_shot:
@@ -716,13 +759,13 @@ def main():
                 out["exact_grid"] = grid_extra
             if weak is not None:
                 out["weak"] = weak
-            if world == 1 and not args.no_cpu_baseline:
+            if args.full and world == 1 and not args.no_cpu_baseline:
                 out["cpu_baseline"] = cpu_baseline(src, tgt)
         cs.free(); ct.free()
         del full_src
 
     # ==================================================================================================== c4: configs[3]
-    if (args.workload == "c4" or (args.workload == "c2" and not args.no_c4 and not args.no_extras)) and world == 1:
+    if (args.workload == "c4" or (args.workload == "c2" and args.full and not args.no_c4 and not args.no_extras)) and world == 1:
         c4 = bench_c4(ctx, pcr, synth, np, args)
         if args.workload == "c4":
             out = c4
@@ -730,7 +773,7 @@ def main():
             out["c4"] = c4
 
     # ==================================================================================================== c5: configs[4]
-    if args.workload == "c5" or (args.workload == "c2" and not args.no_c5 and not args.no_extras):
+    if args.workload == "c5" or (args.workload == "c2" and args.full and not args.no_c5 and not args.no_extras):
         n5 = (args.points or 10_000_000) if args.workload == "c5" else args.c5_points
         full_src, tgt = synth.kitti_like_pair(n5)
         ct = ctx.cloud(tgt)
@@ -739,12 +782,14 @@ def main():
         steps5 = args.steps if args.workload == "c5" else min(args.steps, 10)
         warm5 = args.warmup if args.workload == "c5" else min(args.warmup, 2)
         T, st, dt = timed_icp(cs, ct, 2, src, prof=1, steps=steps5, warmup=warm5)
+        if args.dump_outputs and args.workload == "c5" and rank == 0:
+            dump_outputs(np, args.dump_outputs, icp_outputs(np, T, st))
         gl, gms = ctx.prof_get("nn1_grid")
         kern_s = gms / 1e3 / max(gl, 1)
-        bd = kernel_breakdown(cs, ct, 2, min(steps5, 5))
+        bd = kernel_breakdown(cs, ct, 2, min(steps5, 5)) if args.full else {}
         n_q, n_t = src.shape[1], tgt.shape[1]
-        groof = grid_roofline(ctx, pcr, np, cs, ct, T, n_q, n_t, kern_s, sha)      # (every rank: its ICP loops are collective)
-        pred_c5 = predicted_scaling(full_src, ct, 2, 20, T) if (world == 1 and not args.no_predict) else None
+        groof = grid_roofline(ctx, pcr, np, cs, ct, T, n_q, n_t, kern_s, sha) if args.full else None     # (every rank: its ICP loops are collective)
+        pred_c5 = predicted_scaling(full_src, ct, 2, 20, T) if (args.full and world == 1 and not args.no_predict) else None
         del full_src
         if rank == 0:
             c5 = {"metric": METRIC, "value": n5 * steps5 / dt / 1e6, "unit": "M corr/s", "icp_iter_per_s": steps5 / dt, "n_gpus": world, "steps": steps5,
@@ -756,9 +801,10 @@ def main():
                              "sharding": f"sources x{world} ({args.shard}), target replicated", "collective": collective,
                              "pose_err_vs_gt_fro": float(np.linalg.norm(T.astype(np.float64) - synth.gt_pose())),
                              "kept_pairs_last_iter": int(st["last_pairs"]), "lib_sha16": sha,
-                             "pose_bits": "".join(f"{int(v):08x}" for v in np.ascontiguousarray(T, np.float32).view(np.uint32).ravel())},
-                  "roofline": groof,
-                  "kernels": stream_kernels(bd, n_q, int(st["last_pairs"]) * n_q // max(n5, 1))}
+                             "pose_bits": "".join(f"{int(v):08x}" for v in np.ascontiguousarray(T, np.float32).view(np.uint32).ravel())}}
+            if args.full:
+                c5["roofline"] = groof
+                c5["kernels"] = stream_kernels(bd, n_q, int(st["last_pairs"]) * n_q // max(n5, 1))
             if pred_c5 is not None:
                 c5["predicted_scaling"] = pred_c5
             if args.workload == "c5":
@@ -870,6 +916,11 @@ def bench_c4(ctx, pcr, synth, np, args):
     rc = L.pcr_db64_radius(ctx.h, d.h, db.ctypes.data, n, C.c_double(1.0), row.ctypes.data, idx.ctypes.data, dist.ctypes.data)
     full_call_ms = (time.perf_counter() - t0) * 1e3
     assert rc == 0
+    if args.dump_outputs and args.workload == "c4":
+        # the rows hold ~2e8 neighbours at the default size: a fixed, seeded sample of 2^20 entries (rows in ascending index order)
+        sel = np.sort((synth.splitmix64(11, np.arange(min(total, 1 << 20), dtype=np.uint64)) % np.uint64(max(total, 1))).astype(np.int64))
+        dump_outputs(np, args.dump_outputs, {"plane_counts": counts.astype(np.float64), "radius_counts": np.diff(row).astype(np.float64),
+                                             "radius_sample_index": idx[sel].astype(np.float64), "radius_sample_dist": dist[sel]})
     # the same search with its rows kept in HBM (pcr_rows) and REDUCED there: what a consumer that only needs neighbour counts / sums /
     # moments pays at the boundary — the search, m + 1 offsets and m doubles over PCIe instead of 12 B per neighbour
     R = d.radius_rows(None, 1.0); R.free()                               # (code objects, allocator warm-up)
@@ -929,7 +980,7 @@ def bench_c4(ctx, pcr, synth, np, args):
                      "kernel": "radius pipeline (count + fill + sort + dist)",
                      "algorithmic": "compulsory output bytes: 12 B per reported neighbour + 8 B row pointer per query"},
     }
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import orc
         t0 = time.perf_counter()

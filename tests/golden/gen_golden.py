@@ -17,6 +17,7 @@ Fixtures:
                              ground_detection_ransac.py:138-139,152-153; params from the reference's own
                              estimate_plane_params, :158-169, executed from its source)
   F7 voxel_filter_hw1.npz    Homework1 voxel_filter (centroid mode) outputs on a KITTI subset and a synthetic scan
+  F11 *_live.npz            the reference's answers on the seeded inputs of the tests that call it live (replayed without oracle/_ref)
   F6 icp_selfgolden.npz      ICP trace from the repo's own f64 restatement (SELF-GOLDEN: hw9 cannot be
                              built here — PCL/Eigen absent — so this pins regression, not reference parity)
 """
@@ -26,6 +27,7 @@ import importlib
 import math
 import os
 import sys
+import zipfile
 
 import numpy as np
 
@@ -45,7 +47,13 @@ def sha(a: np.ndarray) -> str:
 
 def save(name, **kw):
     path = os.path.join(OUT, name)
-    np.savez_compressed(path, **kw)
+    np.savez(path, **kw)
+    # LZMA members (np.load reads any zipfile codec): keeps every fixture under the 1 MiB limit of a committed file
+    with zipfile.ZipFile(path) as z:
+        members = [(i.filename, z.read(i.filename)) for i in z.infolist()]
+    with zipfile.ZipFile(path, "w", compression=zipfile.ZIP_LZMA) as z:
+        for fn, data in members:
+            z.writestr(fn, data)
     print(f"{name}: {os.path.getsize(path)/1024:.1f} KiB  " + ", ".join(f"{k}{getattr(v, 'shape', '')}" for k, v in kw.items()))
 
 
@@ -339,7 +347,47 @@ def lib_d2(a, b):
     return orc.lib().orc_d2_dim_f32(np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32), a.size)
 
 
+# ------------------------------------------------------------------ the "live" tests' reference answers
+def f11():
+    """The answers of the compiled reference on the seeded inputs of the tests that call it live, so that they run where oracle/_ref is
+    not built (the tests compare a live reference with these recordings).  Inputs come from the tests' own functions; their sha256
+    is stored beside the answers."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import test_global_registration as tgr
+    import test_iss as tiss
+    import test_config1 as tc1
+    import test_oracle_golden as tog
+    out = {}
+    for dim in tgr.LIVE_DIMS:
+        db, q = tgr.live_dim_inputs(dim)
+        out[f"inputs_sha_{dim}"] = np.array(hashlib.sha256(db.tobytes() + q.tobytes()).hexdigest())
+        out[f"idx_{dim}"], out[f"d2_{dim}"] = orc.ref_nano_nn1_dim_f32(db, q)
+    save("nn1_dim_nanoflann_live.npz", **out)
+    db, q = tiss.hw7_live_inputs(synth)
+    out = {"inputs_sha": np.array(hashlib.sha256(db.tobytes() + q.tobytes()).hexdigest())}
+    for r in tiss.HW7_LIVE_RADII:
+        out[f"row_{r}"], out[f"idx_{r}"], out[f"dist_{r}"] = orc.ref_hw7_radius(db, q, r)
+    save("radius_hw7_live.npz", **out)
+    src, tgt = tog.live_pair(synth)
+    i1, d1, _, _ = orc.ref_nano_nn1_f32(tgt, src, leaf=2)
+    i3, _, _, _ = orc.ref_nano_nn1_f32(tgt, src, leaf=2, threads=4)
+    save("nn1_nanoflann_live.npz", inputs_sha=np.array(hashlib.sha256(src.tobytes() + tgt.tobytes()).hexdigest()), idx=i1, d2=d1, idx_4_threads=i3)
+    out, shas = {}, []
+    for trial, kind, db, q, k, leaf in tog.sweep_cases():
+        shas.append(hashlib.sha256(db.tobytes() + q.tobytes()).hexdigest())
+        t32, s32 = np.ascontiguousarray(db.T.astype(np.float32)), np.ascontiguousarray(q.T.astype(np.float32))
+        out[f"t{trial}_nn_idx"], out[f"t{trial}_nn_d2"], _, _ = orc.ref_nano_nn1_f32(t32, s32, leaf=2)
+        if k is not None:
+            out[f"t{trial}_knn_dist"] = orc.ref_hw2_kd_knn(db, q, k, leaf=leaf)[1]
+            r = tog.sweep_radius(orc.knn_f64(db, q, k)[1], db.shape[0], k)       # the radius the test derives from the oracle's k-NN
+            out[f"t{trial}_radius_row"], out[f"t{trial}_radius_idx"], _ = orc.ref_hw2_kd_radius(db, q, r, leaf=leaf)
+    save("sweep_ref_live.npz", inputs_sha=np.array(shas), **out)
+    db, q = tc1.c1_inputs(synth)
+    _, dist = orc.ref_hw2_kd_knn(np.unique(db.astype(np.float64), axis=0), q.astype(np.float64), 1, leaf=32)
+    save("knn_hw2_c1_live.npz", inputs_sha=np.array(hashlib.sha256(db.tobytes() + q.tobytes()).hexdigest()), dist=dist)
+
+
 if __name__ == "__main__":
     assert os.path.isdir(REF), "reference not present"
     orc.build(ref=True)
-    f1(); f2_f3_f4(); f5(); f6(); f7(); f8(); f9(); f10()
+    f1(); f2_f3_f4(); f5(); f6(); f7(); f8(); f9(); f10(); f11()

@@ -10,6 +10,7 @@ import signal
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -17,14 +18,16 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def run_bench(gpus, *flags, timeout=420):
+def run_bench(gpus, *flags, timeout=420, full=True):
     # a rank that is still running after 300 s dumps its Python stacks and exits (bench.py PCR_BENCH_WATCHDOG_S): a deadlock says where;
     # the launcher and its ranks form one process group that is killed as a whole if the call does not come back in time — no rank may
     # outlive its test on the GPU (the box allows six processes on the card)
     env = dict(os.environ, PCR_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="1", HSA_ENABLE_IPC_MODE_LEGACY="0",
                PCR_BENCH_WATCHDOG_S="300")
     env.pop("WORLD_SIZE", None); env.pop("RANK", None); env.pop("LOCAL_RANK", None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", "3", "--warmup", "1", "--no-cpu-baseline", *flags]
+    # --full: the roofline, weak, exact_grid and c5 blocks checked below are measured only by a full run
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", "3", "--warmup", "1",
+           *(["--full", "--no-cpu-baseline"] if full else []), *flags]
     p = subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env, cwd=ROOT, start_new_session=True)
     try:
         stdout, stderr = p.communicate(timeout=timeout)
@@ -88,3 +91,24 @@ def test_bench_four_ranks_gloo_rehearsal_no_c5(one_rank):
     assert "c5" not in line and line["weak"]["value"] > 0
     assert line["config"]["pose_bits"] == one_rank["config"]["pose_bits"]
     assert line["config"]["kept_pairs_last_iter"] == one_rank["config"]["kept_pairs_last_iter"]
+
+
+def test_bench_plain_line_and_dumped_outputs(one_rank, tmp_path):
+    """the plain run (no --full): the headline alone, a short line, and --dump-outputs writes what the timed call returned —
+    the same pose as the full run's headline, bit for bit"""
+    line = run_bench(1, "--dump-outputs", str(tmp_path), full=False)
+    raw = json.dumps(line)
+    assert len(raw) < 4096, len(raw)
+    assert line["n_gpus"] == 1 and line["steps"] == 3 and line["warmup"] == 1
+    assert line["unit"] == "M corr/s" and line["dtype"] == "f32" and line["higher_is_better"] is True
+    assert line["metric"] == one_rank["metric"] and line["value"] > 0 and line["ms_per_step"] > 0
+    assert abs(line["value"] * line["ms_per_step"] * 1e3 - 120000) < 1e-6 * 120000        # value = points / ms_per_step
+    for key in ("roofline", "kernels", "one_shot", "exact_grid", "weak", "predicted_scaling", "cpu_baseline", "c4", "c5"):
+        assert key not in line, key
+    assert line["config"]["pose_bits"] == one_rank["config"]["pose_bits"]
+    got = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert set(got) == {"pose", "iters_run", "converged", "empty_pairs", "last_pairs", "last_loss"}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert got["pose"].dtype == np.float32 and got["pose"].shape == (4, 4)
+    assert "".join(f"{int(v):08x}" for v in got["pose"].view(np.uint32).ravel()) == line["config"]["pose_bits"]
+    assert got["iters_run"][0] == 3 and got["last_pairs"][0] == line["config"]["kept_pairs_last_iter"]

@@ -2,6 +2,8 @@
 The reference's brute force exists only in Python: Homework2/hw2/benchmark.py:69-71
     diff = np.linalg.norm(np.expand_dims(query, 0) - db_np, axis=1); nn_idx = np.argsort(diff); nn_dist = diff[nn_idx]
 on float32 points; the inputs follow its generator (test.hpp:142: range * (rand() % 1000) / 1000.0, glibc rand())."""
+import hashlib
+
 import numpy as np
 import pytest
 
@@ -12,10 +14,15 @@ def numpy_brute_force(db32, query32):
     return nn_idx, diff[nn_idx]                                          # :71
 
 
-@pytest.fixture(scope="module")
-def c1_data(synth):
+def c1_inputs(synth):
+    """(database, queries) of config 1 (also read by tests/golden/gen_golden.py)"""
     pts = synth.glibc_rand_lattice(2000, 3, 10.0, seed=1)                # hw2 never seeds: glibc default seed 1
     return pts[:1000].astype(np.float32), pts[1000:].astype(np.float32)  # database, second draw = queries
+
+
+@pytest.fixture(scope="module")
+def c1_data(synth):
+    return c1_inputs(synth)
 
 
 def check_against_numpy(db, q, idx, d2):
@@ -40,12 +47,17 @@ def test_c1_oracle_matches_numpy_brute_force(orc, c1_data):
     check_against_numpy(db, q, idx, d2)
 
 
-def test_c1_reference_kdtree_matches_on_the_same_points(orc, c1_data):
-    if not orc.have_ref():
-        pytest.skip("oracle/_ref not built")
+def test_c1_reference_kdtree_matches_on_the_same_points(orc, c1_data, golden):
+    """against the compiled hw2 kd-tree when oracle/_ref is built, else against its answers on the same points
+    (tests/golden/knn_hw2_c1_live.npz); a live reference must reproduce the recorded answers"""
     db, q = c1_data
+    g = golden("knn_hw2_c1_live.npz")
+    assert str(g["inputs_sha"]) == hashlib.sha256(db.tobytes() + q.tobytes()).hexdigest(), "inputs differ from the recording"
     udb = np.unique(db.astype(np.float64), axis=0)
-    ridx, rdist = orc.ref_hw2_kd_knn(udb, q.astype(np.float64), 1, leaf=32)    # leaf 32: see DESIGN.md §2 (lattice inputs)
+    rdist = g["dist"]
+    if orc.have_ref():
+        _, ldist = orc.ref_hw2_kd_knn(udb, q.astype(np.float64), 1, leaf=32)    # leaf 32: see DESIGN.md §2 (lattice inputs)
+        assert np.array_equal(ldist.view(np.uint64), rdist.view(np.uint64))
     oidx, odist = orc.knn_f64(udb, q.astype(np.float64), 1)
     assert np.array_equal(rdist.view(np.uint64), odist.view(np.uint64))
 

@@ -4,6 +4,8 @@
 Pinning: the 1-NN at dim 33 is PINNED to the vendored nanoflann (tests/golden/desc_match_hw9.npz, generated through
 oracle/_ref).  The sort's tie order (std::sort), the RNG stream (std::random_device) and the f32 Eigen Kabsch are
 unspecified in the reference: UNPINNED, restated (stable sort, explicit seed, f64 moments)."""
+import hashlib
+
 import numpy as np
 import pytest
 
@@ -49,16 +51,30 @@ def test_oracle_nn1_dim33_matches_nanoflann_fixture(orc, golden):
     assert (g["d2_src_of_tgt"][580:590] == 0).all()                 # the planted exact matches
 
 
-@pytest.mark.parametrize("dim", [1, 3, 4, 7, 33, 34])
-def test_oracle_nn1_dim_matches_nanoflann_live(orc, dim):
-    if not orc.have_ref():
-        pytest.skip("oracle/_ref not built (reference absent)")
+LIVE_DIMS = [1, 3, 4, 7, 33, 34]
+
+
+def live_dim_inputs(dim):
+    """the seeded (database, queries) of test_oracle_nn1_dim_matches_nanoflann_live (also read by tests/golden/gen_golden.py)"""
     rng = np.random.default_rng(dim)
     db, q = fpfh_like(rng, 500, dim), fpfh_like(rng, 300, dim)
     if dim == 1:
         db, q = rng.normal(0, 1, (500, 1)).astype(np.float32), rng.normal(0, 1, (300, 1)).astype(np.float32)
+    return db, q
+
+
+@pytest.mark.parametrize("dim", LIVE_DIMS)
+def test_oracle_nn1_dim_matches_nanoflann_live(orc, golden, dim):
+    """against the compiled vendored nanoflann when oracle/_ref is built, else against its answers on the same inputs
+    (tests/golden/nn1_dim_nanoflann_live.npz); a live reference must reproduce the recorded answers"""
+    db, q = live_dim_inputs(dim)
+    g = golden("nn1_dim_nanoflann_live.npz")
+    assert str(g[f"inputs_sha_{dim}"]) == hashlib.sha256(db.tobytes() + q.tobytes()).hexdigest(), "inputs differ from the recording"
+    ri, rd = g[f"idx_{dim}"], g[f"d2_{dim}"]
+    if orc.have_ref():
+        li, ld = orc.ref_nano_nn1_dim_f32(db, q)
+        assert np.array_equal(li, ri) and np.array_equal(ld.view(np.uint32), rd.view(np.uint32))
     idx, d2 = orc.nn1_dim_f32(db, q)
-    ri, rd = orc.ref_nano_nn1_dim_f32(db, q)
     check_tie_rule(orc, db, q, idx, d2, ri, rd)
 
 

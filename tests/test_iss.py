@@ -5,6 +5,8 @@ holds (count, index sum, index xor) per point from the reference's own kd-tree c
 test clouds at the driver's radii (main.cpp:84-91).  The covariance / eigenvalue half needs Eigen (absent): UNPINNED, the
 oracle restates it with f64 accumulation; lambda3 is compared with a tolerance and the keypoint decision is checked
 exactly against the decision rule applied to the GPU's own lambda3."""
+import hashlib
+
 import numpy as np
 import pytest
 
@@ -32,14 +34,28 @@ def test_oracle_radius_f32_matches_hw7_kdtree_fixture(orc, golden, name):
         assert np.array_equal(sxor, g[f"{tag}_xor_{name}"])
 
 
-def test_oracle_radius_f32_matches_hw7_kdtree_live(orc, synth):
-    if not orc.have_hw7():
-        pytest.skip("oracle/_ref/libhw7_ref.so not built (reference absent)")
+HW7_LIVE_RADII = (0.3, 1.0, 2.5)
+
+
+def hw7_live_inputs(synth):
+    """the seeded (database, queries) of test_oracle_radius_f32_matches_hw7_kdtree_live (also read by tests/golden/gen_golden.py)"""
     rng = np.random.default_rng(5)
     db = np.ascontiguousarray(synth.kitti_like_scan(3000).T)
     q = db[rng.integers(0, 3000, 300)] + rng.normal(0, 0.05, (300, 3)).astype(np.float32)
-    for r in (0.3, 1.0, 2.5):
-        row, idx, dist = orc.ref_hw7_radius(db, q, r)
+    return db, q
+
+
+def test_oracle_radius_f32_matches_hw7_kdtree_live(orc, synth, golden):
+    """against hw7's compiled kd-tree when oracle/_ref is built, else against its answers on the same inputs
+    (tests/golden/radius_hw7_live.npz); a live reference must reproduce the recorded answers"""
+    db, q = hw7_live_inputs(synth)
+    g = golden("radius_hw7_live.npz")
+    assert str(g["inputs_sha"]) == hashlib.sha256(db.tobytes() + q.tobytes()).hexdigest(), "inputs differ from the recording"
+    for r in HW7_LIVE_RADII:
+        row, idx, dist = g[f"row_{r}"], g[f"idx_{r}"], g[f"dist_{r}"]
+        if orc.have_hw7():
+            lrow, lidx, ldist = orc.ref_hw7_radius(db, q, r)
+            assert np.array_equal(lrow, row) and np.array_equal(lidx, idx) and np.array_equal(ldist.view(np.uint32), dist.view(np.uint32))
         orow, oidx, odist = orc.radius_f32(db, q, r)
         assert np.array_equal(row, orow)
         for i in range(300):

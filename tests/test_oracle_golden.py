@@ -1,6 +1,8 @@
 """CPU tests (-m "not gpu"): pin the oracle (oracle/pcr_oracle.c) against the fixtures generated from the
 REFERENCE ITSELF (tests/golden/gen_golden.py: compiled hw2 kd-tree/octree, vendored nanoflann, HW4 numpy
 expression), i.e. SURVEY.md §8c F1-F6.  Tie handling follows the tie-set rule of SURVEY.md §7.2."""
+import hashlib
+
 import numpy as np
 import pytest
 
@@ -274,14 +276,24 @@ def test_icp_converges_to_ground_truth_on_dense_pair(orc, synth):
 
 
 # ---------------------------------------------------------------- reference harness live (when built)
-def test_live_reference_agrees_with_oracle_when_present(orc, synth):
-    if not orc.have_ref():
-        pytest.skip("oracle/_ref not built (reference absent)")
-    src, tgt = synth.kitti_like_pair(3000, seed_target=99, seed_pair=98)
-    i1, d1, _, _ = orc.ref_nano_nn1_f32(tgt, src, leaf=2)
+def live_pair(synth):
+    """the pair of test_live_reference_agrees_with_oracle_when_present (also read by tests/golden/gen_golden.py)"""
+    return synth.kitti_like_pair(3000, seed_target=99, seed_pair=98)
+
+
+def test_live_reference_agrees_with_oracle_when_present(orc, synth, golden):
+    """against the compiled vendored nanoflann when oracle/_ref is built, else against its answers on the same pair
+    (tests/golden/nn1_nanoflann_live.npz); a live reference must reproduce the recorded answers"""
+    src, tgt = live_pair(synth)
+    g = golden("nn1_nanoflann_live.npz")
+    assert str(g["inputs_sha"]) == hashlib.sha256(src.tobytes() + tgt.tobytes()).hexdigest(), "inputs differ from the recording"
+    i1, d1, i3 = g["idx"], g["d2"], g["idx_4_threads"]
+    if orc.have_ref():
+        li, ld, _, _ = orc.ref_nano_nn1_f32(tgt, src, leaf=2)
+        l3, _, _, _ = orc.ref_nano_nn1_f32(tgt, src, leaf=2, threads=4)
+        assert np.array_equal(li, i1) and np.array_equal(bits32(ld), bits32(d1)) and np.array_equal(l3, i3)
     i2, d2 = orc.nn1_f32(tgt, src)
     assert np.array_equal(i1, i2) and np.array_equal(bits32(d1), bits32(d2))
-    i3, d3, _, _ = orc.ref_nano_nn1_f32(tgt, src, leaf=2, threads=4)
     assert np.array_equal(i1, i3)
 
 
@@ -298,37 +310,63 @@ def random_cloud(rng, n, kind):
     return rng.normal(0, 1, (n, 3)) * s
 
 
-def test_live_reference_randomised_sweep(orc):
-    """200 random small problems against the compiled reference: nanoflann f32 1-NN (d2 bits; index equal or inside the
-    tie set), hw2 kd-tree k-NN distances and radius sets — continuous, lattice, clustered and extreme-magnitude clouds."""
-    if not orc.have_ref():
-        pytest.skip("oracle/_ref not built (reference absent)")
+def sweep_cases():
+    """the 200 seeded problems of test_live_reference_randomised_sweep: (trial, kind, db, q, k, leaf); k = leaf = None where
+    the hw2 kd-tree is not run (also read by tests/golden/gen_golden.py)"""
     rng = np.random.default_rng(20240607)
-    ties_seen = 0
     for trial in range(200):
         kind = trial % 4
         n, m = int(rng.integers(1, 300)), int(rng.integers(1, 40))
         db, q = random_cloud(rng, n, kind), random_cloud(rng, m, kind)
         if trial % 3 == 0:
             q[: min(m, n) // 2] = db[: min(m, n) // 2]                        # exact hits
-        # --- A1/A3/A6: nanoflann f32, leaf 2
-        t32, s32 = np.ascontiguousarray(db.T.astype(np.float32)), np.ascontiguousarray(q.T.astype(np.float32))
-        ri, rd, _, _ = orc.ref_nano_nn1_f32(t32, s32, leaf=2)
-        oi, od = orc.nn1_f32(t32, s32)
-        assert np.array_equal(bits32(rd), bits32(od)), trial
-        for k in np.flatnonzero(ri != oi):
-            assert oi[k] < ri[k] and orc.lib().orc_d2_f32(*map(float, s32[:, k]), *map(float, t32[:, ri[k]])) == od[k]
-            ties_seen += 1
-        # --- A2/A4: hw2 kd-tree k-NN (lattice clouds can make its median split recurse forever: leaf >= 32 there, see DESIGN)
+        k = leaf = None
+        # (lattice clouds can make the hw2 kd-tree's median split recurse forever: leaf >= 32 there, see DESIGN)
         if np.unique(db, axis=0).shape[0] == n or kind != 1:
             k = int(rng.integers(1, 9))
             leaf = 32 if kind == 1 else 1
-            hi, hd = orc.ref_hw2_kd_knn(db, q, k, leaf=leaf)
+        yield trial, kind, db, q, k, leaf
+
+
+def sweep_radius(kd, n, k):
+    return float(np.median(kd[:, -1])) if n >= k else 1.0
+
+
+def test_live_reference_randomised_sweep(orc, golden):
+    """200 random small problems against the compiled reference: nanoflann f32 1-NN (d2 bits; index equal or inside the
+    tie set), hw2 kd-tree k-NN distances and radius sets — continuous, lattice, clustered and extreme-magnitude clouds.
+    Without oracle/_ref the reference's answers to the same problems come from tests/golden/sweep_ref_live.npz; a live
+    reference must reproduce them."""
+    g = golden("sweep_ref_live.npz")
+    live = orc.have_ref()
+    ties_seen = 0
+    for trial, kind, db, q, k, leaf in sweep_cases():
+        n, m = db.shape[0], q.shape[0]
+        assert str(g["inputs_sha"][trial]) == hashlib.sha256(db.tobytes() + q.tobytes()).hexdigest(), ("inputs differ from the recording", trial)
+        # --- A1/A3/A6: nanoflann f32, leaf 2
+        t32, s32 = np.ascontiguousarray(db.T.astype(np.float32)), np.ascontiguousarray(q.T.astype(np.float32))
+        ri, rd = g[f"t{trial}_nn_idx"], g[f"t{trial}_nn_d2"]
+        if live:
+            li, ld, _, _ = orc.ref_nano_nn1_f32(t32, s32, leaf=2)
+            assert np.array_equal(li, ri) and np.array_equal(bits32(ld), bits32(rd)), trial
+        oi, od = orc.nn1_f32(t32, s32)
+        assert np.array_equal(bits32(rd), bits32(od)), trial
+        for kk in np.flatnonzero(ri != oi):
+            assert oi[kk] < ri[kk] and orc.lib().orc_d2_f32(*map(float, s32[:, kk]), *map(float, t32[:, ri[kk]])) == od[kk]
+            ties_seen += 1
+        # --- A2/A4: hw2 kd-tree k-NN
+        if k is not None:
+            hd = g[f"t{trial}_knn_dist"]
+            if live:
+                assert np.array_equal(orc.ref_hw2_kd_knn(db, q, k, leaf=leaf)[1].view(np.uint64), hd.view(np.uint64)), trial
             ki, kd = orc.knn_f64(db, q, k)
             assert np.array_equal(hd.view(np.uint64), kd.view(np.uint64)), trial
             # --- A11: radius sets
-            r = float(np.median(kd[:, -1])) if n >= k else 1.0
-            row, ridx, rdist = orc.ref_hw2_kd_radius(db, q, r, leaf=leaf)
+            r = sweep_radius(kd, n, k)
+            row, ridx = g[f"t{trial}_radius_row"], g[f"t{trial}_radius_idx"]
+            if live:
+                lrow, lidx, _ = orc.ref_hw2_kd_radius(db, q, r, leaf=leaf)
+                assert np.array_equal(lrow, row) and np.array_equal(lidx, ridx), trial
             orow, oidx, odist = orc.radius_f64(db, q, r)
             assert np.array_equal(row, orow)
             for i in range(m):

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Condense the rocprofv3 outputs merged into gpurun_out/ into small text files under profiles/ (committed).
-usage: python tools/summarize_prof.py r01"""
+usage: python tools/summarize_prof.py r01 [<output dir of tools/gpu_check.sh>]"""
 import collections, csv, glob, hashlib, json, os, sys
 
 tag = sys.argv[1] if len(sys.argv) > 1 else "rXX"
@@ -8,6 +8,8 @@ root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # the counters describe ONE build of the library: bench.py trusts them only while the sha of the loaded libpcr_hip.so is the same
 LIB_SHA16 = hashlib.sha256(open(os.path.join(root, "hands-on-point-cloud-processing_amd", "libpcr_hip.so"), "rb").read()).hexdigest()[:16]
 go = os.path.join(root, "gpurun_out")
+if len(sys.argv) > 2:
+    go = os.path.abspath(sys.argv[2])
 out = os.path.join(root, "profiles")
 os.makedirs(out, exist_ok=True)
 
@@ -20,7 +22,7 @@ def newest(pattern):
 lines = []
 f = newest("prof_bench/*/*_kernel_stats.csv")
 if f:
-    lines.append("## rocprofv3 --kernel-trace --stats -- python3 bench.py --no-cpu-baseline   (kernel_stats.csv)\n")
+    lines.append("## rocprofv3 --kernel-trace --stats -- python3 bench.py --full --no-cpu-baseline   (kernel_stats.csv)\n")
     lines.append("| kernel | calls | total ms | avg us | % |")
     lines.append("|---|---|---|---|---|")
     for r in csv.DictReader(open(f)):
