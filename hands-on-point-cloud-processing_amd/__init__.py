@@ -63,6 +63,7 @@ ABI_SYMBOLS = [
     "pcr_nn1_desc_f32", "pcr_match_union_f32", "pcr_match_inter_f32", "pcr_ransac_sample_quads", "pcr_consensus_count_f32", "pcr_ransac_global_f32", "pcr_db64_create", "pcr_db64_destroy", "pcr_db64_size", "pcr_db64_knn", "pcr_db64_radius",
     "pcr_ctx_trim", "pcr_ctx_parked_bytes", "pcr_cloud_shard_spatial", "pcr_cloud_global_index", "pcr_cloud_sort_for_target", "pcr_nn1_f32_loop",
     "pcr_db64_radius_rows", "pcr_rows_destroy", "pcr_rows_info", "pcr_rows_row_ptr", "pcr_rows_fetch", "pcr_rows_reduce", "pcr_rows_moments",
+    "pcr_dbscan_f32", "pcr_statistical_outlier_f32",
 ]
 
 
@@ -152,6 +153,8 @@ def lib():
     L.pcr_fast_eigen3x3.argtypes = [vp, vp]
     L.pcr_ground_seeds_f64.argtypes = [vp, vp, sz, C.c_double, vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
     L.pcr_ground_detection_f64.argtypes = [vp, vp, C.c_int, sz, C.c_double, vp, vp, C.POINTER(C.c_uint64)]
+    L.pcr_dbscan_f32.argtypes = [vp, vp, C.c_double, C.c_int, vp, vp, vp, C.POINTER(C.c_uint64)]
+    L.pcr_statistical_outlier_f32.argtypes = [vp, vp, C.c_int, C.c_double, vp, vp, vp, C.POINTER(C.c_uint64), C.POINTER(vp)]
     L.pcr_nn1_desc_f32.argtypes = [vp, vp, sz, vp, sz, C.c_int, vp, vp]
     L.pcr_match_union_f32.argtypes = [vp, vp, sz, vp, sz, C.c_int, C.c_float, vp, vp, C.POINTER(sz)]
     L.pcr_match_inter_f32.argtypes = [vp, vp, sz, vp, sz, C.c_int, C.c_float, vp, vp, C.POINTER(sz)]
@@ -601,6 +604,34 @@ class Context:
         self._ck(lib().pcr_ground_detection_f64(self.h, cloud.h, int(max_iter), int(lpr_size), float(threshold_dist), params.ctypes.data,
                                                 mask.ctypes.data, C.byref(cnt)))
         return params, mask[:n].astype(bool)
+
+    # ---- Homework4 foreground stage
+    def dbscan(self, cloud: Cloud, eps: float, min_points: int):
+        """DBSCAN (cluster_dbscan, ground_detection_SVD.py:173) -> (labels i32[n] (-1 = noise), is_core bool[n], |N(p)| u32[n],
+        n_clusters); the contract of pcr_dbscan_f32 (sklearn.cluster.DBSCAN's labels)."""
+        n = len(cloud)
+        labels = np.zeros(max(n, 1), np.int32)
+        core = np.zeros(max(n, 1), np.uint8)
+        counts = np.zeros(max(n, 1), np.uint32)
+        nc = C.c_uint64()
+        self._ck(lib().pcr_dbscan_f32(self.h, cloud.h, float(eps), int(min_points), labels.ctypes.data, core.ctypes.data, counts.ctypes.data,
+                                      C.byref(nc)))
+        return labels[:n], core[:n].astype(bool), counts[:n], int(nc.value)
+
+    def statistical_outlier(self, cloud: Cloud, nb_neighbors: int, std_ratio: float):
+        """remove_statistical_outlier (ground_detection_SVD.py:33) -> (keep bool[n], avg distance f64[n], (mean, std, thr), kept
+        points as a new device cloud, ascending input order); the contract of pcr_statistical_outlier_f32."""
+        n = len(cloud)
+        keep = np.zeros(max(n, 1), np.uint8)
+        avg = np.zeros(max(n, 1), np.float64)
+        st = np.zeros(3, np.float64)
+        nk = C.c_uint64()
+        h = C.c_void_p()
+        self._ck(lib().pcr_statistical_outlier_f32(self.h, cloud.h, int(nb_neighbors), float(std_ratio), keep.ctypes.data, avg.ctypes.data,
+                                                   st.ctypes.data, C.byref(nk), C.byref(h)))
+        kept = Cloud(self, h)
+        assert len(kept) == nk.value
+        return keep[:n].astype(bool), avg[:n], (float(st[0]), float(st[1]), float(st[2])), kept
 
     # ---- N4
     def nn1_desc(self, db, q):

@@ -376,6 +376,8 @@ int knn_grid_for(pcr_ctx* ctx, const pcr_cloud* db, int k, Grid** out, bool* own
     return PCR_OK;
 }
 
+}  // namespace
+
 // device results: idx [m x k], val [m x k], found [m] at the head of a fresh allocation (caller frees)
 int knn_grid_device(pcr_ctx* ctx, const pcr_cloud* db, const pcr_cloud* q, int k, double cap_s, bool squared, double empty_val, int32_t empty_idx,
                     void** result, int32_t** idx_dev, double** val_dev, uint32_t** found_dev)
@@ -426,8 +428,6 @@ int knn_grid_device(pcr_ctx* ctx, const pcr_cloud* db, const pcr_cloud* q, int k
     if (e != hipSuccess) { hipFree(res); *result = nullptr; return fail(ctx, PCR_ERR_HIP, "knn_grid", e); }
     return PCR_OK;
 }
-
-}  // namespace
 
 // Small batches (m <= KNN_SMALL_MAX queries given on the host as f32 rows): ONE launch and one stream synchronisation — no
 // query cloud, no result allocation, no copy command.  The kernel reads the queries from pinned host memory and writes the

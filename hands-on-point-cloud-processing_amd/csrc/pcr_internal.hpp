@@ -215,6 +215,9 @@ int radius_grid(pcr_ctx* ctx, const pcr_cloud* db, const pcr_cloud* q, double r,
 // exact grid k-NN between resident clouds (knn_grid.hip); host outputs idx/val [m x k], found [m] (optional)
 int cloud_knn_host(pcr_ctx* ctx, const pcr_cloud* db, const pcr_cloud* q, int k, double cap_s, bool squared, double empty_val, int32_t empty_idx,
                    int32_t* idx, double* val, uint32_t* found);
+// the same with the results left on the device: idx / val [m x k], found [m] at the head of a fresh allocation *result (caller frees)
+int knn_grid_device(pcr_ctx* ctx, const pcr_cloud* db, const pcr_cloud* q, int k, double cap_s, bool squared, double empty_val, int32_t empty_idx,
+                    void** result, int32_t** idx_dev, double** val_dev, uint32_t** found_dev);
 // the same for a small batch of host queries (f32 rows): one launch, zero-copy in and out
 constexpr size_t KNN_SMALL_MAX = 4096;
 int cloud_knn_small(pcr_ctx* ctx, const pcr_cloud* db, const float* q_rows, size_t m, int k, double cap_s, bool squared, double empty_val,

@@ -8,6 +8,8 @@ Mirrors (same names, argument meaning and return values):
   extract_initial_seeds   Homework4/ground_detection_SVD.py:46-71        (GPU: radix-select of the lowest z, pcr_ground_seeds_f64)
   ground_detection        Homework4/ground_detection_SVD.py:88-101       (GPU: pcr_ground_detection_f64, PCA refit loop)
   ground_detection_on3segs  Homework4/ground_detection_SVD.py:104-126
+  pcd_preprocessing       Homework4/ground_detection_SVD.py:22-37        (GPU: y crop on the host, pcr_statistical_outlier_f32)
+  cluster_dbscan          open3d PointCloud.cluster_dbscan, ground_detection_SVD.py:173   (GPU: pcr_dbscan_f32)
 
 The hot loop of my_ransac — `dists = |[X 1] . params|; inliers = sum(dists < thr)` evaluated once per hypothesis
 (:138-139) — becomes ONE launch of pcr_plane_count_f64 over all `max_iteration` hypotheses: the points are read
@@ -113,6 +115,37 @@ def ground_detection_on3segs(pcd_points: np.ndarray, main_dist=20, max_iter=6, t
         stacked_ground_idx = np.r_[stacked_ground_idx, ground]
         stacked_foregr_idx = np.r_[stacked_foregr_idx, foreground]
     return stacked_ground_idx, stacked_foregr_idx
+
+
+def pcd_preprocessing(data, *, ctx=None) -> np.ndarray:
+    """ground_detection_SVD.py:22-37: keep -15 < y < 30, then remove_statistical_outlier(nb_neighbors=20, std_ratio=2.7) ->
+    the kept points as an f64 (N, 3) array in input order, as the reference returns them."""
+    data = np.asarray(data)
+    data = data[np.logical_and(data[:, 1] < 30, data[:, 1] > -15)]
+    ctx = ctx or default_context()
+    cloud = ctx.cloud(np.ascontiguousarray(data[:, :3], np.float32), 1)
+    try:
+        _, _, _, kept = ctx.statistical_outlier(cloud, 20, 2.7)
+    finally:
+        cloud.free()
+    try:
+        return kept.numpy().T.astype(np.float64)
+    finally:
+        kept.free()
+
+
+def cluster_dbscan(points, eps, min_points, print_progress=False, *, ctx=None) -> np.ndarray:
+    """open3d PointCloud.cluster_dbscan(eps, min_points, print_progress) on an (N, 3) array -> int32 labels, -1 = noise
+    (ground_detection_SVD.py:173).  Labels follow pcr_dbscan_f32: sklearn.cluster.DBSCAN's; Open3D's are unpinned.
+    print_progress is accepted for the signature and ignored."""
+    pts = np.asarray(points)
+    ctx = ctx or default_context()
+    cloud = ctx.cloud(np.ascontiguousarray(pts[:, :3], np.float32), 1)
+    try:
+        labels, _, _, _ = ctx.dbscan(cloud, eps, min_points)
+    finally:
+        cloud.free()
+    return labels
 
 
 def my_ransac(data: np.ndarray, indices: np.ndarray, max_iteration: int, threshold: float, *, ctx=None, rng=None):

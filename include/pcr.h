@@ -249,6 +249,34 @@ int pcr_ground_seeds_f64(pcr_ctx* ctx, const pcr_cloud* cloud, size_t lpr_size, 
 int pcr_ground_detection_f64(pcr_ctx* ctx, const pcr_cloud* cloud, int max_iter, size_t lpr_size, double threshold_dist,
                              double params[4], uint8_t* ground_mask, uint64_t* n_ground);
 
+/* ---- Homework4 foreground stage: DBSCAN and statistical outlier removal, ground_detection_SVD.py:22-37 and :173 ---------
+ * Distances as pcr_cloud_knn_f64: the f32 coordinates widened to f64, s = ((dx*dx) + dy*dy) + dz*dz, unfused.
+ * pcr_dbscan_f32 (foreground_pcd.cluster_dbscan(0.8, 20), :173; foreground_clustering_DBSCAN.py):
+ *   N(p) = { j : s(p, j) <= eps*eps } (p included, eps*eps the f64 product); core(p) = |N(p)| >= min_points (min_points <= 1:
+ *   every finite point is core).  Clusters = connected components of the core points under "within eps"; a cluster's key is
+ *   its smallest core index (input numbering) and ids 0, 1, ... follow ascending keys.  A non-core point with a core neighbour
+ *   (border point) takes the SMALLEST id among its core neighbours' clusters; every other point is noise, label -1.
+ *   Non-finite points are noise and nobody's neighbour.  This is what sklearn.cluster.DBSCAN returns (points visited in
+ *   index order, a border point goes to the first cluster that reaches it); equivalence with Open3D's ClusterDBSCAN (BFS in
+ *   the same order, an inclusive or strict radius test depending on its version) is UNPINNED.
+ *   labels: n int32 (required); is_core: n bytes, neighbor_counts: n u32 (|N(p)|), n_clusters: optional.  PCR_ERR_ARG for
+ *   eps < 0, NaN or inf, or n > 2^31 - 16; eps = 0 links exact duplicates only.  PCR_ERR_STATE if the union-find's bound
+ *   is exceeded (never in a correct run).
+ * pcr_statistical_outlier_f32 (pcd.remove_statistical_outlier(nb_neighbors = 20, std_ratio = 2.7), :33; Open3D's
+ * PointCloud::RemoveStatisticalOutliers):
+ *   avg[i] = (sum of sqrt(s) over the nb_neighbors nearest points, itself included — pcr_cloud_knn_f64 with squared = 1,
+ *   fewer when n < k — added in slot order) / found, -1 for a non-finite point; valid = points with found > 0;
+ *   mean = sum_{avg > 0} avg / valid; std = sqrt(sum_{avg > 0} (avg - mean)^2 / (valid - 1)); thr = mean + std_ratio std;
+ *   keep[i] = avg[i] > 0 && avg[i] < thr (Open3D's quirk: a point with k or more exact duplicates has avg 0 and is dropped).
+ *   The two global sums are deterministic (fixed reduction order) but not Open3D's sequential std::accumulate bit for bit.
+ *   stats3 = (mean, std, thr); kept_cloud = a new device cloud of the kept points in ascending input order (input to the
+ *   ground fit or to DBSCAN without a host round trip).  Every output is optional.  PCR_ERR_ARG for nb_neighbors < 1 or
+ *   > 32 (the limit of the k-NN service) and for std_ratio <= 0 or non-finite (Open3D rejects the same). */
+int pcr_dbscan_f32(pcr_ctx* ctx, const pcr_cloud* cloud, double eps, int min_points, int32_t* labels, uint8_t* is_core,
+                   uint32_t* neighbor_counts, uint64_t* n_clusters);
+int pcr_statistical_outlier_f32(pcr_ctx* ctx, const pcr_cloud* cloud, int nb_neighbors, double std_ratio, uint8_t* keep, double* avg_dist,
+                                double stats3[3], uint64_t* n_kept, pcr_cloud** kept_cloud);
+
 /* ---- next row N4: global-registration front half, Homework9/hw9/src/registration.cpp:288-434, :535-615 -----------
  * N4a: exhaustive 1-NN between two descriptor sets (row-major n x dim / m x dim f32, host memory; dim 33 = FPFH),
  * nanoflann's evalMetric arithmetic for any dim (nanoflann.hpp:382-405: groups of four + tail, f32, unfused), canonical
