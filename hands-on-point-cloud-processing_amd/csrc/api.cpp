@@ -172,7 +172,6 @@ static void cloud_forget(pcr_ctx* ctx, pcr_cloud* c)
     if (ctx && ctx->qperm_src == c) ctx->qperm_src = nullptr;
     if (ctx && ctx->keys_src == c) ctx->keys_src = nullptr;
     if (ctx && ctx->keys_tgt == c) { ctx->keys_tgt = nullptr; ctx->keys_warm = false; ctx->wpos_valid = false; }
-    if (ctx && ctx->work_orig_src == c) ctx->work_orig_src = nullptr;
     if (ctx && (ctx->keys_seed_src == c || ctx->keys_seed_tgt == c)) { ctx->keys_seeded = false; ctx->keys_seed_src = ctx->keys_seed_tgt = nullptr; }
     cloud_modified(c);
 }
@@ -185,6 +184,7 @@ void cloud_release(pcr_ctx* ctx, pcr_cloud* c)
     if (!c) return;
     cloud_forget(ctx, c);
     if (c->gidx) { hipFree(c->gidx); c->gidx = nullptr; }
+    if (c->orig_buf) { hipFree(c->orig_buf); c->orig_buf = nullptr; }
     if (c->base) {
         // (buffers beyond 2 GB are not kept: a spare slot is a convenience, not a cache of the caller's memory)
         int slot = -1;
@@ -332,6 +332,21 @@ int pcr_cloud_create(pcr_ctx* ctx, const float* host_xyz, size_t n, int layout, 
     return PCR_OK;
 }
 
+// a copy of a spatial shard is that shard: dst takes src's global indices (device to device), and loses its own when src has none
+// (a clone of a shard fell back to the order key of a contiguous shard: test_context_state.py §C)
+static hipError_t copy_gidx(pcr_ctx* ctx, pcr_cloud* dst, const pcr_cloud* src)
+{
+    if (!src->gidx) {
+        if (dst->gidx) { hipFree(dst->gidx); dst->gidx = nullptr; }
+        return hipSuccess;
+    }
+    if (!dst->gidx) {
+        hipError_t e = hipMalloc((void**)&dst->gidx, std::max<size_t>(src->n, 1) * sizeof(uint32_t));
+        if (e != hipSuccess) { dst->gidx = nullptr; return e; }
+    }
+    return src->n ? hipMemcpyAsync(dst->gidx, src->gidx, src->n * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream) : hipSuccess;
+}
+
 int pcr_cloud_clone(pcr_ctx* ctx, const pcr_cloud* src, pcr_cloud** out)
 {
     if (!ctx || !src || !out) return fail(ctx, PCR_ERR_ARG, "pcr_cloud_clone");
@@ -339,6 +354,7 @@ int pcr_cloud_clone(pcr_ctx* ctx, const pcr_cloud* src, pcr_cloud** out)
     int rc = cloud_alloc(ctx, src->n, &c);
     if (rc) return rc;
     hipError_t e = hipMemcpyAsync(c->base, src->base, 3 * c->cap * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream);
+    if (e == hipSuccess) e = copy_gidx(ctx, c, src);
     if (e != hipSuccess) { pcr_cloud_destroy(ctx, c); return fail(ctx, PCR_ERR_HIP, "cloud clone", e); }
     *out = c;
     return PCR_OK;
@@ -347,8 +363,12 @@ int pcr_cloud_clone(pcr_ctx* ctx, const pcr_cloud* src, pcr_cloud** out)
 int pcr_cloud_assign(pcr_ctx* ctx, pcr_cloud* dst, const pcr_cloud* src)
 {
     if (!ctx || !dst || !src || dst->n != src->n) return fail(ctx, PCR_ERR_ARG, "pcr_cloud_assign");
+    if (dst == src) return PCR_OK;
     cloud_modified(dst);
+    dst->orig = nullptr;                  // (dst is in src's order now, which is not the order a sort of dst described)
+    dst->cells_tag = 0;
     PCR_HIP(ctx, hipMemcpyAsync(dst->base, src->base, 3 * src->cap * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
+    PCR_HIP(ctx, copy_gidx(ctx, dst, src));
     return PCR_OK;
 }
 
@@ -387,6 +407,7 @@ int pcr_cloud_destroy(pcr_ctx* ctx, pcr_cloud* c)
     if (ctx) hipStreamSynchronize(ctx->stream);
     cloud_forget(ctx, c);
     if (c->gidx) hipFree(c->gidx);
+    if (c->orig_buf) hipFree(c->orig_buf);
     if (c->base) hipFree(c->base);        // the caller's memory goes back to the device at once, whatever context the handle is destroyed through
     delete c;
     return PCR_OK;
@@ -423,7 +444,9 @@ int pcr_nn1_f32_loop(pcr_ctx* ctx, const pcr_cloud* tgt, const pcr_cloud* src, f
     if (!ctx || !tgt || !src || !(max_corr > 0.0f)) return fail(ctx, PCR_ERR_ARG, "pcr_nn1_f32_loop");
     const float gate = tune_get(ctx, "icp_bounded_search", 1) == 1 ? max_corr : __builtin_inff();
     const LoopHint hint(ctx, 1000);       // (the dispatcher's rule for loops, as in pcr_cloud_sort_for_target)
-    return launch_nn1(ctx, tgt, src, true, gate);
+    int rc = launch_nn1(ctx, tgt, src, true, gate);
+    if (rc == PCR_OK && !nn1_auto_grid(ctx, tgt, true, src->n)) rc = launch_nn1_gate(ctx, src->n, gate);
+    return rc;
 }
 
 int pcr_cloud_sort_for_target(pcr_ctx* ctx, const pcr_cloud* tgt, pcr_cloud* cloud, uint32_t* orig_index)
@@ -435,10 +458,9 @@ int pcr_cloud_sort_for_target(pcr_ctx* ctx, const pcr_cloud* tgt, pcr_cloud* clo
     const LoopHint hint(ctx, 1000);       // (a caller that sorts its cloud iterates: the dispatcher's rule for loops)
     int rc = nn1_auto_grid(ctx, tgt, true, n) ? grid_sort_working_cloud(ctx, tgt, &w, true) : bt_sort_working_cloud(ctx, tgt, &w, true);
     if (rc) return rc;
-    const bool sorted = ctx->work_orig_src == cloud && ctx->work_orig_n == n;
     if (orig_index && n) {
-        if (sorted) {
-            PCR_HIP(ctx, hipMemcpyAsync(orig_index, ctx->work_orig, n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        if (cloud->orig) {
+            PCR_HIP(ctx, hipMemcpyAsync(orig_index, cloud->orig, n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
             PCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
         } else {
             for (size_t i = 0; i < n; i++) orig_index[i] = (uint32_t)i;      // (the library left the order alone: small clouds, switched off)

@@ -32,8 +32,16 @@ namespace pcr {
 constexpr int GR_BLOCK = 256;
 
 // ---- two host-read counters of the index builds, through pinned words behind an event each (pcr_internal.hpp pin_words)
-static hipError_t pin_word_begin(pcr_ctx* ctx, int slot, const uint32_t* dev_word)
+// waits for the read-back of word `slot` in flight, if any; its value then stays readable in pin_words until the next read-back
+static void pin_word_settle(pcr_ctx* ctx, int slot)
 {
+    if (ctx->pin_pending[slot]) { (void)hipEventSynchronize(ctx->pin_ev[slot]); ctx->pin_pending[slot] = false; }
+}
+// starts a read-back of *dev_word into pinned word `slot` and returns its tag (0: none); the value of the previous read-back of the slot is
+// kept in the history first (a grid built between the target's build and its first loop search kept the tile search off: test_context_state.py §D)
+static hipError_t pin_word_begin(pcr_ctx* ctx, int slot, const uint32_t* dev_word, uint64_t* tag)
+{
+    *tag = 0;
     hipError_t e = hipSuccess;
     if (!ctx->pin_words) {
         e = hipHostMalloc((void**)&ctx->pin_words, 64, hipHostMallocDefault);
@@ -41,25 +49,31 @@ static hipError_t pin_word_begin(pcr_ctx* ctx, int slot, const uint32_t* dev_wor
         for (int k = 0; k < 2 && e == hipSuccess; k++) e = hipEventCreateWithFlags(&ctx->pin_ev[k], hipEventDisableTiming);
         if (e != hipSuccess) return e;
     }
+    if (ctx->pin_gen[slot]) {
+        pin_word_settle(ctx, slot);
+        const int h = (int)(ctx->pin_gen[slot] % pcr_ctx::PIN_HIST);
+        ctx->pin_hist_tag[slot][h] = ctx->pin_gen[slot];
+        ctx->pin_hist_val[slot][h] = ctx->pin_words[slot * 8];
+    }
     e = hipMemcpyAsync(&ctx->pin_words[slot * 8], dev_word, 4, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipEventRecord(ctx->pin_ev[slot], ctx->stream);
     ctx->pin_pending[slot] = e == hipSuccess;
-    if (slot == 1) ctx->pin_gen++;
+    if (e == hipSuccess) *tag = ++ctx->pin_gen[slot];
     return e;
 }
-static uint32_t work_cells_now(pcr_ctx* ctx)
+// the value of read-back `tag` of word `slot` (waits for it once), 0 when unknown (no read-back, or one that left the history)
+static uint32_t pin_word_value(pcr_ctx* ctx, int slot, uint64_t tag)
 {
-    if (ctx->pin_pending[0]) {
-        if (hipEventSynchronize(ctx->pin_ev[0]) == hipSuccess) ctx->work_cells = ctx->pin_words[0];
-        ctx->pin_pending[0] = false;
-    }
-    return ctx->work_cells;
+    if (tag == 0 || !ctx->pin_words) return 0;
+    if (tag == ctx->pin_gen[slot]) { pin_word_settle(ctx, slot); return ctx->pin_words[slot * 8]; }
+    const int h = (int)(tag % pcr_ctx::PIN_HIST);
+    return ctx->pin_hist_tag[slot][h] == tag ? ctx->pin_hist_val[slot][h] : 0u;
 }
 static uint32_t grid_occupied_now(pcr_ctx* ctx, Grid* g)
 {
-    if (g->occupied == 0 && g->occupied_tag != 0 && g->occupied_tag == ctx->pin_gen && ctx->pin_words) {      // (a later build took the word: unknown, the walk serves)
-        if (ctx->pin_pending[1]) { (void)hipEventSynchronize(ctx->pin_ev[1]); ctx->pin_pending[1] = false; }
-        g->occupied = ctx->pin_words[8];
+    if (g->occupied == 0 && g->occupied_tag != 0) {
+        g->occupied = pin_word_value(ctx, 1, g->occupied_tag);
+        if (g->occupied) g->occupied_tag = 0;
     }
     return g->occupied;
 }
@@ -1275,8 +1289,8 @@ int grid_build(pcr_ctx* ctx, const pcr_cloud* c, Grid** out, double cell_edge, i
         e = hipMemsetAsync(nzf, 0, 4, ctx->stream);
         if (e == hipSuccess) {
             hipLaunchKernelGGL(count_nonzero_kernel, dim3(256), dim3(GR_BLOCK), 0, ctx->stream, count, (uint32_t)cells, nzf);
-            e = pin_word_begin(ctx, 1, nzf);
-            g->occupied = 0; g->occupied_tag = ctx->pin_gen;
+            g->occupied = 0;
+            e = pin_word_begin(ctx, 1, nzf, &g->occupied_tag);
         }
         if (e != hipSuccess) { grid_free(g); return fail(ctx, PCR_ERR_HIP, "grid occupancy", e); }
     }
@@ -1322,7 +1336,7 @@ int grid_build(pcr_ctx* ctx, const pcr_cloud* c, Grid** out, double cell_edge, i
 // 30.6 -> 26.0 ms per search with 2^22 instead of 2^17 bins, profiles/r01_c5_10M_single_gpu.txt).  perm[] goes to ctx->qperm.
 static int sort_queries(pcr_ctx* ctx, const Grid* g, const pcr_cloud* src)
 {
-    ctx->work_cells = 0; ctx->pin_pending[0] = false;     // (coarse bins: the density of the order is unknown)
+    src->cells_tag = 0;                                   // (coarse bins: the density of the order is unknown)
     GridParams cp = g->p;
     int f = (int)tune_get(ctx, "grid_query_bin_min", 2);
     for (;;) {
@@ -1435,14 +1449,14 @@ static int sort_queries_fine(pcr_ctx* ctx, const Grid* g, const pcr_cloud* src)
     hipError_t e = sort_pairs_u64_u32(sc + 2 * a8 + a4, temp_bytes, k_in, k_out, v_in, ctx->qperm, n, begin_bit, key_bits + QKEY_SUB_BITS, ctx->stream);
     if (e != hipSuccess) return fail(ctx, PCR_ERR_HIP, "radix sort(queries)", e);
     PCR_HIP(ctx, hipGetLastError());
-    // how many cells of the target's grid the queries occupy (-> ctx->work_cells with the caller's next synchronisation; the sort's
+    // how many cells of the target's grid the queries occupy (-> pinned word 0, read with the caller's next synchronisation; the sort's
     // input keys are dead by now: their first word is the counter)
     uint32_t* runs = (uint32_t*)k_in;
-    ctx->work_cells = 0; ctx->pin_pending[0] = false;
+    src->cells_tag = 0;                                   // (the count is a property of the points: their order does not change it)
     if (tile_possible) {
         PCR_HIP(ctx, hipMemsetAsync(runs, 0, 4, ctx->stream));
         hipLaunchKernelGGL(count_key_runs_kernel, dim3(256), dim3(GR_BLOCK), 0, ctx->stream, k_out, (uint32_t)n, QKEY_SUB_BITS, runs);
-        PCR_HIP(ctx, pin_word_begin(ctx, 0, runs));
+        PCR_HIP(ctx, pin_word_begin(ctx, 0, runs, &src->cells_tag));
     }
     ctx->qperm_n = n;
     ctx->qperm_src = src;
@@ -2062,37 +2076,53 @@ __global__ __launch_bounds__(GR_BLOCK) void permute_cloud_kernel(const float* __
     dx[t] = sx[i]; dy[t] = sy[i]; dz[t] = sz[i];
 }
 
-// Re-orders the working cloud of an ICP loop into the order of the target's index (sort_queries_any), ONCE: every later search reads
-// its queries with coalesced loads (no perm indirection), writes keys / winner positions coalesced, and the Kabsch pass walks
-// pairs whose targets are neighbours in the record array.  ctx->work_orig[t] = index the point had in the caller's cloud (the
-// "last kept pair" of registration.cpp:939 is defined in that order).  The sums are exact, so the order changes no result.
-int grid_sort_working_cloud(pcr_ctx* ctx, const pcr_cloud* tgt, pcr_cloud** work, bool in_place)
+// where the original indices of a sort of w go: the caller's cloud (in_place, pcr_cloud_sort_for_target) owns them, so that no other call on the
+// context can take its mapping (test_context_state.py §B); a loop's working copy lives for one call and uses the context's buffer
+static int orig_storage(pcr_ctx* ctx, pcr_cloud* w, bool in_place, uint32_t** out)
 {
-    pcr_cloud* w = *work;
     const size_t n = w->n;
-    ctx->work_orig_src = nullptr;
-    if (n == 0 || tune_get(ctx, "grid_sort_work", 1) != 1) return PCR_OK;
-    int rc = grid_prepare_queries(ctx, tgt, w);                  // builds the target index if needed; ctx->qperm = the order
-    if (rc) return rc;
-    if (ctx->work_orig_cap < n) {                                 // (before the clone: nothing to give back on these error paths)
+    if (in_place) {
+        if (!w->orig_buf) PCR_HIP(ctx, hipMalloc((void**)&w->orig_buf, padded(n) * sizeof(uint32_t)));     // (a handle's size never changes)
+        *out = w->orig_buf;
+        return PCR_OK;
+    }
+    if (ctx->work_orig_cap < n) {
         if (ctx->work_orig) PCR_HIP(ctx, hipFree(ctx->work_orig));
         ctx->work_orig = nullptr; ctx->work_orig_cap = 0;
         PCR_HIP(ctx, hipMalloc((void**)&ctx->work_orig, padded(n) * sizeof(uint32_t)));
         ctx->work_orig_cap = padded(n);
     }
+    *out = ctx->work_orig;
+    return PCR_OK;
+}
+
+// Re-orders the working cloud of an ICP loop into the order of the target's index (sort_queries_any), ONCE: every later search reads
+// its queries with coalesced loads (no perm indirection), writes keys / winner positions coalesced, and the Kabsch pass walks
+// pairs whose targets are neighbours in the record array.  orig[t] = index the point had in the caller's cloud (the
+// "last kept pair" of registration.cpp:939 is defined in that order).  The sums are exact, so the order changes no result.
+int grid_sort_working_cloud(pcr_ctx* ctx, const pcr_cloud* tgt, pcr_cloud** work, bool in_place)
+{
+    pcr_cloud* w = *work;
+    const size_t n = w->n;
+    w->orig = nullptr;
+    if (n == 0 || tune_get(ctx, "grid_sort_work", 1) != 1) return PCR_OK;
+    int rc = grid_prepare_queries(ctx, tgt, w);                  // builds the target index if needed; ctx->qperm = the order
+    if (rc) return rc;
+    uint32_t* orig = nullptr;
+    if ((rc = orig_storage(ctx, w, in_place, &orig))) return rc;   // (before the clone: nothing to give back on these error paths)
     pcr_cloud* sorted = nullptr;
     rc = cloud_alloc(ctx, n, &sorted);                            // same size; the permute writes all of it, padding included
     if (rc) return rc;
     hipLaunchKernelGGL(permute_cloud_kernel, dim3((unsigned)((sorted->cap + GR_BLOCK - 1) / GR_BLOCK)), dim3(GR_BLOCK), 0, ctx->stream, w->x(), w->y(), w->z(), ctx->qperm,
                        (uint32_t)n, sorted->x(), sorted->y(), sorted->z(), (uint32_t)sorted->cap);
     hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(ctx->work_orig, ctx->qperm, n * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(orig, ctx->qperm, n * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream);
     if (e != hipSuccess) { pcr_cloud_destroy(ctx, sorted); return fail(ctx, PCR_ERR_HIP, "grid_sort_working_cloud", e); }
+    sorted->cells_tag = w->cells_tag;                              // (the same points: the same occupied cells)
     if (in_place) { std::swap(w->base, sorted->base); std::swap(w, sorted); cloud_modified(sorted); }   // the caller's handle keeps its identity and gets the sorted buffer
     cloud_release(ctx, w);                                         // (no synchronisation: the permute above still reads it — the buffer stays allocated)
     *work = sorted;
-    ctx->work_orig_src = sorted;
-    ctx->work_orig_n = n;
+    sorted->orig = orig;
     ctx->qperm_src = nullptr;                                      // the permutation belongs to the cloud that no longer exists
     return PCR_OK;
 }
@@ -2101,13 +2131,13 @@ int grid_sort_working_cloud(pcr_ctx* ctx, const pcr_cloud* tgt, pcr_cloud** work
 // The queries of a wave then lie next to each other: the slices that can matter to them coincide, so most (wave, slice) pairs are
 // settled for the whole wave by the published bound, and the queries a slice cannot settle cluster in few (wave, slice) pairs instead
 // of one here, one there (a source cloud in random order is the worst case: measured 0.620 -> 0.600 ms per 120 k x 120 k search).
-// ctx->work_orig[t] = the index the point had in the caller's cloud, as in grid_sort_working_cloud; the sums are exact, so the
+// orig[t] = the index the point had in the caller's cloud, as in grid_sort_working_cloud; the sums are exact, so the
 // order changes no result.  Costs one key kernel, one 30-bit radix sort and one gather.
 int bt_sort_working_cloud(pcr_ctx* ctx, const pcr_cloud* tgt, pcr_cloud** work, bool in_place)
 {
     pcr_cloud* w = *work;
     const size_t n = w->n;
-    ctx->work_orig_src = nullptr;
+    w->orig = nullptr;
     if (n < 4096 || n > 0x7FFFFFF0ull || tune_get(ctx, "bt_sort_work", 1) != 1) return PCR_OK;
     int rc = bt_ensure(ctx, tgt);
     if (rc) return rc;
@@ -2124,17 +2154,11 @@ int bt_sort_working_cloud(pcr_ctx* ctx, const pcr_cloud* tgt, pcr_cloud** work, 
     uint32_t* v_in = (uint32_t*)(sc + 2 * a8);
     uint32_t* v_out = (uint32_t*)(sc + 2 * a8 + a4);
     char* temp = sc + 2 * a8 + 2 * a4;
-    if (ctx->work_orig_cap < n) {                                 // (before the clone: nothing to give back on these error paths)
-        if (ctx->work_orig) PCR_HIP(ctx, hipFree(ctx->work_orig));
-        ctx->work_orig = nullptr; ctx->work_orig_cap = 0;
-        PCR_HIP(ctx, hipMalloc((void**)&ctx->work_orig, padded(n) * sizeof(uint32_t)));
-        ctx->work_orig_cap = padded(n);
-    }
+    if ((rc = orig_storage(ctx, w, in_place, &v_out))) return rc;  // (the sorted values ARE the original indices: no copy behind the sort)
     pcr_cloud* sorted = nullptr;
     rc = cloud_alloc(ctx, n, &sorted);                            // same size; the permute writes all of it, padding included
     if (rc) return rc;
     const unsigned blocks = (unsigned)((n + GR_BLOCK - 1) / GR_BLOCK);
-    v_out = ctx->work_orig;                                       // (the sorted values ARE the original indices: no copy behind the sort)
     hipLaunchKernelGGL(bt_keys_kernel, dim3(blocks), dim3(GR_BLOCK), 0, ctx->stream, w->x(), w->y(), w->z(), (uint32_t)n, bt->key_lo[0], bt->key_lo[1],
                        bt->key_lo[2], bt->key_inv, bt->key_inv, bt->key_inv, k_in, v_in, 0);
     // (tune bt_sort_begin_bit: the low bits of the Morton key the sort ignores — the order inside the cells they span stays the caller's; every
@@ -2147,11 +2171,11 @@ int bt_sort_working_cloud(pcr_ctx* ctx, const pcr_cloud* tgt, pcr_cloud** work, 
         e = hipGetLastError();
     }
     if (e != hipSuccess) { pcr_cloud_destroy(ctx, sorted); return fail(ctx, PCR_ERR_HIP, "bt_sort_working_cloud", e); }
+    sorted->cells_tag = w->cells_tag;
     if (in_place) { std::swap(w->base, sorted->base); std::swap(w, sorted); cloud_modified(sorted); }
     cloud_release(ctx, w);                                         // (no synchronisation: the permute above still reads it — the buffer stays allocated)
     *work = sorted;
-    ctx->work_orig_src = sorted;
-    ctx->work_orig_n = n;
+    sorted->orig = v_out;
     return PCR_OK;
 }
 
@@ -2251,7 +2275,7 @@ int launch_nn1_grid(pcr_ctx* ctx, const pcr_cloud* tgt, const pcr_cloud* src, bo
     if (rc) return rc;
     ctx->keys_n = ns;
     // the working cloud of an ICP loop is already in cell order (grid_sort_working_cloud): no permutation to read
-    const bool sorted = reuse_perm && ctx->work_orig_src == src && ctx->work_orig_n == ns && tgt->grid;
+    const bool sorted = reuse_perm && src->orig && tgt->grid;
     const bool have_perm = sorted || (reuse_perm && tgt->grid && ctx->qperm && ctx->qperm_n == ns && ctx->qperm_src == src);
     if (!have_perm) {
         rc = grid_prepare_queries(ctx, tgt, src);
@@ -2342,7 +2366,7 @@ int launch_nn1_grid(pcr_ctx* ctx, const pcr_cloud* tgt, const pcr_cloud* src, bo
     // the 10 M pair, 1.44 against 1.04 ms (tile ahead) at 1 / 2 — profiles/r03_c5_tile_search.txt.  Density = queries per occupied cell of
     // the target's grid against targets per occupied cell; a spatially compact shard keeps its local density and the tile search.
     // (both counters come back through pinned words behind an event: the first search after a sort / a build waits for them here, once)
-    const uint32_t work_cells = (tile_tune != 2 && tgt->n >= 4000000) ? work_cells_now(ctx) : 0u, occupied = work_cells ? grid_occupied_now(ctx, tgt->grid) : 0u;
+    const uint32_t work_cells = (tile_tune != 2 && tgt->n >= 4000000) ? pin_word_value(ctx, 0, src->cells_tag) : 0u, occupied = work_cells ? grid_occupied_now(ctx, tgt->grid) : 0u;
     const bool dense = work_cells > 0 && occupied > 0 && (double)ns / (double)work_cells >= 0.4 * (double)tgt->n / (double)occupied;
     // (round 4: the FIRST search of a loop too — warm == 0: no correspondences yet — where the sign tile search can make itself a seed per query:
     // stile_seed_kernel, tune grid_stile_cold: 2 = the plain walk as before)

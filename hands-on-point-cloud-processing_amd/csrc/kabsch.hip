@@ -392,7 +392,7 @@ int launch_kabsch_partial(pcr_ctx* ctx, const pcr_cloud* tgt, const pcr_cloud* s
     const uint32_t blocks = kabsch_blocks(ctx, ns);
     // the grid search of an ICP loop leaves the record position of every winner behind (ctx->wpos): gather from the records
     const bool rec = ctx->wpos_valid && ctx->wpos_n == ns && tgt->grid && tgt->grid->records && tune_get(ctx, "kabsch_records", 1) == 1;
-    const uint32_t* orig = (ctx->work_orig && ctx->work_orig_n == ns && ctx->work_orig_src == src) ? ctx->work_orig : nullptr;
+    const uint32_t* orig = src->orig;     // (the cloud's own mapping: no other call on the context resets it — test_context_state.py §B)
     {
         ProfScope p(ctx, "kabsch_partial");
         const uint32_t per_block = (uint32_t)((ns + blocks - 1) / blocks);      // as the kernel computes it

@@ -1172,6 +1172,24 @@ __global__ __launch_bounds__(NN_BLOCK) void bt_seed_morton_kernel(const float4* 
     keys[i] = key;
 }
 
+// a caller's loop search is bounded by its gate (pcr.h pcr_nn1_f32_loop): a key at or beyond it becomes "none", as the grid search returns it
+// (test_context_state.py §A / §E: the exhaustive path returned the neighbour outside the gate)
+__global__ __launch_bounds__(NN_BLOCK) void nn1_gate_kernel(unsigned long long* __restrict__ keys, uint32_t ns, float gate)
+{
+    const uint32_t i = blockIdx.x * NN_BLOCK + threadIdx.x;
+    if (i >= ns) return;
+    const unsigned long long k = keys[i];
+    if ((uint32_t)k != 0xFFFFFFFFu && !(__uint_as_float((uint32_t)(k >> 32)) < gate)) keys[i] = (0x7F800000ull << 32) | 0xFFFFFFFFull;   // none: (+inf, UINT32_MAX)
+}
+
+int launch_nn1_gate(pcr_ctx* ctx, size_t ns, float gate)
+{
+    if (ns == 0 || !(gate < __builtin_inff())) return PCR_OK;
+    hipLaunchKernelGGL(nn1_gate_kernel, dim3((unsigned)((ns + NN_BLOCK - 1) / NN_BLOCK)), dim3(NN_BLOCK), 0, ctx->stream, ctx->keys, (uint32_t)ns, gate);
+    PCR_HIP(ctx, hipGetLastError());
+    return PCR_OK;
+}
+
 // keys -> (idx, d2) split for the host-facing API
 __global__ void nn1_unpack_kernel(const unsigned long long* __restrict__ keys, uint32_t n,
                                   uint32_t* __restrict__ idx, float* __restrict__ d2)
@@ -1309,12 +1327,15 @@ static int launch_matrix(pcr_ctx* ctx, const pcr_cloud* tgt, const pcr_cloud* sr
         // first search of a fresh pair, 120 k, three pairs: 0.147 / 0.295 / 0.290 -> 0.095 / 0.159 / 0.212 ms; a one-shot search of unsorted queries 0.366 ->
         // 0.304 ms, 6.5 -> 2.4 chunks evaluated per query — and the centre alone where stale correspondences are merged in: 0.185 against 0.194 ms)
         const int64_t seed_tune = tune_get(ctx, "nn1_seed_mode", 0), seed_mode = seed_tune ? seed_tune : (cold_seed ? 3 : 1);
-        if ((cold_seed || reseed) && seed_mode >= 2 && g->key_inv > 0.f)
+        // the centre seed merges only with what this search wrote: without the Morton seed (a target of zero extent, or one below the Morton lattice:
+        // key_inv = 0) a cold search's keys[] still holds an earlier search's keys (test_context_state.py §A)
+        const bool morton = (cold_seed || reseed) && seed_mode >= 2 && g->key_inv > 0.f;
+        if (morton)
             hipLaunchKernelGGL(bt_seed_morton_kernel, dim3((unsigned)((ns + NN_BLOCK - 1) / NN_BLOCK)), dim3(NN_BLOCK), 0, ctx->stream, g->records, n_super * BT_SUPER,
                                g->key_lo[0], g->key_lo[1], g->key_lo[2], g->key_inv, src->x(), src->y(), src->z(), (uint32_t)ns, ctx->keys, reseed ? 1 : 0);
         if ((cold_seed || reseed) && (seed_mode < 2 || seed_mode == 3 || !(g->key_inv > 0.f)))          // (inside the timed scope: it is part of the search)
             hipLaunchKernelGGL(bt_seed_kernel, dim3((unsigned)((ns + NN_BLOCK - 1) / NN_BLOCK)), dim3(NN_BLOCK), 0, ctx->stream, g->centres, g->records, n_super,
-                               std::max<uint32_t>(1u, n_super / 1024u), src->x(), src->y(), src->z(), (uint32_t)ns, ctx->keys, (reseed || seed_mode == 3) ? 1 : 0,
+                               std::max<uint32_t>(1u, n_super / 1024u), src->x(), src->y(), src->z(), (uint32_t)ns, ctx->keys, (reseed || (morton && seed_mode == 3)) ? 1 : 0,
                                (sphere && tune_get(ctx, "nn1_seed_levels", 0) != 1) ? g->l1_centres : (const float4*)nullptr, (uint32_t)g->n_l1_super);
         // XCD-aware launch (tune nn1_xcd: 1 / 2 / 4 = query-block groups per 8 XCDs, -1 = the plain 2-D launch): see the kernel
         // STRACK: entries in a wave's list from which the end of a super-tile evaluates them (tune nn1_sign_flush; the end of the slice always does)

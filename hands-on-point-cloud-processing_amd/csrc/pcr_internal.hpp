@@ -83,6 +83,13 @@ struct pcr_cloud {
     // a SHARD of a larger cloud (pcr_cloud_shard_spatial): the index every point has in the whole cloud, ascending (device, n entries).
     // "The last kept pair" of an iteration (registration.cpp:939) is then the kept pair with the largest GLOBAL index over all ranks.
     uint32_t* gidx = nullptr;
+    // a cloud in the order of a target's index (pcr_cloud_sort_for_target, or the sorted working copy of an ICP loop): orig[t] = the index its
+    // point t had before the sort (device, n entries), nullptr for a cloud in its own order.  The caller's clouds own the buffer (orig_buf); a
+    // loop's working copy points into ctx->work_orig.  Kept by cloud_modified: a transform keeps the order (tests/test_context_state.py §B)
+    uint32_t* orig = nullptr;
+    uint32_t* orig_buf = nullptr;
+    // which read-back of the context's pinned word 0 counts the target-grid cells this cloud's points occupy (0: none; pcr_ctx::pin_words)
+    mutable uint64_t cells_tag = 0;
     float* x() const { return base; }
     float* y() const { return base + cap; }
     float* z() const { return base + 2 * cap; }
@@ -120,21 +127,23 @@ struct pcr_ctx {
     size_t wpos_cap = 0;
     size_t wpos_n = 0;
     bool wpos_valid = false;
-    uint32_t* work_orig = nullptr;
+    uint32_t* work_orig = nullptr;        // (the storage of the working copy's pcr_cloud::orig)
     size_t work_orig_cap = 0;
-    size_t work_orig_n = 0;
-    const pcr_cloud* work_orig_src = nullptr;
     // two spare cloud buffers (base, cap): the working copies an ICP call clones and gives back (cloud_release) are re-used by the next
     // clone of the same size instead of two hipMalloc + two hipFree (each free a device synchronisation) per call
     float* spare_base[2] = { nullptr, nullptr };
     size_t spare_cap[2] = { 0, 0 };
-    uint32_t work_cells = 0;              // distinct target-grid cells the sorted working cloud occupies (0: unknown); read through work_cells_now()
     // two counters of the index builds come back through PINNED words behind an event each (a hipMemcpyAsync into pageable memory is ordered only
-    // by what the runtime happens to do): [0] work_cells, [1] the occupied cells of the grid built last (Grid::occupied_tag says whose)
+    // by what the runtime happens to do): [0] the target-grid cells a sorted query cloud occupies (pcr_cloud::cells_tag says whose), [1] the occupied
+    // cells of a grid (Grid::occupied_tag says whose).  pin_gen[k] numbers the read-backs of word k; before the next one overwrites it, the value of the
+    // last one moves into pin_hist (a ring of the latest PIN_HIST per word), so a later build never takes it from its owner (test_context_state.py §D)
+    static constexpr int PIN_HIST = 8;
     uint32_t* pin_words = nullptr;
     hipEvent_t pin_ev[2] = { nullptr, nullptr };
     bool pin_pending[2] = { false, false };
-    uint64_t pin_gen = 0;
+    uint64_t pin_gen[2] = { 0, 0 };
+    uint64_t pin_hist_tag[2][PIN_HIST] = {};
+    uint32_t pin_hist_val[2][PIN_HIST] = {};
     double* partials = nullptr;           // block rows of the Kabsch pass (8192 x 58 doubles)
     size_t partials_cap = 0;
     double* dev_out = nullptr;            // 128 doubles: reduced sums / limbs + bookkeeping
@@ -205,6 +214,8 @@ int st_sphere_selftest(pcr_ctx* ctx, int trials, unsigned long long res[4]);   /
 int st_sign_selftest(pcr_ctx* ctx, int trials, unsigned long long res[4]);   // nn1_brute.hip: the sign form's decision, checked on the device
 bool mfma_verdict(pcr_ctx* ctx, bool f16);     // cached per context; runs the short self-test on first use
 int launch_nn1_brute(pcr_ctx* ctx, const pcr_cloud* tgt, const pcr_cloud* src, bool in_loop);
+// keys[i] of the last search <- none where d2 >= gate (the exhaustive kernels are not bounded by a caller's loop gate)
+int launch_nn1_gate(pcr_ctx* ctx, size_t ns, float gate);
 int launch_nn1_brute_list(pcr_ctx* ctx, const pcr_cloud* tgt, const pcr_cloud* src, const uint32_t* qlist, const uint32_t* qcount, uint32_t qcap);
 // cap2: the caller only uses neighbours with d2 < cap2 (ICP's max_corres_dist gate) — the walk may stop once no such target can exist
 int launch_nn1_grid(pcr_ctx* ctx, const pcr_cloud* tgt, const pcr_cloud* src, bool reuse_perm, float cap2);

@@ -56,6 +56,8 @@ int pcr_ctx_device_info(const pcr_ctx* ctx, char* arch, size_t arch_cap, int* n_
 
 /* ---- clouds --------------------------------------------------------------------------------------- */
 int pcr_cloud_create(pcr_ctx* ctx, const float* host_xyz, size_t n, int layout, pcr_cloud** out);
+/* clone and assign copy a spatial shard's global indices with its points (pcr_cloud_global_index answers the same for the copy); assign
+ * drops dst's own when src has none, and dst loses the mapping of an earlier pcr_cloud_sort_for_target (it is now in src's order) */
 int pcr_cloud_clone(pcr_ctx* ctx, const pcr_cloud* src, pcr_cloud** out);
 int pcr_cloud_assign(pcr_ctx* ctx, pcr_cloud* dst, const pcr_cloud* src);   /* dst <- src, same size, on device */
 int pcr_cloud_read(pcr_ctx* ctx, const pcr_cloud* c, float* host_xyz, int layout);

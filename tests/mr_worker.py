@@ -201,6 +201,8 @@ def main():
         full_far = ctx.cloud(src_far)
         Tf, stf = ctx.icp_point2point(full_far, ct, max_corr=1.0, max_iter=6, eps=1e-8)
         spf = ctx.shard_spatial(ct, full_far, world, rank, 5)
+        spc = spf.clone()                        # a copy of a shard is that shard: same global indices, so the same order key and loss
+        assert np.array_equal(ctx.global_index(spc), ctx.global_index(spf))
         for method in (1, 2):
             ctx.tune("nn_method", method)
             for pipe in (0, -1):
@@ -208,7 +210,10 @@ def main():
                 ctx.comm_init_callback(world, rank, allreduce)
                 T5, st5 = ctx.icp_point2point(sp, ct, max_corr=1.0, max_iter=8, eps=1e-8)
                 T6, st6 = ctx.icp_point2point(spf, ct, max_corr=1.0, max_iter=6, eps=1e-8)
+                T7, st7 = ctx.icp_point2point(spc, ct, max_corr=1.0, max_iter=6, eps=1e-8)
                 ctx.comm_destroy()
+                assert np.array_equal(T6.view(np.uint32), T7.view(np.uint32)) and st7["last_pairs"] == st6["last_pairs"], (method, pipe)
+                assert np.float32(st6["last_loss"]).view(np.uint32) == np.float32(st7["last_loss"]).view(np.uint32), (method, pipe, st6, st7)
                 assert np.array_equal(T1.view(np.uint32), T5.view(np.uint32)) and st5["last_pairs"] == st1["last_pairs"], (method, pipe)
                 assert np.float32(st1["last_loss"]).view(np.uint32) == np.float32(st5["last_loss"]).view(np.uint32), (method, pipe)
                 assert np.array_equal(Tf.view(np.uint32), T6.view(np.uint32)) and st6["last_pairs"] == stf["last_pairs"], (method, pipe)

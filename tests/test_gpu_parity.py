@@ -320,6 +320,8 @@ def test_nn1_ragged_sizes_vs_oracle(ctx, orc, synth, qpl, ns, nt, variant):
     src, tgt = np.ascontiguousarray(src[:, :ns]), np.ascontiguousarray(tgt[:, :nt])
     cs, ct = ctx.cloud(src), ctx.cloud(tgt)
     idx, d2 = ctx.nn1(ct, cs)
+    if variant == 10:                         # every size here fits f16 and the sphere index: the forced kernel really ran
+        assert ctx.mfma_check()["last_nn1_kernel"] == "strack3", (ns, nt)
     oidx, od2 = orc.nn1_f32(tgt, src)
     assert np.array_equal(idx, oidx) and np.array_equal(bits32(d2), bits32(od2))
     cs.free(); ct.free()
@@ -352,6 +354,8 @@ def test_nn1_ties_and_duplicates_pick_lowest_index(ctx, orc, synth, variant):
     ctx.tune("nn1_tiles_per_slice", 1)
     cs, ct = ctx.cloud(src), ctx.cloud(tgt)
     idx, d2 = ctx.nn1(ct, cs)
+    if variant == 10:
+        assert ctx.mfma_check()["last_nn1_kernel"] == "strack3"
     ctx.tune("nn1_tiles_per_slice", 0)
     oidx, od2 = orc.nn1_f32(tgt, src)
     ctx.tune("nn1_variant", 0)
@@ -1069,7 +1073,7 @@ def test_spatial_shards_are_a_partition_and_keep_the_scene_dense(pcr, synth):
         assert len(e) == 0 and ctx.global_index(e).size == 0
 
 
-def test_caller_stepped_loop_equals_icp_call(pcr, synth):
+def test_caller_stepped_loop_equals_icp_call(pcr, orc, synth):
     """pcr_cloud_sort_for_target + pcr_nn1_f32_loop + pcr_kabsch_sums + pcr_kabsch_solve + pcr_transform_f32 stepped by the caller
     = pcr_icp_p2p_f32, pose bits and kept pairs, with the exact grid and with the exhaustive search (registration.cpp:917-1006)."""
     for n, method in ((30000, 2), (30000, 1), (3000, 0)):
@@ -1083,9 +1087,16 @@ def test_caller_stepped_loop_equals_icp_call(pcr, synth):
             assert np.array_equal(np.sort(orig), np.arange(n, dtype=np.uint32))
             assert np.array_equal(work.numpy(), src[:, orig])
             T = np.eye(4, dtype=np.float32)
+            inv = np.argsort(orig)
             for it in range(6):
+                cur = work.numpy()[:, inv]                       # the moved cloud in the original order
                 ctx.nn1_loop(ct, work, 1.0)
                 sums, last, _ = ctx.kabsch_sums(ct, work, 1.0)
+                idx, d2 = ctx.nn1_fetch(n)
+                gi, gd = np.empty_like(idx), np.empty_like(d2)
+                gi[orig], gd[orig] = idx, d2
+                # pcr.h: last_kept in the ORIGINAL numbering for a cloud sorted by pcr_cloud_sort_for_target
+                assert last == orc.kabsch_accumulate(cur, tgt, gi, gd, 1.0)[1], (n, method, it)
                 rc, R, t = pcr.kabsch_solve(sums)
                 assert rc == 0
                 Td = np.eye(4, dtype=np.float32); Td[:3, :3], Td[:3, 3] = R, t
