@@ -63,7 +63,7 @@ ABI_SYMBOLS = [
     "pcr_nn1_desc_f32", "pcr_match_union_f32", "pcr_match_inter_f32", "pcr_ransac_sample_quads", "pcr_consensus_count_f32", "pcr_ransac_global_f32", "pcr_db64_create", "pcr_db64_destroy", "pcr_db64_size", "pcr_db64_knn", "pcr_db64_radius",
     "pcr_ctx_trim", "pcr_ctx_parked_bytes", "pcr_cloud_shard_spatial", "pcr_cloud_global_index", "pcr_cloud_sort_for_target", "pcr_nn1_f32_loop",
     "pcr_db64_radius_rows", "pcr_rows_destroy", "pcr_rows_info", "pcr_rows_row_ptr", "pcr_rows_fetch", "pcr_rows_reduce", "pcr_rows_moments",
-    "pcr_dbscan_f32", "pcr_statistical_outlier_f32",
+    "pcr_dbscan_f32", "pcr_statistical_outlier_f32", "pcr_fpfh33_f32",
 ]
 
 
@@ -155,6 +155,7 @@ def lib():
     L.pcr_ground_detection_f64.argtypes = [vp, vp, C.c_int, sz, C.c_double, vp, vp, C.POINTER(C.c_uint64)]
     L.pcr_dbscan_f32.argtypes = [vp, vp, C.c_double, C.c_int, vp, vp, vp, C.POINTER(C.c_uint64)]
     L.pcr_statistical_outlier_f32.argtypes = [vp, vp, C.c_int, C.c_double, vp, vp, vp, C.POINTER(C.c_uint64), C.POINTER(vp)]
+    L.pcr_fpfh33_f32.argtypes = [vp, vp, vp, vp, C.c_float, vp, vp, vp]
     L.pcr_nn1_desc_f32.argtypes = [vp, vp, sz, vp, sz, C.c_int, vp, vp]
     L.pcr_match_union_f32.argtypes = [vp, vp, sz, vp, sz, C.c_int, C.c_float, vp, vp, C.POINTER(sz)]
     L.pcr_match_inter_f32.argtypes = [vp, vp, sz, vp, sz, C.c_int, C.c_float, vp, vp, C.POINTER(sz)]
@@ -632,6 +633,26 @@ class Context:
         kept = Cloud(self, h)
         assert len(kept) == nk.value
         return keep[:n].astype(bool), avg[:n], (float(st[0]), float(st[1]), float(st[2])), kept
+
+    # ---- Homework9 descriptors
+    def fpfh33(self, surface: Cloud, normals, radius: float, keypoints=None, spfh: bool = False):
+        """getFPFH33Descriptors (hw9 registration.cpp:254-269, PCL FPFHEstimation with radius `radius`) -> (fpfh f32 [m,33], |N(q)| u32 [m])
+        or (fpfh, counts, spfh f32 [n,33]); the contract of pcr_fpfh33_f32.  normals: a Cloud or an [n,3] array (cast to f32: ctx.normals()
+        returns f64); keypoints: a Cloud, an [m,3] array or None (= the surface itself)."""
+        if not isinstance(normals, Cloud):
+            normals = self.cloud(np.asarray(normals, np.float32).reshape(-1, 3), PCR_AOS3)
+        if keypoints is not None and not isinstance(keypoints, Cloud):
+            keypoints = self.cloud(np.asarray(keypoints, np.float32).reshape(-1, 3), PCR_AOS3)
+        n = len(surface)
+        m = n if keypoints is None else len(keypoints)
+        out = np.zeros((max(m, 1), 33), np.float32)
+        cnt = np.zeros(max(m, 1), np.uint32)
+        sp = np.zeros((max(n, 1), 33), np.float32) if spfh else None
+        self._ck(lib().pcr_fpfh33_f32(self.h, surface.h, normals.h, None if keypoints is None else keypoints.h, float(radius), out.ctypes.data,
+                                      cnt.ctypes.data, None if sp is None else sp.ctypes.data))
+        if spfh:
+            return out[:m], cnt[:m], sp[:n]
+        return out[:m], cnt[:m]
 
     # ---- N4
     def nn1_desc(self, db, q):

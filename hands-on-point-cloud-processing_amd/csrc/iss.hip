@@ -41,72 +41,6 @@ __device__ __forceinline__ float hw7_s(float tx, float ty, float tz, float qx, f
     return s;
 }
 
-// the 9 x-rows of the 27-cell block around cell (cx, cy, cz): row k -> [begin, end) in records
-__device__ __forceinline__ void row_range(const GridParams& g, const uint32_t* __restrict__ cell_start, int cx, int cy, int cz, int k,
-                                          uint32_t& b, uint32_t& e)
-{
-    const int yy = cy + (k % 3) - 1, zz = cz + (k / 3) - 1;
-    if (yy < 0 || yy >= g.n[1] || zz < 0 || zz >= g.n[2]) { b = e = 0; return; }
-    const int x0 = max(cx - 1, 0), x1 = min(cx + 1, g.n[0] - 1);
-    const uint32_t row = (uint32_t)((zz * g.n[1] + yy) * g.n[0]);
-    b = cell_start[row + x0];
-    e = cell_start[row + x1 + 1];
-}
-
-// The records of a row are sorted by x (grid_build): cut [b, e) to the records with lo <= x <= hi, the only ones that can
-// lie within the radius.  Two bounded binary searches, worth it on long rows only; uniform over the lanes of a group.
-__device__ __forceinline__ void clip_row_x(const float4* __restrict__ records, uint32_t& b, uint32_t& e, float lo, float hi)
-{
-    if (e - b <= 384u) return;
-    uint32_t l = b, h = e;
-    for (int it = 0; it < 32 && l < h; it++) {
-        const uint32_t mid = l + ((h - l) >> 1);
-        if (records[mid].x < lo) l = mid + 1; else h = mid;
-    }
-    const uint32_t nb = l;
-    h = e;
-    for (int it = 0; it < 32 && l < h; it++) {
-        const uint32_t mid = l + ((h - l) >> 1);
-        if (records[mid].x <= hi) l = mid + 1; else h = mid;
-    }
-    b = nb;
-    e = l;
-}
-
-// [lo, hi] around qx that contains every x whose hw7 sum can still be <= s_max: |dx|^2 <= s_max (1 + 3 * 2^-24); the floor
-// 1e-18 covers differences whose squares vanish in f32 (|e| < 3.7e-23 gives s == 0), the pad the rounding of qx -+ d
-__device__ __forceinline__ void radius_window(float qx, float s_max, float& lo, float& hi)
-{
-    const float d = sqrtf(fmaxf(s_max, 0.0f)) * 1.00001f + 1e-18f;
-    const float pad = (fabsf(qx) + d) * 2.4e-7f;
-    lo = qx - d - pad;
-    hi = qx + d + pad;
-}
-
-template <int G>
-__device__ __forceinline__ unsigned group_sum_u32(unsigned v)
-{
-#pragma unroll
-    for (int o = G / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, G);
-    return v;
-}
-template <int G>
-__device__ __forceinline__ double group_sum_f64(double v)
-{
-#pragma unroll
-    for (int o = G / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, G);
-    return v;
-}
-
-// cells of a query: every point of the cloud lies inside the grid box, non-finite ones were binned into cell 0 and
-// never pass a distance test (inf - inf = NaN)
-__device__ __forceinline__ void query_cell(const GridParams& g, const float4& q, int& cx, int& cy, int& cz)
-{
-    cx = min(max(cell_coord(q.x, g.lo[0], g.inv_h), 0), g.n[0] - 1);
-    cy = min(max(cell_coord(q.y, g.lo[1], g.inv_h), 0), g.n[1] - 1);
-    cz = min(max(cell_coord(q.z, g.lo[2], g.inv_h), 0), g.n[2] - 1);
-}
-
 template <int G>
 __global__ __launch_bounds__(ISS_BLOCK) void iss_count_kernel(const float4* __restrict__ records, const uint32_t* __restrict__ cell_start,
                                                               GridParams g, uint32_t n, float s_max, uint32_t* __restrict__ cnt_sorted,

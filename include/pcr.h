@@ -279,6 +279,41 @@ int pcr_dbscan_f32(pcr_ctx* ctx, const pcr_cloud* cloud, double eps, int min_poi
 int pcr_statistical_outlier_f32(pcr_ctx* ctx, const pcr_cloud* cloud, int nb_neighbors, double std_ratio, uint8_t* keep, double* avg_dist,
                                 double stats3[3], uint64_t* n_kept, pcr_cloud** kept_cloud);
 
+/* ---- Homework9 descriptors: FPFH33, getFPFH33Descriptors (Homework9/hw9/src/registration.cpp:254-269, PCL FPFHEstimationOMP) --
+ * PCL is not pinned here: this is the library's own operation sequence, a restatement of PCL's FPFHEstimation.
+ * Inputs: surface (n points), normals (one per surface point, a cloud whose x/y/z are normal_x/y/z, used as given, not
+ * re-normalised), keypoints (m query points; NULL = the surface itself, m = n), radius.  All arithmetic below is unfused.
+ * Neighbourhood (FLANN's radius search at dim 3): N(q) = { j in surface : s(q, j) < r2 }, STRICT, with
+ *   s = ((dx*dx) + dy*dy) + dz*dz in f32 and r2 = (float)((double)radius * (double)radius).  A non-finite surface point is
+ *   nobody's neighbour; a surface point is its own neighbour.
+ * Pair features computePairFeatures(p1 = centre, n1, p2 = neighbour, n2), f32, dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z,
+ * cross(a, b) = (a.y*b.z - a.z*b.y, a.z*b.x - a.x*b.z, a.x*b.y - a.y*b.x):
+ *   a pair with a non-finite normal at either end is skipped (the library's rule; PCL's behaviour there is undefined);
+ *   dp = p2 - p1, f4 = sqrtf(dot(dp, dp)), skipped if f4 == 0; a1 = dot(n1, dp) / f4, a2 = dot(n2, dp) / f4;
+ *   swap iff |a1| <= 1 && |a2| <= 1 && |a1| < |a2| (PCL: acos(|a1|) > acos(|a2|), NaN above 1): then exchange n1 and n2,
+ *   negate dp and f3 = -a2, else f3 = a1;  v = cross(dp, n1), vn = sqrtf(dot(v, v)), skipped if vn == 0, v = v / vn (three
+ *   divides);  w = cross(n1, v);  f2 = dot(v, n2);  f1 = (float)atan2((double)dot(w, n2), (double)dot(n1, n2)) (f64 atan2).
+ * Bins (PCL's double arithmetic on the f32 features), each floor()ed and clamped to [0, 10] (NaN -> 0):
+ *   b1 = 11 * (((double)f1 + M_PI) * (double)(1.0f / (2.0f * (float)M_PI))), b2 = 11 * (((double)f2 + 1.0) * 0.5), b3 the same on f3;
+ *   the 33 slots are [f1 bins | f2 bins | f3 bins] (FPFHSignature33).
+ * SPFH of surface point p: incr = 100.0f / (float)(|N(p)| - 1); every pair (p, j), j in N(p), j != p BY INDEX, that is not
+ *   skipped adds incr to its three bins; a bin's value is incr added to 0.0f cnt times in f32 (equal addends: independent of
+ *   order, equal to PCL's repeated +=).  A point with |N(p)| == 0 (non-finite) has an all-zero SPFH.
+ * FPFH of keypoint q: for j in N(q) with s(q, j) != 0, w = 1.0f / s(q, j) (the SQUARED distance, as PCL's
+ *   weightPointSPFHSignature), val_b = spfh_j[b] * w in f32; per sub-histogram acc_b and sum are accumulated in f64 and
+ *   out_b = (float)(acc_b * (100.0 / sum)), or acc_b unchanged when sum == 0.  The keypoint's own SPFH is NOT added (PCL's
+ *   behaviour, not the paper's nor Open3D's).  A non-finite keypoint or one with empty N(q) gets a row of NaN (PCL computeFeature).
+ * Order: PCL accumulates the histogram in f32 in FLANN's distance order; here the f64 accumulation order is free (lanes of a
+ *   group, then a fixed shuffle tree).  Promise: every run gives the same bits; results agree with the exact-order
+ *   restatement (f64 in ascending-s order) to <= 1 f32 ulp per slot.  UNPINNED: PCL's f32 accumulation order and FLANN's strict
+ *   `<`, which are restated here and not checked against PCL.
+ * fpfh: m x 33 row-major (required); neighbor_counts (optional, m) = |N(q)|; spfh (optional, n x 33) = every surface point's SPFH.
+ * PCR_ERR_ARG for a radius that is non-finite or <= 0, or a normal cloud whose size differs from the surface's; an empty
+ * surface or no keypoints: PCR_OK with nothing written.  Tune key fpfh_lanes (lanes per query: 1, 2, 4, 8, 16, 32); profile
+ * names fpfh_grid_build, fpfh_spfh, fpfh_weight. */
+int pcr_fpfh33_f32(pcr_ctx* ctx, const pcr_cloud* surface, const pcr_cloud* normals, const pcr_cloud* keypoints, float radius, float* fpfh,
+                   uint32_t* neighbor_counts, float* spfh);
+
 /* ---- next row N4: global-registration front half, Homework9/hw9/src/registration.cpp:288-434, :535-615 -----------
  * N4a: exhaustive 1-NN between two descriptor sets (row-major n x dim / m x dim f32, host memory; dim 33 = FPFH),
  * nanoflann's evalMetric arithmetic for any dim (nanoflann.hpp:382-405: groups of four + tail, f32, unfused), canonical
@@ -446,7 +481,7 @@ int pcr_ctx_mfma_check(pcr_ctx* ctx, int run_now, pcr_mfma_check* out);
  *  ICP loop    icp_pipeline [0 = 1 device-resident] -1 synchronous · icp_chunk [4] · icp_bounded_search [on] 2 = off ·
  *              icp_fused_move [on] 2 = off, icp_fused_max [262 144] · icp_seed_in_move [on] 2 = off · icp_force_slots (tests) ·
  *              kabsch_bfly [on], kabsch_records [on], kabsch_one_pair_blocks [128], kabsch_max_blocks [1 024]
- *  other       plane_group [20: hypotheses per workgroup row of the plane count] · iss_lanes [32] · radius_fused [on] 2 = off · grid_stats 1 = the next 1-NN launch fills pcr_nn1_stats · prof 0 / 1 / 2 */
+ *  other       plane_group [20: hypotheses per workgroup row of the plane count] · iss_lanes [32] · fpfh_lanes [16] · radius_fused [on] 2 = off · grid_stats 1 = the next 1-NN launch fills pcr_nn1_stats · prof 0 / 1 / 2 */
 int pcr_tune_set(pcr_ctx* ctx, const char* key, int64_t value);
 
 #ifdef __cplusplus

@@ -157,6 +157,7 @@ public:
 
 #include <functional>
 #include <iostream>
+#include <limits>
 
 // ---- (2) the reference's own types and signatures (Homework9/hw9/include/registration.hpp) --------------------------------
 // Everything below compiles only where PCL + Eigen exist (the reference's build environment).  In this repository it is
@@ -236,8 +237,8 @@ public:
     }
 
     // The PCL-internal stages of compute() / ICPpoint2point().  Unset keypoints or fpfh33: compute() has no global
-    // registration to run and starts ICP from the identity.  Unset normal_space_sampling: ICP runs on the full clouds (the
-    // reference's own commented alternative, registration.cpp:883-884).
+    // registration to run and starts ICP from the identity (gpuFPFH33Stage() below is a GPU body for fpfh33).  Unset
+    // normal_space_sampling: ICP runs on the full clouds (the reference's own commented alternative, registration.cpp:883-884).
     struct Stages {
         // getHarris3DKeypoints (registration.hpp:152-154, registration.cpp:214-251)
         std::function<void(const PointCloud& input_cloud, const NormalCloud& input_normals, PointCloud& keypoints_cloud)> keypoints;
@@ -248,6 +249,17 @@ public:
         std::function<void(const PointCloud& input_cloud, const NormalCloud& input_normals, PointCloud& sampled_cloud, NormalCloud& sampled_normals)>
             normal_space_sampling;
     } stages;
+
+    // getFPFH33Descriptors on the GPU (pcr_fpfh33_f32, include/pcr.h: the library's restatement of PCL's FPFHEstimation) with the
+    // radius of setFPFHparams, read when the stage runs.  Opt-in: `reg.stages.fpfh33 = reg.gpuFPFH33Stage();`;
+    // an unset stage keeps its meaning.  The stage refers to this Registration, so it must not outlive it.
+    decltype(Stages::fpfh33) gpuFPFH33Stage()
+    {
+        return [this](const PointCloud& input_cloud, const PointCloud& input_keypoints_cloud, const NormalCloud& input_normals,
+                      pcl::PointCloud<pcl::FPFHSignature33>& fpfh_descriptors) {
+            gpuFPFH33(input_cloud, input_keypoints_cloud, input_normals, fpfh_descriptors);
+        };
+    }
 
     uint64_t ransac_seed = 5489u;          // the reference seeds std::mt19937 from std::random_device (registration.cpp:298-299)
     pcr_icp_stats last_icp_stats{};        // iterations run, kept pairs, ... of the last ICP
@@ -403,6 +415,41 @@ private:
             for (int c = 0; c < 3; ++c) R(r, c) = out_T[4 * r + c];
             t(r) = out_T[4 * r + 3];
         }
+    }
+
+    // the body of gpuFPFH33Stage: one row per keypoint, NaN rows (and is_dense = false) where PCL's computeFeature writes them
+    void gpuFPFH33(const PointCloud& input_cloud, const PointCloud& input_keypoints_cloud, const NormalCloud& input_normals,
+                   pcl::PointCloud<pcl::FPFHSignature33>& fpfh_descriptors) const
+    {
+        const size_t m = input_keypoints_cloud.size(), n = input_cloud.size();
+        std::vector<float> rows(33 * m + 33, std::numeric_limits<float>::quiet_NaN());
+        int rc = PCR_OK;
+        if (m > 0 && n > 0) {
+            std::vector<float> n3(3 * input_normals.size() + 3);
+            for (size_t i = 0; i < input_normals.size(); i++) {
+                n3[3 * i] = input_normals.points[i].normal_x; n3[3 * i + 1] = input_normals.points[i].normal_y; n3[3 * i + 2] = input_normals.points[i].normal_z;
+            }
+            pcr_ctx* ctx = default_ctx();
+            pcr_cloud *cs = nullptr, *ck = nullptr, *cn = nullptr;
+            rc = pcr_cloud_create(ctx, reinterpret_cast<const float*>(input_cloud.points.data()), n, PCR_AOS4, &cs);
+            if (rc == PCR_OK) rc = pcr_cloud_create(ctx, reinterpret_cast<const float*>(input_keypoints_cloud.points.data()), m, PCR_AOS4, &ck);
+            if (rc == PCR_OK) rc = pcr_cloud_create(ctx, n3.data(), input_normals.size(), PCR_AOS3, &cn);
+            if (rc == PCR_OK) rc = pcr_fpfh33_f32(ctx, cs, cn, ck, m_fpfh_feature_radius, rows.data(), nullptr, nullptr);
+            pcr_cloud_destroy(ctx, cs);
+            pcr_cloud_destroy(ctx, ck);
+            pcr_cloud_destroy(ctx, cn);
+        }
+        check(rc, "pcr_fpfh33_f32");
+        fpfh_descriptors.points.resize(m);
+        fpfh_descriptors.width = (uint32_t)m;
+        fpfh_descriptors.height = 1;
+        fpfh_descriptors.is_dense = true;
+        for (size_t i = 0; i < m; i++)
+            for (int k = 0; k < 33; k++) {
+                const float v = rows[33 * i + k];
+                fpfh_descriptors.points[i].histogram[k] = v;
+                if (v != v) fpfh_descriptors.is_dense = false;
+            }
     }
 
     static void to_rows(const Eigen::Matrix3f& R, const Eigen::Vector3f& t, float Rr[9], float tr[3])

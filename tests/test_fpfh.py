@@ -1,0 +1,508 @@
+"""FPFH33 descriptors (pcr_fpfh33_f32, Context.fpfh33, Registration::gpuFPFH33Stage): Homework9's getFPFH33Descriptors
+(registration.cpp:254-269, PCL FPFHEstimationOMP with radius voxel_size * 4).
+
+The numpy restatement below follows the contract written above pcr_fpfh33_f32 in include/pcr.h operation by operation: f32 with
+unfused ops, atan2 in f64, PCL's double bin arithmetic, SPFH values as repeated f32 adds, FPFH accumulated in f64 in ascending-s
+order.  PCL itself is not on this machine, so nothing here pins PCL: the restatement IS the contract.
+
+CPU: the restatement's pair features on hand-built pairs with closed-form answers, the properties of its rows, the header and the
+Python entry point.  GPU: SPFH bit-equal, FPFH within 1 ulp (>= 99.9 % of rows bit-identical) on a synthetic scene and on a real
+scan, edge cases, determinism across calls and lane counts, the drop-in stage, and hw9's whole chain ISS -> FPFH -> matching ->
+RANSAC -> ICP on two real scans that start 30 degrees apart."""
+import os
+import struct
+import subprocess
+import time
+
+import numpy as np
+import pytest
+from scipy.spatial import cKDTree
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+F32 = np.float32
+D_PI = F32(1.0) / (F32(2.0) * F32(np.pi))                   # 1.0f / (2.0f * (float)M_PI)
+
+
+# ---------------------------------------------------------------------------------------------------- numpy restatement
+def _dot(ax, ay, az, bx, by, bz):
+    return (ax * bx + ay * by) + az * bz
+
+
+def _bin(v):
+    f = np.floor(v)
+    return np.where(f >= 10.0, 10, np.where(f >= 0.0, f, 0)).astype(np.int64)      # NaN -> 0
+
+
+def pair_features(p1, n1, p2, n2):
+    """computePairFeatures(p1 = centre, n1, p2 = neighbour, n2) on arrays of pairs ([k, 3] f32) ->
+    (valid, f1, f2, f3, atan2 in f64, bins [k, 3])."""
+    p1, n1, p2, n2 = (np.asarray(a, F32).reshape(-1, 3) for a in (p1, n1, p2, n2))
+    with np.errstate(all="ignore"):
+        dpx, dpy, dpz = p2[:, 0] - p1[:, 0], p2[:, 1] - p1[:, 1], p2[:, 2] - p1[:, 2]
+        fin = np.isfinite(n1).all(1) & np.isfinite(n2).all(1)
+        f4 = np.sqrt(_dot(dpx, dpy, dpz, dpx, dpy, dpz))
+        a1 = _dot(n1[:, 0], n1[:, 1], n1[:, 2], dpx, dpy, dpz) / f4
+        a2 = _dot(n2[:, 0], n2[:, 1], n2[:, 2], dpx, dpy, dpz) / f4
+        sw = (np.abs(a1) <= 1) & (np.abs(a2) <= 1) & (np.abs(a1) < np.abs(a2))
+        u = np.where(sw[:, None], n2, n1)
+        nn = np.where(sw[:, None], n1, n2)
+        sg = np.where(sw, F32(-1), F32(1))
+        dpx, dpy, dpz = dpx * sg, dpy * sg, dpz * sg
+        f3 = np.where(sw, -a2, a1)
+        vx, vy, vz = dpy * u[:, 2] - dpz * u[:, 1], dpz * u[:, 0] - dpx * u[:, 2], dpx * u[:, 1] - dpy * u[:, 0]
+        vn = np.sqrt(_dot(vx, vy, vz, vx, vy, vz))
+        vx, vy, vz = vx / vn, vy / vn, vz / vn
+        wx, wy, wz = u[:, 1] * vz - u[:, 2] * vy, u[:, 2] * vx - u[:, 0] * vz, u[:, 0] * vy - u[:, 1] * vx
+        f2 = _dot(vx, vy, vz, nn[:, 0], nn[:, 1], nn[:, 2])
+        t64 = np.arctan2(_dot(wx, wy, wz, nn[:, 0], nn[:, 1], nn[:, 2]).astype(np.float64), _dot(u[:, 0], u[:, 1], u[:, 2], nn[:, 0], nn[:, 1], nn[:, 2]).astype(np.float64))
+        f1 = t64.astype(F32)
+        valid = fin & (f4 != 0) & (vn != 0)
+        bins = np.stack([_bin(11 * ((f1.astype(np.float64) + np.pi) * np.float64(D_PI))),
+                         _bin(11 * ((f2.astype(np.float64) + 1.0) * 0.5)), _bin(11 * ((f3.astype(np.float64) + 1.0) * 0.5))], 1)
+    return valid, f1, f2, f3, t64, bins
+
+
+def fragile_atan2(t64):
+    """pairs whose f64 atan2 lies within 4 f64 ulp of an f32 rounding midpoint: there a device libm and the host's may round apart"""
+    f = t64.astype(F32)
+    with np.errstate(all="ignore"):
+        lo = (f.astype(np.float64) + np.nextafter(f, F32(-np.inf)).astype(np.float64)) * 0.5
+        hi = (f.astype(np.float64) + np.nextafter(f, F32(np.inf)).astype(np.float64)) * 0.5
+        tol = 4 * np.spacing(np.abs(t64))
+        return np.isfinite(t64) & ((np.abs(t64 - lo) <= tol) | (np.abs(t64 - hi) <= tol))
+
+
+def neighbours(surface, queries, radius):
+    """flat (query row, surface index, s) of every member of N(q): s < r2 in f32, candidates from a kd-tree with a wider f64 radius"""
+    surface = np.asarray(surface, F32).reshape(-1, 3)
+    queries = np.asarray(queries, F32).reshape(-1, 3)
+    r2 = F32(np.float64(radius) * np.float64(radius))
+    sfin = np.isfinite(surface).all(1)
+    sidx = np.flatnonzero(sfin)
+    qfin = np.flatnonzero(np.isfinite(queries).all(1))
+    if sidx.size == 0 or qfin.size == 0:
+        return np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, F32)
+    tree = cKDTree(surface[sidx].astype(np.float64))
+    lists = tree.query_ball_point(queries[qfin].astype(np.float64), r=float(radius) * (1 + 1e-5) + 1e-12)
+    lens = np.array([len(l) for l in lists], np.int64)
+    qi = np.repeat(qfin, lens)
+    j = sidx[np.concatenate([np.asarray(l, np.int64) for l in lists])] if lens.sum() else np.zeros(0, np.int64)
+    d = surface[j] - queries[qi]
+    s = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
+    keep = s < r2
+    return qi[keep], j[keep], s[keep]
+
+
+def spfh_numpy(surface, normals, radius):
+    """-> (spfh [n, 33] f32, |N(p)| [n], fragile row mask [n])"""
+    surface = np.asarray(surface, F32).reshape(-1, 3)
+    normals = np.asarray(normals, F32).reshape(-1, 3)
+    n = surface.shape[0]
+    qi, j, _ = neighbours(surface, surface, radius)
+    cnt = np.bincount(qi, minlength=n)
+    other = qi != j
+    p, j = qi[other], j[other]
+    valid, _, _, _, t64, bins = pair_features(surface[p], normals[p], surface[j], normals[j])
+    hist = np.zeros((n, 33), np.int64)
+    for h in range(3):
+        np.add.at(hist, (p[valid], h * 11 + bins[valid, h]), 1)
+    fragile = np.zeros(n, bool)
+    fragile[p[valid & fragile_atan2(t64)]] = True
+    out = np.zeros((n, 33), F32)
+    with np.errstate(all="ignore"):
+        for c in np.unique(cnt):
+            rows = np.flatnonzero(cnt == c)
+            incr = F32(100.0) / F32(int(c) - 1)
+            k = int(hist[rows].max()) if rows.size else 0
+            table = np.concatenate([[F32(0)], np.add.accumulate(np.full(k, incr, F32))]).astype(F32)   # repeated f32 +=
+            out[rows] = table[hist[rows]]
+    return out, cnt, fragile
+
+
+def fpfh_numpy(surface, spfh, radius, keypoints=None):
+    """-> (fpfh [m, 33] f32, |N(q)| [m]); f64 accumulation in ascending-s order (ties by surface index)"""
+    surface = np.asarray(surface, F32).reshape(-1, 3)
+    kp = surface if keypoints is None else np.asarray(keypoints, F32).reshape(-1, 3)
+    m = kp.shape[0]
+    qi, j, s = neighbours(surface, kp, radius)
+    cnt = np.bincount(qi, minlength=m)
+    order = np.lexsort((j, s, qi))
+    qi, j, s = qi[order], j[order], s[order]
+    nz = s != 0
+    qi, j, s = qi[nz], j[nz], s[nz]
+    with np.errstate(all="ignore"):
+        w = F32(1.0) / s
+        val = spfh[j] * w[:, None]                          # f32
+    starts = np.searchsorted(qi, np.arange(m))
+    ends = np.searchsorted(qi, np.arange(m), side="right")
+    acc = np.zeros((m, 33), np.float64)
+    sums = np.zeros((m, 3), np.float64)
+    rank = np.arange(qi.size) - starts[qi]
+    for k in range(int(rank.max()) + 1 if rank.size else 0):
+        sel = rank == k
+        rows, v = qi[sel], val[sel].astype(np.float64)
+        acc[rows] += v
+        for h in range(3):
+            for b in range(11):
+                sums[rows, h] += v[:, h * 11 + b]
+    del ends
+    out = np.empty((m, 33), F32)
+    with np.errstate(all="ignore"):
+        for h in range(3):
+            sl = slice(h * 11, h * 11 + 11)
+            sc = 100.0 / sums[:, h:h + 1]
+            out[:, sl] = np.where(sums[:, h:h + 1] != 0, acc[:, sl] * sc, acc[:, sl]).astype(F32)
+    bad = ~np.isfinite(kp).all(1) | (cnt == 0)
+    out[bad] = np.nan
+    return out, cnt
+
+
+def ulp_diff(a, b):
+    """|a - b| in f32 ulps per slot (values >= 0); NaN against NaN = 0, NaN against a number = huge"""
+    ai, bi = a.view(np.int32).astype(np.int64), b.view(np.int32).astype(np.int64)
+    d = np.abs(ai - bi)
+    na, nb = np.isnan(a), np.isnan(b)
+    d[na & nb] = 0
+    d[na ^ nb] = 1 << 40
+    return d
+
+
+# ---------------------------------------------------------------------------------------------------- scenes
+def synthetic_scene(seed=5):
+    """plane z = 0, sphere of radius 2 at (0, 0, 3), box [3, 5] x [-1, 1] x [0, 2]: analytic normals"""
+    rng = np.random.default_rng(seed)
+    pl = np.c_[rng.uniform(-6, 6, (3000, 2)), np.zeros(3000)]
+    npl = np.tile([0.0, 0.0, 1.0], (3000, 1))
+    d = rng.normal(size=(1500, 3)); d /= np.linalg.norm(d, axis=1, keepdims=True)
+    sp = d * 2.0 + [0.0, 0.0, 3.0]
+    bx, nbx = [], []
+    for ax in range(3):
+        for side, val in ((-1, (3.0, -1.0, 0.0)[ax]), (1, (5.0, 1.0, 2.0)[ax])):
+            p = rng.uniform([3, -1, 0], [5, 1, 2], (250, 3))
+            p[:, ax] = val
+            nv = np.zeros(3); nv[ax] = side
+            bx.append(p); nbx.append(np.tile(nv, (250, 1)))
+    pts = np.concatenate([pl, sp, *bx]).astype(F32)
+    nrm = np.concatenate([npl, d, *nbx]).astype(F32)
+    return pts, nrm
+
+
+def real_scan(ctx, pts=None):
+    """the KITTI scan of the golden fixture voxelled at 0.3 (hw9's voxel_size), with pcr_normals_knn_f64 normals as f32"""
+    if pts is None:
+        pts = np.load(os.path.join(ROOT, "tests", "golden", "kat_kitti_q5.npz"))["db_f32"]
+    c = ctx.voxel_filter(ctx.cloud(np.ascontiguousarray(pts, F32), 1), 0.3)
+    xyz = np.ascontiguousarray(c.numpy().T)
+    nrm = ctx.normals(c, 10, 1.2).astype(F32)
+    return c, xyz, nrm
+
+
+# ---------------------------------------------------------------------------------------------------- CPU
+def test_restatement_pair_features_closed_form():
+    # n1 = z, dp = x, n2 tilted by 30 degrees about y: a1 = 0, a2 = -sin 30 -> |a1| < |a2|: the swap branch
+    p1, p2 = [0, 0, 0], [1, 0, 0]
+    n1 = [0, 0, 1]
+    c, s = np.cos(np.pi / 6), np.sin(np.pi / 6)
+    n2 = [-s, 0, c]
+    valid, f1, f2, f3, _, bins = pair_features(p1, n1, p2, n2)
+    assert valid[0]
+    # swapped: u = n2, dp = -x, f3 = -a2 = s; v = (-x) x n2 = (0, c, 0)/|.| = y; w = n2 x y; f2 = y . n1 = 0; f1 = atan2(w . n1, n2 . n1)
+    assert f3[0] == F32(s) or abs(f3[0] - s) < 1e-7
+    assert abs(f2[0]) < 1e-7
+    w = np.cross(np.array(n2), [0, 1, 0])
+    assert abs(f1[0] - np.arctan2(w @ n1, np.dot(n2, n1))) < 1e-6
+    # no swap: n1 = n2 = z, dp = x -> a1 = a2 = 0, f3 = 0, v = x cross z = -y, w = z x -y = x, f2 = 0, f1 = atan2(0, 1) = 0
+    valid, f1, f2, f3, _, bins = pair_features(p1, n1, p2, n1)
+    assert valid[0] and f1[0] == 0 and f2[0] == 0 and f3[0] == 0
+    assert list(bins[0]) == [5, 5, 5]
+    # n2 = -z: f1 = atan2(0, -1) = pi -> bin 11 clamped to 10
+    valid, f1, _, _, _, bins = pair_features(p1, n1, p2, [0, 0, -1])
+    assert valid[0] and f1[0] == F32(np.pi) and bins[0, 0] == 10
+    # n2 = y: f2 = v . y = -1 -> bin 0; f1 = atan2(x . y, z . y) = 0
+    valid, f1, f2, _, _, bins = pair_features(p1, n1, p2, [0, 1, 0])
+    assert valid[0] and f2[0] == -1 and bins[0, 1] == 0 and f1[0] == 0
+    # coincident points and a normal parallel to dp are skipped; so is a non-finite normal
+    assert not pair_features(p1, n1, p1, n1)[0][0]
+    assert not pair_features(p1, [1, 0, 0], p2, [1, 0, 0])[0][0]
+    assert not pair_features(p1, n1, p2, [np.nan, 0, 1])[0][0]
+    # |a| above 1 (unnormalised normals) never swaps: f3 = a1
+    valid, _, _, f3, _, _ = pair_features(p1, [0.5, 0, 2], p2, [3, 0, 1])
+    assert valid[0] and f3[0] == F32(0.5)
+
+
+def test_restatement_rows_sum_to_100_and_edge_rows():
+    pts, nrm = synthetic_scene()
+    sp, cnt, _ = spfh_numpy(pts, nrm, 0.5)
+    assert cnt.min() >= 1
+    kp = np.concatenate([pts[::97], [[100.0, 100.0, 100.0]], [[np.nan, 0, 0]]]).astype(F32)
+    out, kc = fpfh_numpy(pts, sp, 0.5, kp)
+    for row in out[:-2]:
+        for h in range(3):
+            s = float(row[h * 11:(h + 1) * 11].astype(np.float64).sum())
+            assert s == 0 or abs(s - 100.0) < 1e-3, s
+    assert np.isnan(out[-2]).all() and np.isnan(out[-1]).all() and kc[-2] == 0 and kc[-1] == 0
+    # every neighbour of the keypoint coincides with it: no weighted term, a zero row
+    dup = np.array([[0, 0, 0], [0, 0, 0], [0, 0, 0], [10, 0, 0]], F32)
+    dn = np.tile(np.array([0, 0, 1], F32), (4, 1))
+    sp2, c2, _ = spfh_numpy(dup, dn, 1.0)
+    assert list(c2) == [3, 3, 3, 1] and not sp2.any()
+    out2, _ = fpfh_numpy(dup, sp2, 1.0, dup[:1])
+    assert (out2 == 0).all()
+    # SPFH: incr = 100 / (|N| - 1) per pair, each sub-histogram of a point whose pairs are all valid sums to ~100
+    full = (cnt > 1)
+    tot = sp[full, :11].astype(np.float64).sum(1)
+    assert np.all(tot <= 100.0 + 1e-3)
+
+
+def test_header_declares_fpfh_and_stays_strict_c11(pcr, tmp_path):
+    text = open(os.path.join(ROOT, "include", "pcr.h")).read()
+    assert "int pcr_fpfh33_f32(pcr_ctx* ctx, const pcr_cloud* surface, const pcr_cloud* normals, const pcr_cloud* keypoints, float radius" in text
+    src = tmp_path / "fpfh_c.c"
+    src.write_text('#include "pcr.h"\n#include <stdio.h>\n'
+                   'int main(void) { int (*f)(pcr_ctx*, const pcr_cloud*, const pcr_cloud*, const pcr_cloud*, float, float*, uint32_t*, float*) = pcr_fpfh33_f32;\n'
+                   '  printf("%d\\n", pcr_fpfh33_f32(NULL, NULL, NULL, NULL, 1.0f, NULL, NULL, NULL) == PCR_ERR_ARG && f != NULL); return 0; }\n')
+    libdir = os.path.dirname(pcr.LIB_PATH)
+    exe = tmp_path / "fpfh_c"
+    r = subprocess.run(["gcc", "-std=c11", "-Wall", "-Wextra", "-pedantic", "-Werror", "-I" + os.path.join(ROOT, "include"), str(src), "-o", str(exe),
+                        "-L" + libdir, "-lpcr_hip", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and r.stdout.strip() == "1", r.stdout + r.stderr
+    assert callable(getattr(pcr.Context, "fpfh33", None))
+    assert "pcr_fpfh33_f32" in pcr.ABI_SYMBOLS
+
+
+STAGE_SRC = os.path.join(ROOT, "tests", "cpp", "fpfh_stage_check.cpp")
+LIBDIR = os.path.join(ROOT, "hands-on-point-cloud-processing_amd")
+
+
+def build_stage(tmp_path):
+    exe = tmp_path / "fpfh_stage_check"
+    r = subprocess.run(["g++", "-std=c++14", "-O1", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include", "pcr"), "-I" + os.path.join(ROOT, "tests", "mock"),
+                        STAGE_SRC, "-o", str(exe), "-L" + LIBDIR, "-lpcr_hip", "-Wl,-rpath," + LIBDIR, "-Wl,-rpath,/opt/rocm/lib"], capture_output=True, text=True)
+    return r, exe
+
+
+def test_dropin_fpfh_stage_compiles(tmp_path):
+    r, _ = build_stage(tmp_path)
+    assert r.returncode == 0, r.stderr[-4000:]
+
+
+# ---------------------------------------------------------------------------------------------------- GPU
+def check_spfh(gpu, want, fragile, what):
+    diff = np.flatnonzero((gpu.view(np.uint32) != want.view(np.uint32)).any(1))
+    excused = diff[fragile[diff]]
+    for r in excused:
+        print(f"{what}: SPFH row {r} differs; it holds a pair whose f64 atan2 lies within 4 ulp of an f32 midpoint: "
+              f"gpu {gpu[r].tolist()} restatement {want[r].tolist()}")
+    assert np.array_equal(np.sort(excused), diff), f"{what}: SPFH rows differ without a fragile pair: {diff[~fragile[diff]][:10]}"
+    return excused
+
+
+def check_fpfh(gpu, want, what):
+    d = ulp_diff(gpu, want)
+    assert int(d.max(initial=0)) <= 1, (what, int(d.max()), np.argwhere(d > 1)[:5])
+    same = float((d == 0).all(1).mean()) if d.size else 1.0
+    assert same >= 0.999, (what, same)
+    assert np.array_equal(np.isnan(gpu), np.isnan(want))
+    return same
+
+
+def run_all_cases(ctx, surf_cloud, xyz, nrm, radius, kp_sets, what):
+    fp, cnt, sp = ctx.fpfh33(surf_cloud, nrm, radius, spfh=True)
+    sp_ref, cnt_ref, fragile = spfh_numpy(xyz, nrm, radius)
+    excused = check_spfh(sp, sp_ref, fragile, what)
+    sp_use = sp_ref.copy()
+    sp_use[excused] = sp[excused]
+    ref, rc = fpfh_numpy(xyz, sp_use, radius)
+    assert np.array_equal(cnt, rc) and np.array_equal(cnt, cnt_ref)
+    check_fpfh(fp, ref, what + " keypoints=NULL")
+    for name, kp in kp_sets:
+        f2, c2 = ctx.fpfh33(surf_cloud, nrm, radius, keypoints=kp)
+        r2_, rc2 = fpfh_numpy(xyz, sp_use, radius, kp)
+        assert np.array_equal(c2, rc2), name
+        check_fpfh(f2, r2_, f"{what} keypoints={name}")
+    return fp, cnt, sp
+
+
+def off_surface(xyz, rng, k=300):
+    fin = xyz[np.isfinite(xyz).all(1)]
+    lo, hi = fin.min(0), fin.max(0)
+    near = fin[rng.integers(0, fin.shape[0], k)] + rng.normal(0, 0.4, (k, 3))
+    far = rng.uniform(lo - 30, hi + 30, (k, 3))
+    return np.concatenate([near, far, [[np.nan, 0, 0], [np.inf, 1, 1]]]).astype(F32)
+
+
+@pytest.mark.gpu
+def test_gpu_fpfh_synthetic_scene(pcr):
+    pts, nrm = synthetic_scene()
+    rng = np.random.default_rng(3)
+    with pcr.Context(0) as ctx:
+        c = ctx.cloud(pts, pcr.PCR_AOS3)
+        idx, _, _ = ctx.iss_keypoints(c, 0.5, 0.5, 0.9, 0.9, 5, False)
+        kp_sets = [("iss", pts[idx] if idx.size else pts[:5]), ("off-surface", off_surface(pts, rng))]
+        fp, cnt, _ = run_all_cases(ctx, c, pts, nrm, 0.5, kp_sets, "synthetic")
+        assert cnt.min() >= 1 and not np.isnan(fp).any()
+
+
+@pytest.mark.gpu
+def test_gpu_fpfh_real_scan(pcr):
+    rng = np.random.default_rng(4)
+    with pcr.Context(0) as ctx:
+        c, xyz, nrm = real_scan(ctx)
+        idx, _, _ = ctx.iss_keypoints(c, 0.9, 0.9, 0.52, 0.52, 6, False)
+        print(f"real scan: {xyz.shape[0]} points after the voxel filter, {idx.size} ISS keypoints")
+        assert idx.size >= 50
+        kp_sets = [("iss", xyz[idx]), ("off-surface", off_surface(xyz, rng))]
+        _, cnt, _ = run_all_cases(ctx, c, xyz, nrm, 1.2, kp_sets, "kitti")
+        print(f"|N| min {cnt.min()} mean {cnt.mean():.1f} max {cnt.max()}")
+
+
+@pytest.mark.gpu
+def test_gpu_fpfh_edge_cases(pcr):
+    rng = np.random.default_rng(9)
+    pts, nrm = synthetic_scene(11)
+    pts, nrm = pts[::7].copy(), nrm[::7].copy()
+    pts[5] = pts[6]                                          # duplicates
+    pts[10] = pts[11]; nrm[10] = nrm[11]
+    pts[20] = [np.nan, 1, 1]; pts[21] = [np.inf, 0, 0]       # non-finite points
+    nrm[30] = [np.nan, 0, 1]; nrm[31] = [0, np.inf, 0]       # non-finite normals
+    nrm[40] = [0, 0, 0]                                      # zero normal: v = 0, its pairs are skipped
+    with pcr.Context(0) as ctx:
+        c = ctx.cloud(pts, pcr.PCR_AOS3)
+        for radius in (0.8, 0.05):                           # 0.05: below the spacing, most neighbourhoods are the point alone
+            run_all_cases(ctx, c, pts, nrm, radius, [("off-surface", off_surface(pts, rng, 50))], f"edges r={radius}")
+        for k in (1, 2):
+            sub = pts[:k] if k == 1 else np.array([[0, 0, 0], [0.3, 0, 0]], F32)
+            sn = nrm[:k] if k == 1 else np.array([[0, 0, 1], [0, 1, 0]], F32)
+            cs = ctx.cloud(sub, pcr.PCR_AOS3)
+            fp, cnt, sp = ctx.fpfh33(cs, sn, 1.0, spfh=True)
+            sr, _, _ = spfh_numpy(sub, sn, 1.0)
+            fr, cr = fpfh_numpy(sub, sr, 1.0)
+            assert np.array_equal(sp.view(np.uint32), sr.view(np.uint32)) and np.array_equal(cnt, cr)
+            assert ulp_diff(fp, fr).max() <= 1
+        # argument errors
+        for bad in (0.0, -1.0, float("nan"), float("inf")):
+            with pytest.raises(pcr.PcrError):
+                ctx.fpfh33(c, nrm, bad)
+        with pytest.raises(pcr.PcrError):
+            ctx.fpfh33(c, nrm[:-1], 0.5)
+        # empty surface / no keypoints: nothing written, no error
+        e = ctx.cloud(np.zeros((0, 3), F32), pcr.PCR_AOS3)
+        f, cn = ctx.fpfh33(e, np.zeros((0, 3), F32), 0.5)
+        assert f.shape == (0, 33) and cn.shape == (0,)
+        f, cn = ctx.fpfh33(c, nrm, 0.5, keypoints=np.zeros((0, 3), F32))
+        assert f.shape == (0, 33)
+
+
+@pytest.mark.gpu
+def test_gpu_fpfh_deterministic_and_lane_counts(pcr):
+    with pcr.Context(0) as ctx:
+        c, xyz, nrm = real_scan(ctx)
+        kp = xyz[::13].copy()
+        f0, c0, s0 = ctx.fpfh33(c, nrm, 1.2, spfh=True)
+        k0, _ = ctx.fpfh33(c, nrm, 1.2, keypoints=kp)
+        # other work on the same context, then the same calls again
+        ctx.iss_keypoints(c, 0.9, 0.9, 0.52, 0.52, 6, False)
+        ctx.icp_point2point(c, c, max_corr=1.0, max_iter=3)
+        ctx.dbscan(c, 0.8, 10)
+        f1, c1, s1 = ctx.fpfh33(c, nrm, 1.2, spfh=True)
+        k1, _ = ctx.fpfh33(c, nrm, 1.2, keypoints=kp)
+        assert np.array_equal(f0.view(np.uint32), f1.view(np.uint32)) and np.array_equal(s0.view(np.uint32), s1.view(np.uint32))
+        assert np.array_equal(k0.view(np.uint32), k1.view(np.uint32)) and np.array_equal(c0, c1)
+        for G in (1, 2, 4, 8, 16, 32):
+            ctx.tune("fpfh_lanes", G)
+            f, cn, s = ctx.fpfh33(c, nrm, 1.2, spfh=True)
+            assert np.array_equal(s.view(np.uint32), s0.view(np.uint32)), G
+            assert np.array_equal(cn, c0) and ulp_diff(f, f0).max() <= 1, G
+            k, _ = ctx.fpfh33(c, nrm, 1.2, keypoints=kp)
+            assert ulp_diff(k, k0).max() <= 1, G
+        ctx.tune("fpfh_lanes", 0)
+
+
+def pca_normals_toward(xyz, origin, k=10):
+    """PCA normals of the k nearest points, oriented toward the sensor origin (numpy / scipy)"""
+    tree = cKDTree(xyz.astype(np.float64))
+    _, nb = tree.query(xyz.astype(np.float64), k=k)
+    P = xyz.astype(np.float64)[nb]
+    P = P - P.mean(1, keepdims=True)
+    C = np.einsum("nki,nkj->nij", P, P)
+    _, V = np.linalg.eigh(C)
+    nrm = V[:, :, 0]
+    flip = np.einsum("ni,ni->n", nrm, origin - xyz) < 0
+    nrm[flip] *= -1
+    return nrm.astype(F32)
+
+
+def rot_err_deg(R, Rgt):
+    c = (np.trace(R.astype(np.float64).T @ Rgt) - 1) / 2
+    return float(np.degrees(np.arccos(np.clip(c, -1, 1))))
+
+
+@pytest.mark.gpu
+def test_gpu_hw9_global_registration_end_to_end(pcr):
+    """hw9's chain on two scans of the same place: ISS -> FPFH33 -> union matching -> RANSAC -> point-to-point ICP"""
+    raw = np.load(os.path.join(ROOT, "tests", "golden", "kat_kitti_q5.npz"))["db_f32"].astype(F32)
+    rng = np.random.default_rng(2024)
+    yaw = np.radians(30.0)
+    Rgt = np.array([[np.cos(yaw), -np.sin(yaw), 0], [np.sin(yaw), np.cos(yaw), 0], [0, 0, 1]])
+    tgt_t = np.array([2.0, -1.0, 0.1])
+    sub = raw[rng.permutation(raw.shape[0])[: int(0.8 * raw.shape[0])]]
+    src_raw = (sub.astype(np.float64) @ Rgt.T + tgt_t).astype(F32)      # the source: the scene seen from a moved sensor
+    # the pose that maps the source back onto the target: R = Rgt^T, t = -Rgt^T tgt_t
+    Rwant, twant = Rgt.T, -Rgt.T @ tgt_t
+    with pcr.Context(0) as ctx:
+        clouds = {}
+        for name, pts, origin in (("tgt", raw, np.zeros(3)), ("src", src_raw, tgt_t)):
+            c = ctx.voxel_filter(ctx.cloud(pts, pcr.PCR_AOS3), 0.3)
+            xyz = np.ascontiguousarray(c.numpy().T)
+            nrm = pca_normals_toward(xyz, origin)
+            idx, _, _ = ctx.iss_keypoints(c, 0.9, 0.9, 0.52, 0.52, 6, False)
+            fp, cnt = ctx.fpfh33(c, nrm, 1.2, keypoints=xyz[idx])
+            ok = ~np.isnan(fp).any(1)
+            clouds[name] = (c, xyz, idx[ok], fp[ok])
+            print(f"{name}: {xyz.shape[0]} points, {idx.size} keypoints, |N| mean {cnt.mean():.1f}")
+        cs, xs, ks, ds = clouds["src"]
+        ct, xt, kt, dt = clouds["tgt"]
+        pairs, _ = ctx.match_union(ds, dt, 0.5)
+        kps, kpt = xs[ks], xt[kt]
+        inl = np.linalg.norm((kps[pairs[:, 0]].astype(np.float64) @ Rwant.T + twant) - kpt[pairs[:, 1]], axis=1) < 1.2
+        print(f"{pairs.shape[0]} correspondences, inlier ratio {inl.mean():.3f}")
+        quads = pcr.ransac_sample_quads(kps, pairs, 80000, 12345)
+        win, R0, t0, best, _ = ctx.ransac_global(kps, kpt, pairs, quads, 1.2)
+        print(f"RANSAC: winner {win}, consensus {best}, rotation error {rot_err_deg(R0, Rwant):.3f} deg, t error {np.linalg.norm(t0 - twant):.3f} m")
+        T0 = np.eye(4, dtype=F32); T0[:3, :3], T0[:3, 3] = R0, t0
+        T, st = ctx.icp_point2point(cs, ct, init_T=T0, max_corr=1.0, max_iter=800, eps=1e-8)
+        er, et = rot_err_deg(T[:3, :3], Rwant), float(np.linalg.norm(T[:3, 3] - twant))
+        print(f"ICP from RANSAC: rotation error {er:.4f} deg, translation error {et:.4f} m, {st['iters_run']} iterations")
+        Ti, _ = ctx.icp_point2point(cs.clone(), ct, max_corr=1.0, max_iter=800, eps=1e-8)
+        eri, eti = rot_err_deg(Ti[:3, :3], Rwant), float(np.linalg.norm(Ti[:3, 3] - twant))
+        print(f"ICP from the identity: rotation error {eri:.4f} deg, translation error {eti:.4f} m")
+        assert er < 0.5 and et < 0.05
+        assert not (eri < 0.5 and eti < 0.05), "ICP from the identity alone reached the bar: the descriptors were not needed"
+
+
+def write_stage_scene(path, surface, normals, kp, radius):
+    with open(path, "wb") as f:
+        f.write(struct.pack("<IIf", surface.shape[0], kp.shape[0], radius))
+        for a in (surface, normals, kp):
+            f.write(np.ascontiguousarray(a, F32).tobytes())
+
+
+@pytest.mark.gpu
+def test_gpu_dropin_fpfh_stage_equals_c_abi(pcr, tmp_path):
+    r, exe = build_stage(tmp_path)
+    assert r.returncode == 0, r.stderr[-4000:]
+    with pcr.Context(0) as ctx:
+        c, xyz, nrm = real_scan(ctx)
+        idx, _, _ = ctx.iss_keypoints(c, 0.9, 0.9, 0.52, 0.52, 6, False)
+        kp = np.concatenate([xyz[idx], [[1e4, 1e4, 1e4]]]).astype(F32)
+        want, _ = ctx.fpfh33(c, nrm, 1.2, keypoints=kp)
+    write_stage_scene(tmp_path / "s.bin", xyz, nrm, kp, 1.2)
+    rr = subprocess.run([str(exe), str(tmp_path / "s.bin"), str(tmp_path / "o.bin")], capture_output=True, text=True, timeout=300)
+    assert rr.returncode == 0, rr.stdout + rr.stderr
+    raw = open(tmp_path / "o.bin", "rb").read()
+    m, dense = struct.unpack("<II", raw[:8])
+    got = np.frombuffer(raw[8:], F32).reshape(m, 33)
+    assert m == kp.shape[0] and dense == 0
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
