@@ -1653,15 +1653,15 @@ __global__ __launch_bounds__(GR_BLOCK) void bt_l1_centres_kernel(const float4* _
     centres[s] = make_float4(cx, cy, cz, ldexpf(1.0f, k));
 }
 
-// one thread per chunk of 16 records: its row of its level-1 tile (MFMA row m <-> chunk 16 ((m >> 2) & 1) + 4 (m >> 3) + (m & 3), so that
-// the 16 accumulators of lane-half h are the chunks 16 h + i of the tile, in order)
+// one thread per chunk of 16 records: its row of its level-1 tile (stored row m <-> chunk 2 (m & 15) + (m >> 4): the order STRACK3's
+// transposed level 1 reads — the two chunks of level-2 tile k are rows k and k + 16; see l1_chunk_operand)
 __global__ __launch_bounds__(GR_BLOCK) void bt_l1_ops_kernel(const float4* __restrict__ rec, uint32_t n_rec, uint32_t n_l1_tiles, const float4* __restrict__ centres,
                                                              uint4* __restrict__ ops)
 {
     const uint32_t gid = blockIdx.x * GR_BLOCK + threadIdx.x;
     const uint32_t T = gid >> 5, m = gid & 31;
     if (T >= n_l1_tiles) return;
-    const uint32_t chunk = T * 32 + 16 * ((m >> 2) & 1) + 4 * (m >> 3) + (m & 3);
+    const uint32_t chunk = T * 32 + 2 * (m & 15) + (m >> 4);
     const float4 C = centres[T / (BT_L1_SUPER / 512)];
     float tx[16], ty[16], tz[16];
     bool fin[16];
@@ -1737,8 +1737,8 @@ __global__ __launch_bounds__(GR_BLOCK) void bt_l0_centres_kernel(const float4* _
     centres[s] = make_float4(cx, cy, cz, ldexpf(1.0f, k));
 }
 
-// one wave per level-1 tile: its row of its level-0 tile (row m <-> level-1 tile 16 ((m >> 2) & 1) + 4 (m >> 3) + (m & 3) of the 32, as the chunks
-// of a level-1 tile: the 16 accumulators of lane-half h are the tiles 16 h + i, in order)
+// one wave per level-1 tile: its row of its level-0 tile (stored row m <-> level-1 tile m of the 32: STRACK3's transposed level 0 reads the
+// row mask straight from one ballot; see l1_chunk_operand)
 __global__ __launch_bounds__(GR_BLOCK) void bt_l0_ops_kernel(const float4* __restrict__ rec, uint32_t n_rec, uint32_t n_rows, const float4* __restrict__ centres,
                                                              uint4* __restrict__ ops)
 {
@@ -1784,7 +1784,7 @@ __global__ __launch_bounds__(GR_BLOCK) void bt_l0_ops_kernel(const float4* __res
     if (lane != 0) return;
     uint4 lo, hi;
     sph_finish(any, pp, c, r2, lo, hi);
-    const uint32_t T0 = T1 >> 5, j = T1 & 31u, m = (((j >> 2) & 3u) << 3) | ((j >> 4) << 2) | (j & 3u);
+    const uint32_t T0 = T1 >> 5, m = T1 & 31u;
     ops[(size_t)T0 * 64 + m] = lo;
     ops[(size_t)T0 * 64 + 32 + m] = hi;
 }

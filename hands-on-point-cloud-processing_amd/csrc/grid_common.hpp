@@ -373,7 +373,15 @@ __device__ __forceinline__ void sph_finish(bool any, uint32_t (&p)[3][2], float 
     hi = make_uint4(p[2][0] | (p[2][1] << 16), p[2][0] | (m2 << 16), w1 | (w2 << 16), HT_THETA_CONSTS);
 }
 
-// the two lanes' words of MFMA row `m` of a level-1 tile for one chunk: t[16][3] = the chunk's records in the scaled units of its level-1
+// WHERE A SPHERE ROW IS STORED (bt_l0_ops_kernel, bt_l1_ops_kernel; read by nn1_strack3_body only).  A tile is [64 lanes] x 16 bytes: lane n holds
+// K-slots 0..7 of stored row n, lane 32 + n its K-slots 8..15 — the layout of EITHER operand of v_mfma_f32_32x32x16_f16.  STRACK3 runs levels 0 and 1
+// with the tile as the B operand, so stored row n is COLUMN n of the result: lane (n, h) holds row n against 16 of the queries, and bit n (and
+// 32 + n) of one ballot is "some query flagged stored row n".  The stored order is chosen so that this mask needs no permutation:
+//   level 0: stored row n = level-1 tile n of the level-0 tile's 32 (mask bit j = tile T0 * 32 + j: the list comes out ascending);
+//   level 1: stored row n = chunk 2 (n & 15) + (n >> 4) of the level-1 tile: level-2 tile k (chunks 2 k, 2 k + 1) is rows k and k + 16, its
+//            bit is (mask | mask >> 16) & 0xFFFF.
+// (With the tile as A — nn1_strack3_rows_kernel — accumulator i of lane-half h is stored row 8 (i >> 2) + 4 h + (i & 3).)
+// the two lanes' words of a stored row of a level-1 tile for one chunk: t[16][3] = the chunk's records in the scaled units of its level-1
 // super-tile (exact scaling), fin[16] = finite and inside the super-tile's range
 __device__ __forceinline__ void l1_chunk_operand(const float (&tx)[16], const float (&ty)[16], const float (&tz)[16], const bool (&fin)[16], uint4& lo, uint4& hi)
 {

@@ -1365,7 +1365,13 @@ static int launch_matrix(pcr_ctx* ctx, const pcr_cloud* tgt, const pcr_cloud* sr
 #define PCR_STRACK3(Q)                                                                                                                     \
     hipLaunchKernelGGL((nn1_strack3_kernel<Q>), grid3, dim3(NN_BLOCK), 0, ctx->stream, g->l0_centres, g->l0_ops, g->l1_centres, g->l1_ops, g->l1_rec_ops, g->records,  \
                        n_super * BT_SUPER, n_l0, l0ps, src->x(), src->y(), src->z(), (uint32_t)ns, ctx->keys, ctx->stop_flag_dev, stats_dev, std::min<uint32_t>(st_flush_at, (uint32_t)S2_CAP), s3_flush_end)
-            if (qg3 == 1) PCR_STRACK3(1); else if (qg3 == 2) PCR_STRACK3(2); else PCR_STRACK3(4);
+            // how levels 0 / 1 read the sphere-row masks (tune nn1_s3_transposed: 1 = one ballot of the transposed product, default; 2 = one ballot per accumulator)
+#define PCR_STRACK3_ROWS(Q)                                                                                                                \
+    hipLaunchKernelGGL((nn1_strack3_rows_kernel<Q>), grid3, dim3(NN_BLOCK), 0, ctx->stream, g->l0_centres, g->l0_ops, g->l1_centres, g->l1_ops, g->l1_rec_ops, g->records,  \
+                       n_super * BT_SUPER, n_l0, l0ps, src->x(), src->y(), src->z(), (uint32_t)ns, ctx->keys, ctx->stop_flag_dev, stats_dev, std::min<uint32_t>(st_flush_at, (uint32_t)S2_CAP), s3_flush_end)
+            if (tune_get(ctx, "nn1_s3_transposed", 1) == 2) { if (qg3 == 1) PCR_STRACK3_ROWS(1); else if (qg3 == 2) PCR_STRACK3_ROWS(2); else PCR_STRACK3_ROWS(4); }
+            else if (qg3 == 1) PCR_STRACK3(1); else if (qg3 == 2) PCR_STRACK3(2); else PCR_STRACK3(4);
+#undef PCR_STRACK3_ROWS
 #undef PCR_STRACK3
         }
         else if (sign) { if (qg == 2) PCR_STRACK(2); else PCR_STRACK(4); }
@@ -1892,8 +1898,8 @@ __global__ __launch_bounds__(64) void sp_selftest_kernel(const float* __restrict
     const uint32_t lane = threadIdx.x, T = blockIdx.x, n = lane & 31;
     const bool h = lane >= 32;
     const float sc = scale[T];
-    // row n of the tile <-> chunk 16 ((n >> 2) & 1) + 4 (n >> 3) + (n & 3) (bt_l1_ops_kernel)
-    const uint32_t chunk = 16 * ((n >> 2) & 1) + 4 * (n >> 3) + (n & 3);
+    // the product in the role STRACK3 uses (nn1_strack3_body, TR): queries as A, sphere rows as B.  Lane n builds chunk n's row and query n's operand.
+    const uint32_t chunk = n;
     float tx[16], ty[16], tz[16];
     bool fin[16];
 #pragma unroll
@@ -1904,11 +1910,11 @@ __global__ __launch_bounds__(64) void sp_selftest_kernel(const float* __restrict
     }
     uint4 lo, hi;
     l1_chunk_operand(tx, ty, tz, fin, lo, hi);
-    const uint4 A = h ? hi : lo;
+    const uint4 B = h ? hi : lo;
     const float* q = qs + ((size_t)T * 32 + n) * 3;
     uint32_t P[4], Q[4];
     st_setup_l1(q[0], q[1], q[2], make_float4(0.0f, 0.0f, 0.0f, sc), thr[(size_t)T * 32 + n], sc * sc, P, Q);
-    const uint4 B = h ? make_uint4(Q[0], Q[1], Q[2], Q[3]) : make_uint4(P[0], P[1], P[2], P[3]);
+    const uint4 A = h ? make_uint4(Q[0], Q[1], Q[2], Q[3]) : make_uint4(P[0], P[1], P[2], P[3]);
     f32x16 zero;
 #pragma unroll
     for (int j = 0; j < 16; j++) zero[j] = 0.0f;
@@ -1990,7 +1996,7 @@ int st_sphere_selftest(pcr_ctx* ctx, int trials, unsigned long long res[4])
     for (size_t T = 0; T < n_tiles; T++)
         for (int lane = 0; lane < 64; lane++)
             for (int reg = 0; reg < 16; reg++) {
-                const int n = lane & 31, chunk = 16 * (lane >> 5) + reg;       // accumulator `reg` of lane-half h <-> chunk 16 h + reg of the tile
+                const int chunk = lane & 31, n = 8 * (reg >> 2) + 4 * (lane >> 5) + (reg & 3);       // lane (c, h): chunk c; its accumulator `reg` <-> query 8 (reg >> 2) + 4 h + (reg & 3)
                 uint32_t bits; std::memcpy(&bits, &out[(T * 64 + lane) * 16 + reg], 4);
                 const bool flagged = (bits >> 31) != 0;
                 const float* q = &in[q_off + (T * 32 + n) * 3];

@@ -21,6 +21,8 @@ constexpr int S2_TILES = 512;                 // level-2 tiles a wave may collec
 constexpr int S2_CAP = 128;                   // flagged (query, chunk) pairs a wave lists before it evaluates them
 
 // the listed chunks against their queries: four lanes per chunk, four records each, sixteen chunks per round
+// (Measured and dropped: the second round skipped wave-uniformly when e0 + 16 >= cnt — a wave lists ~37 chunks per search over several flushes, so
+// that round is mostly empty lanes: 0.0307-0.0321 ms per 120 k search with both rounds, 0.0308-0.0318 with the skip: no difference to measure.)
 template <int QG, class LDS>
 __device__ __forceinline__ void s2_flush(LDS& L, uint32_t cnt, const float4* __restrict__ records, uint32_t lane)
 {
@@ -91,8 +93,19 @@ struct S3WaveLds {
     uint32_t list[S2_CAP + 256 * QG];         // (chunk << 7) | query slot: what a batch of four level-2 tiles can add fits behind S2_CAP entries
 };
 
-template <int QG>
-__global__ __launch_bounds__(NN_BLOCK, PCR_S2_WAVES) void nn1_strack3_kernel(
+// TR: how levels 0 and 1 read "which sphere rows did any of the 32 queries flag" (tune nn1_s3_transposed: 1 = true and default, 2 = false).
+//   true:  the product runs TRANSPOSED — the queries' operand as A, the stored sphere tile as B (both operands of v_mfma_f32_32x32x16_f16 have the
+//          same register layout: lane l carries row / column l % 32, K-slots 8 (l / 32) .. + 7; the same pairs of f16 values meet, so the signs
+//          are the same).  Lane (n, h) then holds sphere row n of the tile against the 16 queries 8 (i >> 2) + 4 h + (i & 3): one s2_or16 and ONE
+//          ballot give a 64-bit mask whose halves are the two halves of the queries — the row mask is lo | hi.
+//   false: spheres as A, queries as B, one ballot per accumulator (16 per level-0 tile behind a repeated MFMA, 8 per level-1 tile): each is a
+//          chain of v_cmp / s_cmp / s_cselect / 64-bit v_cmp of the mask / s_and / s_cselect / s_or / s_or, 8 instructions alternating between
+//          the vector and the scalar unit — 4 095 static instructions in <1> (1 940 scalar, 1 582 vector, 28 MFMA) against 2 423 (832, 1 069, 20);
+//          0.033-0.035 against 0.027-0.029 ms per settled 120 k search (profiles/strack3_transposed.txt).  Kept as nn1_strack3_rows_kernel for
+//          A/B runs in one process.
+// Both read the same index: bt_l0_ops_kernel / bt_l1_ops_kernel store the rows in the order the B role wants (see l1_chunk_operand).
+template <int QG, bool TR>
+__device__ __forceinline__ void nn1_strack3_body(
     const float4* __restrict__ l0_centres, const uint4* __restrict__ l0_ops, const float4* __restrict__ l1_centres, const uint4* __restrict__ l1_ops,
     const uint4* __restrict__ ops, const float4* __restrict__ records, uint32_t n_rec, uint32_t n_l0, uint32_t l0_per_slice,
     const float* __restrict__ sx, const float* __restrict__ sy, const float* __restrict__ sz, uint32_t ns,
@@ -150,7 +163,7 @@ __global__ __launch_bounds__(NN_BLOCK, PCR_S2_WAVES) void nn1_strack3_kernel(
             thr[p] = ok[p] ? fminf(thr[p], __uint_as_float(fb)) : thr[p];
         }
     };
-    // B operands: bq0 = sphere rows in a level-0 super-tile's scale; bq1 / bq2 = sphere rows / record rows in a level-1 super-tile's scale
+    // the queries' operands (A where the product runs transposed, B otherwise): bq0 = sphere rows in a level-0 super-tile's scale; bq1 / bq2 = sphere rows / record rows in a level-1 super-tile's scale
     // (lane (n, h) builds the whole operand of query n of group 2 p + h, the halves change places by v_permlane32_swap: nn1_strack_kernel)
     uint4 bq0[QG], bq1[QG], bq2[QG];
     auto setup0 = [&](const float4 C) {
@@ -240,28 +253,36 @@ __global__ __launch_bounds__(NN_BLOCK, PCR_S2_WAVES) void nn1_strack3_kernel(
         for (int t = 0; t < 8; t++) {
             const uint32_t T0 = S0 * 8 + t;
             const uint4 A0 = A0s[t];
-            uint32_t anyg[QG];
+            uint32_t rmask[QG];                               // bit j: row j of this level-0 tile (level-1 tile T0 * 32 + j) flagged by the group
+            if (TR) {
 #pragma unroll
-            for (int g = 0; g < QG; g++)
-                anyg[g] = s2_or16(__builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, A0), __builtin_bit_cast(f16x8, bq0[g]), zero, 0, 0, 0));
-            if (stats) st_l0 += QG;
-            uint32_t anyall = anyg[0];
+                for (int g = 0; g < QG; g++) {
+                    const uint32_t og = s2_or16(__builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, bq0[g]), __builtin_bit_cast(f16x8, A0), zero, 0, 0, 0));
+                    const unsigned long long m = __builtin_amdgcn_ballot_w64((int)og < 0);       // lane (j, h): row j against the queries of half h
+                    rmask[g] = (uint32_t)m | (uint32_t)(m >> 32);
+                }
+                if (stats) st_l0 += QG;
+            }
+            else {
+                uint32_t anyg[QG];
 #pragma unroll
-            for (int g = 1; g < QG; g++) anyall |= anyg[g];
-            if (__builtin_amdgcn_ballot_w64((int)anyall < 0)) {
-                uint32_t rmask[QG];                           // bit j: row j of this level-0 tile (level-1 tile T0 * 32 + j) flagged by the group
+                for (int g = 0; g < QG; g++)
+                    anyg[g] = s2_or16(__builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, A0), __builtin_bit_cast(f16x8, bq0[g]), zero, 0, 0, 0));
+                if (stats) st_l0 += QG;
 #pragma unroll
                 for (int g = 0; g < QG; g++) {
                     rmask[g] = 0u;
                     if (!__builtin_amdgcn_ballot_w64((int)anyg[g] < 0)) continue;
                     const f32x16 acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, A0), __builtin_bit_cast(f16x8, bq0[g]), zero, 0, 0, 0);
 #pragma unroll
-                    for (int i = 0; i < 16; i++) {
+                    for (int i = 0; i < 16; i++) {            // (accumulator i of lane-half h <-> MFMA row 8 (i >> 2) + 4 h + (i & 3) = row j of the tile)
                         const unsigned long long m = __builtin_amdgcn_ballot_w64((int)__float_as_uint(acc[i]) < 0);
-                        rmask[g] |= ((uint32_t)m != 0u ? 1u : 0u) << i;                        // lanes < 32: rows 0..15
-                        rmask[g] |= ((uint32_t)(m >> 32) != 0u ? 1u : 0u) << (16 + i);         // lanes >= 32: rows 16..31
+                        rmask[g] |= ((uint32_t)m != 0u ? 1u : 0u) << (8 * (i >> 2) + (i & 3));
+                        rmask[g] |= ((uint32_t)(m >> 32) != 0u ? 1u : 0u) << (8 * (i >> 2) + 4 + (i & 3));
                     }
                 }
+            }
+            {
                 uint32_t un = rmask[0];
 #pragma unroll
                 for (int g = 1; g < QG; g++) un |= rmask[g];
@@ -314,14 +335,23 @@ __global__ __launch_bounds__(NN_BLOCK, PCR_S2_WAVES) void nn1_strack3_kernel(
                 for (int g = 0; g < QG; g++) {
                     tmask[g] = 0u;
                     if (!((gm1 >> g) & 1u)) continue;         // (wave-uniform)
-                    const f32x16 acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, Ar[u]), __builtin_bit_cast(f16x8, bq1[g]), zero, 0, 0, 0);
-                    if (stats) st_l1++;
-                    if (!__builtin_amdgcn_ballot_w64((int)s2_or16(acc) < 0)) continue;
+                    if (TR) {                                 // (stored row n of the tile = chunk 2 (n & 15) + (n >> 4): level-2 tile k is rows k and k + 16)
+                        const uint32_t og = s2_or16(__builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, bq1[g]), __builtin_bit_cast(f16x8, Ar[u]), zero, 0, 0, 0));
+                        if (stats) st_l1++;
+                        const unsigned long long m = __builtin_amdgcn_ballot_w64((int)og < 0);
+                        const uint32_t cm = (uint32_t)m | (uint32_t)(m >> 32);
+                        tmask[g] = (cm | (cm >> 16)) & 0xFFFFu;
+                    }
+                    else {
+                        const f32x16 acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, Ar[u]), __builtin_bit_cast(f16x8, bq1[g]), zero, 0, 0, 0);
+                        if (stats) st_l1++;
+                        if (!__builtin_amdgcn_ballot_w64((int)s2_or16(acc) < 0)) continue;
 #pragma unroll
-                    for (int i = 0; i < 16; i += 2) {         // (lanes < 32 hold chunks 0..15 of the tile, lanes >= 32 chunks 16..31: accumulator i <-> chunk 16 h + i)
-                        const unsigned long long m = __builtin_amdgcn_ballot_w64((int)(__float_as_uint(acc[i]) | __float_as_uint(acc[i + 1])) < 0);
-                        tmask[g] |= ((uint32_t)m != 0u ? 1u : 0u) << (i / 2);
-                        tmask[g] |= ((uint32_t)(m >> 32) != 0u ? 1u : 0u) << (8 + i / 2);
+                        for (int i = 0; i < 8; i++) {         // (accumulators i and i + 8 of lane-half h: rows k and k + 16, k = 8 (i >> 2) + 4 h + (i & 3))
+                            const unsigned long long m = __builtin_amdgcn_ballot_w64((int)(__float_as_uint(acc[i]) | __float_as_uint(acc[i + 8])) < 0);
+                            tmask[g] |= ((uint32_t)m != 0u ? 1u : 0u) << (8 * (i >> 2) + (i & 3));
+                            tmask[g] |= ((uint32_t)(m >> 32) != 0u ? 1u : 0u) << (8 * (i >> 2) + 4 + (i & 3));
+                        }
                     }
                     un |= tmask[g];
                 }
@@ -390,3 +420,16 @@ __global__ __launch_bounds__(NN_BLOCK, PCR_S2_WAVES) void nn1_strack3_kernel(
         if (st_l2) atomicAdd(&stats[10], st_l2);                          // level-2 MFMAs
     }
 }
+
+#define PCR_S3_PARAMS                                                                                                                                   \
+    const float4* __restrict__ l0_centres, const uint4* __restrict__ l0_ops, const float4* __restrict__ l1_centres, const uint4* __restrict__ l1_ops,   \
+    const uint4* __restrict__ ops, const float4* __restrict__ records, uint32_t n_rec, uint32_t n_l0, uint32_t l0_per_slice,                            \
+    const float* __restrict__ sx, const float* __restrict__ sy, const float* __restrict__ sz, uint32_t ns,                                              \
+    unsigned long long* __restrict__ keys, const int* __restrict__ stop, unsigned long long* __restrict__ stats, uint32_t flush_at, uint32_t flush_end
+#define PCR_S3_ARGS l0_centres, l0_ops, l1_centres, l1_ops, ops, records, n_rec, n_l0, l0_per_slice, sx, sy, sz, ns, keys, stop, stats, flush_at, flush_end
+template <int QG>
+__global__ __launch_bounds__(NN_BLOCK, PCR_S2_WAVES) void nn1_strack3_kernel(PCR_S3_PARAMS) { nn1_strack3_body<QG, true>(PCR_S3_ARGS); }
+template <int QG>
+__global__ __launch_bounds__(NN_BLOCK, PCR_S2_WAVES) void nn1_strack3_rows_kernel(PCR_S3_PARAMS) { nn1_strack3_body<QG, false>(PCR_S3_ARGS); }      // tune nn1_s3_transposed = 2
+#undef PCR_S3_PARAMS
+#undef PCR_S3_ARGS

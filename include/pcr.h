@@ -459,6 +459,7 @@ int pcr_ctx_mfma_check(pcr_ctx* ctx, int run_now, pcr_mfma_check* out);
  *              nn1_sign_dense [12: flagged half-lanes of one (group, tile) from which they evaluate their chunk in place] ·
  *              nn1_sphere_qg [1: groups of 32 queries per STRACK3 wave] 2 / 4 · nn1_sphere_flush_end [1: entries from which the end of
  *              a level-1 super-tile evaluates them] · nn1_sphere_l0_per_slice [from nn1_sphere_blocks = 1 024] ·
+ *              nn1_s3_transposed [1: STRACK3 reads its sphere-row masks from one ballot of the transposed product] 2 = one ballot per accumulator ·
  *              nn1_xcd [4] 1 / 2 / 4, -1 plain launch · nn1_cold_seed [on] 2 = off, 3 = round 3's rule (sliced launches only) ·
  *              nn1_seed_mode [0: centre of the nearest super-tile + Morton neighbour for a cold search, the centre alone beside stale correspondences]
  *              1 centre / 2 Morton neighbour / 3 both · nn1_seed_levels [2: the centre scan goes through the level-1 super-tiles' centres first] 1 = all centres · nn1_sphere_reseed [on] 2 = a warm search of the sphere forms keeps stale seeds as they are ·
