@@ -2,8 +2,13 @@
 // row of processDataSet :152-165) reduced to the part that is on the hot path: read a source / target pair, run
 // point-to-point ICP with the shipped parameters (main.cpp:88-95) on the MI355X, print
 //     idx1,idx2,t_x,t_y,t_z,q_w,q_x,q_y,q_z
-// Everything upstream in the reference (voxel grid, Harris, FPFH, feature RANSAC, normal-space sampling) needs PCL and
-// is out of scope; the initial pose is the identity unless given.
+// This driver is built without PCL, so the initial pose is the identity.  With PCL's point types at hand the upstream stages plug
+// into the drop-in class as GPU bodies:
+//     pcr::Registration reg;  reg.setHarris3Dparams(voxel_size * 2, 1e-8, 8, true, false);  reg.setFPFHparams(voxel_size * 4);
+//     reg.stages.keypoints = reg.gpuHarris3DStage();      // getHarris3DKeypoints on the GPU (pcr_harris3d_f32)
+//     reg.stages.fpfh33 = reg.gpuFPFH33Stage();           // getFPFH33Descriptors on the GPU (pcr_fpfh33_f32)
+//     reg.compute(cloud_source, cloud_target, normals_source, normals_target, R, t);
+// Normal-space sampling (a seeded random draw through PCL's own generator) stays the reference's code.
 //   usage: hw9_registration_driver <src.bin> <tgt.bin> <floats_per_point: 4 (KITTI x y z i) | 6 (hw9 x y z nx ny nz)>
 //                                  [idx_src idx_tgt [max_iter]]
 #include <cmath>

@@ -38,6 +38,10 @@ class IssParams(C.Structure):
                 ("min_neighbors", C.c_int), ("weighted_covariance", C.c_int)]
 
 
+class Harris3dParams(C.Structure):
+    _fields_ = [("radius", C.c_float), ("threshold", C.c_float), ("method", C.c_int), ("non_max_suppression", C.c_int)]
+
+
 class IcpStats(C.Structure):
     _fields_ = [("iters_run", C.c_uint64), ("converged", C.c_int32), ("empty_pairs", C.c_int32),
                 ("last_pairs", C.c_uint64), ("last_loss", C.c_float), ("reserved", C.c_float),
@@ -63,7 +67,7 @@ ABI_SYMBOLS = [
     "pcr_nn1_desc_f32", "pcr_match_union_f32", "pcr_match_inter_f32", "pcr_ransac_sample_quads", "pcr_consensus_count_f32", "pcr_ransac_global_f32", "pcr_db64_create", "pcr_db64_destroy", "pcr_db64_size", "pcr_db64_knn", "pcr_db64_radius",
     "pcr_ctx_trim", "pcr_ctx_parked_bytes", "pcr_cloud_shard_spatial", "pcr_cloud_global_index", "pcr_cloud_sort_for_target", "pcr_nn1_f32_loop",
     "pcr_db64_radius_rows", "pcr_rows_destroy", "pcr_rows_info", "pcr_rows_row_ptr", "pcr_rows_fetch", "pcr_rows_reduce", "pcr_rows_moments",
-    "pcr_dbscan_f32", "pcr_statistical_outlier_f32", "pcr_fpfh33_f32",
+    "pcr_dbscan_f32", "pcr_statistical_outlier_f32", "pcr_fpfh33_f32", "pcr_harris3d_f32",
 ]
 
 
@@ -156,6 +160,7 @@ def lib():
     L.pcr_dbscan_f32.argtypes = [vp, vp, C.c_double, C.c_int, vp, vp, vp, C.POINTER(C.c_uint64)]
     L.pcr_statistical_outlier_f32.argtypes = [vp, vp, C.c_int, C.c_double, vp, vp, vp, C.POINTER(C.c_uint64), C.POINTER(vp)]
     L.pcr_fpfh33_f32.argtypes = [vp, vp, vp, vp, C.c_float, vp, vp, vp]
+    L.pcr_harris3d_f32.argtypes = [vp, vp, vp, C.POINTER(Harris3dParams), vp, vp, vp, C.POINTER(C.c_uint64)]
     L.pcr_nn1_desc_f32.argtypes = [vp, vp, sz, vp, sz, C.c_int, vp, vp]
     L.pcr_match_union_f32.argtypes = [vp, vp, sz, vp, sz, C.c_int, C.c_float, vp, vp, C.POINTER(sz)]
     L.pcr_match_inter_f32.argtypes = [vp, vp, sz, vp, sz, C.c_int, C.c_float, vp, vp, C.POINTER(sz)]
@@ -653,6 +658,24 @@ class Context:
         if spfh:
             return out[:m], cnt[:m], sp[:n]
         return out[:m], cnt[:m]
+
+    # ---- Homework9 keypoints
+    def harris3d(self, cloud: Cloud, normals, radius, threshold=1e-8, method=0, nms=True):
+        """getHarris3DKeypoints (hw9 registration.cpp:221-250, PCL HarrisKeypoint3D with the caller's normals) -> (keypoint indices
+        ascending, response f32[n], |N(i)| u32[n]); the contract of pcr_harris3d_f32.  normals: a Cloud or an [n,3] array (cast to
+        f32); method 0 HARRIS, 1 NOBLE, 2 LOWE; nms=False returns every finite point."""
+        if not isinstance(normals, Cloud):
+            normals = self.cloud(np.asarray(normals, np.float32).reshape(-1, 3), PCR_AOS3)
+        n = len(cloud)
+        key = np.zeros(max(n, 1), np.uint8)
+        resp = np.zeros(max(n, 1), np.float32)
+        cn = np.zeros(max(n, 1), np.uint32)
+        prm = Harris3dParams(float(radius), float(threshold), int(method), int(bool(nms)))
+        cnt = C.c_uint64()
+        self._ck(lib().pcr_harris3d_f32(self.h, cloud.h, normals.h, C.byref(prm), key.ctypes.data, resp.ctypes.data, cn.ctypes.data, C.byref(cnt)))
+        idx = np.flatnonzero(key[:n])
+        assert idx.size == cnt.value
+        return idx, resp[:n], cn[:n]
 
     # ---- N4
     def nn1_desc(self, db, q):

@@ -314,6 +314,46 @@ int pcr_statistical_outlier_f32(pcr_ctx* ctx, const pcr_cloud* cloud, int nb_nei
 int pcr_fpfh33_f32(pcr_ctx* ctx, const pcr_cloud* surface, const pcr_cloud* normals, const pcr_cloud* keypoints, float radius, float* fpfh,
                    uint32_t* neighbor_counts, float* spfh);
 
+/* ---- Homework9 keypoints: Harris3D, getHarris3DKeypoints (Homework9/hw9/src/registration.cpp:221-250, PCL HarrisKeypoint3D) -----
+ * PCL is not pinned here: this is the library's own operation sequence, a restatement of PCL's
+ * HarrisKeypoint3D<PointXYZ, PointXYZI> as hw9 configures it: normals supplied by the caller (setNormals), setRadius,
+ * setThreshold, setNonMaxSupression, setRefine(false), default method HARRIS.  All f32 arithmetic below is unfused.
+ * Inputs: cloud (n points), normals (one per point, a cloud whose x/y/z are normal_x/y/z, used as given).
+ * Neighbourhood (the same as pcr_fpfh33_f32): N(i) = { j : s(i, j) < r2 }, STRICT, s = ((dx*dx) + dy*dy) + dz*dz in f32,
+ *   r2 = (float)((double)radius * (double)radius).  A non-finite point is nobody's neighbour; a finite point is its own.
+ * Normal moments (calculateNormalCovar): neighbour j contributes iff all three components of its normal are finite and of
+ *   magnitude <= 2 (the library's rule; PCL tests normal_x only); count = the number of contributors.  For each of the six
+ *   products xx, xy, xz, yy, yz, zz of a contributor's normal: p = fl32(a * b), q = rint(ldexp((double)p, 32)) (ties to
+ *   even; an integer of magnitude <= 2^34), S = the sum of q over the contributors AS AN EXACT INTEGER, and the coefficient is
+ *   c = (float)(((double)S * 0x1p-32) / (double)count); all six are 0 when count == 0.  This departs from PCL on purpose: PCL
+ *   adds the f32 products in FLANN's distance order or in SSE lanes, depending on how it was built, so there is no single PCL
+ *   answer to match; the integer sum does not depend on neighbour order, lanes per point, grid layout or input permutation.
+ *   The quantisation is <= 2^-33 per coefficient.
+ * Response (responseHarris): trace = (cxx + cyy) + czz; when trace != 0,
+ *   det = cxx*cyy*czz + 2.0f*cxy*cxz*cyz - cxz*cxz*cyy - cxy*cxy*czz - cyz*cyz*cxx (left to right, as C parses it) and
+ *   method 0 (HARRIS): response = (0.04f + det) - (0.04f * trace) * trace;  1 (NOBLE): det / trace;  2 (LOWE): det / (trace * trace);
+ *   response = 0 when trace == 0 and for a non-finite point.  TOMASI, CURVATURE and setRefine(true) are not provided: any other
+ *   method is PCR_ERR_ARG.
+ * Keypoints (detectKeypoints): non_max_suppression != 0: is_key[i] = 1 iff point i is finite, response[i] is finite,
+ *   !(response[i] < threshold), and no j in N(i) has response[i] < response[j] (strict: equal responses suppress nobody, so
+ *   the result does not depend on the visiting order).  non_max_suppression == 0: is_key[i] = 1 for every finite point (PCL
+ *   copies the whole response cloud and ignores the threshold).  PCL emits keypoints in OpenMP completion order; here the
+ *   order is ascending input index.
+ * UNPINNED (restated, not compared with PCL): FLANN's strict `<`; PCL's f32 accumulation order (replaced by the integer sum
+ *   above); the response formula 0.04f + det - 0.04f * trace * trace of PCL 1.8-1.12's harris_3d.hpp.
+ * is_key: n bytes (required); response (optional, n floats), neighbor_counts (optional, n) = |N(i)|, n_keypoints (optional) the
+ * number of ones.  PCR_ERR_ARG for a NULL context / cloud / normals / params / is_key, a radius that is non-finite or <= 0, a NaN
+ * threshold, a normal cloud of another size; an empty cloud: PCR_OK with nothing written.  Tune key harris_lanes (lanes per
+ * point: 1, 2, 4, 8, 16, 32); profile names harris_grid_build, harris_response, harris_nms. */
+typedef struct {
+    float radius;
+    float threshold;
+    int method;                  /* 0 HARRIS, 1 NOBLE, 2 LOWE */
+    int non_max_suppression;
+} pcr_harris3d_params;
+int pcr_harris3d_f32(pcr_ctx* ctx, const pcr_cloud* cloud, const pcr_cloud* normals, const pcr_harris3d_params* prm, uint8_t* is_key,
+                     float* response, uint32_t* neighbor_counts, uint64_t* n_keypoints);
+
 /* ---- next row N4: global-registration front half, Homework9/hw9/src/registration.cpp:288-434, :535-615 -----------
  * N4a: exhaustive 1-NN between two descriptor sets (row-major n x dim / m x dim f32, host memory; dim 33 = FPFH),
  * nanoflann's evalMetric arithmetic for any dim (nanoflann.hpp:382-405: groups of four + tail, f32, unfused), canonical
@@ -482,7 +522,7 @@ int pcr_ctx_mfma_check(pcr_ctx* ctx, int run_now, pcr_mfma_check* out);
  *  ICP loop    icp_pipeline [0 = 1 device-resident] -1 synchronous · icp_chunk [4] · icp_bounded_search [on] 2 = off ·
  *              icp_fused_move [on] 2 = off, icp_fused_max [262 144] · icp_seed_in_move [on] 2 = off · icp_force_slots (tests) ·
  *              kabsch_bfly [on], kabsch_records [on], kabsch_one_pair_blocks [128], kabsch_max_blocks [1 024]
- *  other       plane_group [20: hypotheses per workgroup row of the plane count] · iss_lanes [32] · fpfh_lanes [16] · radius_fused [on] 2 = off · grid_stats 1 = the next 1-NN launch fills pcr_nn1_stats · prof 0 / 1 / 2 */
+ *  other       plane_group [20: hypotheses per workgroup row of the plane count] · iss_lanes [32] · fpfh_lanes [16] · harris_lanes [16] · radius_fused [on] 2 = off · grid_stats 1 = the next 1-NN launch fills pcr_nn1_stats · prof 0 / 1 / 2 */
 int pcr_tune_set(pcr_ctx* ctx, const char* key, int64_t value);
 
 #ifdef __cplusplus

@@ -203,8 +203,8 @@ inline void transformNormalsInplace(NormalCloud& cloud, const Eigen::Matrix3f& R
 // class Registration, registration.hpp:67-251 — same public interface (the seven setters and compute) and the same private
 // members for the stages this library accelerates (RANSAC, findRANSACCorrespondencesUnion / Inter, ICPpoint2point,
 // ICPpoint2plane), each with the reference's exact signature.  The remaining private stages of the reference are PCL
-// library calls outside the hot path (Harris3D / ISS keypoints, FPFH / SHOT descriptors, NormalSpaceSampling,
-// VoxelGrid); they are pluggable `stages` so that a maintainer passes the reference's own bodies.
+// library calls (Harris3D / ISS keypoints, FPFH / SHOT descriptors, NormalSpaceSampling, VoxelGrid); they are
+// pluggable `stages` so that a maintainer passes the reference's own bodies or the GPU ones below.
 class Registration
 {
 public:
@@ -237,7 +237,7 @@ public:
     }
 
     // The PCL-internal stages of compute() / ICPpoint2point().  Unset keypoints or fpfh33: compute() has no global
-    // registration to run and starts ICP from the identity (gpuFPFH33Stage() below is a GPU body for fpfh33).  Unset
+    // registration to run and starts ICP from the identity (gpuHarris3DStage() / gpuFPFH33Stage() below are GPU bodies for them).  Unset
     // normal_space_sampling: ICP runs on the full clouds (the reference's own commented alternative, registration.cpp:883-884).
     struct Stages {
         // getHarris3DKeypoints (registration.hpp:152-154, registration.cpp:214-251)
@@ -258,6 +258,17 @@ public:
         return [this](const PointCloud& input_cloud, const PointCloud& input_keypoints_cloud, const NormalCloud& input_normals,
                       pcl::PointCloud<pcl::FPFHSignature33>& fpfh_descriptors) {
             gpuFPFH33(input_cloud, input_keypoints_cloud, input_normals, fpfh_descriptors);
+        };
+    }
+
+    // getHarris3DKeypoints on the GPU (pcr_harris3d_f32, include/pcr.h: the library's restatement of PCL's HarrisKeypoint3D, method
+    // HARRIS) with the radius, threshold and nms flag of setHarris3Dparams, read when the stage runs (threads: ignored; is_refine =
+    // true is not provided and is reported like a failed call).  Opt-in: `reg.stages.keypoints = reg.gpuHarris3DStage();`
+    // (INTEGRATION.md, hw9); an unset stage keeps its meaning.  The stage refers to this Registration, so it must not outlive it.
+    decltype(Stages::keypoints) gpuHarris3DStage()
+    {
+        return [this](const PointCloud& input_cloud, const NormalCloud& input_normals, PointCloud& keypoints_cloud) {
+            gpuHarris3D(input_cloud, input_normals, keypoints_cloud);
         };
     }
 
@@ -415,6 +426,37 @@ private:
             for (int c = 0; c < 3; ++c) R(r, c) = out_T[4 * r + c];
             t(r) = out_T[4 * r + 3];
         }
+    }
+
+    // the body of gpuHarris3DStage: the keypoints in ascending input index, filled as registration.cpp:239-249 does
+    void gpuHarris3D(const PointCloud& input_cloud, const NormalCloud& input_normals, PointCloud& keypoints_cloud) const
+    {
+        const size_t n = input_cloud.size();
+        std::vector<uint8_t> key(n + 1, 0);
+        int rc = m_harris3d_is_refine ? PCR_ERR_ARG : PCR_OK;                                    // setRefine(true): not provided
+        if (rc == PCR_OK && n > 0) {
+            std::vector<float> n3(3 * input_normals.size() + 3);
+            for (size_t i = 0; i < input_normals.size(); i++) {
+                n3[3 * i] = input_normals.points[i].normal_x; n3[3 * i + 1] = input_normals.points[i].normal_y; n3[3 * i + 2] = input_normals.points[i].normal_z;
+            }
+            pcr_ctx* ctx = default_ctx();
+            pcr_cloud *cs = nullptr, *cn = nullptr;
+            pcr_harris3d_params prm;
+            prm.radius = m_harris3d_radius; prm.threshold = m_harris3d_nms_threshold; prm.method = 0;
+            prm.non_max_suppression = m_harris3d_is_nms ? 1 : 0;
+            rc = pcr_cloud_create(ctx, reinterpret_cast<const float*>(input_cloud.points.data()), n, PCR_AOS4, &cs);
+            if (rc == PCR_OK) rc = pcr_cloud_create(ctx, n3.data(), input_normals.size(), PCR_AOS3, &cn);
+            if (rc == PCR_OK) rc = pcr_harris3d_f32(ctx, cs, cn, &prm, key.data(), nullptr, nullptr, nullptr);
+            pcr_cloud_destroy(ctx, cs);
+            pcr_cloud_destroy(ctx, cn);
+        }
+        check(rc, m_harris3d_is_refine ? "pcr_harris3d_f32: setRefine(true) is not provided" : "pcr_harris3d_f32");
+        keypoints_cloud.points.clear();
+        for (size_t i = 0; i < n; i++)
+            if (key[i]) keypoints_cloud.points.push_back(input_cloud.points[i]);
+        keypoints_cloud.height = 1;                                                              // :246-248
+        keypoints_cloud.width = (uint32_t)keypoints_cloud.points.size();
+        keypoints_cloud.is_dense = true;
     }
 
     // the body of gpuFPFH33Stage: one row per keypoint, NaN rows (and is_dense = false) where PCL's computeFeature writes them
