@@ -67,7 +67,7 @@ ABI_SYMBOLS = [
     "pcr_nn1_desc_f32", "pcr_match_union_f32", "pcr_match_inter_f32", "pcr_ransac_sample_quads", "pcr_consensus_count_f32", "pcr_ransac_global_f32", "pcr_db64_create", "pcr_db64_destroy", "pcr_db64_size", "pcr_db64_knn", "pcr_db64_radius",
     "pcr_ctx_trim", "pcr_ctx_parked_bytes", "pcr_cloud_shard_spatial", "pcr_cloud_global_index", "pcr_cloud_sort_for_target", "pcr_nn1_f32_loop",
     "pcr_db64_radius_rows", "pcr_rows_destroy", "pcr_rows_info", "pcr_rows_row_ptr", "pcr_rows_fetch", "pcr_rows_reduce", "pcr_rows_moments",
-    "pcr_dbscan_f32", "pcr_statistical_outlier_f32", "pcr_fpfh33_f32", "pcr_harris3d_f32",
+    "pcr_dbscan_f32", "pcr_statistical_outlier_f32", "pcr_fpfh33_f32", "pcr_harris3d_f32", "pcr_voxel_grid_normals_f32", "pcr_normal_space_sample_f32",
 ]
 
 
@@ -161,6 +161,8 @@ def lib():
     L.pcr_statistical_outlier_f32.argtypes = [vp, vp, C.c_int, C.c_double, vp, vp, vp, C.POINTER(C.c_uint64), C.POINTER(vp)]
     L.pcr_fpfh33_f32.argtypes = [vp, vp, vp, vp, C.c_float, vp, vp, vp]
     L.pcr_harris3d_f32.argtypes = [vp, vp, vp, C.POINTER(Harris3dParams), vp, vp, vp, C.POINTER(C.c_uint64)]
+    L.pcr_voxel_grid_normals_f32.argtypes = [vp, vp, vp, C.c_float, C.c_int, C.POINTER(vp), C.POINTER(vp), vp, vp, C.POINTER(C.c_uint64)]
+    L.pcr_normal_space_sample_f32.argtypes = [vp, vp, vp, sz, C.c_uint64, vp, C.POINTER(sz), vp, C.POINTER(vp), C.POINTER(vp)]
     L.pcr_nn1_desc_f32.argtypes = [vp, vp, sz, vp, sz, C.c_int, vp, vp]
     L.pcr_match_union_f32.argtypes = [vp, vp, sz, vp, sz, C.c_int, C.c_float, vp, vp, C.POINTER(sz)]
     L.pcr_match_inter_f32.argtypes = [vp, vp, sz, vp, sz, C.c_int, C.c_float, vp, vp, C.POINTER(sz)]
@@ -676,6 +678,49 @@ class Context:
         idx = np.flatnonzero(key[:n])
         assert idx.size == cnt.value
         return idx, resp[:n], cn[:n]
+
+    # ---- Homework9 sampling stages
+    def voxel_grid_normals(self, cloud: Cloud, normals, leaf, normal_mode=1):
+        """readBinaryAndVoxelDown's filter (hw9 registration.cpp:37-41, pcl::VoxelGrid<PointNormal> with setDownsampleAllData(true)) -> (centroids
+        Cloud, voxel normals Cloud or None, voxel_of_point i32[n], counts u32[m]); the contract of pcr_voxel_grid_normals_f32.  normals: a
+        Cloud, an [n,3] array (cast to f32) or None; normal_mode 0 = mean, 1 = mean scaled to unit length (hw9)."""
+        if normals is not None and not isinstance(normals, Cloud):
+            normals = self.cloud(np.asarray(normals, np.float32).reshape(-1, 3), PCR_AOS3)
+        n = len(cloud)
+        vop = np.zeros(max(n, 1), np.int32)
+        cnt = np.zeros(max(n, 1), np.uint32)
+        hc, hn, m = C.c_void_p(), C.c_void_p(), C.c_uint64()
+        self._ck(lib().pcr_voxel_grid_normals_f32(self.h, cloud.h, None if normals is None else normals.h, float(leaf), int(normal_mode), C.byref(hc),
+                                                  None if normals is None else C.byref(hn), vop.ctypes.data, cnt.ctypes.data, C.byref(m)))
+        return Cloud(self, hc), (None if normals is None else Cloud(self, hn)), vop[:n], cnt[: m.value]
+
+    def normal_space_sample(self, normals, bins=(10, 10, 10), sample=4000, seed=0, gather=()):
+        """normalSpaceSampling (hw9 registration.cpp:630-662, PCL NormalSpaceSampling) -> (indices u32[min(sample, n_valid)], *gathered); the
+        contract of pcr_normal_space_sample_f32.  normals: a Cloud or an [n,3] array (cast to f32); gather: a Cloud or a tuple of Clouds of n
+        points each — for every one a new device Cloud of its points at the indices comes back, in the tuple's order (the normals Cloud itself
+        may be one of them)."""
+        if not isinstance(normals, Cloud):
+            normals = self.cloud(np.asarray(normals, np.float32).reshape(-1, 3), PCR_AOS3)
+        if isinstance(gather, Cloud):
+            gather = (gather,)
+        n = len(normals)
+        b = (C.c_uint32 * 3)(*[int(v) for v in bins])
+        others = [g for g in gather if g is not normals] or [None]
+        want_normals = any(g is normals for g in gather)
+        out, idx0, sampled_normals = {}, None, None
+        for k, g in enumerate(others):
+            idx = np.zeros(max(min(int(sample), n), 1), np.uint32)
+            m, hc, hn = C.c_size_t(), C.c_void_p(), C.c_void_p()
+            self._ck(lib().pcr_normal_space_sample_f32(self.h, normals.h, b, int(sample), int(seed), idx.ctypes.data, C.byref(m), None if g is None else g.h,
+                                                       None if g is None else C.byref(hc), C.byref(hn) if (want_normals and k == 0) else None))
+            if g is not None:
+                out[id(g)] = Cloud(self, hc)
+            if want_normals and k == 0:
+                sampled_normals = Cloud(self, hn)
+            idx = idx[: m.value]
+            assert idx0 is None or np.array_equal(idx, idx0)
+            idx0 = idx
+        return (idx0, *[sampled_normals if g is normals else out[id(g)] for g in gather])
 
     # ---- N4
     def nn1_desc(self, db, q):

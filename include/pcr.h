@@ -354,6 +354,68 @@ typedef struct {
 int pcr_harris3d_f32(pcr_ctx* ctx, const pcr_cloud* cloud, const pcr_cloud* normals, const pcr_harris3d_params* prm, uint8_t* is_key,
                      float* response, uint32_t* neighbor_counts, uint64_t* n_keypoints);
 
+/* ---- Homework9, the front of the flow: readBinaryAndVoxelDown (Homework9/hw9/src/registration.cpp:8-68) and VoxelGridSampling
+ * (:665-707) — pcl::VoxelGrid<pcl::PointNormal> over points AND normals -----------------------------------------------------------
+ * PCL is not pinned here: this is the library's own operation sequence, a restatement of PCL 1.8-1.12 voxel_grid.hpp::applyFilter
+ * with one leaf size for the three axes, setDownsampleAllData(true), no field filter, min_points_per_voxel 0.  (pcr_voxel_filter_f32
+ * above is Homework1's script: another lattice — anchored at the cloud's minimum — xyz only, last voxel dropped.)  All f32
+ * arithmetic below is unfused.
+ * Inputs: cloud (n points), normals (NULL, or one per point: a cloud whose x/y/z are normal_x/y/z), leaf, normal_mode.
+ * Lattice: inv = 1.0f / leaf (f32); per axis c = (int)floorf(fl32(x * inv)); a point with a non-finite coordinate is SKIPPED (hw9
+ *   sets is_dense = true, so PCL does not look).  min_b / max_b = min / max of c over the other points, div = max_b - min_b + 1,
+ *   voxel id = (cx - min_bx) + (cy - min_by) * div_x + (cz - min_bz) * div_x * div_y  (int64).
+ * Output: one row per occupied voxel in ASCENDING VOXEL ID (PCL's order), the last one included; m rows.
+ * Centroid: E = the smallest integer >= -149 such that every coordinate of a point that is not skipped has |coordinate| < 2^E.  Each
+ *   f32 coordinate v becomes the integer q = rint(ldexp((double)v, 32 - E)) (ties to even, |q| <= 2^32), S = the sum of q over the
+ *   voxel's points AS AN EXACT INTEGER (int64: n <= 2^31 - 16), and the output is (float)(((double)S * 2^(E - 32)) / (double)count).
+ *   The quantisation is <= 2^(E - 33) per component of the mean, before the one rounding to f32.
+ * Normal: the same form with E = 2 fixed: a normal contributes iff its three components are finite and of magnitude <= 2 (the rule
+ *   of pcr_harris3d_f32), q = rint(ldexp((double)v, 30)), mean = (float)(((double)S * 2^-30) / (double)count_n) with count_n the
+ *   number of contributing normals of the voxel; (0, 0, 0) when count_n == 0.  A point whose normal does not contribute still counts
+ *   for the centroid.  Quantisation <= 2^-31 per component.
+ *   normal_mode 0: the mean.  normal_mode 1: the mean scaled to unit length in f32, len = sqrtf((nx*nx + ny*ny) + nz*nz), each
+ *   component divided by len; left as it is when len == 0.  hw9's stage is mode 1.
+ * This departs from PCL on purpose: PCL adds the f32 values of a voxel in the order std::sort (unstable) leaves them in, so there
+ *   is no single PCL answer to match; the integer sums do not depend on the order of the points, on how the work is split over
+ *   lanes or on the launch geometry.  Promise: the outputs are a function of the SET of (point, normal) pairs — the same bits for
+ *   any permutation of the input (rows are keyed by voxel id) and on every run.
+ * UNPINNED (restated, not compared with PCL): the lattice arithmetic above as PCL 1.8-1.12 write it; that PCL's CentroidPoint
+ *   normalises an accumulated normal (accumulators.hpp, from memory — which is why normal_mode is a parameter); PCL's f32
+ *   accumulation order (replaced by the integer sums).
+ * out_cloud (required) / out_normals (required iff normals != NULL): new device clouds of m points, the caller's to destroy.
+ * voxel_of_point (optional, n int32, host): the output row of every input point, -1 for a skipped point.  counts (optional, host,
+ * room for n entries, the first m written): points per voxel.  n_voxels (optional): m.
+ * PCR_ERR_ARG: NULL ctx / cloud / out_cloud; a leaf that is non-finite or <= 0 or whose f32 reciprocal is infinite; a normal_mode
+ * other than 0 / 1; a normal cloud of another size or without out_normals; n > 2^31 - 16; a voxel coordinate outside int32 or
+ * div_x * div_y * div_z > INT32_MAX (PCL prints a warning and returns its input).  Empty input, or no finite point: PCR_OK, m = 0.
+ * Profile names vgn_bounds, vgn_keys, vgn_sort, vgn_segments, vgn_accum, vgn_finalize. */
+int pcr_voxel_grid_normals_f32(pcr_ctx* ctx, const pcr_cloud* cloud, const pcr_cloud* normals, float leaf, int normal_mode,
+                               pcr_cloud** out_cloud, pcr_cloud** out_normals, int32_t* voxel_of_point, uint32_t* counts, uint64_t* n_voxels);
+
+/* ---- Homework9, in front of ICP: normalSpaceSampling (Homework9/hw9/src/registration.cpp:630-662, called at :728-729 / :880-881) ---
+ * PCL is not pinned here: this is the library's own operation sequence, a restatement of PCL's NormalSpaceSampling (normal_space.hpp).
+ * Inputs: normals (n, a cloud whose x/y/z are normal_x/y/z), bins[3], sample, seed.  hw9: bins 10 x 10 x 10, sample 4 000, seed 0.
+ * Bin of point i (f32, unfused): ix = roundf((0.5f * (bins_x - 1.f)) * (nx + 1.f)) (half away from zero), clamped to [0, bins_x - 1]
+ *   as a float before the conversion to unsigned; the same for y and z; bin = ix * (bins_y * bins_z) + iy * bins_z + iz.  A point
+ *   whose normal has a non-finite component is never sampled; n_valid = the number of the others.
+ * sample >= n_valid: every samplable point, in ascending index (PCL returns its index list unchanged).
+ * Otherwise PCL goes round the bins in ascending bin order and draws from each bin that is not exhausted one member not yet drawn,
+ *   uniformly at random, until `sample` points are out.  The order-free form of that, which is the contract: point i has the key
+ *     z = seed ^ (0x9E3779B97F4A7C15 * (i + 1));  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;
+ *     k(i) = z ^ (z >> 31)                       (uint64 arithmetic modulo 2^64: SplitMix64's output function on seed ^ golden * (i + 1))
+ *   inside a bin the members are ranked by (k, i) ascending -> rank r = 0, 1, ...; the output is the first `sample` points in
+ *   ascending (r, bin), in that order.  Within a bin this is a uniform draw without replacement, across bins it is PCL's round-robin.
+ * The result depends on (normals, bins, sample, seed) only, not on lanes or launch geometry.
+ * UNPINNED: the random STREAM is not PCL's (boost::mt19937 through `% size` with rejection of members already drawn), so the points
+ *   drawn differ from PCL's for the same seed; PCL's bin formula and its clamping of out-of-range normals are restated, not compared.
+ * indices (host, room for min(sample, n) entries; may be NULL when that is 0): the first *n_out = min(sample, n_valid) written.
+ * gather_cloud + out_cloud (optional, together; gather_cloud has n points): a new device cloud of gather_cloud's points at the
+ * indices, in their order; out_normals (optional): the same of the normals — so that ICP takes both without a host round trip.
+ * PCR_ERR_ARG: NULL ctx / normals / bins / n_out; a bin count < 1 or a product of the three > 2^20; gather_cloud without out_cloud
+ * or the reverse, or of another size; n > 2^31 - 16.  Profile names nss_keys, nss_sort, nss_rank, nss_gather. */
+int pcr_normal_space_sample_f32(pcr_ctx* ctx, const pcr_cloud* normals, const uint32_t bins[3], size_t sample, uint64_t seed, uint32_t* indices,
+                                size_t* n_out, const pcr_cloud* gather_cloud, pcr_cloud** out_cloud, pcr_cloud** out_normals);
+
 /* ---- next row N4: global-registration front half, Homework9/hw9/src/registration.cpp:288-434, :535-615 -----------
  * N4a: exhaustive 1-NN between two descriptor sets (row-major n x dim / m x dim f32, host memory; dim 33 = FPFH),
  * nanoflann's evalMetric arithmetic for any dim (nanoflann.hpp:382-405: groups of four + tail, f32, unfused), canonical

@@ -154,10 +154,15 @@ public:
 #include <Eigen/Core>
 #include <pcl/point_cloud.h>
 #include <pcl/point_types.h>
+#if __has_include(<pcl/impl/point_types.hpp>)
+#include <pcl/impl/point_types.hpp>                             // pcl::PointNormal's definition (PCL's point_types.h includes it itself)
+#endif
 
+#include <fstream>
 #include <functional>
 #include <iostream>
 #include <limits>
+#include <string>
 
 // ---- (2) the reference's own types and signatures (Homework9/hw9/include/registration.hpp) --------------------------------
 // Everything below compiles only where PCL + Eigen exist (the reference's build environment).  In this repository it is
@@ -200,11 +205,85 @@ inline void transformNormalsInplace(NormalCloud& cloud, const Eigen::Matrix3f& R
     }
 }
 
+// The voxel grid of hw9 (pcl::VoxelGrid<pcl::PointNormal> with setDownsampleAllData(true): pcr_voxel_grid_normals_f32, normal_mode 1,
+// include/pcr.h — the library's restatement, not PCL bit for bit) over a cloud and its normals: the filter of readBinaryAndVoxelDown
+// (registration.cpp:37-41) and the whole of VoxelGridSampling (:665-707).  Rows come out in ascending voxel id.
+inline void voxelGridWithNormals(const PointCloud& input_cloud, const NormalCloud& input_normals, float leaf, PointCloud& out_cloud, NormalCloud& out_normals)
+{
+    const size_t n = input_cloud.size();
+    std::vector<float> n3(3 * input_normals.size() + 3);
+    for (size_t i = 0; i < input_normals.size(); i++) {
+        n3[3 * i] = input_normals.points[i].normal_x; n3[3 * i + 1] = input_normals.points[i].normal_y; n3[3 * i + 2] = input_normals.points[i].normal_z;
+    }
+    pcr_ctx* ctx = default_ctx();
+    pcr_cloud *cs = nullptr, *cn = nullptr, *oc = nullptr, *on = nullptr;
+    uint64_t m = 0;
+    std::vector<PointT> pts;
+    std::vector<float> nr;
+    int rc = pcr_cloud_create(ctx, reinterpret_cast<const float*>(input_cloud.points.data()), n, PCR_AOS4, &cs);
+    if (rc == PCR_OK) rc = pcr_cloud_create(ctx, n3.data(), input_normals.size(), PCR_AOS3, &cn);
+    if (rc == PCR_OK) rc = pcr_voxel_grid_normals_f32(ctx, cs, cn, leaf, 1, &oc, &on, nullptr, nullptr, &m);
+    if (rc == PCR_OK) {
+        pts.resize((size_t)m);                                      // default-constructed: data[3] = 1, as PCL's points have
+        nr.resize(3 * (size_t)m + 3);
+        rc = pcr_cloud_read(ctx, oc, reinterpret_cast<float*>(pts.data()), PCR_AOS4);
+        if (rc == PCR_OK) rc = pcr_cloud_read(ctx, on, nr.data(), PCR_AOS3);
+    }
+    pcr_cloud_destroy(ctx, cs);
+    pcr_cloud_destroy(ctx, cn);
+    pcr_cloud_destroy(ctx, oc);
+    pcr_cloud_destroy(ctx, on);
+    check(rc, "pcr_voxel_grid_normals_f32");
+    out_cloud.points = pts;
+    out_normals.points.assign((size_t)m, NormalT());
+    for (size_t i = 0; i < (size_t)m; i++) {
+        out_normals.points[i].normal_x = nr[3 * i]; out_normals.points[i].normal_y = nr[3 * i + 1]; out_normals.points[i].normal_z = nr[3 * i + 2];
+    }
+    out_cloud.height = 1;                                           // :61-66, :690-696
+    out_cloud.width = (uint32_t)out_cloud.points.size();
+    out_cloud.is_dense = true;
+    out_normals.height = 1;
+    out_normals.width = (uint32_t)out_normals.points.size();
+    out_normals.is_dense = true;
+}
+
+// readBinaryAndVoxelDown, registration.hpp:50-53 / registration.cpp:8-68, with the reference's signature: the reader loop as written
+// there and the voxel grid on the GPU.  The `good() && !eof()` loop tests the stream BEFORE each read, so the read that hits the end of
+// the file still appends its point: one extra default-constructed pcl::PointNormal (all zeros) follows the last row, and it takes part
+// in the voxel grid like any other point (a voxel at the origin with a zero normal) — the same kind of quirk as readBinary's extra
+// point in Homework2, kept because it is what hw9 computes.
+inline void readBinaryAndVoxelDown(const std::string& fileName, PointCloud& cloud, NormalCloud& normals, float voxel_size)
+{
+    std::fstream input(fileName.c_str(), std::ios::in | std::ios::binary);
+    input.seekg(0, std::ios::beg);
+    if (!input.good()) {
+        std::cerr << "Read file " << fileName << " failed!";
+        std::exit(EXIT_FAILURE);
+    }
+    PointCloud raw_cloud;
+    NormalCloud raw_normals;
+    for (int i = 0; input.good() && !input.eof(); i++) {
+        pcl::PointNormal point_normal_tmp;
+        input.read((char*)&point_normal_tmp.x, 3 * sizeof(float));
+        input.read((char*)&point_normal_tmp.normal_x, 3 * sizeof(float));
+        PointT p;
+        p.x = point_normal_tmp.x; p.y = point_normal_tmp.y; p.z = point_normal_tmp.z;
+        NormalT nn;
+        nn.normal_x = point_normal_tmp.normal_x; nn.normal_y = point_normal_tmp.normal_y; nn.normal_z = point_normal_tmp.normal_z;
+        raw_cloud.points.push_back(p);
+        raw_normals.points.push_back(nn);
+    }
+    input.close();
+    voxelGridWithNormals(raw_cloud, raw_normals, voxel_size, cloud, normals);
+}
+
 // class Registration, registration.hpp:67-251 — same public interface (the seven setters and compute) and the same private
 // members for the stages this library accelerates (RANSAC, findRANSACCorrespondencesUnion / Inter, ICPpoint2point,
 // ICPpoint2plane), each with the reference's exact signature.  The remaining private stages of the reference are PCL
 // library calls (Harris3D / ISS keypoints, FPFH / SHOT descriptors, NormalSpaceSampling, VoxelGrid); they are
-// pluggable `stages` so that a maintainer passes the reference's own bodies or the GPU ones below.
+// pluggable `stages` so that a maintainer passes the reference's own bodies or the GPU ones below: with
+// gpuHarris3DStage(), gpuFPFH33Stage() and gpuNormalSpaceSamplingStage() set, and readBinaryAndVoxelDown above in front, the whole
+// shipped flow runs without a PCL algorithm.
 class Registration
 {
 public:
@@ -238,7 +317,8 @@ public:
 
     // The PCL-internal stages of compute() / ICPpoint2point().  Unset keypoints or fpfh33: compute() has no global
     // registration to run and starts ICP from the identity (gpuHarris3DStage() / gpuFPFH33Stage() below are GPU bodies for them).  Unset
-    // normal_space_sampling: ICP runs on the full clouds (the reference's own commented alternative, registration.cpp:883-884).
+    // normal_space_sampling: ICP runs on the full clouds (the reference's own commented alternative, registration.cpp:883-884);
+    // gpuNormalSpaceSamplingStage() / gpuVoxelGridSamplingStage() below are GPU bodies for it.
     struct Stages {
         // getHarris3DKeypoints (registration.hpp:152-154, registration.cpp:214-251)
         std::function<void(const PointCloud& input_cloud, const NormalCloud& input_normals, PointCloud& keypoints_cloud)> keypoints;
@@ -269,6 +349,28 @@ public:
     {
         return [this](const PointCloud& input_cloud, const NormalCloud& input_normals, PointCloud& keypoints_cloud) {
             gpuHarris3D(input_cloud, input_normals, keypoints_cloud);
+        };
+    }
+
+    // normalSpaceSampling on the GPU (pcr_normal_space_sample_f32, include/pcr.h: the library's restatement of PCL's NormalSpaceSampling —
+    // PCL's round-robin over the normal bins with the library's own seeded keys, not boost's stream) with the bins and the sample size
+    // of setICPparams, read when the stage runs, and seed 0 (registration.cpp:638-640).  Opt-in:
+    // `reg.stages.normal_space_sampling = reg.gpuNormalSpaceSamplingStage();`; an unset stage keeps its meaning
+    // (ICP on the full clouds).  Fewer samplable points than the sample size: all of them come back (the reference asserts instead, :646).
+    // The stage refers to this Registration, so it must not outlive it.
+    decltype(Stages::normal_space_sampling) gpuNormalSpaceSamplingStage()
+    {
+        return [this](const PointCloud& input_cloud, const NormalCloud& input_normals, PointCloud& sampled_cloud, NormalCloud& sampled_normals) {
+            gpuNormalSpaceSampling(input_cloud, input_normals, sampled_cloud, sampled_normals);
+        };
+    }
+
+    // VoxelGridSampling (registration.hpp:175-177, registration.cpp:665-707: the reference's own commented alternative, :883-884) as a
+    // second body for the same stage: the voxel grid over points and normals at leaf 1.75 (pcr_voxel_grid_normals_f32, normal_mode 1).
+    decltype(Stages::normal_space_sampling) gpuVoxelGridSamplingStage()
+    {
+        return [](const PointCloud& input_cloud, const NormalCloud& input_normals, PointCloud& sampled_cloud, NormalCloud& sampled_normals) {
+            voxelGridWithNormals(input_cloud, input_normals, 1.75f, sampled_cloud, sampled_normals);
         };
     }
 
@@ -426,6 +528,45 @@ private:
             for (int c = 0; c < 3; ++c) R(r, c) = out_T[4 * r + c];
             t(r) = out_T[4 * r + 3];
         }
+    }
+
+    // the body of gpuNormalSpaceSamplingStage: the sampled points and their normals in the order of the draw, filled as :641-660 does
+    void gpuNormalSpaceSampling(const PointCloud& input_cloud, const NormalCloud& input_normals, PointCloud& sampled_cloud, NormalCloud& sampled_normals) const
+    {
+        const size_t n = input_normals.size();
+        std::vector<uint32_t> indices(n + 1);
+        size_t m = 0;
+        int rc = input_cloud.size() == n && m_ICP_normal_bins >= 1 ? PCR_OK : PCR_ERR_ARG;
+        if (rc == PCR_OK) {
+            std::vector<float> n3(3 * n + 3);
+            for (size_t i = 0; i < n; i++) {
+                n3[3 * i] = input_normals.points[i].normal_x; n3[3 * i + 1] = input_normals.points[i].normal_y; n3[3 * i + 2] = input_normals.points[i].normal_z;
+            }
+            pcr_ctx* ctx = default_ctx();
+            pcr_cloud* cn = nullptr;
+            const uint32_t bins[3] = { (uint32_t)m_ICP_normal_bins, (uint32_t)m_ICP_normal_bins, (uint32_t)m_ICP_normal_bins };
+            rc = pcr_cloud_create(ctx, n3.data(), n, PCR_AOS3, &cn);
+            if (rc == PCR_OK) rc = pcr_normal_space_sample_f32(ctx, cn, bins, m_ICP_sampled_size, 0, indices.data(), &m, nullptr, nullptr, nullptr);
+            pcr_cloud_destroy(ctx, cn);
+        }
+        check(rc, "pcr_normal_space_sample_f32");
+        sampled_cloud.points.clear();
+        NormalCloud new_normals;
+        for (size_t i = 0; i < m; i++) {
+            sampled_cloud.points.push_back(input_cloud.points[indices[i]]);
+            NormalT nn;
+            nn.normal_x = input_normals.points[indices[i]].normal_x;
+            nn.normal_y = input_normals.points[indices[i]].normal_y;
+            nn.normal_z = input_normals.points[indices[i]].normal_z;
+            new_normals.points.push_back(nn);
+        }
+        sampled_cloud.height = 1;
+        sampled_cloud.width = (uint32_t)m;
+        sampled_cloud.is_dense = true;
+        new_normals.height = 1;                                                                  // :651-653
+        new_normals.width = (uint32_t)m;
+        new_normals.is_dense = true;
+        sampled_normals = new_normals;
     }
 
     // the body of gpuHarris3DStage: the keypoints in ascending input index, filled as registration.cpp:239-249 does
