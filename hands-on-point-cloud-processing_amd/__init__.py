@@ -19,6 +19,7 @@ LIB_PATH = os.environ.get("PCR_LIB_PATH") or os.path.join(_HERE, "libpcr_hip.so"
 INCLUDE_DIR = os.path.join(os.path.dirname(_HERE), "include")
 
 PCR_SOA, PCR_AOS3, PCR_AOS4, PCR_AOS6 = 0, 1, 2, 6
+PCR_FPS_F32, PCR_FPS_F64 = 0, 1
 ERRORS = {0: "ok", -1: "bad argument", -2: "HIP error", -3: "out of memory", -4: "bad state",
           -5: "RCCL/collective error", -6: "no correspondence kept"}
 
@@ -68,6 +69,7 @@ ABI_SYMBOLS = [
     "pcr_ctx_trim", "pcr_ctx_parked_bytes", "pcr_cloud_shard_spatial", "pcr_cloud_global_index", "pcr_cloud_sort_for_target", "pcr_nn1_f32_loop",
     "pcr_db64_radius_rows", "pcr_rows_destroy", "pcr_rows_info", "pcr_rows_row_ptr", "pcr_rows_fetch", "pcr_rows_reduce", "pcr_rows_moments",
     "pcr_dbscan_f32", "pcr_statistical_outlier_f32", "pcr_fpfh33_f32", "pcr_harris3d_f32", "pcr_voxel_grid_normals_f32", "pcr_normal_space_sample_f32",
+    "pcr_fps_f32", "pcr_ball_query_f32", "pcr_group_points_f32", "pcr_objects_from_labels_f32",
 ]
 
 
@@ -163,6 +165,10 @@ def lib():
     L.pcr_harris3d_f32.argtypes = [vp, vp, vp, C.POINTER(Harris3dParams), vp, vp, vp, C.POINTER(C.c_uint64)]
     L.pcr_voxel_grid_normals_f32.argtypes = [vp, vp, vp, C.c_float, C.c_int, C.POINTER(vp), C.POINTER(vp), vp, vp, C.POINTER(C.c_uint64)]
     L.pcr_normal_space_sample_f32.argtypes = [vp, vp, vp, sz, C.c_uint64, vp, C.POINTER(sz), vp, C.POINTER(vp), C.POINTER(vp)]
+    L.pcr_fps_f32.argtypes = [vp, vp, vp, sz, sz, C.c_int, vp, vp, vp]
+    L.pcr_ball_query_f32.argtypes = [vp, vp, vp, vp, vp, sz, C.c_double, sz, vp, vp]
+    L.pcr_group_points_f32.argtypes = [vp, vp, vp, vp, vp, sz, vp, sz, vp, sz, vp, vp]
+    L.pcr_objects_from_labels_f32.argtypes = [vp, vp, vp, sz, sz, C.c_double, C.c_double, vp, C.c_uint64, vp, vp, vp, vp, vp, vp, vp, C.POINTER(sz)]
     L.pcr_nn1_desc_f32.argtypes = [vp, vp, sz, vp, sz, C.c_int, vp, vp]
     L.pcr_match_union_f32.argtypes = [vp, vp, sz, vp, sz, C.c_int, C.c_float, vp, vp, C.POINTER(sz)]
     L.pcr_match_inter_f32.argtypes = [vp, vp, sz, vp, sz, C.c_int, C.c_float, vp, vp, C.POINTER(sz)]
@@ -721,6 +727,96 @@ class Context:
             assert idx0 is None or np.array_equal(idx, idx0)
             idx0 = idx
         return (idx0, *[sampled_normals if g is normals else out[id(g)] for g in gather])
+
+    # ---- HomeworkFinal: PointNet++ sampling / grouping and the object extraction loop
+    @staticmethod
+    def _seg(seg_ptr):
+        sp = np.ascontiguousarray(seg_ptr, np.uint32).reshape(-1)
+        if sp.size < 1:
+            raise PcrError("seg_ptr needs n_seg + 1 entries")
+        return sp
+
+    def fps(self, cloud: Cloud, seg_ptr, npoint: int, start, mode: int = PCR_FPS_F32, return_regime: bool = False):
+        """Farthest point sampling per segment (pointnet_util.farthest_point_sample in PCR_FPS_F32, DataLoader.farthest_point_sample in
+        PCR_FPS_F64) -> segment-local indices u32 [n_seg, npoint] (and the kernel regime u8 [n_seg] of each segment); the contract of
+        pcr_fps_f32.  start: the first pick of every segment (the reference draws it unseeded)."""
+        sp = self._seg(seg_ptr)
+        n_seg = sp.size - 1
+        st = np.ascontiguousarray(start, np.uint32).reshape(-1)
+        if st.size != n_seg:
+            raise PcrError("one start per segment")
+        out = np.zeros((n_seg, max(int(npoint), 0)), np.uint32)
+        reg = np.zeros(max(n_seg, 1), np.uint8)
+        self._ck(lib().pcr_fps_f32(self.h, cloud.h, sp.ctypes.data, n_seg, int(npoint), int(mode), st.ctypes.data if n_seg else None,
+                                   out.ctypes.data if out.size else None, reg.ctypes.data))
+        return (out, reg[:n_seg]) if return_regime else out
+
+    def ball_query(self, cloud: Cloud, seg_ptr, centres: Cloud, centre_seg_ptr, radius: float, nsample: int):
+        """query_ball_point per segment (pointnet_util.py:90-116) -> (segment-local indices u32 [rows, nsample], hits per row capped at
+        nsample u32 [rows]); the contract of pcr_ball_query_f32 (an empty row holds the segment's size)."""
+        sp, cp = self._seg(seg_ptr), self._seg(centre_seg_ptr)
+        if sp.size != cp.size:
+            raise PcrError("the two seg_ptr arrays describe the same segments")
+        rows = int(cp[-1]) - int(cp[0])
+        idx = np.zeros((max(rows, 1), max(int(nsample), 1)), np.uint32)
+        cnt = np.zeros(max(rows, 1), np.uint32)
+        self._ck(lib().pcr_ball_query_f32(self.h, cloud.h, sp.ctypes.data, centres.h, cp.ctypes.data, sp.size - 1, float(radius), int(nsample),
+                                          idx.ctypes.data, cnt.ctypes.data))
+        return idx[:rows], cnt[:rows]
+
+    def group_points(self, cloud: Cloud, seg_ptr, centres: Cloud, centre_seg_ptr, idx, features=None):
+        """The gather of sample_and_group (pointnet_util.py:145-150) -> (new_xyz f32 [rows, 3], new_points f32 [rows, nsample, 3 + D]); the
+        contract of pcr_group_points_f32.  features: None or [len(cloud), D] (cast to f32)."""
+        sp, cp = self._seg(seg_ptr), self._seg(centre_seg_ptr)
+        if sp.size != cp.size:
+            raise PcrError("the two seg_ptr arrays describe the same segments")
+        rows = int(cp[-1]) - int(cp[0])
+        ix = np.ascontiguousarray(idx, np.uint32)
+        nsample = ix.shape[-1] if ix.ndim >= 2 else 0
+        ix = ix.reshape(-1, max(nsample, 1))
+        if ix.shape[0] != rows:
+            raise PcrError("one index row per centre")
+        feat, D = None, 0
+        if features is not None:
+            feat = np.ascontiguousarray(features, np.float32)
+            feat = feat.reshape(feat.shape[0], -1)
+            D = feat.shape[1]
+            if feat.shape[0] != len(cloud):
+                raise PcrError("one feature row per point of the cloud")
+        new_xyz = np.zeros((max(rows, 1), 3), np.float32)
+        new_points = np.zeros((max(rows, 1), max(nsample, 1), 3 + D), np.float32)
+        self._ck(lib().pcr_group_points_f32(self.h, cloud.h, sp.ctypes.data, centres.h, cp.ctypes.data, sp.size - 1, None if not D else feat.ctypes.data, D,
+                                            ix.ctypes.data, int(nsample), new_xyz.ctypes.data, new_points.ctypes.data))
+        return new_xyz[:rows], new_points[:rows]
+
+    def objects_from_labels(self, cloud: Cloud, labels, n_clusters: int, npoints: int = 256, ground_z: float = 0.0, z_min_above_ground: float = 0.5,
+                            z_extent=(1.0, 2.3), seed: int = 0, starts=None):
+        """The per-cluster loop of foreground_obj_cls.py:143-180 -> dict(objects f32 [n_obj, npoints, 3], cluster u32 [n_obj], source_index
+        u32 [n_obj, npoints], codes i32 [n_clusters] (3 = gated as the reference writes it, -1 = to be classified), z_min_max f32
+        [n_clusters, 2], sizes u32 [n_clusters]); the contract of pcr_objects_from_labels_f32.  starts: None, or per cluster the first FPS
+        pick inside the cluster (0xFFFFFFFF = draw it from the seed)."""
+        lab = np.ascontiguousarray(labels, np.int32).reshape(-1)
+        if lab.size != len(cloud):
+            raise PcrError("one label per point")
+        nc = int(n_clusters)
+        cap = max(nc, 1)
+        objects = np.zeros((cap, int(npoints), 3), np.float32)
+        oc = np.zeros(cap, np.uint32)
+        src = np.zeros((cap, int(npoints)), np.uint32)
+        codes = np.zeros(cap, np.int32)
+        zmm = np.zeros((cap, 2), np.float32)
+        sizes = np.zeros(cap, np.uint32)
+        ext = np.ascontiguousarray(z_extent, np.float64).reshape(2)
+        st = None if starts is None else np.ascontiguousarray(starts, np.uint32).reshape(-1)
+        if st is not None and st.size != nc:
+            raise PcrError("one start per cluster")
+        m = C.c_size_t()
+        self._ck(lib().pcr_objects_from_labels_f32(self.h, cloud.h, lab.ctypes.data if lab.size else None, nc, int(npoints), float(ground_z),
+                                                   float(z_min_above_ground), ext.ctypes.data, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                                   None if st is None or not nc else st.ctypes.data, objects.ctypes.data, oc.ctypes.data, src.ctypes.data,
+                                                   codes.ctypes.data, zmm.ctypes.data, sizes.ctypes.data, C.byref(m)))
+        k = m.value
+        return {"objects": objects[:k], "cluster": oc[:k], "source_index": src[:k], "codes": codes[:nc], "z_min_max": zmm[:nc], "sizes": sizes[:nc]}
 
     # ---- N4
     def nn1_desc(self, db, q):

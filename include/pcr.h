@@ -416,6 +416,83 @@ int pcr_voxel_grid_normals_f32(pcr_ctx* ctx, const pcr_cloud* cloud, const pcr_c
 int pcr_normal_space_sample_f32(pcr_ctx* ctx, const pcr_cloud* normals, const uint32_t bins[3], size_t sample, uint64_t seed, uint32_t* indices,
                                 size_t* n_out, const pcr_cloud* gather_cloud, pcr_cloud** out_cloud, pcr_cloud** out_normals);
 
+/* ---- HomeworkFinal: the sampling and grouping front of PointNet++ (HomeworkFinal/models/pointnet_util.py:66-156) and the object
+ * extraction loop of HomeworkFinal/foreground_obj_cls.py:143-180 ------------------------------------------------------------------------
+ * The three operators work on SEGMENTS of one cloud: seg_ptr[n_seg + 1] (host) holds ascending offsets into the cloud, segment s is
+ * the points [seg_ptr[s], seg_ptr[s + 1]).  A PointNet batch [B, N, 3] is seg_ptr[b] = b * N; the objects of a scan are the ragged case.
+ * Every index returned is SEGMENT-LOCAL (the reference's are batch-local).  All arithmetic below is unfused.
+ *
+ * pcr_fps_f32 — farthest point sampling, two arithmetic modes over the same f32 coordinates:
+ *   PCR_FPS_F32  pointnet_util.farthest_point_sample (:66-87, torch f32): s = ((dx*dx) + dy*dy) + dz*dz in f32, d = p - centre,
+ *                running distance starts at 1e10f;
+ *   PCR_FPS_F64  DataLoader.farthest_point_sample (HomeworkFinal/data_utils/DataLoader.py:17-38, numpy f64 on widened f32 points):
+ *                the same expression in f64 on the coordinates widened to f64, running distance starts at 1e10.
+ *   The two modes are two contracts: on real neighbourhoods they pick different sequences now and then.
+ *   Rule (both): pick[0] = start[s] (an input: the reference draws it unseeded); for k >= 1: every point's running distance becomes s
+ *   when s < distance (strict), then pick[k] = the point with the LARGEST running distance, ties to the LOWEST index (np.argmax /
+ *   torch.max return the first maximum).  npoint larger than the segment is legal and follows from the rule: once every distance is 0
+ *   the argmax is index 0.  A point with a non-finite coordinate is never picked by the rule: its running distance counts as -inf and is
+ *   never updated (so a NaN cannot be chosen forever); start[s] itself is returned as given.  When every running distance is -inf — a
+ *   segment with no finite point — every pick after the first is index 0.  A non-finite CENTRE updates nobody (s is NaN or +inf).
+ *   indices: n_seg x npoint (host); regime (optional, n_seg bytes): which kernel served the segment — 1 one wave (<= 256 points, no barrier
+ *   in the loop), 2 / 3 / 4 one workgroup holding 4 x 256 / 4 x 1024 / 16 x 1024 points in registers, 5 one launch per pick (any size).
+ *   Tune key fps_regime [0] r = no segment is served by a regime below r (results never depend on it).  Profile names fps_small, fps_large.
+ *   PCR_ERR_ARG: NULL ctx / cloud / seg_ptr, or start / indices with something to do; another mode; a seg_ptr that descends or ends
+ *   beyond the cloud; start[s] outside its segment (so: an EMPTY segment with npoint > 0); n_seg x npoint > 2^31 - 16.  n_seg == 0 or
+ *   npoint == 0: PCR_OK, nothing written.  PCR_ERR_STATE if a pick lies outside its segment (never in a correct run).
+ *
+ * pcr_ball_query_f32 — pointnet_util.query_ball_point (:90-116).  centres is a second segmented cloud (centre_seg_ptr, the same n_seg);
+ *   its points need not be members of the first.  For every centre q of segment s: the hits are the points j of segment s with
+ *   s(q, j) <= r2, s = ((dx*dx) + dy*dy) + dz*dz in f32 computed DIRECTLY from d = q - p (the reference expands -2 q.p + |q|^2 + |p|^2
+ *   through a matmul: the two forms can differ for a pair whose distance is within rounding of the radius), r2 = (float)(radius * radius)
+ *   with the product in f64 (what comparing an f32 tensor with the Python float radius ** 2 does).  A comparison with NaN is false: a
+ *   non-finite point is never a hit and a non-finite centre has none.  Row q = the first nsample hits in ascending index, the rest of
+ *   the row filled with the first hit; an EMPTY row is filled with the segment's size N, as the reference leaves it.  counts (optional)
+ *   = min(hits seen, nsample) per row — the walk stops at the chunk of 64 points that fills the row — 0 for an empty row.
+ *   idx: (number of centres) x nsample, rows in centre order starting at centre_seg_ptr[0].  PCR_ERR_ARG: NULL ctx / clouds / seg_ptrs / idx;
+ *   nsample == 0; a radius that is negative or non-finite; a seg_ptr that descends or ends beyond its cloud.  Profile name ball_query.
+ *
+ * pcr_group_points_f32 — the gather of pointnet_util.sample_and_group (:145-150) in one pass: new_xyz[q] = centre q (rows x 3) and
+ *   new_points[q][k] = (xyz[idx[q][k]] - centre q | features[idx[q][k]]), rows x nsample x (3 + D), one f32 subtraction per coordinate
+ *   (bit-exact against torch).  features: host, one row of D floats per point of the CLOUD (addressed by cloud position; only the rows of
+ *   the segments are read), NULL with D == 0.  idx: host, segment-local, rows x nsample.  PCR_ERR_ARG as above, and for an index outside
+ *   its segment — which is what an empty ball-query row holds: the reference's indexing raises there too.  Profile name group_points.
+ *
+ * pcr_objects_from_labels_f32 — the loop of foreground_obj_cls.py:143-180 in one call.  labels: n int32 (host), -1 = noise, else a cluster
+ *   id < n_clusters (pcr_dbscan_f32's output).  Members of a cluster are taken in ascending input index (cluster_indices_dict's order: a
+ *   STABLE sort by label).  Per cluster c: size, z_min, z_max (f32, exact) and the class code
+ *     3   when the cluster is empty, or (double)z_min - ground_z > z_min_above_ground (:162), or e = (double)z_max - (double)z_min has
+ *         e < z_extent[0] or e > z_extent[1] (:167) — the reference writes 3 there and goes on;
+ *     -1  "to be classified": the cluster gives one object row.
+ *   Object rows come in ascending cluster id (the reference walks its dict in order of first appearance and keys its result by cluster).
+ *   A row has npoints members (member = position inside the cluster):
+ *     size > npoints: PCR_FPS_F64 picks with pick[0] = starts[c] when starts != NULL and starts[c] != UINT32_MAX, else
+ *         K(seed, (c + 1) << 32) mod size;
+ *     size <= npoints: members 0 .. size - 1, then for t = 0 .. npoints - size - 1 member K(seed, (c + 1) << 32 | (t + 1)) mod size (a draw with
+ *         replacement, :177);
+ *     K(seed, a): z = seed ^ (0x9E3779B97F4A7C15 * (a + 1)); z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) * 0x94D049BB133111EB;
+ *         K = z ^ (z >> 31) (uint64 arithmetic modulo 2^64: the keying of pcr_normal_space_sample_f32).  A draw depends on (seed, c, t) only,
+ *         never on lanes or launch geometry.
+ *   Centroid (pc_normalize, :24-29): per coordinate the f64 sum of the npoints rows IN ROW ORDER starting from 0.0, divided by npoints;
+ *   objects[row][t] = (float)((double)p - centroid): rounded to f32 once, as `input[0, ...] = torch.from_numpy(obj_pts)` does (:183).
+ *   UNPINNED: the reference's draws (np.random.randint / np.random.choice, unseeded) — the stream here is the library's own; with
+ *   explicit starts the FPS rows are the reference's.
+ *   objects: room for n_clusters x npoints x 3 floats, object_cluster: n_clusters (the cluster of each row), source_index (optional): n_clusters x
+ *   npoints (the cloud index of every row member); the first *n_objects rows are written.  codes: n_clusters; z_min_max (optional): n_clusters x 2
+ *   ((+inf, -inf) for an empty cluster); sizes (optional): n_clusters.  PCR_ERR_ARG: NULL ctx / cloud / labels / z_extent / n_objects / objects /
+ *   object_cluster / codes; a label outside [-1, n_clusters); npoints outside [1, 4096]; a NaN gate; a start outside its cluster.
+ *   Profile names obj_sort, obj_zstats, obj_build (+ fps_*). */
+enum pcr_fps_mode { PCR_FPS_F32 = 0, PCR_FPS_F64 = 1 };
+int pcr_fps_f32(pcr_ctx* ctx, const pcr_cloud* cloud, const uint32_t* seg_ptr, size_t n_seg, size_t npoint, int mode, const uint32_t* start,
+                uint32_t* indices, uint8_t* regime);
+int pcr_ball_query_f32(pcr_ctx* ctx, const pcr_cloud* cloud, const uint32_t* seg_ptr, const pcr_cloud* centres, const uint32_t* centre_seg_ptr,
+                       size_t n_seg, double radius, size_t nsample, uint32_t* idx, uint32_t* counts);
+int pcr_group_points_f32(pcr_ctx* ctx, const pcr_cloud* cloud, const uint32_t* seg_ptr, const pcr_cloud* centres, const uint32_t* centre_seg_ptr,
+                         size_t n_seg, const float* features, size_t D, const uint32_t* idx, size_t nsample, float* new_xyz, float* new_points);
+int pcr_objects_from_labels_f32(pcr_ctx* ctx, const pcr_cloud* cloud, const int32_t* labels, size_t n_clusters, size_t npoints, double ground_z,
+                                double z_min_above_ground, const double z_extent[2], uint64_t seed, const uint32_t* starts, float* objects,
+                                uint32_t* object_cluster, uint32_t* source_index, int32_t* codes, float* z_min_max, uint32_t* sizes, size_t* n_objects);
+
 /* ---- next row N4: global-registration front half, Homework9/hw9/src/registration.cpp:288-434, :535-615 -----------
  * N4a: exhaustive 1-NN between two descriptor sets (row-major n x dim / m x dim f32, host memory; dim 33 = FPFH),
  * nanoflann's evalMetric arithmetic for any dim (nanoflann.hpp:382-405: groups of four + tail, f32, unfused), canonical
