@@ -132,20 +132,23 @@ def fpfh_numpy(surface, spfh, radius, keypoints=None):
     qi, j, s = qi[nz], j[nz], s[nz]
     with np.errstate(all="ignore"):
         w = F32(1.0) / s
-        val = spfh[j] * w[:, None]                          # f32
     starts = np.searchsorted(qi, np.arange(m))
-    ends = np.searchsorted(qi, np.arange(m), side="right")
+    lens = np.bincount(qi, minlength=m)
     acc = np.zeros((m, 33), np.float64)
     sums = np.zeros((m, 3), np.float64)
-    rank = np.arange(qi.size) - starts[qi]
-    for k in range(int(rank.max()) + 1 if rank.size else 0):
-        sel = rank == k
-        rows, v = qi[sel], val[sel].astype(np.float64)
+    # step k adds every row's k-th term (ascending s): only the rows that still have one are touched, longest rows first in
+    # `by_len`, so the whole loop costs one pass over the pairs however uneven the neighbourhoods are
+    by_len = np.argsort(-lens, kind="stable")
+    neg_len = -lens[by_len]
+    for k in range(int(lens.max()) if qi.size else 0):
+        rows = by_len[: np.searchsorted(neg_len, -k, side="left")]          # the rows with more than k terms
+        at = starts[rows] + k
+        with np.errstate(all="ignore"):
+            v = (spfh[j[at]] * w[at][:, None]).astype(np.float64)           # the product in f32
         acc[rows] += v
         for h in range(3):
             for b in range(11):
                 sums[rows, h] += v[:, h * 11 + b]
-    del ends
     out = np.empty((m, 33), F32)
     with np.errstate(all="ignore"):
         for h in range(3):
@@ -299,11 +302,12 @@ def check_spfh(gpu, want, fragile, what):
     return excused
 
 
-def check_fpfh(gpu, want, what):
+def check_fpfh(gpu, want, what, min_same=0.999):
+    """min_same: the share of rows that must be bit-identical (a sweep over clouds of a few points passes 0: one row is 20 % of five)"""
     d = ulp_diff(gpu, want)
     assert int(d.max(initial=0)) <= 1, (what, int(d.max()), np.argwhere(d > 1)[:5])
     same = float((d == 0).all(1).mean()) if d.size else 1.0
-    assert same >= 0.999, (what, same)
+    assert same >= min_same, (what, same)
     assert np.array_equal(np.isnan(gpu), np.isnan(want))
     return same
 

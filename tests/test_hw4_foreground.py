@@ -288,12 +288,14 @@ def run_sor(ctx, pts32, k, r):
         cloud.free()
 
 
-def assert_sor_equal(got, pts, want, what):
+def assert_sor_equal(got, pts, want, what, equal_nan=False):
+    """equal_nan: a NaN statistic (fewer than two valid points: 0 / 0) must be NaN on both sides instead of failing the comparison"""
     keep, avg, st, kept = got
     wk, wa, wst = want
     assert np.array_equal(avg.view(np.uint64), wa.view(np.uint64)), f"{what}: avg not bit-equal at {np.flatnonzero(avg != wa)[:5]}"
-    assert np.allclose(st, wst, rtol=1e-12, atol=0), (what, st, wst)
-    near = np.abs(avg - wst[2]) <= 1e-9 * abs(wst[2])
+    assert np.allclose(st, wst, rtol=1e-12, atol=0, equal_nan=equal_nan), (what, st, wst)
+    # (avg <= 0 is dropped whatever the threshold: it needs no allowance — and with thr == 0, every avg being 0, all of them would sit on it)
+    near = (avg > 0) & (np.abs(avg - wst[2]) <= 1e-9 * abs(wst[2]))
     assert near.sum() <= 4, what
     assert np.array_equal(keep[~near], wk[~near]), what
     assert np.array_equal(kept, pts[keep]), what
