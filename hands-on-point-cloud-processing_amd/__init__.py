@@ -20,6 +20,8 @@ INCLUDE_DIR = os.path.join(os.path.dirname(_HERE), "include")
 
 PCR_SOA, PCR_AOS3, PCR_AOS4, PCR_AOS6 = 0, 1, 2, 6
 PCR_FPS_F32, PCR_FPS_F64 = 0, 1
+PCR_KMEANS_PY, PCR_KMEANS_CPP = 0, 1
+PCR_EMPTY_CLUSTER = 1          # positive status of the K-Means calls: completed, a cluster has no member
 ERRORS = {0: "ok", -1: "bad argument", -2: "HIP error", -3: "out of memory", -4: "bad state",
           -5: "RCCL/collective error", -6: "no correspondence kept"}
 
@@ -70,6 +72,8 @@ ABI_SYMBOLS = [
     "pcr_db64_radius_rows", "pcr_rows_destroy", "pcr_rows_info", "pcr_rows_row_ptr", "pcr_rows_fetch", "pcr_rows_reduce", "pcr_rows_moments",
     "pcr_dbscan_f32", "pcr_statistical_outlier_f32", "pcr_fpfh33_f32", "pcr_harris3d_f32", "pcr_voxel_grid_normals_f32", "pcr_normal_space_sample_f32",
     "pcr_fps_f32", "pcr_ball_query_f32", "pcr_group_points_f32", "pcr_objects_from_labels_f32",
+    "pcr_mat64_create", "pcr_mat64_destroy", "pcr_mat64_info", "pcr_kmeans_step_f64", "pcr_kmeans_fit_f64", "pcr_kmeans_predict_f64", "pcr_kmeanspp_init_f64",
+    "pcr_gmm_em_step_f64", "pcr_gmm_fit_f64", "pcr_gmm_predict_f64",
 ]
 
 
@@ -169,6 +173,17 @@ def lib():
     L.pcr_ball_query_f32.argtypes = [vp, vp, vp, vp, vp, sz, C.c_double, sz, vp, vp]
     L.pcr_group_points_f32.argtypes = [vp, vp, vp, vp, vp, sz, vp, sz, vp, sz, vp, vp]
     L.pcr_objects_from_labels_f32.argtypes = [vp, vp, vp, sz, sz, C.c_double, C.c_double, vp, C.c_uint64, vp, vp, vp, vp, vp, vp, vp, C.POINTER(sz)]
+    ip = C.POINTER(C.c_int)
+    L.pcr_mat64_create.argtypes = [vp, vp, sz, C.c_int, C.POINTER(vp)]
+    L.pcr_mat64_destroy.argtypes = [vp, vp]
+    L.pcr_mat64_info.argtypes = [vp, C.POINTER(sz), ip, ip]
+    L.pcr_kmeans_step_f64.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp]
+    L.pcr_kmeans_fit_f64.argtypes = [vp, vp, C.c_int, vp, C.c_double, C.c_int, C.c_int, vp, vp, ip, ip]
+    L.pcr_kmeans_predict_f64.argtypes = [vp, vp, C.c_int, vp, vp]
+    L.pcr_kmeanspp_init_f64.argtypes = [vp, vp, C.c_int, C.c_double, vp, C.c_uint64, vp, vp]
+    L.pcr_gmm_em_step_f64.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp]
+    L.pcr_gmm_fit_f64.argtypes = [vp, vp, C.c_int, vp, C.c_double, C.c_double, C.c_int, C.c_uint64, vp, vp, vp, ip, ip, ip]
+    L.pcr_gmm_predict_f64.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp]
     L.pcr_nn1_desc_f32.argtypes = [vp, vp, sz, vp, sz, C.c_int, vp, vp]
     L.pcr_match_union_f32.argtypes = [vp, vp, sz, vp, sz, C.c_int, C.c_float, vp, vp, C.POINTER(sz)]
     L.pcr_match_inter_f32.argtypes = [vp, vp, sz, vp, sz, C.c_int, C.c_float, vp, vp, C.POINTER(sz)]
@@ -324,6 +339,118 @@ class Db64:
         self.h = None
 
 
+class Mat64:
+    """n x dim f64 rows resident in HBM (pcr_mat64): uploaded once, clustered many times — K-Means, its seeding and Gaussian-mixture EM
+    (Homework3; the contracts are in include/pcr.h).  The K-Means calls return their status (0, or PCR_EMPTY_CLUSTER) beside the results."""
+
+    def __init__(self, ctx: "Context", rows):
+        rows = np.ascontiguousarray(rows, np.float64)
+        if rows.ndim != 2:
+            raise PcrError("rows: an n x dim array")
+        h = C.c_void_p()
+        ctx._ck(lib().pcr_mat64_create(ctx.h, rows.ctypes.data, rows.shape[0], rows.shape[1], C.byref(h)))
+        self.ctx, self.h, self.n, self.dim = ctx, h, rows.shape[0], rows.shape[1]
+        ctx._handles.add(self)
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:   # noqa: BLE001
+            pass
+
+    def free(self):
+        if self.h and self.ctx.h:
+            lib().pcr_mat64_destroy(self.ctx.h, self.h)
+        self.h = None
+
+    def grid_exponent(self) -> int:
+        e = C.c_int()
+        self.ctx._ck(lib().pcr_mat64_info(self.h, None, None, C.byref(e)))
+        return e.value
+
+    def _ck_pos(self, rc: int) -> int:
+        if rc < 0:
+            self.ctx._ck(rc)
+        return rc
+
+    def _centres(self, c):
+        c = np.ascontiguousarray(c, np.float64)
+        if c.ndim != 2 or c.shape[1] != self.dim:
+            raise PcrError("centres: a k x dim array")
+        return c
+
+    def kmeans_step(self, centres):
+        """-> (labels int32 [n], counts int64 [k], new centres [k, dim], status)"""
+        c = self._centres(centres)
+        k = c.shape[0]
+        labels, counts, out = np.zeros(self.n, np.int32), np.zeros(k, np.int64), np.zeros((k, self.dim))
+        rc = self._ck_pos(lib().pcr_kmeans_step_f64(self.ctx.h, self.h, k, c.ctypes.data, labels.ctypes.data, counts.ctypes.data, out.ctypes.data))
+        return labels, counts, out, rc
+
+    def kmeans_fit(self, init_centres, tol: float = 1e-4, max_iter: int = 200, mode: int = PCR_KMEANS_PY, want_labels: bool = True):
+        """-> (centres, labels or None, iters, converged, status)"""
+        c = self._centres(init_centres)
+        k = c.shape[0]
+        out = np.zeros((k, self.dim))
+        labels = np.zeros(self.n, np.int32) if want_labels else None
+        it, cv = C.c_int(), C.c_int()
+        rc = self._ck_pos(lib().pcr_kmeans_fit_f64(self.ctx.h, self.h, k, c.ctypes.data, float(tol), int(max_iter), int(mode), out.ctypes.data,
+                                                   labels.ctypes.data if want_labels else None, C.byref(it), C.byref(cv)))
+        return out, labels, it.value, bool(cv.value), rc
+
+    def kmeans_predict(self, centres):
+        c = self._centres(centres)
+        labels = np.zeros(self.n, np.int32)
+        self.ctx._ck(lib().pcr_kmeans_predict_f64(self.ctx.h, self.h, c.shape[0], c.ctypes.data, labels.ctypes.data))
+        return labels
+
+    def kmeanspp_init(self, k: int, factor: float = 1.0, u=None, seed: int = 0, want_p: bool = False):
+        """-> picks int32 [k] (and the distribution of the last pick [n])"""
+        idx = np.zeros(int(k), np.int32)
+        p = np.zeros(self.n) if want_p else None
+        if u is not None:
+            u = np.ascontiguousarray(u, np.float64)
+            if u.shape != (int(k),):
+                raise PcrError("u: one uniform per pick")
+        self.ctx._ck(lib().pcr_kmeanspp_init_f64(self.ctx.h, self.h, int(k), float(factor), u.ctypes.data if u is not None else None, int(seed),
+                                                 idx.ctypes.data, p.ctypes.data if want_p else None))
+        return (idx, p) if want_p else idx
+
+    def _params(self, mean, cov, pi):
+        mean = self._centres(mean)
+        k = mean.shape[0]
+        cov = np.ascontiguousarray(cov, np.float64)
+        pi = np.ascontiguousarray(pi, np.float64)
+        if cov.shape != (k, self.dim, self.dim) or pi.shape != (k,):
+            raise PcrError("cov: k x dim x dim, pi: k")
+        return k, mean, cov, pi
+
+    def gmm_em_step(self, mean, cov, pi, want_post: bool = False):
+        """-> (mean_new, cov_new, pi_new[, post n x k])"""
+        k, mean, cov, pi = self._params(mean, cov, pi)
+        m2, c2, p2 = np.zeros_like(mean), np.zeros_like(cov), np.zeros_like(pi)
+        post = np.zeros((self.n, k)) if want_post else None
+        self.ctx._ck(lib().pcr_gmm_em_step_f64(self.ctx.h, self.h, k, mean.ctypes.data, cov.ctypes.data, pi.ctypes.data, m2.ctypes.data, c2.ctypes.data,
+                                               p2.ctypes.data, post.ctypes.data if want_post else None))
+        return (m2, c2, p2, post) if want_post else (m2, c2, p2)
+
+    def gmm_fit(self, init_mean, amplitude: float = 0.3, eps: float = 1e-4, max_iter: int = 100, seed: int = 0):
+        """-> (mean, cov, pi, {"iters", "converged", "resets"})"""
+        mean = self._centres(init_mean)
+        k = mean.shape[0]
+        m2, c2, p2 = np.zeros_like(mean), np.zeros((k, self.dim, self.dim)), np.zeros(k)
+        it, cv, rs = C.c_int(), C.c_int(), C.c_int()
+        self.ctx._ck(lib().pcr_gmm_fit_f64(self.ctx.h, self.h, k, mean.ctypes.data, float(amplitude), float(eps), int(max_iter), int(seed), m2.ctypes.data,
+                                           c2.ctypes.data, p2.ctypes.data, C.byref(it), C.byref(cv), C.byref(rs)))
+        return m2, c2, p2, {"iters": it.value, "converged": bool(cv.value), "resets": rs.value}
+
+    def gmm_predict(self, mean, cov, pi):
+        k, mean, cov, pi = self._params(mean, cov, pi)
+        labels = np.zeros(self.n, np.int32)
+        self.ctx._ck(lib().pcr_gmm_predict_f64(self.ctx.h, self.h, k, mean.ctypes.data, cov.ctypes.data, pi.ctypes.data, labels.ctypes.data))
+        return labels
+
+
 class Rows:
     """Device-resident CSR rows of a radius search (include/pcr.h pcr_rows): reduce them on the GPU or fetch them block by block."""
     COUNT, SUM_DIST, MAX_DIST = 0, 1, 2
@@ -418,6 +545,10 @@ class Context:
 
     def sync(self):
         self._ck(lib().pcr_ctx_sync(self.h))
+
+    def mat64(self, rows) -> Mat64:
+        """n x dim f64 rows (1 <= dim <= 8) resident in HBM for the Homework3 clustering calls"""
+        return Mat64(self, rows)
 
     def device_info(self):
         arch = C.create_string_buffer(64)

@@ -563,6 +563,67 @@ void pcr_shard_range(size_t n, int nranks, int rank, size_t* begin, size_t* end)
 int pcr_cloud_shard_spatial(pcr_ctx* ctx, const pcr_cloud* tgt, const pcr_cloud* full, int nranks, int rank, int chunks_per_rank, pcr_cloud** out);
 int pcr_cloud_global_index(pcr_ctx* ctx, const pcr_cloud* shard, uint32_t* index);   /* host, pcr_cloud_size(shard) entries, ascending */
 
+/* ---- Homework3: K-Means, its k-means++-style seeding and Gaussian-mixture EM (csrc/mixture.hip) ------------------------
+ * Data is row-major f64, n x dim, as the reference's arrays are; limits 1 <= dim <= 8, 1 <= k <= 64, k <= n < 2^31, every datum finite
+ * and the largest |x| within 2^-400 .. 2^400 (or 0).  Anything else is PCR_ERR_ARG.  pcr_mat64_create uploads the data ONCE; no call
+ * below moves an n-sized array across the bus inside its loop (labels, p_last and post are copied out once, at the end, when asked for).
+ *
+ * ORDER-FREE SUMS.  Every sum over points (cluster coordinate sums, the seeding's mean distance, N_k, sum gamma x, sum gamma (x - mu)(x - mu)^T)
+ * is taken on a fixed-point grid: with 2^e the smallest power of two above every |x| of the handle, a term is cut towards zero to a
+ * multiple of the unit — 2^(e - 96) for coordinates and gamma x, 2^-95 for gamma, 2^(e + 3 - 96) for distances, 2^(2e + 2 - 96) for the
+ * second moments —, the multiples are added as integers (three signed 32-bit limbs in 64-bit words) and the total is rounded to f64 once.
+ * The results are the same bits under any launch geometry: pcr_tune_set(ctx, "mixture_geometry", 1) selects another one (128-lane
+ * workgroups, at most 24 of them, one shared set of limb rows) for tests to show this; "mixture_batch" [8] = iterations per read-back.
+ *
+ * pcr_kmeans_step_f64: one iteration of KMeans.py:61-65.  Assignment: s = sum_d (x_d - c_d)^2 in f64, unfused, ascending d starting from
+ *   (x_0 - c_0)^2; argmin s, lowest centre index on ties (scipy's KDTree returns sqrt(s); which of two centres within a rounding of each
+ *   other it reports is UNPINNED).  centres_out[j] = (order-free sum of the members, rounded once) / count, so
+ *   |c - exact mean| <= 2^-52 max|x|.  An empty cluster has count 0 and a NaN centre (np.mean of an empty slice), and the call returns the
+ *   positive status PCR_EMPTY_CLUSTER.  labels (int32, n), counts (k), centres_out (k dim) may each be NULL.
+ * pcr_kmeans_fit_f64: the whole loop on the device; the host reads one 32-byte status record per batch of iterations.
+ *   PCR_KMEANS_PY  (KMeans.py:55-70): `while not converged and count <= max_iter`, i.e. up to max_iter + 1 passes; the SIGNED test
+ *                  all((new - old) < tol) as written.  PCR_KMEANS_CPP (spectralClustering.cpp:337-407, 413-427): the fabs test; converged
+ *                  when it holds and count < max_iter, else the loop ends unconverged once count > max_iter.
+ *   centres = the centres of the last pass (the reference's center_ on convergence), *iters = passes made, labels (may be NULL) = the
+ *   assignment under those centres (KMeans.predict).  Stops at, and returns, PCR_EMPTY_CLUSTER (the reference goes on with NaN centres).
+ * pcr_kmeans_predict_f64: the assignment alone (KMeans.py:73-83); any k <= 64.
+ * pcr_kmeanspp_init_f64: init_choice of hw3/sript/KMeans.py:16-41 (factor 1.0) and hw3/sript/GMM.py (factor 1.25).  idx[0] = floor(u_0 n);
+ *   for each further pick j: d_i = distance to the nearest chosen point (sqrt(s), a running minimum), mean_d = (order-free sum of d) / n,
+ *   w_i = 0 where d_i < factor mean_d, else exp(d_i); idx[j] = the first i with cumsum(w)_i / cumsum(w)_{n-1} > u_j, which is what
+ *   Generator.choice(n, 1, p = w / sum w) computes from one uniform (searchsorted(cdf, u, side = 'right')).  The reference draws unseeded:
+ *   the uniforms are the caller's (u, k entries in [0, 1)), or with u == NULL u_j = (K(seed, j) >> 11) 2^-53 under the SplitMix64 keying
+ *   of pcr_normal_space_sample_f32.  UNPINNED: numpy's stream, the order of the inclusive scan (a rocPRIM device scan) and so a pick
+ *   whose u lies within rounding of a cdf edge.  exp overflow (d > 709.78) and weights that sum to 0 are PCR_ERR_STATE (the reference
+ *   gets NaN probabilities and raises).  p_last (n, may be NULL, needs k >= 2): the distribution w / sum w of the last pick.
+ * pcr_gmm_em_step_f64: GMM.posterior + GMM.EM of nano_vs_my/sript/GMM.py:43-78.  gamma_nk proportional to pi_k N(x_n; mu_k, Sigma_k), evaluated
+ *   in the LOG domain: Sigma_k = L L^T (Cholesky), log p = log pi_k - (dim log 2 pi + log det Sigma_k) / 2 - |L^-1 (x - mu_k)|^2 / 2, and
+ *   a log-sum-exp over k.  N_k = sum gamma, pi = N_k / n, mu_new = sum gamma x / N_k, Sigma_new = sum (gamma (x - mu_new)) (x - mu_new)^T / N_k
+ *   around the NEW mean, from the stored gamma in a second pass.  A covariance that is not positive definite is PCR_ERR_STATE (scipy raises).
+ *   DIFFERS from the reference where its plain pdf underflows: a row whose every pi_k pdf is 0 is 0 / 0 = NaN there, and a well-defined
+ *   posterior here.  post (n x k, may be NULL) receives gamma.
+ * pcr_gmm_fit_f64: GMM.fit.  Initial Sigma = amplitude I, pi = 1 / k, mu = init_mean (hw3/sript/GMM.py: amplitude 0.3, eps 1e-4;
+ *   nano_vs_my/sript/GMM.py: 1 and 1e-3).  After each EM pass: a component with ||Sigma_k||_F < 0.01 gets Sigma_k = amplitude I and
+ *   mu_k = data[K(seed, count << 32 | k) mod n] (the reference draws unseeded; *resets counts how often this fired); the loop ends when
+ *   the max-abs differences of mean, covariance and pi are all < eps (*converged = 1) or when count == max_iter.  *iters = count.
+ * pcr_gmm_predict_f64: argmax_k of the log posterior, the first maximum wins (GMM.predict). */
+#define PCR_EMPTY_CLUSTER 1  /* positive: the call completed, a cluster has no member */
+#define PCR_KMEANS_PY 0
+#define PCR_KMEANS_CPP 1
+typedef struct pcr_mat64 pcr_mat64;
+int pcr_mat64_create(pcr_ctx* ctx, const double* rows, size_t n, int dim, pcr_mat64** out);
+int pcr_mat64_destroy(pcr_ctx* ctx, pcr_mat64* m);
+int pcr_mat64_info(const pcr_mat64* m, size_t* n, int* dim, int* grid_exponent);   /* grid_exponent = e above */
+int pcr_kmeans_step_f64(pcr_ctx* ctx, pcr_mat64* data, int k, const double* centres_in, int32_t* labels, int64_t* counts, double* centres_out);
+int pcr_kmeans_fit_f64(pcr_ctx* ctx, pcr_mat64* data, int k, const double* init_centres, double tol, int max_iter, int mode, double* centres,
+                       int32_t* labels, int* iters, int* converged);
+int pcr_kmeans_predict_f64(pcr_ctx* ctx, pcr_mat64* data, int k, const double* centres, int32_t* labels);
+int pcr_kmeanspp_init_f64(pcr_ctx* ctx, pcr_mat64* data, int k, double factor, const double* u, uint64_t seed, int32_t* idx_out, double* p_last);
+int pcr_gmm_em_step_f64(pcr_ctx* ctx, pcr_mat64* data, int k, const double* mean_in, const double* cov_in, const double* pi_in, double* mean_out,
+                        double* cov_out, double* pi_out, double* post);
+int pcr_gmm_fit_f64(pcr_ctx* ctx, pcr_mat64* data, int k, const double* init_mean, double amplitude, double eps, int max_iter, uint64_t seed,
+                    double* mean, double* cov, double* pi, int* iters, int* converged, int* resets);
+int pcr_gmm_predict_f64(pcr_ctx* ctx, pcr_mat64* data, int k, const double* mean, const double* cov, const double* pi, int32_t* labels);
+
 /* ---- profiling hooks for bench.py: HIP-event timing of the dominant kernel on the ctx stream ----------
  * Off by default (an event pair costs ~6 us of stream time on each side of the kernel it brackets):
  * pcr_tune_set(ctx, "prof", 1) times the correspondence kernels, 2 every kernel, 0 switches it off again. */

@@ -1,0 +1,186 @@
+"""Writes tests/golden/hw3_clustering_ref.npz: what the reference's own Homework3 classes return on its five data sets, and how far the
+numpy restatement of tests/test_hw3_clustering.py lies from them.  The fixture holds DATA only.
+
+Runs on a CPU (numpy + scipy):   python tests/golden/gen_golden_hw3.py <reference root>
+  <reference root>/Homework3/hw3/sript/KMeans.py            class K_Means lifted out alone (the file's __main__ part is not needed)
+  <reference root>/Homework3/hw3/sript/GMM.py               class GMM lifted out alone (the file imports pylab and selects a matplotlib style
+                                                            that no longer exists); its `posterior` cannot run (multivariate_normal.pdf without
+                                                            x) and is replaced by the one of
+  <reference root>/Homework3/nano_vs_my/sript/GMM.py        the working copy — the two copies differ in init_choice, eps / amplitude and that line
+  <reference root>/Homework3/hw3/data/{aniso,blobs,circle,moons,varied}.txt
+
+Only the reference's RNG draws are unseeded.  Here: initial indices are fixed (init_choice is overridden per run), and for the init_choice
+records numpy's Generator is replaced by an object that answers choice(n, 1, p = ...) from a given uniform the way Generator.choice does
+(cdf = cumsum(p); cdf /= cdf[-1]; searchsorted(cdf, u, side = 'right')) and keeps the p it was handed.  Per-iteration K-Means centres are
+what the class hands to spatial.KDTree at the top of every pass.
+"""
+import ast
+import importlib.util
+import os
+import sys
+import types
+
+import numpy as np
+import scipy
+import scipy.stats  # noqa: F401  (the lifted posterior uses scipy.stats.multivariate_normal)
+from scipy import spatial
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+SETS = {"aniso": 3, "blobs": 3, "circle": 2, "moons": 2, "varied": 3}
+
+
+def load_restatement():
+    spec = importlib.util.spec_from_file_location("t_hw3", os.path.join(os.path.dirname(HERE), "test_hw3_clustering.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def class_node(path, name):
+    return [n for n in ast.parse(open(path).read()).body if isinstance(n, ast.ClassDef) and n.name == name][0]
+
+
+class FakeRng:
+    def __init__(self, u):
+        self.u, self.j, self.p = list(u), 0, []
+
+    def choice(self, n, size=None, replace=True, p=None):
+        u = self.u[self.j]
+        self.j += 1
+        if p is None:
+            return np.array([min(int(np.floor(u * n)), n - 1)])
+        p = np.asarray(p, np.float64)
+        self.p.append(p.copy())
+        cdf = np.cumsum(p)
+        cdf /= cdf[-1]
+        return np.array([int(cdf.searchsorted(u, side="right"))])
+
+
+class KDTreeSpy:
+    log = None
+
+    def __init__(self, data, *a, **k):
+        if KDTreeSpy.log is not None:
+            KDTreeSpy.log.append(np.array(data, np.float64, copy=True))
+        self.t = spatial.KDTree(data, *a, **k)
+
+    def query(self, *a, **k):
+        return self.t.query(*a, **k)
+
+
+def lift(root):
+    fake_random = types.SimpleNamespace(default_rng=None)
+    np_proxy = types.SimpleNamespace(**{k: getattr(np, k) for k in dir(np) if not k.startswith("__")})
+    np_proxy.random = fake_random
+    sp_proxy = types.SimpleNamespace(KDTree=KDTreeSpy)
+    ns = {"np": np_proxy, "scipy": scipy, "spatial": sp_proxy, "print": lambda *a, **k: None}
+    km = class_node(os.path.join(root, "Homework3/hw3/sript/KMeans.py"), "K_Means")
+    gm = class_node(os.path.join(root, "Homework3/hw3/sript/GMM.py"), "GMM")
+    good = [n for n in class_node(os.path.join(root, "Homework3/nano_vs_my/sript/GMM.py"), "GMM").body
+            if isinstance(n, ast.FunctionDef) and n.name == "posterior"][0]
+    gm.body = [good if isinstance(n, ast.FunctionDef) and n.name == "posterior" else n for n in gm.body]
+    for node in (km, gm):
+        exec(compile(ast.Module([node], []), "<reference>", "exec"), ns)
+    return ns, fake_random
+
+
+def main(root):
+    T = load_restatement()
+    ns, fake_random = lift(root)
+    out = {}
+    for name, k in SETS.items():
+        x = np.loadtxt(os.path.join(root, f"Homework3/hw3/data/{name}.txt"), delimiter=",")
+        assert x.shape == (1500, 2)
+        out[f"data_{name}"] = x
+        n = x.shape[0]
+        # ---- K-Means: three fixed initialisations
+        for t, base in enumerate((0, 7, 450)):
+            while True:
+                init = [(base + 100 * i * (3 if k == 2 else 2)) % n for i in range(k)]
+                ref = ns["K_Means"](n_clusters=k)
+                ref.init_choice = lambda data, init=init: list(init)
+                KDTreeSpy.log = []
+                ref.fit(x)
+                hist = list(KDTreeSpy.log)
+                KDTreeSpy.log = None
+                conv = ref.center_ is not None
+                hist.append(np.array(ref.center_) if conv else hist[-1])
+                labels = ref.predict(x)
+                rh, rc, rv = T.rs_kmeans_fit(x, x[init], 1e-4, 200)
+                mine, s = T.rs_assign(x, rh[-1])
+                bad = mine != labels
+                if conv and rc == len(hist) - 1 and rv == conv and not (bad & ~T.rs_near_tie(s)).any() and bad.mean() <= 0.005:
+                    break
+                base += 1
+            out[f"km_{name}_{t}_init"] = np.array(init, np.int32)
+            out[f"km_{name}_{t}_centres"] = np.array(hist)
+            out[f"km_{name}_{t}_passes"] = np.int32(len(hist) - 1)
+            out[f"km_{name}_{t}_converged"] = np.int32(conv)
+            out[f"km_{name}_{t}_labels"] = labels.astype(np.uint8)
+            print(name, "kmeans", t, init, "passes", len(hist) - 1)
+        # ---- init_choice: picks and the last distribution from given uniforms
+        for tag, cls, args in (("km", "K_Means", dict(n_clusters=k + 1)), ("gmm", "GMM", dict(n_clusters=k + 1))):
+            u = np.array([0.137, 0.529, 0.861, 0.303][: k + 1]) + 0.011 * list(SETS).index(name)
+            while True:
+                rng = FakeRng(u)
+                fake_random.default_rng = lambda rng=rng: rng
+                picks = ns[cls](**args).init_choice(x)
+                cdf = np.cumsum(rng.p[-1])
+                if np.min(np.abs(cdf / cdf[-1] - u[-1])) > 1e-9:
+                    break
+                u = u + 1e-3
+            rp, rpl = T.rs_seed(x, k + 1, 1.0 if tag == "km" else 1.25, u)
+            assert np.array_equal(rp, picks), (name, tag, rp, picks)
+            out[f"seed_{tag}_{name}_u"] = u
+            out[f"seed_{tag}_{name}_picks"] = np.array(picks, np.int32)
+            out[f"seed_{tag}_{name}_p"] = rng.p[-1]
+            print(name, "seeding", tag, picks)
+        # ---- GMM: EM steps with the reference's own parameters, and the full fit
+        base = 0
+        while True:
+            init = [(base + 100 * i * (3 if k == 2 else 2)) % n for i in range(k)]
+            ref = ns["GMM"](n_clusters=k, max_iter=100)
+            ref.init_choice = lambda data, init=init: list(init)
+            drew = []
+            fake_random.default_rng = lambda: types.SimpleNamespace(choice=lambda *a, **kw: drew.append(1) or np.array([0]))
+            log = []
+            em = ref.EM
+
+            def spy(data, m, c, p, em=em, log=log):
+                res = em(data, m, c, p)
+                log.append((np.array(m), np.array(c), np.array(p), res[0].copy(), res[1].copy(), res[2].copy()))
+                return res
+            ref.EM = spy
+            ref.fit(x)
+            mean, cov, pi, count, margins = T.rs_gmm_fit(x, x[init], 0.3, 1e-4, 100)
+            last = np.max(margins[-2:], axis=1) if len(margins) > 1 else np.array([0.0, 0.0])
+            labels = ref.predict(x)
+            lp = np.sort(T.rs_logpost(x, mean, cov, pi), axis=1)
+            bad = T.rs_logpost(x, mean, cov, pi).argmax(axis=1) != labels
+            ok = (not drew and count == len(log) and count < 100 and np.all(np.abs(last / 1e-4 - 1.0) > 0.01)
+                  and not (bad & ~((lp[:, -1] - lp[:, -2]) <= 1e-9)).any() and bad.mean() <= 0.005)
+            if ok:
+                break
+            base += 13
+        rec = sorted({0, len(log) // 2, len(log) - 1})
+        step_err = np.zeros(3)
+        for r in rec:
+            got = T.rs_em_step(x, log[r][0], log[r][1], log[r][2])
+            step_err = np.maximum(step_err, [np.max(np.abs(got[q] - log[r][3 + q])) for q in range(3)])
+        for q, key in enumerate(("mean", "cov", "pi")):
+            out[f"em_{name}_in_{key}"] = np.array([log[r][q] for r in rec])
+            out[f"em_{name}_out_{key}"] = np.array([log[r][3 + q] for r in rec])
+            out[f"gmm_{name}_{key}"] = np.array(ref.model_params[q])
+        out[f"em_{name}_step_err"] = step_err
+        out[f"gmm_{name}_fit_err"] = np.array([np.max(np.abs(a - np.array(b))) for a, b in zip((mean, cov, pi), ref.model_params)])
+        out[f"gmm_{name}_init"] = np.array(init, np.int32)
+        out[f"gmm_{name}_iters"] = np.int32(len(log))
+        out[f"gmm_{name}_labels"] = labels.astype(np.uint8)
+        print(name, "gmm", init, "iterations", len(log), "em_step_err", step_err, "fit_err", out[f"gmm_{name}_fit_err"])
+    path = os.path.join(HERE, "hw3_clustering_ref.npz")
+    np.savez_compressed(path, **out)
+    print(path, os.path.getsize(path), "bytes")
+
+
+if __name__ == "__main__":
+    main(sys.argv[1])
