@@ -151,7 +151,13 @@ static int icp_pipelined(pcr_ctx* ctx, const pcr_cloud* src, const pcr_cloud* tg
 
     constexpr int RING = 4;
     if (!ctx->icp_state_dev) {
-        PCR_HIP(ctx, hipMalloc((void**)&ctx->icp_state_dev, 2 * sizeof(IcpState)));      // [1]: the other buffer of the fused solve + move
+        // [1]: the other buffer of the fused solve + move; behind the two states, on a line of its own, the counter of the grid barrier of
+        // the fused sums + move launch (kabsch.hip).  Zeroed ONCE: the counter only ever grows, and [1].barrier_timeout must not start as garbage
+        static_assert(2 * sizeof(IcpState) <= 512, "the barrier counter lies 512 bytes behind the states");
+        PCR_HIP(ctx, hipMalloc((void**)&ctx->icp_state_dev, 512 + 128));
+        PCR_HIP(ctx, hipMemsetAsync(ctx->icp_state_dev, 0, 512 + 128, ctx->stream));
+        ctx->icp_barrier_dev = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(ctx->icp_state_dev) + 512);
+        ctx->icp_barrier_arrived = 0;
         PCR_HIP(ctx, hipHostMalloc((void**)&ctx->icp_state_host, (RING + 1) * sizeof(IcpState), hipHostMallocDefault));
         for (int k = 0; k < RING; k++) PCR_HIP(ctx, hipEventCreateWithFlags(&ctx->icp_events[k], hipEventDisableTiming));
     }
@@ -193,12 +199,19 @@ static int icp_pipelined(pcr_ctx* ctx, const pcr_cloud* src, const pcr_cloud* tg
     const bool fused = nranks == 1 && !force_slots && work->n > 0 && work->n <= (size_t)fused_max && tune_get(ctx, "icp_fused_move", 1) == 1;
     // exhaustive searches of a loop seed themselves from the previous correspondences: the move writes those seeds (tune icp_seed_in_move: 2 = off)
     const pcr_cloud* seed_tgt = (!icp_uses_grid(ctx, tgt) && tune_get(ctx, "icp_seed_in_move", 1) == 1 && tune_get(ctx, "nn1_warm_start", 1) == 1) ? tgt : nullptr;
+    // the sums as well in that launch (kabsch.hip icp_sums_update_move_kernel; tune icp_fused_sums: 2 = off): search -> sums + solve + move
+    // + seed, two launches, where the cloud has at least icp_fused_sums_min points and takes at most one workgroup per CU (icp_fused_sums_max_blocks);
+    // otherwise the three-launch chain.  Exhaustive loops only by default: the kernel serves the grid loop too (targets by index; icp_fused_sums_grid = 1,
+    // same bits), but that was measured only at hw9's 4 000 points, where it loses
+    const bool fused_sums = fused && (!icp_uses_grid(ctx, tgt) || tune_get(ctx, "icp_fused_sums_grid", 0) == 1) && icp_fused_sums_blocks(ctx, work->n) != 0;
     // (Measured and dropped, round 4: the Kabsch sums taken by the search kernel itself — STRACK3 ends with every query's final key in one wave, so each
     // wave added its 32 pairs' limbs (wave sums, a row per workgroup, f64 atomics into 64 rows; same bits) and the streaming pass + its launch gap
     // (7 + 4.5 us) went away: the search grew from 0.034 to 0.049 ms — 41 limbs x 6 f64 shuffle-adds per wave, four waves per SIMD ending together on
     // the LDS crossbar and the half-rate f64 pipe — and an iteration from 0.0707 to 0.0755 ms.  A second form without any cross-lane traffic (lane l takes
     // moment l of the wave's 32 pairs from LDS) still cost the search 7.5 us — the block waits for its slowest wave, every wave ends 2 us later — for 0-1.3 us
-    // per iteration.  Also measured: the 3 x 3 solve is 4.6 of the 17.5 us of the solve + move.)
+    // per iteration.  Also measured: the 3 x 3 solve is 4.6 of the 17.5 us of the solve + move.
+    // Measured now (profiles/icp_fused_sums.txt): the sums in the solve + move launch instead, behind one grid barrier — 7.8 + 17.3 us of kernels become 23.1 us,
+    // the search keeps its 26.2 us, and a step of the bench line goes from 63.6 to 61.8 us.)
     uint64_t enq = 0, chunks = 0;
     bool stopped = false;
     while (rc == PCR_OK && !stopped && enq < prm->max_iter) {
@@ -206,6 +219,10 @@ static int icp_pipelined(pcr_ctx* ctx, const pcr_cloud* src, const pcr_cloud* tg
             IcpState* cur = fused ? dev + (enq & 1) : dev;                                        // the state this iteration starts from
             ctx->stop_flag_dev = &cur->stop;     // correspondence kernels no-op once stop or stop_after_transform is set
             if ((rc = launch_nn1(ctx, tgt, work, true, gate))) break;                             // :925-934
+            if (fused_sums) {
+                if ((rc = launch_icp_sums_update_move(ctx, tgt, work, prm->max_corr, cur, dev + ((enq + 1) & 1), plan, seed_tgt))) break;   // :936-1003
+                continue;
+            }
             uint32_t blocks = 0;
             if (work->n && (rc = launch_kabsch_partial(ctx, tgt, work, prm->max_corr, plan, &blocks))) break;   // :936-940,:964-985
             if (fused) {
@@ -233,7 +250,7 @@ static int icp_pipelined(pcr_ctx* ctx, const pcr_cloud* src, const pcr_cloud* tg
             const int old = (int)((chunks - 2) % RING);
             e = hipEventSynchronize(ctx->icp_events[old]);
             if (e != hipSuccess) { rc = fail(ctx, PCR_ERR_HIP, "icp snapshot wait", e); break; }
-            if (host[old].stop || host[old].stop_after_transform) stopped = true;
+            if (host[old].stop || host[old].stop_after_transform || host[old].barrier_timeout) stopped = true;
         }
     }
     ctx->stop_flag_dev = nullptr;
@@ -248,6 +265,11 @@ static int icp_pipelined(pcr_ctx* ctx, const pcr_cloud* src, const pcr_cloud* tg
     if (rc) return rc;
     const IcpState& f = host[RING];
     if (f.overflow) return fail(ctx, PCR_ERR_STATE, "ICP: a kept source point lies more than 2^20 target extents away from the target");
+    if (f.barrier_timeout) {
+        // (the flag must not outlive the call in the state buffer the next call does not upload)
+        hipMemsetAsync(dev, 0, 2 * sizeof(IcpState), ctx->stream);
+        return fail(ctx, PCR_ERR_STATE, "ICP: the workgroups of the fused sums + move launch did not meet at their grid barrier in time (tune icp_fused_sums = 2 runs the three-launch chain)");
+    }
     memcpy(out_T, f.T_total, sizeof f.T_total);                                  // :1008-1009
     st.iters_run = f.iters_run;
     st.converged = f.converged;

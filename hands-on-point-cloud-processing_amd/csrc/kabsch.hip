@@ -11,7 +11,9 @@
 #include "grid_common.hpp"
 #include "numerics.hpp"
 
+#include <algorithm>
 #include <cmath>
+#include <cstddef>
 
 #pragma clang fp contract(off)
 
@@ -112,12 +114,13 @@ constexpr int KB_NLC = 40;            // the limbs that are not carry slots (12 
 // carries: false when the carry slots of tn[] are known to be zero (no per-thread normalisation): they are not exchanged at all
 // BFLY: the halving butterfly over the 40 live limbs (needs carries == false); it keeps all of them in registers at once (~160
 // VGPRs), so only the instance for few terms per thread — where the reduction IS the pass — is built with it
-template <bool BFLY>
+// WAVES: the wavefronts of the workgroup (the sums are exact integers: any grouping gives the same row)
+template <bool BFLY, int WAVES = KB_BLOCK / 64>
 __device__ __forceinline__ void block_reduce_limbs(double (&tn)[KB_NL], unsigned long long lastkey, int overflow,
-                                                   double (&red)[KB_BLOCK / 64][KB_NL], double (&row)[KB_ROW], bool carries)
+                                                   double (&red)[WAVES][KB_NL], double (&row)[KB_ROW], bool carries)
 {
-    __shared__ unsigned long long red_key[KB_BLOCK / 64];
-    __shared__ int red_ovf[KB_BLOCK / 64];
+    __shared__ unsigned long long red_key[WAVES];
+    __shared__ int red_ovf[WAVES];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     if (!BFLY) {
 #pragma unroll
@@ -145,12 +148,16 @@ __device__ __forceinline__ void block_reduce_limbs(double (&tn)[KB_NL], unsigned
     __syncthreads();
     if (threadIdx.x < KB_NL) {
         const int k = threadIdx.x;
-        row[k] = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
+        double t = red[0][k];
+#pragma unroll
+        for (int w = 1; w < WAVES; w++) t += red[w][k];
+        row[k] = t;
     } else if (threadIdx.x == KB_NL) {
         unsigned long long m = red_key[0];
-        for (int w = 1; w < KB_BLOCK / 64; w++) m = red_key[w] > m ? red_key[w] : m;
+        int ov = red_ovf[0];
+        for (int w = 1; w < WAVES; w++) { m = red_key[w] > m ? red_key[w] : m; ov |= red_ovf[w]; }
         row[55] = __longlong_as_double((long long)m);
-        row[56] = (red_ovf[0] | red_ovf[1] | red_ovf[2] | red_ovf[3]) ? 1.0 : 0.0;
+        row[56] = ov ? 1.0 : 0.0;
         row[57] = 0.0;
     }
     __syncthreads();
@@ -257,7 +264,9 @@ __global__ __launch_bounds__(KB_BLOCK) void kabsch_partial_kernel(
 constexpr int KF_BLOCK = 1024;
 constexpr int KF_GROUPS = KF_BLOCK / 64;
 
-__device__ __forceinline__ void reduce_rows(const double* __restrict__ partials, uint32_t n_blocks, double (&red)[KF_GROUPS][64], double (&row)[KB_ROW])
+// (GROUPS: the wavefronts of the calling workgroup, 16 for the KF_BLOCK kernels)
+template <int GROUPS = KF_GROUPS>
+__device__ __forceinline__ void reduce_rows(const double* __restrict__ partials, uint32_t n_blocks, double (&red)[GROUPS][64], double (&row)[KB_ROW])
 {
     const int k = threadIdx.x & 63, grp = threadIdx.x >> 6;
     double acc = 0.0;
@@ -266,7 +275,7 @@ __device__ __forceinline__ void reduce_rows(const double* __restrict__ partials,
         // more rows than groups: eight rows of a group in flight at once (a row that does not exist reads as 0.0, neutral for the sum,
         // the key maximum and the flag alike) — one memory round trip per eight rows instead of one per row; the additions are exact,
         // any order.  Few rows (small clouds, where this kernel is pure latency): the one-row loop, a fraction of the code to fetch.
-        if (n_blocks <= (uint32_t)KF_GROUPS) {
+        if (n_blocks <= (uint32_t)GROUPS) {
             if ((uint32_t)grp < n_blocks) {
                 const double v = partials[(size_t)grp * KB_ROW + k];
                 if (k == 55) key = (unsigned long long)__double_as_longlong(v);
@@ -275,11 +284,11 @@ __device__ __forceinline__ void reduce_rows(const double* __restrict__ partials,
             }
         } else {
             constexpr int INF = 8;
-            for (uint32_t b = grp; b < n_blocks; b += KF_GROUPS * INF) {
+            for (uint32_t b = grp; b < n_blocks; b += GROUPS * INF) {
                 double v[INF];
 #pragma unroll
                 for (int j = 0; j < INF; j++) {
-                    const uint32_t bb = b + (uint32_t)j * KF_GROUPS;
+                    const uint32_t bb = b + (uint32_t)j * GROUPS;
                     v[j] = bb < n_blocks ? partials[(size_t)bb * KB_ROW + k] : 0.0;
                 }
 #pragma unroll
@@ -297,11 +306,11 @@ __device__ __forceinline__ void reduce_rows(const double* __restrict__ partials,
         const int c = threadIdx.x;
         if (c == 55) {
             unsigned long long m = 0;
-            for (int g = 0; g < KF_GROUPS; g++) { const unsigned long long lk = (unsigned long long)__double_as_longlong(red[g][c]); m = lk > m ? lk : m; }
+            for (int g = 0; g < GROUPS; g++) { const unsigned long long lk = (unsigned long long)__double_as_longlong(red[g][c]); m = lk > m ? lk : m; }
             row[c] = __longlong_as_double((long long)m);
         } else {
             double t = 0.0;
-            for (int g = 0; g < KF_GROUPS; g++) t += red[g][c];
+            for (int g = 0; g < GROUPS; g++) t += red[g][c];
             row[c] = c == 56 ? (t != 0.0 ? 1.0 : 0.0) : t;
         }
     }
@@ -597,6 +606,205 @@ __global__ __launch_bounds__(KF_BLOCK) void icp_update_move_kernel(const double*
     }
 }
 
+// Exhaustive and grid loops on one rank whose cloud fits one workgroup per CU: the SUMS as well — kabsch_partial_kernel<., true> + icp_update_move_kernel as
+// ONE launch.  Both passes read the same three things per pair (key, source point, gathered target point); here a thread reads its four
+// consecutive pairs once, adds their limbs exactly as the sums pass does, the workgroup writes its row, and all workgroups meet ONCE at a grid barrier —
+// one monotonic counter, never reset: the host passes the value it has when everybody has arrived (the release / acquire hand-off: rows, the storing
+// wave's vmcnt(0), an agent-scope release by the arriving lane, the add; waiters poll relaxed with s_sleep; one agent-scope acquire before the rows are
+// read).  Behind it every workgroup reduces the gridDim.x rows, solves and moves its points from registers, as icp_update_move_kernel does.  The sums are
+// exact integers, so the new grouping of the pairs changes no bit (6b).
+// All workgroups are resident from the grid size alone: the host launches at most one per CU (icp_fused_sums_blocks).  EVERY workgroup arrives exactly once
+// per launch, in every phase (a stopped loop's launches too: that keeps the counter in step with the host's count); only phase 2 waits.
+// The spin is bounded: FS_SPIN_TICKS of s_memrealtime (100 MHz) = 50 ms.  A legitimate wait is the skew between the workgroups of one launch — all of them
+// are dispatched within a microsecond and do a few microseconds of identical work — so three to four orders of magnitude lie between it and the bound, which
+// also covers a chip that other processes keep busy for whole milliseconds; 50 ms per launch still ends a loop that can never meet within seconds.  On
+// expiry the workgroup raises barrier_timeout in the state it hands on (the host turns it into PCR_ERR_STATE), stops the loop and does not move.
+constexpr int FS_TMO_WORD = (int)(offsetof(IcpState, barrier_timeout) / 4);
+constexpr unsigned long long FS_SPIN_TICKS = 5000000ull;
+static_assert(KB_ROW <= 64, "one wave stores the workgroup's row and arrives for it");
+
+template <int T>
+__global__ __launch_bounds__(T) void icp_sums_update_move_kernel(
+    const float* __restrict__ tx, const float* __restrict__ ty, const float* __restrict__ tz, const uint32_t* __restrict__ orig,
+    unsigned long long* __restrict__ keys, uint32_t nt, float max_corr, KabschPlan plan, double* partials, unsigned long long* counter,
+    unsigned long long target, const IcpState* __restrict__ st_in, IcpState* __restrict__ st_out, double* __restrict__ out, float* __restrict__ x,
+    float* __restrict__ y, float* __restrict__ z, uint32_t n, uint32_t n4, int seed
+#ifdef PCR_FS_PROF
+    , unsigned long long* prof
+#endif
+    )
+{
+    constexpr int WAVES = T / 64;
+    __shared__ double red_l[WAVES][KB_NL];
+    __shared__ double red[WAVES][64];
+    __shared__ double row[KB_ROW];
+    __shared__ double o18[19];
+    __shared__ IcpState s_st;
+    __shared__ int s_tmo;
+#ifdef PCR_FS_PROF
+    const unsigned long long pt_a = __builtin_amdgcn_s_memrealtime();
+    unsigned long long pt_b = pt_a;
+#endif
+    const uint32_t i = blockIdx.x * T + threadIdx.x;
+    const bool mine = i < n4;
+    const uint32_t base = 4 * i;
+    // everything that depends on nothing else is requested in one go, the state first: it is on the critical path and loads retire in order
+    uint32_t stw = 0;
+    if (threadIdx.x < ST_WORDS) stw = reinterpret_cast<const uint32_t*>(st_in)[threadIdx.x];
+    float4 px = make_float4(0.f, 0.f, 0.f, 0.f), py = px, pz = px;
+    unsigned long long sk[4] = { ~0ull, ~0ull, ~0ull, ~0ull };             // (no pair: NaN distance, no target)
+    uint32_t og[4] = { base, base + 1, base + 2, base + 3 };
+    if (mine) {
+        px = reinterpret_cast<float4*>(x)[i]; py = reinterpret_cast<float4*>(y)[i]; pz = reinterpret_cast<float4*>(z)[i];
+        if (base + 3 < n) {
+            const ulonglong2 k01 = reinterpret_cast<const ulonglong2*>(keys)[2 * i], k23 = reinterpret_cast<const ulonglong2*>(keys)[2 * i + 1];
+            sk[0] = k01.x; sk[1] = k01.y; sk[2] = k23.x; sk[3] = k23.y;
+            if (orig) { const uint4 o = reinterpret_cast<const uint4*>(orig)[i]; og[0] = o.x; og[1] = o.y; og[2] = o.z; og[3] = o.w; }
+        } else {
+#pragma unroll
+            for (int u = 0; u < 4; u++)
+                if (base + u < n) { sk[u] = keys[base + u]; if (orig) og[u] = orig[base + u]; }
+        }
+    }
+    // the target points of the four pairs, gathered ONCE: they serve the sums and the seeds of the next search
+    float sq[4][3] = { { 0.f, 0.f, 0.f }, { 0.f, 0.f, 0.f }, { 0.f, 0.f, 0.f }, { 0.f, 0.f, 0.f } };
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+        const uint32_t j = (uint32_t)(sk[u] & 0xFFFFFFFFull);
+        if (j < nt) { sq[u][0] = tx[j]; sq[u][1] = ty[j]; sq[u][2] = tz[j]; }
+    }
+    if (threadIdx.x < ST_WORDS) reinterpret_cast<uint32_t*>(&s_st)[threadIdx.x] = stw;
+    __syncthreads();
+    // uniform over the GRID: every workgroup reads the same st_in (a raised barrier_timeout ends the loop like a stop)
+    const int phase = (s_st.stop || s_st.barrier_timeout) ? 0 : (s_st.stop_after_transform ? 1 : 2);
+    if (phase == 2) {
+        double c0[6], c1[6], p0[9], p1[9], p2[9], cnt = 0.0;
+#pragma unroll
+        for (int k = 0; k < 6; k++) { c0[k] = 0.0; c1[k] = 0.0; }
+#pragma unroll
+        for (int k = 0; k < 9; k++) { p0[k] = 0.0; p1[k] = 0.0; p2[k] = 0.0; }
+        unsigned long long lastkey = 0;
+        int overflow = 0;
+        const float sx4[4] = { px.x, px.y, px.z, px.w }, sy4[4] = { py.x, py.y, py.z, py.w }, sz4[4] = { pz.x, pz.y, pz.z, pz.w };
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            const uint32_t d2b = (uint32_t)(sk[u] >> 32);
+            const float d2 = __uint_as_float(d2b);
+            const uint32_t j = (uint32_t)(sk[u] & 0xFFFFFFFFull);
+            if (d2 < max_corr && j < nt) {                       // registration.cpp:936 (kabsch_partial_kernel's gate, term for term)
+                const float pf0 = sx4[u], pf1 = sy4[u], pf2 = sz4[u];
+                if (!(fabsf(pf0) < plan.lim && fabsf(pf1) < plan.lim && fabsf(pf2) < plan.lim)) { overflow = 1; continue; }
+                const double P[3] = { pf0, pf1, pf2 }, Q[3] = { sq[u][0], sq[u][1], sq[u][2] };
+#pragma unroll
+                for (int c = 0; c < 3; c++) { acc2(P[c], plan.sc, c0[c], c1[c]); acc2(Q[c], plan.sc, c0[3 + c], c1[3 + c]); }
+#pragma unroll
+                for (int r = 0; r < 3; r++)
+#pragma unroll
+                    for (int c = 0; c < 3; c++) acc3(Q[r] * P[c], plan.sp, p0[3 * r + c], p1[3 * r + c], p2[3 * r + c]);
+                cnt += 1.0;
+                const unsigned long long lk = ((unsigned long long)og[u] << 32) | d2b;
+                lastkey = lk > lastkey ? lk : lastkey;
+            }
+        }
+        double tn[KB_NL];                    // at most 4 terms per thread: no per-thread carries
+#pragma unroll
+        for (int c = 0; c < 6; c++) { tn[3 * c] = c0[c]; tn[3 * c + 1] = c1[c]; tn[3 * c + 2] = 0.0; }
+#pragma unroll
+        for (int k = 0; k < 9; k++) { tn[18 + 4 * k] = p0[k]; tn[19 + 4 * k] = p1[k]; tn[20 + 4 * k] = p2[k]; tn[21 + 4 * k] = 0.0; }
+        tn[54] = cnt;
+        block_reduce_limbs<true>(tn, lastkey, overflow, red_l, row, false);
+#ifdef PCR_FS_PROF
+        pt_b = __builtin_amdgcn_s_memrealtime();
+#endif
+        if (threadIdx.x < KB_ROW) partials[(size_t)blockIdx.x * KB_ROW + threadIdx.x] = row[threadIdx.x];
+    }
+    // ---- the barrier: wave 0 stored the row; it drains its stores, its lane 0 releases, arrives and (phase 2) waits
+    if (threadIdx.x < 64) {
+        if (phase == 2) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (threadIdx.x == 0) {
+            int tmo = 0;
+            if (phase == 2) {
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // (kept behind the fence whatever the compiler thinks of the scoreboard)
+            }
+            __hip_atomic_fetch_add(counter, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (phase == 2) {
+                const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
+                while (__hip_atomic_load(counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
+                    __builtin_amdgcn_s_sleep(2);
+                    if (__builtin_amdgcn_s_memrealtime() - t0 > FS_SPIN_TICKS) { tmo = 1; break; }
+                }
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the invalidate is over before the barrier below lets the other waves read
+#ifdef PCR_FS_PROF
+                if (prof) {
+                    const unsigned long long pt_c = __builtin_amdgcn_s_memrealtime();
+                    atomicAdd(prof + 12, pt_c - pt_b); atomicMax(prof + 13, pt_c - pt_b); atomicAdd(prof + 14, 1ull); atomicAdd(prof + 15, pt_b - pt_a);
+                }
+#endif
+            }
+            s_tmo = tmo;
+        }
+    }
+    __syncthreads();
+    const bool tmo = s_tmo != 0;
+    if (phase == 2 && !tmo) {
+        reduce_rows(partials, gridDim.x, red, row);
+        row_to_out18(row, plan.e, o18);
+        __syncthreads();
+        if (blockIdx.x == 0 && threadIdx.x < 19) out[threadIdx.x] = o18[threadIdx.x];
+        if (threadIdx.x == 0) icp_state_step(&s_st, o18, o18[16] >= 0.0, (float)o18[17], o18[18] != 0.0);
+    } else if (threadIdx.x == 0) {
+        s_st.stop = 1;                         // (phase 0: stays stopped; phase 1: max_iter reached, the loop is over; timeout)
+        if (tmo) {
+            s_st.barrier_timeout = 1;
+            // workgroup 0 may not have timed out (it writes every word but this one then): the flag goes out from whoever did
+            __hip_atomic_store(&st_out->barrier_timeout, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+    __syncthreads();
+    if (blockIdx.x == 0 && threadIdx.x < ST_WORDS && (threadIdx.x != FS_TMO_WORD || s_st.barrier_timeout))
+        reinterpret_cast<uint32_t*>(st_out)[threadIdx.x] = reinterpret_cast<const uint32_t*>(&s_st)[threadIdx.x];
+    if (s_st.stop || !mine) return;
+    const float r0 = s_st.Rd[0], r1 = s_st.Rd[1], r2 = s_st.Rd[2], r3 = s_st.Rd[3], r4 = s_st.Rd[4], r5 = s_st.Rd[5],
+                r6 = s_st.Rd[6], r7 = s_st.Rd[7], r8 = s_st.Rd[8], t0 = s_st.td[0], t1 = s_st.td[1], t2 = s_st.td[2];
+    float4 ox, oy, oz;
+#define PCR_ROW(o, a, b, c, tt)                      \
+    o.x = ((a * px.x + b * py.x) + c * pz.x) + tt;   \
+    o.y = ((a * px.y + b * py.y) + c * pz.y) + tt;   \
+    o.z = ((a * px.z + b * py.z) + c * pz.z) + tt;   \
+    o.w = ((a * px.w + b * py.w) + c * pz.w) + tt;
+    PCR_ROW(ox, r0, r1, r2, t0)
+    PCR_ROW(oy, r3, r4, r5, t1)
+    PCR_ROW(oz, r6, r7, r8, t2)
+#undef PCR_ROW
+    if (base + 3 >= n) {                             // (the padding invariant of the tail group: transform_state_kernel)
+        const float inf = __builtin_inff();
+        if (base + 0 >= n) { ox.x = inf; oy.x = 0.f; oz.x = 0.f; }
+        if (base + 1 >= n) { ox.y = inf; oy.y = 0.f; oz.y = 0.f; }
+        if (base + 2 >= n) { ox.z = inf; oy.z = 0.f; oz.z = 0.f; }
+        if (base + 3 >= n) { ox.w = inf; oy.w = 0.f; oz.w = 0.f; }
+    }
+    reinterpret_cast<float4*>(x)[i] = ox;
+    reinterpret_cast<float4*>(y)[i] = oy;
+    reinterpret_cast<float4*>(z)[i] = oz;
+    if (seed) {
+        const float mx[4] = { ox.x, ox.y, ox.z, ox.w }, my[4] = { oy.x, oy.y, oy.z, oy.w }, mz[4] = { oz.x, oz.y, oz.z, oz.w };
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            if (base + u >= n) continue;
+            const uint32_t j = (uint32_t)(sk[u] & 0xFFFFFFFFull);
+            unsigned long long key = ~0ull;
+            if (j < nt) {
+                const float dx = mx[u] - sq[u][0], dy = my[u] - sq[u][1], dz = mz[u] - sq[u][2];
+                const uint32_t e2 = __float_as_uint((dx * dx + dy * dy) + dz * dz);       // A1, unfused (nanoflann.hpp:403-406): seed_next_search's arithmetic
+                if (e2 < 0x7F7FFFFFu) key = ((unsigned long long)e2 << 32) | j;            // FLT_MAX gate, nanoflann.hpp:163,1360
+            }
+            keys[base + u] = key;
+        }
+    }
+}
+
 // multi rank, step 1: reduce the block rows into the all-reduce buffer
 //   [0..54] normalised limbs, [55] overflow flag, [56 + 2r] ORDER KEY of rank r's last kept pair (0: it kept none), [57 + 2r] that pair's d2
 // (every entry is summed exactly by the all-reduce: integers below 2^40 x ranks, one non-zero pair of words per rank).  The order key
@@ -724,6 +932,52 @@ int launch_icp_update_move(pcr_ctx* ctx, uint32_t n_blocks, const IcpState* st_i
                            st_out, ctx->dev_out, c->x(), c->y(), c->z(), (uint32_t)c->n, n4, sd);
     }
     PCR_HIP(ctx, hipGetLastError());
+    return PCR_OK;
+}
+
+// threads per workgroup of the fused sums + move launch (4 pairs per thread): 512 = 59 workgroups at 120 k (tune icp_fused_sums_threads: 256)
+static int fs_threads(const pcr_ctx* ctx) { return tune_get(ctx, "icp_fused_sums_threads", 512) == 256 ? 256 : 512; }
+
+// the workgroups the fused sums + move launch takes for n points, or 0 where it does not run: tune icp_fused_sums = 2 (off), more workgroups than
+// min(CUs, tune icp_fused_sums_max_blocks) — one workgroup per CU BY COUNT is what makes all of them resident, with a wide margin — or fewer than
+// icp_fused_sums_min points: the barrier (3.9 us from a workgroup's row store to the end of its wait) costs more than the launch boundary and the second
+// pass it replaces while those are short (4 000 points: 25.0 against 22.4 us per iteration; 60 k 49.3 / 50.8, 120 k 61.2 / 63.4, 250 k 98.6 / 107.1:
+// profiles/icp_fused_sums.txt)
+uint32_t icp_fused_sums_blocks(const pcr_ctx* ctx, size_t n)
+{
+    if (n == 0 || tune_get(ctx, "icp_fused_sums", 1) != 1 || (int64_t)n < tune_get(ctx, "icp_fused_sums_min", 60000)) return 0;
+    const uint64_t T = (uint64_t)fs_threads(ctx), n4 = ((uint64_t)n + 3) / 4, blocks = (n4 + T - 1) / T;
+    const int64_t cus = ctx->prop.multiProcessorCount;
+    const int64_t cap = std::min<int64_t>(cus, tune_get(ctx, "icp_fused_sums_max_blocks", cus));
+    return (int64_t)blocks <= cap ? (uint32_t)blocks : 0u;
+}
+
+int launch_icp_sums_update_move(pcr_ctx* ctx, const pcr_cloud* tgt, pcr_cloud* c, float max_corr, const IcpState* st_in, IcpState* st_out,
+                                const KabschPlan& plan, const pcr_cloud* seed_tgt)
+{
+    if (ctx->keys_n != c->n) return fail(ctx, PCR_ERR_STATE, "kabsch: no matching correspondence pass");
+    const uint32_t blocks = icp_fused_sums_blocks(ctx, c->n);
+    if (!blocks || !ctx->icp_barrier_dev || (seed_tgt && seed_tgt != tgt)) return fail(ctx, PCR_ERR_STATE, "launch_icp_sums_update_move");
+    const uint32_t n4 = (uint32_t)((c->n + 3) / 4);
+    const SeedArgs sd = seed_args(ctx, c, seed_tgt);
+    const unsigned long long target = ctx->icp_barrier_arrived + blocks;      // the counter's value once every workgroup of this launch has arrived
+    {
+        ProfScope p(ctx, "icp_update");
+#ifdef PCR_FS_PROF
+#define PCR_FS_EXTRA , ctx->grid_stats_dev
+#else
+#define PCR_FS_EXTRA
+#endif
+#define PCR_FS(T)                                                                                                                                   \
+        hipLaunchKernelGGL((icp_sums_update_move_kernel<T>), dim3(blocks), dim3(T), 0, ctx->stream, tgt->x(), tgt->y(), tgt->z(), c->orig, ctx->keys, \
+                           (uint32_t)tgt->n, max_corr, plan, ctx->partials, ctx->icp_barrier_dev, target, st_in, st_out, ctx->dev_out, c->x(), c->y(),  \
+                           c->z(), (uint32_t)c->n, n4, sd.tx ? 1 : 0 PCR_FS_EXTRA)
+        if (fs_threads(ctx) == 256) PCR_FS(256); else PCR_FS(512);
+#undef PCR_FS
+#undef PCR_FS_EXTRA
+    }
+    PCR_HIP(ctx, hipGetLastError());
+    ctx->icp_barrier_arrived = target;        // (counted only once the launch is on the stream)
     return PCR_OK;
 }
 

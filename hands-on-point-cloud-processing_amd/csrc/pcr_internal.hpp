@@ -41,7 +41,7 @@ struct IcpState {
     int stop;                    // set by the update kernel: later kernels of the stream become no-ops
     int stop_after_transform;    // max_iter reached: stop once the last transform has been applied
     int overflow;                // a kept source point lay beyond the fixed-point grid of the Kabsch sums (kabsch_plan): PCR_ERR_STATE
-    int pad_;
+    int barrier_timeout;         // the workgroups of a fused sums + move launch did not meet within its bound (kabsch.hip): PCR_ERR_STATE
     unsigned long long unchanged;
     unsigned long long iters_run;
     unsigned long long max_iter;
@@ -161,6 +161,10 @@ struct pcr_ctx {
     void* aux = nullptr;                  // second device scratch (partial results of sliced searches), grows on demand
     size_t aux_cap = 0;
     pcr::IcpState* icp_state_dev = nullptr;    // pipelined ICP: device state, pinned snapshots, snapshot events
+    // the grid barrier of the fused sums + move launch (kabsch.hip): ONE monotonic counter in device memory (a line of its own behind the two
+    // states, never reset) and the value it has once every workgroup of every launch so far has arrived
+    unsigned long long* icp_barrier_dev = nullptr;
+    uint64_t icp_barrier_arrived = 0;
     pcr::IcpState* icp_state_host = nullptr;
     hipEvent_t icp_events[4] = { nullptr, nullptr, nullptr, nullptr };
     unsigned long long* grid_stats_dev = nullptr;   // diagnostics of the grid search (tune grid_stats)
@@ -280,6 +284,11 @@ int launch_transform_state(pcr_ctx* ctx, pcr_cloud* c, IcpState* st_dev, const p
 // small clouds, one rank: icp_update + transform_state in one launch; the state alternates between the two buffers st_in / st_out
 int launch_icp_update_move(pcr_ctx* ctx, uint32_t n_blocks, const IcpState* st_in, IcpState* st_out, const KabschPlan& plan, pcr_cloud* c,
                            const pcr_cloud* seed_tgt = nullptr);
+// exhaustive loops, one rank, a grid of at most one workgroup per CU: kabsch_partial + icp_update_move in ONE launch whose workgroups meet once at a
+// grid barrier.  icp_fused_sums_blocks = the workgroups it would take (0: the cloud or the device rules it out)
+uint32_t icp_fused_sums_blocks(const pcr_ctx* ctx, size_t n);
+int launch_icp_sums_update_move(pcr_ctx* ctx, const pcr_cloud* tgt, pcr_cloud* c, float max_corr, const IcpState* st_in, IcpState* st_out,
+                                const KabschPlan& plan, const pcr_cloud* seed_tgt);
 int comm_allreduce_f64_device(pcr_ctx* ctx, double* dev_buf, int n);   // RCCL on the ctx stream, no host round trip
 int launch_plane_count(pcr_ctx* ctx, const pcr_cloud* pts, const double* planes4_host, size_t n_planes,
                        double thr, unsigned long long* counts_out);

@@ -1,0 +1,65 @@
+#!/usr/bin/env python3
+"""The tail of an ICP iteration (sums -> solve -> move -> seeds) with and without the fused sums + move launch (tune icp_fused_sums 1 / 2).
+usage: run_icp_tail.py trace [n]            two 20-iteration exhaustive loops at n points, nothing else (under rocprofv3 --kernel-trace; tools/trace_iter.py)
+       run_icp_tail.py ab [reps]            wall time per iteration, icp_fused_sums 1 / 2 alternating in ONE process: 60 k / 120 k / 250 k exhaustive
+                                            (20 iterations) and hw9's 4 000 points with the grid (800 iterations); median and spread (max - min) over reps;
+                                            at 120 k also 256-thread workgroups (icp_fused_sums_threads)
+       run_icp_tail.py stamps [n]           profile build (tools/ab_build.sh fsprof kabsch.hip -DPCR_FS_PROF; PCR_LIB_PATH=.../libpcr_fsprof.so): per workgroup
+                                            the time from its row store to the end of its wait at the grid barrier, last iteration of a 20-iteration loop
+PCR_TUNE="key=value,..." sets any other knob."""
+import importlib, os, sys, time
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+pcr = importlib.import_module("hands-on-point-cloud-processing_amd")
+synth = importlib.import_module("hands-on-point-cloud-processing_amd.synth")
+mode = sys.argv[1] if len(sys.argv) > 1 else "ab"
+ctx = pcr.Context(0)
+ctx.tune("icp_fused_sums_min", 1); ctx.tune("icp_fused_sums_grid", 1)      # every size and both searches take the fused launch when icp_fused_sums is 1
+for kv in os.environ.get("PCR_TUNE", "").split(","):
+    if "=" in kv:
+        k_, v_ = kv.split("="); ctx.tune(k_, int(v_))
+
+
+def pair(n):
+    src, tgt = synth.kitti_like_pair(n)
+    return ctx.cloud(src), ctx.cloud(tgt)
+
+
+if mode == "trace":
+    n = int(sys.argv[2]) if len(sys.argv) > 2 else 120000
+    cs, ct = pair(n); ctx.tune("nn_method", 1)
+    for _ in range(2):
+        T, st = ctx.icp_point2point(cs, ct, max_corr=1.0, max_iter=20, eps=0.0)
+    print(f"n={n}: iters_run {st['iters_run']} last_pairs {st['last_pairs']}")
+elif mode == "stamps":
+    n = int(sys.argv[2]) if len(sys.argv) > 2 else 120000
+    cs, ct = pair(n); ctx.tune("nn_method", 1)
+    ctx.icp_point2point(cs, ct, max_corr=1.0, max_iter=20, eps=0.0)
+    ctx.tune("grid_stats", 1)
+    for threads in (512, 256):
+        ctx.tune("icp_fused_sums_threads", threads)
+        ctx.icp_point2point(cs, ct, max_corr=1.0, max_iter=20, eps=0.0)
+        w = ctx.nn1_stats(); k = max(w[14], 1)
+        print(f"n={n} threads {threads}: workgroups stamped {w[14]}; row store -> end of wait: mean {w[12] / k / 100:.2f} us, longest {w[13] / 100:.2f} us; "
+              f"kernel entry -> row store: mean {w[15] / k / 100:.2f} us")
+else:
+    reps = int(sys.argv[2]) if len(sys.argv) > 2 else 8
+    for n, method, iters, arms in ((60000, 1, 20, ((1, 512), (2, 512))), (120000, 1, 20, ((1, 512), (2, 512), (1, 256))), (250000, 1, 20, ((1, 512), (2, 512))),
+                                   (4000, 2, 800, ((1, 512), (2, 512)))):
+        cs, ct = pair(n); ctx.tune("nn_method", method)
+        us = {a: [] for a in arms}
+        poses = {}
+        for r in range(reps + 1):                      # (the first round warms up: indexes, spare buffers)
+            for a in arms:
+                ctx.tune("icp_fused_sums", a[0]); ctx.tune("icp_fused_sums_threads", a[1])
+                t0 = time.perf_counter()
+                T, st = ctx.icp_point2point(cs, ct, max_corr=1.0, max_iter=iters, eps=0.0)
+                dt = time.perf_counter() - t0
+                if r: us[a].append(dt / max(st["iters_run"], 1) * 1e6)
+                poses[a] = T.view(np.uint32).tobytes()
+        same = all(p == poses[arms[0]] for p in poses.values())
+        for a in arms:
+            v = np.array(us[a])
+            print(f"n={n} method={method} iterations={iters} icp_fused_sums={a[0]} threads={a[1]}: median {np.median(v):.2f} us/iteration, spread {v.max() - v.min():.2f} "
+                  f"(min {v.min():.2f}, max {v.max():.2f}; {reps} calls); pose bits equal: {same}")
+        cs.free(); ct.free()
