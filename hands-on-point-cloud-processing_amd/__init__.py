@@ -74,6 +74,8 @@ ABI_SYMBOLS = [
     "pcr_fps_f32", "pcr_ball_query_f32", "pcr_group_points_f32", "pcr_objects_from_labels_f32",
     "pcr_mat64_create", "pcr_mat64_destroy", "pcr_mat64_info", "pcr_kmeans_step_f64", "pcr_kmeans_fit_f64", "pcr_kmeans_predict_f64", "pcr_kmeanspp_init_f64",
     "pcr_gmm_em_step_f64", "pcr_gmm_fit_f64", "pcr_gmm_predict_f64",
+    "pcr_range_image_create_f32", "pcr_range_image_from_host_f64", "pcr_range_image_shape", "pcr_range_image_read", "pcr_range_image_close_f64",
+    "pcr_range_image_label_f64", "pcr_range_image_assign", "pcr_range_image_destroy", "pcr_range_cluster_f32",
 ]
 
 
@@ -184,6 +186,15 @@ def lib():
     L.pcr_gmm_em_step_f64.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp]
     L.pcr_gmm_fit_f64.argtypes = [vp, vp, C.c_int, vp, C.c_double, C.c_double, C.c_int, C.c_uint64, vp, vp, vp, ip, ip, ip]
     L.pcr_gmm_predict_f64.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp]
+    L.pcr_range_image_create_f32.argtypes = [vp, vp, C.c_double, C.POINTER(vp)]
+    L.pcr_range_image_from_host_f64.argtypes = [vp, vp, sz, sz, C.POINTER(vp)]
+    L.pcr_range_image_shape.argtypes = [vp, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz), C.POINTER(C.c_uint64)]
+    L.pcr_range_image_read.argtypes = [vp, vp, vp, vp]
+    L.pcr_range_image_close_f64.argtypes = [vp, vp, C.c_int]
+    L.pcr_range_image_label_f64.argtypes = [vp, vp, C.c_double, C.c_double, C.c_int, vp, C.POINTER(C.c_uint64)]
+    L.pcr_range_image_assign.argtypes = [vp, vp, vp]
+    L.pcr_range_image_destroy.argtypes = [vp, vp]
+    L.pcr_range_cluster_f32.argtypes = [vp, vp, C.c_double, C.c_double, C.c_int, vp, C.POINTER(C.c_uint64), vp]
     L.pcr_nn1_desc_f32.argtypes = [vp, vp, sz, vp, sz, C.c_int, vp, vp]
     L.pcr_match_union_f32.argtypes = [vp, vp, sz, vp, sz, C.c_int, C.c_float, vp, vp, C.POINTER(sz)]
     L.pcr_match_inter_f32.argtypes = [vp, vp, sz, vp, sz, C.c_int, C.c_float, vp, vp, C.POINTER(sz)]
@@ -497,6 +508,57 @@ class Rows:
         self.ctx._handles.discard(self)
 
 
+class RangeImage:
+    """A range image resident in HBM (include/pcr.h pcr_range_image): projected from a cloud or taken from the host."""
+
+    def __init__(self, ctx: "Context", handle):
+        self.ctx, self.h = ctx, handle
+        ctx._handles.add(self)
+        r, c, n, d = C.c_size_t(), C.c_size_t(), C.c_size_t(), C.c_uint64()
+        lib().pcr_range_image_shape(self.h, C.byref(r), C.byref(c), C.byref(n), C.byref(d))
+        self.shape, self.n_points, self.n_dropped = (r.value, c.value), n.value, d.value
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:   # noqa: BLE001
+            pass
+
+    def image(self) -> np.ndarray:
+        out = np.empty(self.shape, np.float64)
+        self.ctx._ck(lib().pcr_range_image_read(self.ctx.h, self.h, out.ctypes.data, None))
+        return out
+
+    def pixels(self) -> np.ndarray:
+        """per point: r * cols + c in the cropped image, -1 = dropped"""
+        out = np.empty(max(self.n_points, 1), np.int32)
+        self.ctx._ck(lib().pcr_range_image_read(self.ctx.h, self.h, None, out.ctypes.data))
+        return out[:self.n_points]
+
+    def close_gaps(self, pad: int):
+        """depth_completion (foreground_clustering_range.py:136-149), in place"""
+        self.ctx._ck(lib().pcr_range_image_close_f64(self.ctx.h, self.h, int(pad)))
+
+    def label(self, phi: float, theta: float, nn_mode: int):
+        """range_image_labeling (:51-95) -> (image_label int32 rows x cols, n_labels)"""
+        out = np.empty(self.shape, np.int32)
+        nl = C.c_uint64()
+        self.ctx._ck(lib().pcr_range_image_label_f64(self.ctx.h, self.h, float(phi), float(theta), int(nn_mode), out.ctypes.data, C.byref(nl)))
+        return out, int(nl.value)
+
+    def assign(self) -> np.ndarray:
+        """cluster_assignment (:124-133) -> cluster_idx int32 [n_points]"""
+        out = np.empty(max(self.n_points, 1), np.int32)
+        self.ctx._ck(lib().pcr_range_image_assign(self.ctx.h, self.h, out.ctypes.data))
+        return out[:self.n_points]
+
+    def free(self):
+        if self.h and self.ctx.h:
+            lib().pcr_range_image_destroy(self.ctx.h, self.h)
+        self.h = None
+        self.ctx._handles.discard(self)
+
+
 def read_kitti_bin(path: str, floats_per_point: int = 4) -> np.ndarray:
     """A velodyne .bin as the reference reads it: N x 4 f32 rows x, y, z, intensity (read_velodyne_bin,
     Homework4/ground_detection_ransac.py:23-34; Homework2/hw2/include/test.hpp:26-28 without its EOF duplicate) or the hw9
@@ -762,6 +824,31 @@ class Context:
         self._ck(lib().pcr_dbscan_f32(self.h, cloud.h, float(eps), int(min_points), labels.ctypes.data, core.ctypes.data, counts.ctypes.data,
                                       C.byref(nc)))
         return labels[:n], core[:n].astype(bool), counts[:n], int(nc.value)
+
+    def range_image(self, cloud: Cloud, resolution: float) -> RangeImage:
+        """pcd_to_range_image (foreground_clustering_range.py:13-48) of a resident cloud; the contract of pcr_range_image_create_f32."""
+        h = C.c_void_p()
+        self._ck(lib().pcr_range_image_create_f32(self.h, cloud.h, float(resolution), C.byref(h)))
+        return RangeImage(self, h)
+
+    def range_image_from_host(self, image) -> RangeImage:
+        """A caller's rows x cols f64 range image as it is (-1 = empty), no crop."""
+        a = np.ascontiguousarray(image, np.float64)
+        if a.ndim != 2:
+            raise PcrError("range image: rows x cols")
+        h = C.c_void_p()
+        self._ck(lib().pcr_range_image_from_host_f64(self.h, a.ctypes.data if a.size else None, a.shape[0], a.shape[1], C.byref(h)))
+        return RangeImage(self, h)
+
+    def range_cluster(self, cloud: Cloud, resolution: float, theta: float, nn_mode: int):
+        """foreground_clustering_range.py's __main__ (:164-167) in one call -> (cluster_idx i32[n], n_clusters, {rows, cols, dropped,
+        full_pixels}); the contract of pcr_range_cluster_f32."""
+        n = len(cloud)
+        out = np.empty(max(n, 1), np.int32)
+        nc = C.c_uint64()
+        st = np.zeros(4, np.uint64)
+        self._ck(lib().pcr_range_cluster_f32(self.h, cloud.h, float(resolution), float(theta), int(nn_mode), out.ctypes.data, C.byref(nc), st.ctypes.data))
+        return out[:n], int(nc.value), {"rows": int(st[0]), "cols": int(st[1]), "dropped": int(st[2]), "full_pixels": int(st[3])}
 
     def statistical_outlier(self, cloud: Cloud, nb_neighbors: int, std_ratio: float):
         """remove_statistical_outlier (ground_detection_SVD.py:33) -> (keep bool[n], avg distance f64[n], (mean, std, thr), kept

@@ -699,4 +699,109 @@ void pcr_shard_range(size_t n, int nranks, int rank, size_t* begin, size_t* end)
     if (end) *end = e;
 }
 
+// ---- range image (range_image.hip): foreground_clustering_range.py -----------------------------------------------------------------
+static int ri_check_label_args(pcr_ctx* ctx, const pcr_range_image* img, double phi_deg, double theta_deg, int nn_mode, const char* who)
+{
+    if (!std::isfinite(phi_deg)) return fail(ctx, PCR_ERR_ARG, who);
+    if (!(theta_deg >= 0.0 && theta_deg < 90.0)) return fail(ctx, PCR_ERR_ARG, "range image: theta must lie in [0, 90)");
+    if (nn_mode < 1 || nn_mode > 8) return fail(ctx, PCR_ERR_ARG, "range image: nn_mode must lie in 1 ... 8");
+    if (img && img->cols < nn_mode) return fail(ctx, PCR_ERR_ARG, "range image: the image is narrower than nn_mode columns");
+    return PCR_OK;
+}
+
+int pcr_range_image_create_f32(pcr_ctx* ctx, const pcr_cloud* cloud, double resolution_deg, pcr_range_image** img)
+{
+    if (img) *img = nullptr;
+    if (!ctx || !cloud || !img) return fail(ctx, PCR_ERR_ARG, "pcr_range_image_create_f32");
+    if (!std::isfinite(resolution_deg) || !(resolution_deg > 0.0)) return fail(ctx, PCR_ERR_ARG, "pcr_range_image_create_f32: resolution must be finite and > 0");
+    const double w = std::floor(360 / resolution_deg) + 1, h = std::floor(60 / resolution_deg) + 1;      // :21-22
+    if (!(w * h <= (double)0x7FFFFFF0ull)) return fail(ctx, PCR_ERR_ARG, "pcr_range_image_create_f32: more than 2^31 - 16 pixels");
+    if (cloud->n > 0x7FFFFFF0ull) return fail(ctx, PCR_ERR_ARG, "pcr_range_image_create_f32: cloud too large");
+    if (cloud->n == 0) return fail(ctx, PCR_ERR_EMPTY, "pcr_range_image_create_f32: no point lands in the image");
+    PCR_HIP(ctx, hipSetDevice(ctx->device));
+    return ri_create(ctx, cloud, resolution_deg, (int)w, (int)h, img);
+}
+
+int pcr_range_image_from_host_f64(pcr_ctx* ctx, const double* image, size_t rows, size_t cols, pcr_range_image** img)
+{
+    if (img) *img = nullptr;
+    if (!ctx || !image || !img || rows == 0 || cols == 0) return fail(ctx, PCR_ERR_ARG, "pcr_range_image_from_host_f64");
+    if (rows > 0x7FFFFFF0ull || cols > 0x7FFFFFF0ull || rows * cols > 0x7FFFFFF0ull) return fail(ctx, PCR_ERR_ARG, "pcr_range_image_from_host_f64: more than 2^31 - 16 pixels");
+    PCR_HIP(ctx, hipSetDevice(ctx->device));
+    return ri_from_host(ctx, image, (int)rows, (int)cols, img);
+}
+
+int pcr_range_image_shape(const pcr_range_image* img, size_t* rows, size_t* cols, size_t* n_points, uint64_t* n_dropped)
+{
+    if (!img) return PCR_ERR_ARG;
+    if (rows) *rows = (size_t)img->rows;
+    if (cols) *cols = (size_t)img->cols;
+    if (n_points) *n_points = img->n_points;
+    if (n_dropped) *n_dropped = img->dropped;
+    return PCR_OK;
+}
+
+int pcr_range_image_read(pcr_ctx* ctx, const pcr_range_image* img, double* image, int32_t* pixel)
+{
+    if (!ctx || !img) return fail(ctx, PCR_ERR_ARG, "pcr_range_image_read");
+    PCR_HIP(ctx, hipSetDevice(ctx->device));
+    return ri_read(ctx, img, image, pixel);
+}
+
+int pcr_range_image_close_f64(pcr_ctx* ctx, pcr_range_image* img, int pad)
+{
+    if (!ctx || !img) return fail(ctx, PCR_ERR_ARG, "pcr_range_image_close_f64");
+    if (pad < 0 || pad > 16) return fail(ctx, PCR_ERR_ARG, "pcr_range_image_close_f64: pad must lie in 0 ... 16");
+    PCR_HIP(ctx, hipSetDevice(ctx->device));
+    return ri_close(ctx, img, pad);
+}
+
+int pcr_range_image_label_f64(pcr_ctx* ctx, pcr_range_image* img, double phi_deg, double theta_deg, int nn_mode, int32_t* image_label, uint64_t* n_labels)
+{
+    if (n_labels) *n_labels = 0;
+    if (!ctx || !img) return fail(ctx, PCR_ERR_ARG, "pcr_range_image_label_f64");
+    int rc = ri_check_label_args(ctx, img, phi_deg, theta_deg, nn_mode, "pcr_range_image_label_f64: phi must be finite");
+    if (rc) return rc;
+    PCR_HIP(ctx, hipSetDevice(ctx->device));
+    return ri_label(ctx, img, phi_deg, theta_deg, nn_mode, image_label, n_labels);
+}
+
+int pcr_range_image_assign(pcr_ctx* ctx, const pcr_range_image* img, int32_t* cluster_idx)
+{
+    if (!ctx || !img || (img->n_points && !cluster_idx)) return fail(ctx, PCR_ERR_ARG, "pcr_range_image_assign");
+    if (!img->labelled) return fail(ctx, PCR_ERR_STATE, "pcr_range_image_assign: the image has not been labelled");
+    PCR_HIP(ctx, hipSetDevice(ctx->device));
+    return ri_assign(ctx, img, cluster_idx);
+}
+
+int pcr_range_image_destroy(pcr_ctx* ctx, pcr_range_image* img)
+{
+    if (!img) return PCR_OK;
+    if (ctx) hipSetDevice(ctx->device);
+    return ri_destroy(ctx, img);
+}
+
+int pcr_range_cluster_f32(pcr_ctx* ctx, const pcr_cloud* cloud, double resolution_deg, double theta_deg, int nn_mode, int32_t* cluster_idx,
+                          uint64_t* n_clusters, uint64_t stats4[4])
+{
+    if (n_clusters) *n_clusters = 0;
+    if (!ctx || !cloud || (cloud->n && !cluster_idx)) return fail(ctx, PCR_ERR_ARG, "pcr_range_cluster_f32");
+    int rc = ri_check_label_args(ctx, nullptr, resolution_deg, theta_deg, nn_mode, "pcr_range_cluster_f32: resolution must be finite and > 0");
+    if (rc) return rc;
+    pcr_range_image* img = nullptr;
+    rc = pcr_range_image_create_f32(ctx, cloud, resolution_deg, &img);
+    if (rc) return rc;
+    uint64_t nl = 0;
+    rc = pcr_range_image_label_f64(ctx, img, resolution_deg, theta_deg, nn_mode, nullptr, &nl);      // phi = resolution (:166)
+    if (!rc) rc = ri_assign(ctx, img, cluster_idx);
+    if (!rc) {
+        if (n_clusters) *n_clusters = nl;
+        if (stats4) { stats4[0] = (uint64_t)img->rows; stats4[1] = (uint64_t)img->cols; stats4[2] = img->dropped; stats4[3] = (uint64_t)img->full_rows * img->full_cols; }
+    }
+    const std::string keep = ctx->err;                     // (the destroy below does not fail, but must not lose the message either)
+    ri_destroy(ctx, img);
+    if (rc) ctx->err = keep;
+    return rc;
+}
+
 }  // extern "C"

@@ -12,7 +12,7 @@
 //   final   full pointer jumping (root[p]), key[root] = min original index of the component's core points
 //   border  a non-core record with a neighbour takes the smallest key over its core neighbours' components
 //   label   flag[i] = core(i) && key[root(i)] == i (input numbering); exclusive scan = cluster ids in ascending key order
-// Union-find: parent[] in record numbering, parent[x] <= x always (a root is hooked under a SMALLER root by
+// Union-find (union_find.hpp): parent[] in record numbering, parent[x] <= x always (a root is hooked under a SMALLER root by
 // atomicCAS(&parent[hi], hi, lo)), so every path strictly decreases and a find takes at most n steps; more means a corrupt
 // structure: a device error word is set and the call returns PCR_ERR_STATE.  A failed CAS means another lane hooked `hi`
 // first; the union continues from the value the CAS returned.  Hooks succeed at most n - 1 times overall, so the retry loop
@@ -25,6 +25,7 @@
 // in slot order / found (-1 without a neighbour); the two global sums in a fixed order (a fixed number of workgroups for a
 // given n, each a fixed strided sequence + a shuffle tree), mask, exclusive scan, gather into a new device cloud.
 #include "grid_common.hpp"
+#include "union_find.hpp"
 
 #include <cfloat>
 #include <cmath>
@@ -149,43 +150,6 @@ __global__ __launch_bounds__(CL_BLOCK) void db_init_kernel(uint32_t* __restrict_
     if (i >= n) return;
     parent[i] = i;
     key[i] = CL_NONE;
-}
-
-__device__ __forceinline__ uint32_t uf_load(const uint32_t* parent, uint32_t i)
-{
-    return __hip_atomic_load(parent + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// root of x, with path halving while HALVE; at most n steps (indices strictly decrease along a path), else err |= 1
-template <bool HALVE = true>
-__device__ __forceinline__ uint32_t uf_find(uint32_t* parent, uint32_t x, uint32_t n, uint32_t* err)
-{
-    for (uint32_t step = 0; step <= n; step++) {
-        const uint32_t px = uf_load(parent, x);
-        if (px == x) return x;
-        const uint32_t gp = uf_load(parent, px);
-        if (gp == px) return px;
-        if (HALVE) __hip_atomic_store(parent + x, gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        x = gp;
-    }
-    atomicOr(err, 1u);
-    return x;
-}
-
-// a and b are roots (or ancestors of the two sets); hooks the larger root under the smaller one
-__device__ __forceinline__ void uf_union(uint32_t* parent, uint32_t a, uint32_t b, uint32_t n, uint32_t* err)
-{
-    for (uint32_t it = 0; it <= n; it++) {
-        a = uf_find(parent, a, n, err);
-        b = uf_find(parent, b, n, err);
-        if (a == b) return;
-        const uint32_t hi = max(a, b), lo = min(a, b);
-        const uint32_t old = atomicCAS(parent + hi, hi, lo);
-        if (old == hi) return;
-        a = old;                                            // hi was hooked by another lane in between: go on from there
-        b = lo;
-    }
-    atomicOr(err, 2u);
 }
 
 template <int G>

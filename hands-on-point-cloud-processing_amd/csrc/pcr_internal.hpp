@@ -95,6 +95,19 @@ struct pcr_cloud {
     float* z() const { return base + 2 * cap; }
 };
 
+// a range image resident in HBM (range_image.hip): the cropped f64 image, its labels and, for an image projected from a cloud, the pixel of every point
+struct pcr_range_image {
+    size_t n_points = 0;         // 0: an image taken from the host (pcr_range_image_from_host_f64)
+    int rows = 0, cols = 0;      // the cropped image
+    int full_rows = 0, full_cols = 0;
+    uint64_t dropped = 0;        // points outside the image or non-finite
+    double* image = nullptr;     // rows x cols, -1 = empty
+    int32_t* label = nullptr;    // rows x cols, valid while `labelled`
+    int32_t* pix = nullptr;      // n_points: r * cols + c in the cropped image, -1 = dropped
+    bool labelled = false;
+    uint64_t n_labels = 0;
+};
+
 struct pcr_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -240,6 +253,14 @@ int cloud_knn_small(pcr_ctx* ctx, const pcr_cloud* db, const float* q_rows, size
 // device-wide exclusive scan of u32 (grid.hip): totals needs ceil(n / SCAN_TILE) + 1 words
 constexpr int SCAN_TILE = 2048;
 int exclusive_scan_u32(pcr_ctx* ctx, const uint32_t* in, uint32_t* out, size_t n, uint32_t* totals, uint32_t* grand);
+// range image (range_image.hip); arguments are validated by the entry points in api.cpp
+int ri_create(pcr_ctx* ctx, const pcr_cloud* cloud, double resolution_deg, int width, int height, pcr_range_image** out);
+int ri_from_host(pcr_ctx* ctx, const double* image, int rows, int cols, pcr_range_image** out);
+int ri_read(pcr_ctx* ctx, const pcr_range_image* img, double* image, int32_t* pixel);
+int ri_close(pcr_ctx* ctx, pcr_range_image* img, int pad);
+int ri_label(pcr_ctx* ctx, pcr_range_image* img, double phi_deg, double theta_deg, int nn_mode, int32_t* image_label, uint64_t* n_labels);
+int ri_assign(pcr_ctx* ctx, const pcr_range_image* img, int32_t* cluster_idx);
+int ri_destroy(pcr_ctx* ctx, pcr_range_image* img);
 // dispatcher: tune "nn_method" 0 = auto (grid for targets >= 2048 points), 1 = brute force, 2 = grid
 // (auto: api.cpp nn1_auto_grid — inside an iterated loop the grid from 128 points on; one-shot searches of a target without an index
 // stay exhaustive while queries x targets is small)

@@ -10,6 +10,11 @@ Mirrors (same names, argument meaning and return values):
   ground_detection_on3segs  Homework4/ground_detection_SVD.py:104-126
   pcd_preprocessing       Homework4/ground_detection_SVD.py:22-37        (GPU: y crop on the host, pcr_statistical_outlier_f32)
   cluster_dbscan          open3d PointCloud.cluster_dbscan, ground_detection_SVD.py:173   (GPU: pcr_dbscan_f32)
+  pcd_to_range_image      Homework4/foreground_clustering_range.py:13-48   (GPU: pcr_range_image_create_f32; :34 restated with atan2)
+  range_image_labeling    Homework4/foreground_clustering_range.py:51-95   (GPU: pcr_range_image_label_f64; all connected components)
+  cluster_assignment      Homework4/foreground_clustering_range.py:124-133 (GPU: pcr_range_image_assign)
+  depth_completion        Homework4/foreground_clustering_range.py:136-149 (GPU: pcr_range_image_close_f64)
+  cluster_range_image     Homework4/foreground_clustering_range.py:164-167 (__main__'s three calls at once: pcr_range_cluster_f32)
 
 The hot loop of my_ransac — `dists = |[X 1] . params|; inliers = sum(dists < thr)` evaluated once per hypothesis
 (:138-139) — becomes ONE launch of pcr_plane_count_f64 over all `max_iteration` hypotheses: the points are read
@@ -146,6 +151,105 @@ def cluster_dbscan(points, eps, min_points, print_progress=False, *, ctx=None) -
     finally:
         cloud.free()
     return labels
+
+
+class IdxImage:
+    """The reference's idx_image (foreground_clustering_range.py:29, :39): `.shape`, and `[r, c]` -> None for a pixel without a point, else
+    the object array [None, i, ...] of the pixel's point indices, ascending.  Built lazily from the per-point pixels; keeps the
+    device-resident image alive for range_image_labeling and cluster_assignment."""
+
+    def __init__(self, handle, image, pixels):
+        self.handle, self.image, self.pixels = handle, image, pixels
+        self.shape = image.shape
+        self.last_label = None
+        self._order = self._start = None
+
+    def __getitem__(self, rc):
+        r, c = rc
+        rows, cols = self.shape
+        r, c = (r + rows if r < 0 else r), (c + cols if c < 0 else c)
+        if not (0 <= r < rows and 0 <= c < cols):
+            raise IndexError(f"index {rc} is out of bounds for shape {self.shape}")
+        if self._order is None:
+            self._order = np.argsort(self.pixels, kind="stable")                  # ascending point index inside a pixel
+            self._start = np.searchsorted(self.pixels[self._order], np.arange(rows * cols + 1))
+        p = r * cols + c
+        members = self._order[self._start[p]:self._start[p + 1]]
+        if members.size == 0:
+            return None
+        out = np.empty(members.size + 1, dtype=object)                           # np.append(None, i), repeated (:39)
+        out[0] = None
+        out[1:] = [int(i) for i in members]
+        return out
+
+
+def pcd_to_range_image(pcd_points, resolution, *, ctx=None):
+    """foreground_clustering_range.py:13-48 -> (range_image f64, idx_image, d).  :34 (math.asin with two arguments: TypeError) is
+    restated as atan2(z, sqrt(x*x + y*y)); a point the reference would raise IndexError on is dropped (in no pixel, label -1).  The
+    points are taken as float32, the precision of the scans pcd_preprocessing returns widened."""
+    pts = np.ascontiguousarray(np.asarray(pcd_points)[:, :3], np.float32)
+    ctx = ctx or default_context()
+    cloud = ctx.cloud(pts, 1)
+    try:
+        handle = ctx.range_image(cloud, resolution)
+    finally:
+        cloud.free()
+    image = handle.image()
+    return image, IdxImage(handle, image, handle.pixels()), np.linalg.norm(pts.astype(np.float64), axis=1)
+
+
+def _same_array(a, b):
+    return a is b or (isinstance(a, np.ndarray) and a.shape == b.shape and np.array_equal(a, b, equal_nan=True))
+
+
+def range_image_labeling(range_image, idx_image, depth_list, phi, theta, nn_mode, *, ctx=None):
+    """foreground_clustering_range.py:51-95 -> image_label (int32, -1 = no label): every connected component of the reference's
+    neighbour test, numbered by its first pixel in raster order (pcr_range_image_label_f64 says how the reference's own flood fill
+    relates to that).  idx_image and depth_list are unused there too (:82-85 are commented out)."""
+    img = np.asarray(range_image, np.float64)
+    if isinstance(idx_image, IdxImage) and idx_image.handle.h and _same_array(img, idx_image.image):
+        label, _ = idx_image.handle.label(phi, theta, nn_mode)                  # the labels stay on the device for cluster_assignment
+        idx_image.last_label = label
+        return label
+    handle = (ctx or default_context()).range_image_from_host(img)              # e.g. the image depth_completion returned
+    try:
+        return handle.label(phi, theta, nn_mode)[0]
+    finally:
+        handle.free()
+
+
+def cluster_assignment(idx_image, image_label, pcd_size):
+    """foreground_clustering_range.py:124-133 -> cluster_idx[pcd_size]: every point takes its pixel's label."""
+    assert idx_image.shape == image_label.shape
+    if idx_image.last_label is not None and idx_image.handle.h and _same_array(image_label, idx_image.last_label):
+        out = idx_image.handle.assign()
+    else:                                                                       # labels the device does not hold: a host gather
+        pix = idx_image.pixels
+        out = np.where(pix >= 0, np.asarray(image_label).reshape(-1)[np.maximum(pix, 0)], -1).astype(np.int32)
+    cluster_idx = np.full(pcd_size, -1, dtype=np.int32)
+    cluster_idx[:out.size] = out[:pcd_size]
+    return cluster_idx
+
+
+def depth_completion(image, pad, *, ctx=None):
+    """foreground_clustering_range.py:136-149: dilation then erosion with a (2 pad + 1)^2 window, the pad border left at -1."""
+    handle = (ctx or default_context()).range_image_from_host(np.asarray(image, np.float64))
+    try:
+        handle.close_gaps(pad)
+        return handle.image()
+    finally:
+        handle.free()
+
+
+def cluster_range_image(points, resolution=0.7, theta=30, nn_mode=7, *, ctx=None) -> np.ndarray:
+    """foreground_clustering_range.py:164-167 in one call (phi = resolution, as there) -> cluster_idx int32, -1 = no cluster."""
+    pts = np.ascontiguousarray(np.asarray(points)[:, :3], np.float32)
+    ctx = ctx or default_context()
+    cloud = ctx.cloud(pts, 1)
+    try:
+        return ctx.range_cluster(cloud, resolution, theta, nn_mode)[0]
+    finally:
+        cloud.free()
 
 
 def my_ransac(data: np.ndarray, indices: np.ndarray, max_iteration: int, threshold: float, *, ctx=None, rng=None):

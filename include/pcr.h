@@ -279,6 +279,68 @@ int pcr_dbscan_f32(pcr_ctx* ctx, const pcr_cloud* cloud, double eps, int min_poi
 int pcr_statistical_outlier_f32(pcr_ctx* ctx, const pcr_cloud* cloud, int nb_neighbors, double std_ratio, uint8_t* keep, double* avg_dist,
                                 double stats3[3], uint64_t* n_kept, pcr_cloud** kept_cloud);
 
+/* ---- Homework4 foreground stage, second path: range-image clustering, Homework4/foreground_clustering_range.py ---------------
+ * A pcr_range_image is an opaque, device-resident handle: the cropped f64 range image (-1 = empty pixel), its labels once
+ * labelled and, for an image projected from a cloud, the pixel of every point.
+ * pcr_range_image_create_f32 (pcd_to_range_image, :13-48), f64 on the cloud's f32 coordinates widened (what pcd_preprocessing
+ * hands over), every operation rounded, unfused:
+ *   res_rad = pi / 180 * resolution; width = floor(360 / resolution) + 1, height = floor(60 / resolution) + 1, offsets
+ *   ceil(size / 2); d = sqrt((x*x + y*y) + z*z) (np.linalg.norm); alpha = atan2(y, x);
+ *   beta = atan2(z, sqrt(x*x + y*y))   DIFFERS: :34 is math.asin(z, sqrt(...)), which raises TypeError (two arguments) — the
+ *   reference's function cannot run; the two-argument form with the horizontal range second is atan2's;
+ *   x = width - 1 - (floor(alpha / res_rad) + offset_width), y likewise from beta; an index in [-size, 0) wraps as numpy's
+ *   negative indexing does.  A point with an index outside [-size, size) (the reference: IndexError) or a non-finite coordinate
+ *   is DROPPED: pixel -1, label -1, counted in n_dropped.  The pixel's range is d of its HIGHEST point index (:38 in index
+ *   order).  Rows without a point are removed, then columns without a point (:41-47); a point at the origin has range 0, which
+ *   is neither empty nor ever labelled.  PCR_ERR_ARG for a resolution that is non-finite or <= 0 or gives more than 2^31 - 16
+ *   pixels; PCR_ERR_EMPTY when no point lands in the image (an empty cloud included).
+ * pcr_range_image_from_host_f64: the caller's rows x cols image as it is (no crop, no points; assign is then a no-op).
+ * pcr_range_image_shape: rows / cols of the cropped image, the number of points and of dropped points (each optional).
+ * pcr_range_image_read: the image (rows x cols f64) and the pixel of every point (r * cols + c, -1 = dropped), each optional.
+ * pcr_range_image_close_f64 (depth_completion, :136-149), in place: dila[r, c] = max of the (2 pad + 1)^2 window for
+ *   pad <= r < rows - pad, pad <= c < cols - pad, else -1; result = the same with min over dila.  NaN propagates as in
+ *   np.amax / np.amin.  pad in 0 ... 16 (PCR_ERR_ARG).  Labels of an earlier call are dropped.
+ * pcr_range_image_label_f64 (range_image_labeling, :51-95; phi, theta in degrees): phi_rad = phi * pi / 180, thr = theta * pi /
+ *   180, sin(phi_rad) and cos(phi_rad) from the host's libm.  Two pixels are LINKED when both ranges are > 0, the second lies in
+ *   the first's window (rows r - nn_mode .. r + nn_mode clipped to the image, columns c - nn_mode .. c + nn_mode wrapped ONCE
+ *   around the image), and with d1 = max, d2 = min of the two ranges: fabs(d1 - d2) < 1 and
+ *   atan2(d2 * sin(phi), d1 - d2 * cos(phi)) > thr.  The relation is symmetric.
+ *   DIFFERS: image_label = the CONNECTED COMPONENTS of that relation, numbered 0, 1, ... by each component's first pixel in
+ *   raster order; pixels with range <= 0 get -1.  The reference's flood fill assigns `[r, c] = queue[0]` (:66) and thereby
+ *   overwrites the row variable of its own seed scan: for the rest of that row it scans a wrong row, so that some components
+ *   are never seeded (all their pixels stay -1) and the numbers follow no raster order.  Relation to its output: on the
+ *   pixels the reference labels, its labels and the components correspond one to one; every occupied pixel it leaves at -1
+ *   lies in a component it labels nowhere (measured: 182 labels of 236 components on the 000099 foreground at (0.7, 30, 7)).
+ *   Which components it drops depends on its FIFO order.
+ *   PCR_ERR_ARG for theta outside [0, 90), nn_mode outside 1 ... 8, a non-finite phi, or an image narrower than nn_mode columns
+ *   (single wrapping equals the reference only from that width on).  image_label (rows x cols int32) and n_labels are optional;
+ *   the labels stay in the handle.  PCR_ERR_STATE if the union-find's bound is exceeded (never in a correct run).
+ * pcr_range_image_assign (cluster_assignment, :124-133): cluster_idx[i] = image_label[pixel(i)], every point of a pixel, -1 for
+ *   a dropped point.  PCR_ERR_STATE before a labelling.
+ * pcr_range_cluster_f32: `__main__` :164-167 in one call — create(resolution), label(phi = resolution, theta, nn_mode), assign.
+ *   stats4 (optional) = rows, cols of the cropped image, dropped points, pixels of the full image.
+ * ROUNDING BAND.  Everything above is IEEE arithmetic both sides agree on bit for bit, except atan2: glibc documents an error
+ *   of at most 1 ulp for its double atan2, the device library (OCML) is held to OpenCL's bound for double atan2, 6 ulp.  Hence
+ *   two results for the same arguments lie within 7 ulp(a) <= 7 * 2^-52 |a| of each other.
+ *   (1) pixel: q = fl(a / res_rad) adds half an ulp on either side: |q_dev - q_host| <= (7 + 1) * 2^-52 |q| = 2^-49 |q|.  A point
+ *       with |q - round(q)| <= 2^-49 max(|q|, 1) for alpha or beta may land in the neighbouring pixel; all others are pinned.
+ *   (2) edge: a pair with |angle - thr| <= 2^-49 max(angle, thr) may or may not be linked (the arguments of that atan2 are
+ *       equal bit for bit); all others are pinned.  The library's partition then lies between the components of the certain
+ *       links and those of the certain plus the in-band links.
+ *   On the KITTI scans the points in band (1) are those with y = 0 or z = 0 exactly (atan2(+-0, x > 0) = +-0 on both sides, C Annex F). */
+typedef struct pcr_range_image pcr_range_image;
+int pcr_range_image_create_f32(pcr_ctx* ctx, const pcr_cloud* cloud, double resolution_deg, pcr_range_image** img);
+int pcr_range_image_from_host_f64(pcr_ctx* ctx, const double* image, size_t rows, size_t cols, pcr_range_image** img);
+int pcr_range_image_shape(const pcr_range_image* img, size_t* rows, size_t* cols, size_t* n_points, uint64_t* n_dropped);
+int pcr_range_image_read(pcr_ctx* ctx, const pcr_range_image* img, double* image, int32_t* pixel);
+int pcr_range_image_close_f64(pcr_ctx* ctx, pcr_range_image* img, int pad);
+int pcr_range_image_label_f64(pcr_ctx* ctx, pcr_range_image* img, double phi_deg, double theta_deg, int nn_mode, int32_t* image_label,
+                              uint64_t* n_labels);
+int pcr_range_image_assign(pcr_ctx* ctx, const pcr_range_image* img, int32_t* cluster_idx);
+int pcr_range_image_destroy(pcr_ctx* ctx, pcr_range_image* img);
+int pcr_range_cluster_f32(pcr_ctx* ctx, const pcr_cloud* cloud, double resolution_deg, double theta_deg, int nn_mode, int32_t* cluster_idx,
+                          uint64_t* n_clusters, uint64_t stats4[4]);
+
 /* ---- Homework9 descriptors: FPFH33, getFPFH33Descriptors (Homework9/hw9/src/registration.cpp:254-269, PCL FPFHEstimationOMP) --
  * PCL is not pinned here: this is the library's own operation sequence, a restatement of PCL's FPFHEstimation.
  * Inputs: surface (n points), normals (one per surface point, a cloud whose x/y/z are normal_x/y/z, used as given, not
