@@ -753,7 +753,8 @@ extern "C" int pcr_kmeans_fit_f64(pcr_ctx* ctx, pcr_mat64* m, int k, const doubl
     int rc = mx_state_push(ctx, m);
     if (rc != PCR_OK) return rc;
     const long long total = (long long)max_iter + 1;              // both loops make at most max_iter + 1 passes
-    const long long batch = tune_get(ctx, "mixture_batch", 8);
+    long long batch = tune_get(ctx, "mixture_batch", 8);
+    if (batch < 1) batch = 1;                                     // a batch of no passes would never end the loop below
     long long done = 0;
     while (done < total) {
         const long long b = total - done < batch ? total - done : batch;
@@ -886,7 +887,8 @@ extern "C" int pcr_gmm_fit_f64(pcr_ctx* ctx, pcr_mat64* m, int k, const double* 
         s->pi[j] = 1.0 / (double)k;
     }
     if ((rc = mx_state_push(ctx, m)) != PCR_OK) return rc;
-    const long long batch = tune_get(ctx, "mixture_batch", 8);
+    long long batch = tune_get(ctx, "mixture_batch", 8);
+    if (batch < 1) batch = 1;                                     // a batch of no passes would never end the loop below
     long long done = 0;
     while (done < max_iter) {
         const long long b = max_iter - done < batch ? max_iter - done : batch;
