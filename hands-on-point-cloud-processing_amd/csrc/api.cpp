@@ -56,6 +56,22 @@ int ensure_aux(pcr_ctx* ctx, size_t bytes)
     return PCR_OK;
 }
 
+int bind_scratch(pcr_ctx* ctx, const Layout& L)
+{
+    const int rc = ensure_scratch(ctx, L.bytes());
+    if (rc) return rc;
+    L.bind(ctx->scratch);
+    return PCR_OK;
+}
+
+int bind_aux(pcr_ctx* ctx, const Layout& L)
+{
+    const int rc = ensure_aux(ctx, L.bytes());
+    if (rc) return rc;
+    L.bind(ctx->aux);
+    return PCR_OK;
+}
+
 int ensure_stage(pcr_ctx* ctx, size_t bytes)
 {
     if (bytes <= ctx->host_stage_cap) return PCR_OK;
@@ -490,10 +506,13 @@ int pcr_nn1_fetch(pcr_ctx* ctx, size_t n, uint32_t* idx, float* d2)
 {
     if (!ctx || n != ctx->keys_n || (n && (!idx || !d2))) return fail(ctx, PCR_ERR_ARG, "pcr_nn1_fetch");
     if (n == 0) return PCR_OK;
-    int rc = ensure_scratch(ctx, n * 8);
+    uint32_t* idx_dev;
+    float* d2_dev;
+    Layout L;
+    L.add(&idx_dev, n);
+    L.add(&d2_dev, n);
+    int rc = bind_scratch(ctx, L);
     if (rc) return rc;
-    uint32_t* idx_dev = (uint32_t*)ctx->scratch;
-    float* d2_dev = (float*)((char*)ctx->scratch + n * 4);
     rc = nn1_unpack(ctx, n, idx_dev, d2_dev);
     if (rc) return rc;
     PCR_HIP(ctx, hipMemcpyAsync(idx, idx_dev, n * 4, hipMemcpyDeviceToHost, ctx->stream));

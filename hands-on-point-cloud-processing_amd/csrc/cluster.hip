@@ -352,8 +352,6 @@ __global__ __launch_bounds__(CL_BLOCK) void sor_gather_kernel(const float* __res
     if (t < cap) { ox[t] = __builtin_inff(); oy[t] = 0.0f; oz[t] = 0.0f; }
 }
 
-inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 }  // namespace
 
 }  // namespace pcr
@@ -380,26 +378,28 @@ extern "C" int pcr_dbscan_f32(pcr_ctx* ctx, const pcr_cloud* cloud, double eps, 
         int rc = grid_build(ctx, cloud, &g, std::max(eps * 1.01, 2e-15));
         if (rc) return rc;
     }
-    if ((double)g->p.h < eps * 1.005) { grid_free(g); return fail(ctx, PCR_ERR_STATE, "pcr_dbscan_f32: grid cell smaller than eps"); }
-    const size_t a4 = al256(n * 4), a1 = al256(n);
-    const size_t nb = (n + SCAN_TILE - 1) / SCAN_TILE;
-    const size_t need = 9 * a4 + 2 * a1 + al256((nb + 2) * 4) + 256;
-    int rc = ensure_scratch(ctx, need);
-    if (rc) { grid_free(g); return rc; }
-    char* s = (char*)ctx->scratch;
-    uint32_t* cnt_sorted = (uint32_t*)s;  s += a4;
-    uint32_t* cnt_out = (uint32_t*)s;     s += a4;
-    uint32_t* parent = (uint32_t*)s;      s += a4;
-    uint32_t* root = (uint32_t*)s;        s += a4;
-    uint32_t* key = (uint32_t*)s;         s += a4;     // indexed by root record, value = original index
-    uint32_t* bkey = (uint32_t*)s;        s += a4;
-    uint32_t* flag = (uint32_t*)s;        s += a4;     // input numbering
-    uint32_t* ids = (uint32_t*)s;         s += a4;     // input numbering
-    int32_t* lab_out = (int32_t*)s;       s += a4;
-    uint8_t* core_sorted = (uint8_t*)s;   s += a1;
-    uint8_t* core_out = (uint8_t*)s;      s += a1;
-    uint32_t* totals = (uint32_t*)s;      s += al256((nb + 2) * 4);
-    uint32_t* err = (uint32_t*)s;
+    const GridPtr g_owner(g);
+    if ((double)g->p.h < eps * 1.005) return fail(ctx, PCR_ERR_STATE, "pcr_dbscan_f32: grid cell smaller than eps");
+    uint32_t *cnt_sorted, *cnt_out, *parent, *root, *key, *bkey, *flag, *ids, *totals, *n_ids, *err;
+    int32_t* lab_out;
+    uint8_t *core_sorted, *core_out;
+    Layout L;
+    L.add(&cnt_sorted, n);
+    L.add(&cnt_out, n);
+    L.add(&parent, n);
+    L.add(&root, n);
+    L.add(&key, n);          // indexed by root record, value = original index
+    L.add(&bkey, n);
+    L.add(&flag, n);         // input numbering
+    L.add(&ids, n);          // input numbering
+    L.add(&lab_out, n);
+    L.add(&core_sorted, n);
+    L.add(&core_out, n);
+    L.add(&totals, scan_blocks(n));
+    L.add(&n_ids, 1);        // the scan's grand total: the number of clusters
+    L.add(&err, 1);
+    int rc = bind_scratch(ctx, L);
+    if (rc) return rc;
     const dim3 grid1((unsigned)((n + CL_BLOCK - 1) / CL_BLOCK));
     hipError_t e = hipMemsetAsync(err, 0, 4, ctx->stream);
     const int G = (int)tune_get(ctx, "dbscan_lanes", 32);    // lanes per query, as iss_lanes
@@ -432,7 +432,7 @@ extern "C" int pcr_dbscan_f32(pcr_ctx* ctx, const pcr_cloud* cloud, double eps, 
         ProfScope ps(ctx, "dbscan_label", 1);
         hipLaunchKernelGGL(db_flag_kernel, grid1, dim3(CL_BLOCK), 0, ctx->stream, g->records, (uint32_t)n, core_sorted, root, key, flag);
         if (e == hipSuccess) e = hipGetLastError();
-        if (e == hipSuccess && exclusive_scan_u32(ctx, flag, ids, n, totals, totals + nb)) e = hipErrorUnknown;
+        if (e == hipSuccess && exclusive_scan_u32(ctx, flag, ids, n, totals, n_ids)) e = hipErrorUnknown;
         hipLaunchKernelGGL(db_label_kernel, grid1, dim3(CL_BLOCK), 0, ctx->stream, g->records, (uint32_t)n, core_sorted, root, key, bkey, ids, lab_out);
     }
     uint32_t words[2] = { 0, 0 };                           // error word, clusters
@@ -441,9 +441,8 @@ extern "C" int pcr_dbscan_f32(pcr_ctx* ctx, const pcr_cloud* cloud, double eps, 
     if (e == hipSuccess && is_core) e = hipMemcpyAsync(is_core, core_out, n, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess && neighbor_counts) e = hipMemcpyAsync(neighbor_counts, cnt_out, n * 4, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(&words[0], err, 4, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(&words[1], totals + nb, 4, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&words[1], n_ids, 4, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    grid_free(g);
     if (e != hipSuccess) return fail(ctx, PCR_ERR_HIP, "pcr_dbscan_f32", e);
     prof_flush(ctx);
     if (words[0]) return fail(ctx, PCR_ERR_STATE, "pcr_dbscan_f32: union-find bound exceeded (corrupt structure)");
@@ -480,20 +479,22 @@ extern "C" int pcr_statistical_outlier_f32(pcr_ctx* ctx, const pcr_cloud* cloud,
     }
     if (rc) return rc;
     const uint32_t nblk = (uint32_t)std::min<size_t>(SOR_MAX_BLOCKS, (n + CL_BLOCK - 1) / CL_BLOCK);    // a function of n only: fixed sum order
-    const size_t a8 = al256(n * 8), a4 = al256(n * 4), a1 = al256(n);
-    const size_t nb = (n + SCAN_TILE - 1) / SCAN_TILE;
-    rc = ensure_scratch(ctx, a8 + 2 * a4 + a1 + 3 * al256(SOR_MAX_BLOCKS * 8) + 256 + al256((nb + 2) * 4));
+    double *avg, *part_a, *part_b, *part_sq, *stats;
+    uint32_t *flag, *pos, *totals, *n_kept_dev;
+    uint8_t* keep_dev;
+    Layout L;
+    L.add(&avg, n);
+    L.add(&flag, n);
+    L.add(&pos, n);
+    L.add(&keep_dev, n);
+    L.add(&part_a, SOR_MAX_BLOCKS);
+    L.add(&part_b, SOR_MAX_BLOCKS);
+    L.add(&part_sq, SOR_MAX_BLOCKS);
+    L.add(&stats, 4);        // mean, std, threshold, valid count (sor_stats_kernel)
+    L.add(&totals, scan_blocks(n));
+    L.add(&n_kept_dev, 1);
+    rc = bind_scratch(ctx, L);
     if (rc) { hipFree(res); return rc; }
-    char* s = (char*)ctx->scratch;
-    double* avg = (double*)s;             s += a8;
-    uint32_t* flag = (uint32_t*)s;        s += a4;
-    uint32_t* pos = (uint32_t*)s;         s += a4;
-    uint8_t* keep_dev = (uint8_t*)s;      s += a1;
-    double* part_a = (double*)s;          s += al256(SOR_MAX_BLOCKS * 8);
-    double* part_b = (double*)s;          s += al256(SOR_MAX_BLOCKS * 8);
-    double* part_sq = (double*)s;         s += al256(SOR_MAX_BLOCKS * 8);
-    double* stats = (double*)s;           s += 256;
-    uint32_t* totals = (uint32_t*)s;
     const dim3 grid1((unsigned)((n + CL_BLOCK - 1) / CL_BLOCK));
     {
         ProfScope ps(ctx, "sor_stats", 1);
@@ -504,13 +505,13 @@ extern "C" int pcr_statistical_outlier_f32(pcr_ctx* ctx, const pcr_cloud* cloud,
         hipLaunchKernelGGL(sor_mask_kernel, grid1, dim3(CL_BLOCK), 0, ctx->stream, avg, (uint32_t)n, stats, keep_dev, flag);
     }
     hipError_t e = hipGetLastError();
-    if (e == hipSuccess && exclusive_scan_u32(ctx, flag, pos, n, totals, totals + nb)) e = hipErrorUnknown;
+    if (e == hipSuccess && exclusive_scan_u32(ctx, flag, pos, n, totals, n_kept_dev)) e = hipErrorUnknown;
     double st[4] = { 0, 0, 0, 0 };
     uint32_t kept = 0;
     if (e == hipSuccess && keep) e = hipMemcpyAsync(keep, keep_dev, n, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess && avg_dist) e = hipMemcpyAsync(avg_dist, avg, n * 8, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(st, stats, sizeof(st), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(&kept, totals + nb, 4, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&kept, n_kept_dev, 4, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     hipFree(res);
     if (e != hipSuccess) return fail(ctx, PCR_ERR_HIP, "pcr_statistical_outlier_f32", e);

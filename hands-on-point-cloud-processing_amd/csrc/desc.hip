@@ -119,13 +119,14 @@ __global__ void fill_keys_kernel(unsigned long long* keys, uint32_t m)
 int nn1_dim(pcr_ctx* ctx, const float* db, size_t n, const float* q, size_t m, int dim, uint32_t* idx, float* d2)
 {
     if (m == 0) return PCR_OK;
-    const size_t db_b = (std::max<size_t>(n, 1) * dim * 4 + 255) & ~(size_t)255, q_b = (m * dim * 4 + 255) & ~(size_t)255, k_b = (m * 8 + 255) & ~(size_t)255;
-    int rc = ensure_scratch(ctx, db_b + q_b + k_b);
+    float *ddb, *dq;
+    unsigned long long* keys;
+    Layout L;
+    L.add(&ddb, std::max<size_t>(n, 1) * dim);
+    L.add(&dq, m * dim);
+    L.add(&keys, m);
+    int rc = bind_scratch(ctx, L);
     if (rc) return rc;
-    char* s = (char*)ctx->scratch;
-    float* ddb = (float*)s;
-    float* dq = (float*)(s + db_b);
-    unsigned long long* keys = (unsigned long long*)(s + db_b + q_b);
     if (n) PCR_HIP(ctx, hipMemcpyAsync(ddb, db, n * dim * 4, hipMemcpyHostToDevice, ctx->stream));
     PCR_HIP(ctx, hipMemcpyAsync(dq, q, m * dim * 4, hipMemcpyHostToDevice, ctx->stream));
     hipLaunchKernelGGL(fill_keys_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, ctx->stream, keys, (uint32_t)m);
@@ -234,12 +235,9 @@ int check_pairs(pcr_ctx* ctx, const uint32_t* pairs, size_t n_pairs, size_t n_sr
     return PCR_OK;
 }
 
-// uploads the gathered correspondences; returns the device pointer (in scratch) and the offset of the free space after it
-int upload_pairs(pcr_ctx* ctx, const float* src_xyz, const float* tgt_xyz, const uint32_t* pairs, size_t n_pairs, size_t extra_bytes, PairXyz** dev, char** extra)
+// uploads the gathered correspondences to dev (n_pairs entries, in the caller's scratch layout)
+int upload_pairs(pcr_ctx* ctx, const float* src_xyz, const float* tgt_xyz, const uint32_t* pairs, size_t n_pairs, PairXyz* dev)
 {
-    const size_t pb = (std::max<size_t>(n_pairs, 1) * sizeof(PairXyz) + 255) & ~(size_t)255;
-    int rc = ensure_scratch(ctx, pb + extra_bytes);
-    if (rc) return rc;
     std::vector<PairXyz> host(n_pairs);
     for (size_t i = 0; i < n_pairs; i++) {
         for (int c = 0; c < 3; c++) {
@@ -248,10 +246,8 @@ int upload_pairs(pcr_ctx* ctx, const float* src_xyz, const float* tgt_xyz, const
         }
         host[i].pad[0] = host[i].pad[1] = 0.f;
     }
-    *dev = (PairXyz*)ctx->scratch;
-    *extra = (char*)ctx->scratch + pb;
     if (n_pairs) {
-        PCR_HIP(ctx, hipMemcpyAsync(*dev, host.data(), n_pairs * sizeof(PairXyz), hipMemcpyHostToDevice, ctx->stream));
+        PCR_HIP(ctx, hipMemcpyAsync(dev, host.data(), n_pairs * sizeof(PairXyz), hipMemcpyHostToDevice, ctx->stream));
         PCR_HIP(ctx, hipStreamSynchronize(ctx->stream));     // `host` dies at return
     }
     return PCR_OK;
@@ -402,14 +398,18 @@ int pcr_consensus_count_f32(pcr_ctx* ctx, const float* src_xyz, size_t n_src, co
     int rc = check_pairs(ctx, pairs, n_pairs, n_src, n_tgt);
     if (rc) return rc;
     PCR_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t rb = (n_hyp * 48 + 255) & ~(size_t)255, cb = (n_hyp * 4 + 255) & ~(size_t)255, ob = (n_hyp + 255) & ~(size_t)255;
-    PairXyz* dpairs = nullptr;
-    char* extra = nullptr;
-    rc = upload_pairs(ctx, src_xyz, tgt_xyz, pairs, n_pairs, rb + cb + ob, &dpairs, &extra);
+    PairXyz* dpairs;
+    float* dRt;
+    uint32_t* dcounts;
+    uint8_t* dok;
+    Layout L;
+    L.add(&dpairs, std::max<size_t>(n_pairs, 1));
+    L.add(&dRt, n_hyp * 12);
+    L.add(&dcounts, n_hyp);
+    L.add(&dok, n_hyp);
+    rc = bind_scratch(ctx, L);
+    if (rc == PCR_OK) rc = upload_pairs(ctx, src_xyz, tgt_xyz, pairs, n_pairs, dpairs);
     if (rc) return rc;
-    float* dRt = (float*)extra;
-    uint32_t* dcounts = (uint32_t*)(extra + rb);
-    uint8_t* dok = (uint8_t*)(extra + rb + cb);
     PCR_HIP(ctx, hipMemcpyAsync(dRt, Rt, n_hyp * 48, hipMemcpyHostToDevice, ctx->stream));
     PCR_HIP(ctx, hipMemsetAsync(dok, 1, n_hyp, ctx->stream));
     rc = launch_consensus(ctx, dpairs, n_pairs, dRt, dok, n_hyp, thr, dcounts);
@@ -433,15 +433,19 @@ int pcr_ransac_global_f32(pcr_ctx* ctx, const float* src_xyz, size_t n_src, cons
     for (size_t i = 0; i < 4 * n_hyp; i++)
         if (quads[i] >= n_pairs) return fail(ctx, PCR_ERR_ARG, "pcr_ransac_global_f32: quad index out of range");
     PCR_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t rb = (n_hyp * 48 + 255) & ~(size_t)255, cb = (n_hyp * 4 + 255) & ~(size_t)255, ob = (n_hyp + 255) & ~(size_t)255, qb = (n_hyp * 16 + 255) & ~(size_t)255;
-    PairXyz* dpairs = nullptr;
-    char* extra = nullptr;
-    rc = upload_pairs(ctx, src_xyz, tgt_xyz, pairs, n_pairs, rb + cb + ob + qb, &dpairs, &extra);
+    PairXyz* dpairs;
+    float* dRt;
+    uint32_t *dcounts, *dquads;
+    uint8_t* dok;
+    Layout L;
+    L.add(&dpairs, std::max<size_t>(n_pairs, 1));
+    L.add(&dRt, n_hyp * 12);
+    L.add(&dcounts, n_hyp);
+    L.add(&dok, n_hyp);
+    L.add(&dquads, n_hyp * 4);
+    rc = bind_scratch(ctx, L);
+    if (rc == PCR_OK) rc = upload_pairs(ctx, src_xyz, tgt_xyz, pairs, n_pairs, dpairs);
     if (rc) return rc;
-    float* dRt = (float*)extra;
-    uint32_t* dcounts = (uint32_t*)(extra + rb);
-    uint8_t* dok = (uint8_t*)(extra + rb + cb);
-    uint32_t* dquads = (uint32_t*)(extra + rb + cb + ob);
     PCR_HIP(ctx, hipMemcpyAsync(dquads, quads, n_hyp * 16, hipMemcpyHostToDevice, ctx->stream));
     {
         ProfScope ps(ctx, "ransac_hypotheses", 1);

@@ -215,16 +215,17 @@ extern "C" int pcr_fpfh33_f32(pcr_ctx* ctx, const pcr_cloud* surface, const pcr_
         int rc = grid_build(ctx, surface, &g, std::max((double)radius * 1.01, 2e-15));
         if (rc) return rc;
     }
-    if ((double)g->p.h < (double)radius * 1.005) { grid_free(g); return fail(ctx, PCR_ERR_STATE, "pcr_fpfh33_f32: grid cell smaller than the radius"); }
-    const size_t a_n33 = (n * FPFH_DIM * 4 + 255) & ~(size_t)255, a_m33 = (m * FPFH_DIM * 4 + 255) & ~(size_t)255;
-    const size_t a_m = (m * 4 + 255) & ~(size_t)255;
-    int rc = ensure_scratch(ctx, a_n33 * (spfh ? 2 : 1) + a_m33 + a_m);
-    if (rc) { grid_free(g); return rc; }
-    char* sp = (char*)ctx->scratch;
-    float* spfh_sorted = (float*)sp;
-    float* fpfh_dev = (float*)(sp + a_n33);
-    uint32_t* cnt_dev = (uint32_t*)(sp + a_n33 + a_m33);
-    float* spfh_dev = spfh ? (float*)(sp + a_n33 + a_m33 + a_m) : nullptr;
+    const GridPtr g_owner(g);
+    if ((double)g->p.h < (double)radius * 1.005) return fail(ctx, PCR_ERR_STATE, "pcr_fpfh33_f32: grid cell smaller than the radius");
+    float *spfh_sorted, *fpfh_dev, *spfh_dev = nullptr;
+    uint32_t* cnt_dev;
+    Layout L;
+    L.add(&spfh_sorted, n * FPFH_DIM);
+    L.add(&fpfh_dev, m * FPFH_DIM);
+    L.add(&cnt_dev, m);
+    if (spfh) L.add(&spfh_dev, n * FPFH_DIM);
+    int rc = bind_scratch(ctx, L);
+    if (rc) return rc;
     const float4* qrec = keypoints ? nullptr : g->records;
     const float* kx = keypoints ? keypoints->x() : nullptr;
     const float* ky = keypoints ? keypoints->y() : nullptr;
@@ -253,7 +254,6 @@ extern "C" int pcr_fpfh33_f32(pcr_ctx* ctx, const pcr_cloud* surface, const pcr_
     if (e == hipSuccess && neighbor_counts) e = hipMemcpyAsync(neighbor_counts, cnt_dev, m * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess && spfh) e = hipMemcpyAsync(spfh, spfh_dev, n * FPFH_DIM * sizeof(float), hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    grid_free(g);
     if (e != hipSuccess) return fail(ctx, PCR_ERR_HIP, "pcr_fpfh33_f32", e);
     prof_flush(ctx);
     return PCR_OK;

@@ -1167,18 +1167,19 @@ int grid_build(pcr_ctx* ctx, const pcr_cloud* c, Grid** out, double cell_edge, i
     if (n > 0x7FFFFFF0ull) return fail(ctx, PCR_ERR_ARG, "grid index: more than 2^31 points");
     Grid* g = new (std::nothrow) Grid();
     if (!g) return fail(ctx, PCR_ERR_NOMEM, "grid");
+    GridPtr g_owner(g);                                             // grid_free takes a partially built grid
     g->n_points = n;
     // 1. bounding box of the finite points
     const uint32_t bb_blocks = (uint32_t)std::min<size_t>(256, (n + GR_BLOCK - 1) / GR_BLOCK ? (n + GR_BLOCK - 1) / GR_BLOCK : 1);
     int rc = ensure_scratch(ctx, bb_blocks * 6 * sizeof(float));
-    if (rc) { delete g; return rc; }
+    if (rc) return rc;
     float lo[3] = { 0, 0, 0 }, hi[3] = { 0, 0, 0 };
     if (n) {
         hipLaunchKernelGGL(bbox_kernel, dim3(bb_blocks), dim3(GR_BLOCK), 0, ctx->stream, c->x(), c->y(), c->z(), (uint32_t)n, (float*)ctx->scratch);
         std::vector<float> hb(bb_blocks * 6);
         hipError_t e = hipMemcpyAsync(hb.data(), ctx->scratch, hb.size() * sizeof(float), hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) { delete g; return fail(ctx, PCR_ERR_HIP, "bbox", e); }
+        if (e != hipSuccess) return fail(ctx, PCR_ERR_HIP, "bbox", e);
         for (int k = 0; k < 3; k++) { lo[k] = FLT_MAX; hi[k] = -FLT_MAX; }
         for (uint32_t b = 0; b < bb_blocks; b++)
             for (int k = 0; k < 3; k++) { lo[k] = std::min(lo[k], hb[b * 6 + k]); hi[k] = std::max(hi[k], hb[b * 6 + 3 + k]); }
@@ -1218,21 +1219,22 @@ int grid_build(pcr_ctx* ctx, const pcr_cloud* c, Grid** out, double cell_edge, i
     set_params(h);
     if (user_um <= 0 && n >= 1024) {
         const size_t cells0 = g->n_cells;
-        const size_t off_count0 = ((n * 4 + 255) & ~(size_t)255);
-        rc = ensure_scratch(ctx, off_count0 + (cells0 + 1) * 4 + 512);
-        if (rc) { delete g; return rc; }
-        uint32_t* cell_of0 = (uint32_t*)ctx->scratch;
-        uint32_t* count0 = (uint32_t*)((char*)ctx->scratch + off_count0);
-        uint32_t* nz = count0 + cells0 + 1;
-        hipError_t e0 = hipMemsetAsync(count0, 0, (cells0 + 2) * 4, ctx->stream);
-        if (e0 != hipSuccess) { delete g; return fail(ctx, PCR_ERR_HIP, "memset(grid)", e0); }
+        uint32_t *cell_of0, *count0, *nz;
+        Layout L0;                                                  // the occupancy pre-pass; the final build lays the scratch out anew below
+        L0.add(&cell_of0, n);
+        L0.add(&count0, cells0 + 1);
+        L0.add(&nz, 1);                                             // (directly behind count0: one memset clears both)
+        rc = bind_scratch(ctx, L0);
+        if (rc) return rc;
+        hipError_t e0 = hipMemsetAsync(count0, 0, (char*)(nz + 1) - (char*)count0, ctx->stream);
+        if (e0 != hipSuccess) return fail(ctx, PCR_ERR_HIP, "memset(grid)", e0);
         hipLaunchKernelGGL(cell_count_kernel, dim3((unsigned)((n + GR_BLOCK - 1) / GR_BLOCK)), dim3(GR_BLOCK), 0, ctx->stream,
                            c->x(), c->y(), c->z(), (uint32_t)n, g->p, cell_of0, count0, 0u);
         hipLaunchKernelGGL(count_nonzero_kernel, dim3(256), dim3(GR_BLOCK), 0, ctx->stream, count0, (uint32_t)cells0, nz);
         uint32_t occupied = 0;
         e0 = hipMemcpyAsync(&occupied, nz, 4, hipMemcpyDeviceToHost, ctx->stream);
         if (e0 == hipSuccess) e0 = hipStreamSynchronize(ctx->stream);
-        if (e0 != hipSuccess) { delete g; return fail(ctx, PCR_ERR_HIP, "grid occupancy", e0); }
+        if (e0 != hipSuccess) return fail(ctx, PCR_ERR_HIP, "grid occupancy", e0);
         const double occ = (double)n / (double)std::max<uint32_t>(occupied, 1);
         const double want = (double)tune_get(ctx, "grid_occupancy_x10", 20) / 10.0;
         if (occ > 1.5 * want) {
@@ -1254,45 +1256,46 @@ int grid_build(pcr_ctx* ctx, const pcr_cloud* c, Grid** out, double cell_edge, i
     // 3. sort by (cell, x).  Histogram + scan give cell_start; one radix sort of (cell << 32 | x bits, index) gives the
     //    order (deterministic: no atomics decide a position).  Non-finite points go to the extra cell `cells`.
     const size_t ncell = cells + 2;                                  // real cells, the non-finite cell, the end sentinel
-    const size_t nb = (ncell + SC_TILE - 1) / SC_TILE;
     int key_bits = 1;
     while (((size_t)1 << key_bits) < cells + 1) key_bits++;
     size_t temp_bytes = 0;
     sort_pairs_u64_u32(nullptr, temp_bytes, nullptr, nullptr, nullptr, nullptr, n, 0, 32 + key_bits, ctx->stream);
-    const size_t a4 = (n * 4 + 255) & ~(size_t)255, a8 = (n * 8 + 255) & ~(size_t)255;
-    const size_t off_count = a4, off_tot = off_count + ((ncell * 4 + 255) & ~(size_t)255), off_kin = off_tot + (((nb + 2) * 4 + 255) & ~(size_t)255),
-                 off_kout = off_kin + a8, off_vin = off_kout + a8, off_vout = off_vin + a4, off_temp = off_vout + a4;
-    rc = ensure_scratch(ctx, off_temp + temp_bytes + 256);
-    if (rc) { delete g; return rc; }
-    char* sc = (char*)ctx->scratch;
-    uint32_t* cell_of = (uint32_t*)sc;
-    uint32_t* count = (uint32_t*)(sc + off_count);
-    uint32_t* totals = (uint32_t*)(sc + off_tot);
-    unsigned long long* k_in = (unsigned long long*)(sc + off_kin);
-    unsigned long long* k_out = (unsigned long long*)(sc + off_kout);
-    uint32_t* v_in = (uint32_t*)(sc + off_vin);
-    uint32_t* v_out = (uint32_t*)(sc + off_vout);
+    uint32_t *cell_of, *count, *totals, *grand, *nzf, *v_in, *v_out;
+    unsigned long long *k_in, *k_out;
+    void* sort_temp;
+    Layout L;
+    L.add(&cell_of, n);
+    L.add(&count, ncell);
+    L.add(&totals, scan_blocks(ncell));
+    L.add(&grand, 1);
+    L.add(&nzf, 1);                                                 // occupied cells of the final grid
+    L.add(&k_in, n);
+    L.add(&k_out, n);
+    L.add(&v_in, n);
+    L.add(&v_out, n);
+    L.add(&sort_temp, temp_bytes);
+    rc = bind_scratch(ctx, L);
+    if (rc) return rc;
     hipError_t e = hipMalloc((void**)&g->cell_start, ncell * sizeof(uint32_t));
     const size_t n_padded = (n + GRID_CHUNK - 1) / GRID_CHUNK * GRID_CHUNK;
     if (e == hipSuccess) e = hipMalloc((void**)&g->records, std::max<size_t>(n_padded, GRID_CHUNK) * sizeof(float4));
-    if (e != hipSuccess) { grid_free(g); return fail(ctx, PCR_ERR_HIP, "hipMalloc(grid)", e); }
+    if (e != hipSuccess) return fail(ctx, PCR_ERR_HIP, "hipMalloc(grid)", e);
     e = hipMemsetAsync(count, 0, ncell * 4, ctx->stream);
-    if (e != hipSuccess) { grid_free(g); return fail(ctx, PCR_ERR_HIP, "memset(grid)", e); }
+    if (e != hipSuccess) return fail(ctx, PCR_ERR_HIP, "memset(grid)", e);
     const dim3 gridn((unsigned)((n + GR_BLOCK - 1) / GR_BLOCK));
     if (n) hipLaunchKernelGGL(cell_count_kernel, gridn, dim3(GR_BLOCK), 0, ctx->stream, c->x(), c->y(), c->z(), (uint32_t)n, g->p, cell_of, count, (uint32_t)cells);
-    rc = exclusive_scan_u32(ctx, count, g->cell_start, ncell, totals, totals + nb);
-    if (rc) { grid_free(g); return rc; }
+    rc = exclusive_scan_u32(ctx, count, g->cell_start, ncell, totals, grand);
+    if (rc) return rc;
     if (n) {
         // occupied cells of the final grid (the tile search compares the working cloud's density with the target's: launch_nn1_grid).
-        // totals[nb + 1] is a free word of the scan's workspace; the value reaches the host with the next synchronisation.
-        uint32_t* nzf = totals + nb + 1;
+        // The value reaches the host with the next synchronisation.
         e = hipMemsetAsync(nzf, 0, 4, ctx->stream);
         if (e == hipSuccess) {
             hipLaunchKernelGGL(count_nonzero_kernel, dim3(256), dim3(GR_BLOCK), 0, ctx->stream, count, (uint32_t)cells, nzf);
             g->occupied = 0;
             e = pin_word_begin(ctx, 1, nzf, &g->occupied_tag);
         }
-        if (e != hipSuccess) { grid_free(g); return fail(ctx, PCR_ERR_HIP, "grid occupancy", e); }
+        if (e != hipSuccess) return fail(ctx, PCR_ERR_HIP, "grid occupancy", e);
     }
     if (n) {
         g->x_sorted = order != GRID_ORDER_MORTON;
@@ -1300,8 +1303,8 @@ int grid_build(pcr_ctx* ctx, const pcr_cloud* c, Grid** out, double cell_edge, i
             hipLaunchKernelGGL(record_keys_kernel<false>, gridn, dim3(GR_BLOCK), 0, ctx->stream, c->x(), c->y(), c->z(), (uint32_t)n, g->p, cell_of, k_in, v_in);
         else
             hipLaunchKernelGGL(record_keys_kernel<true>, gridn, dim3(GR_BLOCK), 0, ctx->stream, c->x(), c->y(), c->z(), (uint32_t)n, g->p, cell_of, k_in, v_in);
-        e = sort_pairs_u64_u32(sc + off_temp, temp_bytes, k_in, k_out, v_in, v_out, n, 0, 32 + key_bits, ctx->stream);
-        if (e != hipSuccess) { grid_free(g); return fail(ctx, PCR_ERR_HIP, "radix sort(grid)", e); }
+        e = sort_pairs_u64_u32(sort_temp, temp_bytes, k_in, k_out, v_in, v_out, n, 0, 32 + key_bits, ctx->stream);
+        if (e != hipSuccess) return fail(ctx, PCR_ERR_HIP, "radix sort(grid)", e);
         hipLaunchKernelGGL(gather_records_kernel, dim3((unsigned)((n_padded + GR_BLOCK - 1) / GR_BLOCK)), dim3(GR_BLOCK), 0, ctx->stream, c->x(), c->y(), c->z(),
                            (uint32_t)n, (uint32_t)n_padded, v_out, g->records);
     }
@@ -1311,23 +1314,23 @@ int grid_build(pcr_ctx* ctx, const pcr_cloud* c, Grid** out, double cell_edge, i
     int unsafe_host = 1;
     if (g->n_chunks) {
         e = hipMalloc((void**)&g->chunks, g->n_chunks * GRID_CHUNK_FLOATS * sizeof(float));
-        if (e != hipSuccess) { grid_free(g); return fail(ctx, PCR_ERR_HIP, "hipMalloc(grid chunks)", e); }
+        if (e != hipSuccess) return fail(ctx, PCR_ERR_HIP, "hipMalloc(grid chunks)", e);
         e = hipMemsetAsync(unsafe_dev, 0, 4, ctx->stream);
-        if (e != hipSuccess) { grid_free(g); return fail(ctx, PCR_ERR_HIP, "memset(grid)", e); }
+        if (e != hipSuccess) return fail(ctx, PCR_ERR_HIP, "memset(grid)", e);
         hipLaunchKernelGGL(build_chunks_kernel, dim3((unsigned)((g->n_chunks + GR_BLOCK - 1) / GR_BLOCK)), dim3(GR_BLOCK), 0, ctx->stream, g->records, (uint32_t)n,
                            (uint32_t)g->n_chunks, g->chunks, unsafe_dev);
         e = hipMalloc((void**)&g->spheres, g->n_chunks * sizeof(float4));
-        if (e != hipSuccess) { grid_free(g); return fail(ctx, PCR_ERR_HIP, "hipMalloc(grid spheres)", e); }
+        if (e != hipSuccess) return fail(ctx, PCR_ERR_HIP, "hipMalloc(grid spheres)", e);
         hipLaunchKernelGGL(build_spheres_kernel, dim3((unsigned)((g->n_chunks + GR_BLOCK - 1) / GR_BLOCK)), dim3(GR_BLOCK), 0, ctx->stream, g->records,
                            (uint32_t)g->n_chunks, g->spheres);
         e = hipMemcpyAsync(&unsafe_host, unsafe_dev, 4, hipMemcpyDeviceToHost, ctx->stream);
-        if (e != hipSuccess) { grid_free(g); return fail(ctx, PCR_ERR_HIP, "grid chunks", e); }
+        if (e != hipSuccess) return fail(ctx, PCR_ERR_HIP, "grid chunks", e);
     }
     e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);   // the scratch is reused by the caller right away
-    if (e != hipSuccess) { grid_free(g); return fail(ctx, PCR_ERR_HIP, "grid build", e); }
+    if (e != hipSuccess) return fail(ctx, PCR_ERR_HIP, "grid build", e);
     g->chunk_safe = g->n_chunks != 0 && unsafe_host == 0;
-    *out = g;
+    *out = g_owner.release();
     return PCR_OK;
 }
 
@@ -1350,11 +1353,14 @@ static int sort_queries(pcr_ctx* ctx, const Grid* g, const pcr_cloud* src)
     size_t cells = 1;
     for (int k = 0; k < 3; k++) { cp.n[k] = (g->p.n[k] + f - 1) / f + 1; cells *= (size_t)cp.n[k]; }
     const size_t n = src->n;
-    const size_t nb = (cells + 1 + SC_TILE - 1) / SC_TILE;
-    const size_t off_count = ((n * 4 + 255) & ~(size_t)255);
-    const size_t off_start = off_count + (((cells + 1) * 4 + 255) & ~(size_t)255);
-    const size_t off_tot = off_start + (((cells + 1) * 4 + 255) & ~(size_t)255);
-    int rc = ensure_scratch(ctx, off_tot + (nb + 2) * 4 + 256);
+    uint32_t *cell_of, *count, *start, *totals, *grand;
+    Layout L;
+    L.add(&cell_of, n);
+    L.add(&count, cells + 1);
+    L.add(&start, cells + 1);
+    L.add(&totals, scan_blocks(cells + 1));
+    L.add(&grand, 1);
+    int rc = bind_scratch(ctx, L);
     if (rc) return rc;
     if (ctx->qperm_cap < n) {
         if (ctx->qperm) PCR_HIP(ctx, hipFree(ctx->qperm));
@@ -1362,14 +1368,10 @@ static int sort_queries(pcr_ctx* ctx, const Grid* g, const pcr_cloud* src)
         PCR_HIP(ctx, hipMalloc((void**)&ctx->qperm, padded(n) * sizeof(uint32_t)));
         ctx->qperm_cap = padded(n);
     }
-    uint32_t* cell_of = (uint32_t*)ctx->scratch;
-    uint32_t* count = (uint32_t*)((char*)ctx->scratch + off_count);
-    uint32_t* start = (uint32_t*)((char*)ctx->scratch + off_start);
-    uint32_t* totals = (uint32_t*)((char*)ctx->scratch + off_tot);
     PCR_HIP(ctx, hipMemsetAsync(count, 0, (cells + 1) * 4, ctx->stream));
     const dim3 gridn((unsigned)((n + GR_BLOCK - 1) / GR_BLOCK));
     hipLaunchKernelGGL(cell_count_kernel, gridn, dim3(GR_BLOCK), 0, ctx->stream, src->x(), src->y(), src->z(), (uint32_t)n, cp, cell_of, count, 0u);
-    rc = exclusive_scan_u32(ctx, count, start, cells + 1, totals, totals + nb);
+    rc = exclusive_scan_u32(ctx, count, start, cells + 1, totals, grand);
     if (rc) return rc;
     PCR_HIP(ctx, hipMemsetAsync(count, 0, (cells + 1) * 4, ctx->stream));
     hipLaunchKernelGGL(scatter_perm_kernel, gridn, dim3(GR_BLOCK), 0, ctx->stream, (uint32_t)n, cell_of, start, count, ctx->qperm);
@@ -1431,8 +1433,15 @@ static int sort_queries_fine(pcr_ctx* ctx, const Grid* g, const pcr_cloud* src)
     const int begin_bit = tile_possible ? 0 : QKEY_SUB_BITS - 12;
     size_t temp_bytes = 0;
     sort_pairs_u64_u32(nullptr, temp_bytes, nullptr, nullptr, nullptr, nullptr, n, begin_bit, key_bits + QKEY_SUB_BITS, ctx->stream);
-    const size_t a4 = (n * 4 + 255) & ~(size_t)255, a8 = (n * 8 + 255) & ~(size_t)255;
-    int rc = ensure_scratch(ctx, 2 * a8 + a4 + temp_bytes + 256);
+    unsigned long long *k_in, *k_out;
+    uint32_t* v_in;
+    void* sort_temp;
+    Layout L;
+    L.add(&k_in, n);
+    L.add(&k_out, n);
+    L.add(&v_in, n);
+    L.add(&sort_temp, temp_bytes);
+    int rc = bind_scratch(ctx, L);
     if (rc) return rc;
     if (ctx->qperm_cap < n) {
         if (ctx->qperm) PCR_HIP(ctx, hipFree(ctx->qperm));
@@ -1440,13 +1449,9 @@ static int sort_queries_fine(pcr_ctx* ctx, const Grid* g, const pcr_cloud* src)
         PCR_HIP(ctx, hipMalloc((void**)&ctx->qperm, padded(n) * sizeof(uint32_t)));
         ctx->qperm_cap = padded(n);
     }
-    char* sc = (char*)ctx->scratch;
-    unsigned long long* k_in = (unsigned long long*)sc;
-    unsigned long long* k_out = (unsigned long long*)(sc + a8);
-    uint32_t* v_in = (uint32_t*)(sc + 2 * a8);
     hipLaunchKernelGGL(query_keys_kernel, dim3((unsigned)((n + GR_BLOCK - 1) / GR_BLOCK)), dim3(GR_BLOCK), 0, ctx->stream, src->x(), src->y(), src->z(), (uint32_t)n,
                        g->p, (uint32_t)g->n_cells, k_in, v_in);
-    hipError_t e = sort_pairs_u64_u32(sc + 2 * a8 + a4, temp_bytes, k_in, k_out, v_in, ctx->qperm, n, begin_bit, key_bits + QKEY_SUB_BITS, ctx->stream);
+    hipError_t e = sort_pairs_u64_u32(sort_temp, temp_bytes, k_in, k_out, v_in, ctx->qperm, n, begin_bit, key_bits + QKEY_SUB_BITS, ctx->stream);
     if (e != hipSuccess) return fail(ctx, PCR_ERR_HIP, "radix sort(queries)", e);
     PCR_HIP(ctx, hipGetLastError());
     // how many cells of the target's grid the queries occupy (-> pinned word 0, read with the caller's next synchronisation; the sort's
@@ -1796,15 +1801,18 @@ int bt_ensure_l1(pcr_ctx* ctx, const pcr_cloud* tgt)
     if (bt->l1_block) return PCR_OK;
     const size_t n_pad = bt->n_tiles * 32, n_l1 = (n_pad + BT_L1_SUPER - 1) / BT_L1_SUPER, n_l1_tiles = n_l1 * (BT_L1_SUPER / 512);
     const size_t n_l0 = (n_pad + BT_L0_SUPER - 1) / BT_L0_SUPER, n_l0_tiles = n_l0 * (BT_L0_SUPER / 512 / 32);
-    const size_t off_ops = (n_l1 * sizeof(float4) + 255) & ~(size_t)255, off_rec = off_ops + n_l1_tiles * 64 * sizeof(uint4),
-                 off_c0 = off_rec + bt->n_tiles * 64 * sizeof(uint4), off_ops0 = (off_c0 + n_l0 * sizeof(float4) + 255) & ~(size_t)255,
-                 off_flag = off_ops0 + n_l0_tiles * 64 * sizeof(uint4), total = off_flag + 256;
-    char* blk = nullptr;
-    hipError_t e = hipMalloc((void**)&blk, total);
+    Layout L;                                                      // (the operand rows are whole multiples of 256 B: no padding between them)
+    L.add(&bt->l1_centres, n_l1);
+    L.add(&bt->l1_ops, n_l1_tiles * 64);
+    L.add(&bt->l1_rec_ops, bt->n_tiles * 64);
+    L.add(&bt->l0_centres, n_l0);
+    L.add(&bt->l0_ops, n_l0_tiles * 64);
+    L.add(&bt->l1_bad, 1);
+    void* blk = nullptr;
+    hipError_t e = hipMalloc(&blk, L.bytes());
     if (e != hipSuccess) return fail(ctx, PCR_ERR_HIP, "hipMalloc(level-1 operands)", e);
-    bt->l1_block = blk; bt->l1_centres = (float4*)blk; bt->l1_ops = (uint4*)(blk + off_ops); bt->l1_rec_ops = (uint4*)(blk + off_rec);
-    bt->l0_centres = (float4*)(blk + off_c0); bt->l0_ops = (uint4*)(blk + off_ops0); bt->n_l0_super = n_l0;
-    bt->l1_bad = (int*)(blk + off_flag); bt->n_l1_super = n_l1;
+    L.bind(blk);
+    bt->l1_block = (char*)blk; bt->n_l0_super = n_l0; bt->n_l1_super = n_l1;
     e = hipMemsetAsync(bt->l1_bad, 0, sizeof(int), ctx->stream);
     if (e != hipSuccess) return fail(ctx, PCR_ERR_HIP, "level-1 operands", e);
     hipLaunchKernelGGL(bt_l1_centres_kernel, dim3((unsigned)n_l1), dim3(GR_BLOCK), 0, ctx->stream, bt->records, (uint32_t)n_pad, (uint32_t)n_l1, bt->l1_centres, bt->l1_bad);
@@ -1907,24 +1915,29 @@ int bt_ensure_tile(pcr_ctx* ctx, const pcr_cloud* tgt)
     // grid_stile_cbits 6 .. 9 (measured at 10 M points: 8 bits 2.05 ms per converged search, 9 bits 1.90: a pass tests a third of the tiles)
     const int cbits = (int)std::min<int64_t>(9, std::max<int64_t>(6, tune_get(ctx, "grid_stile_cbits", 9)));
     const size_t n_cells = (size_t)1 << (3 * cbits);
-    const size_t off_sph = ((n_cells + 2) * sizeof(uint32_t) + 255) & ~(size_t)255, off_gob = off_sph + ((n_tiles * sizeof(float4) + 255) & ~(size_t)255),
-                 off_bog = off_gob + ((n_pad * sizeof(uint32_t) + 255) & ~(size_t)255),
-                 total = off_bog + ((g->n_chunks * GRID_CHUNK * sizeof(uint32_t) + 255) & ~(size_t)255);
-    const size_t scan_blocks = (n_cells + 2 + SC_TILE - 1) / SC_TILE;
-    int rc = ensure_scratch(ctx, std::max(n * sizeof(uint32_t), (scan_blocks + 1) * sizeof(uint32_t)) + 256);
+    uint32_t *totals, *grand;
+    Layout Ls;                                                     // scratch of the scan; gpos (n words) overlays it afterwards
+    Ls.add(&totals, scan_blocks(n_cells + 2));
+    Ls.add(&grand, 1);
+    int rc = ensure_scratch(ctx, std::max(Ls.bytes(), n * sizeof(uint32_t)));
     if (rc) return rc;
-    char* blk = nullptr;
-    hipError_t e = hipMalloc((void**)&blk, total);
+    Ls.bind(ctx->scratch);
+    Layout L;
+    L.add(&bt->cell_start, n_cells + 2);
+    L.add(&bt->tile_spheres, n_tiles);
+    L.add(&bt->g_of_b, n_pad);
+    L.add(&bt->b_of_g, g->n_chunks * GRID_CHUNK);
+    void* blk = nullptr;
+    hipError_t e = hipMalloc(&blk, L.bytes());
     if (e != hipSuccess) return fail(ctx, PCR_ERR_HIP, "hipMalloc(tile extras)", e);
-    bt->tile_block = blk;
-    bt->cell_start = (uint32_t*)blk; bt->tile_spheres = (float4*)(blk + off_sph); bt->g_of_b = (uint32_t*)(blk + off_gob); bt->b_of_g = (uint32_t*)(blk + off_bog);
+    L.bind(blk);
+    bt->tile_block = (char*)blk;
     bt->cbits = cbits;
     e = hipMemsetAsync(bt->cell_start, 0, (n_cells + 2) * sizeof(uint32_t), ctx->stream);
     if (e != hipSuccess) return fail(ctx, PCR_ERR_HIP, "tile extras", e);
     hipLaunchKernelGGL(bt_cell_count_kernel, dim3((unsigned)((n_pad + GR_BLOCK - 1) / GR_BLOCK)), dim3(GR_BLOCK), 0, ctx->stream, bt->records, (uint32_t)n_pad,
                        bt->key_lo[0], bt->key_lo[1], bt->key_lo[2], bt->key_inv, 3 * (10 - cbits), bt->cell_start);
-    uint32_t* totals = (uint32_t*)ctx->scratch;
-    rc = exclusive_scan_u32(ctx, bt->cell_start, bt->cell_start, n_cells + 2, totals, totals + scan_blocks);
+    rc = exclusive_scan_u32(ctx, bt->cell_start, bt->cell_start, n_cells + 2, totals, grand);
     if (rc) return rc;
     uint32_t* gpos = (uint32_t*)ctx->scratch;                 // (stream order: the scan is done with the scratch before the scatter writes it)
     hipLaunchKernelGGL(bt_tile_spheres_kernel, dim3((unsigned)((n_tiles + GR_BLOCK - 1) / GR_BLOCK)), dim3(GR_BLOCK), 0, ctx->stream, bt->records, (uint32_t)n_tiles,
@@ -1950,12 +1963,18 @@ int bt_ensure(pcr_ctx* ctx, const pcr_cloud* tgt)
     const size_t n = tgt->n;
     BtIndex* bt = new (std::nothrow) BtIndex();
     if (!bt) return fail(ctx, PCR_ERR_NOMEM, "btiles");
-    if (n == 0 || n > 0x7FFFFFF0ull) { const_cast<pcr_cloud*>(tgt)->bt = bt; return PCR_OK; }       // safe = false: the other kernels answer
+    BtPtr bt_owner(bt);
+    if (n == 0 || n > 0x7FFFFFF0ull) { const_cast<pcr_cloud*>(tgt)->bt = bt_owner.release(); return PCR_OK; }       // safe = false: the other kernels answer
     const size_t n_super = (n + BT_SUPER - 1) / BT_SUPER, n_pad = n_super * BT_SUPER, n_tiles = n_pad / 32;
     const uint32_t bb_blocks = (uint32_t)std::min<size_t>(256, (n + GR_BLOCK - 1) / GR_BLOCK);
-    const size_t off_cen = n_pad * sizeof(float4), off_ops = off_cen + ((n_super * sizeof(float4) + 255) & ~(size_t)255),
-                 off_o16 = off_ops + n_tiles * 128 * sizeof(uint4), off_bb = off_o16 + n_tiles * 64 * sizeof(uint4),
-                 off_flag = off_bb + ((bb_blocks * 6 * sizeof(float) + 255) & ~(size_t)255), total = off_flag + 256;
+    float* bb_dev;
+    Layout L;                                                      // (records and operand rows are whole multiples of 256 B: no padding between them)
+    L.add(&bt->records, n_pad);
+    L.add(&bt->centres, n_super);
+    L.add(&bt->ops, n_tiles * 128);
+    L.add(&bt->ops16, n_tiles * 64);
+    L.add(&bb_dev, (size_t)bb_blocks * 6);
+    L.add(&bt->bad16, 1);
     // order inside a lattice cell: arrival order below 1 M points (a cell holds a few points at most), a 6-bit-per-axis Morton code of
     // the position inside the cell from there on (tune bt_fine_bits: 0 auto, 1 .. 7 bits, -1 none)
     int64_t fb_tune = tune_get(ctx, "bt_fine_bits", 0);
@@ -1963,24 +1982,30 @@ int bt_ensure(pcr_ctx* ctx, const pcr_cloud* tgt)
     const int key_bits = 31 + 3 * fine_bits;
     size_t temp_bytes = 0;
     sort_pairs_u64_u32(nullptr, temp_bytes, nullptr, nullptr, nullptr, nullptr, n, 0, key_bits, ctx->stream);
-    const size_t a4 = (n * 4 + 255) & ~(size_t)255, a8 = (n * 8 + 255) & ~(size_t)255;
-    int rc = ensure_scratch(ctx, 2 * a8 + 2 * a4 + temp_bytes + 256);
-    if (rc) { delete bt; return rc; }
-    char* blk = nullptr;
-    hipError_t e = hipMalloc((void**)&blk, total);
-    if (e != hipSuccess) { delete bt; return fail(ctx, PCR_ERR_HIP, "hipMalloc(btiles)", e); }
-    bt->block = blk;
-    bt->records = (float4*)blk; bt->centres = (float4*)(blk + off_cen); bt->ops = (uint4*)(blk + off_ops);
-    bt->ops16 = (uint4*)(blk + off_o16); bt->bad16 = (int*)(blk + off_flag);
+    unsigned long long *k_in, *k_out;
+    uint32_t *v_in, *v_out;
+    void* sort_temp;
+    Layout Ls;
+    Ls.add(&k_in, n);
+    Ls.add(&k_out, n);
+    Ls.add(&v_in, n);
+    Ls.add(&v_out, n);
+    Ls.add(&sort_temp, temp_bytes);
+    int rc = bind_scratch(ctx, Ls);
+    if (rc) return rc;
+    void* blk = nullptr;
+    hipError_t e = hipMalloc(&blk, L.bytes());
+    if (e != hipSuccess) return fail(ctx, PCR_ERR_HIP, "hipMalloc(btiles)", e);
+    L.bind(blk);
+    bt->block = (char*)blk;
     e = hipMemsetAsync(bt->bad16, 0, sizeof(int), ctx->stream);
-    if (e != hipSuccess) { bt_free(bt); return fail(ctx, PCR_ERR_HIP, "btiles", e); }
-    float* bb_dev = (float*)(blk + off_bb);
+    if (e != hipSuccess) return fail(ctx, PCR_ERR_HIP, "btiles", e);
     // the one host round trip: the bounding box of the finite points
     hipLaunchKernelGGL(bbox_kernel, dim3(bb_blocks), dim3(GR_BLOCK), 0, ctx->stream, tgt->x(), tgt->y(), tgt->z(), (uint32_t)n, bb_dev);
     std::vector<float> hb(bb_blocks * 6);
     e = hipMemcpyAsync(hb.data(), bb_dev, hb.size() * sizeof(float), hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { bt_free(bt); return fail(ctx, PCR_ERR_HIP, "btiles bbox", e); }
+    if (e != hipSuccess) return fail(ctx, PCR_ERR_HIP, "btiles bbox", e);
     float lo[3] = { FLT_MAX, FLT_MAX, FLT_MAX }, hi[3] = { -FLT_MAX, -FLT_MAX, -FLT_MAX };
     for (uint32_t b = 0; b < bb_blocks; b++)
         for (int k = 0; k < 3; k++) { lo[k] = std::min(lo[k], hb[b * 6 + k]); hi[k] = std::max(hi[k], hb[b * 6 + 3 + k]); }
@@ -1999,15 +2024,9 @@ int bt_ensure(pcr_ctx* ctx, const pcr_cloud* tgt)
         if (!(iv1 < 3e38f)) iv1 = 0.0f;
         const float iv[3] = { iv1, iv1, iv1 };
         bt->key_lo[0] = lo[0]; bt->key_lo[1] = lo[1]; bt->key_lo[2] = lo[2]; bt->key_inv = iv1;
-        char* sc = (char*)ctx->scratch;
-        unsigned long long* k_in = (unsigned long long*)sc;
-        unsigned long long* k_out = (unsigned long long*)(sc + a8);
-        uint32_t* v_in = (uint32_t*)(sc + 2 * a8);
-        uint32_t* v_out = (uint32_t*)(sc + 2 * a8 + a4);
-        char* temp = sc + 2 * a8 + 2 * a4;
         hipLaunchKernelGGL(bt_keys_kernel, dim3((unsigned)((n + GR_BLOCK - 1) / GR_BLOCK)), dim3(GR_BLOCK), 0, ctx->stream, tgt->x(), tgt->y(), tgt->z(), (uint32_t)n,
                            lo[0], lo[1], lo[2], iv[0], iv[1], iv[2], k_in, v_in, fine_bits);
-        e = sort_pairs_u64_u32(temp, temp_bytes, k_in, k_out, v_in, v_out, n, 0, key_bits, ctx->stream);
+        e = sort_pairs_u64_u32(sort_temp, temp_bytes, k_in, k_out, v_in, v_out, n, 0, key_bits, ctx->stream);
         if (e == hipSuccess) {
             hipLaunchKernelGGL(gather_records_kernel, dim3((unsigned)((n_pad + GR_BLOCK - 1) / GR_BLOCK)), dim3(GR_BLOCK), 0, ctx->stream, tgt->x(), tgt->y(), tgt->z(),
                                (uint32_t)n, (uint32_t)n_pad, v_out, bt->records);
@@ -2019,11 +2038,11 @@ int bt_ensure(pcr_ctx* ctx, const pcr_cloud* tgt)
                                bt->centres, bt->ops, (int*)nullptr);
             e = hipGetLastError();
         }
-        if (e != hipSuccess) { bt_free(bt); return fail(ctx, PCR_ERR_HIP, "btiles", e); }
+        if (e != hipSuccess) return fail(ctx, PCR_ERR_HIP, "btiles", e);
         bt->n_tiles = n_tiles;
         // (stream order: the scratch may be reused by later launches on ctx->stream, which run after the sort and the gather)
     }
-    const_cast<pcr_cloud*>(tgt)->bt = bt;
+    const_cast<pcr_cloud*>(tgt)->bt = bt_owner.release();
     return PCR_OK;
 }
 
@@ -2145,15 +2164,17 @@ int bt_sort_working_cloud(pcr_ctx* ctx, const pcr_cloud* tgt, pcr_cloud** work, 
     if (!bt || !bt->safe || !bt->n_tiles) return PCR_OK;
     size_t temp_bytes = 0;
     sort_pairs_u64_u32(nullptr, temp_bytes, nullptr, nullptr, nullptr, nullptr, n, 0, 31, ctx->stream);
-    const size_t a4 = (n * 4 + 255) & ~(size_t)255, a8 = (n * 8 + 255) & ~(size_t)255;
-    rc = ensure_scratch(ctx, 2 * a8 + 2 * a4 + temp_bytes + 256);
+    unsigned long long *k_in, *k_out;
+    uint32_t *v_in, *v_out;
+    void* temp;
+    Layout L;
+    L.add(&k_in, n);
+    L.add(&k_out, n);
+    L.add(&v_in, n);
+    L.add(&v_out, n);
+    L.add(&temp, temp_bytes);
+    rc = bind_scratch(ctx, L);
     if (rc) return rc;
-    char* sc = (char*)ctx->scratch;
-    unsigned long long* k_in = (unsigned long long*)sc;
-    unsigned long long* k_out = (unsigned long long*)(sc + a8);
-    uint32_t* v_in = (uint32_t*)(sc + 2 * a8);
-    uint32_t* v_out = (uint32_t*)(sc + 2 * a8 + a4);
-    char* temp = sc + 2 * a8 + 2 * a4;
     if ((rc = orig_storage(ctx, w, in_place, &v_out))) return rc;  // (the sorted values ARE the original indices: no copy behind the sort)
     pcr_cloud* sorted = nullptr;
     rc = cloud_alloc(ctx, n, &sorted);                            // same size; the permute writes all of it, padding included
@@ -2223,35 +2244,39 @@ int cloud_shard_spatial(pcr_ctx* ctx, const pcr_cloud* tgt, const pcr_cloud* ful
     int rc = build_target_grid(ctx, tgt);
     if (rc) return rc;
     size_t count = 0;
-    const size_t a4 = (n * 4 + 255) & ~(size_t)255;
-    uint32_t* member = nullptr, *pos = nullptr, *totals = nullptr;
-    const size_t scan_blocks = (n + SC_TILE - 1) / SC_TILE;
+    uint32_t* member = nullptr, *pos = nullptr, *totals = nullptr, *count_dev = nullptr;
+    void* blk = nullptr;
     if (n) {
         rc = sort_queries_fine(ctx, tgt->grid, full);          // ctx->qperm[t] = original index of the point at sorted position t (radix sort: stable, deterministic)
         if (rc) return rc;
         ctx->qperm_src = nullptr;                             // (the order belongs to `full`, which no search will use)
-        hipError_t e = hipMalloc((void**)&member, 2 * a4 + (scan_blocks + 2) * sizeof(uint32_t));   // (not the scratch: the sort above lives there)
+        Layout L;
+        L.add(&member, n);
+        L.add(&pos, n);
+        L.add(&totals, scan_blocks(n));
+        L.add(&count_dev, 1);
+        hipError_t e = hipMalloc(&blk, L.bytes());               // (not the scratch: the sort above lives there)
         if (e != hipSuccess) return fail(ctx, PCR_ERR_HIP, "hipMalloc(shard)", e);
-        pos = (uint32_t*)((char*)member + a4); totals = (uint32_t*)((char*)member + 2 * a4);
+        L.bind(blk);
         const size_t n_chunks = (size_t)nranks * (size_t)std::max(1, chunks_per_rank);
         const uint32_t chunk_len = (uint32_t)std::max<size_t>(1, (n + n_chunks - 1) / n_chunks);
         const unsigned blocks = (unsigned)((n + GR_BLOCK - 1) / GR_BLOCK);
         hipLaunchKernelGGL(shard_mark_kernel, dim3(blocks), dim3(GR_BLOCK), 0, ctx->stream, ctx->qperm, (uint32_t)n, chunk_len, (uint32_t)nranks, (uint32_t)rank, member);
-        rc = exclusive_scan_u32(ctx, member, pos, n, totals, totals + scan_blocks);
+        rc = exclusive_scan_u32(ctx, member, pos, n, totals, count_dev);
         uint32_t h_count = 0;
         if (rc == PCR_OK) {
-            e = hipMemcpyAsync(&h_count, totals + scan_blocks, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream);
+            e = hipMemcpyAsync(&h_count, count_dev, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream);
             if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
             if (e != hipSuccess) rc = fail(ctx, PCR_ERR_HIP, "shard count", e);
         }
-        if (rc) { hipFree(member); return rc; }
+        if (rc) { hipFree(blk); return rc; }
         count = h_count;
     }
     pcr_cloud* c = nullptr;
     rc = alloc(ctx, count, &c);
-    if (rc) { if (member) hipFree(member); return rc; }
+    if (rc) { if (blk) hipFree(blk); return rc; }
     hipError_t e = hipMalloc((void**)&c->gidx, std::max<size_t>(count, 1) * sizeof(uint32_t));
-    if (e != hipSuccess) { if (member) hipFree(member); pcr_cloud_destroy(ctx, c); return fail(ctx, PCR_ERR_HIP, "hipMalloc(shard indices)", e); }
+    if (e != hipSuccess) { if (blk) hipFree(blk); pcr_cloud_destroy(ctx, c); return fail(ctx, PCR_ERR_HIP, "hipMalloc(shard indices)", e); }
     if (n)
         hipLaunchKernelGGL(shard_gather_kernel, dim3((unsigned)((n + GR_BLOCK - 1) / GR_BLOCK)), dim3(GR_BLOCK), 0, ctx->stream, full->x(), full->y(), full->z(), (uint32_t)n,
                            member, pos, c->x(), c->y(), c->z(), c->gidx);
@@ -2259,7 +2284,7 @@ int cloud_shard_spatial(pcr_ctx* ctx, const pcr_cloud* tgt, const pcr_cloud* ful
                        (uint32_t)c->cap);
     e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (member) hipFree(member);
+    if (blk) hipFree(blk);
     if (e != hipSuccess) { pcr_cloud_destroy(ctx, c); return fail(ctx, PCR_ERR_HIP, "shard gather", e); }
     *out = c;
     return PCR_OK;

@@ -130,14 +130,15 @@ int seed_upper_bound(pcr_ctx* ctx, const pcr_cloud* c, size_t lpr_size, double t
     const size_t n = c->n;
     size_t temp_bytes = 0;
     sort_keys_u32(nullptr, temp_bytes, nullptr, nullptr, n, 0, 32, ctx->stream);
-    const size_t kb = (n * 4 + 255) & ~(size_t)255;
-    int rc = ensure_scratch(ctx, 2 * kb + 256 + temp_bytes + 256);
+    uint32_t *k_in, *k_out, *n_cand_dev;
+    void* temp;
+    Layout L;
+    L.add(&k_in, n);
+    L.add(&k_out, n);
+    L.add(&n_cand_dev, 1);
+    L.add(&temp, temp_bytes);
+    int rc = bind_scratch(ctx, L);
     if (rc) return rc;
-    char* s = (char*)ctx->scratch;
-    uint32_t* k_in = (uint32_t*)s;
-    uint32_t* k_out = (uint32_t*)(s + kb);
-    uint32_t* n_cand_dev = (uint32_t*)(s + 2 * kb);
-    void* temp = s + 2 * kb + 256;
     PCR_HIP(ctx, hipMemsetAsync(n_cand_dev, 0, 4, ctx->stream));
     {
         ProfScope ps(ctx, "ground_seed_select", 1);
@@ -179,10 +180,12 @@ int moments(pcr_ctx* ctx, const pcr_cloud* c, const Pred& pr, double centre[3], 
 {
     const size_t n = c->n;
     const unsigned blocks = gd_blocks(n);
-    int rc = ensure_scratch(ctx, (size_t)blocks * 10 * sizeof(double));
+    double *p1, *p2;
+    Layout L;
+    L.add(&p1, (size_t)blocks * 4);
+    L.add(&p2, (size_t)blocks * 6);
+    int rc = bind_scratch(ctx, L);
     if (rc) return rc;
-    double* p1 = (double*)ctx->scratch;
-    double* p2 = p1 + (size_t)blocks * 4;
     std::vector<double> h((size_t)blocks * 6);
     {
         ProfScope ps(ctx, "ground_moments", 1);
@@ -214,7 +217,7 @@ int moments(pcr_ctx* ctx, const pcr_cloud* c, const Pred& pr, double centre[3], 
 int fetch_mask(pcr_ctx* ctx, const pcr_cloud* c, const Pred& pr, uint8_t* host_mask)
 {
     const size_t n = c->n;
-    int rc = ensure_scratch(ctx, n + 256);
+    int rc = ensure_scratch(ctx, n);
     if (rc) return rc;
     uint8_t* dm = (uint8_t*)ctx->scratch;
     hipLaunchKernelGGL(gd_mask_kernel, dim3((unsigned)((n + GD_BLOCK - 1) / GD_BLOCK)), dim3(GD_BLOCK), 0, ctx->stream, c->x(), c->y(), c->z(), (uint32_t)n, pr, dm);

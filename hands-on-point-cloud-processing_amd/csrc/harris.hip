@@ -207,16 +207,20 @@ extern "C" int pcr_harris3d_f32(pcr_ctx* ctx, const pcr_cloud* cloud, const pcr_
         int rc = grid_build(ctx, cloud, &g, std::max((double)radius * 1.01, 2e-15));
         if (rc) return rc;
     }
-    if ((double)g->p.h < (double)radius * 1.005) { grid_free(g); return fail(ctx, PCR_ERR_STATE, "pcr_harris3d_f32: grid cell smaller than the radius"); }
-    const size_t a16 = (n * 16 + 255) & ~(size_t)255, a4 = (n * 4 + 255) & ~(size_t)255, a1 = (n + 255) & ~(size_t)255;
-    int rc = ensure_scratch(ctx, a16 + 3 * a4 + a1);
-    if (rc) { grid_free(g); return rc; }
-    char* sp = (char*)ctx->scratch;
-    float4* nrec = (float4*)sp;
-    float* resp_sorted = (float*)(sp + a16);
-    float* resp_dev = (float*)(sp + a16 + a4);
-    uint32_t* cnt_dev = (uint32_t*)(sp + a16 + 2 * a4);
-    uint8_t* key_dev = (uint8_t*)(sp + a16 + 3 * a4);
+    const GridPtr g_owner(g);
+    if ((double)g->p.h < (double)radius * 1.005) return fail(ctx, PCR_ERR_STATE, "pcr_harris3d_f32: grid cell smaller than the radius");
+    float4* nrec;
+    float *resp_sorted, *resp_dev;
+    uint32_t* cnt_dev;
+    uint8_t* key_dev;
+    Layout L;
+    L.add(&nrec, n);
+    L.add(&resp_sorted, n);
+    L.add(&resp_dev, n);
+    L.add(&cnt_dev, n);
+    L.add(&key_dev, n);
+    int rc = bind_scratch(ctx, L);
+    if (rc) return rc;
     const int nms = prm->non_max_suppression ? 1 : 0;
     const int G = (int)tune_get(ctx, "harris_lanes", 16);   // measured: profiles/harris.txt (best at hw9's size)
 #define PCR_HARRIS(GG)                                                                                                                \
@@ -245,7 +249,6 @@ extern "C" int pcr_harris3d_f32(pcr_ctx* ctx, const pcr_cloud* cloud, const pcr_
     if (e == hipSuccess && response) e = hipMemcpyAsync(response, resp_dev, n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess && neighbor_counts) e = hipMemcpyAsync(neighbor_counts, cnt_dev, n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    grid_free(g);
     if (e != hipSuccess) return fail(ctx, PCR_ERR_HIP, "pcr_harris3d_f32", e);
     prof_flush(ctx);
     if (n_keypoints) {

@@ -238,7 +238,8 @@ extern "C" int pcr_iss_keypoints_f32(pcr_ctx* ctx, const pcr_cloud* cloud, const
         int rc = grid_build(ctx, cloud, &g, std::max(rmax * 1.01, 2e-15));
         if (rc) return rc;
     }
-    if ((double)g->p.h < rmax * 1.005) { grid_free(g); return fail(ctx, PCR_ERR_STATE, "pcr_iss_keypoints_f32: grid cell smaller than the radius"); }
+    const GridPtr g_owner(g);
+    if ((double)g->p.h < rmax * 1.005) return fail(ctx, PCR_ERR_STATE, "pcr_iss_keypoints_f32: grid cell smaller than the radius");
     IssParams ip;
     ip.s_local = sqrt_threshold(prm->local_radius);
     ip.s_nms = sqrt_threshold(prm->non_max_radius);
@@ -246,18 +247,19 @@ extern "C" int pcr_iss_keypoints_f32(pcr_ctx* ctx, const pcr_cloud* cloud, const
     ip.gamma32 = prm->gamma32;
     ip.min_neighbors = (unsigned)prm->min_neighbors;      // size_t < int comparison of the reference (:92): negative -> huge
     ip.weighted = prm->weighted_covariance ? 1 : 0;
-    const size_t a4 = (n * 4 + 255) & ~(size_t)255, a1 = (n + 255) & ~(size_t)255;
-    const size_t a8 = (n * 8 + 255) & ~(size_t)255;
-    int rc = ensure_scratch(ctx, 7 * a8 + 4 * a4 + a1 + 256);
-    if (rc) { grid_free(g); return rc; }
-    char* s = (char*)ctx->scratch;
-    double* sums = (double*)s;                              // 7 arrays of n (only the first n of each a8 slot pitch is used)
-    s += 7 * a8;
-    uint32_t* cnt_sorted = (uint32_t*)s;
-    float* l3_sorted = (float*)(s + a4);
-    float* l3_out = (float*)(s + 2 * a4);
-    uint32_t* cnt_out = (uint32_t*)(s + 3 * a4);
-    uint8_t* key_dev = (uint8_t*)(s + 4 * a4);
+    double* sums;
+    uint32_t *cnt_sorted, *cnt_out;
+    float *l3_sorted, *l3_out;
+    uint8_t* key_dev;
+    Layout L;
+    L.add(&sums, 7 * n);         // 7 arrays of n, back to back
+    L.add(&cnt_sorted, n);
+    L.add(&l3_sorted, n);
+    L.add(&l3_out, n);
+    L.add(&cnt_out, n);
+    L.add(&key_dev, n);
+    int rc = bind_scratch(ctx, L);
+    if (rc) return rc;
     const int G = (int)tune_get(ctx, "iss_lanes", 32);   // measured: profiles/r01_iss.txt (neighbourhoods of 10^2-10^3 points)
 #define PCR_ISS(GG)                                                                                                                   \
     {                                                                                                                                 \
@@ -285,7 +287,6 @@ extern "C" int pcr_iss_keypoints_f32(pcr_ctx* ctx, const pcr_cloud* cloud, const
     if (e == hipSuccess && lambda3) e = hipMemcpyAsync(lambda3, l3_out, n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess && neighbor_counts) e = hipMemcpyAsync(neighbor_counts, cnt_out, n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    grid_free(g);
     if (e != hipSuccess) return fail(ctx, PCR_ERR_HIP, "pcr_iss_keypoints_f32", e);
     prof_flush(ctx);
     if (n_keypoints) {

@@ -387,22 +387,24 @@ int knn_grid_device(pcr_ctx* ctx, const pcr_cloud* db, const pcr_cloud* q, int k
     bool owned = false;
     int rc = knn_grid_for(ctx, db, k, &g, &owned);
     if (rc) return rc;
+    const GridPtr g_owner(owned ? g : nullptr);
     const uint32_t* perm = nullptr;
     if (q != db) {
         // cell-sorted permutation of the queries (coarse cells of db's cached grid; any spatial grouping will do)
         ProfScope p(ctx, "grid_sort_queries");
         rc = grid_prepare_queries(ctx, db, q);
-        if (rc) { if (owned) grid_free(g); return rc; }
+        if (rc) return rc;
         perm = ctx->qperm;
     }
-    const size_t vb = (m * (size_t)k * 8 + 255) & ~(size_t)255, ib = (m * (size_t)k * 4 + 255) & ~(size_t)255, fb = (m * 4 + 255) & ~(size_t)255;
-    char* res = nullptr;
-    hipError_t e = hipMalloc((void**)&res, vb + ib + fb);
-    if (e != hipSuccess) { if (owned) grid_free(g); return fail(ctx, PCR_ERR_HIP, "hipMalloc(knn)", e); }
+    Layout L;
+    L.add(val_dev, m * (size_t)k);
+    L.add(idx_dev, m * (size_t)k);
+    L.add(found_dev, m);
+    void* res = nullptr;
+    hipError_t e = hipMalloc(&res, L.bytes());
+    if (e != hipSuccess) return fail(ctx, PCR_ERR_HIP, "hipMalloc(knn)", e);
+    L.bind(res);
     *result = res;
-    *val_dev = (double*)res;
-    *idx_dev = (int32_t*)(res + vb);
-    *found_dev = (uint32_t*)(res + vb + ib);
     {
         ProfScope p(ctx, "knn_grid", 1);
         const dim3 grid((unsigned)((m + KG_BLOCK - 1) / KG_BLOCK));
@@ -424,7 +426,6 @@ int knn_grid_device(pcr_ctx* ctx, const pcr_cloud* db, const pcr_cloud* q, int k
     }
     e = hipGetLastError();
     if (e == hipSuccess && owned) e = hipStreamSynchronize(ctx->stream);      // the private grid must outlive the kernel
-    if (owned) grid_free(g);
     if (e != hipSuccess) { hipFree(res); *result = nullptr; return fail(ctx, PCR_ERR_HIP, "knn_grid", e); }
     return PCR_OK;
 }
@@ -507,19 +508,24 @@ int cloud_knn_small(pcr_ctx* ctx, const pcr_cloud* db, const float* q_rows, size
     bool owned = false;
     int rc = knn_grid_for(ctx, db, k, &g, &owned);
     if (rc) return rc;
+    const GridPtr g_owner(owned ? g : nullptr);
     if (m <= KNN_COOP_MAX && !owned && tune_get(ctx, "knn_coop", 1) == 1) return cloud_knn_coop(ctx, g, q_rows, m, k, cap_s, squared, empty_val, empty_idx, idx, val);
-    const size_t mp = (m + 63) & ~(size_t)63;
-    const size_t off_val = (3 * mp * 4 + 255) & ~(size_t)255, off_idx = off_val + ((m * (size_t)k * 8 + 255) & ~(size_t)255),
-                 off_found = off_idx + ((m * (size_t)k * 4 + 255) & ~(size_t)255), total = off_found + m * 4 + 256;
-    rc = ensure_stage(ctx, total);
+    float *qx, *qy, *qz;
+    double* val_p;
+    int32_t* idx_p;
+    uint32_t* found_p;
+    Layout L;
+    L.add(&qx, m);
+    L.add(&qy, m);
+    L.add(&qz, m);
+    L.add(&val_p, m * (size_t)k);
+    L.add(&idx_p, m * (size_t)k);
+    L.add(&found_p, m);
+    rc = ensure_stage(ctx, L.bytes());
     if (rc == PCR_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = fail(ctx, PCR_ERR_HIP, "knn small: sync");
-    if (rc) { if (owned) grid_free(g); return rc; }
-    char* st = (char*)ctx->host_stage;
-    float* qx = (float*)st; float* qy = qx + mp; float* qz = qy + mp;
+    if (rc) return rc;
+    L.bind(ctx->host_stage);
     for (size_t i = 0; i < m; i++) { qx[i] = q_rows[3 * i]; qy[i] = q_rows[3 * i + 1]; qz[i] = q_rows[3 * i + 2]; }
-    double* val_p = (double*)(st + off_val);
-    int32_t* idx_p = (int32_t*)(st + off_idx);
-    uint32_t* found_p = (uint32_t*)(st + off_found);
     {
         ProfScope p(ctx, "knn_grid", 1);
         const dim3 grid((unsigned)((m + KG_BLOCK - 1) / KG_BLOCK));
@@ -541,7 +547,6 @@ int cloud_knn_small(pcr_ctx* ctx, const pcr_cloud* db, const float* q_rows, size
     }
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (owned) grid_free(g);
     if (e != hipSuccess) return fail(ctx, PCR_ERR_HIP, "knn small", e);
     memcpy(idx, idx_p, m * (size_t)k * 4);
     memcpy(val, val_p, m * (size_t)k * 8);

@@ -1650,15 +1650,20 @@ __global__ __launch_bounds__(64) void ht_selftest_kernel(const uint4* __restrict
 // device buffers of a self-test: the context's scratch and pinned stage (no allocation in the common case — the verdict runs inside a search)
 static int selftest_run(pcr_ctx* ctx, const void* h_in, size_t in_bytes, size_t out_bytes, float** h_out, void** d_in, float** d_out)
 {
-    const size_t in_al = (in_bytes + 255) & ~(size_t)255;
-    int rc = ensure_scratch(ctx, in_al + out_bytes);
+    void* h_stage;
+    Layout Ld, Lh;                                             // the same two slots on the device and in the pinned stage
+    Ld.add(d_in, in_bytes);
+    Ld.add((void**)d_out, out_bytes);
+    Lh.add(&h_stage, in_bytes);
+    Lh.add((void**)h_out, out_bytes);
+    int rc = bind_scratch(ctx, Ld);
     if (rc) return rc;
-    rc = ensure_stage(ctx, in_al + out_bytes);
+    rc = ensure_stage(ctx, Lh.bytes());
     if (rc) return rc;
+    Lh.bind(ctx->host_stage);
     PCR_HIP(ctx, hipStreamSynchronize(ctx->stream));           // the staging buffer may still be in flight
-    std::memcpy(ctx->host_stage, h_in, in_bytes);
-    *d_in = ctx->scratch; *d_out = (float*)((char*)ctx->scratch + in_al); *h_out = (float*)((char*)ctx->host_stage + in_al);
-    PCR_HIP(ctx, hipMemcpyAsync(*d_in, ctx->host_stage, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+    std::memcpy(h_stage, h_in, in_bytes);
+    PCR_HIP(ctx, hipMemcpyAsync(*d_in, h_stage, in_bytes, hipMemcpyHostToDevice, ctx->stream));
     return PCR_OK;
 }
 
@@ -1755,7 +1760,7 @@ int ht_mfma_selftest(pcr_ctx* ctx, int trials, double worst[4])
     const Fmt& F = FMT_F16;
     const size_t n_raw = (size_t)trials + SELF_STRUCT, n_tiles = n_raw + (size_t)trials + SELF_EDGE;
     // one upload: [n_raw][A, B][64 lanes] x 16 bytes of f16 patterns, then [n_tiles][64 rows (32 queries, 32 targets)] x 3 floats
-    const size_t ab_words = n_raw * 128 * 4, rt_off = (ab_words * 4 + 255) & ~(size_t)255, rt_floats = n_tiles * 64 * 3;
+    const size_t ab_words = n_raw * 128 * 4, rt_off = al256(ab_words * 4), rt_floats = n_tiles * 64 * 3;
     std::vector<unsigned char> blob(rt_off + rt_floats * 4, 0);
     uint32_t* hab = reinterpret_cast<uint32_t*>(blob.data());
     float* rt = reinterpret_cast<float*>(blob.data() + rt_off);

@@ -7,10 +7,12 @@
 #include <cstdio>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <string>
 #include <vector>
 
 #include "pcr.h"
+#include "scratch_layout.hpp"
 
 namespace pcr {
 
@@ -66,7 +68,14 @@ struct Comm {
 
 }  // namespace pcr
 
-namespace pcr { struct Grid; void grid_free(Grid*); struct BtIndex; void bt_free(BtIndex*); }
+namespace pcr {
+struct Grid; void grid_free(Grid*); struct BtIndex; void bt_free(BtIndex*);
+// owners of an index under construction or of a temporary one: release() where ownership passes on (both frees take a partially built object)
+struct GridFree { void operator()(Grid* g) const { grid_free(g); } };
+struct BtFree { void operator()(BtIndex* b) const { bt_free(b); } };
+using GridPtr = std::unique_ptr<Grid, GridFree>;
+using BtPtr = std::unique_ptr<BtIndex, BtFree>;
+}
 
 struct pcr_cloud {
     pcr::Grid* grid = nullptr;   // exact-NN index over this cloud as a target; built lazily, dropped on modification
@@ -212,6 +221,9 @@ int ensure_keys(pcr_ctx* ctx, size_t n);
 int ensure_scratch(pcr_ctx* ctx, size_t bytes);
 int ensure_stage(pcr_ctx* ctx, size_t bytes);
 int ensure_aux(pcr_ctx* ctx, size_t bytes);
+// ensure_scratch / ensure_aux for L.bytes(), then L.bind(): every pointer declared on L points into the block
+int bind_scratch(pcr_ctx* ctx, const Layout& L);
+int bind_aux(pcr_ctx* ctx, const Layout& L);
 int64_t tune_get(const pcr_ctx* ctx, const char* key, int64_t dflt);
 
 // profiling: record a (start, stop) event pair around a launch on ctx->stream
@@ -250,8 +262,9 @@ int knn_grid_device(pcr_ctx* ctx, const pcr_cloud* db, const pcr_cloud* q, int k
 constexpr size_t KNN_SMALL_MAX = 4096;
 int cloud_knn_small(pcr_ctx* ctx, const pcr_cloud* db, const float* q_rows, size_t m, int k, double cap_s, bool squared, double empty_val,
                     int32_t empty_idx, int32_t* idx, double* val);
-// device-wide exclusive scan of u32 (grid.hip): totals needs ceil(n / SCAN_TILE) + 1 words
+// device-wide exclusive scan of u32 (grid.hip): totals needs scan_blocks(n) words, grand one word (the sum of all n)
 constexpr int SCAN_TILE = 2048;
+inline size_t scan_blocks(size_t n) { return (n + SCAN_TILE - 1) / SCAN_TILE; }
 int exclusive_scan_u32(pcr_ctx* ctx, const uint32_t* in, uint32_t* out, size_t n, uint32_t* totals, uint32_t* grand);
 // range image (range_image.hip); arguments are validated by the entry points in api.cpp
 int ri_create(pcr_ctx* ctx, const pcr_cloud* cloud, double resolution_deg, int width, int height, pcr_range_image** out);

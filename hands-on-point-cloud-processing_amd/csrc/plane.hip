@@ -166,10 +166,13 @@ extern "C" int pcr_plane_mask_f64(pcr_ctx* ctx, const pcr_cloud* pts, const doub
     if (n_inliers) *n_inliers = 0;
     if (pts->n == 0) return PCR_OK;
     PCR_HIP(ctx, hipSetDevice(ctx->device));
-    int rc = ensure_scratch(ctx, pts->n + 64);
+    unsigned long long* count_dev;
+    uint8_t* mask_dev;
+    Layout L;
+    L.add(&count_dev, 1);
+    L.add(&mask_dev, pts->n);
+    int rc = bind_scratch(ctx, L);
     if (rc) return rc;
-    unsigned long long* count_dev = (unsigned long long*)ctx->scratch;
-    uint8_t* mask_dev = (uint8_t*)ctx->scratch + 64;
     PCR_HIP(ctx, hipMemsetAsync(count_dev, 0, 8, ctx->stream));
     rc = launch_plane_mask(ctx, pts, plane4, thr, mask_dev, count_dev);
     if (rc) return rc;

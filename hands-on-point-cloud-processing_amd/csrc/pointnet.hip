@@ -418,7 +418,6 @@ __global__ __launch_bounds__(PN_BLOCK) void obj_build_kernel(const float* __rest
     }
 }
 
-inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
 inline dim3 blocks_for(size_t n) { return dim3((unsigned)((n + PN_BLOCK - 1) / PN_BLOCK)); }
 inline unsigned bit_length(unsigned long long v) { unsigned b = 0; while (v) { b++; v >>= 1; } return b; }
 
@@ -470,17 +469,24 @@ int fps_run(pcr_ctx* ctx, const float* x, const float* y, const float* z, std::v
         tab.push_back(t);
     }
     const size_t dsz = mode == 1 ? 8 : 4;
-    const size_t off_jobs = 0, off_tab = off_jobs + al256(sorted.size() * sizeof(FpsJob)), off_wg = off_tab + al256(tab.size() * sizeof(FpsLargeSeg)),
-                 off_part = off_wg + al256(wg_tab.size() * 4), off_dist = off_part + 2 * al256(wg_tab.size() * sizeof(FpsPart)),
-                 total = off_dist + al256((size_t)dist_total * dsz) + 256;
-    int rc = ensure_aux(ctx, total);
+    FpsJob* jobs_dev;
+    FpsLargeSeg* tab_dev;
+    uint32_t* wg_dev;
+    FpsPart* part[2];
+    void* dist_dev;
+    Layout L;
+    L.add(&jobs_dev, sorted.size());
+    L.add(&tab_dev, tab.size());
+    L.add(&wg_dev, wg_tab.size());
+    L.add(&part[0], wg_tab.size());
+    L.add(&part[1], wg_tab.size());
+    L.add(&dist_dev, (size_t)dist_total * dsz);
+    int rc = bind_aux(ctx, L);
     if (rc) return rc;
-    char* a = (char*)ctx->aux;
-    const FpsJob* jobs_dev = (const FpsJob*)(a + off_jobs);
-    PCR_HIP(ctx, hipMemcpyAsync(a + off_jobs, sorted.data(), sorted.size() * sizeof(FpsJob), hipMemcpyHostToDevice, ctx->stream));
+    PCR_HIP(ctx, hipMemcpyAsync(jobs_dev, sorted.data(), sorted.size() * sizeof(FpsJob), hipMemcpyHostToDevice, ctx->stream));
     if (!tab.empty()) {
-        PCR_HIP(ctx, hipMemcpyAsync(a + off_tab, tab.data(), tab.size() * sizeof(FpsLargeSeg), hipMemcpyHostToDevice, ctx->stream));
-        PCR_HIP(ctx, hipMemcpyAsync(a + off_wg, wg_tab.data(), wg_tab.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+        PCR_HIP(ctx, hipMemcpyAsync(tab_dev, tab.data(), tab.size() * sizeof(FpsLargeSeg), hipMemcpyHostToDevice, ctx->stream));
+        PCR_HIP(ctx, hipMemcpyAsync(wg_dev, wg_tab.data(), wg_tab.size() * 4, hipMemcpyHostToDevice, ctx->stream));
     }
     PCR_HIP(ctx, hipStreamSynchronize(ctx->stream));      // the host vectors go out of scope with this call
     if (mode == 1) {
@@ -496,16 +502,13 @@ int fps_run(pcr_ctx* ctx, const float* x, const float* y, const float* z, std::v
     }
     if (!tab.empty()) {
         ProfScope ps(ctx, "fps_large");
-        const FpsLargeSeg* tab_dev = (const FpsLargeSeg*)(a + off_tab);
-        const uint32_t* wg_dev = (const uint32_t*)(a + off_wg);
-        FpsPart* part[2] = { (FpsPart*)(a + off_part), (FpsPart*)(a + off_part + al256(wg_tab.size() * sizeof(FpsPart))) };
         for (uint32_t step = 0; step < npoint; step++) {      // launch `step` resolves pick `step` from what launch `step - 1` left in part[(step - 1) & 1]
             if (mode == 1)
                 hipLaunchKernelGGL((fps_large_kernel<true>), dim3((unsigned)wg_tab.size()), dim3(PN_BLOCK), 0, ctx->stream, x, y, z, tab_dev, wg_dev,
-                                   (double*)(a + off_dist), part[(step + 1) & 1], part[step & 1], step, npoint, out_dev);
+                                   (double*)dist_dev, part[(step + 1) & 1], part[step & 1], step, npoint, out_dev);
             else
                 hipLaunchKernelGGL((fps_large_kernel<false>), dim3((unsigned)wg_tab.size()), dim3(PN_BLOCK), 0, ctx->stream, x, y, z, tab_dev, wg_dev,
-                                   (float*)(a + off_dist), part[(step + 1) & 1], part[step & 1], step, npoint, out_dev);
+                                   (float*)dist_dev, part[(step + 1) & 1], part[step & 1], step, npoint, out_dev);
         }
     }
     PCR_HIP(ctx, hipGetLastError());
@@ -544,7 +547,7 @@ extern "C" int pcr_fps_f32(pcr_ctx* ctx, const pcr_cloud* cloud, const uint32_t*
     }
     PCR_HIP(ctx, hipSetDevice(ctx->device));
     const size_t out_bytes = n_seg * npoint * 4;
-    int rc = ensure_scratch(ctx, out_bytes + 256);
+    int rc = ensure_scratch(ctx, out_bytes);
     if (rc) return rc;
     uint32_t* out_dev = (uint32_t*)ctx->scratch;
     rc = fps_run(ctx, cloud->x(), cloud->y(), cloud->z(), std::move(jobs), (uint32_t)npoint, mode, out_dev, regime);
@@ -589,24 +592,26 @@ extern "C" int pcr_ball_query_f32(pcr_ctx* ctx, const pcr_cloud* cloud, const ui
     if (nq > 0x7FFFFFF0ull / nsample) return fail(ctx, PCR_ERR_ARG, "pcr_ball_query_f32: too large");
     PCR_HIP(ctx, hipSetDevice(ctx->device));
     std::vector<uint32_t> cs = centre_segments(centre_seg_ptr, n_seg);      // indexed by centre (rows below q0 unused)
-    const size_t off_seg = 0, off_cs = off_seg + al256((n_seg + 1) * 4), off_idx = off_cs + al256(cs.size() * 4), off_cnt = off_idx + al256(nq * nsample * 4),
-                 total = off_cnt + al256(nq * 4) + 256;
-    int rc = ensure_scratch(ctx, total);
+    uint32_t *seg_dev, *cs_dev, *idx_dev, *cnt_dev;
+    Layout L;
+    L.add(&seg_dev, n_seg + 1);
+    L.add(&cs_dev, cs.size());
+    L.add(&idx_dev, nq * nsample);
+    L.add(&cnt_dev, nq);
+    int rc = bind_scratch(ctx, L);
     if (rc) return rc;
-    char* s = (char*)ctx->scratch;
-    PCR_HIP(ctx, hipMemcpyAsync(s + off_seg, seg_ptr, (n_seg + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-    PCR_HIP(ctx, hipMemcpyAsync(s + off_cs, cs.data(), cs.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    PCR_HIP(ctx, hipMemcpyAsync(seg_dev, seg_ptr, (n_seg + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+    PCR_HIP(ctx, hipMemcpyAsync(cs_dev, cs.data(), cs.size() * 4, hipMemcpyHostToDevice, ctx->stream));
     PCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
     const float r2 = (float)(radius * radius);
     {
         ProfScope ps(ctx, "ball_query");
         hipLaunchKernelGGL(ball_query_kernel, dim3((unsigned)((nq + PN_BLOCK / 64 - 1) / (PN_BLOCK / 64))), dim3(PN_BLOCK), 0, ctx->stream, cloud->x(), cloud->y(),
-                           cloud->z(), centres->x() + q0, centres->y() + q0, centres->z() + q0, (const uint32_t*)(s + off_seg), (const uint32_t*)(s + off_cs) + q0,
-                           (uint32_t)nq, r2, (uint32_t)nsample, (uint32_t*)(s + off_idx), (uint32_t*)(s + off_cnt));
+                           cloud->z(), centres->x() + q0, centres->y() + q0, centres->z() + q0, seg_dev, cs_dev + q0, (uint32_t)nq, r2, (uint32_t)nsample, idx_dev, cnt_dev);
     }
     PCR_HIP(ctx, hipGetLastError());
-    PCR_HIP(ctx, hipMemcpyAsync(idx, s + off_idx, nq * nsample * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (counts) PCR_HIP(ctx, hipMemcpyAsync(counts, s + off_cnt, nq * 4, hipMemcpyDeviceToHost, ctx->stream));
+    PCR_HIP(ctx, hipMemcpyAsync(idx, idx_dev, nq * nsample * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (counts) PCR_HIP(ctx, hipMemcpyAsync(counts, cnt_dev, nq * 4, hipMemcpyDeviceToHost, ctx->stream));
     PCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
     prof_flush(ctx);
     return PCR_OK;
@@ -635,27 +640,32 @@ extern "C" int pcr_group_points_f32(pcr_ctx* ctx, const pcr_cloud* cloud, const 
     PCR_HIP(ctx, hipSetDevice(ctx->device));
     const size_t p0 = seg_ptr[0], np = seg_ptr[n_seg] - p0;
     const size_t total_e = nq * nsample * C;
-    const size_t off_seg = 0, off_cs = off_seg + al256((n_seg + 1) * 4), off_idx = off_cs + al256(cs.size() * 4), off_feat = off_idx + al256(nq * nsample * 4),
-                 off_xyz = off_feat + al256(np * D * 4), off_out = off_xyz + al256(nq * 12), total = off_out + al256(total_e * 4) + 256;
-    int rc = ensure_scratch(ctx, total);
+    uint32_t *seg_dev, *cs_dev, *idx_dev;
+    float *feat_dev, *xyz_dev, *out_dev;
+    Layout L;
+    L.add(&seg_dev, n_seg + 1);
+    L.add(&cs_dev, cs.size());
+    L.add(&idx_dev, nq * nsample);
+    L.add(&feat_dev, np * D);
+    L.add(&xyz_dev, nq * 3);
+    L.add(&out_dev, total_e);
+    int rc = bind_scratch(ctx, L);
     if (rc) return rc;
-    char* s = (char*)ctx->scratch;
-    PCR_HIP(ctx, hipMemcpyAsync(s + off_seg, seg_ptr, (n_seg + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-    PCR_HIP(ctx, hipMemcpyAsync(s + off_cs, cs.data(), cs.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-    PCR_HIP(ctx, hipMemcpyAsync(s + off_idx, idx, nq * nsample * 4, hipMemcpyHostToDevice, ctx->stream));
-    if (D && np) PCR_HIP(ctx, hipMemcpyAsync(s + off_feat, features + p0 * D, np * D * 4, hipMemcpyHostToDevice, ctx->stream));
+    PCR_HIP(ctx, hipMemcpyAsync(seg_dev, seg_ptr, (n_seg + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+    PCR_HIP(ctx, hipMemcpyAsync(cs_dev, cs.data(), cs.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    PCR_HIP(ctx, hipMemcpyAsync(idx_dev, idx, nq * nsample * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (D && np) PCR_HIP(ctx, hipMemcpyAsync(feat_dev, features + p0 * D, np * D * 4, hipMemcpyHostToDevice, ctx->stream));
     PCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
     {
         ProfScope ps(ctx, "group_points");
         // features are addressed by cloud position: the pointer is moved back by the p0 rows that were not uploaded (never dereferenced there)
         hipLaunchKernelGGL(group_kernel, blocks_for(total_e), dim3(PN_BLOCK), 0, ctx->stream, cloud->x(), cloud->y(), cloud->z(), centres->x() + q0,
-                           centres->y() + q0, centres->z() + q0, (const uint32_t*)(s + off_seg), (const uint32_t*)(s + off_cs) + q0, (const uint32_t*)(s + off_idx),
-                           (const float*)(s + off_feat) - p0 * D, (uint32_t)D, (uint32_t)nsample, (unsigned long long)total_e, (float*)(s + off_xyz),
-                           (float*)(s + off_out));
+                           centres->y() + q0, centres->z() + q0, seg_dev, cs_dev + q0, idx_dev, feat_dev - p0 * D, (uint32_t)D, (uint32_t)nsample,
+                           (unsigned long long)total_e, xyz_dev, out_dev);
     }
     PCR_HIP(ctx, hipGetLastError());
-    PCR_HIP(ctx, hipMemcpyAsync(new_xyz, s + off_xyz, nq * 12, hipMemcpyDeviceToHost, ctx->stream));
-    PCR_HIP(ctx, hipMemcpyAsync(new_points, s + off_out, total_e * 4, hipMemcpyDeviceToHost, ctx->stream));
+    PCR_HIP(ctx, hipMemcpyAsync(new_xyz, xyz_dev, nq * 12, hipMemcpyDeviceToHost, ctx->stream));
+    PCR_HIP(ctx, hipMemcpyAsync(new_points, out_dev, total_e * 4, hipMemcpyDeviceToHost, ctx->stream));
     PCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
     prof_flush(ctx);
     return PCR_OK;
@@ -687,32 +697,40 @@ extern "C" int pcr_objects_from_labels_f32(pcr_ctx* ctx, const pcr_cloud* cloud,
     PCR_HIP(ctx, hipSetDevice(ctx->device));
     size_t temp_bytes = 0;
     sort_pairs_u64_u32(nullptr, temp_bytes, nullptr, nullptr, nullptr, nullptr, std::max<size_t>(n, 1), 0, 32, ctx->stream);
-    const size_t kb = al256(n * 8), vb = al256(n * 4);
-    const size_t off_lab = 0, off_kin = off_lab + vb, off_kout = off_kin + kb, off_vin = off_kout + kb, off_vout = off_vin + vb, off_sx = off_vout + vb,
-                 off_seg = off_sx + 3 * vb, off_zmm = off_seg + al256(seg.size() * 4), off_temp = off_zmm + al256(n_clusters * 8),
-                 total = off_temp + temp_bytes + 256;
-    int rc = ensure_scratch(ctx, total);
+    int32_t* lab_dev;
+    unsigned long long *k_in, *k_out;
+    uint32_t *v_in, *order, *seg_dev;
+    float *sx, *sy, *sz, *zmm_dev;
+    void* sort_temp;
+    Layout L;
+    L.add(&lab_dev, n);
+    L.add(&k_in, n);
+    L.add(&k_out, n);
+    L.add(&v_in, n);
+    L.add(&order, n);
+    L.add(&sx, n);
+    L.add(&sy, n);
+    L.add(&sz, n);
+    L.add(&seg_dev, seg.size());
+    L.add(&zmm_dev, n_clusters * 2);
+    L.add(&sort_temp, temp_bytes);
+    int rc = bind_scratch(ctx, L);
     if (rc) return rc;
-    char* s = (char*)ctx->scratch;
-    uint32_t* order = (uint32_t*)(s + off_vout);
-    float *sx = (float*)(s + off_sx), *sy = (float*)(s + off_sx + vb), *sz = (float*)(s + off_sx + 2 * vb);
     std::vector<float> zmm(n_clusters * 2);
-    PCR_HIP(ctx, hipMemcpyAsync(s + off_seg, seg.data(), seg.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    PCR_HIP(ctx, hipMemcpyAsync(seg_dev, seg.data(), seg.size() * 4, hipMemcpyHostToDevice, ctx->stream));
     if (n) {
-        PCR_HIP(ctx, hipMemcpyAsync(s + off_lab, labels, n * 4, hipMemcpyHostToDevice, ctx->stream));
+        PCR_HIP(ctx, hipMemcpyAsync(lab_dev, labels, n * 4, hipMemcpyHostToDevice, ctx->stream));
         ProfScope ps(ctx, "obj_sort");
-        hipLaunchKernelGGL(obj_keys_kernel, blocks_for(n), dim3(PN_BLOCK), 0, ctx->stream, (const int32_t*)(s + off_lab), (uint32_t)n, (uint32_t)n_clusters,
-                           (unsigned long long*)(s + off_kin), (uint32_t*)(s + off_vin));
-        PCR_HIP(ctx, sort_pairs_u64_u32(s + off_temp, temp_bytes, (unsigned long long*)(s + off_kin), (unsigned long long*)(s + off_kout), (uint32_t*)(s + off_vin),
-                                        order, n, 0, std::max(1u, bit_length(n_clusters)), ctx->stream));
+        hipLaunchKernelGGL(obj_keys_kernel, blocks_for(n), dim3(PN_BLOCK), 0, ctx->stream, lab_dev, (uint32_t)n, (uint32_t)n_clusters, k_in, v_in);
+        PCR_HIP(ctx, sort_pairs_u64_u32(sort_temp, temp_bytes, k_in, k_out, v_in, order, n, 0, std::max(1u, bit_length(n_clusters)), ctx->stream));
         hipLaunchKernelGGL(obj_gather_kernel, blocks_for(n), dim3(PN_BLOCK), 0, ctx->stream, cloud->x(), cloud->y(), cloud->z(), order, (uint32_t)n, sx, sy, sz);
     }
     {
         ProfScope ps(ctx, "obj_zstats");
-        hipLaunchKernelGGL(obj_zstats_kernel, dim3((unsigned)n_clusters), dim3(PN_BLOCK), 0, ctx->stream, sz, (const uint32_t*)(s + off_seg), (float*)(s + off_zmm));
+        hipLaunchKernelGGL(obj_zstats_kernel, dim3((unsigned)n_clusters), dim3(PN_BLOCK), 0, ctx->stream, sz, seg_dev, zmm_dev);
     }
     PCR_HIP(ctx, hipGetLastError());
-    PCR_HIP(ctx, hipMemcpyAsync(zmm.data(), s + off_zmm, n_clusters * 8, hipMemcpyDeviceToHost, ctx->stream));
+    PCR_HIP(ctx, hipMemcpyAsync(zmm.data(), zmm_dev, n_clusters * 8, hipMemcpyDeviceToHost, ctx->stream));
     PCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
     // ---- gates (f64 on the widened f32 statistics, foreground_obj_cls.py:160-169), the objects in ascending cluster id
     std::vector<ObjDesc> objs;
@@ -746,21 +764,28 @@ extern "C" int pcr_objects_from_labels_f32(pcr_ctx* ctx, const pcr_cloud* cloud,
     const size_t n_obj = objs.size();
     if (n_obj == 0) { prof_flush(ctx); return PCR_OK; }
     // ---- FPS (f64 mode) of the large clusters, then one workgroup per object
-    const size_t off_desc = 0, off_fps = off_desc + al256(n_obj * sizeof(ObjDesc)), off_obj = off_fps + al256(jobs.size() * npoints * 4),
-                 off_src = off_obj + al256(n_obj * npoints * 12), total2 = off_src + al256(n_obj * npoints * 4) + 256;
-    char* b2 = nullptr;
-    PCR_HIP(ctx, hipMalloc((void**)&b2, total2));
-    hipError_t e = hipMemcpyAsync(b2 + off_desc, objs.data(), n_obj * sizeof(ObjDesc), hipMemcpyHostToDevice, ctx->stream);
+    ObjDesc* desc_dev;
+    uint32_t *fps_dev, *src_dev;
+    float* obj_dev;
+    Layout L2;
+    L2.add(&desc_dev, n_obj);
+    L2.add(&fps_dev, jobs.size() * npoints);
+    L2.add(&obj_dev, n_obj * npoints * 3);
+    L2.add(&src_dev, n_obj * npoints);
+    void* b2 = nullptr;
+    PCR_HIP(ctx, hipMalloc(&b2, L2.bytes()));
+    L2.bind(b2);
+    hipError_t e = hipMemcpyAsync(desc_dev, objs.data(), n_obj * sizeof(ObjDesc), hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     rc = PCR_OK;
-    if (e == hipSuccess && !jobs.empty()) rc = fps_run(ctx, sx, sy, sz, jobs, (uint32_t)npoints, PCR_FPS_F64, (uint32_t*)(b2 + off_fps), nullptr);
+    if (e == hipSuccess && !jobs.empty()) rc = fps_run(ctx, sx, sy, sz, jobs, (uint32_t)npoints, PCR_FPS_F64, fps_dev, nullptr);
     if (e == hipSuccess && rc == PCR_OK) {
         ProfScope ps(ctx, "obj_build");
-        hipLaunchKernelGGL(obj_build_kernel, dim3((unsigned)n_obj), dim3(PN_BLOCK), npoints * 12, ctx->stream, sx, sy, sz, order, (const ObjDesc*)(b2 + off_desc),
-                           (const uint32_t*)(b2 + off_fps), (uint32_t)npoints, (unsigned long long)seed, (float*)(b2 + off_obj), (uint32_t*)(b2 + off_src));
+        hipLaunchKernelGGL(obj_build_kernel, dim3((unsigned)n_obj), dim3(PN_BLOCK), npoints * 12, ctx->stream, sx, sy, sz, order, desc_dev, fps_dev,
+                           (uint32_t)npoints, (unsigned long long)seed, obj_dev, src_dev);
         e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(objects, b2 + off_obj, n_obj * npoints * 12, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess && source_index) e = hipMemcpyAsync(source_index, b2 + off_src, n_obj * npoints * 4, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(objects, obj_dev, n_obj * npoints * 12, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess && source_index) e = hipMemcpyAsync(source_index, src_dev, n_obj * npoints * 4, hipMemcpyDeviceToHost, ctx->stream);
     }
     const hipError_t e2 = hipStreamSynchronize(ctx->stream);
     (void)hipFree(b2);

@@ -238,7 +238,6 @@ __global__ __launch_bounds__(RI_BLOCK) void ri_close_kernel(const double* __rest
     out[(size_t)r * cols + c] = m;
 }
 
-inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
 inline dim3 grid1(size_t n) { return dim3((unsigned)((n + RI_BLOCK - 1) / RI_BLOCK)); }
 inline dim3 grid2(int rows, int cols) { return dim3((unsigned)((cols + RI_TW - 1) / RI_TW), (unsigned)((rows + RI_TH - 1) / RI_TH)); }
 
@@ -281,25 +280,27 @@ int ri_create(pcr_ctx* ctx, const pcr_cloud* cloud, double resolution_deg, int w
     g.off_w = std::ceil(width / 2.0);
     g.off_h = std::ceil(height / 2.0);
     g.res_rad = M_PI / 180 * resolution_deg;               // :19
-    const size_t nbp = (n + SCAN_TILE - 1) / SCAN_TILE, nbw = (width + SCAN_TILE - 1) / SCAN_TILE, nbh = (height + SCAN_TILE - 1) / SCAN_TILE;
-    const size_t a_win = al256(npix * 4), a_d = al256(n * 8), a_n4 = al256(n * 4), a_w = al256((size_t)width * 4), a_h = al256((size_t)height * 4);
-    const size_t a_tot = al256((nbp + nbw + nbh + 8) * 4);
-    int rc = ensure_scratch(ctx, a_win + a_d + 3 * a_n4 + 2 * a_w + 2 * a_h + a_tot + 256);
+    int32_t *winner, *pixfull;
+    double* d;
+    uint32_t *dropflag, *dropscan, *rowflag, *colflag, *rowmap, *colmap, *tot_rows, *tot_cols, *tot_drop, *grand;
+    Layout L;
+    L.add(&winner, npix);
+    L.add(&d, n);
+    L.add(&pixfull, n);
+    L.add(&dropflag, n);
+    L.add(&dropscan, n);
+    L.add(&rowflag, height);
+    L.add(&colflag, width);      // (directly behind rowflag: one memset clears both)
+    L.add(&rowmap, height);
+    L.add(&colmap, width);
+    L.add(&tot_rows, scan_blocks(height));
+    L.add(&tot_cols, scan_blocks(width));
+    L.add(&tot_drop, scan_blocks(n));
+    L.add(&grand, 3);            // [0] rows, [1] cols, [2] dropped points
+    int rc = bind_scratch(ctx, L);
     if (rc) return rc;
-    char* s = (char*)ctx->scratch;
-    int32_t* winner = (int32_t*)s;        s += a_win;
-    double* d = (double*)s;               s += a_d;
-    int32_t* pixfull = (int32_t*)s;       s += a_n4;
-    uint32_t* dropflag = (uint32_t*)s;    s += a_n4;
-    uint32_t* dropscan = (uint32_t*)s;    s += a_n4;
-    uint32_t* rowflag = (uint32_t*)s;     s += a_h;
-    uint32_t* colflag = (uint32_t*)s;     s += a_w;      // (rowflag | colflag contiguous up to the padding: two memsets)
-    uint32_t* rowmap = (uint32_t*)s;      s += a_h;
-    uint32_t* colmap = (uint32_t*)s;      s += a_w;
-    uint32_t* totals = (uint32_t*)s;      s += a_tot;
-    uint32_t* grand = (uint32_t*)s;                         // [0] rows, [1] cols, [2] dropped points
     hipError_t e = hipMemsetAsync(winner, 0xFF, npix * 4, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(rowflag, 0, a_h + a_w, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(rowflag, 0, (char*)(colflag + width) - (char*)rowflag, ctx->stream);
     if (e != hipSuccess) return fail(ctx, PCR_ERR_HIP, "pcr_range_image_create_f32: memset", e);
     {
         ProfScope ps(ctx, "ri_project", 1);
@@ -311,9 +312,9 @@ int ri_create(pcr_ctx* ctx, const pcr_cloud* cloud, double resolution_deg, int w
     uint32_t words[3] = { 0, 0, 0 };
     {
         ProfScope ps(ctx, "ri_crop", 1);
-        if (e == hipSuccess && exclusive_scan_u32(ctx, rowflag, rowmap, height, totals, grand + 0)) e = hipErrorUnknown;
-        if (e == hipSuccess && exclusive_scan_u32(ctx, colflag, colmap, width, totals + nbh + 2, grand + 1)) e = hipErrorUnknown;
-        if (e == hipSuccess && exclusive_scan_u32(ctx, dropflag, dropscan, n, totals + nbh + nbw + 4, grand + 2)) e = hipErrorUnknown;
+        if (e == hipSuccess && exclusive_scan_u32(ctx, rowflag, rowmap, height, tot_rows, grand + 0)) e = hipErrorUnknown;
+        if (e == hipSuccess && exclusive_scan_u32(ctx, colflag, colmap, width, tot_cols, grand + 1)) e = hipErrorUnknown;
+        if (e == hipSuccess && exclusive_scan_u32(ctx, dropflag, dropscan, n, tot_drop, grand + 2)) e = hipErrorUnknown;
         if (e == hipSuccess) e = hipMemcpyAsync(words, grand, sizeof words, hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     }
@@ -366,7 +367,7 @@ int ri_read(pcr_ctx* ctx, const pcr_range_image* img, double* image, int32_t* pi
 int ri_close(pcr_ctx* ctx, pcr_range_image* img, int pad)
 {
     const size_t npix = (size_t)img->rows * img->cols;
-    int rc = ensure_scratch(ctx, al256(npix * 8));
+    int rc = ensure_scratch(ctx, npix * 8);
     if (rc) return rc;
     double* dila = (double*)ctx->scratch;
     {
@@ -386,16 +387,17 @@ int ri_close(pcr_ctx* ctx, pcr_range_image* img, int pad)
 int ri_label(pcr_ctx* ctx, pcr_range_image* img, double phi_deg, double theta_deg, int nn_mode, int32_t* image_label, uint64_t* n_labels)
 {
     const size_t npix = (size_t)img->rows * img->cols;
-    const size_t a4 = al256(npix * 4), nb = (npix + SCAN_TILE - 1) / SCAN_TILE;
-    int rc = ensure_scratch(ctx, 4 * a4 + al256((nb + 2) * 4) + 256);
+    uint32_t *parent, *root, *flag, *ids, *totals, *n_ids, *err;
+    Layout L;
+    L.add(&parent, npix);
+    L.add(&root, npix);
+    L.add(&flag, npix);
+    L.add(&ids, npix);
+    L.add(&totals, scan_blocks(npix));
+    L.add(&n_ids, 1);            // the scan's grand total: the number of labels
+    L.add(&err, 1);
+    int rc = bind_scratch(ctx, L);
     if (rc) return rc;
-    char* s = (char*)ctx->scratch;
-    uint32_t* parent = (uint32_t*)s;      s += a4;
-    uint32_t* root = (uint32_t*)s;        s += a4;
-    uint32_t* flag = (uint32_t*)s;        s += a4;
-    uint32_t* ids = (uint32_t*)s;         s += a4;
-    uint32_t* totals = (uint32_t*)s;      s += al256((nb + 2) * 4);
-    uint32_t* err = (uint32_t*)s;
     RiEdge ed;
     const double phi = phi_deg * M_PI / 180;               // :52
     ed.thr = theta_deg * M_PI / 180;                       // :53
@@ -416,14 +418,14 @@ int ri_label(pcr_ctx* ctx, pcr_range_image* img, double phi_deg, double theta_de
         ProfScope ps(ctx, "ri_label", 1);
         hipLaunchKernelGGL(ri_flatten_kernel, grid1(npix), dim3(RI_BLOCK), 0, ctx->stream, img->image, (uint32_t)npix, parent, root, flag, err);
         if (e == hipSuccess) e = hipGetLastError();
-        if (e == hipSuccess && exclusive_scan_u32(ctx, flag, ids, npix, totals, totals + nb)) e = hipErrorUnknown;
+        if (e == hipSuccess && exclusive_scan_u32(ctx, flag, ids, npix, totals, n_ids)) e = hipErrorUnknown;
         hipLaunchKernelGGL(ri_label_kernel, grid1(npix), dim3(RI_BLOCK), 0, ctx->stream, img->image, (uint32_t)npix, root, ids, img->label);
     }
     uint32_t words[2] = { 0, 0 };                           // error word, labels
     if (e == hipSuccess) e = hipGetLastError();
     if (e == hipSuccess && image_label) e = hipMemcpyAsync(image_label, img->label, npix * 4, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(&words[0], err, 4, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(&words[1], totals + nb, 4, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&words[1], n_ids, 4, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) return fail(ctx, PCR_ERR_HIP, "pcr_range_image_label_f64", e);
     prof_flush(ctx);
@@ -438,7 +440,7 @@ int ri_assign(pcr_ctx* ctx, const pcr_range_image* img, int32_t* cluster_idx)
 {
     const size_t n = img->n_points;
     if (n == 0) return PCR_OK;
-    int rc = ensure_scratch(ctx, al256(n * 4));
+    int rc = ensure_scratch(ctx, n * 4);
     if (rc) return rc;
     int32_t* out = (int32_t*)ctx->scratch;
     {

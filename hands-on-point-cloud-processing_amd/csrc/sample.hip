@@ -271,7 +271,6 @@ __global__ __launch_bounds__(SM_BLOCK) void ns_gather_kernel(const float* __rest
     ox[t] = a; oy[t] = b; oz[t] = c;
 }
 
-inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
 inline unsigned bit_length(unsigned long long v) { unsigned b = 0; while (v) { b++; v >>= 1; } return b; }
 inline dim3 blocks_for(size_t n) { return dim3((unsigned)((n + SM_BLOCK - 1) / SM_BLOCK)); }
 
@@ -308,21 +307,25 @@ extern "C" int pcr_voxel_grid_normals_f32(pcr_ctx* ctx, const pcr_cloud* cloud, 
     size_t temp_bytes = 0;
     sort_pairs_u64_u32(nullptr, temp_bytes, nullptr, nullptr, nullptr, nullptr, n, 0, 32, ctx->stream);
     const uint32_t bb = (uint32_t)std::max<size_t>(1, std::min<size_t>(256, (n + SM_BLOCK - 1) / SM_BLOCK));
-    const size_t kb = al256(n * 8), vb = al256(n * 4), nb = (n + 1 + SCAN_TILE - 1) / SCAN_TILE;
-    const size_t off_kin = al256(bb * 7 * sizeof(float)), off_kout = off_kin + kb, off_vin = off_kout + kb, off_vout = off_vin + vb, off_flags = off_vout + vb,
-                 off_gid = off_flags + vb, off_vop = off_gid + vb, off_tot = off_vop + vb, off_temp = off_tot + al256((nb + 2) * 4);
-    int rc = ensure_scratch(ctx, off_temp + temp_bytes + 256);
+    float* bounds_dev;
+    unsigned long long *k_in, *k_out;
+    uint32_t *v_in, *v_out, *flags, *gid, *totals, *m_dev;
+    int32_t* vop_dev;
+    void* sort_temp;
+    Layout L;
+    L.add(&bounds_dev, (size_t)bb * 7);
+    L.add(&k_in, n);
+    L.add(&k_out, n);
+    L.add(&v_in, n);
+    L.add(&v_out, n);
+    L.add(&flags, n);
+    L.add(&gid, n);
+    L.add(&vop_dev, n);
+    L.add(&totals, scan_blocks(n));
+    L.add(&m_dev, 1);            // the scan's grand total: the number of voxels
+    L.add(&sort_temp, temp_bytes);
+    int rc = bind_scratch(ctx, L);
     if (rc) return rc;
-    char* s = (char*)ctx->scratch;
-    float* bounds_dev = (float*)s;
-    unsigned long long* k_in = (unsigned long long*)(s + off_kin);
-    unsigned long long* k_out = (unsigned long long*)(s + off_kout);
-    uint32_t* v_in = (uint32_t*)(s + off_vin);
-    uint32_t* v_out = (uint32_t*)(s + off_vout);
-    uint32_t* flags = (uint32_t*)(s + off_flags);
-    uint32_t* gid = (uint32_t*)(s + off_gid);
-    int32_t* vop_dev = (int32_t*)(s + off_vop);
-    uint32_t* totals = (uint32_t*)(s + off_tot);
     const dim3 gridn = blocks_for(n);
     // ---- 1. the box (the one read-back of it)
     {
@@ -367,15 +370,15 @@ extern "C" int pcr_voxel_grid_normals_f32(pcr_ctx* ctx, const pcr_cloud* cloud, 
         }
         {
             ProfScope ps(ctx, "vgn_sort");
-            PCR_HIP(ctx, sort_pairs_u64_u32(s + off_temp, temp_bytes, k_in, k_out, v_in, v_out, n, 0, std::max(1u, bit_length((unsigned long long)p.total)), ctx->stream));
+            PCR_HIP(ctx, sort_pairs_u64_u32(sort_temp, temp_bytes, k_in, k_out, v_in, v_out, n, 0, std::max(1u, bit_length((unsigned long long)p.total)), ctx->stream));
         }
         {
             ProfScope ps(ctx, "vgn_segments");
             hipLaunchKernelGGL(vg_heads_kernel, gridn, dim3(SM_BLOCK), 0, ctx->stream, k_out, (uint32_t)n, (unsigned long long)p.total, flags);
-            rc = exclusive_scan_u32(ctx, flags, gid, n, totals, totals + nb);
+            rc = exclusive_scan_u32(ctx, flags, gid, n, totals, m_dev);
             if (rc) return rc;
         }
-        PCR_HIP(ctx, hipMemcpyAsync(&m, totals + nb, 4, hipMemcpyDeviceToHost, ctx->stream));
+        PCR_HIP(ctx, hipMemcpyAsync(&m, m_dev, 4, hipMemcpyDeviceToHost, ctx->stream));
         PCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
         if (m > n) return fail(ctx, PCR_ERR_STATE, "pcr_voxel_grid_normals_f32: more voxels than points");
     }
@@ -383,10 +386,13 @@ extern "C" int pcr_voxel_grid_normals_f32(pcr_ctx* ctx, const pcr_cloud* cloud, 
     pcr_cloud *oc = nullptr, *on = nullptr;
     rc = cloud_alloc(ctx, m, &oc);
     if (rc == PCR_OK && has_n) rc = cloud_alloc(ctx, m, &on);
-    if (rc == PCR_OK) rc = ensure_aux(ctx, al256((size_t)m * VG_WORDS * 8) + al256((size_t)m * 4) + 256);
+    unsigned long long* table;
+    uint32_t* counts_dev;
+    Layout La;
+    La.add(&table, (size_t)m * VG_WORDS);
+    La.add(&counts_dev, m);
+    if (rc == PCR_OK) rc = bind_aux(ctx, La);
     if (rc) { pcr_cloud_destroy(ctx, oc); pcr_cloud_destroy(ctx, on); return rc; }
-    unsigned long long* table = (unsigned long long*)ctx->aux;
-    uint32_t* counts_dev = (uint32_t*)((char*)ctx->aux + al256((size_t)m * VG_WORDS * 8));
     hipError_t e = hipSuccess;
     if (any_finite) {
         e = hipMemsetAsync(table, 0, (size_t)m * VG_WORDS * 8, ctx->stream);
@@ -449,19 +455,20 @@ extern "C" int pcr_normal_space_sample_f32(pcr_ctx* ctx, const pcr_cloud* normal
     if (n > 0) {
         size_t temp_bytes = 0;
         sort_pairs_u64_u32(nullptr, temp_bytes, nullptr, nullptr, nullptr, nullptr, n, 0, 64, ctx->stream);
-        const size_t kb = al256(n * 8), vb = al256(n * 4), sb = al256(((size_t)p.nbins + 2) * 4);
-        const size_t off_kb = kb, off_va = 2 * kb, off_vb = off_va + vb, off_bin = off_vb + vb, off_start = off_bin + vb, off_cnt = off_start + sb,
-                     off_temp = off_cnt + 256;
-        int rc = ensure_scratch(ctx, off_temp + temp_bytes + 256);
+        unsigned long long *k_a, *k_b;
+        uint32_t *v_a, *v_b, *bin_of, *start, *cnt_dev;
+        void* sort_temp;
+        Layout L;
+        L.add(&k_a, n);
+        L.add(&k_b, n);
+        L.add(&v_a, n);
+        L.add(&v_b, n);
+        L.add(&bin_of, n);
+        L.add(&start, (size_t)p.nbins + 1);
+        L.add(&cnt_dev, 1);
+        L.add(&sort_temp, temp_bytes);
+        int rc = bind_scratch(ctx, L);
         if (rc) return rc;
-        char* s = (char*)ctx->scratch;
-        unsigned long long* k_a = (unsigned long long*)s;
-        unsigned long long* k_b = (unsigned long long*)(s + off_kb);
-        uint32_t* v_a = (uint32_t*)(s + off_va);
-        uint32_t* v_b = (uint32_t*)(s + off_vb);
-        uint32_t* bin_of = (uint32_t*)(s + off_bin);
-        uint32_t* start = (uint32_t*)(s + off_start);
-        uint32_t* cnt_dev = (uint32_t*)(s + off_cnt);
         const dim3 gridn = blocks_for(n);
         PCR_HIP(ctx, hipMemsetAsync(cnt_dev, 0, 4, ctx->stream));
         {
@@ -471,15 +478,15 @@ extern "C" int pcr_normal_space_sample_f32(pcr_ctx* ctx, const pcr_cloud* normal
         {
             ProfScope ps(ctx, "nss_sort");
             // by key (ties: ascending index, the sort is stable), then by bin: (bin, key, index) order, keys in k_b, indices in v_a
-            PCR_HIP(ctx, sort_pairs_u64_u32(s + off_temp, temp_bytes, k_a, k_b, v_a, v_b, n, 0, 64, ctx->stream));
+            PCR_HIP(ctx, sort_pairs_u64_u32(sort_temp, temp_bytes, k_a, k_b, v_a, v_b, n, 0, 64, ctx->stream));
             hipLaunchKernelGGL(ns_bin_keys_kernel, gridn, dim3(SM_BLOCK), 0, ctx->stream, bin_of, v_b, (uint32_t)n, k_a);
-            PCR_HIP(ctx, sort_pairs_u64_u32(s + off_temp, temp_bytes, k_a, k_b, v_b, v_a, n, 0, std::max(1u, bit_length(p.nbins)), ctx->stream));
+            PCR_HIP(ctx, sort_pairs_u64_u32(sort_temp, temp_bytes, k_a, k_b, v_b, v_a, n, 0, std::max(1u, bit_length(p.nbins)), ctx->stream));
         }
         {
             ProfScope ps(ctx, "nss_rank");
             hipLaunchKernelGGL(ns_starts_kernel, gridn, dim3(SM_BLOCK), 0, ctx->stream, k_b, (uint32_t)n, p.nbins, start);
             hipLaunchKernelGGL(ns_rank_keys_kernel, gridn, dim3(SM_BLOCK), 0, ctx->stream, k_b, v_a, start, cnt_dev, (uint32_t)n, p, k_a);
-            PCR_HIP(ctx, sort_pairs_u64_u32(s + off_temp, temp_bytes, k_a, k_b, v_a, v_b, n, 0, rank_bits + 1, ctx->stream));
+            PCR_HIP(ctx, sort_pairs_u64_u32(sort_temp, temp_bytes, k_a, k_b, v_a, v_b, n, 0, rank_bits + 1, ctx->stream));
         }
         order = v_b;
         hipError_t e = hipGetLastError();

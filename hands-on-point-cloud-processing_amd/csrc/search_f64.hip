@@ -206,11 +206,11 @@ int launch_knn_f64(pcr_ctx* ctx, const double* db_soa, size_t n, size_t n_cap, c
     int32_t* pidx = idx_dev;
     double* pdist = dist_dev;
     if (slices > 1) {
-        const size_t pd = (((size_t)slices * m * (size_t)k * 8) + 255) & ~(size_t)255;
-        int rc = ensure_aux(ctx, pd + (size_t)slices * m * (size_t)k * 4 + 256);
+        Layout L;
+        L.add(&pdist, (size_t)slices * m * (size_t)k);
+        L.add(&pidx, (size_t)slices * m * (size_t)k);
+        int rc = bind_aux(ctx, L);
         if (rc) return rc;
-        pdist = (double*)ctx->aux;
-        pidx = (int32_t*)((char*)ctx->aux + pd);
     }
     ProfScope p(ctx, "knn_f64");
 #define PCR_KNN(K)                                                                                              \
@@ -388,15 +388,18 @@ extern "C" int pcr_db64_knn(pcr_ctx* ctx, const pcr_db64* db, const double* q, s
         }
     }
     const size_t m_cap = ((m + SF_TILE - 1) / SF_TILE) * SF_TILE;
-    const size_t bytes_q = 3 * m_cap * 8, bytes_i = m * (size_t)k * 4, bytes_d = m * (size_t)k * 8;
-    const size_t off_d = bytes_q, off_i = off_d + ((bytes_d + 63) & ~(size_t)63);
-    int rc = ensure_scratch(ctx, off_i + bytes_i + 64);
+    double *q_dev, *dist_dev;
+    int32_t* idx_dev;
+    Layout L;
+    L.add(&q_dev, 3 * m_cap);
+    L.add(&dist_dev, m * (size_t)k);
+    L.add(&idx_dev, m * (size_t)k);
+    int rc = bind_scratch(ctx, L);
     if (rc) return rc;
-    char* s = (char*)ctx->scratch;
-    if ((rc = upload_soa_f64(ctx, q, m, m_cap, (double*)s))) return rc;
-    if ((rc = launch_knn_f64(ctx, db->dev, db->n, db->cap, (double*)s, m, k, (int32_t*)(s + off_i), (double*)(s + off_d), squared != 0))) return rc;
-    PCR_HIP(ctx, hipMemcpyAsync(idx, s + off_i, bytes_i, hipMemcpyDeviceToHost, ctx->stream));
-    PCR_HIP(ctx, hipMemcpyAsync(dist, s + off_d, bytes_d, hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = upload_soa_f64(ctx, q, m, m_cap, q_dev))) return rc;
+    if ((rc = launch_knn_f64(ctx, db->dev, db->n, db->cap, q_dev, m, k, idx_dev, dist_dev, squared != 0))) return rc;
+    PCR_HIP(ctx, hipMemcpyAsync(idx, idx_dev, m * (size_t)k * 4, hipMemcpyDeviceToHost, ctx->stream));
+    PCR_HIP(ctx, hipMemcpyAsync(dist, dist_dev, m * (size_t)k * 8, hipMemcpyDeviceToHost, ctx->stream));
     PCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return PCR_OK;
 }
@@ -448,16 +451,18 @@ extern "C" int pcr_db64_radius(pcr_ctx* ctx, const pcr_db64* db, const double* q
     // small batches: the database in slices (search_slices); counts and write offsets are per (query, slice), query-major
     const uint32_t slices = tune_get(ctx, "knn_slices", 1) == 1 ? search_slices(n, m, 16) : 1u;
     const size_t ms = m * (size_t)slices;
-    const size_t bytes_q = 3 * m_cap * 8, bytes_c = (ms + 1) * 8;
-    const size_t off_c = bytes_q;
-    int rc = ensure_scratch(ctx, off_c + bytes_c + 64);
+    double* q_dev;
+    unsigned long long* cnt_dev;       // pass 1: counts; pass 2: the ms + 1 write offsets
+    Layout L;
+    L.add(&q_dev, 3 * m_cap);
+    L.add(&cnt_dev, ms + 1);
+    int rc = bind_scratch(ctx, L);
     if (rc) return rc;
-    char* s = (char*)ctx->scratch;
-    if ((rc = upload_soa_f64(ctx, q, m, m_cap, (double*)s))) return rc;
+    if ((rc = upload_soa_f64(ctx, q, m, m_cap, q_dev))) return rc;
     // pass 1: counts -> exclusive scan on the host
-    if ((rc = launch_radius_count(ctx, db->dev, n, n_cap, (double*)s, m, r2max, (unsigned long long*)(s + off_c), slices))) return rc;
+    if ((rc = launch_radius_count(ctx, db->dev, n, n_cap, q_dev, m, r2max, cnt_dev, slices))) return rc;
     std::vector<unsigned long long> cnt(ms);
-    PCR_HIP(ctx, hipMemcpyAsync(cnt.data(), s + off_c, ms * 8, hipMemcpyDeviceToHost, ctx->stream));
+    PCR_HIP(ctx, hipMemcpyAsync(cnt.data(), cnt_dev, ms * 8, hipMemcpyDeviceToHost, ctx->stream));
     PCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
     std::vector<long long> offs(ms + 1);
     int64_t acc = 0;
@@ -475,9 +480,9 @@ extern "C" int pcr_db64_radius(pcr_ctx* ctx, const pcr_db64* db, const double* q
     PCR_HIP(ctx, hipMalloc((void**)&idx_dev, total * 4));
     hipError_t e = hipMalloc((void**)&dist_dev, total * 8);
     if (e != hipSuccess) { hipFree(idx_dev); return fail(ctx, PCR_ERR_HIP, "hipMalloc(radius)", e); }
-    e = hipMemcpyAsync(s + off_c, offs.data(), (ms + 1) * 8, hipMemcpyHostToDevice, ctx->stream);
+    e = hipMemcpyAsync(cnt_dev, offs.data(), (ms + 1) * 8, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess)
-        rc = launch_radius_fill(ctx, db->dev, n, n_cap, (double*)s, m, r2max, (const long long*)(s + off_c), idx_dev, dist_dev, slices);
+        rc = launch_radius_fill(ctx, db->dev, n, n_cap, q_dev, m, r2max, (const long long*)cnt_dev, idx_dev, dist_dev, slices);
     if (e == hipSuccess && rc == PCR_OK) e = hipMemcpyAsync(idx, idx_dev, total * 4, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess && rc == PCR_OK) e = hipMemcpyAsync(dist, dist_dev, total * 8, hipMemcpyDeviceToHost, ctx->stream);
     hipError_t e2 = hipStreamSynchronize(ctx->stream);

@@ -157,30 +157,31 @@ extern "C" int pcr_voxel_filter_f32(pcr_ctx* ctx, const pcr_cloud* in, double le
     // 2. keys + stable sort
     size_t temp_bytes = 0;
     sort_pairs_u64_u32(nullptr, temp_bytes, nullptr, nullptr, nullptr, nullptr, n, 0, 64, ctx->stream);
-    const size_t kb = ((n * 8 + 255) & ~(size_t)255), vb = ((n * 4 + 255) & ~(size_t)255);
-    const size_t nb = (n + 1 + SCAN_TILE - 1) / SCAN_TILE;
-    const size_t off_kout = kb, off_vin = 2 * kb, off_vout = 2 * kb + vb, off_flags = 2 * kb + 2 * vb, off_gid = off_flags + vb,
-                 off_starts = off_gid + vb, off_tot = off_starts + vb + 256, off_temp = off_tot + ((nb + 2) * 4 + 255 & ~(size_t)255);
-    rc = ensure_scratch(ctx, off_temp + temp_bytes + 256);
+    unsigned long long *k_in, *k_out;
+    uint32_t *v_in, *v_out, *flags, *gid, *starts, *totals, *groups_dev;
+    void* sort_temp;
+    Layout L;
+    L.add(&k_in, n);
+    L.add(&k_out, n);
+    L.add(&v_in, n);
+    L.add(&v_out, n);
+    L.add(&flags, n);
+    L.add(&gid, n);
+    L.add(&starts, n);
+    L.add(&totals, scan_blocks(n));
+    L.add(&groups_dev, 1);       // the scan's grand total
+    L.add(&sort_temp, temp_bytes);
+    rc = bind_scratch(ctx, L);
     if (rc) return rc;
-    char* s = (char*)ctx->scratch;
-    unsigned long long* k_in = (unsigned long long*)s;
-    unsigned long long* k_out = (unsigned long long*)(s + off_kout);
-    uint32_t* v_in = (uint32_t*)(s + off_vin);
-    uint32_t* v_out = (uint32_t*)(s + off_vout);
-    uint32_t* flags = (uint32_t*)(s + off_flags);
-    uint32_t* gid = (uint32_t*)(s + off_gid);
-    uint32_t* starts = (uint32_t*)(s + off_starts);
-    uint32_t* totals = (uint32_t*)(s + off_tot);
     const dim3 gridn((unsigned)((n + VX_BLOCK - 1) / VX_BLOCK));
     hipLaunchKernelGGL(vx_keys_kernel, gridn, dim3(VX_BLOCK), 0, ctx->stream, in->x(), in->y(), in->z(), (uint32_t)n, p, k_in, v_in);
-    PCR_HIP(ctx, sort_pairs_u64_u32(s + off_temp, temp_bytes, k_in, k_out, v_in, v_out, n, 0, 64, ctx->stream));
+    PCR_HIP(ctx, sort_pairs_u64_u32(sort_temp, temp_bytes, k_in, k_out, v_in, v_out, n, 0, 64, ctx->stream));
     // 3. segments
     hipLaunchKernelGGL(vx_heads_kernel, gridn, dim3(VX_BLOCK), 0, ctx->stream, k_out, (uint32_t)n, flags);
-    rc = exclusive_scan_u32(ctx, flags, gid, n, totals, totals + nb);
+    rc = exclusive_scan_u32(ctx, flags, gid, n, totals, groups_dev);
     if (rc) return rc;
     uint32_t groups = 0;
-    PCR_HIP(ctx, hipMemcpyAsync(&groups, totals + nb, 4, hipMemcpyDeviceToHost, ctx->stream));
+    PCR_HIP(ctx, hipMemcpyAsync(&groups, groups_dev, 4, hipMemcpyDeviceToHost, ctx->stream));
     PCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
     hipLaunchKernelGGL(vx_starts_kernel, gridn, dim3(VX_BLOCK), 0, ctx->stream, flags, gid, (uint32_t)n, starts);
     const size_t n_out = groups ? groups - 1 : 0;        // the last voxel is never emitted
