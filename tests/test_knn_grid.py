@@ -215,7 +215,9 @@ def test_gpu_db64_radius_grid_route_equals_exhaustive_scan(pcr, orc, synth):
             grow, gidx, gdist = h.radius(q, r)
             assert np.array_equal(brow, grow), r
             assert np.array_equal(bidx, gidx) and np.array_equal(bdist.view(np.uint64), gdist.view(np.uint64)), r
-        assert (bdist == r_edge).any() or True
+            if r == r_edge:
+                edge_dist = bdist
+        assert (edge_dist == r_edge).any()                               # the inclusive boundary: r_edge is one of this kernel's own distances
         # every point queries its own cloud (benchmark.hpp protocol); the oracle on a sample
         ctx.tune("radius_method", 2)
         row, idx, dist = h.radius(db, 0.5)
