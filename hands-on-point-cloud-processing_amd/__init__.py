@@ -63,7 +63,7 @@ ABI_SYMBOLS = [
     "pcr_device_count", "pcr_ctx_create", "pcr_ctx_destroy", "pcr_ctx_sync", "pcr_ctx_last_error", "pcr_version", "pcr_ctx_device_info",
     "pcr_cloud_create", "pcr_cloud_clone", "pcr_cloud_assign", "pcr_cloud_read", "pcr_cloud_size", "pcr_cloud_destroy",
     "pcr_nn1_f32", "pcr_nn1_f32_async", "pcr_nn1_fetch", "pcr_transform_f32", "pcr_kabsch_sums", "pcr_kabsch_solve", "pcr_kabsch_grid_exponent", "pcr_kabsch_limbs_to_sums",
-    "pcr_icp_p2p_f32", "pcr_plane_count_f64", "pcr_plane_mask_f64", "pcr_knn_f64", "pcr_radius_f64",
+    "pcr_icp_p2p_f32", "pcr_icp_last_chain", "pcr_icp_move_route", "pcr_plane_count_f64", "pcr_plane_mask_f64", "pcr_knn_f64", "pcr_radius_f64",
     "pcr_comm_unique_id", "pcr_comm_init_rccl", "pcr_comm_init_callback", "pcr_comm_destroy", "pcr_comm_selftest", "pcr_shard_range",
     "pcr_prof_reset", "pcr_prof_get", "pcr_prof_get_each", "pcr_tune_set",
     "pcr_grid_stats", "pcr_nn1_stats", "pcr_selftest_mfma_bf16", "pcr_selftest_mfma_f16", "pcr_selftest_mfma_bf16_v2", "pcr_selftest_mfma_f16_v2", "pcr_selftest_sign_f16", "pcr_selftest_sphere_f16", "pcr_ctx_mfma_check", "pcr_voxel_filter_f32", "pcr_iss_keypoints_f32", "pcr_icp_p2plane_f32", "pcr_cloud_knn_f64", "pcr_normals_knn_f64", "pcr_cloud_pca_f64", "pcr_fast_eigen3x3", "pcr_ground_seeds_f64", "pcr_ground_detection_f64",
@@ -119,6 +119,8 @@ def lib():
     L.pcr_kabsch_grid_exponent.argtypes = [C.c_float, C.c_float]
     L.pcr_kabsch_limbs_to_sums.argtypes = [vp, C.c_int, vp]
     L.pcr_icp_p2p_f32.argtypes = [vp, vp, vp, vp, C.POINTER(IcpParams), vp, C.POINTER(IcpStats)]
+    L.pcr_icp_last_chain.argtypes = [vp]
+    L.pcr_icp_move_route.argtypes = [C.c_uint64, C.c_uint64, C.c_int] + [C.c_int64] * 7
     L.pcr_plane_count_f64.argtypes = [vp, vp, vp, sz, C.c_double, vp]
     L.pcr_plane_mask_f64.argtypes = [vp, vp, vp, C.c_double, vp, C.POINTER(C.c_int64)]
     L.pcr_knn_f64.argtypes = [vp, vp, sz, vp, sz, C.c_int, vp, vp]
@@ -216,6 +218,14 @@ def shard_range(n: int, nranks: int, rank: int):
     b, e = C.c_size_t(), C.c_size_t()
     lib().pcr_shard_range(n, nranks, rank, C.byref(b), C.byref(e))
     return b.value, e.value
+
+
+def icp_move_route(n_src: int, n_tgt: int, nranks: int = 1, move_in_search: int = 0, fused_sums: int = 0, fused_sums_min: int = 0,
+                   s3_transposed: int = 0, sphere_qg: int = 0, sphere_l0_per_slice: int = 0, sphere_blocks: int = 0) -> bool:
+    """Would a single-rank exhaustive ICP loop whose searches take the three-level sphere kernel let the next search move the cloud
+    (pcr_icp_move_route; raw tune values, 0 = default; host logic, no GPU)?"""
+    return bool(lib().pcr_icp_move_route(n_src, n_tgt, nranks, move_in_search, fused_sums, fused_sums_min, s3_transposed, sphere_qg,
+                                         sphere_l0_per_slice, sphere_blocks))
 
 
 def fast_eigen3x3(A):
@@ -1118,6 +1128,11 @@ class Context:
         self._ck(lib().pcr_icp_p2p_f32(self.h, src.h, tgt.h, T0.ctypes.data, C.byref(prm), out.ctypes.data, C.byref(st)))
         stats = {f: getattr(st, f) for f, _ in IcpStats._fields_ if f != "reserved"}
         return out.reshape(4, 4), stats
+
+    def icp_last_chain(self) -> int:
+        """The tail of the last icp_point2point call's iterations (pcr_icp_last_chain): 0 synchronous loop, 1 separate launches, 2 solve + move,
+        3 sums + solve + move, 4 sums + solve with the move in the next search."""
+        return int(lib().pcr_icp_last_chain(self.h))
 
     # ---- A10
     def plane_count(self, pts: Cloud, planes4, thr: float) -> np.ndarray:

@@ -27,6 +27,23 @@ static int icp_sort_for_brute(pcr_ctx* ctx, const pcr_cloud* tgt, pcr_cloud** wo
     return bt_sort_working_cloud(ctx, tgt, work);
 }
 
+// The chain search (moves the cloud by the previous solve) -> sums + solve: the loop's own conditions and the search's (nn1_brute.hip
+// s3_move_route), from plain numbers — raw tune values, 0 = default.  One rank; tune icp_move_in_search: 0 = auto, 1 = on where possible, 2 = off; the switch
+// and the lower bound of the fused sums launch (icp_fused_sums = 2 keeps the three-launch chain, icp_fused_sums_min); STRACK3 in its transposed form with one
+// slice of n_l0 level-0 super-tiles.  (What only the running loop knows — the solve + move fused at all, an exhaustive search that seeds itself, the kernel
+// family the dispatcher really took — is checked there.)
+// Auto = on: the headline A/B of profiles/icp_move_in_search.txt (61.8 -> 59.0 us per step of the bench line, a gain by the rule).
+constexpr bool ICP_MOVE_IN_SEARCH_AUTO = true;
+bool pcr::icp_move_route(uint64_t n_src, uint64_t n_l0, int nranks, int64_t move_in_search_tune, int64_t fused_sums_tune, int64_t fused_sums_min_tune,
+                         int64_t transposed_tune, int64_t qg_tune, int64_t l0_per_slice_tune, int64_t blocks_tune)
+{
+    if (nranks != 1 || n_src == 0) return false;
+    if (move_in_search_tune == 2 || (move_in_search_tune != 1 && !ICP_MOVE_IN_SEARCH_AUTO)) return false;
+    if (fused_sums_tune != 0 && fused_sums_tune != 1) return false;
+    if ((int64_t)n_src < (fused_sums_min_tune ? fused_sums_min_tune : 60000)) return false;
+    return s3_move_route(n_l0, n_src, transposed_tune, qg_tune, l0_per_slice_tune, blocks_tune);
+}
+
 // ---- synchronous loop: one host round trip per iteration (needed by the host-callback transport; also the
 // reference implementation of the loop the pipelined variant below must reproduce bit for bit)
 static int icp_sync(pcr_ctx* ctx, const pcr_cloud* src, const pcr_cloud* tgt, const float init_T[16],
@@ -37,6 +54,7 @@ static int icp_sync(pcr_ctx* ctx, const pcr_cloud* src, const pcr_cloud* tgt, co
     memset(&st, 0, sizeof st);
     const LoopHint hint(ctx, prm->max_iter);
     ctx->keys_seeded = false;            // (seeds a move of an earlier loop left behind describe positions that no longer exist)
+    ctx->icp_last_chain = 0;
 
     // prof bookkeeping: report only this call's nn1 time
     PCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -144,6 +162,7 @@ static int icp_pipelined(pcr_ctx* ctx, const pcr_cloud* src, const pcr_cloud* tg
     memset(&st, 0, sizeof st);
     const LoopHint hint(ctx, prm->max_iter);
     ctx->keys_seeded = false;            // (seeds a move of an earlier loop left behind describe positions that no longer exist)
+    ctx->icp_last_chain = 0;
     PCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
     prof_flush(ctx);
     const uint64_t nn_l0 = ctx->prof["nn1_brute"].launches + ctx->prof["nn1_grid"].launches;
@@ -204,6 +223,15 @@ static int icp_pipelined(pcr_ctx* ctx, const pcr_cloud* src, const pcr_cloud* tg
     // otherwise the three-launch chain.  Exhaustive loops only by default: the kernel serves the grid loop too (targets by index; icp_fused_sums_grid = 1,
     // same bits), but that was measured only at hw9's 4 000 points, where it loses
     const bool fused_sums = fused && (!icp_uses_grid(ctx, tgt) || tune_get(ctx, "icp_fused_sums_grid", 0) == 1) && icp_fused_sums_blocks(ctx, work->n) != 0;
+    // A third chain (tune icp_move_in_search: 2 = off): search -> sums + solve (kabsch.hip icp_sums_solve_kernel), and the search of iteration
+    // k + 1 moves the cloud by the Rd, td of solve k while it loads its queries, seeding itself on the way (nn1_sphere.hpp, MV) — no grid barrier, no
+    // residency condition, and no move at all behind the last solve: the working cloud is released, only T_total is returned.  Conditions: those of the
+    // fused solve + move above, a search that seeds itself (seed_tgt), the switch and the lower bound of the fused sums launch, and STRACK3 in its transposed
+    // form with ONE slice (every target of up to 131 072 records; larger ones where the queries alone fill the launch) — icp_move_route.  The dispatcher decides the kernel family late, so the chain is chosen behind
+    // the FIRST search, which runs as ever (nothing to move yet): if it did not take STRACK3, the whole call keeps one of the chains above; a later search
+    // that cannot carry the move is an error of the dispatcher, not a fallback.
+    const bool move_cand = fused && seed_tgt && icp_sums_solve_blocks(ctx, work->n) != 0;
+    bool move_in_search = false;
     // (Measured and dropped, round 4: the Kabsch sums taken by the search kernel itself — STRACK3 ends with every query's final key in one wave, so each
     // wave added its 32 pairs' limbs (wave sums, a row per workgroup, f64 atomics into 64 rows; same bits) and the streaming pass + its launch gap
     // (7 + 4.5 us) went away: the search grew from 0.034 to 0.049 ms — 41 limbs x 6 f64 shuffle-adds per wave, four waves per SIMD ending together on
@@ -218,7 +246,20 @@ static int icp_pipelined(pcr_ctx* ctx, const pcr_cloud* src, const pcr_cloud* tg
         for (int64_t c = 0; rc == PCR_OK && c < chunk && enq < prm->max_iter; c++, enq++) {   // :917
             IcpState* cur = fused ? dev + (enq & 1) : dev;                                        // the state this iteration starts from
             ctx->stop_flag_dev = &cur->stop;     // correspondence kernels no-op once stop or stop_after_transform is set
-            if ((rc = launch_nn1(ctx, tgt, work, true, gate))) break;                             // :925-934
+            ctx->nn1_move_state = move_in_search ? cur : nullptr;        // (iteration 0 decides: nothing to move in front of it)
+            rc = launch_nn1(ctx, tgt, work, true, gate);                                          // :925-934
+            ctx->nn1_move_state = nullptr;
+            if (rc) break;
+            if (enq == 0)
+                move_in_search = move_cand && ctx->nn1_move_l0 != 0 &&
+                                 icp_move_route(work->n, ctx->nn1_move_l0, nranks, tune_get(ctx, "icp_move_in_search", 0), tune_get(ctx, "icp_fused_sums", 0),
+                                                tune_get(ctx, "icp_fused_sums_min", 0), tune_get(ctx, "nn1_s3_transposed", 0), tune_get(ctx, "nn1_sphere_qg", 0),
+                                                tune_get(ctx, "nn1_sphere_l0_per_slice", 0), tune_get(ctx, "nn1_sphere_blocks", 0));
+            else if (move_in_search && !ctx->nn1_moved) { rc = fail(ctx, PCR_ERR_STATE, "ICP: a search of the chain search -> sums + solve did not move the cloud"); break; }
+            if (move_in_search) {
+                if ((rc = launch_icp_sums_solve(ctx, tgt, work, prm->max_corr, cur, dev + ((enq + 1) & 1), plan))) break;                            // :936-1002
+                continue;
+            }
             if (fused_sums) {
                 if ((rc = launch_icp_sums_update_move(ctx, tgt, work, prm->max_corr, cur, dev + ((enq + 1) & 1), plan, seed_tgt))) break;   // :936-1003
                 continue;
@@ -263,6 +304,7 @@ static int icp_pipelined(pcr_ctx* ctx, const pcr_cloud* src, const pcr_cloud* tg
     }
     cloud_release(ctx, work);             // (synchronised above; the loop's own working copy: parked for the next call's clone)
     if (rc) return rc;
+    ctx->icp_last_chain = move_in_search ? 4 : fused_sums ? 3 : fused ? 2 : 1;
     const IcpState& f = host[RING];
     if (f.overflow) return fail(ctx, PCR_ERR_STATE, "ICP: a kept source point lies more than 2^20 target extents away from the target");
     if (f.barrier_timeout) {
@@ -282,6 +324,15 @@ static int icp_pipelined(pcr_ctx* ctx, const pcr_cloud* src, const pcr_cloud* tg
     st.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
     if (stats) *stats = st;
     return PCR_OK;
+}
+
+extern "C" int pcr_icp_last_chain(const pcr_ctx* ctx) { return ctx ? ctx->icp_last_chain : 0; }
+
+extern "C" int pcr_icp_move_route(uint64_t n_src, uint64_t n_tgt, int nranks, int64_t move_in_search, int64_t fused_sums, int64_t fused_sums_min,
+                                  int64_t s3_transposed, int64_t sphere_qg, int64_t sphere_l0_per_slice, int64_t sphere_blocks)
+{
+    return icp_move_route(n_src, s3_l0_super_tiles(n_tgt), nranks, move_in_search, fused_sums, fused_sums_min, s3_transposed, sphere_qg, sphere_l0_per_slice,
+                          sphere_blocks) ? 1 : 0;
 }
 
 extern "C" int pcr_icp_p2p_f32(pcr_ctx* ctx, const pcr_cloud* src, const pcr_cloud* tgt, const float init_T[16],

@@ -805,6 +805,151 @@ __global__ __launch_bounds__(T) void icp_sums_update_move_kernel(
     }
 }
 
+// A thread's four consecutive pairs as icp_sums_update_move_kernel reads them — points, keys, original indices and the gathered target points, everything
+// that depends on nothing else requested in one go — for icp_sums_solve_kernel below.  (That kernel keeps its own copy of these lines: routed through
+// these functions it took 156 VGPRs instead of 142, and it is the path of every loop the chain below does not serve.)
+struct FsPairs {
+    float4 px, py, pz;
+    unsigned long long sk[4];              // (no pair: NaN distance, no target)
+    uint32_t og[4];
+    float sq[4][3];
+};
+
+__device__ __forceinline__ void fs_load_pairs(FsPairs& P, bool mine, uint32_t i, uint32_t n, const float* x, const float* y, const float* z,
+                                              const unsigned long long* keys, const uint32_t* __restrict__ orig, const float* __restrict__ tx,
+                                              const float* __restrict__ ty, const float* __restrict__ tz, uint32_t nt)
+{
+    const uint32_t base = 4 * i;
+    P.px = make_float4(0.f, 0.f, 0.f, 0.f); P.py = P.px; P.pz = P.px;
+#pragma unroll
+    for (int u = 0; u < 4; u++) { P.sk[u] = ~0ull; P.og[u] = base + u; }
+    if (mine) {
+        P.px = reinterpret_cast<const float4*>(x)[i]; P.py = reinterpret_cast<const float4*>(y)[i]; P.pz = reinterpret_cast<const float4*>(z)[i];
+        if (base + 3 < n) {
+            const ulonglong2 k01 = reinterpret_cast<const ulonglong2*>(keys)[2 * i], k23 = reinterpret_cast<const ulonglong2*>(keys)[2 * i + 1];
+            P.sk[0] = k01.x; P.sk[1] = k01.y; P.sk[2] = k23.x; P.sk[3] = k23.y;
+            if (orig) { const uint4 o = reinterpret_cast<const uint4*>(orig)[i]; P.og[0] = o.x; P.og[1] = o.y; P.og[2] = o.z; P.og[3] = o.w; }
+        } else {
+#pragma unroll
+            for (int u = 0; u < 4; u++)
+                if (base + u < n) { P.sk[u] = keys[base + u]; if (orig) P.og[u] = orig[base + u]; }
+        }
+    }
+    // the target points of the four pairs, gathered ONCE: nothing else in this launch needs them
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+        P.sq[u][0] = 0.f; P.sq[u][1] = 0.f; P.sq[u][2] = 0.f;
+        const uint32_t j = (uint32_t)(P.sk[u] & 0xFFFFFFFFull);
+        if (j < nt) { P.sq[u][0] = tx[j]; P.sq[u][1] = ty[j]; P.sq[u][2] = tz[j]; }
+    }
+}
+
+// ... and their limbs, added exactly as the sums pass adds them (kabsch_partial_kernel's gate, term for term), reduced to the workgroup's row
+template <int WAVES>
+__device__ __forceinline__ void fs_pairs_row(const FsPairs& P, float max_corr, const KabschPlan& plan, uint32_t nt, double (&red_l)[WAVES][KB_NL],
+                                             double (&row)[KB_ROW])
+{
+    double c0[6], c1[6], p0[9], p1[9], p2[9], cnt = 0.0;
+#pragma unroll
+    for (int k = 0; k < 6; k++) { c0[k] = 0.0; c1[k] = 0.0; }
+#pragma unroll
+    for (int k = 0; k < 9; k++) { p0[k] = 0.0; p1[k] = 0.0; p2[k] = 0.0; }
+    unsigned long long lastkey = 0;
+    int overflow = 0;
+    const float sx4[4] = { P.px.x, P.px.y, P.px.z, P.px.w }, sy4[4] = { P.py.x, P.py.y, P.py.z, P.py.w }, sz4[4] = { P.pz.x, P.pz.y, P.pz.z, P.pz.w };
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+        const uint32_t d2b = (uint32_t)(P.sk[u] >> 32);
+        const float d2 = __uint_as_float(d2b);
+        const uint32_t j = (uint32_t)(P.sk[u] & 0xFFFFFFFFull);
+        if (d2 < max_corr && j < nt) {                       // registration.cpp:936 (kabsch_partial_kernel's gate, term for term)
+            const float pf0 = sx4[u], pf1 = sy4[u], pf2 = sz4[u];
+            if (!(fabsf(pf0) < plan.lim && fabsf(pf1) < plan.lim && fabsf(pf2) < plan.lim)) { overflow = 1; continue; }
+            const double Pd[3] = { pf0, pf1, pf2 }, Q[3] = { P.sq[u][0], P.sq[u][1], P.sq[u][2] };
+#pragma unroll
+            for (int c = 0; c < 3; c++) { acc2(Pd[c], plan.sc, c0[c], c1[c]); acc2(Q[c], plan.sc, c0[3 + c], c1[3 + c]); }
+#pragma unroll
+            for (int r = 0; r < 3; r++)
+#pragma unroll
+                for (int c = 0; c < 3; c++) acc3(Q[r] * Pd[c], plan.sp, p0[3 * r + c], p1[3 * r + c], p2[3 * r + c]);
+            cnt += 1.0;
+            const unsigned long long lk = ((unsigned long long)P.og[u] << 32) | d2b;
+            lastkey = lk > lastkey ? lk : lastkey;
+        }
+    }
+    double tn[KB_NL];                    // at most 4 terms per thread: no per-thread carries
+#pragma unroll
+    for (int c = 0; c < 6; c++) { tn[3 * c] = c0[c]; tn[3 * c + 1] = c1[c]; tn[3 * c + 2] = 0.0; }
+#pragma unroll
+    for (int k = 0; k < 9; k++) { tn[18 + 4 * k] = p0[k]; tn[19 + 4 * k] = p1[k]; tn[20 + 4 * k] = p2[k]; tn[21 + 4 * k] = 0.0; }
+    tn[54] = cnt;
+    block_reduce_limbs<true>(tn, lastkey, overflow, red_l, row, false);
+}
+
+// Exhaustive loops whose NEXT SEARCH moves the cloud (nn1_sphere.hpp, MV): the sums and the solve alone.  The front half is that of
+// icp_sums_update_move_kernel — same loads, same gate, same limbs, same row, same release — but nobody waits: every workgroup takes a TICKET from the same
+// monotonic counter (every workgroup of every launch arrives, in every phase; the host passes the value the counter has once all of this launch have), and
+// the ONE workgroup whose ticket is the last acquires, reduces the gridDim.x rows, solves and publishes the whole state to st_out; every other workgroup
+// returns.  No spin, no residency condition on the grid: the move needs the new R, t, but the move is the next launch's — the search loads every query
+// anyway and applies Rd, td of the state it reads its stop flags from.  Phases 0 and 1 (stopped loop, stop_after_transform): the last arriver writes the
+// stopped state, as workgroup 0 of the other kernel does.
+template <int T>
+__global__ __launch_bounds__(T) void icp_sums_solve_kernel(
+    const float* __restrict__ tx, const float* __restrict__ ty, const float* __restrict__ tz, const uint32_t* __restrict__ orig,
+    const unsigned long long* __restrict__ keys, uint32_t nt, float max_corr, KabschPlan plan, double* partials, unsigned long long* counter,
+    unsigned long long target, const IcpState* __restrict__ st_in, IcpState* __restrict__ st_out, double* __restrict__ out, const float* __restrict__ x,
+    const float* __restrict__ y, const float* __restrict__ z, uint32_t n, uint32_t n4)
+{
+    constexpr int WAVES = T / 64;
+    __shared__ double red_l[WAVES][KB_NL];
+    __shared__ double red[WAVES][64];
+    __shared__ double row[KB_ROW];
+    __shared__ double o18[19];
+    __shared__ IcpState s_st;
+    __shared__ int s_last;
+    const uint32_t i = blockIdx.x * T + threadIdx.x;
+    uint32_t stw = 0;                       // (the state first: it is on the critical path and loads retire in order)
+    if (threadIdx.x < ST_WORDS) stw = reinterpret_cast<const uint32_t*>(st_in)[threadIdx.x];
+    FsPairs P;
+    fs_load_pairs(P, i < n4, i, n, x, y, z, keys, orig, tx, ty, tz, nt);
+    if (threadIdx.x < ST_WORDS) reinterpret_cast<uint32_t*>(&s_st)[threadIdx.x] = stw;
+    __syncthreads();
+    const int phase = (s_st.stop || s_st.barrier_timeout) ? 0 : (s_st.stop_after_transform ? 1 : 2);       // uniform over the GRID
+    if (phase == 2) {
+        fs_pairs_row(P, max_corr, plan, nt, red_l, row);
+        if (threadIdx.x < KB_ROW) partials[(size_t)blockIdx.x * KB_ROW + threadIdx.x] = row[threadIdx.x];
+    }
+    // ---- the ticket: wave 0 stored the row; it drains its stores, its lane 0 releases and arrives; the last arriver acquires
+    if (threadIdx.x < 64) {
+        if (phase == 2) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (threadIdx.x == 0) {
+            if (phase == 2) {
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // (kept behind the fence whatever the compiler thinks of the scoreboard)
+            }
+            const int last = __hip_atomic_fetch_add(counter, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1ull == target;
+            if (last && phase == 2) {
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the invalidate is over before the barrier below lets the other waves read
+            }
+            s_last = last;
+        }
+    }
+    __syncthreads();
+    if (!s_last) return;
+    if (phase == 2) {
+        reduce_rows(partials, gridDim.x, red, row);
+        row_to_out18(row, plan.e, o18);
+        __syncthreads();
+        if (threadIdx.x < 19) out[threadIdx.x] = o18[threadIdx.x];
+        if (threadIdx.x == 0) icp_state_step(&s_st, o18, o18[16] >= 0.0, (float)o18[17], o18[18] != 0.0);
+    } else if (threadIdx.x == 0) {
+        s_st.stop = 1;                         // (phase 0: stays stopped; phase 1: max_iter reached, the loop is over)
+    }
+    __syncthreads();
+    if (threadIdx.x < ST_WORDS) reinterpret_cast<uint32_t*>(st_out)[threadIdx.x] = reinterpret_cast<const uint32_t*>(&s_st)[threadIdx.x];
+}
+
 // multi rank, step 1: reduce the block rows into the all-reduce buffer
 //   [0..54] normalised limbs, [55] overflow flag, [56 + 2r] ORDER KEY of rank r's last kept pair (0: it kept none), [57 + 2r] that pair's d2
 // (every entry is summed exactly by the all-reduce: integers below 2^40 x ranks, one non-zero pair of words per rank).  The order key
@@ -975,6 +1120,44 @@ int launch_icp_sums_update_move(pcr_ctx* ctx, const pcr_cloud* tgt, pcr_cloud* c
         if (fs_threads(ctx) == 256) PCR_FS(256); else PCR_FS(512);
 #undef PCR_FS
 #undef PCR_FS_EXTRA
+    }
+    PCR_HIP(ctx, hipGetLastError());
+    ctx->icp_barrier_arrived = target;        // (counted only once the launch is on the stream)
+    return PCR_OK;
+}
+
+// threads per workgroup of the sums + solve launch (4 pairs per thread; tune icp_sums_solve_threads: 128 / 256 / 512; profiles/icp_move_in_search.txt)
+static int ss_threads(const pcr_ctx* ctx)
+{
+    const int64_t t = tune_get(ctx, "icp_sums_solve_threads", 512);
+    return t == 128 ? 128 : t == 256 ? 256 : 512;
+}
+
+// the workgroups the sums + solve launch takes for n points, or 0 where it does not run: the switch and the lower bound of the fused sums + move launch
+// (icp_fused_sums = 2, icp_fused_sums_min), but no cap at one workgroup per CU — nobody waits for anybody
+uint32_t icp_sums_solve_blocks(const pcr_ctx* ctx, size_t n)
+{
+    if (n == 0 || tune_get(ctx, "icp_fused_sums", 1) != 1 || (int64_t)n < tune_get(ctx, "icp_fused_sums_min", 60000)) return 0;
+    const uint64_t T = (uint64_t)ss_threads(ctx), n4 = ((uint64_t)n + 3) / 4, blocks = (n4 + T - 1) / T;
+    return blocks <= (uint64_t)KB_MAX_BLOCKS ? (uint32_t)blocks : 0u;
+}
+
+int launch_icp_sums_solve(pcr_ctx* ctx, const pcr_cloud* tgt, const pcr_cloud* c, float max_corr, const IcpState* st_in, IcpState* st_out, const KabschPlan& plan)
+{
+    if (ctx->keys_n != c->n) return fail(ctx, PCR_ERR_STATE, "kabsch: no matching correspondence pass");
+    const uint32_t blocks = icp_sums_solve_blocks(ctx, c->n);
+    if (!blocks || !ctx->icp_barrier_dev) return fail(ctx, PCR_ERR_STATE, "launch_icp_sums_solve");
+    const uint32_t n4 = (uint32_t)((c->n + 3) / 4);
+    const unsigned long long target = ctx->icp_barrier_arrived + blocks;      // the counter's value once every workgroup of this launch has arrived
+    {
+        ProfScope p(ctx, "icp_update");
+#define PCR_SS(T)                                                                                                                                 \
+        hipLaunchKernelGGL((icp_sums_solve_kernel<T>), dim3(blocks), dim3(T), 0, ctx->stream, tgt->x(), tgt->y(), tgt->z(), c->orig, ctx->keys,      \
+                           (uint32_t)tgt->n, max_corr, plan, ctx->partials, ctx->icp_barrier_dev, target, st_in, st_out, ctx->dev_out, c->x(), c->y(), \
+                           c->z(), (uint32_t)c->n, n4)
+        const int T = ss_threads(ctx);
+        if (T == 128) PCR_SS(128); else if (T == 256) PCR_SS(256); else PCR_SS(512);
+#undef PCR_SS
     }
     PCR_HIP(ctx, hipGetLastError());
     ctx->icp_barrier_arrived = target;        // (counted only once the launch is on the stream)

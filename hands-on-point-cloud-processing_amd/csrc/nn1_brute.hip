@@ -1266,11 +1266,45 @@ static void seed_warm(pcr_ctx* ctx, const pcr_cloud* tgt, const pcr_cloud* src, 
                        (uint32_t)tgt->n, src->x(), src->y(), src->z(), (uint32_t)src->n, ctx->keys);
 }
 
+// STRACK3's launch: one wave per 32 x qg queries and slice of level-0 super-tiles (131 072 records each).  From plain numbers: the loop asks before it
+// has a launch to look at (s3_move_route)
+struct S3Geometry { uint32_t qg, qblocks, l0_per_slice, slices; };
+static S3Geometry s3_geometry(uint64_t n_l0, uint64_t ns, int64_t qg_tune, int64_t l0_per_slice_tune, int64_t blocks_tune)
+{
+    S3Geometry G;
+    G.qg = qg_tune == 4 ? 4u : qg_tune == 2 ? 2u : 1u;        // (one group of 32 queries per wave: 120 000 queries are 3 750 waves for 1 024 SIMDs — the search is a chain of
+                                                              // dependent trips to memory per wave, and waves are what hides them)
+    const uint64_t qpb = (uint64_t)(NN_BLOCK / 64) * 32 * G.qg;
+    G.qblocks = (uint32_t)((ns + qpb - 1) / qpb);
+    G.slices = 1;
+    G.l0_per_slice = slice_plan((uint32_t)n_l0, G.qblocks, l0_per_slice_tune, blocks_tune ? blocks_tune : 1024, &G.slices);
+    return G;
+}
+
+uint64_t s3_l0_super_tiles(uint64_t n_tgt)
+{
+    const uint64_t n_pad = (n_tgt + BT_SUPER - 1) / BT_SUPER * BT_SUPER;       // (bt_ensure pads to whole super-tiles of records, bt_ensure_l1 counts from there)
+    return (n_pad + BT_L0_SUPER - 1) / BT_L0_SUPER;
+}
+
+// Can a seeded STRACK3 search of ns queries over n_l0 level-0 super-tiles move its queries in place (nn1_strack3_move_kernel)?  Only the transposed
+// default form is built with the move, and only ONE slice is safe: with more, several workgroups read a query block that one of them overwrites.
+// Raw tune values (0 = default), no context: pure host logic (pcr_icp_move_route)
+bool s3_move_route(uint64_t n_l0, uint64_t ns, int64_t transposed_tune, int64_t qg_tune, int64_t l0_per_slice_tune, int64_t blocks_tune)
+{
+    if (ns == 0 || n_l0 == 0 || transposed_tune == 2) return false;
+    return s3_geometry(n_l0, ns, qg_tune, l0_per_slice_tune, blocks_tune).slices == 1;
+}
+
 // HTRACK / BTRACK over the target's Morton-ordered operands (bt_ensure)
 static int launch_matrix(pcr_ctx* ctx, const pcr_cloud* tgt, const pcr_cloud* src, bool f16, bool warm, bool pre_seeded, bool force_sign)
 {
     const BtIndex* g = tgt->bt;
     const size_t ns = src->n;
+    // the loop's chain search -> sums + solve (icp.cpp): this search moves its queries by the pending Rd, td of that state and seeds itself from the
+    // previous correspondences on the way — nothing to seed in front of it.  It is STRACK3's move-carrying form or an error, never another kernel
+    const IcpState* const move_state = ctx->nn1_move_state;
+    if (move_state) pre_seeded = true;
     // query groups (of 32) per wave: four amortise the per-tile operand loads best on a full batch; a source shard of a strong-scaling run
     // (15-30 k queries against the whole target) fills the chip better with two — measured, per ICP iteration: 15 k queries 0.158 -> 0.137
     // ms, 30 k 0.241 -> 0.218, 60 k 0.378 / 0.375, 120 k 0.664 -> 0.723
@@ -1315,6 +1349,10 @@ static int launch_matrix(pcr_ctx* ctx, const pcr_cloud* tgt, const pcr_cloud* sr
     }
     // (the sphere forms pay far less for a poor seed than STRACK does — tune nn1_sphere_reseed: 2 = a warm search keeps its stale seeds as they are)
     if (sphere && tune_get(ctx, "nn1_sphere_reseed", 0) == 2) reseed = false;
+    const int64_t s3_tr = tune_get(ctx, "nn1_s3_transposed", 0), s3_qg = tune_get(ctx, "nn1_sphere_qg", 0), s3_l0ps = tune_get(ctx, "nn1_sphere_l0_per_slice", 0),
+                  s3_blocks = tune_get(ctx, "nn1_sphere_blocks", 0);
+    ctx->nn1_move_l0 = sphere ? g->n_l0_super : 0;      // (what the loop asks after its first search: icp_move_route)
+    if (move_state && !(sphere && warm && s3_move_route(g->n_l0_super, ns, s3_tr, s3_qg, s3_l0ps, s3_blocks))) return fail(ctx, PCR_ERR_STATE, "nn1: this search cannot carry the loop's pending move (STRACK3, transposed, one slice)");
     ctx->last_nn1_kernel = sphere ? "strack3" : sign ? "strack" : f16 ? "htrack" : "btrack";
     if (warm) seed_warm(ctx, tgt, src, pre_seeded);
     else if (merge_atomic && !cold_seed) PCR_HIP(ctx, hipMemsetAsync(ctx->keys, 0xFF, ns * sizeof(unsigned long long), ctx->stream));
@@ -1354,13 +1392,9 @@ static int launch_matrix(pcr_ctx* ctx, const pcr_cloud* tgt, const pcr_cloud* sr
         if (sphere) {
             // one wave per 128 (64: tune nn1_sphere_qg = 2) queries and slice of level-0 super-tiles (131 072 records each: one slice up to there)
             const uint32_t n_l0 = (uint32_t)g->n_l0_super;
-            const int64_t qg3_t = tune_get(ctx, "nn1_sphere_qg", 0);
-            const uint32_t qg3 = qg3_t == 4 ? 4u : qg3_t == 2 ? 2u : 1u;      // (one group of 32 queries per wave: 120 000 queries are 3 750 waves for 1 024 SIMDs — the search is a chain of
-                                                                           // dependent trips to memory per wave, and waves are what hides them)
-            const uint32_t qblocks3 = (uint32_t)((ns + (size_t)(NN_BLOCK / 64) * 32 * qg3 - 1) / ((size_t)(NN_BLOCK / 64) * 32 * qg3));
-            uint32_t s3_slices = 1;
-            const uint32_t l0ps = slice_plan(n_l0, qblocks3, tune_get(ctx, "nn1_sphere_l0_per_slice", 0), tune_get(ctx, "nn1_sphere_blocks", 1024), &s3_slices);
-            const dim3 grid3(qblocks3, s3_slices);
+            const S3Geometry G3 = s3_geometry(n_l0, ns, s3_qg, s3_l0ps, s3_blocks);
+            const uint32_t qg3 = G3.qg, l0ps = G3.l0_per_slice;
+            const dim3 grid3(G3.qblocks, G3.slices);
             const uint32_t s3_flush_end = (uint32_t)std::min<int64_t>(std::max<int64_t>(tune_get(ctx, "nn1_sphere_flush_end", 1), 1), S2_CAP);   // entries from which the end of a level-1 super-tile evaluates them
 #define PCR_STRACK3(Q)                                                                                                                     \
     hipLaunchKernelGGL((nn1_strack3_kernel<Q>), grid3, dim3(NN_BLOCK), 0, ctx->stream, g->l0_centres, g->l0_ops, g->l1_centres, g->l1_ops, g->l1_rec_ops, g->records,  \
@@ -1369,8 +1403,14 @@ static int launch_matrix(pcr_ctx* ctx, const pcr_cloud* tgt, const pcr_cloud* sr
 #define PCR_STRACK3_ROWS(Q)                                                                                                                \
     hipLaunchKernelGGL((nn1_strack3_rows_kernel<Q>), grid3, dim3(NN_BLOCK), 0, ctx->stream, g->l0_centres, g->l0_ops, g->l1_centres, g->l1_ops, g->l1_rec_ops, g->records,  \
                        n_super * BT_SUPER, n_l0, l0ps, src->x(), src->y(), src->z(), (uint32_t)ns, ctx->keys, ctx->stop_flag_dev, stats_dev, std::min<uint32_t>(st_flush_at, (uint32_t)S2_CAP), s3_flush_end)
-            if (tune_get(ctx, "nn1_s3_transposed", 1) == 2) { if (qg3 == 1) PCR_STRACK3_ROWS(1); else if (qg3 == 2) PCR_STRACK3_ROWS(2); else PCR_STRACK3_ROWS(4); }
+#define PCR_STRACK3_MOVE(Q)                                                                                                                \
+    hipLaunchKernelGGL((nn1_strack3_move_kernel<Q>), grid3, dim3(NN_BLOCK), 0, ctx->stream, g->l0_centres, g->l0_ops, g->l1_centres, g->l1_ops, g->l1_rec_ops, g->records,  \
+                       n_super * BT_SUPER, n_l0, l0ps, src->x(), src->y(), src->z(), (uint32_t)ns, ctx->keys, stats_dev, std::min<uint32_t>(st_flush_at, (uint32_t)S2_CAP), s3_flush_end, \
+                       S3Move{ move_state, tgt->x(), tgt->y(), tgt->z(), (uint32_t)tgt->n })
+            if (move_state) { if (qg3 == 1) PCR_STRACK3_MOVE(1); else if (qg3 == 2) PCR_STRACK3_MOVE(2); else PCR_STRACK3_MOVE(4); ctx->nn1_moved = true; }
+            else if (s3_tr == 2) { if (qg3 == 1) PCR_STRACK3_ROWS(1); else if (qg3 == 2) PCR_STRACK3_ROWS(2); else PCR_STRACK3_ROWS(4); }
             else if (qg3 == 1) PCR_STRACK3(1); else if (qg3 == 2) PCR_STRACK3(2); else PCR_STRACK3(4);
+#undef PCR_STRACK3_MOVE
 #undef PCR_STRACK3_ROWS
 #undef PCR_STRACK3
         }
@@ -1446,6 +1486,7 @@ int launch_nn1_brute(pcr_ctx* ctx, const pcr_cloud* tgt, const pcr_cloud* src, b
     // ... and the move of the previous iteration already turned them into this search's seeds (kabsch.hip seed_next_search)?
     const bool pre_seeded = warm && ctx->keys_seeded && ctx->keys_seed_src == src && ctx->keys_seed_tgt == tgt && ctx->keys_n == ns;
     ctx->keys_seeded = false;
+    ctx->nn1_move_l0 = 0; ctx->nn1_moved = false;      // (set by launch_matrix alone: every other family leaves "no")
     int rc = ensure_keys(ctx, ns);
     if (rc) return rc;
     ctx->keys_n = ns;

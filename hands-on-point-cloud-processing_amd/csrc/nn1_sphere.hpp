@@ -104,16 +104,40 @@ struct S3WaveLds {
 //          0.033-0.035 against 0.027-0.029 ms per settled 120 k search (profiles/strack3_transposed.txt).  Kept as nn1_strack3_rows_kernel for
 //          A/B runs in one process.
 // Both read the same index: bt_l0_ops_kernel / bt_l1_ops_kernel store the rows in the order the B role wants (see l1_chunk_operand).
-template <int QG, bool TR>
+//
+// MV: the search of an ICP loop that MOVES its own queries first (icp.cpp, the chain search -> sums + solve).  mv is the state the solve of
+// the previous iteration published (kabsch.hip icp_sums_solve_kernel): its stop flags are this launch's stop flags, its Rd, td the pending move.  A lane
+// loads its point and the previous winner's key as always, gathers that winner's target point, moves the point with transform_state_kernel's arithmetic
+// term for term — ((a x + b y) + c z) + t, unfused — and evaluates the seed of THIS search with seed_next_search's expression and gate (kabsch.hip): the
+// same point, the same seed and the same threshold the move launch would have left in memory.  The owner of a query stores the moved point before the
+// scan; the seed key goes into the wave's best[] instead of keys[], so the one store of keys[i] at the end is min(seed, what the scan found) — what
+// merge_key makes of the two — and no lane reads back from memory what another wrote in this launch.  In place, hence only for launches in which ONE
+// workgroup reads a query (one slice; the host checks: s3_move_route).  A stopped loop's launch moves nothing and writes nothing.
+struct S3Move {
+    const IcpState* st;                                       // stop flags + Rd, td
+    const float* tx; const float* ty; const float* tz;        // the target in its own order (keys[] index it)
+    uint32_t nt;
+};
+template <bool MV> struct S3Src { typedef const float* __restrict__ ptr; };
+template <> struct S3Src<true> { typedef float* ptr; };        // (read and written in place)
+
+template <int QG, bool TR, bool MV>
 __device__ __forceinline__ void nn1_strack3_body(
     const float4* __restrict__ l0_centres, const uint4* __restrict__ l0_ops, const float4* __restrict__ l1_centres, const uint4* __restrict__ l1_ops,
     const uint4* __restrict__ ops, const float4* __restrict__ records, uint32_t n_rec, uint32_t n_l0, uint32_t l0_per_slice,
-    const float* __restrict__ sx, const float* __restrict__ sy, const float* __restrict__ sz, uint32_t ns,
-    unsigned long long* __restrict__ keys, const int* __restrict__ stop, unsigned long long* __restrict__ stats, uint32_t flush_at, uint32_t flush_end)
+    typename S3Src<MV>::ptr sx, typename S3Src<MV>::ptr sy, typename S3Src<MV>::ptr sz, uint32_t ns,
+    unsigned long long* __restrict__ keys, const int* __restrict__ stop, unsigned long long* __restrict__ stats, uint32_t flush_at, uint32_t flush_end, const S3Move mv)
 {
     static_assert(QG == 4 || QG == 2 || QG == 1, "query groups per wave: pairs (a lane owns query n of the groups 2 p + h) or ONE (both half-lanes own query n)");
     constexpr int NP = QG == 1 ? 1 : QG / 2;
-    const int stopv = stop ? (stop[0] | stop[1]) : 0;
+    const int stopv = MV ? (mv.st->stop | mv.st->stop_after_transform) : stop ? (stop[0] | stop[1]) : 0;
+    float mr[9] = {}, mt[3] = {};                             // (MV: the pending move, requested with the stop flags)
+    if (MV) {
+#pragma unroll
+        for (int k = 0; k < 9; k++) mr[k] = mv.st->Rd[k];
+#pragma unroll
+        for (int k = 0; k < 3; k++) mt[k] = mv.st->td[k];
+    }
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint32_t n = lane & 31;
     const bool h = lane >= 32;
@@ -130,11 +154,28 @@ __device__ __forceinline__ void nn1_strack3_body(
     for (int p = 0; p < NP; p++) {
         const uint32_t slot = slot_of(p), i = min(qbase + slot, ns - 1);
         qx[p] = sx[i]; qy[p] = sy[i]; qz[p] = sz[i];
-        const uint32_t cb = (uint32_t)(__atomic_load_n(&keys[i], __ATOMIC_RELAXED) >> 32);      // the candidate's d2 (or what other slices published)
+        unsigned long long k0 = __atomic_load_n(&keys[i], __ATOMIC_RELAXED);                     // the candidate (or what other slices published)
+        if constexpr (MV) if (!stopv) {
+            const uint32_t j = (uint32_t)(k0 & 0xFFFFFFFFull);
+            float ux = 0.0f, uy = 0.0f, uz = 0.0f;
+            if (j < mv.nt) { ux = mv.tx[j]; uy = mv.ty[j]; uz = mv.tz[j]; }
+            const float x = qx[p], y = qy[p], z = qz[p];
+            qx[p] = ((mr[0] * x + mr[1] * y) + mr[2] * z) + mt[0];                               // transform_state_kernel's PCR_ROW, term for term
+            qy[p] = ((mr[3] * x + mr[4] * y) + mr[5] * z) + mt[1];
+            qz[p] = ((mr[6] * x + mr[7] * y) + mr[8] * z) + mt[2];
+            k0 = ~0ull;
+            if (j < mv.nt) {
+                const float dx = qx[p] - ux, dy = qy[p] - uy, dz = qz[p] - uz;
+                const uint32_t e = __float_as_uint((dx * dx + dy * dy) + dz * dz);               // A1, unfused: seed_next_search's arithmetic
+                if (e < 0x7F7FFFFFu) k0 = ((unsigned long long)e << 32) | j;                      // FLT_MAX gate
+            }
+            if ((QG > 1 || !h) && qbase + slot < ns) { sx[i] = qx[p]; sy[i] = qy[p]; sz[i] = qz[p]; }      // (the slot's one owner; lanes past ns read point ns - 1 and store nothing)
+        }
+        const uint32_t cb = (uint32_t)(k0 >> 32);
         ok[p] = fabsf(qx[p]) < 1e18f && fabsf(qy[p]) < 1e18f && fabsf(qz[p]) < 1e18f && cb < 0x7F7FFFFFu;
         thr[p] = ok[p] ? __uint_as_float(cb) : -INFINITY;
         L.q[slot] = make_float4(qx[p], qy[p], qz[p], 0.0f);
-        L.best[slot] = ~0ull;
+        L.best[slot] = MV ? k0 : ~0ull;
         if (!ok[p]) { qx[p] = 0.0f; qy[p] = 0.0f; qz[p] = 0.0f; }                                // (finite operands; thr = -inf: no flag, ever)
         const unsigned long long okm = __builtin_amdgcn_ballot_w64(ok[p]);
         okg[QG == 1 ? 0 : 2 * p] = (uint32_t)okm == 0xFFFFFFFFu;
@@ -395,7 +436,8 @@ __device__ __forceinline__ void nn1_strack3_body(
             if (kbest == ~0ull) kbest = 0x7F800000FFFFFFFFull;           // "no neighbour" is the key (+inf, no index), as every other kernel writes it
         }
         const uint32_t i = qbase + g * 32 + n;
-        if (!h && i < ns && kbest != ~0ull) merge_key(&keys[i], kbest);
+        if (MV) { if (!h && i < ns) keys[i] = kbest; }                   // (best[] started from the seed: this IS the merged key, ~0 = no claim included)
+        else if (!h && i < ns && kbest != ~0ull) merge_key(&keys[i], kbest);
     }
 #ifdef PCR_S2_PROF
     PCR_S2_TICK(pt_epi)
@@ -428,8 +470,19 @@ __device__ __forceinline__ void nn1_strack3_body(
     unsigned long long* __restrict__ keys, const int* __restrict__ stop, unsigned long long* __restrict__ stats, uint32_t flush_at, uint32_t flush_end
 #define PCR_S3_ARGS l0_centres, l0_ops, l1_centres, l1_ops, ops, records, n_rec, n_l0, l0_per_slice, sx, sy, sz, ns, keys, stop, stats, flush_at, flush_end
 template <int QG>
-__global__ __launch_bounds__(NN_BLOCK, PCR_S2_WAVES) void nn1_strack3_kernel(PCR_S3_PARAMS) { nn1_strack3_body<QG, true>(PCR_S3_ARGS); }
+__global__ __launch_bounds__(NN_BLOCK, PCR_S2_WAVES) void nn1_strack3_kernel(PCR_S3_PARAMS) { nn1_strack3_body<QG, true, false>(PCR_S3_ARGS, S3Move{}); }
 template <int QG>
-__global__ __launch_bounds__(NN_BLOCK, PCR_S2_WAVES) void nn1_strack3_rows_kernel(PCR_S3_PARAMS) { nn1_strack3_body<QG, false>(PCR_S3_ARGS); }      // tune nn1_s3_transposed = 2
+__global__ __launch_bounds__(NN_BLOCK, PCR_S2_WAVES) void nn1_strack3_rows_kernel(PCR_S3_PARAMS) { nn1_strack3_body<QG, false, false>(PCR_S3_ARGS, S3Move{}); }      // tune nn1_s3_transposed = 2
 #undef PCR_S3_PARAMS
+// the transposed form that moves its queries first (MV above): the working cloud is read AND written, one slice only
+template <int QG>
+__global__ __launch_bounds__(NN_BLOCK, PCR_S2_WAVES) void nn1_strack3_move_kernel(
+    const float4* __restrict__ l0_centres, const uint4* __restrict__ l0_ops, const float4* __restrict__ l1_centres, const uint4* __restrict__ l1_ops,
+    const uint4* __restrict__ ops, const float4* __restrict__ records, uint32_t n_rec, uint32_t n_l0, uint32_t l0_per_slice,
+    float* sx, float* sy, float* sz, uint32_t ns, unsigned long long* __restrict__ keys, unsigned long long* __restrict__ stats, uint32_t flush_at,
+    uint32_t flush_end, const S3Move mv)
+{
+    const int* stop = nullptr;
+    nn1_strack3_body<QG, true, true>(PCR_S3_ARGS, mv);
+}
 #undef PCR_S3_ARGS

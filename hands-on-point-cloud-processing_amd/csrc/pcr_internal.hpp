@@ -191,6 +191,14 @@ struct pcr_ctx {
     hipEvent_t icp_events[4] = { nullptr, nullptr, nullptr, nullptr };
     unsigned long long* grid_stats_dev = nullptr;   // diagnostics of the grid search (tune grid_stats)
     const int* stop_flag_dev = nullptr;        // when set, the correspondence kernels exit early once *flag != 0
+    // the chain search -> sums + solve of an ICP loop (icp.cpp).  nn1_move_state: set by the loop around a search that must move its queries
+    // by the pending Rd, td of that state first (nn1_sphere.hpp, MV) — the exhaustive dispatcher launches the move-carrying kernel or fails.  nn1_move_l0:
+    // the level-0 super-tiles of the last exhaustive search's target if it took the family that has such a form (STRACK3), else 0 — the loop asks after its
+    // first search; nn1_moved: the last search WAS that form
+    const pcr::IcpState* nn1_move_state = nullptr;
+    uint64_t nn1_move_l0 = 0;
+    bool nn1_moved = false;
+    int icp_last_chain = 0;                    // the tail of the last ICP call's iterations (pcr_icp_last_chain)
     uint64_t loop_iters_hint = 0;              // set by an iterated loop (ICP) for its duration: how many searches of one target may follow (nn1_auto_grid)
     uint32_t* far_list = nullptr;              // far queries handed from the grid walk to the exhaustive kernel: [cap] indices + [1] count
     size_t far_cap = 0;
@@ -323,6 +331,16 @@ int launch_icp_update_move(pcr_ctx* ctx, uint32_t n_blocks, const IcpState* st_i
 uint32_t icp_fused_sums_blocks(const pcr_ctx* ctx, size_t n);
 int launch_icp_sums_update_move(pcr_ctx* ctx, const pcr_cloud* tgt, pcr_cloud* c, float max_corr, const IcpState* st_in, IcpState* st_out,
                                 const KabschPlan& plan, const pcr_cloud* seed_tgt);
+// the chain search (moves the cloud by the previous solve) -> sums + solve: the front half of the launch above and a ticket, the last
+// workgroup to arrive reduces and solves; nobody waits and nothing moves.  icp_sums_solve_blocks = its workgroups (0: switched off or too few points)
+uint32_t icp_sums_solve_blocks(const pcr_ctx* ctx, size_t n);
+int launch_icp_sums_solve(pcr_ctx* ctx, const pcr_cloud* tgt, const pcr_cloud* c, float max_corr, const IcpState* st_in, IcpState* st_out, const KabschPlan& plan);
+// nn1_brute.hip: can a seeded STRACK3 search of ns queries over n_l0 level-0 super-tiles carry the move (transposed form, one slice)?  Raw tune values
+uint64_t s3_l0_super_tiles(uint64_t n_tgt);          // the level-0 super-tiles the index of a target of n_tgt points has (bt_ensure_l1)
+bool s3_move_route(uint64_t n_l0, uint64_t ns, int64_t transposed_tune, int64_t qg_tune, int64_t l0_per_slice_tune, int64_t blocks_tune);
+// icp.cpp: the loop's own conditions for that chain, from plain numbers (pcr_icp_move_route)
+bool icp_move_route(uint64_t n_src, uint64_t n_l0, int nranks, int64_t move_in_search_tune, int64_t fused_sums_tune, int64_t fused_sums_min_tune,
+                    int64_t transposed_tune, int64_t qg_tune, int64_t l0_per_slice_tune, int64_t blocks_tune);
 int comm_allreduce_f64_device(pcr_ctx* ctx, double* dev_buf, int n);   // RCCL on the ctx stream, no host round trip
 int launch_plane_count(pcr_ctx* ctx, const pcr_cloud* pts, const double* planes4_host, size_t n_planes,
                        double thr, unsigned long long* counts_out);

@@ -132,6 +132,17 @@ typedef struct {
 int pcr_icp_p2p_f32(pcr_ctx* ctx, const pcr_cloud* src, const pcr_cloud* tgt, const float init_T[16],
                     const pcr_icp_params* prm, float out_T[16], pcr_icp_stats* stats);
 
+/* Which tail the iterations of the last pcr_icp_p2p_f32 call on this context took (diagnostics; every chain gives the same bits):
+ * 0 = the synchronous loop, no call yet, or a call that failed; 1 = sums, solve and move as launches of their own; 2 = sums -> solve + move;
+ * 3 = sums + solve + move in one launch; 4 = sums + solve in one launch, the NEXT search moves the cloud (tune "icp_move_in_search"). */
+int pcr_icp_last_chain(const pcr_ctx* ctx);
+/* Host logic, no GPU: would a single-rank exhaustive loop of n_src points over a target of n_tgt points, whose searches take the three-level
+ * sphere kernel, run chain 4?  The tunes are passed as RAW values, 0 = default: icp_move_in_search (1 on / 2 off), icp_fused_sums (2 off),
+ * icp_fused_sums_min, nn1_s3_transposed (2 = the form without the move), nn1_sphere_qg, nn1_sphere_l0_per_slice, nn1_sphere_blocks (the search
+ * must be ONE slice: it moves its queries in place).  Returns 1 or 0. */
+int pcr_icp_move_route(uint64_t n_src, uint64_t n_tgt, int nranks, int64_t move_in_search, int64_t fused_sums, int64_t fused_sums_min,
+                       int64_t s3_transposed, int64_t sphere_qg, int64_t sphere_l0_per_slice, int64_t sphere_blocks);
+
 /* ---- A10: plane-inlier count, Homework4/ground_detection_ransac.py:138-139,152-153 -------------------
  * dist_i = |((x a + y b) + z c) + d| in f64; counts[h] = #{i : dist_i < thr} for n_planes hypotheses in
  * ONE pass over the points. planes4: n_planes x 4 f64. */

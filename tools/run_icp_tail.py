@@ -1,9 +1,12 @@
 #!/usr/bin/env python3
-"""The tail of an ICP iteration (sums -> solve -> move -> seeds) with and without the fused sums + move launch (tune icp_fused_sums 1 / 2).
+"""The tail of an ICP iteration (sums -> solve -> move -> seeds): the fused sums + move launch (tune icp_fused_sums 1 / 2) and the chain whose NEXT SEARCH
+moves the cloud (tune icp_move_in_search 1 / 2).
 usage: run_icp_tail.py trace [n]            two 20-iteration exhaustive loops at n points, nothing else (under rocprofv3 --kernel-trace; tools/trace_iter.py)
-       run_icp_tail.py ab [reps]            wall time per iteration, icp_fused_sums 1 / 2 alternating in ONE process: 60 k / 120 k / 250 k exhaustive
-                                            (20 iterations) and hw9's 4 000 points with the grid (800 iterations); median and spread (max - min) over reps;
-                                            at 120 k also 256-thread workgroups (icp_fused_sums_threads)
+       run_icp_tail.py ab [reps]            wall time per iteration, the arms alternating in ONE process — move in search / fused sums + move / three
+                                            launches: 60 k / 120 k / 250 k exhaustive (20 iterations; 250 k is multi-slice: the first arm falls back to
+                                            the second) and hw9's 4 000 points with the grid (800 iterations); median and spread (max - min) over reps;
+                                            at 120 k also 256-thread workgroups (icp_fused_sums_threads) and the other geometries of the sums + solve
+                                            launch (icp_sums_solve_threads 256 / 128)
        run_icp_tail.py stamps [n]           profile build (tools/ab_build.sh fsprof kabsch.hip -DPCR_FS_PROF; PCR_LIB_PATH=.../libpcr_fsprof.so): per workgroup
                                             the time from its row store to the end of its wait at the grid barrier, last iteration of a 20-iteration loop
 PCR_TUNE="key=value,..." sets any other knob."""
@@ -44,22 +47,26 @@ elif mode == "stamps":
               f"kernel entry -> row store: mean {w[15] / k / 100:.2f} us")
 else:
     reps = int(sys.argv[2]) if len(sys.argv) > 2 else 8
-    for n, method, iters, arms in ((60000, 1, 20, ((1, 512), (2, 512))), (120000, 1, 20, ((1, 512), (2, 512), (1, 256))), (250000, 1, 20, ((1, 512), (2, 512))),
-                                   (4000, 2, 800, ((1, 512), (2, 512)))):
+    # an arm: (icp_move_in_search, icp_fused_sums, icp_fused_sums_threads, icp_sums_solve_threads)
+    MV, FS, TL = (1, 1, 512, 512), (2, 1, 512, 512), (2, 2, 512, 512)
+    for n, method, iters, arms in ((60000, 1, 20, (MV, FS, TL)), (120000, 1, 20, (MV, FS, TL, (2, 1, 256, 512), (1, 1, 512, 256), (1, 1, 512, 128))),
+                                   (250000, 1, 20, (MV, FS, TL)), (4000, 2, 800, (FS, TL))):
         cs, ct = pair(n); ctx.tune("nn_method", method)
         us = {a: [] for a in arms}
-        poses = {}
+        poses, chains = {}, {}
         for r in range(reps + 1):                      # (the first round warms up: indexes, spare buffers)
             for a in arms:
-                ctx.tune("icp_fused_sums", a[0]); ctx.tune("icp_fused_sums_threads", a[1])
+                for k_, v_ in zip(("icp_move_in_search", "icp_fused_sums", "icp_fused_sums_threads", "icp_sums_solve_threads"), a):
+                    ctx.tune(k_, v_)
                 t0 = time.perf_counter()
                 T, st = ctx.icp_point2point(cs, ct, max_corr=1.0, max_iter=iters, eps=0.0)
                 dt = time.perf_counter() - t0
                 if r: us[a].append(dt / max(st["iters_run"], 1) * 1e6)
-                poses[a] = T.view(np.uint32).tobytes()
+                poses[a] = T.view(np.uint32).tobytes(); chains[a] = ctx.icp_last_chain()
         same = all(p == poses[arms[0]] for p in poses.values())
         for a in arms:
             v = np.array(us[a])
-            print(f"n={n} method={method} iterations={iters} icp_fused_sums={a[0]} threads={a[1]}: median {np.median(v):.2f} us/iteration, spread {v.max() - v.min():.2f} "
+            print(f"n={n} method={method} iterations={iters} icp_move_in_search={a[0]} icp_fused_sums={a[1]} threads={a[2]} solve threads={a[3]} chain {chains[a]}: "
+                  f"median {np.median(v):.2f} us/iteration, spread {v.max() - v.min():.2f} "
                   f"(min {v.min():.2f}, max {v.max():.2f}; {reps} calls); pose bits equal: {same}")
         cs.free(); ct.free()
