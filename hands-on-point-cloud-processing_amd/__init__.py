@@ -22,6 +22,7 @@ PCR_SOA, PCR_AOS3, PCR_AOS4, PCR_AOS6 = 0, 1, 2, 6
 PCR_FPS_F32, PCR_FPS_F64 = 0, 1
 PCR_KMEANS_PY, PCR_KMEANS_CPP = 0, 1
 PCR_EMPTY_CLUSTER = 1          # positive status of the K-Means calls: completed, a cluster has no member
+PCR_SPECTRAL_DUPLICATE, PCR_SPECTRAL_COMPLEX, PCR_SPECTRAL_NOT_CONVERGED, PCR_SPECTRAL_FEW_SEEDS = 2, 3, 4, 5   # positive statuses of the spectral calls
 ERRORS = {0: "ok", -1: "bad argument", -2: "HIP error", -3: "out of memory", -4: "bad state",
           -5: "RCCL/collective error", -6: "no correspondence kept"}
 
@@ -56,6 +57,18 @@ class MfmaCheck(C.Structure):
                 ("check_ms", C.c_double), ("last_nn1_kernel", C.c_char * 16)]
 
 
+class SpectralInfo(C.Structure):
+    _fields_ = [("k_clusters", C.c_int32), ("n_eig", C.c_int32), ("n_basis", C.c_int32), ("solver_steps", C.c_int32), ("one_workgroup", C.c_int32),
+                ("kmeans_iters", C.c_int32), ("kmeans_converged", C.c_int32), ("complex_mask", C.c_uint32), ("residual", C.c_double),
+                ("eigenvalues", C.c_double * 16), ("eigenvalues_im", C.c_double * 16)]
+
+    def as_dict(self):
+        n = self.n_eig
+        return {"K": self.k_clusters, "n_eig": n, "n_basis": self.n_basis, "steps": self.solver_steps, "one_workgroup": bool(self.one_workgroup),
+                "kmeans_iters": self.kmeans_iters, "kmeans_converged": bool(self.kmeans_converged), "complex_mask": self.complex_mask,
+                "residual": self.residual, "eigenvalues": np.array(self.eigenvalues[:n]), "eigenvalues_im": np.array(self.eigenvalues_im[:n])}
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_int)
 
 # every symbol include/pcr.h declares (checked by tests/test_abi.py against the header text)
@@ -74,6 +87,8 @@ ABI_SYMBOLS = [
     "pcr_fps_f32", "pcr_ball_query_f32", "pcr_group_points_f32", "pcr_objects_from_labels_f32",
     "pcr_mat64_create", "pcr_mat64_destroy", "pcr_mat64_info", "pcr_kmeans_step_f64", "pcr_kmeans_fit_f64", "pcr_kmeans_predict_f64", "pcr_kmeanspp_init_f64",
     "pcr_gmm_em_step_f64", "pcr_gmm_fit_f64", "pcr_gmm_predict_f64",
+    "pcr_mat64_knn_f64", "pcr_spectral_graph_f64", "pcr_spgraph_info", "pcr_spgraph_read", "pcr_spgraph_destroy", "pcr_eig_small_f64",
+    "pcr_spectral_embed_f64", "pcr_spectral_select_k", "pcr_spectral_cluster_f64",
     "pcr_range_image_create_f32", "pcr_range_image_from_host_f64", "pcr_range_image_shape", "pcr_range_image_read", "pcr_range_image_close_f64",
     "pcr_range_image_label_f64", "pcr_range_image_assign", "pcr_range_image_destroy", "pcr_range_cluster_f32",
 ]
@@ -185,6 +200,15 @@ def lib():
     L.pcr_kmeans_fit_f64.argtypes = [vp, vp, C.c_int, vp, C.c_double, C.c_int, C.c_int, vp, vp, ip, ip]
     L.pcr_kmeans_predict_f64.argtypes = [vp, vp, C.c_int, vp, vp]
     L.pcr_kmeanspp_init_f64.argtypes = [vp, vp, C.c_int, C.c_double, vp, C.c_uint64, vp, vp]
+    L.pcr_mat64_knn_f64.argtypes = [vp, vp, C.c_int, vp, vp]
+    L.pcr_spectral_graph_f64.argtypes = [vp, vp, C.c_int, C.POINTER(vp)]
+    L.pcr_spgraph_info.argtypes = [vp, C.POINTER(sz), C.POINTER(sz)]
+    L.pcr_spgraph_read.argtypes = [vp, vp, vp, vp, vp]
+    L.pcr_spgraph_destroy.argtypes = [vp, vp]
+    L.pcr_eig_small_f64.argtypes = [C.c_int, vp, vp, vp, vp]
+    L.pcr_spectral_embed_f64.argtypes = [vp, vp, C.c_int, C.c_int, C.c_double, C.c_int, vp, vp, C.POINTER(SpectralInfo)]
+    L.pcr_spectral_select_k.argtypes = [vp, C.c_int]
+    L.pcr_spectral_cluster_f64.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.POINTER(SpectralInfo)]
     L.pcr_gmm_em_step_f64.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp]
     L.pcr_gmm_fit_f64.argtypes = [vp, vp, C.c_int, vp, C.c_double, C.c_double, C.c_int, C.c_uint64, vp, vp, vp, ip, ip, ip]
     L.pcr_gmm_predict_f64.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp]
@@ -260,6 +284,26 @@ def kabsch_limbs_to_sums(row, e: int):
     if rc != 0:
         raise PcrError(f"pcr_kabsch_limbs_to_sums failed (rc = {rc})")
     return sums
+
+
+def eig_small(a):
+    """every eigenpair of a real n x n matrix, n <= 16, on the host (pcr_eig_small_f64) -> (eigenvalues complex [n] ascending by real part,
+    vectors [n, n]: a real column, or the real and imaginary part of a conjugate pair's first vector)"""
+    a = np.ascontiguousarray(a, np.float64)
+    if a.ndim != 2 or a.shape[0] != a.shape[1]:
+        raise PcrError("a: a square matrix")
+    n = a.shape[0]
+    wr, wi, v = np.zeros(n), np.zeros(n), np.zeros((n, n))
+    rc = lib().pcr_eig_small_f64(n, a.ctypes.data, wr.ctypes.data, wi.ctypes.data, v.ctypes.data)
+    if rc != 0:
+        raise PcrError(f"pcr_eig_small_f64: {ERRORS.get(rc, rc)}")
+    return wr + 1j * wi, v
+
+
+def spectral_select_k(eigenvalues) -> int:
+    """the eigengap rule of spectralClustering.cpp:188-197 (pcr_spectral_select_k)"""
+    e = np.ascontiguousarray(eigenvalues, np.float64)
+    return int(lib().pcr_spectral_select_k(e.ctypes.data, e.shape[0]))
 
 
 def kabsch_solve(sums):
@@ -437,6 +481,30 @@ class Mat64:
                                                  idx.ctypes.data, p.ctypes.data if want_p else None))
         return (idx, p) if want_p else idx
 
+    def knn(self, k: int):
+        """the k nearest rows of every row among all rows, itself included -> (idx int32 [n, k], d2 [n, k]) ascending by (d2, index)"""
+        idx, d2 = np.zeros((self.n, int(k)), np.int32), np.zeros((self.n, int(k)))
+        self.ctx._ck(lib().pcr_mat64_knn_f64(self.ctx.h, self.h, int(k), idx.ctypes.data, d2.ctypes.data))
+        return idx, d2
+
+    def spectral_graph(self, k_neighbors: int):
+        """-> SpGraph (the random-walk Laplacian of the kNN graph, resident), or None with a duplicate point (PCR_SPECTRAL_DUPLICATE)"""
+        h = C.c_void_p()
+        rc = self._ck_pos(lib().pcr_spectral_graph_f64(self.ctx.h, self.h, int(k_neighbors), C.byref(h)))
+        return SpGraph(self.ctx, h) if rc == 0 else None
+
+    def spectral_cluster(self, k_neighbors: int = 10, n_eig: int = 8, n_clusters: int = 0):
+        """Spec_Cluster::fit -> (labels int32 [n], features [n, K] or None, info dict, status)"""
+        labels = np.zeros(self.n, np.int32)
+        feat = np.zeros((self.n, 8))
+        info = SpectralInfo()
+        rc = self._ck_pos(lib().pcr_spectral_cluster_f64(self.ctx.h, self.h, int(k_neighbors), int(n_eig), int(n_clusters), labels.ctypes.data,
+                                                         feat.ctypes.data, C.byref(info)))
+        d = info.as_dict()
+        K = d["K"]
+        features = feat.reshape(-1)[: self.n * K].reshape(self.n, K).copy() if rc in (0, PCR_EMPTY_CLUSTER) and K > 0 else None
+        return labels, features, d, rc
+
     def _params(self, mean, cov, pi):
         mean = self._centres(mean)
         k = mean.shape[0]
@@ -470,6 +538,44 @@ class Mat64:
         labels = np.zeros(self.n, np.int32)
         self.ctx._ck(lib().pcr_gmm_predict_f64(self.ctx.h, self.h, k, mean.ctypes.data, cov.ctypes.data, pi.ctypes.data, labels.ctypes.data))
         return labels
+
+
+class SpGraph:
+    """The random-walk Laplacian L = I - D^-1 W of a kNN graph, resident in HBM as CSR with ascending columns (pcr_spgraph)."""
+
+    def __init__(self, ctx: "Context", handle):
+        self.ctx, self.h = ctx, handle
+        n, nnz = C.c_size_t(), C.c_size_t()
+        ctx._ck(lib().pcr_spgraph_info(handle, C.byref(n), C.byref(nnz)))
+        self.n, self.nnz = n.value, nnz.value
+        ctx._handles.add(self)
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:   # noqa: BLE001
+            pass
+
+    def free(self):
+        if self.h and self.ctx.h:
+            lib().pcr_spgraph_destroy(self.ctx.h, self.h)
+        self.h = None
+
+    def read(self):
+        """-> (row_ptr int64 [n + 1], col int32 [nnz], val [nnz])"""
+        row_ptr, col, val = np.zeros(self.n + 1, np.int64), np.zeros(self.nnz, np.int32), np.zeros(self.nnz)
+        self.ctx._ck(lib().pcr_spgraph_read(self.ctx.h, self.h, row_ptr.ctypes.data, col.ctypes.data, val.ctypes.data))
+        return row_ptr, col, val
+
+    def embed(self, n_eig: int = 8, n_basis: int = 13, tol: float = 1e-10, max_iter: int = 0):
+        """the n_eig eigenpairs of L with the smallest real part -> (eigenvalues [n_eig], vectors [n, n_eig], info dict, status)"""
+        ev, vec = np.zeros(int(n_eig)), np.zeros((self.n, int(n_eig)))
+        info = SpectralInfo()
+        rc = lib().pcr_spectral_embed_f64(self.ctx.h, self.h, int(n_eig), int(n_basis), float(tol), int(max_iter), ev.ctypes.data, vec.ctypes.data,
+                                          C.byref(info))
+        if rc < 0:
+            self.ctx._ck(rc)
+        return ev, vec, info.as_dict(), rc
 
 
 class Rows:

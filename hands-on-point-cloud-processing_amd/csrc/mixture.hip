@@ -714,6 +714,10 @@ extern "C" int pcr_mat64_destroy(pcr_ctx* ctx, pcr_mat64* m)
     return PCR_OK;
 }
 
+namespace pcr {
+const double* mat64_rows_dev(const pcr_mat64* m) { return m ? m->x : nullptr; }
+}
+
 extern "C" int pcr_mat64_info(const pcr_mat64* m, size_t* n, int* dim, int* grid_exponent)
 {
     if (!m) return PCR_ERR_ARG;

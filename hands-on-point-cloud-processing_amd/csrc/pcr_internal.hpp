@@ -357,6 +357,11 @@ int launch_radius_fill(pcr_ctx* ctx, const double* db_soa, size_t n, size_t n_ca
 void svd3(const double A[9], double U[9], double S[3], double V[9]);
 int kabsch_solve(const double sums[16], float R[9], float t[3]);
 void mat4_mul_f32(const float A[16], const float B[16], float out[16]);
+// every eigenpair of a real n x n matrix, n <= 16 (numerics.cpp; the contract of pcr_eig_small_f64), and the eigengap rule of Homework3
+int eig_small(int n, const double* a, double* wr, double* wi, double* vec);
+int spectral_select_k(const double* eig, int n_eig);
+// the device rows of a pcr_mat64 (mixture.hip owns the struct): row-major n x dim
+const double* mat64_rows_dev(const pcr_mat64* m);
 
 // ---- collectives ----------------------------------------------------------------------------------------
 int comm_allreduce_f64(pcr_ctx* ctx, double* host_buf, double* dev_buf, int n);

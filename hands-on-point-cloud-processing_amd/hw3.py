@@ -1,6 +1,7 @@
 """Homework3's clustering classes on the GPU: K_Means (Homework3/hw3/sript/KMeans.py) and GMM (Homework3/hw3/sript/GMM.py with the working
 `posterior` of Homework3/nano_vs_my/sript/GMM.py), with the reference's attributes and methods, behind the C ABI of include/pcr.h
-(csrc/mixture.hip).  compare_cluster.py runs with its two import lines changed.
+(csrc/mixture.hip).  compare_cluster.py runs with its two import lines changed.  Spec_Cluster is the C++ class of
+Homework3/hw3/spectralClustering.cpp (csrc/spectral.hip).
 
 The reference draws its initial points unseeded.  Here the draws are keyed by `seed` (SplitMix64, include/pcr.h), or the initial indices
 are given outright with `init_idx`.  There is no CPU fall-back: a missing library or GPU is an error.
@@ -9,7 +10,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from . import PCR_KMEANS_PY, Context
+from . import PCR_KMEANS_PY, Context, PcrError
 
 _ctx = None
 
@@ -110,3 +111,33 @@ class GMM(object):
             return m.gmm_predict(*self.model_params).astype(np.int64)
         finally:
             m.free()
+
+
+class Spec_Cluster(object):
+    """Spec_Cluster of Homework3/hw3/include/spectralClustering.hpp: the (k_neigh, k_clus_estimation) constructor and fit(points) -> labels.
+    n_clusters > 0 fixes K instead of the eigengap rule.  After fit: eigenvalues_ (k_clus_estimation values, ascending), K_clusters,
+    features_ (n x K_clusters), info_ (solver steps, residual, K-Means passes)."""
+
+    def __init__(self, k_neigh, k_clus_estimation, n_clusters=0, ctx=None):
+        self.K_neighbors = int(k_neigh)
+        self.K_clusters_estimation = int(k_clus_estimation)
+        self.n_clusters = int(n_clusters)
+        self.K_clusters = 1
+        self.eigenvalues_ = None
+        self.features_ = None
+        self.info_ = None
+        self.status_ = 0
+        self._ctx = ctx
+
+    def fit(self, points):
+        points = np.ascontiguousarray(points, np.float64)
+        m = (self._ctx or _context()).mat64(points)
+        try:
+            labels, self.features_, self.info_, self.status_ = m.spectral_cluster(self.K_neighbors, self.K_clusters_estimation, self.n_clusters)
+        finally:
+            m.free()
+        self.eigenvalues_ = self.info_["eigenvalues"]
+        self.K_clusters = self.info_["K"]
+        if self.status_ != 0:
+            raise PcrError(f"Spec_Cluster.fit: status {self.status_} (include/pcr.h: PCR_EMPTY_CLUSTER / PCR_SPECTRAL_*)")
+        return labels

@@ -697,6 +697,67 @@ int pcr_gmm_fit_f64(pcr_ctx* ctx, pcr_mat64* data, int k, const double* init_mea
                     double* mean, double* cov, double* pi, int* iters, int* converged, int* resets);
 int pcr_gmm_predict_f64(pcr_ctx* ctx, pcr_mat64* data, int k, const double* mean, const double* cov, const double* pi, int32_t* labels);
 
+/* ---- Homework3: spectral clustering (csrc/spectral.hip, csrc/numerics.cpp) -----------------------------------------------
+ * Spec_Cluster::fit of Homework3/hw3/spectralClustering.cpp: kNN graph -> random-walk Laplacian L = I - D^-1 W -> the eigenpairs of L with
+ * the smallest real part -> K by the eigengap rule -> K-Means (PCR_KMEANS_CPP above) on the first K eigenvector columns.  All f64 over a
+ * pcr_mat64.  Every sum runs in a fixed order (no floating-point atomics): a call repeats bit for bit.
+ *
+ * pcr_mat64_knn_f64: the k nearest rows of every row among ALL rows, the row itself included (nanoflann's findNeighbors returns it).
+ *   d2 = sum_dim (a - b) (a - b), accumulated from 0 in dimension order, unfused; results ascending by (d2, index); 1 <= k <= 32, k <= n.
+ *   idx (int32) and d2: n x k, host.  Exhaustive and tiled (targets through LDS, the result set of a row in registers); d2 must not overflow.
+ * pcr_spectral_graph_f64: buildKNNGraph (:53-119).  Row i holds 1 on the diagonal and -(w_ij / s_i) for every neighbour j != i of its
+ *   k_neighbors nearest rows (only the row's own index is skipped, :90), w_ij = 1 / sqrt(d2_ij), s_i = the w of the row added in ascending
+ *   column order starting from 0.  Columns ascending within a row; every row has k_neighbors entries.  2 <= k_neighbors <= 32.
+ *   A neighbour at distance 0 (a duplicate point: inf / NaN in the reference) gives the positive status PCR_SPECTRAL_DUPLICATE and no graph.
+ *   pcr_spgraph_read copies the CSR arrays to the host (row_ptr: n + 1, col / val: nnz; each may be NULL); pcr_spgraph_info reports n and nnz.
+ *   buildRNNGraph (:122-161) is never called by the reference and is not provided.
+ * pcr_eig_small_f64 (host, no GPU): every eigenpair of a real n x n matrix (row-major, 1 <= n <= 16): Householder -> Hessenberg, shifted QR
+ *   with accumulated transformations, back-substitution.  Eigenvalues (wr, wi) ascending by real part, a conjugate pair adjacent with the
+ *   positive imaginary part first.  vectors (n x n row-major, may be NULL): column j is the unit eigenvector of a real eigenvalue; for a pair
+ *   at (j, j + 1) the columns are the real and the imaginary part of the unit vector of wr[j] + i wi[j].  PCR_ERR_STATE: no convergence.
+ * pcr_spectral_embed_f64: the n_eig eigenpairs of L with the smallest real part, by block iteration with n_basis orthonormal columns on the
+ *   damped walk A = I - L / 2 (re-orthonormalised every 8 steps, Cholesky-QR on the device), a Rayleigh-Ritz step on T = Q^T L Q
+ *   (pcr_eig_small_f64) every 256 steps, and the stop rule max_j |L v_j - theta_j v_j| <= tol over the n_eig unit Ritz vectors.
+ *   1 <= n_eig <= n_basis <= 16, n_basis <= n; 0 selects the defaults 8 and n_eig + 5 (clamped); tol <= 0: 1e-10; max_iter <= 0: 400 000 steps.
+ *   n <= 4 096: one persistent workgroup runs all steps between two Ritz checks in one launch; larger n: one launch per step over all CUs.
+ *   eigenvalues: n_eig real parts, ascending.  vectors: n x n_eig row-major, unit 2-norm, the component of largest magnitude (the first
+ *   such) positive.  A complex Ritz pair among the n_eig is flagged in info->complex_mask (bit j: column j belongs to a pair; its two
+ *   columns hold the real and the imaginary part of the unit complex vector, the real part's largest component positive) and its imaginary
+ *   part stands in info->eigenvalues_im.  Positive status PCR_SPECTRAL_NOT_CONVERGED when max_iter ends first (outputs = the last Ritz pairs).
+ * pcr_spectral_select_k (host): the eigengap rule of :188-197 as written — diff = e[1] - e[0]; the first i >= 1 with e[i + 1] - e[i] >
+ *   50 diff gives K = i + 1 — reading e[i + 1] only while i + 1 < n_eig (the reference reads one past its vector); 1 if no gap fires.
+ * pcr_spectral_cluster_f64: graph, embedding (n_eig, its default basis, tol 1e-10), K = n_clusters if > 0 else the rule (K <= min(8, n_eig)),
+ *   initial_choice (:249-289: row 0, then every row whose squared distance to each chosen row is >= 1e-4, until K are chosen; on the host
+ *   over the n x K features) — PCR_SPECTRAL_FEW_SEEDS if fewer than K exist —, then pcr_kmeans_fit_f64(PCR_KMEANS_CPP, tol 1e-4, 200).
+ *   PCR_SPECTRAL_COMPLEX if a complex pair falls inside the K columns (the reference takes .real() of an arbitrary phase there).
+ *   labels: n int32.  features (may be NULL): n x K.  info (may be NULL) carries K, the eigenvalues, steps, residual and K-Means passes. */
+#define PCR_SPECTRAL_DUPLICATE 2
+#define PCR_SPECTRAL_COMPLEX 3
+#define PCR_SPECTRAL_NOT_CONVERGED 4
+#define PCR_SPECTRAL_FEW_SEEDS 5
+typedef struct pcr_spgraph pcr_spgraph;
+typedef struct {
+    int32_t k_clusters;          /* K used by pcr_spectral_cluster_f64 (0 from pcr_spectral_embed_f64) */
+    int32_t n_eig, n_basis;
+    int32_t solver_steps;        /* applications of A */
+    int32_t one_workgroup;       /* 1: the persistent single-workgroup path served the iteration */
+    int32_t kmeans_iters, kmeans_converged;
+    uint32_t complex_mask;
+    double residual;             /* the largest |L v - theta v| over the n_eig Ritz pairs at the last check */
+    double eigenvalues[16], eigenvalues_im[16];
+} pcr_spectral_info;
+int pcr_mat64_knn_f64(pcr_ctx* ctx, pcr_mat64* data, int k, int32_t* idx, double* d2);
+int pcr_spectral_graph_f64(pcr_ctx* ctx, pcr_mat64* data, int k_neighbors, pcr_spgraph** out);
+int pcr_spgraph_info(const pcr_spgraph* g, size_t* n, size_t* nnz);
+int pcr_spgraph_read(pcr_ctx* ctx, const pcr_spgraph* g, int64_t* row_ptr, int32_t* col, double* val);
+int pcr_spgraph_destroy(pcr_ctx* ctx, pcr_spgraph* g);
+int pcr_eig_small_f64(int n, const double* a, double* wr, double* wi, double* vectors);
+int pcr_spectral_embed_f64(pcr_ctx* ctx, pcr_spgraph* graph, int n_eig, int n_basis, double tol, int max_iter, double* eigenvalues, double* vectors,
+                           pcr_spectral_info* info);
+int pcr_spectral_select_k(const double* eigenvalues, int n_eig);
+int pcr_spectral_cluster_f64(pcr_ctx* ctx, pcr_mat64* data, int k_neighbors, int n_eig, int n_clusters, int32_t* labels, double* features,
+                             pcr_spectral_info* info);
+
 /* ---- profiling hooks for bench.py: HIP-event timing of the dominant kernel on the ctx stream ----------
  * Off by default (an event pair costs ~6 us of stream time on each side of the kernel it brackets):
  * pcr_tune_set(ctx, "prof", 1) times the correspondence kernels, 2 every kernel, 0 switches it off again. */
