@@ -568,8 +568,10 @@ class SpGraph:
         return row_ptr, col, val
 
     def embed(self, n_eig: int = 8, n_basis: int = 13, tol: float = 1e-10, max_iter: int = 0):
-        """the n_eig eigenpairs of L with the smallest real part -> (eigenvalues [n_eig], vectors [n, n_eig], info dict, status)"""
-        ev, vec = np.zeros(int(n_eig)), np.zeros((self.n, int(n_eig)))
+        """the n_eig eigenpairs of L with the smallest real part -> (eigenvalues [n_eig], vectors [n, n_eig], info dict, status); n_basis = 0 leaves the
+        method to the library (up to 32 rows: the dense host solver), a value asks for block iteration with that many columns"""
+        width = int(n_eig) if int(n_eig) > 0 else min(self.n, 8)          # 0: the library's default
+        ev, vec = np.zeros(width), np.zeros((self.n, width))
         info = SpectralInfo()
         rc = lib().pcr_spectral_embed_f64(self.ctx.h, self.h, int(n_eig), int(n_basis), float(tol), int(max_iter), ev.ctypes.data, vec.ctypes.data,
                                           C.byref(info))

@@ -20,15 +20,19 @@ void mat4_mul_f32(const float A[16], const float B[16], float out[16]) { num::ma
 // ---- small dense real nonsymmetric eigenproblem (Homework3 spectral clustering: the Ritz matrix of csrc/spectral.hip) ----------
 // Householder reduction to Hessenberg form, then the shifted (Francis double-step) QR iteration on the Hessenberg matrix with the
 // transformations accumulated, and back-substitution for the eigenvectors: the public-domain EISPACK routines orthes / ortran / hqr2, as
-// restated in JAMA (NIST).  No balancing: the callers' matrices are Rayleigh quotients in an orthonormal basis.
+// restated in JAMA (NIST).  pcr_eig_small_f64 does no balancing: its matrices are Rayleigh quotients in an orthonormal basis.  eig_dense (the
+// Laplacian of a small graph itself, up to 32 rows) runs the permutation half of EISPACK's balanc first: rows and columns that isolate an eigenvalue
+// leave the window [low, high] the QR iteration works on, and that eigenvalue is read off the diagonal exactly.  No scaling.
 namespace pcr {
 namespace {
 
 constexpr int EIG_MAX = 16;
+constexpr int EIG_DENSE_MAX = 32;
 
+template <int MAX>
 struct EigWork {
-    int n;
-    double H[EIG_MAX][EIG_MAX], V[EIG_MAX][EIG_MAX], d[EIG_MAX], e[EIG_MAX], ort[EIG_MAX];
+    int n, low, high, perm[MAX];
+    double H[MAX][MAX], V[MAX][MAX], d[MAX], e[MAX], ort[MAX];
     double cdr, cdi;
     void cdiv(double xr, double xi, double yr, double yi)
     {
@@ -43,9 +47,56 @@ struct EigWork {
     }
 };
 
-void eig_orthes(EigWork& W)
+// balanc without its scaling: a row whose off-diagonal entries inside the window are all zero goes to the bottom, such a column to the left
+template <class WK>
+void eig_isolate(WK& W)
 {
-    const int n = W.n, low = 0, high = n - 1;
+    const int n = W.n;
+    auto& H = W.H;
+    int low = 0, high = n - 1;
+    auto exchange = [&](int j, int m) {
+        W.perm[m] = j;
+        if (j == m) return;
+        for (int i = 0; i <= high; i++) { const double t = H[i][j]; H[i][j] = H[i][m]; H[i][m] = t; }
+        for (int i = low; i < n; i++) { const double t = H[j][i]; H[j][i] = H[m][i]; H[m][i] = t; }
+    };
+    for (bool found = true; found && high > 0;) {
+        found = false;
+        for (int j = high; j >= 0 && !found; j--) {
+            bool zero = true;
+            for (int i = 0; i <= high && zero; i++) zero = i == j || H[j][i] == 0.0;
+            if (zero) { exchange(j, high); high--; found = true; }
+        }
+    }
+    for (bool found = true; found && low < high;) {
+        found = false;
+        for (int j = low; j <= high && !found; j++) {
+            bool zero = true;
+            for (int i = low; i <= high && zero; i++) zero = i == j || H[i][j] == 0.0;
+            if (zero) { exchange(j, low); low++; found = true; }
+        }
+    }
+    W.low = low; W.high = high;
+}
+
+// balbak: the rows of the vectors back to the order of the caller's matrix
+template <class WK>
+void eig_unpermute(WK& W)
+{
+    const int n = W.n;
+    auto swap_rows = [&](int i) {
+        const int k = W.perm[i];
+        if (k == i) return;
+        for (int j = 0; j < n; j++) { const double t = W.V[i][j]; W.V[i][j] = W.V[k][j]; W.V[k][j] = t; }
+    };
+    for (int i = W.low - 1; i >= 0; i--) swap_rows(i);
+    for (int i = W.high + 1; i < n; i++) swap_rows(i);
+}
+
+template <class WK>
+void eig_orthes(WK& W)
+{
+    const int n = W.n, low = W.low, high = W.high;
     auto& H = W.H; auto& V = W.V; auto& ort = W.ort;
     for (int m = low + 1; m <= high - 1; m++) {
         double scale = 0.0;
@@ -88,16 +139,19 @@ void eig_orthes(EigWork& W)
     }
 }
 
-bool eig_hqr2(EigWork& W)
+template <class WK>
+bool eig_hqr2(WK& W)
 {
-    const int nn = W.n, low = 0, high = nn - 1;
-    int n = nn - 1;
+    const int nn = W.n, low = W.low, high = W.high;
+    int n = high;
     auto& H = W.H; auto& V = W.V; auto& d = W.d; auto& e = W.e;
     const double eps = std::ldexp(1.0, -52);
     double exshift = 0.0, p = 0, q = 0, r = 0, s = 0, z = 0, t, w, x, y;
     double norm = 0.0;
-    for (int i = 0; i < nn; i++)
+    for (int i = 0; i < nn; i++) {
+        if (i < low || i > high) { d[i] = H[i][i]; e[i] = 0.0; }          // a root the permutation isolated
         for (int j = (i > 0 ? i - 1 : 0); j < nn; j++) norm += std::fabs(H[i][j]);
+    }
     int iter = 0, total = 0;
     while (n >= low) {
         int l = n;
@@ -289,7 +343,10 @@ bool eig_hqr2(EigWork& W)
             }
         }
     }
-    // back to the original coordinates
+    // the vectors of the isolated roots, then back to the original coordinates
+    for (int i = 0; i < nn; i++)
+        if (i < low || i > high)
+            for (int j = i; j < nn; j++) V[i][j] = H[i][j];
     for (int j = nn - 1; j >= low; j--)
         for (int i = low; i <= high; i++) {
             z = 0.0;
@@ -301,19 +358,26 @@ bool eig_hqr2(EigWork& W)
 
 }  // namespace
 
-int eig_small(int n, const double* a, double* wr, double* wi, double* vec)
+namespace {
+
+template <int MAX>
+int eig_run(int n, const double* a, double* wr, double* wi, double* vec, bool isolate)
 {
-    if (n < 1 || n > EIG_MAX || !a || !wr || !wi) return PCR_ERR_ARG;
+    if (n < 1 || n > MAX || !a || !wr || !wi) return PCR_ERR_ARG;
     for (int i = 0; i < n * n; i++)
         if (!(std::fabs(a[i]) <= 1.79769313486231570815e308)) return PCR_ERR_ARG;
-    EigWork W;
-    W.n = n;
-    for (int i = 0; i < n; i++)
+    EigWork<MAX> W;
+    W.n = n; W.low = 0; W.high = n - 1;
+    for (int i = 0; i < n; i++) {
+        W.perm[i] = i;
         for (int j = 0; j < n; j++) W.H[i][j] = a[i * n + j];
+    }
+    if (isolate) eig_isolate(W);
     eig_orthes(W);
     if (!eig_hqr2(W)) return PCR_ERR_STATE;
+    if (isolate) eig_unpermute(W);
     // units (a real root, or a conjugate pair with the positive imaginary part first) in ascending order of the real part; a stable insertion sort
-    int start[EIG_MAX], len[EIG_MAX], units = 0;
+    int start[MAX], len[MAX], units = 0;
     for (int j = 0; j < n;) {
         const int l = W.e[j] != 0.0 ? 2 : 1;
         start[units] = j; len[units] = l; units++;
@@ -339,6 +403,11 @@ int eig_small(int n, const double* a, double* wr, double* wi, double* vec)
         }
     return PCR_OK;
 }
+
+}  // namespace
+
+int eig_small(int n, const double* a, double* wr, double* wi, double* vec) { return eig_run<EIG_MAX>(n, a, wr, wi, vec, false); }
+int eig_dense(int n, const double* a, double* wr, double* wi, double* vec) { return eig_run<EIG_DENSE_MAX>(n, a, wr, wi, vec, true); }
 
 // the eigengap rule of spectralClustering.cpp:188-197 as written, with eig(i + 1) read only while it exists
 int spectral_select_k(const double* eig, int n_eig)

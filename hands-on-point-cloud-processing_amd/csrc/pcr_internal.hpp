@@ -359,6 +359,8 @@ int kabsch_solve(const double sums[16], float R[9], float t[3]);
 void mat4_mul_f32(const float A[16], const float B[16], float out[16]);
 // every eigenpair of a real n x n matrix, n <= 16 (numerics.cpp; the contract of pcr_eig_small_f64), and the eigengap rule of Homework3
 int eig_small(int n, const double* a, double* wr, double* wi, double* vec);
+// the same for n <= 32, after the permutation that isolates eigenvalues (a row or column with zeros off the diagonal): the dense path of spectral.hip
+int eig_dense(int n, const double* a, double* wr, double* wi, double* vec);
 int spectral_select_k(const double* eig, int n_eig);
 // the device rows of a pcr_mat64 (mixture.hip owns the struct): row-major n x dim
 const double* mat64_rows_dev(const pcr_mat64* m);

@@ -11,6 +11,9 @@
 //                  lanes meet at workgroup barriers only.  Larger n: one launch per step (sp_axpy_kernel), per Gram matrix (sp_gram_kernel +
 //                  sp_chol_kernel) and per basis change (sp_apply_kernel), in stream order.  No grid barrier, no floating-point atomics: a Gram entry
 //                  is a per-lane sum over rows i = lane, lane + 64, ..., a butterfly over the wave, and a sum over the workgroups in index order.
+//                  n <= 32 with n_basis left at 0: no iteration.  L goes to the host as a dense matrix and eig_dense returns its eigenpairs: the
+//                  iteration cannot serve every such graph (a 16-column block may be the whole space, L of a 2-row cloud has the eigenvalue 2 that
+//                  A = I - L / 2 maps to 0, and with k_neighbors = 2 L is defective, where block iteration stalls near sqrt(eps)).
 #include "pcr_internal.hpp"
 
 #include <cfloat>
@@ -27,6 +30,7 @@ constexpr int SP_ROUNDS = 32;        // orthonormalisations between two Ritz che
 constexpr int SP_ONE_MAX = 4096;     // rows up to which one workgroup iterates alone
 constexpr int SP_WG = 1024;          // lanes of the Gram / one-workgroup kernels: 16 waves, wave a owns row a of a 16 x 16 product
 constexpr int SP_GRAM_MAX = 256;     // workgroups of a Gram launch at most
+constexpr int SP_DENSE_MAX = 32;     // rows up to which the default call solves the dense problem on the host (eig_dense's limit; twice the widest block)
 
 // ---------------------------------------------------------------------------------------------------------------------------- kNN
 template <int DIM, int KC>
@@ -399,6 +403,89 @@ int sp_round_many(const SpRun& r, int passes)
     return PCR_OK;
 }
 
+// the eigenvectors in V (n rows of stride ld, m_cols columns in use): normalise, fix the sign, hand out the first n_eig columns
+void sp_hand_out(double* V, size_t ld, size_t n, int n_eig, int m_cols, uint32_t cmask, const double* wr, const double* wi, double* eigenvalues, double* vectors)
+{
+    for (int j = 0; j < m_cols; j++) {
+        const bool cpx = cmask >> j & 1;
+        if (cpx && !(wi[j] > 0.0)) continue;               // handled with its partner
+        const int w = cpx ? 2 : 1;
+        double s = 0.0;
+        for (size_t i = 0; i < n; i++)
+            for (int c = j; c < j + w; c++) s += V[i * ld + c] * V[i * ld + c];
+        double big = 0.0, sign = 1.0;
+        for (size_t i = 0; i < n; i++)
+            if (std::fabs(V[i * ld + j]) > big) { big = std::fabs(V[i * ld + j]); sign = V[i * ld + j] < 0.0 ? -1.0 : 1.0; }
+        const double sc = s > 0.0 ? sign / std::sqrt(s) : 0.0;
+        for (size_t i = 0; i < n; i++)
+            for (int c = j; c < j + w; c++) V[i * ld + c] *= sc;
+    }
+    if (vectors)
+        for (size_t i = 0; i < n; i++)
+            for (int j = 0; j < n_eig; j++) vectors[i * n_eig + j] = V[i * ld + j];
+    if (eigenvalues) for (int j = 0; j < n_eig; j++) eigenvalues[j] = wr[j];
+}
+
+void sp_fill_info(pcr_spectral_info* info, int n_eig, int n_basis, int steps, int one, uint32_t cmask, int m_cols, double residual, const double* wr, const double* wi)
+{
+    memset(info, 0, sizeof(*info));
+    info->n_eig = n_eig; info->n_basis = n_basis; info->solver_steps = steps; info->one_workgroup = one;
+    info->complex_mask = cmask & ((1u << n_eig) - 1u);
+    if (m_cols > n_eig) info->complex_mask |= 1u << (n_eig - 1);
+    info->residual = residual;
+    for (int j = 0; j < n_eig; j++) { info->eigenvalues[j] = wr[j]; info->eigenvalues_im[j] = wi[j]; }
+}
+
+// n <= SP_DENSE_MAX: L as a dense matrix on the host, every eigenpair from eig_dense, the residuals of the wanted ones in plain loops
+int sp_embed_dense(pcr_ctx* ctx, const pcr_spgraph* g, int n_eig, double tol, double* eigenvalues, double* vectors, pcr_spectral_info* info)
+{
+    const int n = (int)g->n, k = g->k;
+    int32_t col[SP_DENSE_MAX * SP_KMAX];
+    double val[SP_DENSE_MAX * SP_KMAX], Ld[SP_DENSE_MAX * SP_DENSE_MAX], wr[SP_DENSE_MAX], wi[SP_DENSE_MAX], Y[SP_DENSE_MAX * SP_DENSE_MAX];
+    double V[SP_DENSE_MAX * (SP_NB + 1)], W[SP_DENSE_MAX * (SP_NB + 1)];
+    PCR_HIP(ctx, hipMemcpyAsync(col, g->col, (size_t)n * k * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    PCR_HIP(ctx, hipMemcpyAsync(val, g->val, (size_t)n * k * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    PCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (int a = 0; a < n * n; a++) Ld[a] = 0.0;
+    for (int i = 0; i < n; i++)
+        for (int e = 0; e < k; e++) {
+            const int32_t j = col[i * k + e];
+            if (j < 0 || j >= n) return fail(ctx, PCR_ERR_STATE, "pcr_spectral_embed_f64: a column outside the graph");
+            Ld[i * n + j] = val[i * k + e];
+        }
+    const int rc = eig_dense(n, Ld, wr, wi, Y);
+    if (rc != PCR_OK) return fail(ctx, rc, "pcr_spectral_embed_f64: the dense eigenproblem");
+    // the wanted columns: the n_eig of smallest real part, one more if a conjugate pair would be cut
+    const int m_cols = wi[n_eig - 1] > 0.0 && n_eig < n ? n_eig + 1 : n_eig;
+    const size_t ld = (size_t)m_cols;
+    uint32_t cmask = 0;
+    for (int j = 0; j < m_cols; j++) {
+        if (wi[j] > 0.0 && j + 1 < m_cols) cmask |= 3u << j;
+        for (int i = 0; i < n; i++) V[i * ld + j] = Y[i * n + j];
+    }
+    // W = L V - V Theta (Theta block diagonal: a pair is the 2 x 2 block [wr wi; -wi wr]), the entries of a row of L in column order
+    for (int i = 0; i < n; i++)
+        for (int j = 0; j < m_cols; j++) {
+            double acc = 0.0;
+            for (int e = 0; e < k; e++) acc = acc + val[i * k + e] * V[(size_t)col[i * k + e] * ld + j];
+            double t = wr[j] * V[i * ld + j];
+            if (cmask >> j & 1) t = wi[j] > 0.0 ? t - wi[j] * V[i * ld + j + 1] : t - wi[j] * V[i * ld + j - 1];
+            W[i * ld + j] = acc - t;
+        }
+    double residual = 0.0;
+    for (int j = 0; j < m_cols; j++) {
+        const int j0 = (cmask >> j & 1) && !(wi[j] > 0.0) ? j - 1 : j, j1 = (cmask >> j & 1) ? j0 + 1 : j0;
+        double nv = 0.0, nr = 0.0;
+        for (int i = 0; i < n; i++)
+            for (int c = j0; c <= j1; c++) { nv += V[i * ld + c] * V[i * ld + c]; nr += W[i * ld + c] * W[i * ld + c]; }
+        const double res = nv > 0.0 ? std::sqrt(nr / nv) : __builtin_inf();
+        residual = res > residual || res != res ? res : residual;
+    }
+    sp_hand_out(V, ld, (size_t)n, n_eig, m_cols, cmask, wr, wi, eigenvalues, vectors);
+    if (info) sp_fill_info(info, n_eig, 0, 0, 0, cmask, m_cols, residual, wr, wi);
+    return residual <= tol ? PCR_OK : PCR_SPECTRAL_NOT_CONVERGED;
+}
+
 }  // namespace
 
 extern "C" int pcr_mat64_knn_f64(pcr_ctx* ctx, pcr_mat64* m, int k, int32_t* idx, double* d2)
@@ -502,11 +589,13 @@ extern "C" int pcr_spectral_embed_f64(pcr_ctx* ctx, pcr_spgraph* g, int n_eig, i
     if (!ctx || !g || !g->col || !g->val || g->n < 1) return fail(ctx, PCR_ERR_ARG, "pcr_spectral_embed_f64");
     const size_t n = g->n;
     if (n_eig == 0) n_eig = (int)(n < 8 ? n : 8);
+    const bool dense = n_basis == 0 && n <= (size_t)SP_DENSE_MAX;
     if (n_basis == 0) { n_basis = n_eig + 5 > SP_NB ? SP_NB : n_eig + 5; if ((size_t)n_basis > n) n_basis = (int)n; }
     if (n_eig < 1 || n_basis < n_eig || n_basis > SP_NB || (size_t)n_basis > n || tol != tol) return fail(ctx, PCR_ERR_ARG, "pcr_spectral_embed_f64: 1 <= n_eig <= n_basis <= 16, n_basis <= n");
     if (!(tol > 0.0)) tol = 1e-10;
     if (max_iter <= 0) max_iter = 400000;
     PCR_HIP(ctx, hipSetDevice(ctx->device));
+    if (dense) return sp_embed_dense(ctx, g, n_eig, tol, eigenvalues, vectors, info);
     SpRun r;
     r.ctx = ctx; r.g = g; r.n = (uint32_t)n; r.nb = n_basis;
     r.rowblocks = (uint32_t)((n + 255) / 256);
@@ -587,37 +676,13 @@ extern "C" int pcr_spectral_embed_f64(pcr_ctx* ctx, pcr_spgraph* g, int n_eig, i
         }
         if (residual <= tol) { status = PCR_OK; break; }
     }
-    // the Ritz vectors of the last check lie in Z: normalise, fix the sign, hand out the first n_eig columns
+    // the Ritz vectors of the last check lie in Z
     if (ensure_stage(ctx, n * SP_NB * sizeof(double)) != PCR_OK) return fail(ctx, PCR_ERR_NOMEM, "pcr_spectral_embed_f64: staging");
     double* V = (double*)ctx->host_stage;
     PCR_HIP(ctx, hipMemcpyAsync(V, r.b.Z, n * SP_NB * sizeof(double), hipMemcpyDeviceToHost, st));
     PCR_HIP(ctx, hipStreamSynchronize(st));
-    for (int j = 0; j < m_cols; j++) {
-        const bool cpx = cmask >> j & 1;
-        if (cpx && !(wi[j] > 0.0)) continue;               // handled with its partner
-        const int w = cpx ? 2 : 1;
-        double s = 0.0;
-        for (size_t i = 0; i < n; i++)
-            for (int c = j; c < j + w; c++) s += V[i * SP_NB + c] * V[i * SP_NB + c];
-        double big = 0.0, sign = 1.0;
-        for (size_t i = 0; i < n; i++)
-            if (std::fabs(V[i * SP_NB + j]) > big) { big = std::fabs(V[i * SP_NB + j]); sign = V[i * SP_NB + j] < 0.0 ? -1.0 : 1.0; }
-        const double sc = s > 0.0 ? sign / std::sqrt(s) : 0.0;
-        for (size_t i = 0; i < n; i++)
-            for (int c = j; c < j + w; c++) V[i * SP_NB + c] *= sc;
-    }
-    if (vectors)
-        for (size_t i = 0; i < n; i++)
-            for (int j = 0; j < n_eig; j++) vectors[i * n_eig + j] = V[i * SP_NB + j];
-    if (eigenvalues) for (int j = 0; j < n_eig; j++) eigenvalues[j] = wr[j];
-    if (info) {
-        memset(info, 0, sizeof(*info));
-        info->n_eig = n_eig; info->n_basis = n_basis; info->solver_steps = steps; info->one_workgroup = one ? 1 : 0;
-        info->complex_mask = cmask & ((n_eig >= 32 ? 0u : (1u << n_eig)) - 1u);
-        if (m_cols > n_eig) info->complex_mask |= 1u << (n_eig - 1);
-        info->residual = residual;
-        for (int j = 0; j < n_eig; j++) { info->eigenvalues[j] = wr[j]; info->eigenvalues_im[j] = wi[j]; }
-    }
+    sp_hand_out(V, SP_NB, n, n_eig, m_cols, cmask, wr, wi, eigenvalues, vectors);
+    if (info) sp_fill_info(info, n_eig, n_basis, steps, one ? 1 : 0, cmask, m_cols, residual, wr, wi);
     return status;
 }
 
@@ -632,7 +697,7 @@ extern "C" int pcr_spectral_cluster_f64(pcr_ctx* ctx, pcr_mat64* m, int k_neighb
     pcr_spgraph* g = nullptr;
     int rc = pcr_spectral_graph_f64(ctx, m, k_neighbors, &g);
     if (rc != PCR_OK) return rc;
-    pcr_spectral_info inf;
+    pcr_spectral_info inf{};                              // an embedding that refuses its arguments fills nothing: the caller then reads zeros
     std::vector<double> vec(n * (size_t)n_eig), eig(n_eig);
     rc = pcr_spectral_embed_f64(ctx, g, n_eig, 0, 0.0, 0, eig.data(), vec.data(), &inf);
     pcr_spgraph_destroy(ctx, g);

@@ -724,13 +724,25 @@ int pcr_gmm_predict_f64(pcr_ctx* ctx, pcr_mat64* data, int k, const double* mean
  *   such) positive.  A complex Ritz pair among the n_eig is flagged in info->complex_mask (bit j: column j belongs to a pair; its two
  *   columns hold the real and the imaginary part of the unit complex vector, the real part's largest component positive) and its imaginary
  *   part stands in info->eigenvalues_im.  Positive status PCR_SPECTRAL_NOT_CONVERGED when max_iter ends first (outputs = the last Ritz pairs).
+ *   A pair that n_eig cuts is completed inside while n_eig < n_basis (bit n_eig - 1 is set, column n_eig - 1 is the real part of the unit
+ *   complex vector); with n_basis == n_eig there is no room, its first member is then treated as real and the call ends NOT_CONVERGED.
+ *   n <= 32 with n_basis == 0: no iteration.  L is read back as a dense matrix and the host solves it whole (the algorithm of
+ *   pcr_eig_small_f64 after a permutation that isolates eigenvalues): same outputs, solver_steps = 0, n_basis = 0 and one_workgroup = 0 in
+ *   info, residual <= tol decides between PCR_OK and NOT_CONVERGED as above.  Block iteration cannot serve every such graph: L of a 2-row
+ *   cloud has the eigenvalue 2, which A maps to 0, and with k_neighbors = 2 (every row has one neighbour, mutual pairs give the eigenvalues
+ *   0 and 2, the rows hanging off them Jordan blocks at 1) L is defective.  A given n_basis always asks for the iteration: it returns
+ *   PCR_ERR_STATE when Cholesky-QR meets a pivot <= 0 (rank((I - L/2)^8) < n_basis: n_basis near n, or such a graph), and on a defective L of
+ *   any size it either stalls near a residual of 1e-8 or stops at tol with an eigenvalue off by up to 1e-3 (a Jordan block of size m turns a
+ *   residual r into an eigenvalue error near r^(1/m)).  k_neighbors = 2 above 32 rows is therefore accepted but not served accurately.
  * pcr_spectral_select_k (host): the eigengap rule of :188-197 as written — diff = e[1] - e[0]; the first i >= 1 with e[i + 1] - e[i] >
  *   50 diff gives K = i + 1 — reading e[i + 1] only while i + 1 < n_eig (the reference reads one past its vector); 1 if no gap fires.
  * pcr_spectral_cluster_f64: graph, embedding (n_eig, its default basis, tol 1e-10), K = n_clusters if > 0 else the rule (K <= min(8, n_eig)),
  *   initial_choice (:249-289: row 0, then every row whose squared distance to each chosen row is >= 1e-4, until K are chosen; on the host
  *   over the n x K features) — PCR_SPECTRAL_FEW_SEEDS if fewer than K exist —, then pcr_kmeans_fit_f64(PCR_KMEANS_CPP, tol 1e-4, 200).
  *   PCR_SPECTRAL_COMPLEX if a complex pair falls inside the K columns (the reference takes .real() of an arbitrary phase there).
- *   labels: n int32.  features (may be NULL): n x K.  info (may be NULL) carries K, the eigenvalues, steps, residual and K-Means passes. */
+ *   labels: n int32.  features (may be NULL): n x K.  info (may be NULL) carries K, the eigenvalues, steps, residual and K-Means passes; it is
+ *   written once the graph exists, and holds zeros in every byte when the embedding then refuses its arguments (n_eig > n).  A call that
+ *   fails before that (arguments, PCR_SPECTRAL_DUPLICATE) leaves it untouched. */
 #define PCR_SPECTRAL_DUPLICATE 2
 #define PCR_SPECTRAL_COMPLEX 3
 #define PCR_SPECTRAL_NOT_CONVERGED 4
