@@ -76,7 +76,7 @@ ABI_SYMBOLS = [
     "pcr_device_count", "pcr_ctx_create", "pcr_ctx_destroy", "pcr_ctx_sync", "pcr_ctx_last_error", "pcr_version", "pcr_ctx_device_info",
     "pcr_cloud_create", "pcr_cloud_clone", "pcr_cloud_assign", "pcr_cloud_read", "pcr_cloud_size", "pcr_cloud_destroy",
     "pcr_nn1_f32", "pcr_nn1_f32_async", "pcr_nn1_fetch", "pcr_transform_f32", "pcr_kabsch_sums", "pcr_kabsch_solve", "pcr_kabsch_grid_exponent", "pcr_kabsch_limbs_to_sums",
-    "pcr_icp_p2p_f32", "pcr_icp_last_chain", "pcr_icp_move_route", "pcr_plane_count_f64", "pcr_plane_mask_f64", "pcr_knn_f64", "pcr_radius_f64",
+    "pcr_icp_p2p_f32", "pcr_icp_last_chain", "pcr_icp_move_route", "pcr_s3_walk_visits", "pcr_plane_count_f64", "pcr_plane_mask_f64", "pcr_knn_f64", "pcr_radius_f64",
     "pcr_comm_unique_id", "pcr_comm_init_rccl", "pcr_comm_init_callback", "pcr_comm_destroy", "pcr_comm_selftest", "pcr_shard_range",
     "pcr_prof_reset", "pcr_prof_get", "pcr_prof_get_each", "pcr_tune_set",
     "pcr_grid_stats", "pcr_nn1_stats", "pcr_selftest_mfma_bf16", "pcr_selftest_mfma_f16", "pcr_selftest_mfma_bf16_v2", "pcr_selftest_mfma_f16_v2", "pcr_selftest_sign_f16", "pcr_selftest_sphere_f16", "pcr_ctx_mfma_check", "pcr_voxel_filter_f32", "pcr_iss_keypoints_f32", "pcr_icp_p2plane_f32", "pcr_cloud_knn_f64", "pcr_normals_knn_f64", "pcr_cloud_pca_f64", "pcr_fast_eigen3x3", "pcr_ground_seeds_f64", "pcr_ground_detection_f64",
@@ -136,6 +136,7 @@ def lib():
     L.pcr_icp_p2p_f32.argtypes = [vp, vp, vp, vp, C.POINTER(IcpParams), vp, C.POINTER(IcpStats)]
     L.pcr_icp_last_chain.argtypes = [vp]
     L.pcr_icp_move_route.argtypes = [C.c_uint64, C.c_uint64, C.c_int] + [C.c_int64] * 7
+    L.pcr_s3_walk_visits.argtypes = [C.c_uint32, vp, vp, C.c_uint32, vp, sz, C.POINTER(sz)]
     L.pcr_plane_count_f64.argtypes = [vp, vp, vp, sz, C.c_double, vp]
     L.pcr_plane_mask_f64.argtypes = [vp, vp, vp, C.c_double, vp, C.POINTER(C.c_int64)]
     L.pcr_knn_f64.argtypes = [vp, vp, sz, vp, sz, C.c_int, vp, vp]
@@ -250,6 +251,19 @@ def icp_move_route(n_src: int, n_tgt: int, nranks: int = 1, move_in_search: int 
     (pcr_icp_move_route; raw tune values, 0 = default; host logic, no GPU)?"""
     return bool(lib().pcr_icp_move_route(n_src, n_tgt, nranks, move_in_search, fused_sums, fused_sums_min, s3_transposed, sphere_qg,
                                          sphere_l0_per_slice, sphere_blocks))
+
+
+def s3_walk_visits(S0: int, rows, tiles, n_rec: int):
+    """What the default three-level sphere kernel visits in level-0 super-tile S0 for the flag masks rows (8 x u32) and tiles (256 x u16), in its order:
+    an (m, 2) u32 array of (kind, value) pairs (pcr_s3_walk_visits; host logic, no GPU)."""
+    rows = np.ascontiguousarray(rows, np.uint32).reshape(8)
+    tiles = np.ascontiguousarray(tiles, np.uint16).reshape(256)
+    out = np.zeros((8192, 2), np.uint32)
+    m = C.c_size_t(0)
+    rc = lib().pcr_s3_walk_visits(S0, rows.ctypes.data, tiles.ctypes.data, n_rec, out.ctypes.data, out.size, C.byref(m))
+    if rc:
+        raise PcrError(f"pcr_s3_walk_visits failed: {rc}")
+    return out[:m.value].copy()
 
 
 def fast_eigen3x3(A):

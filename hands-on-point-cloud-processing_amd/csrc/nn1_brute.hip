@@ -2096,3 +2096,47 @@ int nn1_unpack(pcr_ctx* ctx, size_t n, uint32_t* idx_dev, float* d2_dev)
 }
 
 }  // namespace pcr
+
+// The visits of STRACK3's scalar walk (nn1_sphere.hpp, S3 SCALAR WALK) over ONE level-0 super-tile, enumerated on the host with the kernel's own index
+// functions and loop order: pure host logic for the test that sets it against the list form (tests/test_strack3_scalar_walk.py).  Contract: include/pcr.h
+extern "C" int pcr_s3_walk_visits(uint32_t S0, const uint32_t rows[8], const uint16_t tiles[256], uint32_t n_rec, uint32_t* out, size_t cap, size_t* n_out)
+{
+    using namespace pcr;
+    if (!rows || !tiles || !n_out || (!out && cap)) return PCR_ERR_ARG;
+    size_t k = 0;
+    bool fits = true;
+    auto emit = [&](uint32_t kind, uint32_t v) { if (2 * k + 2 <= cap) { out[2 * k] = kind; out[2 * k + 1] = v; } else fits = false; k++; };
+    const uint32_t n_l1_tiles = (n_rec + 511u) / 512u, n_l2 = (n_rec + 31u) / 32u;
+    uint32_t w0[8];
+    for (uint32_t t = 0; t < 8; t++) w0[t] = rows[t] & s3w_valid32((S0 * 8u + t) * 32u, n_l1_tiles);
+    unsigned long long m0 = w0[0] | ((unsigned long long)w0[1] << 32), m1 = w0[2] | ((unsigned long long)w0[3] << 32),
+                       m2 = w0[4] | ((unsigned long long)w0[5] << 32), m3 = w0[6] | ((unsigned long long)w0[7] << 32);
+    for (uint32_t s1b = S0 * 32u; m0 | m1 | m2 | m3; s1b += 8u) {
+        unsigned long long cur = m0;
+        m0 = m1; m1 = m2; m2 = m3; m3 = 0ull;
+        while (cur) {
+            uint32_t rm;
+            const uint32_t S1 = s1b + s3w_take_run(cur, rm);
+            emit(0u, S1);
+            unsigned long long tl = 0ull, th = 0ull;
+            for (uint32_t u = 0; u < 8; u++) {
+                if (!((rm >> u) & 1u)) continue;
+                const uint32_t T1 = S1 * 8u + u;
+                emit(1u, T1);
+                const unsigned long long tm = tiles[T1 - S0 * 256u];
+                if (u < 4) tl |= tm << (16 * (u & 3)); else th |= tm << (16 * (u & 3));
+            }
+            const uint32_t t2b = S1 * 128u;
+            tl &= s3w_valid64(t2b, n_l2); th &= s3w_valid64(t2b + 64u, n_l2);
+            uint32_t left = (uint32_t)__builtin_popcountll(tl) + (uint32_t)__builtin_popcountll(th), tb = 0u;
+            while (left) {
+                const uint32_t nb = left < 4u ? left : 4u;
+                emit(2u, nb);
+                for (uint32_t u = 0; u < nb; u++) emit(3u, t2b + s3w_next(tl, th, tb));
+                left -= nb;
+            }
+        }
+    }
+    *n_out = k;
+    return fits ? PCR_OK : PCR_ERR_ARG;
+}

@@ -84,7 +84,13 @@ __device__ __forceinline__ uint32_t s2_or16(const f32x16 acc)
 // level 0 a wave looks at 8 level-0 tiles, then only at the level-1 tiles whose sphere some query's ball reaches: a few of 240.)
 constexpr int S3_L1LIST = 256;                // level-1 tiles of one level-0 super-tile
 
-template <int QG>
+// LISTS: the rows form and the instances with several query groups keep their flagged level-1 tiles and level-2 tiles as lists in LDS, written by lane 0,
+// fenced, and read back per run / per batch (ds_read_b32 + v_readfirstlane per entry).  The default instance — ONE group, transposed — gets every flag
+// set as a wave-uniform ballot, i.e. in scalar registers, and walks it there (S3 SCALAR WALK below): no list, no fence, no read-back, and a group mask
+// that is always 1 is not carried.  Its four waves hold 9 216 B per workgroup instead of 21 504.  Per wave of 32 queries at the settled 120 k pose
+// (PMC): 1 500 -> 1 263 vector, 1 163 -> 994 scalar, 109 -> 21 LDS instructions, the 32 MFMAs unchanged; a settled search 26.8 -> 21.5 us
+// (profiles/strack3_scalar_walk.txt).
+template <int QG, bool LISTS>
 struct S3WaveLds {
     float4 q[QG * 32];
     unsigned long long best[QG * 32];
@@ -92,6 +98,42 @@ struct S3WaveLds {
     uint32_t tiles[S2_TILES];                 // level-2 tile | groups << 28
     uint32_t list[S2_CAP + 256 * QG];         // (chunk << 7) | query slot: what a batch of four level-2 tiles can add fits behind S2_CAP entries
 };
+template <int QG>
+struct S3WaveLds<QG, false> {
+    float4 q[QG * 32];
+    unsigned long long best[QG * 32];
+    uint32_t list[S2_CAP + 256 * QG];
+};
+
+// ---- S3 SCALAR WALK: the index arithmetic of the default instance's walk over its flag masks, shared by the kernel and by the host enumeration
+// (pcr_s3_walk_visits, tests/test_strack3_scalar_walk.py).  Level 0 leaves eight 32-bit row masks per level-0 super-tile S0: bit j of word t is
+// level-1 tile T1 = (S0 * 8 + t) * 32 + j.  Two words make one 64-bit scalar; level-1 super-tile S0 * 32 + 8 i + B (eight level-1 tiles, one RUN) is
+// byte B of scalar i.  Level 1 leaves one 16-bit mask per level-1 tile of the run: 128 bits, bit 16 u + k = level-2 tile (S1 * 8 + u) * 16 + k.
+// Rows / tiles [first, first + 32 or 64) that lie below n (the index is padded to whole super-tiles; rows behind the records are never visited):
+__host__ __device__ __forceinline__ uint32_t s3w_valid32(uint32_t first, uint32_t n)
+{
+    return n <= first ? 0u : n - first >= 32u ? ~0u : (1u << (n - first)) - 1u;
+}
+__host__ __device__ __forceinline__ unsigned long long s3w_valid64(uint32_t first, uint32_t n)
+{
+    return n <= first ? 0ull : n - first >= 64u ? ~0ull : (1ull << (n - first)) - 1ull;
+}
+// the lowest non-empty byte of cur: its position B and its eight bits (the flagged level-1 tiles of the run); the byte is cleared
+__host__ __device__ __forceinline__ uint32_t s3w_take_run(unsigned long long& cur, uint32_t& rm)
+{
+    const uint32_t B = (uint32_t)__builtin_ctzll(cur) >> 3;
+    rm = (uint32_t)(cur >> (8u * B)) & 0xFFu;
+    cur &= ~(0xFFull << (8u * B));
+    return B;
+}
+// the lowest set bit of the 128 (lo, hi; at least one is set): its position, cleared.  hi moves down once lo is used up — base counts the 64 it stood for
+__host__ __device__ __forceinline__ uint32_t s3w_next(unsigned long long& lo, unsigned long long& hi, uint32_t& base)
+{
+    if (!lo) { lo = hi; hi = 0ull; base += 64u; }
+    const uint32_t b = (uint32_t)__builtin_ctzll(lo);
+    lo &= lo - 1ull;
+    return base + b;
+}
 
 // TR: how levels 0 and 1 read "which sphere rows did any of the 32 queries flag" (tune nn1_s3_transposed: 1 = true and default, 2 = false).
 //   true:  the product runs TRANSPOSED — the queries' operand as A, the stored sphere tile as B (both operands of v_mfma_f32_32x32x16_f16 have the
@@ -142,8 +184,9 @@ __device__ __forceinline__ void nn1_strack3_body(
     const uint32_t n = lane & 31;
     const bool h = lane >= 32;
     const uint32_t qb = blockIdx.x, sl = blockIdx.y;
-    __shared__ S3WaveLds<QG> lds_all[NN_BLOCK / 64];
-    S3WaveLds<QG>& L = lds_all[wave];
+    constexpr bool SW = QG == 1 && TR;                        // the scalar walk: flag masks stay in SGPRs, no lists
+    __shared__ S3WaveLds<QG, !SW> lds_all[NN_BLOCK / 64];
+    S3WaveLds<QG, !SW>& L = lds_all[wave];
     const uint32_t qbase = (qb * (NN_BLOCK / 64) + wave) * (32 * QG);
     if (qbase >= ns) return;                                  // (a surplus wave: no workgroup barrier below)
     float qx[NP], qy[NP], qz[NP], thr[NP];
@@ -251,35 +294,40 @@ __device__ __forceinline__ void nn1_strack3_body(
     // LEVEL 2 over the collected tiles of 32 records: the per-record filter for the groups that flagged the tile, four tiles per trip to memory;
     // flagged (query, chunk) pairs are listed and evaluated exactly between batches (from flush_at entries) and at the end (from flush_end);
     // thresholds fall after an evaluation
-    auto level2 = [&](uint32_t n_tiles) {
+    auto l2_tile = [&](const uint4 A, uint32_t T, uint32_t gm) {      // one level-2 tile for the groups gm (wave-uniform): its flagged (query, chunk) pairs go on the list
+        const uint32_t chunk = 2u * T + (h ? 1u : 0u);
+#pragma unroll
+        for (int g = 0; g < QG; g++) {
+            if (!((gm >> g) & 1u)) continue;                  // (wave-uniform)
+            const uint32_t og = s2_or16(__builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, A), __builtin_bit_cast(f16x8, bq2[g]), zero, 0, 0, 0));
+            if (stats) st_l2++;
+            const unsigned long long m = __builtin_amdgcn_ballot_w64((int)og < 0);
+            if (!m) continue;
+            if ((int)og < 0) L.list[cnt + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] = (chunk << 7) | (uint32_t)(g * 32) | n;
+            cnt += (uint32_t)__popcll(m);
+        }
+    };
+    auto flush_from = [&](uint32_t at) {                      // evaluate the listed pairs once there are at least `at` of them; thresholds fall behind an evaluation
+        if (cnt >= at) { s2_flush<QG>(L, cnt, records, lane); st_flushes++; st_eval += cnt; cnt = 0; refresh(); }
+    };
+    auto level2 = [&](auto& LL, uint32_t n_tiles) {           // (the list form; LL = L, a parameter so that the instance without lists never names them)
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");       // (lane 0 wrote the list)
         for (uint32_t k0 = 0; k0 < n_tiles; k0 += 4) {
             uint32_t Eb[4];
             uint4 Ab[4];
 #pragma unroll
             for (int u = 0; u < 4; u++) {
-                Eb[u] = (uint32_t)__builtin_amdgcn_readfirstlane((int)L.tiles[min(k0 + u, n_tiles - 1)]);
+                Eb[u] = (uint32_t)__builtin_amdgcn_readfirstlane((int)LL.tiles[min(k0 + u, n_tiles - 1)]);
                 Ab[u] = ops[(size_t)(Eb[u] & 0x0FFFFFFFu) * 64 + lane];
             }
 #pragma unroll
             for (int u = 0; u < 4; u++) {
                 if (k0 + u >= n_tiles) break;                 // (wave-uniform)
-                const uint32_t T = Eb[u] & 0x0FFFFFFFu, gm = Eb[u] >> 28;
-                const uint32_t chunk = 2u * T + (h ? 1u : 0u);
-#pragma unroll
-                for (int g = 0; g < QG; g++) {
-                    if (!((gm >> g) & 1u)) continue;          // (wave-uniform)
-                    const uint32_t og = s2_or16(__builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, Ab[u]), __builtin_bit_cast(f16x8, bq2[g]), zero, 0, 0, 0));
-                    if (stats) st_l2++;
-                    const unsigned long long m = __builtin_amdgcn_ballot_w64((int)og < 0);
-                    if (!m) continue;
-                    if ((int)og < 0) L.list[cnt + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] = (chunk << 7) | (uint32_t)(g * 32) | n;
-                    cnt += (uint32_t)__popcll(m);
-                }
+                l2_tile(Ab[u], Eb[u] & 0x0FFFFFFFu, Eb[u] >> 28);
             }
-            if (cnt >= flush_at) { s2_flush<QG>(L, cnt, records, lane); st_flushes++; st_eval += cnt; cnt = 0; refresh(); }      // (flush_at <= S2_CAP: host)
+            flush_from(flush_at);                             // (flush_at <= S2_CAP: host)
         }
-        if (cnt >= flush_end) { s2_flush<QG>(L, cnt, records, lane); st_flushes++; st_eval += cnt; cnt = 0; refresh(); }
+        flush_from(flush_end);
     };
     const uint32_t n_l1_tiles = (n_rec + 511u) / 512u;        // level-1 tiles that hold records (rows behind them: W = +inf, never flagged)
     for (uint32_t S0 = sb; S0 < se; S0++) {
@@ -287,6 +335,7 @@ __device__ __forceinline__ void nn1_strack3_body(
         setup0(l0_centres[S0]);
         PCR_S2_TICK(pt_pro)
         uint32_t n1 = 0;
+        uint32_t w0[8];                                       // (SW) the flagged rows of the eight level-0 tiles: 256 bits, one per level-1 tile
         uint4 A0s[8];                                         // the eight level-0 tiles at once: one round trip to memory instead of eight
 #pragma unroll
         for (int t = 0; t < 8; t++) A0s[t] = l0_ops[((size_t)S0 * 8 + t) * 64 + lane];
@@ -323,7 +372,11 @@ __device__ __forceinline__ void nn1_strack3_body(
                     }
                 }
             }
-            {
+            if constexpr (SW) {                               // the word IS the list: rows behind the records masked once, not bit by bit
+                w0[t] = rmask[0] & s3w_valid32(T0 * 32u, n_l1_tiles);
+                n1 += (uint32_t)__popc(w0[t]);
+            }
+            else {
                 uint32_t un = rmask[0];
 #pragma unroll
                 for (int g = 1; g < QG; g++) un |= rmask[g];
@@ -353,66 +406,131 @@ __device__ __forceinline__ void nn1_strack3_body(
         // LEVEL 1 over the listed level-1 tiles, for the groups that reached them: chunk rows.  The list is ascending, so the (at most eight) tiles
         // of one level-1 super-tile follow each other: their operands come in ONE trip to memory, the super-tile's scale serves level 1 and
         // level 2, and the level-2 tiles with a flagged chunk are filtered and evaluated before the next super-tile's operands are built
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");       // (lane 0 wrote the list)
-        for (uint32_t k = 0; k < n1;) {
-            uint32_t Er[8];
-            uint4 Ar[8];
+        if constexpr (SW) {
+            // the 256 row bits as four 64-bit scalars, walked from the lowest: a RUN — the flagged level-1 tiles of one level-1 super-tile — is one
+            // non-empty byte, its operands the contiguous 8 KB at l1_ops + S1 * 8 * 64: one address, the eight tiles at immediate offsets of
+            // -4 KB ... +3 KB around the middle of the block (global loads of gfx950 carry a signed 13-bit offset)
+            unsigned long long m0 = w0[0] | ((unsigned long long)w0[1] << 32), m1 = w0[2] | ((unsigned long long)w0[3] << 32),
+                               m2 = w0[4] | ((unsigned long long)w0[5] << 32), m3 = w0[6] | ((unsigned long long)w0[7] << 32);
+            const uint32_t n_l2 = (n_rec + 31u) / 32u;        // level-2 tiles that hold records (tiles of the index's padding hold nothing)
+#pragma nounroll
+            for (uint32_t s1b = S0 * 32u; m0 | m1 | m2 | m3; s1b += 8u) {
+                unsigned long long cur = m0;
+                m0 = m1; m1 = m2; m2 = m3; m3 = 0ull;
+                while (cur) {                                 // wave-uniform; ascending level-1 super-tiles
+                    uint32_t rm;
+                    const uint32_t S1 = s1b + s3w_take_run(cur, rm);
+                    const uint4* const mid = l1_ops + ((size_t)S1 * 8 + 4) * 64 + lane;
+                    uint4 Ar[8];
 #pragma unroll
-            for (int u = 0; u < 8; u++) {
-                Er[u] = (uint32_t)__builtin_amdgcn_readfirstlane((int)L.l1list[min(k + u, n1 - 1)]);
-                Ar[u] = l1_ops[(size_t)(Er[u] & 0x0FFFFFFFu) * 64 + lane];
-            }
-            const uint32_t S1 = (Er[0] & 0x0FFFFFFFu) >> 3;
-            setup1(l1_centres[S1]);
-            uint32_t n_tiles = 0, run = 0;
+                    for (int u = 0; u < 8; u++) Ar[u] = mid[(u - 4) * 64];
+                    // (Measured and dropped: the loads of the run's unflagged tiles skipped by wave-uniform branches — eight branches in front of the
+                    // one trip to memory: 53.7-54.2 us per step of the headline against 52.8-54.3 with all eight loads, medians 53.9 / 53.0,
+                    // four processes each, alternating: profiles/strack3_scalar_walk.txt.)
+                    setup1(l1_centres[S1]);
+                    unsigned long long tl = 0ull, th = 0ull;  // the flagged level-2 tiles of the run: 8 x 16 bits
 #pragma unroll
-            for (int u = 0; u < 8; u++) {
-                if (k + u >= n1 || ((Er[u] & 0x0FFFFFFFu) >> 3) != S1) break;       // (wave-uniform: the end of the list or of this super-tile's run)
-                run++;
-                const uint32_t T1 = Er[u] & 0x0FFFFFFFu, gm1 = Er[u] >> 28;
-                uint32_t tmask[QG];                           // bit k: level-2 tile k of this level-1 tile (chunks 2 k, 2 k + 1) flagged by the group
-                uint32_t un = 0u;
-#pragma unroll
-                for (int g = 0; g < QG; g++) {
-                    tmask[g] = 0u;
-                    if (!((gm1 >> g) & 1u)) continue;         // (wave-uniform)
-                    if (TR) {                                 // (stored row n of the tile = chunk 2 (n & 15) + (n >> 4): level-2 tile k is rows k and k + 16)
-                        const uint32_t og = s2_or16(__builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, bq1[g]), __builtin_bit_cast(f16x8, Ar[u]), zero, 0, 0, 0));
+                    for (int u = 0; u < 8; u++) {
+                        if (!((rm >> u) & 1u)) continue;      // (wave-uniform)
+                        const uint32_t og = s2_or16(__builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, bq1[0]), __builtin_bit_cast(f16x8, Ar[u]), zero, 0, 0, 0));
                         if (stats) st_l1++;
-                        const unsigned long long m = __builtin_amdgcn_ballot_w64((int)og < 0);
+                        const unsigned long long m = __builtin_amdgcn_ballot_w64((int)og < 0);      // (stored row n of the tile = chunk 2 (n & 15) + (n >> 4): level-2 tile k is rows k and k + 16)
                         const uint32_t cm = (uint32_t)m | (uint32_t)(m >> 32);
-                        tmask[g] = (cm | (cm >> 16)) & 0xFFFFu;
+                        const uint32_t tm = (cm | (cm >> 16)) & 0xFFFFu;
+                        if (stats) st_l2flag += (unsigned long long)__popc(tm);
+                        if (u < 4) tl |= (unsigned long long)tm << (16 * (u & 3)); else th |= (unsigned long long)tm << (16 * (u & 3));
                     }
-                    else {
-                        const f32x16 acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, Ar[u]), __builtin_bit_cast(f16x8, bq1[g]), zero, 0, 0, 0);
-                        if (stats) st_l1++;
-                        if (!__builtin_amdgcn_ballot_w64((int)s2_or16(acc) < 0)) continue;
+                    const uint32_t t2b = S1 * 128u;           // the run's first level-2 tile
+                    tl &= s3w_valid64(t2b, n_l2); th &= s3w_valid64(t2b + 64u, n_l2);
+                    PCR_S2_TICK(pt_l1)
+                    // LEVEL 2: the 128 bits in ascending order, four tiles per trip to memory (operands: ops + (t2b + bit) * 64)
+                    const uint4* const rb = ops + (size_t)t2b * 64 + lane;
+                    uint32_t left = (uint32_t)__popcll(tl) + (uint32_t)__popcll(th), tb = 0u;
+                    while (left) {
+                        const uint32_t nb = min(left, 4u);
+                        uint32_t id[4];
+                        uint4 Ab[4];
 #pragma unroll
-                        for (int i = 0; i < 8; i++) {         // (accumulators i and i + 8 of lane-half h: rows k and k + 16, k = 8 (i >> 2) + 4 h + (i & 3))
-                            const unsigned long long m = __builtin_amdgcn_ballot_w64((int)(__float_as_uint(acc[i]) | __float_as_uint(acc[i + 8])) < 0);
-                            tmask[g] |= ((uint32_t)m != 0u ? 1u : 0u) << (8 * (i >> 2) + (i & 3));
-                            tmask[g] |= ((uint32_t)(m >> 32) != 0u ? 1u : 0u) << (8 * (i >> 2) + 4 + (i & 3));
+                        for (int u = 0; u < 4; u++) {
+                            if (u && (uint32_t)u >= nb) break;               // (wave-uniform: a short batch loads what it has)
+                            id[u] = s3w_next(tl, th, tb);
+                            Ab[u] = rb[id[u] * 64u];
                         }
-                    }
-                    un |= tmask[g];
-                }
-                if (stats) st_l2flag += (unsigned long long)__popc(un);
-                while (un) {                                  // wave-uniform (at most 8 x 16 = 128 tiles per super-tile: the list of 512 holds them)
-                    const uint32_t k2 = (uint32_t)__builtin_ctz(un);
-                    un &= un - 1u;
-                    uint32_t gm = 0u;
 #pragma unroll
-                    for (int g = 0; g < QG; g++) gm |= ((tmask[g] >> k2) & 1u) << g;
-                    const uint32_t T2 = T1 * 16u + k2;
-                    if ((size_t)T2 * 32 < n_rec) { if (lane == 0) L.tiles[n_tiles] = T2 | (gm << 28); n_tiles++; }      // (tiles of the index's padding hold nothing)
+                        for (int u = 0; u < 4; u++) {
+                            if ((uint32_t)u >= nb) break;     // (wave-uniform)
+                            l2_tile(Ab[u], t2b + id[u], 1u);
+                        }
+                        left -= nb;
+                        flush_from(flush_at);                 // (flush_at <= S2_CAP: host)
+                    }
+                    flush_from(flush_end);
+                    PCR_S2_TICK(pt_l2)
                 }
             }
-            k += run;
-            PCR_S2_TICK(pt_l1)
-            if (n_tiles) level2(n_tiles);
-            PCR_S2_TICK(pt_l2)
         }
-        if (cnt) { s2_flush<QG>(L, cnt, records, lane); st_flushes++; st_eval += cnt; cnt = 0; refresh(); }
+        else {
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");       // (lane 0 wrote the list)
+            for (uint32_t k = 0; k < n1;) {
+                uint32_t Er[8];
+                uint4 Ar[8];
+#pragma unroll
+                for (int u = 0; u < 8; u++) {
+                    Er[u] = (uint32_t)__builtin_amdgcn_readfirstlane((int)L.l1list[min(k + u, n1 - 1)]);
+                    Ar[u] = l1_ops[(size_t)(Er[u] & 0x0FFFFFFFu) * 64 + lane];
+                }
+                const uint32_t S1 = (Er[0] & 0x0FFFFFFFu) >> 3;
+                setup1(l1_centres[S1]);
+                uint32_t n_tiles = 0, run = 0;
+#pragma unroll
+                for (int u = 0; u < 8; u++) {
+                    if (k + u >= n1 || ((Er[u] & 0x0FFFFFFFu) >> 3) != S1) break;       // (wave-uniform: the end of the list or of this super-tile's run)
+                    run++;
+                    const uint32_t T1 = Er[u] & 0x0FFFFFFFu, gm1 = Er[u] >> 28;
+                    uint32_t tmask[QG];                           // bit k: level-2 tile k of this level-1 tile (chunks 2 k, 2 k + 1) flagged by the group
+                    uint32_t un = 0u;
+#pragma unroll
+                    for (int g = 0; g < QG; g++) {
+                        tmask[g] = 0u;
+                        if (!((gm1 >> g) & 1u)) continue;         // (wave-uniform)
+                        if (TR) {                                 // (stored row n of the tile = chunk 2 (n & 15) + (n >> 4): level-2 tile k is rows k and k + 16)
+                            const uint32_t og = s2_or16(__builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, bq1[g]), __builtin_bit_cast(f16x8, Ar[u]), zero, 0, 0, 0));
+                            if (stats) st_l1++;
+                            const unsigned long long m = __builtin_amdgcn_ballot_w64((int)og < 0);
+                            const uint32_t cm = (uint32_t)m | (uint32_t)(m >> 32);
+                            tmask[g] = (cm | (cm >> 16)) & 0xFFFFu;
+                        }
+                        else {
+                            const f32x16 acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, Ar[u]), __builtin_bit_cast(f16x8, bq1[g]), zero, 0, 0, 0);
+                            if (stats) st_l1++;
+                            if (!__builtin_amdgcn_ballot_w64((int)s2_or16(acc) < 0)) continue;
+#pragma unroll
+                            for (int i = 0; i < 8; i++) {         // (accumulators i and i + 8 of lane-half h: rows k and k + 16, k = 8 (i >> 2) + 4 h + (i & 3))
+                                const unsigned long long m = __builtin_amdgcn_ballot_w64((int)(__float_as_uint(acc[i]) | __float_as_uint(acc[i + 8])) < 0);
+                                tmask[g] |= ((uint32_t)m != 0u ? 1u : 0u) << (8 * (i >> 2) + (i & 3));
+                                tmask[g] |= ((uint32_t)(m >> 32) != 0u ? 1u : 0u) << (8 * (i >> 2) + 4 + (i & 3));
+                            }
+                        }
+                        un |= tmask[g];
+                    }
+                    if (stats) st_l2flag += (unsigned long long)__popc(un);
+                    while (un) {                                  // wave-uniform (at most 8 x 16 = 128 tiles per super-tile: the list of 512 holds them)
+                        const uint32_t k2 = (uint32_t)__builtin_ctz(un);
+                        un &= un - 1u;
+                        uint32_t gm = 0u;
+#pragma unroll
+                        for (int g = 0; g < QG; g++) gm |= ((tmask[g] >> k2) & 1u) << g;
+                        const uint32_t T2 = T1 * 16u + k2;
+                        if ((size_t)T2 * 32 < n_rec) { if (lane == 0) L.tiles[n_tiles] = T2 | (gm << 28); n_tiles++; }      // (tiles of the index's padding hold nothing)
+                    }
+                }
+                k += run;
+                PCR_S2_TICK(pt_l1)
+                if (n_tiles) level2(L, n_tiles);
+                PCR_S2_TICK(pt_l2)
+            }
+        }
+        flush_from(1u);
         PCR_S2_TICK(pt_l2)
     }
 #pragma unroll

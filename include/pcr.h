@@ -142,6 +142,13 @@ int pcr_icp_last_chain(const pcr_ctx* ctx);
  * must be ONE slice: it moves its queries in place).  Returns 1 or 0. */
 int pcr_icp_move_route(uint64_t n_src, uint64_t n_tgt, int nranks, int64_t move_in_search, int64_t fused_sums, int64_t fused_sums_min,
                        int64_t s3_transposed, int64_t sphere_qg, int64_t sphere_l0_per_slice, int64_t sphere_blocks);
+/* Host logic, no GPU: what the default three-level sphere kernel visits in ONE level-0 super-tile S0 (131 072 records) given its flag masks, in its
+ * order.  rows[t] bit j: level 0 flagged level-1 tile T1 = (S0 * 8 + t) * 32 + j (512 records); tiles[T1 - S0 * 256] bit k: level 1 flagged level-2
+ * tile T1 * 16 + k (32 records).  Tiles at or behind n_rec records (the padded size of the index) are not visited.  The visits are written as pairs
+ * (kind, value): 0 = a run starts, value = the level-1 super-tile (eight level-1 tiles); 1 = a level-1 tile of the run; 2 = a batch of value (1 ... 4)
+ * level-2 tiles starts; 3 = a level-2 tile of the batch.  *n_out = the number of pairs; PCR_ERR_ARG (with *n_out set) when out holds fewer than
+ * 2 * *n_out words (cap counts words). */
+int pcr_s3_walk_visits(uint32_t S0, const uint32_t rows[8], const uint16_t tiles[256], uint32_t n_rec, uint32_t* out, size_t cap, size_t* n_out);
 
 /* ---- A10: plane-inlier count, Homework4/ground_detection_ransac.py:138-139,152-153 -------------------
  * dist_i = |((x a + y b) + z c) + d| in f64; counts[h] = #{i : dist_i < thr} for n_planes hypotheses in

@@ -9,16 +9,17 @@ import collections, re, sys
 
 def kernel_body(lines, key):
     start = next(i for i, l in enumerate(lines) if re.match(r"^_Z\w*:", l) and key in l)
-    end = next(i for i in range(start, len(lines)) if lines[i].lstrip().startswith("s_endpgm"))
+    # to the end of the FUNCTION (.Lfunc_end<n>: / .size), not to the first s_endpgm: a kernel whose surplus waves leave early has one near its top
+    end = next(i for i in range(start, len(lines)) if re.match(r"^\.Lfunc_end\d+:", lines[i]) or lines[i].lstrip().startswith(".size"))
     meta = {}
-    for l in lines[end:]:
+    for l in lines[start:]:                      # (the kernel's descriptor block stands in front of .Lfunc_end, behind the last instruction)
         m = re.match(r"\s*\.(vgpr_count|sgpr_count|private_segment_fixed_size|group_segment_fixed_size|vgpr_spill_count):?\s+(\w+)", l) or \
             re.match(r"\s*\.amdhsa_(next_free_vgpr|next_free_sgpr|private_segment_fixed_size|group_segment_fixed_size)\s+(\w+)", l)
         if m and m.group(1) not in meta:
             meta[m.group(1)] = m.group(2)
         if l.lstrip().startswith(".end_amdhsa_kernel"):
             break
-    return lines[start + 1:end + 1], meta
+    return lines[start + 1:end], meta
 
 
 def unit(op):
