@@ -413,6 +413,7 @@ int radius_grid(pcr_ctx* ctx, const pcr_cloud* db, const pcr_cloud* q, double r,
 #define PCR_EMIT(CAPV, c)                                                                                                                     \
     if (!lists[c].empty()) {                                                                                                                  \
         const size_t lds = ((size_t)words + CAPV + 32) * 4;                                                                                    \
+        ProfScope pc(ctx, "radius_emit_class", 3);       /* prof 3 only: one scope per launch, so that a test can count the classes */        \
         hipFuncSetAttribute((const void*)radius_emit_kernel<CAPV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                      \
         hipLaunchKernelGGL((radius_emit_kernel<CAPV>), dim3((unsigned)lists[c].size()), dim3(RE_BLOCK), lds, ctx->stream, g->records, g->cell_start, g->p, \
                            q->x(), q->y(), q->z(), (const uint32_t*)lbuf.p + loff[c], (uint32_t)lists[c].size(), r2max, win, (const uint32_t*)rows.p,   \

@@ -877,7 +877,8 @@ int pcr_ctx_mfma_check(pcr_ctx* ctx, int run_now, pcr_mfma_check* out);
  *              icp_fused_sums [on] 2 = off (exhaustive loops: the sums in the solve + move launch, one grid barrier), icp_fused_sums_min [60 000 points],
  *              icp_fused_sums_max_blocks [CUs of the device], icp_fused_sums_threads [512] 256, icp_fused_sums_grid [off] 1 = grid loops too ·
  *              kabsch_bfly [on], kabsch_records [on], kabsch_one_pair_blocks [128], kabsch_max_blocks [1 024]
- *  other       plane_group [20: hypotheses per workgroup row of the plane count] · iss_lanes [32] · fpfh_lanes [16] · harris_lanes [16] · radius_fused [on] 2 = off · grid_stats 1 = the next 1-NN launch fills pcr_nn1_stats · prof 0 / 1 / 2 */
+ *  other       plane_group [20: hypotheses per workgroup row of the plane count] · iss_lanes [32] · fpfh_lanes [16] · harris_lanes [16] · radius_fused [on] 2 = off · grid_stats 1 = the next 1-NN launch fills pcr_nn1_stats · prof 0 / 1 / 2 / 3 (3 = 2 plus one
+ *              radius_emit_class scope per length-class launch inside radius_emit) */
 int pcr_tune_set(pcr_ctx* ctx, const char* key, int64_t value);
 
 #ifdef __cplusplus
