@@ -69,6 +69,21 @@ class SpectralInfo(C.Structure):
                 "residual": self.residual, "eigenvalues": np.array(self.eigenvalues[:n]), "eigenvalues_im": np.array(self.eigenvalues_im[:n])}
 
 
+class Pn2SaDesc(C.Structure):
+    _fields_ = [("npoint", C.c_uint32), ("nsample", C.c_uint32), ("radius", C.c_double), ("group_all", C.c_uint32), ("n_mlp", C.c_uint32),
+                ("widths", C.c_uint32 * 4)]
+
+
+class Pn2Desc(C.Structure):
+    _fields_ = [("D0", C.c_uint32), ("n_sa", C.c_uint32), ("sa", Pn2SaDesc * 4), ("n_fc", C.c_uint32), ("fc_widths", C.c_uint32 * 4),
+                ("bn_eps", C.c_double)]
+
+
+class Pn2Info(C.Structure):
+    _fields_ = [("n_weights", C.c_uint64), ("macs_per_object", C.c_uint64), ("n_sampling", C.c_uint32), ("n_class", C.c_uint32),
+                ("c_last", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_int)
 
 # every symbol include/pcr.h declares (checked by tests/test_abi.py against the header text)
@@ -85,6 +100,7 @@ ABI_SYMBOLS = [
     "pcr_db64_radius_rows", "pcr_rows_destroy", "pcr_rows_info", "pcr_rows_row_ptr", "pcr_rows_fetch", "pcr_rows_reduce", "pcr_rows_moments",
     "pcr_dbscan_f32", "pcr_statistical_outlier_f32", "pcr_fpfh33_f32", "pcr_harris3d_f32", "pcr_voxel_grid_normals_f32", "pcr_normal_space_sample_f32",
     "pcr_fps_f32", "pcr_ball_query_f32", "pcr_group_points_f32", "pcr_objects_from_labels_f32",
+    "pcr_pn2_model_create", "pcr_pn2_model_destroy", "pcr_pn2_model_info", "pcr_sa_mlp_max_f32", "pcr_pn2_forward_f32",
     "pcr_mat64_create", "pcr_mat64_destroy", "pcr_mat64_info", "pcr_kmeans_step_f64", "pcr_kmeans_fit_f64", "pcr_kmeans_predict_f64", "pcr_kmeanspp_init_f64",
     "pcr_gmm_em_step_f64", "pcr_gmm_fit_f64", "pcr_gmm_predict_f64",
     "pcr_mat64_knn_f64", "pcr_spectral_graph_f64", "pcr_spgraph_info", "pcr_spgraph_read", "pcr_spgraph_destroy", "pcr_eig_small_f64",
@@ -194,6 +210,11 @@ def lib():
     L.pcr_group_points_f32.argtypes = [vp, vp, vp, vp, vp, sz, vp, sz, vp, sz, vp, vp]
     L.pcr_objects_from_labels_f32.argtypes = [vp, vp, vp, sz, sz, C.c_double, C.c_double, vp, C.c_uint64, vp, vp, vp, vp, vp, vp, vp, C.POINTER(sz)]
     ip = C.POINTER(C.c_int)
+    L.pcr_pn2_model_create.argtypes = [vp, C.POINTER(Pn2Desc), vp, sz, C.POINTER(vp)]
+    L.pcr_pn2_model_destroy.argtypes = [vp, vp]
+    L.pcr_pn2_model_info.argtypes = [vp, sz, C.POINTER(Pn2Info), C.POINTER(Pn2Desc)]
+    L.pcr_sa_mlp_max_f32.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp, sz, vp, vp, vp]
+    L.pcr_pn2_forward_f32.argtypes = [vp, vp, vp, sz, sz, vp, C.c_uint64, vp, vp, vp, vp]
     L.pcr_mat64_create.argtypes = [vp, vp, sz, C.c_int, C.POINTER(vp)]
     L.pcr_mat64_destroy.argtypes = [vp, vp]
     L.pcr_mat64_info.argtypes = [vp, C.POINTER(sz), ip, ip]
@@ -416,6 +437,66 @@ class Db64:
         if self.h and self.ctx.h:
             lib().pcr_db64_destroy(self.ctx.h, self.h)
         self.h = None
+
+
+def pn2_desc(sa, fc, D0: int = 0, bn_eps: float = 1e-5) -> Pn2Desc:
+    """sa: a list of dicts {npoint, radius, nsample, mlp: [widths]} or {group_all: True, mlp: [...]}; fc: the head's output widths."""
+    d = Pn2Desc()
+    if len(sa) > 4 or len(fc) > 4:
+        raise PcrError("at most 4 SA layers and 4 FC layers")
+    d.D0, d.n_sa, d.n_fc, d.bn_eps = int(D0), len(sa), len(fc), float(bn_eps)
+    for l, s in enumerate(sa):
+        mlp = list(s["mlp"])
+        if len(mlp) > 4:
+            raise PcrError("at most 4 widths per SA layer")
+        e = d.sa[l]
+        e.group_all = 1 if s.get("group_all") else 0
+        if not e.group_all:
+            e.npoint, e.radius, e.nsample = int(s["npoint"]), float(s["radius"]), int(s["nsample"])
+        e.n_mlp = len(mlp)
+        for k, w in enumerate(mlp):
+            e.widths[k] = int(w)
+    for k, w in enumerate(fc):
+        d.fc_widths[k] = int(w)
+    return d
+
+
+class Pn2Model:
+    """A PointNet++ (SSG) classifier resident in HBM (pcr_pn2_model): BN folded into the weights at upload; the contract is in include/pcr.h."""
+
+    def __init__(self, ctx: "Context", desc: Pn2Desc, weights):
+        w = np.ascontiguousarray(weights, np.float32).reshape(-1)
+        h = C.c_void_p()
+        ctx._ck(lib().pcr_pn2_model_create(ctx.h, C.byref(desc), w.ctypes.data if w.size else None, w.size, C.byref(h)))
+        self.ctx, self.h, self.desc = ctx, h, desc
+        ctx._handles.add(self)
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:   # noqa: BLE001
+            pass
+
+    def free(self):
+        if self.h and self.ctx.h:
+            lib().pcr_pn2_model_destroy(self.ctx.h, self.h)
+        self.h = None
+
+    def info(self, npts: int = 0) -> dict:
+        i = Pn2Info()
+        self.ctx._ck(lib().pcr_pn2_model_info(self.h, int(npts), C.byref(i), None))
+        return {"n_weights": int(i.n_weights), "macs_per_object": int(i.macs_per_object), "n_sampling": int(i.n_sampling), "n_class": int(i.n_class),
+                "c_last": int(i.c_last)}
+
+    def sampling_npoints(self):
+        return [int(self.desc.sa[l].npoint) for l in range(self.desc.n_sa) if not self.desc.sa[l].group_all]
+
+    def sa_out_width(self, layer: int) -> int:
+        e = self.desc.sa[layer]
+        return int(e.widths[e.n_mlp - 1])
+
+    def sa_in_features(self, layer: int) -> int:
+        return int(self.desc.D0) if layer == 0 else self.sa_out_width(layer - 1)
 
 
 class Mat64:
@@ -1138,6 +1219,78 @@ class Context:
         self._ck(lib().pcr_group_points_f32(self.h, cloud.h, sp.ctypes.data, centres.h, cp.ctypes.data, sp.size - 1, None if not D else feat.ctypes.data, D,
                                             ix.ctypes.data, int(nsample), new_xyz.ctypes.data, new_points.ctypes.data))
         return new_xyz[:rows], new_points[:rows]
+
+    def pn2_model(self, desc, weights) -> Pn2Model:
+        """desc: a Pn2Desc (pn2_desc(...)); weights: the flat f32 array in the order include/pcr.h states (pointnet.flat_weights builds it
+        from a state dict).  BN is folded at upload."""
+        return Pn2Model(self, desc, weights)
+
+    def sa_mlp_max(self, model: Pn2Model, layer: int, cloud: Cloud, seg_ptr, centres=None, centre_seg_ptr=None, idx=None, features=None):
+        """The fused set-abstraction kernel alone: gather + centre + MLP chain + max per group -> f32 [rows, C_out]; the contract of
+        pcr_sa_mlp_max_f32.  For a group_all layer centres / centre_seg_ptr / idx stay None and rows = the number of segments."""
+        sp = self._seg(seg_ptr)
+        n_seg = sp.size - 1
+        layer = int(layer)
+        if not 0 <= layer < model.desc.n_sa:                              # no such layer: the library's own status (PCR_ERR_ARG), set before it reads anything else
+            self._ck(lib().pcr_sa_mlp_max_f32(self.h, model.h, layer, cloud.h, sp.ctypes.data, None, None, n_seg, None, None, None))
+            raise PcrError("bad argument: no such SA layer")
+        ga = bool(model.desc.sa[layer].group_all)
+        cp, ix = None, None
+        if ga:
+            rows = n_seg
+        else:
+            if centres is None or centre_seg_ptr is None or idx is None:
+                raise PcrError("a sampling layer needs centres, centre_seg_ptr and idx")
+            cp = self._seg(centre_seg_ptr)
+            if sp.size != cp.size:
+                raise PcrError("the two seg_ptr arrays describe the same segments")
+            rows = int(cp[-1]) - int(cp[0])
+            ix = np.ascontiguousarray(idx, np.uint32).reshape(-1)
+            if ix.size != rows * int(model.desc.sa[layer].nsample):
+                raise PcrError("one index row of nsample entries per centre")
+        feat = None
+        D = model.sa_in_features(layer)
+        if D:
+            if features is None:
+                raise PcrError("the layer takes features")
+            feat = np.ascontiguousarray(features, np.float32).reshape(-1, D)
+            if feat.shape[0] != len(cloud):
+                raise PcrError("one feature row per point of the cloud")
+        cout = model.sa_out_width(layer)
+        out = np.zeros((max(rows, 1), cout), np.float32)
+        self._ck(lib().pcr_sa_mlp_max_f32(self.h, model.h, int(layer), cloud.h, sp.ctypes.data, None if ga else centres.h, None if ga else cp.ctypes.data,
+                                          n_seg, None if feat is None else feat.ctypes.data, None if ga or not ix.size else ix.ctypes.data, out.ctypes.data))
+        return out[:rows]
+
+    def pn2_forward(self, model: Pn2Model, objects, starts=None, seed: int = 0, return_all: bool = False):
+        """The whole forward pass: objects f32 [n_obj, npts, 3 + D0] -> log-probabilities f32 [n_obj, n_class]; with return_all a dict
+        (logp, pred int32 [n_obj], global_feat f32 [n_obj, C_last], fps_idx: one u32 [n_obj, npoint] per sampling layer); the contract of
+        pcr_pn2_forward_f32.  starts: [n_sampling_layers, n_obj] first picks, None = drawn from the seed."""
+        obj = np.ascontiguousarray(objects, np.float32)
+        if obj.ndim != 3 or obj.shape[2] != 3 + int(model.desc.D0):
+            raise PcrError("objects: [n_obj, npts, 3 + D0]")
+        n_obj, npts = obj.shape[0], obj.shape[1]
+        inf = model.info(npts)
+        nps = model.sampling_npoints()
+        st = None
+        if starts is not None:
+            st = np.ascontiguousarray(starts, np.uint32).reshape(-1)
+            if st.size != len(nps) * n_obj:
+                raise PcrError("starts: one first pick per sampling layer and object")
+        cap = max(n_obj, 1)
+        logp = np.zeros((cap, inf["n_class"]), np.float32)
+        pred = np.zeros(cap, np.int32)
+        gf = np.zeros((cap, inf["c_last"]), np.float32)
+        fps = np.zeros(max(cap * sum(nps), 1), np.uint32)
+        self._ck(lib().pcr_pn2_forward_f32(self.h, model.h, obj.ctypes.data if obj.size else None, n_obj, npts, None if st is None or not st.size else st.ctypes.data,
+                                           int(seed) & 0xFFFFFFFFFFFFFFFF, logp.ctypes.data, pred.ctypes.data, gf.ctypes.data, fps.ctypes.data))
+        if not return_all:
+            return logp[:n_obj]
+        blocks, off = [], 0
+        for npnt in nps:
+            blocks.append(fps[off:off + n_obj * npnt].reshape(n_obj, npnt))
+            off += n_obj * npnt
+        return {"logp": logp[:n_obj], "pred": pred[:n_obj], "global_feat": gf[:n_obj], "fps_idx": blocks}
 
     def objects_from_labels(self, cloud: Cloud, labels, n_clusters: int, npoints: int = 256, ground_z: float = 0.0, z_min_above_ground: float = 0.5,
                             z_extent=(1.0, 2.3), seed: int = 0, starts=None):

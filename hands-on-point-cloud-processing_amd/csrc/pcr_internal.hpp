@@ -353,6 +353,30 @@ int launch_radius_count(pcr_ctx* ctx, const double* db_soa, size_t n, size_t n_c
 int launch_radius_fill(pcr_ctx* ctx, const double* db_soa, size_t n, size_t n_cap, const double* q_soa,
                        size_t m, double r, const long long* row_ptr_dev, int32_t* idx_dev, double* dist_dev, uint32_t slices);
 
+// ---- PointNet++ sampling on device buffers (pointnet.hip), for callers that chain stages without a host round trip (pointnet2.hip) --------
+// one FPS segment: points [base, base + n) of the coordinate arrays, first pick (segment-local), row of the output
+struct FpsJob {
+    uint32_t base, n, start, out_row;
+};
+// host arrays an asynchronous upload still reads: the caller keeps them until it has synchronised the stream
+struct HostKeep {
+    std::vector<std::shared_ptr<void>> held;
+};
+// the picks of every job into out_dev[job.out_row][npoint]; enqueues on ctx->stream and does NOT synchronise (the job tables live in `keep`).
+// Same kernels and the same rule as pcr_fps_f32.  Uses ctx->aux.
+int fps_device(pcr_ctx* ctx, const float* x, const float* y, const float* z, std::vector<FpsJob> jobs, uint32_t npoint, int mode, uint32_t* out_dev, HostKeep* keep);
+// pcr_ball_query_f32's kernel on device tables: seg_dev[n_seg + 1], centre_seg_dev[nq] (the segment of every centre), idx_dev[nq][nsample], cnt_dev[nq]
+int ball_query_device(pcr_ctx* ctx, const float* x, const float* y, const float* z, const float* qx, const float* qy, const float* qz, const uint32_t* seg_dev,
+                      const uint32_t* centre_seg_dev, size_t nq, double radius, size_t nsample, uint32_t* idx_dev, uint32_t* cnt_dev);
+// SplitMix64 keying of include/pcr.h: K(seed, a)
+inline unsigned long long splitmix_key(unsigned long long seed, unsigned long long a)
+{
+    unsigned long long zz = seed ^ (0x9E3779B97F4A7C15ull * (a + 1ull));
+    zz = (zz ^ (zz >> 30)) * 0xBF58476D1CE4E5B9ull;
+    zz = (zz ^ (zz >> 27)) * 0x94D049BB133111EBull;
+    return zz ^ (zz >> 31);
+}
+
 // ---- host numerics ------------------------------------------------------------------------------------
 void svd3(const double A[9], double U[9], double S[3], double V[9]);
 int kabsch_solve(const double sums[16], float R[9], float t[3]);

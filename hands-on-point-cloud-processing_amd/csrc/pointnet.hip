@@ -166,10 +166,6 @@ struct FpsArith<true> {
     __device__ __forceinline__ static double init(bool ok) { return ok ? 1e10 : -__builtin_inf(); }
 };
 
-struct FpsJob {
-    uint32_t base, n, start, out_row;      // points [base, base + n) of the arrays, first pick (segment-local), row of the output
-};
-
 // ---- small segments: the whole chain in one workgroup, points and running distances in registers -----------------------------------------
 template <bool F64, int T, int P>
 __global__ __launch_bounds__(T) void fps_small_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ z,
@@ -437,7 +433,9 @@ void fps_launch_small(pcr_ctx* ctx, const float* x, const float* y, const float*
 }
 
 // the picks of every job, out_dev[job.out_row][npoint] (device).  Uses ctx->aux; asynchronous on the stream.  regimes (host, optional): per job.
-int fps_run(pcr_ctx* ctx, const float* x, const float* y, const float* z, std::vector<FpsJob> jobs, uint32_t npoint, int mode, uint32_t* out_dev, uint8_t* regimes)
+// keep != nullptr: the job tables move into *keep and the call does not synchronise (fps_device)
+int fps_run(pcr_ctx* ctx, const float* x, const float* y, const float* z, std::vector<FpsJob> jobs, uint32_t npoint, int mode, uint32_t* out_dev, uint8_t* regimes,
+            HostKeep* keep = nullptr)
 {
     if (jobs.empty() || npoint == 0) return PCR_OK;
     const int at_least = (int)tune_get(ctx, "fps_regime", 0);
@@ -449,13 +447,16 @@ int fps_run(pcr_ctx* ctx, const float* x, const float* y, const float* z, std::v
     std::vector<size_t> perm(jobs.size());
     for (size_t j = 0; j < perm.size(); j++) perm[j] = j;
     std::stable_sort(perm.begin(), perm.end(), [&](size_t a, size_t b) { return reg[a] < reg[b]; });
-    std::vector<FpsJob> sorted(jobs.size());
+    auto sorted_h = std::make_shared<std::vector<FpsJob>>(jobs.size());
+    auto tab_h = std::make_shared<std::vector<FpsLargeSeg>>();
+    auto wg_tab_h = std::make_shared<std::vector<uint32_t>>();
+    std::vector<FpsJob>& sorted = *sorted_h;
+    std::vector<FpsLargeSeg>& tab = *tab_h;
+    std::vector<uint32_t>& wg_tab = *wg_tab_h;
     size_t first[7] = { 0, 0, 0, 0, 0, 0, 0 };          // first[r] = first job of regime r in `sorted`
     for (size_t k = 0; k < perm.size(); k++) { sorted[k] = jobs[perm[k]]; first[reg[perm[k]] + 1]++; }
     for (int r = 1; r < 7; r++) first[r] += first[r - 1];
     // the large segments' table
-    std::vector<FpsLargeSeg> tab;
-    std::vector<uint32_t> wg_tab;
     unsigned long long dist_total = 0;
     for (size_t k = first[5]; k < first[6]; k++) {
         const FpsJob& j = sorted[k];
@@ -488,7 +489,13 @@ int fps_run(pcr_ctx* ctx, const float* x, const float* y, const float* z, std::v
         PCR_HIP(ctx, hipMemcpyAsync(tab_dev, tab.data(), tab.size() * sizeof(FpsLargeSeg), hipMemcpyHostToDevice, ctx->stream));
         PCR_HIP(ctx, hipMemcpyAsync(wg_dev, wg_tab.data(), wg_tab.size() * 4, hipMemcpyHostToDevice, ctx->stream));
     }
-    PCR_HIP(ctx, hipStreamSynchronize(ctx->stream));      // the host vectors go out of scope with this call
+    if (keep) {
+        keep->held.push_back(sorted_h);
+        keep->held.push_back(tab_h);
+        keep->held.push_back(wg_tab_h);
+    } else {
+        PCR_HIP(ctx, hipStreamSynchronize(ctx->stream));      // the host vectors go out of scope with this call
+    }
     if (mode == 1) {
         fps_launch_small<true, 64, 4>(ctx, x, y, z, jobs_dev + first[1], first[2] - first[1], npoint, out_dev);
         fps_launch_small<true, 256, 4>(ctx, x, y, z, jobs_dev + first[2], first[3] - first[2], npoint, out_dev);
@@ -524,6 +531,12 @@ bool seg_ptr_ok(const uint32_t* seg_ptr, size_t n_seg, size_t limit)
 }
 
 }  // namespace
+
+int fps_device(pcr_ctx* ctx, const float* x, const float* y, const float* z, std::vector<FpsJob> jobs, uint32_t npoint, int mode, uint32_t* out_dev, HostKeep* keep)
+{
+    if (!keep) return fail(ctx, PCR_ERR_ARG, "fps_device: keep is NULL");
+    return fps_run(ctx, x, y, z, std::move(jobs), npoint, mode, out_dev, nullptr, keep);
+}
 
 }  // namespace pcr
 
@@ -576,6 +589,20 @@ std::vector<uint32_t> centre_segments(const uint32_t* centre_seg_ptr, size_t n_s
 
 }  // namespace
 
+int pcr::ball_query_device(pcr_ctx* ctx, const float* x, const float* y, const float* z, const float* qx, const float* qy, const float* qz, const uint32_t* seg_dev,
+                           const uint32_t* centre_seg_dev, size_t nq, double radius, size_t nsample, uint32_t* idx_dev, uint32_t* cnt_dev)
+{
+    if (nq == 0) return PCR_OK;
+    const float r2 = (float)(radius * radius);
+    {
+        ProfScope ps(ctx, "ball_query");
+        hipLaunchKernelGGL(ball_query_kernel, dim3((unsigned)((nq + PN_BLOCK / 64 - 1) / (PN_BLOCK / 64))), dim3(PN_BLOCK), 0, ctx->stream, x, y, z, qx, qy, qz, seg_dev,
+                           centre_seg_dev, (uint32_t)nq, r2, (uint32_t)nsample, idx_dev, cnt_dev);
+    }
+    PCR_HIP(ctx, hipGetLastError());
+    return PCR_OK;
+}
+
 extern "C" int pcr_ball_query_f32(pcr_ctx* ctx, const pcr_cloud* cloud, const uint32_t* seg_ptr, const pcr_cloud* centres, const uint32_t* centre_seg_ptr,
                                   size_t n_seg, double radius, size_t nsample, uint32_t* idx, uint32_t* counts)
 {
@@ -603,13 +630,9 @@ extern "C" int pcr_ball_query_f32(pcr_ctx* ctx, const pcr_cloud* cloud, const ui
     PCR_HIP(ctx, hipMemcpyAsync(seg_dev, seg_ptr, (n_seg + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
     PCR_HIP(ctx, hipMemcpyAsync(cs_dev, cs.data(), cs.size() * 4, hipMemcpyHostToDevice, ctx->stream));
     PCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const float r2 = (float)(radius * radius);
-    {
-        ProfScope ps(ctx, "ball_query");
-        hipLaunchKernelGGL(ball_query_kernel, dim3((unsigned)((nq + PN_BLOCK / 64 - 1) / (PN_BLOCK / 64))), dim3(PN_BLOCK), 0, ctx->stream, cloud->x(), cloud->y(),
-                           cloud->z(), centres->x() + q0, centres->y() + q0, centres->z() + q0, seg_dev, cs_dev + q0, (uint32_t)nq, r2, (uint32_t)nsample, idx_dev, cnt_dev);
-    }
-    PCR_HIP(ctx, hipGetLastError());
+    rc = ball_query_device(ctx, cloud->x(), cloud->y(), cloud->z(), centres->x() + q0, centres->y() + q0, centres->z() + q0, seg_dev, cs_dev + q0, nq, radius, nsample,
+                           idx_dev, cnt_dev);
+    if (rc) return rc;
     PCR_HIP(ctx, hipMemcpyAsync(idx, idx_dev, nq * nsample * 4, hipMemcpyDeviceToHost, ctx->stream));
     if (counts) PCR_HIP(ctx, hipMemcpyAsync(counts, cnt_dev, nq * 4, hipMemcpyDeviceToHost, ctx->stream));
     PCR_HIP(ctx, hipStreamSynchronize(ctx->stream));

@@ -1,0 +1,722 @@
+// pointnet2.hip — HomeworkFinal's PointNet++ (SSG) classifier in eval mode (models/pointnet2_cls_ssg.py, models/pointnet_util.py:159-215).
+// The contract is written out above pcr_pn2_model_create / pcr_sa_mlp_max_f32 / pcr_pn2_forward_f32 in include/pcr.h.
+//
+//   pn2_chain_kernel   one workgroup (4 waves) per tile of R = 16 / 32 / 64 ROWS (a row = one sample of one group): gathers the rows' input
+//                      channels into LDS, runs the up to four layers relu(W'x + b') with the activations ping-ponging between two LDS
+//                      buffers, and reduces the last layer's outputs by group with an atomic max on the bits of the (non-negative) floats.
+//                      Products run on v_mfma_f32_16x16x4_f32: A = 16 rows x 4 channels of the activations (one ds_read_b128 per four K
+//                      steps), B = 4 channels x 16 outputs of W' (one global_load_dwordx4 per four K steps: the model stores W' in that
+//                      operand order), C starts as the bias.  A wave owns output tiles t = wave, wave + 4, ... and all R rows of each, so
+//                      every output is ONE chain over ascending k whatever R is, and the max is order-free: the result is the same bits
+//                      under every geometry.  The same kernel serves the head (one row per object, no max, no ReLU on the last layer).
+//   LDS               a row of a buffer holds Kpad + 4 floats (the + 4 spreads the 16 rows of an operand read over the banks); inside
+//                      every block of 16 channels the position 4 q + s holds channel 4 s + q, so that the float4 a lane reads is its
+//                      operand of four consecutive K steps.  buffer 0 is as wide as the widest input of an even layer, buffer 1 of an odd one.
+//   forward           upload -> per sampling layer { FPS, centres, ball query, memset, chain } -> group_all chain -> head chain -> log_softmax.
+#include "pcr_internal.hpp"
+
+#include <algorithm>
+#include <cfloat>
+#include <cmath>
+
+#pragma clang fp contract(off)
+
+namespace pcr {
+
+namespace {
+
+constexpr int PN2_BLOCK = 256;
+constexpr int PN2_WAVES = PN2_BLOCK / 64;
+constexpr uint32_t PN2_MAX_WIDTH = 1024;
+constexpr size_t PN2_LDS_LIMIT = 160 * 1024;
+constexpr unsigned long long PN2_MAX_ROWS = 0x7FFFFFF0ull;
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+struct LayerDev {
+    const float* w;      // operand order: [Npad / 16][Kpad / 16][64 lanes][4]: W'[16 t + (lane & 15)][16 kb + 4 s + (lane >> 4)]
+    const float* b;      // Npad floats (0 beyond N)
+    uint32_t K, Kpad, N, Npad;
+};
+
+enum { PN2_GROUPED = 0, PN2_GROUP_ALL = 1, PN2_HEAD = 2 };
+
+struct ChainArgs {
+    const float *x, *y, *z;           // the cloud (GROUPED, GROUP_ALL)
+    const float *qx, *qy, *qz;        // the centres (GROUPED)
+    const uint32_t* seg_ptr;          // n_seg + 1 offsets into the cloud (GROUPED, GROUP_ALL)
+    const uint32_t* centre_seg;       // the segment of every centre (GROUPED)
+    const uint32_t* idx;              // rows segment-local members (GROUPED)
+    const float* feat;                // D floats per point of the cloud; HEAD: per row
+    float* out;                       // groups x N of the last layer
+    uint32_t rows;                    // GROUPED: centres x nsample, GROUP_ALL: points of the segments, HEAD: objects
+    uint32_t D, nsample, n_seg, mode, n_layers, s0, s1, p0;
+    LayerDev L[PCR_PN2_MAX_MLP];
+};
+
+__device__ __forceinline__ float pn2_relu(float v) { return v > 0.0f ? v : 0.0f; }
+
+__device__ __forceinline__ void pn2_atomic_max(float* out, int grp, uint32_t N, uint32_t c, float m)
+{
+    if (m > 0.0f) atomicMax((unsigned int*)(out + (size_t)grp * N + c), __float_as_uint(m));      // out starts at +0; m >= +0: the bits order as the values
+}
+
+template <int RT>
+__global__ __launch_bounds__(PN2_BLOCK) void pn2_chain_kernel(const ChainArgs a)
+{
+    constexpr int R = RT * 16;
+    extern __shared__ __align__(16) float pn2_lds[];
+    float* buf0 = pn2_lds;
+    float* buf1 = buf0 + (size_t)R * a.s0;
+    uint32_t* rowP = (uint32_t*)(buf1 + (size_t)R * a.s1);      // the point (HEAD: the row) a tile row reads
+    int* rowG = (int*)(rowP + R);                               // its group = row of the output, -1: no such row
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    // ---- the rows of this tile
+    if (tid < R) {
+        const unsigned long long g = (unsigned long long)blockIdx.x * R + (unsigned)tid;
+        int grp = -1;
+        uint32_t p = 0;
+        if (g < a.rows) {
+            if (a.mode == PN2_HEAD) {
+                p = (uint32_t)g;
+                grp = (int)g;
+            }
+            if (a.mode == PN2_GROUP_ALL) {
+                p = a.p0 + (uint32_t)g;
+                uint32_t lo = 0, hi = a.n_seg;                  // the last segment that starts at or before p (an empty one never holds p)
+                while (hi - lo > 1) {
+                    const uint32_t mid = (lo + hi) >> 1;
+                    if (a.seg_ptr[mid] <= p) lo = mid; else hi = mid;
+                }
+                grp = (int)lo;
+            }
+            if (a.mode == PN2_GROUPED) {
+                const uint32_t q = (uint32_t)(g / a.nsample);
+                const uint32_t s = a.centre_seg[q], base = a.seg_ptr[s], n = a.seg_ptr[s + 1] - base;
+                if (n) {
+                    uint32_t i = a.idx[g];
+                    if (i >= n) i = n - 1;                      // (never: the host checks the caller's rows, a centre of the forward pass is its own hit)
+                    p = base + i;
+                    grp = (int)q;
+                }
+            }
+        }
+        rowP[tid] = p;
+        rowG[tid] = grp;
+    }
+    __syncthreads();
+    // ---- layer 0's input: (xyz - centre | features | zeros up to Kpad), a row without a group is all zeros
+    {
+        const uint32_t Kp = a.L[0].Kpad;
+        for (uint32_t e = (uint32_t)tid; e < (uint32_t)R * Kp; e += PN2_BLOCK) {
+            const uint32_t r = e / Kp, pos = e - r * Kp, w = pos & 15u;
+            const uint32_t ch = (pos & ~15u) + 4u * (w & 3u) + (w >> 2);
+            const int grp = rowG[r];
+            const uint32_t p = rowP[r];
+            float v = 0.0f;
+            if (grp >= 0) {
+                if (a.mode == PN2_HEAD) {
+                    if (ch < a.D) v = a.feat[(size_t)p * a.D + ch];
+                } else if (ch < 3u) {
+                    const float* pc = ch == 0 ? a.x : (ch == 1 ? a.y : a.z);
+                    v = pc[p];
+                    if (a.mode == PN2_GROUPED) {
+                        const float* cc = ch == 0 ? a.qx : (ch == 1 ? a.qy : a.qz);
+                        v = v - cc[grp];
+                    }
+                } else if (ch < 3u + a.D) {
+                    v = a.feat[(size_t)p * a.D + (ch - 3u)];
+                }
+            }
+            buf0[(size_t)r * a.s0 + pos] = v;
+        }
+    }
+    __syncthreads();
+    // ---- the layers
+    const int j = lane & 15, h = lane >> 4;
+    for (uint32_t l = 0; l < a.n_layers; l++) {
+        const LayerDev L = a.L[l];
+        const float* in = (l & 1u) ? buf1 : buf0;
+        float* outb = (l & 1u) ? buf0 : buf1;
+        const uint32_t sin = (l & 1u) ? a.s1 : a.s0, sout = (l & 1u) ? a.s0 : a.s1;
+        const bool last = l + 1 == a.n_layers;
+        const uint32_t KB = L.Kpad >> 4, NT = L.Npad >> 4;
+        for (uint32_t t = (uint32_t)wave; t < NT; t += PN2_WAVES) {      // wave-uniform
+            const float bias = L.b[t * 16 + j];
+            f32x4 acc[RT];
+#pragma unroll
+            for (int rt = 0; rt < RT; rt++) acc[rt] = f32x4{ bias, bias, bias, bias };
+            const f32x4* wp = (const f32x4*)L.w + (size_t)t * KB * 64 + lane;
+            const float* ap = in + (size_t)j * sin + 4 * h;
+            f32x4 bnext = wp[0];
+            for (uint32_t kb = 0; kb < KB; kb++) {
+                const f32x4 b = bnext;
+                if (kb + 1 < KB) bnext = wp[(size_t)(kb + 1) * 64];      // the next block's operand is in flight during this block's products
+                f32x4 av[RT];
+#pragma unroll
+                for (int rt = 0; rt < RT; rt++) av[rt] = *(const f32x4*)(ap + (size_t)rt * 16 * sin + kb * 16);
+#pragma unroll
+                for (int rt = 0; rt < RT; rt++) acc[rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[rt].x, b.x, acc[rt], 0, 0, 0);
+#pragma unroll
+                for (int rt = 0; rt < RT; rt++) acc[rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[rt].y, b.y, acc[rt], 0, 0, 0);
+#pragma unroll
+                for (int rt = 0; rt < RT; rt++) acc[rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[rt].z, b.z, acc[rt], 0, 0, 0);
+#pragma unroll
+                for (int rt = 0; rt < RT; rt++) acc[rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[rt].w, b.w, acc[rt], 0, 0, 0);
+            }
+            // lane (j, h) holds output channel 16 t + j of the rows 16 rt + 4 h + reg
+            if (!last) {
+                const uint32_t pos = t * 16 + 4u * (uint32_t)(j & 3) + (uint32_t)(j >> 2);
+#pragma unroll
+                for (int rt = 0; rt < RT; rt++)
+#pragma unroll
+                    for (int reg = 0; reg < 4; reg++) outb[(size_t)(rt * 16 + 4 * h + reg) * sout + pos] = pn2_relu(acc[rt][reg]);
+            } else {
+                const uint32_t c = t * 16 + (uint32_t)j;
+                const bool cvalid = c < L.N;
+                if (a.mode == PN2_HEAD) {
+#pragma unroll
+                    for (int rt = 0; rt < RT; rt++)
+#pragma unroll
+                        for (int reg = 0; reg < 4; reg++) {
+                            const int grp = rowG[rt * 16 + 4 * h + reg];
+                            if (grp >= 0 && cvalid) a.out[(size_t)grp * L.N + c] = acc[rt][reg];
+                        }
+                } else {
+#pragma unroll
+                    for (int rt = 0; rt < RT; rt++) {
+                        const int r0 = rt * 16;
+                        const int g0 = rowG[r0], g7 = rowG[r0 + 7], g8 = rowG[r0 + 8], g15 = rowG[r0 + 15];      // groups ascend along the rows, -1 only at the tail
+                        const float v0 = pn2_relu(acc[rt][0]), v1 = pn2_relu(acc[rt][1]), v2 = pn2_relu(acc[rt][2]), v3 = pn2_relu(acc[rt][3]);
+                        if (g0 == g15 || (g0 == g7 && g8 == g15)) {        // wave-uniform: the 16 rows are one group, or two halves of one group each
+                            float m = fmaxf(fmaxf(v0, v1), fmaxf(v2, v3));
+                            m = fmaxf(m, __shfl_xor(m, 16, 64));
+                            if (g0 == g15) {
+                                m = fmaxf(m, __shfl_xor(m, 32, 64));
+                                if (h == 0 && g0 >= 0 && cvalid) pn2_atomic_max(a.out, g0, L.N, c, m);
+                            } else {
+                                const int grp = h < 2 ? g0 : g8;
+                                if ((h & 1) == 0 && grp >= 0 && cvalid) pn2_atomic_max(a.out, grp, L.N, c, m);
+                            }
+                        } else {                                            // runs of equal groups inside the lane's four rows
+                            const float v[4] = { v0, v1, v2, v3 };
+                            int cur = rowG[r0 + 4 * h];
+                            float m = v[0];
+#pragma unroll
+                            for (int reg = 1; reg < 4; reg++) {
+                                const int grp = rowG[r0 + 4 * h + reg];
+                                if (grp != cur) {
+                                    if (cur >= 0 && cvalid) pn2_atomic_max(a.out, cur, L.N, c, m);
+                                    cur = grp;
+                                    m = v[reg];
+                                } else {
+                                    m = fmaxf(m, v[reg]);
+                                }
+                            }
+                            if (cur >= 0 && cvalid) pn2_atomic_max(a.out, cur, L.N, c, m);
+                        }
+                    }
+                }
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// centres of a sampling layer: the picked points of every object (objects of n points, npoint picks each)
+__global__ __launch_bounds__(PN2_BLOCK) void pn2_centres_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ z,
+                                                                const uint32_t* __restrict__ fps, uint32_t n, uint32_t npoint, uint32_t total,
+                                                                float* __restrict__ cx, float* __restrict__ cy, float* __restrict__ cz)
+{
+    const uint32_t q = blockIdx.x * PN2_BLOCK + threadIdx.x;
+    if (q >= total) return;
+    uint32_t i = fps[q];
+    if (i >= n) i = n - 1;      // (never: a pick is a member)
+    const size_t p = (size_t)(q / npoint) * n + i;
+    cx[q] = x[p]; cy[q] = y[p]; cz[q] = z[p];
+}
+
+// log_softmax of a row of logits and its first maximum: one lane per object, ascending class order
+__global__ __launch_bounds__(PN2_BLOCK) void pn2_logsoftmax_kernel(const float* __restrict__ logits, uint32_t n_obj, uint32_t n_class, float* __restrict__ logp,
+                                                                   int32_t* __restrict__ pred)
+{
+    const uint32_t o = blockIdx.x * PN2_BLOCK + threadIdx.x;
+    if (o >= n_obj) return;
+    const float* r = logits + (size_t)o * n_class;
+    float m = r[0];
+    int32_t best = 0;
+    for (uint32_t c = 1; c < n_class; c++)
+        if (r[c] > m) { m = r[c]; best = (int32_t)c; }
+    float s = 0.0f;
+    for (uint32_t c = 0; c < n_class; c++) s = s + expf(r[c] - m);
+    const float ls = logf(s);
+    for (uint32_t c = 0; c < n_class; c++) logp[(size_t)o * n_class + c] = (r[c] - m) - ls;
+    pred[o] = best;
+}
+
+inline uint32_t pad16(uint32_t v) { return (v + 15u) & ~15u; }
+
+// a chain of layers as the kernel takes it
+struct Chain {
+    uint32_t n = 0;
+    LayerDev L[PCR_PN2_MAX_MLP];
+    uint32_t s0 = 4, s1 = 4;
+    uint32_t n_out() const { return L[n - 1].N; }
+    size_t lds_bytes(int R) const { return (size_t)R * (s0 + s1) * 4 + (size_t)R * 8; }
+};
+
+// rows per tile: the tuned value if it fits, else the largest of 64 / 32 / 16 that does (16 always does: two rows of 1028 floats x 16 = 129 KB)
+int chain_rows(const pcr_ctx* ctx, const Chain& ch)
+{
+    const int64_t want = tune_get(ctx, "pn2_rows", 0);
+    const int cand[3] = { 64, 32, 16 };
+    for (int k = 0; k < 3; k++)
+        if ((want == 0 || cand[k] <= want) && ch.lds_bytes(cand[k]) <= PN2_LDS_LIMIT) return cand[k];
+    return 16;
+}
+
+template <int RT>
+int chain_launch_rt(pcr_ctx* ctx, const ChainArgs& a, size_t lds)
+{
+    PCR_HIP(ctx, hipFuncSetAttribute((const void*)pn2_chain_kernel<RT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const unsigned tiles = (unsigned)(((unsigned long long)a.rows + RT * 16 - 1) / (RT * 16));
+    hipLaunchKernelGGL((pn2_chain_kernel<RT>), dim3(tiles), dim3(PN2_BLOCK), lds, ctx->stream, a);
+    PCR_HIP(ctx, hipGetLastError());
+    return PCR_OK;
+}
+
+// a.out (n_groups x n_out) <- the chain over a.rows rows; enqueued on the stream
+int chain_launch(pcr_ctx* ctx, const Chain& ch, ChainArgs a, size_t n_groups, const char* prof)
+{
+    if (a.rows == 0 || n_groups == 0) return PCR_OK;
+    a.n_layers = ch.n;
+    a.s0 = ch.s0;
+    a.s1 = ch.s1;
+    for (uint32_t l = 0; l < ch.n; l++) a.L[l] = ch.L[l];
+    const int R = chain_rows(ctx, ch);
+    const size_t lds = ch.lds_bytes(R);
+    if (lds > PN2_LDS_LIMIT) return fail(ctx, PCR_ERR_STATE, "pointnet2: a chain does not fit in LDS");
+    ProfScope ps(ctx, prof);
+    if (a.mode != PN2_HEAD) PCR_HIP(ctx, hipMemsetAsync(a.out, 0, n_groups * ch.n_out() * 4, ctx->stream));
+    return R == 64 ? chain_launch_rt<4>(ctx, a, lds) : R == 32 ? chain_launch_rt<2>(ctx, a, lds) : chain_launch_rt<1>(ctx, a, lds);
+}
+
+bool seg_ok(const uint32_t* seg_ptr, size_t n_seg, size_t limit)
+{
+    for (size_t s = 0; s < n_seg; s++)
+        if (seg_ptr[s] > seg_ptr[s + 1]) return false;
+    return seg_ptr[n_seg] <= limit;
+}
+
+// carves a block in two passes: add() every slot, then bind(base)
+struct Carve {
+    std::vector<std::pair<void**, size_t>> slots;
+    size_t total = 0;
+    template <class T> void add(T** p, size_t count) { slots.push_back({ (void**)p, total }); total += al256(count * sizeof(T)); }
+    void bind(void* base) const { for (auto& s : slots) *s.first = (char*)base + s.second; }
+};
+
+}  // namespace
+
+}  // namespace pcr
+
+using namespace pcr;
+
+struct pcr_pn2_model {
+    pcr_pn2_desc desc;
+    int device = 0;
+    float* dev = nullptr;            // every layer's operands and biases
+    Chain sa[PCR_PN2_MAX_SA];
+    Chain head;
+    uint32_t sa_in[PCR_PN2_MAX_SA];  // input channels of every SA layer (3 + D)
+    uint64_t n_weights = 0;
+    uint32_t n_sampling = 0;
+};
+
+namespace {
+
+// the layers of a descriptor in weight order: (K, N, has BN); false for a descriptor outside the limits
+struct LayerShape { uint32_t K, N; bool bn; };
+bool pn2_shapes(const pcr_pn2_desc& d, std::vector<LayerShape>& shapes, uint32_t sa_in[PCR_PN2_MAX_SA])
+{
+    if (d.n_sa < 1 || d.n_sa > PCR_PN2_MAX_SA || d.n_fc < 1 || d.n_fc > PCR_PN2_MAX_FC) return false;
+    if (d.D0 > PN2_MAX_WIDTH - 3 || !std::isfinite(d.bn_eps)) return false;
+    uint32_t D = d.D0;
+    for (uint32_t l = 0; l < d.n_sa; l++) {
+        const pcr_pn2_sa_desc& s = d.sa[l];
+        if (s.n_mlp < 1 || s.n_mlp > PCR_PN2_MAX_MLP || s.group_all > 1) return false;
+        if (s.group_all && l + 1 != d.n_sa) return false;
+        if (!s.group_all && (s.npoint < 1 || s.nsample < 1 || s.nsample > 65536 || !(s.radius >= 0.0) || std::isinf(s.radius))) return false;
+        uint32_t K = 3 + D;
+        if (K > PN2_MAX_WIDTH) return false;
+        sa_in[l] = K;
+        for (uint32_t i = 0; i < s.n_mlp; i++) {
+            if (s.widths[i] < 1 || s.widths[i] > PN2_MAX_WIDTH) return false;
+            shapes.push_back({ K, s.widths[i], true });
+            K = s.widths[i];
+        }
+        D = K;
+    }
+    uint32_t K = D;
+    for (uint32_t i = 0; i < d.n_fc; i++) {
+        if (d.fc_widths[i] < 1 || d.fc_widths[i] > PN2_MAX_WIDTH) return false;
+        shapes.push_back({ K, d.fc_widths[i], i + 1 < d.n_fc });
+        K = d.fc_widths[i];
+    }
+    return true;
+}
+
+void chain_strides(Chain& ch)
+{
+    ch.s0 = ch.s1 = 4;
+    for (uint32_t l = 0; l < ch.n; l++) {
+        uint32_t& s = (l & 1u) ? ch.s1 : ch.s0;
+        s = std::max(s, ch.L[l].Kpad + 4);
+    }
+}
+
+}  // namespace
+
+extern "C" int pcr_pn2_model_create(pcr_ctx* ctx, const pcr_pn2_desc* desc, const float* weights, size_t n_weights, pcr_pn2_model** out)
+{
+    if (out) *out = nullptr;
+    if (!ctx || !desc || !weights || !out) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_model_create");
+    std::vector<LayerShape> shapes;
+    uint32_t sa_in[PCR_PN2_MAX_SA] = { 0, 0, 0, 0 };
+    if (!pn2_shapes(*desc, shapes, sa_in)) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_model_create: a descriptor outside the limits (see include/pcr.h)");
+    uint64_t need = 0;
+    for (const LayerShape& s : shapes) need += (uint64_t)s.K * s.N + s.N + (s.bn ? 4ull * s.N : 0ull);
+    if (n_weights != need) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_model_create: n_weights is not the model's count");
+    for (size_t i = 0; i < n_weights; i++)
+        if (!std::isfinite(weights[i])) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_model_create: a non-finite weight");
+    // ---- fold BN (f64, rounded once) into the operand order of the kernel
+    size_t dev_floats = 0;
+    std::vector<size_t> w_off(shapes.size()), b_off(shapes.size());
+    for (size_t i = 0; i < shapes.size(); i++) {
+        const size_t Kp = pad16(shapes[i].K), Np = pad16(shapes[i].N);
+        w_off[i] = dev_floats; dev_floats += Kp * Np;
+        b_off[i] = dev_floats; dev_floats += Np;
+        dev_floats = (dev_floats + 63) & ~(size_t)63;      // every operand block starts on 256 bytes
+    }
+    std::vector<float> img(dev_floats, 0.0f);
+    const float* p = weights;
+    for (size_t i = 0; i < shapes.size(); i++) {
+        const uint32_t K = shapes[i].K, N = shapes[i].N, Kp = pad16(K), KB = Kp / 16;
+        const float *W = p, *b = W + (size_t)K * N;
+        const float *gamma = b + N, *beta = gamma + N, *mean = beta + N, *var = mean + N;
+        p = shapes[i].bn ? var + N : b + N;
+        for (uint32_t n = 0; n < N; n++) {
+            double s = 1.0, bb = (double)b[n];
+            if (shapes[i].bn) {
+                const double v = (double)var[n] + desc->bn_eps;
+                if (!(v > 0.0)) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_model_create: running_var + eps must be positive");
+                s = (double)gamma[n] / std::sqrt(v);
+                bb = ((double)b[n] - (double)mean[n]) * s + (double)beta[n];
+            }
+            const float bf = (float)bb;
+            if (!std::isfinite(bf)) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_model_create: a folded bias is not finite");
+            img[b_off[i] + n] = bf;
+            const uint32_t t = n / 16, j = n % 16;
+            for (uint32_t k = 0; k < K; k++) {
+                const float wf = (float)(s * (double)W[(size_t)n * K + k]);
+                if (!std::isfinite(wf)) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_model_create: a folded weight is not finite");
+                const uint32_t kb = k / 16, sidx = (k % 16) / 4, q = k % 4;
+                img[w_off[i] + (((size_t)t * KB + kb) * 64 + (q * 16 + j)) * 4 + sidx] = wf;
+            }
+        }
+    }
+    PCR_HIP(ctx, hipSetDevice(ctx->device));
+    std::unique_ptr<pcr_pn2_model> m(new pcr_pn2_model());
+    m->desc = *desc;
+    m->device = ctx->device;
+    m->n_weights = need;
+    PCR_HIP(ctx, hipMalloc((void**)&m->dev, dev_floats * 4));
+    hipError_t e = hipMemcpy(m->dev, img.data(), dev_floats * 4, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(m->dev); return fail(ctx, PCR_ERR_HIP, "pcr_pn2_model_create: upload", e); }
+    size_t i = 0;
+    auto layer = [&](const LayerShape& s) {
+        LayerDev L;
+        L.w = m->dev + w_off[i]; L.b = m->dev + b_off[i];
+        L.K = s.K; L.Kpad = pad16(s.K); L.N = s.N; L.Npad = pad16(s.N);
+        i++;
+        return L;
+    };
+    for (uint32_t l = 0; l < desc->n_sa; l++) {
+        Chain& ch = m->sa[l];
+        ch.n = desc->sa[l].n_mlp;
+        for (uint32_t k = 0; k < ch.n; k++) ch.L[k] = layer(shapes[i]);
+        chain_strides(ch);
+        m->sa_in[l] = sa_in[l];
+        if (!desc->sa[l].group_all) m->n_sampling++;
+    }
+    m->head.n = desc->n_fc;
+    for (uint32_t k = 0; k < m->head.n; k++) m->head.L[k] = layer(shapes[i]);
+    chain_strides(m->head);
+    *out = m.release();
+    return PCR_OK;
+}
+
+extern "C" int pcr_pn2_model_destroy(pcr_ctx* ctx, pcr_pn2_model* model)
+{
+    if (!model) return PCR_OK;
+    if (ctx) {
+        (void)hipSetDevice(ctx->device);
+        (void)hipStreamSynchronize(ctx->stream);
+    }
+    if (model->dev) (void)hipFree(model->dev);
+    delete model;
+    return PCR_OK;
+}
+
+extern "C" int pcr_pn2_model_info(const pcr_pn2_model* model, size_t npts_hint, pcr_pn2_info* info, pcr_pn2_desc* desc)
+{
+    if (!model) return PCR_ERR_ARG;
+    if (desc) *desc = model->desc;
+    if (info) {
+        memset(info, 0, sizeof(*info));
+        info->n_weights = model->n_weights;
+        info->n_sampling = model->n_sampling;
+        info->n_class = model->head.n_out();
+        info->c_last = model->sa[model->desc.n_sa - 1].n_out();
+        uint64_t macs = 0, n = npts_hint;
+        for (uint32_t l = 0; l < model->desc.n_sa; l++) {
+            const pcr_pn2_sa_desc& s = model->desc.sa[l];
+            uint64_t per_row = 0;
+            for (uint32_t k = 0; k < model->sa[l].n; k++) per_row += (uint64_t)model->sa[l].L[k].K * model->sa[l].L[k].N;
+            macs += per_row * (s.group_all ? n : (uint64_t)s.npoint * s.nsample);
+            n = s.group_all ? 1 : s.npoint;
+        }
+        for (uint32_t k = 0; k < model->head.n; k++) macs += (uint64_t)model->head.L[k].K * model->head.L[k].N;
+        info->macs_per_object = macs;
+    }
+    return PCR_OK;
+}
+
+extern "C" int pcr_sa_mlp_max_f32(pcr_ctx* ctx, const pcr_pn2_model* model, int layer, const pcr_cloud* cloud, const uint32_t* seg_ptr, const pcr_cloud* centres,
+                                  const uint32_t* centre_seg_ptr, size_t n_seg, const float* features, const uint32_t* idx, float* out)
+{
+    if (!ctx || !model || !cloud || !seg_ptr) return fail(ctx, PCR_ERR_ARG, "pcr_sa_mlp_max_f32");
+    if (layer < 0 || (uint32_t)layer >= model->desc.n_sa) return fail(ctx, PCR_ERR_ARG, "pcr_sa_mlp_max_f32: no such SA layer");
+    if (model->device != ctx->device) return fail(ctx, PCR_ERR_ARG, "pcr_sa_mlp_max_f32: the model lives on another device");
+    const pcr_pn2_sa_desc& sd = model->desc.sa[layer];
+    const Chain& ch = model->sa[layer];
+    const bool ga = sd.group_all != 0;
+    const size_t D = model->sa_in[layer] - 3;
+    if (ga ? (centres || centre_seg_ptr || idx) : (!centres || !centre_seg_ptr)) return fail(ctx, PCR_ERR_ARG, "pcr_sa_mlp_max_f32: centres / centre_seg_ptr / idx go with a sampling layer only");
+    if (D > 0 && !features) return fail(ctx, PCR_ERR_ARG, "pcr_sa_mlp_max_f32: the layer takes features");
+    if (n_seg > PN2_MAX_ROWS || cloud->n > PN2_MAX_ROWS || (centres && centres->n > PN2_MAX_ROWS)) return fail(ctx, PCR_ERR_ARG, "pcr_sa_mlp_max_f32: too large");
+    if (!seg_ok(seg_ptr, n_seg, cloud->n) || (!ga && !seg_ok(centre_seg_ptr, n_seg, centres->n)))
+        return fail(ctx, PCR_ERR_ARG, "pcr_sa_mlp_max_f32: seg_ptr must ascend and end inside its cloud");
+    if (n_seg == 0) return PCR_OK;
+    const size_t nsample = ga ? 1 : sd.nsample;
+    const size_t q0 = ga ? 0 : centre_seg_ptr[0], nq = ga ? n_seg : centre_seg_ptr[n_seg] - q0;
+    const size_t p0 = seg_ptr[0], np = seg_ptr[n_seg] - p0;
+    if (nq == 0) return PCR_OK;
+    if (!out || (!ga && !idx)) return fail(ctx, PCR_ERR_ARG, "pcr_sa_mlp_max_f32: idx / out is NULL");
+    const unsigned long long rows = ga ? np : (unsigned long long)nq * nsample;
+    if (rows > PN2_MAX_ROWS || nq > PN2_MAX_ROWS / ch.n_out()) return fail(ctx, PCR_ERR_ARG, "pcr_sa_mlp_max_f32: too large");
+    std::vector<uint32_t> cs;
+    if (!ga) {
+        cs.resize(centre_seg_ptr[n_seg]);
+        for (size_t s = 0; s < n_seg; s++)
+            for (uint32_t q = centre_seg_ptr[s]; q < centre_seg_ptr[s + 1]; q++) cs[q] = (uint32_t)s;
+        for (size_t q = 0; q < nq; q++) {
+            const uint32_t sg = cs[q0 + q], n = seg_ptr[sg + 1] - seg_ptr[sg];
+            for (size_t k = 0; k < nsample; k++)
+                if (idx[q * nsample + k] >= n) return fail(ctx, PCR_ERR_ARG, "pcr_sa_mlp_max_f32: an index lies outside its segment (an empty ball-query row?)");
+        }
+    }
+    PCR_HIP(ctx, hipSetDevice(ctx->device));
+    uint32_t *seg_dev, *cs_dev, *idx_dev;
+    float *feat_dev, *out_dev;
+    Layout L;
+    L.add(&seg_dev, n_seg + 1);
+    L.add(&cs_dev, cs.size());
+    L.add(&idx_dev, ga ? 0 : nq * nsample);
+    L.add(&feat_dev, np * D);
+    L.add(&out_dev, nq * ch.n_out());
+    int rc = bind_scratch(ctx, L);
+    if (rc) return rc;
+    PCR_HIP(ctx, hipMemcpyAsync(seg_dev, seg_ptr, (n_seg + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (!ga) {
+        PCR_HIP(ctx, hipMemcpyAsync(cs_dev, cs.data(), cs.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+        PCR_HIP(ctx, hipMemcpyAsync(idx_dev, idx, nq * nsample * 4, hipMemcpyHostToDevice, ctx->stream));
+    }
+    if (D && np) PCR_HIP(ctx, hipMemcpyAsync(feat_dev, features + p0 * D, np * D * 4, hipMemcpyHostToDevice, ctx->stream));
+    PCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ChainArgs a;
+    memset(&a, 0, sizeof(a));
+    a.x = cloud->x(); a.y = cloud->y(); a.z = cloud->z();
+    if (!ga) { a.qx = centres->x() + q0; a.qy = centres->y() + q0; a.qz = centres->z() + q0; a.centre_seg = cs_dev + q0; a.idx = idx_dev; }
+    a.seg_ptr = seg_dev;
+    a.feat = feat_dev - p0 * D;          // addressed by cloud position: moved back by the rows that were not uploaded (never dereferenced there)
+    a.out = out_dev;
+    a.rows = (uint32_t)rows;
+    a.D = (uint32_t)D; a.nsample = (uint32_t)nsample; a.n_seg = (uint32_t)n_seg; a.p0 = (uint32_t)p0;
+    a.mode = ga ? PN2_GROUP_ALL : PN2_GROUPED;
+    if (rows == 0) {
+        PCR_HIP(ctx, hipMemsetAsync(out_dev, 0, nq * ch.n_out() * 4, ctx->stream));
+    } else {
+        rc = chain_launch(ctx, ch, a, nq, "pn2_sa");
+        if (rc) return rc;
+    }
+    PCR_HIP(ctx, hipMemcpyAsync(out, out_dev, nq * ch.n_out() * 4, hipMemcpyDeviceToHost, ctx->stream));
+    PCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    prof_flush(ctx);
+    return PCR_OK;
+}
+
+extern "C" int pcr_pn2_forward_f32(pcr_ctx* ctx, const pcr_pn2_model* model, const float* objects, size_t n_obj, size_t npts, const uint32_t* starts, uint64_t seed,
+                                   float* logp, int32_t* pred, float* global_feat, uint32_t* fps_idx)
+{
+    if (!ctx || !model) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_forward_f32");
+    if (model->device != ctx->device) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_forward_f32: the model lives on another device");
+    const pcr_pn2_desc& d = model->desc;
+    if (!d.sa[d.n_sa - 1].group_all) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_forward_f32: the last SA layer must be group_all");
+    if (npts < 1) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_forward_f32: npts must be >= 1");
+    if (n_obj == 0) return PCR_OK;
+    if (!objects || !logp) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_forward_f32: objects / logp is NULL");
+    const uint32_t ns = model->n_sampling, D0 = d.D0, C0 = 3 + D0;
+    const uint32_t n_class = model->head.n_out(), c_last = model->sa[d.n_sa - 1].n_out();
+    // ---- sizes of every stage
+    if (n_obj > PN2_MAX_ROWS || npts > PN2_MAX_ROWS || (unsigned long long)n_obj * npts > PN2_MAX_ROWS / C0) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_forward_f32: too large");
+    size_t N[PCR_PN2_MAX_SA + 1];
+    N[0] = npts;
+    for (uint32_t l = 0; l < ns; l++) {
+        const pcr_pn2_sa_desc& s = d.sa[l];
+        N[l + 1] = s.npoint;
+        const unsigned long long nq = (unsigned long long)n_obj * s.npoint;
+        if (nq > PN2_MAX_ROWS / s.nsample || nq > PN2_MAX_ROWS / model->sa[l].n_out()) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_forward_f32: too large");
+    }
+    if ((unsigned long long)n_obj * std::max<uint32_t>(c_last, n_class) > PN2_MAX_ROWS) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_forward_f32: too large");
+    std::vector<uint32_t> st((size_t)ns * n_obj);
+    for (uint32_t l = 0; l < ns; l++)
+        for (size_t o = 0; o < n_obj; o++) {
+            uint32_t v;
+            if (starts) {
+                v = starts[(size_t)l * n_obj + o];
+                if (v >= N[l]) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_forward_f32: a start outside its object");
+            } else {
+                v = (uint32_t)(splitmix_key(seed, ((unsigned long long)(l + 1) << 32) | (unsigned long long)o) % (unsigned long long)N[l]);
+            }
+            st[(size_t)l * n_obj + o] = v;
+        }
+    PCR_HIP(ctx, hipSetDevice(ctx->device));
+    // ---- one block: [uploaded: x y z feat | seg tables] [per sampling layer: picks, centres, ball rows, features out] [group_all out] [head]
+    const size_t P = n_obj * npts;
+    float *x0, *feat0, *ga_out, *logits, *logp_dev;
+    int32_t* pred_dev;
+    uint32_t* seg[PCR_PN2_MAX_SA + 1];          // the segments of cloud l: n_obj + 1 offsets
+    uint32_t* cseg[PCR_PN2_MAX_SA];             // the segment of every centre of sampling layer l
+    uint32_t *fps[PCR_PN2_MAX_SA], *bidx[PCR_PN2_MAX_SA], *bcnt[PCR_PN2_MAX_SA];
+    float *cxyz[PCR_PN2_MAX_SA], *sa_out[PCR_PN2_MAX_SA];
+    Carve cv;
+    cv.add(&x0, 3 * P);
+    cv.add(&feat0, P * D0);
+    for (uint32_t l = 0; l <= ns; l++) cv.add(&seg[l], n_obj + 1);
+    for (uint32_t l = 0; l < ns; l++) cv.add(&cseg[l], n_obj * N[l + 1]);
+    const size_t upload_bytes = cv.total;
+    for (uint32_t l = 0; l < ns; l++) {
+        const size_t nq = n_obj * N[l + 1];
+        cv.add(&fps[l], nq);
+        cv.add(&cxyz[l], 3 * nq);
+        cv.add(&bidx[l], nq * d.sa[l].nsample);
+        cv.add(&bcnt[l], nq);
+        cv.add(&sa_out[l], nq * model->sa[l].n_out());
+    }
+    cv.add(&ga_out, n_obj * c_last);
+    cv.add(&logits, n_obj * n_class);
+    cv.add(&logp_dev, n_obj * n_class);
+    cv.add(&pred_dev, n_obj);
+    int rc = ensure_scratch(ctx, cv.total);
+    if (rc) return rc;
+    rc = ensure_stage(ctx, upload_bytes);
+    if (rc) return rc;
+    cv.bind(ctx->host_stage);               // the uploaded part, laid out the same way in the pinned staging block
+    {
+        float *hx = x0, *hy = x0 + P, *hz = x0 + 2 * P;
+        for (size_t i = 0; i < P; i++) {
+            const float* r = objects + i * C0;
+            for (uint32_t c = 0; c < C0; c++)
+                if (!(fabsf(r[c]) <= FLT_MAX)) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_forward_f32: a non-finite coordinate or feature");
+            hx[i] = r[0]; hy[i] = r[1]; hz[i] = r[2];
+            for (uint32_t c = 0; c < D0; c++) feat0[i * D0 + c] = r[3 + c];
+        }
+        for (uint32_t l = 0; l <= ns; l++)
+            for (size_t o = 0; o <= n_obj; o++) seg[l][o] = (uint32_t)(o * N[l]);
+        for (uint32_t l = 0; l < ns; l++)
+            for (size_t q = 0; q < n_obj * N[l + 1]; q++) cseg[l][q] = (uint32_t)(q / N[l + 1]);
+    }
+    cv.bind(ctx->scratch);
+    PCR_HIP(ctx, hipMemcpyAsync(ctx->scratch, ctx->host_stage, upload_bytes, hipMemcpyHostToDevice, ctx->stream));
+    // ---- the sampling layers
+    HostKeep keep;
+    const float *cx = x0, *cy = x0 + P, *cz = x0 + 2 * P, *feat = feat0;
+    uint32_t D = D0;
+    for (uint32_t l = 0; l < ns; l++) {
+        const pcr_pn2_sa_desc& s = d.sa[l];
+        const size_t nq = n_obj * N[l + 1];
+        std::vector<FpsJob> jobs(n_obj);
+        for (size_t o = 0; o < n_obj; o++) jobs[o] = { (uint32_t)(o * N[l]), (uint32_t)N[l], st[(size_t)l * n_obj + o], (uint32_t)o };
+        rc = fps_device(ctx, cx, cy, cz, std::move(jobs), s.npoint, PCR_FPS_F32, fps[l], &keep);
+        if (rc) break;
+        float *qx = cxyz[l], *qy = qx + nq, *qz = qy + nq;
+        {
+            ProfScope ps(ctx, "pn2_centres");
+            hipLaunchKernelGGL(pn2_centres_kernel, dim3((unsigned)((nq + PN2_BLOCK - 1) / PN2_BLOCK)), dim3(PN2_BLOCK), 0, ctx->stream, cx, cy, cz, fps[l], (uint32_t)N[l],
+                               s.npoint, (uint32_t)nq, qx, qy, qz);
+        }
+        rc = ball_query_device(ctx, cx, cy, cz, qx, qy, qz, seg[l], cseg[l], nq, s.radius, s.nsample, bidx[l], bcnt[l]);
+        if (rc) break;
+        ChainArgs a;
+        memset(&a, 0, sizeof(a));
+        a.x = cx; a.y = cy; a.z = cz; a.qx = qx; a.qy = qy; a.qz = qz;
+        a.seg_ptr = seg[l]; a.centre_seg = cseg[l]; a.idx = bidx[l]; a.feat = feat; a.out = sa_out[l];
+        a.rows = (uint32_t)(nq * s.nsample);
+        a.D = D; a.nsample = s.nsample; a.n_seg = (uint32_t)n_obj; a.mode = PN2_GROUPED;
+        rc = chain_launch(ctx, model->sa[l], a, nq, "pn2_sa");
+        if (rc) break;
+        cx = qx; cy = qy; cz = qz; feat = sa_out[l];
+        D = model->sa[l].n_out();
+    }
+    if (rc == PCR_OK) {                      // the group_all layer, then the head on its rows
+        ChainArgs a;
+        memset(&a, 0, sizeof(a));
+        a.x = cx; a.y = cy; a.z = cz; a.seg_ptr = seg[ns]; a.feat = feat; a.out = ga_out;
+        a.rows = (uint32_t)(n_obj * N[ns]);
+        a.D = D; a.nsample = 1; a.n_seg = (uint32_t)n_obj; a.mode = PN2_GROUP_ALL;
+        rc = chain_launch(ctx, model->sa[ns], a, n_obj, "pn2_sa");
+    }
+    if (rc == PCR_OK) {
+        ChainArgs a;
+        memset(&a, 0, sizeof(a));
+        a.feat = ga_out; a.out = logits;
+        a.rows = (uint32_t)n_obj;
+        a.D = c_last; a.nsample = 1; a.mode = PN2_HEAD;
+        rc = chain_launch(ctx, model->head, a, n_obj, "pn2_head");
+    }
+    hipError_t e = hipSuccess;
+    if (rc == PCR_OK) {
+        {
+            ProfScope ps(ctx, "pn2_logsoftmax");
+            hipLaunchKernelGGL(pn2_logsoftmax_kernel, dim3((unsigned)((n_obj + PN2_BLOCK - 1) / PN2_BLOCK)), dim3(PN2_BLOCK), 0, ctx->stream, logits, (uint32_t)n_obj, n_class,
+                               logp_dev, pred_dev);
+        }
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(logp, logp_dev, n_obj * n_class * 4, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess && pred) e = hipMemcpyAsync(pred, pred_dev, n_obj * 4, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess && global_feat) e = hipMemcpyAsync(global_feat, ga_out, n_obj * c_last * 4, hipMemcpyDeviceToHost, ctx->stream);
+        if (fps_idx) {
+            size_t off = 0;
+            for (uint32_t l = 0; l < ns && e == hipSuccess; l++) {
+                e = hipMemcpyAsync(fps_idx + off, fps[l], n_obj * N[l + 1] * 4, hipMemcpyDeviceToHost, ctx->stream);
+                off += n_obj * N[l + 1];
+            }
+        }
+    }
+    const hipError_t e2 = hipStreamSynchronize(ctx->stream);      // the one wait: `keep` and the staging block are read until here
+    if (rc) return rc;
+    if (e != hipSuccess || e2 != hipSuccess) return fail(ctx, PCR_ERR_HIP, "pcr_pn2_forward_f32", e != hipSuccess ? e : e2);
+    prof_flush(ctx);
+    return PCR_OK;
+}

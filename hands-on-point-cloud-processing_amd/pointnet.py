@@ -5,7 +5,9 @@ Mirrors (same names, argument order and return shapes):
   query_ball_point        HomeworkFinal/models/pointnet_util.py:90-116    (GPU: pcr_ball_query_f32)
   index_points            HomeworkFinal/models/pointnet_util.py:46-63     (host indexing: it is a gather of a few KB)
   sample_and_group        HomeworkFinal/models/pointnet_util.py:119-156   (GPU: the three operators, one fused gather)
-  classify_foreground_objects   the flow of HomeworkFinal/foreground_obj_cls.py:97-180 up to the classifier's input
+  get_model               HomeworkFinal/models/pointnet2_cls_ssg.py           (GPU: pcr_pn2_forward_f32, eval mode only)
+  classify_foreground_objects   the flow of HomeworkFinal/foreground_obj_cls.py:97-188: up to the classifier's input, or with
+                          classifier= through it to pred_final
 
 The functions take [B, N, C] numpy arrays or torch tensors and return the same kind (indices as int64, like the reference).  Torch is
 plumbing here: a tensor is brought to the host, the library works on its own device cloud, and the result is put back on the tensor's
@@ -127,13 +129,131 @@ def sample_and_group(npoint, radius, nsample, xyz, points, returnfps=False, *, s
     return _like(new_xyz, proto), _like(new_points, proto), _like(grouped_xyz, proto), _like(fps_idx.astype(np.int64), proto, integer=True)
 
 
+# the reference's layers (pointnet2_cls_ssg.py:13-24): name in the state dict, npoint, radius, nsample, widths
+_SSG_SA = (("sa1", 64, 0.2, 8, (64, 64, 128)), ("sa2", 32, 0.4, 16, (128, 128, 256)), ("sa3", None, None, None, (256, 512, 1024)))
+_SSG_FC = (("fc1", "bn1", 512), ("fc2", "bn2", 256), ("fc3", None, None))
+_BN_KEYS = ("weight", "bias", "running_mean", "running_var")
+
+
+class get_model:
+    """models/pointnet2_cls_ssg.get_model in eval mode on the library: the same constructor arguments, state-dict keys and call.
+    load_state_dict takes the reference's checkpoint entries (Conv2d weights [out, in, 1, 1] or [out, in]; torch tensors or numpy arrays;
+    num_batches_tracked is ignored); the model is uploaded (BN folded) on the first call and again after the next load_state_dict.
+    __call__(xyz [B, 3 or 6, N]) -> (log_probs [B, num_class], l3_points [B, 1024, 1]), numpy or torch like the input; start= fixes the
+    first FPS pick of both sampling layers ([2, B]; None draws them from np.random as the reference draws them unseeded), ctx= the context.
+    Training is out of scope: train() raises."""
+
+    def __init__(self, num_class, normal_channel=False):
+        self.num_class, self.normal_channel = int(num_class), bool(normal_channel)
+        self.training = True
+        self._state, self._model, self._model_ctx = None, None, None
+
+    # ---- the layers in weight order: (prefix of the conv / linear, prefix of its BN or None, out, in)
+    def _layers(self):
+        out, last = [], 6 if self.normal_channel else 3
+        for name, _, _, _, mlp in _SSG_SA:
+            cin = last if name == "sa1" else last + 3
+            for i, w in enumerate(mlp):
+                out.append((f"{name}.mlp_convs.{i}", f"{name}.mlp_bns.{i}", w, cin))
+                cin = w
+            last = cin
+        cin = last
+        for fc, bn, w in _SSG_FC:
+            w = self.num_class if w is None else w
+            out.append((fc, bn, w, cin))
+            cin = w
+        return out
+
+    def desc(self):
+        from . import pn2_desc
+        sa = [dict(group_all=True, mlp=mlp) if npoint is None else dict(npoint=npoint, radius=radius, nsample=nsample, mlp=mlp)
+              for _, npoint, radius, nsample, mlp in _SSG_SA]
+        return pn2_desc(sa, [512, 256, self.num_class], D0=3 if self.normal_channel else 0, bn_eps=1e-5)
+
+    def state_dict(self):
+        return dict(self._state or {})
+
+    def load_state_dict(self, state, strict=True):
+        new = {}
+        for conv, bn, w, cin in self._layers():
+            keys = [(f"{conv}.weight", (w, cin)), (f"{conv}.bias", (w,))] + ([(f"{bn}.{k}", (w,)) for k in _BN_KEYS] if bn else [])
+            for key, shape in keys:
+                if key not in state:
+                    raise KeyError(f"missing key in state_dict: {key}")
+                a = np.asarray(_to_host(state[key])[0], np.float32)
+                if a.size != int(np.prod(shape)) or a.reshape(-1).size != a.size or (a.ndim >= 1 and a.shape[0] != shape[0]):
+                    raise ValueError(f"size mismatch for {key}: {a.shape}, the model takes {shape}")
+                new[key] = np.ascontiguousarray(a.reshape(shape))
+        if strict:
+            extra = [k for k in state if k not in new and not k.endswith("num_batches_tracked")]
+            if extra:
+                raise KeyError(f"unexpected keys in state_dict: {extra}")
+        self._state = new
+        self._drop()
+        return self
+
+    def flat_weights(self):
+        """the flat f32 array pcr_pn2_model_create takes"""
+        if self._state is None:
+            raise RuntimeError("no weights: call load_state_dict first (the reference ships no checkpoint)")
+        parts = []
+        for conv, bn, _, _ in self._layers():
+            parts += [self._state[f"{conv}.weight"].reshape(-1), self._state[f"{conv}.bias"]]
+            if bn:
+                parts += [self._state[f"{bn}.{k}"] for k in _BN_KEYS]
+        return np.concatenate(parts).astype(np.float32)
+
+    def eval(self):
+        self.training = False
+        return self
+
+    def train(self, mode=True):
+        if mode:
+            raise NotImplementedError("training is out of scope: the library runs the eval-mode forward pass only")
+        return self.eval()
+
+    def _drop(self):
+        if self._model is not None:
+            self._model.free()
+        self._model, self._model_ctx = None, None
+
+    def model(self, ctx=None):
+        """the device model on ctx (uploaded once per context and state dict)"""
+        ctx = _ctx(ctx)
+        if self._model is None or self._model_ctx is not ctx or not self._model.h:
+            self._drop()
+            self._model, self._model_ctx = ctx.pn2_model(self.desc(), self.flat_weights()), ctx
+        return self._model
+
+    def forward(self, xyz, *, start=None, seed=None, ctx=None, return_all=False):
+        if self.training:
+            raise RuntimeError("the model is in training mode: call eval() (BatchNorm batch statistics and dropout are out of scope)")
+        x, proto = _to_host(xyz)
+        C0 = 6 if self.normal_channel else 3
+        if x.ndim != 3 or x.shape[1] != C0:
+            raise ValueError(f"xyz: [B, {C0}, N]")
+        B, N = x.shape[0], x.shape[2]
+        st, _ = _to_host(start)
+        if st is None and seed is None:
+            st = np.stack([np.random.randint(0, N, size=B), np.random.randint(0, _SSG_SA[0][1], size=B)])
+        ctx = _ctx(ctx)
+        res = ctx.pn2_forward(self.model(ctx), np.ascontiguousarray(np.transpose(x, (0, 2, 1)), np.float32), st, 0 if seed is None else seed, return_all=True)
+        out = _like(res["logp"], proto), _like(res["global_feat"][:, :, None], proto)
+        return out + (res,) if return_all else out
+
+    __call__ = forward
+
+
 def classify_foreground_objects(points, npoints=256, eps=0.5, min_points=8, z_min_above_ground=0.5, z_extent=(1.0, 2.3), seed=0, *, ctx=None,
-                                preprocess=True):
-    """foreground_obj_cls.py:97-180 without the classifier (the reference ships no weights; the classifier stays the caller's):
-    pcd_preprocessing -> ground_detection_on3segs -> ground_z = mean z of the ground -> cluster_dbscan(eps, min_points) on the foreground
-    -> objects_from_labels.  points: (N, >= 3) scan rows.  Returns (objects f32 [n_obj, npoints, 3], codes i32 [n_clusters]: 3 where the
+                                preprocess=True, classifier=None):
+    """foreground_obj_cls.py:97-188: pcd_preprocessing -> ground_detection_on3segs -> ground_z = mean z of the ground ->
+    cluster_dbscan(eps, min_points) on the foreground -> objects_from_labels (-> the classifier).  points: (N, >= 3) scan rows.
+    Without a classifier (the reference ships no weights) returns (objects f32 [n_obj, npoints, 3], codes i32 [n_clusters]: 3 where the
     reference writes 3, -1 = to be classified) and a dict with everything in between (points, ground / foreground indices, ground_z,
-    labels, n_clusters, and the outputs of Context.objects_from_labels)."""
+    labels, n_clusters, and the outputs of Context.objects_from_labels).
+    With classifier= (a get_model in eval mode) every object goes through it in ONE batched forward pass (the first FPS picks drawn from
+    `seed`) and the second value is pred_final as the reference builds it (:152-188): i32 [n_clusters], 3 where it writes 3, the predicted
+    class elsewhere; the dict then also holds log_probs [n_obj, num_class]."""
     from . import hw4
     ctx = _ctx(ctx)
     pts = np.asarray(points)[:, :3]
@@ -148,4 +268,15 @@ def classify_foreground_objects(points, npoints=256, eps=0.5, min_points=8, z_mi
     finally:
         cloud.free()
     res.update(points=pts, ground_idx=ground_idx, foreground_idx=foreground_idx, ground_z=ground_z, labels=labels, n_clusters=n_clusters)
-    return res["objects"], res["codes"], res
+    if classifier is None:
+        return res["objects"], res["codes"], res
+    pred_final = np.array(res["codes"], np.int32)
+    objects = np.asarray(res["objects"], np.float32)
+    if len(objects):
+        _, _, out = classifier(np.transpose(objects, (0, 2, 1)), seed=seed, ctx=ctx, return_all=True)
+        pred_final[np.asarray(res["cluster"], np.int64)] = out["pred"]
+        res["log_probs"] = out["logp"]
+    else:
+        res["log_probs"] = np.zeros((0, classifier.num_class), np.float32)
+    res["pred_final"] = pred_final
+    return res["objects"], pred_final, res

@@ -573,6 +573,88 @@ int pcr_objects_from_labels_f32(pcr_ctx* ctx, const pcr_cloud* cloud, const int3
                                 double z_min_above_ground, const double z_extent[2], uint64_t seed, const uint32_t* starts, float* objects,
                                 uint32_t* object_cluster, uint32_t* source_index, int32_t* codes, float* z_min_max, uint32_t* sizes, size_t* n_objects);
 
+/* ---- HomeworkFinal: the PointNet++ (SSG) classifier, HomeworkFinal/models/pointnet2_cls_ssg.py + pointnet_util.py:159-215, eval mode -----------
+ * A model is a chain of up to 4 set-abstraction (SA) layers and up to 4 fully connected (FC) layers, described by pcr_pn2_desc:
+ *   D0         feature channels of the input besides xyz (0: xyz only, 3: normal_channel)
+ *   sa[l]      npoint, radius, nsample (sampling layers), group_all (0 / 1), n_mlp in 1 ... 4 shared-MLP widths.  The input of an SA layer has
+ *              3 + D channels, xyz FIRST (torch.cat([grouped_xyz_norm, grouped_points]), pointnet_util.py:150), D = D0 or the width the layer
+ *              before ends in; a group_all layer takes xyz un-centred (:173) and makes ONE group of all points of a segment.  Only the LAST
+ *              SA layer may be group_all, and pcr_pn2_forward_f32 needs it to be (the head reads one row per object).
+ *   fc_widths  n_fc in 1 ... 4 output widths; the input of the head is the last SA layer's last width; every FC layer but the last carries
+ *              BatchNorm + ReLU (dropout is the identity in eval mode); the last width is the number of classes.
+ *   bn_eps     BatchNorm's eps (torch: 1e-5)
+ * weights: ONE flat f32 array, layer after layer in the order SA 0 (its convolutions in order) ... SA n_sa - 1, FC 0 ... FC n_fc - 1; per
+ *   convolution / linear layer: W [out][in] row-major, bias [out], then — where the layer has BN (every convolution, every FC but the last) —
+ *   gamma [out], beta [out], running_mean [out], running_var [out].  pcr_pn2_model_info reports the length this adds up to.
+ * BN is folded on the host in f64 and rounded to f32 ONCE, at pcr_pn2_model_create: s = gamma / sqrt(var + eps), W' = s W,
+ *   b' = (b - mean) s + beta.  The device copy holds W' with K zero-padded to 16 (four K steps of the MFMA), in the operand order of the kernel.
+ * Arithmetic of every layer: out[n] = relu(c_K), c_0 = b'[n], c_(k+1) = fmaf(x[k], W'[n][k], c_k) for k = 0 ... K - 1 ASCENDING input channel —
+ *   ONE f32 fma chain per output that STARTS FROM THE BIAS IN THE ACCUMULATOR (not: the bias added after the chain).  It runs on
+ *   v_mfma_f32_16x16x4_f32, which is bit for bit that chain; the zero padding adds fmaf(0, 0, c) = c.  relu(v) = v > 0 ? v : +0.  The last FC
+ *   layer has no ReLU.  So a row's result does not depend on the tile geometry, on the other rows of the call, or on the workgroup that served it.
+ * Limits (PCR_ERR_ARG otherwise): n_sa in 1 ... 4, n_mlp in 1 ... 4, n_fc in 1 ... 4, every width and 3 + D0 in 1 ... 1024; a sampling layer
+ *   has npoint >= 1, nsample in 1 ... 65536 and a finite radius >= 0; group_all only on the last SA layer; bn_eps finite; n_weights equal to the
+ *   model's count; every weight finite; var + eps > 0.
+ *
+ * pcr_sa_mlp_max_f32 — ONE fused launch for SA layer `layer` of the model: per group gather the nsample members (idx, segment-local, as
+ *   pcr_ball_query_f32 returns them), subtract the centre (one f32 subtraction, as pcr_group_points_f32), run the layer's MLP chain, take the
+ *   max over the group's samples.  The activations of a row tile stay in LDS; nothing of size rows x nsample x C goes to memory.  Arguments as
+ *   in pcr_group_points_f32 (features: host, one row of D floats per point of the cloud, D = the layer's input channels - 3; NULL with D == 0);
+ *   for a group_all layer centres, centre_seg_ptr and idx are NULL and every segment is one group (an empty segment gives a row of zeros).
+ *   out: rows x C_out f32 (host), rows = number of centres, or n_seg for group_all.  Tune key pn2_rows [0 = the largest that fits in LDS]
+ *   16 / 32 / 64 rows per workgroup tile (results never depend on it; a value that does not fit falls back to the largest that does).
+ *   PCR_ERR_ARG as pcr_group_points_f32, and for a layer outside the model or centres / idx that do not go with its group_all flag.
+ *   Profile name pn2_sa.
+ *
+ * pcr_pn2_forward_f32 — the whole forward pass for n_obj objects of npts points each.  objects: host, n_obj x npts x (3 + D0), uploaded once.
+ *   Per sampling layer l (cloud = the input points, then the centres of the layer before): pcr_fps_f32's rule in PCR_FPS_F32 mode ->
+ *   centres = the picked points -> pcr_ball_query_f32's rule -> the fused kernel; the group_all layer; then the head through the same chain
+ *   kernel and log_softmax in f32, x - m - log(sum exp(x - m)), m = max, the sum in ascending class order.
+ *   starts (optional): n_sampling_layers x n_obj first picks, each below the layer's cloud size (npts, then npoint of the layer before).  NULL:
+ *   K(seed, (layer + 1) << 32 | obj) mod that size with the SplitMix keying above.  UNPINNED: the reference's unseeded torch.randint.
+ *   logp: n_obj x n_class; pred (optional): the FIRST maximum of a row, as max(1)[1]; global_feat (optional): n_obj x C_last, the reference's
+ *   l3_points; fps_idx (optional): the picks of the sampling layers one block after the other, block l = n_obj x npoint_l (object-local).
+ *   The stages hand device buffers to each other; the number of launches depends on the model and on npts, not on n_obj; the host waits once,
+ *   at the end.  n_obj == 0: PCR_OK, nothing written.  PCR_ERR_ARG: NULL ctx / model / objects / logp; a model whose last SA layer is not
+ *   group_all; npts < 1; a non-finite coordinate or feature (checked on the host copy); a start outside its object; more than 2^31 - 16 rows in
+ *   a stage.  Profile names pn2_sa, pn2_head, pn2_centres, pn2_logsoftmax (+ fps_small / fps_large, ball_query). */
+#define PCR_PN2_MAX_SA 4
+#define PCR_PN2_MAX_MLP 4
+#define PCR_PN2_MAX_FC 4
+typedef struct pcr_pn2_sa_desc {
+    uint32_t npoint;     /* ignored for group_all */
+    uint32_t nsample;    /* ignored for group_all */
+    double radius;       /* ignored for group_all */
+    uint32_t group_all;
+    uint32_t n_mlp;
+    uint32_t widths[PCR_PN2_MAX_MLP];
+} pcr_pn2_sa_desc;
+typedef struct pcr_pn2_desc {
+    uint32_t D0;
+    uint32_t n_sa;
+    pcr_pn2_sa_desc sa[PCR_PN2_MAX_SA];
+    uint32_t n_fc;
+    uint32_t fc_widths[PCR_PN2_MAX_FC];
+    double bn_eps;
+} pcr_pn2_desc;
+typedef struct pcr_pn2_info {
+    uint64_t n_weights;          /* length of the flat weight array */
+    uint64_t macs_per_object;    /* multiply-adds of one object of npts_hint points (unpadded) */
+    uint32_t n_sampling;         /* SA layers that are not group_all */
+    uint32_t n_class;
+    uint32_t c_last;             /* width of the global feature */
+    uint32_t reserved;
+} pcr_pn2_info;
+typedef struct pcr_pn2_model pcr_pn2_model;
+int pcr_pn2_model_create(pcr_ctx* ctx, const pcr_pn2_desc* desc, const float* weights, size_t n_weights, pcr_pn2_model** out);
+int pcr_pn2_model_destroy(pcr_ctx* ctx, pcr_pn2_model* model);
+/* desc (optional): the descriptor the model was made from; npts_hint: the object size macs_per_object is counted for */
+int pcr_pn2_model_info(const pcr_pn2_model* model, size_t npts_hint, pcr_pn2_info* info, pcr_pn2_desc* desc);
+int pcr_sa_mlp_max_f32(pcr_ctx* ctx, const pcr_pn2_model* model, int layer, const pcr_cloud* cloud, const uint32_t* seg_ptr, const pcr_cloud* centres,
+                       const uint32_t* centre_seg_ptr, size_t n_seg, const float* features, const uint32_t* idx, float* out);
+int pcr_pn2_forward_f32(pcr_ctx* ctx, const pcr_pn2_model* model, const float* objects, size_t n_obj, size_t npts, const uint32_t* starts, uint64_t seed,
+                        float* logp, int32_t* pred, float* global_feat, uint32_t* fps_idx);
+
 /* ---- next row N4: global-registration front half, Homework9/hw9/src/registration.cpp:288-434, :535-615 -----------
  * N4a: exhaustive 1-NN between two descriptor sets (row-major n x dim / m x dim f32, host memory; dim 33 = FPFH),
  * nanoflann's evalMetric arithmetic for any dim (nanoflann.hpp:382-405: groups of four + tail, f32, unfused), canonical
