@@ -79,6 +79,19 @@ class Pn2Desc(C.Structure):
                 ("bn_eps", C.c_double)]
 
 
+class Pn2BranchDesc(C.Structure):
+    _fields_ = [("radius", C.c_double), ("nsample", C.c_uint32), ("n_mlp", C.c_uint32), ("widths", C.c_uint32 * 4)]
+
+
+class Pn2MsgSaDesc(C.Structure):
+    _fields_ = [("npoint", C.c_uint32), ("group_all", C.c_uint32), ("xyz_last", C.c_uint32), ("n_branch", C.c_uint32), ("branch", Pn2BranchDesc * 4)]
+
+
+class Pn2MsgDesc(C.Structure):
+    _fields_ = [("D0", C.c_uint32), ("n_sa", C.c_uint32), ("sa", Pn2MsgSaDesc * 4), ("n_fc", C.c_uint32), ("fc_widths", C.c_uint32 * 4),
+                ("bn_eps", C.c_double)]
+
+
 class Pn2Info(C.Structure):
     _fields_ = [("n_weights", C.c_uint64), ("macs_per_object", C.c_uint64), ("n_sampling", C.c_uint32), ("n_class", C.c_uint32),
                 ("c_last", C.c_uint32), ("reserved", C.c_uint32)]
@@ -101,6 +114,7 @@ ABI_SYMBOLS = [
     "pcr_dbscan_f32", "pcr_statistical_outlier_f32", "pcr_fpfh33_f32", "pcr_harris3d_f32", "pcr_voxel_grid_normals_f32", "pcr_normal_space_sample_f32",
     "pcr_fps_f32", "pcr_ball_query_f32", "pcr_group_points_f32", "pcr_objects_from_labels_f32",
     "pcr_pn2_model_create", "pcr_pn2_model_destroy", "pcr_pn2_model_info", "pcr_sa_mlp_max_f32", "pcr_pn2_forward_f32",
+    "pcr_pn2_msg_model_create", "pcr_pn2_msg_model_info", "pcr_ball_query_multi_f32", "pcr_sa_msg_mlp_max_f32",
     "pcr_mat64_create", "pcr_mat64_destroy", "pcr_mat64_info", "pcr_kmeans_step_f64", "pcr_kmeans_fit_f64", "pcr_kmeans_predict_f64", "pcr_kmeanspp_init_f64",
     "pcr_gmm_em_step_f64", "pcr_gmm_fit_f64", "pcr_gmm_predict_f64",
     "pcr_mat64_knn_f64", "pcr_spectral_graph_f64", "pcr_spgraph_info", "pcr_spgraph_read", "pcr_spgraph_destroy", "pcr_eig_small_f64",
@@ -215,6 +229,10 @@ def lib():
     L.pcr_pn2_model_info.argtypes = [vp, sz, C.POINTER(Pn2Info), C.POINTER(Pn2Desc)]
     L.pcr_sa_mlp_max_f32.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp, sz, vp, vp, vp]
     L.pcr_pn2_forward_f32.argtypes = [vp, vp, vp, sz, sz, vp, C.c_uint64, vp, vp, vp, vp]
+    L.pcr_pn2_msg_model_create.argtypes = [vp, C.POINTER(Pn2MsgDesc), vp, sz, C.POINTER(vp)]
+    L.pcr_pn2_msg_model_info.argtypes = [vp, sz, C.POINTER(Pn2Info), C.POINTER(Pn2MsgDesc)]
+    L.pcr_ball_query_multi_f32.argtypes = [vp, vp, vp, vp, vp, sz, sz, vp, vp, vp, vp]
+    L.pcr_sa_msg_mlp_max_f32.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp, sz, vp, vp, vp]
     L.pcr_mat64_create.argtypes = [vp, vp, sz, C.c_int, C.POINTER(vp)]
     L.pcr_mat64_destroy.argtypes = [vp, vp]
     L.pcr_mat64_info.argtypes = [vp, C.POINTER(sz), ip, ip]
@@ -461,14 +479,61 @@ def pn2_desc(sa, fc, D0: int = 0, bn_eps: float = 1e-5) -> Pn2Desc:
     return d
 
 
-class Pn2Model:
-    """A PointNet++ (SSG) classifier resident in HBM (pcr_pn2_model): BN folded into the weights at upload; the contract is in include/pcr.h."""
+def pn2_msg_desc(sa, fc, D0: int = 0, bn_eps: float = 1e-5) -> Pn2MsgDesc:
+    """sa: a list of dicts {npoint, xyz_last (default False), branches: [{radius, nsample, mlp: [widths]}, ...]} or {group_all: True, mlp: [...]}
+    (a dict of pn2_desc's kind, {npoint, radius, nsample, mlp}, is one branch); fc: the head's output widths.  The contract is above
+    pcr_pn2_msg_model_create in include/pcr.h."""
+    d = Pn2MsgDesc()
+    if len(sa) > 4 or len(fc) > 4:
+        raise PcrError("at most 4 SA layers and 4 FC layers")
+    d.D0, d.n_sa, d.n_fc, d.bn_eps = int(D0), len(sa), len(fc), float(bn_eps)
+    for l, s in enumerate(sa):
+        e = d.sa[l]
+        e.group_all = 1 if s.get("group_all") else 0
+        e.xyz_last = 1 if s.get("xyz_last") else 0
+        branches = s["branches"] if "branches" in s else [s]
+        if len(branches) > 4:
+            raise PcrError("at most 4 branches per SA layer")
+        e.n_branch = len(branches)
+        if not e.group_all:
+            e.npoint = int(s["npoint"])
+        for b, br in enumerate(branches):
+            mlp = list(br["mlp"])
+            if len(mlp) > 4:
+                raise PcrError("at most 4 widths per branch")
+            if not e.group_all:
+                e.branch[b].radius, e.branch[b].nsample = float(br["radius"]), int(br["nsample"])
+            e.branch[b].n_mlp = len(mlp)
+            for k, w in enumerate(mlp):
+                e.branch[b].widths[k] = int(w)
+    for k, w in enumerate(fc):
+        d.fc_widths[k] = int(w)
+    return d
 
-    def __init__(self, ctx: "Context", desc: Pn2Desc, weights):
+
+def pn2_msg_desc_info(desc: Pn2MsgDesc, npts: int = 0) -> dict:
+    """What a model made from desc would report (Pn2Model.info), without a device: pcr_pn2_msg_model_info with no model."""
+    i = Pn2Info()
+    rc = lib().pcr_pn2_msg_model_info(None, int(npts), C.byref(i), C.byref(desc))
+    if rc != 0:
+        raise PcrError(f"{ERRORS.get(rc, rc)}: a descriptor outside the limits (see include/pcr.h)")
+    return {"n_weights": int(i.n_weights), "macs_per_object": int(i.macs_per_object), "n_sampling": int(i.n_sampling), "n_class": int(i.n_class),
+            "c_last": int(i.c_last)}
+
+
+class Pn2Model:
+    """A PointNet++ classifier resident in HBM (pcr_pn2_model), single-scale (a Pn2Desc) or multi-scale (a Pn2MsgDesc): BN folded into the
+    weights at upload; the contract is in include/pcr.h.  desc is the descriptor the model was made from, mdesc the superset descriptor the
+    library holds for every model."""
+
+    def __init__(self, ctx: "Context", desc, weights):
         w = np.ascontiguousarray(weights, np.float32).reshape(-1)
         h = C.c_void_p()
-        ctx._ck(lib().pcr_pn2_model_create(ctx.h, C.byref(desc), w.ctypes.data if w.size else None, w.size, C.byref(h)))
+        create = lib().pcr_pn2_msg_model_create if isinstance(desc, Pn2MsgDesc) else lib().pcr_pn2_model_create
+        ctx._ck(create(ctx.h, C.byref(desc), w.ctypes.data if w.size else None, w.size, C.byref(h)))
         self.ctx, self.h, self.desc = ctx, h, desc
+        self.mdesc = Pn2MsgDesc()
+        ctx._ck(lib().pcr_pn2_msg_model_info(h, 0, None, C.byref(self.mdesc)))
         ctx._handles.add(self)
 
     def __del__(self):
@@ -492,8 +557,12 @@ class Pn2Model:
         return [int(self.desc.sa[l].npoint) for l in range(self.desc.n_sa) if not self.desc.sa[l].group_all]
 
     def sa_out_width(self, layer: int) -> int:
-        e = self.desc.sa[layer]
-        return int(e.widths[e.n_mlp - 1])
+        e = self.mdesc.sa[layer]
+        return sum(int(e.branch[b].widths[e.branch[b].n_mlp - 1]) for b in range(e.n_branch))
+
+    def sa_nsamples(self, layer: int):
+        e = self.mdesc.sa[layer]
+        return [int(e.branch[b].nsample) for b in range(e.n_branch)]
 
     def sa_in_features(self, layer: int) -> int:
         return int(self.desc.D0) if layer == 0 else self.sa_out_width(layer - 1)
@@ -1220,6 +1289,75 @@ class Context:
                                             ix.ctypes.data, int(nsample), new_xyz.ctypes.data, new_points.ctypes.data))
         return new_xyz[:rows], new_points[:rows]
 
+    def ball_query_multi(self, cloud: Cloud, seg_ptr, centres: Cloud, centre_seg_ptr, radii, nsamples):
+        """query_ball_point at up to four radii in one walk -> (a list of u32 [rows, nsamples[b]], counts u32 [len(radii), rows]); every radius
+        as Context.ball_query gives it; the contract of pcr_ball_query_multi_f32."""
+        sp, cp = self._seg(seg_ptr), self._seg(centre_seg_ptr)
+        if sp.size != cp.size:
+            raise PcrError("the two seg_ptr arrays describe the same segments")
+        rad = np.ascontiguousarray(radii, np.float64).reshape(-1)
+        ns = np.ascontiguousarray(nsamples, np.uint64).reshape(-1)
+        if rad.size != ns.size:
+            raise PcrError("one nsample per radius")
+        rows = int(cp[-1]) - int(cp[0])
+        total = int(ns.sum()) if 1 <= ns.size <= 4 else 0
+        idx = np.zeros(max(rows * total, 1), np.uint32)
+        cnt = np.zeros((max(ns.size, 1), max(rows, 1)), np.uint32)
+        self._ck(lib().pcr_ball_query_multi_f32(self.h, cloud.h, sp.ctypes.data, centres.h, cp.ctypes.data, sp.size - 1, rad.size, rad.ctypes.data if rad.size else None,
+                                                ns.ctypes.data if ns.size else None, idx.ctypes.data, cnt.ctypes.data))
+        blocks, off = [], 0
+        for k in ns.tolist():
+            blocks.append(idx[off:off + rows * int(k)].reshape(rows, int(k)))
+            off += rows * int(k)
+        cnt = np.ascontiguousarray(cnt[:, :rows]) if rows else np.zeros((ns.size, 0), np.uint32)
+        return blocks, cnt
+
+    def pn2_msg_model(self, desc, weights) -> Pn2Model:
+        """desc: a Pn2MsgDesc (pn2_msg_desc(...)); weights: the flat f32 array, layer by layer, branch by branch, convolution by convolution,
+        then the FC layers (pointnet.get_model_msg.flat_weights builds it from a state dict)."""
+        if not isinstance(desc, Pn2MsgDesc):
+            raise PcrError("desc: a Pn2MsgDesc")
+        return Pn2Model(self, desc, weights)
+
+    def sa_msg_mlp_max(self, model: Pn2Model, layer: int, cloud: Cloud, seg_ptr, centres=None, centre_seg_ptr=None, idx=None, features=None):
+        """One SA layer with every branch -> f32 [rows, the layer's concatenated width]; the contract of pcr_sa_msg_mlp_max_f32.  idx: a list with
+        one [rows, nsample_b] array per branch (or the blocks already laid one after the other)."""
+        sp = self._seg(seg_ptr)
+        n_seg = sp.size - 1
+        layer = int(layer)
+        if not 0 <= layer < model.mdesc.n_sa:
+            self._ck(lib().pcr_sa_msg_mlp_max_f32(self.h, model.h, layer, cloud.h, sp.ctypes.data, None, None, n_seg, None, None, None))
+            raise PcrError("bad argument: no such SA layer")
+        ga = bool(model.mdesc.sa[layer].group_all)
+        cp, ix = None, None
+        if ga:
+            rows = n_seg
+        else:
+            if centres is None or centre_seg_ptr is None or idx is None:
+                raise PcrError("a sampling layer needs centres, centre_seg_ptr and idx")
+            cp = self._seg(centre_seg_ptr)
+            if sp.size != cp.size:
+                raise PcrError("the two seg_ptr arrays describe the same segments")
+            rows = int(cp[-1]) - int(cp[0])
+            if isinstance(idx, (list, tuple)):
+                ix = np.concatenate([np.ascontiguousarray(b, np.uint32).reshape(-1) for b in idx]) if len(idx) else np.zeros(0, np.uint32)
+            else:
+                ix = np.ascontiguousarray(idx, np.uint32).reshape(-1)
+            if ix.size != rows * sum(model.sa_nsamples(layer)):
+                raise PcrError("one index row of nsample entries per centre and branch")
+        feat = None
+        D = model.sa_in_features(layer)
+        if D:
+            if features is None:
+                raise PcrError("the layer takes features")
+            feat = np.ascontiguousarray(features, np.float32).reshape(-1, D)
+            if feat.shape[0] != len(cloud):
+                raise PcrError("one feature row per point of the cloud")
+        out = np.zeros((max(rows, 1), model.sa_out_width(layer)), np.float32)
+        self._ck(lib().pcr_sa_msg_mlp_max_f32(self.h, model.h, layer, cloud.h, sp.ctypes.data, None if ga else centres.h, None if ga else cp.ctypes.data,
+                                              n_seg, None if feat is None else feat.ctypes.data, None if ga or not ix.size else ix.ctypes.data, out.ctypes.data))
+        return out[:rows]
+
     def pn2_model(self, desc, weights) -> Pn2Model:
         """desc: a Pn2Desc (pn2_desc(...)); weights: the flat f32 array in the order include/pcr.h states (pointnet.flat_weights builds it
         from a state dict).  BN is folded at upload."""
@@ -1246,7 +1384,7 @@ class Context:
                 raise PcrError("the two seg_ptr arrays describe the same segments")
             rows = int(cp[-1]) - int(cp[0])
             ix = np.ascontiguousarray(idx, np.uint32).reshape(-1)
-            if ix.size != rows * int(model.desc.sa[layer].nsample):
+            if model.mdesc.sa[layer].n_branch == 1 and ix.size != rows * model.sa_nsamples(layer)[0]:
                 raise PcrError("one index row of nsample entries per centre")
         feat = None
         D = model.sa_in_features(layer)

@@ -368,6 +368,10 @@ int fps_device(pcr_ctx* ctx, const float* x, const float* y, const float* z, std
 // pcr_ball_query_f32's kernel on device tables: seg_dev[n_seg + 1], centre_seg_dev[nq] (the segment of every centre), idx_dev[nq][nsample], cnt_dev[nq]
 int ball_query_device(pcr_ctx* ctx, const float* x, const float* y, const float* z, const float* qx, const float* qy, const float* qz, const uint32_t* seg_dev,
                       const uint32_t* centre_seg_dev, size_t nq, double radius, size_t nsample, uint32_t* idx_dev, uint32_t* cnt_dev);
+// pcr_ball_query_multi_f32's kernel on device tables: n_radii in 1 ... 4; per radius b idx_dev[b][nq][nsamples[b]] and cnt_dev[b][nq]
+int ball_query_multi_device(pcr_ctx* ctx, const float* x, const float* y, const float* z, const float* qx, const float* qy, const float* qz, const uint32_t* seg_dev,
+                            const uint32_t* centre_seg_dev, size_t nq, size_t n_radii, const double* radii, const uint32_t* nsamples, uint32_t* const* idx_dev,
+                            uint32_t* const* cnt_dev);
 // SplitMix64 keying of include/pcr.h: K(seed, a)
 inline unsigned long long splitmix_key(unsigned long long seed, unsigned long long a)
 {

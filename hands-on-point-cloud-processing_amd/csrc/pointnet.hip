@@ -296,6 +296,63 @@ __global__ __launch_bounds__(PN_BLOCK) void ball_query_kernel(const float* __res
     if (lane == 0) counts[q] = cnt;
 }
 
+// ---- ball query at up to four radii: one wave per centre, ONE walk of the segment, one distance per point and chunk, one ballot per radius.
+// Every radius keeps the state of ball_query_kernel (cnt, first) and stops taking hits at the chunk that fills its row, so its row and its
+// count are what that kernel gives; the walk ends when every row is full.
+struct BallMultiArgs {
+    float r2[4];
+    uint32_t nsample[4];
+    uint32_t* idx[4];
+    uint32_t* counts[4];
+    uint32_t n_radii;
+};
+
+__global__ __launch_bounds__(PN_BLOCK) void ball_query_multi_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ z,
+                                                                    const float* __restrict__ qx, const float* __restrict__ qy, const float* __restrict__ qz,
+                                                                    const uint32_t* __restrict__ seg_ptr, const uint32_t* __restrict__ centre_seg, uint32_t n_centres,
+                                                                    const BallMultiArgs a)
+{
+    const uint32_t q = blockIdx.x * (PN_BLOCK / 64) + (threadIdx.x >> 6);      // wave-uniform
+    if (q >= n_centres) return;
+    const int lane = threadIdx.x & 63;
+    const uint32_t s = centre_seg[q], base = seg_ptr[s], n = seg_ptr[s + 1] - base;
+    const float ax = qx[q], ay = qy[q], az = qz[q];
+    uint32_t cnt[4] = { 0, 0, 0, 0 }, first[4] = { n, n, n, n };
+    uint32_t open = 0;                                                         // radii whose row is not full yet
+#pragma unroll
+    for (int b = 0; b < 4; b++)
+        if ((uint32_t)b < a.n_radii) open |= 1u << b;
+    for (uint32_t i0 = 0; i0 < n && open != 0u; i0 += 64) {                    // bounded by the segment
+        const uint32_t i = i0 + (uint32_t)lane;
+        float d = __builtin_nanf("");                                          // no point: no hit at any radius
+        if (i < n) {
+            const float dx = ax - x[base + i], dy = ay - y[base + i], dz = az - z[base + i];
+            d = (dx * dx + dy * dy) + dz * dz;
+        }
+#pragma unroll
+        for (int b = 0; b < 4; b++) {
+            if (!(open & (1u << b))) continue;                                 // wave-uniform
+            const bool hit = d <= a.r2[b];                                     // false for NaN: a non-finite point is never a hit
+            const unsigned long long mask = __ballot(hit);
+            if (mask != 0ull) {
+                const uint32_t pos = cnt[b] + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
+                if (hit && pos < a.nsample[b]) a.idx[b][(size_t)q * a.nsample[b] + pos] = i;
+                if (cnt[b] == 0) first[b] = i0 + (uint32_t)__builtin_ctzll(mask);
+                cnt[b] += (uint32_t)__popcll(mask);
+                if (cnt[b] >= a.nsample[b]) open &= ~(1u << b);
+            }
+        }
+    }
+#pragma unroll
+    for (int b = 0; b < 4; b++) {
+        if ((uint32_t)b >= a.n_radii) continue;
+        const uint32_t ns = a.nsample[b], c = cnt[b] > ns ? ns : cnt[b];
+        uint32_t* row = a.idx[b] + (size_t)q * ns;
+        for (uint32_t p = c + (uint32_t)lane; p < ns; p += 64) row[p] = first[b];      // the first hit, or the segment's size for an empty row
+        if (lane == 0) a.counts[b][q] = c;
+    }
+}
+
 // ---- group: new_points[q][k] = (xyz[idx] - centre | features[idx]) ------------------------------------------------------------------------------
 __global__ __launch_bounds__(PN_BLOCK) void group_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ z,
                                                          const float* __restrict__ qx, const float* __restrict__ qy, const float* __restrict__ qz,
@@ -635,6 +692,80 @@ extern "C" int pcr_ball_query_f32(pcr_ctx* ctx, const pcr_cloud* cloud, const ui
     if (rc) return rc;
     PCR_HIP(ctx, hipMemcpyAsync(idx, idx_dev, nq * nsample * 4, hipMemcpyDeviceToHost, ctx->stream));
     if (counts) PCR_HIP(ctx, hipMemcpyAsync(counts, cnt_dev, nq * 4, hipMemcpyDeviceToHost, ctx->stream));
+    PCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    prof_flush(ctx);
+    return PCR_OK;
+}
+
+int pcr::ball_query_multi_device(pcr_ctx* ctx, const float* x, const float* y, const float* z, const float* qx, const float* qy, const float* qz,
+                                 const uint32_t* seg_dev, const uint32_t* centre_seg_dev, size_t nq, size_t n_radii, const double* radii, const uint32_t* nsamples,
+                                 uint32_t* const* idx_dev, uint32_t* const* cnt_dev)
+{
+    if (nq == 0) return PCR_OK;
+    if (n_radii < 1 || n_radii > 4) return fail(ctx, PCR_ERR_ARG, "ball_query_multi_device: 1 ... 4 radii");
+    BallMultiArgs a;
+    memset(&a, 0, sizeof(a));
+    a.n_radii = (uint32_t)n_radii;
+    for (size_t b = 0; b < n_radii; b++) {
+        a.r2[b] = (float)(radii[b] * radii[b]);
+        a.nsample[b] = nsamples[b];
+        a.idx[b] = idx_dev[b];
+        a.counts[b] = cnt_dev[b];
+    }
+    {
+        ProfScope ps(ctx, "ball_query_multi");
+        hipLaunchKernelGGL(ball_query_multi_kernel, dim3((unsigned)((nq + PN_BLOCK / 64 - 1) / (PN_BLOCK / 64))), dim3(PN_BLOCK), 0, ctx->stream, x, y, z, qx, qy, qz,
+                           seg_dev, centre_seg_dev, (uint32_t)nq, a);
+    }
+    PCR_HIP(ctx, hipGetLastError());
+    return PCR_OK;
+}
+
+extern "C" int pcr_ball_query_multi_f32(pcr_ctx* ctx, const pcr_cloud* cloud, const uint32_t* seg_ptr, const pcr_cloud* centres, const uint32_t* centre_seg_ptr,
+                                        size_t n_seg, size_t n_radii, const double* radii, const size_t* nsamples, uint32_t* idx, uint32_t* counts)
+{
+    if (!ctx || !cloud || !seg_ptr || !centres || !centre_seg_ptr || !radii || !nsamples) return fail(ctx, PCR_ERR_ARG, "pcr_ball_query_multi_f32");
+    if (n_radii < 1 || n_radii > 4) return fail(ctx, PCR_ERR_ARG, "pcr_ball_query_multi_f32: n_radii must be 1 ... 4");
+    size_t row_total = 0;
+    for (size_t b = 0; b < n_radii; b++) {
+        if (!(radii[b] >= 0.0) || std::isinf(radii[b])) return fail(ctx, PCR_ERR_ARG, "pcr_ball_query_multi_f32: a radius must be finite and >= 0");
+        if (nsamples[b] == 0 || nsamples[b] > 0x7FFFFFF0ull) return fail(ctx, PCR_ERR_ARG, "pcr_ball_query_multi_f32: nsample must be >= 1");
+        row_total += nsamples[b];
+    }
+    if (n_seg > 0x7FFFFFF0ull || cloud->n > 0x7FFFFFF0ull || centres->n > 0x7FFFFFF0ull) return fail(ctx, PCR_ERR_ARG, "pcr_ball_query_multi_f32: too large");
+    if (!seg_ptr_ok(seg_ptr, n_seg, cloud->n) || !seg_ptr_ok(centre_seg_ptr, n_seg, centres->n))
+        return fail(ctx, PCR_ERR_ARG, "pcr_ball_query_multi_f32: seg_ptr must ascend and end inside its cloud");
+    if (n_seg == 0) return PCR_OK;
+    const size_t q0 = centre_seg_ptr[0], nq = centre_seg_ptr[n_seg] - q0;
+    if (nq == 0) return PCR_OK;
+    if (!idx) return fail(ctx, PCR_ERR_ARG, "pcr_ball_query_multi_f32: idx is NULL");
+    if (nq > 0x7FFFFFF0ull / row_total) return fail(ctx, PCR_ERR_ARG, "pcr_ball_query_multi_f32: too large");
+    PCR_HIP(ctx, hipSetDevice(ctx->device));
+    std::vector<uint32_t> cs = centre_segments(centre_seg_ptr, n_seg);      // indexed by centre (rows below q0 unused)
+    uint32_t *seg_dev, *cs_dev, *idx_dev, *cnt_dev;
+    Layout L;
+    L.add(&seg_dev, n_seg + 1);
+    L.add(&cs_dev, cs.size());
+    L.add(&idx_dev, nq * row_total);
+    L.add(&cnt_dev, nq * n_radii);
+    int rc = bind_scratch(ctx, L);
+    if (rc) return rc;
+    PCR_HIP(ctx, hipMemcpyAsync(seg_dev, seg_ptr, (n_seg + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+    PCR_HIP(ctx, hipMemcpyAsync(cs_dev, cs.data(), cs.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    PCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    uint32_t *ib[4] = { nullptr, nullptr, nullptr, nullptr }, *cb[4] = { nullptr, nullptr, nullptr, nullptr }, ns[4] = { 0, 0, 0, 0 };
+    size_t off = 0;
+    for (size_t b = 0; b < n_radii; b++) {
+        ib[b] = idx_dev + off;
+        cb[b] = cnt_dev + b * nq;
+        ns[b] = (uint32_t)nsamples[b];
+        off += nq * nsamples[b];
+    }
+    rc = ball_query_multi_device(ctx, cloud->x(), cloud->y(), cloud->z(), centres->x() + q0, centres->y() + q0, centres->z() + q0, seg_dev, cs_dev + q0, nq, n_radii,
+                                 radii, ns, ib, cb);
+    if (rc) return rc;
+    PCR_HIP(ctx, hipMemcpyAsync(idx, idx_dev, nq * row_total * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (counts) PCR_HIP(ctx, hipMemcpyAsync(counts, cnt_dev, nq * n_radii * 4, hipMemcpyDeviceToHost, ctx->stream));
     PCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
     prof_flush(ctx);
     return PCR_OK;

@@ -13,6 +13,10 @@
 //                      every block of 16 channels the position 4 q + s holds channel 4 s + q, so that the float4 a lane reads is its
 //                      operand of four consecutive K steps.  buffer 0 is as wide as the widest input of an even layer, buffer 1 of an odd one.
 //   forward           upload -> per sampling layer { FPS, centres, ball query, memset, chain } -> group_all chain -> head chain -> log_softmax.
+//   MSG               (models/pointnet2_cls_msg.py) a layer has up to four branches over one set of centres: one multi-radius ball query, one
+//                      scan of the counts (pn2_compact), one memset of the concatenated rows, one chain per branch into its own columns
+//                      (out_stride / out_col).  xyz_last puts the features before xyz - centre in layer 0's gather.  With row_ptr a tile row
+//                      maps to (group, member) through the scan of the counts: only real hits are run, the copies that pad a row are not.
 #include "pcr_internal.hpp"
 
 #include <algorithm>
@@ -48,17 +52,19 @@ struct ChainArgs {
     const uint32_t* centre_seg;       // the segment of every centre (GROUPED)
     const uint32_t* idx;              // rows segment-local members (GROUPED)
     const float* feat;                // D floats per point of the cloud; HEAD: per row
-    float* out;                       // groups x N of the last layer
+    const uint32_t* row_ptr;          // compacted rows (GROUPED): n_groups + 1 offsets, the exclusive scan of the groups' counts; NULL: padded rows
+    float* out;                       // groups x out_stride; the chain writes the N columns from out_col on
     uint32_t rows;                    // GROUPED: centres x nsample, GROUP_ALL: points of the segments, HEAD: objects
     uint32_t D, nsample, n_seg, mode, n_layers, s0, s1, p0;
+    uint32_t out_stride, out_col, xyz_last, n_groups;
     LayerDev L[PCR_PN2_MAX_MLP];
 };
 
 __device__ __forceinline__ float pn2_relu(float v) { return v > 0.0f ? v : 0.0f; }
 
-__device__ __forceinline__ void pn2_atomic_max(float* out, int grp, uint32_t N, uint32_t c, float m)
+__device__ __forceinline__ void pn2_atomic_max(float* out, int grp, uint32_t stride, uint32_t c, float m)
 {
-    if (m > 0.0f) atomicMax((unsigned int*)(out + (size_t)grp * N + c), __float_as_uint(m));      // out starts at +0; m >= +0: the bits order as the values
+    if (m > 0.0f) atomicMax((unsigned int*)(out + (size_t)grp * stride + c), __float_as_uint(m));      // out starts at +0; m >= +0: the bits order as the values
 }
 
 template <int RT>
@@ -72,11 +78,17 @@ __global__ __launch_bounds__(PN2_BLOCK) void pn2_chain_kernel(const ChainArgs a)
     int* rowG = (int*)(rowP + R);                               // its group = row of the output, -1: no such row
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     // ---- the rows of this tile
+    uint32_t rows = a.rows;
+    if (a.row_ptr) {                                            // compacted: the launch is sized for the padded rows, a tile past the total has nothing to do
+        rows = a.row_ptr[a.n_groups];
+        if ((unsigned long long)blockIdx.x * R >= rows) return; // block-uniform
+    }
+    float* const outp = a.out + a.out_col;
     if (tid < R) {
         const unsigned long long g = (unsigned long long)blockIdx.x * R + (unsigned)tid;
         int grp = -1;
         uint32_t p = 0;
-        if (g < a.rows) {
+        if (g < rows) {
             if (a.mode == PN2_HEAD) {
                 p = (uint32_t)g;
                 grp = (int)g;
@@ -91,21 +103,34 @@ __global__ __launch_bounds__(PN2_BLOCK) void pn2_chain_kernel(const ChainArgs a)
                 grp = (int)lo;
             }
             if (a.mode == PN2_GROUPED) {
-                const uint32_t q = (uint32_t)(g / a.nsample);
+                uint32_t q, k;                                  // the group and the member of it
+                if (a.row_ptr) {
+                    uint32_t lo = 0, hi = a.n_groups;           // the last group that starts at or before g (a group without a hit never holds g)
+                    while (hi - lo > 1) {
+                        const uint32_t mid = (lo + hi) >> 1;
+                        if (a.row_ptr[mid] <= (uint32_t)g) lo = mid; else hi = mid;
+                    }
+                    q = lo;
+                    k = (uint32_t)g - a.row_ptr[lo];
+                } else {
+                    q = (uint32_t)(g / a.nsample);
+                    k = (uint32_t)(g - (unsigned long long)q * a.nsample);
+                }
                 const uint32_t s = a.centre_seg[q], base = a.seg_ptr[s], n = a.seg_ptr[s + 1] - base;
-                if (n) {
-                    uint32_t i = a.idx[g];
-                    if (i >= n) i = n - 1;                      // (never: the host checks the caller's rows, a centre of the forward pass is its own hit)
+                const uint32_t i = k < a.nsample ? a.idx[(size_t)q * a.nsample + k] : n;
+                if (i < n) {
                     p = base + i;
                     grp = (int)q;
-                }
+                } else {
+                    grp = -2 - (int)q;                          // a group without a hit (its row holds the segment's size): it leaves its zeros.  Negative
+                }                                               // and its own value, so that the rows of a tile still fall into runs of equal groups
             }
         }
         rowP[tid] = p;
         rowG[tid] = grp;
     }
     __syncthreads();
-    // ---- layer 0's input: (xyz - centre | features | zeros up to Kpad), a row without a group is all zeros
+    // ---- layer 0's input: (xyz - centre | features | zeros up to Kpad), or (features | xyz - centre | zeros) with xyz_last; a row without a group is all zeros
     {
         const uint32_t Kp = a.L[0].Kpad;
         for (uint32_t e = (uint32_t)tid; e < (uint32_t)R * Kp; e += PN2_BLOCK) {
@@ -117,15 +142,19 @@ __global__ __launch_bounds__(PN2_BLOCK) void pn2_chain_kernel(const ChainArgs a)
             if (grp >= 0) {
                 if (a.mode == PN2_HEAD) {
                     if (ch < a.D) v = a.feat[(size_t)p * a.D + ch];
-                } else if (ch < 3u) {
-                    const float* pc = ch == 0 ? a.x : (ch == 1 ? a.y : a.z);
-                    v = pc[p];
-                    if (a.mode == PN2_GROUPED) {
-                        const float* cc = ch == 0 ? a.qx : (ch == 1 ? a.qy : a.qz);
-                        v = v - cc[grp];
-                    }
                 } else if (ch < 3u + a.D) {
-                    v = a.feat[(size_t)p * a.D + (ch - 3u)];
+                    const uint32_t x0 = a.xyz_last ? a.D : 0u, f0 = a.xyz_last ? 0u : 3u;      // where xyz and the features start
+                    if (ch >= x0 && ch < x0 + 3u) {
+                        const uint32_t c3 = ch - x0;
+                        const float* pc = c3 == 0 ? a.x : (c3 == 1 ? a.y : a.z);
+                        v = pc[p];
+                        if (a.mode == PN2_GROUPED) {
+                            const float* cc = c3 == 0 ? a.qx : (c3 == 1 ? a.qy : a.qz);
+                            v = v - cc[grp];
+                        }
+                    } else {
+                        v = a.feat[(size_t)p * a.D + (ch - f0)];
+                    }
                 }
             }
             buf0[(size_t)r * a.s0 + pos] = v;
@@ -180,23 +209,23 @@ __global__ __launch_bounds__(PN2_BLOCK) void pn2_chain_kernel(const ChainArgs a)
 #pragma unroll
                         for (int reg = 0; reg < 4; reg++) {
                             const int grp = rowG[rt * 16 + 4 * h + reg];
-                            if (grp >= 0 && cvalid) a.out[(size_t)grp * L.N + c] = acc[rt][reg];
+                            if (grp >= 0 && cvalid) outp[(size_t)grp * a.out_stride + c] = acc[rt][reg];
                         }
                 } else {
 #pragma unroll
                     for (int rt = 0; rt < RT; rt++) {
                         const int r0 = rt * 16;
-                        const int g0 = rowG[r0], g7 = rowG[r0 + 7], g8 = rowG[r0 + 8], g15 = rowG[r0 + 15];      // groups ascend along the rows, -1 only at the tail
+                        const int g0 = rowG[r0], g7 = rowG[r0 + 7], g8 = rowG[r0 + 8], g15 = rowG[r0 + 15];      // the rows of a group are consecutive, -1 only at the tail
                         const float v0 = pn2_relu(acc[rt][0]), v1 = pn2_relu(acc[rt][1]), v2 = pn2_relu(acc[rt][2]), v3 = pn2_relu(acc[rt][3]);
                         if (g0 == g15 || (g0 == g7 && g8 == g15)) {        // wave-uniform: the 16 rows are one group, or two halves of one group each
                             float m = fmaxf(fmaxf(v0, v1), fmaxf(v2, v3));
                             m = fmaxf(m, __shfl_xor(m, 16, 64));
                             if (g0 == g15) {
                                 m = fmaxf(m, __shfl_xor(m, 32, 64));
-                                if (h == 0 && g0 >= 0 && cvalid) pn2_atomic_max(a.out, g0, L.N, c, m);
+                                if (h == 0 && g0 >= 0 && cvalid) pn2_atomic_max(outp, g0, a.out_stride, c, m);
                             } else {
                                 const int grp = h < 2 ? g0 : g8;
-                                if ((h & 1) == 0 && grp >= 0 && cvalid) pn2_atomic_max(a.out, grp, L.N, c, m);
+                                if ((h & 1) == 0 && grp >= 0 && cvalid) pn2_atomic_max(outp, grp, a.out_stride, c, m);
                             }
                         } else {                                            // runs of equal groups inside the lane's four rows
                             const float v[4] = { v0, v1, v2, v3 };
@@ -206,14 +235,14 @@ __global__ __launch_bounds__(PN2_BLOCK) void pn2_chain_kernel(const ChainArgs a)
                             for (int reg = 1; reg < 4; reg++) {
                                 const int grp = rowG[r0 + 4 * h + reg];
                                 if (grp != cur) {
-                                    if (cur >= 0 && cvalid) pn2_atomic_max(a.out, cur, L.N, c, m);
+                                    if (cur >= 0 && cvalid) pn2_atomic_max(outp, cur, a.out_stride, c, m);
                                     cur = grp;
                                     m = v[reg];
                                 } else {
                                     m = fmaxf(m, v[reg]);
                                 }
                             }
-                            if (cur >= 0 && cvalid) pn2_atomic_max(a.out, cur, L.N, c, m);
+                            if (cur >= 0 && cvalid) pn2_atomic_max(outp, cur, a.out_stride, c, m);
                         }
                     }
                 }
@@ -285,20 +314,66 @@ int chain_launch_rt(pcr_ctx* ctx, const ChainArgs& a, size_t lds)
     return PCR_OK;
 }
 
-// a.out (n_groups x n_out) <- the chain over a.rows rows; enqueued on the stream
-int chain_launch(pcr_ctx* ctx, const Chain& ch, ChainArgs a, size_t n_groups, const char* prof)
+// columns [a.out_col, a.out_col + n_out) of a.out (n_groups x a.out_stride; 0 = n_out) <- the chain over a.rows rows; enqueued on the stream.
+// clear: the rows of a.out are zeroed first, under the same profile scope — the caller of a layer with several branches asks for it ONCE, with
+// its first branch (the max is taken with atomics on rows that start at +0).
+int chain_launch(pcr_ctx* ctx, const Chain& ch, ChainArgs a, size_t n_groups, const char* prof, bool clear = true)
 {
     if (a.rows == 0 || n_groups == 0) return PCR_OK;
     a.n_layers = ch.n;
     a.s0 = ch.s0;
     a.s1 = ch.s1;
+    a.n_groups = (uint32_t)n_groups;
+    if (a.out_stride == 0) a.out_stride = ch.n_out();
     for (uint32_t l = 0; l < ch.n; l++) a.L[l] = ch.L[l];
     const int R = chain_rows(ctx, ch);
     const size_t lds = ch.lds_bytes(R);
     if (lds > PN2_LDS_LIMIT) return fail(ctx, PCR_ERR_STATE, "pointnet2: a chain does not fit in LDS");
     ProfScope ps(ctx, prof);
-    if (a.mode != PN2_HEAD) PCR_HIP(ctx, hipMemsetAsync(a.out, 0, n_groups * ch.n_out() * 4, ctx->stream));
+    if (a.mode != PN2_HEAD && clear) PCR_HIP(ctx, hipMemsetAsync(a.out, 0, n_groups * a.out_stride * 4, ctx->stream));
     return R == 64 ? chain_launch_rt<4>(ctx, a, lds) : R == 32 ? chain_launch_rt<2>(ctx, a, lds) : chain_launch_rt<1>(ctx, a, lds);
+}
+
+// row_ptr[b][0 .. nq] <- the exclusive scan of counts[b][0 .. nq), for every branch b = blockIdx.x in ONE launch.  A thread sums a run of
+// consecutive counts, the 256 sums are scanned in LDS, the thread writes its run.
+__global__ __launch_bounds__(PN2_BLOCK) void pn2_scan_kernel(const uint32_t* __restrict__ counts, uint32_t nq, uint32_t* __restrict__ row_ptr)
+{
+    __shared__ uint32_t part[PN2_BLOCK];
+    const uint32_t* c = counts + (size_t)blockIdx.x * nq;
+    uint32_t* rp = row_ptr + (size_t)blockIdx.x * ((size_t)nq + 1);
+    const uint32_t per = (nq + PN2_BLOCK - 1) / PN2_BLOCK;
+    const unsigned long long lo64 = (unsigned long long)threadIdx.x * per;
+    const uint32_t lo = lo64 < nq ? (uint32_t)lo64 : nq, hi = lo64 + per < nq ? (uint32_t)(lo64 + per) : nq;
+    uint32_t sum = 0;
+    for (uint32_t i = lo; i < hi; i++) sum += c[i];
+    part[threadIdx.x] = sum;
+    __syncthreads();
+    for (int d = 1; d < PN2_BLOCK; d <<= 1) {                   // inclusive scan of the 256 sums
+        const uint32_t v = (int)threadIdx.x >= d ? part[threadIdx.x - d] : 0u;
+        __syncthreads();
+        part[threadIdx.x] += v;
+        __syncthreads();
+    }
+    uint32_t run = part[threadIdx.x] - sum;
+    for (uint32_t i = lo; i < hi; i++) { rp[i] = run; run += c[i]; }
+    if (threadIdx.x == PN2_BLOCK - 1) rp[nq] = part[PN2_BLOCK - 1];
+}
+
+int scan_launch(pcr_ctx* ctx, const uint32_t* counts_dev, size_t nq, size_t n_branch, uint32_t* row_ptr_dev)
+{
+    if (nq == 0 || n_branch == 0) return PCR_OK;
+    ProfScope ps(ctx, "pn2_scan");
+    hipLaunchKernelGGL(pn2_scan_kernel, dim3((unsigned)n_branch), dim3(PN2_BLOCK), 0, ctx->stream, counts_dev, (uint32_t)nq, row_ptr_dev);
+    PCR_HIP(ctx, hipGetLastError());
+    return PCR_OK;
+}
+
+// pn2_compact: -1 / unset = the model's default, 0 = padded rows, anything else = compacted
+bool compact_rows(const pcr_ctx* ctx, bool model_default)
+{
+    auto it = ctx->tune.find("pn2_compact");
+    if (it == ctx->tune.end() || it->second < 0) return model_default;
+    return it->second != 0;
 }
 
 bool seg_ok(const uint32_t* seg_ptr, size_t n_seg, size_t limit)
@@ -323,12 +398,16 @@ struct Carve {
 using namespace pcr;
 
 struct pcr_pn2_model {
-    pcr_pn2_desc desc;
+    pcr_pn2_msg_desc desc;           // every model is held in the superset descriptor
+    pcr_pn2_desc ssg;                // the single-scale descriptor, where it can express the model (has_ssg)
+    bool has_ssg = false;
+    bool compact_default = false;    // pn2_compact of a context that does not set it
     int device = 0;
     float* dev = nullptr;            // every layer's operands and biases
-    Chain sa[PCR_PN2_MAX_SA];
+    Chain sa[PCR_PN2_MAX_SA][PCR_PN2_MAX_BRANCH];
     Chain head;
     uint32_t sa_in[PCR_PN2_MAX_SA];  // input channels of every SA layer (3 + D)
+    uint32_t sa_out[PCR_PN2_MAX_SA]; // its width: the sum of its branches' last widths
     uint64_t n_weights = 0;
     uint32_t n_sampling = 0;
 };
@@ -337,25 +416,35 @@ namespace {
 
 // the layers of a descriptor in weight order: (K, N, has BN); false for a descriptor outside the limits
 struct LayerShape { uint32_t K, N; bool bn; };
-bool pn2_shapes(const pcr_pn2_desc& d, std::vector<LayerShape>& shapes, uint32_t sa_in[PCR_PN2_MAX_SA])
+bool pn2_shapes(const pcr_pn2_msg_desc& d, std::vector<LayerShape>& shapes, uint32_t sa_in[PCR_PN2_MAX_SA], uint32_t sa_out[PCR_PN2_MAX_SA])
 {
     if (d.n_sa < 1 || d.n_sa > PCR_PN2_MAX_SA || d.n_fc < 1 || d.n_fc > PCR_PN2_MAX_FC) return false;
     if (d.D0 > PN2_MAX_WIDTH - 3 || !std::isfinite(d.bn_eps)) return false;
     uint32_t D = d.D0;
     for (uint32_t l = 0; l < d.n_sa; l++) {
-        const pcr_pn2_sa_desc& s = d.sa[l];
-        if (s.n_mlp < 1 || s.n_mlp > PCR_PN2_MAX_MLP || s.group_all > 1) return false;
-        if (s.group_all && l + 1 != d.n_sa) return false;
-        if (!s.group_all && (s.npoint < 1 || s.nsample < 1 || s.nsample > 65536 || !(s.radius >= 0.0) || std::isinf(s.radius))) return false;
-        uint32_t K = 3 + D;
-        if (K > PN2_MAX_WIDTH) return false;
-        sa_in[l] = K;
-        for (uint32_t i = 0; i < s.n_mlp; i++) {
-            if (s.widths[i] < 1 || s.widths[i] > PN2_MAX_WIDTH) return false;
-            shapes.push_back({ K, s.widths[i], true });
-            K = s.widths[i];
+        const pcr_pn2_msg_sa_desc& s = d.sa[l];
+        if (s.n_branch < 1 || s.n_branch > PCR_PN2_MAX_BRANCH || s.group_all > 1 || s.xyz_last > 1) return false;
+        if (s.group_all && (l + 1 != d.n_sa || s.n_branch != 1)) return false;
+        if (!s.group_all && s.npoint < 1) return false;
+        const uint32_t K0 = 3 + D;
+        if (K0 > PN2_MAX_WIDTH) return false;
+        sa_in[l] = K0;
+        uint32_t width = 0;
+        for (uint32_t b = 0; b < s.n_branch; b++) {
+            const pcr_pn2_branch_desc& br = s.branch[b];
+            if (br.n_mlp < 1 || br.n_mlp > PCR_PN2_MAX_MLP) return false;
+            if (!s.group_all && (br.nsample < 1 || br.nsample > 65536 || !(br.radius >= 0.0) || std::isinf(br.radius))) return false;
+            uint32_t K = K0;
+            for (uint32_t i = 0; i < br.n_mlp; i++) {
+                if (br.widths[i] < 1 || br.widths[i] > PN2_MAX_WIDTH) return false;
+                shapes.push_back({ K, br.widths[i], true });
+                K = br.widths[i];
+            }
+            width += K;
         }
-        D = K;
+        if (width > PN2_MAX_WIDTH) return false;
+        sa_out[l] = width;
+        D = width;
     }
     uint32_t K = D;
     for (uint32_t i = 0; i < d.n_fc; i++) {
@@ -377,18 +466,21 @@ void chain_strides(Chain& ch)
 
 }  // namespace
 
-extern "C" int pcr_pn2_model_create(pcr_ctx* ctx, const pcr_pn2_desc* desc, const float* weights, size_t n_weights, pcr_pn2_model** out)
+namespace {
+
+// the model of a descriptor; ssg: the single-scale descriptor it was made from, or NULL.  who: the entry point, for the messages
+int model_build(pcr_ctx* ctx, const pcr_pn2_msg_desc* desc, const pcr_pn2_desc* ssg, const float* weights, size_t n_weights, pcr_pn2_model** out, const char* who,
+                bool compact_default)
 {
-    if (out) *out = nullptr;
-    if (!ctx || !desc || !weights || !out) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_model_create");
+    auto bad = [&](const char* what) { return fail(ctx, PCR_ERR_ARG, (std::string(who) + what).c_str()); };
     std::vector<LayerShape> shapes;
-    uint32_t sa_in[PCR_PN2_MAX_SA] = { 0, 0, 0, 0 };
-    if (!pn2_shapes(*desc, shapes, sa_in)) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_model_create: a descriptor outside the limits (see include/pcr.h)");
+    uint32_t sa_in[PCR_PN2_MAX_SA] = { 0, 0, 0, 0 }, sa_out[PCR_PN2_MAX_SA] = { 0, 0, 0, 0 };
+    if (!pn2_shapes(*desc, shapes, sa_in, sa_out)) return bad(": a descriptor outside the limits (see include/pcr.h)");
     uint64_t need = 0;
     for (const LayerShape& s : shapes) need += (uint64_t)s.K * s.N + s.N + (s.bn ? 4ull * s.N : 0ull);
-    if (n_weights != need) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_model_create: n_weights is not the model's count");
+    if (n_weights != need) return bad(": n_weights is not the model's count");
     for (size_t i = 0; i < n_weights; i++)
-        if (!std::isfinite(weights[i])) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_model_create: a non-finite weight");
+        if (!std::isfinite(weights[i])) return bad(": a non-finite weight");
     // ---- fold BN (f64, rounded once) into the operand order of the kernel
     size_t dev_floats = 0;
     std::vector<size_t> w_off(shapes.size()), b_off(shapes.size());
@@ -409,17 +501,17 @@ extern "C" int pcr_pn2_model_create(pcr_ctx* ctx, const pcr_pn2_desc* desc, cons
             double s = 1.0, bb = (double)b[n];
             if (shapes[i].bn) {
                 const double v = (double)var[n] + desc->bn_eps;
-                if (!(v > 0.0)) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_model_create: running_var + eps must be positive");
+                if (!(v > 0.0)) return bad(": running_var + eps must be positive");
                 s = (double)gamma[n] / std::sqrt(v);
                 bb = ((double)b[n] - (double)mean[n]) * s + (double)beta[n];
             }
             const float bf = (float)bb;
-            if (!std::isfinite(bf)) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_model_create: a folded bias is not finite");
+            if (!std::isfinite(bf)) return bad(": a folded bias is not finite");
             img[b_off[i] + n] = bf;
             const uint32_t t = n / 16, j = n % 16;
             for (uint32_t k = 0; k < K; k++) {
                 const float wf = (float)(s * (double)W[(size_t)n * K + k]);
-                if (!std::isfinite(wf)) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_model_create: a folded weight is not finite");
+                if (!std::isfinite(wf)) return bad(": a folded weight is not finite");
                 const uint32_t kb = k / 16, sidx = (k % 16) / 4, q = k % 4;
                 img[w_off[i] + (((size_t)t * KB + kb) * 64 + (q * 16 + j)) * 4 + sidx] = wf;
             }
@@ -428,11 +520,14 @@ extern "C" int pcr_pn2_model_create(pcr_ctx* ctx, const pcr_pn2_desc* desc, cons
     PCR_HIP(ctx, hipSetDevice(ctx->device));
     std::unique_ptr<pcr_pn2_model> m(new pcr_pn2_model());
     m->desc = *desc;
+    if (ssg) m->ssg = *ssg; else memset(&m->ssg, 0, sizeof(m->ssg));
+    m->has_ssg = ssg != nullptr;
+    m->compact_default = compact_default;
     m->device = ctx->device;
     m->n_weights = need;
     PCR_HIP(ctx, hipMalloc((void**)&m->dev, dev_floats * 4));
     hipError_t e = hipMemcpy(m->dev, img.data(), dev_floats * 4, hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(m->dev); return fail(ctx, PCR_ERR_HIP, "pcr_pn2_model_create: upload", e); }
+    if (e != hipSuccess) { (void)hipFree(m->dev); return fail(ctx, PCR_ERR_HIP, "pointnet2: the upload of a model", e); }
     size_t i = 0;
     auto layer = [&](const LayerShape& s) {
         LayerDev L;
@@ -442,11 +537,14 @@ extern "C" int pcr_pn2_model_create(pcr_ctx* ctx, const pcr_pn2_desc* desc, cons
         return L;
     };
     for (uint32_t l = 0; l < desc->n_sa; l++) {
-        Chain& ch = m->sa[l];
-        ch.n = desc->sa[l].n_mlp;
-        for (uint32_t k = 0; k < ch.n; k++) ch.L[k] = layer(shapes[i]);
-        chain_strides(ch);
+        for (uint32_t b = 0; b < desc->sa[l].n_branch; b++) {
+            Chain& ch = m->sa[l][b];
+            ch.n = desc->sa[l].branch[b].n_mlp;
+            for (uint32_t k = 0; k < ch.n; k++) ch.L[k] = layer(shapes[i]);
+            chain_strides(ch);
+        }
         m->sa_in[l] = sa_in[l];
+        m->sa_out[l] = sa_out[l];
         if (!desc->sa[l].group_all) m->n_sampling++;
     }
     m->head.n = desc->n_fc;
@@ -454,6 +552,47 @@ extern "C" int pcr_pn2_model_create(pcr_ctx* ctx, const pcr_pn2_desc* desc, cons
     chain_strides(m->head);
     *out = m.release();
     return PCR_OK;
+}
+
+}  // namespace
+
+extern "C" int pcr_pn2_model_create(pcr_ctx* ctx, const pcr_pn2_desc* desc, const float* weights, size_t n_weights, pcr_pn2_model** out)
+{
+    if (out) *out = nullptr;
+    if (!ctx || !desc || !weights || !out) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_model_create");
+    if (desc->n_sa < 1 || desc->n_sa > PCR_PN2_MAX_SA) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_model_create: a descriptor outside the limits (see include/pcr.h)");
+    pcr_pn2_msg_desc d;                      // the same model in the superset descriptor: one xyz-first branch per layer
+    memset(&d, 0, sizeof(d));
+    d.D0 = desc->D0; d.n_sa = desc->n_sa; d.n_fc = desc->n_fc; d.bn_eps = desc->bn_eps;
+    for (uint32_t k = 0; k < PCR_PN2_MAX_FC; k++) d.fc_widths[k] = desc->fc_widths[k];
+    for (uint32_t l = 0; l < desc->n_sa; l++) {
+        const pcr_pn2_sa_desc& s = desc->sa[l];
+        d.sa[l].npoint = s.npoint; d.sa[l].group_all = s.group_all; d.sa[l].xyz_last = 0; d.sa[l].n_branch = 1;
+        d.sa[l].branch[0].radius = s.radius; d.sa[l].branch[0].nsample = s.nsample; d.sa[l].branch[0].n_mlp = s.n_mlp;
+        for (uint32_t k = 0; k < PCR_PN2_MAX_MLP; k++) d.sa[l].branch[0].widths[k] = s.widths[k];
+    }
+    return model_build(ctx, &d, desc, weights, n_weights, out, "pcr_pn2_model_create", false);
+}
+
+extern "C" int pcr_pn2_msg_model_create(pcr_ctx* ctx, const pcr_pn2_msg_desc* desc, const float* weights, size_t n_weights, pcr_pn2_model** out)
+{
+    if (out) *out = nullptr;
+    if (!ctx || !desc || !weights || !out) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_msg_model_create");
+    pcr_pn2_desc s;                          // the single-scale descriptor, if every layer has one xyz-first branch
+    memset(&s, 0, sizeof(s));
+    bool single = desc->n_sa >= 1 && desc->n_sa <= PCR_PN2_MAX_SA;
+    for (uint32_t l = 0; single && l < desc->n_sa; l++) single = desc->sa[l].n_branch == 1 && desc->sa[l].xyz_last == 0;
+    if (single) {
+        s.D0 = desc->D0; s.n_sa = desc->n_sa; s.n_fc = desc->n_fc; s.bn_eps = desc->bn_eps;
+        for (uint32_t k = 0; k < PCR_PN2_MAX_FC; k++) s.fc_widths[k] = desc->fc_widths[k];
+        for (uint32_t l = 0; l < desc->n_sa; l++) {
+            const pcr_pn2_msg_sa_desc& m = desc->sa[l];
+            s.sa[l].npoint = m.npoint; s.sa[l].group_all = m.group_all;
+            s.sa[l].radius = m.branch[0].radius; s.sa[l].nsample = m.branch[0].nsample; s.sa[l].n_mlp = m.branch[0].n_mlp;
+            for (uint32_t k = 0; k < PCR_PN2_MAX_MLP; k++) s.sa[l].widths[k] = m.branch[0].widths[k];
+        }
+    }
+    return model_build(ctx, desc, single ? &s : nullptr, weights, n_weights, out, "pcr_pn2_msg_model_create", true);
 }
 
 extern "C" int pcr_pn2_model_destroy(pcr_ctx* ctx, pcr_pn2_model* model)
@@ -468,102 +607,185 @@ extern "C" int pcr_pn2_model_destroy(pcr_ctx* ctx, pcr_pn2_model* model)
     return PCR_OK;
 }
 
+namespace {
+
+// the figures of a descriptor (which pn2_shapes accepts): they do not need the device
+bool desc_info(const pcr_pn2_msg_desc& d, size_t npts_hint, pcr_pn2_info* info)
+{
+    std::vector<LayerShape> shapes;
+    uint32_t sa_in[PCR_PN2_MAX_SA] = { 0, 0, 0, 0 }, sa_out[PCR_PN2_MAX_SA] = { 0, 0, 0, 0 };
+    if (!pn2_shapes(d, shapes, sa_in, sa_out)) return false;
+    memset(info, 0, sizeof(*info));
+    for (const LayerShape& s : shapes) info->n_weights += (uint64_t)s.K * s.N + s.N + (s.bn ? 4ull * s.N : 0ull);
+    info->n_class = d.fc_widths[d.n_fc - 1];
+    info->c_last = sa_out[d.n_sa - 1];
+    uint64_t macs = 0, n = npts_hint;
+    size_t i = 0;
+    for (uint32_t l = 0; l < d.n_sa; l++) {
+        const pcr_pn2_msg_sa_desc& s = d.sa[l];
+        if (!s.group_all) info->n_sampling++;
+        for (uint32_t b = 0; b < s.n_branch; b++) {
+            uint64_t per_row = 0;
+            for (uint32_t k = 0; k < s.branch[b].n_mlp; k++, i++) per_row += (uint64_t)shapes[i].K * shapes[i].N;
+            macs += per_row * (s.group_all ? n : (uint64_t)s.npoint * s.branch[b].nsample);
+        }
+        n = s.group_all ? 1 : s.npoint;
+    }
+    for (; i < shapes.size(); i++) macs += (uint64_t)shapes[i].K * shapes[i].N;
+    info->macs_per_object = macs;
+    return true;
+}
+
+void model_info(const pcr_pn2_model* model, size_t npts_hint, pcr_pn2_info* info) { (void)desc_info(model->desc, npts_hint, info); }
+
+}  // namespace
+
 extern "C" int pcr_pn2_model_info(const pcr_pn2_model* model, size_t npts_hint, pcr_pn2_info* info, pcr_pn2_desc* desc)
 {
     if (!model) return PCR_ERR_ARG;
-    if (desc) *desc = model->desc;
-    if (info) {
-        memset(info, 0, sizeof(*info));
-        info->n_weights = model->n_weights;
-        info->n_sampling = model->n_sampling;
-        info->n_class = model->head.n_out();
-        info->c_last = model->sa[model->desc.n_sa - 1].n_out();
-        uint64_t macs = 0, n = npts_hint;
-        for (uint32_t l = 0; l < model->desc.n_sa; l++) {
-            const pcr_pn2_sa_desc& s = model->desc.sa[l];
-            uint64_t per_row = 0;
-            for (uint32_t k = 0; k < model->sa[l].n; k++) per_row += (uint64_t)model->sa[l].L[k].K * model->sa[l].L[k].N;
-            macs += per_row * (s.group_all ? n : (uint64_t)s.npoint * s.nsample);
-            n = s.group_all ? 1 : s.npoint;
-        }
-        for (uint32_t k = 0; k < model->head.n; k++) macs += (uint64_t)model->head.L[k].K * model->head.L[k].N;
-        info->macs_per_object = macs;
+    if (desc) {
+        if (!model->has_ssg) return PCR_ERR_ARG;      // several branches or features-first channels: only pcr_pn2_msg_desc holds them
+        *desc = model->ssg;
     }
+    if (info) model_info(model, npts_hint, info);
     return PCR_OK;
 }
 
-extern "C" int pcr_sa_mlp_max_f32(pcr_ctx* ctx, const pcr_pn2_model* model, int layer, const pcr_cloud* cloud, const uint32_t* seg_ptr, const pcr_cloud* centres,
-                                  const uint32_t* centre_seg_ptr, size_t n_seg, const float* features, const uint32_t* idx, float* out)
+extern "C" int pcr_pn2_msg_model_info(const pcr_pn2_model* model, size_t npts_hint, pcr_pn2_info* info, pcr_pn2_msg_desc* desc)
 {
-    if (!ctx || !model || !cloud || !seg_ptr) return fail(ctx, PCR_ERR_ARG, "pcr_sa_mlp_max_f32");
-    if (layer < 0 || (uint32_t)layer >= model->desc.n_sa) return fail(ctx, PCR_ERR_ARG, "pcr_sa_mlp_max_f32: no such SA layer");
-    if (model->device != ctx->device) return fail(ctx, PCR_ERR_ARG, "pcr_sa_mlp_max_f32: the model lives on another device");
-    const pcr_pn2_sa_desc& sd = model->desc.sa[layer];
-    const Chain& ch = model->sa[layer];
+    if (!model) {                            // no model: *desc is READ, info is what a model made from it would report (no device needed)
+        if (!desc || !info) return PCR_ERR_ARG;
+        return desc_info(*desc, npts_hint, info) ? PCR_OK : PCR_ERR_ARG;
+    }
+    if (desc) *desc = model->desc;
+    if (info) model_info(model, npts_hint, info);
+    return PCR_OK;
+}
+
+namespace {
+
+// one SA layer on the caller's indices.  msg: pcr_sa_msg_mlp_max_f32 (every branch, idx = the branches' row blocks, an all-N row is a group
+// without a hit); else pcr_sa_mlp_max_f32 (one branch, every index inside its segment)
+int sa_layer(pcr_ctx* ctx, const pcr_pn2_model* model, int layer, const pcr_cloud* cloud, const uint32_t* seg_ptr, const pcr_cloud* centres,
+             const uint32_t* centre_seg_ptr, size_t n_seg, const float* features, const uint32_t* idx, float* out, bool msg)
+{
+    const std::string who = msg ? "pcr_sa_msg_mlp_max_f32" : "pcr_sa_mlp_max_f32";
+    auto bad = [&](const char* what) { return fail(ctx, PCR_ERR_ARG, (who + what).c_str()); };
+    if (!ctx || !model || !cloud || !seg_ptr) return bad("");
+    if (layer < 0 || (uint32_t)layer >= model->desc.n_sa) return bad(": no such SA layer");
+    if (model->device != ctx->device) return bad(": the model lives on another device");
+    const pcr_pn2_msg_sa_desc& sd = model->desc.sa[layer];
+    const uint32_t nb = sd.n_branch;
+    if (!msg && nb != 1) return bad(": the layer has several branches (pcr_sa_msg_mlp_max_f32 runs them)");
     const bool ga = sd.group_all != 0;
-    const size_t D = model->sa_in[layer] - 3;
-    if (ga ? (centres || centre_seg_ptr || idx) : (!centres || !centre_seg_ptr)) return fail(ctx, PCR_ERR_ARG, "pcr_sa_mlp_max_f32: centres / centre_seg_ptr / idx go with a sampling layer only");
-    if (D > 0 && !features) return fail(ctx, PCR_ERR_ARG, "pcr_sa_mlp_max_f32: the layer takes features");
-    if (n_seg > PN2_MAX_ROWS || cloud->n > PN2_MAX_ROWS || (centres && centres->n > PN2_MAX_ROWS)) return fail(ctx, PCR_ERR_ARG, "pcr_sa_mlp_max_f32: too large");
-    if (!seg_ok(seg_ptr, n_seg, cloud->n) || (!ga && !seg_ok(centre_seg_ptr, n_seg, centres->n)))
-        return fail(ctx, PCR_ERR_ARG, "pcr_sa_mlp_max_f32: seg_ptr must ascend and end inside its cloud");
+    const size_t D = model->sa_in[layer] - 3, width = model->sa_out[layer];
+    if (ga ? (centres || centre_seg_ptr || idx) : (!centres || !centre_seg_ptr)) return bad(": centres / centre_seg_ptr / idx go with a sampling layer only");
+    if (D > 0 && !features) return bad(": the layer takes features");
+    if (n_seg > PN2_MAX_ROWS || cloud->n > PN2_MAX_ROWS || (centres && centres->n > PN2_MAX_ROWS)) return bad(": too large");
+    if (!seg_ok(seg_ptr, n_seg, cloud->n) || (!ga && !seg_ok(centre_seg_ptr, n_seg, centres->n))) return bad(": seg_ptr must ascend and end inside its cloud");
     if (n_seg == 0) return PCR_OK;
-    const size_t nsample = ga ? 1 : sd.nsample;
     const size_t q0 = ga ? 0 : centre_seg_ptr[0], nq = ga ? n_seg : centre_seg_ptr[n_seg] - q0;
     const size_t p0 = seg_ptr[0], np = seg_ptr[n_seg] - p0;
     if (nq == 0) return PCR_OK;
-    if (!out || (!ga && !idx)) return fail(ctx, PCR_ERR_ARG, "pcr_sa_mlp_max_f32: idx / out is NULL");
-    const unsigned long long rows = ga ? np : (unsigned long long)nq * nsample;
-    if (rows > PN2_MAX_ROWS || nq > PN2_MAX_ROWS / ch.n_out()) return fail(ctx, PCR_ERR_ARG, "pcr_sa_mlp_max_f32: too large");
-    std::vector<uint32_t> cs;
+    if (!out || (!ga && !idx)) return bad(": idx / out is NULL");
+    size_t row_total = 0;                                        // entries of idx per centre, over the branches
+    for (uint32_t b = 0; b < nb; b++) row_total += ga ? 0 : sd.branch[b].nsample;
+    if ((ga ? (unsigned long long)np : (unsigned long long)nq * row_total) > PN2_MAX_ROWS || nq > PN2_MAX_ROWS / width) return bad(": too large");
+    const bool compact = !ga && compact_rows(ctx, model->compact_default);
+    std::vector<uint32_t> cs, rp;                                // the segment of every centre; compacted: per branch the nq + 1 row offsets
     if (!ga) {
         cs.resize(centre_seg_ptr[n_seg]);
         for (size_t s = 0; s < n_seg; s++)
             for (uint32_t q = centre_seg_ptr[s]; q < centre_seg_ptr[s + 1]; q++) cs[q] = (uint32_t)s;
-        for (size_t q = 0; q < nq; q++) {
-            const uint32_t sg = cs[q0 + q], n = seg_ptr[sg + 1] - seg_ptr[sg];
-            for (size_t k = 0; k < nsample; k++)
-                if (idx[q * nsample + k] >= n) return fail(ctx, PCR_ERR_ARG, "pcr_sa_mlp_max_f32: an index lies outside its segment (an empty ball-query row?)");
+        if (compact) rp.resize((size_t)nb * (nq + 1));
+        size_t off = 0;
+        for (uint32_t b = 0; b < nb; b++) {
+            const size_t nsample = sd.branch[b].nsample;
+            uint32_t run = 0;
+            for (size_t q = 0; q < nq; q++) {
+                const uint32_t sg = cs[q0 + q], n = seg_ptr[sg + 1] - seg_ptr[sg];
+                const uint32_t* row = idx + off + q * nsample;
+                size_t inside = 0, last = 0;                     // entries inside the segment; the last entry that differs from the first
+                for (size_t k = 0; k < nsample; k++) {
+                    if (row[k] < n) inside++;
+                    else if (!msg || row[k] != n) return bad(": an index lies outside its segment (an empty ball-query row?)");
+                    if (row[k] != row[0]) last = k;
+                }
+                if (inside != 0 && inside != nsample) return bad(": an index lies outside its segment (an empty ball-query row?)");
+                if (compact) { rp[(size_t)b * (nq + 1) + q] = run; run += inside ? (uint32_t)(last + 1) : 0u; }
+            }
+            if (compact) rp[(size_t)b * (nq + 1) + nq] = run;
+            off += nq * nsample;
         }
     }
     PCR_HIP(ctx, hipSetDevice(ctx->device));
-    uint32_t *seg_dev, *cs_dev, *idx_dev;
+    uint32_t *seg_dev, *cs_dev, *idx_dev, *rp_dev;
     float *feat_dev, *out_dev;
     Layout L;
     L.add(&seg_dev, n_seg + 1);
     L.add(&cs_dev, cs.size());
-    L.add(&idx_dev, ga ? 0 : nq * nsample);
+    L.add(&idx_dev, nq * row_total);
+    L.add(&rp_dev, rp.size());
     L.add(&feat_dev, np * D);
-    L.add(&out_dev, nq * ch.n_out());
+    L.add(&out_dev, nq * width);
     int rc = bind_scratch(ctx, L);
     if (rc) return rc;
     PCR_HIP(ctx, hipMemcpyAsync(seg_dev, seg_ptr, (n_seg + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
     if (!ga) {
         PCR_HIP(ctx, hipMemcpyAsync(cs_dev, cs.data(), cs.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-        PCR_HIP(ctx, hipMemcpyAsync(idx_dev, idx, nq * nsample * 4, hipMemcpyHostToDevice, ctx->stream));
+        PCR_HIP(ctx, hipMemcpyAsync(idx_dev, idx, nq * row_total * 4, hipMemcpyHostToDevice, ctx->stream));
+        if (compact) PCR_HIP(ctx, hipMemcpyAsync(rp_dev, rp.data(), rp.size() * 4, hipMemcpyHostToDevice, ctx->stream));
     }
     if (D && np) PCR_HIP(ctx, hipMemcpyAsync(feat_dev, features + p0 * D, np * D * 4, hipMemcpyHostToDevice, ctx->stream));
     PCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ChainArgs a;
-    memset(&a, 0, sizeof(a));
-    a.x = cloud->x(); a.y = cloud->y(); a.z = cloud->z();
-    if (!ga) { a.qx = centres->x() + q0; a.qy = centres->y() + q0; a.qz = centres->z() + q0; a.centre_seg = cs_dev + q0; a.idx = idx_dev; }
-    a.seg_ptr = seg_dev;
-    a.feat = feat_dev - p0 * D;          // addressed by cloud position: moved back by the rows that were not uploaded (never dereferenced there)
-    a.out = out_dev;
-    a.rows = (uint32_t)rows;
-    a.D = (uint32_t)D; a.nsample = (uint32_t)nsample; a.n_seg = (uint32_t)n_seg; a.p0 = (uint32_t)p0;
-    a.mode = ga ? PN2_GROUP_ALL : PN2_GROUPED;
-    if (rows == 0) {
-        PCR_HIP(ctx, hipMemsetAsync(out_dev, 0, nq * ch.n_out() * 4, ctx->stream));
-    } else {
-        rc = chain_launch(ctx, ch, a, nq, "pn2_sa");
-        if (rc) return rc;
+    bool cleared = false;
+    size_t off = 0;
+    uint32_t col = 0;
+    for (uint32_t b = 0; b < nb; b++) {
+        const Chain& ch = model->sa[layer][b];
+        const size_t nsample = ga ? 1 : sd.branch[b].nsample;
+        const unsigned long long rows = ga ? np : (unsigned long long)nq * nsample;
+        ChainArgs a;
+        memset(&a, 0, sizeof(a));
+        a.x = cloud->x(); a.y = cloud->y(); a.z = cloud->z();
+        if (!ga) {
+            a.qx = centres->x() + q0; a.qy = centres->y() + q0; a.qz = centres->z() + q0; a.centre_seg = cs_dev + q0; a.idx = idx_dev + off;
+            if (compact) a.row_ptr = rp_dev + (size_t)b * (nq + 1);
+        }
+        a.seg_ptr = seg_dev;
+        a.feat = feat_dev - p0 * D;          // addressed by cloud position: moved back by the rows that were not uploaded (never dereferenced there)
+        a.out = out_dev;
+        a.out_stride = (uint32_t)width; a.out_col = col; a.xyz_last = sd.xyz_last;
+        a.rows = (uint32_t)rows;
+        a.D = (uint32_t)D; a.nsample = (uint32_t)nsample; a.n_seg = (uint32_t)n_seg; a.p0 = (uint32_t)p0;
+        a.mode = ga ? PN2_GROUP_ALL : PN2_GROUPED;
+        if (rows != 0) {
+            rc = chain_launch(ctx, ch, a, nq, "pn2_sa", !cleared);
+            if (rc) return rc;
+            cleared = true;
+        }
+        off += nq * nsample;
+        col += ch.n_out();
     }
-    PCR_HIP(ctx, hipMemcpyAsync(out, out_dev, nq * ch.n_out() * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (!cleared) PCR_HIP(ctx, hipMemsetAsync(out_dev, 0, nq * width * 4, ctx->stream));
+    PCR_HIP(ctx, hipMemcpyAsync(out, out_dev, nq * width * 4, hipMemcpyDeviceToHost, ctx->stream));
     PCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
     prof_flush(ctx);
     return PCR_OK;
+}
+
+}  // namespace
+
+extern "C" int pcr_sa_mlp_max_f32(pcr_ctx* ctx, const pcr_pn2_model* model, int layer, const pcr_cloud* cloud, const uint32_t* seg_ptr, const pcr_cloud* centres,
+                                  const uint32_t* centre_seg_ptr, size_t n_seg, const float* features, const uint32_t* idx, float* out)
+{
+    return sa_layer(ctx, model, layer, cloud, seg_ptr, centres, centre_seg_ptr, n_seg, features, idx, out, false);
+}
+
+extern "C" int pcr_sa_msg_mlp_max_f32(pcr_ctx* ctx, const pcr_pn2_model* model, int layer, const pcr_cloud* cloud, const uint32_t* seg_ptr, const pcr_cloud* centres,
+                                      const uint32_t* centre_seg_ptr, size_t n_seg, const float* features, const uint32_t* idx, float* out)
+{
+    return sa_layer(ctx, model, layer, cloud, seg_ptr, centres, centre_seg_ptr, n_seg, features, idx, out, true);
 }
 
 extern "C" int pcr_pn2_forward_f32(pcr_ctx* ctx, const pcr_pn2_model* model, const float* objects, size_t n_obj, size_t npts, const uint32_t* starts, uint64_t seed,
@@ -571,22 +793,25 @@ extern "C" int pcr_pn2_forward_f32(pcr_ctx* ctx, const pcr_pn2_model* model, con
 {
     if (!ctx || !model) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_forward_f32");
     if (model->device != ctx->device) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_forward_f32: the model lives on another device");
-    const pcr_pn2_desc& d = model->desc;
+    const pcr_pn2_msg_desc& d = model->desc;
     if (!d.sa[d.n_sa - 1].group_all) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_forward_f32: the last SA layer must be group_all");
     if (npts < 1) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_forward_f32: npts must be >= 1");
     if (n_obj == 0) return PCR_OK;
     if (!objects || !logp) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_forward_f32: objects / logp is NULL");
     const uint32_t ns = model->n_sampling, D0 = d.D0, C0 = 3 + D0;
-    const uint32_t n_class = model->head.n_out(), c_last = model->sa[d.n_sa - 1].n_out();
+    const uint32_t n_class = model->head.n_out(), c_last = model->sa_out[d.n_sa - 1];
+    const bool compact = compact_rows(ctx, model->compact_default);
     // ---- sizes of every stage
     if (n_obj > PN2_MAX_ROWS || npts > PN2_MAX_ROWS || (unsigned long long)n_obj * npts > PN2_MAX_ROWS / C0) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_forward_f32: too large");
     size_t N[PCR_PN2_MAX_SA + 1];
     N[0] = npts;
     for (uint32_t l = 0; l < ns; l++) {
-        const pcr_pn2_sa_desc& s = d.sa[l];
+        const pcr_pn2_msg_sa_desc& s = d.sa[l];
         N[l + 1] = s.npoint;
         const unsigned long long nq = (unsigned long long)n_obj * s.npoint;
-        if (nq > PN2_MAX_ROWS / s.nsample || nq > PN2_MAX_ROWS / model->sa[l].n_out()) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_forward_f32: too large");
+        unsigned long long row_total = 0;
+        for (uint32_t b = 0; b < s.n_branch; b++) row_total += s.branch[b].nsample;
+        if (nq > PN2_MAX_ROWS / row_total || nq > PN2_MAX_ROWS / model->sa_out[l]) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_forward_f32: too large");
     }
     if ((unsigned long long)n_obj * std::max<uint32_t>(c_last, n_class) > PN2_MAX_ROWS) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_forward_f32: too large");
     std::vector<uint32_t> st((size_t)ns * n_obj);
@@ -608,7 +833,7 @@ extern "C" int pcr_pn2_forward_f32(pcr_ctx* ctx, const pcr_pn2_model* model, con
     int32_t* pred_dev;
     uint32_t* seg[PCR_PN2_MAX_SA + 1];          // the segments of cloud l: n_obj + 1 offsets
     uint32_t* cseg[PCR_PN2_MAX_SA];             // the segment of every centre of sampling layer l
-    uint32_t *fps[PCR_PN2_MAX_SA], *bidx[PCR_PN2_MAX_SA], *bcnt[PCR_PN2_MAX_SA];
+    uint32_t *fps[PCR_PN2_MAX_SA], *bidx[PCR_PN2_MAX_SA][PCR_PN2_MAX_BRANCH], *bcnt[PCR_PN2_MAX_SA], *brp[PCR_PN2_MAX_SA];      // bcnt: n_branch x nq, brp: n_branch x (nq + 1)
     float *cxyz[PCR_PN2_MAX_SA], *sa_out[PCR_PN2_MAX_SA];
     Carve cv;
     cv.add(&x0, 3 * P);
@@ -620,9 +845,10 @@ extern "C" int pcr_pn2_forward_f32(pcr_ctx* ctx, const pcr_pn2_model* model, con
         const size_t nq = n_obj * N[l + 1];
         cv.add(&fps[l], nq);
         cv.add(&cxyz[l], 3 * nq);
-        cv.add(&bidx[l], nq * d.sa[l].nsample);
-        cv.add(&bcnt[l], nq);
-        cv.add(&sa_out[l], nq * model->sa[l].n_out());
+        for (uint32_t b = 0; b < d.sa[l].n_branch; b++) cv.add(&bidx[l][b], nq * d.sa[l].branch[b].nsample);
+        cv.add(&bcnt[l], nq * d.sa[l].n_branch);
+        cv.add(&brp[l], compact ? (nq + 1) * d.sa[l].n_branch : 0);
+        cv.add(&sa_out[l], nq * model->sa_out[l]);
     }
     cv.add(&ga_out, n_obj * c_last);
     cv.add(&logits, n_obj * n_class);
@@ -654,7 +880,7 @@ extern "C" int pcr_pn2_forward_f32(pcr_ctx* ctx, const pcr_pn2_model* model, con
     const float *cx = x0, *cy = x0 + P, *cz = x0 + 2 * P, *feat = feat0;
     uint32_t D = D0;
     for (uint32_t l = 0; l < ns; l++) {
-        const pcr_pn2_sa_desc& s = d.sa[l];
+        const pcr_pn2_msg_sa_desc& s = d.sa[l];
         const size_t nq = n_obj * N[l + 1];
         std::vector<FpsJob> jobs(n_obj);
         for (size_t o = 0; o < n_obj; o++) jobs[o] = { (uint32_t)(o * N[l]), (uint32_t)N[l], st[(size_t)l * n_obj + o], (uint32_t)o };
@@ -666,26 +892,43 @@ extern "C" int pcr_pn2_forward_f32(pcr_ctx* ctx, const pcr_pn2_model* model, con
             hipLaunchKernelGGL(pn2_centres_kernel, dim3((unsigned)((nq + PN2_BLOCK - 1) / PN2_BLOCK)), dim3(PN2_BLOCK), 0, ctx->stream, cx, cy, cz, fps[l], (uint32_t)N[l],
                                s.npoint, (uint32_t)nq, qx, qy, qz);
         }
-        rc = ball_query_device(ctx, cx, cy, cz, qx, qy, qz, seg[l], cseg[l], nq, s.radius, s.nsample, bidx[l], bcnt[l]);
+        if (s.n_branch == 1) {
+            rc = ball_query_device(ctx, cx, cy, cz, qx, qy, qz, seg[l], cseg[l], nq, s.branch[0].radius, s.branch[0].nsample, bidx[l][0], bcnt[l]);
+        } else {                                 // every radius in one walk of the object
+            double radii[PCR_PN2_MAX_BRANCH];
+            uint32_t nsamples[PCR_PN2_MAX_BRANCH], *cb[PCR_PN2_MAX_BRANCH];
+            for (uint32_t b = 0; b < s.n_branch; b++) { radii[b] = s.branch[b].radius; nsamples[b] = s.branch[b].nsample; cb[b] = bcnt[l] + (size_t)b * nq; }
+            rc = ball_query_multi_device(ctx, cx, cy, cz, qx, qy, qz, seg[l], cseg[l], nq, s.n_branch, radii, nsamples, bidx[l], cb);
+        }
         if (rc) break;
-        ChainArgs a;
-        memset(&a, 0, sizeof(a));
-        a.x = cx; a.y = cy; a.z = cz; a.qx = qx; a.qy = qy; a.qz = qz;
-        a.seg_ptr = seg[l]; a.centre_seg = cseg[l]; a.idx = bidx[l]; a.feat = feat; a.out = sa_out[l];
-        a.rows = (uint32_t)(nq * s.nsample);
-        a.D = D; a.nsample = s.nsample; a.n_seg = (uint32_t)n_obj; a.mode = PN2_GROUPED;
-        rc = chain_launch(ctx, model->sa[l], a, nq, "pn2_sa");
+        if (compact) {                           // the row offsets of every branch: one launch
+            rc = scan_launch(ctx, bcnt[l], nq, s.n_branch, brp[l]);
+            if (rc) break;
+        }
+        uint32_t col = 0;
+        for (uint32_t b = 0; b < s.n_branch && rc == PCR_OK; b++) {      // one chain per branch into its columns; the rows are cleared once
+            ChainArgs a;
+            memset(&a, 0, sizeof(a));
+            a.x = cx; a.y = cy; a.z = cz; a.qx = qx; a.qy = qy; a.qz = qz;
+            a.seg_ptr = seg[l]; a.centre_seg = cseg[l]; a.idx = bidx[l][b]; a.feat = feat; a.out = sa_out[l];
+            if (compact) a.row_ptr = brp[l] + (size_t)b * (nq + 1);
+            a.out_stride = model->sa_out[l]; a.out_col = col; a.xyz_last = s.xyz_last;
+            a.rows = (uint32_t)(nq * s.branch[b].nsample);
+            a.D = D; a.nsample = s.branch[b].nsample; a.n_seg = (uint32_t)n_obj; a.mode = PN2_GROUPED;
+            rc = chain_launch(ctx, model->sa[l][b], a, nq, "pn2_sa", b == 0);
+            col += model->sa[l][b].n_out();
+        }
         if (rc) break;
         cx = qx; cy = qy; cz = qz; feat = sa_out[l];
-        D = model->sa[l].n_out();
+        D = model->sa_out[l];
     }
     if (rc == PCR_OK) {                      // the group_all layer, then the head on its rows
         ChainArgs a;
         memset(&a, 0, sizeof(a));
         a.x = cx; a.y = cy; a.z = cz; a.seg_ptr = seg[ns]; a.feat = feat; a.out = ga_out;
         a.rows = (uint32_t)(n_obj * N[ns]);
-        a.D = D; a.nsample = 1; a.n_seg = (uint32_t)n_obj; a.mode = PN2_GROUP_ALL;
-        rc = chain_launch(ctx, model->sa[ns], a, n_obj, "pn2_sa");
+        a.D = D; a.nsample = 1; a.n_seg = (uint32_t)n_obj; a.mode = PN2_GROUP_ALL; a.xyz_last = d.sa[ns].xyz_last;
+        rc = chain_launch(ctx, model->sa[ns][0], a, n_obj, "pn2_sa");
     }
     if (rc == PCR_OK) {
         ChainArgs a;

@@ -6,6 +6,8 @@ Mirrors (same names, argument order and return shapes):
   index_points            HomeworkFinal/models/pointnet_util.py:46-63     (host indexing: it is a gather of a few KB)
   sample_and_group        HomeworkFinal/models/pointnet_util.py:119-156   (GPU: the three operators, one fused gather)
   get_model               HomeworkFinal/models/pointnet2_cls_ssg.py           (GPU: pcr_pn2_forward_f32, eval mode only)
+  get_model_msg           HomeworkFinal/models/pointnet2_cls_msg.py           (GPU: the same call on a multi-scale model, eval mode only)
+  MODELS                  the two by the module name train_cls.py --model / test_cls.py import
   classify_foreground_objects   the flow of HomeworkFinal/foreground_obj_cls.py:97-188: up to the classifier's input, or with
                           classifier= through it to pred_final
 
@@ -143,6 +145,8 @@ class get_model:
     first FPS pick of both sampling layers ([2, B]; None draws them from np.random as the reference draws them unseeded), ctx= the context.
     Training is out of scope: train() raises."""
 
+    _npoint1 = _SSG_SA[0][1]          # the size of the second sampling layer's cloud
+
     def __init__(self, num_class, normal_channel=False):
         self.num_class, self.normal_channel = int(num_class), bool(normal_channel)
         self.training = True
@@ -192,8 +196,18 @@ class get_model:
         self._drop()
         return self
 
+    def state_shapes(self):
+        """key -> shape of every entry load_state_dict takes, as the reference's state_dict() has them (Conv2d weights [out, in, 1, 1])"""
+        out = {}
+        for conv, bn, w, cin in self._layers():
+            out[f"{conv}.weight"] = (w, cin, 1, 1) if conv.startswith("sa") else (w, cin)
+            out[f"{conv}.bias"] = (w,)
+            for k in (_BN_KEYS if bn else ()):
+                out[f"{bn}.{k}"] = (w,)
+        return out
+
     def flat_weights(self):
-        """the flat f32 array pcr_pn2_model_create takes"""
+        """the flat f32 array pcr_pn2_model_create / pcr_pn2_msg_model_create takes"""
         if self._state is None:
             raise RuntimeError("no weights: call load_state_dict first (the reference ships no checkpoint)")
         parts = []
@@ -222,8 +236,11 @@ class get_model:
         ctx = _ctx(ctx)
         if self._model is None or self._model_ctx is not ctx or not self._model.h:
             self._drop()
-            self._model, self._model_ctx = ctx.pn2_model(self.desc(), self.flat_weights()), ctx
+            self._model, self._model_ctx = self._upload(ctx), ctx
         return self._model
+
+    def _upload(self, ctx):
+        return ctx.pn2_model(self.desc(), self.flat_weights())
 
     def forward(self, xyz, *, start=None, seed=None, ctx=None, return_all=False):
         if self.training:
@@ -235,13 +252,67 @@ class get_model:
         B, N = x.shape[0], x.shape[2]
         st, _ = _to_host(start)
         if st is None and seed is None:
-            st = np.stack([np.random.randint(0, N, size=B), np.random.randint(0, _SSG_SA[0][1], size=B)])
+            st = np.stack([np.random.randint(0, N, size=B), np.random.randint(0, self._npoint1, size=B)])
         ctx = _ctx(ctx)
         res = ctx.pn2_forward(self.model(ctx), np.ascontiguousarray(np.transpose(x, (0, 2, 1)), np.float32), st, 0 if seed is None else seed, return_all=True)
         out = _like(res["logp"], proto), _like(res["global_feat"][:, :, None], proto)
         return out + (res,) if return_all else out
 
     __call__ = forward
+
+
+# the reference's layers (pointnet2_cls_msg.py:11-15): name, npoint, radii, nsamples, one list of widths per radius
+_MSG_SA = (("sa1", 512, (0.1, 0.2, 0.4), (16, 32, 128), ((32, 32, 64), (64, 64, 128), (64, 96, 128))),
+           ("sa2", 128, (0.2, 0.4, 0.8), (32, 64, 128), ((64, 64, 128), (128, 128, 256), (128, 128, 256))))
+_MSG_SA3 = (256, 512, 1024)
+
+
+class get_model_msg(get_model):
+    """models/pointnet2_cls_msg.get_model in eval mode on the library: the same constructor arguments (normal_channel defaults to True, as
+    there), state-dict keys (sa1.conv_blocks.{i}.{j}.*, sa1.bn_blocks.{i}.{j}.*, sa3.mlp_convs.{j}.*, fc1 / bn1 ...) and call.  sa1 and sa2
+    are PointNetSetAbstractionMsg layers — three radii over one set of centres, input channels (features | xyz - centre) — and sa3 is the
+    group_all PointNetSetAbstraction (xyz first).  Everything else is get_model's: load_state_dict, eval, train() raising, and
+    __call__(xyz [B, 3 or 6, N], start=, seed=, ctx=, return_all=) -> (log_probs, l3_points [B, 1024, 1])."""
+
+    _npoint1 = _MSG_SA[0][1]
+
+    def __init__(self, num_class, normal_channel=True):
+        super().__init__(num_class, normal_channel)
+
+    def _layers(self):
+        out, last = [], 3 if self.normal_channel else 0
+        for name, _, _, _, mlps in _MSG_SA:
+            width = 0
+            for i, mlp in enumerate(mlps):
+                cin = last + 3
+                for j, w in enumerate(mlp):
+                    out.append((f"{name}.conv_blocks.{i}.{j}", f"{name}.bn_blocks.{i}.{j}", w, cin))
+                    cin = w
+                width += cin
+            last = width
+        cin = last + 3
+        for j, w in enumerate(_MSG_SA3):
+            out.append((f"sa3.mlp_convs.{j}", f"sa3.mlp_bns.{j}", w, cin))
+            cin = w
+        for fc, bn, w in _SSG_FC:
+            w = self.num_class if w is None else w
+            out.append((fc, bn, w, cin))
+            cin = w
+        return out
+
+    def desc(self):
+        from . import pn2_msg_desc
+        sa = [dict(npoint=npoint, xyz_last=True, branches=[dict(radius=r, nsample=k, mlp=mlp) for r, k, mlp in zip(radii, nsamples, mlps)])
+              for _, npoint, radii, nsamples, mlps in _MSG_SA]
+        sa.append(dict(group_all=True, mlp=_MSG_SA3))
+        return pn2_msg_desc(sa, [512, 256, self.num_class], D0=3 if self.normal_channel else 0, bn_eps=1e-5)
+
+    def _upload(self, ctx):
+        return ctx.pn2_msg_model(self.desc(), self.flat_weights())
+
+
+# the classifiers by the reference's module name (train_cls.py --model, test_cls.py)
+MODELS = {"pointnet2_cls_ssg": get_model, "pointnet2_cls_msg": get_model_msg}
 
 
 def classify_foreground_objects(points, npoints=256, eps=0.5, min_points=8, z_min_above_ground=0.5, z_extent=(1.0, 2.3), seed=0, *, ctx=None,
@@ -251,7 +322,7 @@ def classify_foreground_objects(points, npoints=256, eps=0.5, min_points=8, z_mi
     Without a classifier (the reference ships no weights) returns (objects f32 [n_obj, npoints, 3], codes i32 [n_clusters]: 3 where the
     reference writes 3, -1 = to be classified) and a dict with everything in between (points, ground / foreground indices, ground_z,
     labels, n_clusters, and the outputs of Context.objects_from_labels).
-    With classifier= (a get_model in eval mode) every object goes through it in ONE batched forward pass (the first FPS picks drawn from
+    With classifier= (a get_model or get_model_msg in eval mode) every object goes through it in ONE batched forward pass (the first FPS picks drawn from
     `seed`) and the second value is pred_final as the reference builds it (:152-188): i32 [n_clusters], 3 where it writes 3, the predicted
     class elsewhere; the dict then also holds log_probs [n_obj, num_class]."""
     from . import hw4

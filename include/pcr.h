@@ -655,6 +655,71 @@ int pcr_sa_mlp_max_f32(pcr_ctx* ctx, const pcr_pn2_model* model, int layer, cons
 int pcr_pn2_forward_f32(pcr_ctx* ctx, const pcr_pn2_model* model, const float* objects, size_t n_obj, size_t npts, const uint32_t* starts, uint64_t seed,
                         float* logp, int32_t* pred, float* global_feat, uint32_t* fps_idx);
 
+/* ---- HomeworkFinal: the multi-scale (MSG) classifier, models/pointnet2_cls_msg.py + pointnet_util.py:223-281, eval mode -----------
+ * pcr_pn2_msg_desc is a superset of pcr_pn2_desc.  An SA layer has npoint, group_all, xyz_last and n_branch in 1 ... 4 BRANCHES over ONE set of
+ * centres; a branch has its own radius, nsample and n_mlp in 1 ... 4 widths.  The branches' outputs are concatenated in branch order
+ * (torch.cat(new_points_list, dim=1), :279): the width of the layer is the sum of its branches' last widths, at most 1024, and it is the D of
+ * the next layer.
+ *   xyz_last   0: the input channels of the layer are (xyz - centre | features), as PointNetSetAbstraction has them (:150);
+ *              1: (features | xyz - centre), as PointNetSetAbstractionMsg has them (:266).  With D == 0 the two are the same.
+ *   group_all  only on the last layer, with ONE branch whose radius and nsample are ignored (the reference's sa3 is a PointNetSetAbstraction:
+ *              xyz first; xyz_last is honoured there too).
+ * weights: layer by layer, branch by branch, convolution by convolution, then the FC layers; every convolution laid out as for
+ *   pcr_pn2_model_create (W, bias, gamma, beta, running_mean, running_var).  The fold and the arithmetic are the ones written there: one f32 fma
+ *   chain per output over ascending input channel IN THE LAYER'S OWN CHANNEL ORDER, starting from the folded bias.
+ * pcr_pn2_msg_model_create returns the same handle type.  On it pcr_pn2_model_destroy, pcr_pn2_forward_f32 (the same arguments: starts stays
+ *   n_sampling x n_obj, one set of centres per layer) and pcr_pn2_model_info work as on any model; pcr_pn2_model_info returns PCR_ERR_ARG when it
+ *   is asked for a pcr_pn2_desc and the model has a layer with several branches or with xyz_last; pcr_pn2_msg_model_info returns the descriptor
+ *   of EVERY model; with model == NULL it READS *desc and fills info with what a model made from it would report (no device is needed;
+ *   PCR_ERR_ARG for a descriptor outside the limits).  pcr_sa_mlp_max_f32 returns PCR_ERR_ARG on a layer with more than one branch.
+ *   Per layer with several branches the forward pass is: FPS, centres, ONE multi-radius ball query, one scan of all branches' counts, one clear
+ *   of the concatenated rows, one chain launch per branch (each writes its own columns).  Profile names ball_query_multi, pn2_scan.
+ *
+ * Tune key pn2_compact [-1 = the model's default] 0: a chain runs every row of the padded groups, npoint x nsample; 1: it runs the real hits
+ *   only — the copies of the first hit that fill a ball-query row are skipped: tile row g maps to (group, member) through the exclusive scan of
+ *   the counts.  The max over a group does not change when copies are dropped, so results NEVER depend on the key.  The launch is sized for the
+ *   padded rows and tiles past the total return at once: the host does not wait to learn the total.  Default: 1 for models of
+ *   pcr_pn2_msg_model_create, 0 for models of pcr_pn2_model_create.
+ *
+ * pcr_ball_query_multi_f32 — n_radii in 1 ... 4 radii per centre in ONE walk of the segment (one wave per centre, one distance per point,
+ *   one ballot per radius; the walk stops when every row is full).  Every radius follows the rule of pcr_ball_query_f32 exactly, with its own
+ *   nsample: idx and counts are equal on every element to pcr_ball_query_f32 called once per radius.  idx: the row blocks one after the other,
+ *   block b = (number of centres) x nsamples[b]; counts (optional): n_radii x (number of centres).  PCR_ERR_ARG as pcr_ball_query_f32, and for
+ *   n_radii outside 1 ... 4 or NULL radii / nsamples.  Profile name ball_query_multi.
+ *
+ * pcr_sa_msg_mlp_max_f32 — ONE SA layer of a model on the caller's indices: the arguments of pcr_sa_mlp_max_f32, with idx holding the branches'
+ *   row blocks one after the other (block b = centres x nsample_b) and out = centres x (the layer's concatenated width).  A row that holds the
+ *   segment's size in EVERY entry (pcr_ball_query_f32's empty row) is a group without a hit: its columns of that branch stay zero; any other
+ *   index outside its segment is PCR_ERR_ARG.  Under pn2_compact 1 the trailing entries of a row that repeat its first entry are not run. */
+#define PCR_PN2_MAX_BRANCH 4
+typedef struct pcr_pn2_branch_desc {
+    double radius;       /* ignored for group_all */
+    uint32_t nsample;    /* ignored for group_all */
+    uint32_t n_mlp;
+    uint32_t widths[PCR_PN2_MAX_MLP];
+} pcr_pn2_branch_desc;
+typedef struct pcr_pn2_msg_sa_desc {
+    uint32_t npoint;     /* ignored for group_all */
+    uint32_t group_all;
+    uint32_t xyz_last;
+    uint32_t n_branch;
+    pcr_pn2_branch_desc branch[PCR_PN2_MAX_BRANCH];
+} pcr_pn2_msg_sa_desc;
+typedef struct pcr_pn2_msg_desc {
+    uint32_t D0;
+    uint32_t n_sa;
+    pcr_pn2_msg_sa_desc sa[PCR_PN2_MAX_SA];
+    uint32_t n_fc;
+    uint32_t fc_widths[PCR_PN2_MAX_FC];
+    double bn_eps;
+} pcr_pn2_msg_desc;
+int pcr_pn2_msg_model_create(pcr_ctx* ctx, const pcr_pn2_msg_desc* desc, const float* weights, size_t n_weights, pcr_pn2_model** out);
+int pcr_pn2_msg_model_info(const pcr_pn2_model* model, size_t npts_hint, pcr_pn2_info* info, pcr_pn2_msg_desc* desc);
+int pcr_ball_query_multi_f32(pcr_ctx* ctx, const pcr_cloud* cloud, const uint32_t* seg_ptr, const pcr_cloud* centres, const uint32_t* centre_seg_ptr,
+                             size_t n_seg, size_t n_radii, const double* radii, const size_t* nsamples, uint32_t* idx, uint32_t* counts);
+int pcr_sa_msg_mlp_max_f32(pcr_ctx* ctx, const pcr_pn2_model* model, int layer, const pcr_cloud* cloud, const uint32_t* seg_ptr, const pcr_cloud* centres,
+                           const uint32_t* centre_seg_ptr, size_t n_seg, const float* features, const uint32_t* idx, float* out);
+
 /* ---- next row N4: global-registration front half, Homework9/hw9/src/registration.cpp:288-434, :535-615 -----------
  * N4a: exhaustive 1-NN between two descriptor sets (row-major n x dim / m x dim f32, host memory; dim 33 = FPFH),
  * nanoflann's evalMetric arithmetic for any dim (nanoflann.hpp:382-405: groups of four + tail, f32, unfused), canonical
