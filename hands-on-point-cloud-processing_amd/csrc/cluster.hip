@@ -4,8 +4,8 @@
 //
 // Arithmetic of both = pcr_cloud_knn_f64: s = ((dx*dx) + dy*dy) + dz*dz on the f32 coordinates widened to f64, unfused.
 //
-// DBSCAN — five passes over the uniform grid of grid_common.hpp with cell edge >= eps, so that N(p) lies in the 27-cell block
-// of p's cell.  As in iss.hip the cloud is searched against itself: query p IS grid record p, G lanes share one query and
+// DBSCAN — five passes over the uniform grid with cell edge >= eps, so that N(p) lies in the 27-cell block of p's cell (the
+// walk: grid_walk.hpp).  The cloud is searched against itself: query p IS grid record p, G lanes share one query and
 // stride over each x-row, long rows are clipped to the x window of the query.  No neighbour list is ever stored: O(n) memory.
 //   count   cnt[p] = |N(p)| (p included), core[p] = finite && cnt >= min_points
 //   union   every core record p unions itself with each core neighbour j < p (record numbering: lock-free union-find, below)
@@ -24,7 +24,7 @@
 // SOR — the existing grid k-NN (knn_grid.hip, squared, self included), then per point avg = sum of sqrt over the found slots
 // in slot order / found (-1 without a neighbour); the two global sums in a fixed order (a fixed number of workgroups for a
 // given n, each a fixed strided sequence + a shuffle tree), mask, exclusive scan, gather into a new device cloud.
-#include "grid_common.hpp"
+#include "grid_walk.hpp"
 #include "union_find.hpp"
 
 #include <cfloat>
@@ -45,68 +45,6 @@ __device__ __forceinline__ double cl_s(const float4& t, double qx, double qy, do
     return (dx * dx + dy * dy) + dz * dz;
 }
 
-// the 9 x-rows of the 27-cell block around cell (cx, cy, cz): row k -> [begin, end) in records
-__device__ __forceinline__ void cl_row_range(const GridParams& g, const uint32_t* __restrict__ cell_start, int cx, int cy, int cz, int k,
-                                             uint32_t& b, uint32_t& e)
-{
-    const int yy = cy + (k % 3) - 1, zz = cz + (k / 3) - 1;
-    if (yy < 0 || yy >= g.n[1] || zz < 0 || zz >= g.n[2]) { b = e = 0; return; }
-    const int x0 = max(cx - 1, 0), x1 = min(cx + 1, g.n[0] - 1);
-    const uint32_t row = (uint32_t)((zz * g.n[1] + yy) * g.n[0]);
-    b = cell_start[row + x0];
-    e = cell_start[row + x1 + 1];
-}
-
-// rows are sorted by x: cut a long [b, e) to lo <= x <= hi by two bounded binary searches (uniform over a lane group)
-__device__ __forceinline__ void cl_clip_row_x(const float4* __restrict__ records, uint32_t& b, uint32_t& e, float lo, float hi)
-{
-    if (e - b <= 384u) return;
-    uint32_t l = b, h = e;
-    for (int it = 0; it < 32 && l < h; it++) {
-        const uint32_t mid = l + ((h - l) >> 1);
-        if (records[mid].x < lo) l = mid + 1; else h = mid;
-    }
-    const uint32_t nb = l;
-    h = e;
-    for (int it = 0; it < 32 && l < h; it++) {
-        const uint32_t mid = l + ((h - l) >> 1);
-        if (records[mid].x <= hi) l = mid + 1; else h = mid;
-    }
-    b = nb;
-    e = l;
-}
-
-// [lo, hi] holds every x whose f64 sum can still be <= eps2: |dx| > sqrt(eps2) (1 + 1e-5) gives dx*dx > eps2; the pad covers
-// the rounding of qx -+ d to f32
-__device__ __forceinline__ void cl_window(float qx, double eps2, float& lo, float& hi)
-{
-    const double d = sqrt(eps2) * 1.00001 + 1e-30, q = qx;
-    lo = (float)((q - d) - (fabs(q) + d) * 2.4e-7);
-    hi = (float)((q + d) + (fabs(q) + d) * 2.4e-7);
-}
-
-__device__ __forceinline__ void cl_query_cell(const GridParams& g, const float4& q, int& cx, int& cy, int& cz)
-{
-    cx = min(max(cell_coord(q.x, g.lo[0], g.inv_h), 0), g.n[0] - 1);
-    cy = min(max(cell_coord(q.y, g.lo[1], g.inv_h), 0), g.n[1] - 1);
-    cz = min(max(cell_coord(q.z, g.lo[2], g.inv_h), 0), g.n[2] - 1);
-}
-
-template <int G>
-__device__ __forceinline__ unsigned cl_group_sum(unsigned v)
-{
-#pragma unroll
-    for (int o = G / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, G);
-    return v;
-}
-template <int G>
-__device__ __forceinline__ unsigned cl_group_min(unsigned v)
-{
-#pragma unroll
-    for (int o = G / 2; o > 0; o >>= 1) v = min(v, (unsigned)__shfl_xor(v, o, G));
-    return v;
-}
-
 // ---------------------------------------------------------------------------------------- DBSCAN
 template <int G>
 __global__ __launch_bounds__(CL_BLOCK) void db_count_kernel(const float4* __restrict__ records, const uint32_t* __restrict__ cell_start, GridParams g,
@@ -122,18 +60,14 @@ __global__ __launch_bounds__(CL_BLOCK) void db_count_kernel(const float4* __rest
     unsigned c = 0;
     if (fin) {
         const double qx = q.x, qy = q.y, qz = q.z;
-        int cx, cy, cz;
-        cl_query_cell(g, q, cx, cy, cz);
-        float wlo, whi;
-        cl_window(q.x, eps2, wlo, whi);
+        const RadiusWalk walk(g, cell_start, records, query_cell(g, q), x_window_f64(q.x, eps2));
         for (int k = 0; k < 9; k++) {
             uint32_t b, e;
-            cl_row_range(g, cell_start, cx, cy, cz, k, b, e);
-            cl_clip_row_x(records, b, e, wlo, whi);
+            walk.row<384>(k, b, e);
             for (uint32_t j = b + sub; j < e; j += G) c += cl_s(records[j], qx, qy, qz) <= eps2;
         }
     }
-    c = cl_group_sum<G>(c);
+    c = group_sum<G>(c);
     if (sub == 0) {
         const uint8_t core = (fin && (long long)c >= (long long)min_points) ? 1 : 0;
         const uint32_t orig = __float_as_uint(q.w);
@@ -164,17 +98,14 @@ __global__ __launch_bounds__(CL_BLOCK) void db_union_kernel(const float4* __rest
     if (!core_sorted[p]) return;                            // uniform over the group; core implies finite
     const float4 q = records[p];
     const double qx = q.x, qy = q.y, qz = q.z;
-    int cx, cy, cz;
-    cl_query_cell(g, q, cx, cy, cz);
-    float wlo, whi;
-    cl_window(q.x, eps2, wlo, whi);
+    const RadiusWalk walk(g, cell_start, records, query_cell(g, q), x_window_f64(q.x, eps2));
     uint32_t rp = p;                                        // an ancestor of p (refreshed by every find)
     for (int k = 0; k < 9; k++) {
         uint32_t b, e;
-        cl_row_range(g, cell_start, cx, cy, cz, k, b, e);
+        walk.range(k, b, e);
         e = min(e, p);                                      // each pair once: the larger record links
         if (b >= e) continue;
-        cl_clip_row_x(records, b, e, wlo, whi);
+        walk.clip<384>(b, e);
         for (uint32_t j = b + sub; j < e; j += G) {
             if (!core_sorted[j] || !(cl_s(records[j], qx, qy, qz) <= eps2)) continue;
             rp = uf_find(parent, rp, n, err);
@@ -211,19 +142,15 @@ __global__ __launch_bounds__(CL_BLOCK) void db_border_kernel(const float4* __res
     if (!core_sorted[p] && cnt_sorted[p] >= 2) {            // uniform over the group; a count implies finite
         const float4 q = records[p];
         const double qx = q.x, qy = q.y, qz = q.z;
-        int cx, cy, cz;
-        cl_query_cell(g, q, cx, cy, cz);
-        float wlo, whi;
-        cl_window(q.x, eps2, wlo, whi);
+        const RadiusWalk walk(g, cell_start, records, query_cell(g, q), x_window_f64(q.x, eps2));
         for (int k = 0; k < 9; k++) {
             uint32_t b, e;
-            cl_row_range(g, cell_start, cx, cy, cz, k, b, e);
-            cl_clip_row_x(records, b, e, wlo, whi);
+            walk.row<384>(k, b, e);
             for (uint32_t j = b + sub; j < e; j += G)
                 if (core_sorted[j] && cl_s(records[j], qx, qy, qz) <= eps2) m = min(m, key[root[j]]);
         }
     }
-    m = cl_group_min<G>(m);
+    m = group_min<G>(m);
     if (sub == 0) bkey[p] = m;
 }
 
@@ -372,10 +299,8 @@ extern "C" int pcr_dbscan_f32(pcr_ctx* ctx, const pcr_cloud* cloud, double eps, 
     const double eps2 = eps * eps;
     Grid* g = nullptr;
     {
-        // cell edge >= eps with a margin for the rounding of the cell coordinate: N(p) lies in the 27-cell block (grid_build may
-        // only enlarge the cell); >= 2e-15 keeps the cell count bounded for eps -> 0 (a point outside the block then has s >= h^2 > eps2)
         ProfScope ps(ctx, "dbscan_grid", 1);
-        int rc = grid_build(ctx, cloud, &g, std::max(eps * 1.01, 2e-15));
+        int rc = grid_build(ctx, cloud, &g, radius_cell_edge(eps));
         if (rc) return rc;
     }
     const GridPtr g_owner(g);
@@ -402,7 +327,7 @@ extern "C" int pcr_dbscan_f32(pcr_ctx* ctx, const pcr_cloud* cloud, double eps, 
     if (rc) return rc;
     const dim3 grid1((unsigned)((n + CL_BLOCK - 1) / CL_BLOCK));
     hipError_t e = hipMemsetAsync(err, 0, 4, ctx->stream);
-    const int G = (int)tune_get(ctx, "dbscan_lanes", 32);    // lanes per query, as iss_lanes
+    const int G = (int)tune_get(ctx, "dbscan_lanes", 32);    // lanes per query
 #define PCR_DB(GG)                                                                                                                     \
     {                                                                                                                                  \
         const dim3 gridg((unsigned)((n * GG + CL_BLOCK - 1) / CL_BLOCK));                                                              \

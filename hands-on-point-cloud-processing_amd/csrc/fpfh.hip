@@ -1,8 +1,8 @@
 // fpfh.hip — FPFH33 descriptors (Homework9/hw9/src/registration.cpp:254-269, PCL's FPFHEstimationOMP) as two radius passes over the
-// uniform grid of grid_common.hpp.  The contract (neighbourhood, pair features, bins, weighting) is written out above
+// uniform grid (the walk: grid_walk.hpp).  The contract (neighbourhood, pair features, bins, weighting) is written out above
 // pcr_fpfh33_f32 in include/pcr.h; this file follows it operation by operation.
 //
-//   pass 1  fpfh_spfh    G lanes per SURFACE point (the queries are the grid records, as in iss.hip): one walk of the 27-cell block
+//   pass 1  fpfh_spfh    G lanes per SURFACE point (the queries are the grid records): one walk of the 27-cell block
 //                        counts |N(p)| and bins every pair (p, j), j != p, into 33 u32 counts in LDS (atomics inside the point's
 //                        group: counts do not depend on order); then the lanes of the group turn the counts into f32 values
 //                        (incr added cnt times) and write the SPFH row in record order (and in input order when asked for)
@@ -13,7 +13,7 @@
 // Distances are the f32 sum s = ((dx*dx) + dy*dy) + dz*dz, member iff s < r2 (FLANN's strict radius test).  The window of a row
 // (radius_window) takes the largest float BELOW r2: its bound |dx|^2 <= s_max (1 + 3 * 2^-24) holds for the f32 sum as well, since
 // every partial sum of non-negative terms rounds to at least its first term.
-#include "grid_common.hpp"
+#include "grid_walk.hpp"
 
 #include <cmath>
 
@@ -87,14 +87,10 @@ __global__ __launch_bounds__(FPFH_BLOCK) void fpfh_spfh_kernel(const float4* __r
         if (finite3(q.x, q.y, q.z)) {
             const uint32_t pi = __float_as_uint(q.w);
             const float n1x = nx[pi], n1y = ny[pi], n1z = nz[pi];
-            int cx, cy, cz;
-            query_cell(g, q, cx, cy, cz);
-            float wlo, whi;
-            radius_window(q.x, s_win, wlo, whi);
+            const RadiusWalk walk(g, cell_start, records, query_cell(g, q), radius_window(q.x, s_win));
             for (int k = 0; k < 9; k++) {
                 uint32_t b, e;
-                row_range(g, cell_start, cx, cy, cz, k, b, e);
-                clip_row_x(records, b, e, wlo, whi);
+                walk.row<384>(k, b, e);
                 for (uint32_t j = b + sub; j < e; j += G) {
                     const float4 t = records[j];
                     const float dx = t.x - q.x, dy = t.y - q.y, dz = t.z - q.z;
@@ -111,7 +107,7 @@ __global__ __launch_bounds__(FPFH_BLOCK) void fpfh_spfh_kernel(const float4* __r
             }
         }
     }
-    c = group_sum_u32<G>(c);
+    c = group_sum<G>(c);
     __syncthreads();
     if (p >= n) return;
     // value of a bin = incr added cnt times in f32: all addends are equal, so this is PCL's repeated += in any order
@@ -144,14 +140,10 @@ __global__ __launch_bounds__(FPFH_BLOCK) void fpfh_weight_kernel(const float4* _
     unsigned c = 0;
     const bool fin = finite3(q.x, q.y, q.z);
     if (fin) {
-        int cx, cy, cz;
-        query_cell(g, q, cx, cy, cz);
-        float wlo, whi;
-        radius_window(q.x, s_win, wlo, whi);
+        const RadiusWalk walk(g, cell_start, records, query_cell(g, q), radius_window(q.x, s_win));
         for (int k = 0; k < 9; k++) {
             uint32_t b, e;
-            row_range(g, cell_start, cx, cy, cz, k, b, e);
-            clip_row_x(records, b, e, wlo, whi);
+            walk.row<384>(k, b, e);
             for (uint32_t j = b + sub; j < e; j += G) {
                 const float4 t = records[j];
                 const float s = fp_s(t.x - q.x, t.y - q.y, t.z - q.z);
@@ -165,9 +157,9 @@ __global__ __launch_bounds__(FPFH_BLOCK) void fpfh_weight_kernel(const float4* _
             }
         }
     }
-    c = group_sum_u32<G>(c);
+    c = group_sum<G>(c);
 #pragma unroll
-    for (int b = 0; b < FPFH_DIM; b++) acc[b] = group_sum_f64<G>(acc[b]);
+    for (int b = 0; b < FPFH_DIM; b++) acc[b] = group_sum<G>(acc[b]);
     if (sub == 0 && cnt_out) cnt_out[row] = c;
     float* out = fpfh + (size_t)row * FPFH_DIM;
     if (!fin || c == 0) {                                   // computeFeature: a row of NaN
@@ -210,9 +202,7 @@ extern "C" int pcr_fpfh33_f32(pcr_ctx* ctx, const pcr_cloud* surface, const pcr_
     Grid* g = nullptr;
     {
         ProfScope ps(ctx, "fpfh_grid_build");
-        // cell edge >= 1.01 radius (every neighbour lies in the 27-cell block) and >= 2e-15 (iss.hip: below that squared f32
-        // distances underflow and a point outside the block could compute s == 0)
-        int rc = grid_build(ctx, surface, &g, std::max((double)radius * 1.01, 2e-15));
+        int rc = grid_build(ctx, surface, &g, radius_cell_edge(radius));
         if (rc) return rc;
     }
     const GridPtr g_owner(g);

@@ -18,7 +18,7 @@
 //   than (r - slack) * h apart; slack covers the f32 rounding of the cell computation), or when the cube
 //   covers the whole grid.  Exactness proof and cost model: DESIGN.md §5b.
 // Traffic (algorithmic): 12 B query + 8 B key + 16 B per visited candidate + 8 B per visited cell row.
-#include "grid_common.hpp"
+#include "grid_walk.hpp"
 
 #include "sort.hpp"
 
@@ -370,35 +370,8 @@ __device__ __forceinline__ void scan_range(const float4* __restrict__ records, u
 // Every x-row of the records is sorted by x (grid_build), so a long range can be cut down to the records whose x lies
 // within the current best distance of the query before any distance is evaluated: the candidates of a dense row (a LiDAR
 // ring packs hundreds of points into one 3-cell row at 10 M points) shrink to the few that can still win or tie.
-// [lo, hi] must contain every x with |x - qx| <= sqrt(best d2) in REAL arithmetic (the caller widens for rounding).
-// Both searches are bounded (32 halvings); predicates are false for NaN, which cannot occur inside a row (non-finite
-// points live in the extra cell).
-__device__ __forceinline__ void clip_range_x(const float4* __restrict__ records, uint32_t& b, uint32_t& e, float lo, float hi)
-{
-    if (e - b <= 48u) return;                                   // short rows: the searches would cost more than they save
-    uint32_t l = b, h = e;                                      // first p with x >= lo
-    for (int it = 0; it < 32 && l < h; it++) {
-        const uint32_t mid = l + ((h - l) >> 1);
-        if (records[mid].x < lo) l = mid + 1; else h = mid;
-    }
-    const uint32_t nb = l;
-    h = e;                                                      // first p >= nb with x > hi
-    for (int it = 0; it < 32 && l < h; it++) {
-        const uint32_t mid = l + ((h - l) >> 1);
-        if (records[mid].x <= hi) l = mid + 1; else h = mid;
-    }
-    b = nb;
-    e = l;
-}
-
-// window for clip_range_x from a squared bound; widened by the rounding of qx -+ d (relative to |qx|, not to d)
-__device__ __forceinline__ void x_window(float qx, float bound2, float& lo, float& hi)
-{
-    const float d = sqrtf(bound2) * 1.00001f;
-    const float pad = (fabsf(qx) + d) * 2.4e-7f;
-    lo = qx - d - pad;
-    hi = qx + d + pad;
-}
+// The clip and its window (x_window) are grid_walk.hpp's; here rows of up to GRID_CLIP_MIN records are left whole.
+constexpr unsigned GRID_CLIP_MIN = 48;
 
 // The nine row ranges of stage 1 as ONE flattened index space: lane l takes candidates l, l + G, ... of the concatenation.
 // Rows are short (1-4 trips of G lanes each), so scanning them one after the other leaves a single load in flight per
@@ -440,7 +413,7 @@ __device__ __forceinline__ void min_step_dpp(unsigned long long& v, uint32_t& po
 }
 
 template <int G>
-__device__ __forceinline__ void group_min(unsigned long long& v, uint32_t& pos)
+__device__ __forceinline__ void group_min_key(unsigned long long& v, uint32_t& pos)
 {
     if (G == 16) {
         // 16 lanes = one DPP row: xor 1, xor 2 (quad permutes), then the half-row and the row mirror — each step pairs groups that are
@@ -566,7 +539,7 @@ __device__ __forceinline__ void scan_range_sph(const float4* __restrict__ record
             if (STATS && l == 0) { st_sph += cb + 16u * k < c1 ? min(16u, c1 - cb - 16u * k) : 0u; st_cand += 16u * (uint32_t)__popc(m); }
             if (m) { scan_hits16(records, m, cb + 16u * k + (uint32_t)l, l, qx, qy, qz, best, bestp); any = true; }
         }
-        if (any) group_min<16>(best, bestp);       // the next pass is tested against the improved bound
+        if (any) group_min_key<16>(best, bestp);       // the next pass is tested against the improved bound
     }
 }
 
@@ -605,7 +578,7 @@ __device__ __forceinline__ void scan_flat9_sph(const float4* __restrict__ record
             if (STATS && l == 0) { st_sph += f0 + 16u * b < off[9] ? min(16u, off[9] - f0 - 16u * b) : 0u; st_cand += 16u * (uint32_t)__popc(m); }
             if (m) { scan_hits16(records, m, cc[b], l, qx, qy, qz, best, bestp); any = true; }
         }
-        if (any) group_min<16>(best, bestp);
+        if (any) group_min_key<16>(best, bestp);
     }
 }
 
@@ -661,7 +634,7 @@ __device__ __forceinline__ void scan_pieces_sph(const float4* __restrict__ recor
         if (STATS && l == 0) { st_sph += min(16u, total - f0); st_cand += 16u * (uint32_t)__popc(m); }
         if (m) {
             scan_hits16(records, m, c, l, qx, qy, qz, best, bestp);
-            group_min<16>(best, bestp);
+            group_min_key<16>(best, bestp);
         }
     }
 }
@@ -728,7 +701,7 @@ __device__ __forceinline__ void stage1_sph(const float4* __restrict__ records, c
         if (STATS && l == 0) { st_sph += min(16u, total - f0); st_cand += 16u * (uint32_t)__popc(m); }
         if (m) {
             scan_hits16(records, m, c, l, qx, qy, qz, best, bestp);
-            group_min<16>(best, bestp);
+            group_min_key<16>(best, bestp);
         }
     }
 }
@@ -860,7 +833,7 @@ __global__ __launch_bounds__(GR_BLOCK, (LIST && !STATS) ? PCR_LIST_WAVES : 1) vo
                 // point or close to it, and the ball every later sphere test and row clip works with is that much smaller.
                 seed_run = pp0 / GRID_CHUNK;
                 scan_run16(records, seed_run, l, qx, qy, qz, best, bestp);
-                group_min<16>(best, bestp);
+                group_min_key<16>(best, bestp);
             } else if (warm_start >= 2) {
                 // ICP, from the second search of a loop on: wpos[] holds the record position of this query's previous winner.
                 // That target, evaluated exactly against the moved query, is a genuine candidate: it bounds the search from the
@@ -894,7 +867,7 @@ __global__ __launch_bounds__(GR_BLOCK, (LIST && !STATS) ? PCR_LIST_WAVES : 1) vo
             if (r == 1 && SPH) {
                 // ---- stage 1, sphere walk: one row per lane
                 stage1_sph<STATS>(records, spheres, cell_start, g, ux, uy, uz, l, qx, qy, qz, best, bestp, st_cand, st_sph, st_rows, seed_run);
-                group_min<G>(best, bestp);
+                group_min_key<G>(best, bestp);
                 const bool covers = (ux - 1 <= 0) && (ux + 1 >= g.n[0] - 1) && (uy - 1 <= 0) && (uy + 1 >= g.n[1] - 1) &&
                                     (uz - 1 <= 0) && (uz + 1 >= g.n[2] - 1);
                 const float reach = (1.0f - g.slack) * g.h;
@@ -902,7 +875,8 @@ __global__ __launch_bounds__(GR_BLOCK, (LIST && !STATS) ? PCR_LIST_WAVES : 1) vo
                                                     (best != KEY_NONE && __uint_as_float((uint32_t)(best >> 32)) < reach * reach * 0.99999f)));
                 r = 2;
             } else if (r == 1) {
-                // ---- stage 1: static 3 x 3 rows, bounds first
+                // ---- stage 1: static 3 x 3 rows, bounds first (not grid_walk.hpp's row_range: with a seed the x range of a row is what
+                // ball_x_cells leaves of it, not the three cells)
                 const int xlo = max(ux - 1, 0), xhi = min(ux + 1, g.n[0] - 1);
                 uint32_t rb[9], re[9];
                 // with a seed (the previous correspondence, re-evaluated) only the rows and cells its ball reaches can matter: at the
@@ -935,23 +909,22 @@ __global__ __launch_bounds__(GR_BLOCK, (LIST && !STATS) ? PCR_LIST_WAVES : 1) vo
                         scan_range<G>(records, rb[4], re[4], l, qx, qy, qz, best, bestp);
                         if (STATS && l == 0) st_cand += re[4] - rb[4];
                         rb[4] = re[4] = 0;
-                        group_min<G>(best, bestp);
+                        group_min_key<G>(best, bestp);
                     }
                     if (best != KEY_NONE && total > 48u) {
-                        float lo, hi;
-                        x_window(qx, fmaxf(__uint_as_float((uint32_t)(best >> 32)), TRUST2) * 1.0001f, lo, hi);
+                        const XWindow win = x_window(qx, fmaxf(__uint_as_float((uint32_t)(best >> 32)), TRUST2) * 1.0001f);
                         if (G >= 9) {
                             // one row per lane: the nine binary searches run side by side (one chain of ~12 dependent loads
                             // instead of nine), the results travel back through shuffles
                             uint32_t cb = 0, ce = 0;
 #pragma unroll
                             for (int k = 0; k < 9; k++) if (l == k) { cb = rb[k]; ce = re[k]; }
-                            if (l < 9) clip_range_x(records, cb, ce, lo, hi);
+                            if (l < 9) clip_row_x<GRID_CLIP_MIN>(records, cb, ce, win.lo, win.hi);
 #pragma unroll
                             for (int k = 0; k < 9; k++) { rb[k] = __shfl(cb, k, G); re[k] = __shfl(ce, k, G); }
                         } else {
 #pragma unroll
-                            for (int k = 0; k < 9; k++) clip_range_x(records, rb[k], re[k], lo, hi);
+                            for (int k = 0; k < 9; k++) clip_row_x<GRID_CLIP_MIN>(records, rb[k], re[k], win.lo, win.hi);
                         }
                     }
                 }
@@ -964,7 +937,7 @@ __global__ __launch_bounds__(GR_BLOCK, (LIST && !STATS) ? PCR_LIST_WAVES : 1) vo
                     }
                     if (STATS && l == 0) { for (int k = 0; k < 9; k++) st_cand += re[k] - rb[k]; }
                 }
-                group_min<G>(best, bestp);
+                group_min_key<G>(best, bestp);
                 const bool covers = (ux - 1 <= 0) && (ux + 1 >= g.n[0] - 1) && (uy - 1 <= 0) && (uy + 1 >= g.n[1] - 1) &&
                                     (uz - 1 <= 0) && (uz + 1 >= g.n[2] - 1);
                 const float reach = (1.0f - g.slack) * g.h;
@@ -994,8 +967,8 @@ __global__ __launch_bounds__(GR_BLOCK, (LIST && !STATS) ? PCR_LIST_WAVES : 1) vo
                 const int ylo = max(uy - r, 0), yhi = min(uy + r, g.n[1] - 1);
                 const int zlo = max(uz - r, 0), zhi = min(uz + r, g.n[2] - 1);
                 const float clip2 = bestf * 1.0001f;
-                float wlo = 0.0f, whi = 0.0f;
-                if (CLIP && have) x_window(qx, clip2, wlo, whi);
+                XWindow win = { 0.0f, 0.0f };
+                if (CLIP && have) win = x_window(qx, clip2);
                 if (xlo <= xhi && ylo <= yhi && zlo <= zhi) {
                     // Far searches open many x-rows, most of them short.  Rows are taken G at a time: every lane resolves
                     // ONE row (clipping + its cell_start bounds: G independent loads in flight per query), then the whole
@@ -1043,8 +1016,8 @@ __global__ __launch_bounds__(GR_BLOCK, (LIST && !STATS) ? PCR_LIST_WAVES : 1) vo
                                     b1 = cell_start[row + xa]; e1 = cell_start[row + xb + 1];
                                 }
                                 if (CLIP && have) {                            // x-sorted rows: keep only |x - qx| <= best
-                                    clip_range_x(records, b1, e1, wlo, whi);
-                                    clip_range_x(records, b2, e2, wlo, whi);
+                                    clip_row_x<GRID_CLIP_MIN>(records, b1, e1, win.lo, win.hi);
+                                    clip_row_x<GRID_CLIP_MIN>(records, b2, e2, win.lo, win.hi);
                                 }
                                 if (STATS) { st_rows++; if (!SPH) st_cand += (e1 - b1) + (e2 - b2); }
                             }
@@ -1069,7 +1042,7 @@ __global__ __launch_bounds__(GR_BLOCK, (LIST && !STATS) ? PCR_LIST_WAVES : 1) vo
                     }
                 }
                 if (STATS && l == 0) st_stages++;
-                group_min<G>(best, bestp);
+                group_min_key<G>(best, bestp);
                 const bool covers = (ux - r <= 0) && (ux + r >= g.n[0] - 1) && (uy - r <= 0) && (uy + r >= g.n[1] - 1) &&
                                     (uz - r <= 0) && (uz + r >= g.n[2] - 1);
                 // every target outside the cube is farther than (r - slack) * h in some axis

@@ -1,4 +1,6 @@
-// grid_common.hpp — the uniform-grid index shared by the exact 1-NN search (grid.hip) and the radius consumers (iss.hip, fpfh.hip).
+// grid_common.hpp — the indexes: the uniform cell grid (GridParams, Grid, how a point is binned), its build declarations, and BTRACK's
+// Morton-ordered index with the f16 operand helpers of the matrix-core 1-NN search.  How a radius neighbourhood is walked over the cell
+// grid — rows, clip, windows, group reductions — is grid_walk.hpp.
 #pragma once
 
 #include "pcr_internal.hpp"
@@ -74,78 +76,15 @@ __device__ __forceinline__ uint32_t clamped_cell_id(const GridParams& g, float x
     return (uint32_t)((cz * g.n[1] + cy) * g.n[0] + cx);
 }
 
-// ---- the radius walk of the radius consumers (iss.hip, fpfh.hip): a query's 27-cell block as 9 x-rows, each row cut to the x-window
-// that can hold a neighbour; G lanes of a group stride over a row and reduce with the shuffles below.
-// the 9 x-rows of the 27-cell block around cell (cx, cy, cz): row k -> [begin, end) in records
-__device__ __forceinline__ void row_range(const GridParams& g, const uint32_t* __restrict__ cell_start, int cx, int cy, int cz, int k,
-                                          uint32_t& b, uint32_t& e)
-{
-    const int yy = cy + (k % 3) - 1, zz = cz + (k / 3) - 1;
-    if (yy < 0 || yy >= g.n[1] || zz < 0 || zz >= g.n[2]) { b = e = 0; return; }
-    const int x0 = max(cx - 1, 0), x1 = min(cx + 1, g.n[0] - 1);
-    const uint32_t row = (uint32_t)((zz * g.n[1] + yy) * g.n[0]);
-    b = cell_start[row + x0];
-    e = cell_start[row + x1 + 1];
-}
-
-// The records of a row are sorted by x (grid_build): cut [b, e) to the records with lo <= x <= hi, the only ones that can
-// lie within the radius.  Two bounded binary searches, worth it on long rows only; uniform over the lanes of a group.
-__device__ __forceinline__ void clip_row_x(const float4* __restrict__ records, uint32_t& b, uint32_t& e, float lo, float hi)
-{
-    if (e - b <= 384u) return;
-    uint32_t l = b, h = e;
-    for (int it = 0; it < 32 && l < h; it++) {
-        const uint32_t mid = l + ((h - l) >> 1);
-        if (records[mid].x < lo) l = mid + 1; else h = mid;
-    }
-    const uint32_t nb = l;
-    h = e;
-    for (int it = 0; it < 32 && l < h; it++) {
-        const uint32_t mid = l + ((h - l) >> 1);
-        if (records[mid].x <= hi) l = mid + 1; else h = mid;
-    }
-    b = nb;
-    e = l;
-}
-
-// [lo, hi] around qx that contains every x whose hw7 sum can still be <= s_max: |dx|^2 <= s_max (1 + 3 * 2^-24); the floor
-// 1e-18 covers differences whose squares vanish in f32 (|e| < 3.7e-23 gives s == 0), the pad the rounding of qx -+ d
-__device__ __forceinline__ void radius_window(float qx, float s_max, float& lo, float& hi)
-{
-    const float d = sqrtf(fmaxf(s_max, 0.0f)) * 1.00001f + 1e-18f;
-    const float pad = (fabsf(qx) + d) * 2.4e-7f;
-    lo = qx - d - pad;
-    hi = qx + d + pad;
-}
-
-template <int G>
-__device__ __forceinline__ unsigned group_sum_u32(unsigned v)
-{
-#pragma unroll
-    for (int o = G / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, G);
-    return v;
-}
-template <int G>
-__device__ __forceinline__ double group_sum_f64(double v)
-{
-#pragma unroll
-    for (int o = G / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, G);
-    return v;
-}
-
-// cells of a query: every point of the cloud lies inside the grid box, non-finite ones were binned into cell 0 and
-// never pass a distance test (inf - inf = NaN)
-__device__ __forceinline__ void query_cell(const GridParams& g, const float4& q, int& cx, int& cy, int& cz)
-{
-    cx = min(max(cell_coord(q.x, g.lo[0], g.inv_h), 0), g.n[0] - 1);
-    cy = min(max(cell_coord(q.y, g.lo[1], g.inv_h), 0), g.n[1] - 1);
-    cz = min(max(cell_coord(q.z, g.lo[2], g.inv_h), 0), g.n[2] - 1);
-}
-
 // builds the index over `c`; cell_edge > 0 forces the cell size (otherwise the heuristic of grid.hip is used)
 int grid_build(pcr_ctx* ctx, const pcr_cloud* c, Grid** out, double cell_edge, int order = GRID_ORDER_X);
 // builds (and caches on tgt) the 1-NN grid if needed
 int build_target_grid(pcr_ctx* ctx, const pcr_cloud* tgt);
+// builds (and caches on tgt) the 1-NN grid if needed, then groups the queries `src` by coarse cell -> ctx->qperm
+int grid_prepare_queries(pcr_ctx* ctx, const pcr_cloud* tgt, const pcr_cloud* src);
+// replaces *work by its cell-sorted copy (its orig = original indices); no-op for empty clouds / tune grid_sort_work = 2
+int grid_sort_working_cloud(pcr_ctx* ctx, const pcr_cloud* tgt, pcr_cloud** work, bool in_place);
+
 // BTRACK's index (nn1_brute.hip), independent of the cell grid: the cloud in Morton order of a lattice of cubic cells (longest extent / 1024) over its bounding
 // box — spatially compact runs — as {x, y, z, original index} records (padded to whole super-tiles of BT_SUPER records with
 // x = +inf), one centre per super-tile, and per tile of 32 records the bf16 A operands of two v_mfma_f32_32x32x16_bf16
@@ -469,10 +408,6 @@ int bt_ensure(pcr_ctx* ctx, const pcr_cloud* tgt);
 int bt_ensure_tile(pcr_ctx* ctx, const pcr_cloud* tgt);
 // ... and level 1 of the two-level sign filter (needs a safe tgt->bt)
 int bt_ensure_l1(pcr_ctx* ctx, const pcr_cloud* tgt);
-// builds (and caches on tgt) the 1-NN grid if needed, then groups the queries `src` by coarse cell -> ctx->qperm
-int grid_prepare_queries(pcr_ctx* ctx, const pcr_cloud* tgt, const pcr_cloud* src);
-// replaces *work by its cell-sorted copy (its orig = original indices); no-op for empty clouds / tune grid_sort_work = 2
-int grid_sort_working_cloud(pcr_ctx* ctx, const pcr_cloud* tgt, pcr_cloud** work, bool in_place);
 // the same for a brute-force loop over the matrix-core index: *work in the Morton order of the target's super-tiles (no-op without that index)
 int bt_sort_working_cloud(pcr_ctx* ctx, const pcr_cloud* tgt, pcr_cloud** work, bool in_place);
 

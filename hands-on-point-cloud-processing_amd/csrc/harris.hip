@@ -1,10 +1,10 @@
 // harris.hip — Harris3D keypoints (Homework9/hw9/src/registration.cpp:221-250, PCL's HarrisKeypoint3D with the caller's normals) as
-// two radius passes over the uniform grid of grid_common.hpp.  The contract (neighbourhood, normal moments as exact integer sums,
+// two radius passes over the uniform grid (the walk: grid_walk.hpp).  The contract (neighbourhood, normal moments as exact integer sums,
 // response, suppression) is written out above pcr_harris3d_f32 in include/pcr.h; this file follows it operation by operation.
 //
 //   pass 0  harris_normals   one lane per grid record: its point's normal in RECORD order, scaled by 2^16, as one float4 whose w is 1
 //                            for a contributor (three finite components of magnitude <= 2) and 0 otherwise (x = y = z = 0 then)
-//   pass 1  harris_response  G lanes per SURFACE point (the queries are the grid records, as in iss.hip / fpfh.hip): one walk of the
+//   pass 1  harris_response  G lanes per SURFACE point (the queries are the grid records): one walk of the
 //                            27-cell block counts |N(i)| and the contributors and adds the six products as integers; a fixed
 //                            xor-shuffle tree sums the group and lane 0 turns the sums into the coefficients and the response
 //   pass 2  harris_nms       G lanes per surface point: a group whose own response fails the finite / threshold test never walks; the
@@ -16,7 +16,7 @@
 // product.  It is added in f64 (v_cvt_f64_f32 + v_add_f64: exact while a lane's pending terms keep |sum| < 2^53) and a lane moves
 // its f64 sums into int64 accumulators before more than 2^18 terms are pending, so that the sums are exact integers for any count.
 // Per pair and product: v_mul_f32, v_rndne_f32, v_cvt_f64_f32, v_add_f64.
-#include "grid_common.hpp"
+#include "grid_walk.hpp"
 
 #include <cmath>
 
@@ -28,25 +28,6 @@ constexpr int HARRIS_BLOCK = 256;
 constexpr uint32_t HARRIS_PENDING_MAX = 1u << 18;          // terms a lane adds in f64 before it moves them to int64: 2^18 * 2^34 < 2^53
 
 __device__ __forceinline__ float hr_s(float dx, float dy, float dz) { return ((dx * dx) + dy * dy) + dz * dz; }
-
-template <int G>
-__device__ __forceinline__ long long group_sum_i64(long long v)
-{
-#pragma unroll
-    for (int o = G / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, G);
-    return v;
-}
-
-// true when any lane of this lane's group of G raised `flag` (lanes of the group that have left count as not raised)
-template <int G>
-__device__ __forceinline__ bool group_any(bool flag)
-{
-    if (G == 1) return flag;
-    const unsigned long long b = __ballot(flag);
-    const unsigned lane = threadIdx.x & 63u;               // one-dimensional workgroups of HARRIS_BLOCK
-    const unsigned long long m = (G >= 64 ? ~0ull : ((1ull << (G & 63)) - 1ull)) << (lane & ~(unsigned)(G - 1));
-    return (b & m) != 0ull;
-}
 
 __global__ __launch_bounds__(HARRIS_BLOCK) void harris_normals_kernel(const float4* __restrict__ records, uint32_t n, const float* __restrict__ nx,
                                                                       const float* __restrict__ ny, const float* __restrict__ nz,
@@ -84,14 +65,10 @@ __global__ __launch_bounds__(HARRIS_BLOCK) void harris_response_kernel(const flo
     long long S[6] = { 0, 0, 0, 0, 0, 0 };
     unsigned c = 0, m = 0, pending = 0;
     if (finite3(q.x, q.y, q.z)) {
-        int cx, cy, cz;
-        query_cell(g, q, cx, cy, cz);
-        float wlo, whi;
-        radius_window(q.x, s_win, wlo, whi);
+        const RadiusWalk walk(g, cell_start, records, query_cell(g, q), radius_window(q.x, s_win));
         for (int k = 0; k < 9; k++) {
             uint32_t b, e;
-            row_range(g, cell_start, cx, cy, cz, k, b, e);
-            clip_row_x(records, b, e, wlo, whi);
+            walk.row<384>(k, b, e);
             while (b < e) {                                 // pieces of at most HARRIS_PENDING_MAX records per lane
                 const uint32_t piece = (e - b + G - 1) / G <= HARRIS_PENDING_MAX ? e : b + HARRIS_PENDING_MAX * G;
                 const uint32_t len = (piece - b + G - 1) / G;
@@ -118,10 +95,10 @@ __global__ __launch_bounds__(HARRIS_BLOCK) void harris_response_kernel(const flo
             }
         }
     }
-    c = group_sum_u32<G>(c);
-    m = group_sum_u32<G>(m);
+    c = group_sum<G>(c);
+    m = group_sum<G>(m);
 #pragma unroll
-    for (int t = 0; t < 6; t++) S[t] = group_sum_i64<G>(S[t] + (long long)f[t]);
+    for (int t = 0; t < 6; t++) S[t] = group_sum<G>(S[t] + (long long)f[t]);
     if (sub != 0) return;
     float co[6] = { 0.f, 0.f, 0.f, 0.f, 0.f, 0.f };
     if (m != 0) {
@@ -153,14 +130,10 @@ __global__ __launch_bounds__(HARRIS_BLOCK) void harris_nms_kernel(const float4* 
         key = fin && fabsf(mine) <= FLT_MAX && !(mine < threshold);
         if (key) {                                          // uniform over the group
             bool beaten = false;
-            int cx, cy, cz;
-            query_cell(g, q, cx, cy, cz);
-            float wlo, whi;
-            radius_window(q.x, s_win, wlo, whi);
+            const RadiusWalk walk(g, cell_start, records, query_cell(g, q), radius_window(q.x, s_win));
             for (int k = 0; k < 9 && !beaten; k++) {
                 uint32_t b, e;
-                row_range(g, cell_start, cx, cy, cz, k, b, e);
-                clip_row_x(records, b, e, wlo, whi);
+                walk.row<384>(k, b, e);
                 for (uint32_t j0 = b; j0 < e; j0 += G) {    // uniform over the group: it leaves together at the first larger neighbour
                     const uint32_t j = j0 + sub;
                     bool lost = false;
@@ -202,9 +175,7 @@ extern "C" int pcr_harris3d_f32(pcr_ctx* ctx, const pcr_cloud* cloud, const pcr_
     Grid* g = nullptr;
     {
         ProfScope ps(ctx, "harris_grid_build");
-        // cell edge >= 1.01 radius (every neighbour lies in the 27-cell block) and >= 2e-15 (iss.hip: below that squared f32
-        // distances underflow and a point outside the block could compute s == 0)
-        int rc = grid_build(ctx, cloud, &g, std::max((double)radius * 1.01, 2e-15));
+        int rc = grid_build(ctx, cloud, &g, radius_cell_edge(radius));
         if (rc) return rc;
     }
     const GridPtr g_owner(g);

@@ -1,5 +1,5 @@
 // iss.hip — next row N1: ISS keypoints (Homework7/hw7/src/iss_detector.cpp:38-152) as three batched radius passes over the
-// uniform grid of grid_common.hpp.  The cloud is searched against itself, so the queries ARE the grid records: query p
+// uniform grid (the walk: grid_walk.hpp).  The cloud is searched against itself, so the queries ARE the grid records: query p
 // is record p, consecutive lanes work on points of the same cell and the 27-cell neighbourhood (9 contiguous x-rows of
 // 3 cells) stays in L1/L2 between them.
 //
@@ -13,7 +13,7 @@
 // component, d = sqrtf(s), member iff d <= r.  sqrtf is monotonic and correctly rounded, so the host finds the largest
 // float s_max with sqrtf(s_max) <= r once and the kernels compare s <= s_max — the same set, no sqrt per pair.
 // G lanes share one query and stride over each row; f64 covariance sums are reduced across the G lanes with shuffles.
-#include "grid_common.hpp"
+#include "grid_walk.hpp"
 
 #include <cmath>
 #include <vector>
@@ -52,21 +52,17 @@ __global__ __launch_bounds__(ISS_BLOCK) void iss_count_kernel(const float4* __re
     const float4 q = records[p];
     unsigned c = 0;
     if (finite3(q.x, q.y, q.z)) {
-        int cx, cy, cz;
-        query_cell(g, q, cx, cy, cz);
-        float wlo, whi;
-        radius_window(q.x, s_max, wlo, whi);
+        const RadiusWalk walk(g, cell_start, records, query_cell(g, q), radius_window(q.x, s_max));
         for (int k = 0; k < 9; k++) {
             uint32_t b, e;
-            row_range(g, cell_start, cx, cy, cz, k, b, e);
-            clip_row_x(records, b, e, wlo, whi);
+            walk.row<384>(k, b, e);
             for (uint32_t j = b + sub; j < e; j += G) {
                 const float4 t = records[j];
                 c += hw7_s(t.x, t.y, t.z, q.x, q.y, q.z) <= s_max;
             }
         }
     }
-    c = group_sum_u32<G>(c);
+    c = group_sum<G>(c);
     if (sub == 0) {
         cnt_sorted[p] = c;
         cnt_out[__float_as_uint(q.w)] = c;
@@ -113,14 +109,10 @@ __global__ __launch_bounds__(ISS_BLOCK) void iss_cov_kernel(const float4* __rest
     const float4 q = records[p];
     double sxx = 0, sxy = 0, sxz = 0, syy = 0, syz = 0, szz = 0, wsum = 0;
     if (cnt_sorted[p] >= 3) {                               // uniform over the group
-        int cx, cy, cz;
-        query_cell(g, q, cx, cy, cz);
-        float wlo, whi;
-        radius_window(q.x, prm.s_local, wlo, whi);
+        const RadiusWalk walk(g, cell_start, records, query_cell(g, q), radius_window(q.x, prm.s_local));
         for (int k = 0; k < 9; k++) {
             uint32_t b, e;
-            row_range(g, cell_start, cx, cy, cz, k, b, e);
-            clip_row_x(records, b, e, wlo, whi);
+            walk.row<384>(k, b, e);
             for (uint32_t j = b + sub; j < e; j += G) {
                 const float4 t = records[j];
                 if (!(hw7_s(t.x, t.y, t.z, q.x, q.y, q.z) <= prm.s_local)) continue;
@@ -133,9 +125,9 @@ __global__ __launch_bounds__(ISS_BLOCK) void iss_cov_kernel(const float4* __rest
             }
         }
     }
-    sxx = group_sum_f64<G>(sxx); sxy = group_sum_f64<G>(sxy); sxz = group_sum_f64<G>(sxz);
-    syy = group_sum_f64<G>(syy); syz = group_sum_f64<G>(syz); szz = group_sum_f64<G>(szz);
-    wsum = group_sum_f64<G>(wsum);
+    sxx = group_sum<G>(sxx); sxy = group_sum<G>(sxy); sxz = group_sum<G>(sxz);
+    syy = group_sum<G>(syy); syz = group_sum<G>(syz); szz = group_sum<G>(szz);
+    wsum = group_sum<G>(wsum);
     if (sub != 0) return;
     sums[p] = sxx; sums[(size_t)n + p] = sxy; sums[2 * (size_t)n + p] = sxz; sums[3 * (size_t)n + p] = syy;
     sums[4 * (size_t)n + p] = syz; sums[5 * (size_t)n + p] = szz; sums[6 * (size_t)n + p] = wsum;
@@ -177,14 +169,10 @@ __global__ __launch_bounds__(ISS_BLOCK) void iss_nms_kernel(const float4* __rest
     const float mine = l3_sorted[p];
     unsigned m = 0, beaten = 0;
     if (mine != -1.0f) {                                    // :88, uniform over the group
-        int cx, cy, cz;
-        query_cell(g, q, cx, cy, cz);
-        float wlo, whi;
-        radius_window(q.x, prm.s_nms, wlo, whi);
+        const RadiusWalk walk(g, cell_start, records, query_cell(g, q), radius_window(q.x, prm.s_nms));
         for (int k = 0; k < 9; k++) {
             uint32_t b, e;
-            row_range(g, cell_start, cx, cy, cz, k, b, e);
-            clip_row_x(records, b, e, wlo, whi);
+            walk.row<384>(k, b, e);
             for (uint32_t j = b + sub; j < e; j += G) {
                 const float4 t = records[j];
                 if (!(hw7_s(t.x, t.y, t.z, q.x, q.y, q.z) <= prm.s_nms)) continue;
@@ -193,8 +181,8 @@ __global__ __launch_bounds__(ISS_BLOCK) void iss_nms_kernel(const float4* __rest
             }
         }
     }
-    m = group_sum_u32<G>(m);
-    beaten = group_sum_u32<G>(beaten);
+    m = group_sum<G>(m);
+    beaten = group_sum<G>(beaten);
     if (sub == 0) is_key[__float_as_uint(q.w)] = (mine != -1.0f && m >= prm.min_neighbors && beaten == 0) ? 1 : 0;
 }
 
@@ -227,15 +215,11 @@ extern "C" int pcr_iss_keypoints_f32(pcr_ctx* ctx, const pcr_cloud* cloud, const
     if (n_keypoints) *n_keypoints = 0;
     if (n == 0) return PCR_OK;
     if (n > 0x7FFFFFF0ull) return fail(ctx, PCR_ERR_ARG, "pcr_iss_keypoints_f32: cloud too large");
-    // cell edge >= the larger radius with a margin for the rounding of the cell coordinate, so that every neighbour lies
-    // in the 27-cell block; grid_build may only enlarge it (cell budget, <= 4001 cells per axis)
-    const double rmax = std::max((double)prm->local_radius, (double)prm->non_max_radius);
+    const double rmax = std::max((double)prm->local_radius, (double)prm->non_max_radius);      // one grid serves both radii
     Grid* g = nullptr;
     {
         ProfScope ps(ctx, "iss_grid_build");
-        // >= 2e-15: below that, squared f32 distances underflow and a point outside the 27-cell block could still compute
-        // s == 0 <= s_max; with h >= 2e-15 every outside point has s >= ~4e-30 (normal range) > s_max
-        int rc = grid_build(ctx, cloud, &g, std::max(rmax * 1.01, 2e-15));
+        int rc = grid_build(ctx, cloud, &g, radius_cell_edge(rmax));
         if (rc) return rc;
     }
     const GridPtr g_owner(g);

@@ -14,7 +14,7 @@
 // is farther: v < ((r - slack) h)^2.  The next radius is the smallest one that can prove the current k-th value
 // (or 2 r while fewer than k points have been seen); only the new shell is scanned, rows beyond the k-th ball are
 // skipped.  Every loop has an unconditional bound.
-#include "grid_common.hpp"
+#include "grid_walk.hpp"
 #include "eig3.hpp"
 
 #include <atomic>
@@ -27,6 +27,7 @@ namespace pcr {
 namespace {
 
 constexpr int KG_BLOCK = 256;
+constexpr unsigned KG_CLIP_MIN = 32;    // rows up to this length are scanned whole (one lane per query: the searches pay off early)
 
 template <int K>
 struct TopK {
@@ -57,25 +58,12 @@ __device__ __forceinline__ void scan_cells(const float4* __restrict__ records, u
                                            TopK<K>& t, double& kth_s)
 {
 #pragma clang fp contract(off)
-    // rows of the index are sorted by x: once a bound is known, a long row shrinks to |x - qx| <= sqrt(bound) by two bounded
-    // binary searches (a candidate outside cannot pass `s < cap_s && s <= kth_s`: s >= dx*dx up to rounding, margin 1e-5)
+    // rows of the index are sorted by x: once a bound is known, a long row shrinks to |x - qx| <= sqrt(bound) (clip_row_x,
+    // grid_walk.hpp; a candidate outside cannot pass `s < cap_s && s <= kth_s`: s >= dx*dx up to rounding, margin 1e-5)
     const double lim = fmin(kth_s, cap_s);
-    if (e - b > 32u && lim < 1e300) {
-        const double d = sqrt(lim) * 1.00001 + 1e-30;
-        const float lo = (float)((qx - d) - (fabs(qx) + d) * 2.4e-7), hi = (float)((qx + d) + (fabs(qx) + d) * 2.4e-7);
-        uint32_t l = b, h = e;
-        for (int it = 0; it < 32 && l < h; it++) {
-            const uint32_t mid = l + ((h - l) >> 1);
-            if (records[mid].x < lo) l = mid + 1; else h = mid;
-        }
-        const uint32_t nb = l;
-        h = e;
-        for (int it = 0; it < 32 && l < h; it++) {
-            const uint32_t mid = l + ((h - l) >> 1);
-            if (records[mid].x <= hi) l = mid + 1; else h = mid;
-        }
-        b = nb;
-        e = l;
+    if (e - b > KG_CLIP_MIN && lim < 1e300) {               // (the length once more: no f64 sqrt for a short row)
+        const XWindow w = x_window_f64(qx, lim);
+        clip_row_x<KG_CLIP_MIN>(records, b, e, w.lo, w.hi);
     }
     for (uint32_t p = b; p < e; p++) {
         const float4 rec = records[p];

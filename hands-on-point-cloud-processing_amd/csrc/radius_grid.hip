@@ -3,13 +3,13 @@
 // exhaustive n x m scan.  Used by pcr_db64_radius when database and queries are f32-representable (KITTI / PLY floats
 // widened to f64, test.hpp:28 — then the f32 twin cloud widened back gives the very same doubles).
 //
-//   cell edge = 1.01 r  ->  every neighbour lies in the 27-cell block = 9 x-sorted record ranges, each cut to |x - qx| <= r
+//   cell edge = 1.01 r  ->  every neighbour lies in the 27-cell block = 9 x-sorted record ranges, each cut to |x - qx| <= r (grid_walk.hpp)
 //   pass 1  count    32 lanes per query (cell-sorted queries), membership s <= r2max (the sqrt hoisted, search_f64.hip)
 //   scan             row_ptr
 //   pass 2  emit     one workgroup per query: a presence bitmap over the database indices in LDS puts the members in ascending
 //                    index order (the canonical order) without a sort; index + d = sqrt(s) leave with coalesced stores
 //   (databases beyond 262 144 points or rows beyond 16 384 neighbours: fill unsorted + rocPRIM segmented radix sort + distances)
-#include "grid_common.hpp"
+#include "grid_walk.hpp"
 
 #include "sort.hpp"
 
@@ -51,37 +51,6 @@ __device__ __forceinline__ void member_band(double r2max, float& flo, float& fhi
     if (r2max > 1e-30 && r2max < 1e30) { flo = (float)(r2max * (1.0 - 9.5367431640625e-07)); fhi = (float)(r2max * (1.0 + 9.5367431640625e-07)); }
 }
 
-__device__ __forceinline__ void clip_x(const float4* __restrict__ records, uint32_t& b, uint32_t& e, float lo, float hi)
-{
-    if (e - b <= 256u) return;
-    uint32_t l = b, h = e;
-    for (int it = 0; it < 32 && l < h; it++) {
-        const uint32_t mid = l + ((h - l) >> 1);
-        if (records[mid].x < lo) l = mid + 1; else h = mid;
-    }
-    const uint32_t nb = l;
-    h = e;
-    for (int it = 0; it < 32 && l < h; it++) {
-        const uint32_t mid = l + ((h - l) >> 1);
-        if (records[mid].x <= hi) l = mid + 1; else h = mid;
-    }
-    b = nb;
-    e = l;
-}
-
-// the k-th of the 9 rows around the query's (unclamped) cell, cut to the x window; empty when outside the grid
-__device__ __forceinline__ void row_k(const GridParams& g, const uint32_t* __restrict__ cell_start, const float4* __restrict__ records, int cx, int cy, int cz,
-                                      int k, float lo, float hi, uint32_t& b, uint32_t& e)
-{
-    const int yy = cy + (k % 3) - 1, zz = cz + (k / 3) - 1;
-    const int x0 = max(cx - 1, 0), x1 = min(cx + 1, g.n[0] - 1);
-    if (yy < 0 || yy >= g.n[1] || zz < 0 || zz >= g.n[2] || x0 > x1) { b = e = 0; return; }
-    const uint32_t row = (uint32_t)((zz * g.n[1] + yy) * g.n[0]);
-    b = cell_start[row + x0];
-    e = cell_start[row + x1 + 1];
-    clip_x(records, b, e, lo, hi);
-}
-
 // FILL = false: counts[q] = |N(q)|;  FILL = true: idx_out[row_ptr[q] ...] = members in grid order
 template <bool FILL>
 __global__ __launch_bounds__(RG_BLOCK) void radius_grid_kernel(const float4* __restrict__ records, const uint32_t* __restrict__ cell_start, GridParams g,
@@ -99,14 +68,12 @@ __global__ __launch_bounds__(RG_BLOCK) void radius_grid_kernel(const float4* __r
     uint32_t w = FILL ? row_ptr[qi] : 0u;
     if (finite3(fx, fy, fz)) {
         const double qx = fx, qy = fy, qz = fz;
-        const int cx = cell_coord(fx, g.lo[0], g.inv_h), cy = cell_coord(fy, g.lo[1], g.inv_h), cz = cell_coord(fz, g.lo[2], g.inv_h);
-        const float pad = (fabsf(fx) + win) * 2.4e-7f;
-        const float lo = fx - win - pad, hi = fx + win + pad;
+        const RadiusWalk walk(g, cell_start, records, cell_of(g, fx, fy, fz), padded_window(fx, win));      // a foreign query: its cell is not clamped
         float flo, fhi;
         member_band(r2max, flo, fhi);
         for (int k = 0; k < 9; k++) {
             uint32_t b, e;
-            row_k(g, cell_start, records, cx, cy, cz, k, lo, hi, b, e);
+            walk.row<256>(k, b, e);
             if (!FILL && bounds && sub == k) { bounds[(size_t)qi * 18 + 2 * k] = b; bounds[(size_t)qi * 18 + 2 * k + 1] = e; }   // for the emit pass
             for (uint32_t j0 = b; j0 < e; j0 += RG_G) {    // uniform trip count over the group (ballot below)
                 const uint32_t j = j0 + sub;
@@ -128,8 +95,7 @@ __global__ __launch_bounds__(RG_BLOCK) void radius_grid_kernel(const float4* __r
         }
     }
     if (!FILL) {
-#pragma unroll
-        for (int o = RG_G / 2; o > 0; o >>= 1) c += __shfl_xor(c, o, RG_G);
+        c = group_sum<RG_G>(c);
         if (sub == 0) counts[qi] = c;
     }
 }
@@ -319,7 +285,7 @@ int radius_grid(pcr_ctx* ctx, const pcr_cloud* db, const pcr_cloud* q, double r,
         }
         ProfScope ps(ctx, "radius_grid_build");
         Grid* built = nullptr;
-        int rc = grid_build(ctx, db, &built, std::max(r * 1.01, 2e-15));
+        int rc = grid_build(ctx, db, &built, radius_cell_edge(r));
         if (rc) return rc;
         mdb->rad_grid = built;
         mdb->rad_grid_r = r;

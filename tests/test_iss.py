@@ -210,6 +210,48 @@ def test_gpu_iss_lidar_scan_and_edges(pcr, orc, synth):
         ctx.close()
 
 
+BAR_R = 0.125
+
+
+def iss_bar_cloud():
+    """a bar in the manner of tests/test_radius_routes.py: 2 048 points at x = 1 + k 2^-12 that take three lines in turn — (y, z) =
+    (2.125, 2.125), (2.125 + 2^-6, 2.125), (2.125, 2.125 + 2^-7): the covariances are not rank one and their two small eigenvalues
+    differ by a factor of six — and 40 scattered points.  At r = 0.125 a three-cell row of the grid (edge 1.01 r) holds about 1 550
+    bar points, far above the 384 records at which the row clip starts to search, and the window of a bar point away from the ends
+    (+- 512 points) cuts that row on both sides."""
+    k = np.arange(2048)
+    line = k % 3
+    bar = np.stack([1.0 + k * 2.0 ** -12, 2.125 + (line == 1) * 2.0 ** -6, 2.125 + (line == 2) * 2.0 ** -7], 1)
+    far = np.random.default_rng(7).uniform([0.5, 1.6, 1.6], [2.0, 2.6, 2.6], (40, 3))
+    pts = np.concatenate([bar, far])
+    return np.ascontiguousarray(pts[np.random.default_rng(8).permutation(pts.shape[0])].astype(np.float32))
+
+
+def test_iss_bar_cloud_has_a_row_above_the_clip_threshold(orc):
+    """what test_gpu_iss_row_above_the_clip_threshold relies on, without a GPU"""
+    from test_random_sweeps_stages import CLIP, longest_row
+    xyz = iss_bar_cloud()
+    assert longest_row(xyz, BAR_R) > 3 * CLIP
+    cnt = np.diff(orc.radius_f32(xyz, xyz, BAR_R)[0])
+    # one bar point per 2^-12 of x: at most 513 members on one side, itself included, so a point with 1 000 members has them on both
+    # sides, and fewer than its row holds: the window cuts the row at both ends (bar points 512 .. 1535 have the full +- 0.125)
+    assert cnt.max() <= 1025 and (cnt >= 1000).sum() >= 1000
+    key, l3 = orc.iss_f32(np.ascontiguousarray(xyz.T), BAR_R, BAR_R, 0.9, 0.9, 5, True)
+    assert (l3 > 0).sum() > 1500 and 0 < key.sum() < 100                         # the gamma tests pass along the bar; a few maxima
+
+
+@pytest.mark.gpu
+def test_gpu_iss_row_above_the_clip_threshold(pcr, orc):
+    ctx = pcr.Context(0)
+    try:
+        for lanes in (1, 4, 8, 32):
+            ctx.tune("iss_lanes", lanes)
+            idx, l3 = check_gpu_against_oracle(ctx, orc, iss_bar_cloud(), BAR_R, BAR_R)
+            assert idx.size > 0
+    finally:
+        ctx.close()
+
+
 @pytest.mark.gpu
 def test_gpu_iss_full_scan_properties(pcr, synth):
     """120 k-point scan (BASELINE configs[1] size): no O(n^2) oracle — size-independent properties instead."""

@@ -15,7 +15,7 @@ test, so that a wrong builder cannot hide a failure:
   clusters  L distinct points on a 2^-10 sub-lattice (the first L of a 26^3 cube) centred in a lattice void (0.125 + 0.25 i, 1.875, 1.875):
             the void centre has exactly L neighbours at r = 0.1 (the cube's corner is 0.0211 from the centre, the nearest lattice point
             0.2165), L on both sides of every CAP class edge
-  bar       2 048 points at x = 1 + k 2^-12, y = z = 2.125: more than 256 records in the three-cell x range, so clip_x searches; a query
+  bar       2 048 points at x = 1 + k 2^-12, y = z = 2.125: more than 256 records in the three-cell x range, so clip_row_x<256> searches; a query
             at bar point 512 with r = 0.125 has 1 025 members, two of them at exactly d == r
   shell     the 150 integer vectors with |v|^2 = 625 scaled by 2^-8 around (0.125, 0.125, 0.125): all at exactly d == r = 25/256; a second
             copy one f32 ulp outward along the largest component, a third one ulp inward (inside member()'s f32 band: f64 decides)

@@ -41,7 +41,7 @@ FIXED_KIND = (0, 2, 3, 0, 2, 3, 1, 0, 1, 2, 1)                      # (a lattice
 LANES = (1, 2, 4, 8, 16, 32)
 LATTICE_R = (0.5, 1.0, 1.5, 0.75)                                   # r2 exact in f32; axis neighbours sit exactly on the first three, nobody on 0.75
 ON_BOUNDARY_R = (0.5, 1.0, 1.5)
-CLIP = 384                                                          # clip_row_x / cl_clip_row_x search rows longer than this
+CLIP = 384                                                          # clip_row_x<384> (grid_walk.hpp) searches rows longer than this
 DENSE_MIN = 9 * CLIP + 1                                            # neighbours that force a clipped row among the nine a point walks
 FRAGILE_CAP = 1e-3                                                  # the share of SPFH rows the restatement may mark fragile
 
