@@ -112,7 +112,7 @@ ABI_SYMBOLS = [
     "pcr_ctx_trim", "pcr_ctx_parked_bytes", "pcr_cloud_shard_spatial", "pcr_cloud_global_index", "pcr_cloud_sort_for_target", "pcr_nn1_f32_loop",
     "pcr_db64_radius_rows", "pcr_rows_destroy", "pcr_rows_info", "pcr_rows_row_ptr", "pcr_rows_fetch", "pcr_rows_reduce", "pcr_rows_moments",
     "pcr_dbscan_f32", "pcr_statistical_outlier_f32", "pcr_fpfh33_f32", "pcr_harris3d_f32", "pcr_voxel_grid_normals_f32", "pcr_normal_space_sample_f32",
-    "pcr_fps_f32", "pcr_ball_query_f32", "pcr_group_points_f32", "pcr_objects_from_labels_f32",
+    "pcr_fps_f32", "pcr_ball_query_f32", "pcr_group_points_f32", "pcr_objects_from_labels_f32", "pcr_points_in_boxes_f64", "pcr_label_aabb_f32",
     "pcr_pn2_model_create", "pcr_pn2_model_destroy", "pcr_pn2_model_info", "pcr_sa_mlp_max_f32", "pcr_pn2_forward_f32",
     "pcr_pn2_msg_model_create", "pcr_pn2_msg_model_info", "pcr_ball_query_multi_f32", "pcr_sa_msg_mlp_max_f32",
     "pcr_mat64_create", "pcr_mat64_destroy", "pcr_mat64_info", "pcr_kmeans_step_f64", "pcr_kmeans_fit_f64", "pcr_kmeans_predict_f64", "pcr_kmeanspp_init_f64",
@@ -223,6 +223,8 @@ def lib():
     L.pcr_ball_query_f32.argtypes = [vp, vp, vp, vp, vp, sz, C.c_double, sz, vp, vp]
     L.pcr_group_points_f32.argtypes = [vp, vp, vp, vp, vp, sz, vp, sz, vp, sz, vp, vp]
     L.pcr_objects_from_labels_f32.argtypes = [vp, vp, vp, sz, sz, C.c_double, C.c_double, vp, C.c_uint64, vp, vp, vp, vp, vp, vp, vp, C.POINTER(sz)]
+    L.pcr_points_in_boxes_f64.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp, sz, vp, C.POINTER(C.c_uint64)]
+    L.pcr_label_aabb_f32.argtypes = [vp, vp, vp, sz, vp, vp]
     ip = C.POINTER(C.c_int)
     L.pcr_pn2_model_create.argtypes = [vp, C.POINTER(Pn2Desc), vp, sz, C.POINTER(vp)]
     L.pcr_pn2_model_destroy.argtypes = [vp, vp]
@@ -1311,6 +1313,42 @@ class Context:
             off += rows * int(k)
         cnt = np.ascontiguousarray(cnt[:, :rows]) if rows else np.zeros((ns.size, 0), np.uint32)
         return blocks, cnt
+
+    # ---- HomeworkFinal: the box operators of the dataset build and of the labelled output
+    def points_in_boxes(self, cloud: Cloud, seg_ptr, boxes, box_seg_ptr, want_hits: bool = True):
+        """The points of every segment inside each of its oriented boxes -> (row_ptr u64 [n_boxes + 1], segment-local indices u32 [total],
+        ascending inside a row, hits u32 [len(cloud)] or None); the contract of pcr_points_in_boxes_f64.  boxes: [n_boxes, 15] f64 rows of
+        (centre 3 | R row-major 9, column a = box axis a | extent 3).  Two calls: the counting one, then the one that fills."""
+        sp, bp = self._seg(seg_ptr), self._seg(box_seg_ptr)
+        if sp.size != bp.size:
+            raise PcrError("the two seg_ptr arrays describe the same segments")
+        bx = np.ascontiguousarray(boxes, np.float64).reshape(-1, 15)
+        if bx.shape[0] < int(bp[-1]):
+            raise PcrError("box_seg_ptr ends beyond the boxes")
+        nb = int(bp[-1])
+        row_ptr = np.zeros(nb + 1, np.uint64)
+        hits = np.zeros(max(len(cloud), 1), np.uint32) if want_hits else None
+        total = C.c_uint64()
+        args = (self.h, cloud.h, sp.ctypes.data, sp.size - 1, bx.ctypes.data if nb else None, bp.ctypes.data, row_ptr.ctypes.data)
+        rc = lib().pcr_points_in_boxes_f64(*args, None, 0, None if hits is None else hits.ctypes.data, C.byref(total))
+        if rc != 0 and not (rc == -1 and total.value > 0):
+            self._ck(rc)
+        idx = np.zeros(max(int(total.value), 1), np.uint32)
+        if total.value:
+            self._ck(lib().pcr_points_in_boxes_f64(*args, idx.ctypes.data, int(total.value), None, None))
+        return row_ptr, idx[: int(total.value)], (None if hits is None else hits[: len(cloud)])
+
+    def label_aabb(self, cloud: Cloud, labels, n_clusters: int):
+        """Per cluster the exact f32 (min x, min y, min z, max x, max y, max z) and the member count -> (aabb f32 [n_clusters, 6], counts u32
+        [n_clusters]); the contract of pcr_label_aabb_f32 ((+inf, -inf) for an empty cluster, label -1 skipped)."""
+        lb = np.ascontiguousarray(labels, np.int32).reshape(-1)
+        if lb.size != len(cloud):
+            raise PcrError("one label per point")
+        k = int(n_clusters)
+        aabb = np.zeros((max(k, 1), 6), np.float32)
+        cnt = np.zeros(max(k, 1), np.uint32)
+        self._ck(lib().pcr_label_aabb_f32(self.h, cloud.h, lb.ctypes.data if lb.size else None, k, aabb.ctypes.data, cnt.ctypes.data))
+        return aabb[:k], cnt[:k]
 
     def pn2_msg_model(self, desc, weights) -> Pn2Model:
         """desc: a Pn2MsgDesc (pn2_msg_desc(...)); weights: the flat f32 array, layer by layer, branch by branch, convolution by convolution,

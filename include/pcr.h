@@ -573,6 +573,47 @@ int pcr_objects_from_labels_f32(pcr_ctx* ctx, const pcr_cloud* cloud, const int3
                                 double z_min_above_ground, const double z_extent[2], uint64_t seed, const uint32_t* starts, float* objects,
                                 uint32_t* object_cluster, uint32_t* source_index, int32_t* codes, float* z_min_max, uint32_t* sizes, size_t* n_objects);
 
+/* ---- HomeworkFinal: the two box operators — the points inside ORIENTED boxes (dataset_building/dataset_build.py:97-125, Open3D's
+ * OrientedBoundingBox::GetPointIndicesWithinBoundingBox) and the AXIS-ALIGNED box of every cluster (foreground_obj_cls.py:190-199) -------
+ * pcr_obox: centre, R row-major whose COLUMN a is box axis a, extent = the full edge lengths along the three axes.
+ *
+ * pcr_points_in_boxes_f64 — many points against a few boxes, on SEGMENTS as pcr_ball_query_f32: segment s of the cloud, the points
+ *   [seg_ptr[s], seg_ptr[s + 1]), is tested against the boxes [box_seg_ptr[s], box_seg_ptr[s + 1]) only (a batch of frames is one call; boxes
+ *   holds box_seg_ptr[n_seg] entries, n_boxes below).  Every index returned is SEGMENT-LOCAL.
+ *   Membership: point p (the f32 coordinates widened to f64) is inside box b iff |t_a| <= extent[a] * 0.5 for a = 0, 1, 2, with d = p - centre
+ *   and t_a = (d0*R[0][a] + d1*R[1][a]) + d2*R[2][a], every operation rounded, unfused, left to right: the CLOSED box of Open3D.  A comparison
+ *   with NaN is false: a non-finite point is in no box, and a box with a non-finite field (centre, R or extent) holds nothing.  R is used as
+ *   given (orthonormality is not checked).  extent[a] == 0 is legal: a rectangle, which holds the points exactly on it.
+ *   row_ptr: n_boxes + 1 (host), ALWAYS written: row b of idx is [row_ptr[b], row_ptr[b + 1]) = the members of box b in ASCENDING index (the
+ *   order of Open3D's loop, so points[idx] is the instance dataset_build.py writes).  hits (optional): one entry per point OF THE CLOUD, the
+ *   number of boxes of its segment that hold it (0 for a point in no segment): hits == 0 is the mask of other_obj_idx.  total (optional) =
+ *   row_ptr[n_boxes].  When idx_cap < total, idx is left alone and the call returns PCR_ERR_ARG with row_ptr, hits and total valid (the
+ *   convention of pcr_s3_walk_visits): idx == NULL with idx_cap == 0 is the counting call.
+ *   The rows are the same bits in the same order under any launch geometry: a position is a prefix sum of ballot popcounts, never the
+ *   outcome of an atomic.  Tune key pib_tile [512]: the points per workgroup, clamped to 64 ... 2048 and rounded down to a multiple of 64
+ *   (results never depend on it).  Profile names pib_count, pib_scan, pib_fill.
+ *   PCR_ERR_ARG: NULL ctx / cloud / seg_ptr / box_seg_ptr / row_ptr, or boxes with n_boxes > 0, or idx with total > 0 and room for it; a seg_ptr
+ *   that descends or ends beyond the cloud, a box_seg_ptr that descends; a negative extent; more than 2^31 - 16 points or boxes, or
+ *   sum over segments of (boxes x ceil(points / pib_tile)) beyond that.  n_seg == 0 or no boxes: PCR_OK, row_ptr all zero, hits all zero.
+ *   PCR_ERR_STATE for a row_ptr that descends (never in a correct run).
+ *
+ * pcr_label_aabb_f32 — per cluster id c < n_clusters the exact f32 minimum and maximum of x, y, z over the points with labels[i] == c, and
+ *   the member count; labels: n int32 (host) as pcr_dbscan_f32 writes them, -1 (noise) is skipped.  aabb: n_clusters x 6 =
+ *   (min x, min y, min z, max x, max y, max z), which is AxisAlignedBoundingBox.create_from_points's (min_bound, max_bound); counts
+ *   (optional): n_clusters.  The library's own rules where the reference has none: an EMPTY cluster gives (+inf, -inf) in every coordinate;
+ *   a NaN coordinate is skipped IN THAT COORDINATE (fminf / fmaxf; the point still counts as a member), so a coordinate that is NaN in every
+ *   member also gives (+inf, -inf); -0 orders below +0.  Min and max do not depend on order: the same bits for any permutation of the input
+ *   and any launch geometry.  PCR_ERR_ARG: NULL ctx / cloud / labels / aabb with something to do; a label outside [-1, n_clusters);
+ *   n > 2^31 - 16.  n_clusters == 0: PCR_OK, nothing written.  Profile name label_aabb. */
+typedef struct pcr_obox {
+    double centre[3];
+    double R[9];
+    double extent[3];
+} pcr_obox;
+int pcr_points_in_boxes_f64(pcr_ctx* ctx, const pcr_cloud* cloud, const uint32_t* seg_ptr, size_t n_seg, const pcr_obox* boxes,
+                            const uint32_t* box_seg_ptr, uint64_t* row_ptr, uint32_t* idx, size_t idx_cap, uint32_t* hits, uint64_t* total);
+int pcr_label_aabb_f32(pcr_ctx* ctx, const pcr_cloud* cloud, const int32_t* labels, size_t n_clusters, float* aabb, uint32_t* counts);
+
 /* ---- HomeworkFinal: the PointNet++ (SSG) classifier, HomeworkFinal/models/pointnet2_cls_ssg.py + pointnet_util.py:159-215, eval mode -----------
  * A model is a chain of up to 4 set-abstraction (SA) layers and up to 4 fully connected (FC) layers, described by pcr_pn2_desc:
  *   D0         feature channels of the input besides xyz (0: xyz only, 3: normal_channel)
