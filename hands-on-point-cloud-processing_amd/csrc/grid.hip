@@ -189,14 +189,16 @@ __global__ __launch_bounds__(GR_BLOCK) void record_keys_kernel(const float* __re
     vals[i] = i;
 }
 
-// one thread per run of GRID_CHUNK records: bounding sphere of its finite members (centre = middle of their box, radius rounded up)
-__global__ __launch_bounds__(GR_BLOCK) void build_spheres_kernel(const float4* __restrict__ records, uint32_t n_chunks, float4* __restrict__ spheres)
+// one thread per run of LEN records: bounding sphere of its finite members (centre = middle of their box, radius rounded up).
+// LEN = GRID_CHUNK: Grid::spheres; LEN = 32: BtIndex::tile_spheres (the tiles of the sign tile search, grid_stile.hpp)
+template <int LEN>
+__global__ __launch_bounds__(GR_BLOCK) void build_spheres_kernel(const float4* __restrict__ records, uint32_t n_runs, float4* __restrict__ spheres)
 {
     const uint32_t c = blockIdx.x * GR_BLOCK + threadIdx.x;
-    if (c >= n_chunks) return;
+    if (c >= n_runs) return;
     float mn[3] = { FLT_MAX, FLT_MAX, FLT_MAX }, mx[3] = { -FLT_MAX, -FLT_MAX, -FLT_MAX };
-    for (int j = 0; j < GRID_CHUNK; j++) {
-        const float4 r = records[(size_t)c * GRID_CHUNK + j];
+    for (int j = 0; j < LEN; j++) {
+        const float4 r = records[(size_t)c * LEN + j];
         if (finite3(r.x, r.y, r.z)) {
             mn[0] = fminf(mn[0], r.x); mn[1] = fminf(mn[1], r.y); mn[2] = fminf(mn[2], r.z);
             mx[0] = fmaxf(mx[0], r.x); mx[1] = fmaxf(mx[1], r.y); mx[2] = fmaxf(mx[2], r.z);
@@ -205,8 +207,8 @@ __global__ __launch_bounds__(GR_BLOCK) void build_spheres_kernel(const float4* _
     if (mn[0] > mx[0]) { spheres[c] = make_float4(0.f, 0.f, 0.f, -1.0f); return; }     // no finite member: radius < 0 = never opened
     const float cx = 0.5f * mn[0] + 0.5f * mx[0], cy = 0.5f * mn[1] + 0.5f * mx[1], cz = 0.5f * mn[2] + 0.5f * mx[2];
     float r2 = 0.f;
-    for (int j = 0; j < GRID_CHUNK; j++) {
-        const float4 r = records[(size_t)c * GRID_CHUNK + j];
+    for (int j = 0; j < LEN; j++) {
+        const float4 r = records[(size_t)c * LEN + j];
         if (finite3(r.x, r.y, r.z)) {
             const float dx = r.x - cx, dy = r.y - cy, dz = r.z - cz;
             r2 = fmaxf(r2, (dx * dx + dy * dy) + dz * dz);
@@ -399,15 +401,9 @@ __device__ __forceinline__ void scan_flat9(const float4* __restrict__ records, c
 
 // minimum key over the sub-group, together with the record position that produced it
 template <int CTRL>
-__device__ __forceinline__ uint32_t dpp_mov(uint32_t x)
-{
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, 0xF, 0xF, false);
-}
-
-template <int CTRL>
 __device__ __forceinline__ void min_step_dpp(unsigned long long& v, uint32_t& pos)
 {
-    const unsigned long long w = ((unsigned long long)dpp_mov<CTRL>((uint32_t)(v >> 32)) << 32) | dpp_mov<CTRL>((uint32_t)v);
+    const unsigned long long w = key_dpp<CTRL>(v);
     const uint32_t wp = dpp_mov<CTRL>(pos);
     if (w < v) { v = w; pos = wp; }
 }
@@ -1095,26 +1091,47 @@ int exclusive_scan_u32(pcr_ctx* ctx, const uint32_t* in, uint32_t* out, size_t n
     return PCR_OK;
 }
 
+// Bounding box of the finite points of a cloud of n > 0 points, the one host round trip of an index build: bbox_kernel into `dev` (the caller's
+// buffer, bbox_blocks(n) * 6 floats), one copy + synchronise, the fold over the blocks here.  A block without a finite point reports lo > hi and
+// drops out of the fold; *any = false when every block did (lo and hi are then +-FLT_MAX: each caller has its own rule for that).
+static uint32_t bbox_blocks(size_t n) { return (uint32_t)std::min<size_t>(256, (n + GR_BLOCK - 1) / GR_BLOCK); }
+static hipError_t cloud_bbox(pcr_ctx* ctx, const pcr_cloud* c, float* dev, float (&lo)[3], float (&hi)[3], bool* any)
+{
+    const uint32_t blocks = bbox_blocks(c->n);
+    hipLaunchKernelGGL(bbox_kernel, dim3(blocks), dim3(GR_BLOCK), 0, ctx->stream, c->x(), c->y(), c->z(), (uint32_t)c->n, dev);
+    std::vector<float> hb(blocks * 6);
+    hipError_t e = hipMemcpyAsync(hb.data(), dev, hb.size() * sizeof(float), hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) return e;
+    for (int k = 0; k < 3; k++) { lo[k] = FLT_MAX; hi[k] = -FLT_MAX; }
+    for (uint32_t b = 0; b < blocks; b++)
+        for (int k = 0; k < 3; k++) { lo[k] = std::min(lo[k], hb[b * 6 + k]); hi[k] = std::max(hi[k], hb[b * 6 + 3 + k]); }
+    *any = lo[0] <= hi[0];
+    return hipSuccess;
+}
+// largest |coordinate| of a box: of all the values in [lo, hi] the ends are the largest in magnitude, so this IS the maximum over the blocks
+// (and over the points) that a fold of max(|lo|, |hi|) block by block gives
+static float bbox_absmax(const float (&lo)[3], const float (&hi)[3])
+{
+    float a = 0.f;
+    for (int k = 0; k < 3; k++) a = std::max(a, std::max(std::fabs(lo[k]), std::fabs(hi[k])));
+    return a;
+}
+
 // largest finite |coordinate| of the cloud (0 when it has no finite point), cached on the cloud until it is modified
 int cloud_absmax(pcr_ctx* ctx, const pcr_cloud* c, float* out)
 {
     if (c->absmax >= 0.f) { *out = c->absmax; return PCR_OK; }
     float a = 0.f;
     if (c->n) {
-        const uint32_t bb_blocks = (uint32_t)std::min<size_t>(256, (c->n + GR_BLOCK - 1) / GR_BLOCK);
         float* dev = nullptr;
-        PCR_HIP(ctx, hipMalloc((void**)&dev, bb_blocks * 6 * sizeof(float)));       // not the shared scratch: callers may be using it
-        hipLaunchKernelGGL(bbox_kernel, dim3(bb_blocks), dim3(GR_BLOCK), 0, ctx->stream, c->x(), c->y(), c->z(), (uint32_t)c->n, dev);
-        std::vector<float> hb(bb_blocks * 6);
-        hipError_t e = hipMemcpyAsync(hb.data(), dev, hb.size() * sizeof(float), hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        PCR_HIP(ctx, hipMalloc((void**)&dev, bbox_blocks(c->n) * 6 * sizeof(float)));       // not the shared scratch: callers may be using it
+        float lo[3], hi[3];
+        bool any = false;
+        const hipError_t e = cloud_bbox(ctx, c, dev, lo, hi, &any);
         hipFree(dev);
         if (e != hipSuccess) return fail(ctx, PCR_ERR_HIP, "cloud_absmax", e);
-        for (uint32_t b = 0; b < bb_blocks; b++)
-            for (int k = 0; k < 3; k++) {
-                const float lo = hb[b * 6 + k], hi = hb[b * 6 + 3 + k];
-                if (lo <= hi) a = std::max(a, std::max(std::fabs(lo), std::fabs(hi)));      // a block without a finite point reports lo > hi
-            }
+        if (any) a = bbox_absmax(lo, hi);
     }
     const_cast<pcr_cloud*>(c)->absmax = a;
     *out = a;
@@ -1143,21 +1160,15 @@ int grid_build(pcr_ctx* ctx, const pcr_cloud* c, Grid** out, double cell_edge, i
     GridPtr g_owner(g);                                             // grid_free takes a partially built grid
     g->n_points = n;
     // 1. bounding box of the finite points
-    const uint32_t bb_blocks = (uint32_t)std::min<size_t>(256, (n + GR_BLOCK - 1) / GR_BLOCK ? (n + GR_BLOCK - 1) / GR_BLOCK : 1);
-    int rc = ensure_scratch(ctx, bb_blocks * 6 * sizeof(float));
+    int rc = ensure_scratch(ctx, std::max(bbox_blocks(n), 1u) * 6 * sizeof(float));
     if (rc) return rc;
-    float lo[3] = { 0, 0, 0 }, hi[3] = { 0, 0, 0 };
+    float lo[3], hi[3];
+    bool any = false;
     if (n) {
-        hipLaunchKernelGGL(bbox_kernel, dim3(bb_blocks), dim3(GR_BLOCK), 0, ctx->stream, c->x(), c->y(), c->z(), (uint32_t)n, (float*)ctx->scratch);
-        std::vector<float> hb(bb_blocks * 6);
-        hipError_t e = hipMemcpyAsync(hb.data(), ctx->scratch, hb.size() * sizeof(float), hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        const hipError_t e = cloud_bbox(ctx, c, (float*)ctx->scratch, lo, hi, &any);
         if (e != hipSuccess) return fail(ctx, PCR_ERR_HIP, "bbox", e);
-        for (int k = 0; k < 3; k++) { lo[k] = FLT_MAX; hi[k] = -FLT_MAX; }
-        for (uint32_t b = 0; b < bb_blocks; b++)
-            for (int k = 0; k < 3; k++) { lo[k] = std::min(lo[k], hb[b * 6 + k]); hi[k] = std::max(hi[k], hb[b * 6 + 3 + k]); }
-        if (lo[0] > hi[0]) { for (int k = 0; k < 3; k++) lo[k] = hi[k] = 0.f; }   // no finite point at all
     }
+    if (!any) { for (int k = 0; k < 3; k++) lo[k] = hi[k] = 0.f; }   // no point, or no finite point at all
     // 2. cell size.  First guess ~ 4 n cells in the bounding volume; LiDAR clouds are surfaces, so most of those
     //    cells are empty and the occupied ones are crowded: measure the occupancy and shrink h once so that an
     //    occupied cell holds ~ grid_occupancy_x10 / 10 points (points per occupied cell ~ h^2 on surfaces).
@@ -1294,7 +1305,7 @@ int grid_build(pcr_ctx* ctx, const pcr_cloud* c, Grid** out, double cell_edge, i
                            (uint32_t)g->n_chunks, g->chunks, unsafe_dev);
         e = hipMalloc((void**)&g->spheres, g->n_chunks * sizeof(float4));
         if (e != hipSuccess) return fail(ctx, PCR_ERR_HIP, "hipMalloc(grid spheres)", e);
-        hipLaunchKernelGGL(build_spheres_kernel, dim3((unsigned)((g->n_chunks + GR_BLOCK - 1) / GR_BLOCK)), dim3(GR_BLOCK), 0, ctx->stream, g->records,
+        hipLaunchKernelGGL(build_spheres_kernel<GRID_CHUNK>, dim3((unsigned)((g->n_chunks + GR_BLOCK - 1) / GR_BLOCK)), dim3(GR_BLOCK), 0, ctx->stream, g->records,
                            (uint32_t)g->n_chunks, g->spheres);
         e = hipMemcpyAsync(&unsafe_host, unsafe_dev, 4, hipMemcpyDeviceToHost, ctx->stream);
         if (e != hipSuccess) return fail(ctx, PCR_ERR_HIP, "grid chunks", e);
@@ -1304,6 +1315,17 @@ int grid_build(pcr_ctx* ctx, const pcr_cloud* c, Grid** out, double cell_edge, i
     if (e != hipSuccess) return fail(ctx, PCR_ERR_HIP, "grid build", e);
     g->chunk_safe = g->n_chunks != 0 && unsafe_host == 0;
     *out = g_owner.release();
+    return PCR_OK;
+}
+
+// room for the order of n queries in ctx->qperm (grown, never shrunk; the old contents are not kept)
+static int ensure_qperm(pcr_ctx* ctx, size_t n)
+{
+    if (ctx->qperm_cap >= n) return PCR_OK;
+    if (ctx->qperm) PCR_HIP(ctx, hipFree(ctx->qperm));
+    ctx->qperm = nullptr; ctx->qperm_cap = 0;
+    PCR_HIP(ctx, hipMalloc((void**)&ctx->qperm, padded(n) * sizeof(uint32_t)));
+    ctx->qperm_cap = padded(n);
     return PCR_OK;
 }
 
@@ -1335,12 +1357,7 @@ static int sort_queries(pcr_ctx* ctx, const Grid* g, const pcr_cloud* src)
     L.add(&grand, 1);
     int rc = bind_scratch(ctx, L);
     if (rc) return rc;
-    if (ctx->qperm_cap < n) {
-        if (ctx->qperm) PCR_HIP(ctx, hipFree(ctx->qperm));
-        ctx->qperm = nullptr; ctx->qperm_cap = 0;
-        PCR_HIP(ctx, hipMalloc((void**)&ctx->qperm, padded(n) * sizeof(uint32_t)));
-        ctx->qperm_cap = padded(n);
-    }
+    if ((rc = ensure_qperm(ctx, n))) return rc;
     PCR_HIP(ctx, hipMemsetAsync(count, 0, (cells + 1) * 4, ctx->stream));
     const dim3 gridn((unsigned)((n + GR_BLOCK - 1) / GR_BLOCK));
     hipLaunchKernelGGL(cell_count_kernel, gridn, dim3(GR_BLOCK), 0, ctx->stream, src->x(), src->y(), src->z(), (uint32_t)n, cp, cell_of, count, 0u);
@@ -1416,12 +1433,7 @@ static int sort_queries_fine(pcr_ctx* ctx, const Grid* g, const pcr_cloud* src)
     L.add(&sort_temp, temp_bytes);
     int rc = bind_scratch(ctx, L);
     if (rc) return rc;
-    if (ctx->qperm_cap < n) {
-        if (ctx->qperm) PCR_HIP(ctx, hipFree(ctx->qperm));
-        ctx->qperm = nullptr; ctx->qperm_cap = 0;
-        PCR_HIP(ctx, hipMalloc((void**)&ctx->qperm, padded(n) * sizeof(uint32_t)));
-        ctx->qperm_cap = padded(n);
-    }
+    if ((rc = ensure_qperm(ctx, n))) return rc;
     hipLaunchKernelGGL(query_keys_kernel, dim3((unsigned)((n + GR_BLOCK - 1) / GR_BLOCK)), dim3(GR_BLOCK), 0, ctx->stream, src->x(), src->y(), src->z(), (uint32_t)n,
                        g->p, (uint32_t)g->n_cells, k_in, v_in);
     hipError_t e = sort_pairs_u64_u32(sort_temp, temp_bytes, k_in, k_out, v_in, ctx->qperm, n, begin_bit, key_bits + QKEY_SUB_BITS, ctx->stream);
@@ -1473,60 +1485,96 @@ __global__ __launch_bounds__(GR_BLOCK) void bt_keys_kernel(const float* __restri
     vals[i] = i;
 }
 
-// one WAVE per super-tile: centre = mean of its finite records (lane l holds records l, l + 64, ...; butterfly sums — a fixed order, so the
-// centre is a pure function of the records), then the largest offset from it.  (One THREAD per super-tile took 74 us at 120 k points:
-// 469 threads walking 256 records twice — a tenth of a fresh target's first search.)
-__global__ __launch_bounds__(GR_BLOCK) void bt_centres_kernel(const float4* __restrict__ rec, uint32_t n_super, float4* __restrict__ centres, int* __restrict__ bad16)
+// the scale of the f16 forms for a super-tile whose records lie within rho (|.|_inf) of its centre: the power of two with rho * scale <= 2^7
+// (exponent clamped to [-60, 60]: *bad, where the caller has such a flag, when it had to be)
+__device__ __forceinline__ float pow2_scale(float rho, int* __restrict__ bad)
 {
-    static_assert(BT_SUPER % 64 == 0 && GR_BLOCK % 64 == 0, "whole waves");
-    constexpr int PER = BT_SUPER / 64;
-    const uint32_t s = blockIdx.x * (GR_BLOCK / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (s >= n_super) return;                                 // (wave-uniform)
-    float4 r[PER];
-    bool fin[PER];
-    float cx = 0.f, cy = 0.f, cz = 0.f, cnt = 0.f;
-#pragma unroll
-    for (int u = 0; u < PER; u++) {
-        r[u] = rec[(size_t)s * BT_SUPER + u * 64 + lane];
-        fin[u] = finite3(r[u].x, r[u].y, r[u].z);
-        if (fin[u]) { cx += r[u].x; cy += r[u].y; cz += r[u].z; cnt += 1.0f; }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { cx += __shfl_xor(cx, o, 64); cy += __shfl_xor(cy, o, 64); cz += __shfl_xor(cz, o, 64); cnt += __shfl_xor(cnt, o, 64); }
-    if (cnt > 0.f) { cx /= cnt; cy /= cnt; cz /= cnt; }
-    // .w: the f16 form's scale, a power of two with |t - C|_inf * scale <= 2^7 (exponent clamped to [-60, 60]: bad16 when it had to be)
-    float rho = 0.f;
-#pragma unroll
-    for (int u = 0; u < PER; u++)
-        if (fin[u]) rho = fmaxf(rho, fmaxf(fmaxf(fabsf(r[u].x - cx), fabsf(r[u].y - cy)), fabsf(r[u].z - cz)));
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) rho = fmaxf(rho, __shfl_xor(rho, o, 64));
-    if (lane != 0) return;
     int k = 0;
     if (rho > 0.f) {
         int e2;
         (void)frexpf(rho, &e2);                            // rho = m 2^e2, m in [0.5, 1)  ->  rho <= 2^e2
         k = 7 - e2;
-        if (k < -60 || k > 60) { if (bad16) atomicOr(bad16, 1); k = k < 0 ? -60 : 60; }
+        if (k < -60 || k > 60) { if (bad) atomicOr(bad, 1); k = k < 0 ? -60 : 60; }
     }
-    centres[s] = make_float4(cx, cy, cz, ldexpf(1.0f, k));
+    return ldexpf(1.0f, k);
+}
+
+// Centre and scale of every super-tile of SUPER records, THREADS threads each (one wave, or the whole workgroup): centre = mean of its
+// finite records, .w = pow2_scale of the largest offset from it.  Thread t sums records t, t + THREADS, ... in ascending order, then the
+// xor butterfly over the wave and, for a workgroup, the fixed tree (w0 + w1) + (w2 + w3) through LDS — a fixed order, so the centre is a
+// pure function of the records.  Up to 16 records per thread stay in registers for the second pass; level 0 has 512 and reads them again,
+// in a loop that ends at n_rec (measured: with the re-read and the padded load in all three instances the first search of a fresh 120 k
+// target took 2 % longer, profiles/index_build_refactor.txt).  Instances: (BT_SUPER, 64) the
+// super-tiles of HTRACK / STRACK, (BT_L1_SUPER, GR_BLOCK) and (BT_L0_SUPER, GR_BLOCK) levels 1 and 0 of STRACK3 (grid_common.hpp: the
+// statement; nn1_sphere.hpp: the search).  (One THREAD per super-tile took 74 us at 120 k points: 469 threads walking 256 records twice —
+// a tenth of a fresh target's first search.)
+template <int SUPER, int THREADS>
+__global__ __launch_bounds__(GR_BLOCK) void bt_centres_kernel(const float4* __restrict__ rec, uint32_t n_rec, uint32_t n_super, float4* __restrict__ centres,
+                                                              int* __restrict__ bad)
+{
+    static_assert((THREADS == 64 || THREADS == GR_BLOCK) && GR_BLOCK == 256 && SUPER % THREADS == 0, "one wave or one workgroup of four per super-tile");
+    constexpr int PER = SUPER / THREADS;
+    constexpr bool KEEP = PER <= 16;
+    constexpr int UNROLL = KEEP ? PER : 1;
+    constexpr bool GROUP = THREADS == GR_BLOCK;
+    __shared__ float red[4][GR_BLOCK / 64];
+    const uint32_t s = blockIdx.x * (GR_BLOCK / THREADS) + threadIdx.x / THREADS, t = threadIdx.x % THREADS, wave = threadIdx.x >> 6;
+    if (s >= n_super) return;                                 // (uniform over the super-tile's threads: a wave, or the workgroup and its barriers)
+    const size_t base = (size_t)s * SUPER + t, end = min((size_t)s * SUPER + SUPER, (size_t)n_rec);
+    const int mine = KEEP ? PER : end > base ? (int)((end - base + THREADS - 1) / THREADS) : 0;      // this thread's records (KEEP: padded to PER)
+    float4 r[KEEP ? PER : 1];
+    float cx = 0.f, cy = 0.f, cz = 0.f, cnt = 0.f;
+#pragma unroll UNROLL
+    for (int u = 0; u < mine; u++) {
+        const float4 q = KEEP ? padded_record(rec, base + (size_t)u * THREADS, n_rec) : rec[base + (size_t)u * THREADS];
+        if (KEEP) r[u] = q;
+        if (finite3(q.x, q.y, q.z)) { cx += q.x; cy += q.y; cz += q.z; cnt += 1.0f; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { cx += __shfl_xor(cx, o, 64); cy += __shfl_xor(cy, o, 64); cz += __shfl_xor(cz, o, 64); cnt += __shfl_xor(cnt, o, 64); }
+    if (GROUP) {
+        if ((t & 63) == 0) { red[0][wave] = cx; red[1][wave] = cy; red[2][wave] = cz; red[3][wave] = cnt; }
+        __syncthreads();
+        cx = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]); cy = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
+        cz = (red[2][0] + red[2][1]) + (red[2][2] + red[2][3]); cnt = (red[3][0] + red[3][1]) + (red[3][2] + red[3][3]);
+    }
+    if (cnt > 0.f) { cx /= cnt; cy /= cnt; cz /= cnt; }
+    if (!finite3(cx, cy, cz)) { cx = 0.f; cy = 0.f; cz = 0.f; if (t == 0 && bad) atomicOr(bad, 1); }      // (sums beyond f32: no f16 form for this cloud)
+    float rho = 0.f;
+#pragma unroll UNROLL
+    for (int u = 0; u < mine; u++) {
+        const float4 q = KEEP ? r[u] : rec[base + (size_t)u * THREADS];
+        if (finite3(q.x, q.y, q.z)) rho = fmaxf(rho, fmaxf(fmaxf(fabsf(q.x - cx), fabsf(q.y - cy)), fabsf(q.z - cz)));
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) rho = fmaxf(rho, __shfl_xor(rho, o, 64));
+    if (GROUP) {
+        __syncthreads();
+        if ((t & 63) == 0) red[0][wave] = rho;
+        __syncthreads();
+    }
+    if (t != 0) return;
+    if (GROUP) rho = fmaxf(fmaxf(red[0][0], red[0][1]), fmaxf(red[0][2], red[0][3]));
+    centres[s] = make_float4(cx, cy, cz, pow2_scale(rho, bad));
 }
 
 // HTRACK operands: one thread per MFMA row (record) of a tile.  K slots of a lane: lanes < 32  [x: (1,1) (1,2) (2,1) (2,2) | y: the same],
 // lanes >= 32  [z: the same | w1, w2, 0, 0]  against the query side [r1, r1, r2, r2] per coordinate and [1, 1, 0, 0];  A holds the
 // two f16 pieces of -2 t'' scale (round to zero, then the remainder) and of w = |t'' scale|^2 (1 - 2^-17).
-__global__ __launch_bounds__(GR_BLOCK) void bt_ops16_kernel(const float4* __restrict__ rec, uint32_t n_tiles, const float4* __restrict__ centres,
-                                                            uint4* __restrict__ ops16)
+// Instances: (BT_SUPER, false) BtIndex::ops16, in the scale of the record's super-tile; (BT_L1_SUPER, true) BtIndex::l1_rec_ops, the same rows in
+// the scale of the record's LEVEL-1 super-tile, where a record of a super-tile flagged bad counts as absent (RANGE: |t''| <= 128)
+template <int SUPER, bool RANGE>
+__global__ __launch_bounds__(GR_BLOCK) void bt_rec_ops_kernel(const float4* __restrict__ rec, uint32_t n_tiles, const float4* __restrict__ centres,
+                                                              uint4* __restrict__ ops)
 {
     const uint32_t gid = blockIdx.x * GR_BLOCK + threadIdx.x;
     const uint32_t T = gid >> 5, m = gid & 31;
     if (T >= n_tiles) return;
-    const uint32_t p = T * 32 + 16 * ((m >> 2) & 1) + 4 * (m >> 3) + (m & 3);
-    const float4 r = rec[p];
-    const float4 C = centres[T / (BT_SUPER / 32)];
-    const bool fin = finite3(r.x, r.y, r.z);
-    const float tx = (r.x - C.x) * C.w, ty = (r.y - C.y) * C.w, tz = (r.z - C.z) * C.w;         // exact scaling, |.| <= 2^7 (unless bad16)
-    uint4* o = ops16 + (size_t)T * 64;
+    const float4 r = rec[T * 32 + mfma_row_record(m)];
+    const float4 C = centres[T / (SUPER / 32)];
+    const float tx = (r.x - C.x) * C.w, ty = (r.y - C.y) * C.w, tz = (r.z - C.z) * C.w;         // exact scaling, |.| <= 2^7 (unless the super-tile is flagged bad)
+    const bool fin = finite3(r.x, r.y, r.z) && (!RANGE || (fabsf(tx) <= 128.0f && fabsf(ty) <= 128.0f && fabsf(tz) <= 128.0f));
+    uint4* o = ops + (size_t)T * 64;
     o[m] = ht_target_operand(tx, ty, tz, fin, false);
     o[32 + m] = ht_target_operand(tx, ty, tz, fin, true);
 }
@@ -1548,8 +1596,7 @@ __global__ __launch_bounds__(GR_BLOCK) void bt_ops_kernel(const float4* __restri
     const uint32_t gid = blockIdx.x * GR_BLOCK + threadIdx.x;
     const uint32_t T = gid >> 5, m = gid & 31;
     if (T >= n_tiles) return;
-    const uint32_t p = T * 32 + 16 * ((m >> 2) & 1) + 4 * (m >> 3) + (m & 3);   // MFMA row m <-> record (nn1_brute.hip)
-    const float4 r = rec[p];
+    const float4 r = rec[T * 32 + mfma_row_record(m)];
     const float4 C = centres[T / (BT_SUPER / 32)];
     uint32_t t[3][3] = { { 0, 0, 0 }, { 0, 0, 0 }, { 0, 0, 0 } }, w[3] = { 0x7F80u, 0, 0 };      // padding / non-finite: w = +inf, never the minimum
     bool bad = !finite3(C.x, C.y, C.z) || fabsf(C.x) > 1e18f || fabsf(C.y) > 1e18f || fabsf(C.z) > 1e18f;
@@ -1586,51 +1633,6 @@ void bt_free(BtIndex* b)
 }
 
 // ---- level 1 of the two-level sign filter (grid_common.hpp: the statement; nn1_sphere.hpp: the search)
-// one workgroup per level-1 super-tile: centre = mean of its finite records, scale = the power of two with |t - C|_inf scale <= 2^7
-__global__ __launch_bounds__(GR_BLOCK) void bt_l1_centres_kernel(const float4* __restrict__ rec, uint32_t n_rec, uint32_t n_l1, float4* __restrict__ centres, int* __restrict__ bad)
-{
-    __shared__ float red[4][GR_BLOCK / 64];
-    const uint32_t s = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (s >= n_l1) return;
-    constexpr int PER = BT_L1_SUPER / GR_BLOCK;
-    float cx = 0.f, cy = 0.f, cz = 0.f, cnt = 0.f;
-    float4 r[PER];
-    bool fin[PER];
-#pragma unroll
-    for (int u = 0; u < PER; u++) {
-        const size_t p = (size_t)s * BT_L1_SUPER + (size_t)u * GR_BLOCK + threadIdx.x;
-        r[u] = p < n_rec ? rec[p] : make_float4(__builtin_inff(), 0.f, 0.f, 0.f);
-        fin[u] = finite3(r[u].x, r[u].y, r[u].z);
-        if (fin[u]) { cx += r[u].x; cy += r[u].y; cz += r[u].z; cnt += 1.0f; }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { cx += __shfl_xor(cx, o, 64); cy += __shfl_xor(cy, o, 64); cz += __shfl_xor(cz, o, 64); cnt += __shfl_xor(cnt, o, 64); }
-    if (lane == 0) { red[0][wave] = cx; red[1][wave] = cy; red[2][wave] = cz; red[3][wave] = cnt; }
-    __syncthreads();
-    cx = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]); cy = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
-    cz = (red[2][0] + red[2][1]) + (red[2][2] + red[2][3]); cnt = (red[3][0] + red[3][1]) + (red[3][2] + red[3][3]);
-    if (cnt > 0.f) { cx /= cnt; cy /= cnt; cz /= cnt; }
-    float rho = 0.f;
-#pragma unroll
-    for (int u = 0; u < PER; u++)
-        if (fin[u]) rho = fmaxf(rho, fmaxf(fmaxf(fabsf(r[u].x - cx), fabsf(r[u].y - cy)), fabsf(r[u].z - cz)));
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) rho = fmaxf(rho, __shfl_xor(rho, o, 64));
-    __syncthreads();
-    if (lane == 0) red[0][wave] = rho;
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    rho = fmaxf(fmaxf(red[0][0], red[0][1]), fmaxf(red[0][2], red[0][3]));
-    int k = 0;
-    if (rho > 0.f) {
-        int e2;
-        (void)frexpf(rho, &e2);                            // rho <= 2^e2
-        k = 7 - e2;
-        if (k < -60 || k > 60) { atomicOr(bad, 1); k = k < 0 ? -60 : 60; }
-    }
-    centres[s] = make_float4(cx, cy, cz, ldexpf(1.0f, k));
-}
-
 // one thread per chunk of 16 records: its row of its level-1 tile (stored row m <-> chunk 2 (m & 15) + (m >> 4): the order STRACK3's
 // transposed level 1 reads — the two chunks of level-2 tile k are rows k and k + 16; see l1_chunk_operand)
 __global__ __launch_bounds__(GR_BLOCK) void bt_l1_ops_kernel(const float4* __restrict__ rec, uint32_t n_rec, uint32_t n_l1_tiles, const float4* __restrict__ centres,
@@ -1645,8 +1647,7 @@ __global__ __launch_bounds__(GR_BLOCK) void bt_l1_ops_kernel(const float4* __res
     bool fin[16];
 #pragma unroll
     for (int j = 0; j < 16; j++) {
-        const size_t p = (size_t)chunk * 16 + j;
-        const float4 r = p < n_rec ? rec[p] : make_float4(__builtin_inff(), 0.f, 0.f, 0.f);
+        const float4 r = padded_record(rec, (size_t)chunk * 16 + j, n_rec);
         tx[j] = (r.x - C.x) * C.w; ty[j] = (r.y - C.y) * C.w; tz[j] = (r.z - C.z) * C.w;       // exact scaling, |.| <= 2^7 (unless the super-tile is flagged bad)
         fin[j] = finite3(r.x, r.y, r.z) && fabsf(tx[j]) <= 128.0f && fabsf(ty[j]) <= 128.0f && fabsf(tz[j]) <= 128.0f;
     }
@@ -1656,65 +1657,8 @@ __global__ __launch_bounds__(GR_BLOCK) void bt_l1_ops_kernel(const float4* __res
     ops[(size_t)T * 64 + 32 + m] = hi;
 }
 
-// the per-record operands in the scale of the record's LEVEL-1 super-tile (bt_ops16_kernel with the level-1 centres: 128 tiles per super-tile)
-__global__ __launch_bounds__(GR_BLOCK) void bt_l1_rec_ops_kernel(const float4* __restrict__ rec, uint32_t n_tiles, const float4* __restrict__ centres, uint4* __restrict__ ops)
-{
-    const uint32_t gid = blockIdx.x * GR_BLOCK + threadIdx.x;
-    const uint32_t T = gid >> 5, m = gid & 31;
-    if (T >= n_tiles) return;
-    const uint32_t p = T * 32 + 16 * ((m >> 2) & 1) + 4 * (m >> 3) + (m & 3);
-    const float4 r = rec[p];
-    const float4 C = centres[T / (BT_L1_SUPER / 32)];
-    const float tx = (r.x - C.x) * C.w, ty = (r.y - C.y) * C.w, tz = (r.z - C.z) * C.w;         // exact scaling, |.| <= 2^7 (unless the super-tile is flagged bad)
-    const bool fin = finite3(r.x, r.y, r.z) && fabsf(tx) <= 128.0f && fabsf(ty) <= 128.0f && fabsf(tz) <= 128.0f;
-    ops[(size_t)T * 64 + m] = ht_target_operand(tx, ty, tz, fin, false);
-    ops[(size_t)T * 64 + 32 + m] = ht_target_operand(tx, ty, tz, fin, true);
-}
-
 // ---- level 0 (STRACK3): one row per level-1 tile = the bounding sphere of its 512 records, in the scale of a level-0 super-tile of
-// BT_L0_SUPER records.  Centres: one workgroup per level-0 super-tile, two passes over its records (mean of the finite ones, then the
-// largest |.|_inf distance from it -> the power-of-two scale with every record inside 2^7 units)
-__global__ __launch_bounds__(GR_BLOCK) void bt_l0_centres_kernel(const float4* __restrict__ rec, uint32_t n_rec, uint32_t n_l0, float4* __restrict__ centres, int* __restrict__ bad)
-{
-    __shared__ float red[4][GR_BLOCK / 64];
-    const uint32_t s = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (s >= n_l0) return;
-    const size_t base = (size_t)s * BT_L0_SUPER, end = min(base + (size_t)BT_L0_SUPER, (size_t)n_rec);
-    float cx = 0.f, cy = 0.f, cz = 0.f, cnt = 0.f;
-    for (size_t p = base + threadIdx.x; p < end; p += GR_BLOCK) {
-        const float4 r = rec[p];
-        if (finite3(r.x, r.y, r.z)) { cx += r.x; cy += r.y; cz += r.z; cnt += 1.0f; }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { cx += __shfl_xor(cx, o, 64); cy += __shfl_xor(cy, o, 64); cz += __shfl_xor(cz, o, 64); cnt += __shfl_xor(cnt, o, 64); }
-    if (lane == 0) { red[0][wave] = cx; red[1][wave] = cy; red[2][wave] = cz; red[3][wave] = cnt; }
-    __syncthreads();
-    cx = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]); cy = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
-    cz = (red[2][0] + red[2][1]) + (red[2][2] + red[2][3]); cnt = (red[3][0] + red[3][1]) + (red[3][2] + red[3][3]);
-    if (cnt > 0.f) { cx /= cnt; cy /= cnt; cz /= cnt; }
-    if (!finite3(cx, cy, cz)) { cx = 0.f; cy = 0.f; cz = 0.f; if (threadIdx.x == 0) atomicOr(bad, 1); }      // (sums beyond f32: no level 0 for this cloud)
-    float rho = 0.f;
-    for (size_t p = base + threadIdx.x; p < end; p += GR_BLOCK) {
-        const float4 r = rec[p];
-        if (finite3(r.x, r.y, r.z)) rho = fmaxf(rho, fmaxf(fmaxf(fabsf(r.x - cx), fabsf(r.y - cy)), fabsf(r.z - cz)));
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) rho = fmaxf(rho, __shfl_xor(rho, o, 64));
-    __syncthreads();
-    if (lane == 0) red[0][wave] = rho;
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    rho = fmaxf(fmaxf(red[0][0], red[0][1]), fmaxf(red[0][2], red[0][3]));
-    int k = 0;
-    if (rho > 0.f) {
-        int e2;
-        (void)frexpf(rho, &e2);                            // rho <= 2^e2
-        k = 7 - e2;
-        if (k < -60 || k > 60) { atomicOr(bad, 1); k = k < 0 ? -60 : 60; }
-    }
-    centres[s] = make_float4(cx, cy, cz, ldexpf(1.0f, k));
-}
-
+// BT_L0_SUPER records (centres: bt_centres_kernel)
 // one wave per level-1 tile: its row of its level-0 tile (stored row m <-> level-1 tile m of the 32: STRACK3's transposed level 0 reads the
 // row mask straight from one ballot; see l1_chunk_operand)
 __global__ __launch_bounds__(GR_BLOCK) void bt_l0_ops_kernel(const float4* __restrict__ rec, uint32_t n_rec, uint32_t n_rows, const float4* __restrict__ centres,
@@ -1729,8 +1673,7 @@ __global__ __launch_bounds__(GR_BLOCK) void bt_l0_ops_kernel(const float4* __res
     bool any = false;
 #pragma unroll
     for (int j = 0; j < 8; j++) {
-        const size_t p = (size_t)T1 * 512 + (size_t)j * 64 + lane;
-        const float4 r = p < n_rec ? rec[p] : make_float4(__builtin_inff(), 0.f, 0.f, 0.f);
+        const float4 r = padded_record(rec, (size_t)T1 * 512 + (size_t)j * 64 + lane, n_rec);
         tx[j] = (r.x - C.x) * C.w; ty[j] = (r.y - C.y) * C.w; tz[j] = (r.z - C.z) * C.w;       // exact scaling, |.| <= 2^7 (unless the super-tile is flagged bad)
         fin[j] = finite3(r.x, r.y, r.z) && fabsf(tx[j]) <= 128.0f && fabsf(ty[j]) <= 128.0f && fabsf(tz[j]) <= 128.0f;
         if (fin[j]) {
@@ -1788,12 +1731,14 @@ int bt_ensure_l1(pcr_ctx* ctx, const pcr_cloud* tgt)
     bt->l1_block = (char*)blk; bt->n_l0_super = n_l0; bt->n_l1_super = n_l1;
     e = hipMemsetAsync(bt->l1_bad, 0, sizeof(int), ctx->stream);
     if (e != hipSuccess) return fail(ctx, PCR_ERR_HIP, "level-1 operands", e);
-    hipLaunchKernelGGL(bt_l1_centres_kernel, dim3((unsigned)n_l1), dim3(GR_BLOCK), 0, ctx->stream, bt->records, (uint32_t)n_pad, (uint32_t)n_l1, bt->l1_centres, bt->l1_bad);
+    hipLaunchKernelGGL((bt_centres_kernel<BT_L1_SUPER, GR_BLOCK>), dim3((unsigned)n_l1), dim3(GR_BLOCK), 0, ctx->stream, bt->records, (uint32_t)n_pad, (uint32_t)n_l1,
+                       bt->l1_centres, bt->l1_bad);
     hipLaunchKernelGGL(bt_l1_ops_kernel, dim3((unsigned)((n_l1_tiles * 32 + GR_BLOCK - 1) / GR_BLOCK)), dim3(GR_BLOCK), 0, ctx->stream, bt->records, (uint32_t)n_pad,
                        (uint32_t)n_l1_tiles, bt->l1_centres, bt->l1_ops);
-    hipLaunchKernelGGL(bt_l1_rec_ops_kernel, dim3((unsigned)((bt->n_tiles * 32 + GR_BLOCK - 1) / GR_BLOCK)), dim3(GR_BLOCK), 0, ctx->stream, bt->records, (uint32_t)bt->n_tiles,
-                       bt->l1_centres, bt->l1_rec_ops);
-    hipLaunchKernelGGL(bt_l0_centres_kernel, dim3((unsigned)n_l0), dim3(GR_BLOCK), 0, ctx->stream, bt->records, (uint32_t)n_pad, (uint32_t)n_l0, bt->l0_centres, bt->l1_bad);
+    hipLaunchKernelGGL((bt_rec_ops_kernel<BT_L1_SUPER, true>), dim3((unsigned)((bt->n_tiles * 32 + GR_BLOCK - 1) / GR_BLOCK)), dim3(GR_BLOCK), 0, ctx->stream, bt->records,
+                       (uint32_t)bt->n_tiles, bt->l1_centres, bt->l1_rec_ops);
+    hipLaunchKernelGGL((bt_centres_kernel<BT_L0_SUPER, GR_BLOCK>), dim3((unsigned)n_l0), dim3(GR_BLOCK), 0, ctx->stream, bt->records, (uint32_t)n_pad, (uint32_t)n_l0,
+                       bt->l0_centres, bt->l1_bad);
     hipLaunchKernelGGL(bt_l0_ops_kernel, dim3((unsigned)((n_l0_tiles * 32 + GR_BLOCK / 64 - 1) / (GR_BLOCK / 64))), dim3(GR_BLOCK), 0, ctx->stream, bt->records, (uint32_t)n_pad,
                        (uint32_t)(n_l0_tiles * 32), bt->l0_centres, bt->l0_ops);
     PCR_HIP(ctx, hipGetLastError());
@@ -1821,32 +1766,6 @@ __global__ __launch_bounds__(GR_BLOCK) void bt_cell_count_kernel(const float4* _
     const bool last = i + 1 == n_rec || (bt_record_key(rec[i + 1], lox, loy, loz, inv) >> shift) != c;
     if (first) atomicSub(&count[c], i);
     if (last) atomicAdd(&count[c], i + 1u);
-}
-
-// bounding sphere of every tile of 32 records (centre = middle of the box of its finite members, radius rounded up; no finite member: radius < 0)
-__global__ __launch_bounds__(GR_BLOCK) void bt_tile_spheres_kernel(const float4* __restrict__ records, uint32_t n_tiles, float4* __restrict__ spheres)
-{
-    const uint32_t t = blockIdx.x * GR_BLOCK + threadIdx.x;
-    if (t >= n_tiles) return;
-    float mn[3] = { FLT_MAX, FLT_MAX, FLT_MAX }, mx[3] = { -FLT_MAX, -FLT_MAX, -FLT_MAX };
-    for (int j = 0; j < 32; j++) {
-        const float4 r = records[(size_t)t * 32 + j];
-        if (finite3(r.x, r.y, r.z)) {
-            mn[0] = fminf(mn[0], r.x); mn[1] = fminf(mn[1], r.y); mn[2] = fminf(mn[2], r.z);
-            mx[0] = fmaxf(mx[0], r.x); mx[1] = fmaxf(mx[1], r.y); mx[2] = fmaxf(mx[2], r.z);
-        }
-    }
-    if (mn[0] > mx[0]) { spheres[t] = make_float4(0.f, 0.f, 0.f, -1.0f); return; }
-    const float cx = 0.5f * mn[0] + 0.5f * mx[0], cy = 0.5f * mn[1] + 0.5f * mx[1], cz = 0.5f * mn[2] + 0.5f * mx[2];
-    float r2 = 0.f;
-    for (int j = 0; j < 32; j++) {
-        const float4 r = records[(size_t)t * 32 + j];
-        if (finite3(r.x, r.y, r.z)) {
-            const float dx = r.x - cx, dy = r.y - cy, dz = r.z - cz;
-            r2 = fmaxf(r2, (dx * dx + dy * dy) + dz * dz);
-        }
-    }
-    spheres[t] = make_float4(cx, cy, cz, sqrtf(r2) * 1.00001f + 1e-30f);    // rounded up (build_spheres_kernel)
 }
 
 __global__ __launch_bounds__(GR_BLOCK) void bt_scatter_gpos_kernel(const float4* __restrict__ grid_rec, uint32_t n_grid, uint32_t n_orig, uint32_t* __restrict__ gpos_of_orig)
@@ -1913,7 +1832,7 @@ int bt_ensure_tile(pcr_ctx* ctx, const pcr_cloud* tgt)
     rc = exclusive_scan_u32(ctx, bt->cell_start, bt->cell_start, n_cells + 2, totals, grand);
     if (rc) return rc;
     uint32_t* gpos = (uint32_t*)ctx->scratch;                 // (stream order: the scan is done with the scratch before the scatter writes it)
-    hipLaunchKernelGGL(bt_tile_spheres_kernel, dim3((unsigned)((n_tiles + GR_BLOCK - 1) / GR_BLOCK)), dim3(GR_BLOCK), 0, ctx->stream, bt->records, (uint32_t)n_tiles,
+    hipLaunchKernelGGL(build_spheres_kernel<32>, dim3((unsigned)((n_tiles + GR_BLOCK - 1) / GR_BLOCK)), dim3(GR_BLOCK), 0, ctx->stream, bt->records, (uint32_t)n_tiles,
                        bt->tile_spheres);
     const size_t n_grid = g->n_chunks * GRID_CHUNK;           // (the grid's records are padded to whole runs)
     hipLaunchKernelGGL(bt_scatter_gpos_kernel, dim3((unsigned)((n_grid + GR_BLOCK - 1) / GR_BLOCK)), dim3(GR_BLOCK), 0, ctx->stream, g->records, (uint32_t)n_grid,
@@ -1939,14 +1858,13 @@ int bt_ensure(pcr_ctx* ctx, const pcr_cloud* tgt)
     BtPtr bt_owner(bt);
     if (n == 0 || n > 0x7FFFFFF0ull) { const_cast<pcr_cloud*>(tgt)->bt = bt_owner.release(); return PCR_OK; }       // safe = false: the other kernels answer
     const size_t n_super = (n + BT_SUPER - 1) / BT_SUPER, n_pad = n_super * BT_SUPER, n_tiles = n_pad / 32;
-    const uint32_t bb_blocks = (uint32_t)std::min<size_t>(256, (n + GR_BLOCK - 1) / GR_BLOCK);
     float* bb_dev;
     Layout L;                                                      // (records and operand rows are whole multiples of 256 B: no padding between them)
     L.add(&bt->records, n_pad);
     L.add(&bt->centres, n_super);
     L.add(&bt->ops, n_tiles * 128);
     L.add(&bt->ops16, n_tiles * 64);
-    L.add(&bb_dev, (size_t)bb_blocks * 6);
+    L.add(&bb_dev, (size_t)bbox_blocks(n) * 6);
     L.add(&bt->bad16, 1);
     // order inside a lattice cell: arrival order below 1 M points (a cell holds a few points at most), a 6-bit-per-axis Morton code of
     // the position inside the cell from there on (tune bt_fine_bits: 0 auto, 1 .. 7 bits, -1 none)
@@ -1974,17 +1892,11 @@ int bt_ensure(pcr_ctx* ctx, const pcr_cloud* tgt)
     e = hipMemsetAsync(bt->bad16, 0, sizeof(int), ctx->stream);
     if (e != hipSuccess) return fail(ctx, PCR_ERR_HIP, "btiles", e);
     // the one host round trip: the bounding box of the finite points
-    hipLaunchKernelGGL(bbox_kernel, dim3(bb_blocks), dim3(GR_BLOCK), 0, ctx->stream, tgt->x(), tgt->y(), tgt->z(), (uint32_t)n, bb_dev);
-    std::vector<float> hb(bb_blocks * 6);
-    e = hipMemcpyAsync(hb.data(), bb_dev, hb.size() * sizeof(float), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    float lo[3], hi[3];
+    bool any = false;
+    e = cloud_bbox(ctx, tgt, bb_dev, lo, hi, &any);
     if (e != hipSuccess) return fail(ctx, PCR_ERR_HIP, "btiles bbox", e);
-    float lo[3] = { FLT_MAX, FLT_MAX, FLT_MAX }, hi[3] = { -FLT_MAX, -FLT_MAX, -FLT_MAX };
-    for (uint32_t b = 0; b < bb_blocks; b++)
-        for (int k = 0; k < 3; k++) { lo[k] = std::min(lo[k], hb[b * 6 + k]); hi[k] = std::max(hi[k], hb[b * 6 + 3 + k]); }
-    float amax = 0.f;
-    bool any = lo[0] <= hi[0];
-    for (int k = 0; k < 3 && any; k++) amax = std::max(amax, std::max(std::fabs(lo[k]), std::fabs(hi[k])));
+    const float amax = any ? bbox_absmax(lo, hi) : 0.f;
     if (tgt->absmax < 0.f) const_cast<pcr_cloud*>(tgt)->absmax = amax;                                // (cloud_absmax's cache, for free)
     // |t - C| < 1e18 and |t - C|^2 < 3e38 for every finite point and any centre inside the box: what the filter's analysis wants
     bt->safe = any && amax < 5e17f;
@@ -2003,9 +1915,9 @@ int bt_ensure(pcr_ctx* ctx, const pcr_cloud* tgt)
         if (e == hipSuccess) {
             hipLaunchKernelGGL(gather_records_kernel, dim3((unsigned)((n_pad + GR_BLOCK - 1) / GR_BLOCK)), dim3(GR_BLOCK), 0, ctx->stream, tgt->x(), tgt->y(), tgt->z(),
                                (uint32_t)n, (uint32_t)n_pad, v_out, bt->records);
-            hipLaunchKernelGGL(bt_centres_kernel, dim3((unsigned)((n_super + GR_BLOCK / 64 - 1) / (GR_BLOCK / 64))), dim3(GR_BLOCK), 0, ctx->stream, bt->records, (uint32_t)n_super,
-                               bt->centres, bt->bad16);
-            hipLaunchKernelGGL(bt_ops16_kernel, dim3((unsigned)((n_tiles * 32 + GR_BLOCK - 1) / GR_BLOCK)), dim3(GR_BLOCK), 0, ctx->stream, bt->records, (uint32_t)n_tiles,
+            hipLaunchKernelGGL((bt_centres_kernel<BT_SUPER, 64>), dim3((unsigned)((n_super + GR_BLOCK / 64 - 1) / (GR_BLOCK / 64))), dim3(GR_BLOCK), 0, ctx->stream, bt->records,
+                               (uint32_t)n_pad, (uint32_t)n_super, bt->centres, bt->bad16);
+            hipLaunchKernelGGL((bt_rec_ops_kernel<BT_SUPER, false>), dim3((unsigned)((n_tiles * 32 + GR_BLOCK - 1) / GR_BLOCK)), dim3(GR_BLOCK), 0, ctx->stream, bt->records, (uint32_t)n_tiles,
                                bt->centres, bt->ops16);
             hipLaunchKernelGGL(bt_ops_kernel, dim3((unsigned)((n_tiles * 32 + GR_BLOCK - 1) / GR_BLOCK)), dim3(GR_BLOCK), 0, ctx->stream, bt->records, (uint32_t)n_tiles,
                                bt->centres, bt->ops, (int*)nullptr);
@@ -2088,6 +2000,29 @@ static int orig_storage(pcr_ctx* ctx, pcr_cloud* w, bool in_place, uint32_t** ou
     return PCR_OK;
 }
 
+// The end of both sorts of a working cloud, in two steps, so that a caller's own copy can stand between them.  First `sorted` (a fresh cloud
+// of the same size; the permute writes all of it, padding included) gets w[perm[t]]; `e`: the outcome of the caller's launches in front.
+static hipError_t permute_into_sorted(pcr_ctx* ctx, const pcr_cloud* w, pcr_cloud* sorted, const uint32_t* perm, hipError_t e)
+{
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(permute_cloud_kernel, dim3((unsigned)((sorted->cap + GR_BLOCK - 1) / GR_BLOCK)), dim3(GR_BLOCK), 0, ctx->stream, w->x(), w->y(), w->z(), perm,
+                       (uint32_t)w->n, sorted->x(), sorted->y(), sorted->z(), (uint32_t)sorted->cap);
+    return hipGetLastError();
+}
+// ... then `sorted` takes the place of *work, with `orig` as its map back to the caller's order.  An error so far (`e`) gives `sorted` back and
+// leaves *work as it was.
+static int adopt_sorted_cloud(pcr_ctx* ctx, pcr_cloud** work, pcr_cloud* sorted, uint32_t* orig, bool in_place, hipError_t e, const char* what)
+{
+    if (e != hipSuccess) { pcr_cloud_destroy(ctx, sorted); return fail(ctx, PCR_ERR_HIP, what, e); }
+    pcr_cloud* w = *work;
+    sorted->cells_tag = w->cells_tag;                              // (the same points: the same occupied cells)
+    if (in_place) { std::swap(w->base, sorted->base); std::swap(w, sorted); cloud_modified(sorted); }   // the caller's handle keeps its identity and gets the sorted buffer
+    cloud_release(ctx, w);                                         // (no synchronisation: the permute still reads it — the buffer stays allocated)
+    *work = sorted;
+    sorted->orig = orig;
+    return PCR_OK;
+}
+
 // Re-orders the working cloud of an ICP loop into the order of the target's index (sort_queries_any), ONCE: every later search reads
 // its queries with coalesced loads (no perm indirection), writes keys / winner positions coalesced, and the Kabsch pass walks
 // pairs whose targets are neighbours in the record array.  orig[t] = index the point had in the caller's cloud (the
@@ -2103,18 +2038,10 @@ int grid_sort_working_cloud(pcr_ctx* ctx, const pcr_cloud* tgt, pcr_cloud** work
     uint32_t* orig = nullptr;
     if ((rc = orig_storage(ctx, w, in_place, &orig))) return rc;   // (before the clone: nothing to give back on these error paths)
     pcr_cloud* sorted = nullptr;
-    rc = cloud_alloc(ctx, n, &sorted);                            // same size; the permute writes all of it, padding included
-    if (rc) return rc;
-    hipLaunchKernelGGL(permute_cloud_kernel, dim3((unsigned)((sorted->cap + GR_BLOCK - 1) / GR_BLOCK)), dim3(GR_BLOCK), 0, ctx->stream, w->x(), w->y(), w->z(), ctx->qperm,
-                       (uint32_t)n, sorted->x(), sorted->y(), sorted->z(), (uint32_t)sorted->cap);
-    hipError_t e = hipGetLastError();
+    if ((rc = cloud_alloc(ctx, n, &sorted))) return rc;
+    hipError_t e = permute_into_sorted(ctx, w, sorted, ctx->qperm, hipSuccess);
     if (e == hipSuccess) e = hipMemcpyAsync(orig, ctx->qperm, n * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream);
-    if (e != hipSuccess) { pcr_cloud_destroy(ctx, sorted); return fail(ctx, PCR_ERR_HIP, "grid_sort_working_cloud", e); }
-    sorted->cells_tag = w->cells_tag;                              // (the same points: the same occupied cells)
-    if (in_place) { std::swap(w->base, sorted->base); std::swap(w, sorted); cloud_modified(sorted); }   // the caller's handle keeps its identity and gets the sorted buffer
-    cloud_release(ctx, w);                                         // (no synchronisation: the permute above still reads it — the buffer stays allocated)
-    *work = sorted;
-    sorted->orig = orig;
+    if ((rc = adopt_sorted_cloud(ctx, work, sorted, orig, in_place, e, "grid_sort_working_cloud"))) return rc;
     ctx->qperm_src = nullptr;                                      // the permutation belongs to the cloud that no longer exists
     return PCR_OK;
 }
@@ -2150,8 +2077,7 @@ int bt_sort_working_cloud(pcr_ctx* ctx, const pcr_cloud* tgt, pcr_cloud** work, 
     if (rc) return rc;
     if ((rc = orig_storage(ctx, w, in_place, &v_out))) return rc;  // (the sorted values ARE the original indices: no copy behind the sort)
     pcr_cloud* sorted = nullptr;
-    rc = cloud_alloc(ctx, n, &sorted);                            // same size; the permute writes all of it, padding included
-    if (rc) return rc;
+    if ((rc = cloud_alloc(ctx, n, &sorted))) return rc;
     const unsigned blocks = (unsigned)((n + GR_BLOCK - 1) / GR_BLOCK);
     hipLaunchKernelGGL(bt_keys_kernel, dim3(blocks), dim3(GR_BLOCK), 0, ctx->stream, w->x(), w->y(), w->z(), (uint32_t)n, bt->key_lo[0], bt->key_lo[1],
                        bt->key_lo[2], bt->key_inv, bt->key_inv, bt->key_inv, k_in, v_in, 0);
@@ -2159,18 +2085,8 @@ int bt_sort_working_cloud(pcr_ctx* ctx, const pcr_cloud* tgt, pcr_cloud** work, 
     // eight bits less are one radix pass less)
     const int begin_bit = (int)std::min<int64_t>(std::max<int64_t>(tune_get(ctx, "bt_sort_begin_bit", 0), 0), 24);
     hipError_t e = sort_pairs_u64_u32(temp, temp_bytes, k_in, k_out, v_in, v_out, n, begin_bit, 31, ctx->stream);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(permute_cloud_kernel, dim3((unsigned)((sorted->cap + GR_BLOCK - 1) / GR_BLOCK)), dim3(GR_BLOCK), 0, ctx->stream, w->x(), w->y(), w->z(), v_out,
-                           (uint32_t)n, sorted->x(), sorted->y(), sorted->z(), (uint32_t)sorted->cap);
-        e = hipGetLastError();
-    }
-    if (e != hipSuccess) { pcr_cloud_destroy(ctx, sorted); return fail(ctx, PCR_ERR_HIP, "bt_sort_working_cloud", e); }
-    sorted->cells_tag = w->cells_tag;
-    if (in_place) { std::swap(w->base, sorted->base); std::swap(w, sorted); cloud_modified(sorted); }
-    cloud_release(ctx, w);                                         // (no synchronisation: the permute above still reads it — the buffer stays allocated)
-    *work = sorted;
-    sorted->orig = v_out;
-    return PCR_OK;
+    e = permute_into_sorted(ctx, w, sorted, v_out, e);
+    return adopt_sorted_cloud(ctx, work, sorted, v_out, in_place, e, "bt_sort_working_cloud");
 }
 
 // ---- spatially coherent shards of a source cloud (multi-GPU: pcr_cloud_shard_spatial, include/pcr.h)

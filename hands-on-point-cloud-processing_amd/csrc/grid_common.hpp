@@ -155,6 +155,39 @@ __device__ __forceinline__ uint4 ht_target_operand(float tx, float ty, float tz,
     return upper_half ? make_uint4(qz, qz, w[0] | (w[1] << 16), HT_THETA_CONSTS) : make_uint4(qx, qx, qy, qy);
 }
 
+// MFMA row m of a tile <-> the record at this position of the tile's 32: the 16 accumulators of lane-half h are then the 16 records of chunk
+// 2 T + h.  Every kernel that reads BtIndex::ops, ops16 or l1_rec_ops depends on it: nn1_btrack_kernel and nn1_strack_kernel
+// (nn1_brute.hip), the STRACK2 / STRACK3 bodies (nn1_sphere.hpp) and nn1_stile_kernel (grid_stile.hpp).
+__device__ __forceinline__ uint32_t mfma_row_record(uint32_t m) { return 16 * ((m >> 2) & 1) + 4 * (m >> 3) + (m & 3); }
+
+// record p of an index whose last tiles reach past its n_rec records: the padding every cloud carries (x = +inf: never finite)
+__device__ __forceinline__ float4 padded_record(const float4* __restrict__ rec, size_t p, size_t n_rec)
+{
+    return p < n_rec ? rec[p] : make_float4(__builtin_inff(), 0.f, 0.f, 0.f);
+}
+
+// ---- 64-bit (d2 bits << 32 | index) keys across lanes: the key a DPP control word brings in, the minimum with it, and the key of lane ^ 32
+template <int CTRL>
+__device__ __forceinline__ uint32_t dpp_mov(uint32_t x)
+{
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, 0xF, 0xF, false);
+}
+template <int CTRL>
+__device__ __forceinline__ unsigned long long key_dpp(unsigned long long key)
+{
+    return ((unsigned long long)dpp_mov<CTRL>((uint32_t)(key >> 32)) << 32) | dpp_mov<CTRL>((uint32_t)key);
+}
+template <int CTRL>
+__device__ __forceinline__ unsigned long long key_min_dpp(unsigned long long key)
+{
+    const unsigned long long w = key_dpp<CTRL>(key);
+    return w < key ? w : key;
+}
+__device__ __forceinline__ unsigned long long key_xor32(unsigned long long key)
+{
+    return ((unsigned long long)(uint32_t)__shfl_xor((int)(key >> 32), 32, 64) << 32) | (uint32_t)__shfl_xor((int)(uint32_t)key, 32, 64);
+}
+
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 

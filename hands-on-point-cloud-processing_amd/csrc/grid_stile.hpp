@@ -86,11 +86,7 @@ __device__ __forceinline__ void sl_flush(StileWaveLds& L, uint32_t cnt, const fl
             if (d < 0x7F7FFFFFu && key < mine) { mine = key; pm = p0 + 4u * j; }   // FLT_MAX gate
         }
         if (!valid) mine = ~0ull;
-        unsigned long long key = mine;
-#define PCR_SL_MIN(CTRL) { const unsigned long long w = ((unsigned long long)dpp_mov<CTRL>((uint32_t)(key >> 32)) << 32) | dpp_mov<CTRL>((uint32_t)key); \
-                           key = w < key ? w : key; }
-        PCR_SL_MIN(0xB1) PCR_SL_MIN(0x4E)                          // quad xor 1, xor 2: the four lanes of the chunk
-#undef PCR_SL_MIN
+        const unsigned long long key = key_min_dpp<0x4E>(key_min_dpp<0xB1>(mine));   // quad xor 1, xor 2: the four lanes of the chunk
         const bool winner = mine == key && mine != ~0ull;          // (original indices are unique: one lane of the four)
         if (winner) atomicMin(&L.best[slot], mine);
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");

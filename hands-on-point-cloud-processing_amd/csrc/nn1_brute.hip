@@ -738,8 +738,7 @@ __global__ __launch_bounds__(NN_BLOCK, (F16 && QG == 4) ? PCR_BT_WAVES : 1) void
                 const unsigned long long key = ((unsigned long long)e << 32) | __float_as_uint(rec.w);
                 if (e < 0x7F7FFFFFu && key < kbest) kbest = key;
             }
-            const unsigned long long ko = ((unsigned long long)(uint32_t)__shfl_xor((int)(kbest >> 32), 32, 64) << 32) |
-                                          (uint32_t)__shfl_xor((int)(uint32_t)kbest, 32, 64);
+            const unsigned long long ko = key_xor32(kbest);
             kbest = ko < kbest ? ko : kbest;
             best = (uint32_t)(kbest >> 32);
             bidx = kbest == ~0ull ? 0xFFFFFFFFu : (uint32_t)(kbest & 0xFFFFFFFFull);
@@ -815,11 +814,8 @@ __device__ __forceinline__ void st_flush(StWaveLds<QG>& L, uint32_t cnt, uint32_
         for (int u = 0; u < 2; u++) {
             const uint32_t d = d2_exact_bits(q[u].x, q[u].y, q[u].z, rec[u].x, rec[u].y, rec[u].z);
             unsigned long long key = (valid[u] && d < 0x7F7FFFFFu) ? (((unsigned long long)d << 32) | __float_as_uint(rec[u].w)) : ~0ull;   // FLT_MAX gate
-#define PCR_ST_MIN(CTRL) { const unsigned long long w = ((unsigned long long)(uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(key >> 32), CTRL, 0xF, 0xF, false) << 32) | \
-                                                      (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)key, CTRL, 0xF, 0xF, false);                              \
-                           key = w < key ? w : key; }
-            PCR_ST_MIN(0xB1) PCR_ST_MIN(0x4E) PCR_ST_MIN(0x141) PCR_ST_MIN(0x140)             // quad xor 1, xor 2, half-row mirror, row mirror
-#undef PCR_ST_MIN
+            key = key_min_dpp<0xB1>(key); key = key_min_dpp<0x4E>(key);                       // quad xor 1, xor 2,
+            key = key_min_dpp<0x141>(key); key = key_min_dpp<0x140>(key);                     // half-row mirror, row mirror
             if ((lane & 15) == 0 && key != ~0ull) atomicMin(&L.best[slot[u]], key);
         }
     }
@@ -1010,8 +1006,7 @@ __global__ __launch_bounds__(NN_BLOCK, PCR_ST_WAVES) void nn1_strack_kernel(
                 const unsigned long long key = ((unsigned long long)e << 32) | __float_as_uint(rec.w);
                 if (e < 0x7F7FFFFFu && key < kbest) kbest = key;
             }
-            const unsigned long long ko = ((unsigned long long)(uint32_t)__shfl_xor((int)(kbest >> 32), 32, 64) << 32) |
-                                          (uint32_t)__shfl_xor((int)(uint32_t)kbest, 32, 64);
+            const unsigned long long ko = key_xor32(kbest);
             kbest = ko < kbest ? ko : kbest;
             // "no neighbour" is the key (+inf, no index), as every other kernel writes it (a seed kernel that found nothing left ~0 behind)
             if (kbest == ~0ull) kbest = 0x7F800000FFFFFFFFull;

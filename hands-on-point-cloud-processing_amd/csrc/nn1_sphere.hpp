@@ -52,11 +52,7 @@ __device__ __forceinline__ void s2_flush(LDS& L, uint32_t cnt, const float4* __r
                 if (d < 0x7F7FFFFFu && k < key) key = k;                   // FLT_MAX gate
             }
             if (!valid[r]) key = ~0ull;
-#define PCR_S2_MIN(CTRL) { const unsigned long long w = ((unsigned long long)(uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(key >> 32), CTRL, 0xF, 0xF, false) << 32) | \
-                                                      (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)key, CTRL, 0xF, 0xF, false);                              \
-                           key = w < key ? w : key; }
-            PCR_S2_MIN(0xB1) PCR_S2_MIN(0x4E)                              // quad xor 1, xor 2: the four lanes of the chunk
-#undef PCR_S2_MIN
+            key = key_min_dpp<0xB1>(key); key = key_min_dpp<0x4E>(key);    // quad xor 1, xor 2: the four lanes of the chunk
             if ((lane & 3u) == 0u && key != ~0ull) atomicMin(&L.best[slot[r]], key);
         }
     }
@@ -548,8 +544,7 @@ __device__ __forceinline__ void nn1_strack3_body(
                 const unsigned long long key = ((unsigned long long)e << 32) | __float_as_uint(rec.w);
                 if (e < 0x7F7FFFFFu && key < kbest) kbest = key;
             }
-            const unsigned long long ko = ((unsigned long long)(uint32_t)__shfl_xor((int)(kbest >> 32), 32, 64) << 32) |
-                                          (uint32_t)__shfl_xor((int)(uint32_t)kbest, 32, 64);
+            const unsigned long long ko = key_xor32(kbest);
             kbest = ko < kbest ? ko : kbest;
             if (kbest == ~0ull) kbest = 0x7F800000FFFFFFFFull;           // "no neighbour" is the key (+inf, no index), as every other kernel writes it
         }

@@ -175,6 +175,48 @@ def test_ragged_ends_of_every_mask_word(ctx, big_scan, nt):
 
 
 @gpu
+def test_target_whose_last_level1_tile_has_no_finite_record(ctx, big_scan):
+    """4 608 targets, the last 600 of them NaN / inf: the index sorts those behind the 4 008 finite ones, so its last tiles of 32, its whole last
+    level-1 tile of 512 and most of the second super-tile of 4 096 hold no finite record (centres, scales and spheres of nothing).  Every sphere
+    form returns the exact kernel's keys, and an ICP loop through the tile search the poses of the exhaustive loop."""
+    tgt_all, src_all = big_scan
+    nt = 4608
+    tgt = np.ascontiguousarray(tgt_all[:, :: tgt_all.shape[1] // nt][:, :nt]).copy()
+    tgt[:, nt - 600:nt - 300] = np.nan; tgt[0, nt - 300:] = np.inf; tgt[1, nt - 100:] = -np.inf
+    ct = ctx.cloud(tgt)
+    try:
+        for ns in (1, 33, 2000):
+            cs = ctx.cloud(np.ascontiguousarray(src_all[:, :ns]))
+            ref = exact(ctx, ct, cs)
+            assert ref[0].max() < nt - 600, ns
+            for qg, sw in FORMS:
+                got = strack3(ctx, ct, cs, qg, sw)
+                assert same(got, ref), (ns, qg, sw, int((got[0] != ref[0]).sum()))
+            cs.free()
+        reset(ctx)
+        cs = ctx.cloud(np.ascontiguousarray(src_all[:, :2000]))
+        ctx.tune("nn_method", 1)
+        ref = [ctx.icp_point2point(cs, ct, max_corr=1.0, max_iter=it, eps=0.0) for it in (1, 3, 6)]
+        ctx.tune("nn_method", 2); ctx.tune("grid_order", 2); ctx.tune("grid_mode", 3); ctx.tune("grid_tile", 1)
+        cm = ctx.cloud(tgt)                                    # a fresh cloud: its index is built Morton-ordered
+        used = set()
+        for it, (Tr, sr) in zip((1, 3, 6), ref):
+            T, st = ctx.icp_point2point(cs, cm, max_corr=1.0, max_iter=it, eps=0.0)
+            if it > 2:
+                used.add(ctx.mfma_check()["last_nn1_kernel"])
+            assert np.array_equal(T.view(np.uint32), Tr.view(np.uint32)), it
+            assert st["last_pairs"] == sr["last_pairs"] and st["iters_run"] == sr["iters_run"], it
+            assert np.float32(st["last_loss"]).view(np.uint32) == np.float32(sr["last_loss"]).view(np.uint32), it
+        assert used == {"grid-stile"}, used
+        cs.free(); cm.free()
+    finally:                                                   # (the context is the module's: a failure must not leave the routes switched)
+        for k in ("grid_order", "grid_mode", "grid_tile"):
+            ctx.tune(k, 0)
+        reset(ctx)
+        ct.free()
+
+
+@gpu
 def test_far_queries_with_stale_seeds_overfill_the_pair_list(ctx, synth):
     """64 queries 300 m outside a target of 8 193 points, searched in a loop from alternating sides.  A search that keeps stale seeds
     (nn1_sphere_reseed = 2) starts from the winners of the pose 300 m on the OTHER side — the far side of the target as seen from here —, so a
