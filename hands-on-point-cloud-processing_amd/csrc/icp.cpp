@@ -173,10 +173,15 @@ static int icp_pipelined(pcr_ctx* ctx, const pcr_cloud* src, const pcr_cloud* tg
         // [1]: the other buffer of the fused solve + move; behind the two states, on a line of its own, the counter of the grid barrier of
         // the fused sums + move launch (kabsch.hip).  Zeroed ONCE: the counter only ever grows, and [1].barrier_timeout must not start as garbage
         static_assert(2 * sizeof(IcpState) <= 512, "the barrier counter lies 512 bytes behind the states");
-        PCR_HIP(ctx, hipMalloc((void**)&ctx->icp_state_dev, 512 + 128));
-        PCR_HIP(ctx, hipMemsetAsync(ctx->icp_state_dev, 0, 512 + 128, ctx->stream));
+        // behind the counter's line, on lines of their own: the accumulators of the sums + solve launch (kabsch.hip icp_sums_solve_kernel), zeroed
+        // here and left all zero by every launch
+        constexpr size_t acc_bytes = (size_t)ICP_ACC_REPLICAS * ICP_ACC_WORDS * sizeof(long long);
+        PCR_HIP(ctx, hipMalloc((void**)&ctx->icp_state_dev, 512 + 128 + acc_bytes));
+        PCR_HIP(ctx, hipMemsetAsync(ctx->icp_state_dev, 0, 512 + 128 + acc_bytes, ctx->stream));
         ctx->icp_barrier_dev = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(ctx->icp_state_dev) + 512);
         ctx->icp_barrier_arrived = 0;
+        ctx->icp_acc_dev = reinterpret_cast<long long*>(reinterpret_cast<char*>(ctx->icp_state_dev) + 512 + 128);
+        ctx->icp_acc_dirty = false;
         PCR_HIP(ctx, hipHostMalloc((void**)&ctx->icp_state_host, (RING + 1) * sizeof(IcpState), hipHostMallocDefault));
         for (int k = 0; k < RING; k++) PCR_HIP(ctx, hipEventCreateWithFlags(&ctx->icp_events[k], hipEventDisableTiming));
     }
@@ -230,6 +235,10 @@ static int icp_pipelined(pcr_ctx* ctx, const pcr_cloud* src, const pcr_cloud* tg
     // form with ONE slice (every target of up to 131 072 records; larger ones where the queries alone fill the launch) — icp_move_route.  The dispatcher decides the kernel family late, so the chain is chosen behind
     // the FIRST search, which runs as ever (nothing to move yet): if it did not take STRACK3, the whole call keeps one of the chains above; a later search
     // that cannot carry the move is an error of the dispatcher, not a fallback.
+    // The sums + solve launch hands a workgroup's limb totals on as int64 atomic adds into eight accumulator rows, not as a row per workgroup (DESIGN.md
+    // 6i, profiles/icp_sums_accumulators.txt): the last arriver reads eight short rows whatever the geometry, so the launch runs 512 threads x 2 pairs
+    // on 118 workgroups — kernel 19.9 -> 17.5 us, a step of the bench line 53.4 -> 50.9 us (8 + 8 alternating processes, spreads 2.5 / 0.9).  What
+    // now bounds it: arrivals at the one ticket counter take ~35 ns each, one after the other (the last of 118 waits 4 us, of 469 16 us), then the solve.
     const bool move_cand = fused && seed_tgt && icp_sums_solve_blocks(ctx, work->n) != 0;
     bool move_in_search = false;
     // (Measured and dropped, round 4: the Kabsch sums taken by the search kernel itself — STRACK3 ends with every query's final key in one wave, so each
@@ -303,6 +312,8 @@ static int icp_pipelined(pcr_ctx* ctx, const pcr_cloud* src, const pcr_cloud* tg
         hipStreamSynchronize(ctx->stream);
     }
     cloud_release(ctx, work);             // (synchronised above; the loop's own working copy: parked for the next call's clone)
+    // the accumulators of the sums + solve launch are all zero behind a call that ran to its end; one that did not says so, and the next call clears them
+    if (move_in_search && (rc || host[RING].overflow || host[RING].barrier_timeout)) ctx->icp_acc_dirty = true;
     if (rc) return rc;
     ctx->icp_last_chain = move_in_search ? 4 : fused_sums ? 3 : fused ? 2 : 1;
     const IcpState& f = host[RING];

@@ -115,7 +115,8 @@ constexpr int KB_NLC = 40;            // the limbs that are not carry slots (12 
 // BFLY: the halving butterfly over the 40 live limbs (needs carries == false); it keeps all of them in registers at once (~160
 // VGPRs), so only the instance for few terms per thread — where the reduction IS the pass — is built with it
 // WAVES: the wavefronts of the workgroup (the sums are exact integers: any grouping gives the same row)
-template <bool BFLY, int WAVES = KB_BLOCK / 64>
+// NORM: false leaves row[] as the workgroup's plain totals (carry slots zero) for a caller that hands them on as integers (icp_sums_solve_kernel)
+template <bool BFLY, int WAVES = KB_BLOCK / 64, bool NORM = true>
 __device__ __forceinline__ void block_reduce_limbs(double (&tn)[KB_NL], unsigned long long lastkey, int overflow,
                                                    double (&red)[WAVES][KB_NL], double (&row)[KB_ROW], bool carries)
 {
@@ -161,6 +162,7 @@ __device__ __forceinline__ void block_reduce_limbs(double (&tn)[KB_NL], unsigned
         row[57] = 0.0;
     }
     __syncthreads();
+    if (!NORM) return;
     if (threadIdx.x < 6) num::limbs_normalize(row + 3 * threadIdx.x, 2);
     else if (threadIdx.x < 15) num::limbs_normalize(row + 18 + 4 * (threadIdx.x - 6), 3);
     __syncthreads();
@@ -808,45 +810,69 @@ __global__ __launch_bounds__(T) void icp_sums_update_move_kernel(
 // A thread's four consecutive pairs as icp_sums_update_move_kernel reads them — points, keys, original indices and the gathered target points, everything
 // that depends on nothing else requested in one go — for icp_sums_solve_kernel below.  (That kernel keeps its own copy of these lines: routed through
 // these functions it took 156 VGPRs instead of 142, and it is the path of every loop the chain below does not serve.)
+// PP = the consecutive pairs of a thread: 4 as there, or 2 or 1, which spread the same pairs over more workgroups.
+template <int PP>
 struct FsPairs {
-    float4 px, py, pz;
-    unsigned long long sk[4];              // (no pair: NaN distance, no target)
-    uint32_t og[4];
-    float sq[4][3];
+    float px[PP], py[PP], pz[PP];
+    unsigned long long sk[PP];             // (no pair: NaN distance, no target)
+    uint32_t og[PP];
+    float sq[PP][3];
 };
 
-__device__ __forceinline__ void fs_load_pairs(FsPairs& P, bool mine, uint32_t i, uint32_t n, const float* x, const float* y, const float* z,
+template <int PP>
+__device__ __forceinline__ void fs_load_pairs(FsPairs<PP>& P, bool mine, uint32_t i, uint32_t n, const float* x, const float* y, const float* z,
                                               const unsigned long long* keys, const uint32_t* __restrict__ orig, const float* __restrict__ tx,
                                               const float* __restrict__ ty, const float* __restrict__ tz, uint32_t nt)
 {
-    const uint32_t base = 4 * i;
-    P.px = make_float4(0.f, 0.f, 0.f, 0.f); P.py = P.px; P.pz = P.px;
+    static_assert(PP == 1 || PP == 2 || PP == 4, "one vector load per array");
+    const uint32_t base = PP * i;
 #pragma unroll
-    for (int u = 0; u < 4; u++) { P.sk[u] = ~0ull; P.og[u] = base + u; }
+    for (int u = 0; u < PP; u++) { P.px[u] = 0.f; P.py[u] = 0.f; P.pz[u] = 0.f; P.sk[u] = ~0ull; P.og[u] = base + u; }
     if (mine) {
-        P.px = reinterpret_cast<const float4*>(x)[i]; P.py = reinterpret_cast<const float4*>(y)[i]; P.pz = reinterpret_cast<const float4*>(z)[i];
-        if (base + 3 < n) {
-            const ulonglong2 k01 = reinterpret_cast<const ulonglong2*>(keys)[2 * i], k23 = reinterpret_cast<const ulonglong2*>(keys)[2 * i + 1];
-            P.sk[0] = k01.x; P.sk[1] = k01.y; P.sk[2] = k23.x; P.sk[3] = k23.y;
-            if (orig) { const uint4 o = reinterpret_cast<const uint4*>(orig)[i]; P.og[0] = o.x; P.og[1] = o.y; P.og[2] = o.z; P.og[3] = o.w; }
+        // (a cloud's arrays are padded to a multiple of four points: the vector loads of the tail group stay inside them)
+        if constexpr (PP == 4) {
+            const float4 a = reinterpret_cast<const float4*>(x)[i], b = reinterpret_cast<const float4*>(y)[i], c = reinterpret_cast<const float4*>(z)[i];
+            P.px[0] = a.x; P.px[1] = a.y; P.px[2] = a.z; P.px[3] = a.w;
+            P.py[0] = b.x; P.py[1] = b.y; P.py[2] = b.z; P.py[3] = b.w;
+            P.pz[0] = c.x; P.pz[1] = c.y; P.pz[2] = c.z; P.pz[3] = c.w;
+        } else if constexpr (PP == 2) {
+            const float2 a = reinterpret_cast<const float2*>(x)[i], b = reinterpret_cast<const float2*>(y)[i], c = reinterpret_cast<const float2*>(z)[i];
+            P.px[0] = a.x; P.px[1] = a.y; P.py[0] = b.x; P.py[1] = b.y; P.pz[0] = c.x; P.pz[1] = c.y;
+        } else {
+            P.px[0] = x[i]; P.py[0] = y[i]; P.pz[0] = z[i];
+        }
+        if (base + (PP - 1) < n) {
+            if constexpr (PP == 4) {
+                const ulonglong2 k01 = reinterpret_cast<const ulonglong2*>(keys)[2 * i], k23 = reinterpret_cast<const ulonglong2*>(keys)[2 * i + 1];
+                P.sk[0] = k01.x; P.sk[1] = k01.y; P.sk[2] = k23.x; P.sk[3] = k23.y;
+                if (orig) { const uint4 o = reinterpret_cast<const uint4*>(orig)[i]; P.og[0] = o.x; P.og[1] = o.y; P.og[2] = o.z; P.og[3] = o.w; }
+            } else if constexpr (PP == 2) {
+                const ulonglong2 k01 = reinterpret_cast<const ulonglong2*>(keys)[i];
+                P.sk[0] = k01.x; P.sk[1] = k01.y;
+                if (orig) { const uint2 o = reinterpret_cast<const uint2*>(orig)[i]; P.og[0] = o.x; P.og[1] = o.y; }
+            } else {
+                P.sk[0] = keys[i];
+                if (orig) P.og[0] = orig[i];
+            }
         } else {
 #pragma unroll
-            for (int u = 0; u < 4; u++)
+            for (int u = 0; u < PP; u++)
                 if (base + u < n) { P.sk[u] = keys[base + u]; if (orig) P.og[u] = orig[base + u]; }
         }
     }
-    // the target points of the four pairs, gathered ONCE: nothing else in this launch needs them
+    // the target points of the pairs, gathered ONCE: nothing else in this launch needs them
 #pragma unroll
-    for (int u = 0; u < 4; u++) {
+    for (int u = 0; u < PP; u++) {
         P.sq[u][0] = 0.f; P.sq[u][1] = 0.f; P.sq[u][2] = 0.f;
         const uint32_t j = (uint32_t)(P.sk[u] & 0xFFFFFFFFull);
         if (j < nt) { P.sq[u][0] = tx[j]; P.sq[u][1] = ty[j]; P.sq[u][2] = tz[j]; }
     }
 }
 
-// ... and their limbs, added exactly as the sums pass adds them (kabsch_partial_kernel's gate, term for term), reduced to the workgroup's row
-template <int WAVES>
-__device__ __forceinline__ void fs_pairs_row(const FsPairs& P, float max_corr, const KabschPlan& plan, uint32_t nt, double (&red_l)[WAVES][KB_NL],
+// ... and their limbs, added exactly as the sums pass adds them (kabsch_partial_kernel's gate, term for term), reduced to the workgroup's TOTALS in row[]:
+// not normalised (block_reduce_limbs, NORM = false) — they leave the workgroup as integers
+template <int PP, int WAVES>
+__device__ __forceinline__ void fs_pairs_row(const FsPairs<PP>& P, float max_corr, const KabschPlan& plan, uint32_t nt, double (&red_l)[WAVES][KB_NL],
                                              double (&row)[KB_ROW])
 {
     double c0[6], c1[6], p0[9], p1[9], p2[9], cnt = 0.0;
@@ -856,14 +882,13 @@ __device__ __forceinline__ void fs_pairs_row(const FsPairs& P, float max_corr, c
     for (int k = 0; k < 9; k++) { p0[k] = 0.0; p1[k] = 0.0; p2[k] = 0.0; }
     unsigned long long lastkey = 0;
     int overflow = 0;
-    const float sx4[4] = { P.px.x, P.px.y, P.px.z, P.px.w }, sy4[4] = { P.py.x, P.py.y, P.py.z, P.py.w }, sz4[4] = { P.pz.x, P.pz.y, P.pz.z, P.pz.w };
 #pragma unroll
-    for (int u = 0; u < 4; u++) {
+    for (int u = 0; u < PP; u++) {
         const uint32_t d2b = (uint32_t)(P.sk[u] >> 32);
         const float d2 = __uint_as_float(d2b);
         const uint32_t j = (uint32_t)(P.sk[u] & 0xFFFFFFFFull);
         if (d2 < max_corr && j < nt) {                       // registration.cpp:936 (kabsch_partial_kernel's gate, term for term)
-            const float pf0 = sx4[u], pf1 = sy4[u], pf2 = sz4[u];
+            const float pf0 = P.px[u], pf1 = P.py[u], pf2 = P.pz[u];
             if (!(fabsf(pf0) < plan.lim && fabsf(pf1) < plan.lim && fabsf(pf2) < plan.lim)) { overflow = 1; continue; }
             const double Pd[3] = { pf0, pf1, pf2 }, Q[3] = { P.sq[u][0], P.sq[u][1], P.sq[u][2] };
 #pragma unroll
@@ -883,51 +908,100 @@ __device__ __forceinline__ void fs_pairs_row(const FsPairs& P, float max_corr, c
 #pragma unroll
     for (int k = 0; k < 9; k++) { tn[18 + 4 * k] = p0[k]; tn[19 + 4 * k] = p1[k]; tn[20 + 4 * k] = p2[k]; tn[21 + 4 * k] = 0.0; }
     tn[54] = cnt;
-    block_reduce_limbs<true>(tn, lastkey, overflow, red_l, row, false);
+    block_reduce_limbs<true, WAVES, false>(tn, lastkey, overflow, red_l, row, false);
 }
 
-// Exhaustive loops whose NEXT SEARCH moves the cloud (nn1_sphere.hpp, MV; DESIGN.md 6h): the sums and the solve alone.  The front half is that of
-// icp_sums_update_move_kernel — same loads, same gate, same limbs, same row, same release — but nobody waits: every workgroup takes a TICKET from the same
-// monotonic counter (every workgroup of every launch arrives, in every phase; the host passes the value the counter has once all of this launch have), and
-// the ONE workgroup whose ticket is the last acquires, reduces the gridDim.x rows, solves and publishes the whole state to st_out; every other workgroup
-// returns.  No spin, no residency condition on the grid: the move needs the new R, t, but the move is the next launch's — the search loads every query
-// anyway and applies Rd, td of the state it reads its stop flags from.  Phases 0 and 1 (stopped loop, stop_after_transform): the last arriver writes the
-// stopped state, as workgroup 0 of the other kernel does.
-template <int T>
+// live limb p (the numbering of block_reduce_limbs' butterfly: 12 coordinate limbs, 27 product limbs, the count) -> its slot of a row
+__host__ __device__ constexpr int live_slot(int p) { return p < 12 ? 3 * (p / 2) + p % 2 : (p < 39 ? 18 + 4 * ((p - 12) / 3) + (p - 12) % 3 : 54); }
+
+// carry propagation of one sum in integer arithmetic, the rule of num::limbs_normalize (quotient truncated toward zero, remainder with the dividend's
+// sign, carry into the next limb): L[0..n) limbs, L[n] the carry limb; out[] the normalised f64 limbs.  The quotient by 2^40 is a shift of the
+// dividend, biased by 2^40 - 1 where it is negative (an arithmetic shift alone rounds toward minus infinity)
+__device__ __forceinline__ void limbs_normalize_i64(long long* L, int n, double* out)
+{
+    constexpr long long W = 1ll << num::KB_W;
+    for (int j = 0; j < n; j++) {
+        const long long c = (L[j] + ((L[j] >> 63) & (W - 1))) >> num::KB_W;
+        L[j] -= c * W;
+        L[j + 1] += c;
+        out[j] = (double)L[j];
+    }
+    out[n] = (double)L[n];
+}
+
+// Exhaustive loops whose NEXT SEARCH moves the cloud (nn1_sphere.hpp, MV; DESIGN.md 6h, 6i): the sums and the solve alone.  The front half is that of
+// icp_sums_update_move_kernel — same loads, same gate, same limbs, same butterfly and LDS combine — for PP pairs per thread, but nobody waits and nobody
+// stores a row: a workgroup's totals are exact integers below 2^53 (T x PP terms below 2^40), so lanes 0 .. 41 of its first wave convert them to int64
+// and ADD them, one atomic instruction, into replica blockIdx.x & (R - 1) of ctx->icp_acc_dev: 40 live limbs, the overflow count, and the last-kept key
+// by an atomic max.  Then the wave drains (vmcnt(0): the atomics have been performed), its lane 0 releases and takes a TICKET from the monotonic counter (every
+// workgroup of every launch arrives, in every phase; the host passes the value the counter has once all of this launch have).  The ONE workgroup whose
+// ticket is the last acquires, reads the R replicas in one trip — whatever the geometry —, writes zeros back over them (the invariant: all zero between
+// launches; the next launch is stream-ordered behind this one), adds them as integers, propagates the carries, and goes on through row_to_out18 and
+// icp_state_step to publish the whole state to st_out; every other workgroup has returned.  No spin, no residency condition on the grid: the move needs
+// the new R, t, but the move is the next launch's.  Phases 0 and 1 (stopped loop, stop_after_transform) add nothing and leave the zeros alone: the last
+// arriver writes the stopped state.
+// An accumulator holds at most n terms below 2^40: n < 2^22 (icp_sums_solve_blocks) keeps it below 2^62.
+constexpr int ACC_R = ICP_ACC_REPLICAS, ACC_W = ICP_ACC_WORDS;      // words of a replica: [0..40) live limbs, [40] overflow count, [41] key, pad to 3 lines
+static_assert((ACC_R & (ACC_R - 1)) == 0 && ACC_W * 8 % 128 == 0 && ACC_W >= KB_NLC + 2, "replicas: a power of two, whole 128-byte lines");
+
+template <int T, int PP>
 __global__ __launch_bounds__(T) void icp_sums_solve_kernel(
     const float* __restrict__ tx, const float* __restrict__ ty, const float* __restrict__ tz, const uint32_t* __restrict__ orig,
-    const unsigned long long* __restrict__ keys, uint32_t nt, float max_corr, KabschPlan plan, double* partials, unsigned long long* counter,
+    const unsigned long long* __restrict__ keys, uint32_t nt, float max_corr, KabschPlan plan, long long* acc, unsigned long long* counter,
     unsigned long long target, const IcpState* __restrict__ st_in, IcpState* __restrict__ st_out, double* __restrict__ out, const float* __restrict__ x,
-    const float* __restrict__ y, const float* __restrict__ z, uint32_t n, uint32_t n4)
+    const float* __restrict__ y, const float* __restrict__ z, uint32_t n, uint32_t np
+#ifdef PCR_SS_PROF
+    , unsigned long long* prof
+#endif
+    )
 {
     constexpr int WAVES = T / 64;
+    static_assert((unsigned long long)T * PP * (1ull << num::KB_W) <= (1ull << 53), "a workgroup's limb totals must be exact in f64");
+    static_assert(T >= 64 && ACC_R * ACC_W <= 2 * T, "the last arriver reads the replicas in at most two loads per thread");
     __shared__ double red_l[WAVES][KB_NL];
-    __shared__ double red[WAVES][64];
+    __shared__ long long s_acc[ACC_R][ACC_W];
     __shared__ double row[KB_ROW];
     __shared__ double o18[19];
     __shared__ IcpState s_st;
     __shared__ int s_last;
+#ifdef PCR_SS_PROF
+    const unsigned long long pt_a = __builtin_amdgcn_s_memrealtime();
+    unsigned long long pt_b = pt_a, pt_c = pt_a;
+#endif
     const uint32_t i = blockIdx.x * T + threadIdx.x;
     uint32_t stw = 0;                       // (the state first: it is on the critical path and loads retire in order)
     if (threadIdx.x < ST_WORDS) stw = reinterpret_cast<const uint32_t*>(st_in)[threadIdx.x];
-    FsPairs P;
-    fs_load_pairs(P, i < n4, i, n, x, y, z, keys, orig, tx, ty, tz, nt);
+    FsPairs<PP> P;
+    fs_load_pairs<PP>(P, i < np, i, n, x, y, z, keys, orig, tx, ty, tz, nt);
     if (threadIdx.x < ST_WORDS) reinterpret_cast<uint32_t*>(&s_st)[threadIdx.x] = stw;
     __syncthreads();
     const int phase = (s_st.stop || s_st.barrier_timeout) ? 0 : (s_st.stop_after_transform ? 1 : 2);       // uniform over the GRID
-    if (phase == 2) {
-        fs_pairs_row(P, max_corr, plan, nt, red_l, row);
-        if (threadIdx.x < KB_ROW) partials[(size_t)blockIdx.x * KB_ROW + threadIdx.x] = row[threadIdx.x];
-    }
-    // ---- the ticket: wave 0 stored the row; it drains its stores, its lane 0 releases and arrives; the last arriver acquires
+    if (phase == 2) fs_pairs_row<PP, WAVES>(P, max_corr, plan, nt, red_l, row);
+    // ---- the contribution and the ticket: wave 0 adds the totals, drains, its lane 0 releases and arrives; the last arriver acquires
     if (threadIdx.x < 64) {
-        if (phase == 2) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (phase == 2) {
+#ifdef PCR_SS_PROF
+            pt_b = __builtin_amdgcn_s_memrealtime();
+#endif
+            long long* mine = acc + (size_t)(blockIdx.x & (ACC_R - 1)) * ACC_W;
+            const int l = threadIdx.x;
+            if (l < KB_NLC) __hip_atomic_fetch_add(mine + l, (long long)row[live_slot(l)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            else if (l == KB_NLC) __hip_atomic_fetch_add(mine + l, row[56] != 0.0 ? 1ll : 0ll, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            else if (l == KB_NLC + 1)
+                __hip_atomic_fetch_max(reinterpret_cast<unsigned long long*>(mine + l), (unsigned long long)__double_as_longlong(row[55]), __ATOMIC_RELAXED,
+                                       __HIP_MEMORY_SCOPE_AGENT);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
         if (threadIdx.x == 0) {
             if (phase == 2) {
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // (kept behind the fence whatever the compiler thinks of the scoreboard)
             }
             const int last = __hip_atomic_fetch_add(counter, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1ull == target;
+#ifdef PCR_SS_PROF
+            pt_c = __builtin_amdgcn_s_memrealtime();
+            if (prof && phase == 2) { atomicAdd(prof + 12, pt_b - pt_a); atomicAdd(prof + 13, pt_c - pt_b); atomicAdd(prof + 14, 1ull); atomicMax(prof + 15, pt_c - pt_b); }
+#endif
             if (last && phase == 2) {
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the invalidate is over before the barrier below lets the other waves read
@@ -938,14 +1012,68 @@ __global__ __launch_bounds__(T) void icp_sums_solve_kernel(
     __syncthreads();
     if (!s_last) return;
     if (phase == 2) {
-        reduce_rows(partials, gridDim.x, red, row);
+#ifdef PCR_SS_PROF
+        const unsigned long long pt_c1 = __builtin_amdgcn_s_memrealtime();
+#endif
+        // the R replicas, one trip (relaxed agent-scope loads: past this CU's L1), and the zeros back over them
+        for (int t = threadIdx.x; t < ACC_R * ACC_W; t += T) {
+            (&s_acc[0][0])[t] = __hip_atomic_load(acc + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(acc + t, 0ll, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        __syncthreads();
+#ifdef PCR_SS_PROF
+        const unsigned long long pt_c2 = __builtin_amdgcn_s_memrealtime();
+#endif
+        const int k = threadIdx.x;
+        if (k < KB_NLC + 2) {
+            // word k over the replicas, into replica 0's place: the sums of the limbs and of the overflow counts, the maximum of the keys
+            long long v = s_acc[0][k];
+#pragma unroll
+            for (int r = 1; r < ACC_R; r++) {
+                const long long o = s_acc[r][k];
+                v = k == KB_NLC + 1 ? (long long)((unsigned long long)o > (unsigned long long)v ? o : v) : v + o;
+            }
+            s_acc[0][k] = v;          // (thread k alone reads and writes column k)
+        }
+        __syncthreads();
+        if (k < 15) {
+            // sum k: its 2 (coordinates) or 3 (products) live limbs, then the carries
+            const int nl = k < 6 ? 2 : 3, p0 = k < 6 ? 2 * k : 12 + 3 * (k - 6), s0 = k < 6 ? 3 * k : 18 + 4 * (k - 6);
+            long long L[4] = { 0, 0, 0, 0 };
+            for (int j = 0; j < nl; j++) L[j] = s_acc[0][p0 + j];
+            limbs_normalize_i64(L, nl, row + s0);
+        } else if (k == 15) {
+            row[54] = (double)s_acc[0][KB_NLC - 1];
+        } else if (k == 16) {
+            row[55] = __longlong_as_double(s_acc[0][KB_NLC + 1]);
+            row[56] = s_acc[0][KB_NLC] != 0 ? 1.0 : 0.0;
+            row[57] = 0.0;
+        }
+        __syncthreads();
+#ifdef PCR_SS_PROF
+        unsigned long long pt_d = __builtin_amdgcn_s_memrealtime(), pt_e = pt_d;
+#endif
         row_to_out18(row, plan.e, o18);
         __syncthreads();
         if (threadIdx.x < 19) out[threadIdx.x] = o18[threadIdx.x];
-        if (threadIdx.x == 0) icp_state_step(&s_st, o18, o18[16] >= 0.0, (float)o18[17], o18[18] != 0.0);
-    } else if (threadIdx.x == 0) {
-        s_st.stop = 1;                         // (phase 0: stays stopped; phase 1: max_iter reached, the loop is over)
+        if (threadIdx.x == 0) {
+            icp_state_step(&s_st, o18, o18[16] >= 0.0, (float)o18[17], o18[18] != 0.0);
+#ifdef PCR_SS_PROF
+            pt_e = __builtin_amdgcn_s_memrealtime();
+#endif
+        }
+        __syncthreads();
+        if (threadIdx.x < ST_WORDS) reinterpret_cast<uint32_t*>(st_out)[threadIdx.x] = reinterpret_cast<const uint32_t*>(&s_st)[threadIdx.x];
+#ifdef PCR_SS_PROF
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (prof && threadIdx.x == 0) {          // (the last arriver alone: plain values, ticket -> replicas reduced -> solved -> published)
+            prof[0] = pt_d - pt_c; prof[1] = pt_e - pt_d; prof[11] = __builtin_amdgcn_s_memrealtime() - pt_e;
+            prof[2] = pt_c1 - pt_c; prof[3] = pt_c2 - pt_c1;     // (ticket -> acquired -> replicas in LDS)
+        }
+#endif
+        return;
     }
+    if (threadIdx.x == 0) s_st.stop = 1;       // (phase 0: stays stopped; phase 1: max_iter reached, the loop is over)
     __syncthreads();
     if (threadIdx.x < ST_WORDS) reinterpret_cast<uint32_t*>(st_out)[threadIdx.x] = reinterpret_cast<const uint32_t*>(&s_st)[threadIdx.x];
 }
@@ -1126,38 +1254,58 @@ int launch_icp_sums_update_move(pcr_ctx* ctx, const pcr_cloud* tgt, pcr_cloud* c
     return PCR_OK;
 }
 
-// threads per workgroup of the sums + solve launch (4 pairs per thread; tune icp_sums_solve_threads: 128 / 256 / 512; profiles/icp_move_in_search.txt)
+// geometry of the sums + solve launch: threads per workgroup (tune icp_sums_solve_threads: 256 / 512) and consecutive pairs per thread (tune
+// icp_sums_solve_pairs: 1 / 2 / 4); any other value is the default (profiles/icp_sums_accumulators.txt)
+constexpr int SS_THREADS_DEFAULT = 512, SS_PAIRS_DEFAULT = 2;
 static int ss_threads(const pcr_ctx* ctx)
 {
-    const int64_t t = tune_get(ctx, "icp_sums_solve_threads", 512);
-    return t == 128 ? 128 : t == 256 ? 256 : 512;
+    const int64_t t = tune_get(ctx, "icp_sums_solve_threads", SS_THREADS_DEFAULT);
+    return t == 256 ? 256 : t == 512 ? 512 : SS_THREADS_DEFAULT;
+}
+static int ss_pairs(const pcr_ctx* ctx)
+{
+    const int64_t p = tune_get(ctx, "icp_sums_solve_pairs", SS_PAIRS_DEFAULT);
+    return p == 1 ? 1 : p == 2 ? 2 : p == 4 ? 4 : SS_PAIRS_DEFAULT;
 }
 
 // the workgroups the sums + solve launch takes for n points, or 0 where it does not run: the switch and the lower bound of the fused sums + move launch
-// (icp_fused_sums = 2, icp_fused_sums_min), but no cap at one workgroup per CU — nobody waits for anybody
+// (icp_fused_sums = 2, icp_fused_sums_min), but no cap at one workgroup per CU — nobody waits for anybody.  From 2^22 points on it never runs, whatever
+// the tunes say: an int64 accumulator takes n terms below 2^40
 uint32_t icp_sums_solve_blocks(const pcr_ctx* ctx, size_t n)
 {
-    if (n == 0 || tune_get(ctx, "icp_fused_sums", 1) != 1 || (int64_t)n < tune_get(ctx, "icp_fused_sums_min", 60000)) return 0;
-    const uint64_t T = (uint64_t)ss_threads(ctx), n4 = ((uint64_t)n + 3) / 4, blocks = (n4 + T - 1) / T;
-    return blocks <= (uint64_t)KB_MAX_BLOCKS ? (uint32_t)blocks : 0u;
+    if (n == 0 || n >= ((size_t)1 << 22) || tune_get(ctx, "icp_fused_sums", 1) != 1 || (int64_t)n < tune_get(ctx, "icp_fused_sums_min", 60000)) return 0;
+    const uint64_t T = (uint64_t)ss_threads(ctx), PP = (uint64_t)ss_pairs(ctx), np = ((uint64_t)n + PP - 1) / PP;
+    return (uint32_t)((np + T - 1) / T);
 }
 
 int launch_icp_sums_solve(pcr_ctx* ctx, const pcr_cloud* tgt, const pcr_cloud* c, float max_corr, const IcpState* st_in, IcpState* st_out, const KabschPlan& plan)
 {
     if (ctx->keys_n != c->n) return fail(ctx, PCR_ERR_STATE, "kabsch: no matching correspondence pass");
     const uint32_t blocks = icp_sums_solve_blocks(ctx, c->n);
-    if (!blocks || !ctx->icp_barrier_dev) return fail(ctx, PCR_ERR_STATE, "launch_icp_sums_solve");
-    const uint32_t n4 = (uint32_t)((c->n + 3) / 4);
+    if (!blocks || !ctx->icp_barrier_dev || !ctx->icp_acc_dev) return fail(ctx, PCR_ERR_STATE, "launch_icp_sums_solve");
+    if (ctx->icp_acc_dirty) {
+        // a call that ended in an error may have left sums behind: clear them once, in front of this call's first launch (a clean call adds nothing here)
+        PCR_HIP(ctx, hipMemsetAsync(ctx->icp_acc_dev, 0, (size_t)ICP_ACC_REPLICAS * ICP_ACC_WORDS * sizeof(long long), ctx->stream));
+        ctx->icp_acc_dirty = false;
+    }
+    const int T = ss_threads(ctx), PP = ss_pairs(ctx);
+    const uint32_t np = (uint32_t)((c->n + PP - 1) / PP);
     const unsigned long long target = ctx->icp_barrier_arrived + blocks;      // the counter's value once every workgroup of this launch has arrived
     {
         ProfScope p(ctx, "icp_update");
-#define PCR_SS(T)                                                                                                                                 \
-        hipLaunchKernelGGL((icp_sums_solve_kernel<T>), dim3(blocks), dim3(T), 0, ctx->stream, tgt->x(), tgt->y(), tgt->z(), c->orig, ctx->keys,      \
-                           (uint32_t)tgt->n, max_corr, plan, ctx->partials, ctx->icp_barrier_dev, target, st_in, st_out, ctx->dev_out, c->x(), c->y(), \
-                           c->z(), (uint32_t)c->n, n4)
-        const int T = ss_threads(ctx);
-        if (T == 128) PCR_SS(128); else if (T == 256) PCR_SS(256); else PCR_SS(512);
+#ifdef PCR_SS_PROF
+#define PCR_SS_EXTRA , ctx->grid_stats_dev
+#else
+#define PCR_SS_EXTRA
+#endif
+#define PCR_SS(T, PP)                                                                                                                             \
+        hipLaunchKernelGGL((icp_sums_solve_kernel<T, PP>), dim3(blocks), dim3(T), 0, ctx->stream, tgt->x(), tgt->y(), tgt->z(), c->orig, ctx->keys,  \
+                           (uint32_t)tgt->n, max_corr, plan, ctx->icp_acc_dev, ctx->icp_barrier_dev, target, st_in, st_out, ctx->dev_out, c->x(),    \
+                           c->y(), c->z(), (uint32_t)c->n, np PCR_SS_EXTRA)
+        if (T == 256) { if (PP == 1) PCR_SS(256, 1); else if (PP == 2) PCR_SS(256, 2); else PCR_SS(256, 4); }
+        else { if (PP == 1) PCR_SS(512, 1); else if (PP == 2) PCR_SS(512, 2); else PCR_SS(512, 4); }
 #undef PCR_SS
+#undef PCR_SS_EXTRA
     }
     PCR_HIP(ctx, hipGetLastError());
     ctx->icp_barrier_arrived = target;        // (counted only once the launch is on the stream)

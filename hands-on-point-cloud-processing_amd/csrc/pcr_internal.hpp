@@ -20,6 +20,8 @@ namespace pcr {
 // padded target can never win a nearest-neighbour comparison (d2 = +inf is not < FLT_MAX).
 constexpr size_t PAD = 1024;
 constexpr int PCR_NSTATS = 16;      // diagnostics words of a 1-NN launch (tune grid_stats; pcr_nn1_stats)
+// the accumulators of the ICP sums + solve launch (kabsch.hip): replicas (a power of two) of 48 int64 = three 128-byte lines each
+constexpr int ICP_ACC_REPLICAS = 8, ICP_ACC_WORDS = 48;
 
 inline size_t padded(size_t n) { return ((n + PAD - 1) / PAD) * PAD + PAD; }   // always >= 1 full pad block
 
@@ -187,6 +189,11 @@ struct pcr_ctx {
     // states, never reset) and the value it has once every workgroup of every launch so far has arrived
     unsigned long long* icp_barrier_dev = nullptr;
     uint64_t icp_barrier_arrived = 0;
+    // the accumulators of the sums + solve launch (kabsch.hip icp_sums_solve_kernel): ICP_ACC_REPLICAS x ICP_ACC_WORDS int64 behind the
+    // counter, zeroed with it; ALL ZERO between launches (the last arriver writes the zeros back).  dirty: a call ended in an error — the next call's
+    // first launch clears them
+    long long* icp_acc_dev = nullptr;
+    bool icp_acc_dirty = false;
     pcr::IcpState* icp_state_host = nullptr;
     hipEvent_t icp_events[4] = { nullptr, nullptr, nullptr, nullptr };
     unsigned long long* grid_stats_dev = nullptr;   // diagnostics of the grid search (tune grid_stats)
@@ -332,7 +339,8 @@ uint32_t icp_fused_sums_blocks(const pcr_ctx* ctx, size_t n);
 int launch_icp_sums_update_move(pcr_ctx* ctx, const pcr_cloud* tgt, pcr_cloud* c, float max_corr, const IcpState* st_in, IcpState* st_out,
                                 const KabschPlan& plan, const pcr_cloud* seed_tgt);
 // the chain search (moves the cloud by the previous solve) -> sums + solve: the front half of the launch above and a ticket, the last
-// workgroup to arrive reduces and solves; nobody waits and nothing moves.  icp_sums_solve_blocks = its workgroups (0: switched off or too few points)
+// workgroup to arrive reduces and solves; nobody waits and nothing moves.  A workgroup's totals go out as int64 atomic adds into ctx->icp_acc_dev, not
+// as a row.  icp_sums_solve_blocks = its workgroups (0: switched off, too few points, or 2^22 points and more)
 uint32_t icp_sums_solve_blocks(const pcr_ctx* ctx, size_t n);
 int launch_icp_sums_solve(pcr_ctx* ctx, const pcr_cloud* tgt, const pcr_cloud* c, float max_corr, const IcpState* st_in, IcpState* st_out, const KabschPlan& plan);
 // nn1_brute.hip: can a seeded STRACK3 search of ns queries over n_l0 level-0 super-tiles carry the move (transposed form, one slice)?  Raw tune values

@@ -5,10 +5,14 @@ usage: run_icp_tail.py trace [n]            two 20-iteration exhaustive loops at
        run_icp_tail.py ab [reps]            wall time per iteration, the arms alternating in ONE process — move in search / fused sums + move / three
                                             launches: 60 k / 120 k / 250 k exhaustive (20 iterations; 250 k is multi-slice: the first arm falls back to
                                             the second) and hw9's 4 000 points with the grid (800 iterations); median and spread (max - min) over reps;
-                                            at 120 k also 256-thread workgroups (icp_fused_sums_threads) and the other geometries of the sums + solve
-                                            launch (icp_sums_solve_threads 256 / 128)
+                                            at 120 k also 256-thread workgroups (icp_fused_sums_threads); at every exhaustive size the six geometries
+                                            of the sums + solve launch (icp_sums_solve_threads 256 / 512 x icp_sums_solve_pairs 1 / 2 / 4)
        run_icp_tail.py stamps [n]           profile build (tools/ab_build.sh fsprof kabsch.hip -DPCR_FS_PROF; PCR_LIB_PATH=.../libpcr_fsprof.so): per workgroup
                                             the time from its row store to the end of its wait at the grid barrier, last iteration of a 20-iteration loop
+       run_icp_tail.py ss_stamps [n] [T:P,...]   profile build (tools/ab_build.sh ssprof kabsch.hip -DPCR_SS_PROF; PCR_LIB_PATH=.../libpcr_ssprof.so): the sums +
+                                            solve launch of the chain search -> sums + solve, last iteration of a 20-iteration loop, per geometry (threads :
+                                            pairs): per workgroup entry -> totals ready and totals ready -> ticket returned; for the last arriver ticket ->
+                                            sums reduced -> solved -> published
 PCR_TUNE="key=value,..." sets any other knob."""
 import importlib, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -45,18 +49,33 @@ elif mode == "stamps":
         w = ctx.nn1_stats(); k = max(w[14], 1)
         print(f"n={n} threads {threads}: workgroups stamped {w[14]}; row store -> end of wait: mean {w[12] / k / 100:.2f} us, longest {w[13] / 100:.2f} us; "
               f"kernel entry -> row store: mean {w[15] / k / 100:.2f} us")
+elif mode == "ss_stamps":
+    n = int(sys.argv[2]) if len(sys.argv) > 2 else 120000
+    geoms = [tuple(int(v) for v in g.split(":")) for g in (sys.argv[3] if len(sys.argv) > 3 else "512:4,512:2,512:1,256:4,256:2,256:1").split(",")]
+    cs, ct = pair(n); ctx.tune("nn_method", 1); ctx.tune("icp_move_in_search", 1)
+    ctx.icp_point2point(cs, ct, max_corr=1.0, max_iter=20, eps=0.0)
+    ctx.tune("grid_stats", 1)
+    for threads, pairs in geoms:
+        ctx.tune("icp_sums_solve_threads", threads); ctx.tune("icp_sums_solve_pairs", pairs)
+        for _ in range(3):
+            ctx.icp_point2point(cs, ct, max_corr=1.0, max_iter=20, eps=0.0)
+            w = ctx.nn1_stats(); k = max(w[14], 1)
+            print(f"n={n} threads {threads} pairs {pairs} chain {ctx.icp_last_chain()}: workgroups {w[14]}; entry -> totals ready: mean {w[12] / k / 100:.2f} us; "
+                  f"totals ready -> ticket returned: mean {w[13] / k / 100:.2f} us, longest {w[15] / 100:.2f} us; last arriver: ticket -> sums reduced "
+                  f"{w[0] / 100:.2f} us (acquired {w[2] / 100:.2f}, replicas in LDS {w[3] / 100:.2f}), -> solved {w[1] / 100:.2f} us, -> published {w[11] / 100:.2f} us")
 else:
     reps = int(sys.argv[2]) if len(sys.argv) > 2 else 8
-    # an arm: (icp_move_in_search, icp_fused_sums, icp_fused_sums_threads, icp_sums_solve_threads)
-    MV, FS, TL = (1, 1, 512, 512), (2, 1, 512, 512), (2, 2, 512, 512)
-    for n, method, iters, arms in ((60000, 1, 20, (MV, FS, TL)), (120000, 1, 20, (MV, FS, TL, (2, 1, 256, 512), (1, 1, 512, 256), (1, 1, 512, 128))),
-                                   (250000, 1, 20, (MV, FS, TL)), (4000, 2, 800, (FS, TL))):
+    # an arm: (icp_move_in_search, icp_fused_sums, icp_fused_sums_threads, icp_sums_solve_threads, icp_sums_solve_pairs)
+    MV, FS, TL = (1, 1, 512, 0, 0), (2, 1, 512, 0, 0), (2, 2, 512, 0, 0)
+    GEO = tuple((1, 1, 512, t, p) for t in (512, 256) for p in (4, 2, 1))
+    for n, method, iters, arms in ((60000, 1, 20, (MV, FS, TL) + GEO), (120000, 1, 20, (MV, FS, TL, (2, 1, 256, 0, 0)) + GEO),
+                                   (250000, 1, 20, (MV, FS, TL) + GEO), (4000, 2, 800, (FS, TL))):
         cs, ct = pair(n); ctx.tune("nn_method", method)
         us = {a: [] for a in arms}
         poses, chains = {}, {}
         for r in range(reps + 1):                      # (the first round warms up: indexes, spare buffers)
             for a in arms:
-                for k_, v_ in zip(("icp_move_in_search", "icp_fused_sums", "icp_fused_sums_threads", "icp_sums_solve_threads"), a):
+                for k_, v_ in zip(("icp_move_in_search", "icp_fused_sums", "icp_fused_sums_threads", "icp_sums_solve_threads", "icp_sums_solve_pairs"), a):
                     ctx.tune(k_, v_)
                 t0 = time.perf_counter()
                 T, st = ctx.icp_point2point(cs, ct, max_corr=1.0, max_iter=iters, eps=0.0)
@@ -66,7 +85,7 @@ else:
         same = all(p == poses[arms[0]] for p in poses.values())
         for a in arms:
             v = np.array(us[a])
-            print(f"n={n} method={method} iterations={iters} icp_move_in_search={a[0]} icp_fused_sums={a[1]} threads={a[2]} solve threads={a[3]} chain {chains[a]}: "
+            print(f"n={n} method={method} iterations={iters} icp_move_in_search={a[0]} icp_fused_sums={a[1]} threads={a[2]} solve threads={a[3]} pairs={a[4]} chain {chains[a]}: "
                   f"median {np.median(v):.2f} us/iteration, spread {v.max() - v.min():.2f} "
                   f"(min {v.min():.2f}, max {v.max():.2f}; {reps} calls); pose bits equal: {same}")
         cs.free(); ct.free()
