@@ -92,6 +92,11 @@ class Pn2MsgDesc(C.Structure):
                 ("bn_eps", C.c_double)]
 
 
+class Pn1Desc(C.Structure):
+    _fields_ = [("D0", C.c_uint32), ("stn3", C.c_uint32), ("fstn", C.c_uint32), ("n_mlp", C.c_uint32), ("widths", C.c_uint32 * 4),
+                ("tnet_conv", C.c_uint32 * 3), ("tnet_fc", C.c_uint32 * 2), ("n_fc", C.c_uint32), ("fc_widths", C.c_uint32 * 4), ("bn_eps", C.c_double)]
+
+
 class Pn2Info(C.Structure):
     _fields_ = [("n_weights", C.c_uint64), ("macs_per_object", C.c_uint64), ("n_sampling", C.c_uint32), ("n_class", C.c_uint32),
                 ("c_last", C.c_uint32), ("reserved", C.c_uint32)]
@@ -115,6 +120,7 @@ ABI_SYMBOLS = [
     "pcr_fps_f32", "pcr_ball_query_f32", "pcr_group_points_f32", "pcr_objects_from_labels_f32", "pcr_points_in_boxes_f64", "pcr_label_aabb_f32",
     "pcr_pn2_model_create", "pcr_pn2_model_destroy", "pcr_pn2_model_info", "pcr_sa_mlp_max_f32", "pcr_pn2_forward_f32",
     "pcr_pn2_msg_model_create", "pcr_pn2_msg_model_info", "pcr_ball_query_multi_f32", "pcr_sa_msg_mlp_max_f32",
+    "pcr_pn1_model_create", "pcr_pn1_model_info", "pcr_pointwise_chain_max_f32", "pcr_pointnet_forward_f32",
     "pcr_mat64_create", "pcr_mat64_destroy", "pcr_mat64_info", "pcr_kmeans_step_f64", "pcr_kmeans_fit_f64", "pcr_kmeans_predict_f64", "pcr_kmeanspp_init_f64",
     "pcr_gmm_em_step_f64", "pcr_gmm_fit_f64", "pcr_gmm_predict_f64",
     "pcr_mat64_knn_f64", "pcr_spectral_graph_f64", "pcr_spgraph_info", "pcr_spgraph_read", "pcr_spgraph_destroy", "pcr_eig_small_f64",
@@ -235,6 +241,10 @@ def lib():
     L.pcr_pn2_msg_model_info.argtypes = [vp, sz, C.POINTER(Pn2Info), C.POINTER(Pn2MsgDesc)]
     L.pcr_ball_query_multi_f32.argtypes = [vp, vp, vp, vp, vp, sz, sz, vp, vp, vp, vp]
     L.pcr_sa_msg_mlp_max_f32.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp, sz, vp, vp, vp]
+    L.pcr_pn1_model_create.argtypes = [vp, C.POINTER(Pn1Desc), vp, sz, C.POINTER(vp)]
+    L.pcr_pn1_model_info.argtypes = [vp, sz, C.POINTER(Pn2Info), C.POINTER(Pn1Desc)]
+    L.pcr_pointwise_chain_max_f32.argtypes = [vp, vp, C.c_int, vp, vp, sz, vp, vp, vp, vp]
+    L.pcr_pointnet_forward_f32.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp, vp]
     L.pcr_mat64_create.argtypes = [vp, vp, sz, C.c_int, C.POINTER(vp)]
     L.pcr_mat64_destroy.argtypes = [vp, vp]
     L.pcr_mat64_info.argtypes = [vp, C.POINTER(sz), ip, ip]
@@ -523,6 +533,36 @@ def pn2_msg_desc_info(desc: Pn2MsgDesc, npts: int = 0) -> dict:
             "c_last": int(i.c_last)}
 
 
+def pn1_desc(widths=(64, 128, 1024), fc=(512, 256, 40), D0: int = 0, stn3: bool = True, fstn: bool = True, tnet_conv=(64, 128, 1024), tnet_fc=(512, 256),
+             bn_eps: float = 1e-5) -> Pn1Desc:
+    """The vanilla PointNet classifier (the defaults are the reference's): widths = the encoder's convolutions, fc = the head's output widths,
+    tnet_conv / tnet_fc = the widths of both T-Nets.  The contract is above pcr_pn1_model_create in include/pcr.h."""
+    widths, fc, tnet_conv, tnet_fc = list(widths), list(fc), list(tnet_conv), list(tnet_fc)
+    if len(widths) > 4 or len(fc) > 4 or len(tnet_conv) != 3 or len(tnet_fc) != 2:
+        raise PcrError("at most 4 encoder widths and 4 FC layers; a T-Net has 3 convolution widths and 2 FC widths")
+    d = Pn1Desc()
+    d.D0, d.stn3, d.fstn, d.n_mlp, d.n_fc, d.bn_eps = int(D0), 1 if stn3 else 0, 1 if fstn else 0, len(widths), len(fc), float(bn_eps)
+    for k, w in enumerate(widths):
+        d.widths[k] = int(w)
+    for k, w in enumerate(tnet_conv):
+        d.tnet_conv[k] = int(w)
+    for k, w in enumerate(tnet_fc):
+        d.tnet_fc[k] = int(w)
+    for k, w in enumerate(fc):
+        d.fc_widths[k] = int(w)
+    return d
+
+
+def pn1_desc_info(desc: Pn1Desc, npts: int = 0) -> dict:
+    """What a model made from desc would report (Pn1Model.info), without a device: pcr_pn1_model_info with no model."""
+    i = Pn2Info()
+    rc = lib().pcr_pn1_model_info(None, int(npts), C.byref(i), C.byref(desc))
+    if rc != 0:
+        raise PcrError(f"{ERRORS.get(rc, rc)}: a descriptor outside the limits (see include/pcr.h)")
+    return {"n_weights": int(i.n_weights), "macs_per_object": int(i.macs_per_object), "n_sampling": int(i.n_sampling), "n_class": int(i.n_class),
+            "c_last": int(i.c_last)}
+
+
 class Pn2Model:
     """A PointNet++ classifier resident in HBM (pcr_pn2_model), single-scale (a Pn2Desc) or multi-scale (a Pn2MsgDesc): BN folded into the
     weights at upload; the contract is in include/pcr.h.  desc is the descriptor the model was made from, mdesc the superset descriptor the
@@ -568,6 +608,28 @@ class Pn2Model:
 
     def sa_in_features(self, layer: int) -> int:
         return int(self.desc.D0) if layer == 0 else self.sa_out_width(layer - 1)
+
+
+class Pn1Model(Pn2Model):
+    """A vanilla PointNet classifier resident in HBM (a pcr_pn2_model made by pcr_pn1_model_create): BN and the T-Nets' identities folded into
+    the weights at upload; the contract is in include/pcr.h.  desc is the Pn1Desc the model was made from."""
+
+    def __init__(self, ctx: "Context", desc: Pn1Desc, weights):
+        w = np.ascontiguousarray(weights, np.float32).reshape(-1)
+        h = C.c_void_p()
+        ctx._ck(lib().pcr_pn1_model_create(ctx.h, C.byref(desc), w.ctypes.data if w.size else None, w.size, C.byref(h)))
+        self.ctx, self.h, self.desc = ctx, h, desc
+        ctx._handles.add(self)
+
+    def info(self, npts: int = 0) -> dict:
+        i = Pn2Info()
+        self.ctx._ck(lib().pcr_pn1_model_info(self.h, int(npts), C.byref(i), None))
+        return {"n_weights": int(i.n_weights), "macs_per_object": int(i.macs_per_object), "n_sampling": int(i.n_sampling), "n_class": int(i.n_class),
+                "c_last": int(i.c_last)}
+
+    def stage_width(self, stage: int) -> int:
+        """the row width pcr_pointwise_chain_max_f32 writes for a stage"""
+        return int(self.desc.widths[self.desc.n_mlp - 1]) if stage == 2 else int(self.desc.tnet_conv[2])
 
 
 class Mat64:
@@ -1437,6 +1499,52 @@ class Context:
         self._ck(lib().pcr_sa_mlp_max_f32(self.h, model.h, int(layer), cloud.h, sp.ctypes.data, None if ga else centres.h, None if ga else cp.ctypes.data,
                                           n_seg, None if feat is None else feat.ctypes.data, None if ga or not ix.size else ix.ctypes.data, out.ctypes.data))
         return out[:rows]
+
+    def pn1_model(self, desc: Pn1Desc, weights) -> Pn1Model:
+        """desc: a Pn1Desc (pn1_desc(...)); weights: the flat f32 array in the order include/pcr.h states (pointnet.get_model_cls.flat_weights
+        builds it from a state dict).  BN and the T-Nets' identities are folded at upload."""
+        if not isinstance(desc, Pn1Desc):
+            raise PcrError("desc: a Pn1Desc")
+        return Pn1Model(self, desc, weights)
+
+    def pointwise_chain_max(self, model: Pn1Model, stage: int, cloud: Cloud, seg_ptr, features=None, trans3=None, trans_feat=None):
+        """One fused stage of the vanilla PointNet on the caller's transforms -> f32 [n_seg, width]; the contract of pcr_pointwise_chain_max_f32.
+        trans3: [n_seg, 3, 3] or None, trans_feat: [n_seg, K, K] (stage 2 of a model with a feature T-Net)."""
+        sp = self._seg(seg_ptr)
+        n_seg, stage = sp.size - 1, int(stage)
+        feat = None
+        if features is not None:
+            feat = np.ascontiguousarray(features, np.float32).reshape(len(cloud), -1)
+        t3 = None if trans3 is None else np.ascontiguousarray(trans3, np.float32).reshape(n_seg, 9)
+        K = int(model.desc.widths[0])
+        tk = None if trans_feat is None else np.ascontiguousarray(trans_feat, np.float32).reshape(n_seg, K * K)
+        out = np.zeros((max(n_seg, 1), model.stage_width(stage) if 0 <= stage <= 2 else 1), np.float32)
+        self._ck(lib().pcr_pointwise_chain_max_f32(self.h, model.h, stage, cloud.h, sp.ctypes.data, n_seg, None if feat is None or not feat.size else feat.ctypes.data,
+                                                   None if t3 is None or not t3.size else t3.ctypes.data, None if tk is None or not tk.size else tk.ctypes.data,
+                                                   out.ctypes.data))
+        return out[:n_seg]
+
+    def pointnet_forward(self, model: Pn1Model, objects, return_all: bool = False):
+        """The vanilla PointNet's forward pass: objects f32 [n_obj, npts, 3 + D0] -> log-probabilities f32 [n_obj, n_class]; with return_all a dict
+        (logp, pred int32 [n_obj], global_feat f32 [n_obj, C_last], trans f32 [n_obj, 3, 3] and trans_feat f32 [n_obj, K, K] where the model has
+        the T-Net, else None); the contract of pcr_pointnet_forward_f32."""
+        obj = np.ascontiguousarray(objects, np.float32)
+        if obj.ndim != 3 or obj.shape[2] != 3 + int(model.desc.D0):
+            raise PcrError("objects: [n_obj, npts, 3 + D0]")
+        n_obj, npts = obj.shape[0], obj.shape[1]
+        inf = model.info(npts)
+        cap, K = max(n_obj, 1), int(model.desc.widths[0])
+        logp = np.zeros((cap, inf["n_class"]), np.float32)
+        pred = np.zeros(cap, np.int32)
+        gf = np.zeros((cap, inf["c_last"]), np.float32)
+        t3 = np.zeros((cap, 3, 3), np.float32) if model.desc.stn3 else None
+        tk = np.zeros((cap, K, K), np.float32) if model.desc.fstn else None
+        self._ck(lib().pcr_pointnet_forward_f32(self.h, model.h, obj.ctypes.data if obj.size else None, n_obj, npts, logp.ctypes.data, pred.ctypes.data, gf.ctypes.data,
+                                                None if t3 is None else t3.ctypes.data, None if tk is None else tk.ctypes.data))
+        if not return_all:
+            return logp[:n_obj]
+        return {"logp": logp[:n_obj], "pred": pred[:n_obj], "global_feat": gf[:n_obj], "trans": None if t3 is None else t3[:n_obj],
+                "trans_feat": None if tk is None else tk[:n_obj]}
 
     def pn2_forward(self, model: Pn2Model, objects, starts=None, seed: int = 0, return_all: bool = False):
         """The whole forward pass: objects f32 [n_obj, npts, 3 + D0] -> log-probabilities f32 [n_obj, n_class]; with return_all a dict

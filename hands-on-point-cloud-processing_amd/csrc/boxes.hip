@@ -13,6 +13,7 @@
 //   label boxes       min / max are order-free: one integer-ordered atomic per (point, coordinate, bound), or one per wave where the 64 labels
 //     (label_aabb)        of a wave agree (DBSCAN's labels come in runs).
 #include "pcr_internal.hpp"
+#include "f32_key.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -195,21 +196,7 @@ __global__ void pib_row_ptr_kernel(const unsigned long long* __restrict__ offs, 
 }
 
 // ---- label boxes ---------------------------------------------------------------------------------------------------------------------
-// the order of the floats as unsigned integers: -inf < ... < -0 < +0 < ... < +inf
-__host__ __device__ inline uint32_t f32_key(float f)
-{
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-inline float f32_from_key(uint32_t k)
-{
-    const uint32_t u = (k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k;
-    float f;
-    memcpy(&f, &u, 4);
-    return f;
-}
-constexpr uint32_t KEY_PINF = 0xFF800000u, KEY_NINF = 0x007FFFFFu;      // f32_key(+inf), f32_key(-inf)
+// the order of the floats as unsigned integers (f32_key.hpp): -inf < ... < -0 < +0 < ... < +inf
 constexpr uint32_t KEY_NONE_MIN = 0xFFFFFFFFu, KEY_NONE_MAX = 0u;      // "no value" of a lane under min / max (a NaN coordinate)
 
 __global__ void aabb_init_kernel(uint32_t* __restrict__ lo, uint32_t* __restrict__ hi, uint32_t* __restrict__ count, uint32_t n_clusters)

@@ -17,7 +17,9 @@
 //                      scan of the counts (pn2_compact), one memset of the concatenated rows, one chain per branch into its own columns
 //                      (out_stride / out_col).  xyz_last puts the features before xyz - centre in layer 0's gather.  With row_ptr a tile row
 //                      maps to (group, member) through the scan of the counts: only real hits are run, the copies that pad a row are not.
+//   vanilla PointNet  (models/pointnet_cls.py, models/pointnet.py) pn1_chain_kernel and its forward pass: the second half of this file, described there.
 #include "pcr_internal.hpp"
+#include "f32_key.hpp"
 
 #include <algorithm>
 #include <cfloat>
@@ -295,7 +297,8 @@ struct Chain {
 };
 
 // rows per tile: the tuned value if it fits, else the largest of 64 / 32 / 16 that does (16 always does: two rows of 1028 floats x 16 = 129 KB)
-int chain_rows(const pcr_ctx* ctx, const Chain& ch)
+template <class C>
+int chain_rows(const pcr_ctx* ctx, const C& ch)
 {
     const int64_t want = tune_get(ctx, "pn2_rows", 0);
     const int cand[3] = { 64, 32, 16 };
@@ -391,6 +394,200 @@ struct Carve {
     void bind(void* base) const { for (auto& s : slots) *s.first = (char*)base + s.second; }
 };
 
+// ---- the vanilla PointNet (models/pointnet_cls.py, models/pointnet.py): the contract is above pcr_pn1_model_create in include/pcr.h -------------
+//   pn1_chain_kernel  one workgroup per tile of R rows = R consecutive points of ONE object (block -> (object, tile of it); an object of fewer
+//                     tiles than the launch has per object returns at once), so the object's own matrices serve every row of the tile:
+//                     gather (xyz . T3 as three plain fmaf per coordinate | features) -> up to five STEPS ping-ponging between the two LDS
+//                     buffers, a step being a convolution of the model (pn2_chain_kernel's products, W' from global memory) or the K x K
+//                     transform (the same products with the object's matrix staged in LDS in W's operand order, accumulators starting at +0,
+//                     no ReLU) -> the max over the tile's real rows on the integer key of f32_key.hpp, one atomicMax per column and tile.
+//   output            rows of keys that start at KEY_NINF; pn1_decode_kernel turns them into floats in place once the chain is done.
+constexpr int PN1_MAX_STEPS = 5;             // convolution 0, the transform, three more convolutions
+constexpr uint32_t PN1_MAX_TRANSFORM = 128;  // the K x K matrix takes Kpad^2 floats of LDS
+
+struct Pn1Stage {
+    uint32_t n = 0;                          // steps; 0: the model has no such stage
+    LayerDev L[PN1_MAX_STEPS];               // the transform step: w = b = NULL, K = N = the matrix's size
+    uint32_t t_step = UINT32_MAX;            // which step is the transform
+    uint32_t relu_last = 1, s0 = 4, s1 = 4;
+    uint32_t n_out() const { return L[n - 1].N; }
+    size_t lds_bytes(int R) const { return ((size_t)R * (s0 + s1) + (t_step < n ? (size_t)L[t_step].Kpad * L[t_step].Npad : 0)) * 4; }
+};
+
+struct Pn1Args {
+    const float *x, *y, *z;                  // the cloud
+    const float* feat;                       // D floats per point of the cloud
+    const uint32_t* seg_ptr;                 // n_seg + 1 offsets into the cloud: a segment is an object
+    const float* trans3;                     // n_seg x 9 or NULL
+    const float* transK;                     // n_seg x K x K: the matrices of the transform step
+    uint32_t* out;                           // n_seg x N keys
+    uint32_t D, tiles_per_seg, n_steps, t_step, relu_last, s0, s1;
+    LayerDev L[PN1_MAX_STEPS];
+};
+
+// acc (starting at the bias) += the K products of one 16-column output tile for the RT row tiles; wp: the tile's operand blocks at this lane
+template <int RT>
+__device__ __forceinline__ void pn1_products(f32x4 (&acc)[RT], const f32x4* wp, const float* ap, uint32_t sin, uint32_t KB)
+{
+    f32x4 bnext = wp[0];
+    for (uint32_t kb = 0; kb < KB; kb++) {
+        const f32x4 b = bnext;
+        if (kb + 1 < KB) bnext = wp[(size_t)(kb + 1) * 64];
+        f32x4 av[RT];
+#pragma unroll
+        for (int rt = 0; rt < RT; rt++) av[rt] = *(const f32x4*)(ap + (size_t)rt * 16 * sin + kb * 16);
+#pragma unroll
+        for (int rt = 0; rt < RT; rt++) acc[rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[rt].x, b.x, acc[rt], 0, 0, 0);
+#pragma unroll
+        for (int rt = 0; rt < RT; rt++) acc[rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[rt].y, b.y, acc[rt], 0, 0, 0);
+#pragma unroll
+        for (int rt = 0; rt < RT; rt++) acc[rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[rt].z, b.z, acc[rt], 0, 0, 0);
+#pragma unroll
+        for (int rt = 0; rt < RT; rt++) acc[rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[rt].w, b.w, acc[rt], 0, 0, 0);
+    }
+}
+
+template <int RT>
+__global__ __launch_bounds__(PN2_BLOCK) void pn1_chain_kernel(const Pn1Args a)
+{
+    constexpr int R = RT * 16;
+    extern __shared__ __align__(16) float pn1_lds[];
+    float* buf0 = pn1_lds;
+    float* buf1 = buf0 + (size_t)R * a.s0;
+    float* tmat = buf1 + (size_t)R * a.s1;                      // the object's K x K matrix in W's operand order
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t seg = blockIdx.x / a.tiles_per_seg, tile = blockIdx.x - seg * a.tiles_per_seg;
+    const uint32_t base = a.seg_ptr[seg], n = a.seg_ptr[seg + 1] - base;
+    if ((unsigned long long)tile * R >= n) return;              // block-uniform: this object has fewer tiles
+    const uint32_t r0 = tile * (uint32_t)R, nrows = n - r0 < (uint32_t)R ? n - r0 : (uint32_t)R;
+    // ---- step 0's input: (xyz . T3 | features | zeros up to Kpad); a row past the object's end is all zeros
+    {
+        const uint32_t Kp = a.L[0].Kpad;
+        const float* t3 = a.trans3 ? a.trans3 + (size_t)seg * 9 : nullptr;
+        for (uint32_t e = (uint32_t)tid; e < (uint32_t)R * Kp; e += PN2_BLOCK) {
+            const uint32_t r = e / Kp, pos = e - r * Kp, w = pos & 15u;
+            const uint32_t ch = (pos & ~15u) + 4u * (w & 3u) + (w >> 2);
+            float v = 0.0f;
+            if (r < nrows && ch < 3u + a.D) {
+                const size_t p = (size_t)base + r0 + r;
+                if (ch >= 3u) {
+                    v = a.feat[p * a.D + (ch - 3u)];
+                } else if (t3) {                                // y[ch] = sum_k x[k] T[k][ch]: one chain from +0, k ascending
+                    v = fmaf(a.x[p], t3[ch], 0.0f);
+                    v = fmaf(a.y[p], t3[3 + ch], v);
+                    v = fmaf(a.z[p], t3[6 + ch], v);
+                } else {
+                    v = (ch == 0 ? a.x : (ch == 1 ? a.y : a.z))[p];
+                }
+            }
+            buf0[(size_t)r * a.s0 + pos] = v;
+        }
+    }
+    if (a.t_step < a.n_steps) {                                 // position ((t KB + kb) 64 + lane) 4 + s holds W'[n][k] = T[k][n], n = 16 t + (lane & 15), k = 16 kb + 4 s + (lane >> 4)
+        const uint32_t K = a.L[a.t_step].K, Kp = a.L[a.t_step].Kpad, KB = Kp >> 4;
+        const float* T = a.transK + (size_t)seg * K * K;
+        for (uint32_t e = (uint32_t)tid; e < Kp * Kp; e += PN2_BLOCK) {
+            const uint32_t s = e & 3u, ln = (e >> 2) & 63u, blk = e >> 8, kb = blk % KB, t = blk / KB;
+            const uint32_t k = 16u * kb + 4u * s + (ln >> 4), nn = 16u * t + (ln & 15u);
+            tmat[e] = (k < K && nn < K) ? T[(size_t)k * K + nn] : 0.0f;
+        }
+    }
+    __syncthreads();
+    // ---- the steps
+    const int j = lane & 15, h = lane >> 4;
+    for (uint32_t l = 0; l < a.n_steps; l++) {
+        const LayerDev L = a.L[l];
+        const float* in = (l & 1u) ? buf1 : buf0;
+        float* outb = (l & 1u) ? buf0 : buf1;
+        const uint32_t sin = (l & 1u) ? a.s1 : a.s0, sout = (l & 1u) ? a.s0 : a.s1;
+        const bool last = l + 1 == a.n_steps, transform = l == a.t_step;
+        const uint32_t KB = L.Kpad >> 4, NT = L.Npad >> 4;
+        for (uint32_t t = (uint32_t)wave; t < NT; t += PN2_WAVES) {      // wave-uniform
+            const float bias = transform ? 0.0f : L.b[t * 16 + j];
+            f32x4 acc[RT];
+#pragma unroll
+            for (int rt = 0; rt < RT; rt++) acc[rt] = f32x4{ bias, bias, bias, bias };
+            const float* ap = in + (size_t)j * sin + 4 * h;
+            if (transform) pn1_products<RT>(acc, (const f32x4*)tmat + (size_t)t * KB * 64 + lane, ap, sin, KB);
+            else pn1_products<RT>(acc, (const f32x4*)L.w + (size_t)t * KB * 64 + lane, ap, sin, KB);
+            // lane (j, h) holds output channel 16 t + j of the rows 16 rt + 4 h + reg
+            if (!last) {
+                const uint32_t pos = t * 16 + 4u * (uint32_t)(j & 3) + (uint32_t)(j >> 2);
+#pragma unroll
+                for (int rt = 0; rt < RT; rt++)
+#pragma unroll
+                    for (int reg = 0; reg < 4; reg++)
+                        outb[(size_t)(rt * 16 + 4 * h + reg) * sout + pos] = transform ? acc[rt][reg] : pn2_relu(acc[rt][reg]);
+            } else {
+                uint32_t m = 0;                                          // below the key of every float the chain can give
+#pragma unroll
+                for (int rt = 0; rt < RT; rt++)
+#pragma unroll
+                    for (int reg = 0; reg < 4; reg++) {
+                        const float v = a.relu_last ? pn2_relu(acc[rt][reg]) : acc[rt][reg];
+                        const uint32_t key = f32_key(v);
+                        if ((uint32_t)(rt * 16 + 4 * h + reg) < nrows && key > m) m = key;
+                    }
+                uint32_t o = __shfl_xor(m, 16, 64);
+                m = o > m ? o : m;
+                o = __shfl_xor(m, 32, 64);
+                m = o > m ? o : m;
+                const uint32_t c = t * 16 + (uint32_t)j;
+                if (h == 0 && c < L.N) atomicMax(a.out + (size_t)seg * L.N + c, m);      // the tile holds a real row: m is a float's key
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// t[o] (k x k, row-major) += the identity: ONE f32 addition per diagonal entry, after the T-Net's last chain, as the reference adds it (pointnet.py:41-46)
+__global__ __launch_bounds__(PN2_BLOCK) void pn1_identity_kernel(float* __restrict__ t, uint32_t n_obj, uint32_t k)
+{
+    const size_t i = (size_t)blockIdx.x * PN2_BLOCK + threadIdx.x;
+    if (i >= (size_t)n_obj * k) return;
+    const size_t o = i / k, d = i - o * k;
+    float* p = t + (o * k + d) * k + d;
+    *p = *p + 1.0f;
+}
+
+__global__ __launch_bounds__(PN2_BLOCK) void pn1_decode_kernel(uint32_t* __restrict__ keys, size_t n)
+{
+    const size_t i = (size_t)blockIdx.x * PN2_BLOCK + threadIdx.x;
+    if (i < n) keys[i] = __float_as_uint(f32_from_key(keys[i]));
+}
+
+template <int RT>
+int pn1_launch_rt(pcr_ctx* ctx, const Pn1Args& a, size_t lds, unsigned blocks)
+{
+    PCR_HIP(ctx, hipFuncSetAttribute((const void*)pn1_chain_kernel<RT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL((pn1_chain_kernel<RT>), dim3(blocks), dim3(PN2_BLOCK), lds, ctx->stream, a);
+    PCR_HIP(ctx, hipGetLastError());
+    return PCR_OK;
+}
+
+// a.out (n_seg x n_out floats) <- the stage over the n_seg segments of a.seg_ptr, none longer than max_pts; enqueued on the stream
+int pn1_launch(pcr_ctx* ctx, const Pn1Stage& st, Pn1Args a, size_t n_seg, size_t max_pts)
+{
+    if (n_seg == 0) return PCR_OK;
+    a.n_steps = st.n; a.t_step = st.t_step; a.relu_last = st.relu_last; a.s0 = st.s0; a.s1 = st.s1;
+    for (uint32_t l = 0; l < st.n; l++) a.L[l] = st.L[l];
+    const int R = chain_rows(ctx, st);
+    const size_t lds = st.lds_bytes(R), cells = n_seg * st.n_out();
+    if (lds > PN2_LDS_LIMIT) return fail(ctx, PCR_ERR_STATE, "pointnet: a stage does not fit in LDS");
+    const unsigned long long tiles = (max_pts + R - 1) / R, blocks = tiles * n_seg;
+    if (blocks > PN2_MAX_ROWS) return fail(ctx, PCR_ERR_ARG, "pointnet: too many tiles (segments x tiles of the longest one)");
+    a.tiles_per_seg = (uint32_t)tiles;
+    ProfScope ps(ctx, "pn1_chain");
+    PCR_HIP(ctx, hipMemsetD32Async((hipDeviceptr_t)a.out, (int)KEY_NINF, cells, ctx->stream));
+    if (blocks) {
+        const int rc = R == 64 ? pn1_launch_rt<4>(ctx, a, lds, (unsigned)blocks) : R == 32 ? pn1_launch_rt<2>(ctx, a, lds, (unsigned)blocks) : pn1_launch_rt<1>(ctx, a, lds, (unsigned)blocks);
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(pn1_decode_kernel, dim3((unsigned)((cells + PN2_BLOCK - 1) / PN2_BLOCK)), dim3(PN2_BLOCK), 0, ctx->stream, a.out, cells);
+    PCR_HIP(ctx, hipGetLastError());
+    return PCR_OK;
+}
+
 }  // namespace
 
 }  // namespace pcr
@@ -410,6 +607,11 @@ struct pcr_pn2_model {
     uint32_t sa_out[PCR_PN2_MAX_SA]; // its width: the sum of its branches' last widths
     uint64_t n_weights = 0;
     uint32_t n_sampling = 0;
+    // ---- a model of pcr_pn1_model_create (the vanilla PointNet): desc / ssg / sa stay empty, head is the classifier's
+    bool pn1 = false;
+    pcr_pn1_desc d1;
+    Pn1Stage stage[3];               // the fused point stages (n == 0: the model has no such stage)
+    Chain tnet_head[2];              // the FC layers of the input / the feature T-Net: -> 9 / K x K floats per object, before the identity is added
 };
 
 namespace {
@@ -468,6 +670,50 @@ void chain_strides(Chain& ch)
 
 namespace {
 
+// BN folded (f64, rounded once) into the operand order of the kernel: img <- every layer's W' block and bias, w_off / b_off <- where they start.
+// NULL, or what is wrong with the weights
+const char* fold_layers(const std::vector<LayerShape>& shapes, const float* weights, double bn_eps, std::vector<float>& img, std::vector<size_t>& w_off,
+                        std::vector<size_t>& b_off)
+{
+    size_t dev_floats = 0;
+    w_off.resize(shapes.size());
+    b_off.resize(shapes.size());
+    for (size_t i = 0; i < shapes.size(); i++) {
+        const size_t Kp = pad16(shapes[i].K), Np = pad16(shapes[i].N);
+        w_off[i] = dev_floats; dev_floats += Kp * Np;
+        b_off[i] = dev_floats; dev_floats += Np;
+        dev_floats = (dev_floats + 63) & ~(size_t)63;      // every operand block starts on 256 bytes
+    }
+    img.assign(dev_floats, 0.0f);
+    const float* p = weights;
+    for (size_t i = 0; i < shapes.size(); i++) {
+        const uint32_t K = shapes[i].K, N = shapes[i].N, Kp = pad16(K), KB = Kp / 16;
+        const float *W = p, *b = W + (size_t)K * N;
+        const float *gamma = b + N, *beta = gamma + N, *mean = beta + N, *var = mean + N;
+        p = shapes[i].bn ? var + N : b + N;
+        for (uint32_t n = 0; n < N; n++) {
+            double s = 1.0, bb = (double)b[n];
+            if (shapes[i].bn) {
+                const double v = (double)var[n] + bn_eps;
+                if (!(v > 0.0)) return ": running_var + eps must be positive";
+                s = (double)gamma[n] / std::sqrt(v);
+                bb = ((double)b[n] - (double)mean[n]) * s + (double)beta[n];
+            }
+            const float bf = (float)bb;
+            if (!std::isfinite(bf)) return ": a folded bias is not finite";
+            img[b_off[i] + n] = bf;
+            const uint32_t t = n / 16, j = n % 16;
+            for (uint32_t k = 0; k < K; k++) {
+                const float wf = (float)(s * (double)W[(size_t)n * K + k]);
+                if (!std::isfinite(wf)) return ": a folded weight is not finite";
+                const uint32_t kb = k / 16, sidx = (k % 16) / 4, q = k % 4;
+                img[w_off[i] + (((size_t)t * KB + kb) * 64 + (q * 16 + j)) * 4 + sidx] = wf;
+            }
+        }
+    }
+    return nullptr;
+}
+
 // the model of a descriptor; ssg: the single-scale descriptor it was made from, or NULL.  who: the entry point, for the messages
 int model_build(pcr_ctx* ctx, const pcr_pn2_msg_desc* desc, const pcr_pn2_desc* ssg, const float* weights, size_t n_weights, pcr_pn2_model** out, const char* who,
                 bool compact_default)
@@ -481,42 +727,10 @@ int model_build(pcr_ctx* ctx, const pcr_pn2_msg_desc* desc, const pcr_pn2_desc* 
     if (n_weights != need) return bad(": n_weights is not the model's count");
     for (size_t i = 0; i < n_weights; i++)
         if (!std::isfinite(weights[i])) return bad(": a non-finite weight");
-    // ---- fold BN (f64, rounded once) into the operand order of the kernel
-    size_t dev_floats = 0;
-    std::vector<size_t> w_off(shapes.size()), b_off(shapes.size());
-    for (size_t i = 0; i < shapes.size(); i++) {
-        const size_t Kp = pad16(shapes[i].K), Np = pad16(shapes[i].N);
-        w_off[i] = dev_floats; dev_floats += Kp * Np;
-        b_off[i] = dev_floats; dev_floats += Np;
-        dev_floats = (dev_floats + 63) & ~(size_t)63;      // every operand block starts on 256 bytes
-    }
-    std::vector<float> img(dev_floats, 0.0f);
-    const float* p = weights;
-    for (size_t i = 0; i < shapes.size(); i++) {
-        const uint32_t K = shapes[i].K, N = shapes[i].N, Kp = pad16(K), KB = Kp / 16;
-        const float *W = p, *b = W + (size_t)K * N;
-        const float *gamma = b + N, *beta = gamma + N, *mean = beta + N, *var = mean + N;
-        p = shapes[i].bn ? var + N : b + N;
-        for (uint32_t n = 0; n < N; n++) {
-            double s = 1.0, bb = (double)b[n];
-            if (shapes[i].bn) {
-                const double v = (double)var[n] + desc->bn_eps;
-                if (!(v > 0.0)) return bad(": running_var + eps must be positive");
-                s = (double)gamma[n] / std::sqrt(v);
-                bb = ((double)b[n] - (double)mean[n]) * s + (double)beta[n];
-            }
-            const float bf = (float)bb;
-            if (!std::isfinite(bf)) return bad(": a folded bias is not finite");
-            img[b_off[i] + n] = bf;
-            const uint32_t t = n / 16, j = n % 16;
-            for (uint32_t k = 0; k < K; k++) {
-                const float wf = (float)(s * (double)W[(size_t)n * K + k]);
-                if (!std::isfinite(wf)) return bad(": a folded weight is not finite");
-                const uint32_t kb = k / 16, sidx = (k % 16) / 4, q = k % 4;
-                img[w_off[i] + (((size_t)t * KB + kb) * 64 + (q * 16 + j)) * 4 + sidx] = wf;
-            }
-        }
-    }
+    std::vector<float> img;
+    std::vector<size_t> w_off, b_off;
+    if (const char* what = fold_layers(shapes, weights, desc->bn_eps, img, w_off, b_off)) return bad(what);
+    const size_t dev_floats = img.size();
     PCR_HIP(ctx, hipSetDevice(ctx->device));
     std::unique_ptr<pcr_pn2_model> m(new pcr_pn2_model());
     m->desc = *desc;
@@ -642,7 +856,7 @@ void model_info(const pcr_pn2_model* model, size_t npts_hint, pcr_pn2_info* info
 
 extern "C" int pcr_pn2_model_info(const pcr_pn2_model* model, size_t npts_hint, pcr_pn2_info* info, pcr_pn2_desc* desc)
 {
-    if (!model) return PCR_ERR_ARG;
+    if (!model || model->pn1) return PCR_ERR_ARG;
     if (desc) {
         if (!model->has_ssg) return PCR_ERR_ARG;      // several branches or features-first channels: only pcr_pn2_msg_desc holds them
         *desc = model->ssg;
@@ -657,6 +871,7 @@ extern "C" int pcr_pn2_msg_model_info(const pcr_pn2_model* model, size_t npts_hi
         if (!desc || !info) return PCR_ERR_ARG;
         return desc_info(*desc, npts_hint, info) ? PCR_OK : PCR_ERR_ARG;
     }
+    if (model->pn1) return PCR_ERR_ARG;      // pcr_pn1_model_info holds its descriptor
     if (desc) *desc = model->desc;
     if (info) model_info(model, npts_hint, info);
     return PCR_OK;
@@ -672,6 +887,7 @@ int sa_layer(pcr_ctx* ctx, const pcr_pn2_model* model, int layer, const pcr_clou
     const std::string who = msg ? "pcr_sa_msg_mlp_max_f32" : "pcr_sa_mlp_max_f32";
     auto bad = [&](const char* what) { return fail(ctx, PCR_ERR_ARG, (who + what).c_str()); };
     if (!ctx || !model || !cloud || !seg_ptr) return bad("");
+    if (model->pn1) return bad(": a model of pcr_pn1_model_create has no SA layers");
     if (layer < 0 || (uint32_t)layer >= model->desc.n_sa) return bad(": no such SA layer");
     if (model->device != ctx->device) return bad(": the model lives on another device");
     const pcr_pn2_msg_sa_desc& sd = model->desc.sa[layer];
@@ -792,6 +1008,7 @@ extern "C" int pcr_pn2_forward_f32(pcr_ctx* ctx, const pcr_pn2_model* model, con
                                    float* logp, int32_t* pred, float* global_feat, uint32_t* fps_idx)
 {
     if (!ctx || !model) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_forward_f32");
+    if (model->pn1) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_forward_f32: a model of pcr_pn1_model_create (pcr_pointnet_forward_f32 runs it)");
     if (model->device != ctx->device) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_forward_f32: the model lives on another device");
     const pcr_pn2_msg_desc& d = model->desc;
     if (!d.sa[d.n_sa - 1].group_all) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_forward_f32: the last SA layer must be group_all");
@@ -960,6 +1177,335 @@ extern "C" int pcr_pn2_forward_f32(pcr_ctx* ctx, const pcr_pn2_model* model, con
     const hipError_t e2 = hipStreamSynchronize(ctx->stream);      // the one wait: `keep` and the staging block are read until here
     if (rc) return rc;
     if (e != hipSuccess || e2 != hipSuccess) return fail(ctx, PCR_ERR_HIP, "pcr_pn2_forward_f32", e != hipSuccess ? e : e2);
+    prof_flush(ctx);
+    return PCR_OK;
+}
+
+// ---- the vanilla PointNet: model, stage entry point, forward pass ---------------------------------------------------------------------------------
+namespace {
+
+constexpr uint32_t PN1_TNET_LAYERS = 6;      // three convolutions, two FC layers with BN, the last linear layer
+
+// the layers of a descriptor in weight order; false for a descriptor outside the limits
+bool pn1_shapes(const pcr_pn1_desc& d, std::vector<LayerShape>& shapes)
+{
+    if (d.D0 > PN2_MAX_WIDTH - 3 || d.stn3 > 1 || d.fstn > 1 || d.n_mlp < 2 || d.n_mlp > PCR_PN2_MAX_MLP || d.n_fc < 1 || d.n_fc > PCR_PN2_MAX_FC) return false;
+    if (!std::isfinite(d.bn_eps)) return false;
+    for (uint32_t i = 0; i < d.n_mlp; i++)
+        if (d.widths[i] < 1 || d.widths[i] > PN2_MAX_WIDTH) return false;
+    for (uint32_t i = 0; i < d.n_fc; i++)
+        if (d.fc_widths[i] < 1 || d.fc_widths[i] > PN2_MAX_WIDTH) return false;
+    if (d.stn3 || d.fstn) {
+        for (uint32_t w : d.tnet_conv) if (w < 1 || w > PN2_MAX_WIDTH) return false;
+        for (uint32_t w : d.tnet_fc) if (w < 1 || w > PN2_MAX_WIDTH) return false;
+    }
+    if (d.fstn && d.widths[0] > PN1_MAX_TRANSFORM) return false;
+    auto tnet = [&](uint32_t cin, uint32_t k) {
+        uint32_t K = cin;
+        for (uint32_t w : d.tnet_conv) { shapes.push_back({ K, w, true }); K = w; }
+        for (uint32_t w : d.tnet_fc) { shapes.push_back({ K, w, true }); K = w; }
+        shapes.push_back({ K, k * k, false });
+    };
+    const uint32_t C0 = 3 + d.D0;
+    if (d.stn3) tnet(C0, 3);
+    uint32_t K = C0;
+    for (uint32_t i = 0; i < d.n_mlp; i++) { shapes.push_back({ K, d.widths[i], true }); K = d.widths[i]; }
+    if (d.fstn) tnet(d.widths[0], d.widths[0]);
+    for (uint32_t i = 0; i < d.n_fc; i++) { shapes.push_back({ K, d.fc_widths[i], i + 1 < d.n_fc }); K = d.fc_widths[i]; }
+    return true;
+}
+
+bool pn1_desc_info(const pcr_pn1_desc& d, size_t npts_hint, pcr_pn2_info* info)
+{
+    std::vector<LayerShape> shapes;
+    if (!pn1_shapes(d, shapes)) return false;
+    memset(info, 0, sizeof(*info));
+    for (const LayerShape& s : shapes) info->n_weights += (uint64_t)s.K * s.N + s.N + (s.bn ? 4ull * s.N : 0ull);
+    info->n_class = d.fc_widths[d.n_fc - 1];
+    info->c_last = d.widths[d.n_mlp - 1];
+    uint64_t per_point = 0, per_object = 0;
+    size_t i = 0;
+    auto tnet = [&](uint32_t k) {
+        for (uint32_t c = 0; c < 3; c++, i++) per_point += (uint64_t)shapes[i].K * shapes[i].N;
+        for (uint32_t c = 0; c < 3; c++, i++) per_object += (uint64_t)shapes[i].K * shapes[i].N;
+        per_point += (uint64_t)k * k;                     // the transform
+    };
+    if (d.stn3) tnet(3);
+    for (uint32_t c = 0; c < d.n_mlp; c++, i++) per_point += (uint64_t)shapes[i].K * shapes[i].N;
+    if (d.fstn) tnet(d.widths[0]);
+    for (; i < shapes.size(); i++) per_object += (uint64_t)shapes[i].K * shapes[i].N;
+    info->macs_per_object = per_point * npts_hint + per_object;
+    return true;
+}
+
+void stage_strides(Pn1Stage& st)
+{
+    st.s0 = st.s1 = 4;
+    for (uint32_t l = 0; l < st.n; l++) {
+        uint32_t& s = (l & 1u) ? st.s1 : st.s0;
+        s = std::max(s, st.L[l].Kpad + 4);
+    }
+}
+
+bool pn1_model_of(pcr_ctx* ctx, const pcr_pn2_model* model, const char* who)
+{
+    if (model->pn1) return true;
+    fail(ctx, PCR_ERR_ARG, (std::string(who) + ": not a model of pcr_pn1_model_create").c_str());
+    return false;
+}
+
+}  // namespace
+
+extern "C" int pcr_pn1_model_create(pcr_ctx* ctx, const pcr_pn1_desc* desc, const float* weights, size_t n_weights, pcr_pn2_model** out)
+{
+    if (out) *out = nullptr;
+    if (!ctx || !desc || !weights || !out) return fail(ctx, PCR_ERR_ARG, "pcr_pn1_model_create");
+    auto bad = [&](const char* what) { return fail(ctx, PCR_ERR_ARG, (std::string("pcr_pn1_model_create") + what).c_str()); };
+    std::vector<LayerShape> shapes;
+    if (!pn1_shapes(*desc, shapes)) return bad(": a descriptor outside the limits (see include/pcr.h)");
+    uint64_t need = 0;
+    for (const LayerShape& s : shapes) need += (uint64_t)s.K * s.N + s.N + (s.bn ? 4ull * s.N : 0ull);
+    if (n_weights != need) return bad(": n_weights is not the model's count");
+    for (size_t i = 0; i < n_weights; i++)
+        if (!std::isfinite(weights[i])) return bad(": a non-finite weight");
+    std::vector<float> img;
+    std::vector<size_t> w_off, b_off;
+    if (const char* what = fold_layers(shapes, weights, desc->bn_eps, img, w_off, b_off)) return bad(what);
+    PCR_HIP(ctx, hipSetDevice(ctx->device));
+    std::unique_ptr<pcr_pn2_model> m(new pcr_pn2_model());
+    memset(&m->desc, 0, sizeof(m->desc));
+    memset(&m->ssg, 0, sizeof(m->ssg));
+    m->pn1 = true;
+    m->d1 = *desc;
+    m->device = ctx->device;
+    m->n_weights = need;
+    PCR_HIP(ctx, hipMalloc((void**)&m->dev, img.size() * 4));
+    hipError_t e = hipMemcpy(m->dev, img.data(), img.size() * 4, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(m->dev); return fail(ctx, PCR_ERR_HIP, "pointnet: the upload of a model", e); }
+    // ---- the stages and the heads over the layers
+    auto layer = [&](size_t i) {
+        LayerDev L;
+        L.w = m->dev + w_off[i]; L.b = m->dev + b_off[i];
+        L.K = shapes[i].K; L.Kpad = pad16(shapes[i].K); L.N = shapes[i].N; L.Npad = pad16(shapes[i].N);
+        return L;
+    };
+    const size_t stn0 = 0, enc0 = desc->stn3 ? PN1_TNET_LAYERS : 0, fstn0 = enc0 + desc->n_mlp, head0 = fstn0 + (desc->fstn ? PN1_TNET_LAYERS : 0);
+    auto tnet_head = [&](Chain& ch, size_t first) {
+        ch.n = 3;
+        for (uint32_t k = 0; k < 3; k++) ch.L[k] = layer(first + 3 + k);
+        chain_strides(ch);
+    };
+    if (desc->stn3) {
+        Pn1Stage& st = m->stage[0];
+        for (uint32_t k = 0; k < 3; k++) st.L[st.n++] = layer(stn0 + k);
+        tnet_head(m->tnet_head[0], stn0);
+    }
+    if (desc->fstn) {
+        Pn1Stage& st = m->stage[1];
+        st.L[st.n++] = layer(enc0);
+        for (uint32_t k = 0; k < 3; k++) st.L[st.n++] = layer(fstn0 + k);
+        tnet_head(m->tnet_head[1], fstn0);
+    }
+    {
+        Pn1Stage& st = m->stage[2];
+        st.L[st.n++] = layer(enc0);
+        if (desc->fstn) {
+            LayerDev T;
+            T.w = T.b = nullptr;
+            T.K = T.N = desc->widths[0]; T.Kpad = T.Npad = pad16(desc->widths[0]);
+            st.t_step = st.n;
+            st.L[st.n++] = T;
+        }
+        for (uint32_t k = 1; k < desc->n_mlp; k++) st.L[st.n++] = layer(enc0 + k);
+        st.relu_last = 0;
+    }
+    for (Pn1Stage& st : m->stage) {
+        stage_strides(st);
+        if (st.n && st.lds_bytes(16) > PN2_LDS_LIMIT) { (void)hipFree(m->dev); return bad(": a stage does not fit in LDS at 16 rows (see include/pcr.h)"); }
+    }
+    m->head.n = desc->n_fc;
+    for (uint32_t k = 0; k < m->head.n; k++) m->head.L[k] = layer(head0 + k);
+    chain_strides(m->head);
+    if (m->head.lds_bytes(16) > PN2_LDS_LIMIT || (desc->stn3 && m->tnet_head[0].lds_bytes(16) > PN2_LDS_LIMIT) || (desc->fstn && m->tnet_head[1].lds_bytes(16) > PN2_LDS_LIMIT)) {
+        (void)hipFree(m->dev);
+        return bad(": a head does not fit in LDS at 16 rows (see include/pcr.h)");
+    }
+    *out = m.release();
+    return PCR_OK;
+}
+
+extern "C" int pcr_pn1_model_info(const pcr_pn2_model* model, size_t npts_hint, pcr_pn2_info* info, pcr_pn1_desc* desc)
+{
+    if (!model) {                            // no model: *desc is READ, info is what a model made from it would report (no device needed)
+        if (!desc || !info) return PCR_ERR_ARG;
+        return pn1_desc_info(*desc, npts_hint, info) ? PCR_OK : PCR_ERR_ARG;
+    }
+    if (!model->pn1) return PCR_ERR_ARG;
+    if (desc) *desc = model->d1;
+    if (info) (void)pn1_desc_info(model->d1, npts_hint, info);
+    return PCR_OK;
+}
+
+extern "C" int pcr_pointwise_chain_max_f32(pcr_ctx* ctx, const pcr_pn2_model* model, int stage, const pcr_cloud* cloud, const uint32_t* seg_ptr, size_t n_seg,
+                                           const float* features, const float* trans3, const float* trans_feat, float* out)
+{
+    auto bad = [&](const char* what) { return fail(ctx, PCR_ERR_ARG, (std::string("pcr_pointwise_chain_max_f32") + what).c_str()); };
+    if (!ctx || !model || !cloud || !seg_ptr) return bad("");
+    if (!pn1_model_of(ctx, model, "pcr_pointwise_chain_max_f32")) return PCR_ERR_ARG;
+    if (stage < 0 || stage > 2 || model->stage[stage].n == 0) return bad(": the model has no such stage");
+    if (model->device != ctx->device) return bad(": the model lives on another device");
+    const Pn1Stage& st = model->stage[stage];
+    const size_t D = model->d1.D0, width = st.n_out(), K = model->d1.widths[0];
+    const bool has_t = st.t_step < st.n;
+    if (D > 0 && !features) return bad(": the model takes features");
+    if (stage == 0 && trans3) return bad(": stage 0 takes no transform");
+    if (has_t ? !trans_feat : trans_feat != nullptr) return bad(": trans_feat goes with stage 2 of a model with a feature T-Net, and only with it");
+    if (n_seg > PN2_MAX_ROWS || cloud->n > PN2_MAX_ROWS) return bad(": too large");
+    if (!seg_ok(seg_ptr, n_seg, cloud->n)) return bad(": seg_ptr must ascend and end inside its cloud");
+    if (n_seg == 0) return PCR_OK;
+    if (!out) return bad(": out is NULL");
+    if (n_seg > PN2_MAX_ROWS / width || (has_t && n_seg > PN2_MAX_ROWS / (K * K))) return bad(": too large");
+    const size_t p0 = seg_ptr[0], np = seg_ptr[n_seg] - p0;
+    size_t max_pts = 0;
+    for (size_t s = 0; s < n_seg; s++) max_pts = std::max<size_t>(max_pts, seg_ptr[s + 1] - seg_ptr[s]);
+    PCR_HIP(ctx, hipSetDevice(ctx->device));
+    uint32_t *seg_dev, *out_dev;
+    float *feat_dev, *t3_dev, *tk_dev;
+    Layout L;
+    L.add(&seg_dev, n_seg + 1);
+    L.add(&feat_dev, np * D);
+    L.add(&t3_dev, trans3 ? n_seg * 9 : 0);
+    L.add(&tk_dev, has_t ? n_seg * K * K : 0);
+    L.add(&out_dev, n_seg * width);
+    int rc = bind_scratch(ctx, L);
+    if (rc) return rc;
+    PCR_HIP(ctx, hipMemcpyAsync(seg_dev, seg_ptr, (n_seg + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (D && np) PCR_HIP(ctx, hipMemcpyAsync(feat_dev, features + p0 * D, np * D * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (trans3) PCR_HIP(ctx, hipMemcpyAsync(t3_dev, trans3, n_seg * 9 * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (has_t) PCR_HIP(ctx, hipMemcpyAsync(tk_dev, trans_feat, n_seg * K * K * 4, hipMemcpyHostToDevice, ctx->stream));
+    PCR_HIP(ctx, hipStreamSynchronize(ctx->stream));           // the caller's arrays are pageable: read before the call returns control to the launches
+    Pn1Args a;
+    memset(&a, 0, sizeof(a));
+    a.x = cloud->x(); a.y = cloud->y(); a.z = cloud->z();
+    a.feat = feat_dev - p0 * D;              // addressed by cloud position: moved back by the rows that were not uploaded (never dereferenced there)
+    a.seg_ptr = seg_dev;
+    a.trans3 = trans3 ? t3_dev : nullptr;
+    a.transK = has_t ? tk_dev : nullptr;
+    a.out = out_dev;
+    a.D = (uint32_t)D;
+    rc = pn1_launch(ctx, st, a, n_seg, max_pts);
+    if (rc) return rc;
+    PCR_HIP(ctx, hipMemcpyAsync(out, out_dev, n_seg * width * 4, hipMemcpyDeviceToHost, ctx->stream));
+    PCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    prof_flush(ctx);
+    return PCR_OK;
+}
+
+extern "C" int pcr_pointnet_forward_f32(pcr_ctx* ctx, const pcr_pn2_model* model, const float* objects, size_t n_obj, size_t npts, float* logp, int32_t* pred,
+                                        float* global_feat, float* trans, float* trans_feat)
+{
+    if (!ctx || !model) return fail(ctx, PCR_ERR_ARG, "pcr_pointnet_forward_f32");
+    if (!pn1_model_of(ctx, model, "pcr_pointnet_forward_f32")) return PCR_ERR_ARG;
+    if (model->device != ctx->device) return fail(ctx, PCR_ERR_ARG, "pcr_pointnet_forward_f32: the model lives on another device");
+    if (npts < 1) return fail(ctx, PCR_ERR_ARG, "pcr_pointnet_forward_f32: npts must be >= 1");
+    const pcr_pn1_desc& d = model->d1;
+    if ((trans && !d.stn3) || (trans_feat && !d.fstn)) return fail(ctx, PCR_ERR_ARG, "pcr_pointnet_forward_f32: the model has no such T-Net");
+    if (n_obj == 0) return PCR_OK;
+    if (!objects || !logp) return fail(ctx, PCR_ERR_ARG, "pcr_pointnet_forward_f32: objects / logp is NULL");
+    const uint32_t D0 = d.D0, C0 = 3 + D0, K = d.widths[0], KK = K * K;
+    const uint32_t n_class = model->head.n_out(), c_last = model->stage[2].n_out(), c_tnet = (d.stn3 || d.fstn) ? d.tnet_conv[2] : 0;
+    if (n_obj > PN2_MAX_ROWS || npts > PN2_MAX_ROWS || (unsigned long long)n_obj * npts > PN2_MAX_ROWS / C0) return fail(ctx, PCR_ERR_ARG, "pcr_pointnet_forward_f32: too large");
+    if ((unsigned long long)n_obj * std::max(std::max(c_last, n_class), std::max(c_tnet, d.fstn ? KK : 0u)) > PN2_MAX_ROWS)
+        return fail(ctx, PCR_ERR_ARG, "pcr_pointnet_forward_f32: too large");
+    PCR_HIP(ctx, hipSetDevice(ctx->device));
+    // ---- one block: [uploaded: x y z | features | segments] [the T-Nets' pooled rows, trans, trans_feat] [global feature] [head]
+    const size_t P = n_obj * npts;
+    float *x0, *feat0, *t3, *tk, *logits, *logp_dev;
+    uint32_t *seg, *pooled, *gf;             // pooled / gf: keys while their chain runs, floats once it is decoded
+    int32_t* pred_dev;
+    Layout L;
+    L.add(&x0, 3 * P);
+    L.add(&feat0, P * D0);
+    L.add(&seg, n_obj + 1);
+    const size_t upload_bytes = L.bytes();
+    L.add(&pooled, n_obj * c_tnet);          // both T-Nets pool into it, one after the other
+    L.add(&t3, d.stn3 ? n_obj * 9 : 0);
+    L.add(&tk, d.fstn ? n_obj * KK : 0);
+    L.add(&gf, n_obj * c_last);
+    L.add(&logits, n_obj * n_class);
+    L.add(&logp_dev, n_obj * n_class);
+    L.add(&pred_dev, n_obj);
+    int rc = bind_scratch(ctx, L);
+    if (rc) return rc;
+    rc = ensure_stage(ctx, upload_bytes);
+    if (rc) return rc;
+    L.bind(ctx->host_stage);                 // the uploaded part, laid out the same way in the pinned staging block
+    {
+        float *hx = x0, *hy = x0 + P, *hz = x0 + 2 * P;
+        for (size_t i = 0; i < P; i++) {
+            const float* r = objects + i * C0;
+            for (uint32_t c = 0; c < C0; c++)
+                if (!(fabsf(r[c]) <= FLT_MAX)) return fail(ctx, PCR_ERR_ARG, "pcr_pointnet_forward_f32: a non-finite coordinate or feature");
+            hx[i] = r[0]; hy[i] = r[1]; hz[i] = r[2];
+            for (uint32_t c = 0; c < D0; c++) feat0[i * D0 + c] = r[3 + c];
+        }
+        for (size_t o = 0; o <= n_obj; o++) seg[o] = (uint32_t)(o * npts);
+    }
+    L.bind(ctx->scratch);
+    PCR_HIP(ctx, hipMemcpyAsync(ctx->scratch, ctx->host_stage, upload_bytes, hipMemcpyHostToDevice, ctx->stream));
+    Pn1Args pa;
+    memset(&pa, 0, sizeof(pa));
+    pa.x = x0; pa.y = x0 + P; pa.z = x0 + 2 * P; pa.feat = feat0; pa.seg_ptr = seg; pa.D = D0;
+    auto head = [&](const Chain& ch, const float* in, uint32_t width, float* to) {      // one row per object through the FC layers
+        ChainArgs a;
+        memset(&a, 0, sizeof(a));
+        a.feat = in; a.out = to;
+        a.rows = (uint32_t)n_obj;
+        a.D = width; a.nsample = 1; a.mode = PN2_HEAD;
+        return chain_launch(ctx, ch, a, n_obj, "pn2_head");
+    };
+    auto tnet = [&](const Chain& ch, float* to, uint32_t k) {                          // pooled rows -> the FC layers -> + identity
+        int r = head(ch, (const float*)pooled, c_tnet, to);
+        if (r) return r;
+        ProfScope ps(ctx, "pn1_identity");
+        hipLaunchKernelGGL(pn1_identity_kernel, dim3((unsigned)((n_obj * k + PN2_BLOCK - 1) / PN2_BLOCK)), dim3(PN2_BLOCK), 0, ctx->stream, to, (uint32_t)n_obj, k);
+        PCR_HIP(ctx, hipGetLastError());
+        return (int)PCR_OK;
+    };
+    if (d.stn3) {                            // the input T-Net on the raw points
+        pa.out = pooled;
+        rc = pn1_launch(ctx, model->stage[0], pa, n_obj, npts);
+        if (rc == PCR_OK) rc = tnet(model->tnet_head[0], t3, 3);
+        pa.trans3 = t3;
+    }
+    if (rc == PCR_OK && d.fstn) {            // the feature T-Net on convolution 0 of the transformed points
+        pa.out = pooled;
+        rc = pn1_launch(ctx, model->stage[1], pa, n_obj, npts);
+        if (rc == PCR_OK) rc = tnet(model->tnet_head[1], tk, K);
+        pa.transK = tk;
+    }
+    if (rc == PCR_OK) {
+        pa.out = gf;
+        rc = pn1_launch(ctx, model->stage[2], pa, n_obj, npts);
+    }
+    if (rc == PCR_OK) rc = head(model->head, (const float*)gf, c_last, logits);
+    hipError_t e = hipSuccess;
+    if (rc == PCR_OK) {
+        {
+            ProfScope ps(ctx, "pn2_logsoftmax");
+            hipLaunchKernelGGL(pn2_logsoftmax_kernel, dim3((unsigned)((n_obj + PN2_BLOCK - 1) / PN2_BLOCK)), dim3(PN2_BLOCK), 0, ctx->stream, logits, (uint32_t)n_obj, n_class,
+                               logp_dev, pred_dev);
+        }
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(logp, logp_dev, n_obj * n_class * 4, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess && pred) e = hipMemcpyAsync(pred, pred_dev, n_obj * 4, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess && global_feat) e = hipMemcpyAsync(global_feat, gf, n_obj * c_last * 4, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess && trans) e = hipMemcpyAsync(trans, t3, n_obj * 9 * 4, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess && trans_feat) e = hipMemcpyAsync(trans_feat, tk, (size_t)n_obj * KK * 4, hipMemcpyDeviceToHost, ctx->stream);
+    }
+    const hipError_t e2 = hipStreamSynchronize(ctx->stream);      // the one wait: the staging block is read until here
+    if (rc) return rc;
+    if (e != hipSuccess || e2 != hipSuccess) return fail(ctx, PCR_ERR_HIP, "pcr_pointnet_forward_f32", e != hipSuccess ? e : e2);
     prof_flush(ctx);
     return PCR_OK;
 }

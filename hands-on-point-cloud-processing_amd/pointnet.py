@@ -7,7 +7,9 @@ Mirrors (same names, argument order and return shapes):
   sample_and_group        HomeworkFinal/models/pointnet_util.py:119-156   (GPU: the three operators, one fused gather)
   get_model               HomeworkFinal/models/pointnet2_cls_ssg.py           (GPU: pcr_pn2_forward_f32, eval mode only)
   get_model_msg           HomeworkFinal/models/pointnet2_cls_msg.py           (GPU: the same call on a multi-scale model, eval mode only)
-  MODELS                  the two by the module name train_cls.py --model / test_cls.py import
+  get_model_cls           HomeworkFinal/models/pointnet_cls.py + pointnet.py  (GPU: pcr_pointnet_forward_f32, the vanilla PointNet with its T-Nets, eval mode only)
+  MODELS                  the two PointNet++ models by the module name train_cls.py --model / test_cls.py import
+  CLASSIFIERS             all three by that name (MODELS and pointnet_cls)
   classify_foreground_objects   the flow of HomeworkFinal/foreground_obj_cls.py:97-188: up to the classifier's input, or with
                           classifier= through it to pred_final
 
@@ -311,8 +313,82 @@ class get_model_msg(get_model):
         return ctx.pn2_msg_model(self.desc(), self.flat_weights())
 
 
-# the classifiers by the reference's module name (train_cls.py --model, test_cls.py)
+# the reference's layers (pointnet.py:10-24, :50-65, :89-101; pointnet_cls.py:15-22)
+_CLS_ENC = (64, 128, 1024)
+_CLS_TNET_CONV, _CLS_TNET_FC = (64, 128, 1024), (512, 256)
+
+
+class get_model_cls(get_model):
+    """models/pointnet_cls.get_model in eval mode on the library: the same constructor arguments and defaults (k=40, normal_channel=True),
+    state-dict keys (feat.stn.conv1.weight ... feat.stn.fc3.bias, feat.conv1 ... feat.bn3, feat.fstn.*, fc1 / bn1 / fc2 / bn2 / fc3; Conv1d
+    weights [out, in, 1] or [out, in]) and call.  __call__(x [B, 3 or 6, N], ctx=, return_all=) -> (log_probs [B, k], trans_feat [B, 64, 64]),
+    numpy or torch like the input; with return_all a third value, the dict of Context.pointnet_forward.  The model samples nothing, so nothing is
+    drawn: start= and seed= are accepted, as on the sibling classes, and ignored.  Everything else is get_model's: load_state_dict, eval,
+    train() raising, state_shapes, flat_weights."""
+
+    def __init__(self, k=40, normal_channel=True):
+        super().__init__(k, normal_channel)
+        self.k = self.num_class
+
+    @staticmethod
+    def _tnet(prefix, cin, k):
+        out = []
+        for i, w in enumerate(_CLS_TNET_CONV):
+            out.append((f"{prefix}.conv{i + 1}", f"{prefix}.bn{i + 1}", w, cin))
+            cin = w
+        for i, w in enumerate(_CLS_TNET_FC):
+            out.append((f"{prefix}.fc{i + 1}", f"{prefix}.bn{len(_CLS_TNET_CONV) + i + 1}", w, cin))
+            cin = w
+        return out + [(f"{prefix}.fc{len(_CLS_TNET_FC) + 1}", None, k * k, cin)]
+
+    def _layers(self):
+        channel = 6 if self.normal_channel else 3
+        out, cin = self._tnet("feat.stn", channel, 3), channel
+        for i, w in enumerate(_CLS_ENC):
+            out.append((f"feat.conv{i + 1}", f"feat.bn{i + 1}", w, cin))
+            cin = w
+        out += self._tnet("feat.fstn", _CLS_ENC[0], _CLS_ENC[0])
+        for fc, bn, w in _SSG_FC:
+            w = self.num_class if w is None else w
+            out.append((fc, bn, w, cin))
+            cin = w
+        return out
+
+    def desc(self):
+        from . import pn1_desc
+        return pn1_desc(_CLS_ENC, [512, 256, self.num_class], D0=3 if self.normal_channel else 0, tnet_conv=_CLS_TNET_CONV, tnet_fc=_CLS_TNET_FC, bn_eps=1e-5)
+
+    def state_shapes(self):
+        """key -> shape of every entry load_state_dict takes, as the reference's state_dict() has them (Conv1d weights [out, in, 1])"""
+        out = {}
+        for conv, bn, w, cin in self._layers():
+            out[f"{conv}.weight"] = (w, cin, 1) if ".conv" in conv else (w, cin)
+            out[f"{conv}.bias"] = (w,)
+            for k in (_BN_KEYS if bn else ()):
+                out[f"{bn}.{k}"] = (w,)
+        return out
+
+    def _upload(self, ctx):
+        return ctx.pn1_model(self.desc(), self.flat_weights())
+
+    def forward(self, x, *, start=None, seed=None, ctx=None, return_all=False):
+        if self.training:
+            raise RuntimeError("the model is in training mode: call eval() (BatchNorm batch statistics and dropout are out of scope)")
+        a, proto = _to_host(x)
+        C0 = 6 if self.normal_channel else 3
+        if a.ndim != 3 or a.shape[1] != C0:
+            raise ValueError(f"x: [B, {C0}, N]")
+        ctx = _ctx(ctx)
+        res = ctx.pointnet_forward(self.model(ctx), np.ascontiguousarray(np.transpose(a, (0, 2, 1)), np.float32), return_all=True)
+        out = _like(res["logp"], proto), _like(res["trans_feat"], proto)
+        return out + (res,) if return_all else out
+
+    __call__ = forward
+
+
+# the PointNet++ classifiers by the reference's module name (train_cls.py --model, test_cls.py), and every classifier by that name
 MODELS = {"pointnet2_cls_ssg": get_model, "pointnet2_cls_msg": get_model_msg}
+CLASSIFIERS = dict(MODELS, pointnet_cls=get_model_cls)
 
 
 def classify_foreground_objects(points, npoints=256, eps=0.5, min_points=8, z_min_above_ground=0.5, z_extent=(1.0, 2.3), seed=0, *, ctx=None,
@@ -322,7 +398,7 @@ def classify_foreground_objects(points, npoints=256, eps=0.5, min_points=8, z_mi
     Without a classifier (the reference ships no weights) returns (objects f32 [n_obj, npoints, 3], codes i32 [n_clusters]: 3 where the
     reference writes 3, -1 = to be classified) and a dict with everything in between (points, ground / foreground indices, ground_z,
     labels, n_clusters, and the outputs of Context.objects_from_labels).
-    With classifier= (a get_model or get_model_msg in eval mode) every object goes through it in ONE batched forward pass (the first FPS picks drawn from
+    With classifier= (a get_model, get_model_msg or get_model_cls in eval mode) every object goes through it in ONE batched forward pass (the first FPS picks, where the model samples, drawn from
     `seed`) and the second value is pred_final as the reference builds it (:152-188): i32 [n_clusters], 3 where it writes 3, the predicted
     class elsewhere; the dict then also holds log_probs [n_obj, num_class]."""
     from . import hw4

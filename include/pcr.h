@@ -761,6 +761,77 @@ int pcr_ball_query_multi_f32(pcr_ctx* ctx, const pcr_cloud* cloud, const uint32_
 int pcr_sa_msg_mlp_max_f32(pcr_ctx* ctx, const pcr_pn2_model* model, int layer, const pcr_cloud* cloud, const uint32_t* seg_ptr, const pcr_cloud* centres,
                            const uint32_t* centre_seg_ptr, size_t n_seg, const float* features, const uint32_t* idx, float* out);
 
+/* ---- HomeworkFinal: the vanilla PointNet classifier, models/pointnet_cls.py + models/pointnet.py (STN3d, STNkd, PointNetEncoder), eval mode -----
+ * No sampling and no grouping: every point goes through shared convolutions, the object's feature is the max over its points, and two small
+ * networks (T-Nets) predict PER OBJECT a 3 x 3 matrix for xyz and a K x K matrix for the features after the first convolution.  pcr_pn1_desc:
+ *   D0         feature channels besides xyz (0, or 3: normal_channel); the input of a point is (xyz | features), C0 = 3 + D0 channels
+ *   stn3       1: a T-Net on the C0 input channels predicts trans (3 x 3); xyz <- xyz . trans, the features pass unchanged (pointnet.py:105-111)
+ *   fstn       1: a T-Net on the first convolution's output predicts trans_feat (K x K, K = widths[0]); x <- x . trans_feat (:114-118)
+ *   widths     n_mlp in 2 ... 4 encoder convolutions (the reference: 64, 128, 1024); BN + ReLU on every one but the LAST, which has BN only
+ *              (:125): the max over the points of an object is a SIGNED max
+ *   tnet_conv  the 3 convolution widths of BOTH T-Nets (64, 128, 1024; BN + ReLU, then the max over points), tnet_fc their 2 FC widths
+ *              (512, 256; BN + ReLU); a last linear layer without BN gives the k x k entries, row-major (k = 3 / K)
+ *   fc_widths  n_fc in 1 ... 4 head widths as in pcr_pn2_desc (512, 256, classes); bn_eps as there
+ * weights: ONE flat f32 array in the reference's module order — [stn3: the T-Net on the input: conv1 conv2 conv3 fc1 fc2 fc3] [the encoder's
+ *   convolutions in order] [fstn: the T-Net on the features, the same six layers] [the head's FC layers]; every layer laid out as for
+ *   pcr_pn2_model_create: W [out][in], bias [out], and gamma, beta, running_mean, running_var where it has BN (all but a T-Net's fc3 and the
+ *   head's last layer).  A T-Net that the flags leave out has no weights.
+ * pcr_pn1_model_create returns the handle type of pcr_pn2_model_create; pcr_pn2_model_destroy frees it.  BN is folded in f64 and rounded ONCE,
+ *   as there.  The "+ identity" that follows a T-Net's fc3 (:41-46, :79-84) is NOT folded into that layer's bias: a chain that starts at
+ *   1 + b rounds every one of its steps in the binade of 1 (measured on the reference model: 8 to 14 times the reference's own f32 deviation
+ *   on trans).  It is ONE f32 addition to the finished chain of every diagonal entry, as the reference adds it.
+ * Arithmetic: the library's — every output is one f32 fma chain over ascending input channel that starts from the folded bias, on
+ *   v_mfma_f32_16x16x4_f32.  A TRANSFORM is the same chain starting from +0 with the object's own matrix as weights:
+ *   y[j] = c_K, c_0 = +0, c_(k+1) = fmaf(x[k], T[k][j], c_k), k ascending (the 3 x 3 one in plain fmaf, the K x K one on the matrix pipe with T
+ *   staged in LDS).  The max over an object's points is taken on the integer key of pcr_label_aabb_f32, which orders ALL floats:
+ *   -inf < ... < -0 < +0 < ... < +inf (so -0 is BELOW +0); the output row starts at the key of -inf, not at +0.  A workgroup tile holds rows of
+ *   ONE object (tiles per object = ceil(npts / R), R = the tune key pn2_rows), so a B operand never mixes two objects' matrices, and a row's
+ *   bits do not depend on R, on the batch, on the object's place in it or on the workgroup that served it.
+ * Limits (PCR_ERR_ARG otherwise): D0 0 ... 1021; stn3, fstn 0 / 1; n_mlp 2 ... 4; n_fc 1 ... 4; every width 1 ... 1024; with fstn widths[0] <= 128
+ *   (the matrix is staged in LDS); bn_eps finite; n_weights the model's count; every weight finite; var + eps > 0.
+ *
+ * pcr_pn1_model_info — info (n_sampling = 0; macs_per_object: every layer and transform ONCE per point of npts_hint points plus the three
+ *   heads, unpadded — the recomputation below is not counted) and the descriptor.  With model == NULL it READS *desc (no device needed).
+ * On a model of pcr_pn1_model_create, pcr_pn2_forward_f32, pcr_pn2_model_info, pcr_pn2_msg_model_info, pcr_sa_mlp_max_f32 and
+ *   pcr_sa_msg_mlp_max_f32 return PCR_ERR_ARG; on any other model pcr_pn1_model_info with a model, pcr_pointwise_chain_max_f32 and
+ *   pcr_pointnet_forward_f32 do.
+ *
+ * pcr_pointwise_chain_max_f32 — ONE fused launch for one stage of the model on the caller's inputs (cloud, seg_ptr, n_seg as
+ *   pcr_sa_mlp_max_f32 takes them: a segment is an object; features: host, D0 floats per point of the cloud, NULL with D0 == 0):
+ *     stage 0   (stn3)  the input T-Net's convolutions -> max                                   out: n_seg x tnet_conv[2]
+ *     stage 1   (fstn)  xyz . trans3 -> conv 0 -> the feature T-Net's convolutions -> max       out: n_seg x tnet_conv[2]
+ *     stage 2           xyz . trans3 -> conv 0 -> . trans_feat -> conv 1 ... (last: no ReLU) -> signed max      out: n_seg x widths[n_mlp - 1]
+ *   trans3: host, n_seg x 9 row-major (NULL: no transform; it must be NULL for stage 0), trans_feat: host, n_seg x K x K: stage 2 of a model
+ *   with fstn needs it, every other call takes NULL.  Convolution 0 is recomputed in stages 1 and 2, not stored: the activations of a tile
+ *   stay in LDS and nothing of size rows x C goes to memory.  An EMPTY segment gives a row of -inf.  PCR_ERR_ARG as pcr_sa_mlp_max_f32, and for a stage the model does not have.
+ *   Profile name pn1_chain.
+ *
+ * pcr_pointnet_forward_f32 — the forward pass for n_obj objects of npts points: objects host, n_obj x npts x (3 + D0), uploaded once ->
+ *   stage 0 -> the T-Net's FC layers (trans) -> stage 1 -> the T-Net's FC layers (trans_feat) -> stage 2 (global_feat) -> the head ->
+ *   log_softmax, as pcr_pn2_forward_f32 has the last two; the identity joins a T-Net's matrix in a launch of its own (pn1_identity).  The stages hand device buffers to each other, the number of launches does not
+ *   depend on n_obj, the host waits once.  logp: n_obj x n_class; optional: pred (the first maximum), global_feat n_obj x widths[n_mlp - 1],
+ *   trans n_obj x 9, trans_feat n_obj x K x K (each must be NULL when the model has no such T-Net).  n_obj == 0: PCR_OK, nothing written.
+ *   PCR_ERR_ARG: NULL ctx / model / objects / logp; npts < 1; a non-finite coordinate or feature (checked on the host copy, nothing is
+ *   launched); more than 2^31 - 16 rows in a stage.  Profile names pn1_chain, pn1_identity, pn2_head, pn2_logsoftmax. */
+typedef struct pcr_pn1_desc {
+    uint32_t D0;
+    uint32_t stn3;
+    uint32_t fstn;
+    uint32_t n_mlp;
+    uint32_t widths[PCR_PN2_MAX_MLP];
+    uint32_t tnet_conv[3];
+    uint32_t tnet_fc[2];
+    uint32_t n_fc;
+    uint32_t fc_widths[PCR_PN2_MAX_FC];
+    double bn_eps;
+} pcr_pn1_desc;
+int pcr_pn1_model_create(pcr_ctx* ctx, const pcr_pn1_desc* desc, const float* weights, size_t n_weights, pcr_pn2_model** out);
+int pcr_pn1_model_info(const pcr_pn2_model* model, size_t npts_hint, pcr_pn2_info* info, pcr_pn1_desc* desc);
+int pcr_pointwise_chain_max_f32(pcr_ctx* ctx, const pcr_pn2_model* model, int stage, const pcr_cloud* cloud, const uint32_t* seg_ptr, size_t n_seg,
+                                const float* features, const float* trans3, const float* trans_feat, float* out);
+int pcr_pointnet_forward_f32(pcr_ctx* ctx, const pcr_pn2_model* model, const float* objects, size_t n_obj, size_t npts, float* logp, int32_t* pred,
+                             float* global_feat, float* trans, float* trans_feat);
+
 /* ---- next row N4: global-registration front half, Homework9/hw9/src/registration.cpp:288-434, :535-615 -----------
  * N4a: exhaustive 1-NN between two descriptor sets (row-major n x dim / m x dim f32, host memory; dim 33 = FPFH),
  * nanoflann's evalMetric arithmetic for any dim (nanoflann.hpp:382-405: groups of four + tail, f32, unfused), canonical
