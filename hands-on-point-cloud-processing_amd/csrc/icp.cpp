@@ -55,6 +55,7 @@ static int icp_sync(pcr_ctx* ctx, const pcr_cloud* src, const pcr_cloud* tgt, co
     const LoopHint hint(ctx, prm->max_iter);
     ctx->keys_seeded = false;            // (seeds a move of an earlier loop left behind describe positions that no longer exist)
     ctx->icp_last_chain = 0;
+    ctx->icp_last_snapshots = 0;
 
     // prof bookkeeping: report only this call's nn1 time
     PCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -151,8 +152,9 @@ static int icp_sync(pcr_ctx* ctx, const pcr_cloud* src, const pcr_cloud* tgt, co
 }
 
 // ---- pipelined loop: the state machine, the Kabsch solve and the pose composition live on the GPU (IcpState,
-// kabsch.hip); iterations are enqueued back to back on the context stream in chunks, the host only looks at a copy
-// of the state two chunks behind to learn when to stop enqueuing.  With RCCL the per-iteration all-reduce is
+// kabsch.hip); iterations are enqueued back to back on the context stream in chunks, the host only looks at a snapshot
+// of the state two chunks behind to learn when to stop enqueuing — a copy on the stream behind an event, or, on the chain
+// search -> sums + solve, a slot of the host ring that launch writes itself (below).  With RCCL the per-iteration all-reduce is
 // enqueued on the same stream, so even the sharded loop needs no host round trip.
 static int icp_pipelined(pcr_ctx* ctx, const pcr_cloud* src, const pcr_cloud* tgt, const float init_T[16],
                          const pcr_icp_params* prm, float out_T[16], pcr_icp_stats* stats)
@@ -182,11 +184,17 @@ static int icp_pipelined(pcr_ctx* ctx, const pcr_cloud* src, const pcr_cloud* tg
         ctx->icp_barrier_arrived = 0;
         ctx->icp_acc_dev = reinterpret_cast<long long*>(reinterpret_cast<char*>(ctx->icp_state_dev) + 512 + 128);
         ctx->icp_acc_dirty = false;
-        PCR_HIP(ctx, hipHostMalloc((void**)&ctx->icp_state_host, (RING + 1) * sizeof(IcpState), hipHostMallocDefault));
+        // the host ring: pinned and explicitly coherent, because the sums + solve launch may store a slot itself (below) and the host
+        // reads it while the stream runs on; zeroed, so that no slot carries a sequence number before a launch has written one
+        PCR_HIP(ctx, hipHostMalloc((void**)&ctx->icp_state_host, (RING + 1) * sizeof(IcpSnapSlot), hipHostMallocCoherent | hipHostMallocMapped));
+        memset(ctx->icp_state_host, 0, (RING + 1) * sizeof(IcpSnapSlot));
+        PCR_HIP(ctx, hipHostGetDevicePointer((void**)&ctx->icp_state_host_dev, ctx->icp_state_host, 0));
         for (int k = 0; k < RING; k++) PCR_HIP(ctx, hipEventCreateWithFlags(&ctx->icp_events[k], hipEventDisableTiming));
     }
+    if (!ctx->icp_state_host || !ctx->icp_state_host_dev) return fail(ctx, PCR_ERR_STATE, "icp host ring");      // (an earlier call failed half way through the set-up above)
     IcpState* dev = ctx->icp_state_dev;
-    IcpState* host = ctx->icp_state_host;      // [0..RING) ring of snapshots, [RING] upload / final download
+    IcpSnapSlot* host = ctx->icp_state_host;   // [0..RING) ring of snapshots, [RING] upload / final state
+    ctx->icp_last_snapshots = 0;
 
     // pairs are kept only if d2 < max_corr (:936), so the grid search need not look farther (tune icp_bounded_search: 2 = off)
     const float gate = tune_get(ctx, "icp_bounded_search", 1) == 1 ? prm->max_corr : __builtin_inff();
@@ -197,7 +205,7 @@ static int icp_pipelined(pcr_ctx* ctx, const pcr_cloud* src, const pcr_cloud* tg
     const float t0[3] = { init_T[3], init_T[7], init_T[11] };
     rc = launch_transform_into(ctx, src, work, R0, t0);                          // :874
     if (rc == PCR_OK) rc = icp_uses_grid(ctx, tgt) ? grid_sort_working_cloud(ctx, tgt, &work) : icp_sort_for_brute(ctx, tgt, &work, prm->max_iter);
-    IcpState& h0 = host[RING];
+    IcpState& h0 = host[RING].state;
     memset(&h0, 0, sizeof h0);
     const float T0[16] = { R0[0], R0[1], R0[2], t0[0], R0[3], R0[4], R0[5], t0[1], R0[6], R0[7], R0[8], t0[2], 0, 0, 0, 1 };
     memcpy(h0.T_total, T0, sizeof T0);                                           // :910-913
@@ -238,7 +246,9 @@ static int icp_pipelined(pcr_ctx* ctx, const pcr_cloud* src, const pcr_cloud* tg
     // The sums + solve launch hands a workgroup's limb totals on as int64 atomic adds into eight accumulator rows, not as a row per workgroup (DESIGN.md
     // 6i, profiles/icp_sums_accumulators.txt): the last arriver reads eight short rows whatever the geometry, so the launch runs 512 threads x 2 pairs
     // on 118 workgroups — kernel 19.9 -> 17.5 us, a step of the bench line 53.4 -> 50.9 us (8 + 8 alternating processes, spreads 2.5 / 0.9).  What
-    // now bounds it: arrivals at the one ticket counter take ~35 ns each, one after the other (the last of 118 waits 4 us, of 469 16 us), then the solve.
+    // now bounds it: the last arriver has its ticket back and its acquire done ~35 ns per arriving workgroup later (4 - 5 us at 118, 9 at 235, 16 at 469),
+    // then the solve.  A ticket per replica (tune icp_ticket_levels = 2: arrivals queue as 15 + 8) does not shorten that wait — 4.1 - 5.5 us
+    // at 118 workgroups, 8.1 - 11.2 at 235 — so whatever the 35 ns are, they are not a queue at one address; one counter stays the default.
     const bool move_cand = fused && seed_tgt && icp_sums_solve_blocks(ctx, work->n) != 0;
     bool move_in_search = false;
     // (Measured and dropped, round 4: the Kabsch sums taken by the search kernel itself — STRACK3 ends with every query's final key in one wave, so each
@@ -249,6 +259,16 @@ static int icp_pipelined(pcr_ctx* ctx, const pcr_cloud* src, const pcr_cloud* tg
     // per iteration.  Also measured: the 3 x 3 solve is 4.6 of the 17.5 us of the solve + move.
     // Measured now (profiles/icp_fused_sums.txt): the sums in the solve + move launch instead, behind one grid barrier — 7.8 + 17.3 us of kernels become 23.1 us,
     // the search keeps its 26.2 us, and a step of the bench line goes from 63.6 to 61.8 us.)
+    // State snapshots of that chain (profiles/icp_host_snapshots.txt; tune icp_host_snapshots: 2 = off): the sums + solve launch that ends
+    // a chunk, or the call, is handed a slot of the host ring and a sequence number; its publishing workgroup stores the state there itself and then
+    // the number, a system-scope release (0.6 us on the launches that do it).  No copy and no event on the stream: the blit kernel (4.3 us) and the
+    // event's marker (5 - 6 us before the next search started) stood in the dependent chain once per chunk.  The host polls the slot two chunks back
+    // for its number (the stream bounds the poll, below) and reads the final state from the slot of the last launch once the stream has drained: a
+    // step of the bench line 50.9 -> 48.9 us.  Every other chain, and a call of no iteration, keeps its copies and events.
+    const bool snap_cand = tune_get(ctx, "icp_host_snapshots", 1) == 1;
+    bool snaps = false;
+    unsigned long long ring_seq[RING + 1] = { 0, 0, 0, 0, 0 };      // the number each slot was last promised
+    int last_slot = -1;                                              // the slot the last sums + solve launch of the call writes
     uint64_t enq = 0, chunks = 0;
     bool stopped = false;
     while (rc == PCR_OK && !stopped && enq < prm->max_iter) {
@@ -265,8 +285,15 @@ static int icp_pipelined(pcr_ctx* ctx, const pcr_cloud* src, const pcr_cloud* tg
                                                 tune_get(ctx, "icp_fused_sums_min", 0), tune_get(ctx, "nn1_s3_transposed", 0), tune_get(ctx, "nn1_sphere_qg", 0),
                                                 tune_get(ctx, "nn1_sphere_l0_per_slice", 0), tune_get(ctx, "nn1_sphere_blocks", 0));
             else if (move_in_search && !ctx->nn1_moved) { rc = fail(ctx, PCR_ERR_STATE, "ICP: a search of the chain search -> sums + solve did not move the cloud"); break; }
+            if (enq == 0) snaps = move_in_search && snap_cand;
             if (move_in_search) {
-                if ((rc = launch_icp_sums_solve(ctx, tgt, work, prm->max_corr, cur, dev + ((enq + 1) & 1), plan))) break;                            // :936-1002
+                // the last launch of the call writes slot [RING], the last of any other chunk the chunk's slot of the ring, the others none
+                const bool ends_call = enq + 1 == prm->max_iter, ends_chunk = c + 1 == chunk;
+                const int slot = !snaps ? -1 : ends_call ? RING : ends_chunk ? (int)(chunks % RING) : -1;
+                if (slot >= 0) ring_seq[slot] = ++ctx->icp_snap_seq;
+                if ((rc = launch_icp_sums_solve(ctx, tgt, work, prm->max_corr, cur, dev + ((enq + 1) & 1), plan,                                     // :936-1002
+                                                slot >= 0 ? ctx->icp_state_host_dev + slot : nullptr, slot >= 0 ? ring_seq[slot] : 0ull))) break;
+                if (slot >= 0) last_slot = slot;
                 continue;
             }
             if (fused_sums) {
@@ -291,32 +318,66 @@ static int icp_pipelined(pcr_ctx* ctx, const pcr_cloud* src, const pcr_cloud* tg
         ctx->stop_flag_dev = nullptr;
         if (rc) break;
         const int slot = (int)(chunks % RING);
-        e = hipMemcpyAsync(&host[slot], fused ? dev + (enq & 1) : dev, sizeof(IcpState), hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipEventRecord(ctx->icp_events[slot], ctx->stream);
-        if (e != hipSuccess) { rc = fail(ctx, PCR_ERR_HIP, "icp snapshot", e); break; }
+        if (!snaps) {
+            e = hipMemcpyAsync(&host[slot].state, fused ? dev + (enq & 1) : dev, sizeof(IcpState), hipMemcpyDeviceToHost, ctx->stream);
+            if (e == hipSuccess) e = hipEventRecord(ctx->icp_events[slot], ctx->stream);
+            if (e != hipSuccess) { rc = fail(ctx, PCR_ERR_HIP, "icp snapshot", e); break; }
+        }
         chunks++;
         if (chunks >= 2) {
             // look two chunks back: deterministic (the same on every rank), and the GPU never runs dry
             const int old = (int)((chunks - 2) % RING);
-            e = hipEventSynchronize(ctx->icp_events[old]);
-            if (e != hipSuccess) { rc = fail(ctx, PCR_ERR_HIP, "icp snapshot wait", e); break; }
-            if (host[old].stop || host[old].stop_after_transform || host[old].barrier_timeout) stopped = true;
+            if (snaps) {
+                // the slot carries its number once the launch that ends that chunk has published.  The poll is bounded by the stream, not by a clock:
+                // any answer of hipStreamQuery but "not ready" ends it, and a stream that has drained has run that launch, so the slot must carry
+                // the number then.  But the stream is asked only once the number is SNAP_PATIENCE late — many times a chunk of the loops that take
+                // this chain — and between all reads from then on: the first query behind a kernel launch puts a marker packet on the stream to
+                // have something to ask after, and that marker, asked for at every chunk, was the 5.9 us gap in front of the next chunk's first
+                // search all over again (profiles/icp_host_snapshots.txt section 2)
+                constexpr auto SNAP_PATIENCE = std::chrono::milliseconds(2);
+                hipError_t q = hipErrorNotReady;
+                bool seen = false, ask = false;
+                const auto t_poll = std::chrono::steady_clock::now();
+                for (uint32_t spin = 0; ; spin++) {
+                    seen = __atomic_load_n(&host[old].seq, __ATOMIC_ACQUIRE) == ring_seq[old];
+                    if (seen || q != hipErrorNotReady) break;        // (behind an answer of the stream the slot has been read once more)
+                    if (!ask && (spin & 255u) == 255u) ask = std::chrono::steady_clock::now() - t_poll > SNAP_PATIENCE;
+                    if (ask) q = hipStreamQuery(ctx->stream);
+                }
+                if (q == hipErrorNotReady) (void)hipGetLastError();  // (the stream's "not ready" is no launch's error: the next launch check must not find it)
+                if (!seen) {
+                    rc = q == hipSuccess ? fail(ctx, PCR_ERR_STATE, "ICP: the stream drained and a state snapshot never arrived in the host ring")
+                                         : fail(ctx, PCR_ERR_HIP, "icp snapshot wait", q);
+                    break;
+                }
+            } else {
+                e = hipEventSynchronize(ctx->icp_events[old]);
+                if (e != hipSuccess) { rc = fail(ctx, PCR_ERR_HIP, "icp snapshot wait", e); break; }
+            }
+            const IcpState& o = host[old].state;
+            if (o.stop || o.stop_after_transform || o.barrier_timeout) stopped = true;
         }
     }
     ctx->stop_flag_dev = nullptr;
+    // the final state: from the slot the last sums + solve launch wrote, once the stream has drained — or, on every other chain and behind a call that
+    // enqueued no such launch (max_iter = 0), by a copy behind the last launch
+    const bool final_in_slot = snaps && last_slot >= 0;
+    const IcpState& f = host[final_in_slot ? last_slot : RING].state;
     if (rc == PCR_OK) {
-        e = hipMemcpyAsync(&host[RING], fused ? dev + (enq & 1) : dev, sizeof(IcpState), hipMemcpyDeviceToHost, ctx->stream);
+        e = final_in_slot ? hipSuccess : hipMemcpyAsync(&host[RING].state, fused ? dev + (enq & 1) : dev, sizeof(IcpState), hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
         if (e != hipSuccess) rc = fail(ctx, PCR_ERR_HIP, "icp state download", e);
+        else if (final_in_slot && __atomic_load_n(&host[last_slot].seq, __ATOMIC_ACQUIRE) != ring_seq[last_slot])
+            rc = fail(ctx, PCR_ERR_STATE, "ICP: the stream drained and the final state never arrived in the host ring");
     } else {
         hipStreamSynchronize(ctx->stream);
     }
     cloud_release(ctx, work);             // (synchronised above; the loop's own working copy: parked for the next call's clone)
     // the accumulators of the sums + solve launch are all zero behind a call that ran to its end; one that did not says so, and the next call clears them
-    if (move_in_search && (rc || host[RING].overflow || host[RING].barrier_timeout)) ctx->icp_acc_dirty = true;
+    if (move_in_search && (rc || f.overflow || f.barrier_timeout)) ctx->icp_acc_dirty = true;
     if (rc) return rc;
     ctx->icp_last_chain = move_in_search ? 4 : fused_sums ? 3 : fused ? 2 : 1;
-    const IcpState& f = host[RING];
+    ctx->icp_last_snapshots = final_in_slot ? 1 : 0;
     if (f.overflow) return fail(ctx, PCR_ERR_STATE, "ICP: a kept source point lies more than 2^20 target extents away from the target");
     if (f.barrier_timeout) {
         // (the flag must not outlive the call in the state buffer the next call does not upload)
@@ -338,6 +399,8 @@ static int icp_pipelined(pcr_ctx* ctx, const pcr_cloud* src, const pcr_cloud* tg
 }
 
 extern "C" int pcr_icp_last_chain(const pcr_ctx* ctx) { return ctx ? ctx->icp_last_chain : 0; }
+extern "C" int pcr_icp_last_snapshots(const pcr_ctx* ctx) { return ctx ? ctx->icp_last_snapshots : 0; }
+extern "C" uint32_t pcr_icp_replica_members(uint32_t blocks, uint32_t replica) { return icp_replica_members(blocks, replica); }
 
 extern "C" int pcr_icp_move_route(uint64_t n_src, uint64_t n_tgt, int nranks, int64_t move_in_search, int64_t fused_sums, int64_t fused_sums_min,
                                   int64_t s3_transposed, int64_t sphere_qg, int64_t sphere_l0_per_slice, int64_t sphere_blocks)

@@ -940,16 +940,32 @@ __device__ __forceinline__ void limbs_normalize_i64(long long* L, int n, double*
 // icp_state_step to publish the whole state to st_out; every other workgroup has returned.  No spin, no residency condition on the grid: the move needs
 // the new R, t, but the move is the next launch's.  Phases 0 and 1 (stopped loop, stop_after_transform) add nothing and leave the zeros alone: the last
 // arriver writes the stopped state.
+// in every phase the publishing workgroup also writes the state into a slot of the host ring where the launch ends a chunk or the call
+// (ss_snapshot below; snap, seq).  levels = 2 (tune icp_ticket_levels; measured, no gain, not the default) arrives in two steps: at a counter of the
+// workgroup's own replica, and only the last of a replica at the shared counter — which then counts the replicas that have workgroups, not the workgroups.
 // An accumulator holds at most n terms below 2^40: n < 2^22 (icp_sums_solve_blocks) keeps it below 2^62.
 constexpr int ACC_R = ICP_ACC_REPLICAS, ACC_W = ICP_ACC_WORDS;      // words of a replica: [0..40) live limbs, [40] overflow count, [41] key, pad to 3 lines
-static_assert((ACC_R & (ACC_R - 1)) == 0 && ACC_W * 8 % 128 == 0 && ACC_W >= KB_NLC + 2, "replicas: a power of two, whole 128-byte lines");
+constexpr int ACC_CNT = KB_NLC + 2;                                  // [42] the replica's arrival counter where every replica has a ticket of its own (6j)
+static_assert((ACC_R & (ACC_R - 1)) == 0 && ACC_W * 8 % 128 == 0 && ACC_W >= KB_NLC + 3, "replicas: a power of two, whole 128-byte lines");
+
+// DESIGN.md 6j.  The state snapshot the host loop looks at (icp.cpp), written by the publishing workgroup itself where the launch is the last of a chunk or
+// of the call (snap: a slot of the pinned, coherent host ring; null otherwise — uniform over the workgroup): the words of the state just published, from
+// the threads that published them, then — behind a workgroup barrier, so that the words precede it — one lane's SYSTEM-scope release store of the
+// sequence number the host waits for.  (All of it is wave 0's: ST_WORDS <= 64.)
+__device__ __forceinline__ void ss_snapshot(IcpSnapSlot* snap, unsigned long long seq, const IcpState* s_st)
+{
+    if (!snap) return;
+    if (threadIdx.x < ST_WORDS) reinterpret_cast<uint32_t*>(&snap->state)[threadIdx.x] = reinterpret_cast<const uint32_t*>(s_st)[threadIdx.x];
+    __syncthreads();
+    if (threadIdx.x == 0) __hip_atomic_store(&snap->seq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
 
 template <int T, int PP>
 __global__ __launch_bounds__(T) void icp_sums_solve_kernel(
     const float* __restrict__ tx, const float* __restrict__ ty, const float* __restrict__ tz, const uint32_t* __restrict__ orig,
     const unsigned long long* __restrict__ keys, uint32_t nt, float max_corr, KabschPlan plan, long long* acc, unsigned long long* counter,
     unsigned long long target, const IcpState* __restrict__ st_in, IcpState* __restrict__ st_out, double* __restrict__ out, const float* __restrict__ x,
-    const float* __restrict__ y, const float* __restrict__ z, uint32_t n, uint32_t np
+    const float* __restrict__ y, const float* __restrict__ z, uint32_t n, uint32_t np, IcpSnapSlot* snap, unsigned long long seq, int levels
 #ifdef PCR_SS_PROF
     , unsigned long long* prof
 #endif
@@ -957,6 +973,7 @@ __global__ __launch_bounds__(T) void icp_sums_solve_kernel(
 {
     constexpr int WAVES = T / 64;
     static_assert((unsigned long long)T * PP * (1ull << num::KB_W) <= (1ull << 53), "a workgroup's limb totals must be exact in f64");
+    static_assert(ST_WORDS <= 64 && offsetof(IcpSnapSlot, state) == 0, "one wave stores a snapshot's words and, behind them, its sequence number");
     static_assert(T >= 64 && ACC_R * ACC_W <= 2 * T, "the last arriver reads the replicas in at most two loads per thread");
     __shared__ double red_l[WAVES][KB_NL];
     __shared__ long long s_acc[ACC_R][ACC_W];
@@ -997,12 +1014,38 @@ __global__ __launch_bounds__(T) void icp_sums_solve_kernel(
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // (kept behind the fence whatever the compiler thinks of the scoreboard)
             }
-            const int last = __hip_atomic_fetch_add(counter, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1ull == target;
+            int last;
+            if (levels == 2) {
+                // a ticket per replica: this workgroup arrives at its replica's counter (word ACC_CNT of the row; zero between launches like the row), and
+                // only the last of the replica's icp_replica_members goes on to the final counter, where at most ACC_R arrive.  It passes on what it
+                // acquired: one acquire-release fence between its two adds, in every phase (the stopped phases hand nothing on but the order of the
+                // counters' own modifications: the final arriver's zeros must come after every add)
+                const uint32_t r = blockIdx.x & (ACC_R - 1);
+                unsigned long long* mine_cnt = reinterpret_cast<unsigned long long*>(acc + (size_t)r * ACC_W + ACC_CNT);
+                if (phase != 2) {
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                }
+                const unsigned long long mine_t = __hip_atomic_fetch_add(mine_cnt, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1ull;
 #ifdef PCR_SS_PROF
-            pt_c = __builtin_amdgcn_s_memrealtime();
+                pt_c = __builtin_amdgcn_s_memrealtime();
+#endif
+                last = 0;
+                if (mine_t == icp_replica_members(gridDim.x, r)) {
+                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "agent");
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                    last = __hip_atomic_fetch_add(counter, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1ull == target;
+                }
+            } else {
+                last = __hip_atomic_fetch_add(counter, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1ull == target;
+#ifdef PCR_SS_PROF
+                pt_c = __builtin_amdgcn_s_memrealtime();
+#endif
+            }
+#ifdef PCR_SS_PROF
             if (prof && phase == 2) { atomicAdd(prof + 12, pt_b - pt_a); atomicAdd(prof + 13, pt_c - pt_b); atomicAdd(prof + 14, 1ull); atomicMax(prof + 15, pt_c - pt_b); }
 #endif
-            if (last && phase == 2) {
+            if (last && (phase == 2 || levels == 2)) {
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the invalidate is over before the barrier below lets the other waves read
             }
@@ -1066,16 +1109,25 @@ __global__ __launch_bounds__(T) void icp_sums_solve_kernel(
         if (threadIdx.x < ST_WORDS) reinterpret_cast<uint32_t*>(st_out)[threadIdx.x] = reinterpret_cast<const uint32_t*>(&s_st)[threadIdx.x];
 #ifdef PCR_SS_PROF
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (prof && threadIdx.x == 0) {          // (the last arriver alone: plain values, ticket -> replicas reduced -> solved -> published)
-            prof[0] = pt_d - pt_c; prof[1] = pt_e - pt_d; prof[11] = __builtin_amdgcn_s_memrealtime() - pt_e;
+        const unsigned long long pt_f = __builtin_amdgcn_s_memrealtime();
+#endif
+        ss_snapshot(snap, seq, &s_st);
+#ifdef PCR_SS_PROF
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (prof && threadIdx.x == 0) {          // (the last arriver alone: plain values, ticket -> replicas reduced -> solved -> published -> snapshot in host memory)
+            prof[0] = pt_d - pt_c; prof[1] = pt_e - pt_d; prof[11] = pt_f - pt_e; prof[4] = snap ? __builtin_amdgcn_s_memrealtime() - pt_f : 0ull;
             prof[2] = pt_c1 - pt_c; prof[3] = pt_c2 - pt_c1;     // (ticket -> acquired -> replicas in LDS)
         }
 #endif
         return;
     }
     if (threadIdx.x == 0) s_st.stop = 1;       // (phase 0: stays stopped; phase 1: max_iter reached, the loop is over)
+    // (a ticket per replica: nothing was added to the rows, but their counters have counted this launch's arrivals — back to zero, behind the acquire above)
+    if (levels == 2 && threadIdx.x < ACC_R)
+        __hip_atomic_store(reinterpret_cast<unsigned long long*>(acc + (size_t)threadIdx.x * ACC_W + ACC_CNT), 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __syncthreads();
     if (threadIdx.x < ST_WORDS) reinterpret_cast<uint32_t*>(st_out)[threadIdx.x] = reinterpret_cast<const uint32_t*>(&s_st)[threadIdx.x];
+    ss_snapshot(snap, seq, &s_st);
 }
 
 // multi rank, step 1: reduce the block rows into the all-reduce buffer
@@ -1278,7 +1330,17 @@ uint32_t icp_sums_solve_blocks(const pcr_ctx* ctx, size_t n)
     return (uint32_t)((np + T - 1) / T);
 }
 
-int launch_icp_sums_solve(pcr_ctx* ctx, const pcr_cloud* tgt, const pcr_cloud* c, float max_corr, const IcpState* st_in, IcpState* st_out, const KabschPlan& plan)
+// arrival counters of the sums + solve launch (tune icp_ticket_levels: 1 = the one counter, 2 = one per replica and the shared one behind them; any other
+// value is the default; DESIGN.md 6j, profiles/icp_host_snapshots.txt)
+constexpr int SS_LEVELS_DEFAULT = 1;      // (measured: the ticket per replica gains nothing at 118 or 235 workgroups)
+static int ss_levels(const pcr_ctx* ctx)
+{
+    const int64_t l = tune_get(ctx, "icp_ticket_levels", SS_LEVELS_DEFAULT);
+    return l == 1 ? 1 : l == 2 ? 2 : SS_LEVELS_DEFAULT;
+}
+
+int launch_icp_sums_solve(pcr_ctx* ctx, const pcr_cloud* tgt, const pcr_cloud* c, float max_corr, const IcpState* st_in, IcpState* st_out, const KabschPlan& plan,
+                          IcpSnapSlot* snap, unsigned long long seq)
 {
     if (ctx->keys_n != c->n) return fail(ctx, PCR_ERR_STATE, "kabsch: no matching correspondence pass");
     const uint32_t blocks = icp_sums_solve_blocks(ctx, c->n);
@@ -1288,9 +1350,12 @@ int launch_icp_sums_solve(pcr_ctx* ctx, const pcr_cloud* tgt, const pcr_cloud* c
         PCR_HIP(ctx, hipMemsetAsync(ctx->icp_acc_dev, 0, (size_t)ICP_ACC_REPLICAS * ICP_ACC_WORDS * sizeof(long long), ctx->stream));
         ctx->icp_acc_dirty = false;
     }
-    const int T = ss_threads(ctx), PP = ss_pairs(ctx);
+    const int T = ss_threads(ctx), PP = ss_pairs(ctx), levels = ss_levels(ctx);
     const uint32_t np = (uint32_t)((c->n + PP - 1) / PP);
-    const unsigned long long target = ctx->icp_barrier_arrived + blocks;      // the counter's value once every workgroup of this launch has arrived
+    // the shared counter's value once every workgroup of this launch has arrived — with a ticket per replica, once the last of every replica that has
+    // workgroups has (the counter is also the grid barrier's of the fused sums + move launch: it only ever grows, by whatever a launch adds)
+    const uint32_t arrivals = levels == 2 ? (blocks < (uint32_t)ICP_ACC_REPLICAS ? blocks : (uint32_t)ICP_ACC_REPLICAS) : blocks;
+    const unsigned long long target = ctx->icp_barrier_arrived + arrivals;
     {
         ProfScope p(ctx, "icp_update");
 #ifdef PCR_SS_PROF
@@ -1301,7 +1366,7 @@ int launch_icp_sums_solve(pcr_ctx* ctx, const pcr_cloud* tgt, const pcr_cloud* c
 #define PCR_SS(T, PP)                                                                                                                             \
         hipLaunchKernelGGL((icp_sums_solve_kernel<T, PP>), dim3(blocks), dim3(T), 0, ctx->stream, tgt->x(), tgt->y(), tgt->z(), c->orig, ctx->keys,  \
                            (uint32_t)tgt->n, max_corr, plan, ctx->icp_acc_dev, ctx->icp_barrier_dev, target, st_in, st_out, ctx->dev_out, c->x(),    \
-                           c->y(), c->z(), (uint32_t)c->n, np PCR_SS_EXTRA)
+                           c->y(), c->z(), (uint32_t)c->n, np, snap, seq, levels PCR_SS_EXTRA)
         if (T == 256) { if (PP == 1) PCR_SS(256, 1); else if (PP == 2) PCR_SS(256, 2); else PCR_SS(256, 4); }
         else { if (PP == 1) PCR_SS(512, 1); else if (PP == 2) PCR_SS(512, 2); else PCR_SS(512, 4); }
 #undef PCR_SS

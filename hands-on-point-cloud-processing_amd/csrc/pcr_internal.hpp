@@ -22,6 +22,12 @@ constexpr size_t PAD = 1024;
 constexpr int PCR_NSTATS = 16;      // diagnostics words of a 1-NN launch (tune grid_stats; pcr_nn1_stats)
 // the accumulators of the ICP sums + solve launch (kabsch.hip): replicas (a power of two) of 48 int64 = three 128-byte lines each
 constexpr int ICP_ACC_REPLICAS = 8, ICP_ACC_WORDS = 48;
+// with a ticket per replica: the workgroups of a launch of `blocks` workgroups that arrive at replica r (workgroup b belongs to replica
+// b & (R - 1)); 0 for a replica the launch does not reach, which nobody waits for
+__host__ __device__ constexpr uint32_t icp_replica_members(uint32_t blocks, uint32_t r)
+{
+    return r < (uint32_t)ICP_ACC_REPLICAS && r < blocks ? (blocks - r + ICP_ACC_REPLICAS - 1) / ICP_ACC_REPLICAS : 0u;
+}
 
 inline size_t padded(size_t n) { return ((n + PAD - 1) / PAD) * PAD + PAD; }   // always >= 1 full pad block
 
@@ -50,6 +56,13 @@ struct IcpState {
     unsigned long long iters_run;
     unsigned long long max_iter;
     unsigned long long last_pairs;
+};
+// a slot of the pinned host ring the pipelined loop learns the state from (icp.cpp): the state, and behind it the sequence number of the launch that
+// wrote it where the sums + solve launch stores the snapshot itself — seq only grows over a context's life, so a slot left by an
+// earlier call or an earlier trip round the ring is never taken for the one awaited
+struct IcpSnapSlot {
+    IcpState state;
+    unsigned long long seq;
 };
 
 // fixed-point grid of one exact Kabsch accumulation (kabsch.hip / numerics.hpp): 2^e bounds every coordinate of a kept pair
@@ -194,7 +207,12 @@ struct pcr_ctx {
     // first launch clears them
     long long* icp_acc_dev = nullptr;
     bool icp_acc_dirty = false;
-    pcr::IcpState* icp_state_host = nullptr;
+    // the pinned, coherent host ring: [0..4) snapshots, [4] upload / final state; its address as the device sees it; the last sequence number handed
+    // to a launch that writes a slot itself (never reset); how the last call took its snapshots (pcr_icp_last_snapshots)
+    pcr::IcpSnapSlot* icp_state_host = nullptr;
+    pcr::IcpSnapSlot* icp_state_host_dev = nullptr;
+    unsigned long long icp_snap_seq = 0;
+    int icp_last_snapshots = 0;
     hipEvent_t icp_events[4] = { nullptr, nullptr, nullptr, nullptr };
     unsigned long long* grid_stats_dev = nullptr;   // diagnostics of the grid search (tune grid_stats)
     const int* stop_flag_dev = nullptr;        // when set, the correspondence kernels exit early once *flag != 0
@@ -340,9 +358,11 @@ int launch_icp_sums_update_move(pcr_ctx* ctx, const pcr_cloud* tgt, pcr_cloud* c
                                 const KabschPlan& plan, const pcr_cloud* seed_tgt);
 // the chain search (moves the cloud by the previous solve) -> sums + solve: the front half of the launch above and a ticket, the last
 // workgroup to arrive reduces and solves; nobody waits and nothing moves.  A workgroup's totals go out as int64 atomic adds into ctx->icp_acc_dev, not
-// as a row.  icp_sums_solve_blocks = its workgroups (0: switched off, too few points, or 2^22 points and more)
+// as a row.  icp_sums_solve_blocks = its workgroups (0: switched off, too few points, or 2^22 points and more).  snap: null, or the slot
+// of the host ring (device address) the publishing workgroup also writes the state to, followed by a system-scope release store of seq
 uint32_t icp_sums_solve_blocks(const pcr_ctx* ctx, size_t n);
-int launch_icp_sums_solve(pcr_ctx* ctx, const pcr_cloud* tgt, const pcr_cloud* c, float max_corr, const IcpState* st_in, IcpState* st_out, const KabschPlan& plan);
+int launch_icp_sums_solve(pcr_ctx* ctx, const pcr_cloud* tgt, const pcr_cloud* c, float max_corr, const IcpState* st_in, IcpState* st_out, const KabschPlan& plan,
+                          IcpSnapSlot* snap, unsigned long long seq);
 // nn1_brute.hip: can a seeded STRACK3 search of ns queries over n_l0 level-0 super-tiles carry the move (transposed form, one slice)?  Raw tune values
 uint64_t s3_l0_super_tiles(uint64_t n_tgt);          // the level-0 super-tiles the index of a target of n_tgt points has (bt_ensure_l1)
 bool s3_move_route(uint64_t n_l0, uint64_t ns, int64_t transposed_tune, int64_t qg_tune, int64_t l0_per_slice_tune, int64_t blocks_tune);

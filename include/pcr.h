@@ -136,6 +136,13 @@ int pcr_icp_p2p_f32(pcr_ctx* ctx, const pcr_cloud* src, const pcr_cloud* tgt, co
  * 0 = the synchronous loop, no call yet, or a call that failed; 1 = sums, solve and move as launches of their own; 2 = sums -> solve + move;
  * 3 = sums + solve + move in one launch; 4 = sums + solve in one launch, the NEXT search moves the cloud (tune "icp_move_in_search"). */
 int pcr_icp_last_chain(const pcr_ctx* ctx);
+/* How the last pcr_icp_p2p_f32 call on this context learnt its loop's state (diagnostics; same bits either way): 0 = copies and events on the stream
+ * (also: no call yet, a call that failed, the synchronous loop, a call of no iteration); 1 = written into pinned host memory by the sums + solve launch
+ * itself (chain 4; tune "icp_host_snapshots": 2 = off). */
+int pcr_icp_last_snapshots(const pcr_ctx* ctx);
+/* Host logic, no GPU: with an arrival counter per accumulator replica (tune "icp_ticket_levels": 1 = one counter, 2 = per replica), how many of the
+ * `blocks` workgroups of a sums + solve launch arrive at replica `replica` (0 .. 7); 0 = the launch does not reach it and nobody waits for it. */
+uint32_t pcr_icp_replica_members(uint32_t blocks, uint32_t replica);
 /* Host logic, no GPU: would a single-rank exhaustive loop of n_src points over a target of n_tgt points, whose searches take the three-level
  * sphere kernel, run chain 4?  The tunes are passed as RAW values, 0 = default: icp_move_in_search (1 on / 2 off), icp_fused_sums (2 off),
  * icp_fused_sums_min, nn1_s3_transposed (2 = the form without the move), nn1_sphere_qg, nn1_sphere_l0_per_slice, nn1_sphere_blocks (the search
@@ -1135,6 +1142,8 @@ int pcr_ctx_mfma_check(pcr_ctx* ctx, int run_now, pcr_mfma_check* out);
  *              icp_fused_move [on] 2 = off, icp_fused_max [262 144] · icp_seed_in_move [on] 2 = off · icp_force_slots (tests) ·
  *              icp_fused_sums [on] 2 = off (exhaustive loops: the sums in the solve + move launch, one grid barrier), icp_fused_sums_min [60 000 points],
  *              icp_fused_sums_max_blocks [CUs of the device], icp_fused_sums_threads [512] 256, icp_fused_sums_grid [off] 1 = grid loops too ·
+ *              icp_host_snapshots [on where the chain is 4: the sums + solve launch writes the state snapshots into pinned host memory] 2 = copies and
+ *              events on the stream · icp_ticket_levels [1: one arrival counter for that launch] 2 = one per accumulator replica ·
  *              kabsch_bfly [on], kabsch_records [on], kabsch_one_pair_blocks [128], kabsch_max_blocks [1 024]
  *  other       plane_group [20: hypotheses per workgroup row of the plane count] · iss_lanes [32] · fpfh_lanes [16] · harris_lanes [16] · radius_fused [on] 2 = off · grid_stats 1 = the next 1-NN launch fills pcr_nn1_stats · prof 0 / 1 / 2 / 3 (3 = 2 plus one
  *              radius_emit_class scope per length-class launch inside radius_emit) */

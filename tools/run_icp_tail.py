@@ -6,13 +6,16 @@ usage: run_icp_tail.py trace [n]            two 20-iteration exhaustive loops at
                                             launches: 60 k / 120 k / 250 k exhaustive (20 iterations; 250 k is multi-slice: the first arm falls back to
                                             the second) and hw9's 4 000 points with the grid (800 iterations); median and spread (max - min) over reps;
                                             at 120 k also 256-thread workgroups (icp_fused_sums_threads); at every exhaustive size the six geometries
-                                            of the sums + solve launch (icp_sums_solve_threads 256 / 512 x icp_sums_solve_pairs 1 / 2 / 4)
+                                            of the sums + solve launch (icp_sums_solve_threads 256 / 512 x icp_sums_solve_pairs 1 / 2 / 4; DESIGN.md 6i);
+                                            at every exhaustive size the default geometry with the state snapshots copied on the stream / written by the
+                                            kernel (icp_host_snapshots 2 / 1) x one arrival counter / one per replica (icp_ticket_levels 1 / 2)
        run_icp_tail.py stamps [n]           profile build (tools/ab_build.sh fsprof kabsch.hip -DPCR_FS_PROF; PCR_LIB_PATH=.../libpcr_fsprof.so): per workgroup
                                             the time from its row store to the end of its wait at the grid barrier, last iteration of a 20-iteration loop
        run_icp_tail.py ss_stamps [n] [T:P,...]   profile build (tools/ab_build.sh ssprof kabsch.hip -DPCR_SS_PROF; PCR_LIB_PATH=.../libpcr_ssprof.so): the sums +
                                             solve launch of the chain search -> sums + solve, last iteration of a 20-iteration loop, per geometry (threads :
-                                            pairs): per workgroup entry -> totals ready and totals ready -> ticket returned; for the last arriver ticket ->
-                                            sums reduced -> solved -> published
+                                            pairs) and per ticket form (icp_ticket_levels 1 / 2): per workgroup entry -> totals ready and totals ready ->
+                                            ticket returned; for the last arriver ticket -> sums reduced -> solved -> published -> snapshot in host memory
+                                            (the last launch of a call writes one unless icp_host_snapshots = 2)
 PCR_TUNE="key=value,..." sets any other knob."""
 import importlib, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -57,35 +60,46 @@ elif mode == "ss_stamps":
     ctx.tune("grid_stats", 1)
     for threads, pairs in geoms:
         ctx.tune("icp_sums_solve_threads", threads); ctx.tune("icp_sums_solve_pairs", pairs)
-        for _ in range(3):
-            ctx.icp_point2point(cs, ct, max_corr=1.0, max_iter=20, eps=0.0)
-            w = ctx.nn1_stats(); k = max(w[14], 1)
-            print(f"n={n} threads {threads} pairs {pairs} chain {ctx.icp_last_chain()}: workgroups {w[14]}; entry -> totals ready: mean {w[12] / k / 100:.2f} us; "
-                  f"totals ready -> ticket returned: mean {w[13] / k / 100:.2f} us, longest {w[15] / 100:.2f} us; last arriver: ticket -> sums reduced "
-                  f"{w[0] / 100:.2f} us (acquired {w[2] / 100:.2f}, replicas in LDS {w[3] / 100:.2f}), -> solved {w[1] / 100:.2f} us, -> published {w[11] / 100:.2f} us")
+        for levels in (1, 2):
+            ctx.tune("icp_ticket_levels", levels)
+            for _ in range(3):
+                ctx.icp_point2point(cs, ct, max_corr=1.0, max_iter=20, eps=0.0)
+                w = ctx.nn1_stats(); k = max(w[14], 1)
+                print(f"n={n} threads {threads} pairs {pairs} ticket levels {levels} chain {ctx.icp_last_chain()} snapshots {ctx.icp_last_snapshots()}: workgroups {w[14]}; "
+                      f"entry -> totals ready: mean {w[12] / k / 100:.2f} us; "
+                      f"totals ready -> ticket returned: mean {w[13] / k / 100:.2f} us, longest {w[15] / 100:.2f} us; last arriver: ticket -> sums reduced "
+                      f"{w[0] / 100:.2f} us (acquired {w[2] / 100:.2f}, replicas in LDS {w[3] / 100:.2f}), -> solved {w[1] / 100:.2f} us, -> published {w[11] / 100:.2f} us, "
+                      f"-> snapshot {w[4] / 100:.2f} us")
 else:
     reps = int(sys.argv[2]) if len(sys.argv) > 2 else 8
-    # an arm: (icp_move_in_search, icp_fused_sums, icp_fused_sums_threads, icp_sums_solve_threads, icp_sums_solve_pairs)
-    MV, FS, TL = (1, 1, 512, 0, 0), (2, 1, 512, 0, 0), (2, 2, 512, 0, 0)
-    GEO = tuple((1, 1, 512, t, p) for t in (512, 256) for p in (4, 2, 1))
-    for n, method, iters, arms in ((60000, 1, 20, (MV, FS, TL) + GEO), (120000, 1, 20, (MV, FS, TL, (2, 1, 256, 0, 0)) + GEO),
-                                   (250000, 1, 20, (MV, FS, TL) + GEO), (4000, 2, 800, (FS, TL))):
+    # an arm: (icp_move_in_search, icp_fused_sums, icp_fused_sums_threads, icp_sums_solve_threads, icp_sums_solve_pairs, icp_host_snapshots, icp_ticket_levels)
+    KEYS = ("icp_move_in_search", "icp_fused_sums", "icp_fused_sums_threads", "icp_sums_solve_threads", "icp_sums_solve_pairs", "icp_host_snapshots", "icp_ticket_levels")
+    MV, FS, TL = (1, 1, 512, 0, 0, 0, 0), (2, 1, 512, 0, 0, 0, 0), (2, 2, 512, 0, 0, 0, 0)
+    GEO = tuple((1, 1, 512, t, p, 0, 0) for t in (512, 256) for p in (4, 2, 1))
+    SNAP = tuple((1, 1, 512, 0, 0, s_, l_) for s_ in (2, 1) for l_ in (1, 2))
+    GRID = (FS, TL)                               # (the control: the grid loop takes neither the move in the search nor what rides on it)
+    CHAINS = (MV, FS, TL)
+    if os.environ.get("PCR_AB_SNAP_ONLY"):        # (a short visit: the default chain and the four snapshot / ticket arms alone)
+        GEO, CHAINS = (), (MV,)
+    for n, method, iters, arms in ((60000, 1, 20, CHAINS + SNAP + GEO), (120000, 1, 20, CHAINS + ((2, 1, 256, 0, 0, 0, 0),) + SNAP + GEO),
+                                   (250000, 1, 20, CHAINS + SNAP + GEO), (4000, 2, 800, GRID)):
         cs, ct = pair(n); ctx.tune("nn_method", method)
         us = {a: [] for a in arms}
         poses, chains = {}, {}
         for r in range(reps + 1):                      # (the first round warms up: indexes, spare buffers)
             for a in arms:
-                for k_, v_ in zip(("icp_move_in_search", "icp_fused_sums", "icp_fused_sums_threads", "icp_sums_solve_threads", "icp_sums_solve_pairs"), a):
+                for k_, v_ in zip(KEYS, a):
                     ctx.tune(k_, v_)
                 t0 = time.perf_counter()
                 T, st = ctx.icp_point2point(cs, ct, max_corr=1.0, max_iter=iters, eps=0.0)
                 dt = time.perf_counter() - t0
                 if r: us[a].append(dt / max(st["iters_run"], 1) * 1e6)
-                poses[a] = T.view(np.uint32).tobytes(); chains[a] = ctx.icp_last_chain()
+                poses[a] = T.view(np.uint32).tobytes(); chains[a] = (ctx.icp_last_chain(), ctx.icp_last_snapshots())
         same = all(p == poses[arms[0]] for p in poses.values())
         for a in arms:
             v = np.array(us[a])
-            print(f"n={n} method={method} iterations={iters} icp_move_in_search={a[0]} icp_fused_sums={a[1]} threads={a[2]} solve threads={a[3]} pairs={a[4]} chain {chains[a]}: "
+            print(f"n={n} method={method} iterations={iters} icp_move_in_search={a[0]} icp_fused_sums={a[1]} threads={a[2]} solve threads={a[3]} pairs={a[4]} "
+                  f"host snapshots={a[5]} ticket levels={a[6]} chain {chains[a][0]} snapshots {chains[a][1]}: "
                   f"median {np.median(v):.2f} us/iteration, spread {v.max() - v.min():.2f} "
                   f"(min {v.min():.2f}, max {v.max():.2f}; {reps} calls); pose bits equal: {same}")
         cs.free(); ct.free()
