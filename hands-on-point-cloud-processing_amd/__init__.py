@@ -102,6 +102,11 @@ class Pn2Info(C.Structure):
                 ("c_last", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class Pn2TrainInfo(C.Structure):
+    _fields_ = [("n_weights", C.c_uint64), ("device_bytes", C.c_uint64), ("keep_per_object", C.c_uint64), ("chunk_rows", C.c_uint32), ("n_class", C.c_uint32),
+                ("n_sampling", C.c_uint32), ("reserved", C.c_uint32), ("dropout_p", C.c_double), ("bn_momentum", C.c_double)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_int)
 
 # every symbol include/pcr.h declares (checked by tests/test_abi.py against the header text)
@@ -121,6 +126,7 @@ ABI_SYMBOLS = [
     "pcr_pn2_model_create", "pcr_pn2_model_destroy", "pcr_pn2_model_info", "pcr_sa_mlp_max_f32", "pcr_pn2_forward_f32",
     "pcr_pn2_msg_model_create", "pcr_pn2_msg_model_info", "pcr_ball_query_multi_f32", "pcr_sa_msg_mlp_max_f32",
     "pcr_pn1_model_create", "pcr_pn1_model_info", "pcr_pointwise_chain_max_f32", "pcr_pointnet_forward_f32",
+    "pcr_pn2_trainer_create", "pcr_pn2_trainer_destroy", "pcr_pn2_trainer_info", "pcr_pn2_trainer_set_weights", "pcr_pn2_trainer_get_weights", "pcr_pn2_train_grad_f32",
     "pcr_mat64_create", "pcr_mat64_destroy", "pcr_mat64_info", "pcr_kmeans_step_f64", "pcr_kmeans_fit_f64", "pcr_kmeans_predict_f64", "pcr_kmeanspp_init_f64",
     "pcr_gmm_em_step_f64", "pcr_gmm_fit_f64", "pcr_gmm_predict_f64",
     "pcr_mat64_knn_f64", "pcr_spectral_graph_f64", "pcr_spgraph_info", "pcr_spgraph_read", "pcr_spgraph_destroy", "pcr_eig_small_f64",
@@ -248,6 +254,12 @@ def lib():
     L.pcr_pn1_model_info.argtypes = [vp, sz, C.POINTER(Pn2Info), C.POINTER(Pn1Desc)]
     L.pcr_pointwise_chain_max_f32.argtypes = [vp, vp, C.c_int, vp, vp, sz, vp, vp, vp, vp]
     L.pcr_pointnet_forward_f32.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp, vp]
+    L.pcr_pn2_trainer_create.argtypes = [vp, C.POINTER(Pn2Desc), vp, sz, C.c_double, C.c_double, C.c_uint32, C.POINTER(vp)]
+    L.pcr_pn2_trainer_destroy.argtypes = [vp, vp]
+    L.pcr_pn2_trainer_info.argtypes = [vp, sz, sz, C.POINTER(Pn2TrainInfo)]
+    L.pcr_pn2_trainer_set_weights.argtypes = [vp, vp, vp, sz, C.c_int]
+    L.pcr_pn2_trainer_get_weights.argtypes = [vp, vp, vp, sz]
+    L.pcr_pn2_train_grad_f32.argtypes = [vp, vp, vp, sz, sz, vp, vp, C.c_uint64, vp, C.POINTER(C.c_double), vp, vp]
     L.pcr_mat64_create.argtypes = [vp, vp, sz, C.c_int, C.POINTER(vp)]
     L.pcr_mat64_destroy.argtypes = [vp, vp]
     L.pcr_mat64_info.argtypes = [vp, C.POINTER(sz), ip, ip]
@@ -639,6 +651,79 @@ class Pn1Model(Pn2Model):
     def stage_width(self, stage: int) -> int:
         """the row width pcr_pointwise_chain_max_f32 writes for a stage"""
         return int(self.desc.widths[self.desc.n_mlp - 1]) if stage == 2 else int(self.desc.tnet_conv[2])
+
+
+class Pn2Trainer:
+    """The training pass of a PointNet++ (SSG) classifier resident in HBM (pcr_pn2_trainer): the raw weights and the running statistics live
+    on the device; train_grad runs the training-mode forward pass, the loss and the gradient of every parameter.  The contract is above
+    pcr_pn2_trainer_create in include/pcr.h.  desc: a Pn2Desc; weights: the flat f32 array of pcr_pn2_model_create, unfolded."""
+
+    def __init__(self, ctx: "Context", desc: Pn2Desc, weights, dropout_p: float = 0.4, bn_momentum: float = 0.1, chunk_rows: int = 0):
+        w = np.ascontiguousarray(weights, np.float32).reshape(-1)
+        h = C.c_void_p()
+        ctx._ck(lib().pcr_pn2_trainer_create(ctx.h, C.byref(desc), w.ctypes.data if w.size else None, w.size, float(dropout_p), float(bn_momentum), int(chunk_rows),
+                                             C.byref(h)))
+        self.ctx, self.h, self.desc = ctx, h, desc
+        ctx._handles.add(self)
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:   # noqa: BLE001
+            pass
+
+    def free(self):
+        if self.h and self.ctx.h:
+            lib().pcr_pn2_trainer_destroy(self.ctx.h, self.h)
+        self.h = None
+
+    def info(self, n_obj: int = 0, npts: int = 0) -> dict:
+        i = Pn2TrainInfo()
+        self.ctx._ck(lib().pcr_pn2_trainer_info(self.h, int(n_obj), int(npts), C.byref(i)))
+        return {"n_weights": int(i.n_weights), "device_bytes": int(i.device_bytes), "keep_per_object": int(i.keep_per_object), "chunk_rows": int(i.chunk_rows),
+                "n_class": int(i.n_class), "n_sampling": int(i.n_sampling), "dropout_p": float(i.dropout_p), "bn_momentum": float(i.bn_momentum)}
+
+    def sampling_npoints(self):
+        return [int(self.desc.sa[l].npoint) for l in range(self.desc.n_sa) if not self.desc.sa[l].group_all]
+
+    def set_weights(self, weights, keep_running_stats: bool = False):
+        w = np.ascontiguousarray(weights, np.float32).reshape(-1)
+        self.ctx._ck(lib().pcr_pn2_trainer_set_weights(self.ctx.h, self.h, w.ctypes.data if w.size else None, w.size, 1 if keep_running_stats else 0))
+
+    def get_weights(self):
+        w = np.zeros(self.info()["n_weights"], np.float32)
+        self.ctx._ck(lib().pcr_pn2_trainer_get_weights(self.ctx.h, self.h, w.ctypes.data, w.size))
+        return w
+
+    def train_grad(self, objects, target, starts=None, seed: int = 0, keep=None):
+        """objects f32 [n_obj, npts, 3 + D0], target int [n_obj] -> (loss float, logp f32 [n_obj, n_class], grad f32 [n_weights]); the contract
+        of pcr_pn2_train_grad_f32.  starts: [n_sampling_layers, n_obj] first picks, None = drawn from the seed; keep: the dropout masks as
+        bytes, [n_obj * keep_per_object] layer after layer, None = drawn from the seed."""
+        obj = np.ascontiguousarray(objects, np.float32)
+        if obj.ndim != 3 or obj.shape[2] != 3 + int(self.desc.D0):
+            raise PcrError("objects: [n_obj, npts, 3 + D0]")
+        n_obj, npts = obj.shape[0], obj.shape[1]
+        inf = self.info()
+        tg = np.ascontiguousarray(target, np.int32).reshape(-1)
+        if tg.size != n_obj:
+            raise PcrError("target: one class per object")
+        st = None
+        if starts is not None:
+            st = np.ascontiguousarray(starts, np.uint32).reshape(-1)
+            if st.size != inf["n_sampling"] * n_obj:
+                raise PcrError("starts: one first pick per sampling layer and object")
+        kp = None
+        if keep is not None:
+            kp = np.ascontiguousarray(np.asarray(keep) != 0, np.uint8).reshape(-1)
+            if kp.size != inf["keep_per_object"] * n_obj:
+                raise PcrError("keep: one byte per object and unit of every FC layer but the last")
+        loss = C.c_double(0.0)
+        logp = np.zeros((max(n_obj, 1), inf["n_class"]), np.float32)
+        grad = np.zeros(inf["n_weights"], np.float32)
+        self.ctx._ck(lib().pcr_pn2_train_grad_f32(self.ctx.h, self.h, obj.ctypes.data if obj.size else None, n_obj, npts, tg.ctypes.data if tg.size else None,
+                                                  None if st is None or not st.size else st.ctypes.data, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                                  None if kp is None or not kp.size else kp.ctypes.data, C.byref(loss), logp.ctypes.data, grad.ctypes.data))
+        return float(loss.value), logp[:n_obj], grad
 
 
 class Mat64:
@@ -1471,6 +1556,10 @@ class Context:
         """desc: a Pn2Desc (pn2_desc(...)); weights: the flat f32 array in the order include/pcr.h states (pointnet.flat_weights builds it
         from a state dict).  BN is folded at upload."""
         return Pn2Model(self, desc, weights)
+
+    def pn2_trainer(self, desc, weights, dropout_p: float = 0.4, bn_momentum: float = 0.1, chunk_rows: int = 0) -> Pn2Trainer:
+        """The training pass of the model a Pn2Desc describes (pcr_pn2_trainer_create): weights as pn2_model takes them, kept unfolded."""
+        return Pn2Trainer(self, desc, weights, dropout_p, bn_momentum, chunk_rows)
 
     def sa_mlp_max(self, model: Pn2Model, layer: int, cloud: Cloud, seg_ptr, centres=None, centre_seg_ptr=None, idx=None, features=None):
         """The fused set-abstraction kernel alone: gather + centre + MLP chain + max per group -> f32 [rows, C_out]; the contract of

@@ -1,0 +1,302 @@
+"""HomeworkFinal's training step for the PointNet++ (SSG) classifier on the GPU: training-mode forward pass, get_loss and the gradient of
+every parameter (HomeworkFinal/train_cls.py:186-196 without its optimiser; models/pointnet2_cls_ssg.py).
+
+  Trainer       the model in training mode on the library (pcr_pn2_train_grad_f32; the contract is above pcr_pn2_trainer_create in include/pcr.h)
+  get_loss      models/pointnet2_cls_ssg.get_loss: the same call, (pred, target, trans_feat) -> the mean negative log-likelihood
+
+The optimiser stays torch's own, on host tensors, exactly as train_cls.py:147-153 builds it:
+
+    tr = Trainer(num_class)
+    opt = torch.optim.Adam(tr.torch_parameters(), lr=1e-3, betas=(0.9, 0.999), eps=1e-08, weight_decay=1e-4)
+    sched = torch.optim.lr_scheduler.StepLR(opt, step_size=20, gamma=0.7)
+    for points, target in loader:                  # points [B, 3 | 6, N]
+        opt.zero_grad()                            # (optional: step_grad overwrites every .grad)
+        loss, logp = tr.step_grad(points, target)
+        opt.step()
+        tr.sync()                                  # the stepped weights go to the device; the running statistics stay the device's
+    classifier = tr.eval_model()                   # a pointnet.get_model in eval mode with the trained weights and running statistics
+
+What is unpinned: the first FPS picks (start= fixes them) and the dropout masks (keep= fixes them); without them both are drawn from `seed`,
+or from np.random where no seed is given, as the reference draws them from torch's stream.  pointnet.get_model is unchanged: its train() raises.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from .pointnet import _BN_KEYS, _SSG_FC, _SSG_SA, _ctx, _like, _to_host, get_model
+
+_PARAM_BN = ("weight", "bias")
+
+
+class _DescModel(get_model):
+    """pointnet.get_model for the layers and the descriptor of a Trainer.from_desc"""
+
+    def __init__(self, num_class, desc, layers):
+        super().__init__(num_class, int(desc.D0) == 3)
+        self._d, self._l = desc, layers
+        nps = [int(desc.sa[l].npoint) for l in range(desc.n_sa) if not desc.sa[l].group_all]
+        self._npoint1 = nps[0] if nps else 1
+
+    def _layers(self):
+        return list(self._l)
+
+    def desc(self):
+        return self._d
+
+    def state_shapes(self):
+        out = {}
+        for conv, bn, w, cin in self._l:
+            out[f"{conv}.weight"] = (w, cin, 1, 1) if "mlp_convs" in conv else (w, cin)
+            out[f"{conv}.bias"] = (w,)
+            for k in (_BN_KEYS if bn else ()):
+                out[f"{bn}.{k}"] = (w,)
+        return out
+
+
+def _desc_layers(desc, names):
+    """(conv / linear prefix, BN prefix or None, out, in) in weight order for a Pn2Desc and one (conv, bn) pair of names per layer"""
+    shapes, D = [], int(desc.D0)
+    for l in range(desc.n_sa):
+        cin = 3 + D
+        for i in range(desc.sa[l].n_mlp):
+            shapes.append((int(desc.sa[l].widths[i]), cin, True))
+            cin = int(desc.sa[l].widths[i])
+        D = cin
+    cin = D
+    for i in range(desc.n_fc):
+        shapes.append((int(desc.fc_widths[i]), cin, i + 1 < desc.n_fc))
+        cin = int(desc.fc_widths[i])
+    names = list(names)
+    if len(names) != len(shapes):
+        raise ValueError(f"names: one (conv, bn) pair per layer, the descriptor has {len(shapes)}")
+    out = []
+    for (conv, bn), (w, cin, has_bn) in zip(names, shapes):
+        if has_bn != (bn is not None):
+            raise ValueError(f"names: layer {conv} {'has' if has_bn else 'has no'} BatchNorm")
+        out.append((conv, bn, w, cin))
+    return out
+
+
+class Trainer:
+    """The reference's pointnet2_cls_ssg.get_model in TRAINING mode on the library.  Trainer(num_class, normal_channel, dropout, momentum,
+    chunk_rows, ctx) is the reference's architecture; Trainer.from_desc(desc, names) any Pn2Desc (names: one (conv prefix, BN prefix or None) per
+    layer in weight order).  Fresh weights follow torch's default initialisation rule (uniform in +-1 / sqrt(fan_in); gamma 1, beta 0), drawn
+    from np.random.default_rng(seed); load_state_dict / state_dict use the reference's keys, the running statistics come from the device and
+    num_batches_tracked is counted.  chunk_rows is part of the arithmetic contract (include/pcr.h): 0 = the library's default."""
+
+    def __init__(self, num_class, normal_channel=False, dropout=0.4, momentum=0.1, chunk_rows=0, ctx=None, *, seed=0):
+        from . import pn2_desc
+        self.num_class, self.normal_channel = int(num_class), bool(normal_channel)
+        proto = get_model(self.num_class, self.normal_channel)
+        self._setup(proto.desc(), proto._layers(), dropout, momentum, chunk_rows, ctx, seed)
+        self._generic = False
+
+    @classmethod
+    def from_desc(cls, desc, names, dropout=0.4, momentum=0.1, chunk_rows=0, ctx=None, *, seed=0):
+        self = cls.__new__(cls)
+        self.num_class, self.normal_channel = int(desc.fc_widths[desc.n_fc - 1]), int(desc.D0) == 3
+        self._setup(desc, _desc_layers(desc, names), dropout, momentum, chunk_rows, ctx, seed)
+        self._generic = True
+        return self
+
+    def _setup(self, desc, layers, dropout, momentum, chunk_rows, ctx, seed):
+        self._desc, self._layer_list = desc, layers
+        self.dropout, self.momentum, self.chunk_rows = float(dropout), float(momentum), int(chunk_rows)
+        self._ctx_arg, self._trainer, self._trainer_ctx = ctx, None, None
+        self._dirty = True                   # the host weights (running statistics included) are newer than the device's
+        self._slots, off = {}, 0             # key -> (offset, shape) into the flat array
+        for conv, bn, w, cin in layers:
+            self._slots[f"{conv}.weight"] = (off, (w, cin, 1, 1) if "mlp_convs" in conv else (w, cin))
+            off += w * cin
+            self._slots[f"{conv}.bias"] = (off, (w,))
+            off += w
+            for k in (_BN_KEYS if bn else ()):
+                self._slots[f"{bn}.{k}"] = (off, (w,))
+                off += w
+        self._flat = np.zeros(off, np.float32)
+        self._gflat = np.zeros(off, np.float32)
+        self._tracked = {bn: 0 for _, bn, _, _ in layers if bn}
+        self._params = None
+        rng = np.random.default_rng(seed)
+        for conv, bn, w, cin in layers:
+            bound = 1.0 / np.sqrt(cin)
+            self._view(f"{conv}.weight")[...] = rng.uniform(-bound, bound, self._slots[f"{conv}.weight"][1])
+            self._view(f"{conv}.bias")[...] = rng.uniform(-bound, bound, w)
+            if bn:
+                self._view(f"{bn}.weight")[...] = 1.0
+                self._view(f"{bn}.running_var")[...] = 1.0
+
+    def _view(self, key, flat=None):
+        off, shape = self._slots[key]
+        return (self._flat if flat is None else flat)[off:off + int(np.prod(shape))].reshape(shape)
+
+    def param_keys(self):
+        """the keys of named_parameters(), in the reference's order per layer: weight, bias, then the BN's weight, bias"""
+        out = []
+        for conv, bn, _, _ in self._layer_list:
+            out += [f"{conv}.weight", f"{conv}.bias"] + ([f"{bn}.{k}" for k in _PARAM_BN] if bn else [])
+        return out
+
+    # ---- the device trainer
+    def trainer(self, ctx=None):
+        ctx = _ctx(ctx if ctx is not None else self._ctx_arg)
+        if self._trainer is None or self._trainer_ctx is not ctx or not self._trainer.h:
+            if self._trainer is not None:
+                self._pull_running()
+                self._trainer.free()
+            self._trainer, self._trainer_ctx = ctx.pn2_trainer(self._desc, self._flat, self.dropout, self.momentum, self.chunk_rows), ctx
+            self._dirty = False
+        elif self._dirty:
+            self._trainer.set_weights(self._flat, keep_running_stats=False)
+            self._dirty = False
+        return self._trainer
+
+    def _pull_running(self):
+        if self._trainer is None or not self._trainer.h or self._dirty:
+            return
+        dev = self._trainer.get_weights()
+        for _, bn, _, _ in self._layer_list:
+            if bn:
+                for k in ("running_mean", "running_var"):
+                    self._view(f"{bn}.{k}")[...] = self._view(f"{bn}.{k}", dev)
+
+    def info(self, n_obj=0, npts=0):
+        return self.trainer().info(n_obj, npts)
+
+    # ---- state
+    def state_dict(self):
+        self._pull_running()
+        out = {}
+        for conv, bn, _, _ in self._layer_list:
+            out[f"{conv}.weight"] = self._view(f"{conv}.weight").copy()
+            out[f"{conv}.bias"] = self._view(f"{conv}.bias").copy()
+            if bn:
+                for k in _BN_KEYS:
+                    out[f"{bn}.{k}"] = self._view(f"{bn}.{k}").copy()
+                out[f"{bn}.num_batches_tracked"] = np.int64(self._tracked[bn])
+        return out
+
+    def load_state_dict(self, state, strict=True):
+        seen = set()
+        for key, (off, shape) in self._slots.items():
+            if key not in state:
+                raise KeyError(f"missing key in state_dict: {key}")
+            a = np.asarray(_to_host(state[key])[0], np.float32)
+            if a.size != int(np.prod(shape)) or (a.ndim >= 1 and a.shape[0] != shape[0]):
+                raise ValueError(f"size mismatch for {key}: {a.shape}, the model takes {shape}")
+            self._view(key)[...] = a.reshape(shape)
+            seen.add(key)
+        for bn in self._tracked:
+            k = f"{bn}.num_batches_tracked"
+            self._tracked[bn] = int(np.asarray(_to_host(state[k])[0])) if k in state else 0
+            seen.add(k)
+        if strict:
+            extra = [k for k in state if k not in seen]
+            if extra:
+                raise KeyError(f"unexpected keys in state_dict: {extra}")
+        self._dirty = True
+        return self
+
+    # ---- the step
+    def step_grad(self, points, target, start=None, seed=None, keep=None, *, ctx=None):
+        """points [B, 3 | 6, N], target [B] or [B, 1] -> (loss, logp [B, num_class]), numpy / float or torch like `points`; every gradient is
+        left in grads() and in the .grad of torch_parameters().  start: [n_sampling_layers, B] first FPS picks; keep: the dropout masks, one
+        [B, width] array per FC layer but the last (or their concatenation); seed: draws whichever of the two is not given."""
+        x, proto = _to_host(points)
+        C0 = 3 + int(self._desc.D0)
+        if x.ndim != 3 or x.shape[1] != C0:
+            raise ValueError(f"points: [B, {C0}, N]")
+        B, N = x.shape[0], x.shape[2]
+        tg = np.asarray(_to_host(target)[0]).reshape(-1)
+        st, _ = _to_host(start)
+        tr = self.trainer(ctx)
+        if seed is None:
+            seed = int(np.random.randint(0, 2 ** 31 - 1))
+            if st is None:
+                sizes = [N] + tr.sampling_npoints()[:-1]
+                st = np.stack([np.random.randint(0, n, size=B) for n in sizes]) if tr.sampling_npoints() else None
+        if keep is not None and isinstance(keep, (list, tuple)):
+            keep = np.concatenate([np.asarray(_to_host(k)[0]).reshape(-1) for k in keep])
+        elif keep is not None:
+            keep = np.asarray(_to_host(keep)[0]).reshape(-1)
+        loss, logp, grad = tr.train_grad(np.ascontiguousarray(np.transpose(x, (0, 2, 1)), np.float32), tg, st, seed, keep)
+        if B:
+            self._gflat[...] = grad
+            for bn in self._tracked:
+                self._tracked[bn] += 1
+        if proto is None:
+            return loss, logp
+        import torch
+        return torch.tensor(loss, dtype=proto.dtype, device=proto.device), _like(logp, proto)
+
+    def grads(self):
+        """key -> the gradient of the last step_grad in the reference's shape, for every key of named_parameters()"""
+        return {k: self._view(k, self._gflat).copy() for k in self.param_keys()}
+
+    def torch_parameters(self):
+        """host torch tensors that SHARE the trainer's weights, in named_parameters() order, each with a .grad that shares the trainer's
+        gradient: an optimiser's step() changes the trainer's host weights in place; sync() then uploads them"""
+        import torch
+        if self._params is None:
+            self._params = []
+            for k in self.param_keys():
+                p = torch.from_numpy(self._view(k)).requires_grad_(True)
+                p.grad = torch.from_numpy(self._view(k, self._gflat))
+                self._params.append(p)
+        else:
+            for k, p in zip(self.param_keys(), self._params):      # zero_grad(set_to_none=True) drops the link: restore it
+                if p.grad is None or p.grad.data_ptr() != self._view(k, self._gflat).ctypes.data:
+                    p.grad = torch.from_numpy(self._view(k, self._gflat))
+        return self._params
+
+    def sync(self, *, ctx=None):
+        """the host weights (after optimizer.step()) -> the device; the running statistics stay the device's"""
+        if self._trainer is None or not self._trainer.h or self._dirty:
+            self.trainer(ctx)
+            return self
+        self._trainer.set_weights(self._flat, keep_running_stats=True)
+        return self
+
+    def step(self, points, target, optimizer, **kw):
+        """zero_grad is not needed: step_grad -> relink the gradients -> optimizer.step() -> sync; returns step_grad's pair"""
+        out = self.step_grad(points, target, **kw)
+        self.torch_parameters()
+        optimizer.step()
+        self.sync()
+        return out
+
+    def eval_model(self):
+        """a pointnet.get_model in eval mode loaded with the current weights and running statistics"""
+        m = _DescModel(self.num_class, self._desc, self._layer_list) if self._generic else get_model(self.num_class, self.normal_channel)
+        m.load_state_dict(self.state_dict(), strict=True)
+        return m.eval()
+
+    def train(self, mode=True):
+        return self
+
+    def free(self):
+        if self._trainer is not None:
+            self._pull_running()
+            self._trainer.free()
+        self._trainer, self._trainer_ctx = None, None
+        self._dirty = True
+
+
+class get_loss:
+    """models/pointnet2_cls_ssg.get_loss: (pred [B, num_class] log-probabilities, target [B], trans_feat ignored) -> the mean of
+    -pred[b, target[b]] (F.nll_loss), a float for numpy input, a tensor like pred for torch input.  The sum runs in f64 over ascending b."""
+
+    def forward(self, pred, target, trans_feat=None):
+        p, proto = _to_host(pred)
+        t = np.asarray(_to_host(target)[0]).reshape(-1).astype(np.int64)
+        p = np.asarray(p, np.float64)
+        s = 0.0
+        for b in range(p.shape[0]):
+            s += p[b, t[b]]
+        loss = -s / max(p.shape[0], 1)
+        if proto is None:
+            return float(loss)
+        import torch
+        return torch.tensor(loss, dtype=proto.dtype, device=proto.device)
+
+    __call__ = forward

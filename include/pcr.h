@@ -839,6 +839,70 @@ int pcr_pointwise_chain_max_f32(pcr_ctx* ctx, const pcr_pn2_model* model, int st
 int pcr_pointnet_forward_f32(pcr_ctx* ctx, const pcr_pn2_model* model, const float* objects, size_t n_obj, size_t npts, float* logp, int32_t* pred,
                              float* global_feat, float* trans, float* trans_feat);
 
+/* ---- HomeworkFinal: the PointNet++ (SSG) TRAINING pass, train_cls.py's step without its optimiser: training-mode forward, get_loss
+ * (pointnet2_cls_ssg.py:50-52) and the gradient of every parameter.  The optimiser stays the caller's (torch.optim.Adam on host tensors).
+ * A trainer is made from a pcr_pn2_desc (any model it can describe whose last SA layer is group_all) and the flat weight array of
+ * pcr_pn2_model_create, UNFOLDED: the trainer keeps W, bias, gamma, beta, running_mean, running_var as they are given.
+ * pcr_pn2_train_grad_f32 runs, for n_obj >= 2 objects of npts points (objects as pcr_pn2_forward_f32 takes them) and int32 target[n_obj]:
+ *   Sampling   FPS and ball query exactly as in pcr_pn2_forward_f32, the same starts / seed rule.  No gradient flows through either.
+ *   Rows       an SA layer's rows are the PADDED rows, centres x nsample, the copies that pad a ball included (torch's statistics count them);
+ *              the group_all layer has one row per point.  A row's input is (xyz - centre in one f32 subtraction | the features), xyz as it
+ *              is for group_all.
+ *   Product    z[n] = the k-ascending fma chain from the bias of pcr_pn2_model_create's contract, on the raw W, b.
+ *   BatchNorm  training mode, over the M rows of the layer (the head: M = n_obj): mu = sum z / M, var = sum (z - mu)^2 / M (biased), both
+ *              accumulated in f64 (below); rstd = 1 / sqrt(var + eps) in f64; y = (z - mu) rstd gamma + beta evaluated in f64 from the f32 z
+ *              and rounded ONCE.  running_mean <- (1 - m) running_mean + m mu, running_var <- (1 - m) running_var + m var M / (M - 1), in
+ *              f64, rounded once to f32; m = bn_momentum (torch: 0.1).  M == 1 is PCR_ERR_ARG, as torch refuses it.
+ *   ReLU, max  relu(v) = v > 0 ? v : +0; the max over a group is taken after it; its gradient goes to the LOWEST member position among the
+ *              maxima (copies tie exactly and carry the same input row, so no parameter gradient depends on the choice); a max of 0 passes nothing.
+ *   Head       FC -> BN -> ReLU -> dropout for every FC layer but the last.  dropout: a = y s where keep != 0, +0 elsewhere, s = f32(1 / (1 - p)),
+ *              one f32 product.  keep (optional): bytes, one per object and unit, layer after layer ([n_obj][fc_widths[0]], [n_obj][fc_widths[1]] ...).
+ *              NULL: keep[layer i][cell e] = (K(seed, (0x100 + i) << 32 | e) >> 11) 2^-53 >= p with the SplitMix keying above.  UNPINNED: torch's stream.
+ *   Loss       log_softmax of the last FC layer as in pcr_pn2_forward_f32; loss = -(1 / n_obj) sum_b logp[b][target[b]], ascending b, in f64.
+ *   Backward   dlogits = (exp(logp) - onehot) / n_obj (f64, rounded once).  Dropout: the same mask and s.  ReLU passes where y > 0.  BN, with
+ *              gy the gradient at y: dbeta = sum gy, dgamma = sum gy xhat, xhat = (z - mu) rstd,
+ *              dz = rstd gamma (gy - dbeta / M - xhat dgamma / M), in f64, rounded once.  dW = dz^T x, dx = dz W (one f32 fma chain from +0
+ *              over ascending output channel).  The gradient of a layer's input features goes back to the point each row read, summed in
+ *              f64 over the rows that read that point, rows ascending, rounded once; the xyz columns are dropped.  The bias of a layer that BN
+ *              follows has a gradient that is analytically zero: the library writes +0 there and does not compute it.  The last FC layer's
+ *              bias gradient is the column sum of dlogits.
+ *   Order      No floating-point atomic anywhere.  Every sum over the rows of a layer (mu, var, dbeta, dgamma, the last bias, dW) runs over
+ *              consecutive chunks of chunk_rows rows: rows ascending inside a chunk, then the chunk partials added in ascending order; in f64
+ *              for the statistics, dbeta, dgamma and the bias, in f32 for dW (one fma chain from +0 per chunk on v_mfma_f32_16x16x4_f32, the
+ *              partials added in f32).  chunk_rows is a creation parameter (0 = 256), reported by pcr_pn2_trainer_info, and the ONLY thing
+ *              besides the inputs the bits may depend on: pn2_rows, every other tune key, the launch geometry and a repeat of the call give
+ *              the same bits.  With chunk_rows >= the rows of every layer each sum is one chunk.
+ *   Outputs    loss (f64), logp n_obj x n_class, grad: n_weights floats in the weight layout, +0 in the running_mean / running_var slots and
+ *              in the pre-BN biases.  The trainer's own running statistics advance once per call, on the device.
+ * pcr_pn2_trainer_set_weights replaces the weights (keep_running_stats != 0: all but the running statistics, which stay the device's);
+ * pcr_pn2_trainer_get_weights reads them back, the updated running statistics included.  pcr_pn2_trainer_info: device_bytes is what a call
+ * with n_obj objects of npts points takes (0 when either is 0); keep_per_object the length of an object's part of `keep`, summed over layers.
+ * PCR_ERR_ARG: NULL arguments; everything pcr_pn2_model_create / pcr_pn2_forward_f32 refuse; n_obj == 1; a layer with one row; a target outside
+ *   [0, n_class); dropout_p outside [0, 1); bn_momentum outside [0, 1]; a last SA layer that is not group_all; a non-finite input or weight;
+ *   more than 65535 chunks or 2^21 rows in a layer.  n_obj == 0: PCR_OK, nothing written, the running statistics untouched.
+ * Profile names pn2t_gather, pn2t_centres, pn2t_gemm_fwd, pn2t_stat, pn2t_bn_relu, pn2t_max, pn2t_loss, pn2t_max_back, pn2t_bn_back,
+ *   pn2t_gemm_dw, pn2t_dw_reduce, pn2t_gemm_dx, pn2t_gather_back (+ fps_small / fps_large, ball_query). */
+typedef struct pcr_pn2_trainer pcr_pn2_trainer;
+typedef struct pcr_pn2_train_info {
+    uint64_t n_weights;
+    uint64_t device_bytes;
+    uint64_t keep_per_object;
+    uint32_t chunk_rows;
+    uint32_t n_class;
+    uint32_t n_sampling;
+    uint32_t reserved;
+    double dropout_p;
+    double bn_momentum;
+} pcr_pn2_train_info;
+int pcr_pn2_trainer_create(pcr_ctx* ctx, const pcr_pn2_desc* desc, const float* weights, size_t n_weights, double dropout_p, double bn_momentum,
+                           uint32_t chunk_rows, pcr_pn2_trainer** out);
+int pcr_pn2_trainer_destroy(pcr_ctx* ctx, pcr_pn2_trainer* trainer);
+int pcr_pn2_trainer_info(const pcr_pn2_trainer* trainer, size_t n_obj, size_t npts, pcr_pn2_train_info* info);
+int pcr_pn2_trainer_set_weights(pcr_ctx* ctx, pcr_pn2_trainer* trainer, const float* weights, size_t n, int keep_running_stats);
+int pcr_pn2_trainer_get_weights(pcr_ctx* ctx, const pcr_pn2_trainer* trainer, float* weights, size_t n);
+int pcr_pn2_train_grad_f32(pcr_ctx* ctx, pcr_pn2_trainer* trainer, const float* objects, size_t n_obj, size_t npts, const int32_t* target,
+                           const uint32_t* starts, uint64_t seed, const uint8_t* keep, double* loss, float* logp, float* grad);
+
 /* ---- next row N4: global-registration front half, Homework9/hw9/src/registration.cpp:288-434, :535-615 -----------
  * N4a: exhaustive 1-NN between two descriptor sets (row-major n x dim / m x dim f32, host memory; dim 33 = FPFH),
  * nanoflann's evalMetric arithmetic for any dim (nanoflann.hpp:382-405: groups of four + tail, f32, unfused), canonical
