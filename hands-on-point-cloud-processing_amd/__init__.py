@@ -127,6 +127,7 @@ ABI_SYMBOLS = [
     "pcr_pn2_msg_model_create", "pcr_pn2_msg_model_info", "pcr_ball_query_multi_f32", "pcr_sa_msg_mlp_max_f32",
     "pcr_pn1_model_create", "pcr_pn1_model_info", "pcr_pointwise_chain_max_f32", "pcr_pointnet_forward_f32",
     "pcr_pn2_trainer_create", "pcr_pn2_trainer_destroy", "pcr_pn2_trainer_info", "pcr_pn2_trainer_set_weights", "pcr_pn2_trainer_get_weights", "pcr_pn2_train_grad_f32",
+    "pcr_pn1_trainer_create", "pcr_pointnet_train_grad_f32",
     "pcr_mat64_create", "pcr_mat64_destroy", "pcr_mat64_info", "pcr_kmeans_step_f64", "pcr_kmeans_fit_f64", "pcr_kmeans_predict_f64", "pcr_kmeanspp_init_f64",
     "pcr_gmm_em_step_f64", "pcr_gmm_fit_f64", "pcr_gmm_predict_f64",
     "pcr_mat64_knn_f64", "pcr_spectral_graph_f64", "pcr_spgraph_info", "pcr_spgraph_read", "pcr_spgraph_destroy", "pcr_eig_small_f64",
@@ -260,6 +261,8 @@ def lib():
     L.pcr_pn2_trainer_set_weights.argtypes = [vp, vp, vp, sz, C.c_int]
     L.pcr_pn2_trainer_get_weights.argtypes = [vp, vp, vp, sz]
     L.pcr_pn2_train_grad_f32.argtypes = [vp, vp, vp, sz, sz, vp, vp, C.c_uint64, vp, C.POINTER(C.c_double), vp, vp]
+    L.pcr_pn1_trainer_create.argtypes = [vp, C.POINTER(Pn1Desc), vp, sz, C.c_double, C.c_double, C.c_double, C.c_uint32, C.POINTER(vp)]
+    L.pcr_pointnet_train_grad_f32.argtypes = [vp, vp, vp, sz, sz, vp, C.c_uint64, vp, C.POINTER(C.c_double), vp, vp, vp, vp]
     L.pcr_mat64_create.argtypes = [vp, vp, sz, C.c_int, C.POINTER(vp)]
     L.pcr_mat64_destroy.argtypes = [vp, vp]
     L.pcr_mat64_info.argtypes = [vp, C.POINTER(sz), ip, ip]
@@ -724,6 +727,52 @@ class Pn2Trainer:
                                                   None if st is None or not st.size else st.ctypes.data, int(seed) & 0xFFFFFFFFFFFFFFFF,
                                                   None if kp is None or not kp.size else kp.ctypes.data, C.byref(loss), logp.ctypes.data, grad.ctypes.data))
         return float(loss.value), logp[:n_obj], grad
+
+
+class Pn1Trainer(Pn2Trainer):
+    """The training pass of a vanilla PointNet classifier resident in HBM (a pcr_pn2_trainer made by pcr_pn1_trainer_create); the contract is
+    above pcr_pn1_trainer_create in include/pcr.h.  desc: a Pn1Desc; weights: the flat f32 array of pcr_pn1_model_create, unfolded.  free, info,
+    set_weights and get_weights are Pn2Trainer's."""
+
+    def __init__(self, ctx: "Context", desc: Pn1Desc, weights, dropout_p: float = 0.4, bn_momentum: float = 0.1, reg_scale: float = 0.001, chunk_rows: int = 0):
+        w = np.ascontiguousarray(weights, np.float32).reshape(-1)
+        h = C.c_void_p()
+        ctx._ck(lib().pcr_pn1_trainer_create(ctx.h, C.byref(desc), w.ctypes.data if w.size else None, w.size, float(dropout_p), float(bn_momentum), float(reg_scale),
+                                             int(chunk_rows), C.byref(h)))
+        self.ctx, self.h, self.desc = ctx, h, desc
+        ctx._handles.add(self)
+
+    def sampling_npoints(self):
+        return []
+
+    def train_grad(self, objects, target, seed: int = 0, keep=None):
+        """objects f32 [n_obj, npts, 3 + D0], target int [n_obj] -> a dict: loss (the total), nll, reg (floats), logp f32 [n_obj, n_class], grad f32
+        [n_weights], trans [n_obj, 3, 3] and trans_feat [n_obj, K, K] (None without the T-Net); the contract of pcr_pointnet_train_grad_f32.
+        keep: the dropout mask as bytes, [n_obj, keep_per_object], None = drawn from the seed."""
+        obj = np.ascontiguousarray(objects, np.float32)
+        if obj.ndim != 3 or obj.shape[2] != 3 + int(self.desc.D0):
+            raise PcrError("objects: [n_obj, npts, 3 + D0]")
+        n_obj, npts = obj.shape[0], obj.shape[1]
+        inf = self.info()
+        tg = np.ascontiguousarray(target, np.int32).reshape(-1)
+        if tg.size != n_obj:
+            raise PcrError("target: one class per object")
+        kp = None
+        if keep is not None:
+            kp = np.ascontiguousarray(np.asarray(keep) != 0, np.uint8).reshape(-1)
+            if kp.size != inf["keep_per_object"] * n_obj:
+                raise PcrError("keep: one byte per object and unit of the last hidden FC layer")
+        K = int(self.desc.widths[0])
+        loss = (C.c_double * 3)(0.0, 0.0, 0.0)
+        logp = np.zeros((max(n_obj, 1), inf["n_class"]), np.float32)
+        grad = np.zeros(inf["n_weights"], np.float32)
+        trans = np.zeros((max(n_obj, 1), 3, 3), np.float32) if self.desc.stn3 else None
+        tfeat = np.zeros((max(n_obj, 1), K, K), np.float32) if self.desc.fstn else None
+        self.ctx._ck(lib().pcr_pointnet_train_grad_f32(self.ctx.h, self.h, obj.ctypes.data if obj.size else None, n_obj, npts, tg.ctypes.data if tg.size else None,
+                                                       int(seed) & 0xFFFFFFFFFFFFFFFF, None if kp is None or not kp.size else kp.ctypes.data, loss, logp.ctypes.data,
+                                                       None if trans is None else trans.ctypes.data, None if tfeat is None else tfeat.ctypes.data, grad.ctypes.data))
+        return {"loss": float(loss[0]), "nll": float(loss[1]), "reg": float(loss[2]), "logp": logp[:n_obj], "grad": grad,
+                "trans": None if trans is None else trans[:n_obj], "trans_feat": None if tfeat is None else tfeat[:n_obj]}
 
 
 class Mat64:
@@ -1560,6 +1609,10 @@ class Context:
     def pn2_trainer(self, desc, weights, dropout_p: float = 0.4, bn_momentum: float = 0.1, chunk_rows: int = 0) -> Pn2Trainer:
         """The training pass of the model a Pn2Desc describes (pcr_pn2_trainer_create): weights as pn2_model takes them, kept unfolded."""
         return Pn2Trainer(self, desc, weights, dropout_p, bn_momentum, chunk_rows)
+
+    def pn1_trainer(self, desc, weights, dropout_p: float = 0.4, bn_momentum: float = 0.1, reg_scale: float = 0.001, chunk_rows: int = 0) -> Pn1Trainer:
+        """The training pass of the model a Pn1Desc describes (pcr_pn1_trainer_create): weights as pn1_model takes them, kept unfolded."""
+        return Pn1Trainer(self, desc, weights, dropout_p, bn_momentum, reg_scale, chunk_rows)
 
     def sa_mlp_max(self, model: Pn2Model, layer: int, cloud: Cloud, seg_ptr, centres=None, centre_seg_ptr=None, idx=None, features=None):
         """The fused set-abstraction kernel alone: gather + centre + MLP chain + max per group -> f32 [rows, C_out]; the contract of

@@ -2,7 +2,8 @@
 // parameter (models/pointnet2_cls_ssg.py, get_loss :50-52; train_cls.py's step without its optimiser).  The contract is written out above
 // pcr_pn2_trainer_create in include/pcr.h.
 //
-// Batch statistics break the eval pass's layer fusion: the pass goes layer by layer and keeps every layer's z and y in HBM.
+// Batch statistics break the eval pass's layer fusion: the pass goes layer by layer and keeps every layer's z and y in HBM.  The kernels live in
+// pointnet_train_common.hpp, which the vanilla PointNet's pass (pointnet_train.hip) includes too:
 //   pn2t_gather        the padded rows of an SA layer: (xyz - centre | features) per row, and the point every row read
 //   pn2t_gemm_fwd      z = x W^T + b        one wave = 32 rows x 64 outputs on v_mfma_f32_16x16x4_f32, the accumulators start at the bias; every
 //   pn2t_gemm_dx       dx = dz W            MFMA takes four consecutive k, so an output is ONE fma chain over ascending k (channel, output or row)
@@ -16,362 +17,7 @@
 //   pn2t_gather_back   the gradient of a layer's input features summed per point over the rows that read it, rows ascending, in f64
 //   pn2t_loss          log_softmax, the loss, dlogits
 // No floating-point atomic anywhere; every sum over rows is ordered by the row index and chunk_rows alone.
-#include "pcr_internal.hpp"
-
-#include <algorithm>
-#include <cfloat>
-#include <cmath>
-
-#pragma clang fp contract(off)
-
-using namespace pcr;
-
-namespace {
-
-constexpr int T_BLOCK = 256;
-constexpr uint32_t T_MAX_WIDTH = 1024;
-constexpr unsigned long long T_MAX_ROWS = 0x7FFFFFF0ull;
-constexpr uint32_t T_DEFAULT_CHUNK = 256;
-constexpr uint32_t T_NONE = 0xFFFFFFFFu;
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-struct TLayer {
-    uint32_t K, N;
-    bool bn;
-    size_t w, b, gamma, beta, rmean, rvar;      // offsets into the flat weight array
-};
-
-struct GemmArgs {
-    const float* a;      // A(i, k) = a[i * sai + k * sak]
-    const float* b;      // B(k, j) = b[k * sbk + j * sbj]
-    const float* init;   // N floats the accumulators start from, or NULL: +0
-    float* c;            // C(i, j) = c[chunk * c_stride + i * N + j]
-    uint32_t M, N, Kt, chunk;
-    size_t sai, sak, sbk, sbj, c_stride;
-};
-
-// C = init + A B, chunk by chunk of k (one chunk = all of k for the forward and the dx product).  A wave owns 32 rows x 64 columns (two row tiles share
-// the B operands, four column tiles the A operands); MFMA number m of its loop takes k = 4 m + (lane >> 4), so that every output is one chain over
-// ascending k.  Operands past an edge are read as +0.
-constexpr int T_RT = 2;                  // 16-row tiles per wave
-constexpr int T_ROWS = 4 * 16 * T_RT;    // rows per workgroup
-__global__ __launch_bounds__(T_BLOCK) void pn2t_gemm_kernel(const GemmArgs g)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & 15, h = lane >> 4;
-    const unsigned long long i0 = ((unsigned long long)blockIdx.x * 4 + (unsigned)wave) * (16 * T_RT);
-    if (i0 >= g.M) return;                                      // wave-uniform; the kernel has no barrier
-    const uint32_t j0 = blockIdx.y * 64;
-    const uint32_t kb = blockIdx.z * g.chunk, ke = g.Kt - kb < g.chunk ? g.Kt : kb + g.chunk;
-    f32x4 acc[T_RT][4];
-#pragma unroll
-    for (int t = 0; t < 4; t++) {
-        const uint32_t col = j0 + 16 * t + j;
-        const float v = (g.init && col < g.N) ? g.init[col] : 0.0f;
-#pragma unroll
-        for (int rt = 0; rt < T_RT; rt++) acc[rt][t] = f32x4{ v, v, v, v };
-    }
-    bool row_ok[T_RT];
-    const float* ap[T_RT];
-#pragma unroll
-    for (int rt = 0; rt < T_RT; rt++) {
-        row_ok[rt] = i0 + 16 * rt + j < g.M;
-        ap[rt] = g.a + (row_ok[rt] ? (size_t)(i0 + 16 * rt + j) * g.sai : 0);
-    }
-    const int nt = (int)std::min<uint32_t>(4u, (g.N - j0 + 15u) / 16u);      // wave-uniform: the 16-column tiles that hold a column
-    const bool two = i0 + 16 < g.M;                                           // wave-uniform: the second row tile holds a row
-#pragma unroll 2
-    for (uint32_t k = kb; k < ke; k += 4) {
-        const uint32_t kk = k + (uint32_t)h;
-        const bool k_ok = kk < ke;
-        float av[T_RT], bv[4];
-#pragma unroll
-        for (int rt = 0; rt < T_RT; rt++) av[rt] = (row_ok[rt] && k_ok) ? ap[rt][(size_t)kk * g.sak] : 0.0f;
-#pragma unroll
-        for (int t = 0; t < 4; t++) {
-            const uint32_t col = j0 + 16 * t + j;
-            bv[t] = (k_ok && col < g.N) ? g.b[(size_t)kk * g.sbk + (size_t)col * g.sbj] : 0.0f;
-        }
-#pragma unroll
-        for (int t = 0; t < 4; t++)
-            if (t < nt) {
-                acc[0][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[0], bv[t], acc[0][t], 0, 0, 0);
-                if (two) acc[1][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[1], bv[t], acc[1][t], 0, 0, 0);
-            }
-    }
-    float* cp = g.c + (size_t)blockIdx.z * g.c_stride;
-#pragma unroll
-    for (int rt = 0; rt < T_RT; rt++)
-#pragma unroll
-        for (int t = 0; t < 4; t++) {
-            const uint32_t col = j0 + 16 * t + j;
-#pragma unroll
-            for (int reg = 0; reg < 4; reg++) {
-                const unsigned long long row = i0 + 16 * rt + 4 * h + reg;
-                if (row < g.M && col < g.N) cp[(size_t)row * g.N + col] = acc[rt][t][reg];
-            }
-        }
-}
-
-// the rows of an SA layer.  grouped: row r = (centre q = r / nsample, member k = r % nsample) reads point idx[q][k] of its object;
-// group_all (idx == NULL): row r is point r.  x[r] = (xyz - centre | features), row_pt[r] = the point (T_NONE: a member outside its object, a row of zeros)
-__global__ __launch_bounds__(T_BLOCK) void pn2t_gather_kernel(const float* __restrict__ px, const float* __restrict__ py, const float* __restrict__ pz,
-                                                              const float* __restrict__ qx, const float* __restrict__ qy, const float* __restrict__ qz,
-                                                              const float* __restrict__ feat, const uint32_t* __restrict__ idx, uint32_t rows, uint32_t nsample,
-                                                              uint32_t npoint, uint32_t n_prev, uint32_t D, float* __restrict__ x, uint32_t* __restrict__ row_pt)
-{
-    const uint32_t r = blockIdx.x * T_BLOCK + threadIdx.x;
-    if (r >= rows) return;
-    const uint32_t K = 3 + D;
-    float* xr = x + (size_t)r * K;
-    uint32_t p = r;
-    float cx = 0.0f, cy = 0.0f, cz = 0.0f;
-    bool sub = false;
-    if (idx) {
-        const uint32_t q = r / nsample, o = q / npoint, i = idx[r];
-        if (i >= n_prev) {
-            for (uint32_t c = 0; c < K; c++) xr[c] = 0.0f;
-            row_pt[r] = T_NONE;
-            return;
-        }
-        p = o * n_prev + i;
-        cx = qx[q]; cy = qy[q]; cz = qz[q];
-        sub = true;
-    }
-    row_pt[r] = p;
-    xr[0] = sub ? px[p] - cx : px[p];
-    xr[1] = sub ? py[p] - cy : py[p];
-    xr[2] = sub ? pz[p] - cz : pz[p];
-    for (uint32_t c = 0; c < D; c++) xr[3 + c] = feat[(size_t)p * D + c];
-}
-
-__global__ __launch_bounds__(T_BLOCK) void pn2t_centres_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ z,
-                                                               const uint32_t* __restrict__ fps, uint32_t n, uint32_t npoint, uint32_t total,
-                                                               float* __restrict__ cx, float* __restrict__ cy, float* __restrict__ cz)
-{
-    const uint32_t q = blockIdx.x * T_BLOCK + threadIdx.x;
-    if (q >= total) return;
-    uint32_t i = fps[q];
-    if (i >= n) i = n - 1;      // (never: a pick is a member)
-    const size_t p = (size_t)(q / npoint) * n + i;
-    cx[q] = x[p]; cy[q] = y[p]; cz[q] = z[p];
-}
-
-// part[c][n] <- the f64 sum over the rows of chunk c, ascending, of v (mu == NULL) or of (v - mu[n])^2
-__global__ __launch_bounds__(T_BLOCK) void pn2t_stat_part_kernel(const float* __restrict__ v, uint32_t M, uint32_t N, uint32_t chunk, uint32_t chunks,
-                                                                 const double* __restrict__ mu, double* __restrict__ part)
-{
-    const size_t e = (size_t)blockIdx.x * T_BLOCK + threadIdx.x;
-    if (e >= (size_t)chunks * N) return;
-    const uint32_t c = (uint32_t)(e / N), n = (uint32_t)(e - (size_t)c * N);
-    const uint32_t r0 = c * chunk, r1 = M - r0 < chunk ? M : r0 + chunk;
-    double s = 0.0;
-    if (mu) {
-        const double m = mu[n];
-#pragma unroll 8
-        for (uint32_t r = r0; r < r1; r++) { const double d = (double)v[(size_t)r * N + n] - m; s = s + d * d; }
-    } else {
-#pragma unroll 8
-        for (uint32_t r = r0; r < r1; r++) s = s + (double)v[(size_t)r * N + n];
-    }
-    part[e] = s;
-}
-
-// pass 0: mu <- the sum / M.  pass 1: var <- the sum / M, rstd, and the running statistics (f64, rounded once).  pass 2: out32 <- the sum (a bias gradient)
-__global__ __launch_bounds__(T_BLOCK) void pn2t_stat_fin_kernel(const double* __restrict__ part, uint32_t chunks, uint32_t N, uint32_t M, int pass, double* __restrict__ mu,
-                                                                double* __restrict__ var, double* __restrict__ rstd, double eps, double mom, float* __restrict__ rmean,
-                                                                float* __restrict__ rvar, float* __restrict__ out32)
-{
-    const uint32_t n = blockIdx.x * T_BLOCK + threadIdx.x;
-    if (n >= N) return;
-    double s = 0.0;
-    for (uint32_t c = 0; c < chunks; c++) s = s + part[(size_t)c * N + n];
-    if (pass == 0) {
-        mu[n] = s / (double)M;
-    } else if (pass == 1) {
-        const double vv = s / (double)M;
-        var[n] = vv;
-        rstd[n] = 1.0 / sqrt(vv + eps);
-        rmean[n] = (float)((1.0 - mom) * (double)rmean[n] + mom * mu[n]);
-        rvar[n] = (float)((1.0 - mom) * (double)rvar[n] + mom * (vv * (double)M / (double)(M - 1)));
-    } else {
-        out32[n] = (float)s;
-    }
-}
-
-// y = relu((z - mu) rstd gamma + beta), evaluated in f64 and rounded once; a (head) = y keep s
-__global__ __launch_bounds__(T_BLOCK) void pn2t_bn_relu_kernel(const float* __restrict__ z, size_t total, uint32_t N, const double* __restrict__ mu,
-                                                               const double* __restrict__ rstd, const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                               float* __restrict__ y, const uint8_t* __restrict__ keep, float s, float* __restrict__ a)
-{
-    const size_t e = (size_t)blockIdx.x * T_BLOCK + threadIdx.x;
-    if (e >= total) return;
-    const uint32_t n = (uint32_t)(e % N);
-    float v = (float)(((double)z[e] - mu[n]) * rstd[n] * (double)gamma[n] + (double)beta[n]);
-    v = v > 0.0f ? v : 0.0f;
-    y[e] = v;
-    if (a) a[e] = (!keep || keep[e]) ? v * s : 0.0f;
-}
-
-// feat[g][c] = the max over the gsize rows of group g; arg[g][c] = the lowest position that holds it, T_NONE where the max is 0
-__global__ __launch_bounds__(T_BLOCK) void pn2t_max_kernel(const float* __restrict__ y, uint32_t groups, uint32_t gsize, uint32_t N, float* __restrict__ feat,
-                                                           uint32_t* __restrict__ arg)
-{
-    const size_t e = (size_t)blockIdx.x * T_BLOCK + threadIdx.x;
-    if (e >= (size_t)groups * N) return;
-    const uint32_t g = (uint32_t)(e / N), c = (uint32_t)(e - (size_t)g * N);
-    const float* p = y + (size_t)g * gsize * N + c;
-    float m = p[0];
-    uint32_t best = 0;
-    for (uint32_t k = 1; k < gsize; k++) {
-        const float v = p[(size_t)k * N];
-        if (v > m) { m = v; best = k; }
-    }
-    feat[e] = m;
-    arg[e] = m > 0.0f ? best : T_NONE;
-}
-
-__global__ __launch_bounds__(T_BLOCK) void pn2t_max_back_kernel(const float* __restrict__ dfeat, const uint32_t* __restrict__ arg, size_t total, uint32_t gsize, uint32_t N,
-                                                                float* __restrict__ dy)
-{
-    const size_t e = (size_t)blockIdx.x * T_BLOCK + threadIdx.x;
-    if (e >= total) return;
-    const size_t r = e / N;
-    const uint32_t c = (uint32_t)(e - r * N);
-    const size_t g = r / gsize;
-    const uint32_t k = (uint32_t)(r - g * gsize);
-    dy[e] = arg[g * N + c] == k ? dfeat[g * N + c] : 0.0f;
-}
-
-// the gradient that reaches BN's output at element e: dropout (the same mask and s), then ReLU (passes where y > 0)
-__device__ __forceinline__ float pn2t_gy(const float* dy, const float* y, const uint8_t* keep, float s, size_t e)
-{
-    float g = dy[e];
-    if (keep) g = keep[e] ? g * s : 0.0f;
-    return y[e] > 0.0f ? g : 0.0f;
-}
-
-// part[c][0][n] <- sum gy, part[c][1][n] <- sum gy xhat over the rows of chunk c, ascending, in f64
-__global__ __launch_bounds__(T_BLOCK) void pn2t_bnb_part_kernel(const float* __restrict__ dy, const float* __restrict__ y, const float* __restrict__ z,
-                                                                const uint8_t* __restrict__ keep, float s, uint32_t M, uint32_t N, uint32_t chunk, uint32_t chunks,
-                                                                const double* __restrict__ mu, const double* __restrict__ rstd, double* __restrict__ part)
-{
-    const size_t t = (size_t)blockIdx.x * T_BLOCK + threadIdx.x;
-    if (t >= (size_t)chunks * N) return;
-    const uint32_t c = (uint32_t)(t / N), n = (uint32_t)(t - (size_t)c * N);
-    const uint32_t r0 = c * chunk, r1 = M - r0 < chunk ? M : r0 + chunk;
-    const double m = mu[n], rs = rstd[n];
-    double s0 = 0.0, s1 = 0.0;
-#pragma unroll 8
-    for (uint32_t r = r0; r < r1; r++) {
-        const size_t e = (size_t)r * N + n;
-        const double g = (double)pn2t_gy(dy, y, keep, s, e);
-        s0 = s0 + g;
-        s1 = s1 + g * (((double)z[e] - m) * rs);
-    }
-    part[((size_t)c * 2) * N + n] = s0;
-    part[((size_t)c * 2 + 1) * N + n] = s1;
-}
-
-__global__ __launch_bounds__(T_BLOCK) void pn2t_bnb_fin_kernel(const double* __restrict__ part, uint32_t chunks, uint32_t N, uint32_t M, float* __restrict__ dgamma,
-                                                               float* __restrict__ dbeta, double* __restrict__ mean_g, double* __restrict__ mean_gx)
-{
-    const uint32_t n = blockIdx.x * T_BLOCK + threadIdx.x;
-    if (n >= N) return;
-    double s0 = 0.0, s1 = 0.0;
-    for (uint32_t c = 0; c < chunks; c++) {
-        s0 = s0 + part[((size_t)c * 2) * N + n];
-        s1 = s1 + part[((size_t)c * 2 + 1) * N + n];
-    }
-    dbeta[n] = (float)s0;
-    dgamma[n] = (float)s1;
-    mean_g[n] = s0 / (double)M;
-    mean_gx[n] = s1 / (double)M;
-}
-
-// dy <- dz = rstd gamma (gy - mean(gy) - xhat mean(gy xhat)), in f64, rounded once
-__global__ __launch_bounds__(T_BLOCK) void pn2t_bnb_dz_kernel(float* __restrict__ dy, const float* __restrict__ y, const float* __restrict__ z, const uint8_t* __restrict__ keep,
-                                                              float s, size_t total, uint32_t N, const double* __restrict__ mu, const double* __restrict__ rstd,
-                                                              const float* __restrict__ gamma, const double* __restrict__ mean_g, const double* __restrict__ mean_gx)
-{
-    const size_t e = (size_t)blockIdx.x * T_BLOCK + threadIdx.x;
-    if (e >= total) return;
-    const uint32_t n = (uint32_t)(e % N);
-    const double g = (double)pn2t_gy(dy, y, keep, s, e);
-    const double xhat = ((double)z[e] - mu[n]) * rstd[n];
-    dy[e] = (float)(rstd[n] * (double)gamma[n] * (g - mean_g[n] - xhat * mean_gx[n]));
-}
-
-__global__ __launch_bounds__(T_BLOCK) void pn2t_dw_reduce_kernel(const float* __restrict__ part, uint32_t chunks, size_t cells, float* __restrict__ dw)
-{
-    const size_t e = (size_t)blockIdx.x * T_BLOCK + threadIdx.x;
-    if (e >= cells) return;
-    float s = part[e];
-    for (uint32_t c = 1; c < chunks; c++) s = s + part[(size_t)c * cells + e];
-    dw[e] = s;
-}
-
-// dfeat[p][c] <- the f64 sum, rows ascending, of dx[r][3 + c] over the rows r of p's object that read point p; rounded once
-__global__ __launch_bounds__(T_BLOCK) void pn2t_gather_back_kernel(const float* __restrict__ dx, const uint32_t* __restrict__ row_pt, uint32_t points, uint32_t n_prev,
-                                                                   uint32_t rows_per_obj, uint32_t D, float* __restrict__ dfeat)
-{
-    const uint32_t p = blockIdx.x;                              // one workgroup per point: row_pt is read uniformly
-    if (p >= points) return;
-    const uint32_t o = p / n_prev, K = 3 + D;
-    const size_t r0 = (size_t)o * rows_per_obj;
-    for (uint32_t c = threadIdx.x; c < D; c += T_BLOCK) {
-        double s = 0.0;
-        for (uint32_t k = 0; k < rows_per_obj; k++)
-            if (row_pt[r0 + k] == p) s = s + (double)dx[(r0 + k) * K + 3 + c];
-        dfeat[(size_t)p * D + c] = (float)s;
-    }
-}
-
-// one workgroup: log_softmax of every row as the eval pass takes it, dlogits = (exp(logp) - onehot) / n_obj, loss = -(1 / n_obj) sum_b logp[b][target[b]] over
-// ascending b in f64
-__global__ __launch_bounds__(T_BLOCK) void pn2t_loss_kernel(const float* __restrict__ logits, const int32_t* __restrict__ target, uint32_t n_obj, uint32_t n_class,
-                                                            float* __restrict__ logp, float* __restrict__ dlogits, double* __restrict__ loss)
-{
-    for (uint32_t o = threadIdx.x; o < n_obj; o += T_BLOCK) {
-        const float* r = logits + (size_t)o * n_class;
-        float m = r[0];
-        for (uint32_t c = 1; c < n_class; c++)
-            if (r[c] > m) m = r[c];
-        float s = 0.0f;
-        for (uint32_t c = 0; c < n_class; c++) s = s + expf(r[c] - m);
-        const float ls = logf(s);
-        for (uint32_t c = 0; c < n_class; c++) {
-            const float lp = (r[c] - m) - ls;
-            logp[(size_t)o * n_class + c] = lp;
-            dlogits[(size_t)o * n_class + c] = (float)((exp((double)lp) - ((int32_t)c == target[o] ? 1.0 : 0.0)) / (double)n_obj);
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double s = 0.0;
-        for (uint32_t o = 0; o < n_obj; o++) s = s + (double)logp[(size_t)o * n_class + (uint32_t)target[o]];
-        *loss = -s / (double)n_obj;
-    }
-}
-
-inline unsigned blocks_for(size_t n) { return (unsigned)((n + T_BLOCK - 1) / T_BLOCK); }
-
-}  // namespace
-
-struct pcr_pn2_trainer {
-    pcr_pn2_desc desc;
-    int device = 0;
-    std::vector<TLayer> layers;          // weight order: the SA layers' convolutions, then the head
-    uint32_t sa_first[PCR_PN2_MAX_SA];   // the first layer of every SA stage
-    uint32_t sa_in[PCR_PN2_MAX_SA], sa_out[PCR_PN2_MAX_SA];
-    uint32_t head_first = 0, n_sampling = 0;
-    uint64_t n_weights = 0;
-    float dropout_p = 0.0f, dropout_s = 1.0f;
-    double momentum = 0.1;
-    uint32_t chunk_rows = T_DEFAULT_CHUNK;
-    float* w_dev = nullptr;              // the flat weight array, running statistics included
-    float* grad_dev = nullptr;           // the same layout
-};
+#include "pointnet_train_common.hpp"
 
 namespace {
 
@@ -419,17 +65,6 @@ bool trainer_shapes(const pcr_pn2_desc& d, pcr_pn2_trainer& t)
     }
     t.n_weights = off;
     return true;
-}
-
-const char* weights_ok(const pcr_pn2_trainer* t, const float* w)
-{
-    for (uint64_t i = 0; i < t->n_weights; i++)
-        if (!std::isfinite(w[i])) return ": a non-finite weight";
-    for (const TLayer& L : t->layers)
-        if (L.bn)
-            for (uint32_t n = 0; n < L.N; n++)
-                if (!((double)w[L.rvar + n] + t->desc.bn_eps > 0.0)) return ": running_var + eps must be positive";
-    return nullptr;
 }
 
 // the stages of one call: every SA layer, then the head
@@ -552,17 +187,6 @@ bool make_plan(const pcr_pn2_trainer* t, size_t n_obj, size_t npts, Plan& P)
     return true;
 }
 
-int launch_gemm(pcr_ctx* ctx, const char* prof, GemmArgs g)
-{
-    if (g.M == 0 || g.N == 0) return PCR_OK;
-    const uint32_t chunks = g.Kt == 0 ? 1u : (g.Kt + g.chunk - 1) / g.chunk;
-    if (chunks > 65535u) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_train_grad_f32: more than 65535 chunks of rows (raise chunk_rows)");
-    ProfScope ps(ctx, prof);
-    hipLaunchKernelGGL(pn2t_gemm_kernel, dim3((g.M + T_ROWS - 1) / T_ROWS, (g.N + 63) / 64, chunks), dim3(T_BLOCK), 0, ctx->stream, g);
-    PCR_HIP(ctx, hipGetLastError());
-    return PCR_OK;
-}
-
 }  // namespace
 
 extern "C" int pcr_pn2_trainer_create(pcr_ctx* ctx, const pcr_pn2_desc* desc, const float* weights, size_t n_weights, double dropout_p, double bn_momentum,
@@ -613,6 +237,7 @@ extern "C" int pcr_pn2_trainer_destroy(pcr_ctx* ctx, pcr_pn2_trainer* t)
 extern "C" int pcr_pn2_trainer_info(const pcr_pn2_trainer* t, size_t n_obj, size_t npts, pcr_pn2_train_info* info)
 {
     if (!t || !info) return PCR_ERR_ARG;
+    if (t->kind == 1) return pn1_trainer_info(t, n_obj, npts, info);
     memset(info, 0, sizeof(*info));
     info->n_weights = t->n_weights;
     info->chunk_rows = t->chunk_rows;
@@ -667,6 +292,7 @@ extern "C" int pcr_pn2_train_grad_f32(pcr_ctx* ctx, pcr_pn2_trainer* t, const fl
     const char* who = "pcr_pn2_train_grad_f32";
     auto bad = [&](const char* what) { return fail(ctx, PCR_ERR_ARG, (std::string(who) + what).c_str()); };
     if (!ctx || !t) return fail(ctx, PCR_ERR_ARG, who);
+    if (t->kind != 0) return bad(": the trainer was made by pcr_pn1_trainer_create (use pcr_pointnet_train_grad_f32)");
     if (t->device != ctx->device) return bad(": the trainer lives on another device");
     if (npts < 1) return bad(": npts must be >= 1");
     if (n_obj == 0) return PCR_OK;
@@ -800,7 +426,7 @@ extern "C" int pcr_pn2_train_grad_f32(pcr_ctx* ctx, pcr_pn2_trainer* t, const fl
             }
             {
                 ProfScope ps(ctx, "pn2t_bn_relu");
-                hipLaunchKernelGGL(pn2t_bn_relu_kernel, dim3(blocks_for(cells)), dim3(T_BLOCK), 0, ctx->stream, P.z[i], cells, L.N, mu, rstd, W + L.gamma, W + L.beta, P.y[i], kp,
+                hipLaunchKernelGGL(pn2t_bn_relu_kernel<true>, dim3(blocks_for(cells)), dim3(T_BLOCK), 0, ctx->stream, P.z[i], cells, L.N, mu, rstd, W + L.gamma, W + L.beta, P.y[i], kp,
                                    drop_s, head ? P.a[i] : (float*)nullptr);
             }
             x = head ? P.a[i] : P.y[i];
@@ -842,10 +468,10 @@ extern "C" int pcr_pn2_train_grad_f32(pcr_ctx* ctx, pcr_pn2_trainer* t, const fl
             if (L.bn) {
                 double *mu = P.stat[i], *rstd = mu + 2 * (size_t)L.N, *mg = mu + 3 * (size_t)L.N, *mgx = mu + 4 * (size_t)L.N;
                 ProfScope ps(ctx, "pn2t_bn_back");
-                hipLaunchKernelGGL(pn2t_bnb_part_kernel, dim3(blocks_for((size_t)chunks * L.N)), dim3(T_BLOCK), 0, ctx->stream, cur, P.y[i], P.z[i], keep_of[i], drop_s, st.M, L.N,
+                hipLaunchKernelGGL(pn2t_bnb_part_kernel<true>, dim3(blocks_for((size_t)chunks * L.N)), dim3(T_BLOCK), 0, ctx->stream, cur, P.y[i], P.z[i], keep_of[i], drop_s, st.M, L.N,
                                    chunk, chunks, mu, rstd, P.part);
                 hipLaunchKernelGGL(pn2t_bnb_fin_kernel, dim3(blocks_for(L.N)), dim3(T_BLOCK), 0, ctx->stream, P.part, chunks, L.N, st.M, G + L.gamma, G + L.beta, mg, mgx);
-                hipLaunchKernelGGL(pn2t_bnb_dz_kernel, dim3(blocks_for(cells)), dim3(T_BLOCK), 0, ctx->stream, cur, P.y[i], P.z[i], keep_of[i], drop_s, cells, L.N, mu, rstd,
+                hipLaunchKernelGGL(pn2t_bnb_dz_kernel<true>, dim3(blocks_for(cells)), dim3(T_BLOCK), 0, ctx->stream, cur, P.y[i], P.z[i], keep_of[i], drop_s, cells, L.N, mu, rstd,
                                    W + L.gamma, mg, mgx);
             } else {                                             // the last FC layer: its bias has a gradient, the column sums of dz
                 ProfScope ps(ctx, "pn2t_stat");

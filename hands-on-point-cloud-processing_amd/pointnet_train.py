@@ -3,6 +3,10 @@ every parameter (HomeworkFinal/train_cls.py:186-196 without its optimiser; model
 
   Trainer       the model in training mode on the library (pcr_pn2_train_grad_f32; the contract is above pcr_pn2_trainer_create in include/pcr.h)
   get_loss      models/pointnet2_cls_ssg.get_loss: the same call, (pred, target, trans_feat) -> the mean negative log-likelihood
+  TrainerCls    the vanilla PointNet (models/pointnet_cls.get_model) in training mode (pcr_pointnet_train_grad_f32; the contract is above
+                pcr_pn1_trainer_create in include/pcr.h): the same surface as Trainer, nothing is sampled
+  get_loss_cls  models/pointnet_cls.get_loss: the NLL plus mat_diff_loss_scale x the feature-transform regulariser
+  TRAINERS      the reference's module name (train_cls.py --model) -> the trainer class
 
 The optimiser stays torch's own, on host tensors, exactly as train_cls.py:147-153 builds it:
 
@@ -23,7 +27,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from .pointnet import _BN_KEYS, _SSG_FC, _SSG_SA, _ctx, _like, _to_host, get_model
+from .pointnet import _BN_KEYS, _SSG_FC, _SSG_SA, _ctx, _like, _to_host, get_model, get_model_cls
 
 _PARAM_BN = ("weight", "bias")
 
@@ -300,3 +304,170 @@ class get_loss:
         return torch.tensor(loss, dtype=proto.dtype, device=proto.device)
 
     __call__ = forward
+
+
+# ---------------------------------------------------------------------------------------------------- the vanilla PointNet (pointnet_cls)
+def _cls_layers(desc):
+    """(conv / linear prefix, BN prefix or None, out, in) in weight order for a Pn1Desc, with the reference's names (feat.stn.*, feat.conv1 ...,
+    feat.fstn.*, fc1 / bn1 ...)"""
+    tc, tf = [int(w) for w in desc.tnet_conv], [int(w) for w in desc.tnet_fc]
+
+    def tnet(prefix, cin, k):
+        out = []
+        for i, w in enumerate(tc):
+            out.append((f"{prefix}.conv{i + 1}", f"{prefix}.bn{i + 1}", w, cin))
+            cin = w
+        for i, w in enumerate(tf):
+            out.append((f"{prefix}.fc{i + 1}", f"{prefix}.bn{len(tc) + i + 1}", w, cin))
+            cin = w
+        return out + [(f"{prefix}.fc{len(tf) + 1}", None, k * k, cin)]
+
+    cin = 3 + int(desc.D0)
+    out = tnet("feat.stn", cin, 3) if desc.stn3 else []
+    for i in range(desc.n_mlp):
+        out.append((f"feat.conv{i + 1}", f"feat.bn{i + 1}", int(desc.widths[i]), cin))
+        cin = int(desc.widths[i])
+    if desc.fstn:
+        out += tnet("feat.fstn", int(desc.widths[0]), int(desc.widths[0]))
+    for i in range(desc.n_fc):
+        out.append((f"fc{i + 1}", f"bn{i + 1}" if i + 1 < desc.n_fc else None, int(desc.fc_widths[i]), cin))
+        cin = int(desc.fc_widths[i])
+    return out
+
+
+class _DescModelCls(get_model_cls):
+    """pointnet.get_model_cls for the layers and the descriptor of a TrainerCls.from_desc"""
+
+    def __init__(self, k, desc, layers):
+        super().__init__(k, int(desc.D0) == 3)
+        self._d, self._l = desc, layers
+
+    def _layers(self):
+        return list(self._l)
+
+    def desc(self):
+        return self._d
+
+    def state_shapes(self):
+        out = {}
+        for conv, bn, w, cin in self._l:
+            out[f"{conv}.weight"] = (w, cin, 1) if ".conv" in conv else (w, cin)
+            out[f"{conv}.bias"] = (w,)
+            for k in (_BN_KEYS if bn else ()):
+                out[f"{bn}.{k}"] = (w,)
+        return out
+
+
+class TrainerCls(Trainer):
+    """The reference's pointnet_cls.get_model in TRAINING mode on the library, with Trainer's whole surface.  TrainerCls(k, normal_channel, dropout,
+    momentum, mat_diff_loss_scale, chunk_rows, ctx) is the reference's architecture; TrainerCls.from_desc(desc) any Pn1Desc (the reference's key
+    names).  step_grad returns (loss, logp) with loss = nll + mat_diff_loss_scale x the regulariser, as pointnet_cls.get_loss gives it, and keeps
+    last_nll, last_reg, last_trans and last_trans_feat.  Nothing is sampled: only the dropout mask is drawn (keep= fixes it)."""
+
+    def __init__(self, k=40, normal_channel=True, dropout=0.4, momentum=0.1, mat_diff_loss_scale=0.001, chunk_rows=0, ctx=None, *, seed=0):
+        self.num_class = self.k = int(k)
+        self.normal_channel = bool(normal_channel)
+        proto = get_model_cls(self.k, self.normal_channel)
+        self._setup_cls(proto.desc(), proto._layers(), dropout, momentum, mat_diff_loss_scale, chunk_rows, ctx, seed)
+        self._generic = False
+
+    @classmethod
+    def from_desc(cls, desc, dropout=0.4, momentum=0.1, mat_diff_loss_scale=0.001, chunk_rows=0, ctx=None, *, seed=0):
+        self = cls.__new__(cls)
+        self.num_class = self.k = int(desc.fc_widths[desc.n_fc - 1])
+        self.normal_channel = int(desc.D0) == 3
+        self._setup_cls(desc, _cls_layers(desc), dropout, momentum, mat_diff_loss_scale, chunk_rows, ctx, seed)
+        self._generic = True
+        return self
+
+    def _setup_cls(self, desc, layers, dropout, momentum, scale, chunk_rows, ctx, seed):
+        self._setup(desc, layers, dropout, momentum, chunk_rows, ctx, seed)
+        self.mat_diff_loss_scale = float(scale)
+        for conv, _, w, cin in layers:                           # Conv1d weights are [out, in, 1] in the reference's state dict
+            if ".conv" in conv:
+                self._slots[f"{conv}.weight"] = (self._slots[f"{conv}.weight"][0], (w, cin, 1))
+        self.last_nll = self.last_reg = self.last_trans = self.last_trans_feat = None
+
+    def param_keys(self):
+        """the keys of named_parameters() in the reference's order: module by module (feat.stn, feat, feat.fstn, the head), the convolutions and
+        linear layers of a module before its BatchNorms"""
+        groups = {}
+        for conv, bn, _, _ in self._layer_list:
+            g = groups.setdefault(conv.rsplit(".", 1)[0] if "." in conv else "", ([], []))
+            g[0].append(conv)
+            if bn:
+                g[1].append(bn)
+        return [f"{m}.{p}" for convs, bns in groups.values() for m in convs + bns for p in _PARAM_BN]
+
+    def trainer(self, ctx=None):
+        ctx = _ctx(ctx if ctx is not None else self._ctx_arg)
+        if self._trainer is None or self._trainer_ctx is not ctx or not self._trainer.h:
+            if self._trainer is not None:
+                self._pull_running()
+                self._trainer.free()
+            self._trainer = ctx.pn1_trainer(self._desc, self._flat, self.dropout, self.momentum, self.mat_diff_loss_scale, self.chunk_rows)
+            self._trainer_ctx = ctx
+            self._dirty = False
+        elif self._dirty:
+            self._trainer.set_weights(self._flat, keep_running_stats=False)
+            self._dirty = False
+        return self._trainer
+
+    def step_grad(self, points, target, seed=None, keep=None, *, ctx=None):
+        """points [B, 3 | 6, N], target [B] or [B, 1] -> (loss, logp [B, k]), numpy / float or torch like `points`; every gradient is left in
+        grads() and in the .grad of torch_parameters().  keep: the dropout mask [B, width of the last hidden FC layer]; seed: draws it otherwise
+        (None: a seed from np.random)."""
+        x, proto = _to_host(points)
+        C0 = 3 + int(self._desc.D0)
+        if x.ndim != 3 or x.shape[1] != C0:
+            raise ValueError(f"points: [B, {C0}, N]")
+        B = x.shape[0]
+        tg = np.asarray(_to_host(target)[0]).reshape(-1)
+        tr = self.trainer(ctx)
+        if seed is None:
+            seed = int(np.random.randint(0, 2 ** 31 - 1))
+        if keep is not None:
+            keep = np.asarray(_to_host(keep)[0]).reshape(-1)
+        res = tr.train_grad(np.ascontiguousarray(np.transpose(x, (0, 2, 1)), np.float32), tg, seed, keep)
+        if B:
+            self._gflat[...] = res["grad"]
+            for bn in self._tracked:
+                self._tracked[bn] += 1
+            self.last_nll, self.last_reg, self.last_trans, self.last_trans_feat = res["nll"], res["reg"], res["trans"], res["trans_feat"]
+        if proto is None:
+            return res["loss"], res["logp"]
+        import torch
+        return torch.tensor(res["loss"], dtype=proto.dtype, device=proto.device), _like(res["logp"], proto)
+
+    def eval_model(self):
+        """a pointnet.get_model_cls in eval mode loaded with the current weights and running statistics"""
+        m = _DescModelCls(self.k, self._desc, self._layer_list) if self._generic else get_model_cls(self.k, self.normal_channel)
+        m.load_state_dict(self.state_dict(), strict=True)
+        return m.eval()
+
+
+class get_loss_cls:
+    """models/pointnet_cls.get_loss: (pred [B, k] log-probabilities, target [B], trans_feat [B, K, K]) -> F.nll_loss + mat_diff_loss_scale x
+    the mean over objects of the Frobenius norm of A (A^T - I), on the host in f64; a float for numpy input, a tensor like pred for torch input."""
+
+    def __init__(self, mat_diff_loss_scale=0.001):
+        self.mat_diff_loss_scale = float(mat_diff_loss_scale)
+
+    def forward(self, pred, target, trans_feat):
+        p, proto = _to_host(pred)
+        nll = float(get_loss()(np.asarray(p, np.float64), np.asarray(_to_host(target)[0])))
+        A = np.asarray(_to_host(trans_feat)[0], np.float64)
+        eye = np.eye(A.shape[1])[None]
+        M = A @ (np.transpose(A, (0, 2, 1)) - eye)
+        reg = float(np.mean(np.sqrt((M * M).sum((1, 2))))) if len(A) else 0.0
+        loss = nll + reg * self.mat_diff_loss_scale
+        if proto is None:
+            return float(loss)
+        import torch
+        return torch.tensor(loss, dtype=proto.dtype, device=proto.device)
+
+    __call__ = forward
+
+
+# the trainers by the reference's module name (train_cls.py --model)
+TRAINERS = {"pointnet2_cls_ssg": Trainer, "pointnet_cls": TrainerCls}

@@ -903,6 +903,67 @@ int pcr_pn2_trainer_get_weights(pcr_ctx* ctx, const pcr_pn2_trainer* trainer, fl
 int pcr_pn2_train_grad_f32(pcr_ctx* ctx, pcr_pn2_trainer* trainer, const float* objects, size_t n_obj, size_t npts, const int32_t* target,
                            const uint32_t* starts, uint64_t seed, const uint8_t* keep, double* loss, float* logp, float* grad);
 
+/* ---- HomeworkFinal: the vanilla PointNet (pointnet_cls) TRAINING pass: training-mode forward, pointnet_cls.get_loss (:32-42, with
+ * pointnet.py:135-141's feature-transform regulariser) and the gradient of every parameter.  The optimiser stays the caller's.
+ * A trainer is made from a pcr_pn1_desc (the limits of pcr_pn1_model_create) and the flat weight array of pcr_pn1_model_create, UNFOLDED: W,
+ * bias, gamma, beta, running_mean, running_var are kept as given.  The handle is the SSG trainer's type: pcr_pn2_trainer_destroy, _info
+ * (n_sampling = 0), _set_weights and _get_weights work on it; pcr_pn2_train_grad_f32 on it is PCR_ERR_ARG, and so is
+ * pcr_pointnet_train_grad_f32 on a trainer of pcr_pn2_trainer_create.
+ * pcr_pointnet_train_grad_f32 runs, for n_obj >= 2 objects of npts points (objects as pcr_pointnet_forward_f32 takes them) and int32 target[n_obj]:
+ *   Rows       a convolution stage has n_obj x npts rows: no sampling, no padding.  An FC stage (the T-Nets' and the head's) has n_obj rows.
+ *   Product    on the raw W, b, BLOCKED over k (v_mfma_f32_16x16x4_f32): inside every block of 64 consecutive k an output is ONE f32 fma chain from +0
+ *              over ascending k; the block results join an f64 sum that starts at the bias, blocks ascending; z[n] is that sum rounded ONCE.  dx is taken
+ *              the same way over the output channels, from +0.  (Not the SSG trainer's single chain: this model has three 1024-term products in front of
+ *              its first FC layers and three 1024-wide convolutions, and one f32 chain over 1024 terms put the gradients of the small exact fixture up
+ *              to 40 of the reference's own f32 errors away from its f64 pass; blocked, 7.)  dW is the SSG trainer's: chains over chunks of rows.
+ *   BatchNorm  the SSG trainer's, word for word: mu, biased var in f64 by chunks, rstd in f64, y evaluated in f64 from the f32 z and rounded
+ *              ONCE; the running statistics of all the model's BatchNorms (15 with both T-Nets) advance once per call, in f64, rounded once.
+ *   T-Net      three times conv -> BN -> ReLU on the stage's rows; the max over the object's points (after the ReLU; its gradient goes to the
+ *              LOWEST position among the maxima, a max of 0 passes nothing); two times FC -> BN -> ReLU; a linear layer WITHOUT BN with k k
+ *              outputs (k = 3, or K = widths[0] <= 128: up to 16 384, the 1 024 limit on a width does not apply to it) whose bias has a real
+ *              gradient, the column sum of its dz; then "+ identity": ONE f32 addition of 1 to every diagonal entry of the finished chain.
+ *   Transform  forward: y[j] = c_K, c_0 = +0, c_(k+1) = fmaf(x[k], T[k][j], c_k) with the object's own matrix, k ascending (3 x 3: plain fmaf
+ *              on xyz, the D0 features pass through; K x K: on the matrix pipe, T staged in LDS, a workgroup serving rows of ONE object).
+ *              The transformed rows are kept in memory.  Backward: dx[k] = the chain from +0 over ascending j of dy[j] T[k][j] (dx = dy T^T;
+ *              not taken for the 3 x 3 transform: the input takes no gradient), and dT[b][k][j] = sum over the rows n of object b ALONE of
+ *              x[b,n][k] dy[b,n][j]: ONE f32 fma chain from +0 over ascending n (the dW product with one chunk per object: chunk_rows does
+ *              not enter it).  dT is the gradient of the T-Net's last layer's output (the identity has none).
+ *   Encoder    conv 0 -> BN -> ReLU; the feature transform; the middle convolutions with BN + ReLU; the last convolution has BN only, so the
+ *              max over an object's points is SIGNED: taken in the order -inf < ... < -0 < +0 < ... < +inf (the integer key of
+ *              pcr_pointnet_forward_f32), the gradient goes to the LOWEST position that holds the maximum, always to exactly one.
+ *   Two paths  conv 0's activation feeds the feature T-Net and the transform: its gradient is g_transform + g_tnet, ONE f32 addition, the
+ *              T-Net's path added to the transform's.
+ *   Head       FC -> BN -> ReLU for every layer but the last; the dropout sits on the PRODUCT of the last hidden FC layer (n_fc - 2), before
+ *              its BN (pointnet_cls.py:25-27: fc2 -> dropout -> bn2 -> relu); none with n_fc == 1.  z <- z s where keep != 0, +0 elsewhere,
+ *              s = f32(1 / (1 - p)), one f32 product; the statistics are those of the dropped z.  keep (optional): one byte per object and
+ *              unit of that layer, [n_obj][keep_per_object].  NULL: keep[e] = (K(seed, (0x100 + n_fc - 2) << 32 | e) >> 11) 2^-53 >= p with the
+ *              SplitMix keying of the SSG trainer.  UNPINNED: torch's stream.  p == 0: s = 1 and a drawn mask is all ones, so z is unchanged
+ *              bit for bit; a caller's mask still applies.  The dropped layer's bias is NOT analytically zero (dropout lies between it and the
+ *              BN): its gradient is computed, the column sum of the masked, scaled dz.
+ *   Loss       loss[1] = the NLL as in the SSG trainer.  With fstn, per object A = trans_feat (f32), in f64 with products and sums rounded
+ *              separately: M = A (A^T - I) = A A^T - A as pointnet.py:140 has it (NOT A A^T - I), M[i][j] = (sum over ascending k of
+ *              A[i][k] A[j][k]) - A[i][j]; norm = sqrt(sum over ascending i of (sum over ascending j of M[i][j]^2)); loss[2] = reg = (sum over
+ *              ascending b of norm_b) / n_obj; loss[0] = nll + reg_scale reg.  dA[p][q] = reg_scale / (n_obj norm) ((sum over ascending j of
+ *              (M[p][j] + M[j][p]) A[j][q]) - M[p][q]) in f64, rounded ONCE, then dT + dA in ONE f32 addition (dA added to the gradient that
+ *              came back through the transform).  Without fstn reg = 0 (the reference would raise).  UNPINNED: a zero norm gives dA = +0,
+ *              where torch gives NaN.
+ *   Backward   everything else as the SSG trainer has it: dlogits, ReLU, BN, dW, +0 in the bias of a layer that BN follows directly; dx as under Product.
+ *   Order      No floating-point atomic anywhere.  Every sum over the rows of a layer follows the SSG trainer's chunk scheme, so the bits
+ *              depend on the inputs and on chunk_rows only: not on pn2_rows or any other tune key, not on a repeat of the call.
+ *   Outputs    loss[3] (f64: total, NLL, the unscaled regulariser), logp n_obj x n_class, grad: n_weights floats in the weight layout, +0 in
+ *              the running-statistic slots and in the biases BN follows directly; optional trans n_obj x 9 and trans_feat n_obj x K x K,
+ *              identity included (each must be NULL when the model has no such T-Net).
+ * PCR_ERR_ARG: NULL arguments; a descriptor pcr_pn1_model_create refuses; a trainer of the other kind; n_obj == 1; npts < 1; a target outside
+ *   [0, n_class); dropout_p outside [0, 1); bn_momentum outside [0, 1]; a non-finite reg_scale, input or weight; trans / trans_feat without
+ *   its T-Net; more than 65535 objects, 65535 chunks or 2^21 rows in a stage.  n_obj == 0: PCR_OK, nothing written, the running statistics
+ *   untouched.
+ * Profile names pn1t_gemm_fwd, pn1t_gemm_dx, pn1t_transform3, pn1t_transform, pn1t_identity, pn1t_smax, pn1t_dropout, pn1t_reg, pn1t_loss_fin, pn1t_add,
+ *   pn1t_gemm_dt; the shared kernels keep pn2t_stat, pn2t_bn_relu, pn2t_max, pn2t_loss, pn2t_max_back, pn2t_bn_back, pn2t_gemm_dw, pn2t_dw_reduce. */
+int pcr_pn1_trainer_create(pcr_ctx* ctx, const pcr_pn1_desc* desc, const float* weights, size_t n_weights, double dropout_p, double bn_momentum,
+                           double reg_scale, uint32_t chunk_rows, pcr_pn2_trainer** out);
+int pcr_pointnet_train_grad_f32(pcr_ctx* ctx, pcr_pn2_trainer* trainer, const float* objects, size_t n_obj, size_t npts, const int32_t* target,
+                                uint64_t seed, const uint8_t* keep, double loss[3], float* logp, float* trans, float* trans_feat, float* grad);
+
 /* ---- next row N4: global-registration front half, Homework9/hw9/src/registration.cpp:288-434, :535-615 -----------
  * N4a: exhaustive 1-NN between two descriptor sets (row-major n x dim / m x dim f32, host memory; dim 33 = FPFH),
  * nanoflann's evalMetric arithmetic for any dim (nanoflann.hpp:382-405: groups of four + tail, f32, unfused), canonical
