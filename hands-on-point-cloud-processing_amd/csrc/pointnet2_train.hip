@@ -2,8 +2,10 @@
 // parameter (models/pointnet2_cls_ssg.py, get_loss :50-52; train_cls.py's step without its optimiser).  The contract is written out above
 // pcr_pn2_trainer_create in include/pcr.h.
 //
-// Batch statistics break the eval pass's layer fusion: the pass goes layer by layer and keeps every layer's z and y in HBM.  The kernels live in
-// pointnet_train_common.hpp, which the vanilla PointNet's pass (pointnet_train.hip) includes too:
+// Batch statistics break the eval pass's layer fusion: the pass goes layer by layer and keeps every layer's z and y in HBM.  This file holds the SSG model's
+// own part: its shapes, its plan's sampling and per-stage buffers, FPS / centres / ball query / gather per stage, the max, the gather back.  The layer step
+// (LayerRun), the plan base, the create / info / call head and tail and the kernels live in pointnet_train_common.hpp, which the vanilla PointNet's pass
+// (pointnet_train.hip) includes too:
 //   pn2t_gather        the padded rows of an SA layer: (xyz - centre | features) per row, and the point every row read
 //   pn2t_gemm_fwd      z = x W^T + b        one wave = 32 rows x 64 outputs on v_mfma_f32_16x16x4_f32, the accumulators start at the bias; every
 //   pn2t_gemm_dx       dx = dz W            MFMA takes four consecutive k, so an output is ONE fma chain over ascending k (channel, output or row)
@@ -26,16 +28,6 @@ bool trainer_shapes(const pcr_pn2_desc& d, pcr_pn2_trainer& t)
 {
     if (d.n_sa < 1 || d.n_sa > PCR_PN2_MAX_SA || d.n_fc < 1 || d.n_fc > PCR_PN2_MAX_FC) return false;
     if (d.D0 > T_MAX_WIDTH - 3 || !std::isfinite(d.bn_eps)) return false;
-    size_t off = 0;
-    auto push = [&](uint32_t K, uint32_t N, bool bn) {
-        TLayer L;
-        L.K = K; L.N = N; L.bn = bn;
-        L.w = off; off += (size_t)K * N;
-        L.b = off; off += N;
-        L.gamma = L.beta = L.rmean = L.rvar = 0;
-        if (bn) { L.gamma = off; L.beta = off + N; L.rmean = off + 2 * (size_t)N; L.rvar = off + 3 * (size_t)N; off += 4 * (size_t)N; }
-        t.layers.push_back(L);
-    };
     uint32_t D = d.D0;
     t.n_sampling = 0;
     for (uint32_t l = 0; l < d.n_sa; l++) {
@@ -49,7 +41,7 @@ bool trainer_shapes(const pcr_pn2_desc& d, pcr_pn2_trainer& t)
         t.sa_in[l] = K;
         for (uint32_t i = 0; i < s.n_mlp; i++) {
             if (s.widths[i] < 1 || s.widths[i] > T_MAX_WIDTH) return false;
-            push(K, s.widths[i], true);
+            layer_push(t, K, s.widths[i], true);
             K = s.widths[i];
         }
         t.sa_out[l] = K;
@@ -60,10 +52,9 @@ bool trainer_shapes(const pcr_pn2_desc& d, pcr_pn2_trainer& t)
     uint32_t K = D;
     for (uint32_t i = 0; i < d.n_fc; i++) {
         if (d.fc_widths[i] < 1 || d.fc_widths[i] > T_MAX_WIDTH) return false;
-        push(K, d.fc_widths[i], i + 1 < d.n_fc);
+        layer_push(t, K, d.fc_widths[i], i + 1 < d.n_fc);
         K = d.fc_widths[i];
     }
-    t.n_weights = off;
     return true;
 }
 
@@ -75,40 +66,19 @@ struct Stage {
     uint32_t groups;
 };
 
-// the device block of one call.  Several Layouts (scratch_layout.hpp holds 24 slots each) laid one behind the other.
-struct Plan {
+// the device block of one call: PlanBase's, with the sampling buffers in `own` and one more Layout per SA stage behind the layers'
+struct Plan : PlanBase {
     size_t N[PCR_PN2_MAX_SA + 1];
     std::vector<Stage> stages;
     // uploaded
     float *x0 = nullptr, *feat0 = nullptr;
-    int32_t* target = nullptr;
-    uint8_t* keep = nullptr;
     uint32_t *seg[PCR_PN2_MAX_SA + 1], *cseg[PCR_PN2_MAX_SA];
-    size_t upload_bytes = 0;
     // sampling
     uint32_t *fps[PCR_PN2_MAX_SA], *bidx[PCR_PN2_MAX_SA], *bcnt[PCR_PN2_MAX_SA];
     float* cxyz[PCR_PN2_MAX_SA];
     // per SA stage
     float *xin[PCR_PN2_MAX_SA], *feat[PCR_PN2_MAX_SA];
     uint32_t *row_pt[PCR_PN2_MAX_SA], *arg[PCR_PN2_MAX_SA];
-    // per layer
-    std::vector<float*> z, y, a;
-    std::vector<double*> stat;       // 5 N doubles: mu, var, rstd, mean_g, mean_gx
-    // shared
-    float *dyA = nullptr, *dyB = nullptr, *dfeat = nullptr, *dw_part = nullptr, *logp = nullptr;
-    double *part = nullptr, *loss = nullptr;
-    Layout up, samp, work;
-    std::vector<Layout> per_layer;
-    size_t total = 0;
-
-    void bind(void* base)
-    {
-        char* p = (char*)base;
-        up.bind(p); p += up.bytes();
-        samp.bind(p); p += samp.bytes();
-        work.bind(p); p += work.bytes();
-        for (Layout& L : per_layer) { L.bind(p); p += L.bytes(); }
-    }
 };
 
 // false: too large
@@ -139,21 +109,18 @@ bool make_plan(const pcr_pn2_trainer* t, size_t n_obj, size_t npts, Plan& P)
     P.up.add(&P.keep, keep_bytes);
     for (uint32_t l = 0; l <= ns; l++) P.up.add(&P.seg[l], n_obj + 1);
     for (uint32_t l = 0; l < ns; l++) P.up.add(&P.cseg[l], n_obj * P.N[l + 1]);
-    P.upload_bytes = P.up.bytes();
     for (uint32_t l = 0; l < ns; l++) {
         const size_t nq = n_obj * P.N[l + 1];
-        P.samp.add(&P.fps[l], nq);
-        P.samp.add(&P.cxyz[l], 3 * nq);
-        P.samp.add(&P.bidx[l], nq * d.sa[l].nsample);
-        P.samp.add(&P.bcnt[l], nq);
+        P.own.add(&P.fps[l], nq);
+        P.own.add(&P.cxyz[l], 3 * nq);
+        P.own.add(&P.bidx[l], nq * d.sa[l].nsample);
+        P.own.add(&P.bcnt[l], nq);
     }
     const size_t nl = t->layers.size();
-    P.z.assign(nl, nullptr); P.y.assign(nl, nullptr); P.a.assign(nl, nullptr); P.stat.assign(nl, nullptr);
-    P.per_layer.assign(nl + d.n_sa, Layout());
-    size_t dy_cells = 1, part_cells = 1, dw_cells = 1, dfeat_cells = 1;
+    P.layers(nl, d.n_sa);
+    P.dfeat_cells = 1;
     for (size_t s = 0; s < P.stages.size(); s++) {
         const Stage& st = P.stages[s];
-        const uint32_t chunks = (st.M + t->chunk_rows - 1) / t->chunk_rows;
         const bool head = st.gsize == 0;
         if (!head) {
             Layout& L = P.per_layer[nl + s];
@@ -161,29 +128,11 @@ bool make_plan(const pcr_pn2_trainer* t, size_t n_obj, size_t npts, Plan& P)
             L.add(&P.row_pt[s], (size_t)st.M);
             L.add(&P.feat[s], (size_t)st.groups * t->sa_out[s]);
             L.add(&P.arg[s], (size_t)st.groups * t->sa_out[s]);
-            dfeat_cells = std::max(dfeat_cells, (size_t)st.groups * t->sa_out[s]);
+            P.dfeat_cells = std::max(P.dfeat_cells, (size_t)st.groups * t->sa_out[s]);
         }
-        for (uint32_t i = st.first; i < st.first + st.count; i++) {
-            const TLayer& Ly = t->layers[i];
-            Layout& L = P.per_layer[i];
-            L.add(&P.z[i], (size_t)st.M * Ly.N);
-            L.add(&P.y[i], Ly.bn ? (size_t)st.M * Ly.N : 0);
-            L.add(&P.a[i], head && Ly.bn ? (size_t)st.M * Ly.N : 0);
-            L.add(&P.stat[i], 5 * (size_t)Ly.N);
-            dy_cells = std::max(dy_cells, (size_t)st.M * std::max(Ly.N, Ly.K));
-            part_cells = std::max(part_cells, 2 * (size_t)chunks * Ly.N);
-            dw_cells = std::max(dw_cells, (size_t)chunks * Ly.N * Ly.K);
-        }
+        for (uint32_t i = st.first; i < st.first + st.count; i++) P.add_layer(i, st.M, t->layers[i], t->chunk_rows, head);
     }
-    P.work.add(&P.dyA, dy_cells);
-    P.work.add(&P.dyB, dy_cells);
-    P.work.add(&P.dfeat, dfeat_cells);
-    P.work.add(&P.dw_part, dw_cells);
-    P.work.add(&P.part, part_cells);
-    P.work.add(&P.logp, n_obj * t->layers.back().N);
-    P.work.add(&P.loss, (size_t)1);
-    P.total = P.up.bytes() + P.samp.bytes() + P.work.bytes();
-    for (const Layout& L : P.per_layer) P.total += L.bytes();
+    P.finish(n_obj, t->layers.back().N, 1);
     return true;
 }
 
@@ -198,27 +147,7 @@ extern "C" int pcr_pn2_trainer_create(pcr_ctx* ctx, const pcr_pn2_desc* desc, co
     t->desc = *desc;
     if (!trainer_shapes(*desc, *t)) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_trainer_create: a descriptor outside the limits (see include/pcr.h)");
     if (!desc->sa[desc->n_sa - 1].group_all) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_trainer_create: the last SA layer must be group_all");
-    if (!(dropout_p >= 0.0 && dropout_p < 1.0)) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_trainer_create: dropout_p must lie in [0, 1)");
-    if (!(bn_momentum >= 0.0 && bn_momentum <= 1.0)) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_trainer_create: bn_momentum must lie in [0, 1]");
-    if (n_weights != t->n_weights) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_trainer_create: n_weights is not the model's count");
-    if (const char* what = weights_ok(t.get(), weights)) return fail(ctx, PCR_ERR_ARG, (std::string("pcr_pn2_trainer_create") + what).c_str());
-    t->dropout_p = (float)dropout_p;
-    t->dropout_s = (float)(1.0 / (1.0 - dropout_p));
-    t->momentum = bn_momentum;
-    t->chunk_rows = chunk_rows ? chunk_rows : T_DEFAULT_CHUNK;
-    t->device = ctx->device;
-    PCR_HIP(ctx, hipSetDevice(ctx->device));
-    PCR_HIP(ctx, hipMalloc((void**)&t->w_dev, t->n_weights * 4));
-    hipError_t e = hipMalloc((void**)&t->grad_dev, t->n_weights * 4);
-    if (e == hipSuccess) e = hipMemcpy(t->w_dev, weights, t->n_weights * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(t->grad_dev, 0, t->n_weights * 4);
-    if (e != hipSuccess) {
-        (void)hipFree(t->w_dev);
-        if (t->grad_dev) (void)hipFree(t->grad_dev);
-        return fail(ctx, PCR_ERR_HIP, "pcr_pn2_trainer_create: the upload of the weights", e);
-    }
-    *out = t.release();
-    return PCR_OK;
+    return trainer_finish(ctx, "pcr_pn2_trainer_create", std::move(t), nullptr, weights, n_weights, dropout_p, bn_momentum, chunk_rows, out);
 }
 
 extern "C" int pcr_pn2_trainer_destroy(pcr_ctx* ctx, pcr_pn2_trainer* t)
@@ -238,14 +167,9 @@ extern "C" int pcr_pn2_trainer_info(const pcr_pn2_trainer* t, size_t n_obj, size
 {
     if (!t || !info) return PCR_ERR_ARG;
     if (t->kind == 1) return pn1_trainer_info(t, n_obj, npts, info);
-    memset(info, 0, sizeof(*info));
-    info->n_weights = t->n_weights;
-    info->chunk_rows = t->chunk_rows;
-    info->n_class = t->layers.back().N;
+    trainer_info_common(t, info);
     info->n_sampling = t->n_sampling;
     for (uint32_t i = 0; i + 1 < t->desc.n_fc; i++) info->keep_per_object += t->desc.fc_widths[i];
-    info->dropout_p = (double)t->dropout_p;
-    info->bn_momentum = t->momentum;
     if (n_obj && npts) {
         Plan P;
         if (!make_plan(t, n_obj, npts, P)) return PCR_ERR_ARG;
@@ -290,60 +214,44 @@ extern "C" int pcr_pn2_train_grad_f32(pcr_ctx* ctx, pcr_pn2_trainer* t, const fl
                                       uint64_t seed, const uint8_t* keep, double* loss, float* logp, float* grad)
 {
     const char* who = "pcr_pn2_train_grad_f32";
-    auto bad = [&](const char* what) { return fail(ctx, PCR_ERR_ARG, (std::string(who) + what).c_str()); };
-    if (!ctx || !t) return fail(ctx, PCR_ERR_ARG, who);
-    if (t->kind != 0) return bad(": the trainer was made by pcr_pn1_trainer_create (use pcr_pointnet_train_grad_f32)");
-    if (t->device != ctx->device) return bad(": the trainer lives on another device");
-    if (npts < 1) return bad(": npts must be >= 1");
-    if (n_obj == 0) return PCR_OK;
-    if (n_obj < 2) return bad(": BatchNorm's batch statistics need n_obj >= 2");
-    if (!objects || !target || !loss || !logp || !grad) return bad(": objects / target / loss / logp / grad is NULL");
+    Plan P;
+    std::vector<uint32_t> st0;               // the first FPS pick of every (sampling layer, object)
+    bool run;
+    int rc = call_head(ctx, t, 0, who, nullptr, !objects || !target || !loss || !logp || !grad, target, n_obj, npts, P, [&]() -> const char* {
+        if (!make_plan(t, n_obj, npts, P)) return ": too large";
+        for (const Stage& st : P.stages)
+            if (st.M < 2) return ": a layer with one row (BatchNorm's batch statistics need two)";
+        st0.resize((size_t)t->n_sampling * n_obj);
+        for (uint32_t l = 0; l < t->n_sampling; l++)
+            for (size_t o = 0; o < n_obj; o++) {
+                uint32_t v;
+                if (starts) {
+                    v = starts[(size_t)l * n_obj + o];
+                    if (v >= P.N[l]) return ": a start outside its object";
+                } else {
+                    v = (uint32_t)(splitmix_key(seed, ((unsigned long long)(l + 1) << 32) | (unsigned long long)o) % (unsigned long long)P.N[l]);
+                }
+                st0[(size_t)l * n_obj + o] = v;
+            }
+        return nullptr;
+    }, run);
+    if (!run) return rc;
     const pcr_pn2_desc& d = t->desc;
     const uint32_t ns = t->n_sampling, D0 = d.D0, C0 = 3 + D0, n_class = t->layers.back().N;
-    for (size_t o = 0; o < n_obj; o++)
-        if (target[o] < 0 || (uint32_t)target[o] >= n_class) return bad(": a target outside [0, n_class)");
-    Plan P;
-    if (!make_plan(t, n_obj, npts, P)) return bad(": too large");
-    for (const Stage& st : P.stages)
-        if (st.M < 2) return bad(": a layer with one row (BatchNorm's batch statistics need two)");
-    std::vector<uint32_t> st0((size_t)ns * n_obj);
-    for (uint32_t l = 0; l < ns; l++)
-        for (size_t o = 0; o < n_obj; o++) {
-            uint32_t v;
-            if (starts) {
-                v = starts[(size_t)l * n_obj + o];
-                if (v >= P.N[l]) return bad(": a start outside its object");
-            } else {
-                v = (uint32_t)(splitmix_key(seed, ((unsigned long long)(l + 1) << 32) | (unsigned long long)o) % (unsigned long long)P.N[l]);
-            }
-            st0[(size_t)l * n_obj + o] = v;
-        }
-    PCR_HIP(ctx, hipSetDevice(ctx->device));
-    int rc = ensure_scratch(ctx, P.total);
-    if (rc) return rc;
-    rc = ensure_stage(ctx, P.upload_bytes);
-    if (rc) return rc;
     const size_t pts = n_obj * npts;
-    P.up.bind(ctx->host_stage);             // the uploaded part, laid out the same way in the pinned staging block
     {
         float *hx = P.x0, *hy = P.x0 + pts, *hz = P.x0 + 2 * pts;
         for (size_t i = 0; i < pts; i++) {
             const float* r = objects + i * C0;
             for (uint32_t c = 0; c < C0; c++)
-                if (!(fabsf(r[c]) <= FLT_MAX)) return bad(": a non-finite coordinate or feature");
+                if (!(fabsf(r[c]) <= FLT_MAX)) return fail(ctx, PCR_ERR_ARG, (std::string(who) + ": a non-finite coordinate or feature").c_str());
             hx[i] = r[0]; hy[i] = r[1]; hz[i] = r[2];
             for (uint32_t c = 0; c < D0; c++) P.feat0[i * D0 + c] = r[3 + c];
         }
-        for (size_t o = 0; o < n_obj; o++) P.target[o] = target[o];
         size_t off = 0;
-        for (uint32_t i = 0; i + 1 < d.n_fc; i++) {              // the masks: the caller's bytes, or K(seed, (0x100 + layer) << 32 | cell) as a uniform in [0, 1) >= p
+        for (uint32_t i = 0; i + 1 < d.n_fc; i++) {              // the masks: the caller's bytes, or the rule
             const size_t cells = n_obj * d.fc_widths[i];
-            for (size_t e = 0; e < cells; e++) {
-                uint8_t k;
-                if (keep) k = keep[off + e] ? 1 : 0;
-                else k = (double)(splitmix_key(seed, ((unsigned long long)(0x100u + i) << 32) | (unsigned long long)e) >> 11) * 0x1.0p-53 >= (double)t->dropout_p ? 1 : 0;
-                P.keep[off + e] = k;
-            }
+            for (size_t e = 0; e < cells; e++) P.keep[off + e] = keep ? (keep[off + e] ? 1 : 0) : keep_rule(seed, i, e, t->dropout_p);
             off += cells;
         }
         for (uint32_t l = 0; l <= ns; l++)
@@ -351,20 +259,16 @@ extern "C" int pcr_pn2_train_grad_f32(pcr_ctx* ctx, pcr_pn2_trainer* t, const fl
         for (uint32_t l = 0; l < ns; l++)
             for (size_t q = 0; q < n_obj * P.N[l + 1]; q++) P.cseg[l][q] = (uint32_t)(q / P.N[l + 1]);
     }
-    P.bind(ctx->scratch);
-    PCR_HIP(ctx, hipMemcpyAsync(ctx->scratch, ctx->host_stage, P.upload_bytes, hipMemcpyHostToDevice, ctx->stream));
-    PCR_HIP(ctx, hipMemsetAsync(t->grad_dev, 0, t->n_weights * 4, ctx->stream));      // +0 where the contract says so: pre-BN biases, the running statistics' slots
-    const float *W = t->w_dev;
-    float* G = t->grad_dev;
-    const uint32_t chunk = t->chunk_rows;
-    const float drop_s = t->dropout_s;
+    rc = call_upload(ctx, t, P);
+    if (rc) return rc;
+    LayerRun R(ctx, t, P, who, launch_gemm, "pn2t_gemm_fwd", "pn2t_gemm_dx");
     HostKeep hold;
     // ---- forward
     const float *cx = P.x0, *cy = P.x0 + pts, *cz = P.x0 + 2 * pts, *feat = P.feat0;
     uint32_t D = D0;
     size_t keep_off = 0;
-    std::vector<const uint8_t*> keep_of(t->layers.size(), nullptr);
-    for (size_t s = 0; s < P.stages.size() && rc == PCR_OK; s++) {
+    std::vector<const uint8_t*> keep_of(t->layers.size(), nullptr);      // the mask of every head layer that has a dropout (fused behind its ReLU)
+    for (size_t s = 0; s < P.stages.size() && R.rc == PCR_OK; s++) {
         const Stage& st = P.stages[s];
         const bool head = st.gsize == 0;
         const float* x = nullptr;
@@ -376,16 +280,16 @@ extern "C" int pcr_pn2_train_grad_f32(pcr_ctx* ctx, pcr_pn2_trainer* t, const fl
                 const size_t nq = n_obj * P.N[s + 1];
                 std::vector<FpsJob> jobs(n_obj);
                 for (size_t o = 0; o < n_obj; o++) jobs[o] = { (uint32_t)(o * P.N[s]), (uint32_t)P.N[s], st0[s * n_obj + o], (uint32_t)o };
-                rc = fps_device(ctx, cx, cy, cz, std::move(jobs), sd.npoint, PCR_FPS_F32, P.fps[s], &hold);
-                if (rc) break;
+                R.rc = fps_device(ctx, cx, cy, cz, std::move(jobs), sd.npoint, PCR_FPS_F32, P.fps[s], &hold);
+                if (R.rc) break;
                 float *wx = P.cxyz[s], *wy = wx + nq, *wz = wy + nq;
                 {
                     ProfScope ps(ctx, "pn2t_centres");
                     hipLaunchKernelGGL(pn2t_centres_kernel, dim3(blocks_for(nq)), dim3(T_BLOCK), 0, ctx->stream, cx, cy, cz, P.fps[s], (uint32_t)P.N[s], sd.npoint, (uint32_t)nq,
                                        wx, wy, wz);
                 }
-                rc = ball_query_device(ctx, cx, cy, cz, wx, wy, wz, P.seg[s], P.cseg[s], nq, sd.radius, sd.nsample, P.bidx[s], P.bcnt[s]);
-                if (rc) break;
+                R.rc = ball_query_device(ctx, cx, cy, cz, wx, wy, wz, P.seg[s], P.cseg[s], nq, sd.radius, sd.nsample, P.bidx[s], P.bcnt[s]);
+                if (R.rc) break;
                 qx = wx; qy = wy; qz = wz;
             }
             {
@@ -398,40 +302,16 @@ extern "C" int pcr_pn2_train_grad_f32(pcr_ctx* ctx, pcr_pn2_trainer* t, const fl
         } else {
             x = feat;
         }
-        const uint32_t chunks = (st.M + chunk - 1) / chunk;
-        for (uint32_t i = st.first; i < st.first + st.count && rc == PCR_OK; i++) {
+        for (uint32_t i = st.first; i < st.first + st.count; i++) {
             const TLayer& L = t->layers[i];
-            GemmArgs g;
-            g.a = x; g.b = W + L.w; g.init = W + L.b; g.c = P.z[i];
-            g.M = st.M; g.N = L.N; g.Kt = L.K; g.chunk = L.K;
-            g.sai = L.K; g.sak = 1; g.sbk = 1; g.sbj = L.K; g.c_stride = 0;
-            rc = launch_gemm(ctx, "pn2t_gemm_fwd", g);
-            if (rc || !L.bn) break;
-            double *mu = P.stat[i], *var = mu + L.N, *rstd = var + L.N;
-            const size_t cells = (size_t)st.M * L.N;
-            {
-                ProfScope ps(ctx, "pn2t_stat");
-                for (int pass = 0; pass < 2; pass++) {
-                    hipLaunchKernelGGL(pn2t_stat_part_kernel, dim3(blocks_for((size_t)chunks * L.N)), dim3(T_BLOCK), 0, ctx->stream, P.z[i], st.M, L.N, chunk, chunks,
-                                       pass ? mu : (const double*)nullptr, P.part);
-                    hipLaunchKernelGGL(pn2t_stat_fin_kernel, dim3(blocks_for(L.N)), dim3(T_BLOCK), 0, ctx->stream, P.part, chunks, L.N, st.M, pass, mu, var, rstd, d.bn_eps,
-                                       t->momentum, t->w_dev + L.rmean, t->w_dev + L.rvar, (float*)nullptr);
-                }
+            if (head && L.bn) {
+                keep_of[i] = P.keep + keep_off;
+                keep_off += (size_t)st.M * L.N;
             }
-            const uint8_t* kp = nullptr;
-            if (head) {
-                kp = P.keep + keep_off;
-                keep_off += cells;
-                keep_of[i] = kp;
-            }
-            {
-                ProfScope ps(ctx, "pn2t_bn_relu");
-                hipLaunchKernelGGL(pn2t_bn_relu_kernel<true>, dim3(blocks_for(cells)), dim3(T_BLOCK), 0, ctx->stream, P.z[i], cells, L.N, mu, rstd, W + L.gamma, W + L.beta, P.y[i], kp,
-                                   drop_s, head ? P.a[i] : (float*)nullptr);
-            }
+            R.fwd(i, x, st.M, true, keep_of[i] ? Drop::fused : Drop::none, keep_of[i]);
             x = head ? P.a[i] : P.y[i];
         }
-        if (rc) break;
+        if (R.rc) break;
         if (!head) {
             const uint32_t last = st.first + st.count - 1, C = t->layers[last].N;
             ProfScope ps(ctx, "pn2t_max");
@@ -441,83 +321,25 @@ extern "C" int pcr_pn2_train_grad_f32(pcr_ctx* ctx, pcr_pn2_trainer* t, const fl
         }
     }
     // ---- the loss, then backward
-    float *cur = P.dyA, *nxt = P.dyB;
-    if (rc == PCR_OK) {
+    if (R.rc == PCR_OK) {
         ProfScope ps(ctx, "pn2t_loss");
-        hipLaunchKernelGGL(pn2t_loss_kernel, dim3(1), dim3(T_BLOCK), 0, ctx->stream, P.z[t->layers.size() - 1], P.target, (uint32_t)n_obj, n_class, P.logp, cur, P.loss);
+        hipLaunchKernelGGL(pn2t_loss_kernel, dim3(1), dim3(T_BLOCK), 0, ctx->stream, P.z[t->layers.size() - 1], P.target, (uint32_t)n_obj, n_class, P.logp, R.cur, P.loss);
     }
-    for (size_t s = P.stages.size(); s-- > 0 && rc == PCR_OK;) {
+    for (size_t s = P.stages.size(); s-- > 0 && R.rc == PCR_OK;) {
         const Stage& st = P.stages[s];
         const bool head = st.gsize == 0;
-        const uint32_t chunks = (st.M + chunk - 1) / chunk;
-        if (!head) {                                             // the gradient of the stage's output -> its last layer's rows
-            const uint32_t last = st.first + st.count - 1, C = t->layers[last].N;
-            const float* dfeat = P.dfeat;
-            float* dst = cur;
-            if (s + 1 == P.stages.size() - 1) { dfeat = cur; dst = nxt; }      // below the head: the head's dx IS the gradient of the global feature
-            {
-                ProfScope ps(ctx, "pn2t_max_back");
-                hipLaunchKernelGGL(pn2t_max_back_kernel, dim3(blocks_for((size_t)st.M * C)), dim3(T_BLOCK), 0, ctx->stream, dfeat, P.arg[s], (size_t)st.M * C, st.gsize, C, dst);
-            }
-            if (dst == nxt) std::swap(cur, nxt);
-        }
-        for (uint32_t i = st.first + st.count; i-- > st.first && rc == PCR_OK;) {
-            const TLayer& L = t->layers[i];
-            const size_t cells = (size_t)st.M * L.N;
+        if (!head)      // the gradient of the stage's output -> its last layer's rows.  Below the head, the head's dx IS the gradient of the global feature
+            R.max_back(s + 2 == P.stages.size() ? R.cur : P.dfeat, P.arg[s], st.M, st.gsize, t->layers[st.first + st.count - 1].N);
+        for (uint32_t i = st.first + st.count; i-- > st.first;) {
             const float* x = i > st.first ? (head ? P.a[i - 1] : P.y[i - 1]) : (head ? P.feat[s - 1] : P.xin[s]);
-            if (L.bn) {
-                double *mu = P.stat[i], *rstd = mu + 2 * (size_t)L.N, *mg = mu + 3 * (size_t)L.N, *mgx = mu + 4 * (size_t)L.N;
-                ProfScope ps(ctx, "pn2t_bn_back");
-                hipLaunchKernelGGL(pn2t_bnb_part_kernel<true>, dim3(blocks_for((size_t)chunks * L.N)), dim3(T_BLOCK), 0, ctx->stream, cur, P.y[i], P.z[i], keep_of[i], drop_s, st.M, L.N,
-                                   chunk, chunks, mu, rstd, P.part);
-                hipLaunchKernelGGL(pn2t_bnb_fin_kernel, dim3(blocks_for(L.N)), dim3(T_BLOCK), 0, ctx->stream, P.part, chunks, L.N, st.M, G + L.gamma, G + L.beta, mg, mgx);
-                hipLaunchKernelGGL(pn2t_bnb_dz_kernel<true>, dim3(blocks_for(cells)), dim3(T_BLOCK), 0, ctx->stream, cur, P.y[i], P.z[i], keep_of[i], drop_s, cells, L.N, mu, rstd,
-                                   W + L.gamma, mg, mgx);
-            } else {                                             // the last FC layer: its bias has a gradient, the column sums of dz
-                ProfScope ps(ctx, "pn2t_stat");
-                hipLaunchKernelGGL(pn2t_stat_part_kernel, dim3(blocks_for((size_t)chunks * L.N)), dim3(T_BLOCK), 0, ctx->stream, cur, st.M, L.N, chunk, chunks,
-                                   (const double*)nullptr, P.part);
-                hipLaunchKernelGGL(pn2t_stat_fin_kernel, dim3(blocks_for(L.N)), dim3(T_BLOCK), 0, ctx->stream, P.part, chunks, L.N, st.M, 2, (double*)nullptr, (double*)nullptr,
-                                   (double*)nullptr, 0.0, 0.0, (float*)nullptr, (float*)nullptr, G + L.b);
-            }
-            {                                                    // dW[n][k] = sum_r dz[r][n] x[r][k]
-                GemmArgs g;
-                g.a = cur; g.b = x; g.init = nullptr; g.c = P.dw_part;
-                g.M = L.N; g.N = L.K; g.Kt = st.M; g.chunk = chunk;
-                g.sai = 1; g.sak = L.N; g.sbk = L.K; g.sbj = 1; g.c_stride = (size_t)L.N * L.K;
-                rc = launch_gemm(ctx, "pn2t_gemm_dw", g);
-                if (rc) break;
-                ProfScope ps(ctx, "pn2t_dw_reduce");
-                hipLaunchKernelGGL(pn2t_dw_reduce_kernel, dim3(blocks_for(g.c_stride)), dim3(T_BLOCK), 0, ctx->stream, P.dw_part, chunks, g.c_stride, G + L.w);
-            }
-            if (i == 0) break;                                   // the input points take no gradient
-            {                                                    // dx[r][k] = sum_n dz[r][n] W[n][k]
-                GemmArgs g;
-                g.a = cur; g.b = W + L.w; g.init = nullptr; g.c = nxt;
-                g.M = st.M; g.N = L.K; g.Kt = L.N; g.chunk = L.N;
-                g.sai = L.N; g.sak = 1; g.sbk = L.K; g.sbj = 1; g.c_stride = 0;
-                rc = launch_gemm(ctx, "pn2t_gemm_dx", g);
-                if (rc) break;
-                std::swap(cur, nxt);
-            }
+            R.bwd(i, x, st.M, true, i != 0, keep_of[i] ? Drop::fused : Drop::none, keep_of[i]);      // layer 0: the input points take no gradient
         }
-        if (rc == PCR_OK && !head && s > 0) {                    // the feature columns of dx back to the points of the stage before
+        if (R.rc == PCR_OK && !head && s > 0) {                  // the feature columns of dx back to the points of the stage before
             const uint32_t Dp = t->sa_in[s] - 3;
             const uint32_t points = (uint32_t)(n_obj * P.N[s]);
             ProfScope ps(ctx, "pn2t_gather_back");
-            hipLaunchKernelGGL(pn2t_gather_back_kernel, dim3(points), dim3(T_BLOCK), 0, ctx->stream, cur, P.row_pt[s], points, (uint32_t)P.N[s], st.M / (uint32_t)n_obj, Dp, P.dfeat);
+            hipLaunchKernelGGL(pn2t_gather_back_kernel, dim3(points), dim3(T_BLOCK), 0, ctx->stream, R.cur, P.row_pt[s], points, (uint32_t)P.N[s], st.M / (uint32_t)n_obj, Dp, P.dfeat);
         }
     }
-    hipError_t e = hipSuccess;
-    if (rc == PCR_OK) {
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(logp, P.logp, n_obj * n_class * 4, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(loss, P.loss, 8, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(grad, G, t->n_weights * 4, hipMemcpyDeviceToHost, ctx->stream);
-    }
-    const hipError_t e2 = hipStreamSynchronize(ctx->stream);      // the one wait: `hold` and the staging block are read until here
-    if (rc) return rc;
-    if (e != hipSuccess || e2 != hipSuccess) return fail(ctx, PCR_ERR_HIP, who, e != hipSuccess ? e : e2);
-    prof_flush(ctx);
-    return PCR_OK;
+    return call_tail(ctx, t, who, R.rc, P, n_obj, logp, loss, 1, grad);      // `hold` lives until its wait is over
 }

@@ -2,19 +2,21 @@
 // regulariser, the gradient of every parameter (models/pointnet_cls.py, models/pointnet.py; train_cls.py's step without its optimiser).  The contract is
 // written out above pcr_pn1_trainer_create in include/pcr.h.
 //
-// The dW product, the statistics, BatchNorm / ReLU, the max after a ReLU and the NLL are pointnet_train_common.hpp's (pn2t_*).  What this model adds:
+// The dW product, the statistics, BatchNorm / ReLU, the max after a ReLU, the NLL (pn2t_*) and pn1t_dropout (the head's dropout BEFORE BatchNorm, in place:
+// forward on the product, backward on its gradient) are pointnet_train_common.hpp's, and so are the layer step (LayerRun, here on the blocked product), the plan
+// base and the create / info / call head and tail.  What this model adds:
 //   pn1t_gemm_fwd / pn1t_gemm_dx     z = x W^T + b and dx = dz W on the same MFMA tiles, blocked over k: f32 chains over 64 k, the blocks added in f64
 //   pn1t_transform3    xyz . trans per object in plain fmaf, the features pass through
 //   pn1t_transform     x . T (forward) or dy . T^T (backward) per object: a workgroup serves rows of ONE object, its K x K matrix staged in LDS in the
 //                      operand order of v_mfma_f32_16x16x4_f32; every output is one chain from +0 over ascending k
 //   pn1t_identity      + 1 on the diagonal entries of a T-Net's last layer
 //   pn1t_smax          the SIGNED max over an object's points on the integer key that orders all floats, the lowest position among the maxima
-//   pn1t_dropout       the head's dropout BEFORE BatchNorm, in place: forward on the product, backward on its gradient
 //   pn1t_reg           per object, in f64: M = A A^T - A, its Frobenius norm, and dA
 //   pn1t_loss_fin      reg = the mean of the norms, total = nll + reg_scale reg
 //   pn1t_add           one f32 addition per element: the two gradient paths into conv 0's activation, dA into dT
 // dT[b] = x[b]^T dy[b] is the shared dW product with one chunk per object (pn1t_gemm_dt).  No floating-point atomic anywhere.
 #include "pointnet_train_common.hpp"
+#include "f32_key.hpp"
 
 namespace {
 
@@ -96,7 +98,7 @@ __global__ __launch_bounds__(T_BLOCK) void pn1t_gemm_kernel(const GemmArgs g)
 }
 
 // the blocked product of one stage: z (from the bias) or dx (from +0)
-int launch_gemm1(pcr_ctx* ctx, const char* prof, const GemmArgs& g)
+int launch_gemm1(pcr_ctx* ctx, const char* prof, const GemmArgs& g, const char*)
 {
     if (g.M == 0 || g.N == 0) return PCR_OK;
     ProfScope ps(ctx, prof);
@@ -175,12 +177,6 @@ __global__ __launch_bounds__(T_BLOCK) void pn1t_identity_kernel(float* __restric
     *p = *p + 1.0f;
 }
 
-__device__ __forceinline__ uint32_t pn1t_key(float v)
-{
-    const uint32_t u = __float_as_uint(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 // feat[g][c] = the max over the gsize rows of group g in the order -inf < ... < -0 < +0 < ... < +inf; arg[g][c] = the lowest position that holds it
 __global__ __launch_bounds__(T_BLOCK) void pn1t_smax_kernel(const float* __restrict__ y, uint32_t groups, uint32_t gsize, uint32_t N, float* __restrict__ feat,
                                                             uint32_t* __restrict__ arg)
@@ -190,22 +186,14 @@ __global__ __launch_bounds__(T_BLOCK) void pn1t_smax_kernel(const float* __restr
     const uint32_t g = (uint32_t)(e / N), c = (uint32_t)(e - (size_t)g * N);
     const float* p = y + (size_t)g * gsize * N + c;
     float m = p[0];
-    uint32_t mk = pn1t_key(m), best = 0;
+    uint32_t mk = f32_key(m), best = 0;
     for (uint32_t k = 1; k < gsize; k++) {
         const float v = p[(size_t)k * N];
-        const uint32_t vk = pn1t_key(v);
+        const uint32_t vk = f32_key(v);
         if (vk > mk) { m = v; mk = vk; best = k; }
     }
     feat[e] = m;
     arg[e] = best;
-}
-
-// v <- keep ? v s : +0
-__global__ __launch_bounds__(T_BLOCK) void pn1t_dropout_kernel(float* __restrict__ v, const uint8_t* __restrict__ keep, float s, size_t total)
-{
-    const size_t e = (size_t)blockIdx.x * T_BLOCK + threadIdx.x;
-    if (e >= total) return;
-    v[e] = keep[e] ? v[e] * s : 0.0f;
 }
 
 __global__ __launch_bounds__(T_BLOCK) void pn1t_add_kernel(const float* a, const float* b, size_t total, float* out)      // out may be a or b
@@ -286,66 +274,33 @@ bool trainer1_shapes(const pcr_pn1_desc& d, pcr_pn2_trainer& t)
             if (w < 1 || w > T_MAX_WIDTH) return false;
     }
     if (d.fstn && d.widths[0] > T1_MAX_K) return false;
-    size_t off = 0;
-    auto push = [&](uint32_t K, uint32_t N, bool bn) {
-        TLayer L;
-        L.K = K; L.N = N; L.bn = bn;
-        L.w = off; off += (size_t)K * N;
-        L.b = off; off += N;
-        L.gamma = L.beta = L.rmean = L.rvar = 0;
-        if (bn) { L.gamma = off; L.beta = off + N; L.rmean = off + 2 * (size_t)N; L.rvar = off + 3 * (size_t)N; off += 4 * (size_t)N; }
-        t.layers.push_back(L);
-    };
     auto tnet = [&](uint32_t cin, uint32_t k) {      // the last layer has k k outputs (up to 16 384): T_MAX_WIDTH does not apply to it
-        for (uint32_t w : d.tnet_conv) { push(cin, w, true); cin = w; }
-        for (uint32_t w : d.tnet_fc) { push(cin, w, true); cin = w; }
-        push(cin, k * k, false);
+        for (uint32_t w : d.tnet_conv) { layer_push(t, cin, w, true); cin = w; }
+        for (uint32_t w : d.tnet_fc) { layer_push(t, cin, w, true); cin = w; }
+        layer_push(t, cin, k * k, false);
     };
     const uint32_t C0 = 3 + d.D0;
     t.stn_first = 0;
     if (d.stn3) tnet(C0, 3);
     t.enc_first = (uint32_t)t.layers.size();
     uint32_t K = C0;
-    for (uint32_t i = 0; i < d.n_mlp; i++) { push(K, d.widths[i], true); K = d.widths[i]; }
+    for (uint32_t i = 0; i < d.n_mlp; i++) { layer_push(t, K, d.widths[i], true); K = d.widths[i]; }
     t.fstn_first = (uint32_t)t.layers.size();
     if (d.fstn) tnet(d.widths[0], d.widths[0]);
     t.head_first = (uint32_t)t.layers.size();
-    for (uint32_t i = 0; i < d.n_fc; i++) { push(K, d.fc_widths[i], i + 1 < d.n_fc); K = d.fc_widths[i]; }
-    t.n_weights = off;
+    for (uint32_t i = 0; i < d.n_fc; i++) { layer_push(t, K, d.fc_widths[i], i + 1 < d.n_fc); K = d.fc_widths[i]; }
     t.n_sampling = 0;
     return true;
 }
 
-// the device block of one call: Layouts (scratch_layout.hpp) laid one behind the other
-struct Plan1 {
+// the device block of one call: PlanBase's, with the per-stack buffers in `own`
+struct Plan1 : PlanBase {
     uint32_t rows = 0, n_obj = 0, npts = 0;
-    // uploaded
-    float* obj = nullptr;
-    int32_t* target = nullptr;
-    uint8_t* keep = nullptr;
-    size_t upload_bytes = 0;
-    // per layer
-    std::vector<float*> z, y;
-    std::vector<double*> stat;       // 5 N doubles: mu, var, rstd, mean_g, mean_gx
+    float* obj = nullptr;            // uploaded
     // per stack
     float *xt = nullptr, *xf = nullptr, *feat_s = nullptr, *feat_f = nullptr, *gfeat = nullptr, *g1 = nullptr, *dA = nullptr;
     uint32_t *arg_s = nullptr, *arg_f = nullptr, *garg = nullptr;
     double *Mb = nullptr, *norm = nullptr;
-    // shared
-    float *dyA = nullptr, *dyB = nullptr, *dw_part = nullptr, *logp = nullptr;
-    double *part = nullptr, *loss = nullptr;
-    Layout up, mid, work;
-    std::vector<Layout> per_layer;
-    size_t total = 0;
-
-    void bind(void* base)
-    {
-        char* p = (char*)base;
-        up.bind(p); p += up.bytes();
-        mid.bind(p); p += mid.bytes();
-        work.bind(p); p += work.bytes();
-        for (Layout& L : per_layer) { L.bind(p); p += L.bytes(); }
-    }
 };
 
 inline uint32_t keep_width(const pcr_pn1_desc& d) { return d.n_fc >= 2 ? d.fc_widths[d.n_fc - 2] : 0u; }
@@ -361,163 +316,40 @@ bool make_plan1(const pcr_pn2_trainer* t, size_t n_obj, size_t npts, Plan1& P)
     P.up.add(&P.obj, rows * C0);
     P.up.add(&P.target, n_obj);
     P.up.add(&P.keep, n_obj * keep_width(d));
-    P.upload_bytes = P.up.bytes();
     const uint32_t Ct = d.tnet_conv[2], Cg = d.widths[d.n_mlp - 1];
-    P.mid.add(&P.xt, d.stn3 ? rows * C0 : 0);
-    P.mid.add(&P.feat_s, d.stn3 ? n_obj * Ct : 0);
-    P.mid.add(&P.arg_s, d.stn3 ? n_obj * Ct : 0);
-    P.mid.add(&P.xf, d.fstn ? rows * K : 0);
-    P.mid.add(&P.g1, d.fstn ? rows * K : 0);
-    P.mid.add(&P.feat_f, d.fstn ? n_obj * Ct : 0);
-    P.mid.add(&P.arg_f, d.fstn ? n_obj * Ct : 0);
-    P.mid.add(&P.dA, d.fstn ? n_obj * K * K : 0);
-    P.mid.add(&P.Mb, d.fstn ? n_obj * K * K : 0);
-    P.mid.add(&P.norm, d.fstn ? n_obj : 0);
-    P.mid.add(&P.gfeat, n_obj * Cg);
-    P.mid.add(&P.garg, n_obj * Cg);
+    P.own.add(&P.xt, d.stn3 ? rows * C0 : 0);
+    P.own.add(&P.feat_s, d.stn3 ? n_obj * Ct : 0);
+    P.own.add(&P.arg_s, d.stn3 ? n_obj * Ct : 0);
+    P.own.add(&P.xf, d.fstn ? rows * K : 0);
+    P.own.add(&P.g1, d.fstn ? rows * K : 0);
+    P.own.add(&P.feat_f, d.fstn ? n_obj * Ct : 0);
+    P.own.add(&P.arg_f, d.fstn ? n_obj * Ct : 0);
+    P.own.add(&P.dA, d.fstn ? n_obj * K * K : 0);
+    P.own.add(&P.Mb, d.fstn ? n_obj * K * K : 0);
+    P.own.add(&P.norm, d.fstn ? n_obj : 0);
+    P.own.add(&P.gfeat, n_obj * Cg);
+    P.own.add(&P.garg, n_obj * Cg);
     const size_t nl = t->layers.size();
-    P.z.assign(nl, nullptr); P.y.assign(nl, nullptr); P.stat.assign(nl, nullptr);
-    P.per_layer.assign(nl, Layout());
-    size_t dy_cells = std::max(rows * C0, n_obj * (size_t)K * K), part_cells = 1, dw_cells = n_obj * (size_t)K * K;
+    P.layers(nl, 0);
+    P.dy_cells = std::max(rows * C0, n_obj * (size_t)K * K);     // the gradient of the input rows; dT
+    P.dw_cells = n_obj * (size_t)K * K;                          // dT: one chunk per object
     auto is_conv = [&](size_t i) {
         if (d.stn3 && i < t->stn_first + 3u) return true;
         if (i >= t->enc_first && i < t->fstn_first) return true;
         return d.fstn && i >= t->fstn_first && i < t->fstn_first + 3u;
     };
-    for (size_t i = 0; i < nl; i++) {
-        const TLayer& Ly = t->layers[i];
-        const size_t M = is_conv(i) ? rows : n_obj;
-        const size_t chunks = (M + t->chunk_rows - 1) / t->chunk_rows;
-        Layout& L = P.per_layer[i];
-        L.add(&P.z[i], M * Ly.N);
-        L.add(&P.y[i], Ly.bn ? M * Ly.N : 0);
-        L.add(&P.stat[i], 5 * (size_t)Ly.N);
-        dy_cells = std::max(dy_cells, M * std::max(Ly.N, Ly.K));
-        part_cells = std::max(part_cells, 2 * chunks * Ly.N);
-        dw_cells = std::max(dw_cells, chunks * Ly.N * Ly.K);
-    }
-    P.work.add(&P.dyA, dy_cells);
-    P.work.add(&P.dyB, dy_cells);
-    P.work.add(&P.dw_part, dw_cells);
-    P.work.add(&P.part, part_cells);
-    P.work.add(&P.logp, n_obj * t->layers.back().N);
-    P.work.add(&P.loss, (size_t)3);
-    P.total = P.up.bytes() + P.mid.bytes() + P.work.bytes();
-    for (const Layout& L : P.per_layer) P.total += L.bytes();
+    for (size_t i = 0; i < nl; i++) P.add_layer(i, is_conv(i) ? rows : n_obj, t->layers[i], t->chunk_rows, false);
+    P.finish(n_obj, t->layers.back().N, 3);
     return true;
 }
 
 const char* const WHO1 = "pcr_pointnet_train_grad_f32";
 
-// one call's launches
-struct Run1 {
-    pcr_ctx* ctx;
-    pcr_pn2_trainer* t;
-    Plan1& P;
-    const float* W;
-    float* G;
-    uint32_t chunk;
-    float *cur, *nxt;
-    int rc = PCR_OK;
+// LayerRun on the blocked product, and what the T-Nets add to it
+struct ClsRun : LayerRun {
+    Plan1& P;                // LayerRun's plan, with this model's fields in reach
 
-    uint32_t chunks_of(uint32_t M) const { return (M + chunk - 1) / chunk; }
-
-    // z = x W^T + b (-> the dropout in place) -> the statistics -> y = BN(z), with or without the ReLU
-    void fwd(uint32_t i, const float* x, uint32_t M, bool relu, const uint8_t* keep = nullptr)
-    {
-        if (rc) return;
-        const TLayer& L = t->layers[i];
-        GemmArgs g;
-        g.a = x; g.b = W + L.w; g.init = W + L.b; g.c = P.z[i];
-        g.M = M; g.N = L.N; g.Kt = L.K; g.chunk = L.K;
-        g.sai = L.K; g.sak = 1; g.sbk = 1; g.sbj = L.K; g.c_stride = 0;
-        rc = launch_gemm1(ctx, "pn1t_gemm_fwd", g);
-        if (rc) return;
-        const size_t cells = (size_t)M * L.N;
-        if (keep) {
-            ProfScope ps(ctx, "pn1t_dropout");
-            hipLaunchKernelGGL(pn1t_dropout_kernel, dim3(blocks_for(cells)), dim3(T_BLOCK), 0, ctx->stream, P.z[i], keep, t->dropout_s, cells);
-        }
-        if (!L.bn) return;
-        const uint32_t chunks = chunks_of(M);
-        double *mu = P.stat[i], *var = mu + L.N, *rstd = var + L.N;
-        {
-            ProfScope ps(ctx, "pn2t_stat");
-            for (int pass = 0; pass < 2; pass++) {
-                hipLaunchKernelGGL(pn2t_stat_part_kernel, dim3(blocks_for((size_t)chunks * L.N)), dim3(T_BLOCK), 0, ctx->stream, P.z[i], M, L.N, chunk, chunks,
-                                   pass ? mu : (const double*)nullptr, P.part);
-                hipLaunchKernelGGL(pn2t_stat_fin_kernel, dim3(blocks_for(L.N)), dim3(T_BLOCK), 0, ctx->stream, P.part, chunks, L.N, M, pass, mu, var, rstd, t->desc1.bn_eps,
-                                   t->momentum, t->w_dev + L.rmean, t->w_dev + L.rvar, (float*)nullptr);
-            }
-        }
-        ProfScope ps(ctx, "pn2t_bn_relu");
-        if (relu)
-            hipLaunchKernelGGL(pn2t_bn_relu_kernel<true>, dim3(blocks_for(cells)), dim3(T_BLOCK), 0, ctx->stream, P.z[i], cells, L.N, mu, rstd, W + L.gamma, W + L.beta, P.y[i],
-                               (const uint8_t*)nullptr, 1.0f, (float*)nullptr);
-        else
-            hipLaunchKernelGGL(pn2t_bn_relu_kernel<false>, dim3(blocks_for(cells)), dim3(T_BLOCK), 0, ctx->stream, P.z[i], cells, L.N, mu, rstd, W + L.gamma, W + L.beta, P.y[i],
-                               (const uint8_t*)nullptr, 1.0f, (float*)nullptr);
-    }
-
-    // the column sums of cur -> the bias gradient
-    void bias_grad(const TLayer& L, uint32_t M)
-    {
-        const uint32_t chunks = chunks_of(M);
-        ProfScope ps(ctx, "pn2t_stat");
-        hipLaunchKernelGGL(pn2t_stat_part_kernel, dim3(blocks_for((size_t)chunks * L.N)), dim3(T_BLOCK), 0, ctx->stream, cur, M, L.N, chunk, chunks, (const double*)nullptr,
-                           P.part);
-        hipLaunchKernelGGL(pn2t_stat_fin_kernel, dim3(blocks_for(L.N)), dim3(T_BLOCK), 0, ctx->stream, P.part, chunks, L.N, M, 2, (double*)nullptr, (double*)nullptr,
-                           (double*)nullptr, 0.0, 0.0, (float*)nullptr, (float*)nullptr, G + L.b);
-    }
-
-    // cur holds the gradient at the layer's output (y, or z without BN) -> the parameter gradients; with need_dx, cur <- the gradient of x
-    void bwd(uint32_t i, const float* x, uint32_t M, bool relu, bool need_dx, const uint8_t* keep = nullptr)
-    {
-        if (rc) return;
-        const TLayer& L = t->layers[i];
-        const size_t cells = (size_t)M * L.N;
-        const uint32_t chunks = chunks_of(M);
-        if (L.bn) {
-            double *mu = P.stat[i], *rstd = mu + 2 * (size_t)L.N, *mg = mu + 3 * (size_t)L.N, *mgx = mu + 4 * (size_t)L.N;
-            ProfScope ps(ctx, "pn2t_bn_back");
-            const uint8_t* nk = nullptr;
-            if (relu) {
-                hipLaunchKernelGGL(pn2t_bnb_part_kernel<true>, dim3(blocks_for((size_t)chunks * L.N)), dim3(T_BLOCK), 0, ctx->stream, cur, P.y[i], P.z[i], nk, 1.0f, M, L.N, chunk,
-                                   chunks, mu, rstd, P.part);
-                hipLaunchKernelGGL(pn2t_bnb_fin_kernel, dim3(blocks_for(L.N)), dim3(T_BLOCK), 0, ctx->stream, P.part, chunks, L.N, M, G + L.gamma, G + L.beta, mg, mgx);
-                hipLaunchKernelGGL(pn2t_bnb_dz_kernel<true>, dim3(blocks_for(cells)), dim3(T_BLOCK), 0, ctx->stream, cur, P.y[i], P.z[i], nk, 1.0f, cells, L.N, mu, rstd, W + L.gamma,
-                                   mg, mgx);
-            } else {
-                hipLaunchKernelGGL(pn2t_bnb_part_kernel<false>, dim3(blocks_for((size_t)chunks * L.N)), dim3(T_BLOCK), 0, ctx->stream, cur, P.y[i], P.z[i], nk, 1.0f, M, L.N, chunk,
-                                   chunks, mu, rstd, P.part);
-                hipLaunchKernelGGL(pn2t_bnb_fin_kernel, dim3(blocks_for(L.N)), dim3(T_BLOCK), 0, ctx->stream, P.part, chunks, L.N, M, G + L.gamma, G + L.beta, mg, mgx);
-                hipLaunchKernelGGL(pn2t_bnb_dz_kernel<false>, dim3(blocks_for(cells)), dim3(T_BLOCK), 0, ctx->stream, cur, P.y[i], P.z[i], nk, 1.0f, cells, L.N, mu, rstd, W + L.gamma,
-                                   mg, mgx);
-            }
-        }
-        if (keep) {
-            ProfScope ps(ctx, "pn1t_dropout");
-            hipLaunchKernelGGL(pn1t_dropout_kernel, dim3(blocks_for(cells)), dim3(T_BLOCK), 0, ctx->stream, cur, keep, t->dropout_s, cells);
-        }
-        if (!L.bn || keep) bias_grad(L, M);
-        {                                                        // dW[n][k] = sum_r dz[r][n] x[r][k]
-            GemmArgs g;
-            g.a = cur; g.b = x; g.init = nullptr; g.c = P.dw_part;
-            g.M = L.N; g.N = L.K; g.Kt = M; g.chunk = chunk;
-            g.sai = 1; g.sak = L.N; g.sbk = L.K; g.sbj = 1; g.c_stride = (size_t)L.N * L.K;
-            rc = launch_gemm(ctx, "pn2t_gemm_dw", g, WHO1);
-            if (rc) return;
-            ProfScope ps(ctx, "pn2t_dw_reduce");
-            hipLaunchKernelGGL(pn2t_dw_reduce_kernel, dim3(blocks_for(g.c_stride)), dim3(T_BLOCK), 0, ctx->stream, P.dw_part, chunks, g.c_stride, G + L.w);
-        }
-        if (!need_dx) return;
-        GemmArgs g;                                              // dx[r][k] = sum_n dz[r][n] W[n][k]
-        g.a = cur; g.b = W + L.w; g.init = nullptr; g.c = nxt;
-        g.M = M; g.N = L.K; g.Kt = L.N; g.chunk = L.N;
-        g.sai = L.N; g.sak = 1; g.sbk = L.K; g.sbj = 1; g.c_stride = 0;
-        rc = launch_gemm1(ctx, "pn1t_gemm_dx", g);
-        if (rc == PCR_OK) std::swap(cur, nxt);
-    }
+    ClsRun(pcr_ctx* c, pcr_pn2_trainer* tr, Plan1& plan) : LayerRun(c, tr, plan, WHO1, launch_gemm1, "pn1t_gemm_fwd", "pn1t_gemm_dx"), P(plan) {}
 
     // a T-Net: x (rows x cin) -> its k x k matrices, identity added, in P.z[first + 5]
     void tnet_fwd(uint32_t first, const float* x, uint32_t k, float* feat, uint32_t* arg)
@@ -539,21 +371,13 @@ struct Run1 {
         hipLaunchKernelGGL(pn1t_identity_kernel, dim3(blocks_for((size_t)P.n_obj * k)), dim3(T_BLOCK), 0, ctx->stream, P.z[first + 5], (size_t)P.n_obj, k);
     }
 
-    void max_back(const uint32_t* arg, uint32_t C)
-    {
-        if (rc) return;
-        ProfScope ps(ctx, "pn2t_max_back");
-        hipLaunchKernelGGL(pn2t_max_back_kernel, dim3(blocks_for((size_t)P.rows * C)), dim3(T_BLOCK), 0, ctx->stream, cur, arg, (size_t)P.rows * C, P.npts, C, nxt);
-        std::swap(cur, nxt);
-    }
-
     // cur holds the gradient of the T-Net's matrices; with need_dx, cur <- the gradient of x
     void tnet_bwd(uint32_t first, const float* x, const float* feat, const uint32_t* arg, bool need_dx)
     {
         bwd(first + 5, P.y[first + 4], P.n_obj, false, true);
         bwd(first + 4, P.y[first + 3], P.n_obj, true, true);
         bwd(first + 3, feat, P.n_obj, true, true);
-        max_back(arg, t->layers[first + 2].N);
+        max_back(cur, arg, P.rows, P.npts, t->layers[first + 2].N);
         bwd(first + 2, P.y[first + 1], P.rows, true, true);
         bwd(first + 1, P.y[first], P.rows, true, true);
         bwd(first, x, P.rows, true, need_dx);
@@ -591,14 +415,8 @@ struct Run1 {
 
 int pcr::pn1_trainer_info(const pcr_pn2_trainer* t, size_t n_obj, size_t npts, pcr_pn2_train_info* info)
 {
-    memset(info, 0, sizeof(*info));
-    info->n_weights = t->n_weights;
-    info->chunk_rows = t->chunk_rows;
-    info->n_class = t->layers.back().N;
-    info->n_sampling = 0;
+    trainer_info_common(t, info);
     info->keep_per_object = keep_width(t->desc1);
-    info->dropout_p = (double)t->dropout_p;
-    info->bn_momentum = t->momentum;
     if (n_obj && npts) {
         Plan1 P;
         if (!make_plan1(t, n_obj, npts, P)) return PCR_ERR_ARG;
@@ -618,69 +436,32 @@ extern "C" int pcr_pn1_trainer_create(pcr_ctx* ctx, const pcr_pn1_desc* desc, co
     t->desc1 = *desc;
     t->desc.bn_eps = desc->bn_eps;
     if (!trainer1_shapes(*desc, *t)) return fail(ctx, PCR_ERR_ARG, "pcr_pn1_trainer_create: a descriptor outside the limits (see include/pcr.h)");
-    if (!(dropout_p >= 0.0 && dropout_p < 1.0)) return fail(ctx, PCR_ERR_ARG, "pcr_pn1_trainer_create: dropout_p must lie in [0, 1)");
-    if (!(bn_momentum >= 0.0 && bn_momentum <= 1.0)) return fail(ctx, PCR_ERR_ARG, "pcr_pn1_trainer_create: bn_momentum must lie in [0, 1]");
-    if (!std::isfinite(reg_scale)) return fail(ctx, PCR_ERR_ARG, "pcr_pn1_trainer_create: reg_scale must be finite");
-    if (n_weights != t->n_weights) return fail(ctx, PCR_ERR_ARG, "pcr_pn1_trainer_create: n_weights is not the model's count");
-    if (const char* what = weights_ok(t.get(), weights)) return fail(ctx, PCR_ERR_ARG, (std::string("pcr_pn1_trainer_create") + what).c_str());
-    t->dropout_p = (float)dropout_p;
-    t->dropout_s = (float)(1.0 / (1.0 - dropout_p));
-    t->momentum = bn_momentum;
     t->reg_scale = reg_scale;
-    t->chunk_rows = chunk_rows ? chunk_rows : T_DEFAULT_CHUNK;
-    t->device = ctx->device;
-    PCR_HIP(ctx, hipSetDevice(ctx->device));
-    PCR_HIP(ctx, hipMalloc((void**)&t->w_dev, t->n_weights * 4));
-    hipError_t e = hipMalloc((void**)&t->grad_dev, t->n_weights * 4);
-    if (e == hipSuccess) e = hipMemcpy(t->w_dev, weights, t->n_weights * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(t->grad_dev, 0, t->n_weights * 4);
-    if (e != hipSuccess) {
-        (void)hipFree(t->w_dev);
-        if (t->grad_dev) (void)hipFree(t->grad_dev);
-        return fail(ctx, PCR_ERR_HIP, "pcr_pn1_trainer_create: the upload of the weights", e);
-    }
-    *out = t.release();
-    return PCR_OK;
+    return trainer_finish(ctx, "pcr_pn1_trainer_create", std::move(t), std::isfinite(reg_scale) ? nullptr : ": reg_scale must be finite", weights, n_weights, dropout_p,
+                          bn_momentum, chunk_rows, out);
 }
 
 extern "C" int pcr_pointnet_train_grad_f32(pcr_ctx* ctx, pcr_pn2_trainer* t, const float* objects, size_t n_obj, size_t npts, const int32_t* target, uint64_t seed,
                                            const uint8_t* keep, double* loss, float* logp, float* trans, float* trans_feat, float* grad)
 {
     const char* who = WHO1;
-    auto bad = [&](const char* what) { return fail(ctx, PCR_ERR_ARG, (std::string(who) + what).c_str()); };
-    if (!ctx || !t) return fail(ctx, PCR_ERR_ARG, who);
-    if (t->kind != 1) return bad(": the trainer was made by pcr_pn2_trainer_create (use pcr_pn2_train_grad_f32)");
-    if (t->device != ctx->device) return bad(": the trainer lives on another device");
-    const pcr_pn1_desc& d = t->desc1;
-    if (npts < 1) return bad(": npts must be >= 1");
-    if ((trans && !d.stn3) || (trans_feat && !d.fstn)) return bad(": trans / trans_feat must be NULL when the model has no such T-Net");
-    if (n_obj == 0) return PCR_OK;
-    if (n_obj < 2) return bad(": BatchNorm's batch statistics need n_obj >= 2");
-    if (!objects || !target || !loss || !logp || !grad) return bad(": objects / target / loss / logp / grad is NULL");
-    const uint32_t C0 = 3 + d.D0, K = d.widths[0], n_class = t->layers.back().N, kw = keep_width(d);
-    for (size_t o = 0; o < n_obj; o++)
-        if (target[o] < 0 || (uint32_t)target[o] >= n_class) return bad(": a target outside [0, n_class)");
+    const char* own_bad = t && ((trans && !t->desc1.stn3) || (trans_feat && !t->desc1.fstn)) ? ": trans / trans_feat must be NULL when the model has no such T-Net" : nullptr;
     Plan1 P;
-    if (!make_plan1(t, n_obj, npts, P)) return bad(": too large");
-    PCR_HIP(ctx, hipSetDevice(ctx->device));
-    int rc = ensure_scratch(ctx, P.total);
-    if (rc) return rc;
-    rc = ensure_stage(ctx, P.upload_bytes);
-    if (rc) return rc;
+    bool run;
+    int rc = call_head(ctx, t, 1, who, own_bad, !objects || !target || !loss || !logp || !grad, target, n_obj, npts, P,
+                       [&]() -> const char* { return make_plan1(t, n_obj, npts, P) ? nullptr : ": too large"; }, run);
+    if (!run) return rc;
+    const pcr_pn1_desc& d = t->desc1;
+    const uint32_t C0 = 3 + d.D0, K = d.widths[0], n_class = t->layers.back().N, kw = keep_width(d);
     const size_t rows = n_obj * npts;
-    P.up.bind(ctx->host_stage);             // the uploaded part, laid out the same way in the pinned staging block
     for (size_t i = 0; i < rows * C0; i++) {
-        if (!(fabsf(objects[i]) <= FLT_MAX)) return bad(": a non-finite coordinate or feature");
+        if (!(fabsf(objects[i]) <= FLT_MAX)) return fail(ctx, PCR_ERR_ARG, (std::string(who) + ": a non-finite coordinate or feature").c_str());
         P.obj[i] = objects[i];
     }
-    for (size_t o = 0; o < n_obj; o++) P.target[o] = target[o];
-    for (size_t e = 0; e < n_obj * kw; e++)      // the mask: the caller's bytes, or K(seed, (0x100 + layer) << 32 | cell) as a uniform in [0, 1) >= p
-        P.keep[e] = keep ? (keep[e] ? 1 : 0)
-                         : ((double)(splitmix_key(seed, ((unsigned long long)(0x100u + d.n_fc - 2u) << 32) | (unsigned long long)e) >> 11) * 0x1.0p-53 >= (double)t->dropout_p ? 1 : 0);
-    P.bind(ctx->scratch);
-    PCR_HIP(ctx, hipMemcpyAsync(ctx->scratch, ctx->host_stage, P.upload_bytes, hipMemcpyHostToDevice, ctx->stream));
-    PCR_HIP(ctx, hipMemsetAsync(t->grad_dev, 0, t->n_weights * 4, ctx->stream));      // +0 where the contract says so
-    Run1 R{ ctx, t, P, t->w_dev, t->grad_dev, t->chunk_rows, P.dyA, P.dyB };
+    for (size_t e = 0; e < n_obj * kw; e++) P.keep[e] = keep ? (keep[e] ? 1 : 0) : keep_rule(seed, d.n_fc - 2u, e, t->dropout_p);      // the mask: the caller's bytes, or the rule
+    rc = call_upload(ctx, t, P);
+    if (rc) return rc;
+    ClsRun R(ctx, t, P);
     const uint32_t M = P.rows, nm = d.n_mlp, e0 = t->enc_first, s0 = t->stn_first, f0 = t->fstn_first, h0 = t->head_first;
     const uint32_t drop_layer = d.n_fc >= 2 ? h0 + d.n_fc - 2 : T_NONE;
     const float *T3 = nullptr, *TK = nullptr;
@@ -710,7 +491,7 @@ extern "C" int pcr_pointnet_train_grad_f32(pcr_ctx* ctx, pcr_pn2_trainer* t, con
         hipLaunchKernelGGL(pn1t_smax_kernel, dim3(blocks_for(n_obj * Cg)), dim3(T_BLOCK), 0, ctx->stream, P.y[e0 + nm - 1], (uint32_t)n_obj, (uint32_t)npts, Cg, P.gfeat, P.garg);
     }
     for (uint32_t i = 0; i < d.n_fc; i++)
-        R.fwd(h0 + i, i == 0 ? P.gfeat : P.y[h0 + i - 1], (uint32_t)n_obj, true, h0 + i == drop_layer ? P.keep : nullptr);
+        R.fwd(h0 + i, i == 0 ? P.gfeat : P.y[h0 + i - 1], (uint32_t)n_obj, true, h0 + i == drop_layer ? Drop::pre_bn : Drop::none, P.keep);
     // ---- the loss
     if (R.rc == PCR_OK) {
         {
@@ -726,8 +507,8 @@ extern "C" int pcr_pointnet_train_grad_f32(pcr_ctx* ctx, pcr_pn2_trainer* t, con
     }
     // ---- backward
     for (uint32_t i = d.n_fc; i-- > 0;)
-        R.bwd(h0 + i, i == 0 ? P.gfeat : P.y[h0 + i - 1], (uint32_t)n_obj, true, true, h0 + i == drop_layer ? P.keep : nullptr);
-    R.max_back(P.garg, Cg);
+        R.bwd(h0 + i, i == 0 ? P.gfeat : P.y[h0 + i - 1], (uint32_t)n_obj, true, true, h0 + i == drop_layer ? Drop::pre_bn : Drop::none, P.keep);
+    R.max_back(R.cur, P.garg, M, (uint32_t)npts, Cg);
     for (uint32_t i = nm; i-- > 1;) R.bwd(e0 + i, i == 1 ? xf : P.y[e0 + i - 1], M, i + 1 < nm, true);
     if (d.fstn) {                                                // cur: the gradient of the transformed rows
         const size_t tc = n_obj * (size_t)K * K;
@@ -744,19 +525,5 @@ extern "C" int pcr_pointnet_train_grad_f32(pcr_ctx* ctx, pcr_pn2_trainer* t, con
         std::swap(R.cur, R.nxt);
         R.tnet_bwd(s0, P.obj, P.feat_s, P.arg_s, false);
     }
-    rc = R.rc;
-    hipError_t e = hipSuccess;
-    if (rc == PCR_OK) {
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(logp, P.logp, n_obj * n_class * 4, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(loss, P.loss, 3 * 8, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(grad, t->grad_dev, t->n_weights * 4, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess && trans) e = hipMemcpyAsync(trans, T3, n_obj * 9 * 4, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess && trans_feat) e = hipMemcpyAsync(trans_feat, TK, n_obj * (size_t)K * K * 4, hipMemcpyDeviceToHost, ctx->stream);
-    }
-    const hipError_t e2 = hipStreamSynchronize(ctx->stream);      // the one wait: the staging block is read until here
-    if (rc) return rc;
-    if (e != hipSuccess || e2 != hipSuccess) return fail(ctx, PCR_ERR_HIP, who, e != hipSuccess ? e : e2);
-    prof_flush(ctx);
-    return PCR_OK;
+    return call_tail(ctx, t, who, R.rc, P, n_obj, logp, loss, 3, grad, { { trans, T3, n_obj * 9 * 4 }, { trans_feat, TK, n_obj * (size_t)K * K * 4 } });
 }

@@ -1,6 +1,11 @@
-// pointnet_train_common.hpp — what the two training passes share (pointnet2_train.hip: PointNet++ SSG; pointnet_train.hip: the vanilla PointNet): the strided
-// MFMA product, the chunked f64 statistics, BatchNorm / ReLU forward and backward, the max with its argmax, the loss kernel and the trainer handle.
-// Every kernel here keeps its pn2t_* profile name in both passes.  The contracts are above pcr_pn2_trainer_create and pcr_pn1_trainer_create in include/pcr.h.
+// pointnet_train_common.hpp — what the two training passes share (pointnet2_train.hip: PointNet++ SSG; pointnet_train.hip: the vanilla PointNet).
+// Kernels: the strided MFMA product, the chunked f64 statistics, BatchNorm / ReLU forward and backward, the in-place dropout, the max with its argmax, the loss.
+// Every kernel here keeps its profile name in both passes.
+// Host: the trainer handle; layer_push (the weight layout of a layer); trainer_finish (what both creates do behind their shape check); trainer_info_common;
+// keep_rule (the dropout mask by rule); PlanBase (the shared part of a call's device block); call_head / call_upload / call_tail (the checks, the staging and
+// the downloads of a call); LayerRun (one layer forward, one layer backward, the bias gradient, the max's scatter back: the only place that launches them).
+// What a pass keeps to itself: its shapes, its plan's own buffers, and what happens between the layers.
+// The contracts are above pcr_pn2_trainer_create and pcr_pn1_trainer_create in include/pcr.h.
 #pragma once
 #include "pcr_internal.hpp"
 
@@ -344,6 +349,14 @@ __global__ __launch_bounds__(T_BLOCK) void pn2t_loss_kernel(const float* __restr
     }
 }
 
+// v <- keep ? v s : +0: a dropout BEFORE BatchNorm, in place (pointnet_cls's head: forward on the product, backward on its gradient)
+__global__ __launch_bounds__(T_BLOCK) void pn1t_dropout_kernel(float* __restrict__ v, const uint8_t* __restrict__ keep, float s, size_t total)
+{
+    const size_t e = (size_t)blockIdx.x * T_BLOCK + threadIdx.x;
+    if (e >= total) return;
+    v[e] = keep[e] ? v[e] * s : 0.0f;
+}
+
 inline unsigned blocks_for(size_t n) { return (unsigned)((n + T_BLOCK - 1) / T_BLOCK); }
 
 }  // namespace
@@ -387,7 +400,69 @@ inline const char* weights_ok(const pcr_pn2_trainer* t, const float* w)
     return nullptr;
 }
 
-inline int launch_gemm(pcr_ctx* ctx, const char* prof, GemmArgs g, const char* who = "pcr_pn2_train_grad_f32")
+// one more layer behind the ones the trainer has, in weight order: w, b and, with BN, gamma, beta, running_mean, running_var.  t.n_weights is the running end
+inline void layer_push(pcr_pn2_trainer& t, uint32_t K, uint32_t N, bool bn)
+{
+    size_t off = t.n_weights;
+    TLayer L;
+    L.K = K; L.N = N; L.bn = bn;
+    L.w = off; off += (size_t)K * N;
+    L.b = off; off += N;
+    L.gamma = L.beta = L.rmean = L.rvar = 0;
+    if (bn) { L.gamma = off; L.beta = off + N; L.rmean = off + 2 * (size_t)N; L.rvar = off + 3 * (size_t)N; off += 4 * (size_t)N; }
+    t.layers.push_back(L);
+    t.n_weights = off;
+}
+
+// what both creates do once the layers are known: the parameter checks, the two device arrays, the upload.  Every message starts with the caller's name.
+// own_bad: the caller's own finding or NULL; it ranks behind bn_momentum
+inline int trainer_finish(pcr_ctx* ctx, const char* who, std::unique_ptr<pcr_pn2_trainer> t, const char* own_bad, const float* weights, size_t n_weights, double dropout_p,
+                          double bn_momentum, uint32_t chunk_rows, pcr_pn2_trainer** out)
+{
+    auto bad = [&](const char* what) { return fail(ctx, PCR_ERR_ARG, (std::string(who) + what).c_str()); };
+    if (!(dropout_p >= 0.0 && dropout_p < 1.0)) return bad(": dropout_p must lie in [0, 1)");
+    if (!(bn_momentum >= 0.0 && bn_momentum <= 1.0)) return bad(": bn_momentum must lie in [0, 1]");
+    if (own_bad) return bad(own_bad);
+    if (n_weights != t->n_weights) return bad(": n_weights is not the model's count");
+    if (const char* what = weights_ok(t.get(), weights)) return bad(what);
+    t->dropout_p = (float)dropout_p;
+    t->dropout_s = (float)(1.0 / (1.0 - dropout_p));
+    t->momentum = bn_momentum;
+    t->chunk_rows = chunk_rows ? chunk_rows : T_DEFAULT_CHUNK;
+    t->device = ctx->device;
+    PCR_HIP(ctx, hipSetDevice(ctx->device));
+    PCR_HIP(ctx, hipMalloc((void**)&t->w_dev, t->n_weights * 4));
+    hipError_t e = hipMalloc((void**)&t->grad_dev, t->n_weights * 4);
+    if (e == hipSuccess) e = hipMemcpy(t->w_dev, weights, t->n_weights * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(t->grad_dev, 0, t->n_weights * 4);
+    if (e != hipSuccess) {
+        (void)hipFree(t->w_dev);
+        if (t->grad_dev) (void)hipFree(t->grad_dev);
+        return fail(ctx, PCR_ERR_HIP, (std::string(who) + ": the upload of the weights").c_str(), e);
+    }
+    *out = t.release();
+    return PCR_OK;
+}
+
+// the fields of pcr_pn2_train_info that the model does not decide; n_sampling, keep_per_object and device_bytes are the caller's
+inline void trainer_info_common(const pcr_pn2_trainer* t, pcr_pn2_train_info* info)
+{
+    memset(info, 0, sizeof(*info));
+    info->n_weights = t->n_weights;
+    info->chunk_rows = t->chunk_rows;
+    info->n_class = t->layers.back().N;
+    info->dropout_p = (double)t->dropout_p;
+    info->bn_momentum = t->momentum;
+}
+
+// the dropout mask where the caller gives none: K(seed, (0x100 + layer) << 32 | cell) as a uniform in [0, 1) >= p
+inline uint8_t keep_rule(uint64_t seed, uint32_t layer, size_t cell, float p)
+{
+    return (double)(splitmix_key(seed, ((unsigned long long)(0x100u + layer) << 32) | (unsigned long long)cell) >> 11) * 0x1.0p-53 >= (double)p ? 1 : 0;
+}
+
+// the chunked chain product: dW and dT in both passes, z and dx in the SSG pass
+inline int launch_gemm(pcr_ctx* ctx, const char* prof, const GemmArgs& g, const char* who)
 {
     if (g.M == 0 || g.N == 0) return PCR_OK;
     const uint32_t chunks = g.Kt == 0 ? 1u : (g.Kt + g.chunk - 1) / g.chunk;
@@ -397,5 +472,269 @@ inline int launch_gemm(pcr_ctx* ctx, const char* prof, GemmArgs g, const char* w
     PCR_HIP(ctx, hipGetLastError());
     return PCR_OK;
 }
+
+// the part of a call's device block that both passes have.  Several Layouts (scratch_layout.hpp holds 24 slots each) laid one behind the other: `up` (the
+// uploaded part), `own` (the model's: sampling / per-stack buffers), `work`, then one per layer and whatever the model appends.  The model's make_plan declares
+// `up` and `own`, calls layers(), add_layer() per layer and finish()
+struct PlanBase {
+    int32_t* target = nullptr;       // in `up`
+    uint8_t* keep = nullptr;
+    size_t upload_bytes = 0;
+    // per layer
+    std::vector<float*> z, y, a;     // a: y keep s, where the dropout is fused behind the ReLU
+    std::vector<double*> stat;       // 5 N doubles: mu, var, rstd, mean_g, mean_gx
+    // shared
+    float *dyA = nullptr, *dyB = nullptr, *dfeat = nullptr, *dw_part = nullptr, *logp = nullptr;
+    double *part = nullptr, *loss = nullptr;
+    size_t dy_cells = 1, part_cells = 1, dw_cells = 1, dfeat_cells = 0;      // the running maxima; dfeat is the SSG pass's (no cells: no room)
+    Layout up, own, work;
+    std::vector<Layout> per_layer;
+    size_t total = 0;
+
+    void layers(size_t nl, size_t more)
+    {
+        z.assign(nl, nullptr); y.assign(nl, nullptr); a.assign(nl, nullptr); stat.assign(nl, nullptr);
+        per_layer.assign(nl + more, Layout());
+    }
+    void add_layer(size_t i, size_t M, const TLayer& Ly, uint32_t chunk_rows, bool with_a)
+    {
+        const size_t chunks = (M + chunk_rows - 1) / chunk_rows;
+        Layout& L = per_layer[i];
+        L.add(&z[i], M * Ly.N);
+        L.add(&y[i], Ly.bn ? M * Ly.N : 0);
+        L.add(&a[i], with_a && Ly.bn ? M * Ly.N : 0);
+        L.add(&stat[i], 5 * (size_t)Ly.N);
+        dy_cells = std::max(dy_cells, M * std::max(Ly.N, Ly.K));
+        part_cells = std::max(part_cells, 2 * chunks * Ly.N);
+        dw_cells = std::max(dw_cells, chunks * Ly.N * Ly.K);
+    }
+    void finish(size_t n_obj, uint32_t n_class, size_t n_loss)
+    {
+        upload_bytes = up.bytes();
+        work.add(&dyA, dy_cells);
+        work.add(&dyB, dy_cells);
+        work.add(&dfeat, dfeat_cells);
+        work.add(&dw_part, dw_cells);
+        work.add(&part, part_cells);
+        work.add(&logp, n_obj * n_class);
+        work.add(&loss, n_loss);
+        total = up.bytes() + own.bytes() + work.bytes();
+        for (const Layout& L : per_layer) total += L.bytes();
+    }
+    void bind(void* base)
+    {
+        char* p = (char*)base;
+        up.bind(p); p += up.bytes();
+        own.bind(p); p += own.bytes();
+        work.bind(p); p += work.bytes();
+        for (Layout& L : per_layer) { L.bind(p); p += L.bytes(); }
+    }
+};
+
+// the common head of a call: the argument checks in their order of precedence (own_bad: the caller's own finding or NULL, behind npts), the targets, the
+// model's plan (make() -> what is wrong with it, or NULL), the device and the pinned block, `up` bound to the latter with the targets in it.
+// run stays false where the call ends here: an error, or no objects
+template <class MakePlan>
+int call_head(pcr_ctx* ctx, const pcr_pn2_trainer* t, int kind, const char* who, const char* own_bad, bool null_arg, const int32_t* target, size_t n_obj, size_t npts,
+              PlanBase& P, MakePlan make, bool& run)
+{
+    run = false;
+    auto bad = [&](const char* what) { return fail(ctx, PCR_ERR_ARG, (std::string(who) + what).c_str()); };
+    if (!ctx || !t) return fail(ctx, PCR_ERR_ARG, who);
+    if (t->kind != kind)
+        return bad(kind == 0 ? ": the trainer was made by pcr_pn1_trainer_create (use pcr_pointnet_train_grad_f32)"
+                             : ": the trainer was made by pcr_pn2_trainer_create (use pcr_pn2_train_grad_f32)");
+    if (t->device != ctx->device) return bad(": the trainer lives on another device");
+    if (npts < 1) return bad(": npts must be >= 1");
+    if (own_bad) return bad(own_bad);
+    if (n_obj == 0) return PCR_OK;
+    if (n_obj < 2) return bad(": BatchNorm's batch statistics need n_obj >= 2");
+    if (null_arg) return bad(": objects / target / loss / logp / grad is NULL");
+    const uint32_t n_class = t->layers.back().N;
+    for (size_t o = 0; o < n_obj; o++)
+        if (target[o] < 0 || (uint32_t)target[o] >= n_class) return bad(": a target outside [0, n_class)");
+    if (const char* what = make()) return bad(what);
+    PCR_HIP(ctx, hipSetDevice(ctx->device));
+    int rc = ensure_scratch(ctx, P.total);
+    if (rc) return rc;
+    rc = ensure_stage(ctx, P.upload_bytes);
+    if (rc) return rc;
+    P.up.bind(ctx->host_stage);             // the uploaded part, laid out the same way in the pinned staging block
+    for (size_t o = 0; o < n_obj; o++) P.target[o] = target[o];
+    run = true;
+    return PCR_OK;
+}
+
+// the staging block is full: the plan onto the scratch block, the upload, +0 into the gradient array (where the contract says so: pre-BN biases, the running
+// statistics' slots)
+inline int call_upload(pcr_ctx* ctx, pcr_pn2_trainer* t, PlanBase& P)
+{
+    P.bind(ctx->scratch);
+    PCR_HIP(ctx, hipMemcpyAsync(ctx->scratch, ctx->host_stage, P.upload_bytes, hipMemcpyHostToDevice, ctx->stream));
+    PCR_HIP(ctx, hipMemsetAsync(t->grad_dev, 0, t->n_weights * 4, ctx->stream));
+    return PCR_OK;
+}
+
+struct Download { void* dst; const void* src; size_t bytes; };      // dst NULL: not wanted
+
+// the tail of a call: logp, the n_loss loss doubles, the gradient array and `more` to the host, the one wait, rc before the HIP error
+inline int call_tail(pcr_ctx* ctx, const pcr_pn2_trainer* t, const char* who, int rc, const PlanBase& P, size_t n_obj, float* logp, double* loss, size_t n_loss, float* grad,
+                     std::initializer_list<Download> more = {})
+{
+    hipError_t e = hipSuccess;
+    if (rc == PCR_OK) {
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(logp, P.logp, n_obj * t->layers.back().N * 4, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(loss, P.loss, n_loss * 8, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(grad, t->grad_dev, t->n_weights * 4, hipMemcpyDeviceToHost, ctx->stream);
+        for (const Download& d : more)
+            if (e == hipSuccess && d.dst) e = hipMemcpyAsync(d.dst, d.src, d.bytes, hipMemcpyDeviceToHost, ctx->stream);
+    }
+    const hipError_t e2 = hipStreamSynchronize(ctx->stream);      // the one wait: the staging block (and the SSG pass's FPS jobs) are read until here
+    if (rc) return rc;
+    if (e != hipSuccess || e2 != hipSuccess) return fail(ctx, PCR_ERR_HIP, who, e != hipSuccess ? e : e2);
+    prof_flush(ctx);
+    return PCR_OK;
+}
+
+// what a layer is beyond its shapes.  The dropout of a layer sits nowhere, behind its ReLU (fused: bn_relu also writes a = y keep s, which the next layer
+// reads, and the BatchNorm-backward kernels apply the same keep and s; the SSG head), or in front of its BatchNorm (pre_bn: in place on z and, backward, on dz,
+// and the bias in front of the BatchNorm then has a gradient; pointnet_cls's head)
+enum class Drop { none, fused, pre_bn };
+
+// the RELU instances of the BatchNorm kernels
+struct BnKernels {
+    decltype(&pn2t_bn_relu_kernel<true>) bn_relu;
+    decltype(&pn2t_bnb_part_kernel<true>) part;
+    decltype(&pn2t_bnb_dz_kernel<true>) dz;
+};
+inline BnKernels bn_kernels(bool relu)
+{
+    if (relu) return { pn2t_bn_relu_kernel<true>, pn2t_bnb_part_kernel<true>, pn2t_bnb_dz_kernel<true> };
+    return { pn2t_bn_relu_kernel<false>, pn2t_bnb_part_kernel<false>, pn2t_bnb_dz_kernel<false> };
+}
+
+// the product that takes z and dx: launch_gemm (one f32 chain) or pointnet_train.hip's launch_gemm1 (blocked over 64 k, f64 joins); DESIGN 8t has the reason
+typedef int (*ProductFn)(pcr_ctx* ctx, const char* prof, const GemmArgs& g, const char* who);
+
+// one call's launches, layer by layer.  Made once the plan is bound to the scratch block; after a failure (rc) every method returns at once
+struct LayerRun {
+    pcr_ctx* ctx;
+    pcr_pn2_trainer* t;
+    PlanBase& P;
+    const char* who;
+    ProductFn product;
+    const char *prof_fwd, *prof_dx;
+    const float* W;
+    float* G;
+    uint32_t chunk;
+    float *cur, *nxt;        // the gradient that travels backward, and the block the next one is written to
+    int rc = PCR_OK;
+
+    LayerRun(pcr_ctx* c, pcr_pn2_trainer* tr, PlanBase& plan, const char* name, ProductFn f, const char* pf, const char* pd)
+        : ctx(c), t(tr), P(plan), who(name), product(f), prof_fwd(pf), prof_dx(pd), W(tr->w_dev), G(tr->grad_dev), chunk(tr->chunk_rows), cur(plan.dyA), nxt(plan.dyB)
+    {
+    }
+
+    uint32_t chunks_of(uint32_t M) const { return (M + chunk - 1) / chunk; }
+
+    void dropout(float* v, const uint8_t* keep, size_t cells)
+    {
+        ProfScope ps(ctx, "pn1t_dropout");
+        hipLaunchKernelGGL(pn1t_dropout_kernel, dim3(blocks_for(cells)), dim3(T_BLOCK), 0, ctx->stream, v, keep, t->dropout_s, cells);
+    }
+
+    // z = x W^T + b (-> the pre_bn dropout) -> the statistics -> y = BN(z) with or without the ReLU (-> a, the fused dropout)
+    void fwd(uint32_t i, const float* x, uint32_t M, bool relu, Drop drop = Drop::none, const uint8_t* keep = nullptr)
+    {
+        if (rc) return;
+        const TLayer& L = t->layers[i];
+        GemmArgs g;
+        g.a = x; g.b = W + L.w; g.init = W + L.b; g.c = P.z[i];
+        g.M = M; g.N = L.N; g.Kt = L.K; g.chunk = L.K;
+        g.sai = L.K; g.sak = 1; g.sbk = 1; g.sbj = L.K; g.c_stride = 0;
+        rc = product(ctx, prof_fwd, g, who);
+        if (rc) return;
+        const size_t cells = (size_t)M * L.N;
+        if (drop == Drop::pre_bn) dropout(P.z[i], keep, cells);
+        if (!L.bn) return;
+        const uint32_t chunks = chunks_of(M);
+        double *mu = P.stat[i], *var = mu + L.N, *rstd = var + L.N;
+        {
+            ProfScope ps(ctx, "pn2t_stat");
+            for (int pass = 0; pass < 2; pass++) {
+                hipLaunchKernelGGL(pn2t_stat_part_kernel, dim3(blocks_for((size_t)chunks * L.N)), dim3(T_BLOCK), 0, ctx->stream, P.z[i], M, L.N, chunk, chunks,
+                                   pass ? mu : (const double*)nullptr, P.part);
+                hipLaunchKernelGGL(pn2t_stat_fin_kernel, dim3(blocks_for(L.N)), dim3(T_BLOCK), 0, ctx->stream, P.part, chunks, L.N, M, pass, mu, var, rstd, t->desc.bn_eps,
+                                   t->momentum, t->w_dev + L.rmean, t->w_dev + L.rvar, (float*)nullptr);
+            }
+        }
+        const bool fused = drop == Drop::fused;
+        ProfScope ps(ctx, "pn2t_bn_relu");
+        hipLaunchKernelGGL(bn_kernels(relu).bn_relu, dim3(blocks_for(cells)), dim3(T_BLOCK), 0, ctx->stream, P.z[i], cells, L.N, mu, rstd, W + L.gamma, W + L.beta, P.y[i],
+                           fused ? keep : (const uint8_t*)nullptr, fused ? t->dropout_s : 1.0f, fused ? P.a[i] : (float*)nullptr);
+    }
+
+    // the column sums of cur -> the bias gradient
+    void bias_grad(const TLayer& L, uint32_t M)
+    {
+        const uint32_t chunks = chunks_of(M);
+        ProfScope ps(ctx, "pn2t_stat");
+        hipLaunchKernelGGL(pn2t_stat_part_kernel, dim3(blocks_for((size_t)chunks * L.N)), dim3(T_BLOCK), 0, ctx->stream, cur, M, L.N, chunk, chunks, (const double*)nullptr,
+                           P.part);
+        hipLaunchKernelGGL(pn2t_stat_fin_kernel, dim3(blocks_for(L.N)), dim3(T_BLOCK), 0, ctx->stream, P.part, chunks, L.N, M, 2, (double*)nullptr, (double*)nullptr,
+                           (double*)nullptr, 0.0, 0.0, (float*)nullptr, (float*)nullptr, G + L.b);
+    }
+
+    // cur holds the gradient at the layer's output (a, y, or z without BN) -> the parameter gradients; with need_dx, cur <- the gradient of x
+    void bwd(uint32_t i, const float* x, uint32_t M, bool relu, bool need_dx, Drop drop = Drop::none, const uint8_t* keep = nullptr)
+    {
+        if (rc) return;
+        const TLayer& L = t->layers[i];
+        const size_t cells = (size_t)M * L.N;
+        const uint32_t chunks = chunks_of(M);
+        if (L.bn) {
+            double *mu = P.stat[i], *rstd = mu + 2 * (size_t)L.N, *mg = mu + 3 * (size_t)L.N, *mgx = mu + 4 * (size_t)L.N;
+            const uint8_t* fk = drop == Drop::fused ? keep : nullptr;
+            const float s = fk ? t->dropout_s : 1.0f;
+            const BnKernels k = bn_kernels(relu);
+            ProfScope ps(ctx, "pn2t_bn_back");
+            hipLaunchKernelGGL(k.part, dim3(blocks_for((size_t)chunks * L.N)), dim3(T_BLOCK), 0, ctx->stream, cur, P.y[i], P.z[i], fk, s, M, L.N, chunk, chunks, mu, rstd, P.part);
+            hipLaunchKernelGGL(pn2t_bnb_fin_kernel, dim3(blocks_for(L.N)), dim3(T_BLOCK), 0, ctx->stream, P.part, chunks, L.N, M, G + L.gamma, G + L.beta, mg, mgx);
+            hipLaunchKernelGGL(k.dz, dim3(blocks_for(cells)), dim3(T_BLOCK), 0, ctx->stream, cur, P.y[i], P.z[i], fk, s, cells, L.N, mu, rstd, W + L.gamma, mg, mgx);
+        }
+        if (drop == Drop::pre_bn) dropout(cur, keep, cells);
+        if (!L.bn || drop == Drop::pre_bn) bias_grad(L, M);      // the biases the contract gives a gradient: no BatchNorm behind it, or a dropout in between
+        {                                                        // dW[n][k] = sum_r dz[r][n] x[r][k]
+            GemmArgs g;
+            g.a = cur; g.b = x; g.init = nullptr; g.c = P.dw_part;
+            g.M = L.N; g.N = L.K; g.Kt = M; g.chunk = chunk;
+            g.sai = 1; g.sak = L.N; g.sbk = L.K; g.sbj = 1; g.c_stride = (size_t)L.N * L.K;
+            rc = launch_gemm(ctx, "pn2t_gemm_dw", g, who);
+            if (rc) return;
+            ProfScope ps(ctx, "pn2t_dw_reduce");
+            hipLaunchKernelGGL(pn2t_dw_reduce_kernel, dim3(blocks_for(g.c_stride)), dim3(T_BLOCK), 0, ctx->stream, P.dw_part, chunks, g.c_stride, G + L.w);
+        }
+        if (!need_dx) return;
+        GemmArgs g;                                              // dx[r][k] = sum_n dz[r][n] W[n][k]
+        g.a = cur; g.b = W + L.w; g.init = nullptr; g.c = nxt;
+        g.M = M; g.N = L.K; g.Kt = L.N; g.chunk = L.N;
+        g.sai = L.N; g.sak = 1; g.sbk = L.K; g.sbj = 1; g.c_stride = 0;
+        rc = product(ctx, prof_dx, g, who);
+        if (rc == PCR_OK) std::swap(cur, nxt);
+    }
+
+    // the gradient dfeat of the maxima of M rows in groups of gsize -> cur, the gradient of the rows.  dfeat may be cur: then the rows go to nxt and the two swap
+    void max_back(const float* dfeat, const uint32_t* arg, uint32_t M, uint32_t gsize, uint32_t C)
+    {
+        if (rc) return;
+        float* dst = dfeat == cur ? nxt : cur;
+        {
+            ProfScope ps(ctx, "pn2t_max_back");
+            hipLaunchKernelGGL(pn2t_max_back_kernel, dim3(blocks_for((size_t)M * C)), dim3(T_BLOCK), 0, ctx->stream, dfeat, arg, (size_t)M * C, gsize, C, dst);
+        }
+        if (dst == nxt) std::swap(cur, nxt);
+    }
+};
 
 }  // namespace

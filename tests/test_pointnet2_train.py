@@ -425,6 +425,7 @@ EDGES = {
     "tiny": dict(sa=((5, 0.4, 3, (4, 1, 8)), (None, None, None, (8, 16))), fc=(6, 3), B=3, N=7, D0=0),
     "normals": dict(sa=((5, 0.4, 3, (6, 9)), (3, 0.7, 2, (8,)), (None, None, None, (12,))), fc=(5, 4, 2), B=3, N=7, D0=3),
 }
+EDGES["one_fc"] = dict(EDGES["tiny"], fc=(3,))                    # a head of one layer: no BatchNorm, no dropout, no mask bytes; its only layer has the bias gradient
 
 
 def edge_case(pn, ctx, name, keep_mode="rule"):
@@ -483,14 +484,17 @@ def assert_close_to_ref(lib, ref, cfg):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name,dropout,keep_mode", [("tiny", 0.4, "rule"), ("normals", 0.4, "rule"), ("tiny", 0.0, "ones"), ("tiny", 0.4, "ones"), ("tiny", 0.4, "zeros")])
+@pytest.mark.parametrize("name,dropout,keep_mode", [("tiny", 0.4, "rule"), ("normals", 0.4, "rule"), ("one_fc", 0.4, "rule"), ("tiny", 0.0, "ones"), ("tiny", 0.4, "ones"),
+                                                    ("tiny", 0.4, "zeros")])
 def test_edges_against_the_restatement(pt, pn, ctx, pcr, name, dropout, keep_mode):
-    """3 objects x 7 points, npoint 5, nsample 3 (45 rows: less than one tile), a layer of width 1, D0 = 3, dropout_p = 0, keep all ones / all zeros"""
+    """3 objects x 7 points, npoint 5, nsample 3 (45 rows: less than one tile), a layer of width 1, D0 = 3, a head of one layer, dropout_p = 0, keep all ones /
+    all zeros"""
     c = edge_case(pn, ctx, name, keep_mode)
     ref = c["ref"] if dropout == gen.DROPOUT_P else None
     if ref is None:                                              # p = 0: s = 1, and the mask of ones is what the library draws
         ref = train_ref(c["cfg"], c["state"], c["x"], c["target"], *edge_sampling(pn, ctx, c), c["masks"], p=dropout)
-    lib = run_library(pt, ctx, pcr, c["cfg"], c["state"], c["x"], c["target"], c["starts"], None if dropout == 0.0 else c["masks"], dropout=dropout, seed=1)
+    keep = None if dropout == 0.0 or not c["masks"] else c["masks"]      # a head of one layer has no mask (keep_per_object 0)
+    lib = run_library(pt, ctx, pcr, c["cfg"], c["state"], c["x"], c["target"], c["starts"], keep, dropout=dropout, seed=1)
     assert_close_to_ref(lib, ref, c["cfg"])
     if keep_mode == "zeros":                                     # nothing passes the first dropout: every dW before it is exactly 0
         first_fc = f"fc1.weight"
