@@ -1,5 +1,7 @@
-// pointnet2.hip — HomeworkFinal's PointNet++ (SSG) classifier in eval mode (models/pointnet2_cls_ssg.py, models/pointnet_util.py:159-215).
-// The contract is written out above pcr_pn2_model_create / pcr_sa_mlp_max_f32 / pcr_pn2_forward_f32 in include/pcr.h.
+// pointnet2.hip — HomeworkFinal's three classifiers in eval mode: PointNet++ single-scale (SSG; models/pointnet2_cls_ssg.py, models/pointnet_util.py:159-215),
+// PointNet++ multi-scale (MSG; models/pointnet2_cls_msg.py) and the vanilla PointNet with its T-Nets (models/pointnet_cls.py, models/pointnet.py).
+// The contracts are written out above pcr_pn2_model_create, pcr_pn2_msg_model_create and pcr_pn1_model_create in include/pcr.h.
+// Stated once for the three: the layers of a descriptor (pointnet_layers.hpp, the training passes read it too), model_upload, the frame of a forward pass (pass_*).
 //
 //   pn2_chain_kernel   one workgroup (4 waves) per tile of R = 16 / 32 / 64 ROWS (a row = one sample of one group): gathers the rows' input
 //                      channels into LDS, runs the up to four layers relu(W'x + b') with the activations ping-ponging between two LDS
@@ -17,9 +19,10 @@
 //                      scan of the counts (pn2_compact), one memset of the concatenated rows, one chain per branch into its own columns
 //                      (out_stride / out_col).  xyz_last puts the features before xyz - centre in layer 0's gather.  With row_ptr a tile row
 //                      maps to (group, member) through the scan of the counts: only real hits are run, the copies that pad a row are not.
-//   vanilla PointNet  (models/pointnet_cls.py, models/pointnet.py) pn1_chain_kernel and its forward pass: the second half of this file, described there.
+//   vanilla PointNet  pn1_chain_kernel and its forward pass: described above the kernel.
 #include "pcr_internal.hpp"
 #include "f32_key.hpp"
+#include "pointnet_layers.hpp"
 
 #include <algorithm>
 #include <cfloat>
@@ -33,9 +36,7 @@ namespace {
 
 constexpr int PN2_BLOCK = 256;
 constexpr int PN2_WAVES = PN2_BLOCK / 64;
-constexpr uint32_t PN2_MAX_WIDTH = 1024;
 constexpr size_t PN2_LDS_LIMIT = 160 * 1024;
-constexpr unsigned long long PN2_MAX_ROWS = 0x7FFFFFF0ull;
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -307,12 +308,23 @@ int chain_rows(const pcr_ctx* ctx, const C& ch)
     return 16;
 }
 
-template <int RT>
-int chain_launch_rt(pcr_ctx* ctx, const ChainArgs& a, size_t lds)
+// the two LDS row strides of a chain (Chain) or a stage (Pn1Stage): buffer 0 holds the inputs of the even layers, buffer 1 of the odd ones
+template <class C>
+void lds_strides(C& ch)
 {
-    PCR_HIP(ctx, hipFuncSetAttribute((const void*)pn2_chain_kernel<RT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const unsigned tiles = (unsigned)(((unsigned long long)a.rows + RT * 16 - 1) / (RT * 16));
-    hipLaunchKernelGGL((pn2_chain_kernel<RT>), dim3(tiles), dim3(PN2_BLOCK), lds, ctx->stream, a);
+    ch.s0 = ch.s1 = 4;
+    for (uint32_t l = 0; l < ch.n; l++) {
+        uint32_t& s = (l & 1u) ? ch.s1 : ch.s0;
+        s = std::max(s, ch.L[l].Kpad + 4);
+    }
+}
+
+// one instance of a chain kernel (pn2_chain_kernel<RT> / pn1_chain_kernel<RT>) with its dynamic LDS
+template <auto Kernel, class A>
+int launch_rt(pcr_ctx* ctx, const A& a, size_t lds, unsigned blocks)
+{
+    PCR_HIP(ctx, hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(Kernel, dim3(blocks), dim3(PN2_BLOCK), lds, ctx->stream, a);
     PCR_HIP(ctx, hipGetLastError());
     return PCR_OK;
 }
@@ -334,7 +346,19 @@ int chain_launch(pcr_ctx* ctx, const Chain& ch, ChainArgs a, size_t n_groups, co
     if (lds > PN2_LDS_LIMIT) return fail(ctx, PCR_ERR_STATE, "pointnet2: a chain does not fit in LDS");
     ProfScope ps(ctx, prof);
     if (a.mode != PN2_HEAD && clear) PCR_HIP(ctx, hipMemsetAsync(a.out, 0, n_groups * a.out_stride * 4, ctx->stream));
-    return R == 64 ? chain_launch_rt<4>(ctx, a, lds) : R == 32 ? chain_launch_rt<2>(ctx, a, lds) : chain_launch_rt<1>(ctx, a, lds);
+    const unsigned tiles = (unsigned)(((unsigned long long)a.rows + R - 1) / R);
+    return R == 64 ? launch_rt<pn2_chain_kernel<4>>(ctx, a, lds, tiles) : R == 32 ? launch_rt<pn2_chain_kernel<2>>(ctx, a, lds, tiles) : launch_rt<pn2_chain_kernel<1>>(ctx, a, lds, tiles);
+}
+
+// one row per object through FC layers (the classifier's head, a T-Net's): in = n_obj x width, out = n_obj x the chain's last width
+int head_launch(pcr_ctx* ctx, const Chain& ch, const float* in, uint32_t width, float* out, size_t n_obj)
+{
+    ChainArgs a;
+    memset(&a, 0, sizeof(a));
+    a.feat = in; a.out = out;
+    a.rows = (uint32_t)n_obj;
+    a.D = width; a.nsample = 1; a.mode = PN2_HEAD;
+    return chain_launch(ctx, ch, a, n_obj, "pn2_head");
 }
 
 // row_ptr[b][0 .. nq] <- the exclusive scan of counts[b][0 .. nq), for every branch b = blockIdx.x in ONE launch.  A thread sums a run of
@@ -386,14 +410,6 @@ bool seg_ok(const uint32_t* seg_ptr, size_t n_seg, size_t limit)
     return seg_ptr[n_seg] <= limit;
 }
 
-// carves a block in two passes: add() every slot, then bind(base)
-struct Carve {
-    std::vector<std::pair<void**, size_t>> slots;
-    size_t total = 0;
-    template <class T> void add(T** p, size_t count) { slots.push_back({ (void**)p, total }); total += al256(count * sizeof(T)); }
-    void bind(void* base) const { for (auto& s : slots) *s.first = (char*)base + s.second; }
-};
-
 // ---- the vanilla PointNet (models/pointnet_cls.py, models/pointnet.py): the contract is above pcr_pn1_model_create in include/pcr.h -------------
 //   pn1_chain_kernel  one workgroup per tile of R rows = R consecutive points of ONE object (block -> (object, tile of it); an object of fewer
 //                     tiles than the launch has per object returns at once), so the object's own matrices serve every row of the tile:
@@ -402,8 +418,7 @@ struct Carve {
 //                     transform (the same products with the object's matrix staged in LDS in W's operand order, accumulators starting at +0,
 //                     no ReLU) -> the max over the tile's real rows on the integer key of f32_key.hpp, one atomicMax per column and tile.
 //   output            rows of keys that start at KEY_NINF; pn1_decode_kernel turns them into floats in place once the chain is done.
-constexpr int PN1_MAX_STEPS = 5;             // convolution 0, the transform, three more convolutions
-constexpr uint32_t PN1_MAX_TRANSFORM = 128;  // the K x K matrix takes Kpad^2 floats of LDS
+constexpr int PN1_MAX_STEPS = 5;             // convolution 0, the transform (K <= PN_MAX_TRANSFORM: the matrix takes Kpad^2 floats of LDS), three more convolutions
 
 struct Pn1Stage {
     uint32_t n = 0;                          // steps; 0: the model has no such stage
@@ -425,7 +440,9 @@ struct Pn1Args {
     LayerDev L[PN1_MAX_STEPS];
 };
 
-// acc (starting at the bias) += the K products of one 16-column output tile for the RT row tiles; wp: the tile's operand blocks at this lane
+// acc (starting at the bias) += the K products of one 16-column output tile for the RT row tiles; wp: the tile's operand blocks at this lane.
+// (pn2_chain_kernel keeps this loop inline: called from there it kept registers and occupancy, but pn2_sa of the MSG model ran 1.35 % longer; the record is the
+// last section of profiles/pointnet2_msg.txt)
 template <int RT>
 __device__ __forceinline__ void pn1_products(f32x4 (&acc)[RT], const f32x4* wp, const float* ap, uint32_t sin, uint32_t KB)
 {
@@ -556,15 +573,6 @@ __global__ __launch_bounds__(PN2_BLOCK) void pn1_decode_kernel(uint32_t* __restr
     if (i < n) keys[i] = __float_as_uint(f32_from_key(keys[i]));
 }
 
-template <int RT>
-int pn1_launch_rt(pcr_ctx* ctx, const Pn1Args& a, size_t lds, unsigned blocks)
-{
-    PCR_HIP(ctx, hipFuncSetAttribute((const void*)pn1_chain_kernel<RT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL((pn1_chain_kernel<RT>), dim3(blocks), dim3(PN2_BLOCK), lds, ctx->stream, a);
-    PCR_HIP(ctx, hipGetLastError());
-    return PCR_OK;
-}
-
 // a.out (n_seg x n_out floats) <- the stage over the n_seg segments of a.seg_ptr, none longer than max_pts; enqueued on the stream
 int pn1_launch(pcr_ctx* ctx, const Pn1Stage& st, Pn1Args a, size_t n_seg, size_t max_pts)
 {
@@ -575,12 +583,13 @@ int pn1_launch(pcr_ctx* ctx, const Pn1Stage& st, Pn1Args a, size_t n_seg, size_t
     const size_t lds = st.lds_bytes(R), cells = n_seg * st.n_out();
     if (lds > PN2_LDS_LIMIT) return fail(ctx, PCR_ERR_STATE, "pointnet: a stage does not fit in LDS");
     const unsigned long long tiles = (max_pts + R - 1) / R, blocks = tiles * n_seg;
-    if (blocks > PN2_MAX_ROWS) return fail(ctx, PCR_ERR_ARG, "pointnet: too many tiles (segments x tiles of the longest one)");
+    if (blocks > PN_MAX_ROWS) return fail(ctx, PCR_ERR_ARG, "pointnet: too many tiles (segments x tiles of the longest one)");
     a.tiles_per_seg = (uint32_t)tiles;
     ProfScope ps(ctx, "pn1_chain");
     PCR_HIP(ctx, hipMemsetD32Async((hipDeviceptr_t)a.out, (int)KEY_NINF, cells, ctx->stream));
     if (blocks) {
-        const int rc = R == 64 ? pn1_launch_rt<4>(ctx, a, lds, (unsigned)blocks) : R == 32 ? pn1_launch_rt<2>(ctx, a, lds, (unsigned)blocks) : pn1_launch_rt<1>(ctx, a, lds, (unsigned)blocks);
+        const unsigned nb = (unsigned)blocks;
+        const int rc = R == 64 ? launch_rt<pn1_chain_kernel<4>>(ctx, a, lds, nb) : R == 32 ? launch_rt<pn1_chain_kernel<2>>(ctx, a, lds, nb) : launch_rt<pn1_chain_kernel<1>>(ctx, a, lds, nb);
         if (rc) return rc;
     }
     hipLaunchKernelGGL(pn1_decode_kernel, dim3((unsigned)((cells + PN2_BLOCK - 1) / PN2_BLOCK)), dim3(PN2_BLOCK), 0, ctx->stream, a.out, cells);
@@ -595,12 +604,13 @@ int pn1_launch(pcr_ctx* ctx, const Pn1Stage& st, Pn1Args a, size_t n_seg, size_t
 using namespace pcr;
 
 struct pcr_pn2_model {
-    pcr_pn2_msg_desc desc;           // every model is held in the superset descriptor
-    pcr_pn2_desc ssg;                // the single-scale descriptor, where it can express the model (has_ssg)
+    pcr_pn2_msg_desc desc = {};      // every model is held in the superset descriptor
+    pcr_pn2_desc ssg = {};           // the single-scale descriptor, where it can express the model (has_ssg)
     bool has_ssg = false;
     bool compact_default = false;    // pn2_compact of a context that does not set it
     int device = 0;
-    float* dev = nullptr;            // every layer's operands and biases
+    float* dev = nullptr;            // every layer's operands and biases: the model owns the block
+    ~pcr_pn2_model() { if (dev) (void)hipFree(dev); }
     Chain sa[PCR_PN2_MAX_SA][PCR_PN2_MAX_BRANCH];
     Chain head;
     uint32_t sa_in[PCR_PN2_MAX_SA];  // input channels of every SA layer (3 + D)
@@ -609,64 +619,10 @@ struct pcr_pn2_model {
     uint32_t n_sampling = 0;
     // ---- a model of pcr_pn1_model_create (the vanilla PointNet): desc / ssg / sa stay empty, head is the classifier's
     bool pn1 = false;
-    pcr_pn1_desc d1;
+    pcr_pn1_desc d1 = {};
     Pn1Stage stage[3];               // the fused point stages (n == 0: the model has no such stage)
     Chain tnet_head[2];              // the FC layers of the input / the feature T-Net: -> 9 / K x K floats per object, before the identity is added
 };
-
-namespace {
-
-// the layers of a descriptor in weight order: (K, N, has BN); false for a descriptor outside the limits
-struct LayerShape { uint32_t K, N; bool bn; };
-bool pn2_shapes(const pcr_pn2_msg_desc& d, std::vector<LayerShape>& shapes, uint32_t sa_in[PCR_PN2_MAX_SA], uint32_t sa_out[PCR_PN2_MAX_SA])
-{
-    if (d.n_sa < 1 || d.n_sa > PCR_PN2_MAX_SA || d.n_fc < 1 || d.n_fc > PCR_PN2_MAX_FC) return false;
-    if (d.D0 > PN2_MAX_WIDTH - 3 || !std::isfinite(d.bn_eps)) return false;
-    uint32_t D = d.D0;
-    for (uint32_t l = 0; l < d.n_sa; l++) {
-        const pcr_pn2_msg_sa_desc& s = d.sa[l];
-        if (s.n_branch < 1 || s.n_branch > PCR_PN2_MAX_BRANCH || s.group_all > 1 || s.xyz_last > 1) return false;
-        if (s.group_all && (l + 1 != d.n_sa || s.n_branch != 1)) return false;
-        if (!s.group_all && s.npoint < 1) return false;
-        const uint32_t K0 = 3 + D;
-        if (K0 > PN2_MAX_WIDTH) return false;
-        sa_in[l] = K0;
-        uint32_t width = 0;
-        for (uint32_t b = 0; b < s.n_branch; b++) {
-            const pcr_pn2_branch_desc& br = s.branch[b];
-            if (br.n_mlp < 1 || br.n_mlp > PCR_PN2_MAX_MLP) return false;
-            if (!s.group_all && (br.nsample < 1 || br.nsample > 65536 || !(br.radius >= 0.0) || std::isinf(br.radius))) return false;
-            uint32_t K = K0;
-            for (uint32_t i = 0; i < br.n_mlp; i++) {
-                if (br.widths[i] < 1 || br.widths[i] > PN2_MAX_WIDTH) return false;
-                shapes.push_back({ K, br.widths[i], true });
-                K = br.widths[i];
-            }
-            width += K;
-        }
-        if (width > PN2_MAX_WIDTH) return false;
-        sa_out[l] = width;
-        D = width;
-    }
-    uint32_t K = D;
-    for (uint32_t i = 0; i < d.n_fc; i++) {
-        if (d.fc_widths[i] < 1 || d.fc_widths[i] > PN2_MAX_WIDTH) return false;
-        shapes.push_back({ K, d.fc_widths[i], i + 1 < d.n_fc });
-        K = d.fc_widths[i];
-    }
-    return true;
-}
-
-void chain_strides(Chain& ch)
-{
-    ch.s0 = ch.s1 = 4;
-    for (uint32_t l = 0; l < ch.n; l++) {
-        uint32_t& s = (l & 1u) ? ch.s1 : ch.s0;
-        s = std::max(s, ch.L[l].Kpad + 4);
-    }
-}
-
-}  // namespace
 
 namespace {
 
@@ -714,56 +670,59 @@ const char* fold_layers(const std::vector<LayerShape>& shapes, const float* weig
     return nullptr;
 }
 
-// the model of a descriptor; ssg: the single-scale descriptor it was made from, or NULL.  who: the entry point, for the messages
-int model_build(pcr_ctx* ctx, const pcr_pn2_msg_desc* desc, const pcr_pn2_desc* ssg, const float* weights, size_t n_weights, pcr_pn2_model** out, const char* who,
-                bool compact_default)
+// what every create does once the layers are known: the count check, the finite check, the fold, the device block and its upload.  m <- a fresh model that
+// owns the block, layer[i] <- layer i as the kernels take it.  who: the entry point, for the argument messages; family: "pointnet2" / "pointnet"
+int model_upload(pcr_ctx* ctx, const char* who, const char* family, const std::vector<LayerShape>& shapes, const float* weights, size_t n_weights, double bn_eps,
+                 std::unique_ptr<pcr_pn2_model>& m, std::vector<LayerDev>& layer)
 {
     auto bad = [&](const char* what) { return fail(ctx, PCR_ERR_ARG, (std::string(who) + what).c_str()); };
-    std::vector<LayerShape> shapes;
-    uint32_t sa_in[PCR_PN2_MAX_SA] = { 0, 0, 0, 0 }, sa_out[PCR_PN2_MAX_SA] = { 0, 0, 0, 0 };
-    if (!pn2_shapes(*desc, shapes, sa_in, sa_out)) return bad(": a descriptor outside the limits (see include/pcr.h)");
-    uint64_t need = 0;
-    for (const LayerShape& s : shapes) need += (uint64_t)s.K * s.N + s.N + (s.bn ? 4ull * s.N : 0ull);
+    const uint64_t need = weight_count(shapes);
     if (n_weights != need) return bad(": n_weights is not the model's count");
     for (size_t i = 0; i < n_weights; i++)
         if (!std::isfinite(weights[i])) return bad(": a non-finite weight");
     std::vector<float> img;
     std::vector<size_t> w_off, b_off;
-    if (const char* what = fold_layers(shapes, weights, desc->bn_eps, img, w_off, b_off)) return bad(what);
-    const size_t dev_floats = img.size();
+    if (const char* what = fold_layers(shapes, weights, bn_eps, img, w_off, b_off)) return bad(what);
     PCR_HIP(ctx, hipSetDevice(ctx->device));
-    std::unique_ptr<pcr_pn2_model> m(new pcr_pn2_model());
-    m->desc = *desc;
-    if (ssg) m->ssg = *ssg; else memset(&m->ssg, 0, sizeof(m->ssg));
-    m->has_ssg = ssg != nullptr;
-    m->compact_default = compact_default;
+    m.reset(new pcr_pn2_model());
     m->device = ctx->device;
     m->n_weights = need;
-    PCR_HIP(ctx, hipMalloc((void**)&m->dev, dev_floats * 4));
-    hipError_t e = hipMemcpy(m->dev, img.data(), dev_floats * 4, hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(m->dev); return fail(ctx, PCR_ERR_HIP, "pointnet2: the upload of a model", e); }
-    size_t i = 0;
-    auto layer = [&](const LayerShape& s) {
-        LayerDev L;
-        L.w = m->dev + w_off[i]; L.b = m->dev + b_off[i];
-        L.K = s.K; L.Kpad = pad16(s.K); L.N = s.N; L.Npad = pad16(s.N);
-        i++;
-        return L;
-    };
+    PCR_HIP(ctx, hipMalloc((void**)&m->dev, img.size() * 4));
+    const hipError_t e = hipMemcpy(m->dev, img.data(), img.size() * 4, hipMemcpyHostToDevice);
+    if (e != hipSuccess) return fail(ctx, PCR_ERR_HIP, (std::string(family) + ": the upload of a model").c_str(), e);
+    for (size_t i = 0; i < shapes.size(); i++)
+        layer.push_back({ m->dev + w_off[i], m->dev + b_off[i], shapes[i].K, pad16(shapes[i].K), shapes[i].N, pad16(shapes[i].N) });
+    return PCR_OK;
+}
+
+// the model of a descriptor; ssg: the single-scale descriptor it was made from, or NULL.  who: the entry point, for the messages
+int model_build(pcr_ctx* ctx, const pcr_pn2_msg_desc* desc, const pcr_pn2_desc* ssg, const float* weights, size_t n_weights, pcr_pn2_model** out, const char* who,
+                bool compact_default)
+{
+    Pn2Layers ly;
+    if (!pn2_layers(*desc, ly)) return fail(ctx, PCR_ERR_ARG, (std::string(who) + ": a descriptor outside the limits (see include/pcr.h)").c_str());
+    std::unique_ptr<pcr_pn2_model> m;
+    std::vector<LayerDev> layer;
+    const int rc = model_upload(ctx, who, "pointnet2", ly.shapes, weights, n_weights, desc->bn_eps, m, layer);
+    if (rc) return rc;
+    m->desc = *desc;
+    if (ssg) m->ssg = *ssg;
+    m->has_ssg = ssg != nullptr;
+    m->compact_default = compact_default;
+    m->n_sampling = ly.n_sampling;
     for (uint32_t l = 0; l < desc->n_sa; l++) {
         for (uint32_t b = 0; b < desc->sa[l].n_branch; b++) {
             Chain& ch = m->sa[l][b];
             ch.n = desc->sa[l].branch[b].n_mlp;
-            for (uint32_t k = 0; k < ch.n; k++) ch.L[k] = layer(shapes[i]);
-            chain_strides(ch);
+            for (uint32_t k = 0; k < ch.n; k++) ch.L[k] = layer[ly.first[l][b] + k];
+            lds_strides(ch);
         }
-        m->sa_in[l] = sa_in[l];
-        m->sa_out[l] = sa_out[l];
-        if (!desc->sa[l].group_all) m->n_sampling++;
+        m->sa_in[l] = ly.sa_in[l];
+        m->sa_out[l] = ly.sa_out[l];
     }
     m->head.n = desc->n_fc;
-    for (uint32_t k = 0; k < m->head.n; k++) m->head.L[k] = layer(shapes[i]);
-    chain_strides(m->head);
+    for (uint32_t k = 0; k < m->head.n; k++) m->head.L[k] = layer[ly.head_first + k];
+    lds_strides(m->head);
     *out = m.release();
     return PCR_OK;
 }
@@ -774,17 +733,8 @@ extern "C" int pcr_pn2_model_create(pcr_ctx* ctx, const pcr_pn2_desc* desc, cons
 {
     if (out) *out = nullptr;
     if (!ctx || !desc || !weights || !out) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_model_create");
-    if (desc->n_sa < 1 || desc->n_sa > PCR_PN2_MAX_SA) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_model_create: a descriptor outside the limits (see include/pcr.h)");
-    pcr_pn2_msg_desc d;                      // the same model in the superset descriptor: one xyz-first branch per layer
-    memset(&d, 0, sizeof(d));
-    d.D0 = desc->D0; d.n_sa = desc->n_sa; d.n_fc = desc->n_fc; d.bn_eps = desc->bn_eps;
-    for (uint32_t k = 0; k < PCR_PN2_MAX_FC; k++) d.fc_widths[k] = desc->fc_widths[k];
-    for (uint32_t l = 0; l < desc->n_sa; l++) {
-        const pcr_pn2_sa_desc& s = desc->sa[l];
-        d.sa[l].npoint = s.npoint; d.sa[l].group_all = s.group_all; d.sa[l].xyz_last = 0; d.sa[l].n_branch = 1;
-        d.sa[l].branch[0].radius = s.radius; d.sa[l].branch[0].nsample = s.nsample; d.sa[l].branch[0].n_mlp = s.n_mlp;
-        for (uint32_t k = 0; k < PCR_PN2_MAX_MLP; k++) d.sa[l].branch[0].widths[k] = s.widths[k];
-    }
+    pcr_pn2_msg_desc d;                      // the same model in the superset descriptor
+    if (!pn2_msg_desc_of(*desc, d)) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_model_create: a descriptor outside the limits (see include/pcr.h)");
     return model_build(ctx, &d, desc, weights, n_weights, out, "pcr_pn2_model_create", false);
 }
 
@@ -816,28 +766,27 @@ extern "C" int pcr_pn2_model_destroy(pcr_ctx* ctx, pcr_pn2_model* model)
         (void)hipSetDevice(ctx->device);
         (void)hipStreamSynchronize(ctx->stream);
     }
-    if (model->dev) (void)hipFree(model->dev);
-    delete model;
+    delete model;                            // frees its device block
     return PCR_OK;
 }
 
 namespace {
 
-// the figures of a descriptor (which pn2_shapes accepts): they do not need the device
+// the figures of a descriptor (which pn2_layers accepts): they do not need the device
 bool desc_info(const pcr_pn2_msg_desc& d, size_t npts_hint, pcr_pn2_info* info)
 {
-    std::vector<LayerShape> shapes;
-    uint32_t sa_in[PCR_PN2_MAX_SA] = { 0, 0, 0, 0 }, sa_out[PCR_PN2_MAX_SA] = { 0, 0, 0, 0 };
-    if (!pn2_shapes(d, shapes, sa_in, sa_out)) return false;
+    Pn2Layers ly;
+    if (!pn2_layers(d, ly)) return false;
+    const std::vector<LayerShape>& shapes = ly.shapes;
     memset(info, 0, sizeof(*info));
-    for (const LayerShape& s : shapes) info->n_weights += (uint64_t)s.K * s.N + s.N + (s.bn ? 4ull * s.N : 0ull);
+    info->n_weights = weight_count(shapes);
     info->n_class = d.fc_widths[d.n_fc - 1];
-    info->c_last = sa_out[d.n_sa - 1];
+    info->c_last = ly.sa_out[d.n_sa - 1];
+    info->n_sampling = ly.n_sampling;
     uint64_t macs = 0, n = npts_hint;
     size_t i = 0;
     for (uint32_t l = 0; l < d.n_sa; l++) {
         const pcr_pn2_msg_sa_desc& s = d.sa[l];
-        if (!s.group_all) info->n_sampling++;
         for (uint32_t b = 0; b < s.n_branch; b++) {
             uint64_t per_row = 0;
             for (uint32_t k = 0; k < s.branch[b].n_mlp; k++, i++) per_row += (uint64_t)shapes[i].K * shapes[i].N;
@@ -850,8 +799,6 @@ bool desc_info(const pcr_pn2_msg_desc& d, size_t npts_hint, pcr_pn2_info* info)
     return true;
 }
 
-void model_info(const pcr_pn2_model* model, size_t npts_hint, pcr_pn2_info* info) { (void)desc_info(model->desc, npts_hint, info); }
-
 }  // namespace
 
 extern "C" int pcr_pn2_model_info(const pcr_pn2_model* model, size_t npts_hint, pcr_pn2_info* info, pcr_pn2_desc* desc)
@@ -861,7 +808,7 @@ extern "C" int pcr_pn2_model_info(const pcr_pn2_model* model, size_t npts_hint, 
         if (!model->has_ssg) return PCR_ERR_ARG;      // several branches or features-first channels: only pcr_pn2_msg_desc holds them
         *desc = model->ssg;
     }
-    if (info) model_info(model, npts_hint, info);
+    if (info) (void)desc_info(model->desc, npts_hint, info);
     return PCR_OK;
 }
 
@@ -873,7 +820,7 @@ extern "C" int pcr_pn2_msg_model_info(const pcr_pn2_model* model, size_t npts_hi
     }
     if (model->pn1) return PCR_ERR_ARG;      // pcr_pn1_model_info holds its descriptor
     if (desc) *desc = model->desc;
-    if (info) model_info(model, npts_hint, info);
+    if (info) (void)desc_info(model->desc, npts_hint, info);
     return PCR_OK;
 }
 
@@ -897,7 +844,7 @@ int sa_layer(pcr_ctx* ctx, const pcr_pn2_model* model, int layer, const pcr_clou
     const size_t D = model->sa_in[layer] - 3, width = model->sa_out[layer];
     if (ga ? (centres || centre_seg_ptr || idx) : (!centres || !centre_seg_ptr)) return bad(": centres / centre_seg_ptr / idx go with a sampling layer only");
     if (D > 0 && !features) return bad(": the layer takes features");
-    if (n_seg > PN2_MAX_ROWS || cloud->n > PN2_MAX_ROWS || (centres && centres->n > PN2_MAX_ROWS)) return bad(": too large");
+    if (n_seg > PN_MAX_ROWS || cloud->n > PN_MAX_ROWS || (centres && centres->n > PN_MAX_ROWS)) return bad(": too large");
     if (!seg_ok(seg_ptr, n_seg, cloud->n) || (!ga && !seg_ok(centre_seg_ptr, n_seg, centres->n))) return bad(": seg_ptr must ascend and end inside its cloud");
     if (n_seg == 0) return PCR_OK;
     const size_t q0 = ga ? 0 : centre_seg_ptr[0], nq = ga ? n_seg : centre_seg_ptr[n_seg] - q0;
@@ -906,7 +853,7 @@ int sa_layer(pcr_ctx* ctx, const pcr_pn2_model* model, int layer, const pcr_clou
     if (!out || (!ga && !idx)) return bad(": idx / out is NULL");
     size_t row_total = 0;                                        // entries of idx per centre, over the branches
     for (uint32_t b = 0; b < nb; b++) row_total += ga ? 0 : sd.branch[b].nsample;
-    if ((ga ? (unsigned long long)np : (unsigned long long)nq * row_total) > PN2_MAX_ROWS || nq > PN2_MAX_ROWS / width) return bad(": too large");
+    if ((ga ? (unsigned long long)np : (unsigned long long)nq * row_total) > PN_MAX_ROWS || nq > PN_MAX_ROWS / width) return bad(": too large");
     const bool compact = !ga && compact_rows(ctx, model->compact_default);
     std::vector<uint32_t> cs, rp;                                // the segment of every centre; compacted: per branch the nq + 1 row offsets
     if (!ga) {
@@ -1004,22 +951,160 @@ extern "C" int pcr_sa_msg_mlp_max_f32(pcr_ctx* ctx, const pcr_pn2_model* model, 
     return sa_layer(ctx, model, layer, cloud, seg_ptr, centres, centre_seg_ptr, n_seg, features, idx, out, true);
 }
 
+// ---- the frame of a forward pass (pcr_pn2_forward_f32, pcr_pointnet_forward_f32): its checks, its upload, its tail -----------------------------------
+namespace {
+
+bool pn1_model_of(pcr_ctx* ctx, const pcr_pn2_model* model, const char* who)
+{
+    if (model->pn1) return true;
+    fail(ctx, PCR_ERR_ARG, (std::string(who) + ": not a model of pcr_pn1_model_create").c_str());
+    return false;
+}
+
+// the handles of a pass: there, of the entry point's kind (pn1: a model of pcr_pn1_model_create), on the context's device
+int pass_model(pcr_ctx* ctx, const pcr_pn2_model* model, const char* who, bool pn1)
+{
+    if (!ctx || !model) return fail(ctx, PCR_ERR_ARG, who);
+    if (pn1 && !pn1_model_of(ctx, model, who)) return PCR_ERR_ARG;
+    if (!pn1 && model->pn1) return fail(ctx, PCR_ERR_ARG, (std::string(who) + ": a model of pcr_pn1_model_create (pcr_pointnet_forward_f32 runs it)").c_str());
+    if (model->device != ctx->device) return fail(ctx, PCR_ERR_ARG, (std::string(who) + ": the model lives on another device").c_str());
+    return PCR_OK;
+}
+
+// the arguments of a pass in their order of precedence (own_bad: the caller's own finding or NULL, behind npts); C0: floats per point.
+// No objects is PCR_OK before objects and logp are looked at: the caller returns on rc != 0 OR n_obj == 0
+int pass_args(pcr_ctx* ctx, const char* who, const char* own_bad, const float* objects, const float* logp, size_t n_obj, size_t npts, uint32_t C0)
+{
+    auto bad = [&](const char* what) { return fail(ctx, PCR_ERR_ARG, (std::string(who) + what).c_str()); };
+    if (npts < 1) return bad(": npts must be >= 1");
+    if (own_bad) return bad(own_bad);
+    if (n_obj == 0) return PCR_OK;
+    if (!objects || !logp) return bad(": objects / logp is NULL");
+    if (n_obj > PN_MAX_ROWS || npts > PN_MAX_ROWS || (unsigned long long)n_obj * npts > PN_MAX_ROWS / C0) return bad(": too large");
+    return PCR_OK;
+}
+
+// the uploaded part of a pass: the objects split into x y z | features, the segment table of every cloud (cloud 0: the objects, N[0] points each; cloud l: the
+// centres of sampling layer l - 1, N[l] each) and, for every cloud behind the first, the segment of each of its points
+struct PassInput {
+    Layout up;
+    size_t P = 0;                               // points of cloud 0
+    float *x0 = nullptr, *feat0 = nullptr;      // x, y, z one after the other, P floats each; P x D0
+    uint32_t* seg[PCR_PN2_MAX_SA + 1];          // the segments of cloud l: n_obj + 1 offsets
+    uint32_t* cseg[PCR_PN2_MAX_SA];             // the segment of every centre of sampling layer l (a point of cloud l + 1)
+
+    void declare(size_t n_obj, const size_t* N, uint32_t n_clouds, uint32_t D0)
+    {
+        P = n_obj * N[0];
+        up.add(&x0, 3 * P);
+        up.add(&feat0, P * D0);
+        for (uint32_t l = 0; l < n_clouds; l++) up.add(&seg[l], n_obj + 1);
+        for (uint32_t l = 0; l + 1 < n_clouds; l++) up.add(&cseg[l], n_obj * N[l + 1]);
+    }
+};
+
+// objects (P points of 3 + D0 floats) -> x, y, z (P floats each, one after the other at x0) and the features; false at the first value that is not finite.
+// FEAT = false: D0 == 0 with a straight-line body, three checks and three stores per point (one generic loop cost pcr_pointnet_forward_f32 0.6 ns per point)
+template <bool FEAT>
+bool stage_points(const float* objects, size_t P, uint32_t D0, float* x0, float* feat0)
+{
+    float *hx = x0, *hy = x0 + P, *hz = x0 + 2 * P;
+    const uint32_t C0 = FEAT ? 3 + D0 : 3;
+    for (size_t i = 0; i < P; i++) {
+        const float* r = objects + i * C0;
+        if (!(fabsf(r[0]) <= FLT_MAX) || !(fabsf(r[1]) <= FLT_MAX) || !(fabsf(r[2]) <= FLT_MAX)) return false;
+        hx[i] = r[0]; hy[i] = r[1]; hz[i] = r[2];
+        if (FEAT)
+            for (uint32_t c = 0; c < D0; c++) {
+                if (!(fabsf(r[3 + c]) <= FLT_MAX)) return false;
+                feat0[i * D0 + c] = r[3 + c];
+            }
+    }
+    return true;
+}
+
+// one scratch block for `in.up` and the layouts `behind` it, back to back; every coordinate and feature checked on its way into the pinned staging block,
+// the tables written there in the same layout; everything bound to the scratch block; the one upload
+int pass_upload(pcr_ctx* ctx, const char* who, PassInput& in, const std::vector<const Layout*>& behind, const float* objects, size_t n_obj, const size_t* N,
+                uint32_t n_clouds, uint32_t D0)
+{
+    PCR_HIP(ctx, hipSetDevice(ctx->device));
+    size_t total = in.up.bytes();
+    for (const Layout* L : behind) total += L->bytes();
+    int rc = ensure_scratch(ctx, total);
+    if (rc) return rc;
+    rc = ensure_stage(ctx, in.up.bytes());
+    if (rc) return rc;
+    in.up.bind(ctx->host_stage);
+    if (!(D0 ? stage_points<true>(objects, in.P, D0, in.x0, in.feat0) : stage_points<false>(objects, in.P, 0, in.x0, in.feat0)))
+        return fail(ctx, PCR_ERR_ARG, (std::string(who) + ": a non-finite coordinate or feature").c_str());
+    for (uint32_t l = 0; l < n_clouds; l++)
+        for (size_t o = 0; o <= n_obj; o++) in.seg[l][o] = (uint32_t)(o * N[l]);
+    for (uint32_t l = 0; l + 1 < n_clouds; l++)
+        for (size_t q = 0; q < n_obj * N[l + 1]; q++) in.cseg[l][q] = (uint32_t)(q / N[l + 1]);
+    char* p = (char*)ctx->scratch;
+    in.up.bind(p);
+    p += in.up.bytes();
+    for (const Layout* L : behind) { L->bind(p); p += L->bytes(); }
+    PCR_HIP(ctx, hipMemcpyAsync(ctx->scratch, ctx->host_stage, in.up.bytes(), hipMemcpyHostToDevice, ctx->stream));
+    return PCR_OK;
+}
+
+struct Download { void* dst; const void* src; size_t bytes; };      // dst NULL: not wanted
+
+// the buffers of a pass's tail: the last slots of its last Layout
+struct PassTail {
+    float *logits = nullptr, *logp = nullptr;
+    int32_t* pred = nullptr;
+    void declare(Layout& L, size_t n_obj, uint32_t n_class)
+    {
+        L.add(&logits, n_obj * n_class);
+        L.add(&logp, n_obj * n_class);
+        L.add(&pred, n_obj);
+    }
+};
+
+// the tail of a pass: the global feature (n_obj x c_last) through the head, log_softmax, logp and `more` to the host, the one wait, rc before the HIP error
+int pass_tail(pcr_ctx* ctx, const char* who, int rc, const pcr_pn2_model* model, const float* gfeat, uint32_t c_last, size_t n_obj, const PassTail& t, float* logp,
+              const std::vector<Download>& more)
+{
+    const uint32_t n_class = model->head.n_out();
+    if (rc == PCR_OK) rc = head_launch(ctx, model->head, gfeat, c_last, t.logits, n_obj);
+    hipError_t e = hipSuccess;
+    if (rc == PCR_OK) {
+        {
+            ProfScope ps(ctx, "pn2_logsoftmax");
+            hipLaunchKernelGGL(pn2_logsoftmax_kernel, dim3((unsigned)((n_obj + PN2_BLOCK - 1) / PN2_BLOCK)), dim3(PN2_BLOCK), 0, ctx->stream, t.logits, (uint32_t)n_obj, n_class,
+                               t.logp, t.pred);
+        }
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(logp, t.logp, n_obj * n_class * 4, hipMemcpyDeviceToHost, ctx->stream);
+        for (const Download& d : more)
+            if (e == hipSuccess && d.dst) e = hipMemcpyAsync(d.dst, d.src, d.bytes, hipMemcpyDeviceToHost, ctx->stream);
+    }
+    const hipError_t e2 = hipStreamSynchronize(ctx->stream);      // the one wait: the staging block (and the SSG / MSG pass's FPS jobs) are read until here
+    if (rc) return rc;
+    if (e != hipSuccess || e2 != hipSuccess) return fail(ctx, PCR_ERR_HIP, who, e != hipSuccess ? e : e2);
+    prof_flush(ctx);
+    return PCR_OK;
+}
+
+}  // namespace
+
 extern "C" int pcr_pn2_forward_f32(pcr_ctx* ctx, const pcr_pn2_model* model, const float* objects, size_t n_obj, size_t npts, const uint32_t* starts, uint64_t seed,
                                    float* logp, int32_t* pred, float* global_feat, uint32_t* fps_idx)
 {
-    if (!ctx || !model) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_forward_f32");
-    if (model->pn1) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_forward_f32: a model of pcr_pn1_model_create (pcr_pointnet_forward_f32 runs it)");
-    if (model->device != ctx->device) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_forward_f32: the model lives on another device");
+    const char* who = "pcr_pn2_forward_f32";
+    int rc = pass_model(ctx, model, who, false);
+    if (rc) return rc;
     const pcr_pn2_msg_desc& d = model->desc;
     if (!d.sa[d.n_sa - 1].group_all) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_forward_f32: the last SA layer must be group_all");
-    if (npts < 1) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_forward_f32: npts must be >= 1");
-    if (n_obj == 0) return PCR_OK;
-    if (!objects || !logp) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_forward_f32: objects / logp is NULL");
-    const uint32_t ns = model->n_sampling, D0 = d.D0, C0 = 3 + D0;
+    const uint32_t ns = model->n_sampling, D0 = d.D0;
+    rc = pass_args(ctx, who, nullptr, objects, logp, n_obj, npts, 3 + D0);
+    if (rc || n_obj == 0) return rc;
     const uint32_t n_class = model->head.n_out(), c_last = model->sa_out[d.n_sa - 1];
     const bool compact = compact_rows(ctx, model->compact_default);
     // ---- sizes of every stage
-    if (n_obj > PN2_MAX_ROWS || npts > PN2_MAX_ROWS || (unsigned long long)n_obj * npts > PN2_MAX_ROWS / C0) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_forward_f32: too large");
     size_t N[PCR_PN2_MAX_SA + 1];
     N[0] = npts;
     for (uint32_t l = 0; l < ns; l++) {
@@ -1028,9 +1113,9 @@ extern "C" int pcr_pn2_forward_f32(pcr_ctx* ctx, const pcr_pn2_model* model, con
         const unsigned long long nq = (unsigned long long)n_obj * s.npoint;
         unsigned long long row_total = 0;
         for (uint32_t b = 0; b < s.n_branch; b++) row_total += s.branch[b].nsample;
-        if (nq > PN2_MAX_ROWS / row_total || nq > PN2_MAX_ROWS / model->sa_out[l]) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_forward_f32: too large");
+        if (nq > PN_MAX_ROWS / row_total || nq > PN_MAX_ROWS / model->sa_out[l]) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_forward_f32: too large");
     }
-    if ((unsigned long long)n_obj * std::max<uint32_t>(c_last, n_class) > PN2_MAX_ROWS) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_forward_f32: too large");
+    if ((unsigned long long)n_obj * std::max<uint32_t>(c_last, n_class) > PN_MAX_ROWS) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_forward_f32: too large");
     std::vector<uint32_t> st((size_t)ns * n_obj);
     for (uint32_t l = 0; l < ns; l++)
         for (size_t o = 0; o < n_obj; o++) {
@@ -1043,58 +1128,33 @@ extern "C" int pcr_pn2_forward_f32(pcr_ctx* ctx, const pcr_pn2_model* model, con
             }
             st[(size_t)l * n_obj + o] = v;
         }
-    PCR_HIP(ctx, hipSetDevice(ctx->device));
-    // ---- one block: [uploaded: x y z feat | seg tables] [per sampling layer: picks, centres, ball rows, features out] [group_all out] [head]
-    const size_t P = n_obj * npts;
-    float *x0, *feat0, *ga_out, *logits, *logp_dev;
-    int32_t* pred_dev;
-    uint32_t* seg[PCR_PN2_MAX_SA + 1];          // the segments of cloud l: n_obj + 1 offsets
-    uint32_t* cseg[PCR_PN2_MAX_SA];             // the segment of every centre of sampling layer l
+    // ---- one block: [uploaded: x y z feat | seg tables] [per sampling layer: picks, centres, ball rows, features out] [group_all out | head]
+    PassInput in;
+    in.declare(n_obj, N, ns + 1, D0);
     uint32_t *fps[PCR_PN2_MAX_SA], *bidx[PCR_PN2_MAX_SA][PCR_PN2_MAX_BRANCH], *bcnt[PCR_PN2_MAX_SA], *brp[PCR_PN2_MAX_SA];      // bcnt: n_branch x nq, brp: n_branch x (nq + 1)
-    float *cxyz[PCR_PN2_MAX_SA], *sa_out[PCR_PN2_MAX_SA];
-    Carve cv;
-    cv.add(&x0, 3 * P);
-    cv.add(&feat0, P * D0);
-    for (uint32_t l = 0; l <= ns; l++) cv.add(&seg[l], n_obj + 1);
-    for (uint32_t l = 0; l < ns; l++) cv.add(&cseg[l], n_obj * N[l + 1]);
-    const size_t upload_bytes = cv.total;
+    float *cxyz[PCR_PN2_MAX_SA], *sa_out[PCR_PN2_MAX_SA], *ga_out;
+    Layout per[PCR_PN2_MAX_SA], last;
+    std::vector<const Layout*> behind;          // one Layout per sampling layer, then the group_all layer's output and the tail
     for (uint32_t l = 0; l < ns; l++) {
         const size_t nq = n_obj * N[l + 1];
-        cv.add(&fps[l], nq);
-        cv.add(&cxyz[l], 3 * nq);
-        for (uint32_t b = 0; b < d.sa[l].n_branch; b++) cv.add(&bidx[l][b], nq * d.sa[l].branch[b].nsample);
-        cv.add(&bcnt[l], nq * d.sa[l].n_branch);
-        cv.add(&brp[l], compact ? (nq + 1) * d.sa[l].n_branch : 0);
-        cv.add(&sa_out[l], nq * model->sa_out[l]);
+        per[l].add(&fps[l], nq);
+        per[l].add(&cxyz[l], 3 * nq);
+        for (uint32_t b = 0; b < d.sa[l].n_branch; b++) per[l].add(&bidx[l][b], nq * d.sa[l].branch[b].nsample);
+        per[l].add(&bcnt[l], nq * d.sa[l].n_branch);
+        per[l].add(&brp[l], compact ? (nq + 1) * d.sa[l].n_branch : 0);
+        per[l].add(&sa_out[l], nq * model->sa_out[l]);
+        behind.push_back(&per[l]);
     }
-    cv.add(&ga_out, n_obj * c_last);
-    cv.add(&logits, n_obj * n_class);
-    cv.add(&logp_dev, n_obj * n_class);
-    cv.add(&pred_dev, n_obj);
-    int rc = ensure_scratch(ctx, cv.total);
+    PassTail tail;
+    last.add(&ga_out, n_obj * c_last);
+    tail.declare(last, n_obj, n_class);
+    behind.push_back(&last);
+    rc = pass_upload(ctx, who, in, behind, objects, n_obj, N, ns + 1, D0);
     if (rc) return rc;
-    rc = ensure_stage(ctx, upload_bytes);
-    if (rc) return rc;
-    cv.bind(ctx->host_stage);               // the uploaded part, laid out the same way in the pinned staging block
-    {
-        float *hx = x0, *hy = x0 + P, *hz = x0 + 2 * P;
-        for (size_t i = 0; i < P; i++) {
-            const float* r = objects + i * C0;
-            for (uint32_t c = 0; c < C0; c++)
-                if (!(fabsf(r[c]) <= FLT_MAX)) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_forward_f32: a non-finite coordinate or feature");
-            hx[i] = r[0]; hy[i] = r[1]; hz[i] = r[2];
-            for (uint32_t c = 0; c < D0; c++) feat0[i * D0 + c] = r[3 + c];
-        }
-        for (uint32_t l = 0; l <= ns; l++)
-            for (size_t o = 0; o <= n_obj; o++) seg[l][o] = (uint32_t)(o * N[l]);
-        for (uint32_t l = 0; l < ns; l++)
-            for (size_t q = 0; q < n_obj * N[l + 1]; q++) cseg[l][q] = (uint32_t)(q / N[l + 1]);
-    }
-    cv.bind(ctx->scratch);
-    PCR_HIP(ctx, hipMemcpyAsync(ctx->scratch, ctx->host_stage, upload_bytes, hipMemcpyHostToDevice, ctx->stream));
     // ---- the sampling layers
     HostKeep keep;
-    const float *cx = x0, *cy = x0 + P, *cz = x0 + 2 * P, *feat = feat0;
+    const size_t P = in.P;
+    const float *cx = in.x0, *cy = in.x0 + P, *cz = in.x0 + 2 * P, *feat = in.feat0;
     uint32_t D = D0;
     for (uint32_t l = 0; l < ns; l++) {
         const pcr_pn2_msg_sa_desc& s = d.sa[l];
@@ -1110,12 +1170,12 @@ extern "C" int pcr_pn2_forward_f32(pcr_ctx* ctx, const pcr_pn2_model* model, con
                                s.npoint, (uint32_t)nq, qx, qy, qz);
         }
         if (s.n_branch == 1) {
-            rc = ball_query_device(ctx, cx, cy, cz, qx, qy, qz, seg[l], cseg[l], nq, s.branch[0].radius, s.branch[0].nsample, bidx[l][0], bcnt[l]);
+            rc = ball_query_device(ctx, cx, cy, cz, qx, qy, qz, in.seg[l], in.cseg[l], nq, s.branch[0].radius, s.branch[0].nsample, bidx[l][0], bcnt[l]);
         } else {                                 // every radius in one walk of the object
             double radii[PCR_PN2_MAX_BRANCH];
             uint32_t nsamples[PCR_PN2_MAX_BRANCH], *cb[PCR_PN2_MAX_BRANCH];
             for (uint32_t b = 0; b < s.n_branch; b++) { radii[b] = s.branch[b].radius; nsamples[b] = s.branch[b].nsample; cb[b] = bcnt[l] + (size_t)b * nq; }
-            rc = ball_query_multi_device(ctx, cx, cy, cz, qx, qy, qz, seg[l], cseg[l], nq, s.n_branch, radii, nsamples, bidx[l], cb);
+            rc = ball_query_multi_device(ctx, cx, cy, cz, qx, qy, qz, in.seg[l], in.cseg[l], nq, s.n_branch, radii, nsamples, bidx[l], cb);
         }
         if (rc) break;
         if (compact) {                           // the row offsets of every branch: one launch
@@ -1127,7 +1187,7 @@ extern "C" int pcr_pn2_forward_f32(pcr_ctx* ctx, const pcr_pn2_model* model, con
             ChainArgs a;
             memset(&a, 0, sizeof(a));
             a.x = cx; a.y = cy; a.z = cz; a.qx = qx; a.qy = qy; a.qz = qz;
-            a.seg_ptr = seg[l]; a.centre_seg = cseg[l]; a.idx = bidx[l][b]; a.feat = feat; a.out = sa_out[l];
+            a.seg_ptr = in.seg[l]; a.centre_seg = in.cseg[l]; a.idx = bidx[l][b]; a.feat = feat; a.out = sa_out[l];
             if (compact) a.row_ptr = brp[l] + (size_t)b * (nq + 1);
             a.out_stride = model->sa_out[l]; a.out_col = col; a.xyz_last = s.xyz_last;
             a.rows = (uint32_t)(nq * s.branch[b].nsample);
@@ -1142,85 +1202,30 @@ extern "C" int pcr_pn2_forward_f32(pcr_ctx* ctx, const pcr_pn2_model* model, con
     if (rc == PCR_OK) {                      // the group_all layer, then the head on its rows
         ChainArgs a;
         memset(&a, 0, sizeof(a));
-        a.x = cx; a.y = cy; a.z = cz; a.seg_ptr = seg[ns]; a.feat = feat; a.out = ga_out;
+        a.x = cx; a.y = cy; a.z = cz; a.seg_ptr = in.seg[ns]; a.feat = feat; a.out = ga_out;
         a.rows = (uint32_t)(n_obj * N[ns]);
         a.D = D; a.nsample = 1; a.n_seg = (uint32_t)n_obj; a.mode = PN2_GROUP_ALL; a.xyz_last = d.sa[ns].xyz_last;
         rc = chain_launch(ctx, model->sa[ns][0], a, n_obj, "pn2_sa");
     }
-    if (rc == PCR_OK) {
-        ChainArgs a;
-        memset(&a, 0, sizeof(a));
-        a.feat = ga_out; a.out = logits;
-        a.rows = (uint32_t)n_obj;
-        a.D = c_last; a.nsample = 1; a.mode = PN2_HEAD;
-        rc = chain_launch(ctx, model->head, a, n_obj, "pn2_head");
+    std::vector<Download> more = { { pred, tail.pred, n_obj * 4 }, { global_feat, ga_out, n_obj * c_last * 4 } };
+    size_t off = 0;
+    for (uint32_t l = 0; l < ns && fps_idx; l++) {
+        more.push_back({ fps_idx + off, fps[l], n_obj * N[l + 1] * 4 });
+        off += n_obj * N[l + 1];
     }
-    hipError_t e = hipSuccess;
-    if (rc == PCR_OK) {
-        {
-            ProfScope ps(ctx, "pn2_logsoftmax");
-            hipLaunchKernelGGL(pn2_logsoftmax_kernel, dim3((unsigned)((n_obj + PN2_BLOCK - 1) / PN2_BLOCK)), dim3(PN2_BLOCK), 0, ctx->stream, logits, (uint32_t)n_obj, n_class,
-                               logp_dev, pred_dev);
-        }
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(logp, logp_dev, n_obj * n_class * 4, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess && pred) e = hipMemcpyAsync(pred, pred_dev, n_obj * 4, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess && global_feat) e = hipMemcpyAsync(global_feat, ga_out, n_obj * c_last * 4, hipMemcpyDeviceToHost, ctx->stream);
-        if (fps_idx) {
-            size_t off = 0;
-            for (uint32_t l = 0; l < ns && e == hipSuccess; l++) {
-                e = hipMemcpyAsync(fps_idx + off, fps[l], n_obj * N[l + 1] * 4, hipMemcpyDeviceToHost, ctx->stream);
-                off += n_obj * N[l + 1];
-            }
-        }
-    }
-    const hipError_t e2 = hipStreamSynchronize(ctx->stream);      // the one wait: `keep` and the staging block are read until here
-    if (rc) return rc;
-    if (e != hipSuccess || e2 != hipSuccess) return fail(ctx, PCR_ERR_HIP, "pcr_pn2_forward_f32", e != hipSuccess ? e : e2);
-    prof_flush(ctx);
-    return PCR_OK;
+    return pass_tail(ctx, who, rc, model, ga_out, c_last, n_obj, tail, logp, more);      // `keep` lives until its wait is over
 }
 
 // ---- the vanilla PointNet: model, stage entry point, forward pass ---------------------------------------------------------------------------------
 namespace {
 
-constexpr uint32_t PN1_TNET_LAYERS = 6;      // three convolutions, two FC layers with BN, the last linear layer
-
-// the layers of a descriptor in weight order; false for a descriptor outside the limits
-bool pn1_shapes(const pcr_pn1_desc& d, std::vector<LayerShape>& shapes)
-{
-    if (d.D0 > PN2_MAX_WIDTH - 3 || d.stn3 > 1 || d.fstn > 1 || d.n_mlp < 2 || d.n_mlp > PCR_PN2_MAX_MLP || d.n_fc < 1 || d.n_fc > PCR_PN2_MAX_FC) return false;
-    if (!std::isfinite(d.bn_eps)) return false;
-    for (uint32_t i = 0; i < d.n_mlp; i++)
-        if (d.widths[i] < 1 || d.widths[i] > PN2_MAX_WIDTH) return false;
-    for (uint32_t i = 0; i < d.n_fc; i++)
-        if (d.fc_widths[i] < 1 || d.fc_widths[i] > PN2_MAX_WIDTH) return false;
-    if (d.stn3 || d.fstn) {
-        for (uint32_t w : d.tnet_conv) if (w < 1 || w > PN2_MAX_WIDTH) return false;
-        for (uint32_t w : d.tnet_fc) if (w < 1 || w > PN2_MAX_WIDTH) return false;
-    }
-    if (d.fstn && d.widths[0] > PN1_MAX_TRANSFORM) return false;
-    auto tnet = [&](uint32_t cin, uint32_t k) {
-        uint32_t K = cin;
-        for (uint32_t w : d.tnet_conv) { shapes.push_back({ K, w, true }); K = w; }
-        for (uint32_t w : d.tnet_fc) { shapes.push_back({ K, w, true }); K = w; }
-        shapes.push_back({ K, k * k, false });
-    };
-    const uint32_t C0 = 3 + d.D0;
-    if (d.stn3) tnet(C0, 3);
-    uint32_t K = C0;
-    for (uint32_t i = 0; i < d.n_mlp; i++) { shapes.push_back({ K, d.widths[i], true }); K = d.widths[i]; }
-    if (d.fstn) tnet(d.widths[0], d.widths[0]);
-    for (uint32_t i = 0; i < d.n_fc; i++) { shapes.push_back({ K, d.fc_widths[i], i + 1 < d.n_fc }); K = d.fc_widths[i]; }
-    return true;
-}
-
 bool pn1_desc_info(const pcr_pn1_desc& d, size_t npts_hint, pcr_pn2_info* info)
 {
-    std::vector<LayerShape> shapes;
-    if (!pn1_shapes(d, shapes)) return false;
+    Pn1Layers ly;
+    if (!pn1_layers(d, ly)) return false;
+    const std::vector<LayerShape>& shapes = ly.shapes;
     memset(info, 0, sizeof(*info));
-    for (const LayerShape& s : shapes) info->n_weights += (uint64_t)s.K * s.N + s.N + (s.bn ? 4ull * s.N : 0ull);
+    info->n_weights = weight_count(shapes);
     info->n_class = d.fc_widths[d.n_fc - 1];
     info->c_last = d.widths[d.n_mlp - 1];
     uint64_t per_point = 0, per_object = 0;
@@ -1238,22 +1243,6 @@ bool pn1_desc_info(const pcr_pn1_desc& d, size_t npts_hint, pcr_pn2_info* info)
     return true;
 }
 
-void stage_strides(Pn1Stage& st)
-{
-    st.s0 = st.s1 = 4;
-    for (uint32_t l = 0; l < st.n; l++) {
-        uint32_t& s = (l & 1u) ? st.s1 : st.s0;
-        s = std::max(s, st.L[l].Kpad + 4);
-    }
-}
-
-bool pn1_model_of(pcr_ctx* ctx, const pcr_pn2_model* model, const char* who)
-{
-    if (model->pn1) return true;
-    fail(ctx, PCR_ERR_ARG, (std::string(who) + ": not a model of pcr_pn1_model_create").c_str());
-    return false;
-}
-
 }  // namespace
 
 extern "C" int pcr_pn1_model_create(pcr_ctx* ctx, const pcr_pn1_desc* desc, const float* weights, size_t n_weights, pcr_pn2_model** out)
@@ -1261,54 +1250,35 @@ extern "C" int pcr_pn1_model_create(pcr_ctx* ctx, const pcr_pn1_desc* desc, cons
     if (out) *out = nullptr;
     if (!ctx || !desc || !weights || !out) return fail(ctx, PCR_ERR_ARG, "pcr_pn1_model_create");
     auto bad = [&](const char* what) { return fail(ctx, PCR_ERR_ARG, (std::string("pcr_pn1_model_create") + what).c_str()); };
-    std::vector<LayerShape> shapes;
-    if (!pn1_shapes(*desc, shapes)) return bad(": a descriptor outside the limits (see include/pcr.h)");
-    uint64_t need = 0;
-    for (const LayerShape& s : shapes) need += (uint64_t)s.K * s.N + s.N + (s.bn ? 4ull * s.N : 0ull);
-    if (n_weights != need) return bad(": n_weights is not the model's count");
-    for (size_t i = 0; i < n_weights; i++)
-        if (!std::isfinite(weights[i])) return bad(": a non-finite weight");
-    std::vector<float> img;
-    std::vector<size_t> w_off, b_off;
-    if (const char* what = fold_layers(shapes, weights, desc->bn_eps, img, w_off, b_off)) return bad(what);
-    PCR_HIP(ctx, hipSetDevice(ctx->device));
-    std::unique_ptr<pcr_pn2_model> m(new pcr_pn2_model());
-    memset(&m->desc, 0, sizeof(m->desc));
-    memset(&m->ssg, 0, sizeof(m->ssg));
+    Pn1Layers ly;
+    if (!pn1_layers(*desc, ly)) return bad(": a descriptor outside the limits (see include/pcr.h)");
+    std::unique_ptr<pcr_pn2_model> m;        // an error path below frees the device block with it
+    std::vector<LayerDev> layer;
+    const int rc = model_upload(ctx, "pcr_pn1_model_create", "pointnet", ly.shapes, weights, n_weights, desc->bn_eps, m, layer);
+    if (rc) return rc;
     m->pn1 = true;
     m->d1 = *desc;
-    m->device = ctx->device;
-    m->n_weights = need;
-    PCR_HIP(ctx, hipMalloc((void**)&m->dev, img.size() * 4));
-    hipError_t e = hipMemcpy(m->dev, img.data(), img.size() * 4, hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(m->dev); return fail(ctx, PCR_ERR_HIP, "pointnet: the upload of a model", e); }
     // ---- the stages and the heads over the layers
-    auto layer = [&](size_t i) {
-        LayerDev L;
-        L.w = m->dev + w_off[i]; L.b = m->dev + b_off[i];
-        L.K = shapes[i].K; L.Kpad = pad16(shapes[i].K); L.N = shapes[i].N; L.Npad = pad16(shapes[i].N);
-        return L;
-    };
-    const size_t stn0 = 0, enc0 = desc->stn3 ? PN1_TNET_LAYERS : 0, fstn0 = enc0 + desc->n_mlp, head0 = fstn0 + (desc->fstn ? PN1_TNET_LAYERS : 0);
+    const size_t stn0 = ly.stn_first, enc0 = ly.enc_first, fstn0 = ly.fstn_first, head0 = ly.head_first;
     auto tnet_head = [&](Chain& ch, size_t first) {
         ch.n = 3;
-        for (uint32_t k = 0; k < 3; k++) ch.L[k] = layer(first + 3 + k);
-        chain_strides(ch);
+        for (uint32_t k = 0; k < 3; k++) ch.L[k] = layer[first + 3 + k];
+        lds_strides(ch);
     };
     if (desc->stn3) {
         Pn1Stage& st = m->stage[0];
-        for (uint32_t k = 0; k < 3; k++) st.L[st.n++] = layer(stn0 + k);
+        for (uint32_t k = 0; k < 3; k++) st.L[st.n++] = layer[stn0 + k];
         tnet_head(m->tnet_head[0], stn0);
     }
     if (desc->fstn) {
         Pn1Stage& st = m->stage[1];
-        st.L[st.n++] = layer(enc0);
-        for (uint32_t k = 0; k < 3; k++) st.L[st.n++] = layer(fstn0 + k);
+        st.L[st.n++] = layer[enc0];
+        for (uint32_t k = 0; k < 3; k++) st.L[st.n++] = layer[fstn0 + k];
         tnet_head(m->tnet_head[1], fstn0);
     }
     {
         Pn1Stage& st = m->stage[2];
-        st.L[st.n++] = layer(enc0);
+        st.L[st.n++] = layer[enc0];
         if (desc->fstn) {
             LayerDev T;
             T.w = T.b = nullptr;
@@ -1316,20 +1286,18 @@ extern "C" int pcr_pn1_model_create(pcr_ctx* ctx, const pcr_pn1_desc* desc, cons
             st.t_step = st.n;
             st.L[st.n++] = T;
         }
-        for (uint32_t k = 1; k < desc->n_mlp; k++) st.L[st.n++] = layer(enc0 + k);
+        for (uint32_t k = 1; k < desc->n_mlp; k++) st.L[st.n++] = layer[enc0 + k];
         st.relu_last = 0;
     }
     for (Pn1Stage& st : m->stage) {
-        stage_strides(st);
-        if (st.n && st.lds_bytes(16) > PN2_LDS_LIMIT) { (void)hipFree(m->dev); return bad(": a stage does not fit in LDS at 16 rows (see include/pcr.h)"); }
+        lds_strides(st);
+        if (st.n && st.lds_bytes(16) > PN2_LDS_LIMIT) return bad(": a stage does not fit in LDS at 16 rows (see include/pcr.h)");
     }
     m->head.n = desc->n_fc;
-    for (uint32_t k = 0; k < m->head.n; k++) m->head.L[k] = layer(head0 + k);
-    chain_strides(m->head);
-    if (m->head.lds_bytes(16) > PN2_LDS_LIMIT || (desc->stn3 && m->tnet_head[0].lds_bytes(16) > PN2_LDS_LIMIT) || (desc->fstn && m->tnet_head[1].lds_bytes(16) > PN2_LDS_LIMIT)) {
-        (void)hipFree(m->dev);
+    for (uint32_t k = 0; k < m->head.n; k++) m->head.L[k] = layer[head0 + k];
+    lds_strides(m->head);
+    if (m->head.lds_bytes(16) > PN2_LDS_LIMIT || (desc->stn3 && m->tnet_head[0].lds_bytes(16) > PN2_LDS_LIMIT) || (desc->fstn && m->tnet_head[1].lds_bytes(16) > PN2_LDS_LIMIT))
         return bad(": a head does not fit in LDS at 16 rows (see include/pcr.h)");
-    }
     *out = m.release();
     return PCR_OK;
 }
@@ -1360,11 +1328,11 @@ extern "C" int pcr_pointwise_chain_max_f32(pcr_ctx* ctx, const pcr_pn2_model* mo
     if (D > 0 && !features) return bad(": the model takes features");
     if (stage == 0 && trans3) return bad(": stage 0 takes no transform");
     if (has_t ? !trans_feat : trans_feat != nullptr) return bad(": trans_feat goes with stage 2 of a model with a feature T-Net, and only with it");
-    if (n_seg > PN2_MAX_ROWS || cloud->n > PN2_MAX_ROWS) return bad(": too large");
+    if (n_seg > PN_MAX_ROWS || cloud->n > PN_MAX_ROWS) return bad(": too large");
     if (!seg_ok(seg_ptr, n_seg, cloud->n)) return bad(": seg_ptr must ascend and end inside its cloud");
     if (n_seg == 0) return PCR_OK;
     if (!out) return bad(": out is NULL");
-    if (n_seg > PN2_MAX_ROWS / width || (has_t && n_seg > PN2_MAX_ROWS / (K * K))) return bad(": too large");
+    if (n_seg > PN_MAX_ROWS / width || (has_t && n_seg > PN_MAX_ROWS / (K * K))) return bad(": too large");
     const size_t p0 = seg_ptr[0], np = seg_ptr[n_seg] - p0;
     size_t max_pts = 0;
     for (size_t s = 0; s < n_seg; s++) max_pts = std::max<size_t>(max_pts, seg_ptr[s + 1] - seg_ptr[s]);
@@ -1404,68 +1372,36 @@ extern "C" int pcr_pointwise_chain_max_f32(pcr_ctx* ctx, const pcr_pn2_model* mo
 extern "C" int pcr_pointnet_forward_f32(pcr_ctx* ctx, const pcr_pn2_model* model, const float* objects, size_t n_obj, size_t npts, float* logp, int32_t* pred,
                                         float* global_feat, float* trans, float* trans_feat)
 {
-    if (!ctx || !model) return fail(ctx, PCR_ERR_ARG, "pcr_pointnet_forward_f32");
-    if (!pn1_model_of(ctx, model, "pcr_pointnet_forward_f32")) return PCR_ERR_ARG;
-    if (model->device != ctx->device) return fail(ctx, PCR_ERR_ARG, "pcr_pointnet_forward_f32: the model lives on another device");
-    if (npts < 1) return fail(ctx, PCR_ERR_ARG, "pcr_pointnet_forward_f32: npts must be >= 1");
+    const char* who = "pcr_pointnet_forward_f32";
+    int rc = pass_model(ctx, model, who, true);
+    if (rc) return rc;
     const pcr_pn1_desc& d = model->d1;
-    if ((trans && !d.stn3) || (trans_feat && !d.fstn)) return fail(ctx, PCR_ERR_ARG, "pcr_pointnet_forward_f32: the model has no such T-Net");
-    if (n_obj == 0) return PCR_OK;
-    if (!objects || !logp) return fail(ctx, PCR_ERR_ARG, "pcr_pointnet_forward_f32: objects / logp is NULL");
-    const uint32_t D0 = d.D0, C0 = 3 + D0, K = d.widths[0], KK = K * K;
+    const uint32_t D0 = d.D0, K = d.widths[0], KK = K * K;
+    rc = pass_args(ctx, who, (trans && !d.stn3) || (trans_feat && !d.fstn) ? ": the model has no such T-Net" : nullptr, objects, logp, n_obj, npts, 3 + D0);
+    if (rc || n_obj == 0) return rc;
     const uint32_t n_class = model->head.n_out(), c_last = model->stage[2].n_out(), c_tnet = (d.stn3 || d.fstn) ? d.tnet_conv[2] : 0;
-    if (n_obj > PN2_MAX_ROWS || npts > PN2_MAX_ROWS || (unsigned long long)n_obj * npts > PN2_MAX_ROWS / C0) return fail(ctx, PCR_ERR_ARG, "pcr_pointnet_forward_f32: too large");
-    if ((unsigned long long)n_obj * std::max(std::max(c_last, n_class), std::max(c_tnet, d.fstn ? KK : 0u)) > PN2_MAX_ROWS)
+    if ((unsigned long long)n_obj * std::max(std::max(c_last, n_class), std::max(c_tnet, d.fstn ? KK : 0u)) > PN_MAX_ROWS)
         return fail(ctx, PCR_ERR_ARG, "pcr_pointnet_forward_f32: too large");
-    PCR_HIP(ctx, hipSetDevice(ctx->device));
-    // ---- one block: [uploaded: x y z | features | segments] [the T-Nets' pooled rows, trans, trans_feat] [global feature] [head]
-    const size_t P = n_obj * npts;
-    float *x0, *feat0, *t3, *tk, *logits, *logp_dev;
-    uint32_t *seg, *pooled, *gf;             // pooled / gf: keys while their chain runs, floats once it is decoded
-    int32_t* pred_dev;
+    // ---- one block: [uploaded: x y z | features | segments] [the T-Nets' pooled rows, trans, trans_feat | global feature | head]
+    PassInput in;
+    in.declare(n_obj, &npts, 1, D0);
+    float *t3, *tk;
+    uint32_t *pooled, *gf;                   // pooled / gf: keys while their chain runs, floats once it is decoded
     Layout L;
-    L.add(&x0, 3 * P);
-    L.add(&feat0, P * D0);
-    L.add(&seg, n_obj + 1);
-    const size_t upload_bytes = L.bytes();
     L.add(&pooled, n_obj * c_tnet);          // both T-Nets pool into it, one after the other
     L.add(&t3, d.stn3 ? n_obj * 9 : 0);
     L.add(&tk, d.fstn ? n_obj * KK : 0);
     L.add(&gf, n_obj * c_last);
-    L.add(&logits, n_obj * n_class);
-    L.add(&logp_dev, n_obj * n_class);
-    L.add(&pred_dev, n_obj);
-    int rc = bind_scratch(ctx, L);
+    PassTail tail;
+    tail.declare(L, n_obj, n_class);
+    rc = pass_upload(ctx, who, in, { &L }, objects, n_obj, &npts, 1, D0);
     if (rc) return rc;
-    rc = ensure_stage(ctx, upload_bytes);
-    if (rc) return rc;
-    L.bind(ctx->host_stage);                 // the uploaded part, laid out the same way in the pinned staging block
-    {
-        float *hx = x0, *hy = x0 + P, *hz = x0 + 2 * P;
-        for (size_t i = 0; i < P; i++) {
-            const float* r = objects + i * C0;
-            for (uint32_t c = 0; c < C0; c++)
-                if (!(fabsf(r[c]) <= FLT_MAX)) return fail(ctx, PCR_ERR_ARG, "pcr_pointnet_forward_f32: a non-finite coordinate or feature");
-            hx[i] = r[0]; hy[i] = r[1]; hz[i] = r[2];
-            for (uint32_t c = 0; c < D0; c++) feat0[i * D0 + c] = r[3 + c];
-        }
-        for (size_t o = 0; o <= n_obj; o++) seg[o] = (uint32_t)(o * npts);
-    }
-    L.bind(ctx->scratch);
-    PCR_HIP(ctx, hipMemcpyAsync(ctx->scratch, ctx->host_stage, upload_bytes, hipMemcpyHostToDevice, ctx->stream));
+    const size_t P = in.P;
     Pn1Args pa;
     memset(&pa, 0, sizeof(pa));
-    pa.x = x0; pa.y = x0 + P; pa.z = x0 + 2 * P; pa.feat = feat0; pa.seg_ptr = seg; pa.D = D0;
-    auto head = [&](const Chain& ch, const float* in, uint32_t width, float* to) {      // one row per object through the FC layers
-        ChainArgs a;
-        memset(&a, 0, sizeof(a));
-        a.feat = in; a.out = to;
-        a.rows = (uint32_t)n_obj;
-        a.D = width; a.nsample = 1; a.mode = PN2_HEAD;
-        return chain_launch(ctx, ch, a, n_obj, "pn2_head");
-    };
+    pa.x = in.x0; pa.y = in.x0 + P; pa.z = in.x0 + 2 * P; pa.feat = in.feat0; pa.seg_ptr = in.seg[0]; pa.D = D0;
     auto tnet = [&](const Chain& ch, float* to, uint32_t k) {                          // pooled rows -> the FC layers -> + identity
-        int r = head(ch, (const float*)pooled, c_tnet, to);
+        int r = head_launch(ctx, ch, (const float*)pooled, c_tnet, to, n_obj);
         if (r) return r;
         ProfScope ps(ctx, "pn1_identity");
         hipLaunchKernelGGL(pn1_identity_kernel, dim3((unsigned)((n_obj * k + PN2_BLOCK - 1) / PN2_BLOCK)), dim3(PN2_BLOCK), 0, ctx->stream, to, (uint32_t)n_obj, k);
@@ -1488,24 +1424,6 @@ extern "C" int pcr_pointnet_forward_f32(pcr_ctx* ctx, const pcr_pn2_model* model
         pa.out = gf;
         rc = pn1_launch(ctx, model->stage[2], pa, n_obj, npts);
     }
-    if (rc == PCR_OK) rc = head(model->head, (const float*)gf, c_last, logits);
-    hipError_t e = hipSuccess;
-    if (rc == PCR_OK) {
-        {
-            ProfScope ps(ctx, "pn2_logsoftmax");
-            hipLaunchKernelGGL(pn2_logsoftmax_kernel, dim3((unsigned)((n_obj + PN2_BLOCK - 1) / PN2_BLOCK)), dim3(PN2_BLOCK), 0, ctx->stream, logits, (uint32_t)n_obj, n_class,
-                               logp_dev, pred_dev);
-        }
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(logp, logp_dev, n_obj * n_class * 4, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess && pred) e = hipMemcpyAsync(pred, pred_dev, n_obj * 4, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess && global_feat) e = hipMemcpyAsync(global_feat, gf, n_obj * c_last * 4, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess && trans) e = hipMemcpyAsync(trans, t3, n_obj * 9 * 4, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess && trans_feat) e = hipMemcpyAsync(trans_feat, tk, (size_t)n_obj * KK * 4, hipMemcpyDeviceToHost, ctx->stream);
-    }
-    const hipError_t e2 = hipStreamSynchronize(ctx->stream);      // the one wait: the staging block is read until here
-    if (rc) return rc;
-    if (e != hipSuccess || e2 != hipSuccess) return fail(ctx, PCR_ERR_HIP, "pcr_pointnet_forward_f32", e != hipSuccess ? e : e2);
-    prof_flush(ctx);
-    return PCR_OK;
+    return pass_tail(ctx, who, rc, model, (const float*)gf, c_last, n_obj, tail, logp,
+                     { { pred, tail.pred, n_obj * 4 }, { global_feat, gf, n_obj * c_last * 4 }, { trans, t3, n_obj * 9 * 4 }, { trans_feat, tk, (size_t)n_obj * KK * 4 } });
 }

@@ -3,7 +3,7 @@
 // pcr_pn2_trainer_create in include/pcr.h.
 //
 // Batch statistics break the eval pass's layer fusion: the pass goes layer by layer and keeps every layer's z and y in HBM.  This file holds the SSG model's
-// own part: its shapes, its plan's sampling and per-stage buffers, FPS / centres / ball query / gather per stage, the max, the gather back.  The layer step
+// own part: its plan's sampling and per-stage buffers, FPS / centres / ball query / gather per stage, the max, the gather back.  The layer step
 // (LayerRun), the plan base, the create / info / call head and tail and the kernels live in pointnet_train_common.hpp, which the vanilla PointNet's pass
 // (pointnet_train.hip) includes too:
 //   pn2t_gather        the padded rows of an SA layer: (xyz - centre | features) per row, and the point every row read
@@ -22,41 +22,6 @@
 #include "pointnet_train_common.hpp"
 
 namespace {
-
-// the layers of a descriptor, or false for one outside the limits of pcr_pn2_model_create
-bool trainer_shapes(const pcr_pn2_desc& d, pcr_pn2_trainer& t)
-{
-    if (d.n_sa < 1 || d.n_sa > PCR_PN2_MAX_SA || d.n_fc < 1 || d.n_fc > PCR_PN2_MAX_FC) return false;
-    if (d.D0 > T_MAX_WIDTH - 3 || !std::isfinite(d.bn_eps)) return false;
-    uint32_t D = d.D0;
-    t.n_sampling = 0;
-    for (uint32_t l = 0; l < d.n_sa; l++) {
-        const pcr_pn2_sa_desc& s = d.sa[l];
-        if (s.group_all > 1 || (s.group_all && l + 1 != d.n_sa)) return false;
-        if (s.n_mlp < 1 || s.n_mlp > PCR_PN2_MAX_MLP) return false;
-        if (!s.group_all && (s.npoint < 1 || s.nsample < 1 || s.nsample > 65536 || !(s.radius >= 0.0) || std::isinf(s.radius))) return false;
-        uint32_t K = 3 + D;
-        if (K > T_MAX_WIDTH) return false;
-        t.sa_first[l] = (uint32_t)t.layers.size();
-        t.sa_in[l] = K;
-        for (uint32_t i = 0; i < s.n_mlp; i++) {
-            if (s.widths[i] < 1 || s.widths[i] > T_MAX_WIDTH) return false;
-            layer_push(t, K, s.widths[i], true);
-            K = s.widths[i];
-        }
-        t.sa_out[l] = K;
-        D = K;
-        if (!s.group_all) t.n_sampling++;
-    }
-    t.head_first = (uint32_t)t.layers.size();
-    uint32_t K = D;
-    for (uint32_t i = 0; i < d.n_fc; i++) {
-        if (d.fc_widths[i] < 1 || d.fc_widths[i] > T_MAX_WIDTH) return false;
-        layer_push(t, K, d.fc_widths[i], i + 1 < d.n_fc);
-        K = d.fc_widths[i];
-    }
-    return true;
-}
 
 // the stages of one call: every SA layer, then the head
 struct Stage {
@@ -86,17 +51,17 @@ bool make_plan(const pcr_pn2_trainer* t, size_t n_obj, size_t npts, Plan& P)
 {
     const pcr_pn2_desc& d = t->desc;
     const uint32_t ns = t->n_sampling, C0 = 3 + d.D0;
-    if (n_obj > T_MAX_ROWS || npts > T_MAX_ROWS || (unsigned long long)n_obj * npts > T_MAX_ROWS / C0) return false;
+    if (n_obj > PN_MAX_ROWS || npts > PN_MAX_ROWS || (unsigned long long)n_obj * npts > PN_MAX_ROWS / C0) return false;
     P.N[0] = npts;
     for (uint32_t l = 0; l < ns; l++) {
         P.N[l + 1] = d.sa[l].npoint;
         const unsigned long long rows = (unsigned long long)n_obj * d.sa[l].npoint * d.sa[l].nsample;
-        if (rows > T_MAX_ROWS / T_MAX_WIDTH) return false;
+        if (rows > PN_MAX_ROWS / PN_MAX_WIDTH) return false;
         P.stages.push_back({ t->sa_first[l], d.sa[l].n_mlp, (uint32_t)rows, d.sa[l].nsample, (uint32_t)(n_obj * d.sa[l].npoint) });
     }
     if (d.sa[d.n_sa - 1].group_all) {
         const unsigned long long rows = (unsigned long long)n_obj * P.N[ns];
-        if (rows > T_MAX_ROWS / T_MAX_WIDTH) return false;
+        if (rows > PN_MAX_ROWS / PN_MAX_WIDTH) return false;
         P.stages.push_back({ t->sa_first[ns], d.sa[ns].n_mlp, (uint32_t)rows, (uint32_t)P.N[ns], (uint32_t)n_obj });
     }
     P.stages.push_back({ t->head_first, d.n_fc, (uint32_t)n_obj, 0u, (uint32_t)n_obj });
@@ -145,7 +110,13 @@ extern "C" int pcr_pn2_trainer_create(pcr_ctx* ctx, const pcr_pn2_desc* desc, co
     if (!ctx || !desc || !weights || !out) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_trainer_create");
     std::unique_ptr<pcr_pn2_trainer> t(new pcr_pn2_trainer());
     t->desc = *desc;
-    if (!trainer_shapes(*desc, *t)) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_trainer_create: a descriptor outside the limits (see include/pcr.h)");
+    pcr_pn2_msg_desc md;                     // the models' superset descriptor: the trainer's layers are the ones a model of the same descriptor has
+    Pn2Layers ly;
+    if (!pn2_msg_desc_of(*desc, md) || !pn2_layers(md, ly)) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_trainer_create: a descriptor outside the limits (see include/pcr.h)");
+    for (const LayerShape& s : ly.shapes) layer_push(*t, s);
+    for (uint32_t l = 0; l < desc->n_sa; l++) { t->sa_first[l] = ly.first[l][0]; t->sa_in[l] = ly.sa_in[l]; t->sa_out[l] = ly.sa_out[l]; }
+    t->head_first = ly.head_first;
+    t->n_sampling = ly.n_sampling;
     if (!desc->sa[desc->n_sa - 1].group_all) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_trainer_create: the last SA layer must be group_all");
     return trainer_finish(ctx, "pcr_pn2_trainer_create", std::move(t), nullptr, weights, n_weights, dropout_p, bn_momentum, chunk_rows, out);
 }

@@ -20,7 +20,6 @@
 
 namespace {
 
-constexpr uint32_t T1_MAX_K = 128;      // a feature transform is staged in LDS
 constexpr uint32_t T1_KB = 64;          // the products z and dx: f32 chains over blocks of 64 k, the blocks added in f64
 
 // C = init + A B as pn2t_gemm_kernel lays it out (one chunk: all of k), but BLOCKED over k: inside a block of T1_KB consecutive k an output is one f32 fma
@@ -209,7 +208,7 @@ __global__ __launch_bounds__(T_BLOCK) void pn1t_add_kernel(const float* a, const
 __global__ __launch_bounds__(T_BLOCK) void pn1t_reg_kernel(const float* __restrict__ A, uint32_t K, uint32_t n_obj, double scale, double* __restrict__ Mb,
                                                            double* __restrict__ norm, float* __restrict__ dA)
 {
-    __shared__ double rows[T1_MAX_K];
+    __shared__ double rows[PN_MAX_TRANSFORM];
     __shared__ double nrm_s;
     const size_t b = blockIdx.x;
     const float* Ab = A + b * K * K;
@@ -258,41 +257,6 @@ __global__ void pn1t_loss_fin_kernel(const double* __restrict__ norm, uint32_t n
     loss[0] = loss[1] + scale * reg;
 }
 
-// the layers of a descriptor in weight order, or false for one outside the limits
-bool trainer1_shapes(const pcr_pn1_desc& d, pcr_pn2_trainer& t)
-{
-    if (d.stn3 > 1 || d.fstn > 1 || d.n_mlp < 2 || d.n_mlp > PCR_PN2_MAX_MLP || d.n_fc < 1 || d.n_fc > PCR_PN2_MAX_FC) return false;
-    if (d.D0 > T_MAX_WIDTH - 3 || !std::isfinite(d.bn_eps)) return false;
-    for (uint32_t i = 0; i < d.n_mlp; i++)
-        if (d.widths[i] < 1 || d.widths[i] > T_MAX_WIDTH) return false;
-    for (uint32_t i = 0; i < d.n_fc; i++)
-        if (d.fc_widths[i] < 1 || d.fc_widths[i] > T_MAX_WIDTH) return false;
-    if (d.stn3 || d.fstn) {
-        for (uint32_t w : d.tnet_conv)
-            if (w < 1 || w > T_MAX_WIDTH) return false;
-        for (uint32_t w : d.tnet_fc)
-            if (w < 1 || w > T_MAX_WIDTH) return false;
-    }
-    if (d.fstn && d.widths[0] > T1_MAX_K) return false;
-    auto tnet = [&](uint32_t cin, uint32_t k) {      // the last layer has k k outputs (up to 16 384): T_MAX_WIDTH does not apply to it
-        for (uint32_t w : d.tnet_conv) { layer_push(t, cin, w, true); cin = w; }
-        for (uint32_t w : d.tnet_fc) { layer_push(t, cin, w, true); cin = w; }
-        layer_push(t, cin, k * k, false);
-    };
-    const uint32_t C0 = 3 + d.D0;
-    t.stn_first = 0;
-    if (d.stn3) tnet(C0, 3);
-    t.enc_first = (uint32_t)t.layers.size();
-    uint32_t K = C0;
-    for (uint32_t i = 0; i < d.n_mlp; i++) { layer_push(t, K, d.widths[i], true); K = d.widths[i]; }
-    t.fstn_first = (uint32_t)t.layers.size();
-    if (d.fstn) tnet(d.widths[0], d.widths[0]);
-    t.head_first = (uint32_t)t.layers.size();
-    for (uint32_t i = 0; i < d.n_fc; i++) { layer_push(t, K, d.fc_widths[i], i + 1 < d.n_fc); K = d.fc_widths[i]; }
-    t.n_sampling = 0;
-    return true;
-}
-
 // the device block of one call: PlanBase's, with the per-stack buffers in `own`
 struct Plan1 : PlanBase {
     uint32_t rows = 0, n_obj = 0, npts = 0;
@@ -310,7 +274,7 @@ bool make_plan1(const pcr_pn2_trainer* t, size_t n_obj, size_t npts, Plan1& P)
 {
     const pcr_pn1_desc& d = t->desc1;
     const uint32_t C0 = 3 + d.D0, K = d.widths[0];
-    if (n_obj > 65535u || npts > T_MAX_ROWS || (unsigned long long)n_obj * npts > T_MAX_ROWS / T_MAX_WIDTH) return false;
+    if (n_obj > 65535u || npts > PN_MAX_ROWS || (unsigned long long)n_obj * npts > PN_MAX_ROWS / PN_MAX_WIDTH) return false;
     const size_t rows = n_obj * npts;
     P.rows = (uint32_t)rows; P.n_obj = (uint32_t)n_obj; P.npts = (uint32_t)npts;
     P.up.add(&P.obj, rows * C0);
@@ -435,7 +399,10 @@ extern "C" int pcr_pn1_trainer_create(pcr_ctx* ctx, const pcr_pn1_desc* desc, co
     t->kind = 1;
     t->desc1 = *desc;
     t->desc.bn_eps = desc->bn_eps;
-    if (!trainer1_shapes(*desc, *t)) return fail(ctx, PCR_ERR_ARG, "pcr_pn1_trainer_create: a descriptor outside the limits (see include/pcr.h)");
+    Pn1Layers ly;                            // the layers a model of the same descriptor has
+    if (!pn1_layers(*desc, ly)) return fail(ctx, PCR_ERR_ARG, "pcr_pn1_trainer_create: a descriptor outside the limits (see include/pcr.h)");
+    for (const LayerShape& s : ly.shapes) layer_push(*t, s);
+    t->stn_first = ly.stn_first; t->enc_first = ly.enc_first; t->fstn_first = ly.fstn_first; t->head_first = ly.head_first;
     t->reg_scale = reg_scale;
     return trainer_finish(ctx, "pcr_pn1_trainer_create", std::move(t), std::isfinite(reg_scale) ? nullptr : ": reg_scale must be finite", weights, n_weights, dropout_p,
                           bn_momentum, chunk_rows, out);

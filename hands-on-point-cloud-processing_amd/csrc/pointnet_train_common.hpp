@@ -4,10 +4,11 @@
 // Host: the trainer handle; layer_push (the weight layout of a layer); trainer_finish (what both creates do behind their shape check); trainer_info_common;
 // keep_rule (the dropout mask by rule); PlanBase (the shared part of a call's device block); call_head / call_upload / call_tail (the checks, the staging and
 // the downloads of a call); LayerRun (one layer forward, one layer backward, the bias gradient, the max's scatter back: the only place that launches them).
-// What a pass keeps to itself: its shapes, its plan's own buffers, and what happens between the layers.
+// What a pass keeps to itself: its plan's own buffers, and what happens between the layers (its layers, limits and weight count: pointnet_layers.hpp).
 // The contracts are above pcr_pn2_trainer_create and pcr_pn1_trainer_create in include/pcr.h.
 #pragma once
 #include "pcr_internal.hpp"
+#include "pointnet_layers.hpp"
 
 #include <algorithm>
 #include <cfloat>
@@ -20,8 +21,6 @@ using namespace pcr;
 namespace {
 
 constexpr int T_BLOCK = 256;
-constexpr uint32_t T_MAX_WIDTH = 1024;
-constexpr unsigned long long T_MAX_ROWS = 0x7FFFFFF0ull;
 constexpr uint32_t T_DEFAULT_CHUNK = 256;
 constexpr uint32_t T_NONE = 0xFFFFFFFFu;
 
@@ -401,17 +400,17 @@ inline const char* weights_ok(const pcr_pn2_trainer* t, const float* w)
 }
 
 // one more layer behind the ones the trainer has, in weight order: w, b and, with BN, gamma, beta, running_mean, running_var.  t.n_weights is the running end
-inline void layer_push(pcr_pn2_trainer& t, uint32_t K, uint32_t N, bool bn)
+inline void layer_push(pcr_pn2_trainer& t, const LayerShape& s)
 {
-    size_t off = t.n_weights;
+    const size_t N = s.N;
     TLayer L;
-    L.K = K; L.N = N; L.bn = bn;
-    L.w = off; off += (size_t)K * N;
-    L.b = off; off += N;
+    L.K = s.K; L.N = s.N; L.bn = s.bn;
+    L.w = t.n_weights;
+    L.b = L.w + (size_t)s.K * N;
     L.gamma = L.beta = L.rmean = L.rvar = 0;
-    if (bn) { L.gamma = off; L.beta = off + N; L.rmean = off + 2 * (size_t)N; L.rvar = off + 3 * (size_t)N; off += 4 * (size_t)N; }
+    if (s.bn) { L.gamma = L.b + N; L.beta = L.b + 2 * N; L.rmean = L.b + 3 * N; L.rvar = L.b + 4 * N; }
     t.layers.push_back(L);
-    t.n_weights = off;
+    t.n_weights += weight_count(s);
 }
 
 // what both creates do once the layers are known: the parameter checks, the two device arrays, the upload.  Every message starts with the caller's name.
