@@ -128,6 +128,7 @@ ABI_SYMBOLS = [
     "pcr_pn1_model_create", "pcr_pn1_model_info", "pcr_pointwise_chain_max_f32", "pcr_pointnet_forward_f32",
     "pcr_pn2_trainer_create", "pcr_pn2_trainer_destroy", "pcr_pn2_trainer_info", "pcr_pn2_trainer_set_weights", "pcr_pn2_trainer_get_weights", "pcr_pn2_train_grad_f32",
     "pcr_pn1_trainer_create", "pcr_pointnet_train_grad_f32",
+    "pcr_pn2_msg_trainer_create", "pcr_pn2_msg_trainer_info",
     "pcr_mat64_create", "pcr_mat64_destroy", "pcr_mat64_info", "pcr_kmeans_step_f64", "pcr_kmeans_fit_f64", "pcr_kmeans_predict_f64", "pcr_kmeanspp_init_f64",
     "pcr_gmm_em_step_f64", "pcr_gmm_fit_f64", "pcr_gmm_predict_f64",
     "pcr_mat64_knn_f64", "pcr_spectral_graph_f64", "pcr_spgraph_info", "pcr_spgraph_read", "pcr_spgraph_destroy", "pcr_eig_small_f64",
@@ -256,6 +257,8 @@ def lib():
     L.pcr_pointwise_chain_max_f32.argtypes = [vp, vp, C.c_int, vp, vp, sz, vp, vp, vp, vp]
     L.pcr_pointnet_forward_f32.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp, vp]
     L.pcr_pn2_trainer_create.argtypes = [vp, C.POINTER(Pn2Desc), vp, sz, C.c_double, C.c_double, C.c_uint32, C.POINTER(vp)]
+    L.pcr_pn2_msg_trainer_create.argtypes = [vp, C.POINTER(Pn2MsgDesc), vp, sz, C.POINTER(C.c_double), sz, C.c_double, C.c_uint32, C.POINTER(vp)]
+    L.pcr_pn2_msg_trainer_info.argtypes = [vp, sz, sz, C.POINTER(Pn2TrainInfo), C.POINTER(Pn2MsgDesc), C.POINTER(C.c_double)]
     L.pcr_pn2_trainer_destroy.argtypes = [vp, vp]
     L.pcr_pn2_trainer_info.argtypes = [vp, sz, sz, C.POINTER(Pn2TrainInfo)]
     L.pcr_pn2_trainer_set_weights.argtypes = [vp, vp, vp, sz, C.c_int]
@@ -727,6 +730,36 @@ class Pn2Trainer:
                                                   None if st is None or not st.size else st.ctypes.data, int(seed) & 0xFFFFFFFFFFFFFFFF,
                                                   None if kp is None or not kp.size else kp.ctypes.data, C.byref(loss), logp.ctypes.data, grad.ctypes.data))
         return float(loss.value), logp[:n_obj], grad
+
+
+class Pn2MsgTrainer(Pn2Trainer):
+    """The training pass of a PointNet++ multi-scale (MSG) classifier resident in HBM (a pcr_pn2_trainer made by pcr_pn2_msg_trainer_create); the
+    contract is above pcr_pn2_msg_trainer_create in include/pcr.h.  desc: a Pn2MsgDesc; weights: the flat f32 array of pcr_pn2_msg_model_create,
+    unfolded; dropout_p: one probability per FC layer but the last.  Everything else, train_grad included, is Pn2Trainer's."""
+
+    def __init__(self, ctx: "Context", desc: Pn2MsgDesc, weights, dropout_p=(0.4, 0.5), bn_momentum: float = 0.1, chunk_rows: int = 0):
+        w = np.ascontiguousarray(weights, np.float32).reshape(-1)
+        ps = [float(p) for p in (() if dropout_p is None else np.atleast_1d(dropout_p))]
+        arr = (C.c_double * max(len(ps), 1))(*ps)
+        h = C.c_void_p()
+        ctx._ck(lib().pcr_pn2_msg_trainer_create(ctx.h, C.byref(desc), w.ctypes.data if w.size else None, w.size, arr if ps else None, len(ps), float(bn_momentum),
+                                                 int(chunk_rows), C.byref(h)))
+        self.ctx, self.h, self.desc = ctx, h, desc
+        ctx._handles.add(self)
+
+    def msg_info(self, n_obj: int = 0, npts: int = 0) -> dict:
+        """info() plus "desc" (the Pn2MsgDesc the trainer holds) and "dropout" (the hidden FC layers' probabilities); pcr_pn2_msg_trainer_info"""
+        return pn2_msg_trainer_info(self, n_obj, npts)
+
+
+def pn2_msg_trainer_info(trainer: Pn2Trainer, n_obj: int = 0, npts: int = 0) -> dict:
+    """pcr_pn2_msg_trainer_info on a Pn2Trainer or a Pn2MsgTrainer: Pn2Trainer.info()'s fields, "desc" in the superset form and "dropout", one
+    probability per FC layer but the last"""
+    i, d, ps = Pn2TrainInfo(), Pn2MsgDesc(), (C.c_double * 3)()
+    trainer.ctx._ck(lib().pcr_pn2_msg_trainer_info(trainer.h, int(n_obj), int(npts), C.byref(i), C.byref(d), ps))
+    return {"n_weights": int(i.n_weights), "device_bytes": int(i.device_bytes), "keep_per_object": int(i.keep_per_object), "chunk_rows": int(i.chunk_rows),
+            "n_class": int(i.n_class), "n_sampling": int(i.n_sampling), "dropout_p": float(i.dropout_p), "bn_momentum": float(i.bn_momentum), "desc": d,
+            "dropout": [float(ps[k]) for k in range(max(int(d.n_fc), 1) - 1)]}
 
 
 class Pn1Trainer(Pn2Trainer):
@@ -1609,6 +1642,11 @@ class Context:
     def pn2_trainer(self, desc, weights, dropout_p: float = 0.4, bn_momentum: float = 0.1, chunk_rows: int = 0) -> Pn2Trainer:
         """The training pass of the model a Pn2Desc describes (pcr_pn2_trainer_create): weights as pn2_model takes them, kept unfolded."""
         return Pn2Trainer(self, desc, weights, dropout_p, bn_momentum, chunk_rows)
+
+    def pn2_msg_trainer(self, desc, weights, dropout_p=(0.4, 0.5), bn_momentum: float = 0.1, chunk_rows: int = 0) -> Pn2MsgTrainer:
+        """The training pass of the model a Pn2MsgDesc describes (pcr_pn2_msg_trainer_create): weights as pn2_msg_model takes them, kept unfolded;
+        dropout_p: one probability per FC layer but the last (the reference: 0.4, 0.5)."""
+        return Pn2MsgTrainer(self, desc, weights, dropout_p, bn_momentum, chunk_rows)
 
     def pn1_trainer(self, desc, weights, dropout_p: float = 0.4, bn_momentum: float = 0.1, reg_scale: float = 0.001, chunk_rows: int = 0) -> Pn1Trainer:
         """The training pass of the model a Pn1Desc describes (pcr_pn1_trainer_create): weights as pn1_model takes them, kept unfolded."""

@@ -1,34 +1,44 @@
-// pointnet2_train.hip — the training pass of HomeworkFinal's PointNet++ (SSG) classifier: training-mode forward, loss, the gradient of every
-// parameter (models/pointnet2_cls_ssg.py, get_loss :50-52; train_cls.py's step without its optimiser).  The contract is written out above
-// pcr_pn2_trainer_create in include/pcr.h.
+// pointnet2_train.hip — the training pass of HomeworkFinal's PointNet++ classifiers, single-scale (SSG) and multi-scale (MSG): training-mode forward, loss,
+// the gradient of every parameter (models/pointnet2_cls_ssg.py, models/pointnet2_cls_msg.py, get_loss; train_cls.py's step without its optimiser).  The
+// contracts are written out above pcr_pn2_trainer_create and pcr_pn2_msg_trainer_create in include/pcr.h.  There is ONE pass, over the superset descriptor:
+// an SSG trainer is the case of one xyz-first branch per layer and one dropout probability.
 //
-// Batch statistics break the eval pass's layer fusion: the pass goes layer by layer and keeps every layer's z and y in HBM.  This file holds the SSG model's
-// own part: its plan's sampling and per-stage buffers, FPS / centres / ball query / gather per stage, the max, the gather back.  The layer step
-// (LayerRun), the plan base, the create / info / call head and tail and the kernels live in pointnet_train_common.hpp, which the vanilla PointNet's pass
-// (pointnet_train.hip) includes too:
-//   pn2t_gather        the padded rows of an SA layer: (xyz - centre | features) per row, and the point every row read
+// Batch statistics break the eval pass's layer fusion: the pass goes layer by layer and keeps every layer's z and y in HBM.  This file holds the model's
+// own part: its plan's sampling and per-(stage, branch) buffers, FPS / centres / ball query once per stage, then per branch the gather, the layers and the max
+// into the branch's columns of the stage's concatenated row; backward per branch the max's scatter from those columns, the layers, and the branch's part of
+// the gather back.  The layer step (LayerRun), the plan base, the create / info / call head and tail and the kernels live in pointnet_train_common.hpp,
+// which the vanilla PointNet's pass (pointnet_train.hip) includes too:
+//   pn2t_gather        the padded rows of one branch: (xyz - centre | features) or (features | xyz - centre) per row, and the point every row read
 //   pn2t_gemm_fwd      z = x W^T + b        one wave = 32 rows x 64 outputs on v_mfma_f32_16x16x4_f32, the accumulators start at the bias; every
 //   pn2t_gemm_dx       dx = dz W            MFMA takes four consecutive k, so an output is ONE fma chain over ascending k (channel, output or row)
 //   pn2t_gemm_dw       dW partials = dz^T x one chain over the rows of a chunk per (chunk, output, input), from +0
 //   pn2t_dw_reduce     dW = the chunk partials added in ascending order (f32)
 //   pn2t_stat_part / pn2t_stat_fin     f64 sums per (chunk, channel) over ascending rows, then over ascending chunks: mean, variance (two passes),
 //                      the running statistics; also the bias gradient of the last FC layer
-//   pn2t_bn_relu       y = relu(BN(z)) and, in the head, the dropout
-//   pn2t_max / pn2t_max_back            the max over a group with the lowest position among the maxima / its gradient
+//   pn2t_bn_relu       y = relu(BN(z)) and, in the head, the layer's dropout
+//   pn2t_max / pn2t_max_back            the max over a group with the lowest position among the maxima, into a column slice of the stage's row / its gradient
 //   pn2t_bnb_part / pn2t_bnb_fin / pn2t_bnb_dz      dropout, ReLU and BatchNorm backward: dbeta, dgamma, then dz in place of dy
-//   pn2t_gather_back   the gradient of a layer's input features summed per point over the rows that read it, rows ascending, in f64
+//   pn2t_gather_back   the gradient of a layer's input features summed per point over the rows of every branch that read it, in f64: one launch per
+//                      branch, branches ascending, the sum handed on in f64 and rounded by the last
 //   pn2t_loss          log_softmax, the loss, dlogits
 // No floating-point atomic anywhere; every sum over rows is ordered by the row index and chunk_rows alone.
 #include "pointnet_train_common.hpp"
 
 namespace {
 
-// the stages of one call: every SA layer, then the head
-struct Stage {
+// one branch of a stage: its layers, its rows, its columns [off, off + the last layer's width) of the stage's row
+struct Branch {
     uint32_t first, count;       // its layers
     uint32_t M;                  // rows
     uint32_t gsize;              // rows per group (head: 0, no max)
-    uint32_t groups;
+    uint32_t off;
+};
+
+// the stages of one call: every SA layer, then the head (one "branch" without a max)
+struct Stage {
+    uint32_t groups, n_branch;
+    Branch br[PCR_PN2_MAX_BRANCH];
+    bool head() const { return br[0].gsize == 0; }
 };
 
 // the device block of one call: PlanBase's, with the sampling buffers in `own` and one more Layout per SA stage behind the layers'
@@ -38,33 +48,50 @@ struct Plan : PlanBase {
     // uploaded
     float *x0 = nullptr, *feat0 = nullptr;
     uint32_t *seg[PCR_PN2_MAX_SA + 1], *cseg[PCR_PN2_MAX_SA];
-    // sampling
+    // sampling: bidx holds the branches' row blocks one after the other (block b = centres x nsample_b), bcnt n_branch x centres
     uint32_t *fps[PCR_PN2_MAX_SA], *bidx[PCR_PN2_MAX_SA], *bcnt[PCR_PN2_MAX_SA];
     float* cxyz[PCR_PN2_MAX_SA];
-    // per SA stage
-    float *xin[PCR_PN2_MAX_SA], *feat[PCR_PN2_MAX_SA];
-    uint32_t *row_pt[PCR_PN2_MAX_SA], *arg[PCR_PN2_MAX_SA];
+    // per (SA stage, branch), and per SA stage at the concatenated width
+    float *xin[PCR_PN2_MAX_SA][PCR_PN2_MAX_BRANCH], *feat[PCR_PN2_MAX_SA];
+    uint32_t *row_pt[PCR_PN2_MAX_SA][PCR_PN2_MAX_BRANCH], *arg[PCR_PN2_MAX_SA];
 };
 
 // false: too large
 bool make_plan(const pcr_pn2_trainer* t, size_t n_obj, size_t npts, Plan& P)
 {
-    const pcr_pn2_desc& d = t->desc;
+    const pcr_pn2_msg_desc& d = t->desc;
     const uint32_t ns = t->n_sampling, C0 = 3 + d.D0;
     if (n_obj > PN_MAX_ROWS || npts > PN_MAX_ROWS || (unsigned long long)n_obj * npts > PN_MAX_ROWS / C0) return false;
     P.N[0] = npts;
-    for (uint32_t l = 0; l < ns; l++) {
-        P.N[l + 1] = d.sa[l].npoint;
-        const unsigned long long rows = (unsigned long long)n_obj * d.sa[l].npoint * d.sa[l].nsample;
-        if (rows > PN_MAX_ROWS / PN_MAX_WIDTH) return false;
-        P.stages.push_back({ t->sa_first[l], d.sa[l].n_mlp, (uint32_t)rows, d.sa[l].nsample, (uint32_t)(n_obj * d.sa[l].npoint) });
+    for (uint32_t l = 0; l < d.n_sa; l++) {
+        const pcr_pn2_msg_sa_desc& sd = d.sa[l];
+        Stage st;
+        memset(&st, 0, sizeof(st));
+        if (!sd.group_all) P.N[l + 1] = sd.npoint;
+        const unsigned long long groups = sd.group_all ? n_obj : (unsigned long long)n_obj * sd.npoint;
+        if (groups > PN_MAX_ROWS) return false;
+        st.groups = (uint32_t)groups;
+        st.n_branch = sd.n_branch;
+        uint32_t off = 0;
+        for (uint32_t b = 0; b < sd.n_branch; b++) {
+            const uint32_t gsize = sd.group_all ? (uint32_t)P.N[l] : sd.branch[b].nsample;
+            const unsigned long long rows = (unsigned long long)st.groups * gsize;
+            unsigned long long widest = t->sa_in[l];             // the widest row of the branch, its input included
+            for (uint32_t i = 0; i < sd.branch[b].n_mlp; i++) widest = std::max<unsigned long long>(widest, sd.branch[b].widths[i]);
+            if (rows > (1ull << 21) || rows * widest > PN_MAX_ROWS) return false;      // 2^21 rows, and every buffer's cells within PN_MAX_ROWS
+            st.br[b] ={ t->sa_first[l][b], sd.branch[b].n_mlp, (uint32_t)rows, gsize, off };
+            off += sd.branch[b].widths[sd.branch[b].n_mlp - 1];
+        }
+        P.stages.push_back(st);
     }
-    if (d.sa[d.n_sa - 1].group_all) {
-        const unsigned long long rows = (unsigned long long)n_obj * P.N[ns];
-        if (rows > PN_MAX_ROWS / PN_MAX_WIDTH) return false;
-        P.stages.push_back({ t->sa_first[ns], d.sa[ns].n_mlp, (uint32_t)rows, (uint32_t)P.N[ns], (uint32_t)n_obj });
+    {
+        Stage st;
+        memset(&st, 0, sizeof(st));
+        st.groups = (uint32_t)n_obj;
+        st.n_branch = 1;
+        st.br[0] = { t->head_first, d.n_fc, (uint32_t)n_obj, 0u, 0u };
+        P.stages.push_back(st);
     }
-    P.stages.push_back({ t->head_first, d.n_fc, (uint32_t)n_obj, 0u, (uint32_t)n_obj });
     const size_t pts = n_obj * npts;
     size_t keep_bytes = 0;
     for (uint32_t i = 0; i + 1 < d.n_fc; i++) keep_bytes += n_obj * d.fc_widths[i];
@@ -76,29 +103,55 @@ bool make_plan(const pcr_pn2_trainer* t, size_t n_obj, size_t npts, Plan& P)
     for (uint32_t l = 0; l < ns; l++) P.up.add(&P.cseg[l], n_obj * P.N[l + 1]);
     for (uint32_t l = 0; l < ns; l++) {
         const size_t nq = n_obj * P.N[l + 1];
+        size_t row = 0;
+        for (uint32_t b = 0; b < d.sa[l].n_branch; b++) row += d.sa[l].branch[b].nsample;
         P.own.add(&P.fps[l], nq);
         P.own.add(&P.cxyz[l], 3 * nq);
-        P.own.add(&P.bidx[l], nq * d.sa[l].nsample);
-        P.own.add(&P.bcnt[l], nq);
+        P.own.add(&P.bidx[l], nq * row);
+        P.own.add(&P.bcnt[l], nq * d.sa[l].n_branch);
     }
     const size_t nl = t->layers.size();
     P.layers(nl, d.n_sa);
     P.dfeat_cells = 1;
     for (size_t s = 0; s < P.stages.size(); s++) {
         const Stage& st = P.stages[s];
-        const bool head = st.gsize == 0;
+        const bool head = st.head();
         if (!head) {
             Layout& L = P.per_layer[nl + s];
-            L.add(&P.xin[s], (size_t)st.M * t->sa_in[s]);
-            L.add(&P.row_pt[s], (size_t)st.M);
+            for (uint32_t b = 0; b < st.n_branch; b++) {
+                L.add(&P.xin[s][b], (size_t)st.br[b].M * t->sa_in[s]);
+                L.add(&P.row_pt[s][b], (size_t)st.br[b].M);
+            }
             L.add(&P.feat[s], (size_t)st.groups * t->sa_out[s]);
             L.add(&P.arg[s], (size_t)st.groups * t->sa_out[s]);
             P.dfeat_cells = std::max(P.dfeat_cells, (size_t)st.groups * t->sa_out[s]);
+            if (s > 0 && st.n_branch > 1) P.dacc_cells = std::max(P.dacc_cells, n_obj * P.N[s] * (t->sa_in[s] - 3));
         }
-        for (uint32_t i = st.first; i < st.first + st.count; i++) P.add_layer(i, st.M, t->layers[i], t->chunk_rows, head);
+        for (uint32_t b = 0; b < st.n_branch; b++)
+            for (uint32_t i = st.br[b].first; i < st.br[b].first + st.br[b].count; i++) P.add_layer(i, st.br[b].M, t->layers[i], t->chunk_rows, head);
     }
     P.finish(n_obj, t->layers.back().N, 1);
     return true;
+}
+
+// what both creates share: the layers of the superset descriptor, the group_all rule, the upload
+int create_from(pcr_ctx* ctx, const char* who, const pcr_pn2_msg_desc& md, const float* weights, size_t n_weights, const double* dropout_p, size_t n_dropout,
+                double bn_momentum, uint32_t chunk_rows, pcr_pn2_trainer** out)
+{
+    std::unique_ptr<pcr_pn2_trainer> t(new pcr_pn2_trainer());
+    t->desc = md;
+    Pn2Layers ly;
+    if (!pn2_layers(md, ly)) return fail(ctx, PCR_ERR_ARG, (std::string(who) + ": a descriptor outside the limits (see include/pcr.h)").c_str());
+    for (const LayerShape& s : ly.shapes) layer_push(*t, s);
+    for (uint32_t l = 0; l < md.n_sa; l++) {
+        for (uint32_t b = 0; b < md.sa[l].n_branch; b++) t->sa_first[l][b] = ly.first[l][b];
+        t->sa_in[l] = ly.sa_in[l];
+        t->sa_out[l] = ly.sa_out[l];
+    }
+    t->head_first = ly.head_first;
+    t->n_sampling = ly.n_sampling;
+    if (!md.sa[md.n_sa - 1].group_all) return fail(ctx, PCR_ERR_ARG, (std::string(who) + ": the last SA layer must be group_all").c_str());
+    return trainer_finish(ctx, who, std::move(t), nullptr, weights, n_weights, dropout_p, n_dropout, bn_momentum, chunk_rows, out);
 }
 
 }  // namespace
@@ -106,19 +159,25 @@ bool make_plan(const pcr_pn2_trainer* t, size_t n_obj, size_t npts, Plan& P)
 extern "C" int pcr_pn2_trainer_create(pcr_ctx* ctx, const pcr_pn2_desc* desc, const float* weights, size_t n_weights, double dropout_p, double bn_momentum,
                                       uint32_t chunk_rows, pcr_pn2_trainer** out)
 {
+    const char* who = "pcr_pn2_trainer_create";
     if (out) *out = nullptr;
-    if (!ctx || !desc || !weights || !out) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_trainer_create");
-    std::unique_ptr<pcr_pn2_trainer> t(new pcr_pn2_trainer());
-    t->desc = *desc;
+    if (!ctx || !desc || !weights || !out) return fail(ctx, PCR_ERR_ARG, who);
     pcr_pn2_msg_desc md;                     // the models' superset descriptor: the trainer's layers are the ones a model of the same descriptor has
-    Pn2Layers ly;
-    if (!pn2_msg_desc_of(*desc, md) || !pn2_layers(md, ly)) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_trainer_create: a descriptor outside the limits (see include/pcr.h)");
-    for (const LayerShape& s : ly.shapes) layer_push(*t, s);
-    for (uint32_t l = 0; l < desc->n_sa; l++) { t->sa_first[l] = ly.first[l][0]; t->sa_in[l] = ly.sa_in[l]; t->sa_out[l] = ly.sa_out[l]; }
-    t->head_first = ly.head_first;
-    t->n_sampling = ly.n_sampling;
-    if (!desc->sa[desc->n_sa - 1].group_all) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_trainer_create: the last SA layer must be group_all");
-    return trainer_finish(ctx, "pcr_pn2_trainer_create", std::move(t), nullptr, weights, n_weights, dropout_p, bn_momentum, chunk_rows, out);
+    if (!pn2_msg_desc_of(*desc, md)) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_trainer_create: a descriptor outside the limits (see include/pcr.h)");
+    const double ps[PCR_PN2_MAX_FC] = { dropout_p, dropout_p, dropout_p, dropout_p };      // every hidden layer's
+    return create_from(ctx, who, md, weights, n_weights, ps, PCR_PN2_MAX_FC, bn_momentum, chunk_rows, out);
+}
+
+extern "C" int pcr_pn2_msg_trainer_create(pcr_ctx* ctx, const pcr_pn2_msg_desc* desc, const float* weights, size_t n_weights, const double* dropout_p, size_t n_dropout,
+                                          double bn_momentum, uint32_t chunk_rows, pcr_pn2_trainer** out)
+{
+    const char* who = "pcr_pn2_msg_trainer_create";
+    if (out) *out = nullptr;
+    if (!ctx || !desc || !weights || !out) return fail(ctx, PCR_ERR_ARG, who);
+    if (desc->n_fc < 1 || desc->n_fc > PCR_PN2_MAX_FC) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_msg_trainer_create: a descriptor outside the limits (see include/pcr.h)");
+    if (n_dropout != desc->n_fc - 1) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_msg_trainer_create: n_dropout must be n_fc - 1, one p per hidden FC layer");
+    if (n_dropout && !dropout_p) return fail(ctx, PCR_ERR_ARG, "pcr_pn2_msg_trainer_create: dropout_p is NULL");
+    return create_from(ctx, who, *desc, weights, n_weights, dropout_p, n_dropout, bn_momentum, chunk_rows, out);
 }
 
 extern "C" int pcr_pn2_trainer_destroy(pcr_ctx* ctx, pcr_pn2_trainer* t)
@@ -146,6 +205,17 @@ extern "C" int pcr_pn2_trainer_info(const pcr_pn2_trainer* t, size_t n_obj, size
         if (!make_plan(t, n_obj, npts, P)) return PCR_ERR_ARG;
         info->device_bytes = P.total + 2 * t->n_weights * 4;
     }
+    return PCR_OK;
+}
+
+extern "C" int pcr_pn2_msg_trainer_info(const pcr_pn2_trainer* t, size_t n_obj, size_t npts, pcr_pn2_train_info* info, pcr_pn2_msg_desc* desc, double* dropout_p)
+{
+    if (!t || !info || t->kind != 0) return PCR_ERR_ARG;
+    const int rc = pcr_pn2_trainer_info(t, n_obj, npts, info);
+    if (rc) return rc;
+    if (desc) *desc = t->desc;
+    if (dropout_p)
+        for (uint32_t i = 0; i + 1 < PCR_PN2_MAX_FC; i++) dropout_p[i] = i + 1 < t->desc.n_fc ? (double)t->drop_p[i] : 0.0;
     return PCR_OK;
 }
 
@@ -191,7 +261,8 @@ extern "C" int pcr_pn2_train_grad_f32(pcr_ctx* ctx, pcr_pn2_trainer* t, const fl
     int rc = call_head(ctx, t, 0, who, nullptr, !objects || !target || !loss || !logp || !grad, target, n_obj, npts, P, [&]() -> const char* {
         if (!make_plan(t, n_obj, npts, P)) return ": too large";
         for (const Stage& st : P.stages)
-            if (st.M < 2) return ": a layer with one row (BatchNorm's batch statistics need two)";
+            for (uint32_t b = 0; b < st.n_branch; b++)
+                if (st.br[b].M < 2) return ": a layer with one row (BatchNorm's batch statistics need two)";
         st0.resize((size_t)t->n_sampling * n_obj);
         for (uint32_t l = 0; l < t->n_sampling; l++)
             for (size_t o = 0; o < n_obj; o++) {
@@ -207,7 +278,7 @@ extern "C" int pcr_pn2_train_grad_f32(pcr_ctx* ctx, pcr_pn2_trainer* t, const fl
         return nullptr;
     }, run);
     if (!run) return rc;
-    const pcr_pn2_desc& d = t->desc;
+    const pcr_pn2_msg_desc& d = t->desc;
     const uint32_t ns = t->n_sampling, D0 = d.D0, C0 = 3 + D0, n_class = t->layers.back().N;
     const size_t pts = n_obj * npts;
     {
@@ -220,9 +291,9 @@ extern "C" int pcr_pn2_train_grad_f32(pcr_ctx* ctx, pcr_pn2_trainer* t, const fl
             for (uint32_t c = 0; c < D0; c++) P.feat0[i * D0 + c] = r[3 + c];
         }
         size_t off = 0;
-        for (uint32_t i = 0; i + 1 < d.n_fc; i++) {              // the masks: the caller's bytes, or the rule
+        for (uint32_t i = 0; i + 1 < d.n_fc; i++) {              // the masks: the caller's bytes, or the rule with the layer's own p
             const size_t cells = n_obj * d.fc_widths[i];
-            for (size_t e = 0; e < cells; e++) P.keep[off + e] = keep ? (keep[off + e] ? 1 : 0) : keep_rule(seed, i, e, t->dropout_p);
+            for (size_t e = 0; e < cells; e++) P.keep[off + e] = keep ? (keep[off + e] ? 1 : 0) : keep_rule(seed, i, e, t->drop_p[i]);
             off += cells;
         }
         for (uint32_t l = 0; l <= ns; l++)
@@ -241,54 +312,66 @@ extern "C" int pcr_pn2_train_grad_f32(pcr_ctx* ctx, pcr_pn2_trainer* t, const fl
     std::vector<const uint8_t*> keep_of(t->layers.size(), nullptr);      // the mask of every head layer that has a dropout (fused behind its ReLU)
     for (size_t s = 0; s < P.stages.size() && R.rc == PCR_OK; s++) {
         const Stage& st = P.stages[s];
-        const bool head = st.gsize == 0;
-        const float* x = nullptr;
-        if (!head) {
-            const bool grouped = s < ns;
-            const float *qx = nullptr, *qy = nullptr, *qz = nullptr;
-            if (grouped) {
-                const pcr_pn2_sa_desc& sd = d.sa[s];
-                const size_t nq = n_obj * P.N[s + 1];
-                std::vector<FpsJob> jobs(n_obj);
-                for (size_t o = 0; o < n_obj; o++) jobs[o] = { (uint32_t)(o * P.N[s]), (uint32_t)P.N[s], st0[s * n_obj + o], (uint32_t)o };
-                R.rc = fps_device(ctx, cx, cy, cz, std::move(jobs), sd.npoint, PCR_FPS_F32, P.fps[s], &hold);
-                if (R.rc) break;
-                float *wx = P.cxyz[s], *wy = wx + nq, *wz = wy + nq;
-                {
-                    ProfScope ps(ctx, "pn2t_centres");
-                    hipLaunchKernelGGL(pn2t_centres_kernel, dim3(blocks_for(nq)), dim3(T_BLOCK), 0, ctx->stream, cx, cy, cz, P.fps[s], (uint32_t)P.N[s], sd.npoint, (uint32_t)nq,
-                                       wx, wy, wz);
-                }
-                R.rc = ball_query_device(ctx, cx, cy, cz, wx, wy, wz, P.seg[s], P.cseg[s], nq, sd.radius, sd.nsample, P.bidx[s], P.bcnt[s]);
-                if (R.rc) break;
-                qx = wx; qy = wy; qz = wz;
-            }
+        const bool head = st.head(), grouped = s < ns;
+        const float *qx = nullptr, *qy = nullptr, *qz = nullptr;
+        const uint32_t* bidx[PCR_PN2_MAX_BRANCH] = {};           // the branches' row blocks
+        if (grouped) {                                           // once per stage: FPS, the centres, every branch's ball in one walk
+            const pcr_pn2_msg_sa_desc& sd = d.sa[s];
+            const size_t nq = n_obj * P.N[s + 1];
+            std::vector<FpsJob> jobs(n_obj);
+            for (size_t o = 0; o < n_obj; o++) jobs[o] = { (uint32_t)(o * P.N[s]), (uint32_t)P.N[s], st0[s * n_obj + o], (uint32_t)o };
+            R.rc = fps_device(ctx, cx, cy, cz, std::move(jobs), sd.npoint, PCR_FPS_F32, P.fps[s], &hold);
+            if (R.rc) break;
+            float *wx = P.cxyz[s], *wy = wx + nq, *wz = wy + nq;
             {
+                ProfScope ps(ctx, "pn2t_centres");
+                hipLaunchKernelGGL(pn2t_centres_kernel, dim3(blocks_for(nq)), dim3(T_BLOCK), 0, ctx->stream, cx, cy, cz, P.fps[s], (uint32_t)P.N[s], sd.npoint, (uint32_t)nq,
+                                   wx, wy, wz);
+            }
+            double radii[PCR_PN2_MAX_BRANCH];
+            uint32_t nsamples[PCR_PN2_MAX_BRANCH], *ib[PCR_PN2_MAX_BRANCH], *cb[PCR_PN2_MAX_BRANCH];
+            size_t at = 0;
+            for (uint32_t b = 0; b < sd.n_branch; b++) {
+                radii[b] = sd.branch[b].radius; nsamples[b] = sd.branch[b].nsample;
+                ib[b] = P.bidx[s] + at; cb[b] = P.bcnt[s] + (size_t)b * nq;
+                bidx[b] = ib[b];
+                at += nq * nsamples[b];
+            }
+            if (sd.n_branch == 1) R.rc = ball_query_device(ctx, cx, cy, cz, wx, wy, wz, P.seg[s], P.cseg[s], nq, radii[0], nsamples[0], ib[0], cb[0]);
+            else R.rc = ball_query_multi_device(ctx, cx, cy, cz, wx, wy, wz, P.seg[s], P.cseg[s], nq, sd.n_branch, radii, nsamples, ib, cb);
+            if (R.rc) break;
+            qx = wx; qy = wy; qz = wz;
+        }
+        for (uint32_t b = 0; b < st.n_branch && R.rc == PCR_OK; b++) {
+            const Branch& br = st.br[b];
+            const float* x = feat;
+            if (!head) {
                 ProfScope ps(ctx, "pn2t_gather");
-                hipLaunchKernelGGL(pn2t_gather_kernel, dim3(blocks_for(st.M)), dim3(T_BLOCK), 0, ctx->stream, cx, cy, cz, qx, qy, qz, feat, grouped ? P.bidx[s] : nullptr, st.M,
-                                   grouped ? d.sa[s].nsample : 1u, grouped ? d.sa[s].npoint : 1u, (uint32_t)P.N[s], D, P.xin[s], P.row_pt[s]);
+                hipLaunchKernelGGL(pn2t_gather_kernel, dim3(blocks_for(br.M)), dim3(T_BLOCK), 0, ctx->stream, cx, cy, cz, qx, qy, qz, feat, bidx[b], br.M, grouped ? br.gsize : 1u,
+                                   grouped ? d.sa[s].npoint : 1u, (uint32_t)P.N[s], D, d.sa[s].xyz_last, P.xin[s][b], P.row_pt[s][b]);
+                x = P.xin[s][b];
             }
-            x = P.xin[s];
-            if (grouped) { cx = qx; cy = qy; cz = qz; }
-        } else {
-            x = feat;
-        }
-        for (uint32_t i = st.first; i < st.first + st.count; i++) {
-            const TLayer& L = t->layers[i];
-            if (head && L.bn) {
-                keep_of[i] = P.keep + keep_off;
-                keep_off += (size_t)st.M * L.N;
+            for (uint32_t i = br.first; i < br.first + br.count; i++) {
+                const TLayer& L = t->layers[i];
+                if (head && L.bn) {
+                    keep_of[i] = P.keep + keep_off;
+                    keep_off += (size_t)br.M * L.N;
+                }
+                R.fwd(i, x, br.M, true, keep_of[i] ? Drop::fused : Drop::none, keep_of[i]);
+                x = head ? P.a[i] : P.y[i];
             }
-            R.fwd(i, x, st.M, true, keep_of[i] ? Drop::fused : Drop::none, keep_of[i]);
-            x = head ? P.a[i] : P.y[i];
+            if (R.rc) break;
+            if (!head) {                                         // the branch's columns of the stage's row
+                const uint32_t last = br.first + br.count - 1;
+                ProfScope ps(ctx, "pn2t_max");
+                hipLaunchKernelGGL(pn2t_max_kernel, dim3(blocks_for((size_t)st.groups * t->layers[last].N)), dim3(T_BLOCK), 0, ctx->stream, P.y[last], st.groups, br.gsize,
+                                   t->layers[last].N, t->sa_out[s], br.off, P.feat[s], P.arg[s]);
+            }
         }
-        if (R.rc) break;
         if (!head) {
-            const uint32_t last = st.first + st.count - 1, C = t->layers[last].N;
-            ProfScope ps(ctx, "pn2t_max");
-            hipLaunchKernelGGL(pn2t_max_kernel, dim3(blocks_for((size_t)st.groups * C)), dim3(T_BLOCK), 0, ctx->stream, P.y[last], st.groups, st.gsize, C, P.feat[s], P.arg[s]);
             feat = P.feat[s];
-            D = C;
+            D = t->sa_out[s];
+            if (grouped) { cx = qx; cy = qy; cz = qz; }
         }
     }
     // ---- the loss, then backward
@@ -298,18 +381,23 @@ extern "C" int pcr_pn2_train_grad_f32(pcr_ctx* ctx, pcr_pn2_trainer* t, const fl
     }
     for (size_t s = P.stages.size(); s-- > 0 && R.rc == PCR_OK;) {
         const Stage& st = P.stages[s];
-        const bool head = st.gsize == 0;
-        if (!head)      // the gradient of the stage's output -> its last layer's rows.  Below the head, the head's dx IS the gradient of the global feature
-            R.max_back(s + 2 == P.stages.size() ? R.cur : P.dfeat, P.arg[s], st.M, st.gsize, t->layers[st.first + st.count - 1].N);
-        for (uint32_t i = st.first + st.count; i-- > st.first;) {
-            const float* x = i > st.first ? (head ? P.a[i - 1] : P.y[i - 1]) : (head ? P.feat[s - 1] : P.xin[s]);
-            R.bwd(i, x, st.M, true, i != 0, keep_of[i] ? Drop::fused : Drop::none, keep_of[i]);      // layer 0: the input points take no gradient
-        }
-        if (R.rc == PCR_OK && !head && s > 0) {                  // the feature columns of dx back to the points of the stage before
-            const uint32_t Dp = t->sa_in[s] - 3;
-            const uint32_t points = (uint32_t)(n_obj * P.N[s]);
-            ProfScope ps(ctx, "pn2t_gather_back");
-            hipLaunchKernelGGL(pn2t_gather_back_kernel, dim3(points), dim3(T_BLOCK), 0, ctx->stream, R.cur, P.row_pt[s], points, (uint32_t)P.N[s], st.M / (uint32_t)n_obj, Dp, P.dfeat);
+        const bool head = st.head();
+        for (uint32_t b = 0; b < st.n_branch && R.rc == PCR_OK; b++) {
+            const Branch& br = st.br[b];
+            if (!head)      // the branch's columns of the gradient of the stage's row -> its last layer's rows.  Below the head, the head's dx IS that gradient
+                R.max_back(s + 2 == P.stages.size() ? R.cur : P.dfeat, P.arg[s], br.M, br.gsize, t->layers[br.first + br.count - 1].N, t->sa_out[s], br.off);
+            for (uint32_t i = br.first + br.count; i-- > br.first;) {
+                const float* x = i > br.first ? (head ? P.a[i - 1] : P.y[i - 1]) : (head ? P.feat[s - 1] : P.xin[s][b]);
+                R.bwd(i, x, br.M, true, head || s > 0 || i > br.first, keep_of[i] ? Drop::fused : Drop::none, keep_of[i]);      // the input points take no gradient
+            }
+            if (R.rc == PCR_OK && !head && s > 0) {              // the feature columns of dx back to the points of the stage before: this branch's part of the sum.
+                                                                 // P.dfeat is free once the last branch has scattered its maxima, and only the last branch writes it
+                const uint32_t Dp = t->sa_in[s] - 3;
+                const uint32_t points = (uint32_t)(n_obj * P.N[s]);
+                ProfScope ps(ctx, "pn2t_gather_back");
+                hipLaunchKernelGGL(pn2t_gather_back_kernel, dim3(points), dim3(T_BLOCK), 0, ctx->stream, R.cur, P.row_pt[s][b], points, (uint32_t)P.N[s], br.M / (uint32_t)n_obj,
+                                   Dp, d.sa[s].xyz_last ? 0u : 3u, b > 0 ? P.dacc : (const double*)nullptr, b + 1 < st.n_branch ? P.dacc : (double*)nullptr, P.dfeat);
+            }
         }
     }
     return call_tail(ctx, t, who, R.rc, P, n_obj, logp, loss, 1, grad);      // `hold` lives until its wait is over

@@ -325,7 +325,8 @@ struct ClsRun : LayerRun {
         const uint32_t C = t->layers[first + 2].N;
         {
             ProfScope ps(ctx, "pn2t_max");
-            hipLaunchKernelGGL(pn2t_max_kernel, dim3(blocks_for((size_t)P.n_obj * C)), dim3(T_BLOCK), 0, ctx->stream, P.y[first + 2], P.n_obj, P.npts, C, feat, arg);
+            hipLaunchKernelGGL(pn2t_max_kernel, dim3(blocks_for((size_t)P.n_obj * C)), dim3(T_BLOCK), 0, ctx->stream, P.y[first + 2], P.n_obj, P.npts, C, C, 0u, feat,
+                               arg);
         }
         fwd(first + 3, feat, P.n_obj, true);
         fwd(first + 4, P.y[first + 3], P.n_obj, true);
@@ -404,8 +405,9 @@ extern "C" int pcr_pn1_trainer_create(pcr_ctx* ctx, const pcr_pn1_desc* desc, co
     for (const LayerShape& s : ly.shapes) layer_push(*t, s);
     t->stn_first = ly.stn_first; t->enc_first = ly.enc_first; t->fstn_first = ly.fstn_first; t->head_first = ly.head_first;
     t->reg_scale = reg_scale;
-    return trainer_finish(ctx, "pcr_pn1_trainer_create", std::move(t), std::isfinite(reg_scale) ? nullptr : ": reg_scale must be finite", weights, n_weights, dropout_p,
-                          bn_momentum, chunk_rows, out);
+    const double ps[PCR_PN2_MAX_FC] = { dropout_p, dropout_p, dropout_p, dropout_p };      // one p: the dropped layer's, whichever it is
+    return trainer_finish(ctx, "pcr_pn1_trainer_create", std::move(t), std::isfinite(reg_scale) ? nullptr : ": reg_scale must be finite", weights, n_weights, ps,
+                          PCR_PN2_MAX_FC, bn_momentum, chunk_rows, out);
 }
 
 extern "C" int pcr_pointnet_train_grad_f32(pcr_ctx* ctx, pcr_pn2_trainer* t, const float* objects, size_t n_obj, size_t npts, const int32_t* target, uint64_t seed,
@@ -425,7 +427,7 @@ extern "C" int pcr_pointnet_train_grad_f32(pcr_ctx* ctx, pcr_pn2_trainer* t, con
         if (!(fabsf(objects[i]) <= FLT_MAX)) return fail(ctx, PCR_ERR_ARG, (std::string(who) + ": a non-finite coordinate or feature").c_str());
         P.obj[i] = objects[i];
     }
-    for (size_t e = 0; e < n_obj * kw; e++) P.keep[e] = keep ? (keep[e] ? 1 : 0) : keep_rule(seed, d.n_fc - 2u, e, t->dropout_p);      // the mask: the caller's bytes, or the rule
+    for (size_t e = 0; e < n_obj * kw; e++) P.keep[e] = keep ? (keep[e] ? 1 : 0) : keep_rule(seed, d.n_fc - 2u, e, t->drop_p[d.n_fc - 2u]);      // the mask: the caller's bytes, or the rule
     rc = call_upload(ctx, t, P);
     if (rc) return rc;
     ClsRun R(ctx, t, P);

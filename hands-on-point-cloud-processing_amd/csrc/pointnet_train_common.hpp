@@ -1,11 +1,11 @@
-// pointnet_train_common.hpp — what the two training passes share (pointnet2_train.hip: PointNet++ SSG; pointnet_train.hip: the vanilla PointNet).
+// pointnet_train_common.hpp — what the two training passes share (pointnet2_train.hip: PointNet++, SSG and MSG; pointnet_train.hip: the vanilla PointNet).
 // Kernels: the strided MFMA product, the chunked f64 statistics, BatchNorm / ReLU forward and backward, the in-place dropout, the max with its argmax, the loss.
 // Every kernel here keeps its profile name in both passes.
 // Host: the trainer handle; layer_push (the weight layout of a layer); trainer_finish (what both creates do behind their shape check); trainer_info_common;
 // keep_rule (the dropout mask by rule); PlanBase (the shared part of a call's device block); call_head / call_upload / call_tail (the checks, the staging and
 // the downloads of a call); LayerRun (one layer forward, one layer backward, the bias gradient, the max's scatter back: the only place that launches them).
 // What a pass keeps to itself: its plan's own buffers, and what happens between the layers (its layers, limits and weight count: pointnet_layers.hpp).
-// The contracts are above pcr_pn2_trainer_create and pcr_pn1_trainer_create in include/pcr.h.
+// The contracts are above pcr_pn2_trainer_create, pcr_pn2_msg_trainer_create and pcr_pn1_trainer_create in include/pcr.h.
 #pragma once
 #include "pcr_internal.hpp"
 #include "pointnet_layers.hpp"
@@ -103,16 +103,18 @@ __global__ __launch_bounds__(T_BLOCK) void pn2t_gemm_kernel(const GemmArgs g)
         }
 }
 
-// the rows of an SA layer.  grouped: row r = (centre q = r / nsample, member k = r % nsample) reads point idx[q][k] of its object;
-// group_all (idx == NULL): row r is point r.  x[r] = (xyz - centre | features), row_pt[r] = the point (T_NONE: a member outside its object, a row of zeros)
+// the rows of one branch of an SA layer.  grouped: row r = (centre q = r / nsample, member k = r % nsample) reads point idx[q][k] of its object;
+// group_all (idx == NULL): row r is point r.  x[r] = (xyz - centre | features), or (features | xyz - centre) with xyz_last; row_pt[r] = the point
+// (T_NONE: a member outside its object, a row of zeros)
 __global__ __launch_bounds__(T_BLOCK) void pn2t_gather_kernel(const float* __restrict__ px, const float* __restrict__ py, const float* __restrict__ pz,
                                                               const float* __restrict__ qx, const float* __restrict__ qy, const float* __restrict__ qz,
                                                               const float* __restrict__ feat, const uint32_t* __restrict__ idx, uint32_t rows, uint32_t nsample,
-                                                              uint32_t npoint, uint32_t n_prev, uint32_t D, float* __restrict__ x, uint32_t* __restrict__ row_pt)
+                                                              uint32_t npoint, uint32_t n_prev, uint32_t D, uint32_t xyz_last, float* __restrict__ x,
+                                                              uint32_t* __restrict__ row_pt)
 {
     const uint32_t r = blockIdx.x * T_BLOCK + threadIdx.x;
     if (r >= rows) return;
-    const uint32_t K = 3 + D;
+    const uint32_t K = 3 + D, cx0 = xyz_last ? D : 0u, cf0 = xyz_last ? 0u : 3u;      // the first xyz column, the first feature column
     float* xr = x + (size_t)r * K;
     uint32_t p = r;
     float cx = 0.0f, cy = 0.0f, cz = 0.0f;
@@ -129,10 +131,10 @@ __global__ __launch_bounds__(T_BLOCK) void pn2t_gather_kernel(const float* __res
         sub = true;
     }
     row_pt[r] = p;
-    xr[0] = sub ? px[p] - cx : px[p];
-    xr[1] = sub ? py[p] - cy : py[p];
-    xr[2] = sub ? pz[p] - cz : pz[p];
-    for (uint32_t c = 0; c < D; c++) xr[3 + c] = feat[(size_t)p * D + c];
+    xr[cx0] = sub ? px[p] - cx : px[p];
+    xr[cx0 + 1] = sub ? py[p] - cy : py[p];
+    xr[cx0 + 2] = sub ? pz[p] - cz : pz[p];
+    for (uint32_t c = 0; c < D; c++) xr[cf0 + c] = feat[(size_t)p * D + c];
 }
 
 __global__ __launch_bounds__(T_BLOCK) void pn2t_centres_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ z,
@@ -204,9 +206,10 @@ __global__ __launch_bounds__(T_BLOCK) void pn2t_bn_relu_kernel(const float* __re
     if (a) a[e] = (!keep || keep[e]) ? v * s : 0.0f;
 }
 
-// feat[g][c] = the max over the gsize rows of group g; arg[g][c] = the lowest position that holds it, T_NONE where the max is 0
-__global__ __launch_bounds__(T_BLOCK) void pn2t_max_kernel(const float* __restrict__ y, uint32_t groups, uint32_t gsize, uint32_t N, float* __restrict__ feat,
-                                                           uint32_t* __restrict__ arg)
+// feat[g][off + c] = the max over the gsize rows of group g; arg[g][off + c] = the lowest position that holds it, T_NONE where the max is 0.
+// feat and arg have rows of `stride` cells: a branch writes its own columns [off, off + N) of the layer's concatenated row
+__global__ __launch_bounds__(T_BLOCK) void pn2t_max_kernel(const float* __restrict__ y, uint32_t groups, uint32_t gsize, uint32_t N, uint32_t stride, uint32_t off,
+                                                           float* __restrict__ feat, uint32_t* __restrict__ arg)
 {
     const size_t e = (size_t)blockIdx.x * T_BLOCK + threadIdx.x;
     if (e >= (size_t)groups * N) return;
@@ -218,12 +221,14 @@ __global__ __launch_bounds__(T_BLOCK) void pn2t_max_kernel(const float* __restri
         const float v = p[(size_t)k * N];
         if (v > m) { m = v; best = k; }
     }
-    feat[e] = m;
-    arg[e] = m > 0.0f ? best : T_NONE;
+    const size_t o = (size_t)g * stride + off + c;
+    feat[o] = m;
+    arg[o] = m > 0.0f ? best : T_NONE;
 }
 
+// dy[r][c] = dfeat[g][off + c] where row r is position arg[g][off + c] of its group g, +0 elsewhere (dfeat and arg: rows of `stride` cells)
 __global__ __launch_bounds__(T_BLOCK) void pn2t_max_back_kernel(const float* __restrict__ dfeat, const uint32_t* __restrict__ arg, size_t total, uint32_t gsize, uint32_t N,
-                                                                float* __restrict__ dy)
+                                                                uint32_t stride, uint32_t off, float* __restrict__ dy)
 {
     const size_t e = (size_t)blockIdx.x * T_BLOCK + threadIdx.x;
     if (e >= total) return;
@@ -231,7 +236,8 @@ __global__ __launch_bounds__(T_BLOCK) void pn2t_max_back_kernel(const float* __r
     const uint32_t c = (uint32_t)(e - r * N);
     const size_t g = r / gsize;
     const uint32_t k = (uint32_t)(r - g * gsize);
-    dy[e] = arg[g * N + c] == k ? dfeat[g * N + c] : 0.0f;
+    const size_t o = g * stride + off + c;
+    dy[e] = arg[o] == k ? dfeat[o] : 0.0f;
 }
 
 // the gradient that reaches BN's output at element e: dropout (the same mask and s), then ReLU (passes where y > 0; RELU == false: everywhere)
@@ -305,19 +311,46 @@ __global__ __launch_bounds__(T_BLOCK) void pn2t_dw_reduce_kernel(const float* __
     dw[e] = s;
 }
 
-// dfeat[p][c] <- the f64 sum, rows ascending, of dx[r][3 + c] over the rows r of p's object that read point p; rounded once
+// one branch's part of the f64 sum per (point p, channel c), rows ascending, of dx[r][col0 + c] over the rows r of p's object that read point p (col0: the
+// first feature column, 3 or, with xyz_last, 0).  The sum starts at +0 (acc_in == NULL: the first branch) or goes on from acc_in[p][c]; it is handed on in
+// acc_out[p][c], or (acc_out == NULL: the last branch) rounded once into dfeat[p][c].  Branches ascending, one launch each: one chain over all the rows.
+// One workgroup per point.  Every wave walks row_pt 64 rows at a time (one coalesced load, one ballot) and takes the matching rows in ascending order,
+// so a thread's sums are chains over ascending rows; a thread owns channels threadIdx.x + 256 j, at most four of them (D <= PN_MAX_WIDTH - 3)
 __global__ __launch_bounds__(T_BLOCK) void pn2t_gather_back_kernel(const float* __restrict__ dx, const uint32_t* __restrict__ row_pt, uint32_t points, uint32_t n_prev,
-                                                                   uint32_t rows_per_obj, uint32_t D, float* __restrict__ dfeat)
+                                                                   uint32_t rows_per_obj, uint32_t D, uint32_t col0, const double* acc_in, double* acc_out,
+                                                                   float* __restrict__ dfeat)
 {
-    const uint32_t p = blockIdx.x;                              // one workgroup per point: row_pt is read uniformly
+    constexpr int CH = (PN_MAX_WIDTH + T_BLOCK - 1) / T_BLOCK;
+    const uint32_t p = blockIdx.x;
     if (p >= points) return;
-    const uint32_t o = p / n_prev, K = 3 + D;
+    const uint32_t o = p / n_prev, K = 3 + D, lane = threadIdx.x & 63;
     const size_t r0 = (size_t)o * rows_per_obj;
-    for (uint32_t c = threadIdx.x; c < D; c += T_BLOCK) {
-        double s = 0.0;
-        for (uint32_t k = 0; k < rows_per_obj; k++)
-            if (row_pt[r0 + k] == p) s = s + (double)dx[(r0 + k) * K + 3 + c];
-        dfeat[(size_t)p * D + c] = (float)s;
+    double s[CH];
+#pragma unroll
+    for (int j = 0; j < CH; j++) {
+        const uint32_t c = threadIdx.x + (uint32_t)j * T_BLOCK;
+        s[j] = (acc_in && c < D) ? acc_in[(size_t)p * D + c] : 0.0;
+    }
+    for (uint32_t k0 = 0; k0 < rows_per_obj; k0 += 64) {         // wave-uniform trip count; the kernel has no barrier
+        const uint32_t k = k0 + lane;
+        unsigned long long m = __ballot(k < rows_per_obj && row_pt[r0 + k] == p);
+        while (m) {                                              // the matching rows of these 64, ascending
+            const uint32_t bit = (uint32_t)__ffsll((long long)m) - 1u;
+            m &= m - 1;
+            const float* row = dx + (r0 + k0 + bit) * K + col0;
+#pragma unroll
+            for (int j = 0; j < CH; j++) {
+                const uint32_t c = threadIdx.x + (uint32_t)j * T_BLOCK;
+                if (c < D) s[j] = s[j] + (double)row[c];
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < CH; j++) {
+        const uint32_t c = threadIdx.x + (uint32_t)j * T_BLOCK;
+        if (c >= D) continue;
+        if (acc_out) acc_out[(size_t)p * D + c] = s[j];
+        else dfeat[(size_t)p * D + c] = (float)s[j];
     }
 }
 
@@ -360,17 +393,17 @@ inline unsigned blocks_for(size_t n) { return (unsigned)((n + T_BLOCK - 1) / T_B
 
 }  // namespace
 
-// the handle of both trainers.  kind 0: pcr_pn2_trainer_create (desc, sa_*, head_first, n_sampling); kind 1: pcr_pn1_trainer_create (desc1, the
-// first layer of its five parts, reg_scale; desc.bn_eps mirrors desc1.bn_eps)
+// the handle of every trainer.  kind 0: pcr_pn2_trainer_create and pcr_pn2_msg_trainer_create (desc: the superset descriptor; sa_*, head_first, n_sampling);
+// kind 1: pcr_pn1_trainer_create (desc1, the first layer of its five parts, reg_scale; desc.bn_eps mirrors desc1.bn_eps)
 struct pcr_pn2_trainer {
-    pcr_pn2_desc desc;
+    pcr_pn2_msg_desc desc;
     int device = 0;
     std::vector<TLayer> layers;          // weight order
-    uint32_t sa_first[PCR_PN2_MAX_SA];   // the first layer of every SA stage
+    uint32_t sa_first[PCR_PN2_MAX_SA][PCR_PN2_MAX_BRANCH];      // the first layer of every (SA stage, branch)
     uint32_t sa_in[PCR_PN2_MAX_SA], sa_out[PCR_PN2_MAX_SA];
     uint32_t head_first = 0, n_sampling = 0;
     uint64_t n_weights = 0;
-    float dropout_p = 0.0f, dropout_s = 1.0f;
+    float drop_p[PCR_PN2_MAX_FC] = {}, drop_s[PCR_PN2_MAX_FC] = { 1.0f, 1.0f, 1.0f, 1.0f };      // per head layer (layer index - head_first): p and f32(1 / (1 - p))
     double momentum = 0.1;
     uint32_t chunk_rows = T_DEFAULT_CHUNK;
     float* w_dev = nullptr;              // the flat weight array, running statistics included
@@ -414,18 +447,21 @@ inline void layer_push(pcr_pn2_trainer& t, const LayerShape& s)
 }
 
 // what both creates do once the layers are known: the parameter checks, the two device arrays, the upload.  Every message starts with the caller's name.
-// own_bad: the caller's own finding or NULL; it ranks behind bn_momentum
-inline int trainer_finish(pcr_ctx* ctx, const char* who, std::unique_ptr<pcr_pn2_trainer> t, const char* own_bad, const float* weights, size_t n_weights, double dropout_p,
-                          double bn_momentum, uint32_t chunk_rows, pcr_pn2_trainer** out)
+// own_bad: the caller's own finding or NULL; it ranks behind bn_momentum.  dropout_p: n_dropout <= PCR_PN2_MAX_FC values, head layer by head layer
+inline int trainer_finish(pcr_ctx* ctx, const char* who, std::unique_ptr<pcr_pn2_trainer> t, const char* own_bad, const float* weights, size_t n_weights,
+                          const double* dropout_p, size_t n_dropout, double bn_momentum, uint32_t chunk_rows, pcr_pn2_trainer** out)
 {
     auto bad = [&](const char* what) { return fail(ctx, PCR_ERR_ARG, (std::string(who) + what).c_str()); };
-    if (!(dropout_p >= 0.0 && dropout_p < 1.0)) return bad(": dropout_p must lie in [0, 1)");
+    for (size_t i = 0; i < n_dropout; i++)
+        if (!(dropout_p[i] >= 0.0 && dropout_p[i] < 1.0)) return bad(": dropout_p must lie in [0, 1)");
     if (!(bn_momentum >= 0.0 && bn_momentum <= 1.0)) return bad(": bn_momentum must lie in [0, 1]");
     if (own_bad) return bad(own_bad);
     if (n_weights != t->n_weights) return bad(": n_weights is not the model's count");
     if (const char* what = weights_ok(t.get(), weights)) return bad(what);
-    t->dropout_p = (float)dropout_p;
-    t->dropout_s = (float)(1.0 / (1.0 - dropout_p));
+    for (size_t i = 0; i < n_dropout; i++) {
+        t->drop_p[i] = (float)dropout_p[i];
+        t->drop_s[i] = (float)(1.0 / (1.0 - dropout_p[i]));
+    }
     t->momentum = bn_momentum;
     t->chunk_rows = chunk_rows ? chunk_rows : T_DEFAULT_CHUNK;
     t->device = ctx->device;
@@ -450,7 +486,7 @@ inline void trainer_info_common(const pcr_pn2_trainer* t, pcr_pn2_train_info* in
     info->n_weights = t->n_weights;
     info->chunk_rows = t->chunk_rows;
     info->n_class = t->layers.back().N;
-    info->dropout_p = (double)t->dropout_p;
+    info->dropout_p = (double)t->drop_p[0];      // the first hidden layer's
     info->bn_momentum = t->momentum;
 }
 
@@ -484,8 +520,9 @@ struct PlanBase {
     std::vector<double*> stat;       // 5 N doubles: mu, var, rstd, mean_g, mean_gx
     // shared
     float *dyA = nullptr, *dyB = nullptr, *dfeat = nullptr, *dw_part = nullptr, *logp = nullptr;
-    double *part = nullptr, *loss = nullptr;
-    size_t dy_cells = 1, part_cells = 1, dw_cells = 1, dfeat_cells = 0;      // the running maxima; dfeat is the SSG pass's (no cells: no room)
+    double *part = nullptr, *loss = nullptr, *dacc = nullptr;
+    size_t dy_cells = 1, part_cells = 1, dw_cells = 1, dfeat_cells = 0, dacc_cells = 0;      // the running maxima; dfeat is the PointNet++ pass's, dacc (the f64 sum
+                                                                                             // that travels from branch to branch) its multi-branch layers' (no cells: no room)
     Layout up, own, work;
     std::vector<Layout> per_layer;
     size_t total = 0;
@@ -517,6 +554,7 @@ struct PlanBase {
         work.add(&part, part_cells);
         work.add(&logp, n_obj * n_class);
         work.add(&loss, n_loss);
+        work.add(&dacc, dacc_cells);
         total = up.bytes() + own.bytes() + work.bytes();
         for (const Layout& L : per_layer) total += L.bytes();
     }
@@ -542,7 +580,7 @@ int call_head(pcr_ctx* ctx, const pcr_pn2_trainer* t, int kind, const char* who,
     if (!ctx || !t) return fail(ctx, PCR_ERR_ARG, who);
     if (t->kind != kind)
         return bad(kind == 0 ? ": the trainer was made by pcr_pn1_trainer_create (use pcr_pointnet_train_grad_f32)"
-                             : ": the trainer was made by pcr_pn2_trainer_create (use pcr_pn2_train_grad_f32)");
+                             : ": the trainer was made by pcr_pn2_trainer_create or pcr_pn2_msg_trainer_create (use pcr_pn2_train_grad_f32)");
     if (t->device != ctx->device) return bad(": the trainer lives on another device");
     if (npts < 1) return bad(": npts must be >= 1");
     if (own_bad) return bad(own_bad);
@@ -637,10 +675,16 @@ struct LayerRun {
 
     uint32_t chunks_of(uint32_t M) const { return (M + chunk - 1) / chunk; }
 
-    void dropout(float* v, const uint8_t* keep, size_t cells)
+    // the dropout scale of layer i: a head layer's own, 1 where there is no dropout
+    float scale_of(uint32_t i, Drop drop) const
+    {
+        return drop != Drop::none && i >= t->head_first && i - t->head_first < PCR_PN2_MAX_FC ? t->drop_s[i - t->head_first] : 1.0f;
+    }
+
+    void dropout(float* v, const uint8_t* keep, float s, size_t cells)
     {
         ProfScope ps(ctx, "pn1t_dropout");
-        hipLaunchKernelGGL(pn1t_dropout_kernel, dim3(blocks_for(cells)), dim3(T_BLOCK), 0, ctx->stream, v, keep, t->dropout_s, cells);
+        hipLaunchKernelGGL(pn1t_dropout_kernel, dim3(blocks_for(cells)), dim3(T_BLOCK), 0, ctx->stream, v, keep, s, cells);
     }
 
     // z = x W^T + b (-> the pre_bn dropout) -> the statistics -> y = BN(z) with or without the ReLU (-> a, the fused dropout)
@@ -655,7 +699,7 @@ struct LayerRun {
         rc = product(ctx, prof_fwd, g, who);
         if (rc) return;
         const size_t cells = (size_t)M * L.N;
-        if (drop == Drop::pre_bn) dropout(P.z[i], keep, cells);
+        if (drop == Drop::pre_bn) dropout(P.z[i], keep, scale_of(i, drop), cells);
         if (!L.bn) return;
         const uint32_t chunks = chunks_of(M);
         double *mu = P.stat[i], *var = mu + L.N, *rstd = var + L.N;
@@ -671,7 +715,7 @@ struct LayerRun {
         const bool fused = drop == Drop::fused;
         ProfScope ps(ctx, "pn2t_bn_relu");
         hipLaunchKernelGGL(bn_kernels(relu).bn_relu, dim3(blocks_for(cells)), dim3(T_BLOCK), 0, ctx->stream, P.z[i], cells, L.N, mu, rstd, W + L.gamma, W + L.beta, P.y[i],
-                           fused ? keep : (const uint8_t*)nullptr, fused ? t->dropout_s : 1.0f, fused ? P.a[i] : (float*)nullptr);
+                           fused ? keep : (const uint8_t*)nullptr, fused ? scale_of(i, drop) : 1.0f, fused ? P.a[i] : (float*)nullptr);
     }
 
     // the column sums of cur -> the bias gradient
@@ -695,14 +739,14 @@ struct LayerRun {
         if (L.bn) {
             double *mu = P.stat[i], *rstd = mu + 2 * (size_t)L.N, *mg = mu + 3 * (size_t)L.N, *mgx = mu + 4 * (size_t)L.N;
             const uint8_t* fk = drop == Drop::fused ? keep : nullptr;
-            const float s = fk ? t->dropout_s : 1.0f;
+            const float s = fk ? scale_of(i, drop) : 1.0f;
             const BnKernels k = bn_kernels(relu);
             ProfScope ps(ctx, "pn2t_bn_back");
             hipLaunchKernelGGL(k.part, dim3(blocks_for((size_t)chunks * L.N)), dim3(T_BLOCK), 0, ctx->stream, cur, P.y[i], P.z[i], fk, s, M, L.N, chunk, chunks, mu, rstd, P.part);
             hipLaunchKernelGGL(pn2t_bnb_fin_kernel, dim3(blocks_for(L.N)), dim3(T_BLOCK), 0, ctx->stream, P.part, chunks, L.N, M, G + L.gamma, G + L.beta, mg, mgx);
             hipLaunchKernelGGL(k.dz, dim3(blocks_for(cells)), dim3(T_BLOCK), 0, ctx->stream, cur, P.y[i], P.z[i], fk, s, cells, L.N, mu, rstd, W + L.gamma, mg, mgx);
         }
-        if (drop == Drop::pre_bn) dropout(cur, keep, cells);
+        if (drop == Drop::pre_bn) dropout(cur, keep, scale_of(i, drop), cells);
         if (!L.bn || drop == Drop::pre_bn) bias_grad(L, M);      // the biases the contract gives a gradient: no BatchNorm behind it, or a dropout in between
         {                                                        // dW[n][k] = sum_r dz[r][n] x[r][k]
             GemmArgs g;
@@ -723,14 +767,16 @@ struct LayerRun {
         if (rc == PCR_OK) std::swap(cur, nxt);
     }
 
-    // the gradient dfeat of the maxima of M rows in groups of gsize -> cur, the gradient of the rows.  dfeat may be cur: then the rows go to nxt and the two swap
-    void max_back(const float* dfeat, const uint32_t* arg, uint32_t M, uint32_t gsize, uint32_t C)
+    // the gradient dfeat of the maxima of M rows in groups of gsize -> cur, the gradient of the rows.  dfeat may be cur: then the rows go to nxt and the two swap.
+    // stride, off: the C columns are [off, off + C) of rows of `stride` cells in dfeat and arg (stride 0: the rows are the C columns)
+    void max_back(const float* dfeat, const uint32_t* arg, uint32_t M, uint32_t gsize, uint32_t C, uint32_t stride = 0, uint32_t off = 0)
     {
         if (rc) return;
         float* dst = dfeat == cur ? nxt : cur;
         {
             ProfScope ps(ctx, "pn2t_max_back");
-            hipLaunchKernelGGL(pn2t_max_back_kernel, dim3(blocks_for((size_t)M * C)), dim3(T_BLOCK), 0, ctx->stream, dfeat, arg, (size_t)M * C, gsize, C, dst);
+            hipLaunchKernelGGL(pn2t_max_back_kernel, dim3(blocks_for((size_t)M * C)), dim3(T_BLOCK), 0, ctx->stream, dfeat, arg, (size_t)M * C, gsize, C, stride ? stride : C, off,
+                               dst);
         }
         if (dst == nxt) std::swap(cur, nxt);
     }

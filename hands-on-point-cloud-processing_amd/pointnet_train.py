@@ -1,4 +1,4 @@
-"""HomeworkFinal's training step for the PointNet++ (SSG) classifier on the GPU: training-mode forward pass, get_loss and the gradient of
+"""HomeworkFinal's training step for the PointNet++ (SSG, MSG) and PointNet classifiers on the GPU: training-mode forward pass, get_loss and the gradient of
 every parameter (HomeworkFinal/train_cls.py:186-196 without its optimiser; models/pointnet2_cls_ssg.py).
 
   Trainer       the model in training mode on the library (pcr_pn2_train_grad_f32; the contract is above pcr_pn2_trainer_create in include/pcr.h)
@@ -6,7 +6,10 @@ every parameter (HomeworkFinal/train_cls.py:186-196 without its optimiser; model
   TrainerCls    the vanilla PointNet (models/pointnet_cls.get_model) in training mode (pcr_pointnet_train_grad_f32; the contract is above
                 pcr_pn1_trainer_create in include/pcr.h): the same surface as Trainer, nothing is sampled
   get_loss_cls  models/pointnet_cls.get_loss: the NLL plus mat_diff_loss_scale x the feature-transform regulariser
-  TRAINERS      the reference's module name (train_cls.py --model) -> the trainer class
+  TrainerMsg    the multi-scale model (models/pointnet2_cls_msg.get_model) in training mode: the same call on a trainer of
+                pcr_pn2_msg_trainer_create, with the head's two dropout probabilities (0.4, 0.5); get_loss serves it unchanged
+  TRAINERS      the reference's module name (train_cls.py --model) -> the trainer class, for the two first built
+  ALL_TRAINERS  the same for every model train_cls.py --model can name
 
 The optimiser stays torch's own, on host tensors, exactly as train_cls.py:147-153 builds it:
 
@@ -27,9 +30,14 @@ from __future__ import annotations
 
 import numpy as np
 
-from .pointnet import _BN_KEYS, _SSG_FC, _SSG_SA, _ctx, _like, _to_host, get_model, get_model_cls
+from .pointnet import _BN_KEYS, _SSG_FC, _SSG_SA, _ctx, _like, _to_host, get_model, get_model_cls, get_model_msg
 
 _PARAM_BN = ("weight", "bias")
+
+
+def _conv2d(conv):
+    """whether a layer's weight is a Conv2d's [out, in, 1, 1] in the reference's state dict (an SA layer's convolution)"""
+    return "mlp_convs" in conv or "conv_blocks" in conv
 
 
 class _DescModel(get_model):
@@ -50,22 +58,30 @@ class _DescModel(get_model):
     def state_shapes(self):
         out = {}
         for conv, bn, w, cin in self._l:
-            out[f"{conv}.weight"] = (w, cin, 1, 1) if "mlp_convs" in conv else (w, cin)
+            out[f"{conv}.weight"] = (w, cin, 1, 1) if _conv2d(conv) else (w, cin)
             out[f"{conv}.bias"] = (w,)
             for k in (_BN_KEYS if bn else ()):
                 out[f"{bn}.{k}"] = (w,)
         return out
 
 
+class _DescModelMsg(_DescModel, get_model_msg):
+    """pointnet.get_model_msg for the layers and the descriptor of a TrainerMsg.from_desc (uploaded through pn2_msg_model)"""
+
+
 def _desc_layers(desc, names):
-    """(conv / linear prefix, BN prefix or None, out, in) in weight order for a Pn2Desc and one (conv, bn) pair of names per layer"""
+    """(conv / linear prefix, BN prefix or None, out, in) in weight order for a Pn2Desc or a Pn2MsgDesc (layer by layer, branch by branch) and one
+    (conv, bn) pair of names per layer"""
     shapes, D = [], int(desc.D0)
     for l in range(desc.n_sa):
-        cin = 3 + D
-        for i in range(desc.sa[l].n_mlp):
-            shapes.append((int(desc.sa[l].widths[i]), cin, True))
-            cin = int(desc.sa[l].widths[i])
-        D = cin
+        sa, width = desc.sa[l], 0
+        for br in ([sa.branch[b] for b in range(sa.n_branch)] if hasattr(sa, "branch") else [sa]):      # a Pn2MsgDesc's branches, or the Pn2Desc's one
+            cin = 3 + D
+            for i in range(br.n_mlp):
+                shapes.append((int(br.widths[i]), cin, True))
+                cin = int(br.widths[i])
+            width += cin
+        D = width
     cin = D
     for i in range(desc.n_fc):
         shapes.append((int(desc.fc_widths[i]), cin, i + 1 < desc.n_fc))
@@ -105,12 +121,13 @@ class Trainer:
 
     def _setup(self, desc, layers, dropout, momentum, chunk_rows, ctx, seed):
         self._desc, self._layer_list = desc, layers
-        self.dropout, self.momentum, self.chunk_rows = float(dropout), float(momentum), int(chunk_rows)
+        self.dropout = tuple(float(p) for p in dropout) if isinstance(dropout, (tuple, list)) else float(dropout)
+        self.momentum, self.chunk_rows = float(momentum), int(chunk_rows)
         self._ctx_arg, self._trainer, self._trainer_ctx = ctx, None, None
         self._dirty = True                   # the host weights (running statistics included) are newer than the device's
         self._slots, off = {}, 0             # key -> (offset, shape) into the flat array
         for conv, bn, w, cin in layers:
-            self._slots[f"{conv}.weight"] = (off, (w, cin, 1, 1) if "mlp_convs" in conv else (w, cin))
+            self._slots[f"{conv}.weight"] = (off, (w, cin, 1, 1) if _conv2d(conv) else (w, cin))
             off += w * cin
             self._slots[f"{conv}.bias"] = (off, (w,))
             off += w
@@ -148,12 +165,16 @@ class Trainer:
             if self._trainer is not None:
                 self._pull_running()
                 self._trainer.free()
-            self._trainer, self._trainer_ctx = ctx.pn2_trainer(self._desc, self._flat, self.dropout, self.momentum, self.chunk_rows), ctx
+            self._trainer, self._trainer_ctx = self._make(ctx), ctx
             self._dirty = False
         elif self._dirty:
             self._trainer.set_weights(self._flat, keep_running_stats=False)
             self._dirty = False
         return self._trainer
+
+    def _make(self, ctx):
+        """the device trainer of this class on ctx, from the host weights"""
+        return ctx.pn2_trainer(self._desc, self._flat, self.dropout, self.momentum, self.chunk_rows)
 
     def _pull_running(self):
         if self._trainer is None or not self._trainer.h or self._dirty:
@@ -399,19 +420,8 @@ class TrainerCls(Trainer):
                 g[1].append(bn)
         return [f"{m}.{p}" for convs, bns in groups.values() for m in convs + bns for p in _PARAM_BN]
 
-    def trainer(self, ctx=None):
-        ctx = _ctx(ctx if ctx is not None else self._ctx_arg)
-        if self._trainer is None or self._trainer_ctx is not ctx or not self._trainer.h:
-            if self._trainer is not None:
-                self._pull_running()
-                self._trainer.free()
-            self._trainer = ctx.pn1_trainer(self._desc, self._flat, self.dropout, self.momentum, self.mat_diff_loss_scale, self.chunk_rows)
-            self._trainer_ctx = ctx
-            self._dirty = False
-        elif self._dirty:
-            self._trainer.set_weights(self._flat, keep_running_stats=False)
-            self._dirty = False
-        return self._trainer
+    def _make(self, ctx):
+        return ctx.pn1_trainer(self._desc, self._flat, self.dropout, self.momentum, self.mat_diff_loss_scale, self.chunk_rows)
 
     def step_grad(self, points, target, seed=None, keep=None, *, ctx=None):
         """points [B, 3 | 6, N], target [B] or [B, 1] -> (loss, logp [B, k]), numpy / float or torch like `points`; every gradient is left in
@@ -469,5 +479,46 @@ class get_loss_cls:
     __call__ = forward
 
 
-# the trainers by the reference's module name (train_cls.py --model)
+# ---------------------------------------------------------------------------------------------------- PointNet++ multi-scale (pointnet2_cls_msg)
+class TrainerMsg(Trainer):
+    """The reference's pointnet2_cls_msg.get_model in TRAINING mode on the library, with Trainer's whole surface.  TrainerMsg(num_class,
+    normal_channel, dropout, momentum, chunk_rows, ctx) is the reference's architecture (normal_channel defaults to False, as on Trainer);
+    TrainerMsg.from_desc(desc, names, dropout) any Pn2MsgDesc whose last SA layer is group_all (names: one (conv prefix, BN prefix or None) per
+    layer in weight order: layer by layer, branch by branch).  dropout: one probability per FC layer but the last (the reference: drop1 0.4,
+    drop2 0.5); a number stands for all of them.  The state-dict keys are the reference's (sa1.conv_blocks.0.0.weight,
+    sa1.bn_blocks.0.0.running_mean ..., sa3.mlp_convs.0.weight, fc1 / bn1 ...), as pointnet.get_model_msg speaks them."""
+
+    def __init__(self, num_class, normal_channel=False, dropout=(0.4, 0.5), momentum=0.1, chunk_rows=0, ctx=None, *, seed=0):
+        self.num_class, self.normal_channel = int(num_class), bool(normal_channel)
+        proto = get_model_msg(self.num_class, self.normal_channel)
+        self._setup(proto.desc(), proto._layers(), self._dropouts(dropout, 3), momentum, chunk_rows, ctx, seed)
+        self._generic = False
+
+    @classmethod
+    def from_desc(cls, desc, names, dropout=(0.4, 0.5), momentum=0.1, chunk_rows=0, ctx=None, *, seed=0):
+        self = cls.__new__(cls)
+        self.num_class, self.normal_channel = int(desc.fc_widths[desc.n_fc - 1]), int(desc.D0) == 3
+        self._setup(desc, _desc_layers(desc, names), cls._dropouts(dropout, int(desc.n_fc)), momentum, chunk_rows, ctx, seed)
+        self._generic = True
+        return self
+
+    @staticmethod
+    def _dropouts(dropout, n_fc):
+        ps = tuple(float(p) for p in dropout) if isinstance(dropout, (tuple, list, np.ndarray)) else (float(dropout),) * (n_fc - 1)
+        if len(ps) != n_fc - 1:
+            raise ValueError(f"dropout: one probability per FC layer but the last, the model has {n_fc - 1}")
+        return ps
+
+    def _make(self, ctx):
+        return ctx.pn2_msg_trainer(self._desc, self._flat, self.dropout, self.momentum, self.chunk_rows)
+
+    def eval_model(self):
+        """a pointnet.get_model_msg in eval mode loaded with the current weights and running statistics"""
+        m = _DescModelMsg(self.num_class, self._desc, self._layer_list) if self._generic else get_model_msg(self.num_class, self.normal_channel)
+        m.load_state_dict(self.state_dict(), strict=True)
+        return m.eval()
+
+
+# the trainers by the reference's module name (train_cls.py --model): the two first built, and all of them
 TRAINERS = {"pointnet2_cls_ssg": Trainer, "pointnet_cls": TrainerCls}
+ALL_TRAINERS = {**TRAINERS, "pointnet2_cls_msg": TrainerMsg}

@@ -964,6 +964,45 @@ int pcr_pn1_trainer_create(pcr_ctx* ctx, const pcr_pn1_desc* desc, const float* 
 int pcr_pointnet_train_grad_f32(pcr_ctx* ctx, pcr_pn2_trainer* trainer, const float* objects, size_t n_obj, size_t npts, const int32_t* target,
                                 uint64_t seed, const uint8_t* keep, double loss[3], float* logp, float* trans, float* trans_feat, float* grad);
 
+/* ---- HomeworkFinal: the PointNet++ multi-scale (MSG) TRAINING pass: training-mode forward, pointnet2_cls_msg.get_loss and the gradient of
+ * every parameter.  A trainer is made from a pcr_pn2_msg_desc (any descriptor pcr_pn2_msg_model_create accepts whose last SA layer is
+ * group_all) and that function's flat weight array, UNFOLDED.  The handle is the SSG trainer's type: pcr_pn2_trainer_destroy, _info,
+ * _set_weights and _get_weights work on it, and pcr_pn2_train_grad_f32 RUNS THE STEP on it with the same arguments (starts stays
+ * n_sampling x n_obj, one set of centres per layer; the same seed rule); pcr_pointnet_train_grad_f32 on it is PCR_ERR_ARG.  It is the SAME
+ * pass: a trainer of pcr_pn2_trainer_create is the case of one xyz-first branch per layer and one p, bit for bit.
+ * dropout_p: n_dropout = n_fc - 1 probabilities in [0, 1), one per hidden FC layer (the reference: drop1 0.4, drop2 0.5,
+ *   pointnet2_cls_msg.py:18,21); with n_fc == 1 n_dropout is 0 and dropout_p may be NULL.  pcr_pn2_trainer_info reports the FIRST hidden
+ *   layer's p in dropout_p (0 with n_fc == 1); pcr_pn2_msg_trainer_info reports all of them.
+ * Everything the SSG trainer's contract says holds word for word per (branch, convolution).  Added:
+ *   Sampling   FPS once per layer; a layer with several branches takes ONE multi-radius walk (pcr_ball_query_multi_f32's kernel): idx is, on
+ *              every element, what pcr_ball_query_f32 gives per radius.  No gradient flows through either.  npoint may exceed the points of
+ *              an object, as in the eval pass (picks repeat index 0 once every distance is 0).
+ *   Rows       branch b of a layer has the PADDED rows, centres x nsample_b, copies included; every (branch, convolution) has its own BatchNorm
+ *              over its own M_b rows with its own chunks.  A row's input is (xyz - centre | features) with xyz_last == 0 and
+ *              (features | xyz - centre) with xyz_last == 1, xyz - centre in one f32 subtraction; the product's chain runs over ascending
+ *              channel IN THAT ORDER.  The limits of 2^21 rows and 65535 chunks apply per (branch, layer).
+ *   Max        per branch, after the ReLU, at the lowest member position; it writes columns [off_b, off_b + w_b) of the layer's concatenated
+ *              row, off_b = the sum of the earlier branches' last widths.  Backward, each branch reads its own columns of that row's gradient.
+ *   Features   the gradient of a layer's input features is, per point and channel, ONE f64 sum over the rows of ALL branches that read the
+ *              point: branches ascending, rows ascending inside a branch (one launch per branch, the sum handed on in f64), rounded once to
+ *              f32.  The xyz columns (0 ... 2, or the last three with xyz_last) are dropped; a point no row read gets +0.  The first SA layer's
+ *              convolutions take no dx.
+ *   Head       as the SSG trainer's with layer i's OWN p: s_i = f32(1 / (1 - p_i)), the drawn mask is keep[i][e] =
+ *              (K(seed, (0x100 + i) << 32 | e) >> 11) 2^-53 >= p_i; the keep bytes are laid out as there.
+ *   Order      No floating-point atomic.  The bits depend on the inputs and chunk_rows only: not on pn2_rows, pn2_compact or any other tune
+ *              key, nor on a repeat.
+ * pcr_pn2_msg_trainer_info — pcr_pn2_trainer_info's fields, plus (optional) the descriptor in the superset form (a trainer of
+ *   pcr_pn2_trainer_create reports one xyz-first branch per layer) and (optional) PCR_PN2_MAX_FC - 1 doubles: the hidden layers' p, 0 behind
+ *   the last.  PCR_ERR_ARG: NULL trainer / info, a trainer of pcr_pn1_trainer_create, a call too large (as pcr_pn2_trainer_info).
+ * PCR_ERR_ARG (create): NULL ctx / desc / weights / out; a descriptor pcr_pn2_msg_model_create refuses; a last SA layer that is not
+ *   group_all; n_dropout != n_fc - 1; NULL dropout_p with n_dropout > 0; a p outside [0, 1); bn_momentum outside [0, 1]; n_weights not the
+ *   model's count; a non-finite weight; var + eps <= 0.  The step: as pcr_pn2_train_grad_f32, a (branch, layer) with one row included.
+ * Profile names: the SSG trainer's (+ ball_query_multi). */
+int pcr_pn2_msg_trainer_create(pcr_ctx* ctx, const pcr_pn2_msg_desc* desc, const float* weights, size_t n_weights, const double* dropout_p,
+                               size_t n_dropout, double bn_momentum, uint32_t chunk_rows, pcr_pn2_trainer** out);
+int pcr_pn2_msg_trainer_info(const pcr_pn2_trainer* trainer, size_t n_obj, size_t npts, pcr_pn2_train_info* info, pcr_pn2_msg_desc* desc,
+                             double* dropout_p);
+
 /* ---- next row N4: global-registration front half, Homework9/hw9/src/registration.cpp:288-434, :535-615 -----------
  * N4a: exhaustive 1-NN between two descriptor sets (row-major n x dim / m x dim f32, host memory; dim 33 = FPFH),
  * nanoflann's evalMetric arithmetic for any dim (nanoflann.hpp:382-405: groups of four + tail, f32, unfused), canonical
