@@ -114,7 +114,7 @@ ABI_SYMBOLS = [
     "pcr_device_count", "pcr_ctx_create", "pcr_ctx_destroy", "pcr_ctx_sync", "pcr_ctx_last_error", "pcr_version", "pcr_ctx_device_info",
     "pcr_cloud_create", "pcr_cloud_clone", "pcr_cloud_assign", "pcr_cloud_read", "pcr_cloud_size", "pcr_cloud_destroy",
     "pcr_nn1_f32", "pcr_nn1_f32_async", "pcr_nn1_fetch", "pcr_transform_f32", "pcr_kabsch_sums", "pcr_kabsch_solve", "pcr_kabsch_grid_exponent", "pcr_kabsch_limbs_to_sums",
-    "pcr_icp_p2p_f32", "pcr_icp_last_chain", "pcr_icp_last_snapshots", "pcr_icp_replica_members", "pcr_icp_move_route", "pcr_s3_walk_visits", "pcr_plane_count_f64", "pcr_plane_mask_f64", "pcr_knn_f64", "pcr_radius_f64",
+    "pcr_icp_p2p_f32", "pcr_icp_last_chain", "pcr_icp_last_snapshots", "pcr_icp_replica_members", "pcr_icp_move_route", "pcr_icp_solve_route", "pcr_icp_solve_in_search_auto", "pcr_s3_walk_visits", "pcr_plane_count_f64", "pcr_plane_mask_f64", "pcr_knn_f64", "pcr_radius_f64",
     "pcr_comm_unique_id", "pcr_comm_init_rccl", "pcr_comm_init_callback", "pcr_comm_destroy", "pcr_comm_selftest", "pcr_shard_range",
     "pcr_prof_reset", "pcr_prof_get", "pcr_prof_get_each", "pcr_tune_set",
     "pcr_grid_stats", "pcr_nn1_stats", "pcr_selftest_mfma_bf16", "pcr_selftest_mfma_f16", "pcr_selftest_mfma_bf16_v2", "pcr_selftest_mfma_f16_v2", "pcr_selftest_sign_f16", "pcr_selftest_sphere_f16", "pcr_ctx_mfma_check", "pcr_voxel_filter_f32", "pcr_iss_keypoints_f32", "pcr_icp_p2plane_f32", "pcr_cloud_knn_f64", "pcr_normals_knn_f64", "pcr_cloud_pca_f64", "pcr_fast_eigen3x3", "pcr_ground_seeds_f64", "pcr_ground_detection_f64",
@@ -183,6 +183,9 @@ def lib():
     L.pcr_icp_replica_members.argtypes = [C.c_uint32, C.c_uint32]
     L.pcr_icp_replica_members.restype = C.c_uint32
     L.pcr_icp_move_route.argtypes = [C.c_uint64, C.c_uint64, C.c_int] + [C.c_int64] * 7
+    L.pcr_icp_solve_route.argtypes = [C.c_uint64, C.c_uint64, C.c_int] + [C.c_int64] * 8
+    L.pcr_icp_solve_in_search_auto.argtypes = []
+    L.pcr_icp_solve_in_search_auto.restype = C.c_uint64
     L.pcr_s3_walk_visits.argtypes = [C.c_uint32, vp, vp, C.c_uint32, vp, sz, C.POINTER(sz)]
     L.pcr_plane_count_f64.argtypes = [vp, vp, vp, sz, C.c_double, vp]
     L.pcr_plane_mask_f64.argtypes = [vp, vp, vp, C.c_double, vp, C.POINTER(C.c_int64)]
@@ -329,6 +332,20 @@ def icp_move_route(n_src: int, n_tgt: int, nranks: int = 1, move_in_search: int 
     (pcr_icp_move_route; raw tune values, 0 = default; host logic, no GPU)?"""
     return bool(lib().pcr_icp_move_route(n_src, n_tgt, nranks, move_in_search, fused_sums, fused_sums_min, s3_transposed, sphere_qg,
                                          sphere_l0_per_slice, sphere_blocks))
+
+
+def icp_solve_route(n_src: int, n_tgt: int, nranks: int = 1, solve_in_search: int = 0, move_in_search: int = 0, fused_sums: int = 0,
+                    fused_sums_min: int = 0, s3_transposed: int = 0, sphere_qg: int = 0, sphere_l0_per_slice: int = 0, sphere_blocks: int = 0) -> bool:
+    """Would that loop also let the next search reduce the sums and solve (chain 5: icp_move_route's conditions and the tune icp_solve_in_search,
+    whose auto holds only while icp_move_in_search is 0 too; pcr_icp_solve_route; raw tune values; host logic, no GPU)?"""
+    return bool(lib().pcr_icp_solve_route(n_src, n_tgt, nranks, solve_in_search, move_in_search, fused_sums, fused_sums_min, s3_transposed, sphere_qg,
+                                          sphere_l0_per_slice, sphere_blocks))
+
+
+def icp_solve_in_search_auto() -> int:
+    """What icp_solve_in_search = 0 means in this build where icp_move_in_search is 0 too: on for up to this many source points, 0 = off
+    (pcr_icp_solve_in_search_auto)."""
+    return int(lib().pcr_icp_solve_in_search_auto())
 
 
 def s3_walk_visits(S0: int, rows, tiles, n_rec: int):
@@ -1879,12 +1896,14 @@ class Context:
 
     def icp_last_chain(self) -> int:
         """The tail of the last icp_point2point call's iterations (pcr_icp_last_chain): 0 synchronous loop, 1 separate launches, 2 solve + move,
-        3 sums + solve + move, 4 sums + solve with the move in the next search."""
+        3 sums + solve + move, 4 sums + solve with the move in the next search, 5 sums alone with the reduce, the solve and the move in the next
+        search (tune icp_solve_in_search)."""
         return int(lib().pcr_icp_last_chain(self.h))
 
     def icp_last_snapshots(self) -> int:
         """How the last icp_point2point call learnt its loop's state (pcr_icp_last_snapshots): 0 copies and events on the stream, 1 written into
-        pinned host memory by the sums + solve launch itself (chain 4; tune icp_host_snapshots: 2 = off)."""
+        pinned host memory by the sums + solve launch itself (chain 4) or by the next chunk's first search and the finishing launch (chain 5); tune
+        icp_host_snapshots: 2 = off."""
         return int(lib().pcr_icp_last_snapshots(self.h))
 
     # ---- A10

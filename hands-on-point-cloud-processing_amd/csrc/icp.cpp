@@ -44,6 +44,22 @@ bool pcr::icp_move_route(uint64_t n_src, uint64_t n_l0, int nranks, int64_t move
     return s3_move_route(n_l0, n_src, transposed_tune, qg_tune, l0_per_slice_tune, blocks_tune);
 }
 
+// The chain sums -> search (finishes the previous iteration, then moves the cloud), taken only where the chain above would be: whether
+// the solve goes into the next search as well.  Tune icp_solve_in_search: 0 = auto, 1 = on where possible, 2 = off; auto holds only while
+// icp_move_in_search is at its own default too — a caller that sets that tune to 1 asked for the chain above and keeps it.
+// Auto = on up to 131 072 source points: the headline A/B of profiles/icp_solve_in_search.txt (49.06 -> 47.26 us per step of the bench line, a gain by the
+// rule; in one process 37.7 -> 35.1 us per iteration at 60 k, 47.6 -> 45.4 at 120 k).  Every workgroup of the search pays the solve before its first
+// query is staged, so the launch pays it once per ROUND of resident workgroups: 131 072 points are the 1 024 workgroups of 128 queries that 256 CUs
+// hold at four waves per SIMD, and at 250 k (two rounds) the chain loses, 80.5 -> 83.9 us.
+constexpr bool ICP_SOLVE_IN_SEARCH_AUTO = true;
+constexpr uint64_t ICP_SOLVE_IN_SEARCH_AUTO_MAX = 131072;
+bool pcr::icp_solve_route(uint64_t n_src, int64_t solve_in_search_tune, int64_t move_in_search_tune)
+{
+    if (solve_in_search_tune == 1) return true;
+    if (solve_in_search_tune == 2) return false;
+    return move_in_search_tune == 0 && ICP_SOLVE_IN_SEARCH_AUTO && n_src <= ICP_SOLVE_IN_SEARCH_AUTO_MAX;
+}
+
 // ---- synchronous loop: one host round trip per iteration (needed by the host-callback transport; also the
 // reference implementation of the loop the pipelined variant below must reproduce bit for bit)
 static int icp_sync(pcr_ctx* ctx, const pcr_cloud* src, const pcr_cloud* tgt, const float init_T[16],
@@ -176,8 +192,9 @@ static int icp_pipelined(pcr_ctx* ctx, const pcr_cloud* src, const pcr_cloud* tg
         // the fused sums + move launch (kabsch.hip).  Zeroed ONCE: the counter only ever grows, and [1].barrier_timeout must not start as garbage
         static_assert(2 * sizeof(IcpState) <= 512, "the barrier counter lies 512 bytes behind the states");
         // behind the counter's line, on lines of their own: the accumulators of the sums + solve launch (kabsch.hip icp_sums_solve_kernel), zeroed
-        // here and left all zero by every launch
-        constexpr size_t acc_bytes = (size_t)ICP_ACC_REPLICAS * ICP_ACC_WORDS * sizeof(long long);
+        // here and left all zero by every launch — two sets of them: the chain sums -> search alternates between the two, every other
+        // chain has set 0 alone, and BOTH are all zero between calls
+        constexpr size_t acc_bytes = (size_t)ICP_ACC_SETS * ICP_ACC_REPLICAS * ICP_ACC_WORDS * sizeof(long long);
         PCR_HIP(ctx, hipMalloc((void**)&ctx->icp_state_dev, 512 + 128 + acc_bytes));
         PCR_HIP(ctx, hipMemsetAsync(ctx->icp_state_dev, 0, 512 + 128 + acc_bytes, ctx->stream));
         ctx->icp_barrier_dev = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(ctx->icp_state_dev) + 512);
@@ -248,9 +265,20 @@ static int icp_pipelined(pcr_ctx* ctx, const pcr_cloud* src, const pcr_cloud* tg
     // on 118 workgroups — kernel 19.9 -> 17.5 us, a step of the bench line 53.4 -> 50.9 us (8 + 8 alternating processes, spreads 2.5 / 0.9).  What
     // now bounds it: the last arriver has its ticket back and its acquire done ~35 ns per arriving workgroup later (4 - 5 us at 118, 9 at 235, 16 at 469),
     // then the solve.  A ticket per replica (tune icp_ticket_levels = 2: arrivals queue as 15 + 8) does not shorten that wait — 4.1 - 5.5 us
-    // at 118 workgroups, 8.1 - 11.2 at 235 — so whatever the 35 ns are, they are not a queue at one address; one counter stays the default.
+    // at 118 workgroups, 8.1 - 11.2 at 235 — so they are not a queue at one address; one counter stays the default.  What the chain sums -> search
+    // (below, DESIGN.md 6k, profiles/icp_solve_in_search.txt) found about that wait: it is a cost of handing the sums over INSIDE a launch and of nothing
+    // else.  The same front half with the same atomics and no release, ticket or acquire behind them is a launch of 7.8 us at 118 workgroups (17.4 with
+    // the hand-over and the solve) and 6.8 us at 235; the next launch finds the rows complete and has them in LDS 0.15 us after the loads it requests
+    // beside its own come back.  The solve itself does not get cheaper by moving: 5.5 - 6.2 us in the last arriver, 6.8 - 9.4 us as one wave of each of
+    // 938 workgroups, which all wait for it.
     const bool move_cand = fused && seed_tgt && icp_sums_solve_blocks(ctx, work->n) != 0;
     bool move_in_search = false;
+    // A fourth chain (tune icp_solve_in_search): search -> sums (kabsch.hip icp_sums_kernel), and the search of iteration k + 1 FINISHES
+    // iteration k in its prologue — every workgroup reads the eight accumulator rows and reduces, solves and steps the state for itself (nn1_sphere.hpp,
+    // SV; icp_finish.hpp) — before it moves the cloud; behind the last sums launch of a call ONE wave does the same (icp_finish_kernel).  No release, no
+    // ticket and no acquire anywhere: every dependency is a launch boundary of the stream.  Taken where the chain above is (icp_solve_route).  State k
+    // (after k iterations) is published by workgroup 0 of search k into dev[k & 1]; iteration k adds into accumulator set k & 1 and zeroes the other.
+    bool solve_in_search = false;
     // (Measured and dropped, round 4: the Kabsch sums taken by the search kernel itself — STRACK3 ends with every query's final key in one wave, so each
     // wave added its 32 pairs' limbs (wave sums, a row per workgroup, f64 atomics into 64 rows; same bits) and the streaming pass + its launch gap
     // (7 + 4.5 us) went away: the search grew from 0.034 to 0.049 ms — 41 limbs x 6 f64 shuffle-adds per wave, four waves per SIMD ending together on
@@ -276,8 +304,20 @@ static int icp_pipelined(pcr_ctx* ctx, const pcr_cloud* src, const pcr_cloud* tg
             IcpState* cur = fused ? dev + (enq & 1) : dev;                                        // the state this iteration starts from
             ctx->stop_flag_dev = &cur->stop;     // correspondence kernels no-op once stop or stop_after_transform is set
             ctx->nn1_move_state = move_in_search ? cur : nullptr;        // (iteration 0 decides: nothing to move in front of it)
+            IcpSolveArgs sv = { nullptr, nullptr, nullptr, nullptr, 0ull, 0 };
+            if (solve_in_search) {
+                // this search finishes iteration enq - 1: from the state that one started from and the set its sums went into, to `cur`.  The first
+                // search of a chunk thereby publishes the state behind the previous chunk: it gets that chunk's slot of the ring
+                const int slot = snaps && c == 0 ? (int)((chunks - 1) % RING) : -1;
+                if (slot >= 0) ring_seq[slot] = ++ctx->icp_snap_seq;
+                sv = IcpSolveArgs{ ctx->icp_acc_dev + (size_t)((enq - 1) & 1) * ICP_ACC_REPLICAS * ICP_ACC_WORDS, cur, ctx->dev_out,
+                                   slot >= 0 ? ctx->icp_state_host_dev + slot : nullptr, slot >= 0 ? ring_seq[slot] : 0ull, plan.e };
+                ctx->nn1_move_state = dev + ((enq - 1) & 1);
+                ctx->nn1_solve = &sv;
+            }
             rc = launch_nn1(ctx, tgt, work, true, gate);                                          // :925-934
             ctx->nn1_move_state = nullptr;
+            ctx->nn1_solve = nullptr;
             if (rc) break;
             if (enq == 0)
                 move_in_search = move_cand && ctx->nn1_move_l0 != 0 &&
@@ -286,6 +326,11 @@ static int icp_pipelined(pcr_ctx* ctx, const pcr_cloud* src, const pcr_cloud* tg
                                                 tune_get(ctx, "nn1_sphere_l0_per_slice", 0), tune_get(ctx, "nn1_sphere_blocks", 0));
             else if (move_in_search && !ctx->nn1_moved) { rc = fail(ctx, PCR_ERR_STATE, "ICP: a search of the chain search -> sums + solve did not move the cloud"); break; }
             if (enq == 0) snaps = move_in_search && snap_cand;
+            if (enq == 0) solve_in_search = move_in_search && icp_solve_route(work->n, tune_get(ctx, "icp_solve_in_search", 0), tune_get(ctx, "icp_move_in_search", 0));
+            if (solve_in_search) {
+                if ((rc = launch_icp_sums(ctx, tgt, work, prm->max_corr, cur, plan, (int)(enq & 1)))) break;                                          // :936-940
+                continue;
+            }
             if (move_in_search) {
                 // the last launch of the call writes slot [RING], the last of any other chunk the chunk's slot of the ring, the others none
                 const bool ends_call = enq + 1 == prm->max_iter, ends_chunk = c + 1 == chunk;
@@ -319,7 +364,9 @@ static int icp_pipelined(pcr_ctx* ctx, const pcr_cloud* src, const pcr_cloud* tg
         if (rc) break;
         const int slot = (int)(chunks % RING);
         if (!snaps) {
-            e = hipMemcpyAsync(&host[slot].state, fused ? dev + (enq & 1) : dev, sizeof(IcpState), hipMemcpyDeviceToHost, ctx->stream);
+            // (the chain sums -> search: the state behind this chunk is the next search's to publish — the copy takes the newest one there is, one
+            // iteration older; what the host sees only decides when it stops enqueuing)
+            e = hipMemcpyAsync(&host[slot].state, solve_in_search ? dev + ((enq - 1) & 1) : fused ? dev + (enq & 1) : dev, sizeof(IcpState), hipMemcpyDeviceToHost, ctx->stream);
             if (e == hipSuccess) e = hipEventRecord(ctx->icp_events[slot], ctx->stream);
             if (e != hipSuccess) { rc = fail(ctx, PCR_ERR_HIP, "icp snapshot", e); break; }
         }
@@ -359,6 +406,13 @@ static int icp_pipelined(pcr_ctx* ctx, const pcr_cloud* src, const pcr_cloud* tg
         }
     }
     ctx->stop_flag_dev = nullptr;
+    // the chain sums -> search: the last iteration enqueued is finished by a launch of its own, which publishes like the sums + solve launch of a call's end
+    if (rc == PCR_OK && solve_in_search && enq > 0) {
+        if (snaps) ring_seq[RING] = ++ctx->icp_snap_seq;
+        rc = launch_icp_finish(ctx, dev + ((enq - 1) & 1), dev + (enq & 1), plan, (int)((enq - 1) & 1), snaps ? ctx->icp_state_host_dev + RING : nullptr,
+                               snaps ? ring_seq[RING] : 0ull);
+        if (rc == PCR_OK && snaps) last_slot = RING;
+    }
     // the final state: from the slot the last sums + solve launch wrote, once the stream has drained — or, on every other chain and behind a call that
     // enqueued no such launch (max_iter = 0), by a copy behind the last launch
     const bool final_in_slot = snaps && last_slot >= 0;
@@ -376,7 +430,7 @@ static int icp_pipelined(pcr_ctx* ctx, const pcr_cloud* src, const pcr_cloud* tg
     // the accumulators of the sums + solve launch are all zero behind a call that ran to its end; one that did not says so, and the next call clears them
     if (move_in_search && (rc || f.overflow || f.barrier_timeout)) ctx->icp_acc_dirty = true;
     if (rc) return rc;
-    ctx->icp_last_chain = move_in_search ? 4 : fused_sums ? 3 : fused ? 2 : 1;
+    ctx->icp_last_chain = solve_in_search ? 5 : move_in_search ? 4 : fused_sums ? 3 : fused ? 2 : 1;
     ctx->icp_last_snapshots = final_in_slot ? 1 : 0;
     if (f.overflow) return fail(ctx, PCR_ERR_STATE, "ICP: a kept source point lies more than 2^20 target extents away from the target");
     if (f.barrier_timeout) {
@@ -408,6 +462,14 @@ extern "C" int pcr_icp_move_route(uint64_t n_src, uint64_t n_tgt, int nranks, in
     return icp_move_route(n_src, s3_l0_super_tiles(n_tgt), nranks, move_in_search, fused_sums, fused_sums_min, s3_transposed, sphere_qg, sphere_l0_per_slice,
                           sphere_blocks) ? 1 : 0;
 }
+
+extern "C" int pcr_icp_solve_route(uint64_t n_src, uint64_t n_tgt, int nranks, int64_t solve_in_search, int64_t move_in_search, int64_t fused_sums,
+                                   int64_t fused_sums_min, int64_t s3_transposed, int64_t sphere_qg, int64_t sphere_l0_per_slice, int64_t sphere_blocks)
+{
+    return pcr_icp_move_route(n_src, n_tgt, nranks, move_in_search, fused_sums, fused_sums_min, s3_transposed, sphere_qg, sphere_l0_per_slice, sphere_blocks) &&
+           icp_solve_route(n_src, solve_in_search, move_in_search) ? 1 : 0;
+}
+extern "C" uint64_t pcr_icp_solve_in_search_auto(void) { return ICP_SOLVE_IN_SEARCH_AUTO ? ICP_SOLVE_IN_SEARCH_AUTO_MAX : 0; }
 
 extern "C" int pcr_icp_p2p_f32(pcr_ctx* ctx, const pcr_cloud* src, const pcr_cloud* tgt, const float init_T[16],
                                const pcr_icp_params* prm, float out_T[16], pcr_icp_stats* stats)

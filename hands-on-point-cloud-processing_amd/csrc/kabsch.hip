@@ -9,6 +9,7 @@
 //   * transform_kernel: A8 transformCloudInplace (registration.cpp:165-178), f32, unfused, in place,
 //     24 B per point, float4-vectorised over the SoA arrays.
 #include "grid_common.hpp"
+#include "icp_finish.hpp"
 #include "numerics.hpp"
 
 #include <algorithm>
@@ -21,8 +22,7 @@ namespace pcr {
 
 constexpr int KB_BLOCK = 256;
 constexpr int KB_NV = 16;             // 3 + 3 + 9 sums + count
-constexpr int KB_NL = num::KB_NL;     // 55 normalised limbs (numerics.hpp)
-constexpr int KB_ROW = 58;            // a partial row: KB_NL limbs, [55] last-kept key (u64 bits), [56] overflow flag, [57] pad
+// (KB_NL, KB_ROW, KB_NLC — the limbs and slots of a partial row — and the steps from a reduced row to the new loop state: icp_finish.hpp)
 constexpr int KB_MAX_BLOCKS = 8192;   // == the capacity of ctx->partials (api.cpp)
 static_assert(KB_ROW * KB_MAX_BLOCKS == 8192 * 58, "api.cpp sizes ctx->partials as 8192 x 58 doubles");
 
@@ -108,8 +108,6 @@ __device__ __forceinline__ int wave_totals(double (&v)[KB_NL], int lane)
     p += (lane & 32) ? (N + 1) / 2 : 0;  ok = ok && p < N;
     return ok ? p : -1;
 }
-
-constexpr int KB_NLC = 40;            // the limbs that are not carry slots (12 + 27) + the count
 
 // carries: false when the carry slots of tn[] are known to be zero (no per-thread normalisation): they are not exchanged at all
 // BFLY: the halving butterfly over the 40 live limbs (needs carries == false); it keeps all of them in registers at once (~160
@@ -323,20 +321,6 @@ __device__ __forceinline__ void reduce_rows(const double* __restrict__ partials,
     __syncthreads();
 }
 
-__device__ __forceinline__ void row_to_out18(const double (&row)[KB_ROW], int e, double* out)
-{
-    const int k = threadIdx.x;
-    if (k < 6) out[k] = num::limbs_value(row + 3 * k, 2, e - 2 * num::KB_W);
-    else if (k < 15) out[k] = num::limbs_value(row + 18 + 4 * (k - 6), 3, 2 * e - 3 * num::KB_W);
-    else if (k == 15) out[15] = row[54];
-    else if (k == 16) {
-        const unsigned long long lk = (unsigned long long)__double_as_longlong(row[55]);
-        out[16] = row[54] > 0.0 ? (double)(uint32_t)(lk >> 32) : -1.0;
-        out[17] = row[54] > 0.0 ? (double)__uint_as_float((uint32_t)(lk & 0xFFFFFFFFull)) : 0.0;
-        out[18] = row[56];
-    }
-}
-
 __global__ __launch_bounds__(KF_BLOCK) void kabsch_final_kernel(const double* __restrict__ partials, uint32_t n_blocks, int e, double* __restrict__ out)
 {
     __shared__ double red[KF_GROUPS][64];
@@ -435,40 +419,9 @@ int launch_kabsch_sums(pcr_ctx* ctx, const pcr_cloud* tgt, const pcr_cloud* src,
 }
 
 // ---------------------------------------------------------------------------------------------- device-resident ICP state
-// The pipelined ICP loop (icp.cpp) keeps the whole state machine of registration.cpp:915-1006 on the GPU so that
-// iterations are enqueued back to back without a host round trip: nn1 -> kabsch_partial -> icp_update -> transform.
-
-// state machine + Kabsch solve + pose composition, one thread (registration.cpp:939-1002).  `st` is the workgroup's LDS copy of
-// the state (icp_state_stage): the step is one thread's serial chain, and every field it touched in HBM was a dependent memory
-// round trip of that chain (stop -> stop_after_transform -> last_loss, eps -> unchanged -> T_total ...).
-__device__ __forceinline__ void icp_state_step(IcpState* st, const double* sums16, bool any_kept, float last_d2, bool overflow)
-{
-    if (st->stop) return;
-    if (st->stop_after_transform) { st->stop = 1; return; }   // max_iter reached: the loop is over
-    if (overflow) { st->overflow = 1; st->stop = 1; return; }  // a kept source beyond the accumulation grid (kabsch_plan)
-    float loss = 0.0f;
-    if (any_kept) loss = last_d2 * last_d2;                                      // :939
-    st->last_pairs = (unsigned long long)sums16[15];
-    st->loss = loss;
-    if (fabsf(st->last_loss - loss) < st->eps) st->unchanged++;                  // :948-951
-    if (st->unchanged > 15) { st->converged = 1; st->stop = 1; return; }         // :954-958
-    st->last_loss = loss;                                                        // :961
-    float Rd[9], td[3];
-    if (num::kabsch_solve(sums16, Rd, td) != 0) { st->empty = 1; st->stop = 1; return; }   // :979-998
-    const float T_delta[16] = { Rd[0], Rd[1], Rd[2], td[0], Rd[3], Rd[4], Rd[5], td[1],
-                                Rd[6], Rd[7], Rd[8], td[2], 0, 0, 0, 1 };
-    num::mat4_mul_f32(T_delta, st->T_total, st->T_total);                        // :1000-1002
-    for (int k = 0; k < 9; k++) st->Rd[k] = Rd[k];
-    for (int k = 0; k < 3; k++) st->td[k] = td[k];
-    st->iters_run++;
-    // max_iter reached: this iteration's transform must still run, everything after it must not
-    if (st->iters_run >= st->max_iter) st->stop_after_transform = 1;
-}
+// (icp_state_step — state machine + Kabsch solve + pose composition, one thread — and ST_WORDS: icp_finish.hpp)
 
 // the whole state in ONE coalesced read: thread w copies 32-bit word w into the workgroup's LDS copy (ends in a barrier)
-constexpr int ST_WORDS = (int)(sizeof(IcpState) / 4);
-static_assert(sizeof(IcpState) % 4 == 0 && ST_WORDS <= 64, "IcpState is staged by one wave, one word per lane");
-
 __device__ __forceinline__ void icp_state_stage(const IcpState* st, IcpState* lds)
 {
     if (threadIdx.x < ST_WORDS)
@@ -914,21 +867,6 @@ __device__ __forceinline__ void fs_pairs_row(const FsPairs<PP>& P, float max_cor
 // live limb p (the numbering of block_reduce_limbs' butterfly: 12 coordinate limbs, 27 product limbs, the count) -> its slot of a row
 __host__ __device__ constexpr int live_slot(int p) { return p < 12 ? 3 * (p / 2) + p % 2 : (p < 39 ? 18 + 4 * ((p - 12) / 3) + (p - 12) % 3 : 54); }
 
-// carry propagation of one sum in integer arithmetic, the rule of num::limbs_normalize (quotient truncated toward zero, remainder with the dividend's
-// sign, carry into the next limb): L[0..n) limbs, L[n] the carry limb; out[] the normalised f64 limbs.  The quotient by 2^40 is a shift of the
-// dividend, biased by 2^40 - 1 where it is negative (an arithmetic shift alone rounds toward minus infinity)
-__device__ __forceinline__ void limbs_normalize_i64(long long* L, int n, double* out)
-{
-    constexpr long long W = 1ll << num::KB_W;
-    for (int j = 0; j < n; j++) {
-        const long long c = (L[j] + ((L[j] >> 63) & (W - 1))) >> num::KB_W;
-        L[j] -= c * W;
-        L[j + 1] += c;
-        out[j] = (double)L[j];
-    }
-    out[n] = (double)L[n];
-}
-
 // Exhaustive loops whose NEXT SEARCH moves the cloud (nn1_sphere.hpp, MV): the sums and the solve alone.  The front half is that of
 // icp_sums_update_move_kernel — same loads, same gate, same limbs, same butterfly and LDS combine — for PP pairs per thread, but nobody waits and nobody
 // stores a row: a workgroup's totals are exact integers below 2^53 (T x PP terms below 2^40), so lanes 0 .. 41 of its first wave convert them to int64
@@ -944,9 +882,7 @@ __device__ __forceinline__ void limbs_normalize_i64(long long* L, int n, double*
 // (ss_snapshot below; snap, seq).  levels = 2 (tune icp_ticket_levels; measured, no gain, not the default) arrives in two steps: at a counter of the
 // workgroup's own replica, and only the last of a replica at the shared counter — which then counts the replicas that have workgroups, not the workgroups.
 // An accumulator holds at most n terms below 2^40: n < 2^22 (icp_sums_solve_blocks) keeps it below 2^62.
-constexpr int ACC_R = ICP_ACC_REPLICAS, ACC_W = ICP_ACC_WORDS;      // words of a replica: [0..40) live limbs, [40] overflow count, [41] key, pad to 3 lines
-constexpr int ACC_CNT = KB_NLC + 2;                                  // [42] the replica's arrival counter where every replica has a ticket of its own (6j)
-static_assert((ACC_R & (ACC_R - 1)) == 0 && ACC_W * 8 % 128 == 0 && ACC_W >= KB_NLC + 3, "replicas: a power of two, whole 128-byte lines");
+// (ACC_R, ACC_W, ACC_CNT — the replicas and the words of one: icp_finish.hpp)
 
 // DESIGN.md 6j.  The state snapshot the host loop looks at (icp.cpp), written by the publishing workgroup itself where the launch is the last of a chunk or
 // of the call (snap: a slot of the pinned, coherent host ring; null otherwise — uniform over the workgroup): the words of the state just published, from
@@ -1068,30 +1004,9 @@ __global__ __launch_bounds__(T) void icp_sums_solve_kernel(
         const unsigned long long pt_c2 = __builtin_amdgcn_s_memrealtime();
 #endif
         const int k = threadIdx.x;
-        if (k < KB_NLC + 2) {
-            // word k over the replicas, into replica 0's place: the sums of the limbs and of the overflow counts, the maximum of the keys
-            long long v = s_acc[0][k];
-#pragma unroll
-            for (int r = 1; r < ACC_R; r++) {
-                const long long o = s_acc[r][k];
-                v = k == KB_NLC + 1 ? (long long)((unsigned long long)o > (unsigned long long)v ? o : v) : v + o;
-            }
-            s_acc[0][k] = v;          // (thread k alone reads and writes column k)
-        }
+        if (k < KB_NLC + 2) acc_fold_column(s_acc, k);      // word k over the replicas, into replica 0's place
         __syncthreads();
-        if (k < 15) {
-            // sum k: its 2 (coordinates) or 3 (products) live limbs, then the carries
-            const int nl = k < 6 ? 2 : 3, p0 = k < 6 ? 2 * k : 12 + 3 * (k - 6), s0 = k < 6 ? 3 * k : 18 + 4 * (k - 6);
-            long long L[4] = { 0, 0, 0, 0 };
-            for (int j = 0; j < nl; j++) L[j] = s_acc[0][p0 + j];
-            limbs_normalize_i64(L, nl, row + s0);
-        } else if (k == 15) {
-            row[54] = (double)s_acc[0][KB_NLC - 1];
-        } else if (k == 16) {
-            row[55] = __longlong_as_double(s_acc[0][KB_NLC + 1]);
-            row[56] = s_acc[0][KB_NLC] != 0 ? 1.0 : 0.0;
-            row[57] = 0.0;
-        }
+        acc_to_row(s_acc, k, row);                         // sum k: its live limbs, then the carries
         __syncthreads();
 #ifdef PCR_SS_PROF
         unsigned long long pt_d = __builtin_amdgcn_s_memrealtime(), pt_e = pt_d;
@@ -1128,6 +1043,77 @@ __global__ __launch_bounds__(T) void icp_sums_solve_kernel(
     __syncthreads();
     if (threadIdx.x < ST_WORDS) reinterpret_cast<uint32_t*>(st_out)[threadIdx.x] = reinterpret_cast<const uint32_t*>(&s_st)[threadIdx.x];
     ss_snapshot(snap, seq, &s_st);
+}
+
+// Chain 5 (icp.cpp): the sums ALONE.  The front half of icp_sums_solve_kernel, unchanged — same loads, same gate, same limbs, same
+// butterfly, the same 42 atomics into replica blockIdx.x & (R - 1) — and nothing behind it: no release, no ticket, no acquire, no last arriver.  The
+// reduce and the solve are the NEXT launch's: every workgroup of the moving search (nn1_sphere.hpp, SV) or, behind the last iteration of a call,
+// icp_finish_kernel below reads the rows for itself (icp_finish.hpp finish_iteration) — a kernel boundary of the stream stands between these adds and
+// those loads.  There are TWO sets of rows: iteration k adds into set k & 1 (acc), and its last workgroup stores zeros over the other set (acc_next):
+// that one's last readers were the workgroups of the search in front of this launch, its next writer is the sums launch behind the next search.  Both
+// sets are all zero between calls (the finishing launch zeroes the one it read).  st_in is the state the preceding search published (the upload in
+// front of the first): a stopped loop, or one behind its last transform, adds nothing — but still zeroes.
+template <int T, int PP>
+__global__ __launch_bounds__(T) void icp_sums_kernel(
+    const float* __restrict__ tx, const float* __restrict__ ty, const float* __restrict__ tz, const uint32_t* __restrict__ orig,
+    const unsigned long long* __restrict__ keys, uint32_t nt, float max_corr, KabschPlan plan, long long* acc, long long* acc_next,
+    const IcpState* __restrict__ st_in, const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ z, uint32_t n, uint32_t np
+#ifdef PCR_SS_PROF
+    , unsigned long long* prof
+#endif
+    )
+{
+    constexpr int WAVES = T / 64;
+    static_assert((unsigned long long)T * PP * (1ull << num::KB_W) <= (1ull << 53), "a workgroup's limb totals must be exact in f64");
+    __shared__ double red_l[WAVES][KB_NL];
+    __shared__ double row[KB_ROW];
+    __shared__ IcpState s_st;
+#ifdef PCR_SS_PROF
+    const unsigned long long pt_a = __builtin_amdgcn_s_memrealtime();
+#endif
+    const uint32_t i = blockIdx.x * T + threadIdx.x;
+    uint32_t stw = 0;                       // (the state first: it is on the critical path and loads retire in order)
+    if (threadIdx.x < ST_WORDS) stw = reinterpret_cast<const uint32_t*>(st_in)[threadIdx.x];
+    FsPairs<PP> P;
+    fs_load_pairs<PP>(P, i < np, i, n, x, y, z, keys, orig, tx, ty, tz, nt);
+    if (threadIdx.x < ST_WORDS) reinterpret_cast<uint32_t*>(&s_st)[threadIdx.x] = stw;
+    if (blockIdx.x == gridDim.x - 1)
+        for (int t = threadIdx.x; t < ACC_R * ACC_W; t += T) __hip_atomic_store(acc_next + t, 0ll, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __syncthreads();
+    if (s_st.stop || s_st.barrier_timeout || s_st.stop_after_transform) return;       // uniform over the GRID
+    fs_pairs_row<PP, WAVES>(P, max_corr, plan, nt, red_l, row);
+    if (threadIdx.x < 64) {
+#ifdef PCR_SS_PROF
+        const unsigned long long pt_b = __builtin_amdgcn_s_memrealtime();
+#endif
+        long long* mine = acc + (size_t)(blockIdx.x & (ACC_R - 1)) * ACC_W;
+        const int l = threadIdx.x;
+        if (l < KB_NLC) __hip_atomic_fetch_add(mine + l, (long long)row[live_slot(l)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        else if (l == KB_NLC) __hip_atomic_fetch_add(mine + l, row[56] != 0.0 ? 1ll : 0ll, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        else if (l == KB_NLC + 1)
+            __hip_atomic_fetch_max(reinterpret_cast<unsigned long long*>(mine + l), (unsigned long long)__double_as_longlong(row[55]), __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_AGENT);
+#ifdef PCR_SS_PROF
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const unsigned long long pt_c = __builtin_amdgcn_s_memrealtime();
+        if (prof && threadIdx.x == 0) { atomicAdd(prof + 12, pt_b - pt_a); atomicAdd(prof + 13, pt_c - pt_b); atomicAdd(prof + 14, 1ull); atomicMax(prof + 15, pt_c - pt_b); }
+#endif
+    }
+}
+
+// ... and the finishing launch of a call on that chain, ONE wave behind the last sums launch: the iteration's back half (finish_iteration), published to
+// st_out, out and — where the host handed one on — slot [RING] of its ring; then zeros over the set it read.  In the stopped phases it only forwards the
+// stopped state (and zeroes all the same: the set is zero already, and stays so whatever happened in front)
+__global__ __launch_bounds__(64) void icp_finish_kernel(long long* acc, int e, const IcpState* __restrict__ st_in, IcpState* __restrict__ st_out,
+                                                        double* __restrict__ out, IcpSnapSlot* snap, unsigned long long seq)
+{
+    __shared__ IcpFinishLds F;
+    const int l = threadIdx.x;
+    IcpFinishLoads Q;
+    finish_request(l, st_in, acc, Q);
+    const bool stepped = finish_iteration(l, Q, e, F);
+    for (int t = l; t < ACC_R * ACC_W; t += 64) __hip_atomic_store(acc + t, 0ll, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // (lane l behind its own loads of these words)
+    finish_publish(l, stepped, F, st_out, out, snap, seq);
 }
 
 // multi rank, step 1: reduce the block rows into the all-reduce buffer
@@ -1309,15 +1295,18 @@ int launch_icp_sums_update_move(pcr_ctx* ctx, const pcr_cloud* tgt, pcr_cloud* c
 // geometry of the sums + solve launch: threads per workgroup (tune icp_sums_solve_threads: 256 / 512) and consecutive pairs per thread (tune
 // icp_sums_solve_pairs: 1 / 2 / 4); any other value is the default (profiles/icp_sums_accumulators.txt)
 constexpr int SS_THREADS_DEFAULT = 512, SS_PAIRS_DEFAULT = 2;
-static int ss_threads(const pcr_ctx* ctx)
+// ... and of the sums launch of the chain sums -> search, behind the same tunes: nobody queues at a ticket there, so more and smaller workgroups pay
+// (profiles/icp_solve_in_search.txt section 5: 256 x 2 = 235 workgroups at 120 k)
+constexpr int SA_THREADS_DEFAULT = 256, SA_PAIRS_DEFAULT = 2;
+static int ss_threads(const pcr_ctx* ctx, int dflt = SS_THREADS_DEFAULT)
 {
-    const int64_t t = tune_get(ctx, "icp_sums_solve_threads", SS_THREADS_DEFAULT);
-    return t == 256 ? 256 : t == 512 ? 512 : SS_THREADS_DEFAULT;
+    const int64_t t = tune_get(ctx, "icp_sums_solve_threads", dflt);
+    return t == 256 ? 256 : t == 512 ? 512 : dflt;
 }
-static int ss_pairs(const pcr_ctx* ctx)
+static int ss_pairs(const pcr_ctx* ctx, int dflt = SS_PAIRS_DEFAULT)
 {
-    const int64_t p = tune_get(ctx, "icp_sums_solve_pairs", SS_PAIRS_DEFAULT);
-    return p == 1 ? 1 : p == 2 ? 2 : p == 4 ? 4 : SS_PAIRS_DEFAULT;
+    const int64_t p = tune_get(ctx, "icp_sums_solve_pairs", dflt);
+    return p == 1 ? 1 : p == 2 ? 2 : p == 4 ? 4 : dflt;
 }
 
 // the workgroups the sums + solve launch takes for n points, or 0 where it does not run: the switch and the lower bound of the fused sums + move launch
@@ -1346,8 +1335,9 @@ int launch_icp_sums_solve(pcr_ctx* ctx, const pcr_cloud* tgt, const pcr_cloud* c
     const uint32_t blocks = icp_sums_solve_blocks(ctx, c->n);
     if (!blocks || !ctx->icp_barrier_dev || !ctx->icp_acc_dev) return fail(ctx, PCR_ERR_STATE, "launch_icp_sums_solve");
     if (ctx->icp_acc_dirty) {
-        // a call that ended in an error may have left sums behind: clear them once, in front of this call's first launch (a clean call adds nothing here)
-        PCR_HIP(ctx, hipMemsetAsync(ctx->icp_acc_dev, 0, (size_t)ICP_ACC_REPLICAS * ICP_ACC_WORDS * sizeof(long long), ctx->stream));
+        // a call that ended in an error may have left sums behind: clear them once, in front of this call's first launch (a clean call adds nothing here);
+        // both sets — this launch uses set 0 alone, the chain sums -> search (launch_icp_sums) both
+        PCR_HIP(ctx, hipMemsetAsync(ctx->icp_acc_dev, 0, (size_t)ICP_ACC_SETS * ICP_ACC_REPLICAS * ICP_ACC_WORDS * sizeof(long long), ctx->stream));
         ctx->icp_acc_dirty = false;
     }
     const int T = ss_threads(ctx), PP = ss_pairs(ctx), levels = ss_levels(ctx);
@@ -1374,6 +1364,53 @@ int launch_icp_sums_solve(pcr_ctx* ctx, const pcr_cloud* tgt, const pcr_cloud* c
     }
     PCR_HIP(ctx, hipGetLastError());
     ctx->icp_barrier_arrived = target;        // (counted only once the launch is on the stream)
+    return PCR_OK;
+}
+
+// chain 5: the sums of one iteration into accumulator set `set`, zeros over the other one (icp_sums_kernel); the geometry and its tunes are those of
+// the sums + solve launch
+int launch_icp_sums(pcr_ctx* ctx, const pcr_cloud* tgt, const pcr_cloud* c, float max_corr, const IcpState* st_in, const KabschPlan& plan, int set)
+{
+    if (ctx->keys_n != c->n) return fail(ctx, PCR_ERR_STATE, "kabsch: no matching correspondence pass");
+    if (!icp_sums_solve_blocks(ctx, c->n) || !ctx->icp_acc_dev || (set != 0 && set != 1)) return fail(ctx, PCR_ERR_STATE, "launch_icp_sums");
+    if (ctx->icp_acc_dirty) {
+        // a call that ended in an error may have left sums behind: clear both sets once, in front of this call's first launch
+        PCR_HIP(ctx, hipMemsetAsync(ctx->icp_acc_dev, 0, (size_t)ICP_ACC_SETS * ICP_ACC_REPLICAS * ICP_ACC_WORDS * sizeof(long long), ctx->stream));
+        ctx->icp_acc_dirty = false;
+    }
+    const int T = ss_threads(ctx, SA_THREADS_DEFAULT), PP = ss_pairs(ctx, SA_PAIRS_DEFAULT);
+    const uint32_t np = (uint32_t)((c->n + PP - 1) / PP), blocks = (np + (uint32_t)T - 1) / (uint32_t)T;
+    long long* const acc = ctx->icp_acc_dev + (size_t)set * ICP_ACC_REPLICAS * ICP_ACC_WORDS;
+    long long* const acc_next = ctx->icp_acc_dev + (size_t)(set ^ 1) * ICP_ACC_REPLICAS * ICP_ACC_WORDS;
+    {
+        ProfScope p(ctx, "icp_update");
+#ifdef PCR_SS_PROF
+#define PCR_SS_EXTRA , ctx->grid_stats_dev
+#else
+#define PCR_SS_EXTRA
+#endif
+#define PCR_SA(T, PP)                                                                                                                        \
+        hipLaunchKernelGGL((icp_sums_kernel<T, PP>), dim3(blocks), dim3(T), 0, ctx->stream, tgt->x(), tgt->y(), tgt->z(), c->orig, ctx->keys, \
+                           (uint32_t)tgt->n, max_corr, plan, acc, acc_next, st_in, c->x(), c->y(), c->z(), (uint32_t)c->n, np PCR_SS_EXTRA)
+        if (T == 256) { if (PP == 1) PCR_SA(256, 1); else if (PP == 2) PCR_SA(256, 2); else PCR_SA(256, 4); }
+        else { if (PP == 1) PCR_SA(512, 1); else if (PP == 2) PCR_SA(512, 2); else PCR_SA(512, 4); }
+#undef PCR_SA
+#undef PCR_SS_EXTRA
+    }
+    PCR_HIP(ctx, hipGetLastError());
+    return PCR_OK;
+}
+
+// chain 5: the finishing launch of a call, behind its last sums launch (icp_finish_kernel): set = the set that launch added into
+int launch_icp_finish(pcr_ctx* ctx, const IcpState* st_in, IcpState* st_out, const KabschPlan& plan, int set, IcpSnapSlot* snap, unsigned long long seq)
+{
+    if (!ctx->icp_acc_dev || (set != 0 && set != 1)) return fail(ctx, PCR_ERR_STATE, "launch_icp_finish");
+    {
+        ProfScope p(ctx, "icp_finish");
+        hipLaunchKernelGGL(icp_finish_kernel, dim3(1), dim3(64), 0, ctx->stream, ctx->icp_acc_dev + (size_t)set * ICP_ACC_REPLICAS * ICP_ACC_WORDS, plan.e,
+                           st_in, st_out, ctx->dev_out, snap, seq);
+    }
+    PCR_HIP(ctx, hipGetLastError());
     return PCR_OK;
 }
 

@@ -26,6 +26,7 @@
 //    "min d2, then lowest index" exactly and independently of arrival order.
 // The kernel is VALU-bound: 9 algorithmic lane-ops per (query, target) pair.
 #include "grid_common.hpp"
+#include "icp_finish.hpp"
 
 #include <algorithm>
 #include <cfloat>
@@ -1300,6 +1301,9 @@ static int launch_matrix(pcr_ctx* ctx, const pcr_cloud* tgt, const pcr_cloud* sr
     // previous correspondences on the way — nothing to seed in front of it.  It is STRACK3's move-carrying form or an error, never another kernel
     const IcpState* const move_state = ctx->nn1_move_state;
     if (move_state) pre_seeded = true;
+    // ... and on the chain sums -> search it finishes the previous iteration first: the same form with the solve in its prologue
+    const IcpSolveArgs* const solve = ctx->nn1_solve;
+    if (solve && !move_state) return fail(ctx, PCR_ERR_STATE, "nn1: a search that finishes an iteration must carry its move");
     // query groups (of 32) per wave: four amortise the per-tile operand loads best on a full batch; a source shard of a strong-scaling run
     // (15-30 k queries against the whole target) fills the chip better with two — measured, per ICP iteration: 15 k queries 0.158 -> 0.137
     // ms, 30 k 0.241 -> 0.218, 60 k 0.378 / 0.375, 120 k 0.664 -> 0.723
@@ -1402,9 +1406,15 @@ static int launch_matrix(pcr_ctx* ctx, const pcr_cloud* tgt, const pcr_cloud* sr
     hipLaunchKernelGGL((nn1_strack3_move_kernel<Q>), grid3, dim3(NN_BLOCK), 0, ctx->stream, g->l0_centres, g->l0_ops, g->l1_centres, g->l1_ops, g->l1_rec_ops, g->records,  \
                        n_super * BT_SUPER, n_l0, l0ps, src->x(), src->y(), src->z(), (uint32_t)ns, ctx->keys, stats_dev, std::min<uint32_t>(st_flush_at, (uint32_t)S2_CAP), s3_flush_end, \
                        S3Move{ move_state, tgt->x(), tgt->y(), tgt->z(), (uint32_t)tgt->n })
-            if (move_state) { if (qg3 == 1) PCR_STRACK3_MOVE(1); else if (qg3 == 2) PCR_STRACK3_MOVE(2); else PCR_STRACK3_MOVE(4); ctx->nn1_moved = true; }
+#define PCR_STRACK3_SOLVE_MOVE(Q)                                                                                                          \
+    hipLaunchKernelGGL((nn1_strack3_solve_move_kernel<Q>), grid3, dim3(NN_BLOCK), 0, ctx->stream, g->l0_centres, g->l0_ops, g->l1_centres, g->l1_ops, g->l1_rec_ops, g->records,  \
+                       n_super * BT_SUPER, n_l0, l0ps, src->x(), src->y(), src->z(), (uint32_t)ns, ctx->keys, stats_dev, std::min<uint32_t>(st_flush_at, (uint32_t)S2_CAP), s3_flush_end, \
+                       S3Move{ move_state, tgt->x(), tgt->y(), tgt->z(), (uint32_t)tgt->n }, *solve)
+            if (move_state && solve) { if (qg3 == 1) PCR_STRACK3_SOLVE_MOVE(1); else if (qg3 == 2) PCR_STRACK3_SOLVE_MOVE(2); else PCR_STRACK3_SOLVE_MOVE(4); ctx->nn1_moved = true; }
+            else if (move_state) { if (qg3 == 1) PCR_STRACK3_MOVE(1); else if (qg3 == 2) PCR_STRACK3_MOVE(2); else PCR_STRACK3_MOVE(4); ctx->nn1_moved = true; }
             else if (s3_tr == 2) { if (qg3 == 1) PCR_STRACK3_ROWS(1); else if (qg3 == 2) PCR_STRACK3_ROWS(2); else PCR_STRACK3_ROWS(4); }
             else if (qg3 == 1) PCR_STRACK3(1); else if (qg3 == 2) PCR_STRACK3(2); else PCR_STRACK3(4);
+#undef PCR_STRACK3_SOLVE_MOVE
 #undef PCR_STRACK3_MOVE
 #undef PCR_STRACK3_ROWS
 #undef PCR_STRACK3

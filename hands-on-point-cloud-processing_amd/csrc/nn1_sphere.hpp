@@ -75,6 +75,9 @@ __device__ __forceinline__ uint32_t s2_or16(const f32x16 acc)
 #ifndef PCR_S2_WAVES
 #define PCR_S2_WAVES 4
 #endif
+#ifndef PCR_SV_SOLVER_SHIFT
+#define PCR_SV_SOLVER_SHIFT 0                 // SV: wave (blockIdx.x >> shift) & 3 of a workgroup finishes the iteration (A/B builds; a matter of speed only)
+#endif
 // ---- the kernel.  (Measured on the two-level predecessor, sorted queries, 120 000 x 120 000, profile build: 86 % of a wave's life went into level 1 —
 // every chunk row of the target for every group of queries, 300 SIMD cycles per level-1 tile — and 10 % into level 2 and the exact evaluation.  With
 // level 0 a wave looks at 8 level-0 tiles, then only at the level-1 tiles whose sphere some query's ball reaches: a few of 240.)
@@ -159,18 +162,29 @@ struct S3Move {
 template <bool MV> struct S3Src { typedef const float* __restrict__ ptr; };
 template <> struct S3Src<true> { typedef float* ptr; };        // (read and written in place)
 
-template <int QG, bool TR, bool MV>
+// SV (with MV; chain 5 of the loop): the search that FINISHES the previous iteration before it moves.  mv.st is then that iteration's INPUT
+// state, and the sums of the iteration lie complete in sv.acc since an earlier launch (kabsch.hip icp_sums_kernel).  Every lane requests what the MV
+// prologue requests — its point and key, then the previous winner's target point: none of it depends on the solve — and then ONE wave of the workgroup
+// runs icp_finish.hpp's finish_iteration into LDS; behind a workgroup barrier every lane takes Rd, td and the stop flags from there and goes on as MV
+// does, with the same move and seed expressions.  Every workgroup computes the same state from the same inputs; workgroup 0 alone writes it out (state
+// slot, sums, the host's ring slot).  The surplus waves of the last workgroup stay for the barrier.  The solving wave is blockIdx.x & 3 — a matter of speed only:
+// the four workgroups of a CU should not all solve on one SIMD.  Measured (profiles/icp_solve_in_search.txt section 5): (blockIdx.x >> 8) & 3, which
+// supposes that workgroups b, b + 256, ... share a CU, is the SLOWEST of the four rules tried, 2 us per iteration behind this one; always wave 0 and
+// (blockIdx.x >> 3) & 3 lie 0.3 - 1 us behind it.
+template <int QG, bool TR, bool MV, bool SV = false>
 __device__ __forceinline__ void nn1_strack3_body(
     const float4* __restrict__ l0_centres, const uint4* __restrict__ l0_ops, const float4* __restrict__ l1_centres, const uint4* __restrict__ l1_ops,
     const uint4* __restrict__ ops, const float4* __restrict__ records, uint32_t n_rec, uint32_t n_l0, uint32_t l0_per_slice,
     typename S3Src<MV>::ptr sx, typename S3Src<MV>::ptr sy, typename S3Src<MV>::ptr sz, uint32_t ns,
-    unsigned long long* __restrict__ keys, const int* __restrict__ stop, unsigned long long* __restrict__ stats, uint32_t flush_at, uint32_t flush_end, const S3Move mv)
+    unsigned long long* __restrict__ keys, const int* __restrict__ stop, unsigned long long* __restrict__ stats, uint32_t flush_at, uint32_t flush_end, const S3Move mv,
+    const IcpSolveArgs sv = IcpSolveArgs{})
 {
     static_assert(QG == 4 || QG == 2 || QG == 1, "query groups per wave: pairs (a lane owns query n of the groups 2 p + h) or ONE (both half-lanes own query n)");
+    static_assert(MV || !SV, "the search that finishes an iteration is a moving search");
     constexpr int NP = QG == 1 ? 1 : QG / 2;
-    const int stopv = MV ? (mv.st->stop | mv.st->stop_after_transform) : stop ? (stop[0] | stop[1]) : 0;
+    int stopv = SV ? 0 : MV ? (mv.st->stop | mv.st->stop_after_transform) : stop ? (stop[0] | stop[1]) : 0;
     float mr[9] = {}, mt[3] = {};                             // (MV: the pending move, requested with the stop flags)
-    if (MV) {
+    if (MV && !SV) {
 #pragma unroll
         for (int k = 0; k < 9; k++) mr[k] = mv.st->Rd[k];
 #pragma unroll
@@ -184,43 +198,110 @@ __device__ __forceinline__ void nn1_strack3_body(
     __shared__ S3WaveLds<QG, !SW> lds_all[NN_BLOCK / 64];
     S3WaveLds<QG, !SW>& L = lds_all[wave];
     const uint32_t qbase = (qb * (NN_BLOCK / 64) + wave) * (32 * QG);
-    if (qbase >= ns) return;                                  // (a surplus wave: no workgroup barrier below)
+    if (!SV && qbase >= ns) return;                           // (a surplus wave: no workgroup barrier below — SV: it leaves behind its barrier)
     float qx[NP], qy[NP], qz[NP], thr[NP];
     bool ok[NP];
     bool okg[QG];
     auto slot_of = [&](int p) { return QG == 1 ? n : (uint32_t)(2 * p + (h ? 1 : 0)) * 32 + n; };
-#pragma unroll
-    for (int p = 0; p < NP; p++) {
-        const uint32_t slot = slot_of(p), i = min(qbase + slot, ns - 1);
+    unsigned long long k0[NP];
+    float ux[NP], uy[NP], uz[NP];
+    // the prologue's loads of pair p: the point and the candidate (or what other slices published) ...
+    auto load_query = [&](int p) {
+        const uint32_t i = min(qbase + slot_of(p), ns - 1);
         qx[p] = sx[i]; qy[p] = sy[i]; qz[p] = sz[i];
-        unsigned long long k0 = __atomic_load_n(&keys[i], __ATOMIC_RELAXED);                     // the candidate (or what other slices published)
-        if constexpr (MV) if (!stopv) {
-            const uint32_t j = (uint32_t)(k0 & 0xFFFFFFFFull);
-            float ux = 0.0f, uy = 0.0f, uz = 0.0f;
-            if (j < mv.nt) { ux = mv.tx[j]; uy = mv.ty[j]; uz = mv.tz[j]; }
-            const float x = qx[p], y = qy[p], z = qz[p];
-            qx[p] = ((mr[0] * x + mr[1] * y) + mr[2] * z) + mt[0];                               // transform_state_kernel's PCR_ROW, term for term
-            qy[p] = ((mr[3] * x + mr[4] * y) + mr[5] * z) + mt[1];
-            qz[p] = ((mr[6] * x + mr[7] * y) + mr[8] * z) + mt[2];
-            k0 = ~0ull;
-            if (j < mv.nt) {
-                const float dx = qx[p] - ux, dy = qy[p] - uy, dz = qz[p] - uz;
-                const uint32_t e = __float_as_uint((dx * dx + dy * dy) + dz * dz);               // A1, unfused: seed_next_search's arithmetic
-                if (e < 0x7F7FFFFFu) k0 = ((unsigned long long)e << 32) | j;                      // FLT_MAX gate
-            }
-            if ((QG > 1 || !h) && qbase + slot < ns) { sx[i] = qx[p]; sy[i] = qy[p]; sz[i] = qz[p]; }      // (the slot's one owner; lanes past ns read point ns - 1 and store nothing)
+        k0[p] = __atomic_load_n(&keys[i], __ATOMIC_RELAXED);
+    };
+    // ... MV: the previous winner's target point ...
+    auto gather_target = [&](int p) {
+        const uint32_t j = (uint32_t)(k0[p] & 0xFFFFFFFFull);
+        ux[p] = 0.0f; uy[p] = 0.0f; uz[p] = 0.0f;
+        if (j < mv.nt) { ux[p] = mv.tx[j]; uy[p] = mv.ty[j]; uz[p] = mv.tz[j]; }
+    };
+    // ... MV: the move, the seed of THIS search and the owner's store of the moved point
+    auto move_and_seed = [&](int p) {
+        const uint32_t slot = slot_of(p), i = min(qbase + slot, ns - 1);
+        const uint32_t j = (uint32_t)(k0[p] & 0xFFFFFFFFull);
+        const float x = qx[p], y = qy[p], z = qz[p];
+        qx[p] = ((mr[0] * x + mr[1] * y) + mr[2] * z) + mt[0];                               // transform_state_kernel's PCR_ROW, term for term
+        qy[p] = ((mr[3] * x + mr[4] * y) + mr[5] * z) + mt[1];
+        qz[p] = ((mr[6] * x + mr[7] * y) + mr[8] * z) + mt[2];
+        k0[p] = ~0ull;
+        if (j < mv.nt) {
+            const float dx = qx[p] - ux[p], dy = qy[p] - uy[p], dz = qz[p] - uz[p];
+            const uint32_t e = __float_as_uint((dx * dx + dy * dy) + dz * dz);               // A1, unfused: seed_next_search's arithmetic
+            if (e < 0x7F7FFFFFu) k0[p] = ((unsigned long long)e << 32) | j;                   // FLT_MAX gate
         }
-        const uint32_t cb = (uint32_t)(k0 >> 32);
+        if constexpr (MV) if ((QG > 1 || !h) && qbase + slot < ns) { sx[i] = qx[p]; sy[i] = qy[p]; sz[i] = qz[p]; }      // (the slot's one owner; lanes past ns read point ns - 1 and store nothing)
+    };
+    auto stage_query = [&](int p) {
+        const uint32_t slot = slot_of(p);
+        const uint32_t cb = (uint32_t)(k0[p] >> 32);
         ok[p] = fabsf(qx[p]) < 1e18f && fabsf(qy[p]) < 1e18f && fabsf(qz[p]) < 1e18f && cb < 0x7F7FFFFFu;
         thr[p] = ok[p] ? __uint_as_float(cb) : -INFINITY;
         L.q[slot] = make_float4(qx[p], qy[p], qz[p], 0.0f);
-        L.best[slot] = MV ? k0 : ~0ull;
+        L.best[slot] = MV ? k0[p] : ~0ull;
         if (!ok[p]) { qx[p] = 0.0f; qy[p] = 0.0f; qz[p] = 0.0f; }                                // (finite operands; thr = -inf: no flag, ever)
         const unsigned long long okm = __builtin_amdgcn_ballot_w64(ok[p]);
         okg[QG == 1 ? 0 : 2 * p] = (uint32_t)okm == 0xFFFFFFFFu;
         if (QG > 1) okg[QG == 1 ? 0 : 2 * p + 1] = (uint32_t)(okm >> 32) == 0xFFFFFFFFu;
+    };
+#ifdef PCR_SV_PROF
+    // profile build (stats != nullptr: tune grid_stats = 1): the solving wave of workgroup 1 stamps its prologue, 10 ns ticks into words 11 .. 15 of the
+    // diagnostics — entry -> loads requested -> replicas in LDS -> solved -> barrier passed -> prologue done (the first level-0 set-up follows)
+    unsigned long long pv_entry = __builtin_amdgcn_s_memrealtime(), pv_loads = 0, pv_replicas = 0, pv_solved = 0, pv_barrier = 0;
+    bool pv_mine = false;
+#endif
+    if constexpr (SV) {
+        __shared__ IcpFinishLds F;
+        const uint32_t solver = (blockIdx.x >> PCR_SV_SOLVER_SHIFT) & (NN_BLOCK / 64 - 1);
+        IcpFinishLoads Q = {};
+        if (wave == solver) finish_request((int)lane, mv.st, sv.acc, Q);      // (first: loads retire in order, and the solve is the longer chain)
+#pragma unroll
+        for (int p = 0; p < NP; p++) load_query(p);
+#pragma unroll
+        for (int p = 0; p < NP; p++) gather_target(p);
+#ifdef PCR_SV_PROF
+        pv_mine = stats && wave == solver && blockIdx.x == min(1u, gridDim.x - 1u) && lane == 0;
+        pv_loads = __builtin_amdgcn_s_memrealtime();
+#endif
+        bool stepped = false;
+        if (wave == solver) stepped = finish_iteration((int)lane, Q, sv.e, F);
+#ifdef PCR_SV_PROF
+        pv_solved = __builtin_amdgcn_s_memrealtime();
+#endif
+        __syncthreads();
+#ifdef PCR_SV_PROF
+        pv_barrier = __builtin_amdgcn_s_memrealtime();
+        pv_replicas = F.pt_replicas;
+#endif
+        if (wave == solver && blockIdx.x == 0 && blockIdx.y == 0) finish_publish((int)lane, stepped, F, sv.st_out, sv.out, sv.snap, sv.seq);
+        stopv = F.st.stop | F.st.stop_after_transform;
+        if (qbase >= ns) return;                              // (a surplus wave)
+#pragma unroll
+        for (int k = 0; k < 9; k++) mr[k] = F.st.Rd[k];
+#pragma unroll
+        for (int k = 0; k < 3; k++) mt[k] = F.st.td[k];
+#pragma unroll
+        for (int p = 0; p < NP; p++) {
+            if (!stopv) move_and_seed(p);
+            stage_query(p);
+        }
+    }
+    else {
+#pragma unroll
+        for (int p = 0; p < NP; p++) {
+            load_query(p);
+            if constexpr (MV) if (!stopv) { gather_target(p); move_and_seed(p); }
+            stage_query(p);
+        }
     }
     if (stopv) return;
+#ifdef PCR_SV_PROF
+    if (SV && pv_mine) {
+        const unsigned long long pv_done = __builtin_amdgcn_s_memrealtime();
+        stats[11] = pv_loads - pv_entry; stats[12] = pv_replicas - pv_loads; stats[13] = pv_solved - pv_replicas; stats[14] = pv_barrier - pv_solved; stats[15] = pv_done - pv_barrier;
+    }
+#endif
 #ifdef PCR_S2_PROF
     unsigned long long* const stats_p = stats;
     stats = nullptr;
@@ -597,5 +678,16 @@ __global__ __launch_bounds__(NN_BLOCK, PCR_S2_WAVES) void nn1_strack3_move_kerne
 {
     const int* stop = nullptr;
     nn1_strack3_body<QG, true, true>(PCR_S3_ARGS, mv);
+}
+// ... and the one that finishes the previous iteration first (SV above)
+template <int QG>
+__global__ __launch_bounds__(NN_BLOCK, PCR_S2_WAVES) void nn1_strack3_solve_move_kernel(
+    const float4* __restrict__ l0_centres, const uint4* __restrict__ l0_ops, const float4* __restrict__ l1_centres, const uint4* __restrict__ l1_ops,
+    const uint4* __restrict__ ops, const float4* __restrict__ records, uint32_t n_rec, uint32_t n_l0, uint32_t l0_per_slice,
+    float* sx, float* sy, float* sz, uint32_t ns, unsigned long long* __restrict__ keys, unsigned long long* __restrict__ stats, uint32_t flush_at,
+    uint32_t flush_end, const S3Move mv, const IcpSolveArgs sv)
+{
+    const int* stop = nullptr;
+    nn1_strack3_body<QG, true, true, true>(PCR_S3_ARGS, mv, sv);
 }
 #undef PCR_S3_ARGS

@@ -22,6 +22,8 @@ constexpr size_t PAD = 1024;
 constexpr int PCR_NSTATS = 16;      // diagnostics words of a 1-NN launch (tune grid_stats; pcr_nn1_stats)
 // the accumulators of the ICP sums + solve launch (kabsch.hip): replicas (a power of two) of 48 int64 = three 128-byte lines each
 constexpr int ICP_ACC_REPLICAS = 8, ICP_ACC_WORDS = 48;
+// ... of which there are two SETS: the chain sums -> search adds iteration k into set k & 1; every other user has set 0 alone
+constexpr int ICP_ACC_SETS = 2;
 // with a ticket per replica: the workgroups of a launch of `blocks` workgroups that arrive at replica r (workgroup b belongs to replica
 // b & (R - 1)); 0 for a replica the launch does not reach, which nobody waits for
 __host__ __device__ constexpr uint32_t icp_replica_members(uint32_t blocks, uint32_t r)
@@ -63,6 +65,17 @@ struct IcpState {
 struct IcpSnapSlot {
     IcpState state;
     unsigned long long seq;
+};
+// what a moving search that also finishes the previous iteration is handed (chain 5; nn1_sphere.hpp, SV): the accumulator set that
+// iteration's sums launch added into, the state slot, the sums' 19 doubles and — null / 0 where the host wants none — the slot of the host ring and its
+// sequence number, all written by workgroup 0 alone; e = the exponent of the accumulation's fixed-point grid (KabschPlan)
+struct IcpSolveArgs {
+    const long long* acc;
+    IcpState* st_out;
+    double* out;
+    IcpSnapSlot* snap;
+    unsigned long long seq;
+    int e;
 };
 
 // fixed-point grid of one exact Kabsch accumulation (kabsch.hip / numerics.hpp): 2^e bounds every coordinate of a kept pair
@@ -202,9 +215,10 @@ struct pcr_ctx {
     // states, never reset) and the value it has once every workgroup of every launch so far has arrived
     unsigned long long* icp_barrier_dev = nullptr;
     uint64_t icp_barrier_arrived = 0;
-    // the accumulators of the sums + solve launch (kabsch.hip icp_sums_solve_kernel): ICP_ACC_REPLICAS x ICP_ACC_WORDS int64 behind the
-    // counter, zeroed with it; ALL ZERO between launches (the last arriver writes the zeros back).  dirty: a call ended in an error — the next call's
-    // first launch clears them
+    // the accumulators of the sums + solve launch (kabsch.hip icp_sums_solve_kernel): ICP_ACC_SETS sets of ICP_ACC_REPLICAS x ICP_ACC_WORDS
+    // int64 behind the counter, zeroed with it; set 0 ALL ZERO between launches of that kernel (the last arriver writes the zeros back), BOTH sets all
+    // zero between calls (the chain sums -> search alternates between them).  dirty: a call ended in an error — the next call's first
+    // launch clears both
     long long* icp_acc_dev = nullptr;
     bool icp_acc_dirty = false;
     // the pinned, coherent host ring: [0..4) snapshots, [4] upload / final state; its address as the device sees it; the last sequence number handed
@@ -220,7 +234,10 @@ struct pcr_ctx {
     // by the pending Rd, td of that state first (nn1_sphere.hpp, MV) — the exhaustive dispatcher launches the move-carrying kernel or fails.  nn1_move_l0:
     // the level-0 super-tiles of the last exhaustive search's target if it took the family that has such a form (STRACK3), else 0 — the loop asks after its
     // first search; nn1_moved: the last search WAS that form
+    // nn1_solve (with nn1_move_state, chain 5): that search also FINISHES the previous iteration first — nn1_move_state is then that
+    // iteration's input state, and the move is by the Rd, td the search works out for itself (nn1_sphere.hpp, SV)
     const pcr::IcpState* nn1_move_state = nullptr;
+    const pcr::IcpSolveArgs* nn1_solve = nullptr;
     uint64_t nn1_move_l0 = 0;
     bool nn1_moved = false;
     int icp_last_chain = 0;                    // the tail of the last ICP call's iterations (pcr_icp_last_chain)
@@ -363,12 +380,19 @@ int launch_icp_sums_update_move(pcr_ctx* ctx, const pcr_cloud* tgt, pcr_cloud* c
 uint32_t icp_sums_solve_blocks(const pcr_ctx* ctx, size_t n);
 int launch_icp_sums_solve(pcr_ctx* ctx, const pcr_cloud* tgt, const pcr_cloud* c, float max_corr, const IcpState* st_in, IcpState* st_out, const KabschPlan& plan,
                           IcpSnapSlot* snap, unsigned long long seq);
+// chain 5: the sums alone into accumulator set `set` (and zeros over the other one); the reduce and the solve are the next search's
+// (ctx->nn1_solve) or, behind the last iteration of a call, launch_icp_finish's: one wave that publishes like the sums + solve launch and zeroes its set
+int launch_icp_sums(pcr_ctx* ctx, const pcr_cloud* tgt, const pcr_cloud* c, float max_corr, const IcpState* st_in, const KabschPlan& plan, int set);
+int launch_icp_finish(pcr_ctx* ctx, const IcpState* st_in, IcpState* st_out, const KabschPlan& plan, int set, IcpSnapSlot* snap, unsigned long long seq);
 // nn1_brute.hip: can a seeded STRACK3 search of ns queries over n_l0 level-0 super-tiles carry the move (transposed form, one slice)?  Raw tune values
 uint64_t s3_l0_super_tiles(uint64_t n_tgt);          // the level-0 super-tiles the index of a target of n_tgt points has (bt_ensure_l1)
 bool s3_move_route(uint64_t n_l0, uint64_t ns, int64_t transposed_tune, int64_t qg_tune, int64_t l0_per_slice_tune, int64_t blocks_tune);
 // icp.cpp: the loop's own conditions for that chain, from plain numbers (pcr_icp_move_route)
 bool icp_move_route(uint64_t n_src, uint64_t n_l0, int nranks, int64_t move_in_search_tune, int64_t fused_sums_tune, int64_t fused_sums_min_tune,
                     int64_t transposed_tune, int64_t qg_tune, int64_t l0_per_slice_tune, int64_t blocks_tune);
+// ... and, where that chain would be taken, whether the solve moves into the next search as well (chain 5; pcr_icp_solve_route): raw values of the
+// tunes icp_solve_in_search and icp_move_in_search; auto is bounded by the source size
+bool icp_solve_route(uint64_t n_src, int64_t solve_in_search_tune, int64_t move_in_search_tune);
 int comm_allreduce_f64_device(pcr_ctx* ctx, double* dev_buf, int n);   // RCCL on the ctx stream, no host round trip
 int launch_plane_count(pcr_ctx* ctx, const pcr_cloud* pts, const double* planes4_host, size_t n_planes,
                        double thr, unsigned long long* counts_out);

@@ -134,11 +134,12 @@ int pcr_icp_p2p_f32(pcr_ctx* ctx, const pcr_cloud* src, const pcr_cloud* tgt, co
 
 /* Which tail the iterations of the last pcr_icp_p2p_f32 call on this context took (diagnostics; every chain gives the same bits):
  * 0 = the synchronous loop, no call yet, or a call that failed; 1 = sums, solve and move as launches of their own; 2 = sums -> solve + move;
- * 3 = sums + solve + move in one launch; 4 = sums + solve in one launch, the NEXT search moves the cloud (tune "icp_move_in_search"). */
+ * 3 = sums + solve + move in one launch; 4 = sums + solve in one launch, the NEXT search moves the cloud (tune "icp_move_in_search"); 5 = the sums
+ * alone in one launch, the NEXT search reduces them, solves and moves the cloud (tune "icp_solve_in_search"). */
 int pcr_icp_last_chain(const pcr_ctx* ctx);
 /* How the last pcr_icp_p2p_f32 call on this context learnt its loop's state (diagnostics; same bits either way): 0 = copies and events on the stream
  * (also: no call yet, a call that failed, the synchronous loop, a call of no iteration); 1 = written into pinned host memory by the sums + solve launch
- * itself (chain 4; tune "icp_host_snapshots": 2 = off). */
+ * itself (chain 4), or by the next chunk's first search and the call's finishing launch (chain 5); tune "icp_host_snapshots": 2 = off. */
 int pcr_icp_last_snapshots(const pcr_ctx* ctx);
 /* Host logic, no GPU: with an arrival counter per accumulator replica (tune "icp_ticket_levels": 1 = one counter, 2 = per replica), how many of the
  * `blocks` workgroups of a sums + solve launch arrive at replica `replica` (0 .. 7); 0 = the launch does not reach it and nobody waits for it. */
@@ -149,6 +150,12 @@ uint32_t pcr_icp_replica_members(uint32_t blocks, uint32_t replica);
  * must be ONE slice: it moves its queries in place).  Returns 1 or 0. */
 int pcr_icp_move_route(uint64_t n_src, uint64_t n_tgt, int nranks, int64_t move_in_search, int64_t fused_sums, int64_t fused_sums_min,
                        int64_t s3_transposed, int64_t sphere_qg, int64_t sphere_l0_per_slice, int64_t sphere_blocks);
+/* Host logic, no GPU: would that loop run chain 5 — chain 4's conditions (pcr_icp_move_route) and the tune icp_solve_in_search: 1 = on, 2 = off,
+ * 0 = auto, which holds only while icp_move_in_search is 0 as well (a caller that sets that tune to 1 keeps chain 4) and is then the library's default:
+ * on for up to pcr_icp_solve_in_search_auto() source points (0 = auto is off).  Raw tune values as above.  Returns 1 or 0. */
+int pcr_icp_solve_route(uint64_t n_src, uint64_t n_tgt, int nranks, int64_t solve_in_search, int64_t move_in_search, int64_t fused_sums,
+                        int64_t fused_sums_min, int64_t s3_transposed, int64_t sphere_qg, int64_t sphere_l0_per_slice, int64_t sphere_blocks);
+uint64_t pcr_icp_solve_in_search_auto(void);
 /* Host logic, no GPU: what the default three-level sphere kernel visits in ONE level-0 super-tile S0 (131 072 records) given its flag masks, in its
  * order.  rows[t] bit j: level 0 flagged level-1 tile T1 = (S0 * 8 + t) * 32 + j (512 records); tiles[T1 - S0 * 256] bit k: level 1 flagged level-2
  * tile T1 * 16 + k (32 records).  Tiles at or behind n_rec records (the padded size of the index) are not visited.  The visits are written as pairs
