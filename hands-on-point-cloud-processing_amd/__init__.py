@@ -107,6 +107,17 @@ class Pn2TrainInfo(C.Structure):
                 ("n_sampling", C.c_uint32), ("reserved", C.c_uint32), ("dropout_p", C.c_double), ("bn_momentum", C.c_double)]
 
 
+class OptimDesc(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("reserved0", C.c_uint32), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("weight_decay", C.c_double),
+                ("momentum", C.c_double), ("dampening", C.c_double), ("reserved", C.c_double * 4)]
+
+
+class OptimInfo(C.Structure):
+    _fields_ = [("desc", OptimDesc), ("step", C.c_uint64), ("state_bytes", C.c_uint64), ("attached", C.c_uint32), ("n_ranges", C.c_uint32)]
+
+
+OPTIM_ADAM, OPTIM_SGD = 1, 2
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_int)
 
 # every symbol include/pcr.h declares (checked by tests/test_abi.py against the header text)
@@ -129,6 +140,8 @@ ABI_SYMBOLS = [
     "pcr_pn2_trainer_create", "pcr_pn2_trainer_destroy", "pcr_pn2_trainer_info", "pcr_pn2_trainer_set_weights", "pcr_pn2_trainer_get_weights", "pcr_pn2_train_grad_f32",
     "pcr_pn1_trainer_create", "pcr_pointnet_train_grad_f32",
     "pcr_pn2_msg_trainer_create", "pcr_pn2_msg_trainer_info",
+    "pcr_pn2_trainer_optim_set", "pcr_pn2_trainer_optim_step", "pcr_pn2_trainer_optim_info", "pcr_pn2_trainer_optim_get_state", "pcr_pn2_trainer_optim_set_state",
+    "pcr_pn2_train_step_f32", "pcr_pointnet_train_step_f32", "pcr_pn2_trainer_get_grad",
     "pcr_mat64_create", "pcr_mat64_destroy", "pcr_mat64_info", "pcr_kmeans_step_f64", "pcr_kmeans_fit_f64", "pcr_kmeans_predict_f64", "pcr_kmeanspp_init_f64",
     "pcr_gmm_em_step_f64", "pcr_gmm_fit_f64", "pcr_gmm_predict_f64",
     "pcr_mat64_knn_f64", "pcr_spectral_graph_f64", "pcr_spgraph_info", "pcr_spgraph_read", "pcr_spgraph_destroy", "pcr_eig_small_f64",
@@ -269,6 +282,14 @@ def lib():
     L.pcr_pn2_train_grad_f32.argtypes = [vp, vp, vp, sz, sz, vp, vp, C.c_uint64, vp, C.POINTER(C.c_double), vp, vp]
     L.pcr_pn1_trainer_create.argtypes = [vp, C.POINTER(Pn1Desc), vp, sz, C.c_double, C.c_double, C.c_double, C.c_uint32, C.POINTER(vp)]
     L.pcr_pointnet_train_grad_f32.argtypes = [vp, vp, vp, sz, sz, vp, C.c_uint64, vp, C.POINTER(C.c_double), vp, vp, vp, vp]
+    L.pcr_pn2_trainer_optim_set.argtypes = [vp, vp, C.POINTER(OptimDesc)]
+    L.pcr_pn2_trainer_optim_step.argtypes = [vp, vp, C.c_double]
+    L.pcr_pn2_trainer_optim_info.argtypes = [vp, C.POINTER(OptimInfo)]
+    L.pcr_pn2_trainer_optim_get_state.argtypes = [vp, vp, C.POINTER(C.c_uint64), vp, vp, sz]
+    L.pcr_pn2_trainer_optim_set_state.argtypes = [vp, vp, C.c_uint64, vp, vp, sz]
+    L.pcr_pn2_trainer_get_grad.argtypes = [vp, vp, vp, sz]
+    L.pcr_pn2_train_step_f32.argtypes = [vp, vp, vp, sz, sz, vp, vp, C.c_uint64, vp, C.c_double, C.POINTER(C.c_double), vp, vp]
+    L.pcr_pointnet_train_step_f32.argtypes = [vp, vp, vp, sz, sz, vp, C.c_uint64, vp, C.c_double, C.POINTER(C.c_double), vp, vp, vp, vp]
     L.pcr_mat64_create.argtypes = [vp, vp, sz, C.c_int, C.POINTER(vp)]
     L.pcr_mat64_destroy.argtypes = [vp, vp]
     L.pcr_mat64_info.argtypes = [vp, C.POINTER(sz), ip, ip]
@@ -722,6 +743,14 @@ class Pn2Trainer:
         """objects f32 [n_obj, npts, 3 + D0], target int [n_obj] -> (loss float, logp f32 [n_obj, n_class], grad f32 [n_weights]); the contract
         of pcr_pn2_train_grad_f32.  starts: [n_sampling_layers, n_obj] first picks, None = drawn from the seed; keep: the dropout masks as
         bytes, [n_obj * keep_per_object] layer after layer, None = drawn from the seed."""
+        return self._train(objects, target, starts, seed, keep, None, True)
+
+    def train_step(self, objects, target, lr: float, starts=None, seed: int = 0, keep=None, want_grad: bool = False):
+        """train_grad's pass, then the attached optimiser's update at `lr` on the device (pcr_pn2_train_step_f32) -> (loss, logp, grad or None):
+        the gradient crosses the bus only with want_grad"""
+        return self._train(objects, target, starts, seed, keep, float(lr), want_grad)
+
+    def _train(self, objects, target, starts, seed, keep, lr, want_grad):
         obj = np.ascontiguousarray(objects, np.float32)
         if obj.ndim != 3 or obj.shape[2] != 3 + int(self.desc.D0):
             raise PcrError("objects: [n_obj, npts, 3 + D0]")
@@ -742,11 +771,59 @@ class Pn2Trainer:
                 raise PcrError("keep: one byte per object and unit of every FC layer but the last")
         loss = C.c_double(0.0)
         logp = np.zeros((max(n_obj, 1), inf["n_class"]), np.float32)
-        grad = np.zeros(inf["n_weights"], np.float32)
-        self.ctx._ck(lib().pcr_pn2_train_grad_f32(self.ctx.h, self.h, obj.ctypes.data if obj.size else None, n_obj, npts, tg.ctypes.data if tg.size else None,
-                                                  None if st is None or not st.size else st.ctypes.data, int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                                  None if kp is None or not kp.size else kp.ctypes.data, C.byref(loss), logp.ctypes.data, grad.ctypes.data))
+        grad = np.zeros(inf["n_weights"], np.float32) if want_grad else None
+        head = (self.ctx.h, self.h, obj.ctypes.data if obj.size else None, n_obj, npts, tg.ctypes.data if tg.size else None,
+                None if st is None or not st.size else st.ctypes.data, int(seed) & 0xFFFFFFFFFFFFFFFF, None if kp is None or not kp.size else kp.ctypes.data)
+        tail = (C.byref(loss), logp.ctypes.data, None if grad is None else grad.ctypes.data)
+        if lr is None:
+            self.ctx._ck(lib().pcr_pn2_train_grad_f32(*head, *tail))
+        else:
+            self.ctx._ck(lib().pcr_pn2_train_step_f32(*head, lr, *tail))
         return float(loss.value), logp[:n_obj], grad
+
+    # ---- the optimiser on the device (the contract is above pcr_pn2_trainer_optim_set in include/pcr.h)
+    def optim_set(self, kind=None, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0, momentum: float = 0.0, dampening: float = 0.0):
+        """attach or replace the optimiser (kind "Adam" / "SGD" or OPTIM_ADAM / OPTIM_SGD; state zeroed, step count 0); kind None detaches it"""
+        if kind is None:
+            self.ctx._ck(lib().pcr_pn2_trainer_optim_set(self.ctx.h, self.h, None))
+            return
+        d = OptimDesc()
+        d.kind = {"adam": OPTIM_ADAM, "sgd": OPTIM_SGD}.get(kind.lower(), 0) if isinstance(kind, str) else int(kind)
+        d.beta1, d.beta2, d.eps, d.weight_decay, d.momentum, d.dampening = float(betas[0]), float(betas[1]), float(eps), float(weight_decay), float(momentum), float(dampening)
+        self.ctx._ck(lib().pcr_pn2_trainer_optim_set(self.ctx.h, self.h, C.byref(d)))
+
+    def optim_step(self, lr: float):
+        """one update from the gradient the last pass left on the device"""
+        self.ctx._ck(lib().pcr_pn2_trainer_optim_step(self.ctx.h, self.h, float(lr)))
+
+    def optim_info(self) -> dict:
+        i = OptimInfo()
+        self.ctx._ck(lib().pcr_pn2_trainer_optim_info(self.h, C.byref(i)))
+        d = i.desc
+        return {"attached": bool(i.attached), "kind": {OPTIM_ADAM: "Adam", OPTIM_SGD: "SGD"}.get(int(d.kind)), "step": int(i.step), "state_bytes": int(i.state_bytes),
+                "n_ranges": int(i.n_ranges), "betas": (float(d.beta1), float(d.beta2)), "eps": float(d.eps), "weight_decay": float(d.weight_decay),
+                "momentum": float(d.momentum), "dampening": float(d.dampening)}
+
+    def get_grad(self):
+        """the gradient the last pass left on the device (what a train_step without want_grad did not download)"""
+        g = np.zeros(self.info()["n_weights"], np.float32)
+        self.ctx._ck(lib().pcr_pn2_trainer_get_grad(self.ctx.h, self.h, g.ctypes.data, g.size))
+        return g
+
+    def optim_get_state(self):
+        """(step count, state0, state1 or None) in the weight layout: Adam's exp_avg and exp_avg_sq, SGD's momentum_buffer"""
+        n = self.info()["n_weights"]
+        adam = self.optim_info()["kind"] == "Adam"
+        step, s0, s1 = C.c_uint64(0), np.zeros(n, np.float32), np.zeros(n, np.float32) if adam else None
+        self.ctx._ck(lib().pcr_pn2_trainer_optim_get_state(self.ctx.h, self.h, C.byref(step), s0.ctypes.data, None if s1 is None else s1.ctypes.data, n))
+        return int(step.value), s0, s1
+
+    def optim_set_state(self, step: int, state0, state1=None):
+        s0 = np.ascontiguousarray(state0, np.float32).reshape(-1)
+        s1 = None if state1 is None else np.ascontiguousarray(state1, np.float32).reshape(-1)
+        if s1 is not None and s1.size != s0.size:
+            raise PcrError("state1: the size of state0")
+        self.ctx._ck(lib().pcr_pn2_trainer_optim_set_state(self.ctx.h, self.h, int(step), s0.ctypes.data if s0.size else None, None if s1 is None else s1.ctypes.data, s0.size))
 
 
 class Pn2MsgTrainer(Pn2Trainer):
@@ -799,6 +876,14 @@ class Pn1Trainer(Pn2Trainer):
         """objects f32 [n_obj, npts, 3 + D0], target int [n_obj] -> a dict: loss (the total), nll, reg (floats), logp f32 [n_obj, n_class], grad f32
         [n_weights], trans [n_obj, 3, 3] and trans_feat [n_obj, K, K] (None without the T-Net); the contract of pcr_pointnet_train_grad_f32.
         keep: the dropout mask as bytes, [n_obj, keep_per_object], None = drawn from the seed."""
+        return self._train1(objects, target, seed, keep, None, True)
+
+    def train_step(self, objects, target, lr: float, seed: int = 0, keep=None, want_grad: bool = False):
+        """train_grad's pass, then the attached optimiser's update at `lr` on the device (pcr_pointnet_train_step_f32) -> train_grad's dict, grad None
+        unless want_grad"""
+        return self._train1(objects, target, seed, keep, float(lr), want_grad)
+
+    def _train1(self, objects, target, seed, keep, lr, want_grad):
         obj = np.ascontiguousarray(objects, np.float32)
         if obj.ndim != 3 or obj.shape[2] != 3 + int(self.desc.D0):
             raise PcrError("objects: [n_obj, npts, 3 + D0]")
@@ -815,12 +900,16 @@ class Pn1Trainer(Pn2Trainer):
         K = int(self.desc.widths[0])
         loss = (C.c_double * 3)(0.0, 0.0, 0.0)
         logp = np.zeros((max(n_obj, 1), inf["n_class"]), np.float32)
-        grad = np.zeros(inf["n_weights"], np.float32)
+        grad = np.zeros(inf["n_weights"], np.float32) if want_grad else None
         trans = np.zeros((max(n_obj, 1), 3, 3), np.float32) if self.desc.stn3 else None
         tfeat = np.zeros((max(n_obj, 1), K, K), np.float32) if self.desc.fstn else None
-        self.ctx._ck(lib().pcr_pointnet_train_grad_f32(self.ctx.h, self.h, obj.ctypes.data if obj.size else None, n_obj, npts, tg.ctypes.data if tg.size else None,
-                                                       int(seed) & 0xFFFFFFFFFFFFFFFF, None if kp is None or not kp.size else kp.ctypes.data, loss, logp.ctypes.data,
-                                                       None if trans is None else trans.ctypes.data, None if tfeat is None else tfeat.ctypes.data, grad.ctypes.data))
+        head = (self.ctx.h, self.h, obj.ctypes.data if obj.size else None, n_obj, npts, tg.ctypes.data if tg.size else None, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                None if kp is None or not kp.size else kp.ctypes.data)
+        tail = (loss, logp.ctypes.data, None if trans is None else trans.ctypes.data, None if tfeat is None else tfeat.ctypes.data, None if grad is None else grad.ctypes.data)
+        if lr is None:
+            self.ctx._ck(lib().pcr_pointnet_train_grad_f32(*head, *tail))
+        else:
+            self.ctx._ck(lib().pcr_pointnet_train_step_f32(*head, lr, *tail))
         return {"loss": float(loss[0]), "nll": float(loss[1]), "reg": float(loss[2]), "logp": logp[:n_obj], "grad": grad,
                 "trans": None if trans is None else trans[:n_obj], "trans_feat": None if tfeat is None else tfeat[:n_obj]}
 

@@ -2,6 +2,7 @@
 // the gradient of every parameter (models/pointnet2_cls_ssg.py, models/pointnet2_cls_msg.py, get_loss; train_cls.py's step without its optimiser).  The
 // contracts are written out above pcr_pn2_trainer_create and pcr_pn2_msg_trainer_create in include/pcr.h.  There is ONE pass, over the superset descriptor:
 // an SSG trainer is the case of one xyz-first branch per layer and one dropout probability.
+// pcr_pn2_train_step_f32 is the same pass with the optimiser's update (pointnet_optim.hip) behind its last kernel and the gradient download optional.
 //
 // Batch statistics break the eval pass's layer fusion: the pass goes layer by layer and keeps every layer's z and y in HBM.  This file holds the model's
 // own part: its plan's sampling and per-(stage, branch) buffers, FPS / centres / ball query once per stage, then per branch the gather, the layers and the max
@@ -189,6 +190,7 @@ extern "C" int pcr_pn2_trainer_destroy(pcr_ctx* ctx, pcr_pn2_trainer* t)
     }
     if (t->w_dev) (void)hipFree(t->w_dev);
     if (t->grad_dev) (void)hipFree(t->grad_dev);
+    optim_free(t);
     delete t;
     return PCR_OK;
 }
@@ -251,14 +253,17 @@ extern "C" int pcr_pn2_trainer_get_weights(pcr_ctx* ctx, const pcr_pn2_trainer* 
     return PCR_OK;
 }
 
-extern "C" int pcr_pn2_train_grad_f32(pcr_ctx* ctx, pcr_pn2_trainer* t, const float* objects, size_t n_obj, size_t npts, const int32_t* target, const uint32_t* starts,
-                                      uint64_t seed, const uint8_t* keep, double* loss, float* logp, float* grad)
+namespace {
+
+// the pass, and behind it (step_lr) the optimiser's update: pcr_pn2_train_grad_f32 (grad wanted) and pcr_pn2_train_step_f32 (grad optional)
+int train_pass(pcr_ctx* ctx, pcr_pn2_trainer* t, const char* who, const float* objects, size_t n_obj, size_t npts, const int32_t* target, const uint32_t* starts,
+               uint64_t seed, const uint8_t* keep, double* loss, float* logp, float* grad, const double* step_lr)
 {
-    const char* who = "pcr_pn2_train_grad_f32";
     Plan P;
     std::vector<uint32_t> st0;               // the first FPS pick of every (sampling layer, object)
     bool run;
-    int rc = call_head(ctx, t, 0, who, nullptr, !objects || !target || !loss || !logp || !grad, target, n_obj, npts, P, [&]() -> const char* {
+    const char* own_bad = t && step_lr ? optim_bad(t, *step_lr) : nullptr;
+    int rc = call_head(ctx, t, 0, who, own_bad, !objects || !target || !loss || !logp || (!grad && !step_lr), target, n_obj, npts, P, [&]() -> const char* {
         if (!make_plan(t, n_obj, npts, P)) return ": too large";
         for (const Stage& st : P.stages)
             for (uint32_t b = 0; b < st.n_branch; b++)
@@ -276,7 +281,7 @@ extern "C" int pcr_pn2_train_grad_f32(pcr_ctx* ctx, pcr_pn2_trainer* t, const fl
                 st0[(size_t)l * n_obj + o] = v;
             }
         return nullptr;
-    }, run);
+    }, run, !step_lr);
     if (!run) return rc;
     const pcr_pn2_msg_desc& d = t->desc;
     const uint32_t ns = t->n_sampling, D0 = d.D0, C0 = 3 + D0, n_class = t->layers.back().N;
@@ -400,5 +405,19 @@ extern "C" int pcr_pn2_train_grad_f32(pcr_ctx* ctx, pcr_pn2_trainer* t, const fl
             }
         }
     }
-    return call_tail(ctx, t, who, R.rc, P, n_obj, logp, loss, 1, grad);      // `hold` lives until its wait is over
+    return call_tail(ctx, t, who, R.rc, P, n_obj, logp, loss, 1, grad, {}, step_lr);      // `hold` lives until its wait is over
+}
+
+}  // namespace
+
+extern "C" int pcr_pn2_train_grad_f32(pcr_ctx* ctx, pcr_pn2_trainer* t, const float* objects, size_t n_obj, size_t npts, const int32_t* target, const uint32_t* starts,
+                                      uint64_t seed, const uint8_t* keep, double* loss, float* logp, float* grad)
+{
+    return train_pass(ctx, t, "pcr_pn2_train_grad_f32", objects, n_obj, npts, target, starts, seed, keep, loss, logp, grad, nullptr);
+}
+
+extern "C" int pcr_pn2_train_step_f32(pcr_ctx* ctx, pcr_pn2_trainer* t, const float* objects, size_t n_obj, size_t npts, const int32_t* target, const uint32_t* starts,
+                                      uint64_t seed, const uint8_t* keep, double lr, double* loss, float* logp, float* grad)
+{
+    return train_pass(ctx, t, "pcr_pn2_train_step_f32", objects, n_obj, npts, target, starts, seed, keep, loss, logp, grad, &lr);
 }

@@ -307,13 +307,11 @@ bool make_plan1(const pcr_pn2_trainer* t, size_t n_obj, size_t npts, Plan1& P)
     return true;
 }
 
-const char* const WHO1 = "pcr_pointnet_train_grad_f32";
-
 // LayerRun on the blocked product, and what the T-Nets add to it
 struct ClsRun : LayerRun {
     Plan1& P;                // LayerRun's plan, with this model's fields in reach
 
-    ClsRun(pcr_ctx* c, pcr_pn2_trainer* tr, Plan1& plan) : LayerRun(c, tr, plan, WHO1, launch_gemm1, "pn1t_gemm_fwd", "pn1t_gemm_dx"), P(plan) {}
+    ClsRun(pcr_ctx* c, pcr_pn2_trainer* tr, Plan1& plan, const char* name) : LayerRun(c, tr, plan, name, launch_gemm1, "pn1t_gemm_fwd", "pn1t_gemm_dx"), P(plan) {}
 
     // a T-Net: x (rows x cin) -> its k x k matrices, identity added, in P.z[first + 5]
     void tnet_fwd(uint32_t first, const float* x, uint32_t k, float* feat, uint32_t* arg)
@@ -356,7 +354,7 @@ struct ClsRun : LayerRun {
         g.a = x; g.b = cur; g.init = nullptr; g.c = nxt;
         g.M = k; g.N = k; g.Kt = P.rows; g.chunk = P.npts;
         g.sai = 1; g.sak = width; g.sbk = width; g.sbj = 1; g.c_stride = (size_t)k * k;
-        rc = launch_gemm(ctx, "pn1t_gemm_dt", g, WHO1);
+        rc = launch_gemm(ctx, "pn1t_gemm_dt", g, who);
     }
 
     void transform(const float* x, const float* T, uint32_t K, bool transposed, float* y)
@@ -410,15 +408,18 @@ extern "C" int pcr_pn1_trainer_create(pcr_ctx* ctx, const pcr_pn1_desc* desc, co
                           PCR_PN2_MAX_FC, bn_momentum, chunk_rows, out);
 }
 
-extern "C" int pcr_pointnet_train_grad_f32(pcr_ctx* ctx, pcr_pn2_trainer* t, const float* objects, size_t n_obj, size_t npts, const int32_t* target, uint64_t seed,
-                                           const uint8_t* keep, double* loss, float* logp, float* trans, float* trans_feat, float* grad)
+namespace {
+
+// the pass, and behind it (step_lr) the optimiser's update: pcr_pointnet_train_grad_f32 (grad wanted) and pcr_pointnet_train_step_f32 (grad optional)
+int train_pass1(pcr_ctx* ctx, pcr_pn2_trainer* t, const char* who, const float* objects, size_t n_obj, size_t npts, const int32_t* target, uint64_t seed,
+                const uint8_t* keep, double* loss, float* logp, float* trans, float* trans_feat, float* grad, const double* step_lr)
 {
-    const char* who = WHO1;
-    const char* own_bad = t && ((trans && !t->desc1.stn3) || (trans_feat && !t->desc1.fstn)) ? ": trans / trans_feat must be NULL when the model has no such T-Net" : nullptr;
+    const char* own_bad = t && t->kind == 1 && ((trans && !t->desc1.stn3) || (trans_feat && !t->desc1.fstn)) ? ": trans / trans_feat must be NULL when the model has no such T-Net" : nullptr;
+    if (!own_bad && t && step_lr) own_bad = optim_bad(t, *step_lr);
     Plan1 P;
     bool run;
-    int rc = call_head(ctx, t, 1, who, own_bad, !objects || !target || !loss || !logp || !grad, target, n_obj, npts, P,
-                       [&]() -> const char* { return make_plan1(t, n_obj, npts, P) ? nullptr : ": too large"; }, run);
+    int rc = call_head(ctx, t, 1, who, own_bad, !objects || !target || !loss || !logp || (!grad && !step_lr), target, n_obj, npts, P,
+                       [&]() -> const char* { return make_plan1(t, n_obj, npts, P) ? nullptr : ": too large"; }, run, !step_lr);
     if (!run) return rc;
     const pcr_pn1_desc& d = t->desc1;
     const uint32_t C0 = 3 + d.D0, K = d.widths[0], n_class = t->layers.back().N, kw = keep_width(d);
@@ -430,7 +431,7 @@ extern "C" int pcr_pointnet_train_grad_f32(pcr_ctx* ctx, pcr_pn2_trainer* t, con
     for (size_t e = 0; e < n_obj * kw; e++) P.keep[e] = keep ? (keep[e] ? 1 : 0) : keep_rule(seed, d.n_fc - 2u, e, t->drop_p[d.n_fc - 2u]);      // the mask: the caller's bytes, or the rule
     rc = call_upload(ctx, t, P);
     if (rc) return rc;
-    ClsRun R(ctx, t, P);
+    ClsRun R(ctx, t, P, who);
     const uint32_t M = P.rows, nm = d.n_mlp, e0 = t->enc_first, s0 = t->stn_first, f0 = t->fstn_first, h0 = t->head_first;
     const uint32_t drop_layer = d.n_fc >= 2 ? h0 + d.n_fc - 2 : T_NONE;
     const float *T3 = nullptr, *TK = nullptr;
@@ -494,5 +495,19 @@ extern "C" int pcr_pointnet_train_grad_f32(pcr_ctx* ctx, pcr_pn2_trainer* t, con
         std::swap(R.cur, R.nxt);
         R.tnet_bwd(s0, P.obj, P.feat_s, P.arg_s, false);
     }
-    return call_tail(ctx, t, who, R.rc, P, n_obj, logp, loss, 3, grad, { { trans, T3, n_obj * 9 * 4 }, { trans_feat, TK, n_obj * (size_t)K * K * 4 } });
+    return call_tail(ctx, t, who, R.rc, P, n_obj, logp, loss, 3, grad, { { trans, T3, n_obj * 9 * 4 }, { trans_feat, TK, n_obj * (size_t)K * K * 4 } }, step_lr);
+}
+
+}  // namespace
+
+extern "C" int pcr_pointnet_train_grad_f32(pcr_ctx* ctx, pcr_pn2_trainer* t, const float* objects, size_t n_obj, size_t npts, const int32_t* target, uint64_t seed,
+                                           const uint8_t* keep, double* loss, float* logp, float* trans, float* trans_feat, float* grad)
+{
+    return train_pass1(ctx, t, "pcr_pointnet_train_grad_f32", objects, n_obj, npts, target, seed, keep, loss, logp, trans, trans_feat, grad, nullptr);
+}
+
+extern "C" int pcr_pointnet_train_step_f32(pcr_ctx* ctx, pcr_pn2_trainer* t, const float* objects, size_t n_obj, size_t npts, const int32_t* target, uint64_t seed,
+                                           const uint8_t* keep, double lr, double* loss, float* logp, float* trans, float* trans_feat, float* grad)
+{
+    return train_pass1(ctx, t, "pcr_pointnet_train_step_f32", objects, n_obj, npts, target, seed, keep, loss, logp, trans, trans_feat, grad, &lr);
 }

@@ -2,7 +2,7 @@
 // Kernels: the strided MFMA product, the chunked f64 statistics, BatchNorm / ReLU forward and backward, the in-place dropout, the max with its argmax, the loss.
 // Every kernel here keeps its profile name in both passes.
 // Host: the trainer handle; layer_push (the weight layout of a layer); trainer_finish (what both creates do behind their shape check); trainer_info_common;
-// keep_rule (the dropout mask by rule); PlanBase (the shared part of a call's device block); call_head / call_upload / call_tail (the checks, the staging and
+// the optimiser's part of the handle (pointnet_optim.hip holds its kernel and calls); keep_rule (the dropout mask by rule); PlanBase (the shared part of a call's device block); call_head / call_upload / call_tail (the checks, the staging and
 // the downloads of a call); LayerRun (one layer forward, one layer backward, the bias gradient, the max's scatter back: the only place that launches them).
 // What a pass keeps to itself: its plan's own buffers, and what happens between the layers (its layers, limits and weight count: pointnet_layers.hpp).
 // The contracts are above pcr_pn2_trainer_create, pcr_pn2_msg_trainer_create and pcr_pn1_trainer_create in include/pcr.h.
@@ -412,11 +412,25 @@ struct pcr_pn2_trainer {
     pcr_pn1_desc desc1;
     uint32_t stn_first = 0, enc_first = 0, fstn_first = 0;      // kind 1: [stn3's six layers] [the encoder] [fstn's six layers] [the head at head_first]
     double reg_scale = 0.0;
+    // the optimiser (pointnet_optim.hip; the contract is above pcr_pn2_trainer_optim_set in include/pcr.h)
+    bool pass_ran = false;               // a pass has left a gradient in grad_dev
+    bool opt_on = false;
+    pcr_optim_desc opt;
+    uint64_t opt_step = 0;               // updates applied
+    double opt_p1 = 1.0, opt_p2 = 1.0;   // beta1^opt_step, beta2^opt_step: the f64 product chain from 1
+    float *opt_s0 = nullptr, *opt_s1 = nullptr;      // Adam: exp_avg, exp_avg_sq; SGD: momentum_buffer, none.  The weight layout
+    void* opt_ranges = nullptr;          // the parameter ranges of the flat array on the device (OptRange), opt_n_ranges of them
+    uint32_t opt_n_ranges = 0;
 };
 
 namespace pcr {
 // pcr_pn2_trainer_info for a kind-1 trainer (pointnet_train.hip)
 int pn1_trainer_info(const pcr_pn2_trainer* t, size_t n_obj, size_t npts, pcr_pn2_train_info* info);
+// pointnet_optim.hip: what is wrong with an update of `t` at `lr` (NULL: nothing); the update launch on the context's stream behind whatever the
+// stream holds, the step count advanced; the state freed
+const char* optim_bad(const pcr_pn2_trainer* t, double lr);
+int optim_launch(pcr_ctx* ctx, pcr_pn2_trainer* t, double lr, const char* who);
+void optim_free(pcr_pn2_trainer* t);
 }
 
 namespace {
@@ -573,20 +587,20 @@ struct PlanBase {
 // run stays false where the call ends here: an error, or no objects
 template <class MakePlan>
 int call_head(pcr_ctx* ctx, const pcr_pn2_trainer* t, int kind, const char* who, const char* own_bad, bool null_arg, const int32_t* target, size_t n_obj, size_t npts,
-              PlanBase& P, MakePlan make, bool& run)
+              PlanBase& P, MakePlan make, bool& run, bool with_grad = true)
 {
     run = false;
     auto bad = [&](const char* what) { return fail(ctx, PCR_ERR_ARG, (std::string(who) + what).c_str()); };
     if (!ctx || !t) return fail(ctx, PCR_ERR_ARG, who);
     if (t->kind != kind)
-        return bad(kind == 0 ? ": the trainer was made by pcr_pn1_trainer_create (use pcr_pointnet_train_grad_f32)"
-                             : ": the trainer was made by pcr_pn2_trainer_create or pcr_pn2_msg_trainer_create (use pcr_pn2_train_grad_f32)");
+        return bad(kind == 0 ? ": the trainer was made by pcr_pn1_trainer_create (use pcr_pointnet_train_grad_f32 / _step_f32)"
+                             : ": the trainer was made by pcr_pn2_trainer_create or pcr_pn2_msg_trainer_create (use pcr_pn2_train_grad_f32 / _step_f32)");
     if (t->device != ctx->device) return bad(": the trainer lives on another device");
     if (npts < 1) return bad(": npts must be >= 1");
     if (own_bad) return bad(own_bad);
     if (n_obj == 0) return PCR_OK;
     if (n_obj < 2) return bad(": BatchNorm's batch statistics need n_obj >= 2");
-    if (null_arg) return bad(": objects / target / loss / logp / grad is NULL");
+    if (null_arg) return bad(with_grad ? ": objects / target / loss / logp / grad is NULL" : ": objects / target / loss / logp is NULL");
     const uint32_t n_class = t->layers.back().N;
     for (size_t o = 0; o < n_obj; o++)
         if (target[o] < 0 || (uint32_t)target[o] >= n_class) return bad(": a target outside [0, n_class)");
@@ -614,16 +628,23 @@ inline int call_upload(pcr_ctx* ctx, pcr_pn2_trainer* t, PlanBase& P)
 
 struct Download { void* dst; const void* src; size_t bytes; };      // dst NULL: not wanted
 
-// the tail of a call: logp, the n_loss loss doubles, the gradient array and `more` to the host, the one wait, rc before the HIP error
-inline int call_tail(pcr_ctx* ctx, const pcr_pn2_trainer* t, const char* who, int rc, const PlanBase& P, size_t n_obj, float* logp, double* loss, size_t n_loss, float* grad,
-                     std::initializer_list<Download> more = {})
+// the tail of a call: with step_lr the optimiser's update behind the pass's last kernel (only where the pass has no error); then logp, the n_loss loss doubles,
+// the gradient array (grad NULL: it stays on the device) and `more` to the host, the one wait, rc before the HIP error
+inline int call_tail(pcr_ctx* ctx, pcr_pn2_trainer* t, const char* who, int rc, const PlanBase& P, size_t n_obj, float* logp, double* loss, size_t n_loss, float* grad,
+                     std::initializer_list<Download> more = {}, const double* step_lr = nullptr)
 {
     hipError_t e = hipSuccess;
     if (rc == PCR_OK) {
         e = hipGetLastError();
+        if (e == hipSuccess) {
+            t->pass_ran = true;
+            if (step_lr) rc = pcr::optim_launch(ctx, t, *step_lr, who);
+        }
+    }
+    if (rc == PCR_OK) {
         if (e == hipSuccess) e = hipMemcpyAsync(logp, P.logp, n_obj * t->layers.back().N * 4, hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(loss, P.loss, n_loss * 8, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(grad, t->grad_dev, t->n_weights * 4, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess && grad) e = hipMemcpyAsync(grad, t->grad_dev, t->n_weights * 4, hipMemcpyDeviceToHost, ctx->stream);
         for (const Download& d : more)
             if (e == hipSuccess && d.dst) e = hipMemcpyAsync(d.dst, d.src, d.bytes, hipMemcpyDeviceToHost, ctx->stream);
     }

@@ -11,7 +11,22 @@ every parameter (HomeworkFinal/train_cls.py:186-196 without its optimiser; model
   TRAINERS      the reference's module name (train_cls.py --model) -> the trainer class, for the two first built
   ALL_TRAINERS  the same for every model train_cls.py --model can name
 
-The optimiser stays torch's own, on host tensors, exactly as train_cls.py:147-153 builds it:
+  DeviceOptimizer   Trainer.optimizer("Adam" | "SGD", ...): torch.optim.Adam / SGD as train_cls.py:147-155 builds them, on the DEVICE (the contract is
+                above pcr_pn2_trainer_optim_set in include/pcr.h), with torch's surface where train_cls.py uses it
+  StepLR        torch.optim.lr_scheduler.StepLR's recurrence on a DeviceOptimizer (or on anything with param_groups)
+
+The whole of train_cls.py:186-199 on the device: per step only the batch goes up, and loss and logp come down.
+
+    tr = Trainer(num_class)
+    opt = tr.optimizer("Adam", lr=1e-3, betas=(0.9, 0.999), eps=1e-08, weight_decay=1e-4)
+    sched = StepLR(opt, step_size=20, gamma=0.7)
+    for epoch in range(epochs):
+        for points, target in loader:
+            loss, logp = tr.step(points, target, opt)      # the pass and the update in one call, at opt.param_groups[0]["lr"]
+        sched.step()
+    torch.save({"model_state_dict": tr.state_dict(), "optimizer_state_dict": opt.state_dict()}, path)
+
+Or the optimiser stays torch's own, on host tensors, exactly as train_cls.py:147-153 builds it:
 
     tr = Trainer(num_class)
     opt = torch.optim.Adam(tr.torch_parameters(), lr=1e-3, betas=(0.9, 0.999), eps=1e-08, weight_decay=1e-4)
@@ -125,6 +140,9 @@ class Trainer:
         self.momentum, self.chunk_rows = float(momentum), int(chunk_rows)
         self._ctx_arg, self._trainer, self._trainer_ctx = ctx, None, None
         self._dirty = True                   # the host weights (running statistics included) are newer than the device's
+        self._dev_ahead = False              # a DeviceOptimizer has stepped: the device's parameters are newer than the host mirror _flat
+        self._grad_on_dev = False            # the last pass left its gradient on the device only
+        self._optimizer = None               # the DeviceOptimizer attached to this trainer
         self._slots, off = {}, 0             # key -> (offset, shape) into the flat array
         for conv, bn, w, cin in layers:
             self._slots[f"{conv}.weight"] = (off, (w, cin, 1, 1) if _conv2d(conv) else (w, cin))
@@ -163,10 +181,12 @@ class Trainer:
         ctx = _ctx(ctx if ctx is not None else self._ctx_arg)
         if self._trainer is None or self._trainer_ctx is not ctx or not self._trainer.h:
             if self._trainer is not None:
-                self._pull_running()
+                self._pull_all()
                 self._trainer.free()
             self._trainer, self._trainer_ctx = self._make(ctx), ctx
             self._dirty = False
+            if self._optimizer is not None:
+                self._optimizer._attach(self._trainer)
         elif self._dirty:
             self._trainer.set_weights(self._flat, keep_running_stats=False)
             self._dirty = False
@@ -175,6 +195,14 @@ class Trainer:
     def _make(self, ctx):
         """the device trainer of this class on ctx, from the host weights"""
         return ctx.pn2_trainer(self._desc, self._flat, self.dropout, self.momentum, self.chunk_rows)
+
+    def _pull_all(self):
+        """before the device trainer goes away: what state_dict() and grads() pull, and the optimiser's state"""
+        self._pull_weights()
+        self._pull_grad()
+        self._dev_ahead = self._grad_on_dev = False
+        if self._optimizer is not None:
+            self._optimizer._save()
 
     def _pull_running(self):
         if self._trainer is None or not self._trainer.h or self._dirty:
@@ -185,12 +213,28 @@ class Trainer:
                 for k in ("running_mean", "running_var"):
                     self._view(f"{bn}.{k}")[...] = self._view(f"{bn}.{k}", dev)
 
+    def _pull_weights(self):
+        """the running statistics, and after a DeviceOptimizer's step the parameters too, into the host mirror"""
+        if self._dev_ahead and not self._dirty and self._trainer is not None and self._trainer.h:
+            self._flat[...] = self._trainer.get_weights()
+            self._dev_ahead = False
+        else:
+            self._pull_running()
+
     def info(self, n_obj=0, npts=0):
         return self.trainer().info(n_obj, npts)
 
+    def optimizer(self, kind="Adam", lr=None, betas=(0.9, 0.999), eps=1e-08, weight_decay=0.0, momentum=0.0, dampening=0.0):
+        """A DeviceOptimizer on this trainer: "Adam" (torch.optim.Adam, amsgrad off; lr defaults to 1e-3) or "SGD" (torch.optim.SGD, no nesterov; lr
+        must be given).  It replaces the one the trainer had.  No device is touched before the first step."""
+        self._optimizer = DeviceOptimizer(self, kind, lr, betas, eps, weight_decay, momentum, dampening)
+        if self._trainer is not None and self._trainer.h:
+            self._optimizer._attach(self._trainer)
+        return self._optimizer
+
     # ---- state
     def state_dict(self):
-        self._pull_running()
+        self._pull_weights()
         out = {}
         for conv, bn, _, _ in self._layer_list:
             out[f"{conv}.weight"] = self._view(f"{conv}.weight").copy()
@@ -219,7 +263,7 @@ class Trainer:
             extra = [k for k in state if k not in seen]
             if extra:
                 raise KeyError(f"unexpected keys in state_dict: {extra}")
-        self._dirty = True
+        self._dirty, self._dev_ahead = True, False      # the host is the newer from here on; a DeviceOptimizer keeps its state, as torch's does
         return self
 
     # ---- the step
@@ -227,6 +271,10 @@ class Trainer:
         """points [B, 3 | 6, N], target [B] or [B, 1] -> (loss, logp [B, num_class]), numpy / float or torch like `points`; every gradient is
         left in grads() and in the .grad of torch_parameters().  start: [n_sampling_layers, B] first FPS picks; keep: the dropout masks, one
         [B, width] array per FC layer but the last (or their concatenation); seed: draws whichever of the two is not given."""
+        return self._pass(points, target, start, seed, keep, ctx, None)
+
+    def _pass(self, points, target, start, seed, keep, ctx, lr):
+        """step_grad (lr None), or the fused step at lr: the same pass, then the attached optimiser's update on the device; the gradient stays there"""
         x, proto = _to_host(points)
         C0 = 3 + int(self._desc.D0)
         if x.ndim != 3 or x.shape[1] != C0:
@@ -244,24 +292,41 @@ class Trainer:
             keep = np.concatenate([np.asarray(_to_host(k)[0]).reshape(-1) for k in keep])
         elif keep is not None:
             keep = np.asarray(_to_host(keep)[0]).reshape(-1)
-        loss, logp, grad = tr.train_grad(np.ascontiguousarray(np.transpose(x, (0, 2, 1)), np.float32), tg, st, seed, keep)
+        obj = np.ascontiguousarray(np.transpose(x, (0, 2, 1)), np.float32)
+        loss, logp, grad = tr.train_grad(obj, tg, st, seed, keep) if lr is None else tr.train_step(obj, tg, lr, st, seed, keep)
         if B:
-            self._gflat[...] = grad
-            for bn in self._tracked:
-                self._tracked[bn] += 1
+            self._after_pass(grad)
         if proto is None:
             return loss, logp
         import torch
         return torch.tensor(loss, dtype=proto.dtype, device=proto.device), _like(logp, proto)
 
+    def _after_pass(self, grad):
+        """grad None: a fused step, the gradient stayed on the device and the device's parameters are now the newer"""
+        if grad is None:
+            self._grad_on_dev = self._dev_ahead = True
+        else:
+            self._gflat[...] = grad
+            self._grad_on_dev = False
+        for bn in self._tracked:
+            self._tracked[bn] += 1
+
+    def _pull_grad(self):
+        if self._grad_on_dev and self._trainer is not None and self._trainer.h:
+            self._gflat[...] = self._trainer.get_grad()
+            self._grad_on_dev = False
+
     def grads(self):
         """key -> the gradient of the last step_grad in the reference's shape, for every key of named_parameters()"""
+        self._pull_grad()
         return {k: self._view(k, self._gflat).copy() for k in self.param_keys()}
 
     def torch_parameters(self):
         """host torch tensors that SHARE the trainer's weights, in named_parameters() order, each with a .grad that shares the trainer's
         gradient: an optimiser's step() changes the trainer's host weights in place; sync() then uploads them"""
         import torch
+        self._pull_weights()
+        self._pull_grad()
         if self._params is None:
             self._params = []
             for k in self.param_keys():
@@ -279,11 +344,19 @@ class Trainer:
         if self._trainer is None or not self._trainer.h or self._dirty:
             self.trainer(ctx)
             return self
+        if self._dev_ahead:                  # nothing on the host is newer than what a DeviceOptimizer left on the device
+            return self
         self._trainer.set_weights(self._flat, keep_running_stats=True)
         return self
 
     def step(self, points, target, optimizer, **kw):
-        """zero_grad is not needed: step_grad -> relink the gradients -> optimizer.step() -> sync; returns step_grad's pair"""
+        """With a DeviceOptimizer: ONE fused call (the pass, then the update at optimizer.param_groups[0]["lr"]); the weights, the gradient and the
+        optimiser's state stay on the device.  With a torch optimiser on torch_parameters(): step_grad -> relink the gradients -> optimizer.step()
+        -> sync (zero_grad is not needed).  Returns step_grad's pair"""
+        if isinstance(optimizer, DeviceOptimizer):
+            if optimizer.trainer is not self or self._optimizer is not optimizer:
+                raise ValueError("optimizer: not this trainer's (Trainer.optimizer makes it)")
+            return self._pass(points, target, kw.get("start"), kw.get("seed"), kw.get("keep"), kw.get("ctx"), float(optimizer.param_groups[0]["lr"]))
         out = self.step_grad(points, target, **kw)
         self.torch_parameters()
         optimizer.step()
@@ -301,10 +374,163 @@ class Trainer:
 
     def free(self):
         if self._trainer is not None:
-            self._pull_running()
+            self._pull_all()
             self._trainer.free()
         self._trainer, self._trainer_ctx = None, None
         self._dirty = True
+
+
+class DeviceOptimizer:
+    """torch.optim.Adam (amsgrad off, coupled weight decay) or torch.optim.SGD (momentum, dampening, weight decay, no nesterov) on the device trainer of a
+    Trainer, with torch's surface where train_cls.py uses it.  Made by Trainer.optimizer.  param_groups[0]["lr"] is read at every step (StepLR writes
+    it); the other hyper-parameters are fixed when the optimiser is made (or loaded).  The state lives on the device in the weight layout; state_dict /
+    load_state_dict speak torch's layout: state[i] per parameter in the trainer's param_keys() order and the reference's shapes, plus param_groups."""
+
+    def __init__(self, trainer, kind, lr, betas, eps, weight_decay, momentum, dampening):
+        kind = {"adam": "Adam", "sgd": "SGD"}.get(str(kind).lower())
+        if kind is None:
+            raise ValueError('kind: "Adam" or "SGD"')
+        if lr is None:
+            if kind == "SGD":
+                raise ValueError("lr: SGD has no default")
+            lr = 1e-3
+        self.trainer, self.kind = trainer, kind
+        n = len(trainer.param_keys())
+        if kind == "Adam":
+            g = dict(lr=float(lr), betas=(float(betas[0]), float(betas[1])), eps=float(eps), weight_decay=float(weight_decay), amsgrad=False, maximize=False, foreach=None,
+                     capturable=False, differentiable=False, fused=None, decoupled_weight_decay=False)
+        else:
+            g = dict(lr=float(lr), momentum=float(momentum), dampening=float(dampening), weight_decay=float(weight_decay), nesterov=False, maximize=False, foreach=None,
+                     differentiable=False, fused=None)
+        g["params"] = list(range(n))
+        self.param_groups = [g]
+        self._host = None                    # (step, state0, state1 or None) while the state is not on a device trainer
+        self._dev = None
+
+    # ---- the device side
+    def _attach(self, dev):
+        g = self.param_groups[0]
+        dev.optim_set(self.kind, betas=g.get("betas", (0.9, 0.999)), eps=g.get("eps", 1e-8), weight_decay=g["weight_decay"], momentum=g.get("momentum", 0.0),
+                      dampening=g.get("dampening", 0.0))
+        if self._host is not None:
+            dev.optim_set_state(*self._host)
+        self._host, self._dev = None, dev
+
+    def _save(self):
+        """the state to the host: the device trainer is about to go away"""
+        if self._dev is not None and self._dev.h:
+            self._host = self._dev.optim_get_state()
+        self._dev = None
+
+    def _state(self):
+        if self._dev is not None and self._dev.h:
+            return self._dev.optim_get_state()
+        if self._host is not None:
+            return self._host
+        n = self.trainer._flat.size
+        return 0, np.zeros(n, np.float32), np.zeros(n, np.float32) if self.kind == "Adam" else None
+
+    def info(self):
+        """pcr_pn2_trainer_optim_info of the device trainer (made if there is none yet)"""
+        return self.trainer.trainer().optim_info()
+
+    # ---- torch's surface
+    def zero_grad(self, set_to_none=True):
+        """nothing: every pass overwrites the whole gradient"""
+
+    def step(self):
+        """one update from the gradient the last step_grad left on the device, at param_groups[0]["lr"]"""
+        tr = self.trainer
+        tr.trainer().optim_step(float(self.param_groups[0]["lr"]))
+        tr._dev_ahead = True
+
+    def state_dict(self, as_torch=False):
+        """torch's optimizer.state_dict(): {"state": {i: {...}}, "param_groups": [...]}; the arrays numpy, or torch tensors with as_torch (what
+        torch.optim's load_state_dict takes).  Before the first step the state is empty, as torch's is."""
+        step, s0, s1 = self._state()
+        tr, state = self.trainer, {}
+        if as_torch:
+            import torch
+            conv = lambda a: torch.from_numpy(np.array(a))
+        else:
+            conv = lambda a: np.array(a)
+        if step > 0:
+            for i, k in enumerate(tr.param_keys()):
+                if self.kind == "Adam":
+                    state[i] = {"step": conv(np.float32(step)), "exp_avg": conv(tr._view(k, s0)), "exp_avg_sq": conv(tr._view(k, s1))}
+                else:
+                    state[i] = {"momentum_buffer": None if self.param_groups[0]["momentum"] == 0 else conv(tr._view(k, s0))}
+        return {"state": state, "param_groups": [dict(g, params=list(g["params"])) for g in self.param_groups]}
+
+    def load_state_dict(self, sd):
+        """a state_dict of this class or of the torch optimiser of the same kind over the same parameters: the state, the step count and the
+        hyper-parameters (the learning rate included) are the checkpoint's from here on"""
+        tr = self.trainer
+        keys = tr.param_keys()
+        groups = sd["param_groups"]
+        if len(groups) != 1 or len(groups[0]["params"]) != len(keys):
+            raise ValueError(f"param_groups: one group of {len(keys)} parameters")
+        g = dict(groups[0])
+        if ("betas" in g) != (self.kind == "Adam"):
+            raise ValueError(f"the checkpoint is not {self.kind}'s")
+        if g.get("amsgrad") or g.get("nesterov") or g.get("maximize") or g.get("decoupled_weight_decay"):
+            raise ValueError("amsgrad, nesterov, maximize and decoupled weight decay are not built")
+        n = tr._flat.size
+        step, s0, s1 = 0, np.zeros(n, np.float32), np.zeros(n, np.float32) if self.kind == "Adam" else None
+        state = sd["state"]
+        if state:
+            steps = set()
+            for i, k in enumerate(keys):
+                st = state[g["params"][i]]
+                shape = tr._slots[k][1]
+                for name, flat in (("exp_avg", s0), ("exp_avg_sq", s1)) if self.kind == "Adam" else (("momentum_buffer", s0),):
+                    if st.get(name) is None:
+                        continue
+                    a = np.asarray(_to_host(st[name])[0], np.float32)
+                    if a.shape != tuple(shape):
+                        raise ValueError(f"size mismatch for {name} of {k}: {a.shape}, the parameter is {shape}")
+                    tr._view(k, flat)[...] = a
+                steps.add(int(np.asarray(_to_host(st["step"])[0])) if "step" in st else 1)
+            if len(steps) != 1:
+                raise ValueError("step: one count for all parameters")
+            step = steps.pop()
+        g["lr"] = float(g["lr"])
+        if "betas" in g:
+            g["betas"] = (float(g["betas"][0]), float(g["betas"][1]))
+        g["params"] = list(range(len(keys)))
+        self.param_groups = [g]
+        self._host = (step, s0, s1)
+        dev, self._dev = self._dev, None
+        if dev is not None and dev.h:
+            self._attach(dev)
+        return self
+
+
+class StepLR:
+    """torch.optim.lr_scheduler.StepLR's recurrence: step() counts an epoch and, at every multiple of step_size, multiplies each group's lr by gamma
+    (one f64 product per boundary, so the sequence is torch's to the bit).  Works on a DeviceOptimizer and on a torch optimiser."""
+
+    def __init__(self, optimizer, step_size=20, gamma=0.7):
+        self.optimizer, self.step_size, self.gamma, self.last_epoch = optimizer, int(step_size), float(gamma), 0
+        for g in optimizer.param_groups:
+            g.setdefault("initial_lr", g["lr"])
+        self._last_lr = [g["lr"] for g in optimizer.param_groups]
+
+    def step(self):
+        self.last_epoch += 1
+        if self.last_epoch % self.step_size == 0:
+            for g in self.optimizer.param_groups:
+                g["lr"] = g["lr"] * self.gamma
+        self._last_lr = [g["lr"] for g in self.optimizer.param_groups]
+
+    def get_last_lr(self):
+        return list(self._last_lr)
+
+    def state_dict(self):
+        return {"step_size": self.step_size, "gamma": self.gamma, "last_epoch": self.last_epoch, "_last_lr": list(self._last_lr)}
+
+    def load_state_dict(self, sd):
+        self.step_size, self.gamma, self.last_epoch, self._last_lr = int(sd["step_size"]), float(sd["gamma"]), int(sd["last_epoch"]), list(sd["_last_lr"])
 
 
 class get_loss:
@@ -427,6 +653,9 @@ class TrainerCls(Trainer):
         """points [B, 3 | 6, N], target [B] or [B, 1] -> (loss, logp [B, k]), numpy / float or torch like `points`; every gradient is left in
         grads() and in the .grad of torch_parameters().  keep: the dropout mask [B, width of the last hidden FC layer]; seed: draws it otherwise
         (None: a seed from np.random)."""
+        return self._pass(points, target, None, seed, keep, ctx, None)
+
+    def _pass(self, points, target, start, seed, keep, ctx, lr):
         x, proto = _to_host(points)
         C0 = 3 + int(self._desc.D0)
         if x.ndim != 3 or x.shape[1] != C0:
@@ -438,11 +667,10 @@ class TrainerCls(Trainer):
             seed = int(np.random.randint(0, 2 ** 31 - 1))
         if keep is not None:
             keep = np.asarray(_to_host(keep)[0]).reshape(-1)
-        res = tr.train_grad(np.ascontiguousarray(np.transpose(x, (0, 2, 1)), np.float32), tg, seed, keep)
+        obj = np.ascontiguousarray(np.transpose(x, (0, 2, 1)), np.float32)
+        res = tr.train_grad(obj, tg, seed, keep) if lr is None else tr.train_step(obj, tg, lr, seed, keep)
         if B:
-            self._gflat[...] = res["grad"]
-            for bn in self._tracked:
-                self._tracked[bn] += 1
+            self._after_pass(res["grad"])
             self.last_nll, self.last_reg, self.last_trans, self.last_trans_feat = res["nll"], res["reg"], res["trans"], res["trans_feat"]
         if proto is None:
             return res["loss"], res["logp"]

@@ -847,7 +847,8 @@ int pcr_pointnet_forward_f32(pcr_ctx* ctx, const pcr_pn2_model* model, const flo
                              float* global_feat, float* trans, float* trans_feat);
 
 /* ---- HomeworkFinal: the PointNet++ (SSG) TRAINING pass, train_cls.py's step without its optimiser: training-mode forward, get_loss
- * (pointnet2_cls_ssg.py:50-52) and the gradient of every parameter.  The optimiser stays the caller's (torch.optim.Adam on host tensors).
+ * (pointnet2_cls_ssg.py:50-52) and the gradient of every parameter.  The optimiser is either the caller's (torch.optim.Adam on host tensors, through
+ * the gradient this call downloads) or the library's own on the device (pcr_pn2_trainer_optim_set and pcr_pn2_train_step_f32, below).
  * A trainer is made from a pcr_pn2_desc (any model it can describe whose last SA layer is group_all) and the flat weight array of
  * pcr_pn2_model_create, UNFOLDED: the trainer keeps W, bias, gamma, beta, running_mean, running_var as they are given.
  * pcr_pn2_train_grad_f32 runs, for n_obj >= 2 objects of npts points (objects as pcr_pn2_forward_f32 takes them) and int32 target[n_obj]:
@@ -911,7 +912,7 @@ int pcr_pn2_train_grad_f32(pcr_ctx* ctx, pcr_pn2_trainer* trainer, const float* 
                            const uint32_t* starts, uint64_t seed, const uint8_t* keep, double* loss, float* logp, float* grad);
 
 /* ---- HomeworkFinal: the vanilla PointNet (pointnet_cls) TRAINING pass: training-mode forward, pointnet_cls.get_loss (:32-42, with
- * pointnet.py:135-141's feature-transform regulariser) and the gradient of every parameter.  The optimiser stays the caller's.
+ * pointnet.py:135-141's feature-transform regulariser) and the gradient of every parameter.  The optimiser: as for the SSG trainer (pcr_pointnet_train_step_f32).
  * A trainer is made from a pcr_pn1_desc (the limits of pcr_pn1_model_create) and the flat weight array of pcr_pn1_model_create, UNFOLDED: W,
  * bias, gamma, beta, running_mean, running_var are kept as given.  The handle is the SSG trainer's type: pcr_pn2_trainer_destroy, _info
  * (n_sampling = 0), _set_weights and _get_weights work on it; pcr_pn2_train_grad_f32 on it is PCR_ERR_ARG, and so is
@@ -1009,6 +1010,69 @@ int pcr_pn2_msg_trainer_create(pcr_ctx* ctx, const pcr_pn2_msg_desc* desc, const
                                size_t n_dropout, double bn_momentum, uint32_t chunk_rows, pcr_pn2_trainer** out);
 int pcr_pn2_msg_trainer_info(const pcr_pn2_trainer* trainer, size_t n_obj, size_t npts, pcr_pn2_train_info* info, pcr_pn2_msg_desc* desc,
                              double* dropout_p);
+
+/* ---- HomeworkFinal: the OPTIMISER of the three trainers on the device: torch.optim.Adam (amsgrad off, coupled weight decay) and
+ * torch.optim.SGD (momentum, dampening, weight decay, no nesterov), the two train_cls.py:147-155 builds.  It lives on the pcr_pn2_trainer handle,
+ * whichever create made it; its state is f32 in the weight layout, on the device, beside the weights and the gradient a pass leaves there.
+ * pcr_pn2_trainer_optim_set attaches or replaces it (state +0, step count 0); a NULL desc detaches it and frees the state, and so does
+ * pcr_pn2_trainer_destroy.  pcr_pn2_trainer_set_weights keeps it, as torch's load_state_dict of a model keeps its optimiser.
+ *   Parameters an element of the flat array is a PARAMETER unless it is a running_mean / running_var slot.  Only parameters move: the update neither
+ *              reads nor writes a running-statistic slot of the weights, the gradient or the state (the state stays +0 there, whatever the
+ *              gradient holds).  Pre-BN biases ARE parameters: their gradient is +0 by the pass's contract and weight decay still moves them.
+ *   Adam       with t = the step count after its increment, per parameter element, every operation in f64 from the f32 w, g, m, v, each operation
+ *              rounded on its own (no fused multiply-add), sqrt and / correctly rounded:
+ *                g' = g + wd w;   m' = m + (1 - beta1) (g' - m);   v' = beta2 v + (1 - beta2) (g' g');
+ *                w <- f32(w - step (m' / (sqrt(v') / sqrt(bc2) + eps))),  m <- f32(m'),  v <- f32(v'): each stored value rounded ONCE, and w
+ *              takes the f64 m' and v' BEFORE their rounding.  On the host in f64: 1 - beta1 and 1 - beta2; bc1 = 1 - p1_t, bc2 = 1 - p2_t with
+ *              p_t = p_(t-1) beta, p_0 = 1 (the product chain, not pow: torch's beta ** t may differ in the last place); step = lr / bc1;
+ *              sqrt(bc2).  torch rounds to f32 after every operation and evaluates step_size m / denom as addcdiv does.
+ *   SGD        g' = g + wd w;  the FIRST update (step count 0 before it) and every update with momentum == 0: b' = g'; later:
+ *              b' = momentum b + (1 - dampening) g';  b <- f32(b'),  w <- f32(w - lr b'), in f64 as above, b' before its rounding.
+ *   Bits       depend on the inputs and the step count only: not on the launch geometry, a tune key or a repeat.  f32 subnormals are kept
+ *              (a subnormal v, an underflowing g' g'), g = 0 gives what IEEE gives.
+ * pcr_pn2_trainer_optim_step applies one update from the gradient the last pass left on the device (one launch on the context's stream, then a
+ *   wait).  pcr_pn2_train_step_f32 / pcr_pointnet_train_step_f32 take the arguments of pcr_pn2_train_grad_f32 / pcr_pointnet_train_grad_f32 with lr
+ *   in front of the outputs and grad OPTIONAL: the same pass, then the update in the same stream (only where the pass raised no error), then the
+ *   downloads of loss, logp, the optional outputs and, where grad is not NULL, the gradient; one wait.  The pass reads the weights BEFORE the
+ *   update, so a pass followed by pcr_pn2_trainer_optim_step gives the same bits.  n_obj == 0: PCR_OK, nothing touched, the count stays.
+ * pcr_pn2_trainer_optim_info: attached (0: everything else is 0), the descriptor, the step count, state_bytes (the state arrays and the range
+ *   table on the device), n_ranges (the merged parameter ranges of the flat array).  pcr_pn2_trainer_info reports what it reported before.
+ * pcr_pn2_trainer_optim_get_state / _set_state: the step count and the state in the weight layout, n = n_weights floats each (Adam: state0 =
+ *   exp_avg, state1 = exp_avg_sq; SGD: state0 = momentum_buffer, state1 unused and may be NULL), for checkpoints.
+ * pcr_pn2_trainer_get_grad reads the gradient the last pass left on the device (n = n_weights floats, the layout of the grad output of
+ *   pcr_pn2_train_grad_f32): what a step call with grad == NULL did not download.  PCR_ERR_ARG before any pass has run.
+ * PCR_ERR_ARG: NULL ctx / trainer (desc may be NULL: detach); a trainer on another device; an unknown kind; a beta outside [0, 1); a negative or
+ *   non-finite eps, weight_decay or momentum; a non-finite dampening.  A step: no optimiser attached; a non-finite lr; pcr_pn2_trainer_optim_step
+ *   before any pass has run on the trainer; the step functions: everything their *_train_grad_f32 refuses but a NULL grad, the other kind of trainer
+ *   included.  The state calls: no optimiser attached; n not the model's count; a NULL array the kind needs; a non-finite value or a negative exp_avg_sq.
+ * Profile names pnopt_adam, pnopt_sgd. */
+enum pcr_optim_kind { PCR_OPTIM_ADAM = 1, PCR_OPTIM_SGD = 2 };
+typedef struct pcr_optim_desc {
+    int32_t kind;            /* PCR_OPTIM_ADAM or PCR_OPTIM_SGD */
+    uint32_t reserved0;
+    double beta1, beta2, eps;        /* Adam */
+    double weight_decay;             /* both */
+    double momentum, dampening;      /* SGD */
+    double reserved[4];
+} pcr_optim_desc;
+typedef struct pcr_optim_info {
+    pcr_optim_desc desc;
+    uint64_t step;
+    uint64_t state_bytes;
+    uint32_t attached;
+    uint32_t n_ranges;
+} pcr_optim_info;
+int pcr_pn2_trainer_optim_set(pcr_ctx* ctx, pcr_pn2_trainer* trainer, const pcr_optim_desc* desc);
+int pcr_pn2_trainer_optim_step(pcr_ctx* ctx, pcr_pn2_trainer* trainer, double lr);
+int pcr_pn2_trainer_optim_info(const pcr_pn2_trainer* trainer, pcr_optim_info* info);
+int pcr_pn2_trainer_optim_get_state(pcr_ctx* ctx, const pcr_pn2_trainer* trainer, uint64_t* step, float* state0, float* state1, size_t n);
+int pcr_pn2_trainer_optim_set_state(pcr_ctx* ctx, pcr_pn2_trainer* trainer, uint64_t step, const float* state0, const float* state1, size_t n);
+int pcr_pn2_trainer_get_grad(pcr_ctx* ctx, const pcr_pn2_trainer* trainer, float* grad, size_t n);
+int pcr_pn2_train_step_f32(pcr_ctx* ctx, pcr_pn2_trainer* trainer, const float* objects, size_t n_obj, size_t npts, const int32_t* target,
+                           const uint32_t* starts, uint64_t seed, const uint8_t* keep, double lr, double* loss, float* logp, float* grad);
+int pcr_pointnet_train_step_f32(pcr_ctx* ctx, pcr_pn2_trainer* trainer, const float* objects, size_t n_obj, size_t npts, const int32_t* target,
+                                uint64_t seed, const uint8_t* keep, double lr, double loss[3], float* logp, float* trans, float* trans_feat,
+                                float* grad);
 
 /* ---- next row N4: global-registration front half, Homework9/hw9/src/registration.cpp:288-434, :535-615 -----------
  * N4a: exhaustive 1-NN between two descriptor sets (row-major n x dim / m x dim f32, host memory; dim 33 = FPFH),
