@@ -124,7 +124,7 @@ ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_int)
 ABI_SYMBOLS = [
     "pcr_device_count", "pcr_ctx_create", "pcr_ctx_destroy", "pcr_ctx_sync", "pcr_ctx_last_error", "pcr_version", "pcr_ctx_device_info",
     "pcr_cloud_create", "pcr_cloud_clone", "pcr_cloud_assign", "pcr_cloud_read", "pcr_cloud_size", "pcr_cloud_destroy",
-    "pcr_nn1_f32", "pcr_nn1_f32_async", "pcr_nn1_fetch", "pcr_transform_f32", "pcr_kabsch_sums", "pcr_kabsch_solve", "pcr_kabsch_grid_exponent", "pcr_kabsch_limbs_to_sums",
+    "pcr_nn1_f32", "pcr_nn1_f32_async", "pcr_nn1_fetch", "pcr_transform_f32", "pcr_kabsch_sums", "pcr_kabsch_solve", "pcr_kabsch_solve_lanes", "pcr_kabsch_solve_batch_device", "pcr_kabsch_grid_exponent", "pcr_kabsch_limbs_to_sums",
     "pcr_icp_p2p_f32", "pcr_icp_last_chain", "pcr_icp_last_snapshots", "pcr_icp_replica_members", "pcr_icp_move_route", "pcr_icp_solve_route", "pcr_icp_solve_in_search_auto", "pcr_s3_walk_visits", "pcr_plane_count_f64", "pcr_plane_mask_f64", "pcr_knn_f64", "pcr_radius_f64",
     "pcr_comm_unique_id", "pcr_comm_init_rccl", "pcr_comm_init_callback", "pcr_comm_destroy", "pcr_comm_selftest", "pcr_shard_range",
     "pcr_prof_reset", "pcr_prof_get", "pcr_prof_get_each", "pcr_tune_set",
@@ -188,6 +188,8 @@ def lib():
     L.pcr_transform_f32.argtypes = [vp, vp, vp]
     L.pcr_kabsch_sums.argtypes = [vp, vp, vp, C.c_float, vp, C.POINTER(C.c_int64), C.POINTER(C.c_float)]
     L.pcr_kabsch_solve.argtypes = [vp, vp, vp]
+    L.pcr_kabsch_solve_lanes.argtypes = [vp, vp, vp]
+    L.pcr_kabsch_solve_batch_device.argtypes = [vp, vp, sz, vp, vp, vp]
     L.pcr_kabsch_grid_exponent.argtypes = [C.c_float, C.c_float]
     L.pcr_kabsch_limbs_to_sums.argtypes = [vp, C.c_int, vp]
     L.pcr_icp_p2p_f32.argtypes = [vp, vp, vp, vp, C.POINTER(IcpParams), vp, C.POINTER(IcpStats)]
@@ -442,6 +444,15 @@ def kabsch_solve(sums):
     R = np.zeros(9, np.float32)
     t = np.zeros(3, np.float32)
     rc = lib().pcr_kabsch_solve(s.ctypes.data, R.ctypes.data, t.ctypes.data)
+    return rc, R.reshape(3, 3), t
+
+
+def kabsch_solve_lanes(sums):
+    """kabsch_solve in the lane form the device-resident loop runs, by the host's lane group (csrc/kabsch_wave.hpp): the same bits, no GPU needed."""
+    s = np.ascontiguousarray(sums, np.float64)
+    R = np.zeros(9, np.float32)
+    t = np.zeros(3, np.float32)
+    rc = lib().pcr_kabsch_solve_lanes(s.ctypes.data, R.ctypes.data, t.ctypes.data)
     return rc, R.reshape(3, 3), t
 
 
@@ -1971,6 +1982,14 @@ class Context:
         d2 = C.c_float()
         self._ck(lib().pcr_kabsch_sums(self.h, tgt.h, src.h, max_corr, sums.ctypes.data, C.byref(last), C.byref(d2)))
         return sums, last.value, d2.value
+
+    def kabsch_solve_batch_device(self, sums):
+        """n Kabsch solves (sums n x 16 f64) by one wavefront each, in the lane form of csrc/kabsch_wave.hpp -> (rc int32[n], R f32[n, 3, 3], t f32[n, 3])."""
+        s = np.ascontiguousarray(sums, np.float64).reshape(-1, 16)
+        n = s.shape[0]
+        R, t, rc = np.zeros((n, 9), np.float32), np.zeros((n, 3), np.float32), np.zeros(n, np.int32)
+        self._ck(lib().pcr_kabsch_solve_batch_device(self.h, s.ctypes.data, n, R.ctypes.data, t.ctypes.data, rc.ctypes.data))
+        return rc, R.reshape(n, 3, 3), t
 
     # ---- A9
     def icp_point2point(self, src: Cloud, tgt: Cloud, init_T=None, max_corr=1.0, max_iter=20, eps=1e-8):

@@ -578,6 +578,18 @@ int pcr_kabsch_solve(const double sums[16], float R[9], float t[3])
     return kabsch_solve(sums, R, t);
 }
 
+int pcr_kabsch_solve_lanes(const double sums[16], float R[9], float t[3])
+{
+    if (!sums || !R || !t) return PCR_ERR_ARG;
+    return kabsch_solve_lanes(sums, R, t);
+}
+
+int pcr_kabsch_solve_batch_device(pcr_ctx* ctx, const double* sums, size_t n, float* R, float* t, int* rc)
+{
+    if (!ctx || (n && (!sums || !R || !t || !rc))) return fail(ctx, PCR_ERR_ARG, "pcr_kabsch_solve_batch_device");
+    return kabsch_solve_batch_device(ctx, sums, n, R, t, rc);
+}
+
 // ---------------------------------------------------------------------------------------------- profiling / tuning
 int pcr_prof_reset(pcr_ctx* ctx)
 {

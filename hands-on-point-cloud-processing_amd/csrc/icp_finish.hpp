@@ -1,11 +1,13 @@
 // icp_finish.hpp — the back half of an ICP iteration on one rank, shared by the launches that run it: accumulator rows -> carries -> the 16 moments ->
 // state machine, Kabsch solve and pose composition (registration.cpp:939-1002).  kabsch.hip's sums + solve launch (chain 4) runs these
 // steps in its last arriver; the chain sums -> search (chain 5) runs them, as ONE WAVE (finish_iteration), in every workgroup of the moving
-// search (nn1_sphere.hpp) and in the finishing launch of a call (kabsch.hip).  One text for all of them: the bits are the same by construction.
+// search (nn1_sphere.hpp) and in the finishing launch of a call (kabsch.hip).  One text for all of them: the bits are the same by construction.  The solve and
+// the pose composition are worked by a whole wave (icp_state_step_wave, kabsch_wave.hpp) wherever the state is stepped on the device.
 #pragma once
 
 #include "pcr_internal.hpp"
 #include "numerics.hpp"
+#include "kabsch_wave.hpp"
 
 #include <cstddef>
 
@@ -124,6 +126,55 @@ __device__ __forceinline__ void fin_wave_sync()
     __builtin_amdgcn_wave_barrier();
 }
 
+// icp_state_step by ONE WAVE, all 64 lanes of it: the Kabsch solve and the pose composition are kabsch_wave.hpp's lane form — the same
+// operations on the same operands, spread over the lanes —; the state machine's decisions are made by every lane alike on what it read from `st` before
+// any lane wrote there, and lane 0 alone writes the scalar fields.  `st` and `sums16` are in LDS, complete (the caller's fin_wave_sync or barrier stands
+// in front); behind the call's closing fin_wave_sync every lane may read the new state.  -DPCR_SOLVE_SCALAR: lane 0 runs the scalar step (the A/B arm)
+__device__ __forceinline__ void icp_state_step_wave(int l, IcpState* st, const double* sums16, bool any_kept, float last_d2, bool overflow)
+{
+#ifdef PCR_SOLVE_SCALAR
+    if (l == 0) icp_state_step(st, sums16, any_kept, last_d2, overflow);
+    fin_wave_sync();
+#else
+    const int stop = st->stop, after = st->stop_after_transform;
+    const float last_loss = st->last_loss, eps = st->eps, T_mine = st->T_total[l & 15];
+    unsigned long long unchanged = st->unchanged;
+    const unsigned long long iters_run = st->iters_run, max_iter = st->max_iter;
+    fin_wave_sync();                           // (every lane has read what it decides on)
+    if (!__builtin_amdgcn_readfirstlane(stop)) {
+        if (__builtin_amdgcn_readfirstlane(after)) { if (l == 0) st->stop = 1; }       // max_iter reached: the loop is over
+        else if (__builtin_amdgcn_readfirstlane((int)overflow)) { if (l == 0) { st->overflow = 1; st->stop = 1; } }  // a kept source beyond the accumulation grid
+        else {
+            float loss = 0.0f;
+            if (any_kept) loss = last_d2 * last_d2;                                      // :939
+            if (fabsf(last_loss - loss) < eps) unchanged++;                              // :948-951
+            const bool converged = __builtin_amdgcn_readfirstlane((int)(unchanged > 15)) != 0;
+            if (l == 0) {
+                st->last_pairs = (unsigned long long)sums16[15];
+                st->loss = loss;
+                st->unchanged = unchanged;
+                if (converged) { st->converged = 1; st->stop = 1; }                      // :954-958
+                else st->last_loss = loss;                                               // :961
+            }
+            if (!converged) {
+                const num::WaveLanes g{ l };
+                float R = 0.0f, t = 0.0f;
+                if (num::kabsch_solve_lanes(g, sums16, R, t) != 0) { if (l == 0) { st->empty = 1; st->stop = 1; } }   // :979-998
+                else {
+                    const float T_new = num::pose_compose_lanes(g, R, t, T_mine);         // :1000-1002
+                    if (l < 9) st->Rd[l] = R;
+                    if (l < 3) st->td[l] = t;
+                    if (l < 16) st->T_total[l] = T_new;
+                    // max_iter reached: this iteration's transform must still run, everything after it must not
+                    if (l == 0) { st->iters_run = iters_run + 1; if (iters_run + 1 >= max_iter) st->stop_after_transform = 1; }
+                }
+            }
+        }
+    }
+    fin_wave_sync();
+#endif
+}
+
 struct IcpFinishLds {
     long long acc[ACC_R][ACC_W];
     double row[KB_ROW];
@@ -177,8 +228,7 @@ __device__ __forceinline__ bool finish_iteration(int l, const IcpFinishLoads& Q,
     fin_wave_sync();
     row_to_out18(l, F.row, e, F.o18);
     fin_wave_sync();
-    if (l == 0) icp_state_step(&F.st, F.o18, F.o18[16] >= 0.0, (float)F.o18[17], F.o18[18] != 0.0);
-    fin_wave_sync();
+    icp_state_step_wave(l, &F.st, F.o18, F.o18[16] >= 0.0, (float)F.o18[17], F.o18[18] != 0.0);
     return true;
 }
 

@@ -419,7 +419,7 @@ int launch_kabsch_sums(pcr_ctx* ctx, const pcr_cloud* tgt, const pcr_cloud* src,
 }
 
 // ---------------------------------------------------------------------------------------------- device-resident ICP state
-// (icp_state_step — state machine + Kabsch solve + pose composition, one thread — and ST_WORDS: icp_finish.hpp)
+// (icp_state_step_wave — state machine + Kabsch solve + pose composition, by the first wave of the kernels below, DESIGN.md 6l — and ST_WORDS: icp_finish.hpp)
 
 // the whole state in ONE coalesced read: thread w copies 32-bit word w into the workgroup's LDS copy (ends in a barrier)
 __device__ __forceinline__ void icp_state_stage(const IcpState* st, IcpState* lds)
@@ -444,9 +444,9 @@ __global__ __launch_bounds__(KF_BLOCK) void icp_update_kernel(const double* __re
     row_to_out18(row, e, o18);
     __syncthreads();
     if (threadIdx.x < 19) out[threadIdx.x] = o18[threadIdx.x];
-    if (threadIdx.x == 0) {
-        icp_state_step(&s_st, o18, o18[16] >= 0.0, (float)o18[17], o18[18] != 0.0);
-        *st = s_st;
+    if (threadIdx.x < 64) {                    // the first wave, whole (icp_finish.hpp icp_state_step_wave)
+        icp_state_step_wave((int)threadIdx.x, &s_st, o18, o18[16] >= 0.0, (float)o18[17], o18[18] != 0.0);
+        if (threadIdx.x == 0) *st = s_st;
     }
 }
 
@@ -514,7 +514,7 @@ __global__ __launch_bounds__(KF_BLOCK) void icp_update_move_kernel(const double*
         row_to_out18(row, e, o18);
         __syncthreads();
         if (blockIdx.x == 0 && threadIdx.x < 19) out[threadIdx.x] = o18[threadIdx.x];
-        if (threadIdx.x == 0) icp_state_step(&s_st, o18, o18[16] >= 0.0, (float)o18[17], o18[18] != 0.0);
+        if (threadIdx.x < 64) icp_state_step_wave((int)threadIdx.x, &s_st, o18, o18[16] >= 0.0, (float)o18[17], o18[18] != 0.0);
     } else if (phase == 1) {
         if (threadIdx.x == 0) s_st.stop = 1;
     }
@@ -708,7 +708,7 @@ __global__ __launch_bounds__(T) void icp_sums_update_move_kernel(
         row_to_out18(row, plan.e, o18);
         __syncthreads();
         if (blockIdx.x == 0 && threadIdx.x < 19) out[threadIdx.x] = o18[threadIdx.x];
-        if (threadIdx.x == 0) icp_state_step(&s_st, o18, o18[16] >= 0.0, (float)o18[17], o18[18] != 0.0);
+        if (threadIdx.x < 64) icp_state_step_wave((int)threadIdx.x, &s_st, o18, o18[16] >= 0.0, (float)o18[17], o18[18] != 0.0);
     } else if (threadIdx.x == 0) {
         s_st.stop = 1;                         // (phase 0: stays stopped; phase 1: max_iter reached, the loop is over; timeout)
         if (tmo) {
@@ -1014,8 +1014,8 @@ __global__ __launch_bounds__(T) void icp_sums_solve_kernel(
         row_to_out18(row, plan.e, o18);
         __syncthreads();
         if (threadIdx.x < 19) out[threadIdx.x] = o18[threadIdx.x];
-        if (threadIdx.x == 0) {
-            icp_state_step(&s_st, o18, o18[16] >= 0.0, (float)o18[17], o18[18] != 0.0);
+        if (threadIdx.x < 64) {
+            icp_state_step_wave((int)threadIdx.x, &s_st, o18, o18[16] >= 0.0, (float)o18[17], o18[18] != 0.0);
 #ifdef PCR_SS_PROF
             pt_e = __builtin_amdgcn_s_memrealtime();
 #endif
@@ -1162,12 +1162,11 @@ __global__ __launch_bounds__(64) void icp_update_from_sums_kernel(double* __rest
     else if (k < 15) { num::limbs_normalize(row + 18 + 4 * (k - 6), 3); sums[k] = num::limbs_value(row + 18 + 4 * (k - 6), 3, 2 * e - 3 * num::KB_W); }
     else if (k == 15) sums[15] = row[54];
     __syncthreads();
-    if (k != 0) return;
-    const int ls = icp_last_slot(buf, nranks);                 // the pair with the largest order key
+    const int ls = icp_last_slot(buf, nranks);                 // the pair with the largest order key (every lane alike)
     const bool any = ls >= 0;
     const float d2 = any ? (float)buf[57 + 2 * ls] : 0.0f;
-    icp_state_step(&s_st, sums, any, d2, buf[55] != 0.0);
-    *st = s_st;
+    icp_state_step_wave(k, &s_st, sums, any, d2, buf[55] != 0.0);
+    if (k == 0) *st = s_st;
 }
 
 __global__ __launch_bounds__(256) void transform_state_kernel(float* __restrict__ x, float* __restrict__ y,
@@ -1419,6 +1418,52 @@ int launch_icp_reduce_slots(pcr_ctx* ctx, uint32_t n_blocks, int nranks, int ran
     hipLaunchKernelGGL(icp_reduce_slots_kernel, dim3(1), dim3(KF_BLOCK), 0, ctx->stream, ctx->partials, n_blocks, ctx->dev_out, nranks, rank,
                        have_points ? 1 : 0, gidx);
     PCR_HIP(ctx, hipGetLastError());
+    return PCR_OK;
+}
+
+// The lane form of the Kabsch solve on its own (kabsch_wave.hpp), for tests: one wave per problem, KSB_WAVES problems per workgroup.  A problem whose
+// solve returns -1 (no pair kept) leaves its R and t as they were (the launcher zeroes them)
+constexpr int KSB_WAVES = 4;
+__global__ __launch_bounds__(64 * KSB_WAVES) void kabsch_solve_batch_kernel(const double* __restrict__ sums, uint32_t n, float* __restrict__ R, float* __restrict__ t,
+                                                                            int* __restrict__ rc)
+{
+    const int l = threadIdx.x & 63;
+    const uint32_t p = blockIdx.x * KSB_WAVES + (threadIdx.x >> 6);
+    if (p >= n) return;                        // (a whole wave leaves, or none of it)
+    const num::WaveLanes g{ l };
+    float Rl = 0.0f, tl = 0.0f;
+    const int r = num::kabsch_solve_lanes(g, sums + 16 * (size_t)p, Rl, tl);
+    if (l == 0) rc[p] = r == 0 ? PCR_OK : PCR_ERR_EMPTY;
+    if (r != 0) return;
+    if (l < 9) R[9 * (size_t)p + l] = Rl;
+    if (l < 3) t[3 * (size_t)p + l] = tl;
+}
+
+int kabsch_solve_batch_device(pcr_ctx* ctx, const double* sums, size_t n, float* R, float* t, int* rc)
+{
+    if (n == 0) return PCR_OK;
+    if (n > 0x7FFFFFFFull / 16) return fail(ctx, PCR_ERR_ARG, "pcr_kabsch_solve_batch_device: too many problems");
+    const size_t b_sums = n * 16 * sizeof(double), b_R = n * 9 * sizeof(float), b_t = n * 3 * sizeof(float), b_rc = n * sizeof(int);
+    char* dev = nullptr;
+    PCR_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&dev), b_sums + b_R + b_t + b_rc));
+    double* d_sums = reinterpret_cast<double*>(dev);
+    float* d_R = reinterpret_cast<float*>(dev + b_sums);
+    float* d_t = reinterpret_cast<float*>(dev + b_sums + b_R);
+    int* d_rc = reinterpret_cast<int*>(dev + b_sums + b_R + b_t);
+    hipError_t e = hipMemcpyAsync(d_sums, sums, b_sums, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d_R, 0, b_R + b_t + b_rc, ctx->stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(kabsch_solve_batch_kernel, dim3((uint32_t)((n + KSB_WAVES - 1) / KSB_WAVES)), dim3(64 * KSB_WAVES), 0, ctx->stream, d_sums, (uint32_t)n,
+                           d_R, d_t, d_rc);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(R, d_R, b_R, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(t, d_t, b_t, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(rc, d_rc, b_rc, hipMemcpyDeviceToHost, ctx->stream);
+    const hipError_t es = hipStreamSynchronize(ctx->stream);
+    if (e == hipSuccess) e = es;
+    (void)hipFree(dev);
+    if (e != hipSuccess) return fail(ctx, PCR_ERR_HIP, "pcr_kabsch_solve_batch_device", e);
     return PCR_OK;
 }
 

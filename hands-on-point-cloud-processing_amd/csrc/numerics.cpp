@@ -1,6 +1,7 @@
 // numerics.cpp — host entry points of the shared 3x3 numerics (numerics.hpp).
 #include "pcr_internal.hpp"
 #include "numerics.hpp"
+#include "kabsch_wave.hpp"
 
 #include <cmath>
 
@@ -11,6 +12,12 @@ void svd3(const double A[9], double U[9], double S[3], double V[9]) { num::svd3(
 int kabsch_solve(const double sums[16], float R[9], float t[3])
 {
     return num::kabsch_solve(sums, R, t) == 0 ? PCR_OK : PCR_ERR_EMPTY;
+}
+
+int kabsch_solve_lanes(const double sums[16], float R[9], float t[3])
+{
+    const int rc = num::kabsch_solve_host_lanes(sums, R, t);
+    return rc == 0 ? PCR_OK : rc == -1 ? PCR_ERR_EMPTY : PCR_ERR_STATE;
 }
 
 void mat4_mul_f32(const float A[16], const float B[16], float out[16]) { num::mat4_mul_f32(A, B, out); }

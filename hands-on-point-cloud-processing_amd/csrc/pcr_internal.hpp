@@ -436,6 +436,9 @@ inline unsigned long long splitmix_key(unsigned long long seed, unsigned long lo
 // ---- host numerics ------------------------------------------------------------------------------------
 void svd3(const double A[9], double U[9], double S[3], double V[9]);
 int kabsch_solve(const double sums[16], float R[9], float t[3]);
+// the same solve in its lane form (kabsch_wave.hpp): by the host's lane group, and by one wave per problem on the device (kabsch.hip; host arrays in and out)
+int kabsch_solve_lanes(const double sums[16], float R[9], float t[3]);
+int kabsch_solve_batch_device(pcr_ctx* ctx, const double* sums, size_t n, float* R, float* t, int* rc);
 void mat4_mul_f32(const float A[16], const float B[16], float out[16]);
 // every eigenpair of a real n x n matrix, n <= 16 (numerics.cpp; the contract of pcr_eig_small_f64), and the eigengap rule of Homework3
 int eig_small(int n, const double* a, double* wr, double* wi, double* vec);

@@ -105,6 +105,12 @@ int pcr_kabsch_sums(pcr_ctx* ctx, const pcr_cloud* tgt, const pcr_cloud* src, fl
                     double sums[16], int64_t* last_kept, float* last_d2);
 /* ---- A7 (solve): registration.cpp:979-998 incl. the det<0 branch (:990-996). Host, f64. -------------- */
 int pcr_kabsch_solve(const double sums[16], float R[9], float t[3]);
+/* The same solve in the form the device-resident ICP loop runs, its operations spread over a group of lanes (bit for bit the
+ * result of pcr_kabsch_solve): by the host's lane group, and by one wavefront per problem on the GPU — n problems, host arrays
+ * sums[16 n] in, R[9 n], t[3 n], rc[n] out; rc[i] is what pcr_kabsch_solve returns for problem i, R and t of a problem that
+ * kept no pair are zero. */
+int pcr_kabsch_solve_lanes(const double sums[16], float R[9], float t[3]);
+int pcr_kabsch_solve_batch_device(pcr_ctx* ctx, const double* sums, size_t n, float* R, float* t, int* rc);
 
 /* ---- A9: Registration::ICPpoint2point, Homework9/hw9/src/registration.cpp:862-1011 -------------------
  * (after its normal-space sampling: the clouds passed here are the sampled clouds). */
