@@ -66,6 +66,11 @@ EIG3_HD V3 in_plane_vector(const double M[9], const V3& w, double lambda)
 }
 
 // mylib.cpp:105-189.  (0,0,0) when the signed maximum coefficient is 0 (:112-115).
+// REF_TIES: the answer for a diagonal matrix diag(a, a, b) with a < b.  The reference's diagonal branch (:177-187) asks for a STRICT minimum on
+// x, then on y, and otherwise answers z — here the eigenvector of the LARGEST eigenvalue.  true keeps that (pcr_fast_eigen3x3 is pinned to the
+// reference function); false answers x, an eigenvector of the smallest eigenvalue: the per-point normals, which are not pinned to it, must
+// not hand a row of points along z its own direction as its normal.  Every other input gives the same answer in both forms.
+template <bool REF_TIES = true>
 EIG3_HD void smallest_eigenvector(const double A[9], double normal[3])
 {
     double M[9];
@@ -105,6 +110,7 @@ EIG3_HD void smallest_eigenvector(const double A[9], double normal[3])
         const double a0 = M[0] * big, a1 = M[4] * big, a2 = M[8] * big;
         if (a0 < a1 && a0 < a2) out = V3{ 1, 0, 0 };
         else if (a1 < a0 && a1 < a2) out = V3{ 0, 1, 0 };
+        else if (!REF_TIES && a0 == a1 && a0 < a2) out = V3{ 1, 0, 0 };
         else out = V3{ 0, 0, 1 };
     }
     normal[0] = out.a; normal[1] = out.b; normal[2] = out.c;

@@ -37,6 +37,17 @@ struct TopK {
 
 __device__ __forceinline__ bool lex_less(double va, int32_t ia, double vb, int32_t ib) { return va < vb || (va == vb && ia < ib); }
 
+// The value of an unused list slot (its index is 0x7FFFFFFF).  SQ = false follows hw2's result set (resultSet.hpp:32,69: worstDist starts at
+// 1e10 and a candidate is rejected when dist > worstDist): a neighbour at d > 1e10 never enters, one at d == 1e10 does — (1e10, j) is
+// lexicographically below the unused slot (1e10, 0x7FFFFFFF), (1e10 + ulp, j) is not.  The same rule as knn_f64_kernel<K, false>.
+template <bool SQ>
+__device__ __forceinline__ constexpr double unused_value() { return SQ ? INFINITY : 1e10; }
+
+// s-domain bound of a k-th value w: nothing with s above it can enter.  While slots are unused w is unused_value(): no bound yet (the walk keeps
+// doubling its cube, rows are not clipped) — in the SQ = false mode that also holds for a full list whose k-th entry sits at exactly 1e10.
+template <bool SQ>
+__device__ __forceinline__ double kth_bound(double w) { return SQ ? w : (w < 1e10 ? w * w * (1.0 + 1e-12) : INFINITY); }   // sqrt(s) <= w  =>  s <= w*w*(1 + 2^-52 ...)
+
 // precondition: (val, idx) < (t.v[K-1], t.i[K-1]).  Slots are rewritten from the back: slot s keeps its entry when the
 // candidate is not better than it, takes its left neighbour when the candidate beats that one too, else the candidate.
 template <int K>
@@ -74,8 +85,7 @@ __device__ __forceinline__ void scan_cells(const float4* __restrict__ records, u
         const double val = SQ ? s : sqrt(s);
         if (lex_less(val, j, t.v[K - 1], t.i[K - 1])) {
             topk_insert<K>(t, val, j);
-            const double w = t.v[K - 1];
-            kth_s = SQ ? w : w * w * (1.0 + 1e-12);               // sqrt(s) <= w  =>  s <= w*w*(1 + 2^-52 ...)
+            kth_s = kth_bound<SQ>(t.v[K - 1]);
         }
     }
 }
@@ -106,7 +116,7 @@ __global__ __launch_bounds__(KG_BLOCK) void knn_grid_kernel(const float4* __rest
     }
     TopK<K> t;
 #pragma unroll
-    for (int s = 0; s < K; s++) { t.v[s] = INFINITY; t.i[s] = 0x7FFFFFFF; }
+    for (int s = 0; s < K; s++) { t.v[s] = unused_value<SQ>(); t.i[s] = 0x7FFFFFFF; }
     double kth_s = INFINITY;
     if (finite3(fx, fy, fz)) {
         const double qx = fx, qy = fy, qz = fz;
@@ -188,7 +198,7 @@ __global__ __launch_bounds__(64) void knn_grid_coop_kernel(const float4* __restr
     double mv[K];                       // the merged global top-k (the same in every lane)
     int32_t mi[K];
 #pragma unroll
-    for (int s = 0; s < K; s++) { t.v[s] = INFINITY; t.i[s] = 0x7FFFFFFF; mv[s] = INFINITY; mi[s] = 0x7FFFFFFF; }
+    for (int s = 0; s < K; s++) { t.v[s] = unused_value<SQ>(); t.i[s] = 0x7FFFFFFF; mv[s] = unused_value<SQ>(); mi[s] = 0x7FFFFFFF; }
     double kth_s = INFINITY;            // s-domain bound of the global k-th entry (from the last merge)
     if (finite3(fx, fy, fz)) {
         const double qx = fx, qy = fy, qz = fz;
@@ -210,8 +220,7 @@ __global__ __launch_bounds__(64) void knn_grid_coop_kernel(const float4* __restr
                 const double val = SQ ? s : sqrt(s);
                 if (lex_less(val, j, t.v[K - 1], t.i[K - 1])) {
                     topk_insert<K>(t, val, j);
-                    const double w = t.v[K - 1];                                           // (a lane's own k-th bounds the global k-th from above)
-                    my_kth = fmin(my_kth, SQ ? w : w * w * (1.0 + 1e-12));
+                    my_kth = fmin(my_kth, kth_bound<SQ>(t.v[K - 1]));                       // (a lane's own k-th bounds the global k-th from above)
                 }
             };
             if (xlo <= xhi && ylo <= yhi && zlo <= zhi) {
@@ -269,13 +278,12 @@ __global__ __launch_bounds__(64) void knn_grid_coop_kernel(const float4* __restr
                 if (t.i[0] == hi && t.v[0] == hv && hi != 0x7FFFFFFF) {                    // mine: pop
 #pragma unroll
                     for (int u = 0; u + 1 < K; u++) { t.v[u] = t.v[u + 1]; t.i[u] = t.i[u + 1]; }
-                    t.v[K - 1] = INFINITY; t.i[K - 1] = 0x7FFFFFFF;
+                    t.v[K - 1] = unused_value<SQ>(); t.i[K - 1] = 0x7FFFFFFF;
                 }
             }
 #pragma unroll
-            for (int s = 0; s < K; s++) { t.v[s] = lane == 0 ? mv[s] : INFINITY; t.i[s] = lane == 0 ? mi[s] : 0x7FFFFFFF; }
-            const double w = mv[K - 1];
-            kth_s = SQ ? w : w * w * (1.0 + 1e-12);                                        // INFINITY while fewer than K were seen
+            for (int s = 0; s < K; s++) { t.v[s] = lane == 0 ? mv[s] : unused_value<SQ>(); t.i[s] = lane == 0 ? mi[s] : 0x7FFFFFFF; }
+            kth_s = kth_bound<SQ>(mv[K - 1]);                                              // INFINITY while fewer than K were seen
             const bool covers = (ux - r <= 0) && (ux + r >= g.n[0] - 1) && (uy - r <= 0) && (uy + r >= g.n[1] - 1) && (uz - r <= 0) && (uz + r >= g.n[2] - 1);
             const double reach = ((double)r - slack) * h;
             const double lim = fmin(kth_s, cap_s);                                         // nothing at or beyond `lim` can enter
@@ -331,7 +339,7 @@ __global__ __launch_bounds__(KG_BLOCK) void normals_kernel(const float* __restri
             xx += dx * dx; xy += dx * dy; xz += dx * dz; yy += dy * dy; yz += dy * dz; zz += dz * dz;   // :22
         }
         const double A[9] = { xx, xy, xz, xy, yy, yz, xz, yz, zz };
-        eig3::smallest_eigenvector(A, out);
+        eig3::smallest_eigenvector<false>(A, out);         // (false: diag(a, a, b), a < b answers x — eig3.hpp)
     }
     normals[3 * (size_t)i] = out[0]; normals[3 * (size_t)i + 1] = out[1]; normals[3 * (size_t)i + 2] = out[2];
 }

@@ -30,6 +30,12 @@ __device__ __forceinline__ double dist2_f64(double t0, double t1, double t2, dou
 
 // SQ = false: hw2 contract (d = sqrt(s), kdtree.hpp:346); SQ = true: nanoflann contract (squared L2, no sqrt,
 // nanoflann.hpp:403-406 with T = double) - ordering then happens on s itself.
+// hw2's result set starts with worstDist = 1e10 and rejects dist > worstDist (resultSet.hpp:32,69): a point at d == 1e10 IS a neighbour and
+// is reported with its index, one beyond never is.  The unused slots therefore carry HW2_UNUSED = the next double above 1e10 while the scan
+// and the merge run — `d < HW2_UNUSED` is `d <= 1e10`, and a real entry at 1e10 sorts in front of them with no further test in the loop —
+// and leave as the documented (1e10, 0).
+constexpr double HW2_UNUSED = 10000000000.000002;      // 1e10 + 2^-19 (one ulp)
+static_assert(HW2_UNUSED > 1e10 && HW2_UNUSED - 1e10 == 0x1p-19, "HW2_UNUSED must be the successor of 1e10");
 // Small batches: the database is cut into gridDim.y slices of tiles_per_slice tiles, each (query block, slice) workgroup keeps
 // the top k of its slice (written to the slice's own [m x k] block of the output), knn_merge_kernel folds the slices in
 // ascending order — the same scan order, so the same canonical result.  gridDim.y == 1: the whole database, final output.
@@ -45,8 +51,8 @@ __global__ __launch_bounds__(SF_BLOCK) void knn_f64_kernel(
     double bd[K];
     int32_t bi[K];
 #pragma unroll
-    // hw2: slots pre-filled with (1e10, 0), resultSet.hpp:35-42; nanoflann: worst = DBL_MAX (nanoflann.hpp:163)
-    for (int s = 0; s < K; s++) { bd[s] = SQ ? 1.7976931348623157e308 : 1e10; bi[s] = SQ ? -1 : 0; }
+    // hw2: slots pre-filled with (1e10, 0), resultSet.hpp:35-42 (HW2_UNUSED until the end, above); nanoflann: worst = DBL_MAX (nanoflann.hpp:163)
+    for (int s = 0; s < K; s++) { bd[s] = SQ ? 1.7976931348623157e308 : HW2_UNUSED; bi[s] = SQ ? -1 : 0; }
     const uint32_t slice_lo = blockIdx.y * tiles_per_slice * SF_TILE;
     const uint32_t slice_hi = (uint32_t)min((unsigned long long)n, (unsigned long long)slice_lo + (unsigned long long)tiles_per_slice * SF_TILE);
     for (uint32_t base = slice_lo; base < slice_hi; base += SF_TILE) {
@@ -85,11 +91,12 @@ __global__ __launch_bounds__(SF_BLOCK) void knn_f64_kernel(
     }
     if (qi < m) {
         const size_t o = ((size_t)blockIdx.y * m + qi) * (size_t)k_out;
+        const bool final = gridDim.y == 1;                   // (a slice's list keeps HW2_UNUSED for the merge)
 #pragma unroll
         for (int s = 0; s < K; s++) {
             if (s < k_out) {
                 idx_out[o + s] = bi[s];
-                dist_out[o + s] = bd[s];
+                dist_out[o + s] = (!SQ && final && bd[s] > 1e10) ? 1e10 : bd[s];
             }
         }
     }
@@ -97,11 +104,12 @@ __global__ __launch_bounds__(SF_BLOCK) void knn_f64_kernel(
 
 // one lane per query: the per-slice top-k lists (each sorted, slices in ascending index order) -> the final list.  An entry is
 // inserted only if strictly smaller than the current worst (equal distances keep the earlier = lower index, the canonical
-// rule); a slice's list is left as soon as one of its entries fails, the rest being no smaller.
+// rule); a slice's list is left as soon as one of its entries fails, the rest being no smaller.  empty_val is the value the slices' unused
+// slots carry (HW2_UNUSED / DBL_MAX: above every real entry, so they fail that test), empty_out the one the caller is promised.
 template <int K>
 __global__ __launch_bounds__(SF_BLOCK) void knn_merge_kernel(const int32_t* __restrict__ pidx, const double* __restrict__ pdist, uint32_t m, int k_out,
-                                                             uint32_t slices, double empty_val, int32_t empty_idx, int32_t* __restrict__ idx_out,
-                                                             double* __restrict__ dist_out)
+                                                             uint32_t slices, double empty_val, double empty_out, int32_t empty_idx,
+                                                             int32_t* __restrict__ idx_out, double* __restrict__ dist_out)
 {
     const uint32_t qi = blockIdx.x * SF_BLOCK + threadIdx.x;
     if (qi >= m) return;
@@ -114,7 +122,7 @@ __global__ __launch_bounds__(SF_BLOCK) void knn_merge_kernel(const int32_t* __re
         for (int e = 0; e < k_out; e++) {
             const double d = pdist[o + e];
             const int32_t j = pidx[o + e];
-            if (!(d < bd[K - 1]) || (d == empty_val && j == empty_idx)) break;       // (placeholders of a short slice never enter)
+            if (!(d < bd[K - 1])) break;                                             // (so do the unused slots of a short slice)
             double cd = d;
             int32_t ci = j;
             bool placed = false;
@@ -133,7 +141,7 @@ __global__ __launch_bounds__(SF_BLOCK) void knn_merge_kernel(const int32_t* __re
     }
 #pragma unroll
     for (int s = 0; s < K; s++)
-        if (s < k_out) { idx_out[(size_t)qi * k_out + s] = bi[s]; dist_out[(size_t)qi * k_out + s] = bd[s]; }
+        if (s < k_out) { idx_out[(size_t)qi * k_out + s] = bi[s]; dist_out[(size_t)qi * k_out + s] = bd[s] == empty_val ? empty_out : bd[s]; }
 }
 
 // FILL = false: counts[q] = #{j : s_j <= r2max}; FILL = true: write idx/dist at row_ptr[q]...
@@ -223,7 +231,7 @@ int launch_knn_f64(pcr_ctx* ctx, const double* db_soa, size_t n, size_t n_cap, c
                                (uint32_t)n, (uint32_t)n_cap, q_soa, (uint32_t)m, (uint32_t)m_cap, k, pidx, pdist, tps); \
         if (slices > 1)                                                                                         \
             hipLaunchKernelGGL((knn_merge_kernel<K>), dim3(blocks), dim3(SF_BLOCK), 0, ctx->stream, pidx, pdist, (uint32_t)m, k, slices, \
-                               squared ? 1.7976931348623157e308 : 1e10, squared ? -1 : 0, idx_dev, dist_dev);     \
+                               squared ? 1.7976931348623157e308 : HW2_UNUSED, squared ? 1.7976931348623157e308 : 1e10, squared ? -1 : 0, idx_dev, dist_dev); \
     } while (0)
     if (k <= 1) PCR_KNN(1);
     else if (k <= 4) PCR_KNN(4);

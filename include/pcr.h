@@ -183,7 +183,10 @@ int pcr_plane_mask_f64(pcr_ctx* ctx, const pcr_cloud* pts, const double plane4[4
  * replaces `KNNResultSet rs(k); KDTreeKNNSearch(root, db, rs, query)` per query
  * (Homework2/hw2/include/kdtree.hpp:329-364, benchmark.hpp:59-66).
  * db: n x 3 f64 AoS (vector<vector<double>> flattened), q: m x 3. idx/dist: m x k; empty slots (n < k)
- * hold (1e10, 0) like the pre-filled result set (resultSet.hpp:35-42). k <= 32. */
+ * hold (1e10, 0) like the pre-filled result set (resultSet.hpp:35-42). k <= 32.
+ * The 1e10 rule: that result set starts with worstDist = 1e10 and rejects dist > worstDist (resultSet.hpp:32,69), so
+ * a point at d > 1e10 is never a neighbour — its slot stays empty — and one at d == 1e10 exactly is, with its index.
+ * Every route of the search answers that way (the exhaustive scan, the grid batches, the one-wave calls). */
 int pcr_knn_f64(pcr_ctx* ctx, const double* db, size_t n, const double* q, size_t m, int k,
                 int32_t* idx, double* dist);
 /* ---- A11: radius search (kdtree.hpp:367-402, resultSet.hpp:130-140): all j with d <= r, CSR, ascending
@@ -259,14 +262,20 @@ int pcr_iss_keypoints_f32(pcr_ctx* ctx, const pcr_cloud* cloud, const pcr_iss_pa
  * hw2 / FLANN / nanoflann at dim 3 on the f32 coordinates widened to f64: s = ((dx*dx) + dy*dy) + dz*dz.
  * squared != 0: order and report s (FLANN / open3d / nanoflann contract), empty slots (DBL_MAX, -1); radius >= 0 adds the
  * hybrid-search cap s < radius^2 (strict, FLANN's KNNRadiusResultSet); radius < 0: none.
- * squared == 0: order and report d = sqrt(s) (hw2, kdtree.hpp:341-346), empty slots (1e10, 0) (resultSet.hpp:35-42).
+ * squared == 0: order and report d = sqrt(s) (hw2, kdtree.hpp:341-346), empty slots (1e10, 0) (resultSet.hpp:35-42);
+ * the 1e10 rule of pcr_knn_f64 holds: d > 1e10 is never a neighbour (not counted in `found`), d == 1e10 is one.  The
+ * squared mode has no such rule: every finite s below the cap is a neighbour.
+ * A non-finite database point is never a neighbour and a non-finite query finds nothing, in both modes.
  * Canonical order: value ascending, then index ascending.  idx, dist: m x k row-major; found (optional): m. */
 int pcr_cloud_knn_f64(pcr_ctx* ctx, const pcr_cloud* db, const pcr_cloud* queries, int k, double radius, int squared,
                       int32_t* idx, double* dist, uint32_t* found);
 /* pca_normal.py:89-103: normals[i] = eigenvector of the smallest eigenvalue of the scatter matrix of the <= k nearest
  * points within `radius` of point i (itself included; the reference: search_hybrid_vector_3d(radius = 5, max_nn = 10) +
  * PCA, :17-36), zeros when fewer than 3.  Sign and eigen-solver follow FastEigen3x3 (the reference's PCA_faster, :39-45;
- * np.linalg.eig leaves the sign unspecified).  normals: n x 3 f64. */
+ * np.linalg.eig leaves the sign unspecified) with ONE exception: a scatter matrix that is exactly diag(a, a, b) with a < b
+ * (a row of points along z) gets (1, 0, 0), where FastEigen3x3 answers (0, 0, 1) — the row's own direction, the
+ * eigenvector of the LARGEST eigenvalue.  pcr_fast_eigen3x3 below keeps the reference's answer.  Zeros also when the
+ * scatter matrix is zero (coincident neighbours).  normals: n x 3 f64. */
 int pcr_normals_knn_f64(pcr_ctx* ctx, const pcr_cloud* cloud, int k, double radius, double* normals);
 
 /* pca_normal.py:17-36 PCA(data, correlation = False, sort = True) of the whole cloud: eigenvalues descending, eigenvectors in

@@ -897,7 +897,9 @@ static vec3d fe_evec1(const double A[9], vec3d e0, double eval1)
     return v3_sub(v3_scale(U, m11), v3_scale(V, m01));
 }
 
-void orc_fast_eigen3x3(const double Ain[9], double normal[3])
+/* ref_ties: the answer for diag(a, a, b), a < b.  1: mylib.cpp:177-187 literally (no strict minimum on x or y -> z, the eigenvector of the
+ * LARGEST eigenvalue); 0: x, an eigenvector of the smallest one (the per-point normals, which are not pinned to that function). */
+static void fast_eigen3x3(const double Ain[9], double normal[3], int ref_ties)
 {
     double A[9];
     memcpy(A, Ain, sizeof A);
@@ -938,10 +940,13 @@ void orc_fast_eigen3x3(const double Ain[9], double normal[3])
         const double a0 = A[0] * max_coeff, a1 = A[4] * max_coeff, a2 = A[8] * max_coeff;
         if (a0 < a1 && a0 < a2) out = v3(1, 0, 0);
         else if (a1 < a0 && a1 < a2) out = v3(0, 1, 0);
+        else if (!ref_ties && a0 == a1 && a0 < a2) out = v3(1, 0, 0);
         else out = v3(0, 0, 1);
     }
     memcpy(normal, out.v, sizeof out.v);
 }
+
+void orc_fast_eigen3x3(const double A[9], double normal[3]) { fast_eigen3x3(A, normal, 1); }
 
 static int cmp_f32(const void* a, const void* b)
 {
@@ -1056,7 +1061,7 @@ void orc_normals_knn_f64(const float* x, const float* y, const float* z, size_t 
             xx += dx * dx; xy += dx * dy; xz += dx * dz; yy += dy * dy; yz += dy * dz; zz += dz * dz;   /* :22 */
         }
         const double XTX[9] = { xx, xy, xz, xy, yy, yz, xz, yz, zz };
-        orc_fast_eigen3x3(XTX, out);                                 /* PCA_faster :39-45 */
+        fast_eigen3x3(XTX, out, 0);                                  /* PCA_faster :39-45, but diag(a, a, b) -> x */
     }
     free(idx); free(ss);
 }

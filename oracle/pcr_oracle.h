@@ -226,7 +226,9 @@ size_t orc_ground_detection_f64(const float* x, const float* y, const float* z, 
 void orc_knn_sq_f32pts(const float* x, const float* y, const float* z, size_t n, const float* qx, const float* qy,
                        const float* qz, size_t m, int k, double cap_s, int32_t* idx, double* s_out, uint32_t* found);
 /* normals[i] = FastEigen3x3 of the scatter matrix (centre = sum / cnt, pca_normal.py:20-22) of point i's <= k nearest
- * points with s < radius^2, in ascending (s, index) order; zeros when fewer than 3 (:97). */
+ * points with s < radius^2, in ascending (s, index) order; zeros when fewer than 3 (:97).  One difference from
+ * FastEigen3x3: a scatter matrix that is exactly diag(a, a, b), a < b, gives (1, 0, 0) — that function answers
+ * (0, 0, 1) there, the eigenvector of the largest eigenvalue (a row of points along z would get its own direction). */
 void orc_normals_knn_f64(const float* x, const float* y, const float* z, size_t n, int k, double radius, double* normals);
 
 /* ---- ICPpoint2plane (Homework9/hw9/src/registration.cpp:710-860), the point-to-plane sibling of A9 on the same 1-NN loop.
