@@ -130,7 +130,7 @@ ABI_SYMBOLS = [
     "pcr_prof_reset", "pcr_prof_get", "pcr_prof_get_each", "pcr_tune_set",
     "pcr_grid_stats", "pcr_nn1_stats", "pcr_selftest_mfma_bf16", "pcr_selftest_mfma_f16", "pcr_selftest_mfma_bf16_v2", "pcr_selftest_mfma_f16_v2", "pcr_selftest_sign_f16", "pcr_selftest_sphere_f16", "pcr_ctx_mfma_check", "pcr_voxel_filter_f32", "pcr_iss_keypoints_f32", "pcr_icp_p2plane_f32", "pcr_cloud_knn_f64", "pcr_normals_knn_f64", "pcr_cloud_pca_f64", "pcr_fast_eigen3x3", "pcr_ground_seeds_f64", "pcr_ground_detection_f64",
     "pcr_nn1_desc_f32", "pcr_match_union_f32", "pcr_match_inter_f32", "pcr_ransac_sample_quads", "pcr_consensus_count_f32", "pcr_ransac_global_f32", "pcr_db64_create", "pcr_db64_destroy", "pcr_db64_size", "pcr_db64_knn", "pcr_db64_radius",
-    "pcr_ctx_trim", "pcr_ctx_parked_bytes", "pcr_cloud_shard_spatial", "pcr_cloud_global_index", "pcr_cloud_sort_for_target", "pcr_nn1_f32_loop",
+    "pcr_ctx_trim", "pcr_ctx_parked_bytes", "pcr_ctx_knn_coop_state", "pcr_cloud_shard_spatial", "pcr_cloud_global_index", "pcr_cloud_sort_for_target", "pcr_nn1_f32_loop",
     "pcr_db64_radius_rows", "pcr_rows_destroy", "pcr_rows_info", "pcr_rows_row_ptr", "pcr_rows_fetch", "pcr_rows_reduce", "pcr_rows_moments",
     "pcr_dbscan_f32", "pcr_statistical_outlier_f32", "pcr_fpfh33_f32", "pcr_harris3d_f32", "pcr_voxel_grid_normals_f32", "pcr_normal_space_sample_f32",
     "pcr_fps_f32", "pcr_ball_query_f32", "pcr_group_points_f32", "pcr_objects_from_labels_f32", "pcr_points_in_boxes_f64", "pcr_label_aabb_f32",
@@ -183,6 +183,7 @@ def lib():
     L.pcr_cloud_shard_spatial.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
     L.pcr_cloud_global_index.argtypes = [vp, vp, vp]
     L.pcr_ctx_parked_bytes.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.pcr_ctx_knn_coop_state.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.pcr_cloud_sort_for_target.argtypes = [vp, vp, vp, vp]
     L.pcr_nn1_f32_loop.argtypes = [vp, vp, vp, C.c_float]
     L.pcr_transform_f32.argtypes = [vp, vp, vp]
@@ -1371,6 +1372,13 @@ class Context:
         b = C.c_uint64()
         self._ck(lib().pcr_ctx_parked_bytes(self.h, C.byref(b)))
         return int(b.value)
+
+    def knn_coop_state(self) -> dict:
+        """The one-wave k-NN route's ticket (read behind a stream synchronisation), the m of its last call, its calls so far and those that fell back
+        to a stream synchronisation (pcr_ctx_knn_coop_state)."""
+        t, m, c, u = C.c_uint32(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._ck(lib().pcr_ctx_knn_coop_state(self.h, C.byref(t), C.byref(m), C.byref(c), C.byref(u)))
+        return {"ticket": int(t.value), "m": int(m.value), "calls": int(c.value), "unseen": int(u.value)}
 
     def nn1_fetch(self, n: int):
         idx = np.empty(n, np.uint32)

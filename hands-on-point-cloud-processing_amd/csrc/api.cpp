@@ -2,6 +2,7 @@
 #include "pcr_internal.hpp"
 #include "numerics.hpp"
 
+#include <atomic>
 #include <cmath>
 #include <limits>
 #include <new>
@@ -121,8 +122,17 @@ void prof_flush(pcr_ctx* ctx)
     }
 }
 
+uint64_t next_serial()
+{
+    static std::atomic<uint64_t> serial{ 0 };
+    return ++serial;                      // (never 0: "none")
+}
+
+// THE place where what anybody remembers about a cloud's content ends: its own indices go, and the fresh rev makes every context's
+// record of a search on it (keys_are_of, wpos_is_of) a record of something else
 void cloud_modified(pcr_cloud* c)
 {
+    if (c) c->rev = next_serial();
     if (c && c->grid) { grid_free(c->grid); c->grid = nullptr; }
     if (c && c->bt) { bt_free(c->bt); c->bt = nullptr; }
     if (c && c->knn_grid) { grid_free(c->knn_grid); c->knn_grid = nullptr; c->knn_grid_factor = 0.0; }
@@ -185,10 +195,11 @@ int cloud_alloc(pcr_ctx* ctx, size_t n, pcr_cloud** out)
 
 static void cloud_forget(pcr_ctx* ctx, pcr_cloud* c)
 {
-    if (ctx && ctx->qperm_src == c) ctx->qperm_src = nullptr;
-    if (ctx && ctx->keys_src == c) ctx->keys_src = nullptr;
-    if (ctx && ctx->keys_tgt == c) { ctx->keys_tgt = nullptr; ctx->keys_warm = false; ctx->wpos_valid = false; }
-    if (ctx && (ctx->keys_seed_src == c || ctx->keys_seed_tgt == c)) { ctx->keys_seeded = false; ctx->keys_seed_src = ctx->keys_seed_tgt = nullptr; }
+    // (tidiness on the context the handle leaves through: an id is never handed out again, so a record of it on ANOTHER context matches nothing either)
+    if (ctx && c && ctx->qperm_src == c->id) ctx->qperm_src = 0;
+    if (ctx && c && ctx->keys_src == c->id) ctx->keys_src = 0;
+    if (ctx && c && ctx->keys_tgt == c->id) { ctx->keys_tgt = 0; ctx->keys_warm = false; ctx->wpos_valid = false; }
+    if (ctx && c && (ctx->keys_seed_src == c->id || ctx->keys_seed_tgt == c->id)) { ctx->keys_seeded = false; ctx->keys_seed_src = ctx->keys_seed_tgt = 0; }
     cloud_modified(c);
 }
 
@@ -437,6 +448,21 @@ int pcr_ctx_parked_bytes(const pcr_ctx* ctx, uint64_t* bytes)
     return PCR_OK;
 }
 
+int pcr_ctx_knn_coop_state(pcr_ctx* ctx, uint32_t* ticket, uint64_t* m, uint64_t* calls, uint64_t* unseen)
+{
+    if (!ctx) return PCR_ERR_ARG;
+    PCR_HIP(ctx, hipSetDevice(ctx->device));
+    PCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (ticket) {
+        *ticket = 0;
+        if (ctx->coop_ticket) PCR_HIP(ctx, hipMemcpy(ticket, ctx->coop_ticket, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    }
+    if (m) *m = ctx->coop_m;
+    if (calls) *calls = ctx->coop_calls;
+    if (unseen) *unseen = ctx->coop_unseen;
+    return PCR_OK;
+}
+
 int pcr_ctx_trim(pcr_ctx* ctx)
 {
     if (!ctx) return PCR_ERR_ARG;
@@ -452,7 +478,9 @@ int pcr_nn1_f32_async(pcr_ctx* ctx, const pcr_cloud* tgt, const pcr_cloud* src)
     if (!ctx || !tgt || !src) return fail(ctx, PCR_ERR_ARG, "pcr_nn1_f32_async");
     // tune "nn1_async_in_loop" = 1: the caller iterates (its own ICP-style loop on the same pair) — the search may then be seeded by the
     // correspondences of its previous call exactly as the searches inside pcr_icp_p2p_f32 are (same results, bit for bit)
-    return launch_nn1(ctx, tgt, src, tune_get(ctx, "nn1_async_in_loop", 0) > 0);
+    const int rc = launch_nn1(ctx, tgt, src, tune_get(ctx, "nn1_async_in_loop", 0) > 0);
+    ctx->keys_caller = rc == PCR_OK;
+    return rc;
 }
 
 int pcr_nn1_f32_loop(pcr_ctx* ctx, const pcr_cloud* tgt, const pcr_cloud* src, float max_corr)
@@ -462,6 +490,7 @@ int pcr_nn1_f32_loop(pcr_ctx* ctx, const pcr_cloud* tgt, const pcr_cloud* src, f
     const LoopHint hint(ctx, 1000);       // (the dispatcher's rule for loops, as in pcr_cloud_sort_for_target)
     int rc = launch_nn1(ctx, tgt, src, true, gate);
     if (rc == PCR_OK && !nn1_auto_grid(ctx, tgt, true, src->n)) rc = launch_nn1_gate(ctx, src->n, gate);
+    ctx->keys_caller = rc == PCR_OK;
     return rc;
 }
 
@@ -506,6 +535,8 @@ int pcr_nn1_fetch(pcr_ctx* ctx, size_t n, uint32_t* idx, float* d2)
 {
     if (!ctx || n != ctx->keys_n || (n && (!idx || !d2))) return fail(ctx, PCR_ERR_ARG, "pcr_nn1_fetch");
     if (n == 0) return PCR_OK;
+    // an ICP call searched on this context since (pcr_icp_p2p_f32, pcr_icp_p2plane_f32: nothing else writes keys[]): the workspace holds ITS correspondences
+    if (!ctx->keys_caller) return fail(ctx, PCR_ERR_STATE, "pcr_nn1_fetch: the last search on this context was not a pcr_nn1_f32_async / pcr_nn1_f32_loop");
     uint32_t* idx_dev;
     float* d2_dev;
     Layout L;
@@ -548,6 +579,9 @@ int pcr_kabsch_sums(pcr_ctx* ctx, const pcr_cloud* tgt, const pcr_cloud* src, fl
         if (last_d2) *last_d2 = 0.f;
         return PCR_OK;
     }
+    // the pairs are those of the caller's last search, which must be the search of THIS pair as both clouds are now (include/pcr.h)
+    if (!ctx->keys_caller || !keys_are_of(ctx, tgt, src))
+        return fail(ctx, PCR_ERR_STATE, "pcr_kabsch_sums: the last search on this context was not pcr_nn1_f32_async / _loop of this target and source as they are now");
     KabschPlan plan;
     int rc = kabsch_plan(ctx, tgt, max_corr, &plan);
     if (rc) return rc;

@@ -1367,7 +1367,7 @@ static int sort_queries(pcr_ctx* ctx, const Grid* g, const pcr_cloud* src)
     hipLaunchKernelGGL(scatter_perm_kernel, gridn, dim3(GR_BLOCK), 0, ctx->stream, (uint32_t)n, cell_of, start, count, ctx->qperm);
     PCR_HIP(ctx, hipGetLastError());
     ctx->qperm_n = n;
-    ctx->qperm_src = src;
+    ctx->qperm_src = src->id;
     return PCR_OK;
 }
 
@@ -1449,7 +1449,7 @@ static int sort_queries_fine(pcr_ctx* ctx, const Grid* g, const pcr_cloud* src)
         PCR_HIP(ctx, pin_word_begin(ctx, 0, runs, &src->cells_tag));
     }
     ctx->qperm_n = n;
-    ctx->qperm_src = src;
+    ctx->qperm_src = src->id;
     return PCR_OK;
 }
 
@@ -2042,7 +2042,7 @@ int grid_sort_working_cloud(pcr_ctx* ctx, const pcr_cloud* tgt, pcr_cloud** work
     hipError_t e = permute_into_sorted(ctx, w, sorted, ctx->qperm, hipSuccess);
     if (e == hipSuccess) e = hipMemcpyAsync(orig, ctx->qperm, n * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream);
     if ((rc = adopt_sorted_cloud(ctx, work, sorted, orig, in_place, e, "grid_sort_working_cloud"))) return rc;
-    ctx->qperm_src = nullptr;                                      // the permutation belongs to the cloud that no longer exists
+    ctx->qperm_src = 0;                                      // the permutation belongs to the cloud that no longer exists
     return PCR_OK;
 }
 
@@ -2138,7 +2138,7 @@ int cloud_shard_spatial(pcr_ctx* ctx, const pcr_cloud* tgt, const pcr_cloud* ful
     if (n) {
         rc = sort_queries_fine(ctx, tgt->grid, full);          // ctx->qperm[t] = original index of the point at sorted position t (radix sort: stable, deterministic)
         if (rc) return rc;
-        ctx->qperm_src = nullptr;                             // (the order belongs to `full`, which no search will use)
+        ctx->qperm_src = 0;                             // (the order belongs to `full`, which no search will use)
         Layout L;
         L.add(&member, n);
         L.add(&pos, n);
@@ -2190,7 +2190,7 @@ int launch_nn1_grid(pcr_ctx* ctx, const pcr_cloud* tgt, const pcr_cloud* src, bo
     ctx->keys_n = ns;
     // the working cloud of an ICP loop is already in cell order (grid_sort_working_cloud): no permutation to read
     const bool sorted = reuse_perm && src->orig && tgt->grid;
-    const bool have_perm = sorted || (reuse_perm && tgt->grid && ctx->qperm && ctx->qperm_n == ns && ctx->qperm_src == src);
+    const bool have_perm = sorted || (reuse_perm && tgt->grid && ctx->qperm && ctx->qperm_n == ns && ctx->qperm_src == src->id);
     if (!have_perm) {
         rc = grid_prepare_queries(ctx, tgt, src);
         if (rc) return rc;
@@ -2207,13 +2207,12 @@ int launch_nn1_grid(pcr_ctx* ctx, const pcr_cloud* tgt, const pcr_cloud* src, bo
     // Unlike the exhaustive kernels (nn1_brute.hip), the grid walk TRUSTS its seed — the radius jumps to the one that proves it —
     // so only the previous iteration of the same cloud object qualifies: correspondences left by another source cloud of the
     // same size would be valid but arbitrarily bad candidates (measured: a 5-iteration ICP 0.93 -> 12.5 ms, profiles/r01_tune_grid.txt).
-    int warm = (reuse_perm && ctx->keys_warm && ctx->keys_src == src && ctx->keys_warm_n == ns &&
+    int warm = (reuse_perm && ctx->keys_warm && ctx->keys_src == src->id && ctx->keys_warm_n == ns &&
                 tune_get(ctx, "grid_warm_start", 1) > 0) ? 1 : 0;
-    if (warm && ctx->wpos_valid && ctx->wpos_n == ns && ctx->wpos) warm = 2;      // the winners' record positions are there: seed from the records
+    if (warm && wpos_is_of(ctx, tgt, ns)) warm = 2;      // the winners' record positions IN THIS GRID are there: seed from the records
     ctx->keys_warm = reuse_perm;
     ctx->keys_warm_n = ns;
-    ctx->keys_src = src;
-    ctx->keys_tgt = tgt;
+    keys_record(ctx, tgt, src);
     // search kernel (tune grid_mode: 0 auto, 1 plain, 2 x-window clipping, 3 bounding spheres):
     //   spheres  — Morton-ordered index (large targets, build_target_grid): runs of 16 records are tested by their bounding sphere first;
     //   clipping — x-sorted index of a large target: 14.1 -> 8.1 ms per search at 10 M x 10 M in round 1 (1 277 -> 462 candidates per query);
@@ -2253,6 +2252,7 @@ int launch_nn1_grid(pcr_ctx* ctx, const pcr_cloud* tgt, const pcr_cloud* src, bo
     if (warm == 2 && mode == 2 && tune_get(ctx, "grid_seed_run", 1) == 1) warm = 3;
     ctx->wpos_valid = wpos != nullptr;
     ctx->wpos_n = ns;
+    ctx->wpos_tgt = tgt->id; ctx->wpos_tgt_rev = tgt->rev;
     // XCD-aware workgroup -> query-block mapping for large batches (tune grid_xcd_run: run length in workgroups, -1 = identity)
     int64_t run = tune_get(ctx, "grid_xcd_run", 0);
     const size_t nblocks = (ns * (size_t)G + GR_BLOCK - 1) / GR_BLOCK;

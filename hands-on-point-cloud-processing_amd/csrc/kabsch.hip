@@ -386,7 +386,8 @@ int launch_kabsch_partial(pcr_ctx* ctx, const pcr_cloud* tgt, const pcr_cloud* s
     if (ctx->keys_n != ns) return fail(ctx, PCR_ERR_STATE, "kabsch: no matching correspondence pass");
     const uint32_t blocks = kabsch_blocks(ctx, ns);
     // the grid search of an ICP loop leaves the record position of every winner behind (ctx->wpos): gather from the records
-    const bool rec = ctx->wpos_valid && ctx->wpos_n == ns && tgt->grid && tgt->grid->records && tune_get(ctx, "kabsch_records", 1) == 1;
+    // — of THIS target's grid as it is now (wpos_is_of): after a rebuild the same positions name other points
+    const bool rec = wpos_is_of(ctx, tgt, ns) && tgt->grid->records && tune_get(ctx, "kabsch_records", 1) == 1;
     const uint32_t* orig = src->orig;     // (the cloud's own mapping: no other call on the context resets it — test_context_state.py §B)
     {
         ProfScope p(ctx, "kabsch_partial");
@@ -1227,7 +1228,7 @@ static SeedArgs seed_args(pcr_ctx* ctx, const pcr_cloud* c, const pcr_cloud* see
     ctx->keys_seeded = false;
     if (seed_tgt && ctx->keys && ctx->keys_n == c->n && c->n) {
         sd = SeedArgs{ seed_tgt->x(), seed_tgt->y(), seed_tgt->z(), ctx->keys, (uint32_t)seed_tgt->n };
-        ctx->keys_seeded = true; ctx->keys_seed_src = c; ctx->keys_seed_tgt = seed_tgt;
+        ctx->keys_seeded = true; ctx->keys_seed_src = c->id; ctx->keys_seed_tgt = seed_tgt->id;
     }
     return sd;
 }

@@ -461,6 +461,7 @@ static int cloud_knn_coop(pcr_ctx* ctx, const Grid* g, const float* q_rows, size
     // the ticket counts waves modulo m: a call must find it at a multiple of m (the previous call used another m: reset it, in stream order)
     if (ctx->coop_m != m) { PCR_HIP(ctx, hipMemsetAsync(ctx->coop_ticket, 0, 4, ctx->stream)); ctx->coop_m = m; }
     const uint32_t target = ++ctx->coop_seq;
+    ctx->coop_calls++;
 #define PCR_KC(KK)                                                                                                                          \
     do {                                                                                                                                    \
         if (squared)                                                                                                                        \
@@ -488,6 +489,7 @@ static int cloud_knn_coop(pcr_ctx* ctx, const Grid* g, const float* q_rows, size
     std::atomic_thread_fence(std::memory_order_acquire);
     if (!seen) {
         // (a wave count the ticket did not expect, a failed launch ...: the stream settles it; the ticket restarts from zero)
+        ctx->coop_unseen++;
         PCR_HIP(ctx, hipStreamSynchronize(ctx->stream));
         PCR_HIP(ctx, hipMemsetAsync(ctx->coop_ticket, 0, 4, ctx->stream));
     }

@@ -1486,10 +1486,10 @@ int launch_nn1_brute(pcr_ctx* ctx, const pcr_cloud* tgt, const pcr_cloud* src, b
     if (ns == 0) { ctx->keys_n = 0; return PCR_OK; }
     if (ns > 0xFFFFFFF0ull || tgt->n > 0xFFFFFFF0ull) return fail(ctx, PCR_ERR_ARG, "cloud too large for u32 indices");
     // keys[] still holds this source's correspondences of the previous ICP iteration?
-    const bool warm = in_loop && ctx->keys_warm && (ctx->keys_src == src || ctx->keys_tgt == tgt) && ctx->keys_warm_n == ns &&
+    const bool warm = in_loop && ctx->keys_warm && (ctx->keys_src == src->id || ctx->keys_tgt == tgt->id) && ctx->keys_warm_n == ns &&
                       tune_get(ctx, "nn1_warm_start", 1) == 1;
     // ... and the move of the previous iteration already turned them into this search's seeds (kabsch.hip seed_next_search)?
-    const bool pre_seeded = warm && ctx->keys_seeded && ctx->keys_seed_src == src && ctx->keys_seed_tgt == tgt && ctx->keys_n == ns;
+    const bool pre_seeded = warm && ctx->keys_seeded && ctx->keys_seed_src == src->id && ctx->keys_seed_tgt == tgt->id && ctx->keys_n == ns;
     ctx->keys_seeded = false;
     ctx->nn1_move_l0 = 0; ctx->nn1_moved = false;      // (set by launch_matrix alone: every other family leaves "no")
     int rc = ensure_keys(ctx, ns);
@@ -1498,8 +1498,7 @@ int launch_nn1_brute(pcr_ctx* ctx, const pcr_cloud* tgt, const pcr_cloud* src, b
     ctx->wpos_valid = false;              // keys[] is about to be rewritten without record positions
     ctx->keys_warm = in_loop;
     ctx->keys_warm_n = ns;
-    ctx->keys_src = src;
-    ctx->keys_tgt = tgt;
+    keys_record(ctx, tgt, src);
 
     const int64_t variant = tune_get(ctx, "nn1_variant", 0), bf16_tune = tune_get(ctx, "nn1_bf16", 0), f16_tune = tune_get(ctx, "nn1_f16", 0);
     // The matrix-core forms, from a target's FIRST search on: the index (operands in Morton order, bt_ensure) costs one bounding-box

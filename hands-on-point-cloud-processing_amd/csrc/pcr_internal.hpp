@@ -103,9 +103,16 @@ struct GridFree { void operator()(Grid* g) const { grid_free(g); } };
 struct BtFree { void operator()(BtIndex* b) const { bt_free(b); } };
 using GridPtr = std::unique_ptr<Grid, GridFree>;
 using BtPtr = std::unique_ptr<BtIndex, BtFree>;
+// Handles are told apart by serial numbers, never by address (operator new readily returns the address of the cloud just deleted): a number
+// is handed out once per process, so it names one handle, or one state of its content, on every context (api.cpp)
+uint64_t next_serial();
 }
 
 struct pcr_cloud {
+    // id: this handle, for its whole life.  rev: what it holds — cloud_modified takes a fresh one, and with it everything a context remembers
+    // about the CONTENT of this cloud (keys[], wpos; pcr_ctx::keys_*) stops matching, whatever context the change went through
+    const uint64_t id = pcr::next_serial();
+    uint64_t rev = id;
     pcr::Grid* grid = nullptr;   // exact-NN index over this cloud as a target; built lazily, dropped on modification
     pcr::BtIndex* bt = nullptr;  // the matrix-core brute-force filter's operands over this cloud as a target (nn1_brute.hip); same lifetime
     pcr::Grid* knn_grid = nullptr;   // the same index with the wider cell of the last k-NN batch (knn_grid.hip), same lifetime
@@ -159,24 +166,27 @@ struct pcr_ctx {
     // the result wrong; the bookkeeping below only decides whether the seeds are likely to be GOOD: same source cloud (the
     // previous iteration), or another same-sized source against the same target (the previous ICP run on this pair).
     bool keys_warm = false;               // keys[] was written by a search of an ICP loop
-    const pcr_cloud* keys_src = nullptr;  // its source (identity only; reset when the cloud is destroyed)
-    const pcr_cloud* keys_tgt = nullptr;  // its target (identity only; reset when the cloud is destroyed)
+    uint64_t keys_src = 0;                // its source (pcr_cloud::id, 0 = none: identity only — a loop moves its source between searches)
+    uint64_t keys_tgt = 0;                // its target (pcr_cloud::id, 0 = none)
+    uint64_t keys_src_rev = 0, keys_tgt_rev = 0;   // pcr_cloud::rev of both when keys[] was written: what keys[] is the correspondence OF
+    bool keys_caller = false;             // keys[] answers a caller's own search (pcr_nn1_f32_async / _loop), not a search inside another stage
     size_t keys_warm_n = 0;               // number of queries of that search
     // the last move of an ICP loop already turned keys[] into the seeds of the next exhaustive search of (keys_seed_src, keys_seed_tgt):
     // launch_nn1_brute then skips its own seed kernel (consumed by the next search, whatever it is)
     bool keys_seeded = false;
-    const pcr_cloud* keys_seed_src = nullptr;
-    const pcr_cloud* keys_seed_tgt = nullptr;
+    uint64_t keys_seed_src = 0;           // (pcr_cloud::id)
+    uint64_t keys_seed_tgt = 0;
     uint32_t* qperm = nullptr;            // queries grouped by target-grid cell (grid NN)
     size_t qperm_cap = 0;
     size_t qperm_n = 0;
-    const pcr_cloud* qperm_src = nullptr;
+    uint64_t qperm_src = 0;               // (pcr_cloud::id, 0 = nobody's)
     // grid ICP: the working cloud is cell-sorted once (work_orig[t] = original index of its point t), and every search leaves
     // the record position of each winner behind (wpos) for the next warm start and for the Kabsch gather
     uint32_t* wpos = nullptr;
     size_t wpos_cap = 0;
     size_t wpos_n = 0;
     bool wpos_valid = false;
+    uint64_t wpos_tgt = 0, wpos_tgt_rev = 0;   // the target whose grid the positions index: (id, rev) — a rebuilt grid has another record order
     uint32_t* work_orig = nullptr;        // (the storage of the working copy's pcr_cloud::orig)
     size_t work_orig_cap = 0;
     // two spare cloud buffers (base, cap): the working copies an ICP call clones and gives back (cloud_release) are re-used by the next
@@ -199,7 +209,7 @@ struct pcr_ctx {
     double* dev_out = nullptr;            // 128 doubles: reduced sums / limbs + bookkeeping
     double* host_out = nullptr;           // pinned mirror
     void* plane_ws = nullptr;             // plane.hip: [ticket | pad to 256 B][partial counts per workgroup]
-    size_t plane_ws_bytes = 0, plane_ws_tick = 0;
+    size_t plane_ws_bytes = 0;
     void* scratch = nullptr;              // generic device scratch
     size_t scratch_cap = 0;
     void* host_stage = nullptr;           // pinned staging for uploads / downloads
@@ -208,6 +218,7 @@ struct pcr_ctx {
     uint32_t* coop_ticket = nullptr;      // its wave ticket (device memory)
     uint32_t coop_seq = 0;                // value the completion word takes at the end of the next call
     size_t coop_m = 0;                    // queries of the last call (the ticket counts modulo m)
+    uint64_t coop_calls = 0, coop_unseen = 0;   // one-wave calls so far; those whose completion word did not show up in time (pcr_ctx_knn_coop_state)
     void* aux = nullptr;                  // second device scratch (partial results of sliced searches), grows on demand
     size_t aux_cap = 0;
     pcr::IcpState* icp_state_dev = nullptr;    // pipelined ICP: device state, pinned snapshots, snapshot events
@@ -338,6 +349,23 @@ struct LoopHint {
 };
 int launch_nn1(pcr_ctx* ctx, const pcr_cloud* tgt, const pcr_cloud* src, bool reuse_perm, float cap2 = __builtin_inff());
 void cloud_modified(pcr_cloud* c);
+// What a context remembers about clouds, asked in ONE place each.  Every search writes keys_record; nobody compares an address.
+inline void keys_record(pcr_ctx* ctx, const pcr_cloud* tgt, const pcr_cloud* src)
+{
+    ctx->keys_src = src->id; ctx->keys_src_rev = src->rev;
+    ctx->keys_tgt = tgt->id; ctx->keys_tgt_rev = tgt->rev;
+    ctx->keys_caller = false;             // (pcr_nn1_f32_async / _loop set it once their search is enqueued)
+}
+// keys[] is the correspondence of exactly this pair as both clouds are NOW (what pcr_kabsch_sums needs)
+inline bool keys_are_of(const pcr_ctx* ctx, const pcr_cloud* tgt, const pcr_cloud* src)
+{
+    return ctx->keys_n == src->n && ctx->keys_src == src->id && ctx->keys_src_rev == src->rev && ctx->keys_tgt == tgt->id && ctx->keys_tgt_rev == tgt->rev;
+}
+// wpos[] indexes the records of the grid tgt has now: written against this target, which was not modified (its grid not rebuilt) since
+inline bool wpos_is_of(const pcr_ctx* ctx, const pcr_cloud* tgt, size_t ns)
+{
+    return ctx->wpos_valid && ctx->wpos && ctx->wpos_n == ns && ctx->wpos_tgt == tgt->id && ctx->wpos_tgt_rev == tgt->rev && tgt->grid != nullptr;
+}
 // gives a cloud back WITHOUT synchronising the stream: its buffer goes to the context's spare slots (or is freed when both are taken).
 // Safe for work enqueued on ctx->stream that still reads the cloud: the buffer stays allocated, and whoever gets it next writes it on
 // the same stream.  (pcr_cloud_destroy = the same behind a stream synchronisation: the public contract.)

@@ -68,6 +68,12 @@ int pcr_cloud_destroy(pcr_ctx* ctx, pcr_cloud* c);
  * as soon as a call needs another size) so that the next call's clone costs no hipMalloc / hipFree.  pcr_ctx_trim frees what is parked. */
 int pcr_ctx_trim(pcr_ctx* ctx);
 int pcr_ctx_parked_bytes(const pcr_ctx* ctx, uint64_t* bytes);   /* HBM held by those parked buffers right now */
+/* DIAGNOSTIC, no stability promise (it may change or go with the route it describes; nothing but tests should call it).
+ * The one-wave-per-query k-NN route (at most 16 host queries on a handle): the ticket its waves draw from, read behind a
+ * stream synchronisation, the batch size m of the last call, the calls so far and those whose completion word did not show up in time (they
+ * fell back to a stream synchronisation).  The wave that draws ticket m - 1 modulo m publishes the completion word, so between calls the
+ * ticket is a multiple of the last m: a call with another m starts it from zero.  Any pointer may be NULL. */
+int pcr_ctx_knn_coop_state(pcr_ctx* ctx, uint32_t* ticket, uint64_t* m, uint64_t* calls, uint64_t* unseen);
 
 /* ---- A6 (search): 1-NN correspondence, brute force over LDS-tiled targets ----------------------------
  * replaces the loop `for i: tar_mat_index.index->findNeighbors(result_set, query, ...)`,
@@ -90,7 +96,13 @@ int pcr_nn1_f32_async(pcr_ctx* ctx, const pcr_cloud* tgt, const pcr_cloud* src);
  *   "none" (idx UINT32_MAX, d2 +inf) instead of with a neighbour the caller would discard.  Same kept pairs, same sums, bit for bit. */
 int pcr_cloud_sort_for_target(pcr_ctx* ctx, const pcr_cloud* tgt, pcr_cloud* cloud, uint32_t* orig_index);
 int pcr_nn1_f32_loop(pcr_ctx* ctx, const pcr_cloud* tgt, const pcr_cloud* src, float max_corr);
-/* fetch the results of the last pcr_nn1_f32_async for n queries */
+/* fetch the results of the caller's last pcr_nn1_f32_async / pcr_nn1_f32_loop for n queries.
+ * WHICH SEARCH: the context has ONE result workspace, and every stage that searches writes it — the two calls above, and inside the library
+ * the searches of pcr_icp_p2p_f32 and pcr_icp_p2plane_f32.  pcr_nn1_fetch answers only while the LAST search on the context was one of
+ * the caller's two: after an ICP call it returns PCR_ERR_STATE (n != the size of the last search: PCR_ERR_ARG), never the loop's
+ * correspondences.  Every other stage (pcr_cloud_sort_for_target and pcr_cloud_shard_spatial, which order queries but pair nothing; k-NN,
+ * radius, normals, voxel grids, descriptors, clustering, PointNet rows, ...) leaves the workspace alone, and so does anything done to the
+ * clouds afterwards: the rows are a record of the search as it ran, indices in the target's numbering at that time. */
 int pcr_nn1_fetch(pcr_ctx* ctx, size_t n, uint32_t* idx, float* d2);
 
 /* ---- A8: transformCloudInplace, Homework9/hw9/src/registration.cpp:165-178 ---------------------------
@@ -100,7 +112,12 @@ int pcr_transform_f32(pcr_ctx* ctx, pcr_cloud* cloud, const float T[16]);
 /* ---- A7 (accumulate): cross-covariance sums over the kept pairs of the last pcr_nn1_f32_async ---------
  * sums[0..2] = sum p, [3..5] = sum q, [6..14] = sum q_r p_c (row-major, rows = target), [15] = count,
  * f64, over pairs with d2 < max_corr (squared distance vs un-squared parameter, registration.cpp:936).
- * last_kept: index of the last kept source or -1; last_d2: its squared distance (loss, :939). */
+ * last_kept: index of the last kept source or -1; last_d2: its squared distance (loss, :939).
+ * WHICH SEARCH: as for pcr_nn1_fetch the last search on the context must be the caller's own, and here it must be the search of exactly
+ * (tgt, src) — the same two handles — with neither modified since (pcr_transform_f32, pcr_cloud_assign, an in-place
+ * pcr_cloud_sort_for_target, destroy + create: a new handle is a new cloud even at the old address).  The sums pair src's points as they are
+ * now with the target points the search named, so a cloud that moved or changed order in between would give sums of pairs that never
+ * were: PCR_ERR_STATE instead.  (A loop therefore runs search -> sums -> transform, as pcr_icp_p2p_f32 does.) */
 int pcr_kabsch_sums(pcr_ctx* ctx, const pcr_cloud* tgt, const pcr_cloud* src, float max_corr,
                     double sums[16], int64_t* last_kept, float* last_d2);
 /* ---- A7 (solve): registration.cpp:979-998 incl. the det<0 branch (:990-996). Host, f64. -------------- */
