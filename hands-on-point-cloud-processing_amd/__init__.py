@@ -118,6 +118,16 @@ class OptimInfo(C.Structure):
 
 OPTIM_ADAM, OPTIM_SGD = 1, 2
 
+
+class KittiCurve(C.Structure):
+    """pcr_kitti_curve: one (metric, difficulty) of pcr_kitti_eval_f64"""
+    _fields_ = [("n_gt", C.c_uint64), ("n_thresholds", C.c_int32), ("has_aos", C.c_int32), ("thresholds", C.c_double * 41),
+                ("tp", C.c_int64 * 41), ("fp", C.c_int64 * 41), ("fn", C.c_int64 * 41), ("similarity", C.c_double * 41),
+                ("precision", C.c_double * 41), ("aos", C.c_double * 41)]
+
+
+KITTI_IMAGE, KITTI_GROUND, KITTI_BOX3D = 0, 1, 2
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_int)
 
 # every symbol include/pcr.h declares (checked by tests/test_abi.py against the header text)
@@ -134,6 +144,7 @@ ABI_SYMBOLS = [
     "pcr_db64_radius_rows", "pcr_rows_destroy", "pcr_rows_info", "pcr_rows_row_ptr", "pcr_rows_fetch", "pcr_rows_reduce", "pcr_rows_moments",
     "pcr_dbscan_f32", "pcr_statistical_outlier_f32", "pcr_fpfh33_f32", "pcr_harris3d_f32", "pcr_voxel_grid_normals_f32", "pcr_normal_space_sample_f32",
     "pcr_fps_f32", "pcr_ball_query_f32", "pcr_group_points_f32", "pcr_objects_from_labels_f32", "pcr_points_in_boxes_f64", "pcr_label_aabb_f32",
+    "pcr_box_overlap_f64", "pcr_kitti_clean_data_f64", "pcr_kitti_frame_stats_f64", "pcr_kitti_thresholds_f64", "pcr_kitti_eval_f64",
     "pcr_pn2_model_create", "pcr_pn2_model_destroy", "pcr_pn2_model_info", "pcr_sa_mlp_max_f32", "pcr_pn2_forward_f32",
     "pcr_pn2_msg_model_create", "pcr_pn2_msg_model_info", "pcr_ball_query_multi_f32", "pcr_sa_msg_mlp_max_f32",
     "pcr_pn1_model_create", "pcr_pn1_model_info", "pcr_pointwise_chain_max_f32", "pcr_pointnet_forward_f32",
@@ -261,6 +272,11 @@ def lib():
     L.pcr_objects_from_labels_f32.argtypes = [vp, vp, vp, sz, sz, C.c_double, C.c_double, vp, C.c_uint64, vp, vp, vp, vp, vp, vp, vp, C.POINTER(sz)]
     L.pcr_points_in_boxes_f64.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp, sz, vp, C.POINTER(C.c_uint64)]
     L.pcr_label_aabb_f32.argtypes = [vp, vp, vp, sz, vp, vp]
+    L.pcr_box_overlap_f64.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, sz, vp, vp, sz]
+    L.pcr_kitti_clean_data_f64.argtypes = [C.c_int, C.c_int, vp, sz, vp, sz, vp, vp, C.POINTER(C.c_uint64)]
+    L.pcr_kitti_frame_stats_f64.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, sz, vp, vp, vp, vp, sz, vp, vp, vp, vp, vp]
+    L.pcr_kitti_thresholds_f64.argtypes = [vp, vp, sz, C.c_uint64, vp, C.POINTER(C.c_int32)]
+    L.pcr_kitti_eval_f64.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, sz, vp]
     ip = C.POINTER(C.c_int)
     L.pcr_pn2_model_create.argtypes = [vp, C.POINTER(Pn2Desc), vp, sz, C.POINTER(vp)]
     L.pcr_pn2_model_destroy.argtypes = [vp, vp]
@@ -1712,6 +1728,79 @@ class Context:
         cnt = np.zeros(max(k, 1), np.uint32)
         self._ck(lib().pcr_label_aabb_f32(self.h, cloud.h, lb.ctypes.data if lb.size else None, k, aabb.ctypes.data, cnt.ctypes.data))
         return aabb[:k], cnt[:k]
+
+    # ---- Homework6: the KITTI object evaluator (csrc/kitti_eval.hip; hw6.py mirrors evaluate_object.cpp on top of these)
+    @staticmethod
+    def _kitti_rows(rows, row_ptr):
+        r = np.ascontiguousarray(rows, np.float64).reshape(-1, 15)
+        p = np.ascontiguousarray(row_ptr, np.uint64).reshape(-1)
+        if p.size < 1 or int(p[-1]) > r.shape[0]:
+            raise PcrError("row_ptr: n_frames + 1 entries that end inside the rows")
+        return r, p
+
+    def _kitti_frames(self, gt_rows, gt_ptr, det_rows, det_ptr):
+        g, gp = self._kitti_rows(gt_rows, gt_ptr)
+        d, dp = self._kitti_rows(det_rows, det_ptr)
+        if gp.size != dp.size:
+            raise PcrError("the two row_ptr arrays describe the same frames")
+        return (g.ctypes.data if g.size else None, gp.ctypes.data, d.ctypes.data if d.size else None, dp.ctypes.data, gp.size - 1), (g, gp, d, dp)
+
+    def box_overlap(self, metric: int, criterion: int, gt_rows, gt_ptr, det_rows, det_ptr):
+        """Every frame's |gt| x |det| overlap matrix -> (mat_ptr u64 [n_frames + 1], flat f64 matrices, row-major); pcr_box_overlap_f64."""
+        args, keep = self._kitti_frames(gt_rows, gt_ptr, det_rows, det_ptr)
+        mat_ptr = np.zeros(args[4] + 1, np.uint64)
+        rc = lib().pcr_box_overlap_f64(self.h, int(metric), int(criterion), *args, mat_ptr.ctypes.data, None, 0)
+        total = int(mat_ptr[-1])
+        if rc != 0 and not (rc == -1 and total > 0):
+            self._ck(rc)
+        out = np.zeros(max(total, 1), np.float64)
+        if total:
+            self._ck(lib().pcr_box_overlap_f64(self.h, int(metric), int(criterion), *args, mat_ptr.ctypes.data, out.ctypes.data, total))
+        return mat_ptr, out[:total]
+
+    def kitti_frame_stats(self, cls: int, metric: int, difficulty: int, compute_fp: bool, compute_aos: bool, thresholds, gt_rows, gt_ptr, det_rows, det_ptr):
+        """computeStatistics for every frame -> dict(tp, fp, fn [n_frames, n_thresholds] i32, similarity f64) with compute_fp, else
+        dict(tp, fp, fn [n_frames], scores: one f64 array per frame); pcr_kitti_frame_stats_f64."""
+        args, keep = self._kitti_frames(gt_rows, gt_ptr, det_rows, det_ptr)
+        nf = args[4]
+        thr = np.ascontiguousarray(thresholds if thresholds is not None else [], np.float64).reshape(-1)
+        width = thr.size if compute_fp else 1
+        tp, fp, fn = (np.zeros((nf, width), np.int32) for _ in range(3))
+        sim = np.zeros((nf, width), np.float64)
+        scores = np.full(max(int(keep[1][-1]), 1), np.nan)
+        self._ck(lib().pcr_kitti_frame_stats_f64(self.h, int(cls), int(metric), int(difficulty), int(bool(compute_fp)), int(bool(compute_aos)),
+                                                 thr.ctypes.data if thr.size else None, thr.size, *args, tp.ctypes.data, fp.ctypes.data, fn.ctypes.data,
+                                                 sim.ctypes.data, scores.ctypes.data))
+        if compute_fp:
+            return {"tp": tp, "fp": fp, "fn": fn, "similarity": sim}
+        gp = keep[1]
+        return {"tp": tp[:, 0], "fp": fp[:, 0], "fn": fn[:, 0], "scores": [scores[int(gp[f]):int(gp[f]) + int(tp[f, 0])].copy() for f in range(nf)]}
+
+    def kitti_thresholds(self, scores, n_gt: int):
+        """getThresholds -> f64 [count <= 41]; pcr_kitti_thresholds_f64."""
+        v = np.ascontiguousarray(scores, np.float64).reshape(-1)
+        out = np.zeros(41, np.float64)
+        cnt = C.c_int32()
+        self._ck(lib().pcr_kitti_thresholds_f64(self.h, v.ctypes.data if v.size else None, v.size, int(n_gt), out.ctypes.data, C.byref(cnt)))
+        return out[: cnt.value].copy()
+
+    def kitti_eval(self, cls: int, compute_aos: bool, gt_rows, gt_ptr, det_rows, det_ptr):
+        """eval_class for 3 metrics x 3 difficulties in one call -> [metric][difficulty] dicts (n_gt, thresholds, tp, fp, fn, similarity,
+        precision [41], aos [41] or None); pcr_kitti_eval_f64."""
+        args, keep = self._kitti_frames(gt_rows, gt_ptr, det_rows, det_ptr)
+        out = (KittiCurve * 9)()
+        self._ck(lib().pcr_kitti_eval_f64(self.h, int(cls), int(bool(compute_aos)), *args, out))
+        res = []
+        for m in range(3):
+            row = []
+            for d in range(3):
+                c = out[3 * m + d]
+                n = int(c.n_thresholds)
+                row.append({"n_gt": int(c.n_gt), "thresholds": np.array(c.thresholds[:n], np.float64), "tp": np.array(c.tp[:n], np.int64),
+                            "fp": np.array(c.fp[:n], np.int64), "fn": np.array(c.fn[:n], np.int64), "similarity": np.array(c.similarity[:n], np.float64),
+                            "precision": np.array(c.precision[:], np.float64), "aos": np.array(c.aos[:], np.float64) if c.has_aos else None})
+            res.append(row)
+        return res
 
     def pn2_msg_model(self, desc, weights) -> Pn2Model:
         """desc: a Pn2MsgDesc (pn2_msg_desc(...)); weights: the flat f32 array, layer by layer, branch by branch, convolution by convolution,

@@ -660,6 +660,83 @@ int pcr_points_in_boxes_f64(pcr_ctx* ctx, const pcr_cloud* cloud, const uint32_t
                             const uint32_t* box_seg_ptr, uint64_t* row_ptr, uint32_t* idx, size_t idx_cap, uint32_t* hits, uint64_t* total);
 int pcr_label_aabb_f32(pcr_ctx* ctx, const pcr_cloud* cloud, const int32_t* labels, size_t n_clusters, float* aabb, uint32_t* counts);
 
+/* ---- Homework6: the KITTI object evaluator, Homework6/devkit_object/cpp/evaluate_object.cpp — box overlaps, computeStatistics, AP curves ----
+ * All arithmetic is f64, every operation rounded, unfused.  Boxes travel as flat rows of 15 doubles with per-frame row_ptr arrays of
+ * n_frames + 1 uint64 entries (row_ptr[0] == 0, ascending; at most 2^22 rows of a kind in one call).
+ *   ground-truth row: class code, truncation, occlusion, alpha, x1, y1, x2, y2, h, w, l, t1, t2, t3, ry       (loadGroundtruth's fscanf order)
+ *   detection row:    class code, alpha, x1, y1, x2, y2, h, w, l, t1, t2, t3, ry, score, one pad              (loadDetections' order)
+ *   class codes: 0 Car, 1 Pedestrian, 2 Cyclist, 3 Van, 4 Person_sitting, 5 DontCare, 6 anything else (names are matched in Python, hw6.py).
+ * metric: PCR_KITTI_IMAGE / GROUND / BOX3D.  criterion: -1 union, 0 over the detection, 1 over the ground truth.  difficulty 0 / 1 / 2.
+ *
+ * The overlap of (detection d, ground truth g):
+ *   IMAGE   imageBoxOverlap(d, g, criterion) with the reference's operations in its order (:230-264).
+ *   GROUND  Both quads are formed as toPolygon forms them (:272-294): with c = cos(ry), s = sin(ry), corner i = (c X_i + s Z_i + t1,
+ *           -s X_i + c Z_i + t3) for (X, Z) = (l/2, w/2), (l/2, -w/2), (-l/2, -w/2), (-l/2, w/2).  c and s are computed ON THE HOST (std::cos,
+ *           std::sin, in csrc/kitti_eval.hip's prepare step) — nowhere else, so the device does plain arithmetic and a matrix does not depend on
+ *           launch geometry.  The INTERSECTION follows a rule of our own (boost::geometry is not reproduced):
+ *             sgn = -1 if the ground-truth quad's fan sum sum_{k=1,2} cross(g_k - g_0, g_{k+1} - g_0) is negative, else +1;
+ *             the detection quad V (4 vertices, corner order) is clipped by ground-truth edge e = 0 ... 3 (g_e -> g_{e+1 mod 4}) in turn:
+ *               d_k = sgn * (ex * (V_k.z - g_e.z) - ez * (V_k.x - g_e.x)), (ex, ez) = g_{e+1} - g_e; a vertex is inside iff d_k >= 0;
+ *               for k = 0 ... n-1 with P = V_k, Q = V_{k+1 mod n}: P is kept if inside, then, if exactly one of P, Q is inside, the point
+ *               I + (O - I) * (d_I / (d_I - d_O)) follows, I the inside one of the two and O the other (a vertex ON the edge is thus
+ *               returned exactly, and boxes that only touch intersect in 0).  At most 8 vertices result (they are kept in registers).
+ *             area = | 0.5 * sum_{k=1}^{n-2} ( (V_k.x - V_0.x)(V_{k+1}.z - V_0.z) - (V_{k+1}.x - V_0.x)(V_k.z - V_0.z) ) |: the shoelace sum in
+ *             vertex order, taken about vertex 0 so that its rounding does not grow with the distance from the origin; 0 for n < 3.
+ *           overlap = inter / (area_d + area_g - inter), inter / area_d or inter / area_g with area = |l * w|.  DEPARTURE from the reference:
+ *           it divides by the area of boost's union_ polygon; the two agree up to rounding for proper boxes.
+ *   BOX3D   box3DOverlap as written (:320-347): ymax = min(d.t2, g.t2), ymin = max(d.t2 - d.h, g.t2 - g.h), inter_vol = inter *
+ *           max(0, ymax - ymin), volumes h * l * w (signed, as there), inter_vol / (det_vol + gt_vol - inter_vol) for the union.
+ *   A 0 / 0 (a zero-area detection under criterion 0) is NaN and matches nothing: every comparison is written as the reference writes it.
+ *
+ * pcr_box_overlap_f64 — one launch, one (ground truth, detection) pair per lane over all frames: frame f's matrix is out[mat_ptr[f] + i * nd_f
+ *   + j] for ground truth i and detection j of the frame.  mat_ptr (n_frames + 1, host) is always written; out_cap < mat_ptr[n_frames]:
+ *   PCR_ERR_ARG with mat_ptr valid (out == NULL, out_cap == 0 is the sizing call).  Profile name kitti_overlap.
+ * pcr_kitti_clean_data_f64 — cleanData's codes (:384-457) for one frame, host only (no context): ignored_gt / ignored_det in {0, 1, -1} and
+ *   the count of valid ground truth.  int32_t height = fabs(y1 - y2) truncates for detections, height <= MIN_HEIGHT in double for ground
+ *   truth; Van for Car and Person_sitting for Pedestrian are neighbour classes.  DontCare areas are the rows of class code 5.
+ * pcr_kitti_frame_stats_f64 — computeStatistics (:459-617) for every frame under one (class, metric, difficulty).  compute_fp != 0: for each
+ *   of n_thresholds <= 41 thresholds, tp / fp / fn / similarity [n_frames][n_thresholds]; similarity is the frame's sum of (1 + cos(delta)) / 2
+ *   in ground-truth order, -1 for a frame without tp and fp, 0 when compute_aos == 0.  compute_fp == 0 (the collecting mode): tp / fp / fn
+ *   [n_frames] and tp_scores (as many doubles as ground-truth rows): frame f's true-positive scores, in the reference's push order, are
+ *   tp_scores[gt_ptr[f] ... gt_ptr[f] + tp[f]); the rest is NaN.  One wave works one frame, lane t carries threshold t; assigned_detection is
+ *   a register bitmask up to 64 detections and spills to lane-interleaved words in device memory beyond: any number of detections in a frame.
+ *   Profile names kitti_collect / kitti_match.
+ * pcr_kitti_thresholds_f64 — getThresholds (:349-382) on the device: thresholds[count <= 41].  Which sorted positions the recall walk keeps
+ *   depends on (n, n_gt) alone; each kept position receives the score of that descending rank (ties: equal values, so the reference's picks).
+ *   A NaN score is PCR_ERR_ARG.  Profile name kitti_thresholds.
+ * pcr_kitti_eval_f64 — eval_class (:623-707) for all 3 metrics x 3 difficulties of one class in ONE call with ONE host wait: out[metric * 3 +
+ *   difficulty].  Overlaps (three launches), the collecting pass, the thresholds and the matching pass of all nine run back to back on the
+ *   stream.  tp / fp / fn are summed over frames with integer atomics; the similarity of every frame is rounded to the grid 2^-40 and summed
+ *   as an integer too (no floating-point atomic: the same bits for any frame order, chunking or launch geometry; the rounding is at most
+ *   2^-41 per frame, so aos moves by less than 4.6e-13).  precision[t] = tp / (tp + fp), aos[t] = similarity / (tp + fp) (IMAGE only, and
+ *   only if compute_aos), both replaced by their running maximum from the right over all 41 entries; entries beyond n_thresholds stay 0.
+ *   Tune key kitti_blocks [2048]: the cap on the workgroups of each launch (results never depend on it).
+ * Empty frames and empty inputs are valid everywhere.  PCR_ERR_ARG: a NULL that is needed, a class outside 0 ... 2, a metric, criterion or
+ *   difficulty out of range, a row_ptr that does not start at 0, descends or ends beyond 2^22, more than 41 thresholds. */
+#define PCR_KITTI_IMAGE 0
+#define PCR_KITTI_GROUND 1
+#define PCR_KITTI_BOX3D 2
+#define PCR_KITTI_SAMPLE_PTS 41
+typedef struct pcr_kitti_curve {
+    uint64_t n_gt;
+    int32_t n_thresholds;
+    int32_t has_aos;
+    double thresholds[PCR_KITTI_SAMPLE_PTS];
+    int64_t tp[PCR_KITTI_SAMPLE_PTS], fp[PCR_KITTI_SAMPLE_PTS], fn[PCR_KITTI_SAMPLE_PTS];
+    double similarity[PCR_KITTI_SAMPLE_PTS];
+    double precision[PCR_KITTI_SAMPLE_PTS], aos[PCR_KITTI_SAMPLE_PTS];
+} pcr_kitti_curve;
+int pcr_box_overlap_f64(pcr_ctx* ctx, int metric, int criterion, const double* gt_rows, const uint64_t* gt_ptr, const double* det_rows,
+                        const uint64_t* det_ptr, size_t n_frames, uint64_t* mat_ptr, double* out, size_t out_cap);
+int pcr_kitti_clean_data_f64(int cls, int difficulty, const double* gt_rows, size_t n_gt_rows, const double* det_rows, size_t n_det_rows,
+                             int32_t* ignored_gt, int32_t* ignored_det, uint64_t* n_gt);
+int pcr_kitti_frame_stats_f64(pcr_ctx* ctx, int cls, int metric, int difficulty, int compute_fp, int compute_aos, const double* thresholds,
+                              size_t n_thresholds, const double* gt_rows, const uint64_t* gt_ptr, const double* det_rows, const uint64_t* det_ptr,
+                              size_t n_frames, int32_t* tp, int32_t* fp, int32_t* fn, double* similarity, double* tp_scores);
+int pcr_kitti_thresholds_f64(pcr_ctx* ctx, const double* scores, size_t n, uint64_t n_gt, double* thresholds, int32_t* count);
+int pcr_kitti_eval_f64(pcr_ctx* ctx, int cls, int compute_aos, const double* gt_rows, const uint64_t* gt_ptr, const double* det_rows,
+                       const uint64_t* det_ptr, size_t n_frames, pcr_kitti_curve* out);
+
 /* ---- HomeworkFinal: the PointNet++ (SSG) classifier, HomeworkFinal/models/pointnet2_cls_ssg.py + pointnet_util.py:159-215, eval mode -----------
  * A model is a chain of up to 4 set-abstraction (SA) layers and up to 4 fully connected (FC) layers, described by pcr_pn2_desc:
  *   D0         feature channels of the input besides xyz (0: xyz only, 3: normal_channel)
